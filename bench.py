@@ -2,7 +2,7 @@
 """Throughput bench of the per-frame stylization path (BASELINE.json metric: stylized frames/sec at
 512x512, 1 style; 1/2/4/8 MI355X + CPU ref).
 
-    python bench.py --gpus N --steps K --warmup W [--size 256|512|1024] [--multistyle S]
+    python bench.py --gpus N --steps K --warmup W [--size 256|512|1024] [--multistyle S] [--dump-outputs DIR]
 
 `value` is HOST -> HOST, as SURVEY.md §8(d) defines the metric and as the reference's transfer() works
 (test/framework.py:109 `.to(device)` ... :40 `.cpu()`): a step = one `rrv_transfer_batch` call over `--batch`
@@ -21,6 +21,11 @@ N > 1: one process per GPU.  Started plainly (`python bench.py --gpus N`) the sc
 under torch.distributed.run it uses the ranks it is given.  Rank 0 runs prepare_style + add + compute and broadcasts
 the 70 KB state blob per style (RCCL); frames are sharded, no per-frame communication ("weak" scaling: every rank
 stylizes steps x batch frames).  Prints ONE JSON line (rank 0).
+
+--dump-outputs DIR: after the timed steps, the float32 frames the LAST timed step returned to its caller are written to
+DIR/frames.npy (rank r > 0: frames_rank<r>.npy) — all of them, or a fixed seeded sample when they exceed 64 MB over all
+ranks (whole frames, or single elements of the flattened array when one frame is over a rank's share; dump_sample).
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -38,6 +43,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4_f32, dense
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 60 * 1000 * 1000    # --dump-outputs: all ranks' arrays together stay under 64 MB (npy headers included)
 EPI_BITS = {"E_RELU": 1, "E_LRELU": 2, "E_NORM1": 4, "E_RES": 8, "E_RES_UPS": 16, "E_NORM2": 32, "E_POOL": 64}
 HBM_KERNELS = ("conv_first", "conv_last")      # the two thin ends of the path are HBM-bound, everything else MFMA-bound
 
@@ -274,6 +280,21 @@ def cpu_baseline(setup, unit, what, budget_s=25.0):
             "one_core_value": round(1.0 / med1, 4), "one_core_sample": "median of %d, 1 thread" % n1}
 
 
+def dump_sample(a, budget, seed=0):
+    """(sample, indices) of the array `a` within `budget` bytes: all of `a` (indices None), else whole entries along its
+    first axis (frames), else single elements of the flattened array — indices drawn with a fixed seed, sorted."""
+    a = np.asarray(a)
+    if a.nbytes <= budget:
+        return np.array(a), None
+    rng = np.random.default_rng(seed)
+    if a.ndim > 1 and a[0].nbytes <= budget:
+        idx = np.sort(rng.choice(a.shape[0], budget // a[0].nbytes, replace=False))
+        return a[idx], idx
+    flat = a.reshape(-1)
+    idx = np.sort(rng.choice(flat.size, max(1, budget // a.itemsize), replace=False))
+    return flat[idx], idx
+
+
 def sub_leg(extra_args, timeout_s=600):
     """One of the other BASELINE configurations as a short run of this script in a child process (after the timed headline
     region, same GPU): returns the few fields the headline line carries as extras, or {"error": ...}."""
@@ -308,7 +329,11 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=1)
     ap.add_argument("--pipeline", type=int, default=2, help="sub-batches in flight per GPU (1 or 2 HIP streams)")
     ap.add_argument("--pageable", action="store_true", help="time the host entry with pageable caller arrays instead of page-locked ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the frames the last timed step returned as DIR/frames.npy (float32, <= 64 MB: a seeded sample of whole frames)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -462,6 +487,16 @@ def main():
         t = mine.clone()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # what the last timed step returned to its caller, before the extras below reuse h_out
+    dumped = None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = h_out[(args.steps - 1) & 1]
+        sample, idx = dump_sample(last, DUMP_BYTES // world)
+        name = "frames" if rank == 0 else "frames_rank%d" % rank
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), sample)
+        dumped = {"dir": args.dump_outputs, name: {"returned_shape": list(last.shape), "dumped_shape": list(sample.shape),
+                                                   "sampled_frames": idx.tolist() if idx is not None and sample.ndim > 1 else None}}
     # the one collective of the path once more through the C ABI (rrv_broadcast_state: ncclBroadcast on an ncclComm_t
     # built from a unique id that travels over the process group), checked bit for bit against the state every rank holds
     c_abi_bcast = None
@@ -505,6 +540,8 @@ def main():
                           "parallelism": "frame-shard x%d" % world},
                "ms_per_frame": round(1e3 * dt / args.steps / B, 4), "roofline": roof, "cpu_baseline": cpu,
                "prep_seconds_rank0": round(prep_s, 3), "kernels": kern}
+        if dumped:
+            out["dump_outputs"] = dumped
         # diagnostics of a multi-rank run (the driver computes scaling efficiency itself from the per-N `value`s)
         rates = [args.steps * B / t for t in per_rank_s]
         out["per_rank"] = {"frames_per_s": [round(r, 1) for r in rates], "min": round(min(rates), 1), "max": round(max(rates), 1),

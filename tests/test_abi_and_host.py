@@ -95,6 +95,25 @@ def test_bench_kernel_name_mapping_and_traffic_lookup():
     assert b.measured_traffic("no_such_kernel<1>") is None
 
 
+def test_bench_dump_sample_is_seeded_and_bounded():
+    """bench.py --dump-outputs: an output within the budget is dumped whole; a larger one as whole frames, or as single
+    elements when one frame is over the budget — the same indices every run, and never more bytes than the budget."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    a = np.random.default_rng(3).random((10, 8, 8, 3), dtype=np.float32)
+    s, idx = b.dump_sample(a, a.nbytes)
+    assert idx is None and np.array_equal(s, a) and s.dtype == np.float32
+    s, idx = b.dump_sample(a, 3 * a[0].nbytes + 5)
+    assert s.shape == (3, 8, 8, 3) and list(idx) == sorted(set(idx)) and np.array_equal(s, a[idx])
+    s2, idx2 = b.dump_sample(a, 3 * a[0].nbytes + 5)
+    assert np.array_equal(idx, idx2) and np.array_equal(s, s2)
+    s, idx = b.dump_sample(a, 100)
+    assert s.shape == (25,) and s.nbytes <= 100 and np.array_equal(s, a.reshape(-1)[idx])
+    assert b.DUMP_BYTES + 16 * 128 <= 64 * 1000 * 1000
+
+
 def test_checkpoint_pth_branch_strict_load(tmp_path, pkg):
     """The reference loads its 107-key .pth with a strict load_state_dict (test/framework.py:74-75).  Write the seeded
     weights as a torch.save'd state_dict WITH the Vgg19.* keys the reference's checkpoint also carries, read it back

@@ -1,5 +1,5 @@
-import importlib, sys, time, numpy as np, torch
-sys.path.insert(0,'/root/repo')
+import importlib, os, sys, time, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("rerevst-code_amd"); V = importlib.import_module("rerevst-code_amd.video")
 S=512; P=V.padded_size(S)
 m = pkg.Stylization(pkg.synthetic_weights(0), cuda=True)

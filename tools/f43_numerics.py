@@ -1,6 +1,7 @@
 """Numerical emulation of F(4x4,3x3) (fp32) inside the oracle, to see how much parity margin the kernel would leave."""
-import sys, importlib, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/oracle'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, importlib, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import state_bounds as C
 import rerevst_oracle as O
 pkg = importlib.import_module("rerevst-code_amd")

@@ -1,6 +1,6 @@
 import importlib, sys, os, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("rerevst-code_amd")
 V = importlib.import_module("rerevst-code_amd.video")
 s = pkg.Stylization(pkg.synthetic_weights(0), cuda=True)
