@@ -247,6 +247,14 @@ int rrv_set_host_io(rrv_handle h, int mode);
  * copied to the host after a full synchronisation.  *floats receives its size (nothing is copied when cap is smaller). */
 int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float* host, size_t cap, size_t* floats);
 
+/* Layer-parity tap: as rrv_debug_copy_tensor, for image `image` of the plan, with indices 23..32 the channel-chunk-major
+ * twins q11 q1 q21 q2 q31 q32 q33 (encoder) and qa4 qa3 qa2 (ResidualBlock.conv1 outputs).  *layout = 0: ring-layout NHWC
+ * [H'+2][W'+2][C]; 1: "P8" [C/8][H'+2][W'+8][8], pixel x at stored column x + 4.  *channels = C.  RRV_E_STATE when the
+ * most recent launch on that workspace plan did not write the tensor for that image (stale data, the other layout, a
+ * replayed graph), so a caller never reads stale data. */
+int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
+                             int* layout, int* channels);
+
 /* Stream-ordered use of the *_device entries from a caller that produces / consumes the buffers on its own HIP
  * stream (e.g. torch.cuda.current_stream().cuda_stream): see ORDERING above.  enable = 0 switches it off. */
 int rrv_set_caller_stream(rrv_handle h, void* hip_stream, int enable);

@@ -44,6 +44,8 @@ struct Tens {
     float* p = nullptr;
     float* base = nullptr;            // debug mode: start of the allocation (guard band in front of p)
     int B = 0, H = 0, W = 0, C = 0;
+    mutable unsigned gen = 0;         // launch (rrv_ctx::launch_gen) whose kernels last wrote this tensor, and for how many images
+    mutable int gen_B = 0;            // (rrv_debug_copy_tensor_ex refuses a tensor its plan's last launch did not write)
     size_t img_floats() const { return (size_t)(H + 2) * (W + 2) * C; }
 };
 
@@ -69,7 +71,8 @@ const int STYLE_SLICE[9] = {1, 2, 2, 3, 3, 4, 4, 4, 4};
 
 struct EncPlan {   // encoder activations for one (B, H, W)
     int B = 0, H = 0, W = 0;
-    unsigned stamp = 0;     // last use (two geometries per slot, least recently used one is replaced)
+    unsigned stamp = 0;
+    unsigned gen = 0;       // last launch that used this plan (rrv_ctx::launch_gen)     // last use (two geometries per slot, least recently used one is replaced)
     Tens c11, p1, c21, p2, c31, c32, c33, p3, c41;
     // channel-chunk-major ("P8": [B][C/8][H+2][W+8][8], conv_f43.h LAY) twins of the tensors BETWEEN two conv_f43_k launches — and of c11, which
     // conv_first_k can write either way — allocated on first use as ring-layout tensors of B * C/8 eight-channel images of width W + 6 (so the
@@ -79,6 +82,7 @@ struct EncPlan {   // encoder activations for one (B, H, W)
 struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRAME batch
     int B = 0, H = 0, W = 0;
     unsigned stamp = 0;
+    unsigned gen = 0;
     Tens d, f1, f2, f3, xs4, a4, o4, xs3, a3, o3, xs2, a2, o2;
     Tens qa4, qa3, qa2;     // channel-chunk-major twins of a4 / a3 / a2 (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above), allocated on first use
     Tens dpart;             // [.., 32 * split]: partial sums of the split-K 512->32 KernelFilter convolution (allocated on first use)
@@ -148,6 +152,7 @@ struct rrv_ctx {
     EncPlan enc_frame[RRV_MAX_SLOTS][2], enc_add, enc_style;
     DecPlan dec[RRV_MAX_SLOTS][2];
     unsigned plan_clock = 0;
+    unsigned launch_gen = 0;                   // counts the launches of the per-frame chain (Tens::gen; a replayed graph stamps nothing)
     // cached raw relu4_1 feature of one (padded) frame, H x W = frame size.  Beyond feat_cap (rrv_set_feature_cache_cap)
     // a frame is kept as its uint8 pixels instead (u8, ~10x smaller) and re-encoded when it is used: the reference's
     // cache is on disk and unbounded (test.py:87-101), this one degrades to "encode + decode per frame" instead of failing
@@ -366,6 +371,8 @@ int talloc(rrv_handle h, Tens* t, int B, int H, int W, int C) {
     g_dbg[t->p] = DbgRec{h, t->base, B, H, W, C, floats};
     return RRV_OK;
 }
+
+void stamp(rrv_handle h, const Tens* t, int B) { t->gen = h->launch_gen; t->gen_B = B; }
 
 template <typename F>
 int launch(rrv_handle h, const char* name, double flops, double bytes, F&& f, double flops_exec = -1.0) {
@@ -625,6 +632,8 @@ int conv(rrv_handle h, const ConvCall& c) {
         if (!k->fn_img) return fail(h, RRV_E_ARG, "conv: this layer has no per-image-state kernel");
         fn = k->fn_img;
     }
+    stamp(h, c.out, c.B);
+    if (fuse_sc) stamp(h, c.sc_out, c.B);
     if (h->profiling) {   // "<kernel>@CinxCout@HxW": bench.py groups by the part before '@'
         char nm[160];
         snprintf(nm, sizeof nm, "%s@%dx%d@%dx%d", lay_name ? lay_name : k->name, w.Cin, w.Cout, c.H, c.W);
@@ -744,6 +753,7 @@ int pointwise(rrv_handle h, const Tens& x, Tens& y, const float* mean, const flo
     if (rows * segs > 16384) rows = 16384 / segs;
     p.segs = segs;
     const int blocks = rows * segs;
+    stamp(h, &y, x.B);
     return launch(h, "pointwise", 0, 0, [&] { hipLaunchKernelGGL(pointwise_k, dim3(blocks), dim3(256), 0, h->stream, p); });
 }
 
@@ -872,6 +882,11 @@ Plan& pick_plan(rrv_handle h, Plan (&v)[2], int B, int H, int W) {
 // unpadded source frame behind a padded geometry (ReshapeTool on the device): pad on the way in, crop on the way out
 struct PadCrop { int src_H, src_W, top, left; };
 
+// A channel-chunk-major image of C channels spans (H+2)*(W+8)*C floats (rows pitched W + 8: conv_f43.h P8_PAD), more than the
+// (H+2)*(W+2)*64 of the frame-size guards; conv_f43_k's P8 store offsets are 32-bit within an image.  A tensor is P8 only when
+// its image stays below 2^31 floats; otherwise the launch keeps NHWC (the same values, which run beyond the 2 GiB mark).
+bool p8_fits(int H, int W, int C) { return (double)(H + 2) * (W + 8) * C < 2147483648.0; }
+
 // nb: images to encode (plans are grow-only, so a plan may hold room for more)
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
 int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr) {
@@ -889,7 +904,7 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     // of use_f43 says yes for every launch with enough work items: the batched entries); any other mix keeps NHWC throughout.  Where every
     // level is a multiple of 32 pixels wide the choice changes no bit of the result (conv_f43_k stages the same bytes from either layout);
     // elsewhere the edge tiles see other discarded columns (conv_f43.h P8_PAD): rounding noise, GPU test.
-    bool p8 = which == 0 && h->f43_path && (h->p8 & 1);
+    bool p8 = which == 0 && h->f43_path && (h->p8 & 1) && p8_fits(H, W, 64) && p8_fits(H / 2, W / 2, 128) && p8_fits(H / 4, W / 4, 256);
     struct TablesScope { rrv_handle h; ~TablesScope() { h->enc_p8_tables = false; } } tables_scope{h};
     {
         const int lh[8] = {0, H, H / 2, H / 2, H / 4, H / 4, H / 4, H / 4}, lw[8] = {0, W, W / 2, W / 2, W / 4, W / 4, W / 4, W / 4};
@@ -915,6 +930,7 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     }
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0};
+    stamp(h, p8 ? &e.q11 : &e.c11, B);
     RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, (3.0 + 256.0) * B * H * W, [&] {
         hipLaunchKernelGGL(conv_first_k, dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
     }));
@@ -1018,6 +1034,7 @@ int filter_down(rrv_handle h, const Tens* cur, DecPlan& d, int f, int B) {
     if (h->state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
     RCHK(conv(h, c));
     const long npix = (long)B * (d.d.H + 2) * (d.d.W + 2);
+    stamp(h, &d.d, B);
     return launch(h, "sum_parts", 0, 4.0 * 32 * (split + 1) * npix, [&] {
         const long nb = (npix * 8 + 255) / 256;
         hipLaunchKernelGGL(sum_parts_lrelu_k, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, h->stream, (const float*)t.p, d.d.p, split, npix);
@@ -1034,7 +1051,7 @@ int resblock_frame(rrv_handle h, int B, const char* blk, const Tens& in, Tens& x
     // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin
     Tens* a_in = &a;
     bool p8 = false;
-    if (qa && (h->p8 & 2)) {
+    if (qa && (h->p8 & 2) && p8_fits(a.H, a.W, a.C)) {
         const ConvW& w2 = h->conv[p + ".conv2"];
         p8 = use_f43(h, w2, B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) && !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
         if (p8 && (!qa->p || qa->B < a.B * (a.C / 8))) RCHK(talloc(h, qa, a.B * (a.C / 8), a.H, a.W + 6, 8));
@@ -1095,6 +1112,7 @@ int transfer_device(rrv_handle h, const uint8_t* d_in, int B, int H, int W, floa
     DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
     RCHK(enc_plan(h, e, B, H, W));
     RCHK(dec_plan(h, d, B, Ho, Wo));
+    e.gen = d.gen = ++h->launch_gen;
     const float* st = h->cur->active;
     auto body = [&]() -> int {
     if (feats) {  // one cached feature and one state set per image
@@ -1105,6 +1123,7 @@ int transfer_device(rrv_handle h, const uint8_t* d_in, int B, int H, int W, floa
             const float* n0 = st + (size_t)b * RRV_STATE_FLOATS + SL.norm[N_DEC0];
             RCHK(pointwise(h, src, dst, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
         }
+        stamp(h, &e.c41, B);
     } else if (feat) {   // cached raw relu4_1 feature: Decoder.norm[0] (saved stats + clamp) as a pointwise step
         Tens src; src.p = const_cast<float*>(feat); src.B = 1; src.H = H / 8; src.W = W / 8; src.C = 512;
         const float* n0 = st + SL.norm[N_DEC0];
@@ -1338,6 +1357,7 @@ int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* 
     DecPlan& d = pick_plan(h, h->dec[0], 1, Ho, Wo);
     RCHK(enc_plan(h, e, 1, H, W));
     RCHK(dec_plan(h, d, 1, Ho, Wo));
+    e.gen = d.gen = ++h->launch_gen;
     constexpr int RS_PARTS = 1;      // (splitting the pixels over several blocks per channel quad measured slower: the merge in pred_mean_k costs more)
     if (!h->frame_S) { RCHK(dalloc(h, &h->frame_S, RS_PARTS * 9 * 512)); RCHK(dalloc(h, &h->frame_cmean, 64)); }
     RCHK(run_encoder(h, e, d_img, 0, nullptr, nullptr, 1));
@@ -2621,6 +2641,7 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         EncPlan& e = pick_plan(h, h->enc_frame[slot], nb, H, W);
         rc = enc_plan(h, e, nb, H, W);
         if (rc != RRV_OK) break;
+        e.gen = ++h->launch_gen;
         Tens out41 = one; out41.B = nb; out41.p = arena + (size_t)k * sub * img;
         rc = run_encoder(h, e, st.d_in, 0, nullptr, nullptr, nb, &out41);
         if (rc != RRV_OK) break;
@@ -2928,6 +2949,42 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
     if (!t || !t->p) return fail(h, RRV_E_STATE, "debug_copy_tensor: no such tensor in this slot");
     *floats = t->img_floats();
     if (host && cap >= *floats) HIPCHK(hipMemcpy(host, t->p, *floats * sizeof(float), hipMemcpyDeviceToHost));
+    return RRV_OK;
+}
+
+// Layer-parity tap: tensor `index` (0..22 as above, 23..32 the channel-chunk-major twins q11 q1 q21 q2 q31 q32 q33 qa4 qa3
+// qa2) of image `image`, as stored.  *layout = 0: ring-layout NHWC [H+2][W+2][C]; 1: P8 [C/8][H+2][W+8][8] (conv_f43.h LAY).
+// Refused (RRV_E_STATE) unless the most recent launch on that plan wrote the tensor for that image; a replayed graph
+// (rrv_ctx::GraphEntry) stamps nothing, so after one every tensor of its plans is refused.
+int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
+                             int* layout, int* channels) {
+    if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 32 || image < 0 || !floats) return RRV_E_ARG;
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(sync_all(h));
+    static const int TWIN_C[10] = {64, 64, 128, 128, 256, 256, 256, 256, 128, 64};
+    const bool enc = index < 9 || (index >= 23 && index < 30);
+    const Tens* t = nullptr;
+    unsigned pgen = 0;
+    for (int k = 0; k < 2; ++k) {
+        EncPlan& e = h->enc_frame[slot][k]; DecPlan& d = h->dec[slot][k];
+        const Tens* all[33] = {&e.c11, &e.p1, &e.c21, &e.p2, &e.c31, &e.c32, &e.c33, &e.p3, &e.c41,
+                               &d.d, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2, &d.dpart,
+                               &e.q11, &e.q1, &e.q21, &e.q2, &e.q31, &e.q32, &e.q33, &d.qa4, &d.qa3, &d.qa2};
+        const bool match = enc ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0);
+        const unsigned g = enc ? e.gen : d.gen;
+        if (match && (!t || g > pgen)) { t = all[index]; pgen = g; }
+    }
+    if (!t || !t->p) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: no such tensor in this slot");
+    if (t->gen != pgen || pgen == 0) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: the plan's last launch did not write this tensor");
+    if (image >= t->gen_B) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: the plan's last launch did not write this image");
+    const bool p8 = index >= 23;
+    const int C = p8 ? TWIN_C[index - 23] : t->C;
+    const size_t n = p8 ? (size_t)(C / 8) * t->img_floats() : t->img_floats();
+    if ((size_t)(image + 1) * n > (p8 ? (size_t)t->B / (C / 8) : (size_t)t->B) * n) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: image beyond the tensor");
+    *floats = n;
+    if (layout) *layout = p8 ? 1 : 0;
+    if (channels) *channels = C;
+    if (host && cap >= n) HIPCHK(hipMemcpy(host, t->p + (size_t)image * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return RRV_OK;
 }
 

@@ -332,6 +332,16 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_tensor(self._h, int(slot), int(index), int(H), int(W), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return out
 
+    def debug_tensor_ex(self, slot, index, H, W, image=0):
+        """Tensor `index` (0..32: 23..32 the channel-chunk-major twins) of image `image` of the last launch on workspace slot
+        `slot` for H x W frames (rrv_debug_copy_tensor_ex): (flat float32 as stored, layout 0 NHWC ring / 1 P8, channels)."""
+        n, lay, ch = C.c_size_t(0), C.c_int(0), C.c_int(0)
+        args = (self._h, int(slot), int(index), int(image), int(H), int(W))
+        self._chk(self._lib.rrv_debug_copy_tensor_ex(*args, None, 0, C.byref(n), C.byref(lay), C.byref(ch)))
+        out = np.empty(n.value, np.float32)
+        self._chk(self._lib.rrv_debug_copy_tensor_ex(*args, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(lay), C.byref(ch)))
+        return out, lay.value, ch.value
+
     def set_host_io(self, mode):
         """0 (default): staged H2D / D2H copies; 1: zero copy — kernels read / write page-locked host memory directly."""
         self._chk(self._lib.rrv_set_host_io(self._h, int(mode)))
