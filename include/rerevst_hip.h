@@ -250,8 +250,8 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
 /* Layer-parity tap: as rrv_debug_copy_tensor, for image `image` of the plan, with indices 23..32 the channel-chunk-major
  * twins q11 q1 q21 q2 q31 q32 q33 (encoder) and qa4 qa3 qa2 (ResidualBlock.conv1 outputs).  *layout = 0: ring-layout NHWC
  * [H'+2][W'+2][C]; 1: "P8" [C/8][H'+2][W'+8][8], pixel x at stored column x + 4.  *channels = C.  RRV_E_STATE when the
- * most recent launch on that workspace plan did not write the tensor for that image (stale data, the other layout, a
- * replayed graph), so a caller never reads stale data. */
+ * most recent launch on that workspace plan did not write the tensor for that image (stale data, the other layout), so
+ * a caller never reads stale data. */
 int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
                              int* layout, int* channels);
 

@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <cmath>
 #include <thread>
 #include <stdio.h>
@@ -119,8 +120,7 @@ struct rrv_ctx {
     int dev = 0;
     hipStream_t stream = nullptr;              // stream the launch helpers use (= streams[slot in use])
     hipStream_t streams[RRV_MAX_SLOTS] = {nullptr};
-    int n_slots = 2, next_slot = 0, last_slot = 0;   // transfer calls alternate over n_slots (stream, workspace) pairs
-    int slot_override = -1;                          // look-ahead tickets: THIS (stream, workspace) pair, whatever rrv_set_pipeline says
+    int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots (stream, workspace) pairs
     hipEvent_t slot_ev[RRV_MAX_SLOTS] = {nullptr};   // ordering against the caller's stream (rrv_set_caller_stream)
     hipStream_t caller_stream = nullptr; bool caller_sync = false;
     int user_style = -1;                             // style the plain transfer entries use (first computed / last set_state)
@@ -152,7 +152,7 @@ struct rrv_ctx {
     EncPlan enc_frame[RRV_MAX_SLOTS][2], enc_add, enc_style;
     DecPlan dec[RRV_MAX_SLOTS][2];
     unsigned plan_clock = 0;
-    unsigned launch_gen = 0;                   // counts the launches of the per-frame chain (Tens::gen; a replayed graph stamps nothing)
+    unsigned launch_gen = 0;                   // counts the launches of the per-frame chain (Tens::gen)
     // cached raw relu4_1 feature of one (padded) frame, H x W = frame size.  Beyond feat_cap (rrv_set_feature_cache_cap)
     // a frame is kept as its uint8 pixels instead (u8, ~10x smaller) and re-encoded when it is used: the reference's
     // cache is on disk and unbounded (test.py:87-101), this one degrades to "encode + decode per frame" instead of failing
@@ -179,8 +179,9 @@ struct rrv_ctx {
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
     // Four sets and two dedicated copy streams: the compute streams never wait behind a DMA of their own stream.
-    struct HostStage { uint8_t* pin_in = nullptr; float* pin_out = nullptr; uint8_t* d_in = nullptr; float* d_out = nullptr;
-                       size_t cap = 0, pcap = 0; hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr; } hstage[4];
+    // Each set holds a device pair and a page-locked host pair (stage_reserve), in bytes of frames / floats of output.
+    struct StageBufs { uint8_t* in = nullptr; float* out = nullptr; size_t in_cap = 0, out_cap = 0; };
+    struct HostStage { StageBufs dev, pin; hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr; } hstage[4];
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     // rrv_transfer_async: ticket t lives in staging set t % 4 until rrv_transfer_wait(t) (or a later submission that needs
     // its set) retires it; `out` / `out_bytes` = where a pageable caller buffer still has to be filled from pin_out
@@ -196,23 +197,6 @@ struct rrv_ctx {
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
     int host_io = 0;                  // rrv_set_host_io: 0 = staged H2D / D2H copies, 1 = zero copy (kernels read / write page-locked host memory), 2 = input only, 3 = output only
-    // One-frame launches as hipGraphs (round 5): the 35 launches of a plain B = 1 transfer are captured once per (slot, geometry,
-    // buffers, kernel choice) and replayed — same kernels, same arguments, same bits; the dispatch gaps between the kernels
-    // of a frame shrink.  Measured: no gain (513 / 918 frames/s at 512 x 512 / 256 x 256 with, 513 / 925 without: the GPU never waits
-    // for a launch call), so it is OFF by default; RRV_GRAPH=1 switches it on (GPU suite green with it).  An entry is first SEEN (a normal run, which also allocates what is
-    // allocated lazily), captured on the second call with the same key and replayed from the third.
-    struct GraphKey {
-        int H = 0, W = 0; const void* d_in = nullptr; const void* d_out = nullptr; int f43_mode = 0; unsigned f43_layers = 0; int grid_share = 0;
-        const void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr, *p3 = nullptr;      // workspace identity: encoder c11, decoder o2, split-K parts, pre-clamp tap
-        bool illcond = false; unsigned direct_layers = 0;      // everything else the captured kernel choice depends on (use_f43's conditioning guard, the direct-form layers)
-        bool operator==(const GraphKey& o) const {
-            return H == o.H && W == o.W && d_in == o.d_in && d_out == o.d_out && f43_mode == o.f43_mode && f43_layers == o.f43_layers &&
-                   grid_share == o.grid_share && p0 == o.p0 && p1 == o.p1 && p2 == o.p2 && p3 == o.p3 && illcond == o.illcond && direct_layers == o.direct_layers;
-        }
-    };
-    struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; unsigned stamp = 0; bool used = false; };
-    GraphEntry graphs[RRV_MAX_SLOTS][4];
-    bool use_graph = false;      // measured +-0 (profiles/r05_one_frame.txt): off unless RRV_GRAPH=1
     int n_cus = 256;
     int debug = 0;                    // rrv_set_debug / RRV_DEBUG: 1 = sync + check after every API call, 2 = after every kernel launch
     int fail_alloc_in = 0;            // rrv_debug_fail_alloc: the n-th next device allocation reports out-of-memory
@@ -237,10 +221,15 @@ namespace {
 int fail(rrv_handle h, int code, const std::string& msg) { h->err = msg; return code; }
 int dmalloc(rrv_handle h, void** p, size_t bytes);
 
-// Captured one-frame launch sequences (RRV_GRAPH=1) point into the plans' tensors: whatever frees or rebuilds a plan drops them
-void free_graphs(rrv_handle h) {
-    for (auto& row : h->graphs)
-        for (auto& g : row) { if (g.exec) (void)hipGraphExecDestroy(g.exec); g = rrv_ctx::GraphEntry{}; }
+// Element indices inside one image are 32-bit in the kernels' epilogues: (H+2)(W+2) x 64 channels must stay below 2^31.
+// The encoder (also run on style images) checks only that; check_frame adds the entries' minimum of 8 x 8 pixels.
+int check_image_size(rrv_handle h, double H, double W, const char* who) {
+    if ((H + 2) * (W + 2) * 64.0 < 2147483648.0) return RRV_OK;
+    return fail(h, RRV_E_ARG, std::string(who) + ": frame too large ((H+2)*(W+2)*64 must be < 2^31)");
+}
+int check_frame(rrv_handle h, int H, int W, const char* who) {
+    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, std::string(who) + ": frames must be at least 8 x 8 pixels");
+    return check_image_size(h, H, W, who);
 }
 
 int sync_all(rrv_handle h) {
@@ -843,8 +832,7 @@ void enc_free(EncPlan& e) {
 // half-built plan that passes the cache test and launch kernels on null tensors).
 int enc_plan(rrv_handle h, EncPlan& e, int B, int H, int W) {      // grow-only in B: a plan made for more images serves fewer
     if (e.B >= B && e.H == H && e.W == W && e.c41.p) return RRV_OK;
-    if ((double)(H + 2) * (W + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "image too large ((H+2)*(W+2)*64 must be < 2^31)");
-    free_graphs(h);
+    RCHK(check_image_size(h, H, W, "encoder"));
     enc_free(e);
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, H8 = H4 / 2, W8 = W4 / 2;
     auto build = [&]() -> int {
@@ -892,7 +880,7 @@ bool p8_fits(int H, int W, int C) { return (double)(H + 2) * (W + 8) * C < 21474
 int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr) {
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
-    if ((double)(H + 2) * (W + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "image too large ((H+2)*(W+2)*64 must be < 2^31)");
+    RCHK(check_image_size(h, H, W, "encoder"));
     auto W_ = [&](int i) -> const ConvW* {
         char k[64];
         if (which == 0) snprintf(k, sizeof k, "Encoder.slice.%d", VGG_IDX[i]);
@@ -960,20 +948,44 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     return RRV_OK;
 }
 
-int ensure_u8(rrv_handle h, size_t bytes) {
-    if (h->d_u8_cap >= bytes) return RRV_OK;
-    if (h->d_u8) (void)hipFree(h->d_u8);
-    RCHK(dmalloc(h, (void**)&h->d_u8, bytes));
-    h->d_u8_cap = bytes;
+// grow-only device buffer of at least n elements (h->d_u8, h->d_outf); empty after a failed allocation
+template <class T>
+int ensure_dev(rrv_handle h, T*& p, size_t& cap, size_t n) {
+    if (cap >= n) return RRV_OK;
+    if (p) (void)hipFree(p);
+    cap = 0;
+    RCHK(dmalloc(h, (void**)&p, n * sizeof(T)));
+    cap = n;
     return RRV_OK;
 }
 
-int ensure_outf(rrv_handle h, size_t floats) {
-    if (h->d_outf_cap >= floats) return RRV_OK;
-    if (h->d_outf) (void)hipFree(h->d_outf);
-    h->d_outf = nullptr; h->d_outf_cap = 0;
-    RCHK(dmalloc(h, (void**)&h->d_outf, floats * sizeof(float)));
-    h->d_outf_cap = floats;
+// Staging buffers of the host entries (rrv_ctx::hstage): one pair on the device, one page-locked on the host.
+void stage_free(rrv_ctx::StageBufs& b, bool pinned) {
+    for (void* p : {(void*)b.in, (void*)b.out})
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    b = rrv_ctx::StageBufs{};
+}
+// Set `set` grows (never shrinks) to at least in_bytes of frames and out_floats of output; 0 = that buffer is not used.
+// The caller makes sure nothing in flight uses the set.  The capacities are recorded only once both buffers exist: a
+// failed allocation leaves the pair empty.
+int stage_reserve(rrv_handle h, int set, size_t in_bytes, size_t out_floats, bool pinned) {
+    rrv_ctx::StageBufs& b = pinned ? h->hstage[set].pin : h->hstage[set].dev;
+    if (b.in_cap >= in_bytes && b.out_cap >= out_floats) return RRV_OK;
+    in_bytes = std::max(in_bytes, b.in_cap);
+    out_floats = std::max(out_floats, b.out_cap);
+    stage_free(b, pinned);
+    auto get = [&](void** p, size_t bytes) -> int {      // device memory through dmalloc (rrv_debug_fail_alloc counts it)
+        if (!bytes) return RRV_OK;
+        if (!pinned) return dmalloc(h, p, bytes);
+        if (hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess) return RRV_OK;
+        *p = nullptr;
+        (void)hipGetLastError();
+        return fail(h, RRV_E_NOMEM, "staging: out of page-locked host memory");
+    };
+    int rc = get((void**)&b.in, in_bytes);
+    if (rc == RRV_OK) rc = get((void**)&b.out, out_floats * sizeof(float));
+    if (rc != RRV_OK) { stage_free(b, pinned); return rc; }
+    b.in_cap = in_bytes; b.out_cap = out_floats;
     return RRV_OK;
 }
 
@@ -985,7 +997,6 @@ void dec_free(rrv_handle h, DecPlan& d) {
 }
 int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W) {       // complete or empty, as enc_plan
     if (d.B >= B && d.H == H && d.W == W && d.pre) return RRV_OK;
-    free_graphs(h);
     dec_free(h, d);
     const int H8 = H / 8, W8 = W / 8, H4 = H / 4, W4 = W / 4, H2 = H / 2, W2 = W / 2;
     auto build = [&]() -> int {
@@ -1085,22 +1096,16 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, float* d_out, fl
 
 // feat != nullptr: skip the encoder and start from a cached raw relu4_1 feature (ring layout, [1,H/8,W/8,512])
 // feats != nullptr (with h->state_images == B): one cached feature per image, each normalised with ITS state set
-int transfer_device(rrv_handle h, const uint8_t* d_in, int B, int H, int W, float* d_out, const float* feat = nullptr,
+// slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
+int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, const float* feat = nullptr,
                     const PadCrop* pc = nullptr, const float* const* feats = nullptr) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     // Any frame size, as the reference: the three 2x2 max pools floor (H, W) to (H/8, W/8) and the decoder returns
     // 8*(H/8) x 8*(W/8) pixels (test/style_network_global.py:271-281, :111-122) — the stylized frame is [Ho][Wo][3].
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
-    if (Ho < 8 || Wo < 8) return fail(h, RRV_E_ARG, "transfer: frames must be at least 8 x 8 pixels");
+    RCHK(check_frame(h, H, W, "transfer"));
     if (h->active_src == -1) return fail(h, RRV_E_STATE, "state not computed: call compute() (or set_state) before transfer()");
     if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-    // element indices inside one image are 32-bit in the kernels' epilogues: (H+2)(W+2) x 64 channels must stay below 2^31
-    if ((double)(H + 2) * (W + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "transfer: frame too large ((H+2)*(W+2)*64 must be < 2^31)");
-    // consecutive calls alternate over two (stream, workspace) pairs so that the tail / store burst of
-    // one batch's kernels overlaps the next batch's kernels (frames are independent)
-    const int slot = h->slot_override >= 0 ? h->slot_override : (h->n_slots > 1 && !h->profiling) ? h->next_slot : 0;
-    h->next_slot = (slot + 1) % h->n_slots;
-    h->last_slot = slot;
     struct StreamScope { rrv_handle h; ~StreamScope() { h->stream = h->streams[0]; h->f43_path = false; } } scope{h};
     h->stream = h->streams[slot];
     h->f43_path = true;            // the per-frame path: layers with an F(4x4,3x3) pack may run on conv_f43_k (use_f43)
@@ -1114,7 +1119,6 @@ int transfer_device(rrv_handle h, const uint8_t* d_in, int B, int H, int W, floa
     RCHK(dec_plan(h, d, B, Ho, Wo));
     e.gen = d.gen = ++h->launch_gen;
     const float* st = h->cur->active;
-    auto body = [&]() -> int {
     if (feats) {  // one cached feature and one state set per image
         if (h->state_images != B) return fail(h, RRV_E_ARG, "transfer: per-image features need per-image state");
         for (int b = 0; b < B; ++b) {
@@ -1168,49 +1172,6 @@ int transfer_device(rrv_handle h, const uint8_t* d_in, int B, int H, int W, floa
     }
     RCHK(resblock_frame(h, B, "slice2", d.o3, d.xs2, d.a2, d.o2, N_S2N1, N_S2N2, N_DEC4, 0, roi ? &wa : nullptr, roi ? &wo : nullptr, &d.qa2));
     RCHK(run_last(h, d.o2, B, Ho, Wo, d_out, d.pre, pc, roi ? &wl : nullptr));
-    return RRV_OK;
-    };
-    // plain one-frame transfers replay a captured graph (see rrv_ctx::GraphEntry)
-    const bool graphable = h->use_graph && B == 1 && !feat && !feats && !pc && !h->profiling && !h->debug && !h->caller_sync &&
-                           h->state_images == 0 && h->cur == &h->sets[0];
-    if (!graphable) {
-        RCHK(body());
-    } else {
-        auto key_now = [&]() { return rrv_ctx::GraphKey{H, W, d_in, d_out, h->f43_mode, h->f43_layers, h->grid_share, e.c11.p, d.o2.p, d.dpart.p, d.pre, h->illcond, h->direct_layers}; };
-        const rrv_ctx::GraphKey key = key_now();
-        rrv_ctx::GraphEntry* ge = nullptr;
-        for (auto& g : h->graphs[slot]) if (g.used && g.key == key) ge = &g;
-        if (ge && ge->exec) {
-            ge->stamp = ++h->plan_clock;
-            HIPCHK(hipGraphLaunch(ge->exec, h->stream));
-            h->last_pre = d.pre; h->last_pre_H = Ho; h->last_pre_W = Wo; h->last_pre_B = 1;
-        } else if (ge) {                  // second sighting: capture, instantiate, replay
-            ge->stamp = ++h->plan_clock;
-            hipGraph_t graph = nullptr;
-            bool ok = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            int rc = RRV_OK;
-            if (ok) {
-                rc = body();
-                ok = hipStreamEndCapture(h->stream, &graph) == hipSuccess && rc == RRV_OK && graph != nullptr;
-            }
-            if (ok) ok = hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!ok) {                    // no graph for this handle from here on; run the frame the ordinary way
-                (void)hipGetLastError();
-                ge->exec = nullptr; ge->used = false;
-                h->use_graph = false;
-                RCHK(body());
-            } else {
-                HIPCHK(hipGraphLaunch(ge->exec, h->stream));
-            }
-        } else {                          // first sighting: an ordinary run (allocates the split-K parts), then remember the key
-            RCHK(body());
-            rrv_ctx::GraphEntry* slot_e = &h->graphs[slot][0];
-            for (auto& g : h->graphs[slot]) { if (!g.used) { slot_e = &g; break; } if (g.stamp < slot_e->stamp) slot_e = &g; }
-            if (slot_e->exec) (void)hipGraphExecDestroy(slot_e->exec);
-            *slot_e = rrv_ctx::GraphEntry{key_now(), nullptr, ++h->plan_clock, true};
-        }
-    }
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
@@ -1669,13 +1630,11 @@ int rrv_create(int device, rrv_handle* out) {
     if (const char* e = getenv("RRV_P8")) h->p8 = atoi(e) & 3;
     if (const char* e = getenv("RRV_F43")) h->f43_mode = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
     if (const char* e = getenv("RRV_DEBUG")) h->debug = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
-    if (const char* e = getenv("RRV_GRAPH")) h->use_graph = atoi(e) != 0;
     *out = h;
     return RRV_OK;
 }
 
 static void free_plans(rrv_handle h) {
-    free_graphs(h);           // captured launches point into the plans
     for (auto& pair : h->enc_frame) for (EncPlan& e : pair) enc_free(e);
     enc_free(h->enc_add); enc_free(h->enc_style);
     for (auto& pair : h->dec) for (DecPlan& d : pair) dec_free(h, d);
@@ -1763,10 +1722,8 @@ int rrv_destroy(rrv_handle h) {
     if (h->stat_acc) (void)hipFree(h->stat_acc);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
     for (auto& st : h->hstage) {
-        if (st.pin_in) (void)hipHostFree(st.pin_in);
-        if (st.pin_out) (void)hipHostFree(st.pin_out);
-        if (st.d_in) (void)hipFree(st.d_in);
-        if (st.d_out) (void)hipFree(st.d_out);
+        stage_free(st.pin, true);
+        stage_free(st.dev, false);
         for (hipEvent_t e : {st.in_done, st.k_done, st.out_done}) if (e) (void)hipEventDestroy(e);
     }
     if (h->copy_in) (void)hipStreamDestroy(h->copy_in);
@@ -1892,7 +1849,7 @@ int rrv_prepare_style(rrv_handle h, const uint8_t* style, int Hs, int Ws, int si
     RCHK(sync_all(h));
     StyleState& S = h->styles[sid];
     if (!S.blob) RCHK(dalloc(h, &S.blob, RRV_STATE_FLOATS));
-    RCHK(ensure_u8(h, (size_t)Hs * Ws * 3));
+    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)Hs * Ws * 3));
     HIPCHK(hipMemcpyAsync(h->d_u8, style, (size_t)Hs * Ws * 3, hipMemcpyHostToDevice, h->stream));
     RCHK(enc_plan(h, h->enc_style, 1, Hs, Ws));
     EncPlan& e = h->enc_style;
@@ -1967,7 +1924,8 @@ static int flush_pending(rrv_handle h) {
 }
 
 int rrv_add(rrv_handle h, const uint8_t* frame, int H, int W) {
-    if (!h || !frame || H < 8 || W < 8) return RRV_E_ARG;
+    if (!h || !frame) return RRV_E_ARG;
+    RCHK(check_frame(h, H, W, "add"));
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     if ((!h->patches.empty() || h->pend_n) && (H != h->add_H || W != h->add_W))
@@ -2137,34 +2095,43 @@ int rrv_broadcast_state(rrv_handle h, void* comm, int root, int my_rank, int sid
     return RRV_OK;
 }
 
-int rrv_transfer_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    if (!h || !d_in || !d_out) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    RCHK(ensure_active(h));
-    return transfer_device(h, (const uint8_t*)d_in, B, H, W, (float*)d_out);
+// The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
+// burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
+static int next_device_slot(rrv_handle h) {
+    const int slot = (h->n_slots > 1 && !h->profiling) ? h->next_slot : 0;
+    h->next_slot = (slot + 1) % h->n_slots;
+    return slot;
 }
 
 static int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
-// [B][H][W][3] UNPADDED uint8 frames in HBM -> [B][H][W][3] float32 stylized frames in HBM: the reference driver's
-// reflect padding (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
+// pad: [B][H][W][3] UNPADDED uint8 frames -> [B][H][W][3] float32 stylized frames: the reference driver's reflect padding
+// (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
+static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, bool pad) {
+    RCHK(ensure_active(h));
+    if (!pad) return transfer_device(h, slot, (const uint8_t*)d_in, B, H, W, (float*)d_out);
+    const PadCrop pc{H, W, 64, 64};
+    return transfer_device(h, slot, (const uint8_t*)d_in, B, padded_size(H), padded_size(W), (float*)d_out, nullptr, &pc);
+}
+
+int rrv_transfer_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    if (!h || !d_in || !d_out) return RRV_E_ARG;
+    HIPCHK(hipSetDevice(h->dev));
+    return transfer_on_slot(h, next_device_slot(h), d_in, B, H, W, d_out, false);
+}
+
 int rrv_transfer_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
     if (!h || !d_in || !d_out || H < 1 || W < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
-    RCHK(ensure_active(h));
-    const PadCrop pc{H, W, 64, 64};
-    return transfer_device(h, (const uint8_t*)d_in, B, padded_size(H), padded_size(W), (float*)d_out, nullptr, &pc);
+    return transfer_on_slot(h, next_device_slot(h), d_in, B, H, W, d_out, true);
 }
 
 int rrv_transfer_device(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
     return rrv_transfer_batch_device(h, d_in, 1, H, W, d_out);
 }
 
-int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
-    if (!h || !d_in || !d_out || !wts || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    RCHK(sync_all(h));
-    h->next_slot = 0;
+// the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
+static int blend_into_current(rrv_handle h, const float* wts, int ns) {
     BlendP bp{};
     bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
     for (int s = 0; s < ns; ++s) {
@@ -2175,26 +2142,31 @@ int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, cons
     HIPCHK(hipGetLastError());
     for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f));
     h->active_src = -2;
-    const int rc = transfer_device(h, (const uint8_t*)d_in, 1, H, W, (float*)d_out);
-    h->next_slot = 0;
-    return rc;
+    return RRV_OK;
 }
 
-// host-buffer wrappers: H2D, same device path, D2H
-static int host_roundtrip(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out, const float* wts, int ns) {
-    if (!h || !frames || !out || B < 1) return RRV_E_ARG;
-    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, "transfer: frames must be at least 8 x 8 pixels");
+// The serialised entries (one shared state set) run on slot 0; the next alternating call starts there.
+int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
+    if (!h || !d_in || !d_out || !wts || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
-    const size_t n = (size_t)B * H * W * 3;                                  // input bytes
-    const size_t no = (size_t)B * (H / 8 * 8) * (W / 8 * 8) * 3;             // output floats: the stylized frame is 8*(H/8) x 8*(W/8)
-    RCHK(ensure_u8(h, n));
-    RCHK(ensure_outf(h, no));
     RCHK(sync_all(h));
-    h->next_slot = 0;                                   // the shared staging buffers serialise this path
-    HIPCHK(hipMemcpyAsync(h->d_u8, frames, n, hipMemcpyHostToDevice, h->streams[0]));
-    if (wts) RCHK(rrv_transfer_blend_device(h, h->d_u8, H, W, wts, ns, h->d_outf));
-    else RCHK(rrv_transfer_batch_device(h, h->d_u8, B, H, W, h->d_outf));
     h->next_slot = 0;
+    RCHK(blend_into_current(h, wts, ns));
+    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, (float*)d_out);
+}
+
+// host-buffer form: H2D, the device entry, D2H
+int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
+    if (!h || !frame || !out || !wts) return RRV_E_ARG;
+    RCHK(check_frame(h, H, W, "transfer"));
+    HIPCHK(hipSetDevice(h->dev));
+    const size_t n = (size_t)H * W * 3;                                  // input bytes
+    const size_t no = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;             // output floats: the stylized frame is 8*(H/8) x 8*(W/8)
+    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, n));
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, no));
+    RCHK(sync_all(h));
+    HIPCHK(hipMemcpyAsync(h->d_u8, frame, n, hipMemcpyHostToDevice, h->streams[0]));
+    RCHK(rrv_transfer_blend_device(h, h->d_u8, H, W, wts, ns, h->d_outf));
     HIPCHK(hipMemcpyAsync(out, h->d_outf, no * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
@@ -2305,47 +2277,38 @@ static bool is_pinned(const void* ptr, size_t bytes) {
     return true;
 }
 static int retire_ticket(rrv_handle h, int set);
+// The entries that use all staging sets: open look-ahead tickets own sets, so retire them and wait for everything; the
+// entry then runs its own slots, and the alternating device entries start again at slot 0 after it.
+static int claim_staging(rrv_handle h) {
+    for (int i = 0; i < HOST_SETS; ++i) RCHK(retire_ticket(h, i));
+    RCHK(sync_all(h));
+    h->next_slot = 0;
+    return RRV_OK;
+}
 static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out, bool pad_on_device = false) {
     if (!h || !frames || !out || B < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
+    // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
+    if (pad_on_device && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer: empty frame");
+    const int KH = pad_on_device ? padded_size(H) : H, KW = pad_on_device ? padded_size(W) : W;
+    RCHK(check_frame(h, KH, KW, "transfer"));
     const size_t fb = (size_t)H * W * 3;                                   // input bytes per frame
     const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output floats per frame (any input size: 8*(H/8) x 8*(W/8))
-    const int sub = pad_on_device ? host_sub(B, (H + 128 + 63) / 64 * 64, (W + 128 + 63) / 64 * 64) : host_sub(B, H, W);
-    {   // refuse oversized frames before any staging buffer is sized for them
-        const double ph = pad_on_device ? (double)((H + 128 + 63) / 64 * 64) : (double)H, pw = pad_on_device ? (double)((W + 128 + 63) / 64 * 64) : (double)W;
-        if (H < 1 || W < 1 || (!pad_on_device && (H < 8 || W < 8))) return fail(h, RRV_E_ARG, "transfer: frames must be at least 8 x 8 pixels");
-        if ((ph + 2) * (pw + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "transfer: frame too large ((H+2)*(W+2)*64 must be < 2^31)");
-    }
+    const int sub = host_sub(B, KH, KW);
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fo * sizeof(float));
-    for (int i = 0; i < HOST_SETS; ++i) RCHK(retire_ticket(h, i));     // open look-ahead tickets own the staging sets
-    RCHK(sync_all(h));
+    RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
     const bool zin = h->host_io == 1 || h->host_io == 2, zout = h->host_io == 1 || h->host_io == 3;
-    for (int i = 0; i < nsets; ++i) {
-        auto& st = h->hstage[i];
-        if (h->host_io != 1 && st.cap < (size_t)sub * fb) {
-            if (st.d_in) (void)hipFree(st.d_in);
-            if (st.d_out) (void)hipFree(st.d_out);
-            st.d_in = nullptr; st.d_out = nullptr; st.cap = 0;
-            RCHK(dmalloc(h, (void**)&st.d_in, (size_t)sub * fb));
-            RCHK(dmalloc(h, (void**)&st.d_out, (size_t)sub * fb * sizeof(float)));
-            st.cap = (size_t)sub * fb;
-        }
-        if ((!in_pin || !out_pin) && st.pcap < (size_t)sub * fb) {     // pinned staging only for pageable caller arrays
-            if (st.pin_in) (void)hipHostFree(st.pin_in);
-            if (st.pin_out) (void)hipHostFree(st.pin_out);
-            st.pin_in = nullptr; st.pin_out = nullptr; st.pcap = 0;
-            HIPCHK(hipHostMalloc((void**)&st.pin_in, (size_t)sub * fb, hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void**)&st.pin_out, (size_t)sub * fb * sizeof(float), hipHostMallocDefault));
-            st.pcap = (size_t)sub * fb;
-        }
+    for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
+        RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fo, false));
+        RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fo, true));
     }
     auto count = [&](int k) { return (k + 1) * sub <= B ? sub : B - k * sub; };
     auto drain = [&](int k) -> int {       // sub-batch k delivered (its staging set is free again)
         auto& st = h->hstage[k % HOST_SETS];
         HIPCHK(hipEventSynchronize(st.out_done));
-        if (!out_pin) host_copy(out + (size_t)k * sub * fo, st.pin_out, (size_t)count(k) * fo * sizeof(float));
+        if (!out_pin) host_copy(out + (size_t)k * sub * fo, st.pin.out, (size_t)count(k) * fo * sizeof(float));
         return RRV_OK;
     };
     int rc = RRV_OK;
@@ -2356,18 +2319,16 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         if (rc != RRV_OK) break;
         const int nb = count(k);
         const uint8_t* src = frames + (size_t)k * sub * fb;
-        if (!in_pin) { host_copy(st.pin_in, src, (size_t)nb * fb); src = st.pin_in; }
+        if (!in_pin) { host_copy(st.pin.in, src, (size_t)nb * fb); src = st.pin.in; }
         const int slot = h->profiling ? 0 : (k & 1) % h->n_slots;
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
-            HIPCHK(hipMemcpyAsync(st.d_in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
-            h->next_slot = slot;
-            rc = pad_on_device ? rrv_transfer_frames_device(h, st.d_in, nb, H, W, st.d_out) : rrv_transfer_batch_device(h, st.d_in, nb, H, W, st.d_out);
+            HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
+            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, pad_on_device);
             if (rc != RRV_OK) break;
-            HIPCHK(hipMemcpyAsync(out_pin ? (void*)out : (void*)st.pin_out, st.d_out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(out_pin ? (void*)out : (void*)st.pin.out, st.dev.out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, cs));
             HIPCHK(hipStreamSynchronize(cs));
-            if (!out_pin) host_copy(out, st.pin_out, (size_t)nb * fo * sizeof(float));
-            h->next_slot = 0;
+            if (!out_pin) host_copy(out, st.pin.out, (size_t)nb * fo * sizeof(float));
             return RRV_OK;
         }
         // zero copy per direction (rrv_set_host_io: 1 both, 2 input only, 3 output only): the first kernel reads the page-locked
@@ -2375,25 +2336,24 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         const uint8_t* k_in = src;
         if (!zin) {
             if (reuse) HIPCHK(hipStreamWaitEvent(h->copy_in, st.k_done, 0));       // the kernels of k-4 have read d_in
-            HIPCHK(hipMemcpyAsync(st.d_in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
+            HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
             HIPCHK(hipEventRecord(st.in_done, h->copy_in));
             HIPCHK(hipStreamWaitEvent(cs, st.in_done, 0));
-            k_in = st.d_in;
+            k_in = st.dev.in;
         }
-        float* const h_dst = out_pin ? out + (size_t)k * sub * fo : st.pin_out;
+        float* const h_dst = out_pin ? out + (size_t)k * sub * fo : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
-        h->next_slot = slot;
-        float* const k_out = zout ? h_dst : st.d_out;
-        rc = pad_on_device ? rrv_transfer_frames_device(h, k_in, nb, H, W, k_out) : rrv_transfer_batch_device(h, k_in, nb, H, W, k_out);
+        float* const k_out = zout ? h_dst : st.dev.out;
+        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, pad_on_device);
         if (rc != RRV_OK) break;
         if (!zin) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
         if (zin) HIPCHK(hipEventRecord(st.k_done, cs));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(h_dst, st.d_out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
+        HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
     }
-    if (rc != RRV_OK) { (void)sync_all(h); h->next_slot = 0; return rc; }
+    if (rc != RRV_OK) { (void)sync_all(h); return rc; }
     const int first_open = (!in_pin || !out_pin) ? (nchunk - HOST_SETS < 0 ? 0 : nchunk - HOST_SETS) : 0;
     if (in_pin && out_pin) {               // nothing to copy on the host: the last D2H of each stream order completes everything
         if (zout) RCHK(sync_all(h));
@@ -2401,7 +2361,6 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     } else {
         for (int k = first_open; k < nchunk; ++k) RCHK(drain(k));
     }
-    h->next_slot = 0;
     return RRV_OK;
 }
 
@@ -2428,15 +2387,14 @@ static int retire_ticket(rrv_handle h, int set) {
     auto& tk = h->tickets[set];
     if (!tk.open) return RRV_OK;
     HIPCHK(hipEventSynchronize(h->hstage[set].out_done));
-    if (tk.out) host_copy(tk.out, h->hstage[set].pin_out, tk.out_bytes);
+    if (tk.out) host_copy(tk.out, h->hstage[set].pin.out, tk.out_bytes);
     tk.open = false;
     return RRV_OK;
 }
 
 int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* out, long* ticket) {
     if (!h || !frame || !out || !ticket) return RRV_E_ARG;
-    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, "transfer: frames must be at least 8 x 8 pixels");
-    if ((double)(H + 2) * (W + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "transfer: frame too large ((H+2)*(W+2)*64 must be < 2^31)");
+    RCHK(check_frame(h, H, W, "transfer"));
     HIPCHK(hipSetDevice(h->dev));
     const size_t fb = (size_t)H * W * 3, fo = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
     const long id = h->next_ticket;
@@ -2444,32 +2402,17 @@ int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* 
     auto& st = h->hstage[set];
     RCHK(retire_ticket(h, set));                                   // the set's previous ticket (four submissions ago)
     const bool in_pin = is_pinned(frame, fb), out_pin = is_pinned(out, fo * sizeof(float));
-    if (st.pcap < fb) {       // (re)size this set's page-locked staging: nothing of it is in flight any more
-        if (st.d_in) (void)hipFree(st.d_in);
-        if (st.d_out) (void)hipFree(st.d_out);
-        if (st.pin_in) (void)hipHostFree(st.pin_in);
-        if (st.pin_out) (void)hipHostFree(st.pin_out);
-        st.d_in = nullptr; st.d_out = nullptr; st.pin_in = nullptr; st.pin_out = nullptr; st.cap = 0; st.pcap = 0;
-        if (hipHostMalloc((void**)&st.pin_in, fb, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&st.pin_out, fb * sizeof(float), hipHostMallocDefault) != hipSuccess)
-            return fail(h, RRV_E_NOMEM, "transfer_async: out of page-locked host memory");
-        st.pcap = fb;
-    }
-    if (st.cap < fb) {        // device-side input of this set (d_out keeps host_pipeline's invariant: 4 x the input bytes)
-        if (st.d_in) (void)hipFree(st.d_in);
-        if (st.d_out) (void)hipFree(st.d_out);
-        st.d_in = nullptr; st.d_out = nullptr; st.cap = 0;
-        RCHK(dmalloc(h, (void**)&st.d_in, fb));
-        RCHK(dmalloc(h, (void**)&st.d_out, fb * sizeof(float)));
-        st.cap = fb;
-    }
+    // this set's staging (nothing of it is in flight any more); the last kernel writes the output to page-locked memory itself
+    RCHK(stage_reserve(h, set, in_pin ? 0 : fb, out_pin ? 0 : fo, true));
+    RCHK(stage_reserve(h, set, fb, 0, false));
     const uint8_t* src = frame;
-    if (!in_pin) { host_copy(st.pin_in, frame, fb); src = st.pin_in; }
+    if (!in_pin) { host_copy(st.pin.in, frame, fb); src = st.pin.in; }
     // Four tickets may be open: each runs on its own (stream, workspace) with a quarter of the CUs per persistent grid, so
     // the frames run side by side instead of queueing behind each other's last partial round of work items (one frame
     // fills 1.56 - 12.5 rounds of 256 workgroups per layer; measured device-resident at 512 x 512, one frame per launch:
     // 508 frames/s on one stream, 569 on two, 603 on four with a quarter of the CUs each — profiles/r03_b1_streams.txt)
-    const int slot = h->profiling ? 0 : (int)(id % RRV_MAX_SLOTS);
+    const int slot = h->profiling ? 0 : (int)(id % RRV_MAX_SLOTS);      // the ticket's own pair, whatever rrv_set_pipeline says
+    h->next_slot = 0;
     hipStream_t cs = h->streams[slot];
     struct ShareScope { rrv_handle h; int saved; ~ShareScope() { h->grid_share = saved; } } share_scope{h, h->grid_share};
     if (!h->profiling && h->grid_share == 1) {       // as many shares as frames in flight once this one is queued (1 .. 4)
@@ -2485,12 +2428,9 @@ int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* 
     // four compute streams — more than hardware queues, and a D2H copy then waits behind another frame's kernels:
     // measured 230-260 frames/s against 551.)
     RCHK(ensure_active(h));
-    HIPCHK(hipMemcpyAsync(st.d_in, src, fb, hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(st.dev.in, src, fb, hipMemcpyHostToDevice, cs));
     HIPCHK(hipEventRecord(st.in_done, cs));      // the frame has left the caller's buffer (waited for below when the copy reads it directly)
-    h->slot_override = slot;       // (rrv_set_pipeline(1) would otherwise put the kernels on stream 0 and the event below on an idle stream)
-    const int rc0 = transfer_device(h, st.d_in, 1, H, W, out_pin ? out : st.pin_out);
-    h->slot_override = -1;
-    h->next_slot = 0;
+    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out);
     // Contract (include/rerevst_hip.h): `frame` may be reused as soon as the call returns.  A pageable frame was copied to
     // staging above; a page-locked one is the DIRECT source of the asynchronous H2D copy, so wait for that copy (queued
     // first on an idle stream: finished long before the launches above were) — also on the error path.
@@ -2516,11 +2456,6 @@ int rrv_transfer_wait(rrv_handle h, long ticket) {
     return retire_ticket(h, set);
 }
 
-int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
-    if (!wts) return RRV_E_ARG;
-    return host_roundtrip(h, frame, 1, H, W, out, wts, ns);
-}
-
 // ---- multi-style feature API ("Multi-style Interpolation/stylization.py":66-100): the reference caches the
 // encoder output of every frame on disk (test.py:87-101) and feeds it back; here the cache lives in HBM.
 static size_t feature_floats(int H, int W) {      // ring-layout [1, H/8, W/8, 512] image + the same slack as talloc (tile-overrun reads stay inside)
@@ -2531,7 +2466,7 @@ static size_t feature_floats(int H, int W) {      // ring-layout [1, H/8, W/8, 5
 int rrv_generate_content_features(rrv_handle h, const uint8_t* frame, int H, int W, int* feature_id) {
     if (!h || !frame || !feature_id) return RRV_E_ARG;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, "generate_content_features: frame too small");
+    RCHK(check_frame(h, H, W, "generate_content_features"));
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     rrv_ctx::Feature ft{nullptr, H, W, nullptr, true};
@@ -2543,7 +2478,7 @@ int rrv_generate_content_features(rrv_handle h, const uint8_t* frame, int H, int
         *feature_id = (int)h->features.size() - 1;
         return RRV_OK;
     }
-    RCHK(ensure_u8(h, (size_t)H * W * 3));
+    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)H * W * 3));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, (size_t)H * W * 3, hipMemcpyHostToDevice, h->stream));
     RCHK(enc_plan(h, h->enc_add, 1, H, W));
     RCHK(run_encoder(h, h->enc_add, h->d_u8, 0, nullptr, nullptr, 1));
@@ -2566,11 +2501,9 @@ int rrv_generate_content_features(rrv_handle h, const uint8_t* frame, int H, int
 int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, int* feature_ids) {
     if (!h || !frames || !feature_ids || B < 1) return RRV_E_ARG;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, "generate_content_features: frame too small");
-    if ((double)(H + 2) * (W + 2) * 64.0 >= 2147483648.0) return fail(h, RRV_E_ARG, "generate_content_features: frame too large ((H+2)*(W+2)*64 must be < 2^31)");
+    RCHK(check_frame(h, H, W, "generate_content_features"));
     HIPCHK(hipSetDevice(h->dev));
-    for (int i = 0; i < HOST_SETS; ++i) RCHK(retire_ticket(h, i));
-    RCHK(sync_all(h));
+    RCHK(claim_staging(h));
     const size_t fb = (size_t)H * W * 3;
     Tens one; one.B = 1; one.H = H / 8; one.W = W / 8; one.C = 512;
     const size_t img = one.img_floats(), slack = feature_floats(H, W) - img;
@@ -2604,26 +2537,11 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
     const int nchunk = (n_res + sub - 1) / sub;
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
     const bool in_pin = is_pinned(frames, (size_t)n_res * fb);
-    for (int i = 0; i < nsets; ++i) {
-        auto& st = h->hstage[i];
-        if (st.cap < (size_t)sub * fb) {
-            if (st.d_in) (void)hipFree(st.d_in);
-            if (st.d_out) (void)hipFree(st.d_out);
-            st.d_in = nullptr; st.d_out = nullptr; st.cap = 0;
-            RCHK(dmalloc(h, (void**)&st.d_in, (size_t)sub * fb));
-            RCHK(dmalloc(h, (void**)&st.d_out, (size_t)sub * fb * sizeof(float)));      // (the staging sets keep host_pipeline's invariant: output = 4 x the input bytes)
-            st.cap = (size_t)sub * fb;
-        }
-        if (!in_pin && st.pcap < (size_t)sub * fb) {
-            if (st.pin_in) (void)hipHostFree(st.pin_in);
-            if (st.pin_out) (void)hipHostFree(st.pin_out);
-            st.pin_in = nullptr; st.pin_out = nullptr; st.pcap = 0;
-            HIPCHK(hipHostMalloc((void**)&st.pin_in, (size_t)sub * fb, hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void**)&st.pin_out, (size_t)sub * fb * sizeof(float), hipHostMallocDefault));
-            st.pcap = (size_t)sub * fb;
-        }
+    for (int i = 0; i < nsets; ++i) {      // input staging only: the encoder writes into the arena
+        RCHK(stage_reserve(h, i, (size_t)sub * fb, 0, false));
+        RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, 0, true));
     }
-    struct Restore { rrv_handle h; ~Restore() { h->stream = h->streams[0]; h->f43_path = false; h->next_slot = 0; } } restore{h};
+    struct Restore { rrv_handle h; ~Restore() { h->stream = h->streams[0]; h->f43_path = false; } } restore{h};
     const int nstreams = (h->profiling || h->n_slots < 2) ? 1 : 2;
     int rc = RRV_OK;
     for (int k = 0; k < nchunk && rc == RRV_OK; ++k) {
@@ -2631,9 +2549,9 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         const int nb = (k + 1) * sub <= n_res ? sub : n_res - k * sub;
         const uint8_t* src = frames + (size_t)k * sub * fb;
         if (k >= HOST_SETS) HIPCHK(hipEventSynchronize(st.k_done));            // the encoder of k-4 has read this set's input (also frees pin_in)
-        if (!in_pin) { host_copy(st.pin_in, src, (size_t)nb * fb); src = st.pin_in; }
+        if (!in_pin) { host_copy(st.pin.in, src, (size_t)nb * fb); src = st.pin.in; }
         const int slot = k % nstreams;
-        HIPCHK(hipMemcpyAsync(st.d_in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
+        HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
         HIPCHK(hipEventRecord(st.in_done, h->copy_in));
         HIPCHK(hipStreamWaitEvent(h->streams[slot], st.in_done, 0));
         h->stream = h->streams[slot];
@@ -2643,7 +2561,7 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         if (rc != RRV_OK) break;
         e.gen = ++h->launch_gen;
         Tens out41 = one; out41.B = nb; out41.p = arena + (size_t)k * sub * img;
-        rc = run_encoder(h, e, st.d_in, 0, nullptr, nullptr, nb, &out41);
+        rc = run_encoder(h, e, st.dev.in, 0, nullptr, nullptr, nb, &out41);
         if (rc != RRV_OK) break;
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
     }
@@ -2711,22 +2629,12 @@ int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns
     if (feature_id < 0 || feature_id >= (int)h->features.size() || !(h->features[feature_id].p || h->features[feature_id].u8)) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
+    h->next_slot = 0;
     const rrv_ctx::Feature& ft = h->features[feature_id];
-    BlendP bp{};
-    bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
-    for (int s = 0; s < ns; ++s) {
-        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "blend: state not computed for every style");
-        bp.st[s] = h->styles[s].blob; bp.w[s] = wts[s];
-    }
-    hipLaunchKernelGGL(blend_state_k, dim3((RRV_STATE_FLOATS + 255) / 256), dim3(256), 0, h->stream, bp);
-    HIPCHK(hipGetLastError());
-    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f));
-    h->active_src = -2;
+    RCHK(blend_into_current(h, wts, ns));
     const size_t n = (size_t)(ft.H / 8 * 8) * (ft.W / 8 * 8) * 3;
-    RCHK(ensure_outf(h, n));
-    h->next_slot = 0;
-    RCHK(transfer_device(h, ft.u8, 1, ft.H, ft.W, h->d_outf, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
-    h->next_slot = 0;
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, n));
+    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
     HIPCHK(hipMemcpyAsync(out, h->d_outf, n * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
@@ -2748,8 +2656,7 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
     const int H = h->features[ids[0]].H, W = h->features[ids[0]].W;
     for (int i = 1; i < n; ++i)
         if (h->features[ids[i]].H != H || h->features[ids[i]].W != W) return fail(h, RRV_E_ARG, "transfer: features of one call must share their size");
-    for (int i = 0; i < HOST_SETS; ++i) RCHK(retire_ticket(h, i));
-    RCHK(sync_all(h));
+    RCHK(claim_staging(h));
     const size_t npx = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
     const bool out_pin = is_pinned(out, (size_t)n * npx * sizeof(float));
     // Frames per launch sequence (rrv_set_multistyle_group; default: the host entries' ~6.6 Mpixel per launch — 4 at 1152 x 1152,
@@ -2772,30 +2679,15 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
     }
     const int ngroups = (int)groups.size();
     const int nslots = (h->profiling || h->n_slots < 2 || ngroups < 2) ? 1 : 2;
-    for (int i = 0; i < nslots; ++i) {
-        auto& st = h->hstage[i];
-        if (st.cap < (size_t)G * npx) {
-            if (st.d_in) (void)hipFree(st.d_in);
-            if (st.d_out) (void)hipFree(st.d_out);
-            st.d_in = nullptr; st.d_out = nullptr; st.cap = 0;
-            RCHK(dmalloc(h, (void**)&st.d_in, (size_t)G * npx));
-            RCHK(dmalloc(h, (void**)&st.d_out, (size_t)G * npx * sizeof(float)));
-            st.cap = (size_t)G * npx;
-        }
-        if (!out_pin && st.pcap < (size_t)G * npx) {
-            if (st.pin_in) (void)hipHostFree(st.pin_in);
-            if (st.pin_out) (void)hipHostFree(st.pin_out);
-            st.pin_in = nullptr; st.pin_out = nullptr; st.pcap = 0;
-            HIPCHK(hipHostMalloc((void**)&st.pin_in, (size_t)G * npx, hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void**)&st.pin_out, (size_t)G * npx * sizeof(float), hipHostMallocDefault));
-            st.pcap = (size_t)G * npx;
-        }
+    for (int i = 0; i < nslots; ++i) {      // output staging only: the features are on the device
+        RCHK(stage_reserve(h, i, 0, (size_t)G * npx, false));
+        RCHK(stage_reserve(h, i, 0, out_pin ? 0 : (size_t)G * npx, true));
     }
-    struct Restore { rrv_handle h; ~Restore() { h->cur = &h->sets[0]; h->state_images = 0; h->stream = h->streams[0]; h->next_slot = 0; h->active_src = -2; } } restore{h};
+    struct Restore { rrv_handle h; ~Restore() { h->cur = &h->sets[0]; h->state_images = 0; h->stream = h->streams[0]; h->active_src = -2; } } restore{h};
     auto drain = [&](int k) -> int {
         auto& st = h->hstage[k % nslots];
         HIPCHK(hipEventSynchronize(st.out_done));
-        if (!out_pin) host_copy(out + (size_t)groups[k].first * npx, st.pin_out, (size_t)groups[k].count * npx * sizeof(float));
+        if (!out_pin) host_copy(out + (size_t)groups[k].first * npx, st.pin.out, (size_t)groups[k].count * npx * sizeof(float));
         return RRV_OK;
     };
     for (int k = 0; k < ngroups; ++k) {
@@ -2822,20 +2714,19 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
             for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
         }
         h->active_src = -2;
-        h->next_slot = slot;
         if (fp[0] && cnt == 1) {       // one frame per launch: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, nullptr, 1, H, W, st.d_out, fp[0]));
+            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, fp[0]));
         } else if (fp[0]) {
             h->state_images = cnt;
-            const int rc = transfer_device(h, nullptr, cnt, H, W, st.d_out, nullptr, nullptr, fp);
+            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, nullptr, nullptr, fp);
             h->state_images = 0;
             RCHK(rc);
         } else {
-            RCHK(transfer_device(h, h->features[ids[first]].u8, 1, H, W, st.d_out, nullptr));      // re-encode the pixels
+            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, nullptr));      // re-encode the pixels
         }
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(out_pin ? (void*)(out + (size_t)first * npx) : (void*)st.pin_out, st.d_out, (size_t)cnt * npx * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
+        HIPCHK(hipMemcpyAsync(out_pin ? (void*)(out + (size_t)first * npx) : (void*)st.pin.out, st.dev.out, (size_t)cnt * npx * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
     }
     if (out_pin) HIPCHK(hipStreamSynchronize(h->copy_out));
@@ -2861,16 +2752,16 @@ int rrv_release_features(rrv_handle h) {
 int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
     if (!h || !frame || !out) return RRV_E_ARG;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    if (H < 8 || W < 8) return fail(h, RRV_E_ARG, "transfer: frames must be at least 8 x 8 pixels");
+    RCHK(check_frame(h, H, W, "transfer"));
     HIPCHK(hipSetDevice(h->dev));
     StyleState& S = h->styles[0];
     if (!S.prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
     RCHK(sync_all(h));
     const size_t nin = (size_t)H * W * 3;
     const size_t n = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;       // the stylized frame is 8*(H/8) x 8*(W/8)
-    RCHK(ensure_u8(h, nin));
+    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, nin));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, nin, hipMemcpyHostToDevice, h->stream));
-    RCHK(ensure_outf(h, n));
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, n));
     RCHK(frame_mode_forward(h, h->d_u8, H, W, h->d_outf));
     HIPCHK(hipMemcpyAsync(out, h->d_outf, n * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
@@ -2954,8 +2845,7 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
 
 // Layer-parity tap: tensor `index` (0..22 as above, 23..32 the channel-chunk-major twins q11 q1 q21 q2 q31 q32 q33 qa4 qa3
 // qa2) of image `image`, as stored.  *layout = 0: ring-layout NHWC [H+2][W+2][C]; 1: P8 [C/8][H+2][W+8][8] (conv_f43.h LAY).
-// Refused (RRV_E_STATE) unless the most recent launch on that plan wrote the tensor for that image; a replayed graph
-// (rrv_ctx::GraphEntry) stamps nothing, so after one every tensor of its plans is refused.
+// Refused (RRV_E_STATE) unless the most recent launch on that plan wrote the tensor for that image.
 int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
                              int* layout, int* channels) {
     if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 32 || image < 0 || !floats) return RRV_E_ARG;
