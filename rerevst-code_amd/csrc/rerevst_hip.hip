@@ -4,6 +4,7 @@
 // (prepare_style / add / compute, test/framework.py:82-104).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
@@ -76,8 +77,8 @@ struct EncPlan {   // encoder activations for one (B, H, W)
     unsigned gen = 0;       // last launch that used this plan (rrv_ctx::launch_gen)     // last use (two geometries per slot, least recently used one is replaced)
     Tens c11, p1, c21, p2, c31, c32, c33, p3, c41;
     // channel-chunk-major ("P8": [B][C/8][H+2][W+8][8], conv_f43.h LAY) twins of the tensors BETWEEN two conv_f43_k launches — and of c11, which
-    // conv_first_k can write either way — allocated on first use as ring-layout tensors of B * C/8 eight-channel images of width W + 6 (so the
-    // debug mode's ring / guard checks cover them unchanged).  A twin and its NHWC original never mix: each keeps its own zero ring.
+    // conv_first_k can write either way — built with the per-frame plans as ring-layout tensors of B * C/8 eight-channel images of width W + 6
+    // (so the debug mode's ring / guard checks cover them unchanged).  A twin and its NHWC original never mix: each keeps its own zero ring.
     Tens q11, q1, q21, q2, q31, q32, q33;
 };
 struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRAME batch
@@ -85,16 +86,50 @@ struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRA
     unsigned stamp = 0;
     unsigned gen = 0;
     Tens d, f1, f2, f3, xs4, a4, o4, xs3, a3, o3, xs2, a2, o2;
-    Tens qa4, qa3, qa2;     // channel-chunk-major twins of a4 / a3 / a2 (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above), allocated on first use
-    Tens dpart;             // [.., 32 * split]: partial sums of the split-K 512->32 KernelFilter convolution (allocated on first use)
+    Tens dpart;             // [.., 32 * split]: partial sums of the split-K 512->32 KernelFilter convolution (kf_split > 1 only)
+    Tens qa4, qa3, qa2;     // channel-chunk-major twins of a4 / a3 / a2 (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above)
     float* pre = nullptr;   // [H][W][3] pre-clamp tap
 };
 
-// workspace of the preparation pass (compute_style) for one geometry
+// workspace of one rrv_compute: the preparation pass (compute_style) or its streaming form (compute_style_streaming)
 struct PrepPlan {
-    int B = 0, hh = 0, ww = 0, sH = 0, sW = 0;
     Tens cn, nxt, t32, d32, u, xs[3], a[3], o[3];
-    float* cmean = nullptr;
+    Tens content;                   // resident pass: the relu4_1 features of every sampled frame
+    Tens grp, f0, su[3];            // streaming pass: one group's features, frame 0's, and its three KernelFilter residuals
+};
+
+// One workspace tensor of a plan: where it lives in the plan, its level (H, W >> level of the plan geometry), its channels
+// and flags.  A P8 twin of a C-channel tensor is B * C/8 eight-channel images of width W + 6 (EncPlan::q11 ..).
+enum { TS_P8 = 1, TS_ONE = 2 /* one image */, TS_SPLIT = 4 /* C x the KernelFilter split, absent at 1 */, TS_RES = 8 /* resident pass only */, TS_STREAM = 16 /* streaming pass only */ };
+template <class P> struct TSpec {
+    size_t off; int level, C, flags;
+    Tens& of(P& p) const { return *(Tens*)((char*)&p + off); }
+    void geo(int& B, int& H, int& W, int& C) const {     // B, H, W of the plan, C of the tensor -> the tensor's talloc arguments
+        if (flags & TS_ONE) B = 1;
+        H >>= level; W >>= level;
+        if (flags & TS_P8) { B *= C / 8; W += 6; C = 8; }
+    }
+};
+// (the order of the rows is that of the debug taps: tap_row)
+const TSpec<EncPlan> ENC_T[] = {
+    {offsetof(EncPlan, c11), 0, 64}, {offsetof(EncPlan, p1), 1, 64}, {offsetof(EncPlan, c21), 1, 128}, {offsetof(EncPlan, p2), 2, 128}, {offsetof(EncPlan, c31), 2, 256},
+    {offsetof(EncPlan, c32), 2, 256}, {offsetof(EncPlan, c33), 2, 256}, {offsetof(EncPlan, p3), 3, 256}, {offsetof(EncPlan, c41), 3, 512},
+    {offsetof(EncPlan, q11), 0, 64, TS_P8}, {offsetof(EncPlan, q1), 1, 64, TS_P8}, {offsetof(EncPlan, q21), 1, 128, TS_P8}, {offsetof(EncPlan, q2), 2, 128, TS_P8},
+    {offsetof(EncPlan, q31), 2, 256, TS_P8}, {offsetof(EncPlan, q32), 2, 256, TS_P8}, {offsetof(EncPlan, q33), 2, 256, TS_P8},
+};
+const TSpec<DecPlan> DEC_T[] = {
+    {offsetof(DecPlan, d), 3, 32}, {offsetof(DecPlan, f1), 3, 512}, {offsetof(DecPlan, f2), 3, 512}, {offsetof(DecPlan, f3), 3, 512}, {offsetof(DecPlan, xs4), 3, 256},
+    {offsetof(DecPlan, a4), 2, 256}, {offsetof(DecPlan, o4), 2, 256}, {offsetof(DecPlan, xs3), 2, 128}, {offsetof(DecPlan, a3), 1, 128}, {offsetof(DecPlan, o3), 1, 128},
+    {offsetof(DecPlan, xs2), 1, 64}, {offsetof(DecPlan, a2), 0, 64}, {offsetof(DecPlan, o2), 0, 64}, {offsetof(DecPlan, dpart), 3, 32, TS_SPLIT},
+    {offsetof(DecPlan, qa4), 2, 256, TS_P8}, {offsetof(DecPlan, qa3), 1, 128, TS_P8}, {offsetof(DecPlan, qa2), 0, 64, TS_P8},
+};
+// levels count from the full-resolution decoder output: relu4_1 (the plan's hh x ww) is level 3
+const TSpec<PrepPlan> PREP_T[] = {
+    {offsetof(PrepPlan, cn), 3, 512}, {offsetof(PrepPlan, nxt), 3, 512}, {offsetof(PrepPlan, t32), 3, 32}, {offsetof(PrepPlan, d32), 3, 32, TS_ONE}, {offsetof(PrepPlan, u), 3, 512, TS_ONE},
+    {offsetof(PrepPlan, xs[0]), 3, 256}, {offsetof(PrepPlan, a[0]), 2, 256}, {offsetof(PrepPlan, o[0]), 2, 256}, {offsetof(PrepPlan, xs[1]), 2, 128}, {offsetof(PrepPlan, a[1]), 1, 128},
+    {offsetof(PrepPlan, o[1]), 1, 128}, {offsetof(PrepPlan, xs[2]), 1, 64}, {offsetof(PrepPlan, a[2]), 0, 64}, {offsetof(PrepPlan, o[2]), 0, 64},
+    {offsetof(PrepPlan, content), 3, 512, TS_RES}, {offsetof(PrepPlan, grp), 3, 512, TS_STREAM}, {offsetof(PrepPlan, f0), 3, 512, TS_ONE | TS_STREAM},
+    {offsetof(PrepPlan, su[0]), 3, 512, TS_ONE | TS_STREAM}, {offsetof(PrepPlan, su[1]), 3, 512, TS_ONE | TS_STREAM}, {offsetof(PrepPlan, su[2]), 3, 512, TS_ONE | TS_STREAM},
 };
 
 struct StyleState {
@@ -164,11 +199,11 @@ struct rrv_ctx {
     int patch_h = 0, patch_w = 0, add_H = 0, add_W = 0;
     uint8_t* d_u8 = nullptr; size_t d_u8_cap = 0;
     float* d_outf = nullptr; size_t d_outf_cap = 0;
-    double* stat_part = nullptr; float* stat_mean = nullptr;      // chan_stats scratch
-    // streaming compute(): second partial buffer, two running accumulators [4][512] doubles, frame 0's filter residuals
-    double* stat_part2 = nullptr; double* stat_acc = nullptr;
-    float *frame_S = nullptr, *frame_cmean = nullptr;      // frame mode: nine rectangle sums [9][512], predicted content means [2][32]
-    Tens stream_u[3], stream_grp, stream_f0;
+    // fixed-size scratch, one allocation made by rrv_finalize_weights: chan_stats partials and means; streaming compute(): second
+    // partial buffer, two running accumulators [4][512] doubles; frame mode: nine rectangle sums [9][512], predicted content means
+    // [2][32]; compute(): the predicted content means
+    double *stat_part = nullptr, *stat_part2 = nullptr, *stat_acc = nullptr;
+    float *stat_mean = nullptr, *frame_S = nullptr, *frame_cmean = nullptr, *prep_cmean = nullptr;
     size_t ws_cap = (size_t)64 << 30;          // preparation-pass workspace above which compute() streams groups of frames
     int last_groups = 0, last_group_size = 0; size_t last_ws_bytes = 0;
     PrepPlan prep;
@@ -344,12 +379,13 @@ void tfree(Tens* t) {
     t->p = nullptr; t->base = nullptr;
 }
 
-// ring-layout tensor; slack rows keep tile-overrun halo reads inside the allocation
+// floats of a ring-layout tensor; slack rows keep tile-overrun halo reads inside the allocation
+size_t tens_floats(int B, int H, int W, int C) { return (size_t)B * (H + 2) * (W + 2) * C + (size_t)20 * (W + 2 + 20) * C; }
+
 int talloc(rrv_handle h, Tens* t, int B, int H, int W, int C) {
     tfree(t);
     t->B = B; t->H = H; t->W = W; t->C = C;
-    const size_t slack = (size_t)20 * (W + 2 + 20) * C;
-    const size_t floats = (size_t)B * t->img_floats() + slack;
+    const size_t floats = tens_floats(B, H, W, C);
     if (!h->debug) return dalloc(h, &t->p, floats, true);
     RCHK(dmalloc(h, (void**)&t->base, (floats + 2 * DBG_GUARD) * sizeof(float)));
     t->p = t->base + DBG_GUARD;
@@ -358,6 +394,22 @@ int talloc(rrv_handle h, Tens* t, int B, int H, int W, int C) {
     HIPCHK(hipMemsetAsync(t->p, 0, floats * sizeof(float), h->stream));
     std::lock_guard<std::mutex> lk(g_dbg_mu);
     g_dbg[t->p] = DbgRec{h, t->base, B, H, W, C, floats};
+    return RRV_OK;
+}
+
+template <class P, size_t N>
+void plan_tfree(P& p, const TSpec<P> (&spec)[N]) { for (const TSpec<P>& s : spec) tfree(&s.of(p)); }
+// The tensors of a plan's table that `chans` gives a channel count (0: not in this plan), for B images of H x W at level 0.
+// Complete or empty: a failed allocation frees every tensor of the table.
+template <class P, size_t N, class F>
+int plan_talloc(rrv_handle h, P& p, const TSpec<P> (&spec)[N], int B, int H, int W, F&& chans) {
+    for (const TSpec<P>& s : spec) {
+        int b = B, hh = H, ww = W, c = chans(s);
+        if (!c) continue;
+        s.geo(b, hh, ww, c);
+        const int rc = talloc(h, &s.of(p), b, hh, ww, c);
+        if (rc != RRV_OK) { plan_tfree(p, spec); return rc; }
+    }
     return RRV_OK;
 }
 
@@ -707,8 +759,6 @@ int chan_stats(rrv_handle h, const Tens& t, int mode, float* out) {
     if (nblk < 1) nblk = 1;
     const int ppb = (int)((npix + nblk - 1) / nblk);
     // scratch shared by all calls: they are ordered on h->stream (1024 partial blocks x 3 x 512 channels at most)
-    if (!h->stat_part) RCHK(dmalloc(h, (void**)&h->stat_part, (size_t)1024 * 3 * 512 * sizeof(double)));
-    if (!h->stat_mean) RCHK(dmalloc(h, (void**)&h->stat_mean, 512 * sizeof(float)));
     if (t.C > 512) return fail(h, RRV_E_ARG, "chan_stats: more than 512 channels");
     double* part = h->stat_part;
     float* mean = h->stat_mean;
@@ -824,31 +874,25 @@ int ensure_active(rrv_handle h) {
 
 // ---- encoder ----------------------------------------------------------------------------
 void enc_free(EncPlan& e) {
-    for (Tens* t : {&e.c11, &e.p1, &e.c21, &e.p2, &e.c31, &e.c32, &e.c33, &e.p3, &e.c41, &e.q11, &e.q1, &e.q21, &e.q2, &e.q31, &e.q32, &e.q33}) tfree(t);
+    plan_tfree(e, ENC_T);
     e.B = e.H = e.W = 0;
 }
+
+// A channel-chunk-major image of C channels spans (H+2)*(W+8)*C floats (rows pitched W + 8: conv_f43.h P8_PAD), more than the
+// (H+2)*(W+2)*64 of the frame-size guards; conv_f43_k's P8 store offsets are 32-bit within an image.  A tensor has a P8 twin only
+// when its image stays below 2^31 floats; otherwise the launch keeps NHWC (the same values, which run beyond the 2 GiB mark).
+bool p8_fits(int H, int W, int C) { return (double)(H + 2) * (W + 8) * C < 2147483648.0; }
+
 // A plan is either complete or empty: the geometry is recorded only after every tensor exists; a failed allocation
 // releases what was built so far, and the next call with the same geometry starts over (it must never find a
 // half-built plan that passes the cache test and launch kernels on null tensors).
-int enc_plan(rrv_handle h, EncPlan& e, int B, int H, int W) {      // grow-only in B: a plan made for more images serves fewer
+// per_frame: a plan of the per-frame path (rrv_ctx::enc_frame), which gets the P8 twins where the chain may run
+int enc_plan(rrv_handle h, EncPlan& e, int B, int H, int W, bool per_frame = false) {      // grow-only in B: a plan made for more images serves fewer
     if (e.B >= B && e.H == H && e.W == W && e.c41.p) return RRV_OK;
     RCHK(check_image_size(h, H, W, "encoder"));
     enc_free(e);
-    const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, H8 = H4 / 2, W8 = W4 / 2;
-    auto build = [&]() -> int {
-        RCHK(talloc(h, &e.c11, B, H, W, 64));
-        RCHK(talloc(h, &e.p1, B, H2, W2, 64));
-        RCHK(talloc(h, &e.c21, B, H2, W2, 128));
-        RCHK(talloc(h, &e.p2, B, H4, W4, 128));
-        RCHK(talloc(h, &e.c31, B, H4, W4, 256));
-        RCHK(talloc(h, &e.c32, B, H4, W4, 256));
-        RCHK(talloc(h, &e.c33, B, H4, W4, 256));
-        RCHK(talloc(h, &e.p3, B, H8, W8, 256));
-        RCHK(talloc(h, &e.c41, B, H8, W8, 512));
-        return RRV_OK;
-    };
-    const int rc = build();
-    if (rc != RRV_OK) { enc_free(e); return rc; }
+    const bool twins = per_frame && (h->p8 & 1) && p8_fits(H, W, 64) && p8_fits(H / 2, W / 2, 128) && p8_fits(H / 4, W / 4, 256);
+    RCHK(plan_talloc(h, e, ENC_T, B, H, W, [&](const TSpec<EncPlan>& s) { return (s.flags & TS_P8) && !twins ? 0 : s.C; }));
     e.B = B; e.H = H; e.W = W;
     return RRV_OK;
 }
@@ -870,11 +914,6 @@ Plan& pick_plan(rrv_handle h, Plan (&v)[2], int B, int H, int W) {
 // unpadded source frame behind a padded geometry (ReshapeTool on the device): pad on the way in, crop on the way out
 struct PadCrop { int src_H, src_W, top, left; };
 
-// A channel-chunk-major image of C channels spans (H+2)*(W+8)*C floats (rows pitched W + 8: conv_f43.h P8_PAD), more than the
-// (H+2)*(W+2)*64 of the frame-size guards; conv_f43_k's P8 store offsets are 32-bit within an image.  A tensor is P8 only when
-// its image stays below 2^31 floats; otherwise the launch keeps NHWC (the same values, which run beyond the 2 GiB mark).
-bool p8_fits(int H, int W, int C) { return (double)(H + 2) * (W + 8) * C < 2147483648.0; }
-
 // nb: images to encode (plans are grow-only, so a plan may hold room for more)
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
 int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr) {
@@ -891,8 +930,9 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     // Channel-chunk-major tensors (conv_f43.h LAY) between the seven packed layers when ALL of them run conv_f43_k in this launch (the rule
     // of use_f43 says yes for every launch with enough work items: the batched entries); any other mix keeps NHWC throughout.  Where every
     // level is a multiple of 32 pixels wide the choice changes no bit of the result (conv_f43_k stages the same bytes from either layout);
-    // elsewhere the edge tiles see other discarded columns (conv_f43.h P8_PAD): rounding noise, GPU test.
-    bool p8 = which == 0 && h->f43_path && (h->p8 & 1) && p8_fits(H, W, 64) && p8_fits(H / 2, W / 2, 128) && p8_fits(H / 4, W / 4, 256);
+    // elsewhere the edge tiles see other discarded columns (conv_f43.h P8_PAD): rounding noise, GPU test.  Only a plan with the twins
+    // (enc_plan) can run the chain.
+    bool p8 = which == 0 && h->f43_path && e.q11.p != nullptr;
     struct TablesScope { rrv_handle h; ~TablesScope() { h->enc_p8_tables = false; } } tables_scope{h};
     {
         const int lh[8] = {0, H, H / 2, H / 2, H / 4, H / 4, H / 4, H / 4}, lw[8] = {0, W, W / 2, W / 2, W / 4, W / 4, W / 4, W / 4};
@@ -900,21 +940,6 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
         h->enc_p8_tables = p8;      // priced as a P8 chain first; if one layer then prefers F(2x2,3x3) the chain is NHWC and every layer is priced again as such (in conv())
         for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, *W_(i), B, lh[i], lw[i], le[i], false, 0, false);
         h->enc_p8_tables = p8;
-    }
-    if (p8 && !e.q33.p) {      // first use of this plan with the chain: the twins, for as many images as the plan holds
-        const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
-        auto build = [&]() -> int {
-            RCHK(talloc(h, &e.q11, e.B * 8, H, W + 6, 8));
-            RCHK(talloc(h, &e.q1, e.B * 8, H2, W2 + 6, 8));
-            RCHK(talloc(h, &e.q21, e.B * 16, H2, W2 + 6, 8));
-            RCHK(talloc(h, &e.q2, e.B * 16, H4, W4 + 6, 8));
-            RCHK(talloc(h, &e.q31, e.B * 32, H4, W4 + 6, 8));
-            RCHK(talloc(h, &e.q32, e.B * 32, H4, W4 + 6, 8));
-            RCHK(talloc(h, &e.q33, e.B * 32, H4, W4 + 6, 8));
-            return RRV_OK;
-        };
-        const int rc = build();
-        if (rc != RRV_OK) { for (Tens* t : {&e.q11, &e.q1, &e.q21, &e.q2, &e.q31, &e.q32, &e.q33}) tfree(t); return rc; }
     }
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0};
@@ -991,56 +1016,48 @@ int stage_reserve(rrv_handle h, int set, size_t in_bytes, size_t out_floats, boo
 
 // ---- per-frame decoder --------------------------------------------------------------------
 void dec_free(rrv_handle h, DecPlan& d) {
-    for (Tens* t : {&d.d, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2, &d.dpart, &d.qa4, &d.qa3, &d.qa2}) tfree(t);
+    plan_tfree(d, DEC_T);
     if (d.pre) { if (h->last_pre == d.pre) h->last_pre = nullptr; (void)hipFree(d.pre); d.pre = nullptr; }
     d.B = d.H = d.W = 0;
 }
+
+// KernelFilter.down_sample with the folded filter F1 + LeakyReLU (filter_down).  At the relu4_1 resolution a frame has few
+// 16x16 pixel tiles (25 at 512x512, 81 at 1024x1024) and the layer a single cout slab, so one launch fills a fraction of
+// the chip with one long item per workgroup.  The contraction over the 512 input channels is therefore split into
+// slices (split K): each slice is its own item with a raw partial output, a small kernel sums them and applies the
+// LeakyReLU.  The split depends on the FRAME's relu4_1 size (H8 x W8) only, so a frame's arithmetic is the same in any batch.
+int kf_split(int H8, int W8) {
+    const int tiles = ((W8 + 15) / 16) * ((H8 + 15) / 16);
+    // measurement knob (profiles/r05_kernelfilter.txt): RRV_KSPLIT = 1 / 2 / 4 / 8 forces the split
+    static const int forced = [] { const char* e = getenv("RRV_KSPLIT"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }();
+    if (forced) return forced;
+    return tiles * 8 <= 320 ? 8 : (tiles * 4 <= 512 ? 4 : (tiles * 2 <= 256 ? 2 : 1));
+}
+
 int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W) {       // complete or empty, as enc_plan
     if (d.B >= B && d.H == H && d.W == W && d.pre) return RRV_OK;
     dec_free(h, d);
-    const int H8 = H / 8, W8 = W / 8, H4 = H / 4, W4 = W / 4, H2 = H / 2, W2 = W / 2;
-    auto build = [&]() -> int {
-        RCHK(talloc(h, &d.d, B, H8, W8, 32));
-        RCHK(talloc(h, &d.f1, B, H8, W8, 512));
-        RCHK(talloc(h, &d.f2, B, H8, W8, 512));
-        RCHK(talloc(h, &d.f3, B, H8, W8, 512));
-        RCHK(talloc(h, &d.xs4, B, H8, W8, 256));
-        RCHK(talloc(h, &d.a4, B, H4, W4, 256));
-        RCHK(talloc(h, &d.o4, B, H4, W4, 256));
-        RCHK(talloc(h, &d.xs3, B, H4, W4, 128));
-        RCHK(talloc(h, &d.a3, B, H2, W2, 128));
-        RCHK(talloc(h, &d.o3, B, H2, W2, 128));
-        RCHK(talloc(h, &d.xs2, B, H2, W2, 64));
-        RCHK(talloc(h, &d.a2, B, H, W, 64));
-        RCHK(talloc(h, &d.o2, B, H, W, 64));
-        RCHK(dalloc(h, &d.pre, (size_t)B * H * W * 3, true));
-        return RRV_OK;
-    };
-    const int rc = build();
+    const int split = kf_split(H / 8, W / 8);
+    RCHK(plan_talloc(h, d, DEC_T, B, H, W, [&](const TSpec<DecPlan>& s) {
+        if (s.flags & TS_P8) return (h->p8 & 2) && p8_fits(H >> s.level, W >> s.level, s.C) ? s.C : 0;
+        if (s.flags & TS_SPLIT) return split > 1 ? s.C * split : 0;
+        return s.C;
+    }));
+    const int rc = dalloc(h, &d.pre, (size_t)B * H * W * 3, true);
     if (rc != RRV_OK) { dec_free(h, d); return rc; }
     d.B = B; d.H = H; d.W = W;
     return RRV_OK;
 }
 
-// KernelFilter.down_sample with the folded filter F1 + LeakyReLU (cur -> d.d).  At the relu4_1 resolution a frame has few
-// 16x16 pixel tiles (25 at 512x512, 81 at 1024x1024) and the layer a single cout slab, so one launch fills a fraction of
-// the chip with one long item per workgroup.  The contraction over the 512 input channels is therefore split into
-// slices (split K): each slice is its own item with a raw partial output, a small kernel sums them and applies the
-// LeakyReLU.  The split depends on the FRAME's tile count only, so a frame's arithmetic is the same in any batch.
+// KernelFilter.down_sample (cur -> d.d), split K by kf_split into the plan's d.dpart
 int filter_down(rrv_handle h, const Tens* cur, DecPlan& d, int f, int B) {
-    const int tiles = ((cur->W + 15) / 16) * ((cur->H + 15) / 16);
-    int split = tiles * 8 <= 320 ? 8 : (tiles * 4 <= 512 ? 4 : (tiles * 2 <= 256 ? 2 : 1));
-    {   // measurement knob (profiles/r05_kernelfilter.txt): RRV_KSPLIT = 1 / 2 / 4 / 8 forces the split
-        static const int forced = [] { const char* e = getenv("RRV_KSPLIT"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }();
-        if (forced) split = forced;
-    }
+    const int split = kf_split(cur->H, cur->W);
     if (split == 1) {
         ConvCall c{cur, &d.d, &h->cur->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = E_LRELU;
         if (h->state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
         return conv(h, c);
     }
     Tens& t = d.dpart;
-    if (!t.p || t.B < B || t.H != d.d.H || t.W != d.d.W || t.C != 32 * split) RCHK(talloc(h, &t, d.d.B, d.d.H, d.d.W, 32 * split));
     ConvCall c{cur, &t, &h->cur->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = 0; c.ksplit = split; c.bias = h->cur->fold_down[f].bias;
     if (h->state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
     RCHK(conv(h, c));
@@ -1059,15 +1076,11 @@ int resblock_frame(rrv_handle h, int B, const char* blk, const Tens& in, Tens& x
     const float* st = h->cur->active;
     const std::string p = std::string("Decoder.") + blk;
     ConvCall c;
-    // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin
-    Tens* a_in = &a;
-    bool p8 = false;
-    if (qa && (h->p8 & 2) && p8_fits(a.H, a.W, a.C)) {
-        const ConvW& w2 = h->conv[p + ".conv2"];
-        p8 = use_f43(h, w2, B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) && !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
-        if (p8 && (!qa->p || qa->B < a.B * (a.C / 8))) RCHK(talloc(h, qa, a.B * (a.C / 8), a.H, a.W + 6, 8));
-        if (p8) a_in = qa;
-    }
+    // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin,
+    // where the plan has one (dec_plan)
+    const bool p8 = qa && qa->p && use_f43(h, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
+                    !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
+    Tens* a_in = p8 ? qa : &a;
     // conv1 behind the upsample and, in the same kernel, the 1x1 shortcut at the input resolution: up(conv1x1(x)) == conv1x1(up(x))
     c = ConvCall{&in, a_in, &h->conv[p + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1; c.n1 = st + SL.norm[n1];
     c.sc_out = &xs; c.out_p8 = p8;
@@ -1115,7 +1128,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     }
     EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
     DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
-    RCHK(enc_plan(h, e, B, H, W));
+    RCHK(enc_plan(h, e, B, H, W, true));
     RCHK(dec_plan(h, d, B, Ho, Wo));
     e.gen = d.gen = ++h->launch_gen;
     const float* st = h->cur->active;
@@ -1181,49 +1194,33 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
 }
 
 // ---- preparation: Decoder.compute for one style ---------------------------------------------
-void prep_free(rrv_handle h) {
-    PrepPlan& P = h->prep;
-    for (Tens* t : {&P.cn, &P.nxt, &P.t32, &P.d32, &P.u}) tfree(t);
-    for (int k = 0; k < 3; ++k) { tfree(&P.xs[k]); tfree(&P.a[k]); tfree(&P.o[k]); }
-    if (P.cmean) (void)hipFree(P.cmean);
-    P = PrepPlan{};
+void prep_free(rrv_handle h) { plan_tfree(h->prep, PREP_T); }
+int prep_chans(const TSpec<PrepPlan>& s, bool streaming) { return s.flags & (streaming ? TS_RES : TS_STREAM) ? 0 : s.C; }
+// rrv_compute's workspace for B frames (streaming: a group of B) of relu4_1 features hh x ww; complete or empty
+int prep_plan(rrv_handle h, int B, int hh, int ww, bool streaming) {
+    return plan_talloc(h, h->prep, PREP_T, B, hh << 3, ww << 3, [&](const TSpec<PrepPlan>& s) { return prep_chans(s, streaming); });
+}
+// what prep_plan allocates
+size_t prep_bytes(int B, int hh, int ww, bool streaming) {
+    size_t n = 0;
+    for (const TSpec<PrepPlan>& s : PREP_T) {
+        int b = B, H = hh << 3, W = ww << 3, c = prep_chans(s, streaming);
+        if (!c) continue;
+        s.geo(b, H, W, c);
+        n += tens_floats(b, H, W, c) * sizeof(float);
+    }
+    return n;
 }
 
-int prep_plan(rrv_handle h, int B, int hh, int ww, int sH, int sW) {
-    PrepPlan& P = h->prep;
-    if (P.B == B && P.hh == hh && P.ww == ww && P.sH == sH && P.sW == sW && P.cn.p) return RRV_OK;
-    RCHK(sync_all(h));
-    prep_free(h);
-    auto build = [&]() -> int {
-        RCHK(dalloc(h, &P.cmean, 64));
-        RCHK(talloc(h, &P.cn, B, hh, ww, 512));
-        RCHK(talloc(h, &P.nxt, B, hh, ww, 512));
-        RCHK(talloc(h, &P.t32, B, hh, ww, 32));
-        RCHK(talloc(h, &P.d32, 1, hh, ww, 32));
-        RCHK(talloc(h, &P.u, 1, hh, ww, 512));
-        const int cout[3] = {256, 128, 64};
-        for (int k = 0, H = hh, W = ww; k < 3; ++k, H *= 2, W *= 2) {
-            RCHK(talloc(h, &P.xs[k], B, H, W, cout[k]));
-            RCHK(talloc(h, &P.a[k], B, 2 * H, 2 * W, cout[k]));
-            RCHK(talloc(h, &P.o[k], B, 2 * H, 2 * W, cout[k]));
-        }
-        return RRV_OK;
-    };
-    const int rc = build();
-    if (rc != RRV_OK) { prep_free(h); return rc; }      // complete or empty, as enc_plan
-    P.B = B; P.hh = hh; P.ww = ww; P.sH = sH; P.sW = sW;
-    return RRV_OK;
-}
-
-// The workspace is released at the end (several GB for a video's sampled frames).
-int compute_style(rrv_handle h, int sid, const Tens& content) {
+// on the plan's content batch (rrv_compute)
+int compute_style(rrv_handle h, int sid) {
     StyleState& S = h->styles[sid];
     float* st = S.blob;
-    const int B = content.B, hh = content.H, ww = content.W;
-    RCHK(prep_plan(h, B, hh, ww, S.map.H, S.map.W));
     PrepPlan& P = h->prep;
+    const Tens& content = P.content;
+    const int B = content.B, hh = content.H, ww = content.W;
     Tens &cn = P.cn, &nxt = P.nxt, &t32 = P.t32, &d32 = P.d32, &u = P.u;
-    float* cmean = P.cmean;
+    float* cmean = h->prep_cmean;
     auto body = [&]() -> int {
         // norm[0].compute on the batch (style_network_global.py:396); the style half of the filter predictions
         // (normalized_style :397 through F.down_sample, :161-172) was evaluated once in prepare_style (S.smean)
@@ -1280,7 +1277,6 @@ int compute_style(rrv_handle h, int sid, const Tens& content) {
     int rc = body();
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute");
     (void)hipStreamSynchronize(h->stream);
-    prep_free(h);
     if (rc == RRV_OK) S.computed = true;
     if (rc == RRV_OK) rc = filter_conditioning(h, S);
     return rc;
@@ -1301,7 +1297,6 @@ int chan_stats1(rrv_handle h, const Tens& t, float* out) {
     if (nblk > 512) nblk = 512;
     if (nblk < 1) nblk = 1;
     if (t.C > 512) return fail(h, RRV_E_ARG, "chan_stats: more than 512 channels");
-    if (!h->stat_part) RCHK(dmalloc(h, (void**)&h->stat_part, (size_t)1024 * 3 * 512 * sizeof(double)));
     StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, h->stat_part, 0, 0};
     RCHK(launch(h, "chan_stat1", 0, 4.0 * npix * t.C, [&] { hipLaunchKernelGGL(chan_stat1_k, dim3(nblk), dim3(256), 0, h->stream, sp); }));
     return launch(h, "chan_stat1_final", 0, 0, [&] {
@@ -1316,11 +1311,10 @@ int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* 
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;       // any frame size, as in transfer_device
     EncPlan& e = pick_plan(h, h->enc_frame[0], 1, H, W);
     DecPlan& d = pick_plan(h, h->dec[0], 1, Ho, Wo);
-    RCHK(enc_plan(h, e, 1, H, W));
+    RCHK(enc_plan(h, e, 1, H, W, true));
     RCHK(dec_plan(h, d, 1, Ho, Wo));
     e.gen = d.gen = ++h->launch_gen;
-    constexpr int RS_PARTS = 1;      // (splitting the pixels over several blocks per channel quad measured slower: the merge in pred_mean_k costs more)
-    if (!h->frame_S) { RCHK(dalloc(h, &h->frame_S, RS_PARTS * 9 * 512)); RCHK(dalloc(h, &h->frame_cmean, 64)); }
+    constexpr int RS_PARTS = 1;      // (splitting the pixels over several blocks per channel quad measured slower: the merge in pred_mean_k costs more; h->frame_S holds one part)
     RCHK(run_encoder(h, e, d_img, 0, nullptr, nullptr, 1));
     Tens c41 = e.c41; c41.B = 1;          // views of one image (plans are grow-only)
     const int hh = c41.H, ww = c41.W;
@@ -1389,16 +1383,6 @@ int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* 
 // frame 0's KernelFilter residual exists and is broadcast to every frame — means nothing else crosses frames.  For
 // each of the 14 sync points every GROUP of G frames re-runs the decoder prefix from its relu4_1 features with the
 // statistics already known, contributes its partial (chan_merge_k) and is dropped.  Workspace = one group, whatever B.
-size_t tens_bytes(int B, int H, int W, int C) { return ((size_t)B * (H + 2) * (W + 2) * C + (size_t)20 * (W + 2 + 20) * C) * sizeof(float); }
-size_t prep_bytes(int B, int hh, int ww, int sH, int sW, bool streaming = false) {      // what prep_plan allocates (+ the [B,hh,ww,512] content batch)
-    (void)sH; (void)sW;
-    if (streaming)       // + frame 0's copy and its three KernelFilter residuals (the group copy is the content batch below)
-        return prep_bytes(B, hh, ww, sH, sW) + 4 * tens_bytes(1, hh, ww, 512);
-    size_t n = 2 * tens_bytes(B, hh, ww, 512) + tens_bytes(B, hh, ww, 32) + tens_bytes(1, hh, ww, 32) + tens_bytes(1, hh, ww, 512) + tens_bytes(B, hh, ww, 512);
-    const int cout[3] = {256, 128, 64};
-    for (int k = 0, H = hh, W = ww; k < 3; ++k, H *= 2, W *= 2) n += tens_bytes(B, H, W, cout[k]) + 2 * tens_bytes(B, 2 * H, 2 * W, cout[k]);
-    return n;
-}
 
 // one group's partial statistics of tensor t merged into accumulator `slot` (n_a elements per channel seen before)
 int chan_stats_group(rrv_handle h, const Tens& t, bool want_m2, int slot, double n_a) {
@@ -1408,10 +1392,6 @@ int chan_stats_group(rrv_handle h, const Tens& t, bool want_m2, int slot, double
     if (nblk < 1) nblk = 1;
     const int ppb = (int)((npix + nblk - 1) / nblk);
     if (t.C > 512) return fail(h, RRV_E_ARG, "chan_stats: more than 512 channels");
-    if (!h->stat_part) RCHK(dmalloc(h, (void**)&h->stat_part, (size_t)1024 * 3 * 512 * sizeof(double)));
-    if (!h->stat_part2) RCHK(dmalloc(h, (void**)&h->stat_part2, (size_t)1024 * 3 * 512 * sizeof(double)));
-    if (!h->stat_mean) RCHK(dmalloc(h, (void**)&h->stat_mean, 512 * sizeof(float)));
-    if (!h->stat_acc) RCHK(dmalloc(h, (void**)&h->stat_acc, (size_t)2 * 4 * 512 * sizeof(double)));
     double* acc = h->stat_acc + (size_t)slot * 4 * 512;
     StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, h->stat_part, 0, ppb};
     const int fb = (t.C + 15) / 16;
@@ -1459,7 +1439,7 @@ int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int
             }
             return RRV_OK;
         }
-        RCHK(pointwise(h, *cur, *other, nullptr, nullptr, false, &h->stream_u[f], 1, nullptr, nullptr));   // + frame 0's residual (Q1)
+        RCHK(pointwise(h, *cur, *other, nullptr, nullptr, false, &P.su[f], 1, nullptr, nullptr));   // + frame 0's residual (Q1)
         Tens* t = cur; cur = other; other = t;
     }
     if (stage == ST_NORM1) return chan_stats_group(h, *cur, true, 0, (double)frames_before * hh * ww);
@@ -1486,24 +1466,20 @@ int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int
     return fail(h, RRV_E_ARG, "stream_prefix: no such stage");
 }
 
-// Decoder.compute for one style over h->patches in groups of G frames
-int compute_style_streaming(rrv_handle h, int sid, int G) {
+// Decoder.compute for one style over h->patches in groups of the plan's P.grp.B frames (rrv_compute)
+int compute_style_streaming(rrv_handle h, int sid) {
     StyleState& S = h->styles[sid];
     float* st = S.blob;
-    const int B = (int)h->patches.size(), hh = h->patch_h, ww = h->patch_w;
-    RCHK(prep_plan(h, G, hh, ww, S.map.H, S.map.W));
     PrepPlan& P = h->prep;
-    RCHK(talloc(h, &h->stream_grp, G, hh, ww, 512));
-    RCHK(talloc(h, &h->stream_f0, 1, hh, ww, 512));
-    for (int f = 0; f < 3; ++f) RCHK(talloc(h, &h->stream_u[f], 1, hh, ww, 512));
-    const size_t img = h->stream_grp.img_floats();
+    const int B = (int)h->patches.size(), G = P.grp.B, hh = h->patch_h, ww = h->patch_w;
+    const size_t img = P.grp.img_floats();
     auto body = [&]() -> int {
         for (int stage = 0; stage < ST_COUNT; ++stage) {
             for (int g0 = 0; g0 < B; g0 += G) {
                 const int nb = B - g0 < G ? B - g0 : G;
                 for (int b = 0; b < nb; ++b)
-                    HIPCHK(hipMemcpyAsync(h->stream_grp.p + (size_t)b * img, h->patches[g0 + b], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-                RCHK(stream_prefix(h, sid, h->stream_grp, nb, stage, g0));
+                    HIPCHK(hipMemcpyAsync(P.grp.p + (size_t)b * img, h->patches[g0 + b], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+                RCHK(stream_prefix(h, sid, P.grp, nb, stage, g0));
             }
             // the sync point: every frame has contributed
             if (stage == ST_NORM0) {
@@ -1511,20 +1487,20 @@ int compute_style_streaming(rrv_handle h, int sid, int G) {
             } else if (stage >= ST_FILTER && stage < ST_FILTER + 3) {
                 const int f = stage - ST_FILTER;
                 for (int gi = 0; gi < 2; ++gi) {
-                    RCHK(chan_stats_finish(h, gi, 32, (double)B * hh * ww, 0, P.cmean));
+                    RCHK(chan_stats_finish(h, gi, 32, (double)B * hh * ww, 0, h->prep_cmean));
                     hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + gi], (const float*)h->fc_b[2 * f + gi],
-                                       (const float*)P.cmean, (const float*)(S.smean + (2 * f + gi) * 32), st + SL.filt[2 * f + gi]);
+                                       (const float*)h->prep_cmean, (const float*)(S.smean + (2 * f + gi) * 32), st + SL.filt[2 * f + gi]);
                     HIPCHK(hipGetLastError());
                 }
                 RCHK(fold_filters(h, st, f));
                 h->active_src = -1;
                 // KernelFilter.compute (:223-230): frame 0 alone passes through apply_filter; its residual u_f is what every frame receives (Q1)
-                HIPCHK(hipMemcpyAsync(h->stream_f0.p, h->patches[0], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(P.f0.p, h->patches[0], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
                 Tens cn0 = P.cn; cn0.B = 1;
-                RCHK(pointwise(h, h->stream_f0, cn0, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
-                for (int f2 = 0; f2 < f; ++f2) RCHK(pointwise(h, cn0, cn0, nullptr, nullptr, false, &h->stream_u[f2], 1, nullptr, nullptr));
+                RCHK(pointwise(h, P.f0, cn0, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
+                for (int f2 = 0; f2 < f; ++f2) RCHK(pointwise(h, cn0, cn0, nullptr, nullptr, false, &P.su[f2], 1, nullptr, nullptr));
                 ConvCall c{&cn0, &P.d32, &h->cur->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, c));
-                ConvCall cu{&P.d32, &h->stream_u[f], &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
+                ConvCall cu{&P.d32, &P.su[f], &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
             } else if (stage == ST_NORM1) {
                 RCHK(chan_stats_finish(h, 0, 512, (double)B * hh * ww, 1, st + SL.norm[N_DEC1]));
             } else {
@@ -1539,9 +1515,6 @@ int compute_style_streaming(rrv_handle h, int sid, int G) {
     int rc = body();
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute (streaming)");
     (void)hipStreamSynchronize(h->stream);
-    prep_free(h);
-    tfree(&h->stream_grp); tfree(&h->stream_f0);
-    for (int f = 0; f < 3; ++f) tfree(&h->stream_u[f]);
     h->active_src = -1;
     if (rc == RRV_OK) S.computed = true;
     if (rc == RRV_OK) rc = filter_conditioning(h, S);
@@ -1715,11 +1688,6 @@ int rrv_destroy(rrv_handle h) {
     if (h->d_outf) (void)hipFree(h->d_outf);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
     if (h->stat_part) (void)hipFree(h->stat_part);
-    if (h->stat_mean) (void)hipFree(h->stat_mean);
-    if (h->stat_part2) (void)hipFree(h->stat_part2);
-    if (h->frame_S) (void)hipFree(h->frame_S);
-    if (h->frame_cmean) (void)hipFree(h->frame_cmean);
-    if (h->stat_acc) (void)hipFree(h->stat_acc);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
     for (auto& st : h->hstage) {
         stage_free(st.pin, true);
@@ -1751,6 +1719,13 @@ int rrv_finalize_weights(rrv_handle h) {
     if (h->finalized) return RRV_OK;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(dalloc(h, &h->zero_bias, 512, true));
+    {   // the fixed-size scratch (rrv_ctx::stat_part ..): 1024 partial blocks x 3 x 512 channels at most per partial buffer
+        constexpr size_t PART = (size_t)1024 * 3 * 512, ACC = (size_t)2 * 4 * 512, FLOATS = 512 + 9 * 512 + 64 + 64;
+        float* base;
+        RCHK(dalloc(h, &base, (2 * PART + ACC) * 2 + FLOATS));
+        h->stat_part = (double*)base; h->stat_part2 = h->stat_part + PART; h->stat_acc = h->stat_part2 + PART;
+        h->stat_mean = (float*)(h->stat_acc + ACC); h->frame_S = h->stat_mean + 512; h->frame_cmean = h->frame_S + 9 * 512; h->prep_cmean = h->frame_cmean + 64;
+    }
     for (int which = 0; which < 2; ++which) {
         for (int i = 0; i < 9; ++i) {
             char k[64];
@@ -1954,28 +1929,32 @@ int rrv_compute(rrv_handle h) {
     int nprep = 0;
     for (StyleState& s : h->styles) nprep += s.prepared ? 1 : 0;
     if (!nprep) return fail(h, RRV_E_STATE, "compute: prepare_style has not been called");
-    const int B = (int)h->patches.size();
-    int sH = 0, sW = 0;
-    for (StyleState& s : h->styles) if (s.prepared) { sH = s.map.H > sH ? s.map.H : sH; sW = s.map.W > sW ? s.map.W : sW; }
-    int rc = RRV_OK, first = -1;
-    if (prep_bytes(B, h->patch_h, h->patch_w, sH, sW) <= h->ws_cap) {      // everything resident (Decoder.compute as written)
-        Tens content;
-        RCHK(talloc(h, &content, B, h->patch_h, h->patch_w, 512));
-        for (int b = 0; b < B; ++b)
+    const int B = (int)h->patches.size(), hh = h->patch_h, ww = h->patch_w;
+    // everything resident (Decoder.compute as written) if it fits the cap, else groups of G frames, one sync point at a time
+    const bool streaming = prep_bytes(B, hh, ww, false) > h->ws_cap;
+    int G = B;
+    if (streaming) {
+        G = 1;
+        while (G < B && prep_bytes(G + 1, hh, ww, true) <= h->ws_cap) ++G;
+    }
+    h->last_groups = (B + G - 1) / G; h->last_group_size = G; h->last_ws_bytes = prep_bytes(G, hh, ww, streaming);
+    RCHK(prep_plan(h, G, hh, ww, streaming));
+    int first = -1;
+    auto body = [&]() -> int {
+        const Tens& content = h->prep.content;
+        for (int b = 0; b < B && !streaming; ++b)
             HIPCHK(hipMemcpyAsync(content.p + (size_t)b * content.img_floats(), h->patches[b], content.img_floats() * sizeof(float),
                                   hipMemcpyDeviceToDevice, h->stream));
-        for (int s = 0; s < RRV_MAX_STYLES && rc == RRV_OK; ++s)
-            if (h->styles[s].prepared) { rc = compute_style(h, s, content); if (first < 0) first = s; }
-        (void)hipStreamSynchronize(h->stream);
-        tfree(&content);
-        h->last_groups = 1; h->last_group_size = B; h->last_ws_bytes = prep_bytes(B, h->patch_h, h->patch_w, sH, sW);
-    } else {                                                                // groups of G frames, one sync point at a time
-        int G = 1;
-        while (G < B && prep_bytes(G + 1, h->patch_h, h->patch_w, sH, sW, true) <= h->ws_cap) ++G;
-        for (int s = 0; s < RRV_MAX_STYLES && rc == RRV_OK; ++s)
-            if (h->styles[s].prepared) { rc = compute_style_streaming(h, s, G); if (first < 0) first = s; }
-        h->last_groups = (B + G - 1) / G; h->last_group_size = G; h->last_ws_bytes = prep_bytes(G, h->patch_h, h->patch_w, sH, sW, true);
-    }
+        for (int s = 0; s < RRV_MAX_STYLES; ++s)
+            if (h->styles[s].prepared) {
+                if (first < 0) first = s;
+                RCHK(streaming ? compute_style_streaming(h, s) : compute_style(h, s));
+            }
+        return RRV_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(h->stream);
+    prep_free(h);      // several GB for a video's sampled frames
     if (rc != RRV_OK) return rc;
     if (h->debug) RCHK(debug_verify(h, "compute"));
     h->active_src = -1;
@@ -2557,7 +2536,7 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         h->stream = h->streams[slot];
         h->f43_path = true;                  // the same kernel choice as the per-frame path's encoder (rrv_set_f43)
         EncPlan& e = pick_plan(h, h->enc_frame[slot], nb, H, W);
-        rc = enc_plan(h, e, nb, H, W);
+        rc = enc_plan(h, e, nb, H, W, true);
         if (rc != RRV_OK) break;
         e.gen = ++h->launch_gen;
         Tens out41 = one; out41.B = nb; out41.p = arena + (size_t)k * sub * img;
@@ -2823,6 +2802,12 @@ int rrv_set_host_io(rrv_handle h, int mode) {
     return RRV_OK;
 }
 
+// Debug tap `index` -> its row in ENC_T (enc) or DEC_T: 0..8 encoder, 9..22 decoder, 23..29 encoder twins, 30..32 decoder twins
+static int tap_row(int index, bool& enc) {
+    enc = index < 9 || (index >= 23 && index < 30);
+    return index < 9 ? index : index < 23 ? index - 9 : index < 30 ? index - 14 : index - 16;
+}
+
 // Debugging aid (race hunting, tools/device_stream_stress.py): copy activation tensor `index` of workspace slot `slot`
 // (0..8 encoder c11 p1 c21 p2 c31 c32 c33 p3 c41, 9..22 decoder d f1 f2 f3 xs4 a4 o4 xs3 a3 o3 xs2 a2 o2 dpart) of the plan
 // for (H, W) to the host, ring layout, first image.  *floats = its size; nothing is copied when cap is too small.
@@ -2830,12 +2815,12 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
     if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 22 || !floats) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
+    bool enc;
+    const int row = tap_row(index, enc);
     const Tens* t = nullptr;
     for (int k = 0; k < 2 && !t; ++k) {
         EncPlan& e = h->enc_frame[slot][k]; DecPlan& d = h->dec[slot][k];
-        const Tens* all[23] = {&e.c11, &e.p1, &e.c21, &e.p2, &e.c31, &e.c32, &e.c33, &e.p3, &e.c41,
-                               &d.d, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2, &d.dpart};
-        if (index < 9 ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0)) t = all[index];
+        if (enc ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0)) t = enc ? &ENC_T[row].of(e) : &DEC_T[row].of(d);
     }
     if (!t || !t->p) return fail(h, RRV_E_STATE, "debug_copy_tensor: no such tensor in this slot");
     *floats = t->img_floats();
@@ -2851,24 +2836,22 @@ int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H
     if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 32 || image < 0 || !floats) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
-    static const int TWIN_C[10] = {64, 64, 128, 128, 256, 256, 256, 256, 128, 64};
-    const bool enc = index < 9 || (index >= 23 && index < 30);
+    bool enc;
+    const int row = tap_row(index, enc);
+    const int flags = enc ? ENC_T[row].flags : DEC_T[row].flags;
     const Tens* t = nullptr;
     unsigned pgen = 0;
     for (int k = 0; k < 2; ++k) {
         EncPlan& e = h->enc_frame[slot][k]; DecPlan& d = h->dec[slot][k];
-        const Tens* all[33] = {&e.c11, &e.p1, &e.c21, &e.p2, &e.c31, &e.c32, &e.c33, &e.p3, &e.c41,
-                               &d.d, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2, &d.dpart,
-                               &e.q11, &e.q1, &e.q21, &e.q2, &e.q31, &e.q32, &e.q33, &d.qa4, &d.qa3, &d.qa2};
         const bool match = enc ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0);
         const unsigned g = enc ? e.gen : d.gen;
-        if (match && (!t || g > pgen)) { t = all[index]; pgen = g; }
+        if (match && (!t || g > pgen)) { t = enc ? &ENC_T[row].of(e) : &DEC_T[row].of(d); pgen = g; }
     }
     if (!t || !t->p) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: no such tensor in this slot");
     if (t->gen != pgen || pgen == 0) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: the plan's last launch did not write this tensor");
     if (image >= t->gen_B) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: the plan's last launch did not write this image");
-    const bool p8 = index >= 23;
-    const int C = p8 ? TWIN_C[index - 23] : t->C;
+    const bool p8 = flags & TS_P8;
+    const int C = p8 ? (enc ? ENC_T[row].C : DEC_T[row].C) : t->C;
     const size_t n = p8 ? (size_t)(C / 8) * t->img_floats() : t->img_floats();
     if ((size_t)(image + 1) * n > (p8 ? (size_t)t->B / (C / 8) : (size_t)t->B) * n) return fail(h, RRV_E_STATE, "debug_copy_tensor_ex: image beyond the tensor");
     *floats = n;

@@ -213,6 +213,32 @@ def test_old_and_new_taps_agree(pkg, weights):
         s.close()
 
 
+def test_p8_twins_are_built_with_the_plan(pkg, weights):
+    """The P8 twins come with the per-frame plan: a launch that takes the P8 chain on the plan an NHWC launch built allocates
+    nothing, and gives the bits of a fresh P8 launch."""
+    blob = load_golden("global_a")["state"]
+    frames = frames_for(pkg, 3, 48, 64)
+    s, _, d_out = launch(pkg, weights, frames, blob, 0)
+    ref, _, d_ref = launch(pkg, weights, frames, blob, 2)
+    try:
+        s.set_pipeline(1)            # the profiled launch ran on slot 0 and moved next_slot on: the next call reuses slot 0's plan
+        s.set_f43(2)
+        d_in = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+        torch.cuda.synchronize()
+        s.debug_fail_alloc(1)        # any device allocation from here on fails
+        try:
+            s.transfer_batch_device(d_in.data_ptr(), 3, 48, 64, d_out.data_ptr())
+            s.sync()
+        finally:
+            s.debug_fail_alloc(0)
+        _, lay, _ = s.debug_tensor_ex(0, LR.TAP["q11"], 48, 64, 0)      # the mode-0 launch wrote c11, this one its twin
+        assert lay == 1
+        assert torch.equal(d_out, d_ref)
+    finally:
+        s.close()
+        ref.close()
+
+
 def test_p8_offset_band_frame(pkg, weights):
     """A frame the size guard admits ((H+2)(W+2)64 < 2^31) whose full-resolution P8 images would not fit 32-bit offsets
     ((H+2)(W+8)64 >= 2^31): the full-resolution tensors keep NHWC, rows beyond the mark repeat the periodic interior bit for
