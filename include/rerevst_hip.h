@@ -214,6 +214,20 @@ int rrv_feature_cache_info(rrv_handle h, int* resident, int* spilled, size_t* by
  * prediction (:53-62,97-105); needs only rrv_prepare_style (style 0).  Host buffers. */
 int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame_bgr, int H, int W, float* out_bgr);
 
+/* The same model for B frames per call, with the shapes of the global entries: _batch as rrv_transfer_batch (any
+ * H, W >= 8, [B][8*(H/8)][8*(W/8)][3] out), _frames as rrv_transfer_frames (UNPADDED frames, reflect pad and crop on
+ * the device, [B][H][W][3] out).  Each frame gets its own statistics and predicted filters in its own state set, in
+ * launch sequences of up to 16 frames; frame b's output is bit-identical to rrv_transfer_frame_mode on that frame
+ * alone (of its padded form for _frames), in every rrv_set_f43 mode: frame mode runs F(2x2,3x3) throughout.
+ * _device: HBM buffers, B in 1..64, asynchronous, alternating over workspace slots 0 and 1, ordered by
+ * rrv_set_caller_stream.  Host forms: sub-batches of at most 16 frames through the staging pipeline
+ * (rrv_set_host_io applies).  Need rrv_prepare_style (style 0), else RRV_E_STATE; style 0's saved state is not
+ * touched.  Scratch per workspace slot and frame size: 3 x 64 x 8*(H/8) doubles per frame plus 20 rows of slack. */
+int rrv_transfer_frame_mode_batch_device(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_f32);
+int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, float* out_bgr);
+int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_f32);
+int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, float* out_bgr);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

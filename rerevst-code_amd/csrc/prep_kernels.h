@@ -106,9 +106,12 @@ __global__ void fold_up_k(const float* __restrict__ F, const float* __restrict__
 }
 
 // ---- FilterPredictor FC: out[1024] = W[1024][64] . [cmean(32), smean(32)] + b ---------
+// blockIdx.y = image of a batched frame-mode launch: cmean and out advance by cmean_bstride / out_bstride floats per image
+// (its predicted content means, its state set); the style half smean is shared
 __global__ void fc_filter_k(const float* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ cmean,
-                            const float* __restrict__ smean, float* __restrict__ out) {
+                            const float* __restrict__ smean, float* __restrict__ out, int cmean_bstride = 0, int out_bstride = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    cmean += (size_t)blockIdx.y * cmean_bstride; out += (size_t)blockIdx.y * out_bstride;
     if (i < 1024) {
         float s = 0.f;
         for (int k = 0; k < 32; ++k) s += W[i * 64 + k] * cmean[k];
@@ -127,6 +130,8 @@ struct StatP {
     double* part;
     int pass;
     int pix_per_blk;
+    int per_image;        // chan_stat1_k: blockIdx.y = image, statistics of that image alone, partials at part + image * part_bstride
+    long part_bstride;
 };
 
 __global__ __launch_bounds__(256) void chan_stat_k(const StatP p) {
@@ -241,7 +246,15 @@ __global__ __launch_bounds__(256) void chan_stat1_k(const StatP p) {
     const int Qb = CQ < 64 ? CQ : 64;
     const int nsub = 256 / Qb;
     const int ql = tid % Qb, sub = tid / Qb;
-    const int nrows = p.B * p.H;
+    const float* x = p.x;
+    double* part = p.part;
+    int nimg = p.B;
+    if (p.per_image) {      // the same block partition of ONE image's rows as a one-image launch with gridDim.x blocks
+        x += (size_t)blockIdx.y * (p.H + 2) * (p.W + 2) * p.C;
+        part += (size_t)blockIdx.y * p.part_bstride;
+        nimg = 1;
+    }
+    const int nrows = nimg * p.H;
     for (int cg = 0; cg < CQ; cg += Qb) {
         const int c = 4 * (cg + ql);
         double sd[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
@@ -250,7 +263,7 @@ __global__ __launch_bounds__(256) void chan_stat1_k(const StatP p) {
         if (sub < nsub)
             for (int r = blockIdx.x; r < nrows; r += gridDim.x) {
                 const int b = r / p.H, y = r - b * p.H;
-                const float* row = p.x + (((long)b * (p.H + 2) + y + 1) * (p.W + 2) + 1) * (long)p.C + c;
+                const float* row = x + (((long)b * (p.H + 2) + y + 1) * (p.W + 2) + 1) * (long)p.C + c;
                 if (n == 0 && sub < p.W) s0 = *(const f32x4*)(row + (long)sub * p.C);
 #pragma unroll 4
                 for (int x = sub; x < p.W; x += nsub) {
@@ -285,7 +298,7 @@ __global__ __launch_bounds__(256) void chan_stat1_k(const StatP p) {
                 }
                 na = nn;
             }
-            double* o = p.part + (size_t)blockIdx.x * 3 * p.C;
+            double* o = part + (size_t)blockIdx.x * 3 * p.C;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { o[c + e] = na; o[p.C + c + e] = mean[e]; o[2 * p.C + c + e] = m2[e]; }
         }
@@ -294,7 +307,10 @@ __global__ __launch_bounds__(256) void chan_stat1_k(const StatP p) {
 }
 // merge of the block partials; out = norm params [4][C]: mean, rsqrt(M2/N + 1e-8), -3e38, +3e38 (frame mode does not clamp).
 // launch: C/4 blocks of 256 threads = 4 channels x 64 lanes; a lane folds every 64th block, then a butterfly of Chan merges.
-__global__ __launch_bounds__(256) void chan_stat1_final_k(const double* __restrict__ part, int nblk, int C, float* __restrict__ out) {
+// blockIdx.y = image (per-image partials of chan_stat1_k, part_bstride doubles apart; its norm params out_bstride floats apart)
+__global__ __launch_bounds__(256) void chan_stat1_final_k(const double* __restrict__ part, int nblk, int C, float* __restrict__ out,
+                                                          long part_bstride = 0, long out_bstride = 0) {
+    part += (size_t)blockIdx.y * part_bstride; out += (size_t)blockIdx.y * out_bstride;
     const int cl = threadIdx.x >> 6, kl = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + cl;
     double na = 0.0, mean = 0.0, m2 = 0.0;
@@ -331,8 +347,11 @@ __global__ __launch_bounds__(256) void chan_stat1_final_k(const double* __restri
 // that falls outside:  mean_o = bias_o + (1/HW) sum_{c,tap} w[o][c][tap] * S[tap][c],
 //   S[(dy,dx)][c] = sum of x[y'][x'][c] over y' in [max(0,dy), H+min(0,dy)), x' likewise.
 // rect_sums_k: one block per channel quad of a [1,H,W,C] ring tensor -> S[9][C] (floats, accumulated in fp64).
-__global__ __launch_bounds__(256) void rect_sums_k(const float* __restrict__ x, int H, int W, int C, float* __restrict__ S) {
-    // grid (C/4, NY): block (q, j) sums every NY-th 256-pixel slice of channel quad q into the partial S[j][9][C]
+__global__ __launch_bounds__(256) void rect_sums_k(const float* __restrict__ x, int H, int W, int C, float* __restrict__ S, long S_bstride = 0) {
+    // grid (C/4, NY, B): block (q, j, b) sums every NY-th 256-pixel slice of channel quad q of image b (a [B,H,W,C] ring tensor)
+    // into the partial S_b[j][9][C], S_b = S + b * S_bstride
+    x += (size_t)blockIdx.z * (H + 2) * (W + 2) * C;
+    S += (size_t)blockIdx.z * S_bstride;
     __shared__ double red[9][4][4];     // [tap][wave][e]
     const int c = blockIdx.x * 4;
     double acc[9][4];
@@ -370,9 +389,11 @@ __global__ __launch_bounds__(256) void rect_sums_k(const float* __restrict__ x, 
     }
 }
 // out[o] = bias[o] + (1/HW) sum_{c,tap} w[o][c][tap] S[tap][c]   (w OIHW [32][C][3][3]); one block per output
+// blockIdx.y = image: its rect_sums_k partials at S + b * S_bstride, its outputs at out + b * out_bstride
 __global__ __launch_bounds__(256) void pred_mean_k(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ S, int nparts, int C,
-                                                   double inv_hw, float* __restrict__ out) {
+                                                   double inv_hw, float* __restrict__ out, long S_bstride = 0, long out_bstride = 0) {
     __shared__ double red[4];
+    S += (size_t)blockIdx.y * S_bstride; out += (size_t)blockIdx.y * out_bstride;
     const int o = blockIdx.x;
     double a = 0.0;
     for (int i = threadIdx.x; i < C * 9; i += 256) {
@@ -453,6 +474,7 @@ struct PointP {
     const float* smean; const float* sstd;   // affine after
     const float* lo; const float* hi;        // clamp of the normalised value (saved-stat forward), may be null
     int segs;                                // blocks per image row (small tensors still fill the chip)
+    long par_bstride;                        // > 0: per-image mean / scale / smean / sstd, this many floats apart (batched frame mode)
 };
 __global__ __launch_bounds__(256) void pointwise_k(const PointP p) {
     // Blocks walk (image row, row segment) pairs; 256 is a multiple of C/4, so a thread keeps ONE channel quad: its
@@ -466,8 +488,15 @@ __global__ __launch_bounds__(256) void pointwise_k(const PointP p) {
     if (p.mean) { mean = *(const f32x4*)(p.mean + c4); scale = *(const f32x4*)(p.scale + c4); }
     if (p.lo) { lo = *(const f32x4*)(p.lo + c4); hi = *(const f32x4*)(p.hi + c4); }
     if (p.smean) { smean = *(const f32x4*)(p.smean + c4); sstd = *(const f32x4*)(p.sstd + c4); }
+    int pimg = 0;      // image whose parameters are loaded (per-image parameters: reloaded where the row walk enters another image)
     for (int r = blockIdx.x / p.segs; r < nrows; r += rstep) {
         const int b = r / p.H, y = r - b * p.H;
+        if (p.par_bstride && b != pimg) {
+            const long o = (long)b * p.par_bstride + c4;
+            if (p.mean) { mean = *(const f32x4*)(p.mean + o); scale = *(const f32x4*)(p.scale + o); }
+            if (p.smean) { smean = *(const f32x4*)(p.smean + o); sstd = *(const f32x4*)(p.sstd + o); }
+            pimg = b;
+        }
         const long row = (((long)b * (p.H + 2) + y + 1) * (p.W + 2) + 1) * (long)p.C + c4;
         const long rrow = (p.res_mode == 1 ? ((long)(y + 1) * (p.Wr + 2) + 1) * (long)p.C
                          : p.res_mode == 2 ? (((long)b * (p.Hr + 2) + (y >> 1) + 1) * (p.Wr + 2) + 1) * (long)p.C : 0) + c4;
@@ -513,6 +542,17 @@ __global__ void sum_parts_lrelu_k(const float* __restrict__ part, float* __restr
 __global__ void identity_norm_k(float* __restrict__ n, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) { n[c] = 0.f; n[C + c] = 1.f; n[2 * C + c] = -3.0e38f; n[3 * C + c] = 3.0e38f; }
+}
+
+// state sets of a batched frame-mode launch: set b (count floats apart, blockIdx.y = b) := the style's blob, with the
+// identity entry of identity_norm_k at n_off (C channels) — every other per-frame entry is overwritten by the launch itself
+__global__ void frame_sets_init_k(const float* __restrict__ blob, float* __restrict__ sets, int count, int n_off, int C) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    float v = blob[i];
+    const int k = i - n_off;
+    if (k >= 0 && k < 4 * C) v = k < C ? 0.f : (k < 2 * C ? 1.f : (k < 3 * C ? -3.0e38f : 3.0e38f));
+    sets[(size_t)blockIdx.y * count + i] = v;
 }
 
 // blended state for multi-style interpolation: out = sum_s w[s] * state_s

@@ -88,6 +88,9 @@ struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRA
     Tens d, f1, f2, f3, xs4, a4, o4, xs3, a3, o3, xs2, a2, o2;
     Tens dpart;             // [.., 32 * split]: partial sums of the split-K 512->32 KernelFilter convolution (kf_split > 1 only)
     Tens qa4, qa3, qa2;     // channel-chunk-major twins of a4 / a3 / a2 (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above)
+    // batched frame mode only (frame_mode_device): per-image scratch, image b in interior row b (frame_row): chan_stat1_k partials
+    // (min(H_l, 512) x 3 x C_l doubles <= 3 x 64 x H), rect_sums_k's nine sums [9][512], pred_mean_k's two predicted means [2][32]
+    Tens spart, srect, scm;
     float* pre = nullptr;   // [H][W][3] pre-clamp tap
 };
 
@@ -100,11 +103,14 @@ struct PrepPlan {
 
 // One workspace tensor of a plan: where it lives in the plan, its level (H, W >> level of the plan geometry), its channels
 // and flags.  A P8 twin of a C-channel tensor is B * C/8 eight-channel images of width W + 6 (EncPlan::q11 ..).
-enum { TS_P8 = 1, TS_ONE = 2 /* one image */, TS_SPLIT = 4 /* C x the KernelFilter split, absent at 1 */, TS_RES = 8 /* resident pass only */, TS_STREAM = 16 /* streaming pass only */ };
+enum { TS_P8 = 1, TS_ONE = 2 /* one image */, TS_SPLIT = 4 /* C x the KernelFilter split, absent at 1 */, TS_RES = 8 /* resident pass only */, TS_STREAM = 16 /* streaming pass only */,
+       TS_FRAME = 32 /* batched frame-mode scratch: ONE tensor of B rows of C x 64 floats (one row per image), built for frame-mode plans only */,
+       TS_PER_ROW = 64 /* TS_FRAME: C x 64 floats per pixel row of the plan (C x 64 x H per image) */ };
 template <class P> struct TSpec {
     size_t off; int level, C, flags;
     Tens& of(P& p) const { return *(Tens*)((char*)&p + off); }
     void geo(int& B, int& H, int& W, int& C) const {     // B, H, W of the plan, C of the tensor -> the tensor's talloc arguments
+        if (flags & TS_FRAME) { W = C * ((flags & TS_PER_ROW) ? H : 1); H = B; B = 1; C = 64; return; }
         if (flags & TS_ONE) B = 1;
         H >>= level; W >>= level;
         if (flags & TS_P8) { B *= C / 8; W += 6; C = 8; }
@@ -122,6 +128,7 @@ const TSpec<DecPlan> DEC_T[] = {
     {offsetof(DecPlan, a4), 2, 256}, {offsetof(DecPlan, o4), 2, 256}, {offsetof(DecPlan, xs3), 2, 128}, {offsetof(DecPlan, a3), 1, 128}, {offsetof(DecPlan, o3), 1, 128},
     {offsetof(DecPlan, xs2), 1, 64}, {offsetof(DecPlan, a2), 0, 64}, {offsetof(DecPlan, o2), 0, 64}, {offsetof(DecPlan, dpart), 3, 32, TS_SPLIT},
     {offsetof(DecPlan, qa4), 2, 256, TS_P8}, {offsetof(DecPlan, qa3), 1, 128, TS_P8}, {offsetof(DecPlan, qa2), 0, 64, TS_P8},
+    {offsetof(DecPlan, spart), 0, 6, TS_FRAME | TS_PER_ROW}, {offsetof(DecPlan, srect), 0, 9 * 512 / 64, TS_FRAME}, {offsetof(DecPlan, scm), 0, 1, TS_FRAME},
 };
 // levels count from the full-resolution decoder output: relu4_1 (the plan's hh x ww) is level 3
 const TSpec<PrepPlan> PREP_T[] = {
@@ -513,7 +520,7 @@ struct F43LayKey { int EPI, LAY; ConvFn fn; const char* name; AttrFn attr; };
 #define UWS(EPI) {32, 10, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1>}
 #define UWSI(EPI) {32, 10, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1, 1>, &wino_launch<EPI, UPW_NW, 1, 1, 1>}
 const ConvKey WINO_TABLE[] = {
-    WK(E_RELU), WK(E_RELU | E_POOL), WK(E_RELU | E_NORM1), WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WK(E_LRELU),
+    WK(E_RELU), WK(E_RELU | E_POOL), WK(E_RELU | E_NORM1), WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WKI(E_LRELU),      // (E_LRELU per image: filter_down of a batched frame-mode launch without split K)
     WKI(0),     // raw partial sums of a split-K launch
     // KernelFilter 32->512 convs with the folded dynamic filter (+ residual, + AdaIN after Filter3)
     WKI(E_RES), WKI(E_RES | E_NORM2),
@@ -780,10 +787,11 @@ int chan_stats(rrv_handle h, const Tens& t, int mode, float* out) {
     return RRV_OK;
 }
 
+// par_bstride > 0: image b of x normalises with mean / scale / smean / sstd + b * par_bstride (batched frame mode)
 int pointwise(rrv_handle h, const Tens& x, Tens& y, const float* mean, const float* scale, bool div, const Tens* res,
-              int res_mode, const float* smean, const float* sstd, const float* lo = nullptr, const float* hi = nullptr) {
+              int res_mode, const float* smean, const float* sstd, const float* lo = nullptr, const float* hi = nullptr, long par_bstride = 0) {
     PointP p{x.p, y.p, x.B, x.H, x.W, x.C, mean, scale, div ? 1 : 0, res ? res->p : nullptr, res_mode,
-             res ? res->H : 0, res ? res->W : 0, smean, sstd, lo, hi, 1};
+             res ? res->H : 0, res ? res->W : 0, smean, sstd, lo, hi, 1, par_bstride};
     // image rows x segments per row: ~4 float4 per thread, at most 16384 blocks (further rows are strided)
     int rows = x.B * x.H;
     int segs = (x.W * (x.C / 4) + 1023) / 1024;
@@ -1034,11 +1042,13 @@ int kf_split(int H8, int W8) {
     return tiles * 8 <= 320 ? 8 : (tiles * 4 <= 512 ? 4 : (tiles * 2 <= 256 ? 2 : 1));
 }
 
-int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W) {       // complete or empty, as enc_plan
-    if (d.B >= B && d.H == H && d.W == W && d.pre) return RRV_OK;
+// frame: with the batched frame mode's scratch (a plan built without it is rebuilt)
+int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W, bool frame = false) {       // complete or empty, as enc_plan
+    if (d.B >= B && d.H == H && d.W == W && d.pre && (!frame || d.spart.p)) return RRV_OK;
     dec_free(h, d);
     const int split = kf_split(H / 8, W / 8);
     RCHK(plan_talloc(h, d, DEC_T, B, H, W, [&](const TSpec<DecPlan>& s) {
+        if (s.flags & TS_FRAME) return frame ? s.C : 0;
         if (s.flags & TS_P8) return (h->p8 & 2) && p8_fits(H >> s.level, W >> s.level, s.C) ? s.C : 0;
         if (s.flags & TS_SPLIT) return split > 1 ? s.C * split : 0;
         return s.C;
@@ -1372,6 +1382,122 @@ int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* 
     }
     RCHK(run_last(h, o2, 1, Ho, Wo, d_out, d.pre, nullptr));
     if (h->debug) RCHK(debug_verify(h, "transfer (frame mode)"));
+    return RRV_OK;
+}
+
+// ---- batched frame mode: B <= MS_GROUP_MAX frames per launch sequence ----------------------------------------------------
+// frame_mode_forward's chain for B frames at once.  Every frame's statistics, predicted filters and folded KernelFilter weights go
+// to its own state set (h->cur + b: the sets MS_GROUP_MAX * slot .., initialised from style 0's blob), and every per-frame kernel
+// runs over the B images with image b's result in set b or in row b of the plan's scratch (DecPlan::spart ..).  The statistics
+// kernels keep the one-image block partition per image and the convolutions are F(2x2,3x3) (f43_path stays false), so image b
+// gets the bits of frame_mode_forward on that frame alone.  Style 0's blob is only read.
+
+// interior row b of a TS_FRAME scratch tensor (ring layout, B = 1, H = images): contiguous, frame_row_stride floats apart
+float* frame_row(const Tens& t) { return t.p + (size_t)(t.W + 3) * t.C; }
+long frame_row_stride(const Tens& t) { return (long)(t.W + 2) * t.C; }
+
+// per-image statistics of the t.B images of t into norm entry `n` of each image's state set (chan_stats1 per image)
+int chan_stats1_images(rrv_handle h, const Tens& t, const DecPlan& d, int n) {
+    const int nblk = t.H < 512 ? t.H : 512;        // chan_stats1's min(B * H, 512) at B = 1: the same block partition per image
+    if ((size_t)nblk * 6 * t.C > (size_t)d.spart.W * d.spart.C || t.B > d.spart.H) return fail(h, RRV_E_ARG, "chan_stats1_images: scratch too small");
+    double* part = (double*)frame_row(d.spart);
+    const long pbs = frame_row_stride(d.spart) / 2;
+    float* out = h->cur->active + SL.norm[n];
+    StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, part, 0, 0, 1, pbs};
+    stamp(h, &d.spart, t.B);
+    RCHK(launch(h, "chan_stat1", 0, 4.0 * t.B * t.H * t.W * t.C, [&] { hipLaunchKernelGGL(chan_stat1_k, dim3(nblk, t.B), dim3(256), 0, h->stream, sp); }));
+    return launch(h, "chan_stat1_final", 0, 0, [&] {
+        hipLaunchKernelGGL(chan_stat1_final_k, dim3((t.C + 3) / 4, t.B), dim3(256), 0, h->stream, (const double*)part, nblk, t.C, out, pbs, (long)RRV_STATE_FLOATS);
+    });
+}
+
+// B frames ([B][H][W][3] uint8; with pc: [B][src_H][src_W][3], padded on the way in, cropped on the way out) on `slot`
+int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, const PadCrop* pc) {
+    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
+    StyleState& S = h->styles[0];
+    const int Ho = H / 8 * 8, Wo = W / 8 * 8;
+    struct Scope { rrv_handle h; ~Scope() { h->stream = h->streams[0]; h->cur = &h->sets[0]; h->state_images = 0; h->active_src = -1; } } scope{h};
+    h->active_src = -1;                                   // set 0 (slot 0) is overwritten: a later global entry re-activates its state
+    h->stream = h->streams[slot];
+    h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];
+    EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
+    DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
+    RCHK(enc_plan(h, e, B, H, W, true));
+    RCHK(dec_plan(h, d, B, Ho, Wo, true));
+    e.gen = d.gen = ++h->launch_gen;
+    float* st = h->cur->active;                          // image b: st + b * RRV_STATE_FLOATS
+    const long PS = RRV_STATE_FLOATS;
+    RCHK(launch(h, "frame_sets_init", 0, 8.0 * B * RRV_STATE_FLOATS, [&] {
+        hipLaunchKernelGGL(frame_sets_init_k, dim3((RRV_STATE_FLOATS + 255) / 256, B), dim3(256), 0, h->stream, (const float*)S.blob, st, (int)RRV_STATE_FLOATS,
+                           SL.norm[N_DEC1], 512);
+    }));
+    RCHK(run_encoder(h, e, d_in, 0, nullptr, pc, B));
+    Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
+    const int hh = c41.H, ww = c41.W;
+    // Decoder.norm[0] with each frame's statistics
+    RCHK(chan_stats1_images(h, c41, d, N_DEC0));
+    RCHK(pointwise(h, c41, c41, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, PS));
+    Tens f1 = d.f1, f2 = d.f2, f3 = d.f3, xs4 = d.xs4, a4 = d.a4, o4 = d.o4, xs3 = d.xs3, a3 = d.a3, o3 = d.o3, xs2 = d.xs2, a2 = d.a2, o2 = d.o2;
+    for (Tens* t : {&f1, &f2, &f3, &xs4, &a4, &o4, &xs3, &a3, &o3, &xs2, &a2, &o2}) t->B = B;
+    // per image: rect_sums_k's sums and pred_mean_k's means in rows of the scratch, the FC into its state set; one fold launch per
+    // step for all sets (fold_filters nsets), the KernelFilter convs with per-image weights (state_images; one image: the shared ones)
+    float* const Sr = frame_row(d.srect);
+    float* const cm = frame_row(d.scm);
+    const long Sbs = frame_row_stride(d.srect), cbs = frame_row_stride(d.scm);
+    stamp(h, &d.srect, B); stamp(h, &d.scm, B);
+    h->state_images = B > 1 ? B : 0;
+    const Tens* cur = &c41;
+    Tens* fo[3] = {&f1, &f2, &f3};
+    for (int f = 0; f < 3; ++f) {
+        RCHK(launch(h, "rect_sums", 0, 4.0 * B * hh * ww * 512, [&] {
+            hipLaunchKernelGGL(rect_sums_k, dim3(128, 1, B), dim3(256), 0, h->stream, (const float*)cur->p, hh, ww, 512, Sr, Sbs);
+        }));
+        for (int g = 0; g < 2; ++g) {
+            char key[96];
+            snprintf(key, sizeof key, "Decoder.Filter%d.F%d.down_sample.0", f + 1, g + 1);
+            const ConvW& wp = h->conv[key];
+            RCHK(launch(h, "pred_mean", 2.0 * B * 32 * 4608, 0, [&] {
+                hipLaunchKernelGGL(pred_mean_k, dim3(32, B), dim3(256), 0, h->stream, (const float*)wp.raw, (const float*)wp.bias, (const float*)Sr, 1, 512,
+                                   1.0 / ((double)hh * ww), cm + 32 * g, Sbs, cbs);
+            }));
+            RCHK(launch(h, "fc_filter", 2.0 * B * 1024 * 64, 0, [&] {
+                hipLaunchKernelGGL(fc_filter_k, dim3(4, B), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + g], (const float*)h->fc_b[2 * f + g],
+                                   (const float*)(cm + 32 * g), (const float*)(S.smean + (2 * f + g) * 32), st + SL.filt[2 * f + g], (int)cbs, (int)RRV_STATE_FLOATS);
+            }));
+        }
+        RCHK(fold_filters(h, st, f, B));
+        RCHK(filter_down(h, cur, d, f, B));
+        ConvCall u{&d.d, fo[f], &h->cur->fold_up[f], hh, ww}; u.B = B;
+        if (h->state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
+        u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
+        if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }     // identity norm, then * style_std + style_mean
+        RCHK(conv(h, u));
+        cur = fo[f];
+    }
+    h->state_images = 0;
+    struct Blk { const char* name; Tens *xs, *a, *o; int cout, n1, n2, nada, sty; };
+    const Blk blks[3] = {{"slice4", &xs4, &a4, &o4, 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", &xs3, &a3, &o3, 128, N_S3N1, N_S3N2, N_DEC3, 1},
+                         {"slice2", &xs2, &a2, &o2, 64, N_S2N1, N_S2N2, N_DEC4, 0}};
+    const Tens* in = cur;
+    for (int k = 0; k < 3; ++k) {       // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
+        const Blk& b = blks[k];
+        const std::string p = std::string("Decoder.") + b.name;
+        ConvCall c;
+        c = ConvCall{in, b.a, &h->conv[p + ".conv1"], b.a->H, b.a->W}; c.B = B; c.ups = true; c.epi = E_LRELU; c.sc_out = b.xs; RCHK(conv(h, c));
+        RCHK(chan_stats1_images(h, *b.a, d, b.n1));
+        RCHK(pointwise(h, *b.a, *b.a, st + SL.norm[b.n1], st + SL.norm[b.n1] + b.cout, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, PS));
+        c = ConvCall{b.a, b.o, &h->conv[p + ".conv2"], b.a->H, b.a->W}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
+        RCHK(chan_stats1_images(h, *b.o, d, b.n2));
+        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.n2], st + SL.norm[b.n2] + b.cout, false, b.xs, 2, nullptr, nullptr, nullptr, nullptr, PS));
+        RCHK(chan_stats1_images(h, *b.o, d, b.nada));
+        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout,
+                       nullptr, nullptr, PS));
+        in = b.o;
+    }
+    RCHK(run_last(h, o2, B, Ho, Wo, d_out, d.pre, pc));
+    // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
+    for (Tens* t : {&e.c41, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2}) stamp(h, t, B);
+    if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
     return RRV_OK;
 }
 
@@ -2084,9 +2210,37 @@ static int next_device_slot(rrv_handle h) {
 
 static int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
+// Stylization(use_Global=False) for 1..64 frames on `slot` (0 or 1): launch sequences of up to MS_GROUP_MAX frames on its stream
+static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, bool pad) {
+    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
+    RCHK(check_frame(h, KH, KW, "transfer"));
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
+    if (!h->styles[0].prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
+    // a global entry's work in flight reads state set 0, which slot 0's sets include
+    if (h->active_src != -1) RCHK(sync_all(h));
+    const size_t fb = (size_t)H * W * 3, fo = pad ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
+    const PadCrop pc{H, W, 64, 64};
+    if (h->caller_sync) {
+        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
+        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
+    }
+    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
+        const int nb = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
+        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb, nb, KH, KW, d_out + (size_t)b0 * fo, pad ? &pc : nullptr));
+    }
+    if (h->caller_sync) {
+        HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
+        HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
+    }
+    return RRV_OK;
+}
+
 // pad: [B][H][W][3] UNPADDED uint8 frames -> [B][H][W][3] float32 stylized frames: the reference driver's reflect padding
 // (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
-static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, bool pad) {
+// frame: the frame-mode model (use_Global=False, frame_mode_on_slot)
+static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, bool pad, bool frame = false) {
+    if (frame) return frame_mode_on_slot(h, slot, (const uint8_t*)d_in, B, H, W, (float*)d_out, pad);
     RCHK(ensure_active(h));
     if (!pad) return transfer_device(h, slot, (const uint8_t*)d_in, B, H, W, (float*)d_out);
     const PadCrop pc{H, W, 64, 64};
@@ -2107,6 +2261,21 @@ int rrv_transfer_frames_device(rrv_handle h, const void* d_in, int B, int H, int
 
 int rrv_transfer_device(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
     return rrv_transfer_batch_device(h, d_in, 1, H, W, d_out);
+}
+
+// the frame-mode device entries alternate over slots 0 and 1 only: each slot's launches use its own sixteen state sets
+static int next_frame_slot(rrv_handle h) { return next_device_slot(h) & 1; }
+
+int rrv_transfer_frame_mode_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    if (!h || !d_in || !d_out) return RRV_E_ARG;
+    HIPCHK(hipSetDevice(h->dev));
+    return transfer_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, false, true);
+}
+
+int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    if (!h || !d_in || !d_out || H < 1 || W < 1) return RRV_E_ARG;
+    HIPCHK(hipSetDevice(h->dev));
+    return transfer_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, true, true);
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
@@ -2264,7 +2433,8 @@ static int claim_staging(rrv_handle h) {
     h->next_slot = 0;
     return RRV_OK;
 }
-static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out, bool pad_on_device = false) {
+// frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each)
+static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out, bool pad_on_device = false, bool frame_mode = false) {
     if (!h || !frames || !out || B < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
@@ -2273,7 +2443,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     RCHK(check_frame(h, KH, KW, "transfer"));
     const size_t fb = (size_t)H * W * 3;                                   // input bytes per frame
     const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output floats per frame (any input size: 8*(H/8) x 8*(W/8))
-    const int sub = host_sub(B, KH, KW);
+    const int sub = frame_mode ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fo * sizeof(float));
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
@@ -2303,7 +2473,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
-            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, pad_on_device);
+            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, pad_on_device, frame_mode);
             if (rc != RRV_OK) break;
             HIPCHK(hipMemcpyAsync(out_pin ? (void*)out : (void*)st.pin.out, st.dev.out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, cs));
             HIPCHK(hipStreamSynchronize(cs));
@@ -2323,7 +2493,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         float* const h_dst = out_pin ? out + (size_t)k * sub * fo : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
         float* const k_out = zout ? h_dst : st.dev.out;
-        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, pad_on_device);
+        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, pad_on_device, frame_mode);
         if (rc != RRV_OK) break;
         if (!zin) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
@@ -2353,6 +2523,14 @@ int rrv_transfer_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W,
 
 int rrv_transfer_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
     return host_pipeline(h, frames, B, H, W, out, true);
+}
+
+int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
+    return host_pipeline(h, frames, B, H, W, out, false, true);
+}
+
+int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
+    return host_pipeline(h, frames, B, H, W, out, true, true);
 }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----

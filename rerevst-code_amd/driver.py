@@ -216,7 +216,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             return (_encode_jpeg(u8, 95), u8.shape) if inline_video else None
 
         on_device = getattr(model, "transfer_frames", None)      # absent on a model with the reference's surface only
-        fast = on_device is not None and use_global and hi > lo
+        fast = on_device is not None and hi > lo
         gpu_s = 0.0
         if fast:
             # The reference reshapes every frame on its own (generate_real_video.py:152-171) and so accepts a list of mixed

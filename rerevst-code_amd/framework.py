@@ -260,12 +260,18 @@ class Stylization():
         return out
 
     # ===== device-resident entry (what bench.py times) =====
+    # With use_Global=False the batch / frames / device entries run the frame-mode model (rrv_transfer_frame_mode_*): each frame
+    # gets its own statistics, bit-identical to transfer() on that frame alone.
     def transfer_device(self, d_in_ptr, H, W, d_out_ptr):
+        if not self.use_Global:
+            self.transfer_batch_device(d_in_ptr, 1, H, W, d_out_ptr)
+            return
         self._chk(self._lib.rrv_transfer_device(self._h, C.c_void_p(d_in_ptr), H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_batch_device(self, d_in_ptr, B, H, W, d_out_ptr):
         """[B][H][W][3] uint8 in HBM -> [B][H][W][3] float32 in HBM, asynchronous on the library stream."""
-        self._chk(self._lib.rrv_transfer_batch_device(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
+        fn = self._lib.rrv_transfer_batch_device if self.use_Global else self._lib.rrv_transfer_frame_mode_batch_device
+        self._chk(fn(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_batch(self, frames, out=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
@@ -281,7 +287,8 @@ class Stylization():
             out = _outputs.empty(oshape)
         elif out.dtype != np.float32 or out.shape != oshape or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float32 array of shape %r" % (oshape,))
-        self._chk(self._lib.rrv_transfer_batch(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
+        fn = self._lib.rrv_transfer_batch if self.use_Global else self._lib.rrv_transfer_frame_mode_batch
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def transfer_frames(self, frames, out=None):
@@ -298,12 +305,14 @@ class Stylization():
             out = _outputs.empty((B, H, W, 3))
         elif out.dtype != np.float32 or out.shape != (B, H, W, 3) or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((B, H, W, 3),))
-        self._chk(self._lib.rrv_transfer_frames(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
+        fn = self._lib.rrv_transfer_frames if self.use_Global else self._lib.rrv_transfer_frame_mode_frames
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32), asynchronous on the library stream."""
-        self._chk(self._lib.rrv_transfer_frames_device(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
+        fn = self._lib.rrv_transfer_frames_device if self.use_Global else self._lib.rrv_transfer_frame_mode_frames_device
+        self._chk(fn(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def sync(self):
         self._chk(self._lib.rrv_sync(self._h))

@@ -102,7 +102,11 @@ def stylize_video(model, frames, style, rank=0, world=1, broadcast=None, interva
     {frame index: float32 BGR HWC stylized frame cropped back to the input size}.
     """
     n = len(frames)
-    if rank == 0:
+    use_global = getattr(model, "use_Global", True)
+    if not use_global:                           # frame mode: per-frame statistics, no saved state to compute or ship
+        model.prepare_style(style)
+        blob = None
+    elif rank == 0:
         model.prepare_style(style)
         model.clean()
         for i in sample_indices(n, interval):
@@ -111,7 +115,7 @@ def stylize_video(model, frames, style, rank=0, world=1, broadcast=None, interva
         blob = model.get_state()
     else:
         blob = None
-    if world > 1:
+    if world > 1 and use_global:
         blob = broadcast(blob, 0)
         if rank != 0:
             model.set_state(blob)
@@ -120,7 +124,7 @@ def stylize_video(model, frames, style, rank=0, world=1, broadcast=None, interva
     out = {}
     on_device = getattr(model, "transfer_frames", None)     # pad / crop inside the first / last kernel
     same = all(f.shape == frames[lo].shape for f in frames[lo:hi]) if hi > lo else False
-    if on_device is not None and same and getattr(model, "use_Global", True):
+    if on_device is not None and same:
         for c0 in range(lo, hi, chunk):
             idx = list(range(c0, min(hi, c0 + chunk)))
             styled = on_device([frames[i] for i in idx])

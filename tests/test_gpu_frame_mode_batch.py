@@ -1,0 +1,279 @@
+"""Batched frame-mode entries (rrv_transfer_frame_mode_batch / _frames and their _device forms): Stylization(use_Global=False)
+for many frames per call, each with its own statistics.  Frame b of a batch must carry the bits of the one-frame entry on
+that frame alone, in every kernel mode and across the 16-frame launch sequences and host sub-batches."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+from conftest import load_golden, decode_png, assert_pre_close, IMG_ATOL, fixed_kernels
+
+pytestmark = pytest.mark.gpu
+
+RRV_E_ARG, RRV_E_STATE, RRV_E_NOMEM = -1, -4, -5
+STYLE = dict(H=64, W=64, kind="smooth", seed=7)
+
+
+def _fm(pkg, weights):
+    s = pkg.Stylization(weights, cuda=True, use_Global=False)
+    s.prepare_style(pkg.synth_style(**STYLE))
+    return s
+
+
+def _mixed(pkg, n, H, W):
+    """Frames of strongly different content: smooth, noise, near-black, near-white, in turn."""
+    out = []
+    for i in range(n):
+        k = i % 4
+        if k == 0:
+            f = pkg.synth_frame(i, H, W, kind="smooth")
+        elif k == 1:
+            f = pkg.synth_frame(i, H, W, kind="noise")
+        else:
+            base = 3 if k == 2 else 250
+            f = np.clip(base + np.random.default_rng(i).integers(-3, 4, (H, W, 3)), 0, 255).astype(np.uint8)
+        out.append(f)
+    return np.stack(out)
+
+
+def _pad(oracle, f):
+    H, W = f.shape[:2]
+    return oracle.reflect_pad(f, oracle.padded_size(H), oracle.padded_size(W))
+
+
+def test_golden_frame_at_position_two(pkg, weights, oracle):
+    g = load_golden("frame_mode")
+    gold = oracle.reflect_pad(pkg.synth_frame(2, 64, 48, kind="smooth"), 192, 192)
+    others = _mixed(pkg, 4, 192, 192)
+    batch = np.stack([others[2], others[3], gold, others[1], others[0]])
+    s = _fm(pkg, weights)
+    out = s.transfer_batch(batch)
+    assert_pre_close(s.preclamp(192, 192, image=2)[64:128, 64:112], g["pre_crop"])
+    assert np.abs(out[2][64:128, 64:112] - g["out_crop"]).max() <= IMG_ATOL
+    o = oracle.Stylization(weights, use_Global=False)
+    o.prepare_style(pkg.synth_style(**STYLE))
+    for k in (0, 1, 3, 4):
+        assert np.abs(out[k] - o.transfer(batch[k])).max() <= IMG_ATOL, "frame %d" % k
+    s.close()
+
+
+@pytest.mark.parametrize("mode", [None, 2])
+def test_batch_is_bit_identical_to_one_frame_entry(pkg, weights, mode):
+    s = _fm(pkg, weights)
+
+    def check():
+        for H, W in ((192, 192), (136, 200)):
+            frames = _mixed(pkg, 40, H, W)
+            ref = np.stack([s.transfer(f) for f in frames])
+            for B in (1, 3, 16, 17, 40):
+                got = s.transfer_batch(frames[:B])
+                for b in range(B):
+                    np.testing.assert_array_equal(got[b], ref[b], err_msg="%dx%d B=%d frame %d" % (H, W, B, b))
+        big = _mixed(pkg, 2, 640, 640)
+        got = s.transfer_batch(big)
+        for b in range(2):
+            np.testing.assert_array_equal(got[b], s.transfer(big[b]))
+
+    if mode is None:
+        check()
+    else:
+        with fixed_kernels(s, mode=mode):
+            check()
+    s.close()
+
+
+def test_frames_entry_pads_and_crops_like_the_reference(pkg, weights, oracle):
+    s = _fm(pkg, weights)
+    for H, W in ((67, 93), (48, 64)):
+        frames = _mixed(pkg, 3, H, W)
+        got = s.transfer_frames(frames)
+        assert got.shape == (3, H, W, 3)
+        for b in range(3):
+            np.testing.assert_array_equal(got[b], s.transfer(_pad(oracle, frames[b]))[64:64 + H, 64:64 + W])
+    s.close()
+    g, gin = load_golden("real_frame_mode"), load_golden("real_default")
+    tid = int(g["transfer_id"])
+    s = pkg.Stylization(weights, cuda=True, use_Global=False)
+    s.prepare_style(decode_png(gin["style_png"]))
+    ids = [0, tid, 24]
+    raw = np.stack([decode_png(gin["frame%d_png" % i]) for i in ids])
+    got = s.transfer_frames(raw)
+    k = ids.index(tid)
+    out = got[k][:436, :1024]
+    assert np.abs(out[::4, ::4] - g["out_grid"]).max() <= IMG_ATOL
+    assert np.abs(out[186:250, 480:544] - g["out_patch"]).max() <= IMG_ATOL
+    H, W = raw.shape[1:3]
+    for b in range(len(ids)):
+        np.testing.assert_array_equal(got[b], s.transfer(_pad(oracle, raw[b]))[64:64 + H, 64:64 + W])
+    s.close()
+
+
+def test_device_entries(pkg, weights, oracle):
+    torch = pytest.importorskip("torch")
+    s = _fm(pkg, weights)
+    H, W = 136, 200
+    frames = _mixed(pkg, 20, H, W)
+    ref = s.transfer_batch(frames)
+    d_in = torch.from_numpy(frames).cuda()
+    d_out = torch.empty((20, H, W, 3), dtype=torch.float32, device="cuda")
+    s.transfer_batch_device(d_in.data_ptr(), 20, H, W, d_out.data_ptr())
+    s.sync()
+    np.testing.assert_array_equal(d_out.cpu().numpy(), ref)
+    ref_f = s.transfer_frames(frames)
+    s.transfer_frames_device(d_in.data_ptr(), 20, H, W, d_out.data_ptr())
+    s.sync()
+    np.testing.assert_array_equal(d_out.cpu().numpy(), ref_f)
+    s.transfer_device(d_in[3].data_ptr(), H, W, d_out.data_ptr())
+    s.sync()
+    np.testing.assert_array_equal(d_out[0].cpu().numpy(), ref[3])
+    # four calls queued on the caller's stream, one sync
+    stream = torch.cuda.Stream()
+    outs = [torch.empty((5, H, W, 3), dtype=torch.float32, device="cuda") for _ in range(4)]
+    s.set_caller_stream(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        for k in range(4):
+            s.transfer_batch_device(d_in[5 * k].data_ptr(), 5, H, W, outs[k].data_ptr())
+    stream.synchronize()
+    s.set_caller_stream(0, enable=False)
+    for k in range(4):
+        np.testing.assert_array_equal(outs[k].cpu().numpy(), ref[5 * k:5 * k + 5])
+    s.close()
+    # one handle: global, frame mode, global, with no sync in between
+    gs = pkg.Stylization(weights, cuda=True)
+    gs.prepare_style(pkg.synth_style(**STYLE))
+    gs.clean()
+    for i in (0, 4):
+        gs.add(_pad(oracle, pkg.synth_frame(i, 48, 64, kind="smooth")))
+    gs.compute()
+    state = gs.get_state()
+    lib = gs._lib
+    B = 6
+    calls = [(lib.rrv_transfer_batch_device, 0), (lib.rrv_transfer_frame_mode_batch_device, 6), (lib.rrv_transfer_batch_device, 12)]
+    outs = [torch.empty((B, H, W, 3), dtype=torch.float32, device="cuda") for _ in calls]
+    alone = []
+    for (fn, k), o in zip(calls, outs):
+        assert fn(gs._h, C.c_void_p(d_in[k].data_ptr()), B, H, W, C.c_void_p(o.data_ptr())) == 0
+        gs.sync()
+        alone.append(o.cpu().numpy().copy())
+        o.zero_()
+    torch.cuda.synchronize()
+    for (fn, k), o in zip(calls, outs):
+        assert fn(gs._h, C.c_void_p(d_in[k].data_ptr()), B, H, W, C.c_void_p(o.data_ptr())) == 0
+    gs.sync()
+    for a, o in zip(alone, outs):
+        np.testing.assert_array_equal(o.cpu().numpy(), a)
+    np.testing.assert_array_equal(alone[1], ref[6:12])
+    np.testing.assert_array_equal(gs.get_state(), state)
+    gs.close()
+
+
+def test_per_image_statistics_from_the_taps(pkg, weights):
+    s = _fm(pkg, weights)
+    H, W = 136, 200
+    frames = np.stack([pkg.synth_frame(i, H, W, kind="noise" if i % 2 else "smooth") for i in range(16)])
+    s.transfer_batch(frames)
+    taps = {8: (H // 8, W // 8, 512), 17: (H // 2, W // 2, 128), 20: (H, W, 64)}      # c41, a3, a2: normalised in place
+    for b in (0, 7, 15):
+        for index, (h, w, c) in taps.items():
+            t, lay, ch = s.debug_tensor_ex(0, index, H, W, image=b)
+            assert lay == 0 and ch == c
+            x = t.reshape(h + 2, w + 2, c)[1:-1, 1:-1].astype(np.float64).reshape(-1, c)
+            mean, var = x.mean(axis=0), x.var(axis=0)
+            assert np.abs(mean).max() <= 1e-4, "image %d tap %d: mean %.3e" % (b, index, np.abs(mean).max())
+            # normalised variance = v / (v + 1e-8) of the raw variance v: 1 for every channel of ordinary spread, below it only for
+            # nearly constant ones; another image's statistics would scatter it both ways
+            assert var.max() <= 1.0 + 1e-3, "image %d tap %d: variance %.4f" % (b, index, var.max())
+            assert np.median(np.abs(var - 1.0)) <= 1e-4, "image %d tap %d: median |variance - 1| %.3e" % (b, index, np.median(np.abs(var - 1.0)))
+    s.close()
+
+
+def test_errors_and_failed_allocations(pkg, weights):
+    torch = pytest.importorskip("torch")
+    s = pkg.Stylization(weights, cuda=True, use_Global=False)
+    frames = _mixed(pkg, 2, 64, 64)
+    with pytest.raises(pkg.RRVError) as e:
+        s.transfer_batch(frames)
+    assert e.value.code == RRV_E_STATE
+    s.prepare_style(pkg.synth_style(**STYLE))
+    lib = s._lib
+    d_in = torch.zeros((2, 64, 64, 3), dtype=torch.uint8, device="cuda")
+    d_out = torch.zeros((2, 64, 64, 3), dtype=torch.float32, device="cuda")
+    out = np.zeros((2, 64, 64, 3), np.float32)
+    assert lib.rrv_transfer_frame_mode_batch(s._h, frames.ctypes.data_as(C.c_void_p), 0, 64, 64, out.ctypes.data_as(C.c_void_p)) == RRV_E_ARG
+    for B in (0, 65):
+        for fn in (lib.rrv_transfer_frame_mode_batch_device, lib.rrv_transfer_frame_mode_frames_device):
+            assert fn(s._h, C.c_void_p(d_in.data_ptr()), B, 64, 64, C.c_void_p(d_out.data_ptr())) == RRV_E_ARG
+    with pytest.raises(pkg.RRVError) as e:
+        s.transfer_batch(np.zeros((2, 7, 7, 3), np.uint8))
+    assert e.value.code == RRV_E_ARG
+    fresh = _fm(pkg, weights)
+    for H, W in ((72, 88), (80, 96)):
+        f = _mixed(pkg, 3, H, W)
+        ref = fresh.transfer_batch(f)
+        s.debug_fail_alloc(1)
+        with pytest.raises(pkg.RRVError) as e:
+            s.transfer_batch(f)
+        assert e.value.code == RRV_E_NOMEM
+        np.testing.assert_array_equal(s.transfer_batch(f), ref)
+    # a failure at any allocation of the device entry's workspaces leaves nothing half-built
+    H, W = 88, 104
+    f = _mixed(pkg, 3, H, W)
+    ref = fresh.transfer_batch(f)
+    d_in = torch.from_numpy(f).cuda()
+    d_out = torch.zeros((3, H, W, 3), dtype=torch.float32, device="cuda")
+    for nth in (1, 9, 17, 25, 33, 36, 37):
+        s.debug_fail_alloc(nth)
+        rc = lib.rrv_transfer_frame_mode_batch_device(s._h, C.c_void_p(d_in.data_ptr()), 3, H, W, C.c_void_p(d_out.data_ptr()))
+        s.debug_fail_alloc(0)
+        assert rc in (0, RRV_E_NOMEM)
+        s.transfer_batch_device(d_in.data_ptr(), 3, H, W, d_out.data_ptr())
+        s.sync()
+        np.testing.assert_array_equal(d_out.cpu().numpy(), ref)
+        s.set_debug(0)                       # frees the workspaces: the next round builds them again
+    fresh.close()
+    s.close()
+
+
+def test_debug_level_two_keeps_the_bits(pkg, weights):
+    s = _fm(pkg, weights)
+    frames = _mixed(pkg, 3, 136, 200)
+    ref = s.transfer_batch(frames)
+    s.set_debug(2)
+    got = s.transfer_batch(frames)
+    got_f = s.transfer_frames(frames)
+    s.set_debug(0)
+    np.testing.assert_array_equal(got, ref)
+    np.testing.assert_array_equal(got_f, s.transfer_frames(frames))
+    s.close()
+
+
+def test_driver_runs_frame_mode_through_transfer_frames(tmp_path, pkg, weights, oracle):
+    D = importlib.import_module("rerevst-code_amd.driver")
+    src = tmp_path / "in"
+    src.mkdir()
+    frames = [pkg.synth_frame(i, 48, 64, kind="smooth") if i < 3 else pkg.synth_frame(i, 40, 56, kind="noise") for i in range(6)]
+    for i, f in enumerate(frames):
+        D.write_image_bgr(str(src / ("f%02d.png" % i)), f)
+    style = pkg.synth_style(**STYLE)
+    D.write_image_bgr(str(tmp_path / "style.png"), style)
+    s = pkg.Stylization(weights, cuda=True, use_Global=False)
+    calls = {"frames": [], "transfer": 0}
+    tf, tr = s.transfer_frames, s.transfer
+
+    def counted_frames(fs, out=None):
+        calls["frames"].append(len(fs))
+        return tf(fs, out=out)
+
+    def counted_transfer(f, style_weight=None):
+        calls["transfer"] += 1
+        return tr(f, style_weight)
+
+    s.transfer_frames, s.transfer = counted_frames, counted_transfer
+    written = D.stylize_files(s, str(tmp_path / "style.png"), D.list_frames(str(src / "*.png")), str(tmp_path / "out"),
+                              chunk=4, io_threads=2, log=lambda *_: None)
+    assert calls["frames"] == [3, 3] and calls["transfer"] == 0
+    for i, p in enumerate(written):
+        H, W = frames[i].shape[:2]
+        np.testing.assert_array_equal(D.read_image_bgr(p), D.to_uint8(tr(_pad(oracle, frames[i]))[64:64 + H, 64:64 + W]))
+    s.close()
