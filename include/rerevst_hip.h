@@ -228,6 +228,33 @@ int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames_bgr, int B
 int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_f32);
 int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, float* out_bgr);
 
+/* uint8 output: every entry that writes a stylized frame has a _u8 twin with the same arguments, except that the output
+ * is uint8 BGR HWC, the same [.][Ho][Wo][3] elements, one byte each (a quarter of the float32 bytes over PCIe, in
+ * staging and in HBM).  The last kernel computes the float32 value exactly as the float twin does, rounds it half to
+ * even (rintf, as numpy's np.rint) and stores the byte; the value is already clamped to 0..255.  So each twin's output is
+ * identical to to_uint8(float twin's output) = np.clip(np.rint(x), 0, 255).astype(np.uint8) (cv2.imwrite's conversion),
+ * bit for bit, on the same inputs with the same frames per call.  Errors, staging, page-locked buffers, rrv_set_host_io,
+ * tickets and rrv_get_preclamp_image behave as for the float twin; rrv_transfer_wait collects rrv_transfer_async_u8 tickets. */
+int rrv_transfer_u8(rrv_handle h, const uint8_t* frame_bgr, int H, int W, uint8_t* out_bgr);       /* == to_uint8(rrv_transfer) */
+int rrv_transfer_async_u8(rrv_handle h, const uint8_t* frame_bgr, int H, int W, uint8_t* out_bgr, long* ticket);   /* == to_uint8(rrv_transfer_async) */
+int rrv_transfer_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, uint8_t* out_bgr);   /* == to_uint8(rrv_transfer_batch) */
+int rrv_transfer_frames_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, uint8_t* out_bgr);  /* == to_uint8(rrv_transfer_frames) */
+int rrv_transfer_device_u8(rrv_handle h, const void* d_frame_bgr_u8, int H, int W, void* d_out_bgr_u8);      /* == to_uint8(rrv_transfer_device) */
+int rrv_transfer_batch_device_u8(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_u8);   /* == to_uint8(rrv_transfer_batch_device) */
+int rrv_transfer_frames_device_u8(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_u8);  /* == to_uint8(rrv_transfer_frames_device) */
+int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame_bgr, int H, int W, const float* style_weight, int n_styles,
+                          uint8_t* out_bgr);                                                                   /* == to_uint8(rrv_transfer_blend) */
+int rrv_transfer_blend_device_u8(rrv_handle h, const void* d_frame_bgr_u8, int H, int W,
+                                 const float* style_weight, int n_styles, void* d_out_bgr_u8);                /* == to_uint8(rrv_transfer_blend_device) */
+int rrv_transfer_features_u8(rrv_handle h, int feature_id, const float* style_weight, int n_styles, uint8_t* out_bgr);   /* == to_uint8(rrv_transfer_features) */
+int rrv_transfer_features_batch_u8(rrv_handle h, const int* feature_ids, const float* style_weight, int n, int n_styles,
+                                   uint8_t* out_bgr);                                                          /* == to_uint8(rrv_transfer_features_batch) */
+int rrv_transfer_frame_mode_u8(rrv_handle h, const uint8_t* frame_bgr, int H, int W, uint8_t* out_bgr);     /* == to_uint8(rrv_transfer_frame_mode) */
+int rrv_transfer_frame_mode_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, uint8_t* out_bgr);   /* == to_uint8(rrv_transfer_frame_mode_batch) */
+int rrv_transfer_frame_mode_batch_device_u8(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_u8);   /* == to_uint8(rrv_transfer_frame_mode_batch_device) */
+int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, uint8_t* out_bgr);  /* == to_uint8(rrv_transfer_frame_mode_frames) */
+int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_u8);  /* == to_uint8(rrv_transfer_frame_mode_frames_device) */
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

@@ -83,6 +83,14 @@ SYMBOLS = {
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
+# the entries that write a stylized frame; each has a _u8 twin with the same arguments and a uint8 output (its float
+# twin's output rounded half to even on the GPU)
+U8_TWINS = ("rrv_transfer", "rrv_transfer_async", "rrv_transfer_batch", "rrv_transfer_frames", "rrv_transfer_device",
+            "rrv_transfer_batch_device", "rrv_transfer_frames_device", "rrv_transfer_blend", "rrv_transfer_blend_device",
+            "rrv_transfer_features", "rrv_transfer_features_batch", "rrv_transfer_frame_mode", "rrv_transfer_frame_mode_batch",
+            "rrv_transfer_frame_mode_batch_device", "rrv_transfer_frame_mode_frames", "rrv_transfer_frame_mode_frames_device")
+SYMBOLS.update({name + "_u8": SYMBOLS[name] for name in U8_TWINS})
+
 
 def _share_torch_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm wheels bundle their own libamdhip64.so

@@ -7,6 +7,8 @@
 // conv_last_k: conv3x3 64->3 + bias (Decoder.slice1, :341,450) fused with
 //   transform_back_image/tensor2numpy (test/framework.py:39-49): *std+mean, clamp(0,1),
 //   *255, RGB->BGR, HWC float32.  Reads 256 B/pixel, writes 12 (+12) B/pixel.
+//   conv_last_k<true>: the same, then rint (v_rndne_f32: round half to even, as np.rint) and one byte per channel: HWC
+//   uint8, the float form's values quantised on the GPU (cv2.imwrite's conversion).  Writes 3 (+12) B/pixel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -214,7 +216,7 @@ struct LastP {
     int H, W, B;
     const float* w;       // pack_last_k: [blk 2][c 4][lane 64][s 4] MFMA A operands of the 27 x 64 tap-rgb matrix
     const float* bias;    // [4]
-    float* out_img;       // [B][H][W][3] BGR float32 0..255
+    void* out_img;        // [B][H][W][3] BGR: float32 0..255 (conv_last_k<false>) or its rint as uint8 (conv_last_k<true>)
     float* out_pre;       // optional [B][H][W][3] RGB pre-clamp (normalised units), may be null
     int tiles_x, tiles_y;
     // optional on-device crop (generate_real_video.py:167): out_img is [B][out_H][out_W][3] and receives the window
@@ -233,6 +235,9 @@ struct LastP {
 // tile, LDS-bound at 0.38 of the HBM peak); here LDS carries 27 floats per halo pixel once in and once out.
 // Workgroups are persistent (the weight registers are loaded once) and walk the tiles of the window.
 #define LAST_GP 330       /* floats per G plane (324 used); 4 planes = 8 banks on: the four row groups of a wave write disjoint banks */
+// U8: the uint8 store form; everything before the store is the same code in both instantiations (a template kernel, not an
+// inlined body: the float instantiation compiles to the instructions of the non-template kernel it replaced)
+template <bool U8>
 __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     __shared__ __attribute__((aligned(16))) float s_g[27 * LAST_GP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -330,8 +335,18 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f) * 255.f;
             const int cy = p.out_H ? y - p.crop_top : y, cx = p.out_H ? xx - p.crop_left : xx;
-            // RGB -> BGR; a lane stores its pixel's 12 bytes, a row of the tile leaves as one 192-byte burst
-            if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) *(f32x3*)(p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3) = f32x3{im[2], im[1], im[0]};
+            // RGB -> BGR; a lane stores its pixel's 12 bytes, a row of the tile leaves as one 192-byte burst (uint8: 3 bytes as one
+            // short + one byte store, a 48-byte row; rows are OW * 3 bytes and in general not dword aligned — measured no slower
+            // than the float form, into HBM and into page-locked host memory: profiles/u8_output_rate.json)
+            if constexpr (U8) {
+                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
+                    uint8_t* q = (uint8_t*)p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) q[c] = (uint8_t)__builtin_rintf(im[2 - c]);      // im is in [0, 255] and never NaN
+                }
+            } else {
+                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) *(f32x3*)((float*)p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3) = f32x3{im[2], im[1], im[0]};
+            }
         }
     }
 }

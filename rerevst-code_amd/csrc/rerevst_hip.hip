@@ -221,13 +221,13 @@ struct rrv_ctx {
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
     // Four sets and two dedicated copy streams: the compute streams never wait behind a DMA of their own stream.
-    // Each set holds a device pair and a page-locked host pair (stage_reserve), in bytes of frames / floats of output.
-    struct StageBufs { uint8_t* in = nullptr; float* out = nullptr; size_t in_cap = 0, out_cap = 0; };
+    // Each set holds a device pair and a page-locked host pair (stage_reserve), in bytes of frames / bytes of output.
+    struct StageBufs { uint8_t* in = nullptr; void* out = nullptr; size_t in_cap = 0, out_cap = 0; };
     struct HostStage { StageBufs dev, pin; hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr; } hstage[4];
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     // rrv_transfer_async: ticket t lives in staging set t % 4 until rrv_transfer_wait(t) (or a later submission that needs
     // its set) retires it; `out` / `out_bytes` = where a pageable caller buffer still has to be filled from pin_out
-    struct Ticket { long id = -1; float* out = nullptr; size_t out_bytes = 0; bool open = false; } tickets[4];
+    struct Ticket { long id = -1; void* out = nullptr; size_t out_bytes = 0; bool open = false; } tickets[4];
     long next_ticket = 0;
     int grid_share = 1;               // rrv_set_grid_share: persistent grids use 1/grid_share of the CUs
     int f43_mode = 1;                 // rrv_set_f43 / RRV_F43: layers with an F(4x4,3x3) pack run on conv_f43_k — 0 never, 1 where the launch has enough work items for it to win (use_f43), 2 always
@@ -981,6 +981,14 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     return RRV_OK;
 }
 
+// Format of a stylized frame: OUT_F32 = float32 BGR in 0..255 (tensor2numpy), OUT_U8 = the same values rounded half to even
+// on the GPU (conv_last_k<true>: cv2.imwrite's / driver.to_uint8's conversion) — the rrv_*_u8 entries.  Elements per frame are
+// the same; only their size differs.
+enum OutFmt { OUT_F32, OUT_U8 };
+inline size_t out_elem(OutFmt f) { return f == OUT_U8 ? 1 : sizeof(float); }
+inline void* out_at(void* p, size_t elems, OutFmt f) { return (char*)p + elems * out_elem(f); }
+inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
+
 // grow-only device buffer of at least n elements (h->d_u8, h->d_outf); empty after a failed allocation
 template <class T>
 int ensure_dev(rrv_handle h, T*& p, size_t& cap, size_t n) {
@@ -994,18 +1002,18 @@ int ensure_dev(rrv_handle h, T*& p, size_t& cap, size_t n) {
 
 // Staging buffers of the host entries (rrv_ctx::hstage): one pair on the device, one page-locked on the host.
 void stage_free(rrv_ctx::StageBufs& b, bool pinned) {
-    for (void* p : {(void*)b.in, (void*)b.out})
+    for (void* p : {(void*)b.in, b.out})
         if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
     b = rrv_ctx::StageBufs{};
 }
-// Set `set` grows (never shrinks) to at least in_bytes of frames and out_floats of output; 0 = that buffer is not used.
-// The caller makes sure nothing in flight uses the set.  The capacities are recorded only once both buffers exist: a
-// failed allocation leaves the pair empty.
-int stage_reserve(rrv_handle h, int set, size_t in_bytes, size_t out_floats, bool pinned) {
+// Set `set` grows (never shrinks) to at least in_bytes of frames and out_bytes of output (float32 or uint8 frames); 0 = that
+// buffer is not used.  The caller makes sure nothing in flight uses the set.  The capacities are recorded only once both
+// buffers exist: a failed allocation leaves the pair empty.
+int stage_reserve(rrv_handle h, int set, size_t in_bytes, size_t out_bytes, bool pinned) {
     rrv_ctx::StageBufs& b = pinned ? h->hstage[set].pin : h->hstage[set].dev;
-    if (b.in_cap >= in_bytes && b.out_cap >= out_floats) return RRV_OK;
+    if (b.in_cap >= in_bytes && b.out_cap >= out_bytes) return RRV_OK;
     in_bytes = std::max(in_bytes, b.in_cap);
-    out_floats = std::max(out_floats, b.out_cap);
+    out_bytes = std::max(out_bytes, b.out_cap);
     stage_free(b, pinned);
     auto get = [&](void** p, size_t bytes) -> int {      // device memory through dmalloc (rrv_debug_fail_alloc counts it)
         if (!bytes) return RRV_OK;
@@ -1016,9 +1024,9 @@ int stage_reserve(rrv_handle h, int set, size_t in_bytes, size_t out_floats, boo
         return fail(h, RRV_E_NOMEM, "staging: out of page-locked host memory");
     };
     int rc = get((void**)&b.in, in_bytes);
-    if (rc == RRV_OK) rc = get((void**)&b.out, out_floats * sizeof(float));
+    if (rc == RRV_OK) rc = get(&b.out, out_bytes);
     if (rc != RRV_OK) { stage_free(b, pinned); return rc; }
-    b.in_cap = in_bytes; b.out_cap = out_floats;
+    b.in_cap = in_bytes; b.out_cap = out_bytes;
     return RRV_OK;
 }
 
@@ -1106,21 +1114,21 @@ int resblock_frame(rrv_handle h, int B, const char* blk, const Tens& in, Tens& x
 }
 
 // Decoder.slice1 + transform_back_image (conv_last_k) on a normalised slice2 output
-int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, float* d_out, float* pre, const PadCrop* pc, const Win* wl = nullptr) {
+int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
-    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + 12.0) * B * H * W, [&] {
+    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + 3.0 * out_elem(fmt)) * B * H * W, [&] {
         const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * B), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
-        hipLaunchKernelGGL(conv_last_k, dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
+        hipLaunchKernelGGL(fmt == OUT_U8 ? conv_last_k<true> : conv_last_k<false>, dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
 }
 
 // feat != nullptr: skip the encoder and start from a cached raw relu4_1 feature (ring layout, [1,H/8,W/8,512])
 // feats != nullptr (with h->state_images == B): one cached feature per image, each normalised with ITS state set
 // slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
-int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, const float* feat = nullptr,
+int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, const float* feat = nullptr,
                     const PadCrop* pc = nullptr, const float* const* feats = nullptr) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     // Any frame size, as the reference: the three 2x2 max pools floor (H, W) to (H/8, W/8) and the decoder returns
@@ -1194,7 +1202,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         wa = grow(wo, 1);          // slice2.conv1 output (and, halved, the shortcut) feeding that
     }
     RCHK(resblock_frame(h, B, "slice2", d.o3, d.xs2, d.a2, d.o2, N_S2N1, N_S2N2, N_DEC4, 0, roi ? &wa : nullptr, roi ? &wo : nullptr, &d.qa2));
-    RCHK(run_last(h, d.o2, B, Ho, Wo, d_out, d.pre, pc, roi ? &wl : nullptr));
+    RCHK(run_last(h, d.o2, B, Ho, Wo, d_out, fmt, d.pre, pc, roi ? &wl : nullptr));
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
@@ -1314,7 +1322,7 @@ int chan_stats1(rrv_handle h, const Tens& t, float* out) {
     });
 }
 
-int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* d_out) {
+int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, void* d_out, OutFmt fmt) {
     StyleState& S = h->styles[0];
     float* st = S.blob;
     h->stream = h->streams[0];
@@ -1380,7 +1388,7 @@ int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, float* 
         RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout));
         in = b.o;
     }
-    RCHK(run_last(h, o2, 1, Ho, Wo, d_out, d.pre, nullptr));
+    RCHK(run_last(h, o2, 1, Ho, Wo, d_out, fmt, d.pre, nullptr));
     if (h->debug) RCHK(debug_verify(h, "transfer (frame mode)"));
     return RRV_OK;
 }
@@ -1412,7 +1420,7 @@ int chan_stats1_images(rrv_handle h, const Tens& t, const DecPlan& d, int n) {
 }
 
 // B frames ([B][H][W][3] uint8; with pc: [B][src_H][src_W][3], padded on the way in, cropped on the way out) on `slot`
-int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, const PadCrop* pc) {
+int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, const PadCrop* pc) {
     if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
     StyleState& S = h->styles[0];
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
@@ -1494,7 +1502,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
                        nullptr, nullptr, PS));
         in = b.o;
     }
-    RCHK(run_last(h, o2, B, Ho, Wo, d_out, d.pre, pc));
+    RCHK(run_last(h, o2, B, Ho, Wo, d_out, fmt, d.pre, pc));
     // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
     for (Tens* t : {&e.c41, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2}) stamp(h, t, B);
     if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
@@ -2211,7 +2219,7 @@ static int next_device_slot(rrv_handle h) {
 static int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
 // Stylization(use_Global=False) for 1..64 frames on `slot` (0 or 1): launch sequences of up to MS_GROUP_MAX frames on its stream
-static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, float* d_out, bool pad) {
+static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
     RCHK(check_frame(h, KH, KW, "transfer"));
@@ -2227,7 +2235,7 @@ static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B
     }
     for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
         const int nb = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
-        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb, nb, KH, KW, d_out + (size_t)b0 * fo, pad ? &pc : nullptr));
+        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb, nb, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
     }
     if (h->caller_sync) {
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
@@ -2239,43 +2247,57 @@ static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B
 // pad: [B][H][W][3] UNPADDED uint8 frames -> [B][H][W][3] float32 stylized frames: the reference driver's reflect padding
 // (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
 // frame: the frame-mode model (use_Global=False, frame_mode_on_slot)
-static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, bool pad, bool frame = false) {
-    if (frame) return frame_mode_on_slot(h, slot, (const uint8_t*)d_in, B, H, W, (float*)d_out, pad);
+static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad, bool frame = false) {
+    if (frame) return frame_mode_on_slot(h, slot, (const uint8_t*)d_in, B, H, W, d_out, fmt, pad);
     RCHK(ensure_active(h));
-    if (!pad) return transfer_device(h, slot, (const uint8_t*)d_in, B, H, W, (float*)d_out);
+    if (!pad) return transfer_device(h, slot, (const uint8_t*)d_in, B, H, W, d_out, fmt);
     const PadCrop pc{H, W, 64, 64};
-    return transfer_device(h, slot, (const uint8_t*)d_in, B, padded_size(H), padded_size(W), (float*)d_out, nullptr, &pc);
-}
-
-int rrv_transfer_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    if (!h || !d_in || !d_out) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    return transfer_on_slot(h, next_device_slot(h), d_in, B, H, W, d_out, false);
-}
-
-int rrv_transfer_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    if (!h || !d_in || !d_out || H < 1 || W < 1) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    return transfer_on_slot(h, next_device_slot(h), d_in, B, H, W, d_out, true);
-}
-
-int rrv_transfer_device(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
-    return rrv_transfer_batch_device(h, d_in, 1, H, W, d_out);
+    return transfer_device(h, slot, (const uint8_t*)d_in, B, padded_size(H), padded_size(W), d_out, fmt, nullptr, &pc);
 }
 
 // the frame-mode device entries alternate over slots 0 and 1 only: each slot's launches use its own sixteen state sets
 static int next_frame_slot(rrv_handle h) { return next_device_slot(h) & 1; }
 
-int rrv_transfer_frame_mode_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    if (!h || !d_in || !d_out) return RRV_E_ARG;
+// the device entries (float32 and _u8 forms): pad = the _frames geometry, frame = the frame-mode model
+static int device_entry(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad, bool frame) {
+    if (!h || !d_in || !d_out || (pad && (H < 1 || W < 1))) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
-    return transfer_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, false, true);
+    return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
+}
+
+int rrv_transfer_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, false, false);
+}
+int rrv_transfer_batch_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, false, false);
+}
+
+int rrv_transfer_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, true, false);
+}
+int rrv_transfer_frames_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, true, false);
+}
+
+int rrv_transfer_device(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
+    return device_entry(h, d_in, 1, H, W, d_out, OUT_F32, false, false);
+}
+int rrv_transfer_device_u8(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
+    return device_entry(h, d_in, 1, H, W, d_out, OUT_U8, false, false);
+}
+
+int rrv_transfer_frame_mode_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, false, true);
+}
+int rrv_transfer_frame_mode_batch_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, false, true);
 }
 
 int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    if (!h || !d_in || !d_out || H < 1 || W < 1) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    return transfer_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, true, true);
+    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, true, true);
+}
+int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
+    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, true, true);
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
@@ -2294,30 +2316,42 @@ static int blend_into_current(rrv_handle h, const float* wts, int ns) {
 }
 
 // The serialised entries (one shared state set) run on slot 0; the next alternating call starts there.
-int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
+static int blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out, OutFmt fmt) {
     if (!h || !d_in || !d_out || !wts || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     h->next_slot = 0;
     RCHK(blend_into_current(h, wts, ns));
-    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, (float*)d_out);
+    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, d_out, fmt);
+}
+int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
+    return blend_device(h, d_in, H, W, wts, ns, d_out, OUT_F32);
+}
+int rrv_transfer_blend_device_u8(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
+    return blend_device(h, d_in, H, W, wts, ns, d_out, OUT_U8);
 }
 
 // host-buffer form: H2D, the device entry, D2H
-int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
+static int blend_host(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, void* out, OutFmt fmt) {
     if (!h || !frame || !out || !wts) return RRV_E_ARG;
     RCHK(check_frame(h, H, W, "transfer"));
     HIPCHK(hipSetDevice(h->dev));
     const size_t n = (size_t)H * W * 3;                                  // input bytes
-    const size_t no = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;             // output floats: the stylized frame is 8*(H/8) x 8*(W/8)
+    const size_t no = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;             // output elements: the stylized frame is 8*(H/8) x 8*(W/8)
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, n));
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, no));
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(no, fmt)));
     RCHK(sync_all(h));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, n, hipMemcpyHostToDevice, h->streams[0]));
-    RCHK(rrv_transfer_blend_device(h, h->d_u8, H, W, wts, ns, h->d_outf));
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, no * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
+    RCHK(blend_device(h, h->d_u8, H, W, wts, ns, h->d_outf, fmt));
+    HIPCHK(hipMemcpyAsync(out, h->d_outf, no * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
+}
+int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
+    return blend_host(h, frame, H, W, wts, ns, out, OUT_F32);
+}
+int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, uint8_t* out) {
+    return blend_host(h, frame, H, W, wts, ns, out, OUT_U8);
 }
 
 // B frames in sub-batches of up to 8 through four staging sets.  Three engines run concurrently: the H2D copy of
@@ -2433,8 +2467,8 @@ static int claim_staging(rrv_handle h) {
     h->next_slot = 0;
     return RRV_OK;
 }
-// frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each)
-static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out, bool pad_on_device = false, bool frame_mode = false) {
+// frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each); fmt: float32 or uint8 `out`
+static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, void* out, OutFmt fmt, bool pad_on_device = false, bool frame_mode = false) {
     if (!h || !frames || !out || B < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
@@ -2442,22 +2476,24 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     const int KH = pad_on_device ? padded_size(H) : H, KW = pad_on_device ? padded_size(W) : W;
     RCHK(check_frame(h, KH, KW, "transfer"));
     const size_t fb = (size_t)H * W * 3;                                   // input bytes per frame
-    const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output floats per frame (any input size: 8*(H/8) x 8*(W/8))
+    const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output elements per frame (any input size: 8*(H/8) x 8*(W/8))
+    const size_t fob = fo * out_elem(fmt);                                  // ... and their bytes
+    char* const outc = (char*)out;
     const int sub = frame_mode ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
-    const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fo * sizeof(float));
+    const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
     const bool zin = h->host_io == 1 || h->host_io == 2, zout = h->host_io == 1 || h->host_io == 3;
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
-        RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fo, false));
-        RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fo, true));
+        RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
+        RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));
     }
     auto count = [&](int k) { return (k + 1) * sub <= B ? sub : B - k * sub; };
     auto drain = [&](int k) -> int {       // sub-batch k delivered (its staging set is free again)
         auto& st = h->hstage[k % HOST_SETS];
         HIPCHK(hipEventSynchronize(st.out_done));
-        if (!out_pin) host_copy(out + (size_t)k * sub * fo, st.pin.out, (size_t)count(k) * fo * sizeof(float));
+        if (!out_pin) host_copy(outc + (size_t)k * sub * fob, st.pin.out, (size_t)count(k) * fob);
         return RRV_OK;
     };
     int rc = RRV_OK;
@@ -2473,11 +2509,11 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
-            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, pad_on_device, frame_mode);
+            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, fmt, pad_on_device, frame_mode);
             if (rc != RRV_OK) break;
-            HIPCHK(hipMemcpyAsync(out_pin ? (void*)out : (void*)st.pin.out, st.dev.out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(out_pin ? out : st.pin.out, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, cs));
             HIPCHK(hipStreamSynchronize(cs));
-            if (!out_pin) host_copy(out, st.pin.out, (size_t)nb * fo * sizeof(float));
+            if (!out_pin) host_copy(out, st.pin.out, (size_t)nb * fob);
             return RRV_OK;
         }
         // zero copy per direction (rrv_set_host_io: 1 both, 2 input only, 3 output only): the first kernel reads the page-locked
@@ -2490,16 +2526,16 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
             HIPCHK(hipStreamWaitEvent(cs, st.in_done, 0));
             k_in = st.dev.in;
         }
-        float* const h_dst = out_pin ? out + (size_t)k * sub * fo : st.pin.out;
+        void* const h_dst = out_pin ? outc + (size_t)k * sub * fob : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
-        float* const k_out = zout ? h_dst : st.dev.out;
-        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, pad_on_device, frame_mode);
+        void* const k_out = zout ? h_dst : st.dev.out;
+        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, fmt, pad_on_device, frame_mode);
         if (rc != RRV_OK) break;
         if (!zin) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
         if (zin) HIPCHK(hipEventRecord(st.k_done, cs));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fo * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
+        HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
     }
     if (rc != RRV_OK) { (void)sync_all(h); return rc; }
@@ -2514,23 +2550,38 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
 }
 
 int rrv_transfer(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
-    return host_pipeline(h, frame, 1, H, W, out);
+    return host_pipeline(h, frame, 1, H, W, out, OUT_F32);
+}
+int rrv_transfer_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frame, 1, H, W, out, OUT_U8);
 }
 
 int rrv_transfer_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out);
+    return host_pipeline(h, frames, B, H, W, out, OUT_F32);
+}
+int rrv_transfer_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frames, B, H, W, out, OUT_U8);
 }
 
 int rrv_transfer_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, true);
+    return host_pipeline(h, frames, B, H, W, out, OUT_F32, true);
+}
+int rrv_transfer_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frames, B, H, W, out, OUT_U8, true);
 }
 
 int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, false, true);
+    return host_pipeline(h, frames, B, H, W, out, OUT_F32, false, true);
+}
+int rrv_transfer_frame_mode_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frames, B, H, W, out, OUT_U8, false, true);
 }
 
 int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, true, true);
+    return host_pipeline(h, frames, B, H, W, out, OUT_F32, true, true);
+}
+int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frames, B, H, W, out, OUT_U8, true, true);
 }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----
@@ -2549,16 +2600,16 @@ static int retire_ticket(rrv_handle h, int set) {
     return RRV_OK;
 }
 
-int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* out, long* ticket) {
+static int transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, void* out, OutFmt fmt, long* ticket) {
     if (!h || !frame || !out || !ticket) return RRV_E_ARG;
     RCHK(check_frame(h, H, W, "transfer"));
     HIPCHK(hipSetDevice(h->dev));
-    const size_t fb = (size_t)H * W * 3, fo = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
+    const size_t fb = (size_t)H * W * 3, fo = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3 * out_elem(fmt);     // input / output bytes
     const long id = h->next_ticket;
     const int set = (int)(id % HOST_SETS);
     auto& st = h->hstage[set];
     RCHK(retire_ticket(h, set));                                   // the set's previous ticket (four submissions ago)
-    const bool in_pin = is_pinned(frame, fb), out_pin = is_pinned(out, fo * sizeof(float));
+    const bool in_pin = is_pinned(frame, fb), out_pin = is_pinned(out, fo);
     // this set's staging (nothing of it is in flight any more); the last kernel writes the output to page-locked memory itself
     RCHK(stage_reserve(h, set, in_pin ? 0 : fb, out_pin ? 0 : fo, true));
     RCHK(stage_reserve(h, set, fb, 0, false));
@@ -2587,7 +2638,7 @@ int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* 
     RCHK(ensure_active(h));
     HIPCHK(hipMemcpyAsync(st.dev.in, src, fb, hipMemcpyHostToDevice, cs));
     HIPCHK(hipEventRecord(st.in_done, cs));      // the frame has left the caller's buffer (waited for below when the copy reads it directly)
-    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out);
+    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out, fmt);
     // Contract (include/rerevst_hip.h): `frame` may be reused as soon as the call returns.  A pageable frame was copied to
     // staging above; a page-locked one is the DIRECT source of the asynchronous H2D copy, so wait for that copy (queued
     // first on an idle stream: finished long before the launches above were) — also on the error path.
@@ -2595,10 +2646,16 @@ int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* 
     if (rc0 != RRV_OK) return rc0;
     HIPCHK(hipEventRecord(st.out_done, cs));
     auto& tk0 = h->tickets[set];
-    tk0.id = id; tk0.out = out_pin ? nullptr : out; tk0.out_bytes = fo * sizeof(float); tk0.open = true;
+    tk0.id = id; tk0.out = out_pin ? nullptr : out; tk0.out_bytes = fo; tk0.open = true;
     h->next_ticket = id + 1;
     *ticket = id;
     return RRV_OK;
+}
+int rrv_transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, float* out, long* ticket) {
+    return transfer_async(h, frame, H, W, out, OUT_F32, ticket);
+}
+int rrv_transfer_async_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out, long* ticket) {
+    return transfer_async(h, frame, H, W, out, OUT_U8, ticket);
 }
 
 int rrv_transfer_wait(rrv_handle h, long ticket) {
@@ -2781,7 +2838,7 @@ int rrv_add_patch(rrv_handle h, int feature_id) {
     return RRV_OK;
 }
 
-int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, float* out) {
+static int transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, void* out, OutFmt fmt) {
     if (!h || !wts || !out || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
     if (feature_id < 0 || feature_id >= (int)h->features.size() || !(h->features[feature_id].p || h->features[feature_id].u8)) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
@@ -2790,11 +2847,17 @@ int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns
     const rrv_ctx::Feature& ft = h->features[feature_id];
     RCHK(blend_into_current(h, wts, ns));
     const size_t n = (size_t)(ft.H / 8 * 8) * (ft.W / 8 * 8) * 3;
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, n));
-    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
+    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, fmt, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
+    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
+}
+int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, float* out) {
+    return transfer_features(h, feature_id, wts, ns, out, OUT_F32);
+}
+int rrv_transfer_features_u8(rrv_handle h, int feature_id, const float* wts, int ns, uint8_t* out) {
+    return transfer_features(h, feature_id, wts, ns, out, OUT_U8);
 }
 
 // n cached features, one weight vector each ([n][ns]), in ONE call.  Frames run in GROUPS of up to sixteen per launch
@@ -2803,7 +2866,7 @@ int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns
 // and consecutive groups alternate over two (stream, workspace, sixteen state sets): group k+1's blends, folds and
 // decoder overlap group k's D2H copy.  With a fixed kernel mode a frame's arithmetic does not depend on its group
 // (bit-identical to one frame per call); the default mode chooses the kernels by the group's frames.  Features beyond the cache cap (kept as pixels) run alone through the encoder + decoder entry.
-int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, float* out) {
+static int transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, void* out, OutFmt fmt) {
     if (!h || !ids || !wts || !out || n < 1 || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     for (int i = 0; i < n; ++i)
@@ -2814,8 +2877,9 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
     for (int i = 1; i < n; ++i)
         if (h->features[ids[i]].H != H || h->features[ids[i]].W != W) return fail(h, RRV_E_ARG, "transfer: features of one call must share their size");
     RCHK(claim_staging(h));
-    const size_t npx = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
-    const bool out_pin = is_pinned(out, (size_t)n * npx * sizeof(float));
+    const size_t npx = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3 * out_elem(fmt);      // output bytes per frame
+    char* const outc = (char*)out;
+    const bool out_pin = is_pinned(out, (size_t)n * npx);
     // Frames per launch sequence (rrv_set_multistyle_group; default: the host entries' ~6.6 Mpixel per launch — 4 at 1152 x 1152,
     // 16 at 640 x 640 and below).  Measured with four styles (conv_f43_k with per-image parameters, round 5): 1152 x 1152
     // 371 / 382 / 381 frames/s for 1 / 2 / 4; 640 x 640 941 / 1070 / 1167; 384 x 384 1750 / 2163 / 2590.
@@ -2844,7 +2908,7 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
     auto drain = [&](int k) -> int {
         auto& st = h->hstage[k % nslots];
         HIPCHK(hipEventSynchronize(st.out_done));
-        if (!out_pin) host_copy(out + (size_t)groups[k].first * npx, st.pin.out, (size_t)groups[k].count * npx * sizeof(float));
+        if (!out_pin) host_copy(outc + (size_t)groups[k].first * npx, st.pin.out, (size_t)groups[k].count * npx);
         return RRV_OK;
     };
     for (int k = 0; k < ngroups; ++k) {
@@ -2872,23 +2936,29 @@ int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, 
         }
         h->active_src = -2;
         if (fp[0] && cnt == 1) {       // one frame per launch: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, fp[0]));
+            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, fmt, fp[0]));
         } else if (fp[0]) {
             h->state_images = cnt;
-            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, nullptr, nullptr, fp);
+            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, fmt, nullptr, nullptr, fp);
             h->state_images = 0;
             RCHK(rc);
         } else {
-            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, nullptr));      // re-encode the pixels
+            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, fmt, nullptr));      // re-encode the pixels
         }
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(out_pin ? (void*)(out + (size_t)first * npx) : (void*)st.pin.out, st.dev.out, (size_t)cnt * npx * sizeof(float), hipMemcpyDeviceToHost, h->copy_out));
+        HIPCHK(hipMemcpyAsync(out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out, st.dev.out, (size_t)cnt * npx, hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
     }
     if (out_pin) HIPCHK(hipStreamSynchronize(h->copy_out));
     else for (int k = (ngroups - nslots < 0 ? 0 : ngroups - nslots); k < ngroups; ++k) RCHK(drain(k));
     return RRV_OK;
+}
+int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, float* out) {
+    return transfer_features_batch(h, ids, wts, n, ns, out, OUT_F32);
+}
+int rrv_transfer_features_batch_u8(rrv_handle h, const int* ids, const float* wts, int n, int ns, uint8_t* out) {
+    return transfer_features_batch(h, ids, wts, n, ns, out, OUT_U8);
 }
 
 int rrv_release_features(rrv_handle h) {
@@ -2906,7 +2976,7 @@ int rrv_release_features(rrv_handle h) {
 // Stylization(use_Global=False).transfer (test/framework.py:106-118 with test/style_network_frame.py):
 // per-frame InstanceNorm statistics and per-frame filter prediction.  Implemented as the preparation
 // frame_mode_forward above.
-int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
+static int transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, void* out, OutFmt fmt) {
     if (!h || !frame || !out) return RRV_E_ARG;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     RCHK(check_frame(h, H, W, "transfer"));
@@ -2918,11 +2988,17 @@ int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, fl
     const size_t n = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;       // the stylized frame is 8*(H/8) x 8*(W/8)
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, nin));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, nin, hipMemcpyHostToDevice, h->stream));
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, n));
-    RCHK(frame_mode_forward(h, h->d_u8, H, W, h->d_outf));
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * sizeof(float), hipMemcpyDeviceToHost, h->streams[0]));
+    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
+    RCHK(frame_mode_forward(h, h->d_u8, H, W, h->d_outf, fmt));
+    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
+}
+int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
+    return transfer_frame_mode(h, frame, H, W, out, OUT_F32);
+}
+int rrv_transfer_frame_mode_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
+    return transfer_frame_mode(h, frame, H, W, out, OUT_U8);
 }
 
 int rrv_get_preclamp_image(rrv_handle h, float* out, int H, int W, int b) {

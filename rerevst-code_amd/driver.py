@@ -50,6 +50,12 @@ def to_uint8(img):
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
 
 
+def uint8_output(model):
+    """Whether `model`'s transfer entries take dtype=np.uint8 / a uint8 `out` (Stylization.uint8_output): the frame as
+    to_uint8 would make it, computed on the GPU.  A model with only the reference's surface does not."""
+    return getattr(model, "uint8_output", False) is True
+
+
 def write_image_bgr(path, img):
     """Write a BGR image (uint8, or float in 0..255) as cv2.imwrite(path, img) would; format from the extension."""
     rgb = np.ascontiguousarray(to_uint8(img)[:, :, ::-1])
@@ -210,13 +216,16 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                         writer = MJPGWriter(video_path, fps, shape[1], shape[0])
                     writer.write_jpeg(data, shape)
 
-        def save(path, img):                     # worker: float -> uint8 (cv2.imwrite's saturation), PNG / JPEG by extension
+        def save(path, img):                     # worker: float -> uint8 (cv2.imwrite's saturation; uint8 frames pass as they are), PNG / JPEG by extension
             u8 = to_uint8(img)
             write_image_bgr(path, u8)
             return (_encode_jpeg(u8, 95), u8.shape) if inline_video else None
 
         on_device = getattr(model, "transfer_frames", None)      # absent on a model with the reference's surface only
         fast = on_device is not None and hi > lo
+        # a model that offers uint8 output quantises on the GPU (== to_uint8 of its float output): uint8 output buffers, a
+        # quarter of the bytes over PCIe and in page-locked memory, nothing left for the encode workers to convert
+        out_dtype = np.uint8 if uint8_output(model) else np.float32
         gpu_s = 0.0
         if fast:
             # The reference reshapes every frame on its own (generate_real_video.py:152-171) and so accepts a list of mixed
@@ -234,7 +243,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     chunks.append([i])
             biggest = max(h * w for h, w in sizes)
             in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
-            out_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.float32) for _ in range(nbuf)]
+            out_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), out_dtype) for _ in range(nbuf)]
 
             def views(k):                        # chunk k's input / output slots: [frames][H][W][3] views of buffer set k % nbuf
                 (H, W), m = sizes[chunks[k][0] - lo], len(chunks[k])
@@ -356,6 +365,7 @@ def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_pat
             model.add_patch(feats[i])
         model.compute_norm()
         many = getattr(model, "transfer_many", None)          # absent on a model with the reference's surface only
+        many_kw = {"dtype": np.uint8} if many is not None and uint8_output(model) else {}     # quantised on the GPU (== to_uint8)
         written, writer, pending = [], None, deque()
 
         def save(path, img):
@@ -374,7 +384,7 @@ def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_pat
         for c0 in range(0, n, chunk):
             idx = list(range(c0, min(n, c0 + chunk)))
             wts = [video.ramp_weights(i, n, S) for i in idx]
-            styled = many([feats[i] for i in idx], wts) if many is not None else [model.transfer(feats[i], w) for i, w in zip(idx, wts)]
+            styled = many([feats[i] for i in idx], wts, **many_kw) if many is not None else [model.transfer(feats[i], w) for i, w in zip(idx, wts)]
             for j, i in enumerate(idx):
                 H, W, _ = shapes[i]
                 out_path = os.path.join(out_dir, "%d.png" % i)

@@ -92,6 +92,28 @@ class _OutputPool:
 
 _outputs = _OutputPool()
 
+_OUT_DTYPES = (np.dtype(np.float32), np.dtype(np.uint8))
+
+
+def _out_u8(dtype):
+    """True for uint8 output (the library's *_u8 entries), False for float32; any other dtype is refused."""
+    dt = np.dtype(dtype)
+    if dt not in _OUT_DTYPES:
+        raise ValueError("dtype must be np.float32 or np.uint8, got %s" % dt)
+    return dt == np.uint8
+
+
+def _output(shape, dtype, out):
+    """(output array, uint8?) of a host entry.  float32 BGR in 0..255 as the reference returns it, or uint8: the same values
+    rounded half to even on the GPU (== driver.to_uint8 of the float output, bit for bit).  A given `out` selects the format
+    by its own dtype; otherwise `dtype` does and the array comes from the page-locked pool."""
+    if out is None:
+        u8 = _out_u8(dtype)
+        return _outputs.empty(shape, np.uint8 if u8 else np.float32), u8
+    if out.dtype not in _OUT_DTYPES or out.shape != tuple(shape) or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 or uint8 array of shape %r" % (tuple(shape),))
+    return out, out.dtype == np.uint8
+
 
 class Stylization():
     """``Stylization(checkpoint, cuda=True, use_Global=True)`` (test/framework.py:57).
@@ -101,6 +123,10 @@ class Stylization():
     checkpoint is download-only).  `device` picks the HIP device ordinal (one process per
     GPU; defaults to LOCAL_RANK or 0).
     """
+
+    # the transfer entries take dtype=np.uint8 / a uint8 `out`: the float32 output rounded half to even on the GPU
+    # (include/rerevst_hip.h, the rrv_*_u8 entries); driver.stylize_files* ask for it
+    uint8_output = True
 
     def __init__(self, checkpoint, cuda=True, use_Global=True, device=None, style_num=1):
         if not cuda:
@@ -199,28 +225,31 @@ class Stylization():
             a = _u8_image(s, "style")
             self._chk(self._lib.rrv_prepare_style(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], sid))
 
-    def transfer(self, frame, style_weight=None):
+    def transfer(self, frame, style_weight=None, dtype=np.float32):
         """uint8 BGR HWC frame -> float32 BGR HWC in 0..255 (test/framework.py:106-118).
         With `style_weight` (list of floats) the saved state of the prepared styles is
-        blended first (stylization.py:94-100)."""
+        blended first (stylization.py:94-100).  dtype=np.uint8: the frame as cv2.imwrite would write it (the float
+        output rounded half to even and saturated, on the GPU): a quarter of the bytes."""
         a = _u8_image(frame, "frame")
         H, W = a.shape[:2]
-        out = _outputs.empty((H // 8 * 8, W // 8 * 8, 3))     # the max pools floor the size, as in the reference
+        out, u8 = _output((H // 8 * 8, W // 8 * 8, 3), dtype, None)     # the max pools floor the size, as in the reference
         if not self.use_Global:
-            self._chk(self._lib.rrv_transfer_frame_mode(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p)))
+            fn = self._lib.rrv_transfer_frame_mode_u8 if u8 else self._lib.rrv_transfer_frame_mode
+            self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p)))
             return out
         if style_weight is None:      # the reference's hot call: plain addresses (ctypes' data_as() objects cost ~10 us a call)
-            rc = self._lib.rrv_transfer(self._h, a.__array_interface__["data"][0], H, W, out.__array_interface__["data"][0])
+            fn = self._lib.rrv_transfer_u8 if u8 else self._lib.rrv_transfer
+            rc = fn(self._h, a.__array_interface__["data"][0], H, W, out.__array_interface__["data"][0])
             if rc != 0:
                 self._chk(rc)
             return out
         w = (C.c_float * len(style_weight))(*[float(v) for v in style_weight])
-        self._chk(self._lib.rrv_transfer_blend(self._h, a.ctypes.data_as(C.c_void_p), H, W, w, len(style_weight),
-                                               out.ctypes.data_as(C.c_void_p)))
+        fn = self._lib.rrv_transfer_blend_u8 if u8 else self._lib.rrv_transfer_blend
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), H, W, w, len(style_weight), out.ctypes.data_as(C.c_void_p)))
         return out
 
     # ===== look-ahead form of transfer() for a one-frame-per-call loop =====
-    def transfer_async(self, frame, out=None):
+    def transfer_async(self, frame, out=None, dtype=np.float32):
         """Queue one frame (H2D copy, kernels, D2H copy) and return a ticket at once; ``result(ticket)`` returns the
         stylized frame.  A driver loop written as
 
@@ -233,18 +262,16 @@ class Stylization():
 
         overlaps frame i+1's copy-in and kernels with frame i's kernel tails, copy-out and file write.  Up to four
         tickets may be open (each on its own stream with a quarter of the CUs per launch): keeping three frames
-        submitted ahead of the one being collected gives the best rate.  Same arithmetic as transfer(): bit-identical results."""
+        submitted ahead of the one being collected gives the best rate.  Same arithmetic as transfer(): bit-identical results.
+        dtype / a uint8 `out`: uint8 output as transfer(dtype=np.uint8)."""
         if not self.use_Global:
             raise RRVError("transfer_async() needs the global-feature-sharing model (use_Global=True)")
         a = _u8_image(frame, "frame")
         H, W = a.shape[:2]
-        oshape = (H // 8 * 8, W // 8 * 8, 3)
-        if out is None:
-            out = _outputs.empty(oshape)
-        elif out.dtype != np.float32 or out.shape != oshape or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % (oshape,))
+        out, u8 = _output((H // 8 * 8, W // 8 * 8, 3), dtype, out)
         t = C.c_long(-1)
-        self._chk(self._lib.rrv_transfer_async(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p), C.byref(t)))
+        fn = self._lib.rrv_transfer_async_u8 if u8 else self._lib.rrv_transfer_async
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p), C.byref(t)))
         # The library owns `out` until the ticket is collected or retired: a caller that drops the ticket (an exception in
         # its loop, `prev` overwritten) must not hand the block back to the pool under a running kernel.  Submitting
         # ticket t retired ticket t - 4 (four staging sets), so only the last four stay referenced here.
@@ -261,58 +288,56 @@ class Stylization():
 
     # ===== device-resident entry (what bench.py times) =====
     # With use_Global=False the batch / frames / device entries run the frame-mode model (rrv_transfer_frame_mode_*): each frame
-    # gets its own statistics, bit-identical to transfer() on that frame alone.
-    def transfer_device(self, d_in_ptr, H, W, d_out_ptr):
+    # gets its own statistics, bit-identical to transfer() on that frame alone.  dtype=np.uint8: d_out receives uint8 BGR
+    # (the *_device_u8 entries), 3 bytes per pixel instead of 12.
+    def _entry(self, name, u8):
+        return getattr(self._lib, name + ("_u8" if u8 else ""))
+
+    def transfer_device(self, d_in_ptr, H, W, d_out_ptr, dtype=np.float32):
         if not self.use_Global:
-            self.transfer_batch_device(d_in_ptr, 1, H, W, d_out_ptr)
+            self.transfer_batch_device(d_in_ptr, 1, H, W, d_out_ptr, dtype)
             return
-        self._chk(self._lib.rrv_transfer_device(self._h, C.c_void_p(d_in_ptr), H, W, C.c_void_p(d_out_ptr)))
+        self._chk(self._entry("rrv_transfer_device", _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), H, W, C.c_void_p(d_out_ptr)))
 
-    def transfer_batch_device(self, d_in_ptr, B, H, W, d_out_ptr):
-        """[B][H][W][3] uint8 in HBM -> [B][H][W][3] float32 in HBM, asynchronous on the library stream."""
-        fn = self._lib.rrv_transfer_batch_device if self.use_Global else self._lib.rrv_transfer_frame_mode_batch_device
-        self._chk(fn(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
+    def transfer_batch_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
+        """[B][H][W][3] uint8 in HBM -> [B][H][W][3] float32 (or uint8) in HBM, asynchronous on the library stream."""
+        name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
+        self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def transfer_batch(self, frames, out=None):
+    def transfer_batch(self, frames, out=None, dtype=np.float32):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
-        pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 [B][H][W][3] array to
-        fill instead of allocating a fresh one."""
+        pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
+        to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does)."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
-        oshape = (B, H // 8 * 8, W // 8 * 8, 3)
-        if out is None:
-            out = _outputs.empty(oshape)
-        elif out.dtype != np.float32 or out.shape != oshape or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % (oshape,))
-        fn = self._lib.rrv_transfer_batch if self.use_Global else self._lib.rrv_transfer_frame_mode_batch
+        out, u8 = _output((B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
+        fn = self._entry("rrv_transfer_batch" if self.use_Global else "rrv_transfer_frame_mode_batch", u8)
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_frames(self, frames, out=None):
+    def transfer_frames(self, frames, out=None, dtype=np.float32):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
-        for a fixed kernel choice, set_f43(0) / set_f43(2); the default picks kernels per launch geometry, the crop window included)."""
+        for a fixed kernel choice, set_f43(0) / set_f43(2); the default picks kernels per launch geometry, the crop window included).
+        `out` / `dtype` as in transfer_batch: uint8 output is to_uint8 of the float output, computed on the GPU."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
-        if out is None:
-            out = _outputs.empty((B, H, W, 3))
-        elif out.dtype != np.float32 or out.shape != (B, H, W, 3) or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((B, H, W, 3),))
-        fn = self._lib.rrv_transfer_frames if self.use_Global else self._lib.rrv_transfer_frame_mode_frames
+        out, u8 = _output((B, H, W, 3), dtype, out)
+        fn = self._entry("rrv_transfer_frames" if self.use_Global else "rrv_transfer_frame_mode_frames", u8)
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr):
-        """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32), asynchronous on the library stream."""
-        fn = self._lib.rrv_transfer_frames_device if self.use_Global else self._lib.rrv_transfer_frame_mode_frames_device
-        self._chk(fn(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
+    def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
+        """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
+        name = "rrv_transfer_frames_device" if self.use_Global else "rrv_transfer_frame_mode_frames_device"
+        self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def sync(self):
         self._chk(self._lib.rrv_sync(self._h))
@@ -453,29 +478,25 @@ class MultiStyleStylization(Stylization):
     def compute_norm(self):
         self.compute()
 
-    def transfer(self, cur_feature, style_weight=[1.], out=None):
+    def transfer(self, cur_feature, style_weight=[1.], out=None, dtype=np.float32):
+        """`out` / `dtype`: float32 (default) or uint8 output, as Stylization.transfer_batch."""
         H, W = cur_feature.shape[0] // 8 * 8, cur_feature.shape[1] // 8 * 8
-        if out is None:
-            out = _outputs.empty((H, W, 3))
-        elif out.dtype != np.float32 or out.shape != (H, W, 3) or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((H, W, 3),))
+        out, u8 = _output((H, W, 3), dtype, out)
         w = (C.c_float * len(style_weight))(*[float(v) for v in style_weight])
-        self._chk(self._lib.rrv_transfer_features(self._h, cur_feature.id, w, len(style_weight), out.ctypes.data_as(C.c_void_p)))
+        fn = self._entry("rrv_transfer_features", u8)
+        self._chk(fn(self._h, cur_feature.id, w, len(style_weight), out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_many(self, features, style_weights, out=None):
+    def transfer_many(self, features, style_weights, out=None, dtype=np.float32):
         """`transfer` for a run of cached features, one weight vector each, pipelined inside the library
-        (rrv_transfer_features_batch).  Returns / fills a float32 [n][H][W][3] array."""
+        (rrv_transfer_features_batch).  Returns / fills a float32 (or, by `out` / `dtype`, uint8) [n][H][W][3] array."""
         n = len(features)
         H, W = features[0].shape[0] // 8 * 8, features[0].shape[1] // 8 * 8
         ns = len(style_weights[0])
-        if out is None:
-            out = _outputs.empty((n, H, W, 3))
-        elif out.dtype != np.float32 or out.shape != (n, H, W, 3) or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((n, H, W, 3),))
+        out, u8 = _output((n, H, W, 3), dtype, out)
         ids = (C.c_int * n)(*[f.id for f in features])
         w = (C.c_float * (n * ns))(*[float(v) for row in style_weights for v in row])
-        self._chk(self._lib.rrv_transfer_features_batch(self._h, ids, w, n, ns, out.ctypes.data_as(C.c_void_p)))
+        self._chk(self._entry("rrv_transfer_features_batch", u8)(self._h, ids, w, n, ns, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def release_features(self):

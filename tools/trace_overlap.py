@@ -24,7 +24,7 @@ def main(path, skip=0.3):
         else:
             cur_e = max(cur_e, e)
     union += cur_e - cur_s
-    nlast = sum(1 for r in rows if r[2].startswith("conv_last_k"))
+    nlast = sum(1 for r in rows if "conv_last_k" in r[2])
     print("steady part: %.1f ms wall, %d frames (conv_last_k launches) -> %.3f ms per frame" % (span / 1e6, nlast, span / 1e6 / max(1, nlast)))
     print("  at least one kernel running %.1f%% of the wall; sum of kernel durations = %.2fx the wall (%.3f ms per frame)"
           % (100.0 * union / span, ssum / span, ssum / 1e6 / max(1, nlast)))
