@@ -2,15 +2,20 @@
 """Throughput bench of the per-frame stylization path (BASELINE.json metric: stylized frames/sec at
 512x512, 1 style; 1/2/4/8 MI355X + CPU ref).
 
-    python bench.py --gpus N --steps K --warmup W [--size 256|512|1024] [--multistyle S] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--size 256|512|1024] [--multistyle S] [--dump-outputs DIR] [--full]
 
 `value` is HOST -> HOST, as SURVEY.md §8(d) defines the metric and as the reference's transfer() works
 (test/framework.py:109 `.to(device)` ... :40 `.cpu()`): a step = one `rrv_transfer_batch` call over `--batch`
 synthetic SxS frames per GPU (reflect-padded to P = roundup64(S+128) as generate_real_video.py:61-83 does), uint8
 frames in (page-locked) host memory -> float32 BGR frames in (page-locked) host memory; the sub-batches of 16 are
-pipelined inside the call (H2D / kernels / D2H on two HIP streams).  Extras, never `value`: the HBM -> HBM rate of
-the same frames (`device_resident_frames_per_s`), the rate with pageable caller arrays, and the unpadded-in /
-cropped-out entry.
+pipelined inside the call (H2D / kernels / D2H on two HIP streams).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps (the last one profiled with HIP events
+for `roofline` / `kernels`), the --dump-outputs arrays and the JSON line.  --full adds, after the timed region, every
+measurement and check beyond it (extras, never `value`): the CPU baseline, the HBM -> HBM rate of the same frames
+(`device_resident_frames_per_s`), the rate with the other kind of caller arrays, the unpadded-in / cropped-out entry,
+one frame per call, zero-copy host I/O, the PNG -> PNG driver, configs 2 and 5 as short legs of their own, and with
+N > 1 the C-ABI RCCL broadcast check.  --no-cpu-baseline / --no-extras / --no-other-configs drop parts of --full.
 
 --multistyle S (BASELINE config 5, default size 1024): the "Multi-style Interpolation" flow — encoder features of
 every frame cached in HBM (test.py:87-101), statistics from every 16th + the last (:72-85), then per frame the DECODER
@@ -298,7 +303,7 @@ def dump_sample(a, budget, seed=0):
 def sub_leg(extra_args, timeout_s=600):
     """One of the other BASELINE configurations as a short run of this script in a child process (after the timed headline
     region, same GPU): returns the few fields the headline line carries as extras, or {"error": ...}."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-extras"] + extra_args
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1"] + extra_args       # a plain run: no --full
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "RRV_BENCH_FORCE_DIST")}
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -323,9 +328,11 @@ def main():
     ap.add_argument("--size", type=int, default=0, help="frame side: 256 / 512 / 1024 (default 512; 1024 with --multistyle)")
     ap.add_argument("--frames", type=int, default=0, help="frames of the synthetic video (default: BASELINE configs, 100 / 300 / 300)")
     ap.add_argument("--multistyle", type=int, default=0, help="S > 0: BASELINE config 5, S-style interpolation, decoder only per frame")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short 256x256 (config 2) and 4-style 1024x1024 (config 5) legs appended to the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline, the extras, configs 2 and 5 and (N > 1) the C-ABI RCCL broadcast check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras and the config 2 / 5 legs")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short 256x256 (config 2) and 4-style 1024x1024 (config 5) legs")
     ap.add_argument("--profile-steps", type=int, default=1)
     ap.add_argument("--pipeline", type=int, default=2, help="sub-batches in flight per GPU (1 or 2 HIP streams)")
     ap.add_argument("--pageable", action="store_true", help="time the host entry with pageable caller arrays instead of page-locked ones")
@@ -500,13 +507,13 @@ def main():
     # the one collective of the path once more through the C ABI (rrv_broadcast_state: ncclBroadcast on an ncclComm_t
     # built from a unique id that travels over the process group), checked bit for bit against the state every rank holds
     c_abi_bcast = None
-    if use_dist and backend == "nccl" and os.environ.get("RRV_BENCH_NO_CABI_BCAST") != "1":
+    if args.full and use_dist and backend == "nccl" and os.environ.get("RRV_BENCH_NO_CABI_BCAST") != "1":
         c_abi_bcast = c_abi_broadcast_check(model, dist, rank, world, max(1, NS))
 
     if rank == 0:
         roof, kern, layers = roofline_and_kernels(rows, nprof, B, S, NS)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             blobs = [model.get_state(k) for k in range(max(1, NS))]
             def frame_of(k):
                 return video.reflect_pad(pkg.synth_frame(k, S, S, kind="noise"), P, P)
@@ -552,7 +559,7 @@ def main():
             out["feature_cache_frames_per_s"] = round(fc, 1)
             # a video end to end = the caching pass (encoder, once per frame) THEN the decoder pass: serial rates combine harmonically
             out["end_to_end_frames_per_s"] = round(1.0 / (1.0 / fc + 1.0 / out["value"]), 1)
-        if world == 1 and not args.no_extras and not NS:
+        if args.full and world == 1 and not args.no_extras and not NS:
             # extras, NOT `value`.  (1) HBM -> HBM on the same frames, one sub-batch per launch, two batches in flight (round 1's headline)
             sbf = max(1, min(32, B, (16 * 640 * 640) // (P * P)))       # the library's sub-batch for this frame size
             d_in = torch.from_numpy(np.ascontiguousarray(h_in[0][:2 * sbf if B >= 2 * sbf else B])).to(dev)
@@ -649,7 +656,7 @@ def main():
         # (5) SURVEY 8(f)4, the driver's file -> file rate: PNG frames on disk -> decode (worker threads) -> transfer_frames ->
         # encode / write (worker threads), the reference script's whole loop (generate_real_video.py:152-171) without its
         # one-off preparation.  Smooth synthetic frames (white noise is the codecs' worst case, not video).
-        if world == 1 and not args.no_extras and not NS and os.environ.get("RRV_BENCH_NO_DRIVER") != "1":
+        if args.full and world == 1 and not args.no_extras and not NS and os.environ.get("RRV_BENCH_NO_DRIVER") != "1":
             try:
                 import shutil
                 import tempfile
@@ -675,9 +682,9 @@ def main():
             except Exception as e:
                 out["driver_png_to_png_frames_per_s"] = None
                 out["driver_png_to_png"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-        # BASELINE configs 2 and 5 as short legs of the SAME default invocation (the driver runs only this one), after the timed
-        # headline region: extras, never `value`.  Each is this script in a child process with its own steps / warm-up.
-        if world == 1 and not args.no_extras and not args.no_other_configs and not NS and S == 512 and not args.pageable:
+        # BASELINE configs 2 and 5 as short legs of the same --full invocation, after the timed headline region: extras, never
+        # `value`.  Each is this script in a child process with its own steps / warm-up.
+        if args.full and world == 1 and not args.no_extras and not args.no_other_configs and not NS and S == 512 and not args.pageable:
             model.close()
             c2 = sub_leg(["--size", "256", "--steps", "12", "--warmup", "3"])
             c5 = sub_leg(["--multistyle", "4", "--steps", "16", "--warmup", "3"])

@@ -468,7 +468,7 @@ def test_bench_nccl_process_group_at_world_size_one():
                MASTER_PORT=str(29900 + os.getpid() % 90))
     env.pop("RRV_BENCH_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "256",
-           "--batch", "8", "--frames", "20", "--no-cpu-baseline", "--no-extras", "--profile-steps", "1"]
+           "--batch", "8", "--frames", "20", "--full", "--no-cpu-baseline", "--no-extras", "--profile-steps", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

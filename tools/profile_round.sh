@@ -21,5 +21,5 @@ python tools/prof_summary.py $(db trace) > $O/kernel_trace.txt 2> $O/kernel_trac
 python tools/pmc_summary.py $(db pmc1) $(db pmc2) $(db pmc3) $(db pmc4) > $O/pmc.txt 2> $O/pmc.err
 python tools/pmc_traffic_json.py $(db pmc3) $(db pmc4) "$CMD" > $O/hbm_traffic.json 2> $O/traffic.err
 rm -rf $O/trace $O/pmc1 $O/pmc2 $O/pmc3 $O/pmc4
-python bench.py $* > $O/bench.json 2> $O/bench.err
+python bench.py --full $* > $O/bench.json 2> $O/bench.err
 ls -la $O; head -12 $O/kernel_trace.txt; tail -c 600 $O/bench.json
