@@ -255,6 +255,41 @@ int rrv_transfer_frame_mode_batch_device_u8(rrv_handle h, const void* d_frames_b
 int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, uint8_t* out_bgr);  /* == to_uint8(rrv_transfer_frame_mode_frames) */
 int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_frames_bgr_u8, int B, int H, int W, void* d_out_bgr_u8);  /* == to_uint8(rrv_transfer_frame_mode_frames_device) */
 
+/* Torch-pipeline forms of the device entries: one descriptor-based entry for the image layouts and value spaces a torch
+ * pipeline holds.  An image is described by its element type, layout and value space:
+ *   dtype  RRV_DT_U8 (uint8) | RRV_DT_F32 (float32)
+ *   layout RRV_LAY_HWC_BGR ([B][H][W][3] BGR, cv2's) | RRV_LAY_CHW_RGB ([B][3][H][W] RGB, torch's NCHW), contiguous
+ *   space  RRV_SP_PIXEL (0..255) | RRV_SP_UNIT (0..1) | RRV_SP_NORM (test/framework.py transform_image: (x/255 - mean)/std)
+ * uint8 is PIXEL only.  The output's spaces: PIXEL float32 = rrv_transfer_batch_device's values; PIXEL uint8 = the _u8
+ * twin's; UNIT = the clamped value the PIXEL form multiplies by 255 (UNIT * 255.0f == PIXEL, bit for bit); NORM = the
+ * pre-clamp network output (rrv_get_preclamp_image), i.e. the output of the reference's `self.model(frame)` for a NORM input.
+ * Bit-identity of the input forms: every form is converted to the normalised value the uint8 path computes from px, so
+ * a frame derived from uint8 px the reference's way gives the uint8 path's output bit for bit: float32 PIXEL (float)px;
+ * UNIT (float)px / 255.0f (correctly rounded, as numpy's float32 division); NORM ((float)px / 255.0f - mean) / std in
+ * float32 with mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225); any uint8 layout.  An output layout changes
+ * only where the values go.
+ * flags: RRV_TF_PAD_CROP = the geometry of rrv_transfer_frames_device (UNPADDED [B][H][W] frames in, reflect pad and crop
+ * on the device, [B][H][W] out); else that of rrv_transfer_batch_device ([B][8*(H/8)][8*(W/8)] out).  RRV_TF_FRAME_MODE =
+ * the frame-mode model of rrv_transfer_frame_mode_{batch,frames}_device (needs rrv_prepare_style).  Shape limits, slots and
+ * errors are those entries': B in 1..64, (H+2)*(W+2)*64 < 2^31 for the padded geometry.  An invalid descriptor (uint8 with
+ * UNIT or NORM, an unknown value) or flag is RRV_E_ARG, and the handle stays usable.
+ * hip_stream != NULL: the call behaves as if it were enqueued on that stream (the events of rrv_set_caller_stream, for this
+ * call only: no host sync); NULL: the ordering of the other *_device entries, unless flags has RRV_TF_ON_STREAM, which
+ * orders the call on hip_stream whatever its value, NULL being the null stream (torch's default stream). */
+typedef struct { int dtype; int layout; int space; } rrv_image_desc;
+#define RRV_DT_U8 0
+#define RRV_DT_F32 1
+#define RRV_LAY_HWC_BGR 0
+#define RRV_LAY_CHW_RGB 1
+#define RRV_SP_PIXEL 0
+#define RRV_SP_UNIT 1
+#define RRV_SP_NORM 2
+#define RRV_TF_PAD_CROP 1      /* unpadded frames in, crop window out (ReshapeTool + crop on the device) */
+#define RRV_TF_FRAME_MODE 2    /* use_Global=False model (per-frame statistics); needs rrv_prepare_style */
+#define RRV_TF_ON_STREAM 4     /* order on hip_stream also when it is NULL (the null stream) */
+int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W,
+                              void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

@@ -15,6 +15,17 @@ MAX_STYLES = 8
 
 _lib = None
 
+
+class ImageDesc(C.Structure):
+    """rrv_image_desc: element type, layout and value space of the images of rrv_transfer_image_device."""
+    _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("space", C.c_int)]
+
+
+DT_U8, DT_F32 = 0, 1
+LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
+SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
+TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM = 1, 2, 4
+
 # name -> (restype, argtypes); must list every symbol declared in include/rerevst_hip.h
 SYMBOLS = {
     "rrv_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -59,6 +70,8 @@ SYMBOLS = {
     "rrv_transfer_frame_mode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_transfer_frame_mode_frames_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_transfer_frame_mode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_transfer_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc,
+                                            C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

@@ -9,14 +9,24 @@
 //   *255, RGB->BGR, HWC float32.  Reads 256 B/pixel, writes 12 (+12) B/pixel.
 //   conv_last_k<true>: the same, then rint (v_rndne_f32: round half to even, as np.rint) and one byte per channel: HWC
 //   uint8, the float form's values quantised on the GPU (cv2.imwrite's conversion).  Writes 3 (+12) B/pixel.
+// Torch forms (rrv_transfer_image_device): conv_first_k<IN> also reads planar [B][3][H][W] RGB (torch's NCHW) and float32
+//   frames in one of three value spaces; conv_last_k<U8, CHW, SPACE> also writes planar RGB and the UNIT / NORM spaces.  The
+//   default instantiations are the uint8 BGR HWC forms above, unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "conv_mfma.h"   // bufld16
 
+// Value spaces of a frame (include/rerevst_hip.h RRV_SP_*): PIXEL 0..255, UNIT 0..1, NORM transform_image's (x/255 - mean)/std
+enum : int { SP_PIXEL = 0, SP_UNIT = 1, SP_NORM = 2 };
+// conv_first_k's input forms (the template argument): bit 0 planar CHW RGB (else HWC BGR), bit 1 float32 (else uint8)
+enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3 };
+inline size_t in_elem(int form) { return (form & 2) ? sizeof(float) : 1; }     // bytes per input channel value
+
 struct FirstP {
-    const uint8_t* img;   // [B][H][W][3] BGR
+    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32
     int H, W, B;
     float* out;           // [B,H,W,64] ring layout
     const float* w;       // [27][64]: row (ky*3+kx)*3 + c_rgb
@@ -29,6 +39,7 @@ struct FirstP {
     // (cv2.BORDER_REFLECT = numpy 'symmetric').  src_H == 0: img already has the padded geometry.
     int src_H, src_W, pad_top, pad_left;
     int p8;               // 1: `out` is channel-chunk-major [B][8 chunks][H+2][W+8][8], pixel x at column x + 4 (conv_f43.h LAY: what conv1_2 on conv_f43_k reads 12-19 % faster); same values
+    int space;            // value space of a float32 input (SP_*); a uint8 input is PIXEL
 };
 
 // symmetric (edge-inclusive) reflection of t into [0, n), any distance
@@ -39,7 +50,14 @@ __device__ __forceinline__ int reflect_sym(int t, int n) {
     return t < n ? t : period - 1 - t;
 }
 
+// IN: input form (IN_*).  Every form turns a source pixel into the normalised value n the uint8 form computes,
+// ((float)px / 255 - mean) / std: a float PIXEL value v as v / 255 (bit-identical for integral v), a UNIT value x in place of
+// px / 255 (the same float where x is the correctly rounded px / 255), a NORM value n as it is.  Everything after that (grey
+// fold, border path, P8 stores, reflect-pad addressing) is shared.
+template <int IN = IN_U8_HWC>
 __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
+    constexpr bool CHW = (IN & 1) != 0, F32 = (IN & 2) != 0;
+    typedef typename std::conditional<F32, float, uint8_t>::type T;
     __shared__ __attribute__((aligned(16))) float s_in[18 * 18 * 4];
     __shared__ __attribute__((aligned(16))) float s_w[27 * 64];
     const int tid = threadIdx.x;
@@ -50,13 +68,21 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
     const int b = bx / p.tiles_y;
     const int y0 = ty * 16, x0 = tx * 16;
     const int SH = p.src_H ? p.src_H : p.H, SW = p.src_H ? p.src_W : p.W;
-    const uint8_t* img = p.img + (size_t)b * SH * SW * 3;
-    auto src_px = [&](int y, int x) {       // padded-frame pixel -> address in the source frame
+    const T* img = (const T*)p.img + (size_t)b * SH * SW * 3;
+    auto src_px = [&](int y, int x) {       // padded-frame pixel -> its index in a plane of the source frame
         if (p.src_H) { y = reflect_sym(y - p.pad_top, SH); x = reflect_sym(x - p.pad_left, SW); }
-        return img + ((size_t)y * SW + x) * 3;
+        return (size_t)y * SW + x;
     };
 
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
+    auto norm_of = [&](size_t i, int c) -> float {      // source pixel i -> normalised value of channel c, RGB order (framework.py:27,33-34)
+        const float v = CHW ? (float)img[(size_t)c * SH * SW + i] : (float)img[i * 3 + 2 - c];
+        if constexpr (F32) {
+            if (p.space == SP_NORM) return v;
+            return ((p.space == SP_UNIT ? v : v / 255.0f) - mean[c]) / sd[c];
+        }
+        return (v / 255.0f - mean[c]) / sd[c];
+    };
     // A greyscaled frame feeds the three input channels with affine functions of one value g (RGB2Gray + the
     // re-normalisation, test/style_network_global.py:487-497): 9 multiplies per output instead of 27.  The fold
     // assumes all nine taps inside the image, so tiles that touch the image border take the general path below.
@@ -64,10 +90,10 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
         float* s_g = s_in;      // [18][18] grey values
         for (int i = tid; i < 18 * 18; i += 256) {
             const int hy = i / 18, hx = i - hy * 18;
-            const uint8_t* px = src_px(y0 + hy - 1, x0 + hx - 1);
+            const size_t px = src_px(y0 + hy - 1, x0 + hx - 1);
             float d[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) d[c] = (((float)px[2 - c] / 255.0f - mean[c]) / sd[c]) * sd[c] + mean[c];   // as the reference rounds it
+            for (int c = 0; c < 3; ++c) d[c] = norm_of(px, c) * sd[c] + mean[c];   // as the reference rounds it
             s_g[i] = d[2] * 0.299f + d[1] * 0.587f + d[0] * 0.114f;   // :493 (sic)
         }
         __syncthreads();
@@ -131,10 +157,10 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
         const int y = y0 + hy - 1, x = x0 + hx - 1;
         float o[3] = {0.f, 0.f, 0.f};
         if (y >= 0 && y < p.H && x >= 0 && x < p.W) {
-            const uint8_t* px = src_px(y, x);
+            const size_t px = src_px(y, x);
             float n[3];   // normalised, RGB order (framework.py:27,33-34)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) n[c] = ((float)px[2 - c] / 255.0f - mean[c]) / sd[c];
+            for (int c = 0; c < 3; ++c) n[c] = norm_of(px, c);
             if (p.grey) {
                 float d[3];
 #pragma unroll
@@ -216,7 +242,7 @@ struct LastP {
     int H, W, B;
     const float* w;       // pack_last_k: [blk 2][c 4][lane 64][s 4] MFMA A operands of the 27 x 64 tap-rgb matrix
     const float* bias;    // [4]
-    void* out_img;        // [B][H][W][3] BGR: float32 0..255 (conv_last_k<false>) or its rint as uint8 (conv_last_k<true>)
+    void* out_img;        // [B][H][W][3] BGR: float32 0..255 (conv_last_k<false>) or its rint as uint8 (conv_last_k<true>); CHW: [B][3][H][W] RGB
     float* out_pre;       // optional [B][H][W][3] RGB pre-clamp (normalised units), may be null
     int tiles_x, tiles_y;
     // optional on-device crop (generate_real_video.py:167): out_img is [B][out_H][out_W][3] and receives the window
@@ -237,7 +263,10 @@ struct LastP {
 #define LAST_GP 330       /* floats per G plane (324 used); 4 planes = 8 banks on: the four row groups of a wave write disjoint banks */
 // U8: the uint8 store form; everything before the store is the same code in both instantiations (a template kernel, not an
 // inlined body: the float instantiation compiles to the instructions of the non-template kernel it replaced)
-template <bool U8>
+// CHW: planar [B][3][OH][OW] RGB (torch's NCHW) instead of HWC BGR.  SPACE: SP_PIXEL (0..255, the forms above), SP_UNIT (the
+// clamped 0..1 value the PIXEL form multiplies by 255, so UNIT * 255.0f == PIXEL bit for bit) or SP_NORM (the pre-clamp network
+// output, the out_pre value); UNIT and NORM are float32 only.
+template <bool U8, bool CHW = false, int SPACE = SP_PIXEL>
 __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     __shared__ __attribute__((aligned(16))) float s_g[27 * LAST_GP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -333,12 +362,28 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
             if (p.out_pre) *(f32x3*)(p.out_pre + (((size_t)b * p.H + y) * p.W + xx) * 3) = f32x3{o[0], o[1], o[2]};
             float im[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f) * 255.f;
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (SPACE == SP_NORM) im[c] = o[c];
+                else if constexpr (SPACE == SP_UNIT) im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f);
+                else im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f) * 255.f;
+            }
             const int cy = p.out_H ? y - p.crop_top : y, cx = p.out_H ? xx - p.crop_left : xx;
             // RGB -> BGR; a lane stores its pixel's 12 bytes, a row of the tile leaves as one 192-byte burst (uint8: 3 bytes as one
             // short + one byte store, a 48-byte row; rows are OW * 3 bytes and in general not dword aligned — measured no slower
             // than the float form, into HBM and into page-locked host memory: profiles/u8_output_rate.json)
-            if constexpr (U8) {
+            // Planar: one store per plane; the 16 lanes of a tile row write 64 contiguous bytes of each plane (uint8: 16), three
+            // streams instead of one 192-byte burst, and a plane row starts on a 64-byte line only where OW * 4 (uint8: OW) is a
+            // multiple of 64 — DESIGN §4's misaligned line starts, up to half the write bandwidth of this 12 (3) B/pixel store.
+            if constexpr (CHW) {
+                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
+                    const size_t plane = (size_t)OH * OW, at = (size_t)b * 3 * plane + (size_t)cy * OW + cx;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        if constexpr (U8) ((uint8_t*)p.out_img)[at + c * plane] = (uint8_t)__builtin_rintf(im[c]);
+                        else ((float*)p.out_img)[at + c * plane] = im[c];
+                    }
+                }
+            } else if constexpr (U8) {
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
                     uint8_t* q = (uint8_t*)p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3;
 #pragma unroll

@@ -165,6 +165,7 @@ struct rrv_ctx {
     int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots (stream, workspace) pairs
     hipEvent_t slot_ev[RRV_MAX_SLOTS] = {nullptr};   // ordering against the caller's stream (rrv_set_caller_stream)
     hipStream_t caller_stream = nullptr; bool caller_sync = false;
+    int in_form = IN_U8_HWC, in_space = SP_PIXEL;    // the content frames' form (conv_first_k<IN>) while rrv_transfer_image_device runs; uint8 BGR HWC otherwise
     int user_style = -1;                             // style the plain transfer entries use (first computed / last set_state)
     std::string err;
     std::map<std::string, std::vector<float>> hostw;
@@ -949,11 +950,14 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
         for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, *W_(i), B, lh[i], lw[i], le[i], false, 0, false);
         h->enc_p8_tables = p8;
     }
+    const int inf = which == 0 ? h->in_form : IN_U8_HWC;
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
-              which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0};
+              which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
+              which == 0 ? h->in_space : SP_PIXEL};
     stamp(h, p8 ? &e.q11 : &e.c11, B);
-    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, (3.0 + 256.0) * B * H * W, [&] {
-        hipLaunchKernelGGL(conv_first_k, dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
+    static void (*const first_k[4])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>};
+    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, (3.0 * in_elem(inf) + 256.0) * B * H * W, [&] {
+        hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
     }));
     ConvCall c;
     if (p8) {
@@ -983,9 +987,10 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
 
 // Format of a stylized frame: OUT_F32 = float32 BGR in 0..255 (tensor2numpy), OUT_U8 = the same values rounded half to even
 // on the GPU (conv_last_k<true>: cv2.imwrite's / driver.to_uint8's conversion) — the rrv_*_u8 entries.  Elements per frame are
-// the same; only their size differs.
-enum OutFmt { OUT_F32, OUT_U8 };
-inline size_t out_elem(OutFmt f) { return f == OUT_U8 ? 1 : sizeof(float); }
+// the same; only their size differs.  rrv_transfer_image_device adds planar RGB (chw) and the UNIT / NORM spaces (float32 only).
+struct OutFmt { bool u8, chw; int space; };
+constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
+inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 inline void* out_at(void* p, size_t elems, OutFmt f) { return (char*)p + elems * out_elem(f); }
 inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
 
@@ -1113,6 +1118,15 @@ int resblock_frame(rrv_handle h, int B, const char* blk, const Tens& in, Tens& x
     return RRV_OK;
 }
 
+// the conv_last_k instantiation that writes `f`
+typedef void (*LastFn)(LastP);
+LastFn last_kernel(OutFmt f) {
+    if (f.u8) return f.chw ? conv_last_k<true, true> : conv_last_k<true>;
+    static const LastFn k[2][3] = {{conv_last_k<false>, conv_last_k<false, false, SP_UNIT>, conv_last_k<false, false, SP_NORM>},
+                                   {conv_last_k<false, true>, conv_last_k<false, true, SP_UNIT>, conv_last_k<false, true, SP_NORM>}};
+    return k[f.chw][f.space];
+}
+
 // Decoder.slice1 + transform_back_image (conv_last_k) on a normalised slice2 output
 int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
@@ -1121,7 +1135,7 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
     return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + 3.0 * out_elem(fmt)) * B * H * W, [&] {
         const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * B), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
-        hipLaunchKernelGGL(fmt == OUT_U8 ? conv_last_k<true> : conv_last_k<false>, dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
+        hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
 }
 
@@ -2235,7 +2249,7 @@ static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B
     }
     for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
         const int nb = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
-        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb, nb, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
+        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb * in_elem(h->in_form), nb, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
     }
     if (h->caller_sync) {
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
@@ -2298,6 +2312,34 @@ int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_in, int B,
 }
 int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
     return device_entry(h, d_in, B, H, W, d_out, OUT_U8, true, true);
+}
+
+// rrv_transfer_image_device: the device entries above with the content frames read as `in` (conv_first_k<IN>) and the
+// stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only
+int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
+                              int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    auto bad = [](const rrv_image_desc& d) {
+        return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
+               d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
+    };
+    if (bad(in) || bad(out)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
+    if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
+    if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM)) return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
+    if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
+    const bool pad = flags & RRV_TF_PAD_CROP, frame = flags & RRV_TF_FRAME_MODE;
+    if (pad && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer_image: frames must be at least 1 x 1 pixels");
+    HIPCHK(hipSetDevice(h->dev));
+    struct Scope {
+        rrv_handle h; hipStream_t cs; bool sync;
+        ~Scope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; h->caller_stream = cs; h->caller_sync = sync; }
+    } scope{h, h->caller_stream, h->caller_sync};
+    h->in_form = (in.dtype == RRV_DT_F32 ? 2 : 0) | (in.layout == RRV_LAY_CHW_RGB ? 1 : 0);
+    h->in_space = in.space;
+    if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
+    const OutFmt fmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
+    return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded

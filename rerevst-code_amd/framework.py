@@ -3,6 +3,7 @@
 ``generate_real_video.py``-style driver runs unchanged.  All compute happens in
 librerevst_hip.so on one MI355X; this class only marshals numpy buffers through the C ABI.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -113,6 +114,72 @@ def _output(shape, dtype, out):
     if out.dtype not in _OUT_DTYPES or out.shape != tuple(shape) or not out.flags.c_contiguous:
         raise ValueError("out must be a C-contiguous float32 or uint8 array of shape %r" % (tuple(shape),))
     return out, out.dtype == np.uint8
+
+
+# ===== torch tensors (rrv_transfer_image_device) =====
+_SPACES = {"pixel": _lib.SP_PIXEL, "unit": _lib.SP_UNIT, "norm": _lib.SP_NORM}
+_LAYOUTS = {"nhwc": _lib.LAY_HWC_BGR, "nchw": _lib.LAY_CHW_RGB}     # nhwc: BGR (cv2's convention), nchw: RGB (torch's)
+TENSOR_BATCH_MAX = 64        # images per rrv_transfer_image_device call; transfer_tensor splits larger batches
+
+
+# what Stylization.transfer_tensor passes to the library, as tensor_io_args() works it out
+TensorIO = collections.namedtuple("TensorIO", "x in_desc out_desc out_shape out_dtype B H W batched")
+
+
+def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
+                   pad_crop=False, out=None):
+    """Check the arguments of Stylization.transfer_tensor against a handle on HIP device `device` (an ordinal) without
+    touching the GPU, and work out the call: raises ValueError for a tensor that is not on that device, a channel count
+    other than 3, a dtype the space does not allow (uint8 is "pixel" only; otherwise float32), an unknown space or
+    layout, or an `out` of the wrong shape, dtype, device or layout.  A non-contiguous `x` is made contiguous."""
+    import torch
+    if space not in _SPACES or out_space not in _SPACES:
+        raise ValueError("space and out_space must be one of %s, got %r / %r" % (sorted(_SPACES), space, out_space))
+    out_layout = layout if out_layout is None else out_layout
+    if layout not in _LAYOUTS or out_layout not in _LAYOUTS:
+        raise ValueError("layout and out_layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r / %r" % (layout, out_layout))
+
+    def on_device(t, what):
+        if t.device.type != "cuda" or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the handle's device), got %s" % (what, int(device), t.device))
+
+    def desc(dtype, sp, lay, what):
+        if dtype == torch.uint8:
+            if sp != "pixel":
+                raise ValueError("%s: uint8 images are in the 'pixel' space (0..255), not %r" % (what, sp))
+            dt = _lib.DT_U8
+        elif dtype == torch.float32:
+            dt = _lib.DT_F32
+        else:
+            raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
+        return _lib.ImageDesc(dt, _LAYOUTS[lay], _SPACES[sp])
+
+    on_device(x, "x")
+    in_desc = desc(x.dtype, space, layout, "x")
+    if x.dim() not in (3, 4):
+        raise ValueError("x must be [B,3,H,W] or [3,H,W] ('nhwc': [B,H,W,3] or [H,W,3]), got shape %s" % (tuple(x.shape),))
+    batched = x.dim() == 4
+    shp = tuple(x.shape) if batched else (1,) + tuple(x.shape)
+    B, H, W = (shp[0], shp[2], shp[3]) if layout == "nchw" else shp[:3]
+    if (shp[1] if layout == "nchw" else shp[3]) != 3:
+        raise ValueError("x must have 3 channels (%s), got shape %s" % (layout, tuple(x.shape)))
+    if B < 1:
+        raise ValueError("x holds no image")
+    Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+    out_shape = (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
+    if not batched:
+        out_shape = out_shape[1:]
+    if out is not None:
+        on_device(out, "out")
+        out_dtype = out.dtype
+        if tuple(out.shape) != out_shape or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_desc = desc(out_dtype, out_space, out_layout, "out")
+    if not x.is_contiguous():
+        x = x.contiguous()
+    return TensorIO(x=x, in_desc=in_desc, out_desc=out_desc, out_shape=out_shape, out_dtype=out_dtype, B=B, H=H, W=W,
+                    batched=batched)
 
 
 class Stylization():
@@ -338,6 +405,33 @@ class Stylization():
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
         name = "rrv_transfer_frames_device" if self.use_Global else "rrv_transfer_frame_mode_frames_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
+
+    def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
+                        pad_crop=False, out=None):
+        """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
+
+        x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
+        returns an unbatched result.  uint8 in 0..255, or float32 in the value space `space`: "pixel" 0..255, "unit" 0..1,
+        "norm" the reference's transform_image output (x/255 - mean)/std.  The output is out_dtype (torch.float32 or
+        torch.uint8; `out`'s dtype when given) in `out_layout` (default: `layout`) and `out_space`: "pixel" the values
+        transfer_batch_device writes (uint8: its _u8 twin's), "unit" those / 255 exactly, "norm" the pre-clamp network
+        output — with space="norm" as well, what the reference's `self.model(frame)` returns.  pad_crop: the geometry of
+        transfer_frames (reflect pad in, crop out: [.., H, W]); otherwise [.., 8*(H//8), 8*(W//8)].  With use_Global=False
+        the frame-mode model runs.  Batches above 64 images are split into calls of 64."""
+        import torch
+        a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
+                           out_layout=out_layout, pad_crop=pad_crop, out=out)
+        if out is None:
+            out = torch.empty(a.out_shape, dtype=a.out_dtype, device=x.device)
+        xb = a.x if a.batched else a.x.unsqueeze(0)
+        ob = out if a.batched else out.unsqueeze(0)
+        flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        for b0 in range(0, a.B, TENSOR_BATCH_MAX):
+            nb = min(TENSOR_BATCH_MAX, a.B - b0)
+            self._chk(self._lib.rrv_transfer_image_device(self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W,
+                                                          C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
+        return out
 
     def sync(self):
         self._chk(self._lib.rrv_sync(self._h))
