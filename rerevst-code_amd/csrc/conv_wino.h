@@ -43,17 +43,16 @@
 //     y[2i+1] = (g0+g1) x[i] + g2 x[i+1]   = s x[i] + g2 (x[i+1] - x[i]),     s = g0+g1+g2
 //   i.e. 3 multiplies per 2 outputs: 9 positions per 2x2 outputs in 2-D (36 for the direct form, 16 for the
 //   a parity-folded 2x2 conv), 3x3 patches one pixel apart, 10x10 low-resolution halo, all coefficients +-1.
-// SC = 1 (with UPS): the ResidualBlock's 1x1 shortcut (test/style_network_global.py:105,113-114) rides along as a
-// TENTH position: conv1x1(up(x)) = up(conv1x1(x)) is one more GEMM on V[0][0] = x[i][j], the centre pixel the
-// upsample-fused transform already holds, with the shortcut weights in the U slot; its output is the low-resolution
-// tensor that conv2's epilogue adds (E_RES_UPS).
+// SC = 1 (conv_wino_k's template argument): ResidualBlock.conv1 with the block's 1x1 shortcut
+// (test/style_network_global.py:105,113-114) fused in runs the five-product form of conv_ups5.h instead, which has its
+// own geometry (Ups5Geo); WinoGeo describes the SC = 0 forms only.
 
-template <int NW, int UPS, int SC = 0>
+template <int NW, int UPS>
 struct WinoGeo {
     static constexpr int NT = NW * 64;                       // threads
     static constexpr int NB = NW == 8 ? 1 : 2;               // 16-cout blocks per wave
     static constexpr int NP = UPS ? 9 : 16;                  // transform positions
-    static constexpr int NPU = NP + SC;                      // GEMM positions = U blocks per chunk
+    static constexpr int NPU = NP;                           // GEMM positions = U blocks per chunk
     static constexpr int PW = UPS ? 3 : 4;                   // patch width; pieces are indexed dx*PW + dy
     static constexpr int NPIECE = PW * PW;
     static constexpr int PPI = UPS ? 3 : 2;                  // patch pieces read per MFMA-loop iteration
@@ -63,7 +62,7 @@ struct WinoGeo {
     static constexpr int PIECES = HALO * HALO * 4;           // 16-byte pieces of one 16-channel raw halo tile
     static constexpr int RAW_IT = (PIECES + NT - 1) / NT;    // LDS-DMA instructions per thread per raw tile
     static constexpr int RAW_BYTES = RAW_IT * NT * 16;       // 24576 / 8192
-    static constexpr int U_BYTES = NPU * 32 * 16 * 4;        // 32768 / 18432 / 20480
+    static constexpr int U_BYTES = NPU * 32 * 16 * 4;        // 32768 / 18432
     static constexpr int U_PIECES = U_BYTES / 16;
     static constexpr int U_IT = (U_PIECES + NT - 1) / NT;
     static constexpr int U_LDS = U_IT * NT * 16;             // LDS bytes per U buffer: a disabled LDS-DMA slot still writes zeros
@@ -180,12 +179,14 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I..
     (f(std::integral_constant<int, I>{}), ...);
 }
 
+#include "conv_ups5.h"      // SC = 1: the five-product form with the shortcut (conv_ups5_body, pack_ups5_k)
+
+// The SC = 0 body of conv_wino_k (9 positions per low-resolution pixel).
 // PERIMG = 1: per-image epilogue parameters (ConvP::par_bstride; weights and bias are shared by the images of a launch), a separate instantiation as in conv_wino_split.h
-template <int EPI, int ABL = 0, int NW = 4, int UPS = 1, int SC = 0, int PERIMG = 0>
-__global__ __launch_bounds__(NW * 64, (WinoGeo<NW, UPS, SC>::OCC)) void conv_wino_k(const ConvP p) {
-    static_assert(UPS == 1 && NW == 4, "library kernel: upsample-fused form, 4 waves");
+template <int EPI, int ABL, int NW, int UPS, int PERIMG>
+__device__ __forceinline__ void conv_upw_body(const ConvP& p) {
     static_assert(!(EPI & E_POOL), "no pooling behind an upsample");
-    using G = WinoGeo<NW, UPS, SC>;
+    using G = WinoGeo<NW, UPS>;
     constexpr int NPU = G::NPU;
     constexpr int RAW_BYTES = G::RAW_BYTES, U_BYTES = G::U_BYTES, U_LDS = G::U_LDS, NT = G::NT, NB = G::NB, NP = G::NP, PW = G::PW, NPIECE = G::NPIECE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(NW * 64, (WinoGeo<NW, UPS, SC>::OCC)) void conv_win
             f32x4 u01[2] = {vcur[0], vcur[1]};
 #pragma unroll
             for (int i = 0; i < NPU; ++i) {
-                const f32x4 vv = vcur[i < NP ? i : 0];
+                const f32x4 vv = vcur[i];
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -388,7 +389,7 @@ __global__ __launch_bounds__(NW * 64, (WinoGeo<NW, UPS, SC>::OCC)) void conv_win
                     if constexpr (i < G::RAW_IT) bufld16_rs(i == G::RAW_IT - 1 ? rs_rl : rs_r, rdst + (i * NT + wave * 64) * 16, asrc[i], rsoff);
                 }
             }
-            const f32x4 vv = vcur[i < NP ? (i % PW) * PW + i / PW : 0];       // position NP (shortcut): V[0][0], the centre pixel
+            const f32x4 vv = vcur[(i % PW) * PW + i / PW];
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -479,14 +480,6 @@ __global__ __launch_bounds__(NW * 64, (WinoGeo<NW, UPS, SC>::OCC)) void conv_win
                             resv[nb][i][j] = *(const f32x4*)(res_b + ((ry + 1) * (p.Wr + 2) + rx + 1) * p.Cout + e_ntile * 32 + nb * 16 + 4 * q);
                     }
         }
-        if constexpr (SC) {      // shortcut output: one low-resolution pixel per tile, no bias (conv_shortcut has none)
-            const int ly = yb >> 1, lx = xb >> 1;
-            if (ly < p.Hi && lx < p.Wi) {
-                float* sc_b = p.sc_out + (size_t)e_b * (size_t)(p.Hi + 2) * (p.Wi + 2) * p.Cout + ((size_t)(ly + 1) * (p.Wi + 2) + lx + 1) * p.Cout;
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) *(f32x4*)(sc_b + e_ntile * 32 + nb * 16 + 4 * q) = acc[NP][nb];
-            }
-        }
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int co = e_ntile * 32 + nb * 16 + 4 * q;
@@ -544,14 +537,22 @@ __global__ __launch_bounds__(NW * 64, (WinoGeo<NW, UPS, SC>::OCC)) void conv_win
     }
 }
 
+// SC = 0: the 9-position form above; SC = 1: the five-product form with the fused shortcut (conv_ups5.h).
+// Instantiated name conv_wino_k<EPI, 0, 4, 1, SC, PERIMG> either way (profiles and bench.py key on it).
+template <int EPI, int ABL = 0, int NW = 4, int UPS = 1, int SC = 0, int PERIMG = 0>
+__global__ __launch_bounds__(NW * 64, (SC ? Ups5Geo::OCC : WinoGeo<NW, UPS>::OCC)) void conv_wino_k(const ConvP p) {
+    static_assert(UPS == 1 && NW == 4, "library kernel: upsample-fused form, 4 waves");
+    if constexpr (SC) conv_ups5_body<EPI, PERIMG>(p);
+    else conv_upw_body<EPI, ABL, NW, UPS, PERIMG>(p);
+}
+
 // Weight transform U = G g G^T, packed as [Cout/32][Cin/16][pos][32 couts][16 floats]; the 16-byte pieces are
 // XOR-swizzled by (cout>>2)&3.  ups = 0: G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (16 positions);
 // ups = 1: G = [[1,1,1],[1,0,0],[0,0,1]] (9 positions, the upsample-fused form above).
-__global__ void pack_wino_k(const float* __restrict__ w, float* __restrict__ dst, int Cout, int Cin, int ups,
-                            const float* __restrict__ wsc = nullptr) {   // wsc: [Cout][Cin] 1x1 shortcut -> position 9 (ups only)
+__global__ void pack_wino_k(const float* __restrict__ w, float* __restrict__ dst, int Cout, int Cin, int ups) {
     constexpr int CH = 16;
     const int npt = ups ? 9 : 16, pw = ups ? 3 : 4;      // transform positions
-    const int np = npt + (wsc ? 1 : 0);                  // U blocks per chunk
+    const int np = npt;                                  // U blocks per chunk
     const size_t total = (size_t)Cout * Cin * np;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         size_t r = i;
@@ -564,7 +565,6 @@ __global__ void pack_wino_k(const float* __restrict__ w, float* __restrict__ dst
         const int e = cl & 3, qs = cl >> 2;
         const int qq = qs ^ ((0 - (j >> 2)) & 3);     // XOR mask (0,3,2,1)[(j>>2)&3]: conflict-free ds_read_b128 of a 16-row fragment
         const int co = n_tile * 32 + j, ci = chunk * CH + qq * 4 + e;
-        if (pos >= npt) { dst[i] = wsc[(size_t)co * Cin + ci]; continue; }
         const float* g = w + ((size_t)co * Cin + ci) * 9;
         const int pr = pos / pw, pc = pos % pw;
         auto G3 = [&](int row, float g0, float g1, float g2) {

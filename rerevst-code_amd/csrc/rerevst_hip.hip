@@ -56,7 +56,7 @@ struct ConvW {           // one convolution's device weights
     float* pk = nullptr;     // kernel-native packed
     float* pk_wino = nullptr; // Winograd F(2x2,3x3) transformed pack for conv_wino_k
     float* pk_ups = nullptr; // upsample-fused transform pack (9 positions) for conv_wino_k<.., UPS = 1> (convs behind a nearest-x2 upsample)
-    float* pk_ups_sc = nullptr; // the same with the block's 1x1 shortcut as tenth position (conv_wino_k<.., UPS = 1, SC = 1>)
+    float* pk_ups_sc = nullptr; // five-product upsample transform (25 positions) + the block's 1x1 shortcut (conv_ups5.h: conv_wino_k<.., UPS = 1, SC = 1>)
     int f43_bit = 0;         // index of the layer in rrv_ctx::f43_layers (encoder conv1_2 .. conv3_4 = 0..6, slice4/3/2.conv2 = 7..9)
     float* pk_f43 = nullptr; // Winograd F(4x4,3x3) transformed pack for conv_f43_k (encoder convs and ResidualBlock.conv2 of the per-frame path)
     float* bias = nullptr;   // [Cout] (zeros for bias-free convs)
@@ -480,16 +480,18 @@ const ConvKey CONV_TABLE[] = {
 };
 
 constexpr int WINO_NW = 8;     // waves per Winograd workgroup (conv_wino.h: 8 = two waves per SIMD, one 16-cout block each)
-constexpr int UPW_NW = 4;      // upsample-fused form: 4 waves, 54 KB of LDS, two workgroups per CU
+constexpr int UPW_NW = 4;      // upsample-fused form: 4 waves, 54 KB of LDS, two workgroups per CU (with the shortcut: 154 KB, one, conv_ups5.h)
+template <int NW, int UPS, int SC>
+constexpr int wino_smem() { return SC ? Ups5Geo::SMEM : WinoGeo<NW, UPS>::SMEM; }
 template <int EPI, int NW, int UPS, int SC, int PERIMG = 0>
 void wino_launch(const ConvP& p, dim3 grid, hipStream_t s) {
-    using Geo = WinoGeo<NW, UPS, SC>;
-    hipLaunchKernelGGL((conv_wino_k<EPI, 0, NW, UPS, SC, PERIMG>), grid, dim3(NW * 64), Geo::SMEM, s, p);
+    constexpr int smem = wino_smem<NW, UPS, SC>();
+    hipLaunchKernelGGL((conv_wino_k<EPI, 0, NW, UPS, SC, PERIMG>), grid, dim3(NW * 64), smem, s, p);
 }
 template <int EPI, int NW, int UPS, int SC, int PERIMG = 0>
 hipError_t wino_attr() {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, WinoGeo<NW, UPS, SC>::SMEM);
-    if (e == hipSuccess && PERIMG) e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WinoGeo<NW, UPS, SC>::SMEM);
+    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_smem<NW, UPS, SC>());
+    if (e == hipSuccess && PERIMG) e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_smem<NW, UPS, SC>());
     return e;
 }
 template <int EPI, int PERIMG>
@@ -518,8 +520,8 @@ struct F43LayKey { int EPI, LAY; ConvFn fn; const char* name; AttrFn attr; };
 // decoder layers: also instantiated with per-image state (grouped multi-style launches)
 #define WKI(EPI) {32, 9, 0, EPI, &wsplit_launch<EPI, 0>, "conv_wino<" #EPI ">", &wsplit_attr<EPI, 1>, &wsplit_launch<EPI, 1>}
 #define UW(EPI) {32, 9, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 0>, "conv_upw<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 0>}
-#define UWS(EPI) {32, 10, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1>}
-#define UWSI(EPI) {32, 10, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1, 1>, &wino_launch<EPI, UPW_NW, 1, 1, 1>}
+#define UWS(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1>}
+#define UWSI(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1, 1>, &wino_launch<EPI, UPW_NW, 1, 1, 1>}
 const ConvKey WINO_TABLE[] = {
     WK(E_RELU), WK(E_RELU | E_POOL), WK(E_RELU | E_NORM1), WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WKI(E_LRELU),      // (E_LRELU per image: filter_down of a batched frame-mode launch without split K)
     WKI(0),     // raw partial sums of a split-K launch
@@ -527,7 +529,7 @@ const ConvKey WINO_TABLE[] = {
     WKI(E_RES), WKI(E_RES | E_NORM2),
     // ResidualBlock.conv1 behind the nearest-x2 upsample (forward pass / preparation pass)
     UW(E_LRELU | E_NORM1), UW(E_LRELU),
-    // the same with the block's 1x1 shortcut fused in as a tenth position (per-frame path)
+    // the same with the block's 1x1 shortcut fused in: five-product form, 25 + 4 positions per 2x2 input pixels (per-frame path)
     UWSI(E_LRELU | E_NORM1),
     // frame mode: raw conv1 output (its statistics are per frame) + fused shortcut
     UWS(E_LRELU),
@@ -596,7 +598,7 @@ int conv(rrv_handle h, const ConvCall& c) {
     if (fuse_sc && !w.pk_ups_sc) return fail(h, RRV_E_ARG, "conv: no shortcut-fused pack for this layer");
     if (!f43 && !c.direct && (c.ups ? w.pk_ups != nullptr : w.pk_wino != nullptr)) {      // every 3x3 layer with a transform-domain pack runs conv_wino_k
         for (const ConvKey& e : WINO_TABLE)
-            if (e.EPI == c.epi && e.UPS == (int)c.ups && (e.TAPS == 10) == fuse_sc) { k = &e; wino = true; break; }
+            if (e.EPI == c.epi && e.UPS == (int)c.ups && (e.TAPS == 29) == fuse_sc) { k = &e; wino = true; break; }
     }
     const int ks = c.ksplit > 1 ? c.ksplit : 1;
     if (ks > 1 && !(wino && !c.ups && w.Cout == 32 && (w.Cin % (32 * ks)) == 0 && c.bias))
@@ -646,20 +648,27 @@ int conv(rrv_handle h, const ConvCall& c) {
     if (c.in->H != eh || c.in->W != ew + (c.in_p8 ? 6 : 0)) return fail(h, RRV_E_ARG, "conv: input geometry mismatch");      // (a P8 twin is 6 pixels wider: conv_f43.h P8_PAD)
     const int oh = (c.epi & E_POOL) ? c.H / 2 : c.H, ow = (c.epi & E_POOL) ? c.W / 2 : c.W;
     if (c.out->H != oh || c.out->W != ow + (c.out_p8 ? 6 : 0)) return fail(h, RRV_E_ARG, "conv: output geometry mismatch");
-    const int TS = f43 ? 32 : 16;                        // pixel tile edge of a work item
+    const int TS = f43 || fuse_sc ? 32 : 16;             // pixel tile edge of a work item
     if (wino) { p.tiles_x = (c.W + TS - 1) / TS; p.tiles_y = (c.H + TS - 1) / TS; }
     double win_frac = 1.0;
     if (wino && c.wy1 > c.wy0 && c.wx1 > c.wx0) {      // output window (on-device crop: nothing outside it is ever read)
         if ((c.wy0 | c.wx0 | c.wy1 | c.wx1) & 15) return fail(h, RRV_E_ARG, "conv: window must be tile aligned");
-        p.ty0 = c.wy0 / TS; p.tx0 = c.wx0 / TS;
-        p.tiles_y = (c.wy1 - c.wy0) / TS; p.tiles_x = (c.wx1 - c.wx0) / TS;
-        win_frac = ((double)(c.wy1 - c.wy0) * (c.wx1 - c.wx0)) / ((double)((c.H + 15) / 16 * 16) * ((c.W + 15) / 16 * 16));
+        int wy0 = c.wy0, wx0 = c.wx0, wy1 = c.wy1, wx1 = c.wx1;
+        if (TS == 32 && !f43) {      // shortcut-fused conv1: round the window out to its 32 x 32 items (the extra outputs are exact)
+            wy0 &= ~31; wx0 &= ~31; wy1 = (wy1 + 31) & ~31; wx1 = (wx1 + 31) & ~31;
+            if (wy1 > ((c.H + 31) & ~31)) wy1 = (c.H + 31) & ~31;
+            if (wx1 > ((c.W + 31) & ~31)) wx1 = (c.W + 31) & ~31;
+        }
+        p.ty0 = wy0 / TS; p.tx0 = wx0 / TS;
+        p.tiles_y = (wy1 - wy0) / TS; p.tiles_x = (wx1 - wx0) / TS;
+        const int TD = fuse_sc ? 32 : 16;          // the shortcut-fused form computes the rounded window's tiles
+        win_frac = ((double)(wy1 - wy0) * (wx1 - wx0)) / ((double)((c.H + TD - 1) / TD * TD) * ((c.W + TD - 1) / TD * TD));
     }
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * c.B), (unsigned)(w.Cout / w.BN));
     if (wino) {   // persistent workgroups (one per CU; two for the upsample-fused form), walking tiles_x*tiles_y*B*(Cout/32) work items
         const unsigned slabs = (unsigned)(w.Cout / 32) * ks;
         const unsigned items = (unsigned)(p.tiles_x * p.tiles_y * c.B) * slabs;
-        const unsigned resident = resident_wgs(h, c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
+        const unsigned resident = resident_wgs(h, fuse_sc ? Ups5Geo::OCC : c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
         grid = dim3(items < resident ? items : resident, 1);
         // slabs of one pixel tile on one XCD (workgroup w runs on XCD w % 8): the raw tile is fetched once per XCD group
         p.xcd_slabs = (grid.x % 8 == 0 && (grid.x / 8) % slabs == 0) ? 1 : 0;
@@ -667,11 +676,11 @@ int conv(rrv_handle h, const ConvCall& c) {
     const double px = (double)c.B * c.H * c.W * win_frac;
     // algorithmic FLOPs = the reference's direct convolution (taps multiply-adds per output);
     // executed: Winograd F(2x2,3x3) needs 16 multiplies per 2x2 outputs (4 per pixel), F(4x4,3x3) 36 per 4x4 (2.25 per pixel), the upsample-fused form 9 (2.25 per pixel)
-    // (a fused shortcut adds its own 1x1 conv at the input resolution: one more GEMM position, 2.5 per output pixel)
+    // (with the fused shortcut the five-product form: 25 + 4 positions per 4x4 outputs, 29/16 per output pixel)
     const double cin = w.Cin;
     const double flops_sc = fuse_sc ? 2.0 * c.B * c.in->H * c.in->W * (double)w.Cout * cin : 0.0;
     const double flops = 2.0 * px * w.Cout * cin * w.taps + flops_sc;
-    const double flops_exec = 2.0 * px * w.Cout * cin * (f43 ? 2.25 : wino ? (c.ups ? (fuse_sc ? 2.5 : 2.25) : 4.0) : (double)w.taps);
+    const double flops_exec = 2.0 * px * w.Cout * cin * (f43 ? 2.25 : wino ? (c.ups ? (fuse_sc ? 29.0 / 16.0 : 2.25) : 4.0) : (double)w.taps);
     const double bytes = 4.0 * ((double)c.B * c.in->H * c.in->W * cin + (double)c.B * oh * ow * w.Cout +
                                 (c.res ? (double)c.B * c.res->H * c.res->W * w.Cout : 0.0) + (double)w.Cout * cin * w.taps +
                                 (fuse_sc ? (double)c.B * c.in->H * c.in->W * w.Cout + (double)w.Cout * cin : 0.0));
@@ -736,12 +745,12 @@ int pack_ups(rrv_handle h, ConvW& w) {
     return RRV_OK;
 }
 
-// the ResidualBlock's conv1 pack with the block's 1x1 shortcut as tenth position
+// the ResidualBlock's conv1 pack for the five-product form, with the block's 1x1 shortcut (conv_ups5.h)
 int pack_ups_sc(rrv_handle h, ConvW& w, const ConvW& sc) {
     if (sc.Cout != w.Cout || sc.Cin != w.Cin || sc.taps != 1) return fail(h, RRV_E_WEIGHTS, "shortcut / conv1 shape mismatch");
-    const size_t total = (size_t)w.Cout * w.Cin * 10;
+    const size_t total = (size_t)w.Cout * w.Cin * Ups5Geo::NUB;
     if (!w.pk_ups_sc) RCHK(dalloc(h, &w.pk_ups_sc, total, false));
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, w.pk_ups_sc, w.Cout, w.Cin, 1, (const float*)sc.raw);
+    hipLaunchKernelGGL(pack_ups5_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, (const float*)sc.raw, w.pk_ups_sc, w.Cout, w.Cin);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }

@@ -91,7 +91,7 @@ static void bench(const char* name, int B, int H, int W, int Cin, int Cout) {
     CK(hipMemcpy(sty, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(bias, 0, Cout * 4)); CK(hipMemset(out, 0, out_f * 4));
     hipLaunchKernelGGL(pack_f43_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w43, Cout, Cin);
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w23, Cout, Cin, 0, (const float*)nullptr);
+    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w23, Cout, Cin, 0);
     CK(hipDeviceSynchronize());
     ConvP p{};
     p.in = in; p.Hi = H; p.Wi = W; p.Cin = Cin; p.out = out; p.H = H; p.W = W; p.Cout = Cout; p.B = B; p.in_bstride0 = 1;

@@ -1,8 +1,6 @@
-// tools/upw_bench.hip — the dominant kernel of the frame, conv_wino_k<E_LRELU | E_NORM1, ABL, 4, UPS = 1, SC = 1>
-// (ResidualBlock.conv1 behind the nearest-x2 upsample + the 1x1 shortcut; rerevst-code_amd/csrc/conv_wino.h), on its three
-// layers at eight 640 x 640 frames per launch, with the library kernel's own ablation switches (template ABL: 1 no LDS-DMA
-// after the first stage, 2 no K-loop barriers, 4 no stores, 32 no epilogue, 128 the MFMA stream alone; the library
-// instantiates ABL = 0 only).
+// tools/upw_bench.hip — the dominant kernel of the frame, conv_wino_k<E_LRELU | E_NORM1, 0, 4, UPS = 1, SC = 1>
+// (ResidualBlock.conv1 behind the nearest-x2 upsample + the 1x1 shortcut, the five-product form of
+// rerevst-code_amd/csrc/conv_ups5.h), on its three layers at sixteen 640 x 640 frames per launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/upw_bench.hip -o tools/bin/upw_bench
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -14,14 +12,14 @@
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 constexpr int EPI = E_LRELU | E_NORM1;
-using Geo = WinoGeo<4, 1, 1>;
+using Geo = Ups5Geo;
 
 template <int ABL>
 float run(ConvP p, int iters) {
-    p.tiles_x = (p.W + 15) / 16; p.tiles_y = (p.H + 15) / 16;
+    p.tiles_x = (p.W + 31) / 32; p.tiles_y = (p.H + 31) / 32;
     const int slabs = p.Cout / 32;
     const int items = p.tiles_x * p.tiles_y * p.B * slabs;
-    dim3 grid(items < 512 ? items : 512, 1);       // two workgroups per CU
+    dim3 grid(items < 256 ? items : 256, 1);       // one workgroup per CU
     p.xcd_slabs = (grid.x % 8 == 0 && (grid.x / 8) % slabs == 0) ? 1 : 0;
     CK(hipFuncSetAttribute((const void*)conv_wino_k<EPI, ABL, 4, 1, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo::SMEM));
     hipEvent_t e0, e1;
@@ -44,7 +42,7 @@ static void layer(const char* name, int B, int Hi, int Wi, int Cin, int Cout) {
     const size_t sc_f = (size_t)B * (Hi + 2) * (Wi + 2) * Cout + 4096;
     float *in, *out, *sc, *w, *wraw, *wsc, *bias, *n1;
     CK(hipMalloc(&in, in_f * 4)); CK(hipMalloc(&out, out_f * 4)); CK(hipMalloc(&sc, sc_f * 4));
-    CK(hipMalloc(&w, (size_t)Cout * Cin * 10 * 4)); CK(hipMalloc(&wraw, (size_t)Cout * Cin * 9 * 4)); CK(hipMalloc(&wsc, (size_t)Cout * Cin * 4));
+    CK(hipMalloc(&w, (size_t)Cout * Cin * Ups5Geo::NUB * 4)); CK(hipMalloc(&wraw, (size_t)Cout * Cin * 9 * 4)); CK(hipMalloc(&wsc, (size_t)Cout * Cin * 4));
     CK(hipMalloc(&bias, Cout * 4)); CK(hipMalloc(&n1, 4 * Cout * 4));
     std::vector<float> hin(in_f), hw((size_t)Cout * Cin * 9), hs((size_t)Cout * Cin), hn(4 * Cout);
     for (auto& v : hin) v = (rand() / (float)RAND_MAX) - 0.5f;
@@ -56,28 +54,24 @@ static void layer(const char* name, int B, int Hi, int Wi, int Cin, int Cout) {
     CK(hipMemcpy(wsc, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(n1, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(bias, 0, Cout * 4)); CK(hipMemset(out, 0, out_f * 4)); CK(hipMemset(sc, 0, sc_f * 4));
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w, Cout, Cin, 1, (const float*)wsc);
+    hipLaunchKernelGGL(pack_ups5_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, (const float*)wsc, w, Cout, Cin);
     CK(hipDeviceSynchronize());
     ConvP p{};
     p.in = in; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.out = out; p.H = H; p.W = W; p.Cout = Cout; p.B = B; p.in_bstride0 = 1;
     p.wpk = w; p.bias = bias; p.n1 = n1; p.n2 = n1; p.sty = n1; p.sc_out = sc;
-    const double fl = 2.0 * B * H * W * (double)Cin * Cout * 2.5;      // executed: 9 positions + the shortcut per 2x2 outputs
+    const double fl = 2.0 * B * H * W * (double)Cin * Cout * 29.0 / 16.0;      // executed: 25 + 4 positions per 4x4 outputs
     run<0>(p, 30);
-    float t0 = 1e9f, t4 = 1e9f, t32 = 1e9f, t33 = 1e9f, t34 = 1e9f, t128 = 1e9f;
-    for (int rep = 0; rep < 3; ++rep) {
-        t0 = fminf(t0, run<0>(p, 10)); t4 = fminf(t4, run<4>(p, 10)); t32 = fminf(t32, run<32>(p, 10));
-        t33 = fminf(t33, run<32 | 1>(p, 10)); t34 = fminf(t34, run<32 | 2>(p, 10)); t128 = fminf(t128, run<32 | 128>(p, 10));
-    }
-    auto f = [&](float ms) { return fl / ms / 1e9 / 157.3; };
-    printf("%-26s as is %.4f ms = %.3f of the fp32-MFMA peak (executed) | no stores %.3f | no epilogue %.3f -> and no LDS-DMA %.3f | and no barriers %.3f | MFMA stream alone %.3f\n",
-           name, t0, f(t0), f(t4), f(t32), f(t33), f(t34), f(t128));
+    float t0 = 1e9f;
+    for (int rep = 0; rep < 3; ++rep) t0 = fminf(t0, run<0>(p, 10));
+    printf("%-28s %.4f ms = %.3f of the fp32-MFMA peak (executed)\n", name, t0, fl / t0 / 1e9 / 157.3);
     for (float* q : {in, out, sc, w, wraw, wsc, bias, n1}) CK(hipFree(q));
 }
 
 int main() {
-    layer("512->256 @80^2->160^2 B8", 8, 80, 80, 512, 256);      // slice4.conv1
-    layer("256->128 @160^2->320^2 B8", 8, 160, 160, 256, 128);   // slice3.conv1
-    layer("128->64 @320^2->640^2 B8", 8, 320, 320, 128, 64);     // slice2.conv1
+    layer("512->256 @80^2->160^2 B16", 16, 80, 80, 512, 256);      // slice4.conv1
+    layer("256->128 @160^2->320^2 B16", 16, 160, 160, 256, 128);   // slice3.conv1
+    layer("128->64 @320^2->640^2 B16", 16, 320, 320, 128, 64);     // slice2.conv1
+    layer("128->64 @70x101->140x202 B4", 4, 70, 101, 128, 64);     // odd low-res size (masked edges)
     layer("128->64 @576^2->1152^2 B1", 1, 576, 576, 128, 64);    // config 5, slice2.conv1
     return 0;
 }

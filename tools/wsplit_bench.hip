@@ -57,7 +57,7 @@ void layer(const char* name, int B, int H, int W, int Cin, int Cout) {
     CK(hipMemcpy(wraw, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(n1, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(sty, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w, Cout, Cin, 0, (const float*)nullptr);
+    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, 0, (const float*)wraw, w, Cout, Cin, 0);
     CK(hipMemset(bias, 0, Cout * 4)); CK(hipMemset(out, 0, out_f * 4));
     ConvP p{};
     p.in = in; p.Hi = H; p.Wi = W; p.Cin = Cin; p.out = out; p.H = H; p.W = W; p.Cout = Cout; p.B = B; p.in_bstride0 = 1;
