@@ -211,7 +211,7 @@ int rrv_feature_cache_info(rrv_handle h, int* resident, int* spilled, size_t* by
 
 /* Stylization(checkpoint, cuda, use_Global=False).transfer (test/framework.py:69-72,106-118 with
  * test/style_network_frame.py): per-frame InstanceNorm statistics (:39-43) and per-frame filter
- * prediction (:53-62,97-105); needs only rrv_prepare_style (style 0).  Host buffers. */
+ * prediction (:53-62,97-105); needs only rrv_prepare_style (style 0), whose saved state is not touched.  Host buffers. */
 int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame_bgr, int H, int W, float* out_bgr);
 
 /* The same model for B frames per call, with the shapes of the global entries: _batch as rrv_transfer_batch (any

@@ -537,15 +537,10 @@ __global__ void sum_parts_lrelu_k(const float* __restrict__ part, float* __restr
     }
 }
 
-// identity saved-statistics entry (mean 0, rstd 1, lo -inf, hi +inf): frame mode has no second
-// normalisation after the filters (test/style_network_frame.py AdaIN_filter: results*std+mean)
-__global__ void identity_norm_k(float* __restrict__ n, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) { n[c] = 0.f; n[C + c] = 1.f; n[2 * C + c] = -3.0e38f; n[3 * C + c] = 3.0e38f; }
-}
-
-// state sets of a batched frame-mode launch: set b (count floats apart, blockIdx.y = b) := the style's blob, with the
-// identity entry of identity_norm_k at n_off (C channels) — every other per-frame entry is overwritten by the launch itself
+// state sets of a frame-mode launch: set b (count floats apart, blockIdx.y = b) := the style's blob, with an identity
+// saved-statistics entry (mean 0, rstd 1, lo -inf, hi +inf) at n_off (C channels): frame mode has no second normalisation
+// after the filters (test/style_network_frame.py AdaIN_filter: results*std+mean).  Every other per-frame entry is
+// overwritten by the launch itself.
 __global__ void frame_sets_init_k(const float* __restrict__ blob, float* __restrict__ sets, int count, int n_off, int C) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;

@@ -85,9 +85,10 @@ struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRA
     int B = 0, H = 0, W = 0;
     unsigned stamp = 0;
     unsigned gen = 0;
-    Tens d, f1, f2, f3, xs4, a4, o4, xs3, a3, o3, xs2, a2, o2;
+    Tens d, f[3];           // KernelFilter: the 32-channel intermediate, the outputs of Filter1..3
+    Tens xs[3], a[3], o[3]; // per residual block (BLKS: slice4, slice3, slice2): shortcut, conv1 output, block output
     Tens dpart;             // [.., 32 * split]: partial sums of the split-K 512->32 KernelFilter convolution (kf_split > 1 only)
-    Tens qa4, qa3, qa2;     // channel-chunk-major twins of a4 / a3 / a2 (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above)
+    Tens qa[3];             // channel-chunk-major twins of a[0..2] (ResidualBlock.conv1's output when conv2 runs conv_f43_k; EncPlan::q11 .. above)
     // batched frame mode only (frame_mode_device): per-image scratch, image b in interior row b (frame_row): chan_stat1_k partials
     // (min(H_l, 512) x 3 x C_l doubles <= 3 x 64 x H), rect_sums_k's nine sums [9][512], pred_mean_k's two predicted means [2][32]
     Tens spart, srect, scm;
@@ -124,10 +125,10 @@ const TSpec<EncPlan> ENC_T[] = {
     {offsetof(EncPlan, q31), 2, 256, TS_P8}, {offsetof(EncPlan, q32), 2, 256, TS_P8}, {offsetof(EncPlan, q33), 2, 256, TS_P8},
 };
 const TSpec<DecPlan> DEC_T[] = {
-    {offsetof(DecPlan, d), 3, 32}, {offsetof(DecPlan, f1), 3, 512}, {offsetof(DecPlan, f2), 3, 512}, {offsetof(DecPlan, f3), 3, 512}, {offsetof(DecPlan, xs4), 3, 256},
-    {offsetof(DecPlan, a4), 2, 256}, {offsetof(DecPlan, o4), 2, 256}, {offsetof(DecPlan, xs3), 2, 128}, {offsetof(DecPlan, a3), 1, 128}, {offsetof(DecPlan, o3), 1, 128},
-    {offsetof(DecPlan, xs2), 1, 64}, {offsetof(DecPlan, a2), 0, 64}, {offsetof(DecPlan, o2), 0, 64}, {offsetof(DecPlan, dpart), 3, 32, TS_SPLIT},
-    {offsetof(DecPlan, qa4), 2, 256, TS_P8}, {offsetof(DecPlan, qa3), 1, 128, TS_P8}, {offsetof(DecPlan, qa2), 0, 64, TS_P8},
+    {offsetof(DecPlan, d), 3, 32}, {offsetof(DecPlan, f[0]), 3, 512}, {offsetof(DecPlan, f[1]), 3, 512}, {offsetof(DecPlan, f[2]), 3, 512}, {offsetof(DecPlan, xs[0]), 3, 256},
+    {offsetof(DecPlan, a[0]), 2, 256}, {offsetof(DecPlan, o[0]), 2, 256}, {offsetof(DecPlan, xs[1]), 2, 128}, {offsetof(DecPlan, a[1]), 1, 128}, {offsetof(DecPlan, o[1]), 1, 128},
+    {offsetof(DecPlan, xs[2]), 1, 64}, {offsetof(DecPlan, a[2]), 0, 64}, {offsetof(DecPlan, o[2]), 0, 64}, {offsetof(DecPlan, dpart), 3, 32, TS_SPLIT},
+    {offsetof(DecPlan, qa[0]), 2, 256, TS_P8}, {offsetof(DecPlan, qa[1]), 1, 128, TS_P8}, {offsetof(DecPlan, qa[2]), 0, 64, TS_P8},
     {offsetof(DecPlan, spart), 0, 6, TS_FRAME | TS_PER_ROW}, {offsetof(DecPlan, srect), 0, 9 * 512 / 64, TS_FRAME}, {offsetof(DecPlan, scm), 0, 1, TS_FRAME},
 };
 // levels count from the full-resolution decoder output: relu4_1 (the plan's hh x ww) is level 3
@@ -208,10 +209,9 @@ struct rrv_ctx {
     uint8_t* d_u8 = nullptr; size_t d_u8_cap = 0;
     float* d_outf = nullptr; size_t d_outf_cap = 0;
     // fixed-size scratch, one allocation made by rrv_finalize_weights: chan_stats partials and means; streaming compute(): second
-    // partial buffer, two running accumulators [4][512] doubles; frame mode: nine rectangle sums [9][512], predicted content means
-    // [2][32]; compute(): the predicted content means
+    // partial buffer, two running accumulators [4][512] doubles; compute(): the predicted content means
     double *stat_part = nullptr, *stat_part2 = nullptr, *stat_acc = nullptr;
-    float *stat_mean = nullptr, *frame_S = nullptr, *frame_cmean = nullptr, *prep_cmean = nullptr;
+    float *stat_mean = nullptr, *prep_cmean = nullptr;
     size_t ws_cap = (size_t)64 << 30;          // preparation-pass workspace above which compute() streams groups of frames
     int last_groups = 0, last_group_size = 0; size_t last_ws_bytes = 0;
     PrepPlan prep;
@@ -235,7 +235,7 @@ struct rrv_ctx {
     unsigned f43_layers = F43_DEFAULT_LAYERS;   // which of the packed layers may run on conv_f43_k (RRV_F43_LAYERS overrides: experiments / parity attribution)
     bool illcond = false;             // some computed style's state is ill-conditioned (StyleState::illcond)
     bool enc_p8_tables = false;       // use_f43 prices the encoder layers with conv_f43_k's P8-input ratios (set by run_encoder while it decides / runs a P8 chain)
-    int p8 = 3;                       // channel-chunk-major tensors in front of conv_f43_k launches (conv_f43.h LAY): bit 0 the encoder chain (EncPlan::q11 ..), bit 1 ResidualBlock.conv2's input (DecPlan::qa4 ..); RRV_P8=0: NHWC everywhere (A/B, same bits)
+    int p8 = 3;                       // channel-chunk-major tensors in front of conv_f43_k launches (conv_f43.h LAY): bit 0 the encoder chain (EncPlan::q11 ..), bit 1 ResidualBlock.conv2's input (DecPlan::qa); RRV_P8=0: NHWC everywhere (A/B, same bits)
     bool f43_path = false;            // true inside transfer_device only: the preparation pass (prepare_style / add / compute, frame mode) always runs F(2x2,3x3)
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
@@ -813,6 +813,12 @@ int pointwise(rrv_handle h, const Tens& x, Tens& y, const float* mean, const flo
     stamp(h, &y, x.B);
     return launch(h, "pointwise", 0, 0, [&] { hipLaunchKernelGGL(pointwise_k, dim3(blocks), dim3(256), 0, h->stream, p); });
 }
+// y = x normalised with the saved statistics norm[n] of state `st` (no clamp) [+ res, upsampled 2x] [* style std + style mean of entry sty]
+int apply_norm(rrv_handle h, const Tens& x, Tens& y, const float* st, int n, const Tens* res = nullptr, int sty = -1, long par_bstride = 0) {
+    const float* m = st + SL.norm[n];
+    const float* s = sty < 0 ? nullptr : st + SL.sty[sty];
+    return pointwise(h, x, y, m, m + x.C, false, res, res ? 2 : 0, s, s ? s + x.C : nullptr, nullptr, nullptr, par_bstride);
+}
 
 // ---- folded KernelFilter weights for a state blob ------------------------------------------
 // (both folded layers run the row-split transform-domain kernel everywhere — per-frame path and compute()'s frame-0
@@ -1101,27 +1107,45 @@ int filter_down(rrv_handle h, const Tens* cur, DecPlan& d, int f, int B) {
     });
 }
 
+// KernelFilter.upsample (d.d -> out) + the residual `cur`, with the per-image folded weights of a state_images launch.  Filter3's
+// epilogue also applies Decoder.norm[1] and its AdaIN affine (frame mode: an identity entry, then * style_std + style_mean).
+int filter_up(rrv_handle h, const Tens* cur, DecPlan& d, Tens* out, int f, int B) {
+    const float* st = h->cur->active;
+    ConvCall u{&d.d, out, &h->cur->fold_up[f], cur->H, cur->W}; u.B = B;
+    if (h->state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
+    u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
+    if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }
+    return conv(h, u);
+}
+
 struct Win { int y0, x0, y1, x1; };     // output window in pixels, tile aligned; y1 == 0: everything
 
-int resblock_frame(rrv_handle h, int B, const char* blk, const Tens& in, Tens& xs, Tens& a, Tens& o, int n1, int n2, int nada, int sty,
-                   const Win* wa = nullptr, const Win* wo = nullptr, Tens* qa = nullptr) {
+// The decoder's three residual blocks: output channels, the saved-statistics entries of norm1 / norm2 / the AdaIN norm behind
+// the block, and the style entry of that AdaIN.  Block k works on the plans' xs[k], a[k], o[k].
+struct BlkDesc { const char* name; int cout, n1, n2, nada, sty; };
+const BlkDesc BLKS[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 128, N_S3N1, N_S3N2, N_DEC3, 1}, {"slice2", 64, N_S2N1, N_S2N2, N_DEC4, 0}};
+
+// block k of the per-frame path, fused across its normalisation layers (saved statistics)
+int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr) {
+    const BlkDesc& b = BLKS[k];
+    Tens &xs = d.xs[k], &a = d.a[k], &o = d.o[k], &qa = d.qa[k];
     const float* st = h->cur->active;
-    const std::string p = std::string("Decoder.") + blk;
+    const std::string p = std::string("Decoder.") + b.name;
     ConvCall c;
     // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin,
     // where the plan has one (dec_plan)
-    const bool p8 = qa && qa->p && use_f43(h, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
+    const bool p8 = qa.p && use_f43(h, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
                     !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
-    Tens* a_in = p8 ? qa : &a;
+    Tens* a_in = p8 ? &qa : &a;
     // conv1 behind the upsample and, in the same kernel, the 1x1 shortcut at the input resolution: up(conv1x1(x)) == conv1x1(up(x))
-    c = ConvCall{&in, a_in, &h->conv[p + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1; c.n1 = st + SL.norm[n1];
+    c = ConvCall{&in, a_in, &h->conv[p + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1; c.n1 = st + SL.norm[b.n1];
     c.sc_out = &xs; c.out_p8 = p8;
     if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
     if (wa) { c.wy0 = wa->y0; c.wx0 = wa->x0; c.wy1 = wa->y1; c.wx1 = wa->x1; }
     RCHK(conv(h, c));
     c = ConvCall{a_in, &o, &h->conv[p + ".conv2"], a.H, a.W}; c.B = B; c.in_p8 = p8;
     if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
-    c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[n2]; c.res = &xs; c.n2 = st + SL.norm[nada]; c.sty = st + SL.sty[sty];
+    c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[b.n2]; c.res = &xs; c.n2 = st + SL.norm[b.nada]; c.sty = st + SL.sty[b.sty];
     if (wo) { c.wy0 = wo->y0; c.wx0 = wo->x0; c.wy1 = wo->y1; c.wx1 = wo->x1; }
     RCHK(conv(h, c));
     return RRV_OK;
@@ -1190,18 +1214,11 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         RCHK(run_encoder(h, e, d_in, 0, st + SL.norm[N_DEC0], pc, B));
     }
     const Tens* cur = &e.c41;
-    Tens* fo[3] = {&d.f1, &d.f2, &d.f3};
     for (int f = 0; f < 3; ++f) {
         RCHK(filter_down(h, cur, d, f, B));
-        ConvCall u{&d.d, fo[f], &h->cur->fold_up[f], cur->H, cur->W}; u.B = B;
-        if (h->state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
-        u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
-        if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }
-        RCHK(conv(h, u));
-        cur = fo[f];
+        RCHK(filter_up(h, cur, d, &d.f[f], f, B));
+        cur = &d.f[f];
     }
-    RCHK(resblock_frame(h, B, "slice4", d.f3, d.xs4, d.a4, d.o4, N_S4N1, N_S4N2, N_DEC2, 2, nullptr, nullptr, &d.qa4));
-    RCHK(resblock_frame(h, B, "slice3", d.o4, d.xs3, d.a3, d.o3, N_S3N1, N_S3N2, N_DEC3, 1, nullptr, nullptr, &d.qa3));
     // On-device crop: nothing outside the crop window is delivered, so the full-resolution layers only compute the
     // tiles the window (plus one halo pixel per 3x3 layer) needs; results inside the window are unchanged.  One level
     // down (320^2) the tile-rounded window already covers the frame for the reference's 64-pixel pad.
@@ -1224,13 +1241,50 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         }
         wa = grow(wo, 1);          // slice2.conv1 output (and, halved, the shortcut) feeding that
     }
-    RCHK(resblock_frame(h, B, "slice2", d.o3, d.xs2, d.a2, d.o2, N_S2N1, N_S2N2, N_DEC4, 0, roi ? &wa : nullptr, roi ? &wo : nullptr, &d.qa2));
-    RCHK(run_last(h, d.o2, B, Ho, Wo, d_out, fmt, d.pre, pc, roi ? &wl : nullptr));
+    for (int k = 0; k < 3; ++k) {       // the windows apply to the full-resolution block only
+        const bool win = roi && k == 2;
+        RCHK(resblock_frame(h, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr));
+    }
+    RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, fmt, d.pre, pc, roi ? &wl : nullptr));
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
     }
     if (h->debug) RCHK(debug_verify(h, "transfer"));
+    return RRV_OK;
+}
+
+// ---- the unfused residual blocks -----------------------------------------------------------------------------------------
+// Decoder.slice4 / slice3 / slice2 where the statistics of the normalisation layers are not known yet, so the chain stops at
+// each of the nine sync points 3 k + {0: norm1, 1: norm2, 2: the AdaIN norm} of block k (BLKS):
+//   conv1 behind the upsample -> [stat] -> normalise -> conv2 -> [stat] -> normalise + shortcut -> [stat] -> normalise + AdaIN.
+// stat(t, n, point) puts the statistics of t into norm[n] of `st` (of every image's set, par_bstride apart) — or finds them
+// there — and returns RRV_OK, or WALK_STOP to end the walk at that point with nothing further launched.  B images from `in`
+// through xs[k], a[k], o[k].  fused_sc: conv1's kernel also writes the 1x1 shortcut; otherwise conv_shortcut is its own launch,
+// issued once norm2's statistic is taken (the first place that needs it).  last_adain: whether o[2] is normalised at the end.
+enum { WALK_STOP = 1 };     // (RRV_E_* are negative)
+template <class Stat>
+int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], const float* st, long par_bstride, bool fused_sc,
+                   bool last_adain, Stat&& stat) {
+    const Tens* in = &x;
+    for (int k = 0; k < 3; ++k) {
+        const BlkDesc& b = BLKS[k];
+        const std::string p = std::string("Decoder.") + b.name;
+        const int H2 = in->H * 2, W2 = in->W * 2;
+        ConvCall c;
+        c = ConvCall{in, &a[k], &h->conv[p + ".conv1"], H2, W2}; c.B = B; c.ups = true; c.epi = E_LRELU;
+        if (fused_sc) c.sc_out = &xs[k];
+        RCHK(conv(h, c));
+        RCHK(stat(a[k], b.n1, 3 * k));
+        RCHK(apply_norm(h, a[k], a[k], st, b.n1, nullptr, -1, par_bstride));
+        c = ConvCall{&a[k], &o[k], &h->conv[p + ".conv2"], H2, W2}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
+        RCHK(stat(o[k], b.n2, 3 * k + 1));
+        if (!fused_sc) { c = ConvCall{in, &xs[k], &h->conv[p + ".conv_shortcut"], in->H, in->W}; c.B = B; RCHK(conv(h, c)); }
+        RCHK(apply_norm(h, o[k], o[k], st, b.n2, &xs[k], -1, par_bstride));
+        RCHK(stat(o[k], b.nada, 3 * k + 2));     // (a fused pointwise + statistics pass measured slower than the two kernels)
+        if (k < 2 || last_adain) RCHK(apply_norm(h, o[k], o[k], st, b.nada, nullptr, b.sty, par_bstride));
+        in = &o[k];
+    }
     return RRV_OK;
 }
 
@@ -1266,7 +1320,7 @@ int compute_style(rrv_handle h, int sid) {
         // norm[0].compute on the batch (style_network_global.py:396); the style half of the filter predictions
         // (normalized_style :397 through F.down_sample, :161-172) was evaluated once in prepare_style (S.smean)
         RCHK(chan_stats(h, content, 1, st + SL.norm[N_DEC0]));
-        RCHK(pointwise(h, content, cn, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
+        RCHK(apply_norm(h, content, cn, st, N_DEC0));
         Tens* cur = &cn; Tens* other = &nxt;
         for (int f = 0; f < 3; ++f) {
             char pre[64];
@@ -1290,30 +1344,9 @@ int compute_style(rrv_handle h, int sid) {
         h->active_src = -1;   // folded weights now belong to this style's blob; re-activate below
         // AdaIN_compute(1) (style_network_global.py:428)
         RCHK(chan_stats(h, *cur, 1, st + SL.norm[N_DEC1]));
-        RCHK(pointwise(h, *cur, *cur, st + SL.norm[N_DEC1], st + SL.norm[N_DEC1] + 512, false, nullptr, 0, st + SL.sty[3], st + SL.sty[3] + 512));
-        struct Blk { const char* name; int cout, n1, n2, nada, sty; };
-        const Blk blks[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 128, N_S3N1, N_S3N2, N_DEC3, 1}, {"slice2", 64, N_S2N1, N_S2N2, N_DEC4, 0}};
-        const Tens* in = cur;
-        for (int k = 0; k < 3; ++k) {
-            const Blk& b = blks[k];
-            const std::string p = std::string("Decoder.") + b.name;
-            Tens &xs = P.xs[k], &a = P.a[k], &o = P.o[k];
-            const int H2 = in->H * 2, W2 = in->W * 2;
-            ConvCall c;
-            c = ConvCall{in, &xs, &h->conv[p + ".conv_shortcut"], in->H, in->W}; c.B = B; RCHK(conv(h, c));
-            c = ConvCall{in, &a, &h->conv[p + ".conv1"], H2, W2}; c.B = B; c.ups = true; c.epi = E_LRELU; RCHK(conv(h, c));
-            RCHK(chan_stats(h, a, 1, st + SL.norm[b.n1]));
-            RCHK(pointwise(h, a, a, st + SL.norm[b.n1], st + SL.norm[b.n1] + b.cout, false, nullptr, 0, nullptr, nullptr));
-            c = ConvCall{&a, &o, &h->conv[p + ".conv2"], H2, W2}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
-            RCHK(chan_stats(h, o, 1, st + SL.norm[b.n2]));
-            RCHK(pointwise(h, o, o, st + SL.norm[b.n2], st + SL.norm[b.n2] + b.cout, false, &xs, 2, nullptr, nullptr));
-            // AdaIN_compute(k+2)
-            RCHK(chan_stats(h, o, 1, st + SL.norm[b.nada]));
-            if (k < 2)
-                RCHK(pointwise(h, o, o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout));
-            in = &o;
-        }
-        return RRV_OK;
+        RCHK(apply_norm(h, *cur, *cur, st, N_DEC1, nullptr, 3));
+        // AdaIN_compute(k + 2) ends block k; nothing reads the last block's normalised output
+        return unfused_blocks(h, B, *cur, P.xs, P.a, P.o, st, 0, false, false, [&](const Tens& t, int n, int) { return chan_stats(h, t, 1, st + SL.norm[n]); });
     };
     int rc = body();
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute");
@@ -1325,111 +1358,28 @@ int compute_style(rrv_handle h, int sid) {
 
 // ---- frame mode (Stylization(use_Global=False), test/style_network_frame.py) ----------------------------------------
 // Per-frame InstanceNorm statistics (:39-43: mean / biased variance over (H,W), no clamp) and per-frame filter prediction
-// (:53-62, :97-105).  One frame per call, so Q1's batch collapse does not arise and the fused per-frame kernels run
+// (:53-62, :97-105).  Every frame is a batch of its own, so Q1's batch collapse does not arise and the fused per-frame kernels run
 // wherever no statistic separates producer and consumer: encoder -> [stats] -> normalise -> per filter {rectangle sums ->
 // predicted means -> FC -> fold -> 512->32 (LReLU) -> 32->512 + residual} (the last one also applies the AdaIN affine,
 // :326-339 ends with * style_std + style_mean and no norm) -> per block {conv1 behind the upsample with the fused
 // shortcut (raw) -> [stats] -> normalise -> conv2 (raw) -> [stats] -> normalise + shortcut -> [stats] -> normalise +
 // AdaIN} -> slice1.  [stats] = ONE read of the tensor (chan_stat1_k) + a merge; the filter predictors' conv + mean is
 // replaced by nine rectangle sums and a 64 x 4608 product (prep_kernels.h), their style half is cached per style.
-int chan_stats1(rrv_handle h, const Tens& t, float* out) {
-    const long npix = (long)t.B * t.H * t.W;
-    int nblk = t.B * t.H;                    // whole rows per block; ~2 blocks per CU keep the merge short
-    if (nblk > 512) nblk = 512;
-    if (nblk < 1) nblk = 1;
-    if (t.C > 512) return fail(h, RRV_E_ARG, "chan_stats: more than 512 channels");
-    StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, h->stat_part, 0, 0};
-    RCHK(launch(h, "chan_stat1", 0, 4.0 * npix * t.C, [&] { hipLaunchKernelGGL(chan_stat1_k, dim3(nblk), dim3(256), 0, h->stream, sp); }));
-    return launch(h, "chan_stat1_final", 0, 0, [&] {
-        hipLaunchKernelGGL(chan_stat1_final_k, dim3((t.C + 3) / 4), dim3(256), 0, h->stream, (const double*)h->stat_part, nblk, t.C, out);
-    });
-}
-
-int frame_mode_forward(rrv_handle h, const uint8_t* d_img, int H, int W, void* d_out, OutFmt fmt) {
-    StyleState& S = h->styles[0];
-    float* st = S.blob;
-    h->stream = h->streams[0];
-    const int Ho = H / 8 * 8, Wo = W / 8 * 8;       // any frame size, as in transfer_device
-    EncPlan& e = pick_plan(h, h->enc_frame[0], 1, H, W);
-    DecPlan& d = pick_plan(h, h->dec[0], 1, Ho, Wo);
-    RCHK(enc_plan(h, e, 1, H, W, true));
-    RCHK(dec_plan(h, d, 1, Ho, Wo));
-    e.gen = d.gen = ++h->launch_gen;
-    constexpr int RS_PARTS = 1;      // (splitting the pixels over several blocks per channel quad measured slower: the merge in pred_mean_k costs more; h->frame_S holds one part)
-    RCHK(run_encoder(h, e, d_img, 0, nullptr, nullptr, 1));
-    Tens c41 = e.c41; c41.B = 1;          // views of one image (plans are grow-only)
-    const int hh = c41.H, ww = c41.W;
-    // Decoder.norm[0] with this frame's statistics
-    RCHK(chan_stats1(h, c41, st + SL.norm[N_DEC0]));
-    RCHK(pointwise(h, c41, c41, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
-    hipLaunchKernelGGL(identity_norm_k, dim3(2), dim3(256), 0, h->stream, st + SL.norm[N_DEC1], 512);
-    HIPCHK(hipGetLastError());
-    Tens f1 = d.f1, f2 = d.f2, f3 = d.f3, xs4 = d.xs4, a4 = d.a4, o4 = d.o4, xs3 = d.xs3, a3 = d.a3, o3 = d.o3, xs2 = d.xs2, a2 = d.a2, o2 = d.o2;
-    for (Tens* t : {&f1, &f2, &f3, &xs4, &a4, &o4, &xs3, &a3, &o3, &xs2, &a2, &o2}) t->B = 1;
-    const Tens* cur = &c41;
-    Tens* fo[3] = {&f1, &f2, &f3};
-    for (int f = 0; f < 3; ++f) {
-        RCHK(launch(h, "rect_sums", 0, 4.0 * hh * ww * 512, [&] {
-            hipLaunchKernelGGL(rect_sums_k, dim3(128, RS_PARTS), dim3(256), 0, h->stream, (const float*)cur->p, hh, ww, 512, h->frame_S);
-        }));
-        for (int g = 0; g < 2; ++g) {
-            char key[96];
-            snprintf(key, sizeof key, "Decoder.Filter%d.F%d.down_sample.0", f + 1, g + 1);
-            const ConvW& wp = h->conv[key];
-            RCHK(launch(h, "pred_mean", 2.0 * 32 * 4608, 0, [&] {
-                hipLaunchKernelGGL(pred_mean_k, dim3(32), dim3(256), 0, h->stream, (const float*)wp.raw, (const float*)wp.bias, (const float*)h->frame_S, RS_PARTS, 512,
-                                   1.0 / ((double)hh * ww), h->frame_cmean + 32 * g);
-            }));
-            hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + g], (const float*)h->fc_b[2 * f + g],
-                               (const float*)(h->frame_cmean + 32 * g), (const float*)(S.smean + (2 * f + g) * 32), st + SL.filt[2 * f + g]);
-            HIPCHK(hipGetLastError());
-        }
-        RCHK(fold_filters(h, st, f));
-        RCHK(filter_down(h, cur, d, f, 1));
-        ConvCall u{&d.d, fo[f], &h->cur->fold_up[f], hh, ww};
-        u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
-        if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }     // identity norm, then * style_std + style_mean
-        RCHK(conv(h, u));
-        cur = fo[f];
-    }
-    h->active_src = -1;        // the folded filter weights are this frame's
-    struct Blk { const char* name; Tens *xs, *a, *o; int cout, n1, n2, nada, sty; };
-    const Blk blks[3] = {{"slice4", &xs4, &a4, &o4, 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", &xs3, &a3, &o3, 128, N_S3N1, N_S3N2, N_DEC3, 1},
-                         {"slice2", &xs2, &a2, &o2, 64, N_S2N1, N_S2N2, N_DEC4, 0}};
-    const Tens* in = cur;
-    for (int k = 0; k < 3; ++k) {
-        const Blk& b = blks[k];
-        const std::string p = std::string("Decoder.") + b.name;
-        ConvCall c;
-        c = ConvCall{in, b.a, &h->conv[p + ".conv1"], b.a->H, b.a->W}; c.ups = true; c.epi = E_LRELU; c.sc_out = b.xs; RCHK(conv(h, c));
-        RCHK(chan_stats1(h, *b.a, st + SL.norm[b.n1]));
-        RCHK(pointwise(h, *b.a, *b.a, st + SL.norm[b.n1], st + SL.norm[b.n1] + b.cout, false, nullptr, 0, nullptr, nullptr));
-        c = ConvCall{b.a, b.o, &h->conv[p + ".conv2"], b.a->H, b.a->W}; c.epi = E_LRELU; RCHK(conv(h, c));
-        RCHK(chan_stats1(h, *b.o, st + SL.norm[b.n2]));
-        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.n2], st + SL.norm[b.n2] + b.cout, false, b.xs, 2, nullptr, nullptr));
-        RCHK(chan_stats1(h, *b.o, st + SL.norm[b.nada]));     // (a fused pointwise + statistics pass measured slower than the two kernels)
-        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout));
-        in = b.o;
-    }
-    RCHK(run_last(h, o2, 1, Ho, Wo, d_out, fmt, d.pre, nullptr));
-    if (h->debug) RCHK(debug_verify(h, "transfer (frame mode)"));
-    return RRV_OK;
-}
 
 // ---- batched frame mode: B <= MS_GROUP_MAX frames per launch sequence ----------------------------------------------------
-// frame_mode_forward's chain for B frames at once.  Every frame's statistics, predicted filters and folded KernelFilter weights go
+// The chain above for B frames at once (the one-frame entry is B = 1).  Every frame's statistics, predicted filters and folded KernelFilter weights go
 // to its own state set (h->cur + b: the sets MS_GROUP_MAX * slot .., initialised from style 0's blob), and every per-frame kernel
 // runs over the B images with image b's result in set b or in row b of the plan's scratch (DecPlan::spart ..).  The statistics
-// kernels keep the one-image block partition per image and the convolutions are F(2x2,3x3) (f43_path stays false), so image b
-// gets the bits of frame_mode_forward on that frame alone.  Style 0's blob is only read.
+// kernels partition every image on its own (chan_stats1_images) and the convolutions are F(2x2,3x3) (f43_path stays false), so
+// an image's bits do not depend on the batch it rides in.  Style 0's blob is only read.
 
 // interior row b of a TS_FRAME scratch tensor (ring layout, B = 1, H = images): contiguous, frame_row_stride floats apart
 float* frame_row(const Tens& t) { return t.p + (size_t)(t.W + 3) * t.C; }
 long frame_row_stride(const Tens& t) { return (long)(t.W + 2) * t.C; }
 
-// per-image statistics of the t.B images of t into norm entry `n` of each image's state set (chan_stats1 per image)
+// per-image statistics of the t.B images of t into norm entry `n` of each image's state set: ONE read of the tensor + a merge
 int chan_stats1_images(rrv_handle h, const Tens& t, const DecPlan& d, int n) {
-    const int nblk = t.H < 512 ? t.H : 512;        // chan_stats1's min(B * H, 512) at B = 1: the same block partition per image
+    const int nblk = t.H < 512 ? t.H : 512;        // per image min(H, 512) blocks of whole rows (~2 blocks per CU keep the merge short), whatever the batch
     if ((size_t)nblk * 6 * t.C > (size_t)d.spart.W * d.spart.C || t.B > d.spart.H) return fail(h, RRV_E_ARG, "chan_stats1_images: scratch too small");
     double* part = (double*)frame_row(d.spart);
     const long pbs = frame_row_stride(d.spart) / 2;
@@ -1467,9 +1417,12 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     const int hh = c41.H, ww = c41.W;
     // Decoder.norm[0] with each frame's statistics
     RCHK(chan_stats1_images(h, c41, d, N_DEC0));
-    RCHK(pointwise(h, c41, c41, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, PS));
-    Tens f1 = d.f1, f2 = d.f2, f3 = d.f3, xs4 = d.xs4, a4 = d.a4, o4 = d.o4, xs3 = d.xs3, a3 = d.a3, o3 = d.o3, xs2 = d.xs2, a2 = d.a2, o2 = d.o2;
-    for (Tens* t : {&f1, &f2, &f3, &xs4, &a4, &o4, &xs3, &a3, &o3, &xs2, &a2, &o2}) t->B = B;
+    RCHK(apply_norm(h, c41, c41, st, N_DEC0, nullptr, -1, PS));
+    Tens fo[3], xs[3], a[3], o[3];
+    for (int k = 0; k < 3; ++k) {
+        fo[k] = d.f[k]; xs[k] = d.xs[k]; a[k] = d.a[k]; o[k] = d.o[k];
+        fo[k].B = xs[k].B = a[k].B = o[k].B = B;
+    }
     // per image: rect_sums_k's sums and pred_mean_k's means in rows of the scratch, the FC into its state set; one fold launch per
     // step for all sets (fold_filters nsets), the KernelFilter convs with per-image weights (state_images; one image: the shared ones)
     float* const Sr = frame_row(d.srect);
@@ -1478,8 +1431,8 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     stamp(h, &d.srect, B); stamp(h, &d.scm, B);
     h->state_images = B > 1 ? B : 0;
     const Tens* cur = &c41;
-    Tens* fo[3] = {&f1, &f2, &f3};
     for (int f = 0; f < 3; ++f) {
+        // (one part: splitting an image's pixels over several blocks per channel quad measured slower, the merge in pred_mean_k costs more)
         RCHK(launch(h, "rect_sums", 0, 4.0 * B * hh * ww * 512, [&] {
             hipLaunchKernelGGL(rect_sums_k, dim3(128, 1, B), dim3(256), 0, h->stream, (const float*)cur->p, hh, ww, 512, Sr, Sbs);
         }));
@@ -1498,36 +1451,17 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
         }
         RCHK(fold_filters(h, st, f, B));
         RCHK(filter_down(h, cur, d, f, B));
-        ConvCall u{&d.d, fo[f], &h->cur->fold_up[f], hh, ww}; u.B = B;
-        if (h->state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
-        u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
-        if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }     // identity norm, then * style_std + style_mean
-        RCHK(conv(h, u));
-        cur = fo[f];
+        RCHK(filter_up(h, cur, d, &fo[f], f, B));
+        cur = &fo[f];
     }
     h->state_images = 0;
-    struct Blk { const char* name; Tens *xs, *a, *o; int cout, n1, n2, nada, sty; };
-    const Blk blks[3] = {{"slice4", &xs4, &a4, &o4, 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", &xs3, &a3, &o3, 128, N_S3N1, N_S3N2, N_DEC3, 1},
-                         {"slice2", &xs2, &a2, &o2, 64, N_S2N1, N_S2N2, N_DEC4, 0}};
-    const Tens* in = cur;
-    for (int k = 0; k < 3; ++k) {       // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
-        const Blk& b = blks[k];
-        const std::string p = std::string("Decoder.") + b.name;
-        ConvCall c;
-        c = ConvCall{in, b.a, &h->conv[p + ".conv1"], b.a->H, b.a->W}; c.B = B; c.ups = true; c.epi = E_LRELU; c.sc_out = b.xs; RCHK(conv(h, c));
-        RCHK(chan_stats1_images(h, *b.a, d, b.n1));
-        RCHK(pointwise(h, *b.a, *b.a, st + SL.norm[b.n1], st + SL.norm[b.n1] + b.cout, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, PS));
-        c = ConvCall{b.a, b.o, &h->conv[p + ".conv2"], b.a->H, b.a->W}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
-        RCHK(chan_stats1_images(h, *b.o, d, b.n2));
-        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.n2], st + SL.norm[b.n2] + b.cout, false, b.xs, 2, nullptr, nullptr, nullptr, nullptr, PS));
-        RCHK(chan_stats1_images(h, *b.o, d, b.nada));
-        RCHK(pointwise(h, *b.o, *b.o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout,
-                       nullptr, nullptr, PS));
-        in = b.o;
-    }
-    RCHK(run_last(h, o2, B, Ho, Wo, d_out, fmt, d.pre, pc));
+    // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
+    RCHK(unfused_blocks(h, B, *cur, xs, a, o, st, PS, true, true, [&](const Tens& t, int n, int) { return chan_stats1_images(h, t, d, n); }));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, fmt, d.pre, pc));
     // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
-    for (Tens* t : {&e.c41, &d.f1, &d.f2, &d.f3, &d.xs4, &d.a4, &d.o4, &d.xs3, &d.a3, &d.o3, &d.xs2, &d.a2, &d.o2}) stamp(h, t, B);
+    stamp(h, &e.c41, B);
+    for (int k = 0; k < 3; ++k)
+        for (Tens* t : {&d.f[k], &d.xs[k], &d.a[k], &d.o[k]}) stamp(h, t, B);
     if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
     return RRV_OK;
 }
@@ -1569,8 +1503,6 @@ int chan_stats_finish(rrv_handle h, int slot, int C, double N, int mode, float* 
     return RRV_OK;
 }
 
-struct BlkDesc { const char* name; int cout, n1, n2, nada, sty; };
-const BlkDesc BLKS[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 128, N_S3N1, N_S3N2, N_DEC3, 1}, {"slice2", 64, N_S2N1, N_S2N2, N_DEC4, 0}};
 enum { ST_NORM0 = 0, ST_FILTER = 1 /* +f */, ST_NORM1 = 4, ST_BLOCKS = 5 /* +3k: n1, n2, nada */, ST_COUNT = 14 };
 
 // Decoder.compute prefix of one group (`grp`: nb raw relu4_1 features) up to sync point `stage`, whose partial
@@ -1584,7 +1516,7 @@ int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int
     Tens g = grp; g.B = nb;
     if (stage == ST_NORM0) return chan_stats_group(h, g, true, 0, (double)frames_before * hh * ww);
     Tens cn = view(P.cn), nxt = view(P.nxt), t32 = view(P.t32);
-    RCHK(pointwise(h, g, cn, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
+    RCHK(apply_norm(h, g, cn, st, N_DEC0));
     Tens* cur = &cn; Tens* other = &nxt;
     for (int f = 0; f < 3; ++f) {
         if (stage == ST_FILTER + f) {
@@ -1600,26 +1532,16 @@ int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int
         Tens* t = cur; cur = other; other = t;
     }
     if (stage == ST_NORM1) return chan_stats_group(h, *cur, true, 0, (double)frames_before * hh * ww);
-    RCHK(pointwise(h, *cur, *cur, st + SL.norm[N_DEC1], st + SL.norm[N_DEC1] + 512, false, nullptr, 0, st + SL.sty[3], st + SL.sty[3] + 512));
-    Tens in = *cur;
-    for (int k = 0; k < 3; ++k) {
-        const BlkDesc& b = BLKS[k];
-        const std::string p = std::string("Decoder.") + b.name;
-        Tens xs = view(P.xs[k]), a = view(P.a[k]), o = view(P.o[k]);
-        const int H2 = in.H * 2, W2 = in.W * 2;
-        const double n_a = (double)frames_before * H2 * W2;
-        ConvCall c;
-        c = ConvCall{&in, &a, &h->conv[p + ".conv1"], H2, W2}; c.B = nb; c.ups = true; c.epi = E_LRELU; RCHK(conv(h, c));
-        if (stage == ST_BLOCKS + 3 * k) return chan_stats_group(h, a, true, 0, n_a);
-        RCHK(pointwise(h, a, a, st + SL.norm[b.n1], st + SL.norm[b.n1] + b.cout, false, nullptr, 0, nullptr, nullptr));
-        c = ConvCall{&a, &o, &h->conv[p + ".conv2"], H2, W2}; c.B = nb; c.epi = E_LRELU; RCHK(conv(h, c));
-        if (stage == ST_BLOCKS + 3 * k + 1) return chan_stats_group(h, o, true, 0, n_a);
-        c = ConvCall{&in, &xs, &h->conv[p + ".conv_shortcut"], in.H, in.W}; c.B = nb; RCHK(conv(h, c));
-        RCHK(pointwise(h, o, o, st + SL.norm[b.n2], st + SL.norm[b.n2] + b.cout, false, &xs, 2, nullptr, nullptr));
-        if (stage == ST_BLOCKS + 3 * k + 2) return chan_stats_group(h, o, true, 0, n_a);
-        RCHK(pointwise(h, o, o, st + SL.norm[b.nada], st + SL.norm[b.nada] + b.cout, false, nullptr, 0, st + SL.sty[b.sty], st + SL.sty[b.sty] + b.cout));
-        in = o;
-    }
+    RCHK(apply_norm(h, *cur, *cur, st, N_DEC1, nullptr, 3));
+    Tens xs[3], a[3], o[3];
+    for (int k = 0; k < 3; ++k) { xs[k] = view(P.xs[k]); a[k] = view(P.a[k]); o[k] = view(P.o[k]); }
+    // the statistics before `stage` are known; at `stage` the group's partial is merged and nothing further is launched
+    const int rc = unfused_blocks(h, nb, *cur, xs, a, o, st, 0, false, true, [&](const Tens& t, int, int point) -> int {
+        if (ST_BLOCKS + point != stage) return RRV_OK;
+        RCHK(chan_stats_group(h, t, true, 0, (double)frames_before * t.H * t.W));
+        return WALK_STOP;
+    });
+    if (rc != RRV_OK) return rc == WALK_STOP ? RRV_OK : rc;
     return fail(h, RRV_E_ARG, "stream_prefix: no such stage");
 }
 
@@ -1654,7 +1576,7 @@ int compute_style_streaming(rrv_handle h, int sid) {
                 // KernelFilter.compute (:223-230): frame 0 alone passes through apply_filter; its residual u_f is what every frame receives (Q1)
                 HIPCHK(hipMemcpyAsync(P.f0.p, h->patches[0], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
                 Tens cn0 = P.cn; cn0.B = 1;
-                RCHK(pointwise(h, P.f0, cn0, st + SL.norm[N_DEC0], st + SL.norm[N_DEC0] + 512, false, nullptr, 0, nullptr, nullptr));
+                RCHK(apply_norm(h, P.f0, cn0, st, N_DEC0));
                 for (int f2 = 0; f2 < f; ++f2) RCHK(pointwise(h, cn0, cn0, nullptr, nullptr, false, &P.su[f2], 1, nullptr, nullptr));
                 ConvCall c{&cn0, &P.d32, &h->cur->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, c));
                 ConvCall cu{&P.d32, &P.su[f], &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
@@ -1877,11 +1799,11 @@ int rrv_finalize_weights(rrv_handle h) {
     HIPCHK(hipSetDevice(h->dev));
     RCHK(dalloc(h, &h->zero_bias, 512, true));
     {   // the fixed-size scratch (rrv_ctx::stat_part ..): 1024 partial blocks x 3 x 512 channels at most per partial buffer
-        constexpr size_t PART = (size_t)1024 * 3 * 512, ACC = (size_t)2 * 4 * 512, FLOATS = 512 + 9 * 512 + 64 + 64;
+        constexpr size_t PART = (size_t)1024 * 3 * 512, ACC = (size_t)2 * 4 * 512, FLOATS = 512 + 64;
         float* base;
         RCHK(dalloc(h, &base, (2 * PART + ACC) * 2 + FLOATS));
         h->stat_part = (double*)base; h->stat_part2 = h->stat_part + PART; h->stat_acc = h->stat_part2 + PART;
-        h->stat_mean = (float*)(h->stat_acc + ACC); h->frame_S = h->stat_mean + 512; h->frame_cmean = h->frame_S + 9 * 512; h->prep_cmean = h->frame_cmean + 64;
+        h->stat_mean = (float*)(h->stat_acc + ACC); h->prep_cmean = h->stat_mean + 512;
     }
     for (int which = 0; which < 2; ++which) {
         for (int i = 0; i < 9; ++i) {
@@ -3025,8 +2947,8 @@ int rrv_release_features(rrv_handle h) {
 }
 
 // Stylization(use_Global=False).transfer (test/framework.py:106-118 with test/style_network_frame.py):
-// per-frame InstanceNorm statistics and per-frame filter prediction.  Implemented as the preparation
-// frame_mode_forward above.
+// per-frame InstanceNorm statistics and per-frame filter prediction.  One frame of frame_mode_device's batch, through
+// blocking pageable copies.
 static int transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, void* out, OutFmt fmt) {
     if (!h || !frame || !out) return RRV_E_ARG;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
@@ -3040,7 +2962,7 @@ static int transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W,
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, nin));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, nin, hipMemcpyHostToDevice, h->stream));
     RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
-    RCHK(frame_mode_forward(h, h->d_u8, H, W, h->d_outf, fmt));
+    RCHK(frame_mode_device(h, 0, h->d_u8, 1, H, W, h->d_outf, fmt, nullptr));
     HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;

@@ -165,6 +165,16 @@ def test_device_entries(pkg, weights, oracle):
         np.testing.assert_array_equal(o.cpu().numpy(), a)
     np.testing.assert_array_equal(alone[1], ref[6:12])
     np.testing.assert_array_equal(gs.get_state(), state)
+    # the one-frame entry between two global calls: the frame's own numbers go to a state set, style 0's computed state is only read
+    one = np.empty((H, W, 3), dtype=np.float32)
+    assert lib.rrv_transfer_frame_mode(gs._h, C.c_void_p(frames[6].ctypes.data), H, W, C.c_void_p(one.ctypes.data)) == 0
+    np.testing.assert_array_equal(gs.get_state(), state)
+    np.testing.assert_array_equal(one, ref[6])
+    fn, k = calls[2]
+    assert fn(gs._h, C.c_void_p(d_in[k].data_ptr()), B, H, W, C.c_void_p(outs[2].data_ptr())) == 0
+    gs.sync()
+    np.testing.assert_array_equal(outs[2].cpu().numpy(), alone[2])
+    np.testing.assert_array_equal(gs.get_state(), state)
     gs.close()
 
 
