@@ -331,6 +331,20 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
 int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
                              int* layout, int* channels);
 
+/* Layer-parity read-back of the per-image numbers of a launch, copied to the host after a full synchronisation; nothing
+ * else changes.
+ *   what = RRV_DBG_STATE_SET: the state set of image `image` as the most recent launch on workspace slot `slot` (0 or 1)
+ *     wrote it — a frame-mode launch (every image's statistics, predicted filters and the identity Decoder.norm[1] entry)
+ *     or a grouped multi-style launch (every image's blended state).  Same blob layout as rrv_get_state,
+ *     n == RRV_STATE_FLOATS.  RRV_E_STATE when the last launch on that slot kept no per-image state or did not write
+ *     that image.
+ *   what = RRV_DBG_STYLE_PRED: the style half of the filter predictions of prepared style `image` (mean over H x W of
+ *     Filter1..3's F1 / F2 down_sample of the normalised style map: [6][32] floats, n == 192); `slot` must be 0.
+ *     RRV_E_STATE when that style has not been prepared. */
+#define RRV_DBG_STATE_SET 0
+#define RRV_DBG_STYLE_PRED 1
+int rrv_debug_copy_state(rrv_handle h, int what, int slot, int image, float* out, int n);
+
 /* Stream-ordered use of the *_device entries from a caller that produces / consumes the buffers on its own HIP
  * stream (e.g. torch.cuda.current_stream().cuda_stream): see ORDERING above.  enable = 0 switches it off. */
 int rrv_set_caller_stream(rrv_handle h, void* hip_stream, int enable);

@@ -25,6 +25,7 @@ DT_U8, DT_F32 = 0, 1
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM = 1, 2, 4
+DBG_STATE_SET, DBG_STYLE_PRED = 0, 1
 
 # name -> (restype, argtypes); must list every symbol declared in include/rerevst_hip.h
 SYMBOLS = {
@@ -80,6 +81,7 @@ SYMBOLS = {
     "rrv_debug_copy_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrv_debug_copy_tensor_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rrv_debug_copy_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "rrv_set_grid_share": (C.c_int, [C.c_void_p, C.c_int]),
     "rrv_set_caller_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rrv_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -188,6 +188,7 @@ struct rrv_ctx {
     struct StateSet { float* active = nullptr; ConvW fold_down[3], fold_up[3]; } sets[N_SETS];
     StateSet* cur = &sets[0];
     int state_images = 0;                        // > 0: the launch's images 0..state_images-1 use sets cur, cur+1, .. (per-image state)
+    int set_images[2] = {0, 0};                  // images whose state sets the last launch on slot 0 / 1 wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
     float* fold_tmp = nullptr;                 // OIHW scratch for folds (512*32*9 floats)
     StyleState styles[RRV_MAX_STYLES];
     int active_src = -1;                       // style id whose state is folded (-2: blend)
@@ -832,6 +833,7 @@ int fold_filters(rrv_handle h, const float* blob, int f /*0..2*/, int nsets = 1)
     const ConvW& wu = h->conv[std::string(pre) + ".upsample.0"];
     ConvW& fd = h->cur->fold_down[f];
     ConvW& fu = h->cur->fold_up[f];
+    h->set_images[(h->cur - h->sets) / rrv_ctx::MS_GROUP_MAX] = 0;      // the slot's sets are being rewritten; a per-image-state launch counts its images once it is queued
     const float* F1 = blob + SL.filt[2 * f];
     const float* F2 = blob + SL.filt[2 * f + 1];
     hipLaunchKernelGGL(fold_down_k, dim3((32 * 512 * 9 + 255) / 256, nsets), dim3(256), 0, h->stream, F1, (const float*)wd.raw,
@@ -1186,6 +1188,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
     struct StreamScope { rrv_handle h; ~StreamScope() { h->stream = h->streams[0]; h->f43_path = false; } } scope{h};
     h->stream = h->streams[slot];
+    if (slot < 2) h->set_images[slot] = 0;      // (the grouped multi-style entry counts its images after this returns)
     h->f43_path = true;            // the per-frame path: layers with an F(4x4,3x3) pack may run on conv_f43_k (use_f43)
     if (h->caller_sync) {    // stream-ordered against the caller: work queued on its stream so far precedes ours
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
@@ -1462,6 +1465,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     stamp(h, &e.c41, B);
     for (int k = 0; k < 3; ++k)
         for (Tens* t : {&d.f[k], &d.xs[k], &d.a[k], &d.o[k]}) stamp(h, t, B);
+    h->set_images[slot] = B;
     if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
     return RRV_OK;
 }
@@ -2918,6 +2922,7 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         } else {
             RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, fmt, nullptr));      // re-encode the pixels
         }
+        h->set_images[slot] = cnt;
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
         HIPCHK(hipMemcpyAsync(out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out, st.dev.out, (size_t)cnt * npx, hipMemcpyDeviceToHost, h->copy_out));
@@ -3085,6 +3090,29 @@ int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H
     if (layout) *layout = p8 ? 1 : 0;
     if (channels) *channels = C;
     if (host && cap >= n) HIPCHK(hipMemcpy(host, t->p + (size_t)image * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RRV_OK;
+}
+
+// Layer-parity read-back (tests/test_gpu_frame_mode_layers.py): the state set image `image` of the last launch on `slot` ran
+// with (frame mode: its statistics and predicted filters; grouped multi-style: its blended state), or the style half of the
+// filter predictions of prepared style `image`.
+int rrv_debug_copy_state(rrv_handle h, int what, int slot, int image, float* out, int n) {
+    if (!h || !out || image < 0) return RRV_E_ARG;
+    if (what == RRV_DBG_STYLE_PRED) {
+        if (slot != 0 || image >= RRV_MAX_STYLES || n != 6 * 32) return RRV_E_ARG;
+        const StyleState& S = h->styles[image];
+        if (!S.prepared || !S.smean) return fail(h, RRV_E_STATE, "debug_copy_state: prepare_style has not been called for this style");
+        HIPCHK(hipSetDevice(h->dev));
+        RCHK(sync_all(h));
+        HIPCHK(hipMemcpy(out, S.smean, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return RRV_OK;
+    }
+    if (what != RRV_DBG_STATE_SET || slot < 0 || slot > 1 || image >= rrv_ctx::MS_GROUP_MAX || n != RRV_STATE_FLOATS) return RRV_E_ARG;
+    if (!h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch kept no per-image state");
+    if (image >= h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch did not write this image");
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(sync_all(h));
+    HIPCHK(hipMemcpy(out, h->sets[rrv_ctx::MS_GROUP_MAX * slot + image].active, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return RRV_OK;
 }
 

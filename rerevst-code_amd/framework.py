@@ -470,6 +470,21 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_tensor_ex(*args, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(lay), C.byref(ch)))
         return out, lay.value, ch.value
 
+    def debug_state_set(self, slot, image=0):
+        """The state set (get_state's blob layout) of image `image` as the last launch on workspace slot `slot` (0 or 1) wrote it
+        (rrv_debug_copy_state): a frame-mode launch's per-image statistics and predicted filters, or a grouped multi-style
+        launch's per-image blended state.  Refused when that launch kept no per-image state or did not write the image."""
+        out = np.empty(_lib.STATE_FLOATS, dtype=np.float32)
+        self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STATE_SET, int(slot), int(image), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def debug_style_pred(self, style_id=0):
+        """The style half of the filter predictions of a prepared style (rrv_debug_copy_state): float32 [6][32], Filter1.F1 ..
+        Filter3.F2."""
+        out = np.empty((6, 32), dtype=np.float32)
+        self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_PRED, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
     def set_host_io(self, mode):
         """0 (default): staged H2D / D2H copies; 1: zero copy — kernels read / write page-locked host memory directly."""
         self._chk(self._lib.rrv_set_host_io(self._h, int(mode)))

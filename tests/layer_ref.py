@@ -15,6 +15,31 @@ and the bound is  |gpu - ref| <= K_family 2^-24 m + 2^-24 |ref|  element-wise, o
 
 Measured ratios max |gpu - ref| / (2^-24 m) on an MI355X over the shapes of tests/test_gpu_layers.py (three forced kernel
 choices, the headline launch and split K) are in MEASURED; each K is set from the largest one of its family (see K).
+
+Frame mode (Stylization(use_Global=False), FRAME_STAGES below) normalises in place with statistics taken per image, so the raw
+tensor a statistic was taken from is gone after the launch.  Each statistic is therefore checked against the float64
+statistic of the float64 stage (value v, per-element error bound b of what the GPU held, b = K_f 2^-24 m for a raw
+convolution output) over the whole tensor of that image:
+  mean      the mean of per-element errors is at most the mean of their bounds:
+            |mean_gpu - mean64| <= mean(b) + K_stat 2^-24 |mean64|
+  variance  x = v + e with |e| <= b:  var(x) = var(v) + 2 cov(v, e) + var(e),  |cov(v, e)| <= sqrt(var v) sqrt(var e)
+            (Cauchy-Schwarz on the centred values) and var(e) <= mean(e^2) <= mean(b^2), so
+            |var_gpu - var64| <= 2 sqrt(var64) rms(b) + mean(b^2) + K_stat 2^-24 (var64 + 1e-8),
+            var_gpu recovered as 1 / rstd_gpu^2 - 1e-8 (biased, over H x W of the image alone).
+The normalised taps are teacher-forced on the GPU's OWN statistics, (v - mean_gpu) rstd_gpu with magnitude
+(m + |mean_gpu|) rstd_gpu, so they see the convolution's and pointwise_k's rounding and no statistic's:
+  |gpu - ref| <= 2^-24 (K_f m_conv + K_point m_point + |ref|)
+with m_conv the convolution's magnitude carried through the later steps' scales only, and m_point the magnitude of every
+pointwise_k pass's own result carried the same way.  The families of the frame-mode path:
+  stat   the statistics kernels' and blend_states_k's own rounding.  Never visible alone at a statistic point (its input is
+         overwritten), so there the measured figure is the EXCESS (err - mean(b)) / (2^-24 |mean64|) (resp. the variance
+         form), 0 where the producer's term covers the error; blend_states_k's float32 sum against the float64 sum of the
+         styles' blobs, relative to the same sum on absolute values, is measured directly.
+  point  pointwise_k.  Its input is overwritten in place, so it is never visible alone either: the measured figure is the
+         WHOLE error of a normalised tap over 2^-24 m_point (an upper estimate: the convolution's rounding is in it), and the
+         bound still carries the convolution's own term with its existing K.
+  pred   rect_sums_k + pred_mean_k + fc_filter_k against the reference's form (zero-padded 3 x 3 down_sample convolution,
+         mean over H x W, FC with the style half), magnitude: the same arithmetic on absolute values through the FC.
 """
 import numpy as np
 import torch
@@ -22,7 +47,7 @@ import torch.nn.functional as TF
 
 U = 2.0 ** -24
 
-FAMILIES = ("direct", "f23", "ups", "f43", "splitk")
+FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred")
 
 # max |gpu - ref| / (2^-24 m) per family, over every tap and shape of tests/test_gpu_layers.py on an MI355X (the worst tap):
 #   direct  30.7  c11 (conv_first: the grey fold multiplies 1/std into the weights, so its rounding is relative to the
@@ -30,11 +55,21 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk")
 #   f23      3.7  c31 (F(2x2,3x3); per tap 1.6 .. 3.7; the unsplit KernelFilter down conv 0.39)
 #   ups      9.2  xs3 (the upsample-fused conv1: a 2.9 .. 4.8; its fused 1x1 shortcut 8.0 .. 9.2)
 #   f43     12.5  c21 (F(4x4,3x3) with the balanced points; per tap 4.4 .. 12.5)
-#   splitk   0.22 d (split-K sum: m carries |F1| |W_down| * |x|, far above the partial sums' own magnitude)
-MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.22}
+#   splitk   0.24 d (split-K sum: m carries |F1| |W_down| * |x|, far above the partial sums' own magnitude; 0.22 on the
+#                 global path, 0.24 in frame mode at 1032 x 8)
+# and over every case of tests/test_gpu_frame_mode_layers.py (frame mode 1 x 8 x 8 .. 16 x 136 x 200, 2 x 640 x 640, the host
+# entry's second launch sequence, one grouped multi-style launch; the convolutions stayed inside the figures above with their
+# raw epilogues: direct 30.7, f23 3.68, ups 9.02):
+#   stat     2.91 blend_states_k, image 6 of the grouped multi-style launch (a float32 sum of four rounded products: up to 4
+#                 by construction; image 0: 1.47).  The statistic points' excess over their producer's term was 0 at every
+#                 point of every image (worst: 0.30 of the bound, norm0 at 16 x 8): chan_stat1_k accumulates in float64.
+#   point    3.73 a3 at 640 x 640 (the whole error of the tap over the pointwise result's magnitude; a taps 3.6 .. 3.7, c41
+#                 3.2, o taps 1.2 .. 1.7)
+#   pred     1.21 Filter1.F1 at 8 x 8 (one pixel; every other shape 0.05 .. 0.19)
+MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
 # still rejecting the defects tests/test_layer_ref.py injects (the smallest of them, one weight off by 2^-8, is at 2480)
-K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5}
+K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5}
 
 # the tap indices of rrv_debug_copy_tensor_ex
 TAP_NAMES = ["c11", "p1", "c21", "p2", "c31", "c32", "c33", "p3", "c41",
@@ -336,3 +371,193 @@ def check(got, v, m, k):
     ratio = err / np.maximum(U * m, 1e-300)
     worst = float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
     return bool(np.all(err <= bound)), worst, float(ratio.max()) if err.size else 0.0
+
+
+# ---- frame mode (Stylization(use_Global=False): frame_mode_device) ---------------------------------------------------------
+# One launch sequence per up to sixteen images, every image with statistics, predicted filters and folded KernelFilter weights
+# of its own in its own state set (rrv_debug_copy_state).  The taps after the launch: c11 .. p3 as in the global path, c41 / a4 /
+# a3 / a2 normalised in place, o4 / o3 / o2 normalised + shortcut + normalised + AdaIN in place, d of the last Filter, f1 .. f3.
+
+EPS32 = float(np.float32(1e-8))
+NO_LO, NO_HI = float(np.float32(-3.0e38)), float(np.float32(3.0e38))
+STAT3 = ["chan_stat1", "chan_stat1_final", "pointwise"]
+# the profile rows of one frame-mode launch sequence without sum_parts ("conv": any conv_* row but conv_first / conv_last)
+FRAME_SEQ = (["frame_sets_init", "conv_first"] + ["conv"] * 8 + STAT3
+             + ["rect_sums", "pred_mean", "fc_filter", "pred_mean", "fc_filter", "conv", "conv"] * 3
+             + (["conv"] + STAT3 + ["conv"] + STAT3 + STAT3) * 3 + ["conv_last"])
+FRAME_ENC = ("c11", "p1", "c21", "p2", "c31", "c32", "c33", "p3")
+FRAME_BLOCKS = (("slice4", "f3", "xs4", "a4", "o4"), ("slice3", "o4", "xs3", "a3", "o3"), ("slice2", "o3", "xs2", "a2", "o2"))
+FRAME_STAGES = (FRAME_ENC + ("stat0", "c41", "pred0", "f1", "pred1", "f2", "pred2", "d", "f3", "norm1")
+                + tuple(n for _, _, xs, a, o in FRAME_BLOCKS for n in (xs, "stat:" + a, a, "stat2:" + o, "stat3:" + o, o)) + ("pre",))
+
+
+def frame_families(seq):
+    """seq: [(profile row name, followed by sum_parts)] of one frame-mode launch sequence without the sum_parts rows.  Asserts
+    that it is FRAME_SEQ (every statistic one chan_stat1 + merge + pointwise, every prediction rectangle sums + predicted
+    means + FC, no F(4x4,3x3)) and returns {stage: kernel family} for the convolutions."""
+    assert len(seq) == len(FRAME_SEQ), [n for n, _ in seq]
+    fams = []
+    for (name, split), want in zip(seq, FRAME_SEQ):
+        k = name.split("@")[0]
+        if want == "conv":
+            assert k.startswith("conv_") and not k.startswith(("conv_first", "conv_last")), (name, want)
+            f = family_of(name, split)
+            assert f != "f43", name
+            fams.append(f)
+        else:
+            assert k == want, (name, want)
+            if want in ("conv_first", "conv_last"):
+                fams.append("direct")
+    keys = (FRAME_ENC + ("c41", "d0", "u0", "d1", "u1", "d2", "u2", "a4", "o4", "a3", "o3", "a2", "o2", "pre"))
+    assert len(fams) == len(keys), (len(fams), len(keys))
+    return dict(zip(keys, fams))
+
+
+def check_stat(entry, v, b, kstat):
+    """One statistic point: the state set's (mean, rstd, lo, hi) against the float64 statistics of the stage value v [H,W,C]
+    with per-element error bound b (module docstring).  Returns (passes, worst fraction of a bound, excess ratio)."""
+    mean_g, rstd_g, lo, hi = entry
+    C = v.shape[-1]
+    v2, b2 = v.reshape(-1, C), np.broadcast_to(b, v.shape).reshape(-1, C)
+    mean, var = v2.mean(axis=0), v2.var(axis=0)
+    msq = (b2 * b2).mean(axis=0)
+    pm, pv = b2.mean(axis=0), 2.0 * np.sqrt(var) * np.sqrt(msq) + msq
+    var_g = 1.0 / (rstd_g * rstd_g) - EPS32
+    em, ev = np.abs(mean_g - mean), np.abs(var_g - var)
+    sm, sv = U * np.abs(mean), U * (var + EPS32)
+    bm, bv = pm + kstat * sm, pv + kstat * sv
+    ok = np.all(em <= bm) and np.all(ev <= bv) and np.all(lo == NO_LO) and np.all(hi == NO_HI)
+    worst = max(float((em / np.maximum(bm, 1e-300)).max()), float((ev / np.maximum(bv, 1e-300)).max()))
+    excess = max(float(((em - pm) / np.maximum(sm, 1e-300)).max()), float(((ev - pv) / sv).max()), 0.0)
+    return bool(ok), worst, excess
+
+
+def predict_filter(x, w, name, smean):
+    """FilterPredictor.forward of the frame-mode model in float64 from the tap x [H,W,512] the Filter reads and the style half
+    smean [32] the GPU cached: (filter [32,32], magnitude)."""
+    p = "Decoder.%s." % name
+    cv, cm = conv3(x, w[p + "down_sample.0.weight"], w[p + "down_sample.0.bias"], 0, x.shape[0])
+    sm = np.asarray(smean, np.float64)
+    vec = np.concatenate([cv.reshape(-1, 32).mean(axis=0), sm])
+    mag = np.concatenate([cm.reshape(-1, 32).mean(axis=0), np.abs(sm)])
+    W, bias = np.asarray(w[p + "FC.weight"], np.float64), np.asarray(w[p + "FC.bias"], np.float64)
+    return (W @ vec + bias).reshape(32, 32), (np.abs(W) @ mag + np.abs(bias)).reshape(32, 32)
+
+
+def _up2(a, H, W):
+    return np.repeat(np.repeat(np.asarray(a, np.float64), 2, axis=0), 2, axis=1)[:H, :W]
+
+
+def frame_checks(get, w, st, smean, fam, k=None, names=None):
+    """Every frame-mode stage (or `names`, of FRAME_STAGES) of one image.  get(name): the tap [H][W][C] ("frame": grey_input of
+    the frame, "pre": the pre-clamp output); st: the image's parsed state set; smean [6][32]: the style half of the filter
+    predictions; fam: frame_families().  Returns [(stage, family or None, passes, worst fraction of its bound, ratio)]:
+    `ratio` is the family's measured figure (module docstring); family None: a composite of two kernels, no figure."""
+    k = K if k is None else k
+    out = []
+
+    def want(n):
+        return names is None or n in names
+
+    def plain(name, got, v, m, f):
+        ok, worst, ratio = check(got, v, m, k[f])
+        out.append((name, f, ok, worst, ratio))
+
+    def stat(name, entry, v, b):
+        out.append((name, "stat") + check_stat(entry, v, b, k["stat"]))
+
+    def forced(name, got, v, mc, mp, f):        # a tap behind pointwise_k, teacher-forced on the GPU's statistics
+        err = np.abs(np.asarray(got, np.float64) - v)
+        bound = U * (k[f] * mc + k["point"] * mp + np.abs(v))
+        out.append((name, "point", bool(np.all(err <= bound)), float((err / np.maximum(bound, 1e-300)).max()),
+                    float((err / np.maximum(U * mp, 1e-300)).max())))
+
+    for name in FRAME_ENC:
+        if not want(name):
+            continue
+        _, inputs, op, _ = STAGES[name]
+        got, inp = get(name), [get(i) for i in inputs]
+        for y0, y1 in strips(got.shape[0]):
+            v, m = op(inp, w, st, y0, y1)
+            plain(name, got[y0:y1], v, m, fam[name])
+    if want("stat0") or want("c41"):
+        p3 = get("p3")
+        v, m = _enc_stage(19, ())([p3], w, st, 0, p3.shape[0])
+        n0 = st["norm"][0]
+        if want("stat0"):
+            stat("stat0", n0, v, k[fam["c41"]] * U * m)
+        if want("c41"):
+            vn, mn = norm(v, m, n0)
+            forced("c41", get("c41"), vn, m * n0[1], mn, fam["c41"])
+    cur = ("c41", "f1", "f2")
+    for f in range(3):
+        if want("pred%d" % f):
+            x = get(cur[f])
+            for g in (1, 2):
+                name = "Filter%d.F%d" % (f + 1, g)
+                v, m = predict_filter(x, w, name, smean[2 * f + g - 1])
+                plain("pred%d.F%d" % (f, g), st["filt"][name], v, m, "pred")
+        if f < 2 and want("f%d" % (f + 1)):
+            x = get(cur[f])
+            v, mu, md = _composite(f)([x], w, st, 0, x.shape[0])
+            err = np.abs(get("f%d" % (f + 1)).astype(np.float64) - v)
+            bound = U * (k[fam["d%d" % f]] * md + k[fam["u%d" % f]] * mu + np.abs(v))
+            out.append(("f%d" % (f + 1), None, bool(np.all(err <= bound)), float((err / bound).max()), 0.0))
+    if want("d"):
+        x = get("f2")
+        plain("d", get("d"), *_down(2)([x], w, st, 0, x.shape[0]), fam["d2"])
+    if want("f3"):
+        x = get("f2")
+        plain("f3", get("f3"), *_up(2)([get("d"), x], w, st, 0, x.shape[0]), fam["u2"])
+    if want("norm1"):       # the identity entry frame_sets_init_k writes, exactly
+        mean, rstd, lo, hi = st["norm"][1]
+        ok = np.all(mean == 0.0) and np.all(rstd == 1.0) and np.all(lo == NO_LO) and np.all(hi == NO_HI)
+        out.append(("norm1", "stat", bool(ok), 0.0 if ok else np.inf, 0.0))
+    for blk, xin, xs, a, o in FRAME_BLOCKS:
+        n1, n2, na, si = RES[blk]
+        pre = "Decoder.%s." % blk
+        if want(xs):
+            x = get(xin)
+            plain(xs, get(xs), *conv1(x, w[pre + "conv_shortcut.weight"], 0, x.shape[0]), fam[a])
+        if want("stat:" + a) or want(a):
+            x = get(xin)
+            v, m = lrelu(*conv3(x, w[pre + "conv1.weight"], w[pre + "conv1.bias"], 0, 2 * x.shape[0], ups=True))
+            e1 = st["norm"][n1]
+            if want("stat:" + a):
+                stat("stat:" + a, e1, v, k[fam[a]] * U * m)
+            if want(a):
+                vn, mn = norm(v, m, e1)
+                forced(a, get(a), vn, m * e1[1], mn, fam[a])
+            del v, m
+        if want("stat2:" + o) or want("stat3:" + o) or want(o):
+            at = get(a)
+            H2, W2 = at.shape[:2]
+            v, m = lrelu(*conv3(at, w[pre + "conv2.weight"], w[pre + "conv2.bias"], 0, H2))
+            e2, ea, (s_mean, s_std) = st["norm"][n2], st["norm"][na], st["sty"][si]
+            if want("stat2:" + o):
+                stat("stat2:" + o, e2, v, k[fam[o]] * U * m)
+            xsu = _up2(get(xs), H2, W2)
+            hv = (v - e2[0]) * e2[1] + xsu                        # norm2 + the upsampled shortcut, on the GPU's statistics
+            mc = m * e2[1]                                        # the convolution's magnitude through the scales
+            mh = (m + np.abs(e2[0])) * e2[1] + np.abs(xsu)        # the first pointwise pass's own result
+            del v, m
+            if want("stat3:" + o):
+                stat("stat3:" + o, ea, hv, U * (k[fam[o]] * mc + k["point"] * mh + np.abs(hv)))
+            if want(o):
+                sc = ea[1] * np.abs(s_std)
+                vo = (hv - ea[0]) * ea[1] * s_std + s_mean
+                mo = (mh + np.abs(ea[0])) * sc + np.abs(s_mean)   # the second pass's own result
+                forced(o, get(o), vo, mc * sc, mh * sc + mo, fam[o])
+    if want("pre"):
+        o2 = get("o2")
+        got = get("pre")
+        for y0, y1 in strips(got.shape[0]):
+            plain("pre", got[y0:y1], *_last([o2], w, st, y0, y1), fam["pre"])
+    return out
+
+
+def blend_ref(blobs, wts):
+    """blend_states_k in float64: sum_s w[s] state_s and the same sum on absolute values (w as the float32 the kernel holds)."""
+    wts = np.asarray(wts, np.float32).astype(np.float64)
+    b = np.stack([np.asarray(x, np.float32).astype(np.float64) for x in blobs])
+    return wts @ b, np.abs(wts) @ np.abs(b)

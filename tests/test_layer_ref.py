@@ -103,5 +103,194 @@ def test_image_given_another_images_state_fails(setup, weights):
 
 
 def test_k_within_four_times_the_measured_maximum():
+    assert set(LR.MEASURED) == set(LR.K) == set(LR.FAMILIES) and {"stat", "point", "pred"} <= set(LR.FAMILIES)
     for f in LR.FAMILIES:
-        assert LR.MEASURED[f] <= LR.K[f] <= 4 * LR.MEASURED[f], f
+        assert 0 < LR.MEASURED[f] <= LR.K[f] <= 4 * LR.MEASURED[f], f
+
+
+# ---- frame mode: the references of tests/test_gpu_frame_mode_layers.py ---------------------------------------------------
+
+STYLE = dict(H=64, W=64, kind="smooth", seed=7)
+FM_NAMES = tuple(n for n in LR.FRAME_STAGES[:LR.FRAME_STAGES.index("o4") + 1] if n not in LR.FRAME_ENC)      # c41 .. block slice4
+CPU_FAM = {n: "direct" for n in LR.FRAME_ENC + ("c41", "d0", "u0", "d1", "u1", "d2", "u2", "a4", "o4", "a3", "o3", "a2", "o2", "pre")}
+
+
+def _style(oracle, pkg, weights):
+    """(F_style of the oracle, style statistics in blob order, float64 style half of the six filter predictions)."""
+    F = oracle.Net(weights).encoder_style(oracle.image_to_tensor(pkg.synth_style(**STYLE)))
+    m4, s4 = F["relu4_1"]
+    sn = ((F["map"] - m4) / s4).astype(np.float32)[0]
+    smean = np.stack([LR.conv3(sn, weights["Decoder.%s.down_sample.0.weight" % n], weights["Decoder.%s.down_sample.0.bias" % n],
+                               0, sn.shape[0])[0].reshape(-1, 32).mean(axis=0) for n in LR.FILTER_NAMES])
+    sty = [tuple(np.asarray(a, np.float64) for a in F[n]) for n in ("relu1_1", "relu2_1", "relu3_1", "relu4_1")]
+    return F, sty, smean
+
+
+def _empty_state(sty):
+    return {"norm": [(np.zeros(C), np.ones(C), np.full(C, LR.NO_LO), np.full(C, LR.NO_HI)) for C in LR.NORM_CH], "filt": {}, "sty": sty}
+
+
+def _stats32(oracle, x, nminus1=False):
+    """chan_stat1_k + chan_stat1_final_k on [H,W,C] float32: the state-set entry (float64 views of float32 values)."""
+    C = x.shape[-1]
+    flat = x.reshape(-1, C)
+    mean = oracle._mean32(flat, axis=0)
+    xc = flat - mean
+    var = np.sum(xc.astype(np.float64) ** 2, axis=0) / (flat.shape[0] - (1 if nminus1 else 0))
+    rstd = (np.float32(1) / np.sqrt(var.astype(np.float32) + np.float32(1e-8))).astype(np.float32)
+    return mean.astype(np.float64), rstd.astype(np.float64), np.full(C, LR.NO_LO), np.full(C, LR.NO_HI)
+
+
+def _pred32(x, w, name, smean, tall=False):
+    """rect_sums_k + pred_mean_k + fc_filter_k on [H,W,512] float32.  tall: the rectangles of the taps that look up (dy < 0) keep
+    the last row (y < H instead of y < H - 1)."""
+    H, W, _ = x.shape
+    p = "Decoder.%s." % name
+    wd = np.asarray(w[p + "down_sample.0.weight"], np.float64)
+    x64, acc = x.astype(np.float64), np.zeros(32)
+    for t in range(9):
+        dy, dx = t // 3 - 1, t % 3 - 1
+        ys = slice(0, H if tall else H - 1) if dy < 0 else slice(1, H) if dy > 0 else slice(0, H)
+        xs = slice(0, W - 1) if dx < 0 else slice(1, W) if dx > 0 else slice(0, W)
+        S = x64[ys, xs].sum(axis=(0, 1)).astype(np.float32).astype(np.float64)
+        acc += wd[:, :, t // 3, t % 3] @ S
+    c = (acc / (H * W) + np.asarray(w[p + "down_sample.0.bias"], np.float64)).astype(np.float32)
+    v = np.concatenate([c, np.asarray(smean, np.float32)])
+    return (w[p + "FC.weight"] @ v + w[p + "FC.bias"]).astype(np.float32).reshape(32, 32)
+
+
+def _standin(oracle, weights, frame, sty, smean, defect=None, other=None):
+    """The frame-mode chain up to block slice4 in the oracle's float32 arithmetic, stage by stage as the kernels run it:
+    (taps, state set).  `defect` plants one of the wrong values the GPU suite is there to catch; `other`: image 0's state set
+    for the defects that read a neighbour's."""
+    O, w = oracle, weights
+    x = O.rgb2gray(O.image_to_tensor(frame))
+    for idx in O.VGG_IDX[:-1]:
+        x = O.relu(O.conv3x3(x, w["Encoder.slice.%d.weight" % idx], w["Encoder.slice.%d.bias" % idx]))
+        if idx in O.POOL_AFTER:
+            x = O.maxpool2(x)
+    taps, st = {"p3": x[0]}, _empty_state(sty)
+
+    def normed(t, e):
+        return ((t - e[0].astype(np.float32)) * e[1].astype(np.float32)).astype(np.float32)
+
+    raw = O.relu(O.conv3x3(x, w["Encoder.slice.19.weight"], w["Encoder.slice.19.bias"]))
+    st["norm"][0] = _stats32(O, raw[0], nminus1=defect == "variance over N - 1")
+    cur = normed(raw, other["norm"][0] if defect == "statistics of image 0" else st["norm"][0])
+    taps["c41"] = cur[0]
+    for f in range(3):
+        fn = "Filter%d" % (f + 1)
+        for g in (1, 2):
+            st["filt"]["%s.F%d" % (fn, g)] = _pred32(cur[0], w, "%s.F%d" % (fn, g), smean[2 * f + g - 1],
+                                                     tall=defect == "rectangle one row too tall").astype(np.float64)
+        use = other if (defect == "filter of image 0 in Filter 2" and f == 1) else st
+        F1, F2 = (use["filt"]["%s.F%d" % (fn, g)].astype(np.float32) for g in (1, 2))
+        p = "Decoder.%s." % fn
+        d = O.lrelu(O.apply_filter(O.conv3x3(cur, w[p + "down_sample.0.weight"], w[p + "down_sample.0.bias"]), F1))
+        cur = cur + O.conv3x3(O.apply_filter(d, F2), w[p + "upsample.0.weight"], w[p + "upsample.0.bias"])
+        taps["f%d" % (f + 1)] = cur[0]
+    taps["d"] = d[0]
+    m4, s4 = (a.astype(np.float32) for a in sty[3])
+    cur = (cur * s4 + m4).astype(np.float32)
+    taps["f3"] = cur[0]
+    n1, n2, na, si = LR.RES["slice4"]
+    taps["xs4"] = O.conv1x1(cur, w["Decoder.slice4.conv_shortcut.weight"])[0]
+    a = O.lrelu(O.conv3x3(O.upsample2(cur), w["Decoder.slice4.conv1.weight"], w["Decoder.slice4.conv1.bias"]))
+    st["norm"][n1] = _stats32(O, a[0])
+    a = normed(a, st["norm"][n1])
+    taps["a4"] = a[0]
+    c2 = O.lrelu(O.conv3x3(a, w["Decoder.slice4.conv2.weight"], w["Decoder.slice4.conv2.bias"]))
+    st["norm"][n2] = _stats32(O, c2[0])
+    xsu = O.upsample2(taps["xs4"][None])
+    h = normed(c2 + xsu, st["norm"][n2]) if defect == "shortcut before the normalisation" else normed(c2, st["norm"][n2]) + xsu
+    st["norm"][na] = _stats32(O, h[0])
+    ms, ss = (v.astype(np.float32) for v in sty[si])
+    taps["o4"] = (normed(h, st["norm"][na]) * ss + ms).astype(np.float32)[0]
+    return taps, st
+
+
+@pytest.fixture(scope="module")
+def fm(pkg, weights, oracle):
+    prev = oracle.CONV_BACKEND
+    oracle.set_conv_backend("numpy")
+    try:
+        _, sty, smean = _style(oracle, pkg, weights)
+        frames = [pkg.synth_frame(0, 64, 80, kind="smooth"), pkg.synth_frame(1, 64, 80, kind="noise")]
+        good = [_standin(oracle, weights, f, sty, smean) for f in frames]
+        yield oracle, frames, sty, smean, good
+    finally:
+        oracle.set_conv_backend(prev)
+
+
+def _failed(taps, st, weights, smean, names=FM_NAMES):
+    return {n: worst for n, _, ok, worst, _ in LR.frame_checks(taps.__getitem__, weights, st, smean, CPU_FAM, names=names) if not ok}
+
+
+def test_frame_mode_float32_stand_in_passes(fm, weights):
+    _, _, _, smean, good = fm
+    for b, (taps, st) in enumerate(good):
+        bad = _failed(taps, st, weights, smean)
+        assert not bad, "image %d: %s" % (b, bad)
+
+
+FM_DEFECTS = {"variance over N - 1": {"stat0"}, "rectangle one row too tall": {"pred0.F1", "pred0.F2"}, "statistics of image 0": {"c41"},
+              "filter of image 0 in Filter 2": {"f2"}, "shortcut before the normalisation": {"o4"}}
+
+
+@pytest.mark.parametrize("defect", sorted(FM_DEFECTS))
+def test_frame_mode_injected_defect_fails(fm, weights, defect):
+    """Image 1 with one wrong value planted; the stages that see it must fail at the committed K."""
+    oracle, frames, sty, smean, good = fm
+    taps, st = _standin(oracle, weights, frames[1], sty, smean, defect=defect, other=good[0][1])
+    bad = _failed(taps, st, weights, smean)
+    assert set(bad) >= FM_DEFECTS[defect], "%s: only %s fail" % (defect, bad)
+
+
+def test_float64_frame_stages_reproduce_the_reference_golden(pkg, weights, oracle):
+    """All float64 stages composed from the golden's frame give tests/golden/frame_mode.npz's pre-clamp output within the
+    stated PRE_ATOL / PRE_RTOL (the stage table follows the unmodified reference), and LR.frame_checks accepts the composed
+    taps with the composed statistics (its arithmetic is that composition)."""
+    from state_bounds import assert_pre_close
+    frame = oracle.reflect_pad(pkg.synth_frame(2, 64, 48, kind="smooth"), 192, 192)
+    _, sty, smean = _style(oracle, pkg, weights)
+    w, st = weights, _empty_state(sty)
+    taps = {"frame": LR.grey_input(frame)}
+
+    def full(op, inputs, rows):
+        return op([taps[i] for i in inputs], w, st, 0, rows)[0]
+
+    def stats(v):
+        f = v.reshape(-1, v.shape[-1])
+        return f.mean(axis=0), 1.0 / np.sqrt(f.var(axis=0) + LR.EPS32), np.full(v.shape[-1], LR.NO_LO), np.full(v.shape[-1], LR.NO_HI)
+
+    for name in LR.FRAME_ENC:
+        _, inputs, op, geo = LR.STAGES[name]
+        taps[name] = full(op, inputs, geo(192, 192)[0])
+    raw = full(LR._enc_stage(19, ()), ["p3"], 24)
+    st["norm"][0] = stats(raw)
+    taps["c41"] = LR.norm(raw, raw, st["norm"][0])[0]
+    cur = "c41"
+    for f in range(3):
+        for g in (1, 2):
+            name = "Filter%d.F%d" % (f + 1, g)
+            st["filt"][name] = LR.predict_filter(taps[cur], w, name, smean[2 * f + g - 1])[0]
+        taps["d"] = full(LR._down(f), [cur], 24)
+        taps["f%d" % (f + 1)] = full(LR._up(f), ["d", cur], 24)
+        cur = "f%d" % (f + 1)
+    for blk, xin, xs, a, o in LR.FRAME_BLOCKS:
+        n1, n2, na, si = LR.RES[blk]
+        p = "Decoder.%s." % blk
+        x = taps[xin]
+        taps[xs] = LR.conv1(x, w[p + "conv_shortcut.weight"], 0, x.shape[0])[0]
+        v = LR.lrelu(*LR.conv3(x, w[p + "conv1.weight"], w[p + "conv1.bias"], 0, 2 * x.shape[0], ups=True))[0]
+        st["norm"][n1] = stats(v)
+        taps[a] = LR.norm(v, v, st["norm"][n1])[0]
+        v = LR.lrelu(*LR.conv3(taps[a], w[p + "conv2.weight"], w[p + "conv2.bias"], 0, 2 * x.shape[0]))[0]
+        st["norm"][n2] = stats(v)
+        h = LR.norm(v, v, st["norm"][n2])[0] + LR._up2(taps[xs], *v.shape[:2])
+        st["norm"][na] = stats(h)
+        taps[o] = LR.adain(h, h, st["norm"][na], sty[si])[0]
+    taps["pre"] = full(LR._last, ["o2"], 192)
+    assert_pre_close(taps["pre"][64:128, 64:112].astype(np.float32), load_golden("frame_mode")["pre_crop"])
+    bad = {n: worst for n, _, ok, worst, _ in LR.frame_checks(taps.__getitem__, w, st, smean, CPU_FAM) if not ok}
+    assert not bad, bad
