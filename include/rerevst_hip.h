@@ -290,6 +290,45 @@ typedef struct { int dtype; int layout; int space; } rrv_image_desc;
 int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W,
                               void* d_out, rrv_image_desc out, int flags, void* hip_stream);
 
+/* Multi-style interpolation from FRAMES, batched ("Multi-style Interpolation/stylization.py":94-100 transfer(feature, style_weight)
+ * with style_network.py:35-53,135-139,348-360 — every saved statistic, dynamic filter and style (mean, std) replaced by
+ * sum_s weight[s] * q_s — and :432-460, the forward pass; the reference blends one cached feature per call, test.py:127-131).
+ * rrv_transfer_image_device with one weight vector per image: style_weight is [B][n_styles] float32, n_styles in
+ * 1..RRV_MAX_STYLES, every style 0..n_styles-1 computed (else RRV_E_STATE).  The frames run in launch sequences of up to sixteen,
+ * each image with its own blended state set (as rrv_transfer_features_batch), encoder and decoder from the frames; consecutive
+ * calls alternate over workspace slots 0 and 1.  For a fixed kernel mode (rrv_set_f43 0 / 2) image b's output is bit-identical
+ * to rrv_transfer_blend on that frame alone with style_weight[b] (of its padded form with RRV_TF_PAD_CROP).
+ * flags: RRV_TF_PAD_CROP, RRV_TF_ON_STREAM as above; RRV_TF_FRAME_MODE is RRV_E_ARG (the reference's frame-mode model has no
+ * blended state).  RRV_TF_WEIGHTS_DEVICE: style_weight points to device memory, produced on hip_stream (or complete before the
+ * call): a blend kernel reads it there, in stream order, and the host never sees the values — weights computed on the GPU need
+ * no synchronisation and no copy.  Without it style_weight is host memory, consumed before the call returns (staged through a
+ * page-locked ring and copied in stream order: no host synchronisation either); the same float32 values give the same bits
+ * either way.  Workspace per slot: 64 x RRV_MAX_STYLES floats in HBM, four times that page-locked. */
+#define RRV_TF_WEIGHTS_DEVICE (1 << 3)   /* = 8, next to RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM */
+int rrv_transfer_image_blend_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W,
+                                    const float* style_weight, int n_styles,
+                                    void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+/* The same model on host buffers (stylization.py:94-100, style_network.py:35-53,135-139,348-360,432-460), pipelined as
+ * rrv_transfer_batch (pad_crop == 0: [B][8*(H/8)][8*(W/8)][3] out) / rrv_transfer_frames (pad_crop != 0: UNPADDED frames, reflect
+ * pad and crop on the device, [B][H][W][3] out): uint8 BGR HWC frames in, float32 BGR out — the _u8 twin: uint8, == to_uint8 of
+ * the float form — any B >= 1 in sub-batches of at most sixteen frames through the same staging sets and copy streams;
+ * style_weight[B][n_styles] in host memory. */
+int rrv_transfer_blend_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                             const float* style_weight, int n_styles, int pad_crop, float* out_bgr),
+    rrv_transfer_blend_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                                const float* style_weight, int n_styles, int pad_crop, uint8_t* out_bgr);
+
+/* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
+ * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;
+ * float32 in PIXEL / UNIT / NORM), one image [Hs][Ws] / [H][W] per call.  The style is read in colour, a sampled frame through
+ * the grey fold, by the same first kernel as the content frames; an image derived from uint8 pixels the reference's way gives the
+ * uint8 entry's state bit for bit.  The image is read in the order of hip_stream (NULL: the null stream): what that stream holds
+ * when the call is made precedes the read, and the read is complete when the call returns (both calls synchronise, as their host
+ * twins do; they run once per video).  rrv_add_image_device defers encoding as rrv_add does and keeps the frame in the form it
+ * arrived in; a frame in another form than the pending ones encodes those first. */
+int rrv_prepare_style_image_device(rrv_handle h, const void* d_style, rrv_image_desc in, int Hs, int Ws, int style_id, void* hip_stream);
+int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, int H, int W, void* hip_stream);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

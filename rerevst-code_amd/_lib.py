@@ -24,7 +24,7 @@ class ImageDesc(C.Structure):
 DT_U8, DT_F32 = 0, 1
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
-TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM = 1, 2, 4
+TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8
 DBG_STATE_SET, DBG_STYLE_PRED = 0, 1
 
 # name -> (restype, argtypes); must list every symbol declared in include/rerevst_hip.h
@@ -73,6 +73,11 @@ SYMBOLS = {
     "rrv_transfer_frame_mode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_transfer_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc,
                                             C.c_int, C.c_void_p]),
+    "rrv_transfer_image_blend_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                  C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),      # style_weight: host or device address
+    "rrv_transfer_blend_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),
@@ -103,7 +108,8 @@ SYMBOLS = {
 U8_TWINS = ("rrv_transfer", "rrv_transfer_async", "rrv_transfer_batch", "rrv_transfer_frames", "rrv_transfer_device",
             "rrv_transfer_batch_device", "rrv_transfer_frames_device", "rrv_transfer_blend", "rrv_transfer_blend_device",
             "rrv_transfer_features", "rrv_transfer_features_batch", "rrv_transfer_frame_mode", "rrv_transfer_frame_mode_batch",
-            "rrv_transfer_frame_mode_batch_device", "rrv_transfer_frame_mode_frames", "rrv_transfer_frame_mode_frames_device")
+            "rrv_transfer_frame_mode_batch_device", "rrv_transfer_frame_mode_frames", "rrv_transfer_frame_mode_frames_device",
+            "rrv_transfer_blend_batch")
 SYMBOLS.update({name + "_u8": SYMBOLS[name] for name in U8_TWINS})
 
 

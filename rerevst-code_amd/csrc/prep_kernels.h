@@ -563,6 +563,18 @@ __global__ void blend_states_k(const BlendManyP p) {
         p.out[(size_t)b * p.count + i] = s;
     }
 }
+// the same with the weights in device memory (w[image][style], n floats per image): what the blended frame entries run, for
+// weights a GPU producer wrote as for host weights staged there.  Same sum, same order: the same float32 weights give the same bits.
+struct BlendDevP { const float* st[8]; const float* w; int n; float* out; int count; };
+__global__ void blend_states_dev_k(const BlendDevP p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i < p.count) {
+        const float* __restrict__ w = p.w + (size_t)b * p.n;
+        float s = 0.f;
+        for (int k = 0; k < p.n; ++k) s += w[k] * p.st[k][i];
+        p.out[(size_t)b * p.count + i] = s;
+    }
+}
 __global__ void blend_state_k(const BlendP p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < p.count) {

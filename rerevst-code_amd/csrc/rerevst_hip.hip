@@ -219,6 +219,12 @@ struct rrv_ctx {
     // frames handed to rrv_add wait here (uint8, HBM) and are encoded together, 8 per encoder launch, when their
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
+    int pend_form = IN_U8_HWC, pend_space = SP_PIXEL;      // form of the pending frames (rrv_add_image_device keeps a frame as it arrived; conv_first_k<IN> reads it)
+    // Weights of the blended frame entries (blend_frames_on_slot), per slot 0 / 1: [64][RRV_MAX_STYLES] floats in HBM, which blend_states_dev_k
+    // reads, and for host weights a page-locked ring of BLEND_W_RING such blocks: a call fills the next block and copies it on the slot's
+    // stream; a block is reused BLEND_W_RING calls later, after its copy's event (long past: no host wait in a running pipeline)
+    static constexpr int BLEND_W_RING = 4, BLEND_W_FLOATS = 64 * RRV_MAX_STYLES;
+    struct BlendW { float* dev = nullptr; float* pin = nullptr; hipEvent_t ev[BLEND_W_RING] = {nullptr}; bool used[BLEND_W_RING] = {false}; unsigned gen = 0; } blend_w[2];
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -524,7 +530,7 @@ struct F43LayKey { int EPI, LAY; ConvFn fn; const char* name; AttrFn attr; };
 #define UWS(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1>}
 #define UWSI(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1, 1>, &wino_launch<EPI, UPW_NW, 1, 1, 1>}
 const ConvKey WINO_TABLE[] = {
-    WK(E_RELU), WK(E_RELU | E_POOL), WK(E_RELU | E_NORM1), WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WKI(E_LRELU),      // (E_LRELU per image: filter_down of a batched frame-mode launch without split K)
+    WK(E_RELU), WK(E_RELU | E_POOL), WKI(E_RELU | E_NORM1) /* conv4_1 + Decoder.norm[0]; per image: blended frames */, WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WKI(E_LRELU),      // (E_LRELU per image: filter_down of a batched frame-mode launch without split K)
     WKI(0),     // raw partial sums of a split-K launch
     // KernelFilter 32->512 convs with the folded dynamic filter (+ residual, + AdaIN after Filter3)
     WKI(E_RES), WKI(E_RES | E_NORM2),
@@ -942,7 +948,9 @@ struct PadCrop { int src_H, src_W, top, left; };
 
 // nb: images to encode (plans are grow-only, so a plan may hold room for more)
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
-int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr) {
+// norm0_bstride != 0: image b's Decoder.norm[0] entry is norm0 + b * norm0_bstride (per-image state sets)
+int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
+                int norm0_bstride = 0) {
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
     RCHK(check_image_size(h, H, W, "encoder"));
@@ -967,10 +975,10 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
         for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, *W_(i), B, lh[i], lw[i], le[i], false, 0, false);
         h->enc_p8_tables = p8;
     }
-    const int inf = which == 0 ? h->in_form : IN_U8_HWC;
+    const int inf = h->in_form;      // (the style encoder reads the same forms, in colour: rrv_prepare_style_image_device)
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
-              which == 0 ? h->in_space : SP_PIXEL};
+              h->in_space};
     stamp(h, p8 ? &e.q11 : &e.c11, B);
     static void (*const first_k[4])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>};
     RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, (3.0 * in_elem(inf) + 256.0) * B * H * W, [&] {
@@ -998,7 +1006,9 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
     c = ConvCall{&e.c32, &e.c33, W_(6), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(6); RCHK(conv(h, c));
     c = ConvCall{&e.c33, &e.p3, W_(7), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(7); RCHK(conv(h, c));
     }
-    c = ConvCall{&e.p3, out41 ? out41 : &e.c41, W_(8), e.p3.H, e.p3.W}; c.B = B; c.epi = E_RELU | (norm0 ? E_NORM1 : 0); c.n1 = norm0; c.direct = D_(8); RCHK(conv(h, c));
+    c = ConvCall{&e.p3, out41 ? out41 : &e.c41, W_(8), e.p3.H, e.p3.W}; c.B = B; c.epi = E_RELU | (norm0 ? E_NORM1 : 0); c.n1 = norm0; c.direct = D_(8);
+    if (norm0) c.par_bstride = norm0_bstride;
+    RCHK(conv(h, c));
     return RRV_OK;
 }
 
@@ -1214,7 +1224,9 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         const float* n0 = st + SL.norm[N_DEC0];
         RCHK(pointwise(h, src, e.c41, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
     } else {
-        RCHK(run_encoder(h, e, d_in, 0, st + SL.norm[N_DEC0], pc, B));
+        // per-image state: every frame's relu4_1 is normalised with ITS set's Decoder.norm[0] entry, as the cached-feature branch above does
+        if (h->state_images && h->state_images != B) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per frame");
+        RCHK(run_encoder(h, e, d_in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, h->state_images ? (int)RRV_STATE_FLOATS : 0));
     }
     const Tens* cur = &e.c41;
     for (int f = 0; f < 3; ++f) {
@@ -1770,6 +1782,11 @@ int rrv_destroy(rrv_handle h) {
     if (h->d_u8) (void)hipFree(h->d_u8);
     if (h->d_outf) (void)hipFree(h->d_outf);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
+    for (auto& bw : h->blend_w) {
+        if (bw.dev) (void)hipFree(bw.dev);
+        if (bw.pin) (void)hipHostFree(bw.pin);
+        for (hipEvent_t e : bw.ev) if (e) (void)hipEventDestroy(e);
+    }
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
     for (auto& st : h->hstage) {
@@ -1900,18 +1917,47 @@ int rrv_finalize_weights(rrv_handle h) {
     return RRV_OK;
 }
 
-int rrv_prepare_style(rrv_handle h, const uint8_t* style, int Hs, int Ws, int sid) {
-    if (!h || !style || Hs < 8 || Ws < 8 || sid < 0 || sid >= RRV_MAX_STYLES) return RRV_E_ARG;
+// The image descriptor of the torch-pipeline entries as conv_first_k's input form and value space; false: not a valid input
+static bool image_in_form(const rrv_image_desc& d, int* form, int* space) {
+    if ((d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
+        d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM || (d.dtype == RRV_DT_U8 && d.space != RRV_SP_PIXEL)) return false;
+    *form = (d.dtype == RRV_DT_F32 ? 2 : 0) | (d.layout == RRV_LAY_CHW_RGB ? 1 : 0);
+    *space = d.space;
+    return true;
+}
+// the handle's stream waits for what `stream` (NULL: the null stream) holds so far
+static int wait_for_stream(rrv_handle h, hipStream_t stream) {
+    HIPCHK(hipEventRecord(h->slot_ev[0], stream));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->slot_ev[0], 0));
+    return RRV_OK;
+}
+// conv_first_k reads `form` / `space` while the scope lives (the style image, the sampled frames), uint8 BGR HWC after it
+struct InFormScope {
+    rrv_handle h;
+    InFormScope(rrv_handle h_, int form, int space) : h(h_) { h->in_form = form; h->in_space = space; }
+    ~InFormScope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; }
+};
+
+// device: `style` is in HBM in the given form, complete once `stream` has run what it holds now; else host uint8 BGR HWC
+static int prepare_style(rrv_handle h, const void* style, bool device, int form, int space, hipStream_t stream, int Hs, int Ws, int sid) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     StyleState& S = h->styles[sid];
     if (!S.blob) RCHK(dalloc(h, &S.blob, RRV_STATE_FLOATS));
-    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)Hs * Ws * 3));
-    HIPCHK(hipMemcpyAsync(h->d_u8, style, (size_t)Hs * Ws * 3, hipMemcpyHostToDevice, h->stream));
+    if (device) {
+        RCHK(wait_for_stream(h, stream));
+    } else {
+        RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)Hs * Ws * 3));
+        HIPCHK(hipMemcpyAsync(h->d_u8, style, (size_t)Hs * Ws * 3, hipMemcpyHostToDevice, h->stream));
+    }
     RCHK(enc_plan(h, h->enc_style, 1, Hs, Ws));
     EncPlan& e = h->enc_style;
-    RCHK(run_encoder(h, e, h->d_u8, 1, nullptr, nullptr, 1));
+    {
+        InFormScope in_scope(h, form, space);
+        const int rc = run_encoder(h, e, device ? (const uint8_t*)style : h->d_u8, 1, nullptr, nullptr, 1);
+        if (rc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc; }      // (the caller's image is not read after the call returns)
+    }
     // cal_mean_std at relu1_1..relu4_1 (style_network_global.py:304-331)
     const Tens* taps[4] = {&e.c11, &e.c21, &e.c31, &e.c41};
     for (int k = 0; k < 4; ++k) RCHK(chan_stats(h, *taps[k], 2, S.blob + SL.sty[k]));
@@ -1942,6 +1988,17 @@ int rrv_prepare_style(rrv_handle h, const uint8_t* style, int Hs, int Ws, int si
     return RRV_OK;
 }
 
+int rrv_prepare_style(rrv_handle h, const uint8_t* style, int Hs, int Ws, int sid) {
+    if (!h || !style || Hs < 8 || Ws < 8 || sid < 0 || sid >= RRV_MAX_STYLES) return RRV_E_ARG;
+    return prepare_style(h, style, false, IN_U8_HWC, SP_PIXEL, nullptr, Hs, Ws, sid);
+}
+int rrv_prepare_style_image_device(rrv_handle h, const void* d_style, rrv_image_desc in, int Hs, int Ws, int sid, void* hip_stream) {
+    if (!h || !d_style || Hs < 8 || Ws < 8 || sid < 0 || sid >= RRV_MAX_STYLES) return RRV_E_ARG;
+    int form, space;
+    if (!image_in_form(in, &form, &space)) return fail(h, RRV_E_ARG, "prepare_style: unknown dtype, layout or space (uint8 is PIXEL only)");
+    return prepare_style(h, d_style, true, form, space, (hipStream_t)hip_stream, Hs, Ws, sid);
+}
+
 int rrv_clean(rrv_handle h) {
     if (!h) return RRV_E_ARG;
     (void)hipSetDevice(h->dev);
@@ -1961,9 +2018,10 @@ int rrv_clean(rrv_handle h) {
 static int flush_pending(rrv_handle h) {
     if (!h->pend_n) return RRV_OK;
     const int H = h->add_H, W = h->add_W;
-    const size_t fb = (size_t)H * W * 3;
+    const size_t fb = (size_t)H * W * 3 * in_elem(h->pend_form);
     const int PB = h->pend_n < 8 ? h->pend_n : 8;        // one plan; the last group may use fewer of its images
     RCHK(enc_plan(h, h->enc_add, PB, H, W));
+    InFormScope in_scope(h, h->pend_form, h->pend_space);      // the pending frames are kept in the form they arrived in
     for (int k0 = 0; k0 < h->pend_n; k0 += PB) {
         const int nb = h->pend_n - k0 < PB ? h->pend_n - k0 : PB;
         RCHK(run_encoder(h, h->enc_add, h->pend_u8 + (size_t)k0 * fb, 0, nullptr, nullptr, nb));
@@ -1981,14 +2039,19 @@ static int flush_pending(rrv_handle h) {
     return RRV_OK;
 }
 
-int rrv_add(rrv_handle h, const uint8_t* frame, int H, int W) {
-    if (!h || !frame) return RRV_E_ARG;
+// device: `frame` is in HBM in the given form, complete once `stream` has run what it holds now; else host uint8 BGR HWC
+static int add_frame(rrv_handle h, const void* frame, bool device, int form, int space, hipStream_t stream, int H, int W) {
     RCHK(check_frame(h, H, W, "add"));
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     if ((!h->patches.empty() || h->pend_n) && (H != h->add_H || W != h->add_W))
         return fail(h, RRV_E_ARG, "add: all sampled frames must have the same size");
-    const size_t fb = (size_t)H * W * 3;
+    if (h->pend_n && (form != h->pend_form || space != h->pend_space)) {      // one encoder launch reads one form: encode the pending ones first
+        RCHK(sync_all(h));
+        RCHK(flush_pending(h));
+    }
+    h->pend_form = form; h->pend_space = space;
+    const size_t fb = (size_t)H * W * 3 * in_elem(form);
     if ((size_t)(h->pend_n + 1) * fb > h->pend_cap) {      // grow (x2) keeping the frames already collected
         const size_t cap = ((size_t)(h->pend_n + 1) * fb) * 2 > 16 * fb ? ((size_t)(h->pend_n + 1) * fb) * 2 : 16 * fb;
         uint8_t* nw = nullptr;
@@ -1997,10 +2060,27 @@ int rrv_add(rrv_handle h, const uint8_t* frame, int H, int W) {
         if (h->pend_u8) (void)hipFree(h->pend_u8);
         h->pend_u8 = nw; h->pend_cap = cap;
     }
-    HIPCHK(hipMemcpy(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyHostToDevice));
+    if (device) {      // in the order of the caller's stream, and consumed before the call returns
+        RCHK(wait_for_stream(h, stream));
+        HIPCHK(hipMemcpyAsync(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(hipMemcpy(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyHostToDevice));
+    }
     h->pend_n += 1;
     h->add_H = H; h->add_W = W;
     return RRV_OK;
+}
+
+int rrv_add(rrv_handle h, const uint8_t* frame, int H, int W) {
+    if (!h || !frame) return RRV_E_ARG;
+    return add_frame(h, frame, false, IN_U8_HWC, SP_PIXEL, nullptr, H, W);
+}
+int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, int H, int W, void* hip_stream) {
+    if (!h || !d_frame) return RRV_E_ARG;
+    int form, space;
+    if (!image_in_form(in, &form, &space)) return fail(h, RRV_E_ARG, "add: unknown dtype, layout or space (uint8 is PIXEL only)");
+    return add_frame(h, d_frame, true, form, space, (hipStream_t)hip_stream, H, W);
 }
 
 int rrv_compute(rrv_handle h) {
@@ -2251,9 +2331,11 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 
 // rrv_transfer_image_device: the device entries above with the content frames read as `in` (conv_first_k<IN>) and the
 // stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only
-int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
-                              int flags, void* hip_stream) {
-    if (!h) return RRV_E_ARG;
+static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad,
+                                const float* wts, int ns, bool w_dev);
+// wts != nullptr: rrv_transfer_image_blend_device, one weight vector per image ([B][ns]; in HBM with RRV_TF_WEIGHTS_DEVICE)
+static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
+                       int flags, void* hip_stream, const float* wts, int ns) {
     auto bad = [](const rrv_image_desc& d) {
         return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
                d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
@@ -2261,10 +2343,15 @@ int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in,
     if (bad(in) || bad(out)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
     if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
     if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
-    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM)) return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (wts ? RRV_TF_WEIGHTS_DEVICE : 0))) return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
     if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
     const bool pad = flags & RRV_TF_PAD_CROP, frame = flags & RRV_TF_FRAME_MODE;
     if (pad && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer_image: frames must be at least 1 x 1 pixels");
+    if (wts) {
+        if (frame) return fail(h, RRV_E_ARG, "transfer_image: the frame-mode model has no blended state (style weights need the global model)");
+        if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
+        if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer_image: n_styles must be in 1..RRV_MAX_STYLES");
+    }
     HIPCHK(hipSetDevice(h->dev));
     struct Scope {
         rrv_handle h; hipStream_t cs; bool sync;
@@ -2274,7 +2361,18 @@ int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in,
     h->in_space = in.space;
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
     const OutFmt fmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
+    if (wts) return blend_frames_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, fmt, pad, wts, ns, (flags & RRV_TF_WEIGHTS_DEVICE) != 0);
     return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
+}
+int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
+                              int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, nullptr, 0);
+}
+int rrv_transfer_image_blend_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, const float* style_weight, int n_styles,
+                                    void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
+    if (!h || !style_weight) return RRV_E_ARG;
+    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, style_weight, n_styles);
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
@@ -2329,6 +2427,79 @@ int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const f
 }
 int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, uint8_t* out) {
     return blend_host(h, frame, H, W, wts, ns, out, OUT_U8);
+}
+
+// n <= BLEND_W_FLOATS host weights -> the slot's device block, by a copy on the slot's stream from the next block of its page-locked ring
+static int stage_blend_weights(rrv_handle h, int slot, const float* wts, size_t n, const float** d_w) {
+    rrv_ctx::BlendW& bw = h->blend_w[slot];
+    if (!bw.pin) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, sizeof(float) * rrv_ctx::BLEND_W_RING * rrv_ctx::BLEND_W_FLOATS, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, RRV_E_NOMEM, "blend weights: out of page-locked host memory");
+        }
+        bw.pin = (float*)p;
+    }
+    for (hipEvent_t& e : bw.ev)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int g = (int)(bw.gen++ % rrv_ctx::BLEND_W_RING);
+    if (bw.used[g]) HIPCHK(hipEventSynchronize(bw.ev[g]));
+    float* const blk = bw.pin + (size_t)g * rrv_ctx::BLEND_W_FLOATS;
+    memcpy(blk, wts, n * sizeof(float));
+    HIPCHK(hipMemcpyAsync(bw.dev, blk, n * sizeof(float), hipMemcpyHostToDevice, h->streams[slot]));
+    HIPCHK(hipEventRecord(bw.ev[g], h->streams[slot]));
+    bw.used[g] = true;
+    *d_w = bw.dev;
+    return RRV_OK;
+}
+
+// Multi-style interpolation from FRAMES for 1..64 frames on `slot` (0 or 1: the slots that own sixteen state sets each), every frame
+// with its own weight vector wts[b][0..ns-1] (w_dev: in HBM, written by work the slot's stream is ordered behind; else host memory,
+// staged).  Launch sequences of up to MS_GROUP_MAX frames: the group's state sets := sum_s w[b][s] x state_s (blend_states_dev_k), their
+// KernelFilters folded, then encoder AND decoder from the frames with per-image state (transfer_device, state_images).  With a
+// fixed kernel mode a frame's arithmetic is that of rrv_transfer_blend on the frame alone, bit for bit.
+static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad,
+                                const float* wts, int ns, bool w_dev) {
+    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
+    RCHK(check_frame(h, KH, KW, "transfer"));
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
+    if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
+    for (int s = 0; s < ns; ++s)
+        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "blend: state not computed for every style");
+    // a single-style entry's work in flight reads state set 0, which slot 0's sets include (blended and frame-mode launches
+    // write a slot's sets on that slot's own stream, in order)
+    if (h->active_src >= 0) RCHK(sync_all(h));
+    rrv_ctx::BlendW& bw = h->blend_w[slot];
+    if (!w_dev && !bw.dev) RCHK(dalloc(h, &bw.dev, rrv_ctx::BLEND_W_FLOATS, false));
+    if (h->caller_sync) {      // the weights and the frames the caller's stream produces precede the blends
+        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
+        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
+    }
+    const float* d_w = wts;
+    if (!w_dev) RCHK(stage_blend_weights(h, slot, wts, (size_t)B * ns, &d_w));
+    struct Restore { rrv_handle h; ~Restore() { h->cur = &h->sets[0]; h->state_images = 0; h->stream = h->streams[0]; h->active_src = -2; } } restore{h};
+    const size_t fb = (size_t)H * W * 3 * in_elem(h->in_form), fo = pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
+    const PadCrop pc{H, W, 64, 64};
+    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
+        const int cnt = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
+        h->stream = h->streams[slot];
+        h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
+        BlendDevP bp{};
+        bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS; bp.w = d_w + (size_t)b0 * ns;
+        for (int s = 0; s < ns; ++s) bp.st[s] = h->styles[s].blob;
+        hipLaunchKernelGGL(blend_states_dev_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
+        HIPCHK(hipGetLastError());
+        h->active_src = -2;
+        for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
+        h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
+        const int rc = transfer_device(h, slot, (const uint8_t*)d_in + (size_t)b0 * fb, cnt, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, nullptr,
+                                       pad ? &pc : nullptr);
+        h->state_images = 0;
+        RCHK(rc);
+        h->set_images[slot] = cnt;
+    }
+    return RRV_OK;
 }
 
 // B frames in sub-batches of up to 8 through four staging sets.  Three engines run concurrently: the H2D copy of
@@ -2445,7 +2616,9 @@ static int claim_staging(rrv_handle h) {
     return RRV_OK;
 }
 // frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each); fmt: float32 or uint8 `out`
-static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, void* out, OutFmt fmt, bool pad_on_device = false, bool frame_mode = false) {
+// wts != nullptr: the blended model, frame b with the weights wts[b][0..ns-1] (blend_frames_on_slot per sub-batch)
+static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, void* out, OutFmt fmt, bool pad_on_device = false, bool frame_mode = false,
+                         const float* wts = nullptr, int ns = 0) {
     if (!h || !frames || !out || B < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
@@ -2456,7 +2629,11 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output elements per frame (any input size: 8*(H/8) x 8*(W/8))
     const size_t fob = fo * out_elem(fmt);                                  // ... and their bytes
     char* const outc = (char*)out;
-    const int sub = frame_mode ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
+    const int sub = frame_mode || wts ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
+    auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out) {      // sub-batch k's kernels
+        if (wts) return blend_frames_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, wts + (size_t)k * sub * ns, ns, false);
+        return transfer_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, frame_mode);
+    };
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
@@ -2486,7 +2663,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
-            rc = transfer_on_slot(h, slot, st.dev.in, nb, H, W, st.dev.out, fmt, pad_on_device, frame_mode);
+            rc = run(slot, k, st.dev.in, nb, st.dev.out);
             if (rc != RRV_OK) break;
             HIPCHK(hipMemcpyAsync(out_pin ? out : st.pin.out, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, cs));
             HIPCHK(hipStreamSynchronize(cs));
@@ -2506,7 +2683,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         void* const h_dst = out_pin ? outc + (size_t)k * sub * fob : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
         void* const k_out = zout ? h_dst : st.dev.out;
-        rc = transfer_on_slot(h, slot, k_in, nb, H, W, k_out, fmt, pad_on_device, frame_mode);
+        rc = run(slot, k, k_in, nb, k_out);
         if (rc != RRV_OK) break;
         if (!zin) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
@@ -2545,6 +2722,17 @@ int rrv_transfer_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W
 }
 int rrv_transfer_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
     return host_pipeline(h, frames, B, H, W, out, OUT_U8, true);
+}
+
+static int blend_batch_host(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, void* out, OutFmt fmt) {
+    if (!h || !frames || !out || !wts || B < 1 || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
+    return host_pipeline(h, frames, B, H, W, out, fmt, pad_crop != 0, false, wts, ns);
+}
+int rrv_transfer_blend_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, float* out) {
+    return blend_batch_host(h, frames, B, H, W, wts, ns, pad_crop, out, OUT_F32);
+}
+int rrv_transfer_blend_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, uint8_t* out) {
+    return blend_batch_host(h, frames, B, H, W, wts, ns, pad_crop, out, OUT_U8);
 }
 
 int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {

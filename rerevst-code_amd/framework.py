@@ -182,6 +182,46 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
                     batched=batched)
 
 
+# the per-frame style weights of a blended call, as style_weight_args() works them out: `host` a C-contiguous float32 [B][S]
+# array, or `dev` a float32 torch tensor on the handle's device ([B,S], or [S] with `broadcast` set: one vector for every frame)
+StyleWeights = collections.namedtuple("StyleWeights", "host dev S broadcast")
+
+
+def style_weight_args(style_weights, B, style_num, device, use_Global=True, tensors=False):
+    """Check the `style_weights` of transfer_batch / transfer_frames / transfer_tensor for B frames on a handle made for
+    `style_num` styles, without touching the GPU.  A host sequence or ndarray of shape [B][S] (or one [S] vector, used for
+    every frame) becomes a float32 array; with tensors=True (transfer_tensor) a torch tensor is passed on as it is and must
+    be float32, contiguous, [B,S] or [S], on cuda:`device`.  Raises ValueError otherwise, for S outside 1..style_num, and on
+    a frame-mode handle (use_Global=False: the reference has no blended frame-mode model)."""
+    if not use_Global:
+        raise ValueError("style_weights need the global-feature-sharing model (use_Global=True)")
+    if hasattr(style_weights, "is_contiguous") and hasattr(style_weights, "device"):        # a torch tensor
+        t = style_weights
+        if not tensors:
+            raise ValueError("style_weights must be a host sequence or ndarray here (transfer_tensor takes device tensors)")
+        if t.device.type != "cuda" or t.device.index != int(device):
+            raise ValueError("a style_weights tensor must be on cuda:%d (the handle's device), got %s; pass host weights as "
+                             "a list or ndarray" % (int(device), t.device))
+        if str(t.dtype) != "torch.float32":
+            raise ValueError("a style_weights tensor must be torch.float32, got %s" % (t.dtype,))
+        shp = tuple(t.shape)
+        if t.dim() not in (1, 2) or (t.dim() == 2 and shp[0] != B):
+            raise ValueError("style_weights must have shape [%d, S] or [S], got %s" % (B, shp))
+        if not t.is_contiguous():
+            raise ValueError("a style_weights tensor must be contiguous")
+        host, dev, S = None, t, shp[-1]
+    else:
+        host = np.asarray(style_weights, dtype=np.float32)
+        if host.ndim == 1:
+            host = np.broadcast_to(host, (B, host.shape[0]))
+        if host.ndim != 2 or host.shape[0] != B:
+            raise ValueError("style_weights must have shape [%d][S] or [S], got %s" % (B, np.shape(style_weights)))
+        host, dev, S = np.ascontiguousarray(host), None, host.shape[1]
+    if not 1 <= S <= min(int(style_num), _lib.MAX_STYLES):
+        raise ValueError("style_weights name %d styles; this handle was made for style_num=%d" % (S, style_num))
+    return StyleWeights(host=host, dev=dev, S=S, broadcast=dev is not None and dev.dim() == 1)
+
+
 class Stylization():
     """``Stylization(checkpoint, cuda=True, use_Global=True)`` (test/framework.py:57).
 
@@ -292,6 +332,32 @@ class Stylization():
             a = _u8_image(s, "style")
             self._chk(self._lib.rrv_prepare_style(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], sid))
 
+    def _device_image(self, x, space, layout):
+        """(tensor_io_args' result, current stream) of an input image tensor, by transfer_tensor's rules"""
+        import torch
+        a = tensor_io_args(x, self.device, space=space, layout=layout)
+        return a, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+    def prepare_style_tensor(self, style, *, space="pixel", layout="nchw"):
+        """prepare_style for style images already on the handle's GPU: one torch tensor [3,H,W] RGB (layout="nchw") or
+        [H,W,3] BGR ("nhwc"), or a list of them (multi-style), uint8 or float32 in `space`: transfer_tensor's input
+        conventions.  Read in the order of torch.cuda.current_stream(); complete when the call returns."""
+        styles = style if isinstance(style, (list, tuple)) else [style]
+        for sid, s in enumerate(styles):
+            a, stream = self._device_image(s, space, layout)
+            if a.batched:
+                raise ValueError("a style is one image: [3,H,W] or [H,W,3], got shape %s" % (tuple(s.shape),))
+            self._chk(self._lib.rrv_prepare_style_image_device(self._h, C.c_void_p(a.x.data_ptr()), a.in_desc, a.H, a.W, sid, stream))
+
+    def add_tensor(self, x, *, space="pixel", layout="nchw"):
+        """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch
+        [B,3,H,W] / [B,H,W,3] whose images are added in order."""
+        self._global_only("add")
+        a, stream = self._device_image(x, space, layout)
+        xb = a.x if a.batched else a.x.unsqueeze(0)
+        for b in range(a.B):
+            self._chk(self._lib.rrv_add_image_device(self._h, C.c_void_p(xb[b].data_ptr()), a.in_desc, a.H, a.W, stream))
+
     def transfer(self, frame, style_weight=None, dtype=np.float32):
         """uint8 BGR HWC frame -> float32 BGR HWC in 0..255 (test/framework.py:106-118).
         With `style_weight` (list of floats) the saved state of the prepared styles is
@@ -371,32 +437,49 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def transfer_batch(self, frames, out=None, dtype=np.float32):
+    def _blend_batch(self, a, out, u8, style_weights, pad_crop):
+        """transfer_batch / transfer_frames with one style weight vector per frame (rrv_transfer_blend_batch)"""
+        B, H, W, _ = a.shape
+        w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
+        fn = self._entry("rrv_transfer_blend_batch", u8)
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S,
+                     1 if pad_crop else 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
-        to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does)."""
+        to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
+        style_weights: multi-style interpolation ("Multi-style Interpolation/stylization.py":94-100) from the frames: [B][S]
+        weights, frame b blending the saved state of styles 0..S-1 with style_weights[b] (one [S] vector: every frame);
+        frame b equals transfer(frames[b], style_weight=style_weights[b]), bit for bit for a fixed kernel choice."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
         out, u8 = _output((B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
+        if style_weights is not None:
+            return self._blend_batch(a, out, u8, style_weights, False)
         fn = self._entry("rrv_transfer_batch" if self.use_Global else "rrv_transfer_frame_mode_batch", u8)
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_frames(self, frames, out=None, dtype=np.float32):
+    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
         for a fixed kernel choice, set_f43(0) / set_f43(2); the default picks kernels per launch geometry, the crop window included).
-        `out` / `dtype` as in transfer_batch: uint8 output is to_uint8 of the float output, computed on the GPU."""
+        `out` / `dtype` as in transfer_batch: uint8 output is to_uint8 of the float output, computed on the GPU.
+        style_weights: [B][S] (or [S]) blend weights per frame, as in transfer_batch."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
         out, u8 = _output((B, H, W, 3), dtype, out)
+        if style_weights is not None:
+            return self._blend_batch(a, out, u8, style_weights, True)
         fn = self._entry("rrv_transfer_frames" if self.use_Global else "rrv_transfer_frame_mode_frames", u8)
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
@@ -407,7 +490,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None):
+                        pad_crop=False, out=None, style_weights=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -417,10 +500,17 @@ class Stylization():
         transfer_batch_device writes (uint8: its _u8 twin's), "unit" those / 255 exactly, "norm" the pre-clamp network
         output — with space="norm" as well, what the reference's `self.model(frame)` returns.  pad_crop: the geometry of
         transfer_frames (reflect pad in, crop out: [.., H, W]); otherwise [.., 8*(H//8), 8*(W//8)].  With use_Global=False
-        the frame-mode model runs.  Batches above 64 images are split into calls of 64."""
+        the frame-mode model runs.  Batches above 64 images are split into calls of 64.
+        style_weights: multi-style interpolation, one weight vector per image: a host sequence / ndarray [B][S] (or [S]), or
+        a float32 torch tensor [B,S] (or [S]) on the handle's device, which the library reads on the GPU in the order of
+        the current stream — weights a kernel has just produced need no synchronisation and never visit the host."""
         import torch
         a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
                            out_layout=out_layout, pad_crop=pad_crop, out=out)
+        w = None
+        if style_weights is not None:
+            w = style_weight_args(style_weights, a.B, self.style_num, self.device, self.use_Global, tensors=True)
+            wd = w.dev.unsqueeze(0).expand(a.B, w.S).contiguous() if w.broadcast else w.dev
         if out is None:
             out = torch.empty(a.out_shape, dtype=a.out_dtype, device=x.device)
         xb = a.x if a.batched else a.x.unsqueeze(0)
@@ -429,6 +519,12 @@ class Stylization():
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for b0 in range(0, a.B, TENSOR_BATCH_MAX):
             nb = min(TENSOR_BATCH_MAX, a.B - b0)
+            if w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
+                wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
+                self._chk(self._lib.rrv_transfer_image_blend_device(
+                    self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(wp), w.S, C.c_void_p(ob[b0].data_ptr()),
+                    a.out_desc, flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
+                continue
             self._chk(self._lib.rrv_transfer_image_device(self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W,
                                                           C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
         return out
