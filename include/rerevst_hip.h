@@ -318,6 +318,37 @@ int rrv_transfer_blend_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int
     rrv_transfer_blend_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
                                 const float* style_weight, int n_styles, int pad_crop, uint8_t* out_bgr);
 
+/* Multi-style interpolation with weights that vary PER PIXEL ("Multi-style Interpolation/stylization.py":94-100 transfer(feature,
+ * style_weight) with style_network.py:35-53 mean / rstd / min / max, :135-139 the dynamic filters, :348-360 the style moments, and the
+ * forward pass :432-460 — the reference blends each saved quantity q as sum_s w_s q_s once per frame; here w is a mask).
+ * d_mask: float32 [mask_images][n_styles][H][W] in device memory, planar and contiguous, at the resolution of the frames as passed
+ * (with RRV_TF_PAD_CROP the UNPADDED frame: the mask is reflect-padded on the device exactly as the frame is); mask_images = B (one
+ * mask per frame) or 1 (one mask for every frame); n_styles in 1..RRV_MAX_STYLES, every style 0..n_styles-1 computed (else
+ * RRV_E_STATE).  Nothing normalises the mask.  For a decoder tensor at stride r = 1, 2, 4, 8 of the network's input frame m_s(p) is
+ * the float32 mean of M[s] over the r x r input pixels that tensor pixel p covers (successive 2 x 2 means, a fixed order), and the
+ * decoder forward uses q(p) = sum_s m_s(p) q_s wherever style_network.py:432-460 uses q: clamp((x - mean(p)) rstd(p), lo(p), hi(p)),
+ * the AdaIN affine * std(p) + mean(p), and apply_filter with F1(p) on down_sample's output before the LeakyReLU and F2(p) on the result
+ * before the upsample convolution.  The encoder does not see the mask.  A mask constant over the frame (M[s] == w_s) is
+ * rrv_transfer_image_blend_device with style_weight = w in real arithmetic; in float32 the two differ by rounding, since this entry
+ * runs the decoder unfused (the frame mode's kernels, F(2x2,3x3) in every rrv_set_f43 mode) in launch sequences of up to sixteen
+ * frames: image b's output does not depend on the batch it rides in, bit for bit.  The saved states are only read.
+ * The mask is read in stream order (hip_stream / RRV_TF_ON_STREAM as for rrv_transfer_image_device): a mask computed on the GPU needs
+ * no synchronisation.  flags: RRV_TF_PAD_CROP, RRV_TF_ON_STREAM; RRV_TF_FRAME_MODE is RRV_E_ARG, as are mask_images not in {1, B},
+ * n_styles out of range and a null mask; the handle stays usable.  All image descriptors of rrv_transfer_image_device, in and out.
+ * Consecutive calls alternate over workspace slots 0 and 1.  Workspace per slot and frame size: 8 x 85/64 floats per pixel and frame. */
+int rrv_transfer_image_mask_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W,
+                                   const float* d_mask, int n_styles, int mask_images,
+                                   void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+/* The same model on host buffers (stylization.py:94-100, style_network.py:35-53,135-139,348-360,432-460), pipelined as
+ * rrv_transfer_blend_batch (pad_crop == 0: [B][8*(H/8)][8*(W/8)][3] out; != 0: UNPADDED frames, reflect pad and crop on the device,
+ * [B][H][W][3] out): uint8 BGR HWC frames in, float32 BGR out — the _u8 twin: uint8, == to_uint8 of the float form — any B >= 1 in
+ * sub-batches of at most sixteen frames; mask[mask_images][n_styles][H][W] in host memory, each sub-batch's part copied to HBM in
+ * front of its kernels. */
+int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                            const float* mask, int n_styles, int mask_images, int pad_crop, float* out_bgr),
+    rrv_transfer_mask_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                               const float* mask, int n_styles, int mask_images, int pad_crop, uint8_t* out_bgr);
+
 /* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
  * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;
  * float32 in PIXEL / UNIT / NORM), one image [Hs][Ws] / [H][W] per call.  The style is read in colour, a sampled frame through

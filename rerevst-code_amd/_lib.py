@@ -76,6 +76,9 @@ SYMBOLS = {
     "rrv_transfer_image_blend_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                   C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),      # style_weight: host or device address
     "rrv_transfer_blend_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "rrv_transfer_image_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),      # d_mask: device address
+    "rrv_transfer_mask_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
@@ -109,7 +112,7 @@ U8_TWINS = ("rrv_transfer", "rrv_transfer_async", "rrv_transfer_batch", "rrv_tra
             "rrv_transfer_batch_device", "rrv_transfer_frames_device", "rrv_transfer_blend", "rrv_transfer_blend_device",
             "rrv_transfer_features", "rrv_transfer_features_batch", "rrv_transfer_frame_mode", "rrv_transfer_frame_mode_batch",
             "rrv_transfer_frame_mode_batch_device", "rrv_transfer_frame_mode_frames", "rrv_transfer_frame_mode_frames_device",
-            "rrv_transfer_blend_batch")
+            "rrv_transfer_blend_batch", "rrv_transfer_mask_batch")
 SYMBOLS.update({name + "_u8": SYMBOLS[name] for name in U8_TWINS})
 
 

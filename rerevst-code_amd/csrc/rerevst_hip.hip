@@ -24,6 +24,7 @@
 #include "conv_f43.h"
 #include "conv_thin.h"
 #include "prep_kernels.h"
+#include "mask_kernels.h"
 
 namespace {
 
@@ -92,6 +93,9 @@ struct DecPlan {   // per-frame decoder activations for one (B, H, W) of the FRA
     // batched frame mode only (frame_mode_device): per-image scratch, image b in interior row b (frame_row): chan_stat1_k partials
     // (min(H_l, 512) x 3 x C_l doubles <= 3 x 64 x H), rect_sums_k's nine sums [9][512], pred_mean_k's two predicted means [2][32]
     Tens spart, srect, scm;
+    // masked multi-style entries only (mask_mode_device): the four level masks, level l at H >> l x W >> l, the S weights of a pixel
+    // contiguous in the interior of a ring-layout tensor of RRV_MAX_STYLES channels (mask_kernels.h LevelMask)
+    Tens lm[4];
     float* pre = nullptr;   // [H][W][3] pre-clamp tap
 };
 
@@ -106,7 +110,8 @@ struct PrepPlan {
 // and flags.  A P8 twin of a C-channel tensor is B * C/8 eight-channel images of width W + 6 (EncPlan::q11 ..).
 enum { TS_P8 = 1, TS_ONE = 2 /* one image */, TS_SPLIT = 4 /* C x the KernelFilter split, absent at 1 */, TS_RES = 8 /* resident pass only */, TS_STREAM = 16 /* streaming pass only */,
        TS_FRAME = 32 /* batched frame-mode scratch: ONE tensor of B rows of C x 64 floats (one row per image), built for frame-mode plans only */,
-       TS_PER_ROW = 64 /* TS_FRAME: C x 64 floats per pixel row of the plan (C x 64 x H per image) */ };
+       TS_PER_ROW = 64 /* TS_FRAME: C x 64 floats per pixel row of the plan (C x 64 x H per image) */,
+       TS_MASK = 128 /* level masks: built for the plans of the masked multi-style entries only */ };
 template <class P> struct TSpec {
     size_t off; int level, C, flags;
     Tens& of(P& p) const { return *(Tens*)((char*)&p + off); }
@@ -130,6 +135,8 @@ const TSpec<DecPlan> DEC_T[] = {
     {offsetof(DecPlan, xs[2]), 1, 64}, {offsetof(DecPlan, a[2]), 0, 64}, {offsetof(DecPlan, o[2]), 0, 64}, {offsetof(DecPlan, dpart), 3, 32, TS_SPLIT},
     {offsetof(DecPlan, qa[0]), 2, 256, TS_P8}, {offsetof(DecPlan, qa[1]), 1, 128, TS_P8}, {offsetof(DecPlan, qa[2]), 0, 64, TS_P8},
     {offsetof(DecPlan, spart), 0, 6, TS_FRAME | TS_PER_ROW}, {offsetof(DecPlan, srect), 0, 9 * 512 / 64, TS_FRAME}, {offsetof(DecPlan, scm), 0, 1, TS_FRAME},
+    {offsetof(DecPlan, lm[0]), 0, RRV_MAX_STYLES, TS_MASK}, {offsetof(DecPlan, lm[1]), 1, RRV_MAX_STYLES, TS_MASK}, {offsetof(DecPlan, lm[2]), 2, RRV_MAX_STYLES, TS_MASK},
+    {offsetof(DecPlan, lm[3]), 3, RRV_MAX_STYLES, TS_MASK},
 };
 // levels count from the full-resolution decoder output: relu4_1 (the plan's hh x ww) is level 3
 const TSpec<PrepPlan> PREP_T[] = {
@@ -231,7 +238,12 @@ struct rrv_ctx {
     // Four sets and two dedicated copy streams: the compute streams never wait behind a DMA of their own stream.
     // Each set holds a device pair and a page-locked host pair (stage_reserve), in bytes of frames / bytes of output.
     struct StageBufs { uint8_t* in = nullptr; void* out = nullptr; size_t in_cap = 0, out_cap = 0; };
-    struct HostStage { StageBufs dev, pin; hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr; } hstage[4];
+    struct HostStage {
+        StageBufs dev, pin; hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr;
+        // rrv_transfer_mask_batch: the sub-batch's style masks, in HBM and (for a pageable caller array) page-locked.  Grow-only and
+        // released by rrv_destroy, as the staging buffers above are: rrv_set_debug and the other calls that drop the WORKSPACES keep all of them
+        float *mask = nullptr, *mask_pin = nullptr; size_t mask_cap = 0, mask_pin_cap = 0;
+    } hstage[4];
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     // rrv_transfer_async: ticket t lives in staging set t % 4 until rrv_transfer_wait(t) (or a later submission that needs
     // its set) retires it; `out` / `out_bytes` = where a pageable caller buffer still has to be filled from pin_out
@@ -1082,13 +1094,15 @@ int kf_split(int H8, int W8) {
     return tiles * 8 <= 320 ? 8 : (tiles * 4 <= 512 ? 4 : (tiles * 2 <= 256 ? 2 : 1));
 }
 
-// frame: with the batched frame mode's scratch (a plan built without it is rebuilt)
-int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W, bool frame = false) {       // complete or empty, as enc_plan
-    if (d.B >= B && d.H == H && d.W == W && d.pre && (!frame || d.spart.p)) return RRV_OK;
+// frame: with the batched frame mode's scratch, mask: with the level masks (a plan built without them is rebuilt, and keeps what it had)
+int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W, bool frame = false, bool mask = false) {       // complete or empty, as enc_plan
+    if (d.B >= B && d.H == H && d.W == W && d.pre && (!frame || d.spart.p) && (!mask || d.lm[0].p)) return RRV_OK;
+    if (d.H == H && d.W == W) { frame = frame || d.spart.p; mask = mask || d.lm[0].p; }
     dec_free(h, d);
     const int split = kf_split(H / 8, W / 8);
     RCHK(plan_talloc(h, d, DEC_T, B, H, W, [&](const TSpec<DecPlan>& s) {
         if (s.flags & TS_FRAME) return frame ? s.C : 0;
+        if (s.flags & TS_MASK) return mask ? s.C : 0;
         if (s.flags & TS_P8) return (h->p8 & 2) && p8_fits(H >> s.level, W >> s.level, s.C) ? s.C : 0;
         if (s.flags & TS_SPLIT) return split > 1 ? s.C * split : 0;
         return s.C;
@@ -1278,9 +1292,9 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
 // through xs[k], a[k], o[k].  fused_sc: conv1's kernel also writes the 1x1 shortcut; otherwise conv_shortcut is its own launch,
 // issued once norm2's statistic is taken (the first place that needs it).  last_adain: whether o[2] is normalised at the end.
 enum { WALK_STOP = 1 };     // (RRV_E_* are negative)
-template <class Stat>
-int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], const float* st, long par_bstride, bool fused_sc,
-                   bool last_adain, Stat&& stat) {
+// norm(x, y, n, res, sty) is the normalisation step: y = x normalised with entry n [+ res, upsampled 2x] [AdaIN with style entry sty].
+template <class Stat, class Norm>
+int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], bool fused_sc, bool last_adain, Stat&& stat, Norm&& norm) {
     const Tens* in = &x;
     for (int k = 0; k < 3; ++k) {
         const BlkDesc& b = BLKS[k];
@@ -1291,16 +1305,23 @@ int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[
         if (fused_sc) c.sc_out = &xs[k];
         RCHK(conv(h, c));
         RCHK(stat(a[k], b.n1, 3 * k));
-        RCHK(apply_norm(h, a[k], a[k], st, b.n1, nullptr, -1, par_bstride));
+        RCHK(norm(a[k], a[k], b.n1, (const Tens*)nullptr, -1));
         c = ConvCall{&a[k], &o[k], &h->conv[p + ".conv2"], H2, W2}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
         RCHK(stat(o[k], b.n2, 3 * k + 1));
         if (!fused_sc) { c = ConvCall{in, &xs[k], &h->conv[p + ".conv_shortcut"], in->H, in->W}; c.B = B; RCHK(conv(h, c)); }
-        RCHK(apply_norm(h, o[k], o[k], st, b.n2, &xs[k], -1, par_bstride));
+        RCHK(norm(o[k], o[k], b.n2, (const Tens*)&xs[k], -1));
         RCHK(stat(o[k], b.nada, 3 * k + 2));     // (a fused pointwise + statistics pass measured slower than the two kernels)
-        if (k < 2 || last_adain) RCHK(apply_norm(h, o[k], o[k], st, b.nada, nullptr, b.sty, par_bstride));
+        if (k < 2 || last_adain) RCHK(norm(o[k], o[k], b.nada, (const Tens*)nullptr, b.sty));
         in = &o[k];
     }
     return RRV_OK;
+}
+// the walk with the saved statistics of state `st` applied by pointwise_k (apply_norm): the preparation pass and the frame mode
+template <class Stat>
+int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], const float* st, long par_bstride, bool fused_sc,
+                   bool last_adain, Stat&& stat) {
+    return unfused_blocks(h, B, x, xs, a, o, fused_sc, last_adain, stat,
+                          [&](const Tens& t, Tens& y, int n, const Tens* res, int sty) { return apply_norm(h, t, y, st, n, res, sty, par_bstride); });
 }
 
 // ---- preparation: Decoder.compute for one style ---------------------------------------------
@@ -1479,6 +1500,115 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
         for (Tens* t : {&d.f[k], &d.xs[k], &d.a[k], &d.o[k]}) stamp(h, t, B);
     h->set_images[slot] = B;
     if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
+    return RRV_OK;
+}
+
+// ---- masked multi-style transfer: the saved state blended per pixel ---------------------------------------------------------
+// "Multi-style Interpolation/stylization.py":94-100 blends every saved quantity q as sum_s w_s q_s once per frame
+// (style_network.py:35-53,135-139,348-360) and runs the forward pass :432-460.  Here w is a mask at the frame's resolution: at a
+// tensor pixel p of a decoder level q(p) = sum_s m_s(p) q_s, m the mean of the mask over the input pixels p covers (mask_kernels.h).
+// The state cannot be folded into weights or fused epilogues, so the decoder runs the unfused walk of the frame mode with the
+// saved statistics of the S styles in place of per-frame ones: encoder (raw relu4_1) -> mask pyramid -> masked norm[0] -> per
+// filter {down_sample raw (split K as filter_down) -> mask_filter_k (F1(p), LeakyReLU, F2(p)) -> upsample + residual} -> masked
+// norm[1] + AdaIN -> per block {conv1 + shortcut -> masked norm1 -> conv2 -> masked norm2 + shortcut -> masked AdaIN} -> slice1.
+// F(2x2,3x3) throughout (f43_path stays false) and a split that follows the frame size: an image's bits do not depend on its batch.
+// The styles' blobs are only read and no state set is written: the entries around a masked call keep their bits.
+
+LevelMask level_mask(const Tens& t, int S, bool one) {
+    return LevelMask{t.p + (size_t)(t.W + 3) * t.C, one ? 0 : (long)t.img_floats(), (t.W + 2) * t.C, S};
+}
+
+int mask_norm(rrv_handle h, const Tens& x, Tens& y, const MaskStates& ms, int S, int n, const Tens* res, int sty, const LevelMask& m) {
+    if (x.C % 64) return fail(h, RRV_E_ARG, "mask_norm: channels must be a multiple of 64");
+    MaskNormP p{x.p, y.p, x.B, x.H, x.W, x.C, ms, S, SL.norm[n], sty < 0 ? -1 : SL.sty[sty], res ? res->p : nullptr, res ? res->H : 0, res ? res->W : 0, m, 1};
+    // one block per image row and group of 64 channels; small tensors split their rows so that a few hundred blocks exist
+    const long rows = (long)x.B * x.H * (x.C / 64);
+    int segs = rows >= 1024 ? 1 : (int)((1024 + rows - 1) / rows);
+    const int max_segs = (x.W + 15) / 16;
+    p.segs = segs > max_segs ? max_segs : segs;
+    stamp(h, &y, x.B);
+    return launch(h, "mask_norm", 0, 8.0 * x.B * x.H * x.W * x.C, [&] { hipLaunchKernelGGL(mask_norm_k, dim3((unsigned)(rows * p.segs)), dim3(256), 0, h->stream, p); });
+}
+
+typedef void (*PyrFn)(const MaskPyrP&, dim3, hipStream_t);
+template <int S> void pyr_launch(const MaskPyrP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(mask_pyramid_k<S>, grid, dim3(256), 0, s, p); }
+
+// B <= MS_GROUP_MAX frames on `slot` (geometry as frame_mode_device); d_mask: [Bm][S][mH][mW] float32 in HBM, Bm = B or 1, at the
+// resolution of the frames as the caller passed them (pc: the unpadded frame)
+int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, const float* d_mask, int S, bool one_mask, void* d_out, OutFmt fmt,
+                     const PadCrop* pc) {
+    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "masked transfer: batch must be in 1..16 on slot 0 or 1");
+    const int Ho = H / 8 * 8, Wo = W / 8 * 8;
+    struct Scope { rrv_handle h; ~Scope() { h->stream = h->streams[0]; } } scope{h};
+    h->stream = h->streams[slot];
+    h->set_images[slot] = 0;                              // this launch keeps no per-image state set
+    EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
+    DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
+    RCHK(enc_plan(h, e, B, H, W, true));
+    RCHK(dec_plan(h, d, B, Ho, Wo, false, true));
+    e.gen = d.gen = ++h->launch_gen;
+    MaskStates ms{};
+    for (int s = 0; s < S; ++s) ms.blob[s] = h->styles[s].blob;
+    {   // the four level masks
+        MaskPyrP pp{d_mask, pc ? pc->src_H : H, pc ? pc->src_W : W, pc ? 1 : 0, pc ? pc->top : 0, pc ? pc->left : 0, Ho / 8, Wo / 8, {}, {}, {}};
+        for (int l = 0; l < 4; ++l) {
+            const LevelMask m = level_mask(d.lm[l], S, false);
+            pp.lv[l] = const_cast<float*>(m.p); pp.bstride[l] = m.bstride; pp.pitch[l] = m.pitch;
+            stamp(h, &d.lm[l], one_mask ? 1 : B);
+        }
+        static const PyrFn pyr[8] = {pyr_launch<1>, pyr_launch<2>, pyr_launch<3>, pyr_launch<4>, pyr_launch<5>, pyr_launch<6>, pyr_launch<7>, pyr_launch<8>};
+        const int nm = one_mask ? 1 : B;
+        RCHK(launch(h, "mask_pyramid", 0, 8.0 * nm * S * Ho * Wo, [&] {
+            pyr[S - 1](pp, dim3((unsigned)(((Ho / 8) * (Wo / 8) + 255) / 256), (unsigned)nm), h->stream);
+        }));
+    }
+    LevelMask lm[4];
+    for (int l = 0; l < 4; ++l) lm[l] = level_mask(d.lm[l], S, one_mask);
+    RCHK(run_encoder(h, e, d_in, 0, nullptr, pc, B));
+    Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
+    Tens fo[3], xs[3], a[3], o[3], dd = d.d, dpart = d.dpart;
+    dd.B = dpart.B = B;
+    for (int k = 0; k < 3; ++k) {
+        fo[k] = d.f[k]; xs[k] = d.xs[k]; a[k] = d.a[k]; o[k] = d.o[k];
+        fo[k].B = xs[k].B = a[k].B = o[k].B = B;
+    }
+    // Decoder.norm[0], clamped, with the statistics blended at every relu4_1 pixel
+    RCHK(mask_norm(h, c41, c41, ms, S, N_DEC0, nullptr, -1, lm[3]));
+    const int split = kf_split(c41.H, c41.W);
+    const Tens* cur = &c41;
+    for (int f = 0; f < 3; ++f) {
+        char pre[64];
+        snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
+        const ConvW& wd = h->conv[std::string(pre) + ".down_sample.0"];
+        const ConvW& wu = h->conv[std::string(pre) + ".upsample.0"];
+        // down_sample, raw: its bias is added by mask_filter_k (split K: the slabs' partial sums are summed there, in order)
+        Tens& raw = split > 1 ? dpart : dd;
+        ConvCall c{cur, &raw, &wd, cur->H, cur->W}; c.B = B; c.epi = 0; c.bias = h->zero_bias;
+        if (split > 1) c.ksplit = split;
+        RCHK(conv(h, c));
+        MaskFilterP fp{raw.p, split, dd.p, wd.bias, ms, S, SL.filt[2 * f], SL.filt[2 * f + 1], lm[3], B, dd.H, dd.W};
+        const long npix = (long)B * dd.H * dd.W;
+        stamp(h, &dd, B);
+        RCHK(launch(h, "mask_filter", 2.0 * npix * 2048 * (S + 1), 4.0 * npix * 32 * (split + 1), [&] {
+            hipLaunchKernelGGL(mask_filter_k, dim3((unsigned)((npix + 63) / 64)), dim3(256), mask_filter_smem(S), h->stream, fp);
+        }));
+        ConvCall u{&dd, &fo[f], &wu, cur->H, cur->W}; u.B = B; u.epi = E_RES; u.res = cur;
+        RCHK(conv(h, u));
+        cur = &fo[f];
+    }
+    // Decoder.norm[1] + the relu4_1 AdaIN affine
+    RCHK(mask_norm(h, *cur, fo[2], ms, S, N_DEC1, nullptr, 3, lm[3]));
+    RCHK(unfused_blocks(h, B, *cur, xs, a, o, true, true, [](const Tens&, int, int) { return (int)RRV_OK; },
+                        [&](const Tens& t, Tens& y, int n, const Tens* res, int sty) {
+                            const int l = t.H == d.lm[0].H ? 0 : t.H == d.lm[1].H ? 1 : 2;
+                            return mask_norm(h, t, y, ms, S, n, res, sty, lm[l]);
+                        }));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, fmt, d.pre, pc));
+    stamp(h, &e.c41, B); stamp(h, &d.d, B);
+    if (split > 1) stamp(h, &d.dpart, B);
+    for (int k = 0; k < 3; ++k)
+        for (Tens* t : {&d.f[k], &d.xs[k], &d.a[k], &d.o[k]}) stamp(h, t, B);
+    if (h->debug) RCHK(debug_verify(h, "transfer (masked multi-style)"));
     return RRV_OK;
 }
 
@@ -1792,6 +1922,8 @@ int rrv_destroy(rrv_handle h) {
     for (auto& st : h->hstage) {
         stage_free(st.pin, true);
         stage_free(st.dev, false);
+        if (st.mask) (void)hipFree(st.mask);
+        if (st.mask_pin) (void)hipHostFree(st.mask_pin);
         for (hipEvent_t e : {st.in_done, st.k_done, st.out_done}) if (e) (void)hipEventDestroy(e);
     }
     if (h->copy_in) (void)hipStreamDestroy(h->copy_in);
@@ -1883,6 +2015,9 @@ int rrv_finalize_weights(rrv_handle h) {
         snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
         RCHK(make_conv(h, std::string(pre) + ".down_sample.0", 32, 512, 9, true, false));
         RCHK(make_conv(h, std::string(pre) + ".upsample.0", 512, 32, 9, true, false));
+        // the masked multi-style entries run both layers unfolded, around mask_filter_k, on the row-split transform-domain kernel
+        RCHK(pack_wino(h, h->conv[std::string(pre) + ".down_sample.0"]));
+        RCHK(pack_wino(h, h->conv[std::string(pre) + ".upsample.0"]));
         for (int g = 0; g < 2; ++g) {
             const std::string q = std::string(pre) + (g ? ".F2" : ".F1");
             RCHK(make_conv(h, q + ".down_sample.0", 32, 512, 9, true));
@@ -2333,9 +2468,12 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 // stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only
 static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad,
                                 const float* wts, int ns, bool w_dev);
+static int mask_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, const float* d_mask, int ns, int mask_images, void* d_out,
+                               OutFmt fmt, bool pad);
+// d_mask != nullptr: rrv_transfer_image_mask_device, the styles blended per pixel by [mask_images][ns][H][W] float32 masks in HBM
 // wts != nullptr: rrv_transfer_image_blend_device, one weight vector per image ([B][ns]; in HBM with RRV_TF_WEIGHTS_DEVICE)
 static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
-                       int flags, void* hip_stream, const float* wts, int ns) {
+                       int flags, void* hip_stream, const float* wts, int ns, const float* d_mask = nullptr, int mask_images = 0) {
     auto bad = [](const rrv_image_desc& d) {
         return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
                d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
@@ -2347,10 +2485,11 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B,
     if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
     const bool pad = flags & RRV_TF_PAD_CROP, frame = flags & RRV_TF_FRAME_MODE;
     if (pad && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer_image: frames must be at least 1 x 1 pixels");
-    if (wts) {
+    if (wts || d_mask) {
         if (frame) return fail(h, RRV_E_ARG, "transfer_image: the frame-mode model has no blended state (style weights need the global model)");
         if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
         if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer_image: n_styles must be in 1..RRV_MAX_STYLES");
+        if (d_mask && mask_images != 1 && mask_images != B) return fail(h, RRV_E_ARG, "transfer_image: mask_images must be 1 or B");
     }
     HIPCHK(hipSetDevice(h->dev));
     struct Scope {
@@ -2362,6 +2501,7 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B,
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
     const OutFmt fmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
     if (wts) return blend_frames_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, fmt, pad, wts, ns, (flags & RRV_TF_WEIGHTS_DEVICE) != 0);
+    if (d_mask) return mask_frames_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_mask, ns, mask_images, d_out, fmt, pad);
     return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
 }
 int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
@@ -2373,6 +2513,13 @@ int rrv_transfer_image_blend_device(rrv_handle h, const void* d_in, rrv_image_de
                                     void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
     if (!h || !style_weight) return RRV_E_ARG;
     return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, style_weight, n_styles);
+}
+
+int rrv_transfer_image_mask_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, const float* d_mask, int n_styles,
+                                   int mask_images, void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!d_mask) return fail(h, RRV_E_ARG, "transfer_image: null mask");
+    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, nullptr, n_styles, d_mask, mask_images);
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
@@ -2502,6 +2649,38 @@ static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B,
     return RRV_OK;
 }
 
+// Per-pixel multi-style blending for 1..64 frames on `slot` (0 or 1): launch sequences of up to MS_GROUP_MAX frames (mask_mode_device).
+// d_mask: [mask_images][ns][H][W] float32 in HBM, written by work the slot's stream is ordered behind; mask_images = B, or 1 = one mask
+// for every frame.  No state set is touched, so nothing in flight has to drain first.
+static int mask_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, const float* d_mask, int ns, int mask_images, void* d_out,
+                               OutFmt fmt, bool pad) {
+    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
+    RCHK(check_frame(h, KH, KW, "transfer"));
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
+    if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
+    if (mask_images != 1 && mask_images != B) return fail(h, RRV_E_ARG, "transfer: mask_images must be 1 or B");
+    for (int s = 0; s < ns; ++s)
+        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "masked transfer: state not computed for every style");
+    if (h->caller_sync) {      // the mask and the frames the caller's stream produces precede the launches
+        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
+        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
+    }
+    const size_t fb = (size_t)H * W * 3 * in_elem(h->in_form), fo = pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
+    const size_t mf = (size_t)ns * H * W;
+    const PadCrop pc{H, W, 64, 64};
+    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
+        const int cnt = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
+        RCHK(mask_mode_device(h, slot, (const uint8_t*)d_in + (size_t)b0 * fb, cnt, KH, KW, d_mask + (mask_images == 1 ? 0 : (size_t)b0 * mf), ns, mask_images == 1,
+                              out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
+    }
+    if (h->caller_sync) {
+        HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
+        HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
+    }
+    return RRV_OK;
+}
+
 // B frames in sub-batches of up to 8 through four staging sets.  Three engines run concurrently: the H2D copy of
 // sub-batch k+1.. (copy_in stream), the kernels of k and k+1 (the two compute streams), the D2H copy of k-1 (copy_out
 // stream); events order a set's H2D -> kernels -> D2H and its re-use four sub-batches later.  With pageable caller
@@ -2618,7 +2797,7 @@ static int claim_staging(rrv_handle h) {
 // frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each); fmt: float32 or uint8 `out`
 // wts != nullptr: the blended model, frame b with the weights wts[b][0..ns-1] (blend_frames_on_slot per sub-batch)
 static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, void* out, OutFmt fmt, bool pad_on_device = false, bool frame_mode = false,
-                         const float* wts = nullptr, int ns = 0) {
+                         const float* wts = nullptr, int ns = 0, const float* mask = nullptr, int mask_images = 0) {
     if (!h || !frames || !out || B < 1) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
@@ -2629,12 +2808,19 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output elements per frame (any input size: 8*(H/8) x 8*(W/8))
     const size_t fob = fo * out_elem(fmt);                                  // ... and their bytes
     char* const outc = (char*)out;
-    const int sub = frame_mode || wts ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
-    auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out) {      // sub-batch k's kernels
+    const int sub = frame_mode || wts || mask ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
+    const size_t mfl = (size_t)ns * H * W;      // floats of one image's masks
+    auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out) -> int {      // sub-batch k's kernels
+        if (mask) return mask_frames_on_slot(h, slot, d_in, nb, H, W, h->hstage[k % HOST_SETS].mask, ns, mask_images == 1 ? 1 : nb, d_out, fmt, pad_on_device);
         if (wts) return blend_frames_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, wts + (size_t)k * sub * ns, ns, false);
         return transfer_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, frame_mode);
     };
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
+    // the masks are staged like the frames: a sub-batch's part goes through the set's page-locked block (unless the caller's array is
+    // page-locked) to its HBM block by a copy on copy_in, in front of the in_done event its kernels wait for; k_done frees both again
+    const size_t msub = (size_t)(mask_images == 1 ? 1 : sub) * mfl;
+    const bool m_pin = mask && is_pinned(mask, (size_t)mask_images * mfl * sizeof(float));
+    const bool host_in = !in_pin || (mask && !m_pin);      // a page-locked input block of the set is refilled by the host
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
@@ -2642,6 +2828,19 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));
+        if (!mask) continue;
+        rrv_ctx::HostStage& st = h->hstage[i];
+        RCHK(ensure_dev(h, st.mask, st.mask_cap, msub));
+        if (!m_pin && st.mask_pin_cap < msub) {
+            if (st.mask_pin) (void)hipHostFree(st.mask_pin);
+            st.mask_pin = nullptr; st.mask_pin_cap = 0;
+            if (hipHostMalloc((void**)&st.mask_pin, msub * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                st.mask_pin = nullptr;
+                return fail(h, RRV_E_NOMEM, "staging: out of page-locked host memory");
+            }
+            st.mask_pin_cap = msub;
+        }
     }
     auto count = [&](int k) { return (k + 1) * sub <= B ? sub : B - k * sub; };
     auto drain = [&](int k) -> int {       // sub-batch k delivered (its staging set is free again)
@@ -2654,15 +2853,23 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
     for (int k = 0; k < nchunk && rc == RRV_OK; ++k) {
         auto& st = h->hstage[k % HOST_SETS];
         const bool reuse = k >= HOST_SETS;
-        if (reuse && (!in_pin || !out_pin)) rc = drain(k - HOST_SETS);   // pinned staging of this set is about to be overwritten
+        if (reuse && (host_in || !out_pin)) rc = drain(k - HOST_SETS);   // pinned staging of this set is about to be overwritten
         if (rc != RRV_OK) break;
         const int nb = count(k);
         const uint8_t* src = frames + (size_t)k * sub * fb;
         if (!in_pin) { host_copy(st.pin.in, src, (size_t)nb * fb); src = st.pin.in; }
+        const float* msrc = nullptr;
+        size_t mbytes = 0;
+        if (mask) {
+            msrc = mask + (mask_images == 1 ? 0 : (size_t)k * sub * mfl);
+            mbytes = (size_t)(mask_images == 1 ? 1 : nb) * mfl * sizeof(float);
+            if (!m_pin) { host_copy(st.mask_pin, msrc, mbytes); msrc = st.mask_pin; }
+        }
         const int slot = h->profiling ? 0 : (k & 1) % h->n_slots;
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
+            if (mask) HIPCHK(hipMemcpyAsync(st.mask, msrc, mbytes, hipMemcpyHostToDevice, cs));
             rc = run(slot, k, st.dev.in, nb, st.dev.out);
             if (rc != RRV_OK) break;
             HIPCHK(hipMemcpyAsync(out_pin ? out : st.pin.out, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, cs));
@@ -2673,28 +2880,31 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
         // zero copy per direction (rrv_set_host_io: 1 both, 2 input only, 3 output only): the first kernel reads the page-locked
         // source over PCIe / the last one writes the destination; the other direction keeps its copy stream
         const uint8_t* k_in = src;
-        if (!zin) {
-            if (reuse) HIPCHK(hipStreamWaitEvent(h->copy_in, st.k_done, 0));       // the kernels of k-4 have read d_in
-            HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
+        if (!zin || mask) {
+            if (reuse) HIPCHK(hipStreamWaitEvent(h->copy_in, st.k_done, 0));       // the kernels of k-4 have read d_in (and the set's masks)
+            if (!zin) {
+                HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
+                k_in = st.dev.in;
+            }
+            if (mask) HIPCHK(hipMemcpyAsync(st.mask, msrc, mbytes, hipMemcpyHostToDevice, h->copy_in));
             HIPCHK(hipEventRecord(st.in_done, h->copy_in));
             HIPCHK(hipStreamWaitEvent(cs, st.in_done, 0));
-            k_in = st.dev.in;
         }
         void* const h_dst = out_pin ? outc + (size_t)k * sub * fob : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
         void* const k_out = zout ? h_dst : st.dev.out;
         rc = run(slot, k, k_in, nb, k_out);
         if (rc != RRV_OK) break;
-        if (!zin) HIPCHK(hipEventRecord(st.k_done, cs));
+        if (!zin || mask) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
-        if (zin) HIPCHK(hipEventRecord(st.k_done, cs));
+        if (zin && !mask) HIPCHK(hipEventRecord(st.k_done, cs));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
         HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
     }
     if (rc != RRV_OK) { (void)sync_all(h); return rc; }
-    const int first_open = (!in_pin || !out_pin) ? (nchunk - HOST_SETS < 0 ? 0 : nchunk - HOST_SETS) : 0;
-    if (in_pin && out_pin) {               // nothing to copy on the host: the last D2H of each stream order completes everything
+    const int first_open = (host_in || !out_pin) ? (nchunk - HOST_SETS < 0 ? 0 : nchunk - HOST_SETS) : 0;
+    if (!host_in && out_pin) {               // nothing to copy on the host: the last D2H of each stream order completes everything
         if (zout) RCHK(sync_all(h));
         else HIPCHK(hipStreamSynchronize(h->copy_out));
     } else {
@@ -2733,6 +2943,21 @@ int rrv_transfer_blend_batch(rrv_handle h, const uint8_t* frames, int B, int H, 
 }
 int rrv_transfer_blend_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, uint8_t* out) {
     return blend_batch_host(h, frames, B, H, W, wts, ns, pad_crop, out, OUT_U8);
+}
+
+static int mask_batch_host(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, void* out, OutFmt fmt) {
+    if (!h) return RRV_E_ARG;
+    if (!frames || !out || !mask || B < 1 || ns < 1 || ns > RRV_MAX_STYLES || (mask_images != 1 && mask_images != B))
+        return fail(h, RRV_E_ARG, "transfer_mask_batch: null buffer, n_styles not in 1..RRV_MAX_STYLES or mask_images not 1 or B");
+    for (int s = 0; s < ns; ++s)
+        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "masked transfer: state not computed for every style");
+    return host_pipeline(h, frames, B, H, W, out, fmt, pad_crop != 0, false, nullptr, ns, mask, mask_images);
+}
+int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, float* out) {
+    return mask_batch_host(h, frames, B, H, W, mask, ns, mask_images, pad_crop, out, OUT_F32);
+}
+int rrv_transfer_mask_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, uint8_t* out) {
+    return mask_batch_host(h, frames, B, H, W, mask, ns, mask_images, pad_crop, out, OUT_U8);
 }
 
 int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {

@@ -222,6 +222,45 @@ def style_weight_args(style_weights, B, style_num, device, use_Global=True, tens
     return StyleWeights(host=host, dev=dev, S=S, broadcast=dev is not None and dev.dim() == 1)
 
 
+StyleMasks = collections.namedtuple("StyleMasks", "host dev S images")
+
+
+def style_mask_args(style_masks, style_weights, B, H, W, style_num, device, use_Global=True, tensors=False):
+    """Check the `style_masks` of transfer_batch / transfer_frames / transfer_tensor for B frames of H x W (the frames as the
+    caller passes them) on a handle made for `style_num` styles, without touching the GPU.  A float32 ndarray [B][S][H][W]
+    (one mask per frame) or [S][H][W] (one mask for every frame); with tensors=True (transfer_tensor) also a contiguous
+    float32 torch tensor of those shapes on cuda:`device`, passed on as it is.  Nothing is converted or normalised: another
+    dtype or shape raises ValueError, as do S outside 1..style_num, style_weights given as well, and a frame-mode handle
+    (use_Global=False: the reference's frame-mode model has no blended state).  `images` is B or 1."""
+    if style_weights is not None:
+        raise ValueError("style_masks and style_weights are mutually exclusive (a mask constant over the frame is a weight vector)")
+    if not use_Global:
+        raise ValueError("style_masks need the global-feature-sharing model (use_Global=True)")
+    m = style_masks
+    if hasattr(m, "is_contiguous") and hasattr(m, "device"):        # a torch tensor
+        if not tensors:
+            raise ValueError("style_masks must be a float32 ndarray here (transfer_tensor takes device tensors)")
+        if m.device.type != "cuda" or m.device.index != int(device):
+            raise ValueError("a style_masks tensor must be on cuda:%d (the handle's device), got %s" % (int(device), m.device))
+        if str(m.dtype) != "torch.float32":
+            raise ValueError("a style_masks tensor must be torch.float32, got %s" % (m.dtype,))
+        if not m.is_contiguous():
+            raise ValueError("a style_masks tensor must be contiguous")
+        host, dev, shp = None, m, tuple(m.shape)
+    else:
+        if not isinstance(m, np.ndarray):
+            raise ValueError("style_masks must be a float32 ndarray (or, for transfer_tensor, a torch tensor), got %s" % type(m).__name__)
+        if m.dtype != np.float32:
+            raise ValueError("style_masks must be float32, got %s" % (m.dtype,))
+        host, dev, shp = np.ascontiguousarray(m), None, m.shape
+    if len(shp) not in (3, 4) or tuple(shp[-2:]) != (H, W) or (len(shp) == 4 and shp[0] != B):
+        raise ValueError("style_masks must have shape [%d][S][%d][%d] or [S][%d][%d], got %s" % (B, H, W, H, W, tuple(shp)))
+    S = shp[-3]
+    if not 1 <= S <= min(int(style_num), _lib.MAX_STYLES):
+        raise ValueError("style_masks name %d styles; this handle was made for style_num=%d" % (S, style_num))
+    return StyleMasks(host=host, dev=dev, S=S, images=B if len(shp) == 4 else 1)
+
+
 class Stylization():
     """``Stylization(checkpoint, cuda=True, use_Global=True)`` (test/framework.py:57).
 
@@ -446,38 +485,57 @@ class Stylization():
                      1 if pad_crop else 0, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None):
+    def _mask_batch(self, a, out, u8, m, pad_crop):
+        """transfer_batch / transfer_frames with per-pixel style masks (rrv_transfer_mask_batch)"""
+        B, H, W, _ = a.shape
+        fn = self._entry("rrv_transfer_mask_batch", u8)
+        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images,
+                     1 if pad_crop else 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
         style_weights: multi-style interpolation ("Multi-style Interpolation/stylization.py":94-100) from the frames: [B][S]
         weights, frame b blending the saved state of styles 0..S-1 with style_weights[b] (one [S] vector: every frame);
-        frame b equals transfer(frames[b], style_weight=style_weights[b]), bit for bit for a fixed kernel choice."""
+        frame b equals transfer(frames[b], style_weight=style_weights[b]), bit for bit for a fixed kernel choice.
+        style_masks: the styles blended PER PIXEL instead: a float32 ndarray [B][S][H][W] (or [S][H][W]: every frame) at the
+        frames' resolution; every saved quantity becomes sum_s m_s(p) q_s at each decoder pixel p, m the mean of the mask
+        over the input pixels p covers (rrv_transfer_mask_batch).  Not normalised; mutually exclusive with style_weights."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
+        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         out, u8 = _output((B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
+        if m is not None:
+            return self._mask_batch(a, out, u8, m, False)
         if style_weights is not None:
             return self._blend_batch(a, out, u8, style_weights, False)
         fn = self._entry("rrv_transfer_batch" if self.use_Global else "rrv_transfer_frame_mode_batch", u8)
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None):
+    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
         for a fixed kernel choice, set_f43(0) / set_f43(2); the default picks kernels per launch geometry, the crop window included).
         `out` / `dtype` as in transfer_batch: uint8 output is to_uint8 of the float output, computed on the GPU.
-        style_weights: [B][S] (or [S]) blend weights per frame, as in transfer_batch."""
+        style_weights: [B][S] (or [S]) blend weights per frame, as in transfer_batch.
+        style_masks: [B][S][H][W] (or [S][H][W]) per-pixel blend weights for the UNPADDED frames, as in transfer_batch; the
+        mask is reflect-padded on the device as the frame is."""
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
+        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         out, u8 = _output((B, H, W, 3), dtype, out)
+        if m is not None:
+            return self._mask_batch(a, out, u8, m, True)
         if style_weights is not None:
             return self._blend_batch(a, out, u8, style_weights, True)
         fn = self._entry("rrv_transfer_frames" if self.use_Global else "rrv_transfer_frame_mode_frames", u8)
@@ -490,7 +548,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None, style_weights=None):
+                        pad_crop=False, out=None, style_weights=None, style_masks=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -503,11 +561,19 @@ class Stylization():
         the frame-mode model runs.  Batches above 64 images are split into calls of 64.
         style_weights: multi-style interpolation, one weight vector per image: a host sequence / ndarray [B][S] (or [S]), or
         a float32 torch tensor [B,S] (or [S]) on the handle's device, which the library reads on the GPU in the order of
-        the current stream — weights a kernel has just produced need no synchronisation and never visit the host."""
+        the current stream — weights a kernel has just produced need no synchronisation and never visit the host.
+        style_masks: the styles blended per pixel (rrv_transfer_image_mask_device): a float32 torch tensor [B,S,H,W] (or
+        [S,H,W]: every image) on the handle's device, read in the order of the current stream with no host synchronisation,
+        or a float32 ndarray of those shapes (copied to the device on that stream).  H, W are those of x.  Mutually exclusive
+        with style_weights."""
         import torch
         a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
                            out_layout=out_layout, pad_crop=pad_crop, out=out)
-        w = None
+        w = m = None
+        if style_masks is not None:
+            m = style_mask_args(style_masks, style_weights, a.B, a.H, a.W, self.style_num, self.device, self.use_Global, tensors=True)
+            md = m.dev if m.dev is not None else torch.from_numpy(m.host).to(x.device, non_blocking=False)
+            md = md if m.images == 1 else md.reshape(a.B, -1)
         if style_weights is not None:
             w = style_weight_args(style_weights, a.B, self.style_num, self.device, self.use_Global, tensors=True)
             wd = w.dev.unsqueeze(0).expand(a.B, w.S).contiguous() if w.broadcast else w.dev
@@ -519,6 +585,12 @@ class Stylization():
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for b0 in range(0, a.B, TENSOR_BATCH_MAX):
             nb = min(TENSOR_BATCH_MAX, a.B - b0)
+            if m is not None:
+                mp = md.data_ptr() if m.images == 1 else md[b0].data_ptr()
+                self._chk(self._lib.rrv_transfer_image_mask_device(
+                    self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb,
+                    C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
+                continue
             if w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
                 wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
                 self._chk(self._lib.rrv_transfer_image_blend_device(
