@@ -227,7 +227,7 @@ struct rrv_ctx {
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
     int pend_form = IN_U8_HWC, pend_space = SP_PIXEL;      // form of the pending frames (rrv_add_image_device keeps a frame as it arrived; conv_first_k<IN> reads it)
-    // Weights of the blended frame entries (blend_frames_on_slot), per slot 0 / 1: [64][RRV_MAX_STYLES] floats in HBM, which blend_states_dev_k
+    // Weights of the blended frame entries (run_xfer, Model::BLEND), per slot 0 / 1: [64][RRV_MAX_STYLES] floats in HBM, which blend_states_dev_k
     // reads, and for host weights a page-locked ring of BLEND_W_RING such blocks: a call fills the next block and copies it on the slot's
     // stream; a block is reused BLEND_W_RING calls later, after its copy's event (long past: no host wait in a running pipeline)
     static constexpr int BLEND_W_RING = 4, BLEND_W_FLOATS = 64 * RRV_MAX_STYLES;
@@ -1033,6 +1033,42 @@ inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 inline void* out_at(void* p, size_t elems, OutFmt f) { return (char*)p + elems * out_elem(f); }
 inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
 
+int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
+
+// One transfer as an entry states it.  The model is named, never inferred from which pointer is set; everything the entries derive
+// from the request (kernel geometry, bytes and elements per frame, the pad and crop window) is computed here and nowhere else.
+//   GLOBAL: Stylization(use_Global=True), one shared state set          FRAME: use_Global=False, statistics per frame
+//   BLEND:  frame b with sum_s wts[b][s] x the state of style s         MASK:  the styles blended per pixel by float32 masks
+enum class Model { GLOBAL, FRAME, BLEND, MASK };
+constexpr bool PLAIN = false, PADDED = true;      // Xfer::pad
+struct Xfer {
+    Model model;
+    int B, H, W;                    // as the caller passed them
+    bool pad;                       // the _frames / RRV_TF_PAD_CROP geometry: UNPADDED frames in and out, the reference driver's reflect padding
+                                    // (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
+    OutFmt fmt;
+    int ns = 0;                     // BLEND, MASK: styles 0..ns-1
+    const float* wts = nullptr;     // BLEND: [B][ns]; in host memory unless w_dev
+    const float* mask = nullptr;    // MASK: [mask_images][ns][H][W], mask_images = B, or 1 = one mask for every frame
+    int mask_images = 0;
+    bool w_dev = false;             // BLEND: wts is in HBM, written by work the slot's stream is ordered behind
+
+    int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
+    int KW() const { return pad ? padded_size(W) : W; }
+    size_t in_bytes(rrv_handle h) const { return (size_t)H * W * 3 * in_elem(h->in_form); }                        // per frame
+    size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
+    size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
+    PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
+};
+
+// What a launch sequence with per-image state sets moves on the handle, put back when it ends: the stream, the current state set and
+// the per-image count.  src: what the sequence leaves in the slot's sets (-1: frame-mode statistics, -2: blends), so that the next
+// global entry re-activates its style.  (transfer_device's own scope puts back the stream only and leaves active_src alone.)
+struct SetScope {
+    rrv_handle h; int src;
+    ~SetScope() { h->stream = h->streams[0]; h->cur = &h->sets[0]; h->state_images = 0; h->active_src = src; }
+};
+
 // grow-only device buffer of at least n elements (h->d_u8, h->d_outf); empty after a failed allocation
 template <class T>
 int ensure_dev(rrv_handle h, T*& p, size_t& cap, size_t n) {
@@ -1433,7 +1469,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
     StyleState& S = h->styles[0];
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
-    struct Scope { rrv_handle h; ~Scope() { h->stream = h->streams[0]; h->cur = &h->sets[0]; h->state_images = 0; h->active_src = -1; } } scope{h};
+    SetScope scope{h, -1};
     h->active_src = -1;                                   // set 0 (slot 0) is overwritten: a later global entry re-activates its state
     h->stream = h->streams[slot];
     h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];
@@ -2380,100 +2416,179 @@ static int next_device_slot(rrv_handle h) {
     return slot;
 }
 
-static int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
-
-// Stylization(use_Global=False) for 1..64 frames on `slot` (0 or 1): launch sequences of up to MS_GROUP_MAX frames on its stream
-static int frame_mode_on_slot(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad) {
+// Every argument and state check of a transfer, once per API call, before anything is staged or launched.  host: the pipeline cuts
+// sub-batches itself, so any B >= 1 is served; the device and image entries take 1..64 frames.
+static int check_xfer(rrv_handle h, const Xfer& x, bool host = false) {
+    const bool blend = x.model == Model::BLEND, mask = x.model == Model::MASK;
+    if (x.B < 1 || (!host && x.B > 64)) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
+    if (x.pad && (x.H < 1 || x.W < 1)) return fail(h, RRV_E_ARG, "transfer: frames must be at least 1 x 1 pixels");
+    RCHK(check_frame(h, x.KH(), x.KW(), "transfer"));      // the geometry the kernels run, refused before any staging is sized for it
+    if ((blend || mask) && (x.ns < 1 || x.ns > RRV_MAX_STYLES)) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
+    if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
+    if (mask && !x.mask) return fail(h, RRV_E_ARG, "transfer: null mask");
+    if (mask && x.mask_images != 1 && x.mask_images != x.B) return fail(h, RRV_E_ARG, "transfer: mask_images must be 1 or B");
+    // A handle without weights has no state either.  Every entry reports the weights, except rrv_transfer_mask_batch, which has
+    // always answered RRV_E_STATE: kept as it is.
+    if (!h->finalized && !(mask && host)) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    if (x.model == Model::FRAME && !h->styles[0].prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
+    for (int s = 0; s < x.ns; ++s)
+        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "transfer: state not computed for every style");
+    if (x.model == Model::GLOBAL && h->active_src < 0) {      // what ensure_active would find nothing to activate for
+        bool any = false;
+        for (const StyleState& S : h->styles) any = any || S.computed;
+        if (!any) return fail(h, RRV_E_STATE, "state not computed: call compute() (or set_state) before transfer()");
+    }
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
-    RCHK(check_frame(h, KH, KW, "transfer"));
-    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-    if (!h->styles[0].prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
-    // a global entry's work in flight reads state set 0, which slot 0's sets include
-    if (h->active_src != -1) RCHK(sync_all(h));
-    const size_t fb = (size_t)H * W * 3, fo = pad ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
-    const PadCrop pc{H, W, 64, 64};
-    if (h->caller_sync) {
+    return RRV_OK;
+}
+
+// n <= BLEND_W_FLOATS host weights -> the slot's device block (allocated on first use), by a copy on the slot's stream from the next block of its page-locked ring
+static int stage_blend_weights(rrv_handle h, int slot, const float* wts, size_t n, const float** d_w) {
+    rrv_ctx::BlendW& bw = h->blend_w[slot];
+    if (!bw.dev) RCHK(dalloc(h, &bw.dev, rrv_ctx::BLEND_W_FLOATS, false));
+    if (!bw.pin) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, sizeof(float) * rrv_ctx::BLEND_W_RING * rrv_ctx::BLEND_W_FLOATS, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, RRV_E_NOMEM, "blend weights: out of page-locked host memory");
+        }
+        bw.pin = (float*)p;
+    }
+    for (hipEvent_t& e : bw.ev)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int g = (int)(bw.gen++ % rrv_ctx::BLEND_W_RING);
+    if (bw.used[g]) HIPCHK(hipEventSynchronize(bw.ev[g]));
+    float* const blk = bw.pin + (size_t)g * rrv_ctx::BLEND_W_FLOATS;
+    memcpy(blk, wts, n * sizeof(float));
+    HIPCHK(hipMemcpyAsync(bw.dev, blk, n * sizeof(float), hipMemcpyHostToDevice, h->streams[slot]));
+    HIPCHK(hipEventRecord(bw.ev[g], h->streams[slot]));
+    bw.used[g] = true;
+    *d_w = bw.dev;
+    return RRV_OK;
+}
+
+
+// Runs a checked request from d_in to d_out on `slot` (the grouped models: 0 or 1, the slots that own sixteen state sets each).
+// GLOBAL is one launch sequence for all B frames; the others walk launch sequences of up to MS_GROUP_MAX frames:
+//   FRAME  frame_mode_device: every frame with its own statistics, written to the slot's state sets
+//   BLEND  the group's state sets := sum_s w[b][s] x state_s (blend_states_dev_k), their KernelFilters folded, then encoder AND decoder
+//          with per-image state (transfer_device, state_images).  With a fixed kernel mode a frame's arithmetic is that of
+//          rrv_transfer_blend on the frame alone, bit for bit.
+//   MASK   mask_mode_device; it touches no state set
+static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const Xfer& x) {
+    // What is in flight and reads the state sets this request rewrites drains first: a global entry's work reads state set 0, which
+    // slot 0's sets include (frame-mode and blended launches write a slot's sets on that slot's own stream, in order)
+    switch (x.model) {
+    case Model::GLOBAL: RCHK(ensure_active(h)); break;
+    case Model::FRAME:  if (h->active_src != -1) RCHK(sync_all(h)); break;
+    case Model::BLEND:  if (h->active_src >= 0) RCHK(sync_all(h)); break;
+    case Model::MASK:   break;
+    }
+    // Against the caller's stream: what it holds so far (the frames, device-resident weights, the masks) precedes the first launch,
+    // and it waits for the last one.  transfer_device brackets its own launches, which is all the global model needs.
+    const bool bracket = h->caller_sync && x.model != Model::GLOBAL;
+    if (bracket) {
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
         HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
     }
-    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
-        const int nb = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
-        RCHK(frame_mode_device(h, slot, d_in + (size_t)b0 * fb * in_elem(h->in_form), nb, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
+    const float* d_w = x.wts;
+    if (x.model == Model::BLEND && !x.w_dev) RCHK(stage_blend_weights(h, slot, x.wts, (size_t)x.B * x.ns, &d_w));
+    const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
+    const size_t fb = x.in_bytes(h), fo = x.out_elems();
+    const PadCrop crop = x.pad_crop();
+    const PadCrop* const pc = x.pad ? &crop : nullptr;
+    for (int b0 = 0; b0 < x.B; b0 += G) {
+        const int cnt = x.B - b0 < G ? x.B - b0 : G;
+        const uint8_t* const in = (const uint8_t*)d_in + (size_t)b0 * fb;
+        void* const out = out_at(d_out, (size_t)b0 * fo, x.fmt);
+        switch (x.model) {
+        case Model::GLOBAL:
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, x.fmt, nullptr, pc));
+            break;
+        case Model::FRAME:
+            RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, x.fmt, pc));
+            break;
+        case Model::MASK:
+            RCHK(mask_mode_device(h, slot, in, cnt, KH, KW, x.mask + (x.mask_images == 1 ? 0 : (size_t)b0 * x.mask_floats()), x.ns, x.mask_images == 1, out,
+                                  x.fmt, pc));
+            break;
+        case Model::BLEND: {
+            SetScope scope{h, -2};
+            h->stream = h->streams[slot];
+            h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
+            BlendDevP bp{};
+            bp.n = x.ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS; bp.w = d_w + (size_t)b0 * x.ns;
+            for (int s = 0; s < x.ns; ++s) bp.st[s] = h->styles[s].blob;
+            hipLaunchKernelGGL(blend_states_dev_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
+            HIPCHK(hipGetLastError());
+            h->active_src = -2;
+            for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
+            h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, x.fmt, nullptr, pc));
+            h->set_images[slot] = cnt;
+            break;
+        }
+        }
     }
-    if (h->caller_sync) {
+    if (bracket) {
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
     }
     return RRV_OK;
 }
 
-// pad: [B][H][W][3] UNPADDED uint8 frames -> [B][H][W][3] float32 stylized frames: the reference driver's reflect padding
-// (64 px + up to a multiple of 64) and crop (:61-83, :167) happen inside the first and last kernel
-// frame: the frame-mode model (use_Global=False, frame_mode_on_slot)
-static int transfer_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad, bool frame = false) {
-    if (frame) return frame_mode_on_slot(h, slot, (const uint8_t*)d_in, B, H, W, d_out, fmt, pad);
-    RCHK(ensure_active(h));
-    if (!pad) return transfer_device(h, slot, (const uint8_t*)d_in, B, H, W, d_out, fmt);
-    const PadCrop pc{H, W, 64, 64};
-    return transfer_device(h, slot, (const uint8_t*)d_in, B, padded_size(H), padded_size(W), d_out, fmt, nullptr, &pc);
-}
-
-// the frame-mode device entries alternate over slots 0 and 1 only: each slot's launches use its own sixteen state sets
+// the grouped models alternate over slots 0 and 1 only: each slot's launches use its own sixteen state sets
 static int next_frame_slot(rrv_handle h) { return next_device_slot(h) & 1; }
+static int next_slot(rrv_handle h, const Xfer& x) { return x.model == Model::GLOBAL ? next_device_slot(h) : next_frame_slot(h); }
 
-// the device entries (float32 and _u8 forms): pad = the _frames geometry, frame = the frame-mode model
-static int device_entry(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad, bool frame) {
-    if (!h || !d_in || !d_out || (pad && (H < 1 || W < 1))) return RRV_E_ARG;
+// the device entries (float32 and _u8 forms): [B][H][W][3] uint8 in HBM -> stylized frames in HBM, asynchronous on the slot's stream
+static int device_entry(rrv_handle h, const void* d_in, void* d_out, const Xfer& x) {
+    if (!h || !d_in || !d_out) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
-    return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
+    RCHK(check_xfer(h, x));
+    return run_xfer(h, next_slot(h, x), d_in, d_out, x);
 }
 
 int rrv_transfer_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, false, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, B, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_batch_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, false, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, B, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, true, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, B, H, W, PADDED, OUT_F32});
 }
 int rrv_transfer_frames_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, true, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, B, H, W, PADDED, OUT_U8});
 }
 
 int rrv_transfer_device(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
-    return device_entry(h, d_in, 1, H, W, d_out, OUT_F32, false, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, 1, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_device_u8(rrv_handle h, const void* d_in, int H, int W, void* d_out) {
-    return device_entry(h, d_in, 1, H, W, d_out, OUT_U8, false, false);
+    return device_entry(h, d_in, d_out, Xfer{Model::GLOBAL, 1, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_frame_mode_batch_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, false, true);
+    return device_entry(h, d_in, d_out, Xfer{Model::FRAME, B, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_frame_mode_batch_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, false, true);
+    return device_entry(h, d_in, d_out, Xfer{Model::FRAME, B, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_frame_mode_frames_device(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_F32, true, true);
+    return device_entry(h, d_in, d_out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_F32});
 }
 int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int B, int H, int W, void* d_out) {
-    return device_entry(h, d_in, B, H, W, d_out, OUT_U8, true, true);
+    return device_entry(h, d_in, d_out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_U8});
 }
 
 // rrv_transfer_image_device: the device entries above with the content frames read as `in` (conv_first_k<IN>) and the
-// stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only
-static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad,
-                                const float* wts, int ns, bool w_dev);
-static int mask_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, const float* d_mask, int ns, int mask_images, void* d_out,
-                               OutFmt fmt, bool pad);
-// d_mask != nullptr: rrv_transfer_image_mask_device, the styles blended per pixel by [mask_images][ns][H][W] float32 masks in HBM
-// wts != nullptr: rrv_transfer_image_blend_device, one weight vector per image ([B][ns]; in HBM with RRV_TF_WEIGHTS_DEVICE)
-static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
-                       int flags, void* hip_stream, const float* wts, int ns, const float* d_mask = nullptr, int mask_images = 0) {
+// stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only.  x: the model, B, H, W and what
+// the model blends with; the flags and `out` supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME)
+static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
+    if (!h) return RRV_E_ARG;
     auto bad = [](const rrv_image_desc& d) {
         return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
                d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
@@ -2481,17 +2596,18 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B,
     if (bad(in) || bad(out)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
     if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
     if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
-    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (wts ? RRV_TF_WEIGHTS_DEVICE : 0))) return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
+        return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
     if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
-    const bool pad = flags & RRV_TF_PAD_CROP, frame = flags & RRV_TF_FRAME_MODE;
-    if (pad && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer_image: frames must be at least 1 x 1 pixels");
-    if (wts || d_mask) {
-        if (frame) return fail(h, RRV_E_ARG, "transfer_image: the frame-mode model has no blended state (style weights need the global model)");
-        if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-        if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer_image: n_styles must be in 1..RRV_MAX_STYLES");
-        if (d_mask && mask_images != 1 && mask_images != B) return fail(h, RRV_E_ARG, "transfer_image: mask_images must be 1 or B");
+    if (flags & RRV_TF_FRAME_MODE) {
+        if (x.model != Model::GLOBAL) return fail(h, RRV_E_ARG, "transfer_image: the frame-mode model has no blended state (style weights need the global model)");
+        x.model = Model::FRAME;
     }
+    x.pad = flags & RRV_TF_PAD_CROP;
+    x.fmt = OutFmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
+    x.w_dev = flags & RRV_TF_WEIGHTS_DEVICE;
     HIPCHK(hipSetDevice(h->dev));
+    RCHK(check_xfer(h, x));
     struct Scope {
         rrv_handle h; hipStream_t cs; bool sync;
         ~Scope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; h->caller_stream = cs; h->caller_sync = sync; }
@@ -2499,27 +2615,21 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, int B,
     h->in_form = (in.dtype == RRV_DT_F32 ? 2 : 0) | (in.layout == RRV_LAY_CHW_RGB ? 1 : 0);
     h->in_space = in.space;
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
-    const OutFmt fmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
-    if (wts) return blend_frames_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_out, fmt, pad, wts, ns, (flags & RRV_TF_WEIGHTS_DEVICE) != 0);
-    if (d_mask) return mask_frames_on_slot(h, next_frame_slot(h), d_in, B, H, W, d_mask, ns, mask_images, d_out, fmt, pad);
-    return transfer_on_slot(h, frame ? next_frame_slot(h) : next_device_slot(h), d_in, B, H, W, d_out, fmt, pad, frame);
+    return run_xfer(h, next_slot(h, x), d_in, d_out, x);
 }
 int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
                               int flags, void* hip_stream) {
-    if (!h) return RRV_E_ARG;
-    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, nullptr, 0);
+    return image_entry(h, d_in, in, d_out, out, flags, hip_stream, Xfer{Model::GLOBAL, B, H, W});
 }
+// one weight vector per image ([B][ns]; in HBM with RRV_TF_WEIGHTS_DEVICE)
 int rrv_transfer_image_blend_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, const float* style_weight, int n_styles,
                                     void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
-    if (!h || !style_weight) return RRV_E_ARG;
-    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, style_weight, n_styles);
+    return image_entry(h, d_in, in, d_out, out, flags, hip_stream, Xfer{Model::BLEND, B, H, W, PLAIN, OUT_F32, n_styles, style_weight});
 }
-
+// the styles blended per pixel by [mask_images][ns][H][W] float32 masks in HBM
 int rrv_transfer_image_mask_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, const float* d_mask, int n_styles,
                                    int mask_images, void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
-    if (!h) return RRV_E_ARG;
-    if (!d_mask) return fail(h, RRV_E_ARG, "transfer_image: null mask");
-    return image_entry(h, d_in, in, B, H, W, d_out, out, flags, hip_stream, nullptr, n_styles, d_mask, mask_images);
+    return image_entry(h, d_in, in, d_out, out, flags, hip_stream, Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, n_styles, /* wts */ nullptr, d_mask, mask_images});
 }
 
 // the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
@@ -2574,111 +2684,6 @@ int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const f
 }
 int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, uint8_t* out) {
     return blend_host(h, frame, H, W, wts, ns, out, OUT_U8);
-}
-
-// n <= BLEND_W_FLOATS host weights -> the slot's device block, by a copy on the slot's stream from the next block of its page-locked ring
-static int stage_blend_weights(rrv_handle h, int slot, const float* wts, size_t n, const float** d_w) {
-    rrv_ctx::BlendW& bw = h->blend_w[slot];
-    if (!bw.pin) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(float) * rrv_ctx::BLEND_W_RING * rrv_ctx::BLEND_W_FLOATS, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, RRV_E_NOMEM, "blend weights: out of page-locked host memory");
-        }
-        bw.pin = (float*)p;
-    }
-    for (hipEvent_t& e : bw.ev)
-        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const int g = (int)(bw.gen++ % rrv_ctx::BLEND_W_RING);
-    if (bw.used[g]) HIPCHK(hipEventSynchronize(bw.ev[g]));
-    float* const blk = bw.pin + (size_t)g * rrv_ctx::BLEND_W_FLOATS;
-    memcpy(blk, wts, n * sizeof(float));
-    HIPCHK(hipMemcpyAsync(bw.dev, blk, n * sizeof(float), hipMemcpyHostToDevice, h->streams[slot]));
-    HIPCHK(hipEventRecord(bw.ev[g], h->streams[slot]));
-    bw.used[g] = true;
-    *d_w = bw.dev;
-    return RRV_OK;
-}
-
-// Multi-style interpolation from FRAMES for 1..64 frames on `slot` (0 or 1: the slots that own sixteen state sets each), every frame
-// with its own weight vector wts[b][0..ns-1] (w_dev: in HBM, written by work the slot's stream is ordered behind; else host memory,
-// staged).  Launch sequences of up to MS_GROUP_MAX frames: the group's state sets := sum_s w[b][s] x state_s (blend_states_dev_k), their
-// KernelFilters folded, then encoder AND decoder from the frames with per-image state (transfer_device, state_images).  With a
-// fixed kernel mode a frame's arithmetic is that of rrv_transfer_blend on the frame alone, bit for bit.
-static int blend_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, void* d_out, OutFmt fmt, bool pad,
-                                const float* wts, int ns, bool w_dev) {
-    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
-    RCHK(check_frame(h, KH, KW, "transfer"));
-    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-    if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
-    for (int s = 0; s < ns; ++s)
-        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "blend: state not computed for every style");
-    // a single-style entry's work in flight reads state set 0, which slot 0's sets include (blended and frame-mode launches
-    // write a slot's sets on that slot's own stream, in order)
-    if (h->active_src >= 0) RCHK(sync_all(h));
-    rrv_ctx::BlendW& bw = h->blend_w[slot];
-    if (!w_dev && !bw.dev) RCHK(dalloc(h, &bw.dev, rrv_ctx::BLEND_W_FLOATS, false));
-    if (h->caller_sync) {      // the weights and the frames the caller's stream produces precede the blends
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
-        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
-    }
-    const float* d_w = wts;
-    if (!w_dev) RCHK(stage_blend_weights(h, slot, wts, (size_t)B * ns, &d_w));
-    struct Restore { rrv_handle h; ~Restore() { h->cur = &h->sets[0]; h->state_images = 0; h->stream = h->streams[0]; h->active_src = -2; } } restore{h};
-    const size_t fb = (size_t)H * W * 3 * in_elem(h->in_form), fo = pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
-    const PadCrop pc{H, W, 64, 64};
-    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
-        const int cnt = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
-        h->stream = h->streams[slot];
-        h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
-        BlendDevP bp{};
-        bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS; bp.w = d_w + (size_t)b0 * ns;
-        for (int s = 0; s < ns; ++s) bp.st[s] = h->styles[s].blob;
-        hipLaunchKernelGGL(blend_states_dev_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
-        HIPCHK(hipGetLastError());
-        h->active_src = -2;
-        for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
-        h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
-        const int rc = transfer_device(h, slot, (const uint8_t*)d_in + (size_t)b0 * fb, cnt, KH, KW, out_at(d_out, (size_t)b0 * fo, fmt), fmt, nullptr,
-                                       pad ? &pc : nullptr);
-        h->state_images = 0;
-        RCHK(rc);
-        h->set_images[slot] = cnt;
-    }
-    return RRV_OK;
-}
-
-// Per-pixel multi-style blending for 1..64 frames on `slot` (0 or 1): launch sequences of up to MS_GROUP_MAX frames (mask_mode_device).
-// d_mask: [mask_images][ns][H][W] float32 in HBM, written by work the slot's stream is ordered behind; mask_images = B, or 1 = one mask
-// for every frame.  No state set is touched, so nothing in flight has to drain first.
-static int mask_frames_on_slot(rrv_handle h, int slot, const void* d_in, int B, int H, int W, const float* d_mask, int ns, int mask_images, void* d_out,
-                               OutFmt fmt, bool pad) {
-    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    const int KH = pad ? padded_size(H) : H, KW = pad ? padded_size(W) : W;
-    RCHK(check_frame(h, KH, KW, "transfer"));
-    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-    if (ns < 1 || ns > RRV_MAX_STYLES) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
-    if (mask_images != 1 && mask_images != B) return fail(h, RRV_E_ARG, "transfer: mask_images must be 1 or B");
-    for (int s = 0; s < ns; ++s)
-        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "masked transfer: state not computed for every style");
-    if (h->caller_sync) {      // the mask and the frames the caller's stream produces precede the launches
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
-        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
-    }
-    const size_t fb = (size_t)H * W * 3 * in_elem(h->in_form), fo = pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;
-    const size_t mf = (size_t)ns * H * W;
-    const PadCrop pc{H, W, 64, 64};
-    for (int b0 = 0; b0 < B; b0 += rrv_ctx::MS_GROUP_MAX) {
-        const int cnt = B - b0 < rrv_ctx::MS_GROUP_MAX ? B - b0 : rrv_ctx::MS_GROUP_MAX;
-        RCHK(mask_mode_device(h, slot, (const uint8_t*)d_in + (size_t)b0 * fb, cnt, KH, KW, d_mask + (mask_images == 1 ? 0 : (size_t)b0 * mf), ns, mask_images == 1,
-                              out_at(d_out, (size_t)b0 * fo, fmt), fmt, pad ? &pc : nullptr));
-    }
-    if (h->caller_sync) {
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
-        HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
-    }
-    return RRV_OK;
 }
 
 // B frames in sub-batches of up to 8 through four staging sets.  Three engines run concurrently: the H2D copy of
@@ -2794,26 +2799,27 @@ static int claim_staging(rrv_handle h) {
     h->next_slot = 0;
     return RRV_OK;
 }
-// frame_mode: the frame-mode model (sub-batches of at most MS_GROUP_MAX frames, one launch sequence each); fmt: float32 or uint8 `out`
-// wts != nullptr: the blended model, frame b with the weights wts[b][0..ns-1] (blend_frames_on_slot per sub-batch)
-static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int W, void* out, OutFmt fmt, bool pad_on_device = false, bool frame_mode = false,
-                         const float* wts = nullptr, int ns = 0, const float* mask = nullptr, int mask_images = 0) {
-    if (!h || !frames || !out || B < 1) return RRV_E_ARG;
+// The host entries: x.B frames from `frames` to `out` (float32 or uint8 by x.fmt), any B >= 1.  The grouped models run sub-batches of at
+// most MS_GROUP_MAX frames, one launch sequence each; the blended one takes the sub-batch's rows of x.wts, the masked one the set's
+// staged mask block.
+static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const Xfer& x) {
+    if (!h || !frames || !out) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
-    // the geometry the kernels run (padded on the device for rrv_transfer_frames), refused before any staging is sized for it
-    if (pad_on_device && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, "transfer: empty frame");
-    const int KH = pad_on_device ? padded_size(H) : H, KW = pad_on_device ? padded_size(W) : W;
-    RCHK(check_frame(h, KH, KW, "transfer"));
-    const size_t fb = (size_t)H * W * 3;                                   // input bytes per frame
-    const size_t fo = pad_on_device ? fb : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;   // output elements per frame (any input size: 8*(H/8) x 8*(W/8))
-    const size_t fob = fo * out_elem(fmt);                                  // ... and their bytes
+    RCHK(check_xfer(h, x, true));
+    const int B = x.B;
+    const float* const mask = x.mask;
+    const int mask_images = x.mask_images;
+    const size_t fb = x.in_bytes(h);                                        // input bytes per frame
+    const size_t fob = x.out_elems() * out_elem(x.fmt);                     // output bytes per frame
     char* const outc = (char*)out;
-    const int sub = frame_mode || wts || mask ? std::min(host_sub(B, KH, KW), (int)rrv_ctx::MS_GROUP_MAX) : host_sub(B, KH, KW);
-    const size_t mfl = (size_t)ns * H * W;      // floats of one image's masks
+    const int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
+    const size_t mfl = x.mask_floats();
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out) -> int {      // sub-batch k's kernels
-        if (mask) return mask_frames_on_slot(h, slot, d_in, nb, H, W, h->hstage[k % HOST_SETS].mask, ns, mask_images == 1 ? 1 : nb, d_out, fmt, pad_on_device);
-        if (wts) return blend_frames_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, wts + (size_t)k * sub * ns, ns, false);
-        return transfer_on_slot(h, slot, d_in, nb, H, W, d_out, fmt, pad_on_device, frame_mode);
+        Xfer part = x;
+        part.B = nb;
+        if (x.wts) part.wts = x.wts + (size_t)k * sub * x.ns;
+        if (mask) { part.mask = h->hstage[k % HOST_SETS].mask; part.mask_images = mask_images == 1 ? 1 : nb; }
+        return run_xfer(h, slot, d_in, d_out, part);
     };
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
     // the masks are staged like the frames: a sub-batch's part goes through the set's page-locked block (unless the caller's array is
@@ -2914,64 +2920,52 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, int B, int H, int 
 }
 
 int rrv_transfer(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
-    return host_pipeline(h, frame, 1, H, W, out, OUT_F32);
+    return host_pipeline(h, frame, out, Xfer{Model::GLOBAL, 1, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
-    return host_pipeline(h, frame, 1, H, W, out, OUT_U8);
+    return host_pipeline(h, frame, out, Xfer{Model::GLOBAL, 1, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_F32);
+    return host_pipeline(h, frames, out, Xfer{Model::GLOBAL, B, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_U8);
+    return host_pipeline(h, frames, out, Xfer{Model::GLOBAL, B, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_F32, true);
+    return host_pipeline(h, frames, out, Xfer{Model::GLOBAL, B, H, W, PADDED, OUT_F32});
 }
 int rrv_transfer_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_U8, true);
+    return host_pipeline(h, frames, out, Xfer{Model::GLOBAL, B, H, W, PADDED, OUT_U8});
 }
 
-static int blend_batch_host(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, void* out, OutFmt fmt) {
-    if (!h || !frames || !out || !wts || B < 1 || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
-    return host_pipeline(h, frames, B, H, W, out, fmt, pad_crop != 0, false, wts, ns);
-}
 int rrv_transfer_blend_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, float* out) {
-    return blend_batch_host(h, frames, B, H, W, wts, ns, pad_crop, out, OUT_F32);
+    return host_pipeline(h, frames, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, OUT_F32, ns, wts});
 }
 int rrv_transfer_blend_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, uint8_t* out) {
-    return blend_batch_host(h, frames, B, H, W, wts, ns, pad_crop, out, OUT_U8);
+    return host_pipeline(h, frames, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, OUT_U8, ns, wts});
 }
 
-static int mask_batch_host(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, void* out, OutFmt fmt) {
-    if (!h) return RRV_E_ARG;
-    if (!frames || !out || !mask || B < 1 || ns < 1 || ns > RRV_MAX_STYLES || (mask_images != 1 && mask_images != B))
-        return fail(h, RRV_E_ARG, "transfer_mask_batch: null buffer, n_styles not in 1..RRV_MAX_STYLES or mask_images not 1 or B");
-    for (int s = 0; s < ns; ++s)
-        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "masked transfer: state not computed for every style");
-    return host_pipeline(h, frames, B, H, W, out, fmt, pad_crop != 0, false, nullptr, ns, mask, mask_images);
-}
 int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, float* out) {
-    return mask_batch_host(h, frames, B, H, W, mask, ns, mask_images, pad_crop, out, OUT_F32);
+    return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, OUT_F32, ns, /* wts */ nullptr, mask, mask_images});
 }
 int rrv_transfer_mask_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop, uint8_t* out) {
-    return mask_batch_host(h, frames, B, H, W, mask, ns, mask_images, pad_crop, out, OUT_U8);
+    return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, OUT_U8, ns, /* wts */ nullptr, mask, mask_images});
 }
 
 int rrv_transfer_frame_mode_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_F32, false, true);
+    return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PLAIN, OUT_F32});
 }
 int rrv_transfer_frame_mode_batch_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_U8, false, true);
+    return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_F32, true, true);
+    return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_F32});
 }
 int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
-    return host_pipeline(h, frames, B, H, W, out, OUT_U8, true, true);
+    return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_U8});
 }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----
@@ -3294,7 +3288,7 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         RCHK(stage_reserve(h, i, 0, (size_t)G * npx, false));
         RCHK(stage_reserve(h, i, 0, out_pin ? 0 : (size_t)G * npx, true));
     }
-    struct Restore { rrv_handle h; ~Restore() { h->cur = &h->sets[0]; h->state_images = 0; h->stream = h->streams[0]; h->active_src = -2; } } restore{h};
+    SetScope scope{h, -2};
     auto drain = [&](int k) -> int {
         auto& st = h->hstage[k % nslots];
         HIPCHK(hipEventSynchronize(st.out_done));

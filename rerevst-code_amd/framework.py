@@ -476,21 +476,25 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _blend_batch(self, a, out, u8, style_weights, pad_crop):
-        """transfer_batch / transfer_frames with one style weight vector per frame (rrv_transfer_blend_batch)"""
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop):
+        """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames, the checked masks or
+        weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one)"""
+        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
+            a = np.ascontiguousarray(frames)
+        else:
+            a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
-        w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
-        fn = self._entry("rrv_transfer_blend_batch", u8)
-        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S,
-                     1 if pad_crop else 0, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def _mask_batch(self, a, out, u8, m, pad_crop):
-        """transfer_batch / transfer_frames with per-pixel style masks (rrv_transfer_mask_batch)"""
-        B, H, W, _ = a.shape
-        fn = self._entry("rrv_transfer_mask_batch", u8)
-        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images,
-                     1 if pad_crop else 0, out.ctypes.data_as(C.c_void_p)))
+        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
+        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
+        head = (self._h, a.ctypes.data_as(C.c_void_p), B, H, W)
+        if m is not None:
+            name, args = "rrv_transfer_mask_batch", (m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop))
+        elif style_weights is not None:
+            w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
+            name, args = "rrv_transfer_blend_batch", (w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, int(pad_crop))
+        else:
+            name, args = ("rrv_transfer" if self.use_Global else "rrv_transfer_frame_mode") + ("_frames" if pad_crop else "_batch"), ()
+        self._chk(self._entry(name, u8)(*head, *args, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
@@ -503,20 +507,7 @@ class Stylization():
         style_masks: the styles blended PER PIXEL instead: a float32 ndarray [B][S][H][W] (or [S][H][W]: every frame) at the
         frames' resolution; every saved quantity becomes sum_s m_s(p) q_s at each decoder pixel p, m the mean of the mask
         over the input pixels p covers (rrv_transfer_mask_batch).  Not normalised; mutually exclusive with style_weights."""
-        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
-            a = np.ascontiguousarray(frames)
-        else:
-            a = np.stack([_u8_image(f, "frame") for f in frames])
-        B, H, W, _ = a.shape
-        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        out, u8 = _output((B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
-        if m is not None:
-            return self._mask_batch(a, out, u8, m, False)
-        if style_weights is not None:
-            return self._blend_batch(a, out, u8, style_weights, False)
-        fn = self._entry("rrv_transfer_batch" if self.use_Global else "rrv_transfer_frame_mode_batch", u8)
-        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
@@ -527,20 +518,7 @@ class Stylization():
         style_weights: [B][S] (or [S]) blend weights per frame, as in transfer_batch.
         style_masks: [B][S][H][W] (or [S][H][W]) per-pixel blend weights for the UNPADDED frames, as in transfer_batch; the
         mask is reflect-padded on the device as the frame is."""
-        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
-            a = np.ascontiguousarray(frames)
-        else:
-            a = np.stack([_u8_image(f, "frame") for f in frames])
-        B, H, W, _ = a.shape
-        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        out, u8 = _output((B, H, W, 3), dtype, out)
-        if m is not None:
-            return self._mask_batch(a, out, u8, m, True)
-        if style_weights is not None:
-            return self._blend_batch(a, out, u8, style_weights, True)
-        fn = self._entry("rrv_transfer_frames" if self.use_Global else "rrv_transfer_frame_mode_frames", u8)
-        self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
