@@ -349,6 +349,49 @@ int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int 
     rrv_transfer_mask_batch_u8(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
                                const float* mask, int n_styles, int mask_images, int pad_crop, uint8_t* out_bgr);
 
+/* 8-bit YUV 4:2:0 output for video encoders (ffmpeg over a pipe, VCN / AMF, libx264, libaom): the colour transform and the 2 x 2
+ * chroma subsampling run in the last kernel's store, 1.5 bytes per pixel leave the GPU and the host touches no pixel.
+ * Arithmetic.  R, G, B are the float32 PIXEL values of the stylized pixel (what the float32 entry delivers, before any rounding) and
+ * m[3][4] a conversion matrix: rows Y, Cb, Cr; columns the coefficients of R, G, B and an offset.
+ *   c_k = ((m[k][0]*R + m[k][1]*G) + m[k][2]*B) + m[k][3]      every product and sum rounded to float32, in this order, no fused multiply-add
+ *   Y byte  = rint(min(max(c_0, 0), 255)), half to even as the _u8 forms round; one per output pixel
+ *   chroma  planes of CH = (OH+1)/2 rows and CW = (OW+1)/2 columns for the OH x OW frame the entry delivers.  Sample (i, j) covers output
+ *           pixels (2i..2i+1, 2j..2j+1): ((tl + tr) + (bl + br)) * 0.25f of the unrounded, unclamped c_1 (then c_2) in float32 in that
+ *           order, then rint(min(max(., 0), 255)).  A pixel of the block outside the frame (the last row / column of an odd OH / OW,
+ *           so only in the pad / crop geometry) takes the value of its nearest pixel of the block inside; the padding is never
+ *           read.  The mean sites the chroma at the block centre: Y4M's C420jpeg.
+ * So a YUV entry's bytes are this arithmetic applied to its float32 twin's output for the same frames and frames per call, bit for bit.
+ * Frame layout, all uint8, frame_bytes = OH*OW + 2*CH*CW, frame b of a call at b * frame_bytes with nothing in between:
+ *   RRV_LAY_I420  [Y: OH*OW][Cb: CH*CW][Cr: CH*CW]                RRV_LAY_NV12  [Y: OH*OW][CbCr interleaved: CH*CW*2]
+ * rrv_yuv_matrix fills m for a standard (Kr, Kb = 0.299, 0.114 for BT.601; 0.2126, 0.0722 for BT.709; Kg = 1 - Kr - Kb) and range — full:
+ * Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited: Y' = 16 + (219/255) Y and the
+ * chroma differences times 224/255 — each coefficient evaluated in double and rounded once to float32; it needs no handle and no GPU.
+ * rrv_set_yuv_matrix installs any twelve finite floats (else RRV_E_ARG); NULL restores the default, BT.601 limited range, which is what
+ * players assume for untagged yuv420p.  The matrix is handle state read when a call launches its last kernel; workspaces and saved state
+ * do not see it.
+ * Host entries, pipelined as their float twins (staging, page-locked buffers and rrv_set_host_io apply), any B >= 1, layout = RRV_LAY_I420
+ * or RRV_LAY_NV12 (anything else is RRV_E_ARG, the handle stays usable):
+ *   rrv_transfer_yuv              flags within RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE (else RRV_E_ARG): rrv_transfer_batch / _frames and
+ *                                 rrv_transfer_frame_mode_batch / _frames
+ *   rrv_transfer_blend_batch_yuv  rrv_transfer_blend_batch            rrv_transfer_mask_batch_yuv  rrv_transfer_mask_batch
+ * Device entries: rrv_transfer_image_device, _blend_device and _mask_device take out.layout = RRV_LAY_I420 / RRV_LAY_NV12 with
+ * out.dtype == RRV_DT_U8 and out.space == RRV_SP_PIXEL (anything else, and either layout for the input, is RRV_E_ARG); all flags and
+ * input forms as before.  rrv_get_preclamp_image works as after the float twin.
+ * Not offered: tickets (rrv_transfer_async), the cached-feature entries (rrv_transfer_features[_batch]), the one-frame
+ * rrv_transfer_blend[_device] and rrv_transfer_frame_mode, and YUV input. */
+enum {                         /* output-only values of rrv_image_desc.layout, after RRV_LAY_HWC_BGR = 0 and RRV_LAY_CHW_RGB = 1 */
+    RRV_LAY_I420 = 2,          /* planar Y, Cb, Cr (ffmpeg's yuv420p) */
+    RRV_LAY_NV12 = 3           /* planar Y, then interleaved Cb Cr */
+};
+enum { RRV_YUV_BT601 = 0, RRV_YUV_BT709 = 1 };      /* rrv_yuv_matrix's standards */
+int rrv_yuv_matrix(int standard, int full_range, float m[12]);
+int rrv_set_yuv_matrix(rrv_handle h, const float m[12]);
+int rrv_transfer_yuv(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W, int flags, int layout, uint8_t* out_yuv);
+int rrv_transfer_blend_batch_yuv(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                                 const float* style_weight, int n_styles, int pad_crop, int layout, uint8_t* out_yuv);
+int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
+                                const float* mask, int n_styles, int mask_images, int pad_crop, int layout, uint8_t* out_yuv);
+
 /* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
  * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;
  * float32 in PIXEL / UNIT / NORM), one image [Hs][Ws] / [H][W] per call.  The style is read in colour, a sampled frame through

@@ -23,6 +23,8 @@ class ImageDesc(C.Structure):
 
 DT_U8, DT_F32 = 0, 1
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
+LAY_I420, LAY_NV12 = 2, 3         # output only: 8-bit YUV 4:2:0, planar / semi-planar
+YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8
 DBG_STATE_SET, DBG_STYLE_PRED = 0, 1
@@ -79,6 +81,13 @@ SYMBOLS = {
     "rrv_transfer_image_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),      # d_mask: device address
     "rrv_transfer_mask_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_yuv_matrix": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rrv_set_yuv_matrix": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rrv_transfer_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_transfer_blend_batch_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                               C.c_void_p]),
+    "rrv_transfer_mask_batch_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p]),
     "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),

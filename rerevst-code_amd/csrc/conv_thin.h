@@ -12,6 +12,9 @@
 // Torch forms (rrv_transfer_image_device): conv_first_k<IN> also reads planar [B][3][H][W] RGB (torch's NCHW) and float32
 //   frames in one of three value spaces; conv_last_k<U8, CHW, SPACE> also writes planar RGB and the UNIT / NORM spaces.  The
 //   default instantiations are the uint8 BGR HWC forms above, unchanged.
+// YUV form (the rrv_*_yuv entries, out.layout = RRV_LAY_I420 / RRV_LAY_NV12): conv_last_k<true, false, SP_PIXEL, true> converts the
+//   float form's values with a 3 x 4 matrix and stores 8-bit 4:2:0, a Y byte per pixel and a Cb, Cr pair per 2 x 2 block.  Writes
+//   1.5 (+12) B/pixel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -249,6 +252,9 @@ struct LastP {
     // that starts at (crop_top, crop_left) of the padded frame.  out_H == 0: the whole padded frame.
     int out_H, out_W, crop_top, crop_left;
     int ty0, tx0;         // first tile row / column of the computed window (tiles_x, tiles_y count its tiles)
+    // the YUV 4:2:0 store form (conv_last_k<true, false, SP_PIXEL, true>): out_img is [B][OH*OW Y][chroma] uint8, frame b at b * (OH*OW + 2*CH*CW)
+    float yuv_m[12];      // rows Y, Cb, Cr; columns the coefficients of R, G, B and an offset (rrv_set_yuv_matrix), by value
+    int yuv_nv12;         // 0: I420, planes [Cb: CH*CW][Cr: CH*CW]; 1: NV12, one plane of CH*CW (Cb, Cr) pairs
 };
 
 // GEMM first, taps second.  out[y][x][rgb] = sum_tap sum_c w[tap][c][rgb] in[y+ky][x+kx][c] is evaluated as
@@ -266,7 +272,12 @@ struct LastP {
 // CHW: planar [B][3][OH][OW] RGB (torch's NCHW) instead of HWC BGR.  SPACE: SP_PIXEL (0..255, the forms above), SP_UNIT (the
 // clamped 0..1 value the PIXEL form multiplies by 255, so UNIT * 255.0f == PIXEL bit for bit) or SP_NORM (the pre-clamp network
 // output, the out_pre value); UNIT and NORM are float32 only.
-template <bool U8, bool CHW = false, int SPACE = SP_PIXEL>
+// YUV: 8-bit YUV 4:2:0 from the float32 PIXEL values (with U8, HWC, SP_PIXEL): c_k = ((m[k][0] R + m[k][1] G) + m[k][2] B) + m[k][3], every
+// product and sum rounded to float32 (no contraction); a Y byte per pixel, rint(clamp(c_0, 0, 255)); a Cb and a Cr byte per 2 x 2 block
+// of the OUTPUT frame, rint(clamp(((tl + tr) + (bl + br)) * 0.25f, 0, 255)) of the unclamped c_1 / c_2, a pixel of the block outside
+// the frame (odd OH / OW, last row / column) replaced by its nearest one inside.  The crop origin and the tile origins are even, so
+// a block's four pixels are lanes l, l^1, l^16, l^17 of one wave.
+template <bool U8, bool CHW = false, int SPACE = SP_PIXEL, bool YUV = false>
 __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     __shared__ __attribute__((aligned(16))) float s_g[27 * LAST_GP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -357,7 +368,63 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
         }
         __syncthreads();                      // G is free for the next tile
         const int y = y0 + row, xx = x0 + col;
-        if (y < p.H && xx < p.W) {
+        if constexpr (YUV) {
+            static_assert(U8 && !CHW && SPACE == SP_PIXEL, "the YUV form stores bytes of the PIXEL values");
+            // every lane computes its pixel's three components: the chroma sums cross lanes, so they run before the bounds branch,
+            // with all 64 lanes active (a lane outside the frame holds a value nobody uses)
+            float im[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f) * 255.f;      // the float form's value
+            const int cy = p.out_H ? y - p.crop_top : y, cx = p.out_H ? xx - p.crop_left : xx;
+            float yuv[3];
+            {
+#pragma clang fp contract(off)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float rg = p.yuv_m[4 * k] * im[0] + p.yuv_m[4 * k + 1] * im[1];
+                    const float rgb = rg + p.yuv_m[4 * k + 2] * im[2];
+                    yuv[k] = rgb + p.yuv_m[4 * k + 3];
+                }
+            }
+            // row sums first (lane ^ 1), then the two rows (lane ^ 16): ((tl + tr) + (bl + br)); a partner outside the frame is
+            // replaced by this lane's own value, a row outside by this row's sum (the same bits as replicating both pixels)
+            const bool right_in = cx + 1 < OW, below_in = cy + 1 < OH;
+            float blk[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float c = yuv[k + 1];
+                const float side = __shfl_xor(c, 1);
+                float rs;
+                {
+#pragma clang fp contract(off)
+                    rs = c + (right_in ? side : c);
+                }
+                const float other = __shfl_xor(rs, 16);
+                {
+#pragma clang fp contract(off)
+                    blk[k] = (rs + (below_in ? other : rs)) * 0.25f;
+                }
+            }
+            if (y < p.H && xx < p.W) {
+                typedef float f32x3 __attribute__((ext_vector_type(3)));
+                if (p.out_pre) *(f32x3*)(p.out_pre + (((size_t)b * p.H + y) * p.W + xx) * 3) = f32x3{o[0], o[1], o[2]};
+                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
+                    // byte stores: the 16 lanes of a tile row write 16 contiguous Y bytes, its 8 even lanes 8 (I420) or 16 (NV12)
+                    // chroma bytes; rows are OW bytes and frames OH*OW + 2*CH*CW, in general not dword aligned
+                    const int CH = (OH + 1) >> 1, CW = (OW + 1) >> 1;
+                    const size_t ysz = (size_t)OH * OW, csz = (size_t)CH * CW;
+                    uint8_t* const fr = (uint8_t*)p.out_img + (size_t)b * (ysz + 2 * csz);
+                    fr[(size_t)cy * OW + cx] = (uint8_t)__builtin_rintf(fminf(fmaxf(yuv[0], 0.f), 255.f));
+                    if (!((row | col) & 1)) {       // the block's top left pixel (cy, cx even: crop and tile origins are even)
+                        const uint8_t cb = (uint8_t)__builtin_rintf(fminf(fmaxf(blk[0], 0.f), 255.f));
+                        const uint8_t cr = (uint8_t)__builtin_rintf(fminf(fmaxf(blk[1], 0.f), 255.f));
+                        const size_t ci = (size_t)(cy >> 1) * CW + (cx >> 1);
+                        if (p.yuv_nv12) { fr[ysz + 2 * ci] = cb; fr[ysz + 2 * ci + 1] = cr; }
+                        else { fr[ysz + ci] = cb; fr[ysz + csz + ci] = cr; }
+                    }
+                }
+            }
+        } else if (y < p.H && xx < p.W) {
             typedef float f32x3 __attribute__((ext_vector_type(3)));
             if (p.out_pre) *(f32x3*)(p.out_pre + (((size_t)b * p.H + y) * p.W + xx) * 3) = f32x3{o[0], o[1], o[2]};
             float im[3];

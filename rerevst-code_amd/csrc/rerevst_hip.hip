@@ -258,6 +258,7 @@ struct rrv_ctx {
     bool f43_path = false;            // true inside transfer_device only: the preparation pass (prepare_style / add / compute, frame mode) always runs F(2x2,3x3)
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
+    float yuv_m[12];                  // rrv_set_yuv_matrix: rows Y, Cb, Cr x (R, G, B, offset) of the YUV store form; read at launch (run_last), BT.601 limited range at rrv_create
     int host_io = 0;                  // rrv_set_host_io: 0 = staged H2D / D2H copies, 1 = zero copy (kernels read / write page-locked host memory), 2 = input only, 3 = output only
     int n_cus = 256;
     int debug = 0;                    // rrv_set_debug / RRV_DEBUG: 1 = sync + check after every API call, 2 = after every kernel launch
@@ -1027,10 +1028,13 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
 // Format of a stylized frame: OUT_F32 = float32 BGR in 0..255 (tensor2numpy), OUT_U8 = the same values rounded half to even
 // on the GPU (conv_last_k<true>: cv2.imwrite's / driver.to_uint8's conversion) — the rrv_*_u8 entries.  Elements per frame are
 // the same; only their size differs.  rrv_transfer_image_device adds planar RGB (chw) and the UNIT / NORM spaces (float32 only).
-struct OutFmt { bool u8, chw; int space; };
+// yuv = RRV_LAY_I420 / RRV_LAY_NV12 (else 0): 8-bit YUV 4:2:0 of the PIXEL values (conv_last_k's YUV form, the rrv_*_yuv entries); a
+// frame is then Xfer::out_bytes() bytes, not elements x element size.
+struct OutFmt { bool u8, chw; int space; int yuv = 0; };
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
+constexpr OutFmt out_yuv(int layout) { return OutFmt{true, false, SP_PIXEL, layout}; }
+inline size_t yuv_frame_bytes(size_t OH, size_t OW) { return OH * OW + 2 * ((OH + 1) / 2) * ((OW + 1) / 2); }
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
-inline void* out_at(void* p, size_t elems, OutFmt f) { return (char*)p + elems * out_elem(f); }
 inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
 
 int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
@@ -1057,6 +1061,9 @@ struct Xfer {
     int KW() const { return pad ? padded_size(W) : W; }
     size_t in_bytes(rrv_handle h) const { return (size_t)H * W * 3 * in_elem(h->in_form); }                        // per frame
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
+    size_t out_bytes() const {                                                                                      // per frame, in x.fmt
+        return fmt.yuv ? (pad ? yuv_frame_bytes(H, W) : yuv_frame_bytes(H / 8 * 8, W / 8 * 8)) : out_elems() * out_elem(fmt);
+    }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
     PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
 };
@@ -1216,6 +1223,7 @@ int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const
 // the conv_last_k instantiation that writes `f`
 typedef void (*LastFn)(LastP);
 LastFn last_kernel(OutFmt f) {
+    if (f.yuv) return conv_last_k<true, false, SP_PIXEL, true>;
     if (f.u8) return f.chw ? conv_last_k<true, true> : conv_last_k<true>;
     static const LastFn k[2][3] = {{conv_last_k<false>, conv_last_k<false, false, SP_UNIT>, conv_last_k<false, false, SP_NORM>},
                                    {conv_last_k<false, true>, conv_last_k<false, true, SP_UNIT>, conv_last_k<false, true, SP_NORM>}};
@@ -1226,9 +1234,14 @@ LastFn last_kernel(OutFmt f) {
 int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
+    if (fmt.yuv) {
+        if (pc && ((pc->top | pc->left) & 1)) return fail(h, RRV_E_ARG, "conv_last: the YUV form needs an even crop origin");
+        memcpy(lp.yuv_m, h->yuv_m, sizeof lp.yuv_m);
+        lp.yuv_nv12 = fmt.yuv == RRV_LAY_NV12;
+    }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
-    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + 3.0 * out_elem(fmt)) * B * H * W, [&] {
+    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 : 3.0 * out_elem(fmt))) * B * H * W, [&] {
         const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * B), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
         hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
@@ -1828,6 +1841,7 @@ int rrv_create(int device, rrv_handle* out) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RRV_E_HIP;
     rrv_ctx* h = new rrv_ctx();
     h->dev = device;
+    (void)rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_m);      // what players assume for untagged yuv420p
     bool ok = hipSetDevice(device) == hipSuccess;
     for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipStreamCreateWithFlags(&h->streams[i], hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
@@ -2494,13 +2508,13 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const float* d_w = x.wts;
     if (x.model == Model::BLEND && !x.w_dev) RCHK(stage_blend_weights(h, slot, x.wts, (size_t)x.B * x.ns, &d_w));
     const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
-    const size_t fb = x.in_bytes(h), fo = x.out_elems();
+    const size_t fb = x.in_bytes(h), fo = x.out_bytes();
     const PadCrop crop = x.pad_crop();
     const PadCrop* const pc = x.pad ? &crop : nullptr;
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* const in = (const uint8_t*)d_in + (size_t)b0 * fb;
-        void* const out = out_at(d_out, (size_t)b0 * fo, x.fmt);
+        void* const out = (char*)d_out + (size_t)b0 * fo;
         switch (x.model) {
         case Model::GLOBAL:
             RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, x.fmt, nullptr, pc));
@@ -2589,11 +2603,13 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 // the model blends with; the flags and `out` supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME)
 static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
     if (!h) return RRV_E_ARG;
-    auto bad = [](const rrv_image_desc& d) {
-        return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
+    const bool yuv = out.layout == RRV_LAY_I420 || out.layout == RRV_LAY_NV12;      // an output layout only
+    auto bad = [](const rrv_image_desc& d, bool yuv_ok) {
+        return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) ||
                d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
     };
-    if (bad(in) || bad(out)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
+    if (bad(in, false) || bad(out, yuv)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
+    if (yuv && (out.dtype != RRV_DT_U8 || out.space != RRV_SP_PIXEL)) return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8 in the PIXEL space");
     if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
     if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
@@ -2604,7 +2620,7 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* 
         x.model = Model::FRAME;
     }
     x.pad = flags & RRV_TF_PAD_CROP;
-    x.fmt = OutFmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
+    x.fmt = yuv ? out_yuv(out.layout) : OutFmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
     x.w_dev = flags & RRV_TF_WEIGHTS_DEVICE;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x));
@@ -2799,7 +2815,7 @@ static int claim_staging(rrv_handle h) {
     h->next_slot = 0;
     return RRV_OK;
 }
-// The host entries: x.B frames from `frames` to `out` (float32 or uint8 by x.fmt), any B >= 1.  The grouped models run sub-batches of at
+// The host entries: x.B frames from `frames` to `out` (float32, uint8 or 8-bit YUV 4:2:0 by x.fmt, x.out_bytes() per frame), any B >= 1.  The grouped models run sub-batches of at
 // most MS_GROUP_MAX frames, one launch sequence each; the blended one takes the sub-batch's rows of x.wts, the masked one the set's
 // staged mask block.
 static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const Xfer& x) {
@@ -2810,7 +2826,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const float* const mask = x.mask;
     const int mask_images = x.mask_images;
     const size_t fb = x.in_bytes(h);                                        // input bytes per frame
-    const size_t fob = x.out_elems() * out_elem(x.fmt);                     // output bytes per frame
+    const size_t fob = x.out_bytes();                     // output bytes per frame
     char* const outc = (char*)out;
     const int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
     const size_t mfl = x.mask_floats();
@@ -2966,6 +2982,52 @@ int rrv_transfer_frame_mode_frames(rrv_handle h, const uint8_t* frames, int B, i
 }
 int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames, int B, int H, int W, uint8_t* out) {
     return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_U8});
+}
+
+// 8-bit YUV 4:2:0 output of the host entries (conv_last_k's YUV form): frame b at b * (OH*OW + 2*CH*CW) bytes of `out`
+static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12; }
+int rrv_transfer_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, int flags, int layout, uint8_t* out) {
+    if (!h) return RRV_E_ARG;
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_yuv: unknown flags");
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    return host_pipeline(h, frames, out, Xfer{flags & RRV_TF_FRAME_MODE ? Model::FRAME : Model::GLOBAL, B, H, W, (flags & RRV_TF_PAD_CROP) != 0, out_yuv(layout)});
+}
+int rrv_transfer_blend_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, int layout, uint8_t* out) {
+    if (!h) return RRV_E_ARG;
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    return host_pipeline(h, frames, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, out_yuv(layout), ns, wts});
+}
+int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop,
+                                int layout, uint8_t* out) {
+    if (!h) return RRV_E_ARG;
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, out_yuv(layout), ns, /* wts */ nullptr, mask, mask_images});
+}
+
+// The conversion matrix of the YUV forms: Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited
+// range scales Y by 219/255 (+16) and the chroma differences by 224/255.  Coefficients in double, each rounded once to float32.
+int rrv_yuv_matrix(int standard, int full_range, float m[12]) {
+    if (!m || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709)) return RRV_E_ARG;
+    const double kr = standard == RRV_YUV_BT601 ? 0.299 : 0.2126, kb = standard == RRV_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double ys = full_range ? 1.0 : 219.0 / 255.0, cs = full_range ? 1.0 : 224.0 / 255.0;
+    const double y[3] = {kr, kg, kb};
+    for (int c = 0; c < 3; ++c) {
+        m[c] = (float)(ys * y[c]);
+        m[4 + c] = (float)(cs * ((c == 2 ? 1.0 : 0.0) - y[c]) / (2.0 * (1.0 - kb)));
+        m[8 + c] = (float)(cs * ((c == 0 ? 1.0 : 0.0) - y[c]) / (2.0 * (1.0 - kr)));
+    }
+    m[3] = full_range ? 0.f : 16.f;
+    m[7] = m[11] = 128.f;
+    return RRV_OK;
+}
+// handle state, read when conv_last_k is launched: launches already queued keep the matrix they were queued with
+int rrv_set_yuv_matrix(rrv_handle h, const float m[12]) {
+    if (!h) return RRV_E_ARG;
+    if (!m) return rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_m);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m[i])) return fail(h, RRV_E_ARG, "set_yuv_matrix: the twelve coefficients must be finite");
+    memcpy(h->yuv_m, m, sizeof h->yuv_m);
+    return RRV_OK;
 }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----

@@ -116,6 +116,44 @@ def _output(shape, dtype, out):
     return out, out.dtype == np.uint8
 
 
+# ===== 8-bit YUV 4:2:0 output (the rrv_*_yuv entries; include/rerevst_hip.h states the arithmetic) =====
+_YUV_LAYOUTS = {"i420": _lib.LAY_I420, "nv12": _lib.LAY_NV12}
+_YUV_STANDARDS = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709}
+
+
+def yuv_frame_bytes(H, W):
+    """Bytes of one H x W frame in I420 or NV12: H*W luma bytes and two chroma planes of ceil(H/2) x ceil(W/2)."""
+    return int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)
+
+
+def yuv_planes(buf, H, W, layout="i420"):
+    """Views (Y [..][H][W], Cb, Cr [..][CH][CW]) of uint8 frames [..][yuv_frame_bytes(H, W)] as transfer_batch / transfer_frames /
+    transfer_tensor(out_format / out_layout = "i420" | "nv12") return them (a numpy array or a torch tensor).  Nothing is copied:
+    for "nv12" the chroma views are strided (every second byte of the interleaved plane)."""
+    if layout not in _YUV_LAYOUTS:
+        raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    H, W = int(H), int(W)
+    CH, CW = (H + 1) // 2, (W + 1) // 2
+    if buf.shape[-1] != yuv_frame_bytes(H, W):
+        raise ValueError("a %d x %d frame has %d bytes, got %d" % (H, W, yuv_frame_bytes(H, W), buf.shape[-1]))
+    lead = tuple(buf.shape[:-1])
+    y = buf[..., :H * W].reshape(lead + (H, W))
+    if layout == "i420":
+        return y, buf[..., H * W:H * W + CH * CW].reshape(lead + (CH, CW)), buf[..., H * W + CH * CW:].reshape(lead + (CH, CW))
+    c = buf[..., H * W:].reshape(lead + (CH, CW, 2))
+    return y, c[..., 0], c[..., 1]
+
+
+def yuv_matrix(standard="bt601", full_range=False):
+    """rrv_yuv_matrix: the float32 [3][4] matrix (rows Y, Cb, Cr; columns R, G, B, offset) of a standard and range; needs no GPU."""
+    if standard not in _YUV_STANDARDS:
+        raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
+    m = np.empty((3, 4), np.float32)
+    if _lib.load().rrv_yuv_matrix(_YUV_STANDARDS[standard], int(bool(full_range)), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("rrv_yuv_matrix refused %r" % (standard,))
+    return m
+
+
 # ===== torch tensors (rrv_transfer_image_device) =====
 _SPACES = {"pixel": _lib.SP_PIXEL, "unit": _lib.SP_UNIT, "norm": _lib.SP_NORM}
 _LAYOUTS = {"nhwc": _lib.LAY_HWC_BGR, "nchw": _lib.LAY_CHW_RGB}     # nhwc: BGR (cv2's convention), nchw: RGB (torch's)
@@ -136,8 +174,11 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
     if space not in _SPACES or out_space not in _SPACES:
         raise ValueError("space and out_space must be one of %s, got %r / %r" % (sorted(_SPACES), space, out_space))
     out_layout = layout if out_layout is None else out_layout
-    if layout not in _LAYOUTS or out_layout not in _LAYOUTS:
-        raise ValueError("layout and out_layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r / %r" % (layout, out_layout))
+    yuv = out_layout in _YUV_LAYOUTS         # an output layout only: uint8 [B][yuv_frame_bytes] in the "pixel" space
+    if layout not in _LAYOUTS or (out_layout not in _LAYOUTS and not yuv):
+        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), out_layout one of those or 'i420' / 'nv12', got %r / %r" % (layout, out_layout))
+    if yuv and out_space != "pixel":
+        raise ValueError("an %r output is in the 'pixel' space, not %r" % (out_layout, out_space))
 
     def on_device(t, what):
         if t.device.type != "cuda" or t.device.index != int(device):
@@ -152,7 +193,7 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
             dt = _lib.DT_F32
         else:
             raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
-        return _lib.ImageDesc(dt, _LAYOUTS[lay], _SPACES[sp])
+        return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else _YUV_LAYOUTS[lay], _SPACES[sp])
 
     on_device(x, "x")
     in_desc = desc(x.dtype, space, layout, "x")
@@ -166,7 +207,7 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
     if B < 1:
         raise ValueError("x holds no image")
     Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-    out_shape = (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
+    out_shape = (B, yuv_frame_bytes(Ho, Wo)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
     if not batched:
         out_shape = out_shape[1:]
     if out is not None:
@@ -174,7 +215,9 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
         out_dtype = out.dtype
         if tuple(out.shape) != out_shape or not out.is_contiguous():
             raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_dtype = (torch.uint8 if yuv else torch.float32) if out_dtype is None else out_dtype
+    if yuv and out_dtype != torch.uint8:
+        raise ValueError("an %r output is torch.uint8, got %s" % (out_layout, out_dtype))
     out_desc = desc(out_dtype, out_space, out_layout, "out")
     if not x.is_contiguous():
         x = x.contiguous()
@@ -273,6 +316,9 @@ class Stylization():
     # the transfer entries take dtype=np.uint8 / a uint8 `out`: the float32 output rounded half to even on the GPU
     # (include/rerevst_hip.h, the rrv_*_u8 entries); driver.stylize_files* ask for it
     uint8_output = True
+    # transfer_batch / transfer_frames take out_format="i420" | "nv12" (the rrv_*_yuv entries): driver.stylize_files asks for it when
+    # it writes only a .y4m video
+    yuv_output = True
 
     def __init__(self, checkpoint, cuda=True, use_Global=True, device=None, style_num=1):
         if not cuda:
@@ -476,17 +522,36 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop):
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr"):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames, the checked masks or
-        weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one)"""
+        weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one);
+        out_format "i420" / "nv12": their _yuv forms, uint8 [B][yuv_frame_bytes] whatever `dtype` says"""
+        if out_format != "bgr" and out_format not in _YUV_LAYOUTS:
+            raise ValueError("out_format must be 'bgr', 'i420' or 'nv12', got %r" % (out_format,))
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
             a = np.stack([_u8_image(f, "frame") for f in frames])
         B, H, W, _ = a.shape
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
         head = (self._h, a.ctypes.data_as(C.c_void_p), B, H, W)
+        if out_format != "bgr":
+            shape = (B, yuv_frame_bytes(H, W) if pad_crop else yuv_frame_bytes(H // 8 * 8, W // 8 * 8))
+            if out is None:
+                out = _outputs.empty(shape, np.uint8)
+            elif out.dtype != np.uint8 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous uint8 array of shape %r" % (shape,))
+            lay, dst = _YUV_LAYOUTS[out_format], out.ctypes.data_as(C.c_void_p)
+            if m is not None:
+                self._chk(self._lib.rrv_transfer_mask_batch_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop), lay, dst))
+            elif style_weights is not None:
+                w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
+                self._chk(self._lib.rrv_transfer_blend_batch_yuv(*head, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, int(pad_crop), lay, dst))
+            else:
+                flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+                self._chk(self._lib.rrv_transfer_yuv(*head, flags, lay, dst))
+            return out
+        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
         if m is not None:
             name, args = "rrv_transfer_mask_batch", (m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop))
         elif style_weights is not None:
@@ -497,7 +562,7 @@ class Stylization():
         self._chk(self._entry(name, u8)(*head, *args, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
+    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr"):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -506,10 +571,13 @@ class Stylization():
         frame b equals transfer(frames[b], style_weight=style_weights[b]), bit for bit for a fixed kernel choice.
         style_masks: the styles blended PER PIXEL instead: a float32 ndarray [B][S][H][W] (or [S][H][W]: every frame) at the
         frames' resolution; every saved quantity becomes sum_s m_s(p) q_s at each decoder pixel p, m the mean of the mask
-        over the input pixels p covers (rrv_transfer_mask_batch).  Not normalised; mutually exclusive with style_weights."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, False)
+        over the input pixels p covers (rrv_transfer_mask_batch).  Not normalised; mutually exclusive with style_weights.
+        out_format: "bgr" (default), or "i420" / "nv12": 8-bit YUV 4:2:0 converted on the GPU with the matrix of set_yuv_matrix
+        (rrv_transfer_yuv and its blend / mask forms): a uint8 [B][yuv_frame_bytes(Ho, Wo)] array (`out` of that shape is
+        filled; yuv_planes() gives the planes), 1.5 bytes per pixel over PCIe; composes with style_weights / style_masks."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format)
 
-    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None):
+    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr"):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -517,8 +585,10 @@ class Stylization():
         `out` / `dtype` as in transfer_batch: uint8 output is to_uint8 of the float output, computed on the GPU.
         style_weights: [B][S] (or [S]) blend weights per frame, as in transfer_batch.
         style_masks: [B][S][H][W] (or [S][H][W]) per-pixel blend weights for the UNPADDED frames, as in transfer_batch; the
-        mask is reflect-padded on the device as the frame is."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, True)
+        mask is reflect-padded on the device as the frame is.
+        out_format: "i420" / "nv12" as in transfer_batch: uint8 [B][yuv_frame_bytes(H, W)]; an odd H or W gives a last chroma row
+        or column that covers one pixel row / column (replicated, never the padding)."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -543,7 +613,9 @@ class Stylization():
         style_masks: the styles blended per pixel (rrv_transfer_image_mask_device): a float32 torch tensor [B,S,H,W] (or
         [S,H,W]: every image) on the handle's device, read in the order of the current stream with no host synchronisation,
         or a float32 ndarray of those shapes (copied to the device on that stream).  H, W are those of x.  Mutually exclusive
-        with style_weights."""
+        with style_weights.
+        out_layout "i420" / "nv12": 8-bit YUV 4:2:0 (the matrix of set_yuv_matrix), a uint8 tensor [B, yuv_frame_bytes(Ho, Wo)]
+        ([yuv_frame_bytes] unbatched) in the "pixel" space; yuv_planes() gives views of the planes."""
         import torch
         a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
                            out_layout=out_layout, pad_crop=pad_crop, out=out)
@@ -630,6 +702,19 @@ class Stylization():
         out = np.empty((6, 32), dtype=np.float32)
         self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_PRED, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    def set_yuv_matrix(self, standard="bt601", full_range=False):
+        """The conversion matrix of the "i420" / "nv12" outputs (rrv_set_yuv_matrix): a standard ("bt601" | "bt709") and range, or
+        twelve finite floats ([3][4]: rows Y, Cb, Cr; columns R, G, B, offset) in place of `standard`; None restores the default,
+        BT.601 limited range.  Read when a call launches; returns the float32 [3][4] matrix now installed."""
+        if standard is None:
+            self._chk(self._lib.rrv_set_yuv_matrix(self._h, None))
+            return yuv_matrix("bt601", False)
+        m = yuv_matrix(standard, full_range) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
+        if m.size != 12:
+            raise ValueError("a YUV matrix has 12 coefficients, got %d" % m.size)
+        self._chk(self._lib.rrv_set_yuv_matrix(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
+        return m.reshape(3, 4).copy()
 
     def set_host_io(self, mode):
         """0 (default): staged H2D / D2H copies; 1: zero copy — kernels read / write page-locked host memory directly."""

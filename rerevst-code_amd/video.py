@@ -86,6 +86,58 @@ def resize_bilinear(img, size):
     return np.clip(np.rint(top * (1 - fy) + bot * fy), 0, 255).astype(np.uint8)
 
 
+YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}      # (Kr, Kb); Kg = 1 - Kr - Kb
+
+
+def yuv_matrix(standard="bt601", full_range=False):
+    """rrv_yuv_matrix on the host: float32 [3][4], rows Y, Cb, Cr, columns the coefficients of R, G, B and an offset.  Full range:
+    Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited range: Y' = 16 + 219/255 Y
+    and the chroma differences times 224/255.  Evaluated in double, each coefficient rounded once to float32."""
+    kr, kb = YUV_STANDARDS[standard]
+    k = np.array([kr, 1.0 - kr - kb, kb], np.float64)
+    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    m = np.zeros((3, 4), np.float64)
+    m[0, :3] = ys * k
+    m[1, :3] = cs * (np.array([0.0, 0.0, 1.0]) - k) / (2.0 * (1.0 - kb))
+    m[2, :3] = cs * (np.array([1.0, 0.0, 0.0]) - k) / (2.0 * (1.0 - kr))
+    m[:, 3] = (0.0 if full_range else 16.0, 128.0, 128.0)
+    return m.astype(np.float32)
+
+
+def yuv_frame_bytes(H, W):
+    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+
+
+def bgr_to_yuv420(img, m, layout="i420"):
+    """The GPU's YUV 4:2:0 conversion (include/rerevst_hip.h, the rrv_*_yuv entries) in numpy float32, for frames that come from files:
+    img [..][H][W][3] BGR, float32 in 0..255 or uint8; m the twelve matrix floats; returns uint8 [..][yuv_frame_bytes(H, W)] in
+    "i420" ([Y][Cb][Cr]) or "nv12" ([Y][CbCr]).  Every product and sum is a float32 operation in the kernel's order, so on the float32
+    output of a transfer entry this gives the bytes of its YUV form."""
+    if layout not in ("i420", "nv12"):
+        raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    f = np.asarray(img).astype(np.float32)
+    m = np.asarray(m, np.float32).reshape(3, 4)
+    H, W = f.shape[-3:-1]
+    lead = f.shape[:-3]
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    zero, top, quarter = np.float32(0), np.float32(255), np.float32(0.25)
+    comp = [((m[k, 0] * r + m[k, 1] * g) + m[k, 2] * b) + m[k, 3] for k in range(3)]
+    byte = lambda v: np.rint(np.minimum(np.maximum(v, zero), top)).astype(np.uint8)
+    y0, x0 = np.arange(0, H, 2), np.arange(0, W, 2)
+    y1, x1 = np.minimum(y0 + 1, H - 1), np.minimum(x0 + 1, W - 1)          # a row / column past the frame: its nearest one inside
+    planes = [byte(comp[0]).reshape(lead + (H * W,))]
+    chroma = []
+    for c in comp[1:]:
+        rows0, rows1 = c[..., y0, :], c[..., y1, :]
+        mean = ((rows0[..., x0] + rows0[..., x1]) + (rows1[..., x0] + rows1[..., x1])) * quarter
+        chroma.append(byte(mean))
+    if layout == "i420":
+        planes += [c.reshape(lead + (-1,)) for c in chroma]
+    else:
+        planes.append(np.stack(chroma, axis=-1).reshape(lead + (-1,)))
+    return np.concatenate(planes, axis=-1)
+
+
 def shard_range(frame_num, rank, world):
     """Contiguous block of frames owned by `rank`."""
     lo = frame_num * rank // world
