@@ -377,9 +377,10 @@ int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int 
  * Device entries: rrv_transfer_image_device, _blend_device and _mask_device take out.layout = RRV_LAY_I420 / RRV_LAY_NV12 with
  * out.dtype == RRV_DT_U8 and out.space == RRV_SP_PIXEL (anything else, and either layout for the input, is RRV_E_ARG); all flags and
  * input forms as before.  rrv_get_preclamp_image works as after the float twin.
- * Not offered: tickets (rrv_transfer_async), the cached-feature entries (rrv_transfer_features[_batch]), the one-frame
- * rrv_transfer_blend[_device] and rrv_transfer_frame_mode, and YUV input. */
-enum {                         /* output-only values of rrv_image_desc.layout, after RRV_LAY_HWC_BGR = 0 and RRV_LAY_CHW_RGB = 1 */
+ * Not offered: tickets (rrv_transfer_async), the cached-feature entries (rrv_transfer_features[_batch]) and the one-frame
+ * rrv_transfer_blend[_device] and rrv_transfer_frame_mode.  The rrv_image_desc entries still refuse RRV_LAY_I420 / RRV_LAY_NV12 as an INPUT
+ * layout (RRV_E_ARG): 8-bit YUV frames enter through the rrv_*_from_yuv entries below. */
+enum {                         /* output-only values of rrv_image_desc.layout (and the in_layout of the _from_yuv entries), after RRV_LAY_HWC_BGR = 0 and RRV_LAY_CHW_RGB = 1 */
     RRV_LAY_I420 = 2,          /* planar Y, Cb, Cr (ffmpeg's yuv420p) */
     RRV_LAY_NV12 = 3           /* planar Y, then interleaved Cb Cr */
 };
@@ -391,6 +392,56 @@ int rrv_transfer_blend_batch_yuv(rrv_handle h, const uint8_t* frames_bgr, int B,
                                  const float* style_weight, int n_styles, int pad_crop, int layout, uint8_t* out_yuv);
 int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames_bgr, int B, int H, int W,
                                 const float* mask, int n_styles, int mask_images, int pad_crop, int layout, uint8_t* out_yuv);
+
+/* 8-bit YUV 4:2:0 INPUT (a hardware decoder's NV12, ffmpeg's yuv420p, a .y4m file): the first kernel reads Y, Cb and Cr, 1.5 bytes per pixel
+ * cross PCIe instead of 3, and the host converts nothing.  With a YUV output the decoder -> stylize -> encoder loop touches no pixel on the host.
+ * Input frame, all uint8, for an H x W frame as passed: CH = (H+1)/2, CW = (W+1)/2, frame_bytes = H*W + 2*CH*CW, frame b at b * frame_bytes;
+ * RRV_LAY_I420 [Y: H*W][Cb: CH*CW][Cr: CH*CW], RRV_LAY_NV12 [Y: H*W][CbCr interleaved: CH*CW*2] — exactly the layouts the output entries write.
+ * Arithmetic.  Pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1): chroma is replicated over its 2 x 2 block, the adjoint of the
+ * output's box mean for C420jpeg siting.  (The content encoder folds a frame to one grey value per pixel — RGB2Gray, test/style_network_global.py
+ * :487-497 — so a better chroma interpolation would not be visible in the result.)  n[3][4] is a conversion matrix: rows R, G, B; columns the
+ * coefficients of Y, Cb, Cr and an offset.
+ *   v_k  = ((n[k][0]*Y + n[k][1]*Cb) + n[k][2]*Cr) + n[k][3]     every product and sum rounded to float32, in this order, no fused multiply-add
+ *   px_k = min(max(v_k, 0), 255)                                   not rounded to an integer
+ * and from there on px is a float32 PIXEL input (RRV_DT_F32, RRV_LAY_HWC_BGR, RRV_SP_PIXEL).  So a YUV call's result equals, bit for bit, the
+ * result of its float32 PIXEL BGR twin fed with the frame this arithmetic produces: over the device entries in every rrv_set_f43 mode, between
+ * the host entries and the device twin in the fixed modes 0 and 2.  With RRV_TF_PAD_CROP the reflection acts on the pixel coordinates first and
+ * the chroma lookup follows, which equals reflect-padding the converted frame, also for odd H / W.
+ * rrv_yuv_input_matrix fills n with the inverse of rrv_yuv_matrix's transform for a standard and range — limited: Y' = (Y - 16) 255/219,
+ * C' = (C - 128) 255/224; full: Y' = Y, C' = C - 128; R = Y' + 2(1-Kr) Cr', B = Y' + 2(1-Kb) Cb', G = Y' - (2 Kb (1-Kb) / Kg) Cb' -
+ * (2 Kr (1-Kr) / Kg) Cr', the offsets folded into column 3 — each coefficient evaluated in double and rounded once to float32; it needs no handle
+ * and no GPU.  rrv_set_yuv_input_matrix installs any twelve finite floats (else RRV_E_ARG); NULL restores the default, BT.601 limited range.  It
+ * is handle state, independent of the output matrix, read when a call launches its first kernel (for rrv_add_from_yuv: when the deferred
+ * encoding runs, in rrv_compute at the latest).
+ * Device entries: rrv_transfer_from_yuv_device, _blend_from_yuv_device and _mask_from_yuv_device are rrv_transfer_image_device, _image_blend_device
+ * and _image_mask_device with in_layout = RRV_LAY_I420 / RRV_LAY_NV12 in place of the input descriptor: the same flags, stream ordering, slots,
+ * limits and errors; H, W >= 8; `out` any output descriptor, RRV_LAY_I420 / RRV_LAY_NV12 included (NV12 in -> NV12 out is decoder to encoder).
+ * Host entries: rrv_transfer_from_yuv (flags within RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE), rrv_transfer_blend_from_yuv and
+ * rrv_transfer_mask_from_yuv (flags within RRV_TF_PAD_CROP), pipelined as rrv_transfer_yuv (sub-batches of at most sixteen frames, staging,
+ * page-locked buffers, every rrv_set_host_io mode), any B >= 1; `out` is float32 or uint8 RRV_LAY_HWC_BGR in RRV_SP_PIXEL, or uint8 I420 / NV12.
+ * rrv_add_from_yuv[_device]: rrv_add / rrv_add_image_device for a sampled frame in one of the two layouts (deferred encoding, as they do).
+ * Anything else — another in_layout, a null buffer, H or W < 8, an unknown flag — is RRV_E_ARG and the handle stays usable.  Not offered:
+ * rrv_prepare_style from YUV (styles are image files), tickets and the cached-feature entries. */
+int rrv_yuv_input_matrix(int standard, int full_range, float n[12]);
+int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]);
+int rrv_transfer_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W,
+                                 void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+int rrv_transfer_blend_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W,
+                                       const float* style_weight, int n_styles,
+                                       void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+int rrv_transfer_mask_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W,
+                                      const float* d_mask, int n_styles, int mask_images,
+                                      void* d_out, rrv_image_desc out, int flags, void* hip_stream);
+int rrv_transfer_from_yuv(rrv_handle h, const uint8_t* frames_yuv, int in_layout, int B, int H, int W,
+                          void* out, rrv_image_desc out_desc, int flags);
+int rrv_transfer_blend_from_yuv(rrv_handle h, const uint8_t* frames_yuv, int in_layout, int B, int H, int W,
+                                const float* style_weight, int n_styles,
+                                void* out, rrv_image_desc out_desc, int flags);
+int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames_yuv, int in_layout, int B, int H, int W,
+                               const float* mask, int n_styles, int mask_images,
+                               void* out, rrv_image_desc out_desc, int flags);
+int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame_yuv, int in_layout, int H, int W);
+int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame_yuv, int in_layout, int H, int W, void* hip_stream);
 
 /* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
  * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;

@@ -88,6 +88,21 @@ SYMBOLS = {
                                                C.c_void_p]),
     "rrv_transfer_mask_batch_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_void_p]),
+    "rrv_yuv_input_matrix": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rrv_set_yuv_input_matrix": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    # 8-bit YUV 4:2:0 input: (h, in, in_layout, B, H, W, [weights, n_styles | mask, n_styles, mask_images,] out, ImageDesc out, flags[, hip_stream])
+    "rrv_transfer_from_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),
+    "rrv_transfer_blend_from_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                     C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),      # style_weight: host or device address
+    "rrv_transfer_mask_from_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_void_p, ImageDesc, C.c_int, C.c_void_p]),       # d_mask: device address
+    "rrv_transfer_from_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_transfer_blend_from_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                              C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_transfer_mask_from_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                             C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_add_from_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "rrv_add_from_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),

@@ -15,6 +15,8 @@
 // YUV form (the rrv_*_yuv entries, out.layout = RRV_LAY_I420 / RRV_LAY_NV12): conv_last_k<true, false, SP_PIXEL, true> converts the
 //   float form's values with a 3 x 4 matrix and stores 8-bit 4:2:0, a Y byte per pixel and a Cb, Cr pair per 2 x 2 block.  Writes
 //   1.5 (+12) B/pixel.
+// YUV input (the rrv_*_from_yuv entries): conv_first_k<IN_YUV_I420 / IN_YUV_NV12> reads a Y byte per pixel and the Cb, Cr bytes of its
+//   2 x 2 block, converts them with a 3 x 4 matrix to the float32 PIXEL value and goes on as the float32 form does.  Reads 1.5 B/pixel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,11 +27,16 @@
 // Value spaces of a frame (include/rerevst_hip.h RRV_SP_*): PIXEL 0..255, UNIT 0..1, NORM transform_image's (x/255 - mean)/std
 enum : int { SP_PIXEL = 0, SP_UNIT = 1, SP_NORM = 2 };
 // conv_first_k's input forms (the template argument): bit 0 planar CHW RGB (else HWC BGR), bit 1 float32 (else uint8)
-enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3 };
-inline size_t in_elem(int form) { return (form & 2) ? sizeof(float) : 1; }     // bytes per input channel value
+// 4, 5: 8-bit YUV 4:2:0 frames, [Y: H*W][Cb: CH*CW][Cr: CH*CW] (I420) or [Y: H*W][CbCr interleaved: CH*CW*2] (NV12), CH = (H+1)/2, CW = (W+1)/2
+enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3, IN_YUV_I420 = 4, IN_YUV_NV12 = 5, IN_FORMS = 6 };
+inline bool in_yuv(int form) { return form >= IN_YUV_I420; }
+inline size_t in_elem(int form) { return !in_yuv(form) && (form & 2) ? sizeof(float) : 1; }     // bytes per input value
+inline size_t in_frame_bytes(int form, size_t H, size_t W) {                                      // bytes of one H x W input frame
+    return in_yuv(form) ? H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2) : H * W * 3 * in_elem(form);
+}
 
 struct FirstP {
-    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32
+    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32; IN_YUV_*: [B][H*W + 2*CH*CW] uint8
     int H, W, B;
     float* out;           // [B,H,W,64] ring layout
     const float* w;       // [27][64]: row (ky*3+kx)*3 + c_rgb
@@ -43,6 +50,7 @@ struct FirstP {
     int src_H, src_W, pad_top, pad_left;
     int p8;               // 1: `out` is channel-chunk-major [B][8 chunks][H+2][W+8][8], pixel x at column x + 4 (conv_f43.h LAY: what conv1_2 on conv_f43_k reads 12-19 % faster); same values
     int space;            // value space of a float32 input (SP_*); a uint8 input is PIXEL
+    float yuv_n[12];      // IN_YUV_*: rows R, G, B; columns the coefficients of Y, Cb, Cr and an offset (rrv_set_yuv_input_matrix), by value
 };
 
 // symmetric (edge-inclusive) reflection of t into [0, n), any distance
@@ -57,9 +65,13 @@ __device__ __forceinline__ int reflect_sym(int t, int n) {
 // ((float)px / 255 - mean) / std: a float PIXEL value v as v / 255 (bit-identical for integral v), a UNIT value x in place of
 // px / 255 (the same float where x is the correctly rounded px / 255), a NORM value n as it is.  Everything after that (grey
 // fold, border path, P8 stores, reflect-pad addressing) is shared.
+// IN_YUV_*: source pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1) — after the reflection of the pad geometry, which
+// therefore equals reflect-padding the converted frame, also for odd H / W — and v_k = ((n[k][0] Y + n[k][1] Cb) + n[k][2] Cr) + n[k][3],
+// every product and sum rounded to float32 (no contraction), px_k = min(max(v_k, 0), 255), not rounded to an integer: the float PIXEL
+// value.  Frame starts and chroma planes are in general not dword aligned: byte loads.
 template <int IN = IN_U8_HWC>
 __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
-    constexpr bool CHW = (IN & 1) != 0, F32 = (IN & 2) != 0;
+    constexpr bool YUV = IN >= IN_YUV_I420, NV12 = IN == IN_YUV_NV12, CHW = !YUV && (IN & 1) != 0, F32 = !YUV && (IN & 2) != 0;
     typedef typename std::conditional<F32, float, uint8_t>::type T;
     __shared__ __attribute__((aligned(16))) float s_in[18 * 18 * 4];
     __shared__ __attribute__((aligned(16))) float s_w[27 * 64];
@@ -71,14 +83,30 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
     const int b = bx / p.tiles_y;
     const int y0 = ty * 16, x0 = tx * 16;
     const int SH = p.src_H ? p.src_H : p.H, SW = p.src_H ? p.src_W : p.W;
-    const T* img = (const T*)p.img + (size_t)b * SH * SW * 3;
-    auto src_px = [&](int y, int x) {       // padded-frame pixel -> its index in a plane of the source frame
+    const int CW = (SW + 1) >> 1;                                              // IN_YUV_*: the chroma planes are CH x CW
+    const size_t ysz = (size_t)SH * SW, csz = (size_t)((SH + 1) >> 1) * CW;
+    const T* img = YUV ? (const T*)p.img + (size_t)b * (ysz + 2 * csz) : (const T*)p.img + (size_t)b * SH * SW * 3;
+    struct SrcPx { size_t i; int y, x; };   // index in a plane of the source frame, and its row and column there
+    auto src_px = [&](int y, int x) {       // padded-frame pixel -> the source pixel it reads
         if (p.src_H) { y = reflect_sym(y - p.pad_top, SH); x = reflect_sym(x - p.pad_left, SW); }
-        return (size_t)y * SW + x;
+        return SrcPx{(size_t)y * SW + x, y, x};
     };
 
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
-    auto norm_of = [&](size_t i, int c) -> float {      // source pixel i -> normalised value of channel c, RGB order (framework.py:27,33-34)
+    auto norm_of = [&](const SrcPx& s, int c) -> float {      // source pixel -> normalised value of channel c, RGB order (framework.py:27,33-34)
+        if constexpr (YUV) {
+            const size_t ci = (size_t)(s.y >> 1) * CW + (s.x >> 1);
+            const float yy = (float)img[s.i], cb = (float)img[NV12 ? ysz + 2 * ci : ysz + ci], cr = (float)img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci];
+            float v;
+            {
+#pragma clang fp contract(off)
+                const float a = p.yuv_n[4 * c] * yy + p.yuv_n[4 * c + 1] * cb;
+                const float ab = a + p.yuv_n[4 * c + 2] * cr;
+                v = ab + p.yuv_n[4 * c + 3];
+            }
+            return (fminf(fmaxf(v, 0.f), 255.f) / 255.0f - mean[c]) / sd[c];      // as a float32 PIXEL value from here on
+        }
+        const size_t i = s.i;
         const float v = CHW ? (float)img[(size_t)c * SH * SW + i] : (float)img[i * 3 + 2 - c];
         if constexpr (F32) {
             if (p.space == SP_NORM) return v;
@@ -93,7 +121,7 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
         float* s_g = s_in;      // [18][18] grey values
         for (int i = tid; i < 18 * 18; i += 256) {
             const int hy = i / 18, hx = i - hy * 18;
-            const size_t px = src_px(y0 + hy - 1, x0 + hx - 1);
+            const SrcPx px = src_px(y0 + hy - 1, x0 + hx - 1);
             float d[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) d[c] = norm_of(px, c) * sd[c] + mean[c];   // as the reference rounds it
@@ -160,7 +188,7 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
         const int y = y0 + hy - 1, x = x0 + hx - 1;
         float o[3] = {0.f, 0.f, 0.f};
         if (y >= 0 && y < p.H && x >= 0 && x < p.W) {
-            const size_t px = src_px(y, x);
+            const SrcPx px = src_px(y, x);
             float n[3];   // normalised, RGB order (framework.py:27,33-34)
 #pragma unroll
             for (int c = 0; c < 3; ++c) n[c] = norm_of(px, c);

@@ -258,6 +258,7 @@ struct rrv_ctx {
     bool f43_path = false;            // true inside transfer_device only: the preparation pass (prepare_style / add / compute, frame mode) always runs F(2x2,3x3)
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
+    float yuv_in_m[12];               // rrv_set_yuv_input_matrix: rows R, G, B x (Y, Cb, Cr, offset) of the YUV input forms; read at launch (run_encoder), BT.601 limited range at rrv_create
     float yuv_m[12];                  // rrv_set_yuv_matrix: rows Y, Cb, Cr x (R, G, B, offset) of the YUV store form; read at launch (run_last), BT.601 limited range at rrv_create
     int host_io = 0;                  // rrv_set_host_io: 0 = staged H2D / D2H copies, 1 = zero copy (kernels read / write page-locked host memory), 2 = input only, 3 = output only
     int n_cus = 256;
@@ -993,8 +994,10 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
               h->in_space};
     stamp(h, p8 ? &e.q11 : &e.c11, B);
-    static void (*const first_k[4])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>};
-    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, (3.0 * in_elem(inf) + 256.0) * B * H * W, [&] {
+    if (in_yuv(inf)) memcpy(fp.yuv_n, h->yuv_in_m, sizeof fp.yuv_n);
+    static void (*const first_k[IN_FORMS])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>,
+                                                      conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>};
+    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? 1.5 : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
         hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
     }));
     ConvCall c;
@@ -1059,7 +1062,7 @@ struct Xfer {
 
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
-    size_t in_bytes(rrv_handle h) const { return (size_t)H * W * 3 * in_elem(h->in_form); }                        // per frame
+    size_t in_bytes(rrv_handle h) const { return in_frame_bytes(h->in_form, H, W); }                               // per frame, in the scoped input form
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
         return fmt.yuv ? (pad ? yuv_frame_bytes(H, W) : yuv_frame_bytes(H / 8 * 8, W / 8 * 8)) : out_elems() * out_elem(fmt);
@@ -1841,6 +1844,7 @@ int rrv_create(int device, rrv_handle* out) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RRV_E_HIP;
     rrv_ctx* h = new rrv_ctx();
     h->dev = device;
+    (void)rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in_m);
     (void)rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_m);      // what players assume for untagged yuv420p
     bool ok = hipSetDevice(device) == hipSuccess;
     for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipStreamCreateWithFlags(&h->streams[i], hipStreamNonBlocking) == hipSuccess;
@@ -2203,7 +2207,7 @@ int rrv_clean(rrv_handle h) {
 static int flush_pending(rrv_handle h) {
     if (!h->pend_n) return RRV_OK;
     const int H = h->add_H, W = h->add_W;
-    const size_t fb = (size_t)H * W * 3 * in_elem(h->pend_form);
+    const size_t fb = in_frame_bytes(h->pend_form, H, W);
     const int PB = h->pend_n < 8 ? h->pend_n : 8;        // one plan; the last group may use fewer of its images
     RCHK(enc_plan(h, h->enc_add, PB, H, W));
     InFormScope in_scope(h, h->pend_form, h->pend_space);      // the pending frames are kept in the form they arrived in
@@ -2236,7 +2240,7 @@ static int add_frame(rrv_handle h, const void* frame, bool device, int form, int
         RCHK(flush_pending(h));
     }
     h->pend_form = form; h->pend_space = space;
-    const size_t fb = (size_t)H * W * 3 * in_elem(form);
+    const size_t fb = in_frame_bytes(form, H, W);
     if ((size_t)(h->pend_n + 1) * fb > h->pend_cap) {      // grow (x2) keeping the frames already collected
         const size_t cap = ((size_t)(h->pend_n + 1) * fb) * 2 > 16 * fb ? ((size_t)(h->pend_n + 1) * fb) * 2 : 16 * fb;
         uint8_t* nw = nullptr;
@@ -2266,6 +2270,25 @@ int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, i
     int form, space;
     if (!image_in_form(in, &form, &space)) return fail(h, RRV_E_ARG, "add: unknown dtype, layout or space (uint8 is PIXEL only)");
     return add_frame(h, d_frame, true, form, space, (hipStream_t)hip_stream, H, W);
+}
+
+// sampled frames as 8-bit YUV 4:2:0 (conv_first_k<IN_YUV_*>); the input matrix is read when the deferred encoding runs
+static bool yuv_in_form(int layout, int* form) {
+    if (layout != RRV_LAY_I420 && layout != RRV_LAY_NV12) return false;
+    *form = layout == RRV_LAY_NV12 ? IN_YUV_NV12 : IN_YUV_I420;
+    return true;
+}
+int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame, int in_layout, int H, int W) {
+    if (!h || !frame) return RRV_E_ARG;
+    int form;
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    return add_frame(h, frame, false, form, SP_PIXEL, nullptr, H, W);
+}
+int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame, int in_layout, int H, int W, void* hip_stream) {
+    if (!h || !d_frame) return RRV_E_ARG;
+    int form;
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    return add_frame(h, d_frame, true, form, SP_PIXEL, (hipStream_t)hip_stream, H, W);
 }
 
 int rrv_compute(rrv_handle h) {
@@ -2601,16 +2624,15 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 // rrv_transfer_image_device: the device entries above with the content frames read as `in` (conv_first_k<IN>) and the
 // stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only.  x: the model, B, H, W and what
 // the model blends with; the flags and `out` supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME)
-static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
-    if (!h) return RRV_E_ARG;
-    const bool yuv = out.layout == RRV_LAY_I420 || out.layout == RRV_LAY_NV12;      // an output layout only
-    auto bad = [](const rrv_image_desc& d, bool yuv_ok) {
-        return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) ||
-               d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
-    };
-    if (bad(in, false) || bad(out, yuv)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
+static bool bad_desc(const rrv_image_desc& d, bool yuv_ok) {
+    return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) ||
+           d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
+}
+// in_form, in_space: the checked input form (a descriptor's, or IN_YUV_* of the _from_yuv_device entries)
+static int image_run(rrv_handle h, const void* d_in, int in_form, int in_space, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
+    const bool yuv = out.layout == RRV_LAY_I420 || out.layout == RRV_LAY_NV12;      // an output layout of the descriptor entries
+    if (bad_desc(out, yuv)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
     if (yuv && (out.dtype != RRV_DT_U8 || out.space != RRV_SP_PIXEL)) return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8 in the PIXEL space");
-    if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
     if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
         return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
@@ -2628,10 +2650,37 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* 
         rrv_handle h; hipStream_t cs; bool sync;
         ~Scope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; h->caller_stream = cs; h->caller_sync = sync; }
     } scope{h, h->caller_stream, h->caller_sync};
-    h->in_form = (in.dtype == RRV_DT_F32 ? 2 : 0) | (in.layout == RRV_LAY_CHW_RGB ? 1 : 0);
-    h->in_space = in.space;
+    h->in_form = in_form;
+    h->in_space = in_space;
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
     return run_xfer(h, next_slot(h, x), d_in, d_out, x);
+}
+static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
+    if (!h) return RRV_E_ARG;
+    if (bad_desc(in, false)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");      // a YUV input goes through the _from_yuv_device entries
+    if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
+    return image_run(h, d_in, (in.dtype == RRV_DT_F32 ? 2 : 0) | (in.layout == RRV_LAY_CHW_RGB ? 1 : 0), in.space, d_out, out, flags, hip_stream, x);
+}
+// the same entries reading 8-bit YUV 4:2:0 frames (conv_first_k<IN_YUV_*>): [B][H*W + 2*CH*CW] uint8 in HBM
+static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
+    if (!h) return RRV_E_ARG;
+    int form;
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
+    return image_run(h, d_in, form, SP_PIXEL, d_out, out, flags, hip_stream, x);
+}
+int rrv_transfer_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W, void* d_out, rrv_image_desc out, int flags,
+                                 void* hip_stream) {
+    return from_yuv_device(h, d_in, in_layout, d_out, out, flags, hip_stream, Xfer{Model::GLOBAL, B, H, W});
+}
+int rrv_transfer_blend_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W, const float* style_weight, int n_styles,
+                                       void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
+    return from_yuv_device(h, d_in, in_layout, d_out, out, flags, hip_stream, Xfer{Model::BLEND, B, H, W, PLAIN, OUT_F32, n_styles, style_weight});
+}
+int rrv_transfer_mask_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W, const float* d_mask, int n_styles,
+                                      int mask_images, void* d_out, rrv_image_desc out, int flags, void* hip_stream) {
+    return from_yuv_device(h, d_in, in_layout, d_out, out, flags, hip_stream,
+                           Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, n_styles, /* wts */ nullptr, d_mask, mask_images});
 }
 int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W, void* d_out, rrv_image_desc out,
                               int flags, void* hip_stream) {
@@ -3002,6 +3051,61 @@ int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int 
     if (!h) return RRV_E_ARG;
     if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
     return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, out_yuv(layout), ns, /* wts */ nullptr, mask, mask_images});
+}
+
+// 8-bit YUV 4:2:0 input of the host entries (conv_first_k<IN_YUV_*>): frame b at b * (H*W + 2*CH*CW) bytes of `frames`; `out` as float32 or
+// uint8 HWC BGR PIXEL frames or as I420 / NV12.  The staging, the zero-copy path and the copy pool size a frame by Xfer::in_bytes.
+static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, void* out, rrv_image_desc od, int flags, int known_flags, Xfer x) {
+    if (!h) return RRV_E_ARG;
+    int form;
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (flags & ~known_flags) return fail(h, RRV_E_ARG, "transfer_from_yuv: unknown flags");
+    if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
+    const bool yuv = yuv_layout(od.layout);
+    if ((od.dtype != RRV_DT_U8 && od.dtype != RRV_DT_F32) || (!yuv && od.layout != RRV_LAY_HWC_BGR) || od.space != RRV_SP_PIXEL || (yuv && od.dtype != RRV_DT_U8))
+        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, or uint8 I420 / NV12");
+    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
+    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
+    x.fmt = yuv ? out_yuv(od.layout) : (od.dtype == RRV_DT_U8 ? OUT_U8 : OUT_F32);
+    InFormScope in_scope(h, form, SP_PIXEL);
+    return host_pipeline(h, frames, out, x);
+}
+int rrv_transfer_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, void* out, rrv_image_desc od, int flags) {
+    return from_yuv_host(h, frames, in_layout, out, od, flags, RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE, Xfer{Model::GLOBAL, B, H, W});
+}
+int rrv_transfer_blend_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, const float* wts, int ns, void* out,
+                                rrv_image_desc od, int flags) {
+    return from_yuv_host(h, frames, in_layout, out, od, flags, RRV_TF_PAD_CROP, Xfer{Model::BLEND, B, H, W, PLAIN, OUT_F32, ns, wts});
+}
+int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, const float* mask, int ns, int mask_images,
+                               void* out, rrv_image_desc od, int flags) {
+    return from_yuv_host(h, frames, in_layout, out, od, flags, RRV_TF_PAD_CROP, Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, ns, /* wts */ nullptr, mask, mask_images});
+}
+
+// The matrix of the YUV input forms, the inverse of rrv_yuv_matrix's transform: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y,
+// C' = C - 128), R = Y' + 2(1-Kr) Cr', B = Y' + 2(1-Kb) Cb', G = Y' - (2 Kb (1-Kb) / Kg) Cb' - (2 Kr (1-Kr) / Kg) Cr'; the offsets folded into
+// column 3.  Coefficients in double, each rounded once to float32.
+int rrv_yuv_input_matrix(int standard, int full_range, float n[12]) {
+    if (!n || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709)) return RRV_E_ARG;
+    const double kr = standard == RRV_YUV_BT601 ? 0.299 : 0.2126, kb = standard == RRV_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double ys = full_range ? 1.0 : 255.0 / 219.0, cs = full_range ? 1.0 : 255.0 / 224.0, y0 = full_range ? 0.0 : 16.0;
+    const double cb[3] = {0.0, -(2.0 * kb * (1.0 - kb) / kg), 2.0 * (1.0 - kb)}, cr[3] = {2.0 * (1.0 - kr), -(2.0 * kr * (1.0 - kr) / kg), 0.0};
+    for (int k = 0; k < 3; ++k) {
+        n[4 * k] = (float)ys;
+        n[4 * k + 1] = (float)(cs * cb[k]);
+        n[4 * k + 2] = (float)(cs * cr[k]);
+        n[4 * k + 3] = (float)(-(ys * y0) - 128.0 * (cs * cb[k]) - 128.0 * (cs * cr[k]));
+    }
+    return RRV_OK;
+}
+// handle state, independent of the output matrix, read when conv_first_k is launched
+int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]) {
+    if (!h) return RRV_E_ARG;
+    if (!n) return rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in_m);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(n[i])) return fail(h, RRV_E_ARG, "set_yuv_input_matrix: the twelve coefficients must be finite");
+    memcpy(h->yuv_in_m, n, sizeof h->yuv_in_m);
+    return RRV_OK;
 }
 
 // The conversion matrix of the YUV forms: Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited

@@ -2,6 +2,7 @@
 
     python -m rerevst-code_amd.driver --style style.jpg --frames 'video/*.png' --checkpoint style_net-TIP-final.pth \
            --out result_frames/name [--video result.avi | result.y4m] [--fps 24] [--no-frames] [--no-global]
+    python -m rerevst-code_amd.driver --style style.jpg --frames in.y4m --checkpoint ... --out dir --video out.y4m --no-frames
 
 Reads the style image and the content frames (PNG / JPEG, through Pillow; BGR uint8 arrays as cv2.imread gives the
 reference), runs prepare_style / clean / add (every 8th frame + the last, :129-143) / compute, stylizes every frame with
@@ -9,6 +10,8 @@ pad + crop on the device (`Stylization.transfer_frames`), writes the stylized fr
 (saturating float -> uint8 as cv2.imwrite does, :170-171) and optionally a Motion-JPEG AVI (:175-186) or, for a target that ends
 in .y4m, an uncompressed YUV4MPEG2 stream (8-bit 4:2:0) that any encoder reads.  With --no-frames only the video is written; a
 .y4m then receives the I420 bytes the GPU converted (`transfer_frames(out_format="i420")`): no image codec on the output side.
+--frames in.y4m reads a YUV4MPEG2 file instead of image files (Y4MReader): its I420 frames go to the GPU unchanged
+(`in_format="i420"`), so .y4m -> .y4m touches no pixel on the host.
 
 Differences from the reference script, on purpose: the frame list is sorted (the reference's comment asks for it, its
 code forgets the sort()); image decoding / encoding is Pillow's, not OpenCV's (neither is part of the measured path).
@@ -132,6 +135,8 @@ def fps_fraction(fps):
     """A frame rate as the fraction a Y4M header wants: 24 -> (24, 1), 23.976 -> (24000, 1001) (the NTSC rates), else the nearest
     fraction with a denominator up to 1000."""
     from fractions import Fraction
+    if isinstance(fps, (tuple, list)):             # already a fraction (a Y4M input's own rate)
+        return int(fps[0]), int(fps[1])
     fps = float(fps)
     if abs(fps - round(fps)) < 1e-9:
         return int(round(fps)), 1
@@ -193,6 +198,105 @@ def read_y4m(path):
                 raise ValueError("%s: truncated frame" % path)
             frames.append(data)
     return fields, frames
+
+
+class Y4MReader:
+    """Streaming reader of a YUV4MPEG2 file with 8-bit 4:2:0 frames (what Y4MWriter, `ffmpeg -pix_fmt yuv420p out.y4m` and every
+    decoder's command line write).  The header gives width, height, fps = (num, den) (None without an F tag), interlace, aspect,
+    colorspace and full_range (XCOLORRANGE=FULL); C420jpeg, C420mpeg2, C420paldv, C420 or no C tag are read — the frames are I420
+    bytes either way, the tag only names the chroma siting — and every other colour space is refused by name.  The frame offsets are
+    indexed once (FRAME lines may carry parameters: frame_params), so frames are read in any order, one or a run at a time, never
+    the whole file.  A last frame shorter than frame_bytes is an error."""
+
+    COLORSPACES = (b"420jpeg", b"420mpeg2", b"420paldv", b"420")
+
+    def __init__(self, path):
+        self.path = path
+        self.f = open(path, "rb")
+        try:
+            self._parse()
+        except Exception:
+            self.f.close()
+            raise
+
+    def _parse(self):
+        f, path = self.f, self.path
+        head = f.readline(4096)
+        if not head.startswith(b"YUV4MPEG2") or not head.endswith(b"\n"):
+            raise ValueError("%s is not a YUV4MPEG2 file" % path)
+        self.fields = [k for k in head[:-1].split(b" ")[1:] if k]
+        self.width = self.height = 0
+        self.fps, self.interlace, self.aspect, self.colorspace, self.full_range = None, None, None, None, False
+        for k in self.fields:
+            tag, val = k[:1], k[1:]
+            if tag == b"W":
+                self.width = int(val)
+            elif tag == b"H":
+                self.height = int(val)
+            elif tag == b"F":
+                num, den = val.split(b":")
+                self.fps = (int(num), int(den))
+            elif tag == b"I":
+                self.interlace = val.decode()
+            elif tag == b"A":
+                self.aspect = val.decode()
+            elif tag == b"C":
+                self.colorspace = val.decode()
+                if val not in self.COLORSPACES:
+                    raise ValueError("%s: colour space C%s is not supported (8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420paldv, C420)"
+                                     % (path, val.decode()))
+            elif k.startswith(b"XCOLORRANGE="):
+                self.full_range = val[len(b"COLORRANGE="):] == b"FULL"
+        if self.width < 1 or self.height < 1:
+            raise ValueError("%s: the header names no frame size" % path)
+        if self.fps is not None and (self.fps[0] < 1 or self.fps[1] < 1):
+            self.fps = None                         # F0:0 = unknown
+        self.frame_bytes = self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
+        size = os.fstat(f.fileno()).st_size
+        self.offsets, self.frame_params = [], []
+        pos = f.tell()
+        while pos < size:
+            f.seek(pos)
+            line = f.readline(4096)
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n") or line[5:6] not in (b" ", b"\n"):
+                raise ValueError("%s: expected a FRAME line at byte %d, got %r" % (path, pos, line[:16]))
+            self.frame_params.append([k for k in line[5:-1].split(b" ") if k])
+            pos += len(line)
+            if pos + self.frame_bytes > size:
+                raise ValueError("%s: truncated frame %d (%d of %d bytes)" % (path, len(self.offsets), size - pos, self.frame_bytes))
+            self.offsets.append(pos)
+            pos += self.frame_bytes
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def read_into(self, i, dst):
+        """Frame i into `dst`, a writable C-contiguous uint8 buffer of frame_bytes."""
+        view = memoryview(dst).cast("B")
+        if view.nbytes != self.frame_bytes:
+            raise ValueError("a frame has %d bytes, the buffer %d" % (self.frame_bytes, view.nbytes))
+        self.f.seek(self.offsets[i])
+        if self.f.readinto(view) != self.frame_bytes:
+            raise ValueError("%s: truncated frame %d" % (self.path, i))
+
+    def read(self, i):
+        out = np.empty(self.frame_bytes, np.uint8)
+        self.read_into(i, out)
+        return out
+
+    def read_run(self, i0, dst):
+        """Frames i0 .. i0 + len(dst) - 1 into the rows of `dst`, uint8 [m][frame_bytes]."""
+        for j in range(len(dst)):
+            self.read_into(i0 + j, dst[j])
+
+    def close(self):
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def is_y4m(video_path):
@@ -453,6 +557,114 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     return written
 
 
+def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
+                yuv=("bt601", False), io_threads=None):
+    """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
+    in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
+    `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
+    write_frames=False: transfer_frames(in_format="i420", out_format="i420"), the output bytes appended unchanged (matrix `yuv`); with
+    image files the chunk's frames are written as stylize_files writes them, named frame_%06d.png (io_threads encode workers, as in
+    stylize_files); any other video_path is the Motion-JPEG AVI.  One rank; returns the paths written."""
+    import importlib
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    video = importlib.import_module("rerevst-code_amd.video")
+    if getattr(model, "yuv_input", False) is not True:
+        raise ValueError("a .y4m input needs a model that reads YUV frames (Stylization.yuv_input)")
+    if not write_frames and video_path is None:
+        raise ValueError("write_frames=False needs a video_path: nothing would be written")
+    if write_frames:
+        os.makedirs(out_dir, exist_ok=True)
+    nthreads = int(io_threads or default_io_threads())
+    with Y4MReader(y4m_path) as reader, ThreadPoolExecutor(nthreads) as pool, ThreadPoolExecutor(1) as rpool, ThreadPoolExecutor(1) as vpool:
+        n, H, W, fb = len(reader), reader.height, reader.width, reader.frame_bytes
+        if n < 1:
+            raise ValueError("%s holds no frame" % y4m_path)
+        y4m = is_y4m(video_path)
+        if fps is None:                          # the file's rate: the exact fraction for a Y4M header, a float for the AVI muxer
+            fps = 24 if reader.fps is None else reader.fps if y4m else reader.fps[0] / reader.fps[1]
+        size = (H, W)
+        encode, open_writer = video_sink(video_path, fps, yuv) if video_path is not None else (None, None)
+        t_start = time.perf_counter()
+        model.set_yuv_input_matrix(yuv[0], reader.full_range)
+        model.prepare_style(read_image_bgr(style_path))
+        if getattr(model, "use_Global", True):
+            ids = video.sample_indices(n)
+            log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
+            model.clean()
+            for i in ids:
+                model.add(reader.read(i), in_format="i420", size=size)
+            model.compute()
+        t_prep = time.perf_counter()
+        direct = y4m and not write_frames
+        if direct:
+            model.set_yuv_matrix(*yuv)
+        out_dtype = np.uint8 if uint8_output(model) and not y4m else np.float32
+        pkg_empty = getattr(importlib.import_module("rerevst-code_amd"), "pinned_empty", None)
+        nbuf = 3
+        chunk = max(1, min(int(chunk), n))
+        in_buf = [_host_buffer(pkg_empty, (chunk, fb), np.uint8) for _ in range(nbuf)]
+        out_buf = [_host_buffer(pkg_empty, (chunk, fb) if direct else (chunk, H, W, 3), np.uint8 if direct else out_dtype) for _ in range(nbuf)]
+        starts = list(range(0, n, chunk))
+        written, writer, gpu_s = [], None, 0.0
+
+        def append_frames(items):                # the one video thread: frames in order, (bytes, shape) each
+            nonlocal writer
+            for data, shape in items:
+                if writer is None:
+                    writer = open_writer(shape)
+                writer.append(data, shape)
+
+        def save(path, img):
+            u8 = to_uint8(img)
+            if write_frames:
+                write_image_bgr(path, u8)
+            return encode(img if y4m else u8) if video_path is not None else None
+
+        def fetch(k):                            # the one reader thread: chunk k into input buffer k % nbuf
+            m = min(chunk, n - starts[k])
+            reader.read_run(starts[k], in_buf[k % nbuf][:m])
+            return m
+        ahead = {0: rpool.submit(fetch, 0)}
+        busy = [[] for _ in range(nbuf)]         # output buffer -> futures still reading it
+        for k, c0 in enumerate(starts):
+            m = ahead.pop(k).result()
+            if k + 1 < len(starts):
+                ahead[k + 1] = rpool.submit(fetch, k + 1)      # (buffer (k+1) % nbuf was chunk k-2's input: consumed)
+            for f in busy[k % nbuf]:
+                f.result()
+            src, dst = in_buf[k % nbuf][:m], out_buf[k % nbuf][:m]
+            t0 = time.perf_counter()
+            if direct:
+                styled = model.transfer_frames(src, out=dst, out_format="i420", in_format="i420", size=size)
+            else:
+                styled = model.transfer_frames(src, out=dst, in_format="i420", size=size)
+            gpu_s += time.perf_counter() - t0
+            if direct:
+                busy[k % nbuf] = [vpool.submit(append_frames, [(fr, (H, W)) for fr in styled])]
+            else:
+                futs = []
+                for j in range(m):
+                    out_path = os.path.join(out_dir, "frame_%06d.png" % (c0 + j))
+                    futs.append(pool.submit(save, out_path, styled[j]))
+                    if write_frames:
+                        written.append(out_path)
+                if video_path is not None:       # encoded on the workers, appended in order by the video thread
+                    futs.append(vpool.submit(lambda fs: append_frames([f.result() for f in fs]), list(futs)))
+                busy[k % nbuf] = futs
+            log("stylized frames %d..%d of %d" % (c0, c0 + m - 1, n))
+        for fl in busy:
+            for f in fl:
+                f.result()
+        if writer is not None:
+            writer.release()
+        t_frames = time.perf_counter()
+    if stats is not None:
+        stats.update(prep_s=t_prep - t_start, frames=n, frames_s=t_frames - t_prep, gpu_call_s=gpu_s, io_threads=nthreads,
+                     frames_per_s=n / max(t_frames - t_prep, 1e-9))
+    return written
+
+
 def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_path=None, fps=24, chunk=16, style_size=(384, 384), log=print,
                              io_threads=None, write_frames=True, yuv=("bt601", False)):
     """"Multi-style Interpolation/test.py" on files (VideoStylization :40-111 + the loop :114-131): styles resized to
@@ -569,15 +781,15 @@ def main(argv=None, model_factory=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--style", required=True, nargs="+", help="one style image, or several for multi-style interpolation")
-    ap.add_argument("--frames", required=True, help="glob pattern of the content frames")
+    ap.add_argument("--frames", required=True, help="glob pattern of the content frames, or one .y4m file (8-bit 4:2:0), read by the GPU as it is")
     ap.add_argument("--checkpoint", required=True, help="style_net-TIP-final.pth (or 'synthetic' for seeded weights)")
     ap.add_argument("--out", required=True, help="directory for the stylized frames")
     ap.add_argument("--video", default=None, help="also write a video here: Motion-JPEG for .avi, uncompressed YUV4MPEG2 (8-bit 4:2:0) for .y4m")
     ap.add_argument("--no-frames", action="store_true", help="write no image files, only --video (one GPU); a .y4m then takes the I420 bytes "
                     "converted on the GPU")
-    ap.add_argument("--yuv", choices=("bt601", "bt709"), default="bt601", help="colour matrix of a .y4m video")
+    ap.add_argument("--yuv", choices=("bt601", "bt709"), default="bt601", help="colour matrix of a .y4m video, written and read")
     ap.add_argument("--full-range", action="store_true", help="full-range (0..255) Y4M instead of limited range (16..235 / 16..240)")
-    ap.add_argument("--fps", type=float, default=24)
+    ap.add_argument("--fps", type=float, default=None, help="frame rate of --video (default: 24, or the rate of a .y4m input)")
     ap.add_argument("--no-global", action="store_true", help="per-frame statistics (use_Global=False)")
     ap.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK, else 0)")
     ap.add_argument("--gpus", type=int, default=1, help="shard the frames over N GPUs of this node: one process per GPU, one broadcast of the "
@@ -589,6 +801,13 @@ def main(argv=None, model_factory=None):
         ap.error("--no-frames needs --video: nothing would be written")
     if args.no_frames and args.gpus > 1:
         ap.error("--no-frames runs on one GPU: the ranks' frames reach the video through their files")
+    y4m_in = is_y4m(args.frames)
+    if y4m_in and args.gpus > 1:
+        ap.error("--gpus N with a .y4m input is not supported: a .y4m is stylized on one GPU")
+    if y4m_in and len(args.style) > 1:
+        ap.error("multi-style interpolation with a .y4m input is not supported: the cached-feature entries read image files")
+    if not y4m_in and args.fps is None:
+        args.fps = 24
     for sp in args.style:
         if not os.path.exists(sp):
             sys.exit("Style image %s not exists" % sp)                # generate_real_video.py:93-94, test.py:51-52
@@ -631,16 +850,19 @@ def main(argv=None, model_factory=None):
     log = print if rank == 0 else (lambda *a, **k: None)
     stats = {}
     t0 = time.perf_counter()
-    if len(args.style) > 1:
+    if y4m_in:
+        stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
+                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None)
+    elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range))
     else:
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
                       write_frames=not args.no_frames, yuv=(args.yuv, args.full_range))
-        if stats:
-            print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
-                  % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)
+    if stats:
+        print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
+              % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)
     if hasattr(model, "close"):
         model.close()
     if world > 1:

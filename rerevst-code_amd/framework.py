@@ -154,6 +154,43 @@ def yuv_matrix(standard="bt601", full_range=False):
     return m
 
 
+def yuv_input_matrix(standard="bt601", full_range=False):
+    """rrv_yuv_input_matrix: the float32 [3][4] matrix (rows R, G, B; columns Y, Cb, Cr, offset) that reads 8-bit YUV of a standard and
+    range, the inverse of yuv_matrix's transform; needs no GPU."""
+    if standard not in _YUV_STANDARDS:
+        raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
+    n = np.empty((3, 4), np.float32)
+    if _lib.load().rrv_yuv_input_matrix(_YUV_STANDARDS[standard], int(bool(full_range)), n.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("rrv_yuv_input_matrix refused %r" % (standard,))
+    return n
+
+
+def _yuv_size(in_format, size):
+    if in_format not in _YUV_LAYOUTS:
+        raise ValueError("in_format must be 'bgr', 'i420' or 'nv12', got %r" % (in_format,))
+    if size is None or len(size) != 2:
+        raise ValueError("%r frames need size=(H, W): the buffer does not carry it" % (in_format,))
+    H, W = int(size[0]), int(size[1])
+    if H < 8 or W < 8:
+        raise ValueError("frames must be at least 8 x 8 pixels, got %d x %d" % (H, W))
+    return H, W
+
+
+def yuv_frames_args(frames, in_format, size):
+    """Check 8-bit YUV 4:2:0 input frames (transfer_batch / transfer_frames / add with in_format "i420" | "nv12") without touching the
+    GPU: `frames` is a uint8 array [B][yuv_frame_bytes(H, W)] (or a list of [yuv_frame_bytes] arrays, or one such array) for
+    size=(H, W).  Returns (C-contiguous uint8 [B][frame_bytes], H, W); raises ValueError for a missing size, another dtype or a
+    wrong byte count."""
+    H, W = _yuv_size(in_format, size)
+    a = np.asarray(frames) if isinstance(frames, np.ndarray) else np.stack([np.asarray(f) for f in frames])
+    if a.ndim == 1:
+        a = a[None]
+    fb = yuv_frame_bytes(H, W)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != fb:
+        raise ValueError("%r frames of %d x %d are uint8 [B][%d], got %s %s" % (in_format, H, W, fb, a.dtype, a.shape))
+    return np.ascontiguousarray(a), H, W
+
+
 # ===== torch tensors (rrv_transfer_image_device) =====
 _SPACES = {"pixel": _lib.SP_PIXEL, "unit": _lib.SP_UNIT, "norm": _lib.SP_NORM}
 _LAYOUTS = {"nhwc": _lib.LAY_HWC_BGR, "nchw": _lib.LAY_CHW_RGB}     # nhwc: BGR (cv2's convention), nchw: RGB (torch's)
@@ -164,39 +201,69 @@ TENSOR_BATCH_MAX = 64        # images per rrv_transfer_image_device call; transf
 TensorIO = collections.namedtuple("TensorIO", "x in_desc out_desc out_shape out_dtype B H W batched")
 
 
+def _on_device(t, what, device):
+    if t.device.type != "cuda" or t.device.index != int(device):
+        raise ValueError("%s must be a tensor on cuda:%d (the handle's device), got %s" % (what, int(device), t.device))
+
+
+def _image_desc(dtype, sp, lay, what):
+    import torch
+    if dtype == torch.uint8:
+        if sp != "pixel":
+            raise ValueError("%s: uint8 images are in the 'pixel' space (0..255), not %r" % (what, sp))
+        dt = _lib.DT_U8
+    elif dtype == torch.float32:
+        dt = _lib.DT_F32
+    else:
+        raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
+    return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else _YUV_LAYOUTS[lay], _SPACES[sp])
+
+
+def _check_out_layout(out_layout, out_space):
+    """the output side of both tensor_io_args forms, before the input is looked at: True for an 'i420' / 'nv12' output"""
+    if out_space not in _SPACES:
+        raise ValueError("out_space must be one of %s, got %r" % (sorted(_SPACES), out_space))
+    yuv = out_layout in _YUV_LAYOUTS         # uint8 [B][yuv_frame_bytes] in the "pixel" space
+    if out_layout not in _LAYOUTS and not yuv:
+        raise ValueError("out_layout must be 'nchw' (RGB), 'nhwc' (BGR), 'i420' or 'nv12', got %r" % (out_layout,))
+    if yuv and out_space != "pixel":
+        raise ValueError("an %r output is in the 'pixel' space, not %r" % (out_layout, out_space))
+    return yuv
+
+
+def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out):
+    """(out_desc, out_shape, out_dtype) of B stylized H x W input frames: shared by tensor_io_args and yuv_tensor_io_args"""
+    import torch
+    yuv = out_layout in _YUV_LAYOUTS
+    Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+    out_shape = (B, yuv_frame_bytes(Ho, Wo)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
+    if not batched:
+        out_shape = out_shape[1:]
+    if out is not None:
+        _on_device(out, "out", device)
+        out_dtype = out.dtype
+        if tuple(out.shape) != out_shape or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
+    out_dtype = (torch.uint8 if yuv else torch.float32) if out_dtype is None else out_dtype
+    if yuv and out_dtype != torch.uint8:
+        raise ValueError("an %r output is torch.uint8, got %s" % (out_layout, out_dtype))
+    return _image_desc(out_dtype, out_space, out_layout, "out"), out_shape, out_dtype
+
+
 def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
                    pad_crop=False, out=None):
     """Check the arguments of Stylization.transfer_tensor against a handle on HIP device `device` (an ordinal) without
     touching the GPU, and work out the call: raises ValueError for a tensor that is not on that device, a channel count
     other than 3, a dtype the space does not allow (uint8 is "pixel" only; otherwise float32), an unknown space or
     layout, or an `out` of the wrong shape, dtype, device or layout.  A non-contiguous `x` is made contiguous."""
-    import torch
-    if space not in _SPACES or out_space not in _SPACES:
-        raise ValueError("space and out_space must be one of %s, got %r / %r" % (sorted(_SPACES), space, out_space))
+    if space not in _SPACES:
+        raise ValueError("space must be one of %s, got %r" % (sorted(_SPACES), space))
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r" % (layout,))
     out_layout = layout if out_layout is None else out_layout
-    yuv = out_layout in _YUV_LAYOUTS         # an output layout only: uint8 [B][yuv_frame_bytes] in the "pixel" space
-    if layout not in _LAYOUTS or (out_layout not in _LAYOUTS and not yuv):
-        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), out_layout one of those or 'i420' / 'nv12', got %r / %r" % (layout, out_layout))
-    if yuv and out_space != "pixel":
-        raise ValueError("an %r output is in the 'pixel' space, not %r" % (out_layout, out_space))
-
-    def on_device(t, what):
-        if t.device.type != "cuda" or t.device.index != int(device):
-            raise ValueError("%s must be a tensor on cuda:%d (the handle's device), got %s" % (what, int(device), t.device))
-
-    def desc(dtype, sp, lay, what):
-        if dtype == torch.uint8:
-            if sp != "pixel":
-                raise ValueError("%s: uint8 images are in the 'pixel' space (0..255), not %r" % (what, sp))
-            dt = _lib.DT_U8
-        elif dtype == torch.float32:
-            dt = _lib.DT_F32
-        else:
-            raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
-        return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else _YUV_LAYOUTS[lay], _SPACES[sp])
-
-    on_device(x, "x")
-    in_desc = desc(x.dtype, space, layout, "x")
+    _check_out_layout(out_layout, out_space)
+    _on_device(x, "x", device)
+    in_desc = _image_desc(x.dtype, space, layout, "x")
     if x.dim() not in (3, 4):
         raise ValueError("x must be [B,3,H,W] or [3,H,W] ('nhwc': [B,H,W,3] or [H,W,3]), got shape %s" % (tuple(x.shape),))
     batched = x.dim() == 4
@@ -206,23 +273,31 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
         raise ValueError("x must have 3 channels (%s), got shape %s" % (layout, tuple(x.shape)))
     if B < 1:
         raise ValueError("x holds no image")
-    Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-    out_shape = (B, yuv_frame_bytes(Ho, Wo)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
-    if not batched:
-        out_shape = out_shape[1:]
-    if out is not None:
-        on_device(out, "out")
-        out_dtype = out.dtype
-        if tuple(out.shape) != out_shape or not out.is_contiguous():
-            raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
-    out_dtype = (torch.uint8 if yuv else torch.float32) if out_dtype is None else out_dtype
-    if yuv and out_dtype != torch.uint8:
-        raise ValueError("an %r output is torch.uint8, got %s" % (out_layout, out_dtype))
-    out_desc = desc(out_dtype, out_space, out_layout, "out")
+    out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
     if not x.is_contiguous():
         x = x.contiguous()
     return TensorIO(x=x, in_desc=in_desc, out_desc=out_desc, out_shape=out_shape, out_dtype=out_dtype, B=B, H=H, W=W,
                     batched=batched)
+
+
+def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=None, out_layout=None, pad_crop=False, out=None):
+    """tensor_io_args for an 8-bit YUV 4:2:0 input tensor (transfer_tensor(layout="i420" | "nv12", size=(H, W))): x is a uint8 tensor
+    [B][yuv_frame_bytes(H, W)] (or [yuv_frame_bytes]) on cuda:`device`; out_layout defaults to `layout` (YUV in, YUV out).  The
+    output side is tensor_io_args'.  The result's in_desc is the RRV_LAY_* value of the input layout.  Raises ValueError as
+    tensor_io_args does, and for a missing size or a wrong byte count."""
+    import torch
+    H, W = _yuv_size(layout, size)
+    out_layout = layout if out_layout is None else out_layout
+    _check_out_layout(out_layout, out_space)
+    _on_device(x, "x", device)
+    fb = yuv_frame_bytes(H, W)
+    if x.dtype != torch.uint8 or x.dim() not in (1, 2) or x.shape[-1] != fb or (x.dim() == 2 and x.shape[0] < 1):
+        raise ValueError("an %r tensor of %d x %d frames is torch.uint8 [B, %d] or [%d], got %s %s" % (layout, H, W, fb, fb, x.dtype, tuple(x.shape)))
+    batched = x.dim() == 2
+    B = x.shape[0] if batched else 1
+    out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
+    return TensorIO(x=x if x.is_contiguous() else x.contiguous(), in_desc=_YUV_LAYOUTS[layout], out_desc=out_desc, out_shape=out_shape,
+                    out_dtype=out_dtype, B=B, H=H, W=W, batched=batched)
 
 
 # the per-frame style weights of a blended call, as style_weight_args() works them out: `host` a C-contiguous float32 [B][S]
@@ -319,6 +394,9 @@ class Stylization():
     # transfer_batch / transfer_frames take out_format="i420" | "nv12" (the rrv_*_yuv entries): driver.stylize_files asks for it when
     # it writes only a .y4m video
     yuv_output = True
+    # transfer_batch / transfer_frames / add take in_format="i420" | "nv12" with size=(H, W) (the rrv_*_from_yuv entries): driver.stylize_y4m
+    # feeds a .y4m input that way
+    yuv_input = True
 
     def __init__(self, checkpoint, cuda=True, use_Global=True, device=None, style_num=1):
         if not cuda:
@@ -373,8 +451,15 @@ class Stylization():
         if not self.use_Global:   # the reference's frame-mode TransformerNet has no add/compute/clean either
             raise RRVError("%s() belongs to Sequence-Level Global Feature Sharing (use_Global=True)" % what)
 
-    def add(self, patch):
+    def add(self, patch, in_format="bgr", size=None):
+        """A sampled frame: uint8 BGR HWC, or with in_format "i420" / "nv12" and size=(H, W) 8-bit YUV 4:2:0 bytes
+        [yuv_frame_bytes(H, W)] (or [B][..]: every frame, in order) read by the first kernel (rrv_add_from_yuv)."""
         self._global_only("add")
+        if in_format != "bgr":
+            a, H, W = yuv_frames_args(patch, in_format, size)
+            for f in a:
+                self._chk(self._lib.rrv_add_from_yuv(self._h, f.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], H, W))
+            return
         a = _u8_image(patch, "patch")
         self._chk(self._lib.rrv_add(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]))
 
@@ -522,12 +607,41 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr"):
+    def _host_frames_yuv_in(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size):
+        """_host_frames for 8-bit YUV 4:2:0 input (the rrv_*_from_yuv entries): one call shape for every output format"""
+        a, H, W = yuv_frames_args(frames, in_format, size)
+        B = a.shape[0]
+        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
+        if out_format != "bgr":
+            shape = (B, yuv_frame_bytes(Ho, Wo))
+            if out is None:
+                out = _outputs.empty(shape, np.uint8)
+            elif out.dtype != np.uint8 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous uint8 array of shape %r" % (shape,))
+            desc = _lib.ImageDesc(_lib.DT_U8, _YUV_LAYOUTS[out_format], _lib.SP_PIXEL)
+        else:
+            out, u8 = _output((B, Ho, Wo, 3), dtype, out)
+            desc = _lib.ImageDesc(_lib.DT_U8 if u8 else _lib.DT_F32, _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+        head = (self._h, a.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], B, H, W)
+        tail = (out.ctypes.data_as(C.c_void_p), desc, _lib.TF_PAD_CROP if pad_crop else 0)
+        if m is not None:
+            self._chk(self._lib.rrv_transfer_mask_from_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, *tail))
+        elif style_weights is not None:
+            w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
+            self._chk(self._lib.rrv_transfer_blend_from_yuv(*head, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, *tail))
+        else:
+            self._chk(self._lib.rrv_transfer_from_yuv(*head, tail[0], desc, tail[2] | (0 if self.use_Global else _lib.TF_FRAME_MODE)))
+        return out
+
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames, the checked masks or
         weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one);
         out_format "i420" / "nv12": their _yuv forms, uint8 [B][yuv_frame_bytes] whatever `dtype` says"""
         if out_format != "bgr" and out_format not in _YUV_LAYOUTS:
             raise ValueError("out_format must be 'bgr', 'i420' or 'nv12', got %r" % (out_format,))
+        if in_format != "bgr":
+            return self._host_frames_yuv_in(frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size)
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
             a = np.ascontiguousarray(frames)
         else:
@@ -562,7 +676,7 @@ class Stylization():
         self._chk(self._entry(name, u8)(*head, *args, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr"):
+    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -574,10 +688,13 @@ class Stylization():
         over the input pixels p covers (rrv_transfer_mask_batch).  Not normalised; mutually exclusive with style_weights.
         out_format: "bgr" (default), or "i420" / "nv12": 8-bit YUV 4:2:0 converted on the GPU with the matrix of set_yuv_matrix
         (rrv_transfer_yuv and its blend / mask forms): a uint8 [B][yuv_frame_bytes(Ho, Wo)] array (`out` of that shape is
-        filled; yuv_planes() gives the planes), 1.5 bytes per pixel over PCIe; composes with style_weights / style_masks."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format)
+        filled; yuv_planes() gives the planes), 1.5 bytes per pixel over PCIe; composes with style_weights / style_masks.
+        in_format: "bgr" (default), or "i420" / "nv12" with size=(H, W): `frames` is a uint8 array [B][yuv_frame_bytes(H, W)] of 8-bit
+        YUV 4:2:0 frames, read by the first kernel with the matrix of set_yuv_input_matrix (the rrv_*_from_yuv entries): 1.5 bytes
+        per pixel in as well, and no conversion on the host.  A wrong byte count or a missing size raises ValueError."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size)
 
-    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr"):
+    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -587,8 +704,10 @@ class Stylization():
         style_masks: [B][S][H][W] (or [S][H][W]) per-pixel blend weights for the UNPADDED frames, as in transfer_batch; the
         mask is reflect-padded on the device as the frame is.
         out_format: "i420" / "nv12" as in transfer_batch: uint8 [B][yuv_frame_bytes(H, W)]; an odd H or W gives a last chroma row
-        or column that covers one pixel row / column (replicated, never the padding)."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format)
+        or column that covers one pixel row / column (replicated, never the padding).
+        in_format / size: "i420" / "nv12" input frames [B][yuv_frame_bytes(H, W)], as in transfer_batch; with out_format set too, a
+        decoder's frames go to an encoder with no pixel touched on the host."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -596,7 +715,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None, style_weights=None, style_masks=None):
+                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -615,10 +734,24 @@ class Stylization():
         or a float32 ndarray of those shapes (copied to the device on that stream).  H, W are those of x.  Mutually exclusive
         with style_weights.
         out_layout "i420" / "nv12": 8-bit YUV 4:2:0 (the matrix of set_yuv_matrix), a uint8 tensor [B, yuv_frame_bytes(Ho, Wo)]
-        ([yuv_frame_bytes] unbatched) in the "pixel" space; yuv_planes() gives views of the planes."""
+        ([yuv_frame_bytes] unbatched) in the "pixel" space; yuv_planes() gives views of the planes.
+        layout "i420" / "nv12" with size=(H, W): x is a uint8 tensor [B, yuv_frame_bytes(H, W)] of 8-bit YUV 4:2:0 frames (a hardware
+        decoder's NV12), read with the matrix of set_yuv_input_matrix (the rrv_*_from_yuv_device entries); out_layout then defaults
+        to the same YUV layout, and may be "nchw" / "nhwc"."""
         import torch
-        a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
-                           out_layout=out_layout, pad_crop=pad_crop, out=out)
+        yuv_in = layout in _YUV_LAYOUTS
+        if yuv_in:
+            if space != "pixel":
+                raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
+            a = yuv_tensor_io_args(x, self.device, layout, size, out_space=out_space, out_dtype=out_dtype, out_layout=out_layout,
+                                   pad_crop=pad_crop, out=out)
+        else:
+            a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
+                               out_layout=out_layout, pad_crop=pad_crop, out=out)
+        mask_fn, blend_fn, plain_fn = ((self._lib.rrv_transfer_mask_from_yuv_device, self._lib.rrv_transfer_blend_from_yuv_device,
+                                        self._lib.rrv_transfer_from_yuv_device) if yuv_in else
+                                       (self._lib.rrv_transfer_image_mask_device, self._lib.rrv_transfer_image_blend_device,
+                                        self._lib.rrv_transfer_image_device))
         w = m = None
         if style_masks is not None:
             m = style_mask_args(style_masks, style_weights, a.B, a.H, a.W, self.style_num, self.device, self.use_Global, tensors=True)
@@ -637,18 +770,18 @@ class Stylization():
             nb = min(TENSOR_BATCH_MAX, a.B - b0)
             if m is not None:
                 mp = md.data_ptr() if m.images == 1 else md[b0].data_ptr()
-                self._chk(self._lib.rrv_transfer_image_mask_device(
+                self._chk(mask_fn(
                     self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb,
                     C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
                 continue
             if w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
                 wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
-                self._chk(self._lib.rrv_transfer_image_blend_device(
+                self._chk(blend_fn(
                     self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(wp), w.S, C.c_void_p(ob[b0].data_ptr()),
                     a.out_desc, flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
                 continue
-            self._chk(self._lib.rrv_transfer_image_device(self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W,
-                                                          C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
+            self._chk(plain_fn(self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W,
+                               C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
         return out
 
     def sync(self):
@@ -715,6 +848,20 @@ class Stylization():
             raise ValueError("a YUV matrix has 12 coefficients, got %d" % m.size)
         self._chk(self._lib.rrv_set_yuv_matrix(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
         return m.reshape(3, 4).copy()
+
+    def set_yuv_input_matrix(self, standard="bt601", full_range=False):
+        """The conversion matrix of the "i420" / "nv12" INPUTS (rrv_set_yuv_input_matrix): a standard ("bt601" | "bt709") and range,
+        or twelve finite floats ([3][4]: rows R, G, B; columns Y, Cb, Cr, offset) in place of `standard`; None restores the default,
+        BT.601 limited range.  Independent of set_yuv_matrix; read when a call launches its first kernel.  Returns the float32
+        [3][4] matrix now installed."""
+        if standard is None:
+            self._chk(self._lib.rrv_set_yuv_input_matrix(self._h, None))
+            return yuv_input_matrix("bt601", False)
+        n = yuv_input_matrix(standard, full_range) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
+        if n.size != 12:
+            raise ValueError("a YUV matrix has 12 coefficients, got %d" % n.size)
+        self._chk(self._lib.rrv_set_yuv_input_matrix(self._h, n.ctypes.data_as(C.POINTER(C.c_float))))
+        return n.reshape(3, 4).copy()
 
     def set_host_io(self, mode):
         """0 (default): staged H2D / D2H copies; 1: zero copy — kernels read / write page-locked host memory directly."""

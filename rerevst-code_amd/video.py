@@ -138,6 +138,50 @@ def bgr_to_yuv420(img, m, layout="i420"):
     return np.concatenate(planes, axis=-1)
 
 
+def yuv_input_matrix(standard="bt601", full_range=False):
+    """rrv_yuv_input_matrix on the host, the inverse of yuv_matrix's transform: float32 [3][4], rows R, G, B, columns the coefficients
+    of Y, Cb, Cr and an offset.  Limited range: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y, C' = C - 128);
+    R = Y' + 2(1-Kr) Cr', B = Y' + 2(1-Kb) Cb', G = Y' - (2 Kb (1-Kb) / Kg) Cb' - (2 Kr (1-Kr) / Kg) Cr', the offsets folded into column 3.
+    Evaluated in double, each coefficient rounded once to float32."""
+    kr, kb = YUV_STANDARDS[standard]
+    kg = 1.0 - kr - kb
+    ys, cs, y0 = (1.0, 1.0, 0.0) if full_range else (255.0 / 219.0, 255.0 / 224.0, 16.0)
+    cb = (0.0, -(2.0 * kb * (1.0 - kb) / kg), 2.0 * (1.0 - kb))
+    cr = (2.0 * (1.0 - kr), -(2.0 * kr * (1.0 - kr) / kg), 0.0)
+    n = np.zeros((3, 4), np.float64)
+    for k in range(3):
+        n[k] = (ys, cs * cb[k], cs * cr[k], -(ys * y0) - 128.0 * (cs * cb[k]) - 128.0 * (cs * cr[k]))
+    return n.astype(np.float32)
+
+
+def yuv420_to_bgr(buf, H, W, n, layout="i420"):
+    """The GPU's YUV 4:2:0 input conversion (include/rerevst_hip.h, the rrv_*_from_yuv entries) in numpy float32: buf uint8
+    [..][yuv_frame_bytes(H, W)] in "i420" or "nv12", n the twelve floats of the input matrix; returns float32 [..][H][W][3] BGR, the PIXEL
+    frame the first kernel sees.  Pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1); every product and sum is a
+    float32 operation in the kernel's order; the value is clamped to 0..255 and not rounded."""
+    if layout not in ("i420", "nv12"):
+        raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    buf = np.asarray(buf)
+    if buf.dtype != np.uint8 or buf.shape[-1] != yuv_frame_bytes(H, W):
+        raise ValueError("a %d x %d %s frame is %d uint8 bytes, got %s %s" % (H, W, layout, yuv_frame_bytes(H, W), buf.dtype, buf.shape))
+    n = np.asarray(n, np.float32).reshape(3, 4)
+    lead = buf.shape[:-1]
+    CH, CW = (H + 1) // 2, (W + 1) // 2
+    y = buf[..., :H * W].reshape(lead + (H, W)).astype(np.float32)
+    if layout == "i420":
+        cb = buf[..., H * W:H * W + CH * CW].reshape(lead + (CH, CW))
+        cr = buf[..., H * W + CH * CW:].reshape(lead + (CH, CW))
+    else:
+        pairs = buf[..., H * W:].reshape(lead + (CH, CW, 2))
+        cb, cr = pairs[..., 0], pairs[..., 1]
+    rows, cols = np.arange(H) >> 1, np.arange(W) >> 1
+    cb = cb[..., rows, :][..., cols].astype(np.float32)
+    cr = cr[..., rows, :][..., cols].astype(np.float32)
+    zero, top = np.float32(0), np.float32(255)
+    rgb = [np.minimum(np.maximum(((n[k, 0] * y + n[k, 1] * cb) + n[k, 2] * cr) + n[k, 3], zero), top) for k in range(3)]
+    return np.stack(rgb[::-1], axis=-1)
+
+
 def shard_range(frame_num, rank, world):
     """Contiguous block of frames owned by `rank`."""
     lo = frame_num * rank // world
