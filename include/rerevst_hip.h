@@ -488,10 +488,13 @@ int rrv_set_host_io(rrv_handle h, int mode);
 int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float* host, size_t cap, size_t* floats);
 
 /* Layer-parity tap: as rrv_debug_copy_tensor, for image `image` of the plan, with indices 23..32 the channel-chunk-major
- * twins q11 q1 q21 q2 q31 q32 q33 (encoder) and qa4 qa3 qa2 (ResidualBlock.conv1 outputs).  *layout = 0: ring-layout NHWC
- * [H'+2][W'+2][C]; 1: "P8" [C/8][H'+2][W'+8][8], pixel x at stored column x + 4.  *channels = C.  RRV_E_STATE when the
- * most recent launch on that workspace plan did not write the tensor for that image (stale data, the other layout), so
- * a caller never reads stale data. */
+ * twins q11 q1 q21 q2 q31 q32 q33 (encoder) and qa4 qa3 qa2 (ResidualBlock.conv1 outputs), and indices 33..36 the level
+ * masks of a masked multi-style launch at stride 1, 2, 4, 8 of the network's frame: RRV_MAX_STYLES-channel ring-layout
+ * tensors, row y + 1 holding the w * S weights of that row's pixels (S innermost) from its first interior pixel on, every
+ * other float 0.  *layout = 0: ring-layout NHWC [H'+2][W'+2][C]; 1: "P8" [C/8][H'+2][W'+8][8], pixel x at stored column
+ * x + 4.  *channels = C.  RRV_E_STATE when the most recent launch on that workspace plan did not write the tensor for that
+ * image (stale data, the other layout, a level mask after a launch without masks, image 1.. of a launch with one mask for
+ * every image), so a caller never reads stale data. */
 int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
                              int* layout, int* channels);
 

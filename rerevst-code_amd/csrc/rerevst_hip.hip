@@ -3607,10 +3607,11 @@ int rrv_set_host_io(rrv_handle h, int mode) {
     return RRV_OK;
 }
 
-// Debug tap `index` -> its row in ENC_T (enc) or DEC_T: 0..8 encoder, 9..22 decoder, 23..29 encoder twins, 30..32 decoder twins
+// Debug tap `index` -> its row in ENC_T (enc) or DEC_T: 0..8 encoder, 9..22 decoder, 23..29 encoder twins, 30..32 decoder twins,
+// 33..36 the level masks lm[0..3] (the TS_MASK rows, behind the three TS_FRAME rows, which have no tap)
 static int tap_row(int index, bool& enc) {
     enc = index < 9 || (index >= 23 && index < 30);
-    return index < 9 ? index : index < 23 ? index - 9 : index < 30 ? index - 14 : index - 16;
+    return index < 9 ? index : index < 23 ? index - 9 : index < 30 ? index - 14 : index < 33 ? index - 16 : index - 13;
 }
 
 // Debugging aid (race hunting, tools/device_stream_stress.py): copy activation tensor `index` of workspace slot `slot`
@@ -3634,11 +3635,13 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
 }
 
 // Layer-parity tap: tensor `index` (0..22 as above, 23..32 the channel-chunk-major twins q11 q1 q21 q2 q31 q32 q33 qa4 qa3
-// qa2) of image `image`, as stored.  *layout = 0: ring-layout NHWC [H+2][W+2][C]; 1: P8 [C/8][H+2][W+8][8] (conv_f43.h LAY).
-// Refused (RRV_E_STATE) unless the most recent launch on that plan wrote the tensor for that image.
+// qa2, 33..36 the level masks of a masked multi-style launch at stride 1, 2, 4, 8: mask_kernels.h LevelMask) of image `image`,
+// as stored.  *layout = 0: ring-layout NHWC [H+2][W+2][C]; 1: P8 [C/8][H+2][W+8][8] (conv_f43.h LAY).
+// Refused (RRV_E_STATE) unless the most recent launch on that plan wrote the tensor for that image (a level mask: a masked
+// launch, and image 0 only when it had one mask for every image).
 int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H, int W, float* host, size_t cap, size_t* floats,
                              int* layout, int* channels) {
-    if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 32 || image < 0 || !floats) return RRV_E_ARG;
+    if (!h || slot < 0 || slot >= RRV_MAX_SLOTS || index < 0 || index > 36 || image < 0 || !floats) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     bool enc;

@@ -812,8 +812,9 @@ class Stylization():
         return out
 
     def debug_tensor_ex(self, slot, index, H, W, image=0):
-        """Tensor `index` (0..32: 23..32 the channel-chunk-major twins) of image `image` of the last launch on workspace slot
-        `slot` for H x W frames (rrv_debug_copy_tensor_ex): (flat float32 as stored, layout 0 NHWC ring / 1 P8, channels)."""
+        """Tensor `index` (0..36: 23..32 the channel-chunk-major twins, 33..36 the four level masks of a masked launch, stride 1,
+        2, 4, 8) of image `image` of the last launch on workspace slot `slot` for H x W frames (rrv_debug_copy_tensor_ex):
+        (flat float32 as stored, layout 0 NHWC ring / 1 P8, channels)."""
         n, lay, ch = C.c_size_t(0), C.c_int(0), C.c_int(0)
         args = (self._h, int(slot), int(index), int(image), int(H), int(W))
         self._chk(self._lib.rrv_debug_copy_tensor_ex(*args, None, 0, C.byref(n), C.byref(lay), C.byref(ch)))

@@ -47,7 +47,7 @@ import torch.nn.functional as TF
 
 U = 2.0 ** -24
 
-FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred")
+FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "mnorm", "mfilt")
 
 # max |gpu - ref| / (2^-24 m) per family, over every tap and shape of tests/test_gpu_layers.py on an MI355X (the worst tap):
 #   direct  30.7  c11 (conv_first: the grey fold multiplies 1/std into the weights, so its rounding is relative to the
@@ -66,15 +66,23 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred")
 #   point    3.73 a3 at 640 x 640 (the whole error of the tap over the pointwise result's magnitude; a taps 3.6 .. 3.7, c41
 #                 3.2, o taps 1.2 .. 1.7)
 #   pred     1.21 Filter1.F1 at 8 x 8 (one pixel; every other shape 0.05 .. 0.19)
-MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21}
+# and the two families of the masked multi-style walk (tests/mask_layer_ref.py, every case of tests/test_gpu_mask_layers.py):
+#   mnorm    3.64 a2, image 15 of 16 x 136 x 200 at S = 4 (mask_norm_k, the whole error of the tap over the pass's own
+#                 magnitude, as `point`; a taps 1.9 .. 3.7, f3 2.6, o taps 0.9 .. 1.2)
+#   mfilt    0.314 d, image 7 of 16 x 136 x 200 at S = 4 (mask_filter_k alone against its own split-K slices; m carries
+#                 |F2|(p) |F1|(p) (sum |slices| + |bias|))
+# measured over the cases 1 x 8 x 8 .. 16 x 136 x 200 (S = 1 .. 8); the split-4, split-1, pad / crop and host-entry cases have
+# NOT yet contributed a figure.  The convolutions stayed inside their figures: direct 28.1, f23 5.24 against its K of 8, ups 10.2
+# against its K of 19.
+MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
 # still rejecting the defects tests/test_layer_ref.py injects (the smallest of them, one weight off by 2^-8, is at 2480)
-K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5}
+K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5, "mnorm": 8.0, "mfilt": 0.7}
 
 # the tap indices of rrv_debug_copy_tensor_ex
 TAP_NAMES = ["c11", "p1", "c21", "p2", "c31", "c32", "c33", "p3", "c41",
              "d", "f1", "f2", "f3", "xs4", "a4", "o4", "xs3", "a3", "o3", "xs2", "a2", "o2", "dpart",
-             "q11", "q1", "q21", "q2", "q31", "q32", "q33", "qa4", "qa3", "qa2"]
+             "q11", "q1", "q21", "q2", "q31", "q32", "q33", "qa4", "qa3", "qa2", "lm0", "lm1", "lm2", "lm3"]
 TAP = {n: i for i, n in enumerate(TAP_NAMES)}
 TWIN = {"c11": "q11", "p1": "q1", "c21": "q21", "p2": "q2", "c31": "q31", "c32": "q32", "c33": "q33",
         "a4": "qa4", "a3": "qa3", "a2": "qa2"}

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import load_golden, assert_pre_close, IMG_ATOL, fixed_kernels
 import mask_ref
+from mask_layer_ref import mask_states, odd_edge_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -118,13 +119,36 @@ def test_constant_mask_matches_reference(pkg, weights, oracle, name):
 
 
 # ---- 2. against the model, masks that vary ----------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["vsplit", "hramp", "regions4"])
-def test_varying_masks_match_the_model(multi, pkg, net, case):
+def _smooth_odd_split(S, H, W):
+    """_smooth over S styles; beyond an edge at an odd row and column (row 27, column 13) styles 0 and 1 trade their weights"""
+    m = _smooth(5, S, H, W)
+    far = odd_edge_mask(2, H, W)[1] > 0
+    m[0], m[1] = np.where(far, m[1], m[0]), np.where(far, m[0], m[1])
+    return np.ascontiguousarray(m)
+
+
+@pytest.fixture(scope="module")
+def many(multi, pkg, weights):
+    """a handle for eight styles: the four computed states of `multi` and fixed blends of pairs of them (mask_layer_ref.mask_states)"""
+    states = mask_states([multi.get_state(k) for k in range(4)], 8)
+    s = pkg.MultiStyleStylization(weights, cuda=True, style_num=8)
+    for k, b in enumerate(states):
+        s.set_state(b, k)
+    yield s, states
+    s.close()
+
+
+@pytest.mark.parametrize("case", ["vsplit", "hramp", "regions4", "smooth3", "smooth8", "oddsplit3", "oddsplit8"])
+def test_varying_masks_match_the_model(multi, many, pkg, net, case):
     H, W = 96, 128
     frames = _mixed(pkg, 60, 3, H, W)
-    S = 4 if case == "regions4" else 2
-    states = [multi.get_state(k) for k in range(S)]
-    base = {"vsplit": _vsplit(2, H, W, 56), "hramp": _hramp(H, W), "regions4": _regions(H, W)}[case]
+    S = {"regions4": 4, "smooth3": 3, "oddsplit3": 3, "smooth8": 8, "oddsplit8": 8}.get(case, 2)
+    if S in (3, 8):         # style counts beyond the goldens': S distinct states on a handle of their own
+        multi, states = many[0], many[1][:S]
+        base = _smooth(4, S, H, W) if case.startswith("smooth") else _smooth_odd_split(S, H, W)
+    else:
+        states = [multi.get_state(k) for k in range(S)]
+        base = {"vsplit": _vsplit(2, H, W, 56), "hramp": _hramp(H, W), "regions4": _regions(H, W)}[case]
     per_frame = np.stack([base, base[:, ::-1].copy(), base[:, :, ::-1].copy()])
     # a mask per frame
     out = multi.transfer_batch(frames, style_masks=per_frame)

@@ -294,3 +294,153 @@ def test_float64_frame_stages_reproduce_the_reference_golden(pkg, weights, oracl
     assert_pre_close(taps["pre"][64:128, 64:112].astype(np.float32), load_golden("frame_mode")["pre_crop"])
     bad = {n: worst for n, _, ok, worst, _ in LR.frame_checks(taps.__getitem__, w, st, smean, CPU_FAM) if not ok}
     assert not bad, bad
+
+
+# ---- the masked multi-style walk: the references of tests/test_gpu_mask_layers.py -------------------------------------------
+
+import mask_layer_ref as MR      # noqa: E402
+import mask_ref                  # noqa: E402
+
+MK_NAMES = ("c41", "f1", "f2", "dpart", "d", "f3", "xs4", "a4", "o4", "xs3", "a3", "o3")
+MK_SPLIT = 8
+MK_STATES = ("global_a", "global_b", "global_a_seed1")
+
+
+def _mask_standin(oracle, weights, frame, blobs, M, defect=None):
+    """The masked walk up to block slice3 in the oracle's float32 arithmetic, stage by stage as the kernels run it, the split-K
+    slices included: the taps, level masks as the GPU's decoded taps.  `defect` plants one wrong step."""
+    O, w = oracle, weights
+    lv = mask_ref.level_masks(M)
+    st = [mask_ref._unpack(b) for b in (blobs[::-1] if defect == "styles blended in swapped order" else blobs)]
+    S = len(st)
+    x = O.rgb2gray(O.image_to_tensor(frame))
+    for idx in O.VGG_IDX[:-1]:
+        x = O.relu(O.conv3x3(x, w["Encoder.slice.%d.weight" % idx], w["Encoder.slice.%d.bias" % idx]))
+        if idx in O.POOL_AFTER:
+            x = O.maxpool2(x)
+    taps = {"p3": x[0]}
+    taps.update({"lm%d" % l: lv[l] for l in range(4)})
+
+    def norm(t, n, m, swap=False):
+        q = [mask_ref.blend(m, [getattr(s["norm"][n], f) for s in st]) for f in ("mean", "rstd", "lo", "hi")]
+        lo, hi = (q[3], q[2]) if swap else (q[2], q[3])
+        return np.minimum(hi, np.maximum(lo, (t - q[0]) * q[1])).astype(np.float32)
+
+    def affine(t, sty, m, swap=False):
+        mean, std = (mask_ref.blend(m, [s["sty"][sty][i] for s in st]) for i in (0, 1))
+        return (t * mean + std if swap else t * std + mean).astype(np.float32)
+
+    def apply(t, k, m):
+        F = np.zeros(m.shape[1:] + (32, 32), np.float32)
+        for s in range(S):
+            F = F + m[s][..., None, None] * st[s]["filt"][k][None, None]
+        return np.einsum("hwij,hwj->hwi", F.astype(np.float32), t[0]).astype(np.float32)[None]
+
+    m3 = np.roll(lv[3], 1, axis=2) if defect == "level mask shifted by one pixel in x" else lv[3]
+    raw = O.relu(O.conv3x3(x, w["Encoder.slice.19.weight"], w["Encoder.slice.19.bias"]))
+    cur = norm(raw, 0, m3, swap=defect == "lo / hi exchanged")
+    taps["c41"] = cur[0]
+    for f in range(3):
+        p = "Decoder.Filter%d." % (f + 1)
+        wd, bd = w[p + "down_sample.0.weight"], w[p + "down_sample.0.bias"]
+        n = 512 // MK_SPLIT
+        part = [O.conv3x3(np.ascontiguousarray(cur[..., k * n:(k + 1) * n]), np.ascontiguousarray(wd[:, k * n:(k + 1) * n]), np.zeros_like(bd))
+                for k in range(MK_SPLIT)]
+        taps["dpart"] = np.concatenate(part, axis=-1)[0]
+        d = part[0]
+        for k in range(1, MK_SPLIT - (1 if defect == "one split-K slice dropped" else 0)):
+            d = d + part[k]
+        if defect != "bias of down_sample omitted":
+            d = (d + bd).astype(np.float32)
+        k1, k2 = (2 * f + 1, 2 * f) if defect == "F1 and F2 exchanged" else (2 * f, 2 * f + 1)
+        d = apply(O.lrelu(d), k1, lv[3]) if defect == "LeakyReLU before F1" else O.lrelu(apply(d, k1, lv[3]))
+        d = apply(d, k2, lv[3])
+        cur = cur + O.conv3x3(d, w[p + "upsample.0.weight"], w[p + "upsample.0.bias"])
+        taps["f%d" % (f + 1)] = cur[0]
+    taps["d"] = d[0]
+    cur = affine(norm(cur, 1, lv[3]), 3, lv[3], swap=defect == "AdaIN mean / std exchanged")
+    taps["f3"] = cur[0]
+    for blk, xin, xs, a, o, l in MR.MASK_BLOCKS[:2]:
+        n1, n2, na, si = LR.RES[blk]
+        m = lv[l]
+        if defect == "level-1 mask from the neighbouring row pair" and l == 1:
+            m = np.ascontiguousarray(m[:, np.arange(m.shape[1]) ^ 1])
+        pre = "Decoder.%s." % blk
+        taps[xs] = O.conv1x1(cur, w[pre + "conv_shortcut.weight"])[0]
+        h = norm(O.lrelu(O.conv3x3(O.upsample2(cur), w[pre + "conv1.weight"], w[pre + "conv1.bias"])), n1, m)
+        taps[a] = h[0]
+        h = norm(O.lrelu(O.conv3x3(h, w[pre + "conv2.weight"], w[pre + "conv2.bias"])), n2, m)
+        xsu = O.upsample2(taps[xs][None])
+        if defect == "shortcut read at x instead of x >> 1" and l == 2:
+            W2 = xsu.shape[2]
+            xsu = np.repeat(taps[xs], 2, axis=0)[None][:, :, np.minimum(np.arange(W2), W2 // 2 - 1)]
+        if defect == "shortcut added after the AdaIN affine" and l == 2:
+            cur = (affine(norm(h, na, m), si, m) + xsu).astype(np.float32)
+        else:
+            cur = affine(norm((h + xsu).astype(np.float32), na, m), si, m)
+        taps[o] = cur[0]
+    return taps
+
+
+@pytest.fixture(scope="module")
+def mk(pkg, weights, oracle):
+    prev = oracle.CONV_BACKEND
+    oracle.set_conv_backend("numpy")
+    try:
+        blobs = [np.asarray(load_golden(n)["state"], np.float32) for n in MK_STATES]
+        frame = pkg.synth_frame(1, 64, 80, kind="smooth")
+        M = MR.softmax_mask(11, len(blobs), 64, 80)
+        yield oracle, frame, blobs, M, [LR.parse_state(b) for b in blobs]
+    finally:
+        oracle.set_conv_backend(prev)
+
+
+def _mask_failed(taps, weights, sts):
+    out = MR.mask_checks(taps.__getitem__, weights, sts, CPU_FAM, MK_SPLIT, names=MK_NAMES)
+    assert tuple(n for n, *_ in out) == MK_NAMES
+    return {n: worst for n, _, ok, worst, _ in out if not ok}
+
+
+def test_masked_float32_stand_in_passes(mk, weights):
+    oracle, frame, blobs, M, sts = mk
+    taps = _mask_standin(oracle, weights, frame, blobs, M)
+    bad = _mask_failed(taps, weights, sts)
+    assert not bad, bad
+    # ... and with the convolution filtered in place (split 1: d composite from f2)
+    out = MR.mask_checks(taps.__getitem__, weights, sts, CPU_FAM, 1, names=("dpart", "d"))
+    assert [(n, ok) for n, _, ok, _, _ in out] == [("d", True)], out
+
+
+MK_DEFECTS = {"level-1 mask from the neighbouring row pair": {"a3", "o3"}, "level mask shifted by one pixel in x": {"c41"},
+              "shortcut read at x instead of x >> 1": {"o4"}, "styles blended in swapped order": {"c41"}, "F1 and F2 exchanged": {"d"},
+              "bias of down_sample omitted": {"d"}, "LeakyReLU before F1": {"d"}, "one split-K slice dropped": {"d"},
+              "lo / hi exchanged": {"c41"}, "AdaIN mean / std exchanged": {"f3"}, "shortcut added after the AdaIN affine": {"o4"}}
+
+
+@pytest.mark.parametrize("defect", sorted(MK_DEFECTS))
+def test_masked_injected_defect_fails(mk, weights, defect):
+    """One wrong step planted in the float32 walk; the stage that sees it must fail at the committed K."""
+    oracle, frame, blobs, M, sts = mk
+    bad = _mask_failed(_mask_standin(oracle, weights, frame, blobs, M, defect=defect), weights, sts)
+    assert set(bad) >= MK_DEFECTS[defect], "%s: only %s fail" % (defect, bad)
+
+
+def test_level_mask_decoder(mk):
+    """A level-mask tap decodes to the mask it was laid out from, and a non-zero float outside the w * S run of a row is refused."""
+    M = mk[3]
+    S = M.shape[0]
+    for lv in mask_ref.level_masks(M):
+        _, h, w = lv.shape
+        t = np.zeros((h + 2, w + 2, MR.MASK_CH), np.float32)
+        t.reshape(h + 2, -1)[1:h + 1, MR.MASK_CH:MR.MASK_CH + w * S] = lv.transpose(1, 2, 0).reshape(h, w * S)
+        np.testing.assert_array_equal(MR.decode_level_mask(t.ravel(), h, w, S), lv)
+        for y, off in ((0, 9), (h + 1, 9), (1, 0), (1, MR.MASK_CH + w * S), (h, (w + 2) * MR.MASK_CH - 1)):
+            bad = t.copy()
+            bad.reshape(h + 2, -1)[y, off] = 1e-30
+            with pytest.raises(AssertionError, match="outside the w \\* S run"):
+                MR.decode_level_mask(bad.ravel(), h, w, S)
+    lv = mask_ref.level_masks(M)
+    assert all(ok for _, _, ok, _, _ in MR.check_level_masks({"lm%d" % l: lv[l] for l in range(4)}.__getitem__, lv, S))
+    off = [a.copy() for a in lv]
+    off[2][1, 3, 4] = np.nextafter(off[2][1, 3, 4], np.float32(2))
+    assert [ok for _, _, ok, _, _ in MR.check_level_masks({"lm%d" % l: off[l] for l in range(4)}.__getitem__, lv, S)] == [True, True, False, True]
