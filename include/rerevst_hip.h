@@ -443,6 +443,45 @@ int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames_yuv, int in_l
 int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame_yuv, int in_layout, int H, int W);
 int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame_yuv, int in_layout, int H, int W, void* hip_stream);
 
+/* 10 / 12 / 16-bit YUV 4:2:0, in and out (HEVC Main10, AV1, VP9 profile 2, ProRes: a hardware decoder's P010, ffmpeg's yuv420p10le, a C420p10
+ * .y4m file): every entry above that takes RRV_LAY_I420 / RRV_LAY_NV12 also takes the two uint16 layouts below; there are no new transfer entries.
+ * Frame layout.  Samples are uint16 in host byte order; CH = (H+1)/2, CW = (W+1)/2, frame_samples = H*W + 2*CH*CW; frame b starts at sample
+ * b * frame_samples with nothing in between (frame_samples can be odd: a frame is only 2-byte aligned).
+ *   RRV_LAY_I420_16  planar [Y][Cb][Cr], the d-bit code in the LOW bits   (ffmpeg yuv420p10le / 12le / 16le, Y4M C420p10 / p12 / p16)
+ *   RRV_LAY_P016     [Y][CbCr interleaved], the code in the HIGH bits, low bits 0   (ffmpeg p010le / p012le / p016le; hardware decoders / encoders)
+ * rrv_set_yuv_depth sets d for the input and the output side: each 10 (the default), 12 or 16; 0 leaves that side as it is; anything else is
+ * RRV_E_ARG.  It is handle state read when a call launches (for rrv_add_from_yuv: when the deferred encoding runs).
+ * Matrices map between RGB in the 0..255 PIXEL scale and d-bit codes, each coefficient evaluated in double and rounded once to float32.
+ * rrv_yuv_matrix_depth: limited range Y' = (16 + 219/255 Y) 2^(d-8), chroma (128 + 224/255 C) 2^(d-8) — the 8-bit matrix times 2^(d-8), exactly;
+ * full range Y' = (2^d - 1)/255 Y, chroma 2^(d-1) + (2^d - 1)/255 C.  rrv_yuv_input_matrix_depth is the inverse of these formulas, written out
+ * from them as rrv_yuv_input_matrix is.  bits is 8 (== rrv_yuv_matrix / rrv_yuv_input_matrix), 10, 12 or 16, else RRV_E_ARG; no handle, no GPU.
+ * rrv_set_yuv16_matrix / rrv_set_yuv16_input_matrix install twelve finite floats (else RRV_E_ARG) for the uint16 layouts only: they are
+ * independent of the 8-bit matrices and of each other.  NULL restores the default: BT.601 limited range at the depth in force when the call
+ * launches.  The 8-bit layouts never see the depth or these matrices.
+ * Output arithmetic: c_k as for 8 bits with the 16-bit matrix; Y code = rint(min(max(c_0, 0), 2^d - 1)), half to even; a chroma code the same clamp
+ * and rint of ((tl + tr) + (bl + br)) * 0.25f of the unclamped c_1 / c_2, odd last rows and columns as for 8 bits; stored sample = code
+ * (RRV_LAY_I420_16) or code << (16 - d) (RRV_LAY_P016).  So a 16-bit entry's samples are this arithmetic applied to its float32 twin's output,
+ * bit for bit, for the same frames and frames per call.
+ * Input arithmetic: code = sample (RRV_LAY_I420_16: used as it is, a well-formed stream sets no bit above d) or sample >> (16 - d) (RRV_LAY_P016:
+ * the low bits are ignored); v_k and px_k = min(max(v_k, 0), 255) as for 8 bits with the 16-bit input matrix, px NOT rounded, so a 10-bit source keeps
+ * its fractional pixel values; from there px is a float32 PIXEL BGR input, with the bit-identity statements of the 8-bit input entries.
+ * Where: rrv_transfer_yuv, rrv_transfer_blend_batch_yuv and rrv_transfer_mask_batch_yuv take layout 8 / 9 (out_yuv then holds 2 * frame_samples bytes
+ * per frame); the three rrv_transfer_image*_device entries and the `out` / `out_desc` of the six rrv_*_from_yuv* entries take
+ * {RRV_DT_U16, 8 | 9, RRV_SP_PIXEL}; the six rrv_*_from_yuv* entries and rrv_add_from_yuv[_device] take in_layout 8 / 9.  Any mix of input and output
+ * depth and layout is allowed (8-bit in -> 10-bit out, P010 -> P010).  RRV_E_ARG, the handle staying usable: RRV_DT_U16 with any other layout or
+ * space, layouts 8 / 9 with another dtype, layouts 8 / 9 as an rrv_image_desc INPUT; layout values 4..7 stay refused.  Flags, stream ordering,
+ * slots, sub-batching, rrv_set_host_io modes, page-locked buffers and rrv_get_preclamp_image behave as for the 8-bit forms.  A sample stream is
+ * 3 bytes per pixel each way, what a uint8 BGR input already is and a quarter of the float32 output.  HDR transfer functions are the caller's:
+ * the network is trained on display-referred 0..1 values, a PQ / HLG source needs tone mapping first. */
+enum { RRV_DT_U16 = 2 };        /* rrv_image_desc.dtype after RRV_DT_U8 = 0 and RRV_DT_F32 = 1: uint16 samples, only with the two layouts below */
+enum { RRV_LAY_I420_16 = 8,     /* planar [Y][Cb][Cr], uint16, code in the LOW bits */
+       RRV_LAY_P016    = 9 };   /* [Y][CbCr interleaved], uint16, code in the HIGH bits, low bits 0 */
+int rrv_set_yuv_depth(rrv_handle h, int in_bits, int out_bits);
+int rrv_yuv_matrix_depth(int standard, int full_range, int bits, float m[12]);
+int rrv_yuv_input_matrix_depth(int standard, int full_range, int bits, float n[12]);
+int rrv_set_yuv16_matrix(rrv_handle h, const float m[12]);
+int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]);
+
 /* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
  * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;
  * float32 in PIXEL / UNIT / NORM), one image [Hs][Ws] / [H][W] per call.  The style is read in colour, a sampled frame through

@@ -22,8 +22,10 @@ class ImageDesc(C.Structure):
 
 
 DT_U8, DT_F32 = 0, 1
+DT_U16 = 2                        # uint16 samples: only with LAY_I420_16 / LAY_P016
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
 LAY_I420, LAY_NV12 = 2, 3         # output only: 8-bit YUV 4:2:0, planar / semi-planar
+LAY_I420_16, LAY_P016 = 8, 9      # 10 / 12 / 16-bit YUV 4:2:0 in uint16 samples: planar with the code in the low bits / semi-planar with it in the high bits
 YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8
@@ -103,6 +105,11 @@ SYMBOLS = {
                                              C.c_void_p, ImageDesc, C.c_int]),
     "rrv_add_from_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_add_from_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_set_yuv_depth": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rrv_yuv_matrix_depth": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rrv_yuv_input_matrix_depth": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rrv_set_yuv16_matrix": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rrv_set_yuv16_input_matrix": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),

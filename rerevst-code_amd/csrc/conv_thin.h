@@ -17,6 +17,10 @@
 //   1.5 (+12) B/pixel.
 // YUV input (the rrv_*_from_yuv entries): conv_first_k<IN_YUV_I420 / IN_YUV_NV12> reads a Y byte per pixel and the Cb, Cr bytes of its
 //   2 x 2 block, converts them with a 3 x 4 matrix to the float32 PIXEL value and goes on as the float32 form does.  Reads 1.5 B/pixel.
+// 10 / 12 / 16-bit YUV (RRV_LAY_I420_16 / RRV_LAY_P016, uint16 samples): conv_first_k<IN_YUV_I420_16 / IN_YUV_P016> loads a uint16 per sample
+//   and shifts it right by FirstP::yuv_shift (0 for the planar form, whose code sits in the low bits; 16 - d for P016, whose code sits in the
+//   high bits); conv_last_k<true, false, SP_PIXEL, true, true> clamps to LastP::yuv_hi = 2^d - 1, shifts the code left by LastP::yuv_shift
+//   and stores a uint16.  3 B/pixel each way.  The 8-bit instantiations are the code they were: the depth is a template argument.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,15 +32,18 @@
 enum : int { SP_PIXEL = 0, SP_UNIT = 1, SP_NORM = 2 };
 // conv_first_k's input forms (the template argument): bit 0 planar CHW RGB (else HWC BGR), bit 1 float32 (else uint8)
 // 4, 5: 8-bit YUV 4:2:0 frames, [Y: H*W][Cb: CH*CW][Cr: CH*CW] (I420) or [Y: H*W][CbCr interleaved: CH*CW*2] (NV12), CH = (H+1)/2, CW = (W+1)/2
-enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3, IN_YUV_I420 = 4, IN_YUV_NV12 = 5, IN_FORMS = 6 };
+// 6, 7: the same two layouts in uint16 samples (10 / 12 / 16-bit codes: planar with the code in the low bits, semi-planar P010 / P012 / P016 with it in the high bits)
+enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3, IN_YUV_I420 = 4, IN_YUV_NV12 = 5, IN_YUV_I420_16 = 6, IN_YUV_P016 = 7, IN_FORMS = 8 };
 inline bool in_yuv(int form) { return form >= IN_YUV_I420; }
-inline size_t in_elem(int form) { return !in_yuv(form) && (form & 2) ? sizeof(float) : 1; }     // bytes per input value
+inline bool in_yuv16(int form) { return form >= IN_YUV_I420_16; }
+inline size_t in_elem(int form) { return in_yuv16(form) ? sizeof(uint16_t) : !in_yuv(form) && (form & 2) ? sizeof(float) : 1; }     // bytes per input value
+inline size_t yuv_frame_samples(size_t H, size_t W) { return H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2); }     // Y, Cb, Cr samples of one 4:2:0 frame
 inline size_t in_frame_bytes(int form, size_t H, size_t W) {                                      // bytes of one H x W input frame
-    return in_yuv(form) ? H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2) : H * W * 3 * in_elem(form);
+    return (in_yuv(form) ? yuv_frame_samples(H, W) : H * W * 3) * in_elem(form);
 }
 
 struct FirstP {
-    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32; IN_YUV_*: [B][H*W + 2*CH*CW] uint8
+    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32; IN_YUV_*: [B][H*W + 2*CH*CW] uint8 (uint16 for the two 16-bit forms)
     int H, W, B;
     float* out;           // [B,H,W,64] ring layout
     const float* w;       // [27][64]: row (ky*3+kx)*3 + c_rgb
@@ -50,7 +57,8 @@ struct FirstP {
     int src_H, src_W, pad_top, pad_left;
     int p8;               // 1: `out` is channel-chunk-major [B][8 chunks][H+2][W+8][8], pixel x at column x + 4 (conv_f43.h LAY: what conv1_2 on conv_f43_k reads 12-19 % faster); same values
     int space;            // value space of a float32 input (SP_*); a uint8 input is PIXEL
-    float yuv_n[12];      // IN_YUV_*: rows R, G, B; columns the coefficients of Y, Cb, Cr and an offset (rrv_set_yuv_input_matrix), by value
+    float yuv_n[12];      // IN_YUV_*: rows R, G, B; columns the coefficients of Y, Cb, Cr and an offset (rrv_set_yuv_input_matrix; the 16-bit forms: rrv_set_yuv16_input_matrix), by value
+    int yuv_shift;        // IN_YUV_I420_16: 0; IN_YUV_P016: 16 - d, the code is sample >> yuv_shift (the low bits are ignored)
 };
 
 // symmetric (edge-inclusive) reflection of t into [0, n), any distance
@@ -68,11 +76,12 @@ __device__ __forceinline__ int reflect_sym(int t, int n) {
 // IN_YUV_*: source pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1) — after the reflection of the pad geometry, which
 // therefore equals reflect-padding the converted frame, also for odd H / W — and v_k = ((n[k][0] Y + n[k][1] Cb) + n[k][2] Cr) + n[k][3],
 // every product and sum rounded to float32 (no contraction), px_k = min(max(v_k, 0), 255), not rounded to an integer: the float PIXEL
-// value.  Frame starts and chroma planes are in general not dword aligned: byte loads.
+// value.  Frame starts and chroma planes are in general not dword aligned: byte loads (the uint16 forms: 2-byte loads; a frame is an odd
+// number of samples where H*W is odd).  The uint16 forms use code = sample >> yuv_shift in place of the byte.
 template <int IN = IN_U8_HWC>
 __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
-    constexpr bool YUV = IN >= IN_YUV_I420, NV12 = IN == IN_YUV_NV12, CHW = !YUV && (IN & 1) != 0, F32 = !YUV && (IN & 2) != 0;
-    typedef typename std::conditional<F32, float, uint8_t>::type T;
+    constexpr bool YUV = IN >= IN_YUV_I420, Y16 = IN >= IN_YUV_I420_16, NV12 = IN == IN_YUV_NV12 || IN == IN_YUV_P016, CHW = !YUV && (IN & 1) != 0, F32 = !YUV && (IN & 2) != 0;
+    typedef typename std::conditional<F32, float, typename std::conditional<Y16, uint16_t, uint8_t>::type>::type T;
     __shared__ __attribute__((aligned(16))) float s_in[18 * 18 * 4];
     __shared__ __attribute__((aligned(16))) float s_w[27 * 64];
     const int tid = threadIdx.x;
@@ -96,7 +105,14 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
     auto norm_of = [&](const SrcPx& s, int c) -> float {      // source pixel -> normalised value of channel c, RGB order (framework.py:27,33-34)
         if constexpr (YUV) {
             const size_t ci = (size_t)(s.y >> 1) * CW + (s.x >> 1);
-            const float yy = (float)img[s.i], cb = (float)img[NV12 ? ysz + 2 * ci : ysz + ci], cr = (float)img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci];
+            float yy, cb, cr;
+            if constexpr (Y16) {
+                yy = (float)(img[s.i] >> p.yuv_shift);
+                cb = (float)(img[NV12 ? ysz + 2 * ci : ysz + ci] >> p.yuv_shift);
+                cr = (float)(img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci] >> p.yuv_shift);
+            } else {
+                yy = (float)img[s.i]; cb = (float)img[NV12 ? ysz + 2 * ci : ysz + ci]; cr = (float)img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci];
+            }
             float v;
             {
 #pragma clang fp contract(off)
@@ -283,6 +299,9 @@ struct LastP {
     // the YUV 4:2:0 store form (conv_last_k<true, false, SP_PIXEL, true>): out_img is [B][OH*OW Y][chroma] uint8, frame b at b * (OH*OW + 2*CH*CW)
     float yuv_m[12];      // rows Y, Cb, Cr; columns the coefficients of R, G, B and an offset (rrv_set_yuv_matrix), by value
     int yuv_nv12;         // 0: I420, planes [Cb: CH*CW][Cr: CH*CW]; 1: NV12, one plane of CH*CW (Cb, Cr) pairs
+    // the uint16 instantiation (conv_last_k<true, false, SP_PIXEL, true, true>): samples in place of bytes, yuv_m the 16-bit matrix
+    float yuv_hi;         // 2^d - 1, the upper clamp bound of a d-bit code
+    int yuv_shift;        // stored sample = code << yuv_shift: 0 planar (code in the low bits), 16 - d for P016 (code in the high bits)
 };
 
 // GEMM first, taps second.  out[y][x][rgb] = sum_tap sum_c w[tap][c][rgb] in[y+ky][x+kx][c] is evaluated as
@@ -305,7 +324,10 @@ struct LastP {
 // of the OUTPUT frame, rint(clamp(((tl + tr) + (bl + br)) * 0.25f, 0, 255)) of the unclamped c_1 / c_2, a pixel of the block outside
 // the frame (odd OH / OW, last row / column) replaced by its nearest one inside.  The crop origin and the tile origins are even, so
 // a block's four pixels are lanes l, l^1, l^16, l^17 of one wave.
-template <bool U8, bool CHW = false, int SPACE = SP_PIXEL, bool YUV = false>
+// Y16 (with YUV): d-bit codes in uint16 samples, 10 / 12 / 16 bits: the clamp's upper bound is p.yuv_hi = 2^d - 1 and the stored sample is
+// code << p.yuv_shift.  The 16 lanes of a tile row write 32 contiguous bytes of Y.  Frames, the chroma planes (OH*OW samples in) and rows are
+// in general only 2-byte aligned, so Cb and Cr leave as two 2-byte stores in both layouts.
+template <bool U8, bool CHW = false, int SPACE = SP_PIXEL, bool YUV = false, bool Y16 = false>
 __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     __shared__ __attribute__((aligned(16))) float s_g[27 * LAST_GP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -397,7 +419,14 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
         __syncthreads();                      // G is free for the next tile
         const int y = y0 + row, xx = x0 + col;
         if constexpr (YUV) {
-            static_assert(U8 && !CHW && SPACE == SP_PIXEL, "the YUV form stores bytes of the PIXEL values");
+            static_assert(U8 && !CHW && SPACE == SP_PIXEL, "the YUV form stores integer codes of the PIXEL values");
+            typedef typename std::conditional<Y16, uint16_t, uint8_t>::type S;      // a stored sample
+            const float hi = Y16 ? p.yuv_hi : 255.f;
+            auto sample = [&](float v) -> S {      // clamp, round half to even, and (uint16 only) move the code to where the layout keeps it
+                const float code = __builtin_rintf(fminf(fmaxf(v, 0.f), hi));
+                if constexpr (Y16) return (S)((unsigned)code << p.yuv_shift);
+                else return (S)code;
+            };
             // every lane computes its pixel's three components: the chroma sums cross lanes, so they run before the bounds branch,
             // with all 64 lanes active (a lane outside the frame holds a value nobody uses)
             float im[3];
@@ -437,15 +466,15 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
                 typedef float f32x3 __attribute__((ext_vector_type(3)));
                 if (p.out_pre) *(f32x3*)(p.out_pre + (((size_t)b * p.H + y) * p.W + xx) * 3) = f32x3{o[0], o[1], o[2]};
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
-                    // byte stores: the 16 lanes of a tile row write 16 contiguous Y bytes, its 8 even lanes 8 (I420) or 16 (NV12)
-                    // chroma bytes; rows are OW bytes and frames OH*OW + 2*CH*CW, in general not dword aligned
+                    // sample stores: the 16 lanes of a tile row write 16 contiguous Y samples, its 8 even lanes 8 (I420) or 16 (NV12)
+                    // chroma samples; rows are OW samples and frames OH*OW + 2*CH*CW, in general not dword aligned
                     const int CH = (OH + 1) >> 1, CW = (OW + 1) >> 1;
                     const size_t ysz = (size_t)OH * OW, csz = (size_t)CH * CW;
-                    uint8_t* const fr = (uint8_t*)p.out_img + (size_t)b * (ysz + 2 * csz);
-                    fr[(size_t)cy * OW + cx] = (uint8_t)__builtin_rintf(fminf(fmaxf(yuv[0], 0.f), 255.f));
+                    S* const fr = (S*)p.out_img + (size_t)b * (ysz + 2 * csz);
+                    fr[(size_t)cy * OW + cx] = sample(yuv[0]);
                     if (!((row | col) & 1)) {       // the block's top left pixel (cy, cx even: crop and tile origins are even)
-                        const uint8_t cb = (uint8_t)__builtin_rintf(fminf(fmaxf(blk[0], 0.f), 255.f));
-                        const uint8_t cr = (uint8_t)__builtin_rintf(fminf(fmaxf(blk[1], 0.f), 255.f));
+                        const S cb = sample(blk[0]);
+                        const S cr = sample(blk[1]);
                         const size_t ci = (size_t)(cy >> 1) * CW + (cx >> 1);
                         if (p.yuv_nv12) { fr[ysz + 2 * ci] = cb; fr[ysz + 2 * ci + 1] = cr; }
                         else { fr[ysz + ci] = cb; fr[ysz + csz + ci] = cr; }

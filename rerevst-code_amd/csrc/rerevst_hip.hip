@@ -259,6 +259,11 @@ struct rrv_ctx {
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
     float yuv_in_m[12];               // rrv_set_yuv_input_matrix: rows R, G, B x (Y, Cb, Cr, offset) of the YUV input forms; read at launch (run_encoder), BT.601 limited range at rrv_create
+    // the uint16 YUV forms (RRV_LAY_I420_16 / RRV_LAY_P016): code depths (rrv_set_yuv_depth) and matrices of their own (rrv_set_yuv16_[input_]matrix);
+    // while a matrix is not set, the launch takes BT.601 limited range at the depth then in force
+    int yuv_in_bits = 10, yuv_out_bits = 10;
+    bool yuv16_in_set = false, yuv16_set = false;
+    float yuv16_in_m[12], yuv16_m[12];
     float yuv_m[12];                  // rrv_set_yuv_matrix: rows Y, Cb, Cr x (R, G, B, offset) of the YUV store form; read at launch (run_last), BT.601 limited range at rrv_create
     int host_io = 0;                  // rrv_set_host_io: 0 = staged H2D / D2H copies, 1 = zero copy (kernels read / write page-locked host memory), 2 = input only, 3 = output only
     int n_cus = 256;
@@ -994,10 +999,14 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
               h->in_space};
     stamp(h, p8 ? &e.q11 : &e.c11, B);
-    if (in_yuv(inf)) memcpy(fp.yuv_n, h->yuv_in_m, sizeof fp.yuv_n);
+    if (in_yuv16(inf)) {
+        if (h->yuv16_in_set) memcpy(fp.yuv_n, h->yuv16_in_m, sizeof fp.yuv_n);
+        else (void)rrv_yuv_input_matrix_depth(RRV_YUV_BT601, 0, h->yuv_in_bits, fp.yuv_n);
+        fp.yuv_shift = inf == IN_YUV_P016 ? 16 - h->yuv_in_bits : 0;
+    } else if (in_yuv(inf)) memcpy(fp.yuv_n, h->yuv_in_m, sizeof fp.yuv_n);
     static void (*const first_k[IN_FORMS])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>,
-                                                      conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>};
-    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? 1.5 : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
+                                                      conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>, conv_first_k<IN_YUV_I420_16>, conv_first_k<IN_YUV_P016>};
+    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? 1.5 * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
         hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
     }));
     ConvCall c;
@@ -1032,11 +1041,13 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
 // on the GPU (conv_last_k<true>: cv2.imwrite's / driver.to_uint8's conversion) — the rrv_*_u8 entries.  Elements per frame are
 // the same; only their size differs.  rrv_transfer_image_device adds planar RGB (chw) and the UNIT / NORM spaces (float32 only).
 // yuv = RRV_LAY_I420 / RRV_LAY_NV12 (else 0): 8-bit YUV 4:2:0 of the PIXEL values (conv_last_k's YUV form, the rrv_*_yuv entries); a
-// frame is then Xfer::out_bytes() bytes, not elements x element size.
+// frame is then Xfer::out_bytes() bytes, not elements x element size.  yuv = RRV_LAY_I420_16 / RRV_LAY_P016: the same in uint16 samples, 10 / 12 /
+// 16-bit codes (conv_last_k's Y16 instantiation), two bytes per sample.
 struct OutFmt { bool u8, chw; int space; int yuv = 0; };
+constexpr bool yuv16_layout(int layout) { return layout == RRV_LAY_I420_16 || layout == RRV_LAY_P016; }
+inline size_t yuv_sample_bytes(OutFmt f) { return yuv16_layout(f.yuv) ? sizeof(uint16_t) : 1; }
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
 constexpr OutFmt out_yuv(int layout) { return OutFmt{true, false, SP_PIXEL, layout}; }
-inline size_t yuv_frame_bytes(size_t OH, size_t OW) { return OH * OW + 2 * ((OH + 1) / 2) * ((OW + 1) / 2); }
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
 
@@ -1065,7 +1076,7 @@ struct Xfer {
     size_t in_bytes(rrv_handle h) const { return in_frame_bytes(h->in_form, H, W); }                               // per frame, in the scoped input form
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
-        return fmt.yuv ? (pad ? yuv_frame_bytes(H, W) : yuv_frame_bytes(H / 8 * 8, W / 8 * 8)) : out_elems() * out_elem(fmt);
+        return fmt.yuv ? (pad ? yuv_frame_samples(H, W) : yuv_frame_samples(H / 8 * 8, W / 8 * 8)) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
     }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
     PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
@@ -1226,6 +1237,7 @@ int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const
 // the conv_last_k instantiation that writes `f`
 typedef void (*LastFn)(LastP);
 LastFn last_kernel(OutFmt f) {
+    if (yuv16_layout(f.yuv)) return conv_last_k<true, false, SP_PIXEL, true, true>;
     if (f.yuv) return conv_last_k<true, false, SP_PIXEL, true>;
     if (f.u8) return f.chw ? conv_last_k<true, true> : conv_last_k<true>;
     static const LastFn k[2][3] = {{conv_last_k<false>, conv_last_k<false, false, SP_UNIT>, conv_last_k<false, false, SP_NORM>},
@@ -1239,12 +1251,18 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
     if (fmt.yuv) {
         if (pc && ((pc->top | pc->left) & 1)) return fail(h, RRV_E_ARG, "conv_last: the YUV form needs an even crop origin");
-        memcpy(lp.yuv_m, h->yuv_m, sizeof lp.yuv_m);
-        lp.yuv_nv12 = fmt.yuv == RRV_LAY_NV12;
+        if (yuv16_layout(fmt.yuv)) {
+            const int d = h->yuv_out_bits;
+            if (h->yuv16_set) memcpy(lp.yuv_m, h->yuv16_m, sizeof lp.yuv_m);
+            else (void)rrv_yuv_matrix_depth(RRV_YUV_BT601, 0, d, lp.yuv_m);
+            lp.yuv_hi = (float)((1 << d) - 1);
+            lp.yuv_shift = fmt.yuv == RRV_LAY_P016 ? 16 - d : 0;
+        } else memcpy(lp.yuv_m, h->yuv_m, sizeof lp.yuv_m);
+        lp.yuv_nv12 = fmt.yuv == RRV_LAY_NV12 || fmt.yuv == RRV_LAY_P016;
     }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
-    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 : 3.0 * out_elem(fmt))) * B * H * W, [&] {
+    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * B * H * W, [&] {
         const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * B), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
         hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
@@ -2273,21 +2291,26 @@ int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, i
 }
 
 // sampled frames as 8-bit YUV 4:2:0 (conv_first_k<IN_YUV_*>); the input matrix is read when the deferred encoding runs
+// (RRV_LAY_I420_16 / RRV_LAY_P016: uint16 samples, the depth and the 16-bit input matrix read then too)
 static bool yuv_in_form(int layout, int* form) {
-    if (layout != RRV_LAY_I420 && layout != RRV_LAY_NV12) return false;
-    *form = layout == RRV_LAY_NV12 ? IN_YUV_NV12 : IN_YUV_I420;
-    return true;
+    switch (layout) {
+    case RRV_LAY_I420: *form = IN_YUV_I420; return true;
+    case RRV_LAY_NV12: *form = IN_YUV_NV12; return true;
+    case RRV_LAY_I420_16: *form = IN_YUV_I420_16; return true;
+    case RRV_LAY_P016: *form = IN_YUV_P016; return true;
+    }
+    return false;
 }
 int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame, int in_layout, int H, int W) {
     if (!h || !frame) return RRV_E_ARG;
     int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     return add_frame(h, frame, false, form, SP_PIXEL, nullptr, H, W);
 }
 int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame, int in_layout, int H, int W, void* hip_stream) {
     if (!h || !d_frame) return RRV_E_ARG;
     int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     return add_frame(h, d_frame, true, form, SP_PIXEL, (hipStream_t)hip_stream, H, W);
 }
 
@@ -2625,14 +2648,20 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 // stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only.  x: the model, B, H, W and what
 // the model blends with; the flags and `out` supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME)
 static bool bad_desc(const rrv_image_desc& d, bool yuv_ok) {
-    return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) ||
-           d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
+    return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32 && !(d.dtype == RRV_DT_U16 && yuv_ok)) ||
+           (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) || d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
+}
+// a YUV 4:2:0 output descriptor: uint8 I420 / NV12 or uint16 RRV_LAY_I420_16 / RRV_LAY_P016, in the PIXEL space
+static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12 || yuv16_layout(layout); }
+static bool yuv_desc_ok(const rrv_image_desc& d) {
+    return d.dtype == (yuv16_layout(d.layout) ? RRV_DT_U16 : RRV_DT_U8) && d.space == RRV_SP_PIXEL;
 }
 // in_form, in_space: the checked input form (a descriptor's, or IN_YUV_* of the _from_yuv_device entries)
 static int image_run(rrv_handle h, const void* d_in, int in_form, int in_space, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
-    const bool yuv = out.layout == RRV_LAY_I420 || out.layout == RRV_LAY_NV12;      // an output layout of the descriptor entries
+    const bool yuv = yuv_layout(out.layout);      // an output layout of the descriptor entries
     if (bad_desc(out, yuv)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
-    if (yuv && (out.dtype != RRV_DT_U8 || out.space != RRV_SP_PIXEL)) return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8 in the PIXEL space");
+    if (yuv && !yuv_desc_ok(out))
+        return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8, an I420_16 / P016 output uint16, in the PIXEL space");
     if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
         return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
@@ -2665,7 +2694,7 @@ static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* 
 static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
     if (!h) return RRV_E_ARG;
     int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
     return image_run(h, d_in, form, SP_PIXEL, d_out, out, flags, hip_stream, x);
 }
@@ -3033,23 +3062,22 @@ int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames, int B
     return host_pipeline(h, frames, out, Xfer{Model::FRAME, B, H, W, PADDED, OUT_U8});
 }
 
-// 8-bit YUV 4:2:0 output of the host entries (conv_last_k's YUV form): frame b at b * (OH*OW + 2*CH*CW) bytes of `out`
-static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12; }
+// YUV 4:2:0 output of the host entries (conv_last_k's YUV form): frame b at b * (OH*OW + 2*CH*CW) samples of `out`, bytes or (layouts 8 / 9) uint16
 int rrv_transfer_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, int flags, int layout, uint8_t* out) {
     if (!h) return RRV_E_ARG;
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_yuv: unknown flags");
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     return host_pipeline(h, frames, out, Xfer{flags & RRV_TF_FRAME_MODE ? Model::FRAME : Model::GLOBAL, B, H, W, (flags & RRV_TF_PAD_CROP) != 0, out_yuv(layout)});
 }
 int rrv_transfer_blend_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, int layout, uint8_t* out) {
     if (!h) return RRV_E_ARG;
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     return host_pipeline(h, frames, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, out_yuv(layout), ns, wts});
 }
 int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop,
                                 int layout, uint8_t* out) {
     if (!h) return RRV_E_ARG;
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, out_yuv(layout), ns, /* wts */ nullptr, mask, mask_images});
 }
 
@@ -3058,12 +3086,12 @@ int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int 
 static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, void* out, rrv_image_desc od, int flags, int known_flags, Xfer x) {
     if (!h) return RRV_E_ARG;
     int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420 or RRV_LAY_NV12");
+    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
     if (flags & ~known_flags) return fail(h, RRV_E_ARG, "transfer_from_yuv: unknown flags");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
     const bool yuv = yuv_layout(od.layout);
-    if ((od.dtype != RRV_DT_U8 && od.dtype != RRV_DT_F32) || (!yuv && od.layout != RRV_LAY_HWC_BGR) || od.space != RRV_SP_PIXEL || (yuv && od.dtype != RRV_DT_U8))
-        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, or uint8 I420 / NV12");
+    if (yuv ? !yuv_desc_ok(od) : ((od.dtype != RRV_DT_U8 && od.dtype != RRV_DT_F32) || od.layout != RRV_LAY_HWC_BGR || od.space != RRV_SP_PIXEL))
+        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016");
     if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
     x.pad = (flags & RRV_TF_PAD_CROP) != 0;
     x.fmt = yuv ? out_yuv(od.layout) : (od.dtype == RRV_DT_U8 ? OUT_U8 : OUT_F32);
@@ -3085,19 +3113,25 @@ int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames, int in_layou
 // The matrix of the YUV input forms, the inverse of rrv_yuv_matrix's transform: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y,
 // C' = C - 128), R = Y' + 2(1-Kr) Cr', B = Y' + 2(1-Kb) Cb', G = Y' - (2 Kb (1-Kb) / Kg) Cb' - (2 Kr (1-Kr) / Kg) Cr'; the offsets folded into
 // column 3.  Coefficients in double, each rounded once to float32.
-int rrv_yuv_input_matrix(int standard, int full_range, float n[12]) {
-    if (!n || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709)) return RRV_E_ARG;
+// d-bit codes (bits = 8, 10, 12, 16; s = 2^(d-8)): limited range Y' = (Y / s - 16) 255/219, C' = (C / s - 128) 255/224, i.e. the 8-bit coefficients
+// divided by s (exact) and the 8-bit offsets; full range Y' = 255/(2^d - 1) Y, C' = 255/(2^d - 1) (C - 2^(d-1)).
+static bool yuv_depth_ok(int bits) { return bits == 8 || bits == 10 || bits == 12 || bits == 16; }
+int rrv_yuv_input_matrix_depth(int standard, int full_range, int bits, float n[12]) {
+    if (!n || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709) || !yuv_depth_ok(bits)) return RRV_E_ARG;
     const double kr = standard == RRV_YUV_BT601 ? 0.299 : 0.2126, kb = standard == RRV_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-    const double ys = full_range ? 1.0 : 255.0 / 219.0, cs = full_range ? 1.0 : 255.0 / 224.0, y0 = full_range ? 0.0 : 16.0;
+    const double s = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
+    const double ys = full_range ? 255.0 / top : 255.0 / 219.0 / s, cs = full_range ? 255.0 / top : 255.0 / 224.0 / s;
+    const double y0 = full_range ? 0.0 : 16.0 * s, c0 = 128.0 * s;
     const double cb[3] = {0.0, -(2.0 * kb * (1.0 - kb) / kg), 2.0 * (1.0 - kb)}, cr[3] = {2.0 * (1.0 - kr), -(2.0 * kr * (1.0 - kr) / kg), 0.0};
     for (int k = 0; k < 3; ++k) {
         n[4 * k] = (float)ys;
         n[4 * k + 1] = (float)(cs * cb[k]);
         n[4 * k + 2] = (float)(cs * cr[k]);
-        n[4 * k + 3] = (float)(-(ys * y0) - 128.0 * (cs * cb[k]) - 128.0 * (cs * cr[k]));
+        n[4 * k + 3] = (float)(-(ys * y0) - c0 * (cs * cb[k]) - c0 * (cs * cr[k]));
     }
     return RRV_OK;
 }
+int rrv_yuv_input_matrix(int standard, int full_range, float n[12]) { return rrv_yuv_input_matrix_depth(standard, full_range, 8, n); }
 // handle state, independent of the output matrix, read when conv_first_k is launched
 int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]) {
     if (!h) return RRV_E_ARG;
@@ -3110,20 +3144,24 @@ int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]) {
 
 // The conversion matrix of the YUV forms: Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited
 // range scales Y by 219/255 (+16) and the chroma differences by 224/255.  Coefficients in double, each rounded once to float32.
-int rrv_yuv_matrix(int standard, int full_range, float m[12]) {
-    if (!m || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709)) return RRV_E_ARG;
+// d-bit codes (s = 2^(d-8)): limited range Y' = (16 + 219/255 Y) s, chroma (128 + 224/255 C) s — the 8-bit matrix times s, exactly; full range
+// Y' = (2^d - 1)/255 Y, chroma 2^(d-1) + (2^d - 1)/255 C.
+int rrv_yuv_matrix_depth(int standard, int full_range, int bits, float m[12]) {
+    if (!m || (standard != RRV_YUV_BT601 && standard != RRV_YUV_BT709) || !yuv_depth_ok(bits)) return RRV_E_ARG;
     const double kr = standard == RRV_YUV_BT601 ? 0.299 : 0.2126, kb = standard == RRV_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-    const double ys = full_range ? 1.0 : 219.0 / 255.0, cs = full_range ? 1.0 : 224.0 / 255.0;
+    const double s = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
+    const double ys = full_range ? top / 255.0 : 219.0 / 255.0 * s, cs = full_range ? top / 255.0 : 224.0 / 255.0 * s;
     const double y[3] = {kr, kg, kb};
     for (int c = 0; c < 3; ++c) {
         m[c] = (float)(ys * y[c]);
         m[4 + c] = (float)(cs * ((c == 2 ? 1.0 : 0.0) - y[c]) / (2.0 * (1.0 - kb)));
         m[8 + c] = (float)(cs * ((c == 0 ? 1.0 : 0.0) - y[c]) / (2.0 * (1.0 - kr)));
     }
-    m[3] = full_range ? 0.f : 16.f;
-    m[7] = m[11] = 128.f;
+    m[3] = full_range ? 0.f : (float)(16.0 * s);
+    m[7] = m[11] = (float)(128.0 * s);
     return RRV_OK;
 }
+int rrv_yuv_matrix(int standard, int full_range, float m[12]) { return rrv_yuv_matrix_depth(standard, full_range, 8, m); }
 // handle state, read when conv_last_k is launched: launches already queued keep the matrix they were queued with
 int rrv_set_yuv_matrix(rrv_handle h, const float m[12]) {
     if (!h) return RRV_E_ARG;
@@ -3132,6 +3170,32 @@ int rrv_set_yuv_matrix(rrv_handle h, const float m[12]) {
         if (!std::isfinite(m[i])) return fail(h, RRV_E_ARG, "set_yuv_matrix: the twelve coefficients must be finite");
     memcpy(h->yuv_m, m, sizeof h->yuv_m);
     return RRV_OK;
+}
+
+// The uint16 forms' state: the code depth of each side, and matrices independent of the 8-bit ones and of each other.  NULL: BT.601 limited
+// range at the depth in force when a call launches (run_encoder / run_last work it out then).
+int rrv_set_yuv_depth(rrv_handle h, int in_bits, int out_bits) {
+    if (!h) return RRV_E_ARG;
+    auto ok = [](int b) { return b == 0 || b == 10 || b == 12 || b == 16; };
+    if (!ok(in_bits) || !ok(out_bits)) return fail(h, RRV_E_ARG, "set_yuv_depth: a depth is 10, 12 or 16 bits (0 leaves it as it is)");
+    if (in_bits) h->yuv_in_bits = in_bits;
+    if (out_bits) h->yuv_out_bits = out_bits;
+    return RRV_OK;
+}
+static int set_yuv16(rrv_handle h, const float* src, float* dst, bool* set, const char* what) {
+    if (!h) return RRV_E_ARG;
+    if (!src) { *set = false; return RRV_OK; }
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(src[i])) return fail(h, RRV_E_ARG, what);
+    memcpy(dst, src, 12 * sizeof(float));
+    *set = true;
+    return RRV_OK;
+}
+int rrv_set_yuv16_matrix(rrv_handle h, const float m[12]) {
+    return h ? set_yuv16(h, m, h->yuv16_m, &h->yuv16_set, "set_yuv16_matrix: the twelve coefficients must be finite") : RRV_E_ARG;
+}
+int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]) {
+    return h ? set_yuv16(h, n, h->yuv16_in_m, &h->yuv16_in_set, "set_yuv16_input_matrix: the twelve coefficients must be finite") : RRV_E_ARG;
 }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----

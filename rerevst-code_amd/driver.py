@@ -8,10 +8,11 @@ Reads the style image and the content frames (PNG / JPEG, through Pillow; BGR ui
 reference), runs prepare_style / clean / add (every 8th frame + the last, :129-143) / compute, stylizes every frame with
 pad + crop on the device (`Stylization.transfer_frames`), writes the stylized frames under the input file names
 (saturating float -> uint8 as cv2.imwrite does, :170-171) and optionally a Motion-JPEG AVI (:175-186) or, for a target that ends
-in .y4m, an uncompressed YUV4MPEG2 stream (8-bit 4:2:0) that any encoder reads.  With --no-frames only the video is written; a
+in .y4m, an uncompressed YUV4MPEG2 stream (4:2:0; 8 bits, or 10 / 12 / 16 with --bit-depth: C420p10 / p12 / p16) that any encoder reads.  With --no-frames only the video is written; a
 .y4m then receives the I420 bytes the GPU converted (`transfer_frames(out_format="i420")`): no image codec on the output side.
 --frames in.y4m reads a YUV4MPEG2 file instead of image files (Y4MReader): its I420 frames go to the GPU unchanged
-(`in_format="i420"`), so .y4m -> .y4m touches no pixel on the host.
+(`in_format="i420"`, or "i420p10" / "i420p12" / "i420p16" for a C420p10 / p12 / p16 file, whose depth the output keeps unless
+--bit-depth says otherwise), so .y4m -> .y4m touches no pixel on the host.
 
 Differences from the reference script, on purpose: the frame list is sorted (the reference's comment asks for it, its
 code forgets the sort()); image decoding / encoding is Pillow's, not OpenCV's (neither is part of the measured path).
@@ -151,20 +152,28 @@ class Y4MWriter:
     """Uncompressed YUV4MPEG2 stream, 8-bit 4:2:0 planar (I420) with the chroma sited at the block centres (C420jpeg): one header
     line, then `FRAME\n` and width*height + 2 * ceil(width/2)*ceil(height/2) bytes per frame.  `ffmpeg -i out.y4m` and every
     encoder's command line read it, from a file or a pipe.  full_range tags the header (XCOLORRANGE); the matrix is not part of
-    the format (readers assume BT.601 for untagged 4:2:0)."""
+    the format (readers assume BT.601 for untagged 4:2:0).  bits = 10, 12, 16: C420p10 / C420p12 / C420p16, the same planes in
+    little-endian 16-bit samples with the code in the low bits (what ffmpeg reads and writes for these tags: yuv420p10le ..), twice
+    the bytes per frame."""
 
-    def __init__(self, path, fps, width, height, full_range=False):
-        self.path, self.w, self.h = path, int(width), int(height)
-        self.frame_bytes = self.w * self.h + 2 * ((self.w + 1) // 2) * ((self.h + 1) // 2)
+    def __init__(self, path, fps, width, height, full_range=False, bits=8):
+        if bits not in (8, 10, 12, 16):
+            raise ValueError("bits must be 8, 10, 12 or 16, got %r" % (bits,))
+        self.path, self.w, self.h, self.bits = path, int(width), int(height), int(bits)
+        self.frame_bytes = (self.w * self.h + 2 * ((self.w + 1) // 2) * ((self.h + 1) // 2)) * (1 if bits == 8 else 2)
         self.frames = 0
         num, den = fps_fraction(fps)
         self.f = open(path, "wb")
-        self.f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=%s\n" % (self.w, self.h, num, den, b"FULL" if full_range else b"LIMITED"))
+        self.f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s XCOLORRANGE=%s\n" % (self.w, self.h, num, den, b"420jpeg" if bits == 8 else b"420p%d" % bits,
+                                                                                 b"FULL" if full_range else b"LIMITED"))
 
     def append(self, data, shape):
-        """One I420 frame (bytes, or a uint8 array) of `shape` = (height, width, ...), written as it is."""
+        """One I420 frame (bytes, or a uint8 array; above 8 bits little-endian bytes or a uint16 array of codes) of `shape` =
+        (height, width, ...), written as it is."""
         if shape[0] != self.h or shape[1] != self.w:
             raise ValueError("frame size %r does not match the video size %r" % (tuple(shape[:2]), (self.h, self.w)))
+        if isinstance(data, np.ndarray) and data.dtype.itemsize == 2:
+            data = np.ascontiguousarray(data.astype("<u2", copy=False))
         data = memoryview(data).cast("B")
         if data.nbytes != self.frame_bytes:
             raise ValueError("an I420 frame of %d x %d has %d bytes, got %d" % (self.h, self.w, self.frame_bytes, data.nbytes))
@@ -176,8 +185,9 @@ class Y4MWriter:
         self.f.close()
 
 
-def read_y4m(path):
-    """(header fields after the magic as a list of bytes, [frame bytes]) of a YUV4MPEG2 file with 8-bit 4:2:0 frames."""
+def read_y4m(path, high_depth=False):
+    """(header fields after the magic as a list of bytes, [frame bytes]) of a YUV4MPEG2 file with 8-bit 4:2:0 frames; high_depth:
+    also C420p10 / C420p12 / C420p16 files, whose frames are twice the bytes (little-endian 16-bit samples)."""
     with open(path, "rb") as f:
         head = f.readline()
         if not head.startswith(b"YUV4MPEG2 ") or not head.endswith(b"\n"):
@@ -186,6 +196,8 @@ def read_y4m(path):
         dims = {k[:1]: int(k[1:]) for k in fields if k[:1] in (b"W", b"H")}
         w, h = dims[b"W"], dims[b"H"]
         nbytes = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+        if high_depth and any(k in Y4MReader.DEEP_COLORSPACES for k in (k[1:] for k in fields if k[:1] == b"C")):
+            nbytes *= 2
         frames = []
         while True:
             line = f.readline()
@@ -206,12 +218,17 @@ class Y4MReader:
     colorspace and full_range (XCOLORRANGE=FULL); C420jpeg, C420mpeg2, C420paldv, C420 or no C tag are read — the frames are I420
     bytes either way, the tag only names the chroma siting — and every other colour space is refused by name.  The frame offsets are
     indexed once (FRAME lines may carry parameters: frame_params), so frames are read in any order, one or a run at a time, never
-    the whole file.  A last frame shorter than frame_bytes is an error."""
+    the whole file.  A last frame shorter than frame_bytes is an error.
+    high_depth=True also reads C420p10 / C420p12 / C420p16 (ffmpeg -pix_fmt yuv420p10le ..): little-endian 16-bit samples with the code
+    in the low bits, frame_bytes doubled, `bits` = 10 / 12 / 16 (8 otherwise) and read() a uint16 array of frame_bytes / 2 samples."""
 
     COLORSPACES = (b"420jpeg", b"420mpeg2", b"420paldv", b"420")
+    DEEP_COLORSPACES = {b"420p10": 10, b"420p12": 12, b"420p16": 16}
 
-    def __init__(self, path):
+    def __init__(self, path, high_depth=False):
         self.path = path
+        self.high_depth = bool(high_depth)
+        self.bits = 8
         self.f = open(path, "rb")
         try:
             self._parse()
@@ -242,7 +259,9 @@ class Y4MReader:
                 self.aspect = val.decode()
             elif tag == b"C":
                 self.colorspace = val.decode()
-                if val not in self.COLORSPACES:
+                if self.high_depth and val in self.DEEP_COLORSPACES:
+                    self.bits = self.DEEP_COLORSPACES[val]
+                elif val not in self.COLORSPACES:
                     raise ValueError("%s: colour space C%s is not supported (8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420paldv, C420)"
                                      % (path, val.decode()))
             elif k.startswith(b"XCOLORRANGE="):
@@ -251,7 +270,8 @@ class Y4MReader:
             raise ValueError("%s: the header names no frame size" % path)
         if self.fps is not None and (self.fps[0] < 1 or self.fps[1] < 1):
             self.fps = None                         # F0:0 = unknown
-        self.frame_bytes = self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
+        self.frame_samples = self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
+        self.frame_bytes = self.frame_samples * (1 if self.bits == 8 else 2)
         size = os.fstat(f.fileno()).st_size
         self.offsets, self.frame_params = [], []
         pos = f.tell()
@@ -271,7 +291,7 @@ class Y4MReader:
         return len(self.offsets)
 
     def read_into(self, i, dst):
-        """Frame i into `dst`, a writable C-contiguous uint8 buffer of frame_bytes."""
+        """Frame i into `dst`, a writable C-contiguous buffer of frame_bytes (uint8; uint16 samples for a high-depth file)."""
         view = memoryview(dst).cast("B")
         if view.nbytes != self.frame_bytes:
             raise ValueError("a frame has %d bytes, the buffer %d" % (self.frame_bytes, view.nbytes))
@@ -280,14 +300,18 @@ class Y4MReader:
             raise ValueError("%s: truncated frame %d" % (self.path, i))
 
     def read(self, i):
-        out = np.empty(self.frame_bytes, np.uint8)
+        out = np.empty(self.frame_samples, np.uint8 if self.bits == 8 else np.uint16)
         self.read_into(i, out)
+        if self.bits > 8 and sys.byteorder != "little":
+            out.byteswap(inplace=True)
         return out
 
     def read_run(self, i0, dst):
-        """Frames i0 .. i0 + len(dst) - 1 into the rows of `dst`, uint8 [m][frame_bytes]."""
+        """Frames i0 .. i0 + len(dst) - 1 into the rows of `dst`, uint8 [m][frame_bytes] (a high-depth file: uint16 [m][frame_samples])."""
         for j in range(len(dst)):
             self.read_into(i0 + j, dst[j])
+        if self.bits > 8 and sys.byteorder != "little":
+            dst.byteswap(inplace=True)
 
     def close(self):
         self.f.close()
@@ -303,15 +327,15 @@ def is_y4m(video_path):
     return video_path is not None and video_path.lower().endswith(".y4m")
 
 
-def video_sink(video_path, fps, yuv=("bt601", False), quality=95):
+def video_sink(video_path, fps, yuv=("bt601", False), quality=95, bits=8):
     """(encode(img) -> (bytes, shape) for the worker threads, open(shape) -> writer with append(bytes, shape) / release()) for a video
-    target: YUV4MPEG2 for *.y4m (video.bgr_to_yuv420 with the matrix of `yuv` = (standard, full_range)), else Motion-JPEG AVI."""
+    target: YUV4MPEG2 for *.y4m (video.bgr_to_yuv420 with the matrix of `yuv` = (standard, full_range), at `bits` bits), else Motion-JPEG AVI."""
     if is_y4m(video_path):
         import importlib
         video = importlib.import_module("rerevst-code_amd.video")
-        m = video.yuv_matrix(*yuv)
-        return (lambda img: (video.bgr_to_yuv420(img, m, "i420").tobytes(), img.shape),
-                lambda shape: Y4MWriter(video_path, fps, shape[1], shape[0], full_range=yuv[1]))
+        m = video.yuv_matrix(*yuv, bits=bits)
+        return (lambda img: (video.bgr_to_yuv420(img, m, "i420", bits=bits).astype("<u2" if bits > 8 else np.uint8, copy=False).tobytes(), img.shape),
+                lambda shape: Y4MWriter(video_path, fps, shape[1], shape[0], full_range=yuv[1], bits=bits))
     return (lambda img: (_encode_jpeg(img, quality), img.shape),
             lambda shape: MJPGWriter(video_path, fps, shape[1], shape[0], quality))
 
@@ -337,11 +361,11 @@ def _encode_jpeg(img, quality):
     return buf.getvalue()
 
 
-def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601", False)):
+def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601", False), bits=8):
     """generate_real_video.py:175-186 as written there: re-read the result frames (sorted) and write the MJPG AVI (or the Y4M stream).
     Used when several ranks wrote the frames; decode + encode on the worker threads, the muxer appends in order."""
     writer = None
-    encode, open_writer = video_sink(video_path, fps, yuv, quality)
+    encode, open_writer = video_sink(video_path, fps, yuv, quality, bits=bits)
     for data, shape in pool.map(lambda p: encode(read_image_bgr(p)), paths):
         if writer is None:
             writer = open_writer(shape)
@@ -351,7 +375,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
-                  io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False)):
+                  io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -364,7 +388,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     video_path: *.y4m = a YUV4MPEG2 stream (Y4MWriter) with the matrix `yuv` = (standard, full_range), else the Motion-JPEG AVI.
     write_frames=False: no image files, only the video (one rank).  A .y4m target then takes the I420 bytes straight from a model
     that converts on the GPU (Stylization.yuv_output: transfer_frames(out_format="i420")), appended unchanged; in every other case
-    the Y4M frames are video.bgr_to_yuv420 of the float frames."""
+    the Y4M frames are video.bgr_to_yuv420 of the float frames.  bit_depth 10 / 12 / 16: a C420p10 / p12 / p16 stream
+    (out_format="i420p10" ..: the codes are roundings of the float32 result, not of its 8-bit form)."""
     import importlib
     import time
     from collections import deque
@@ -380,7 +405,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     nthreads = int(io_threads or default_io_threads())
     use_global = getattr(model, "use_Global", True)
     y4m = is_y4m(video_path)
-    encode, open_writer = video_sink(video_path, fps, yuv) if video_path is not None else (None, None)
+    bit_depth = int(bit_depth) if y4m else 8
+    yuv_fmt, yuv_dtype = ("i420", np.uint8) if bit_depth == 8 else ("i420p%d" % bit_depth, np.uint16)
+    encode, open_writer = video_sink(video_path, fps, yuv, bits=bit_depth) if video_path is not None else (None, None)
     t_start = time.perf_counter()
     with ThreadPoolExecutor(nthreads) as pool:
         # ---- once per video (generate_real_video.py:95-146); the sampled frames are decoded in parallel
@@ -435,7 +462,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         # only a .y4m to write and a model that converts on the GPU: the chunk's I420 bytes go from its output buffer to the file
         direct = fast and y4m and not write_frames and getattr(model, "yuv_output", False) is True
         if direct:
-            model.set_yuv_matrix(*yuv)
+            model.set_yuv_matrix(*yuv, **({"bits": bit_depth} if bit_depth > 8 else {}))
         gpu_s = 0.0
         if fast:
             # The reference reshapes every frame on its own (generate_real_video.py:152-171) and so accepts a list of mixed
@@ -454,7 +481,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             biggest = max(h * w for h, w in sizes)
             in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
             if direct:
-                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w) for h, w in sizes),), np.uint8) for _ in range(nbuf)]
+                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w) for h, w in sizes),), yuv_dtype) for _ in range(nbuf)]
             else:
                 out_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), out_dtype) for _ in range(nbuf)]
 
@@ -494,7 +521,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     f.result()
                 t0 = time.perf_counter()
                 src, dst = views(k)
-                styled = on_device(src, out=dst, out_format="i420") if direct else on_device(src, out=dst)
+                styled = on_device(src, out=dst, out_format=yuv_fmt) if direct else on_device(src, out=dst)
                 gpu_s += time.perf_counter() - t0
                 submit_decode(k + 2)             # its input buffer was chunk k-1's: consumed
                 futs = []
@@ -550,7 +577,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         if barrier is not None:
             barrier()
         if video_path is not None and world > 1 and rank == 0:
-            mux_video_from_files([os.path.join(out_dir, os.path.basename(p)) for p in sorted(frame_paths)], video_path, fps, pool, yuv=yuv)
+            mux_video_from_files([os.path.join(out_dir, os.path.basename(p)) for p in sorted(frame_paths)], video_path, fps, pool, yuv=yuv, bits=bit_depth)
     if stats is not None:
         stats.update(prep_s=t_prep - t_start, frames=hi - lo, frames_s=t_frames - t_prep, gpu_call_s=gpu_s, io_threads=nthreads,
                      frames_per_s=(hi - lo) / max(t_frames - t_prep, 1e-9))
@@ -558,13 +585,15 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
-                yuv=("bt601", False), io_threads=None):
+                yuv=("bt601", False), io_threads=None, bit_depth=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
     write_frames=False: transfer_frames(in_format="i420", out_format="i420"), the output bytes appended unchanged (matrix `yuv`); with
     image files the chunk's frames are written as stylize_files writes them, named frame_%06d.png (io_threads encode workers, as in
-    stylize_files); any other video_path is the Motion-JPEG AVI.  One rank; returns the paths written."""
+    stylize_files); any other video_path is the Motion-JPEG AVI.  One rank; returns the paths written.
+    A C420p10 / p12 / p16 input (Y4MReader(high_depth=True)) is fed as in_format "i420p10" / "i420p12" / "i420p16", uint16 samples.
+    bit_depth: the depth of a .y4m output, 8 / 10 / 12 / 16; None (default): the input file's depth."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -576,35 +605,41 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     if write_frames:
         os.makedirs(out_dir, exist_ok=True)
     nthreads = int(io_threads or default_io_threads())
-    with Y4MReader(y4m_path) as reader, ThreadPoolExecutor(nthreads) as pool, ThreadPoolExecutor(1) as rpool, ThreadPoolExecutor(1) as vpool:
-        n, H, W, fb = len(reader), reader.height, reader.width, reader.frame_bytes
+    with Y4MReader(y4m_path, high_depth=True) as reader, ThreadPoolExecutor(nthreads) as pool, ThreadPoolExecutor(1) as rpool, ThreadPoolExecutor(1) as vpool:
+        n, H, W, fb = len(reader), reader.height, reader.width, reader.frame_samples
+        in_bits = reader.bits
+        out_bits = in_bits if bit_depth is None else int(bit_depth)
+        fmt_of = lambda bits: "i420" if bits == 8 else "i420p%d" % bits
+        in_fmt, out_fmt = fmt_of(in_bits), fmt_of(out_bits)
+        in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
+        deep = lambda bits: {"bits": bits} if bits > 8 else {}
         if n < 1:
             raise ValueError("%s holds no frame" % y4m_path)
         y4m = is_y4m(video_path)
         if fps is None:                          # the file's rate: the exact fraction for a Y4M header, a float for the AVI muxer
             fps = 24 if reader.fps is None else reader.fps if y4m else reader.fps[0] / reader.fps[1]
         size = (H, W)
-        encode, open_writer = video_sink(video_path, fps, yuv) if video_path is not None else (None, None)
+        encode, open_writer = video_sink(video_path, fps, yuv, bits=out_bits if y4m else 8) if video_path is not None else (None, None)
         t_start = time.perf_counter()
-        model.set_yuv_input_matrix(yuv[0], reader.full_range)
+        model.set_yuv_input_matrix(yuv[0], reader.full_range, **deep(in_bits))
         model.prepare_style(read_image_bgr(style_path))
         if getattr(model, "use_Global", True):
             ids = video.sample_indices(n)
             log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
             model.clean()
             for i in ids:
-                model.add(reader.read(i), in_format="i420", size=size)
+                model.add(reader.read(i), in_format=in_fmt, size=size)
             model.compute()
         t_prep = time.perf_counter()
         direct = y4m and not write_frames
         if direct:
-            model.set_yuv_matrix(*yuv)
+            model.set_yuv_matrix(*yuv, **deep(out_bits))
         out_dtype = np.uint8 if uint8_output(model) and not y4m else np.float32
         pkg_empty = getattr(importlib.import_module("rerevst-code_amd"), "pinned_empty", None)
         nbuf = 3
         chunk = max(1, min(int(chunk), n))
-        in_buf = [_host_buffer(pkg_empty, (chunk, fb), np.uint8) for _ in range(nbuf)]
-        out_buf = [_host_buffer(pkg_empty, (chunk, fb) if direct else (chunk, H, W, 3), np.uint8 if direct else out_dtype) for _ in range(nbuf)]
+        in_buf = [_host_buffer(pkg_empty, (chunk, fb), in_dtype) for _ in range(nbuf)]
+        out_buf = [_host_buffer(pkg_empty, (chunk, fb) if direct else (chunk, H, W, 3), yuv_dtype if direct else out_dtype) for _ in range(nbuf)]
         starts = list(range(0, n, chunk))
         written, writer, gpu_s = [], None, 0.0
 
@@ -636,9 +671,9 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
             src, dst = in_buf[k % nbuf][:m], out_buf[k % nbuf][:m]
             t0 = time.perf_counter()
             if direct:
-                styled = model.transfer_frames(src, out=dst, out_format="i420", in_format="i420", size=size)
+                styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size)
             else:
-                styled = model.transfer_frames(src, out=dst, in_format="i420", size=size)
+                styled = model.transfer_frames(src, out=dst, in_format=in_fmt, size=size)
             gpu_s += time.perf_counter() - t0
             if direct:
                 busy[k % nbuf] = [vpool.submit(append_frames, [(fr, (H, W)) for fr in styled])]
@@ -666,7 +701,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
 
 
 def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_path=None, fps=24, chunk=16, style_size=(384, 384), log=print,
-                             io_threads=None, write_frames=True, yuv=("bt601", False)):
+                             io_threads=None, write_frames=True, yuv=("bt601", False), bit_depth=8):
     """"Multi-style Interpolation/test.py" on files (VideoStylization :40-111 + the loop :114-131): styles resized to
     384x384, every frame padded and encoded once (features cached by the model), every 16th + the last feature sampled,
     then frame i with the weight ramp; output frames are numbered %d.png as the reference writes them (:131).
@@ -680,7 +715,7 @@ def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_pat
     if write_frames:
         os.makedirs(out_dir, exist_ok=True)
     y4m = is_y4m(video_path)
-    encode, open_writer = video_sink(video_path, fps, yuv) if video_path else (None, None)
+    encode, open_writer = video_sink(video_path, fps, yuv, bits=int(bit_depth) if y4m else 8) if video_path else (None, None)
     n, S = len(frame_paths), len(style_paths)
     nthreads = int(io_threads or default_io_threads())
     with ThreadPoolExecutor(nthreads) as pool:
@@ -781,14 +816,16 @@ def main(argv=None, model_factory=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--style", required=True, nargs="+", help="one style image, or several for multi-style interpolation")
-    ap.add_argument("--frames", required=True, help="glob pattern of the content frames, or one .y4m file (8-bit 4:2:0), read by the GPU as it is")
+    ap.add_argument("--frames", required=True, help="glob pattern of the content frames, or one .y4m file (4:2:0; 8, 10, 12 or 16 bits), read by the GPU as it is")
     ap.add_argument("--checkpoint", required=True, help="style_net-TIP-final.pth (or 'synthetic' for seeded weights)")
     ap.add_argument("--out", required=True, help="directory for the stylized frames")
-    ap.add_argument("--video", default=None, help="also write a video here: Motion-JPEG for .avi, uncompressed YUV4MPEG2 (8-bit 4:2:0) for .y4m")
+    ap.add_argument("--video", default=None, help="also write a video here: Motion-JPEG for .avi, uncompressed YUV4MPEG2 (4:2:0, see --bit-depth) for .y4m")
     ap.add_argument("--no-frames", action="store_true", help="write no image files, only --video (one GPU); a .y4m then takes the I420 bytes "
                     "converted on the GPU")
     ap.add_argument("--yuv", choices=("bt601", "bt709"), default="bt601", help="colour matrix of a .y4m video, written and read")
     ap.add_argument("--full-range", action="store_true", help="full-range (0..255) Y4M instead of limited range (16..235 / 16..240)")
+    ap.add_argument("--bit-depth", type=int, choices=(8, 10, 12, 16), default=None, help="sample depth of a .y4m video: C420jpeg for 8, C420p10 / p12 / p16 "
+                    "above (default: 8, or the depth of a .y4m input)")
     ap.add_argument("--fps", type=float, default=None, help="frame rate of --video (default: 24, or the rate of a .y4m input)")
     ap.add_argument("--no-global", action="store_true", help="per-frame statistics (use_Global=False)")
     ap.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK, else 0)")
@@ -801,6 +838,8 @@ def main(argv=None, model_factory=None):
         ap.error("--no-frames needs --video: nothing would be written")
     if args.no_frames and args.gpus > 1:
         ap.error("--no-frames runs on one GPU: the ranks' frames reach the video through their files")
+    if args.bit_depth is not None and not is_y4m(args.video):
+        ap.error("--bit-depth belongs to --video out.y4m")
     y4m_in = is_y4m(args.frames)
     if y4m_in and args.gpus > 1:
         ap.error("--gpus N with a .y4m input is not supported: a .y4m is stylized on one GPU")
@@ -852,14 +891,14 @@ def main(argv=None, model_factory=None):
     t0 = time.perf_counter()
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
-                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None)
+                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
-                                 write_frames=not args.no_frames, yuv=(args.yuv, args.full_range))
+                                 write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8)
     else:
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
-                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range))
+                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

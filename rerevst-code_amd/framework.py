@@ -117,25 +117,58 @@ def _output(shape, dtype, out):
 
 
 # ===== 8-bit YUV 4:2:0 output (the rrv_*_yuv entries; include/rerevst_hip.h states the arithmetic) =====
-_YUV_LAYOUTS = {"i420": _lib.LAY_I420, "nv12": _lib.LAY_NV12}
+# 10 / 12 / 16-bit forms (RRV_LAY_I420_16 / RRV_LAY_P016): uint16 samples; the format name carries the depth.  "i420pNN": planar, the code in the
+# low bits (ffmpeg yuv420pNNle, Y4M C420pNN); "p0NN": semi-planar, the code in the high bits (ffmpeg p0NNle, hardware decoders / encoders)
+_YUV_LAYOUTS = {"i420": _lib.LAY_I420, "nv12": _lib.LAY_NV12,
+                "i420p10": _lib.LAY_I420_16, "i420p12": _lib.LAY_I420_16, "i420p16": _lib.LAY_I420_16,
+                "p010": _lib.LAY_P016, "p012": _lib.LAY_P016, "p016": _lib.LAY_P016}
+_YUV_BITS = {"i420": 8, "nv12": 8, "i420p10": 10, "i420p12": 12, "i420p16": 16, "p010": 10, "p012": 12, "p016": 16}
+_YUV_NAMES = "'i420', 'nv12', 'i420p10' / 'p12' / 'p16' or 'p010' / 'p012' / 'p016'"
 _YUV_STANDARDS = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709}
 
 
-def yuv_frame_bytes(H, W):
-    """Bytes of one H x W frame in I420 or NV12: H*W luma bytes and two chroma planes of ceil(H/2) x ceil(W/2)."""
-    return int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)
+def _yuv_np_dtype(fmt):
+    return np.dtype(np.uint8 if _YUV_BITS[fmt] == 8 else np.uint16)
 
 
-def yuv_planes(buf, H, W, layout="i420"):
+def _yuv_torch_dtypes(fmt):
+    """torch dtypes of a YUV tensor in format `fmt`, the preferred one first: torch.uint8 at 8 bits; above, torch.uint16 where this
+    torch has it, and torch.int16 holding the same bits (x.view(torch.int16))"""
+    import torch
+    if _YUV_BITS[fmt] == 8:
+        return (torch.uint8,)
+    return ((torch.uint16,) if hasattr(torch, "uint16") else ()) + (torch.int16,)
+
+
+def _yuv_depth(bits):
+    if bits not in (8, 10, 12, 16):
+        raise ValueError("bits must be 8, 10, 12 or 16, got %r" % (bits,))
+    return int(bits)
+
+
+def yuv_frame_bytes(H, W, bits=8):
+    """Bytes of one H x W frame in I420 or NV12: H*W luma samples and two chroma planes of ceil(H/2) x ceil(W/2); bits = 10, 12, 16: the
+    same samples in uint16, twice the bytes.  yuv_frame_bytes(H, W) is also the SAMPLE count of a frame at any depth: the last axis of
+    the arrays the YUV formats take and return."""
+    return (int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
+
+
+def yuv_planes(buf, H, W, layout="i420", bits=8):
     """Views (Y [..][H][W], Cb, Cr [..][CH][CW]) of uint8 frames [..][yuv_frame_bytes(H, W)] as transfer_batch / transfer_frames /
     transfer_tensor(out_format / out_layout = "i420" | "nv12") return them (a numpy array or a torch tensor).  Nothing is copied:
-    for "nv12" the chroma views are strided (every second byte of the interleaved plane)."""
+    for "nv12" the chroma views are strided (every second byte of the interleaved plane).  bits = 10, 12, 16 (or a layout name that
+    carries the depth: "i420p10", "p010", ..): uint16 samples [..][yuv_frame_bytes(H, W)], the same planes; the samples are returned
+    as stored ("p010": the code in the high bits)."""
     if layout not in _YUV_LAYOUTS:
-        raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+        raise ValueError("layout must be %s, got %r" % (_YUV_NAMES, layout))
+    bits = _yuv_depth(bits) if _YUV_BITS[layout] == 8 else _YUV_BITS[layout]
+    layout = "i420" if _YUV_LAYOUTS[layout] in (_lib.LAY_I420, _lib.LAY_I420_16) else "nv12"
+    if getattr(buf.dtype, "itemsize", None) is not None and buf.dtype.itemsize != (1 if bits == 8 else 2):
+        raise ValueError("%d-bit samples are %d bytes each, got %s" % (bits, 1 if bits == 8 else 2, buf.dtype))
     H, W = int(H), int(W)
     CH, CW = (H + 1) // 2, (W + 1) // 2
     if buf.shape[-1] != yuv_frame_bytes(H, W):
-        raise ValueError("a %d x %d frame has %d bytes, got %d" % (H, W, yuv_frame_bytes(H, W), buf.shape[-1]))
+        raise ValueError("a %d x %d frame has %d samples, got %d" % (H, W, yuv_frame_bytes(H, W), buf.shape[-1]))
     lead = tuple(buf.shape[:-1])
     y = buf[..., :H * W].reshape(lead + (H, W))
     if layout == "i420":
@@ -144,30 +177,31 @@ def yuv_planes(buf, H, W, layout="i420"):
     return y, c[..., 0], c[..., 1]
 
 
-def yuv_matrix(standard="bt601", full_range=False):
-    """rrv_yuv_matrix: the float32 [3][4] matrix (rows Y, Cb, Cr; columns R, G, B, offset) of a standard and range; needs no GPU."""
+def yuv_matrix(standard="bt601", full_range=False, bits=8):
+    """rrv_yuv_matrix[_depth]: the float32 [3][4] matrix (rows Y, Cb, Cr; columns R, G, B, offset) of a standard and range, to codes of
+    `bits` bits (8, 10, 12, 16); needs no GPU."""
     if standard not in _YUV_STANDARDS:
         raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
     m = np.empty((3, 4), np.float32)
-    if _lib.load().rrv_yuv_matrix(_YUV_STANDARDS[standard], int(bool(full_range)), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
-        raise ValueError("rrv_yuv_matrix refused %r" % (standard,))
+    if _lib.load().rrv_yuv_matrix_depth(_YUV_STANDARDS[standard], int(bool(full_range)), _yuv_depth(bits), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("rrv_yuv_matrix_depth refused %r" % (standard,))
     return m
 
 
-def yuv_input_matrix(standard="bt601", full_range=False):
-    """rrv_yuv_input_matrix: the float32 [3][4] matrix (rows R, G, B; columns Y, Cb, Cr, offset) that reads 8-bit YUV of a standard and
-    range, the inverse of yuv_matrix's transform; needs no GPU."""
+def yuv_input_matrix(standard="bt601", full_range=False, bits=8):
+    """rrv_yuv_input_matrix[_depth]: the float32 [3][4] matrix (rows R, G, B; columns Y, Cb, Cr, offset) that reads YUV codes of `bits`
+    bits (8, 10, 12, 16) of a standard and range, the inverse of yuv_matrix's transform; needs no GPU."""
     if standard not in _YUV_STANDARDS:
         raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
     n = np.empty((3, 4), np.float32)
-    if _lib.load().rrv_yuv_input_matrix(_YUV_STANDARDS[standard], int(bool(full_range)), n.ctypes.data_as(C.POINTER(C.c_float))) != 0:
-        raise ValueError("rrv_yuv_input_matrix refused %r" % (standard,))
+    if _lib.load().rrv_yuv_input_matrix_depth(_YUV_STANDARDS[standard], int(bool(full_range)), _yuv_depth(bits), n.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("rrv_yuv_input_matrix_depth refused %r" % (standard,))
     return n
 
 
 def _yuv_size(in_format, size):
     if in_format not in _YUV_LAYOUTS:
-        raise ValueError("in_format must be 'bgr', 'i420' or 'nv12', got %r" % (in_format,))
+        raise ValueError("in_format must be 'bgr', %s, got %r" % (_YUV_NAMES, in_format))
     if size is None or len(size) != 2:
         raise ValueError("%r frames need size=(H, W): the buffer does not carry it" % (in_format,))
     H, W = int(size[0]), int(size[1])
@@ -177,17 +211,18 @@ def _yuv_size(in_format, size):
 
 
 def yuv_frames_args(frames, in_format, size):
-    """Check 8-bit YUV 4:2:0 input frames (transfer_batch / transfer_frames / add with in_format "i420" | "nv12") without touching the
-    GPU: `frames` is a uint8 array [B][yuv_frame_bytes(H, W)] (or a list of [yuv_frame_bytes] arrays, or one such array) for
-    size=(H, W).  Returns (C-contiguous uint8 [B][frame_bytes], H, W); raises ValueError for a missing size, another dtype or a
-    wrong byte count."""
+    """Check YUV 4:2:0 input frames (transfer_batch / transfer_frames / add with in_format "i420" | "nv12", or the uint16 formats
+    "i420p10" | "i420p12" | "i420p16" | "p010" | "p012" | "p016") without touching the GPU: `frames` is a uint8 (uint16) array
+    [B][yuv_frame_bytes(H, W)] (or a list of [yuv_frame_bytes] arrays, or one such array) for size=(H, W).  Returns (C-contiguous
+    [B][frame samples], H, W); raises ValueError for a missing size, a dtype other than the format's or a wrong sample count."""
     H, W = _yuv_size(in_format, size)
     a = np.asarray(frames) if isinstance(frames, np.ndarray) else np.stack([np.asarray(f) for f in frames])
     if a.ndim == 1:
         a = a[None]
     fb = yuv_frame_bytes(H, W)
-    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != fb:
-        raise ValueError("%r frames of %d x %d are uint8 [B][%d], got %s %s" % (in_format, H, W, fb, a.dtype, a.shape))
+    dt = _yuv_np_dtype(in_format)
+    if a.dtype != dt or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != fb:
+        raise ValueError("%r frames of %d x %d are %s [B][%d], got %s %s" % (in_format, H, W, dt.name, fb, a.dtype, a.shape))
     return np.ascontiguousarray(a), H, W
 
 
@@ -208,6 +243,8 @@ def _on_device(t, what, device):
 
 def _image_desc(dtype, sp, lay, what):
     import torch
+    if lay in _YUV_LAYOUTS and _YUV_BITS[lay] > 8:      # (the caller has checked the dtype against _yuv_torch_dtypes)
+        return _lib.ImageDesc(_lib.DT_U16, _YUV_LAYOUTS[lay], _SPACES[sp])
     if dtype == torch.uint8:
         if sp != "pixel":
             raise ValueError("%s: uint8 images are in the 'pixel' space (0..255), not %r" % (what, sp))
@@ -225,7 +262,7 @@ def _check_out_layout(out_layout, out_space):
         raise ValueError("out_space must be one of %s, got %r" % (sorted(_SPACES), out_space))
     yuv = out_layout in _YUV_LAYOUTS         # uint8 [B][yuv_frame_bytes] in the "pixel" space
     if out_layout not in _LAYOUTS and not yuv:
-        raise ValueError("out_layout must be 'nchw' (RGB), 'nhwc' (BGR), 'i420' or 'nv12', got %r" % (out_layout,))
+        raise ValueError("out_layout must be 'nchw' (RGB), 'nhwc' (BGR), %s, got %r" % (_YUV_NAMES, out_layout))
     if yuv and out_space != "pixel":
         raise ValueError("an %r output is in the 'pixel' space, not %r" % (out_layout, out_space))
     return yuv
@@ -244,9 +281,9 @@ def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout,
         out_dtype = out.dtype
         if tuple(out.shape) != out_shape or not out.is_contiguous():
             raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
-    out_dtype = (torch.uint8 if yuv else torch.float32) if out_dtype is None else out_dtype
-    if yuv and out_dtype != torch.uint8:
-        raise ValueError("an %r output is torch.uint8, got %s" % (out_layout, out_dtype))
+    out_dtype = (_yuv_torch_dtypes(out_layout)[0] if yuv else torch.float32) if out_dtype is None else out_dtype
+    if yuv and out_dtype not in _yuv_torch_dtypes(out_layout):
+        raise ValueError("an %r output is %s, got %s" % (out_layout, " or ".join(str(t) for t in _yuv_torch_dtypes(out_layout)), out_dtype))
     return _image_desc(out_dtype, out_space, out_layout, "out"), out_shape, out_dtype
 
 
@@ -281,8 +318,9 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
 
 
 def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=None, out_layout=None, pad_crop=False, out=None):
-    """tensor_io_args for an 8-bit YUV 4:2:0 input tensor (transfer_tensor(layout="i420" | "nv12", size=(H, W))): x is a uint8 tensor
-    [B][yuv_frame_bytes(H, W)] (or [yuv_frame_bytes]) on cuda:`device`; out_layout defaults to `layout` (YUV in, YUV out).  The
+    """tensor_io_args for a YUV 4:2:0 input tensor (transfer_tensor(layout="i420" | "nv12" | "i420p10" | "p010" | .., size=(H, W))): x is
+    a uint8 (the uint16 formats: torch.uint16, or torch.int16 holding the same bits) tensor [B][yuv_frame_bytes(H, W)] (or
+    [yuv_frame_bytes]) on cuda:`device`; out_layout defaults to `layout` (YUV in, YUV out).  The
     output side is tensor_io_args'.  The result's in_desc is the RRV_LAY_* value of the input layout.  Raises ValueError as
     tensor_io_args does, and for a missing size or a wrong byte count."""
     import torch
@@ -291,8 +329,9 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
     _check_out_layout(out_layout, out_space)
     _on_device(x, "x", device)
     fb = yuv_frame_bytes(H, W)
-    if x.dtype != torch.uint8 or x.dim() not in (1, 2) or x.shape[-1] != fb or (x.dim() == 2 and x.shape[0] < 1):
-        raise ValueError("an %r tensor of %d x %d frames is torch.uint8 [B, %d] or [%d], got %s %s" % (layout, H, W, fb, fb, x.dtype, tuple(x.shape)))
+    if x.dtype not in _yuv_torch_dtypes(layout) or x.dim() not in (1, 2) or x.shape[-1] != fb or (x.dim() == 2 and x.shape[0] < 1):
+        raise ValueError("an %r tensor of %d x %d frames is %s [B, %d] or [%d], got %s %s" % (
+            layout, H, W, " or ".join(str(t) for t in _yuv_torch_dtypes(layout)), fb, fb, x.dtype, tuple(x.shape)))
     batched = x.dim() == 2
     B = x.shape[0] if batched else 1
     out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
@@ -451,12 +490,22 @@ class Stylization():
         if not self.use_Global:   # the reference's frame-mode TransformerNet has no add/compute/clean either
             raise RRVError("%s() belongs to Sequence-Level Global Feature Sharing (use_Global=True)" % what)
 
+    def _yuv_depth(self, in_format=None, out_format=None):
+        """the uint16 formats carry their depth: install it (rrv_set_yuv_depth) before the call that reads or writes them"""
+        bi = _YUV_BITS.get(in_format, 8)
+        bo = _YUV_BITS.get(out_format, 8)
+        if bi > 8 or bo > 8:
+            self._chk(self._lib.rrv_set_yuv_depth(self._h, bi if bi > 8 else 0, bo if bo > 8 else 0))
+
     def add(self, patch, in_format="bgr", size=None):
         """A sampled frame: uint8 BGR HWC, or with in_format "i420" / "nv12" and size=(H, W) 8-bit YUV 4:2:0 bytes
-        [yuv_frame_bytes(H, W)] (or [B][..]: every frame, in order) read by the first kernel (rrv_add_from_yuv)."""
+        [yuv_frame_bytes(H, W)] (or [B][..]: every frame, in order) read by the first kernel (rrv_add_from_yuv); in_format "i420p10" /
+        "i420p12" / "i420p16" / "p010" / "p012" / "p016": uint16 samples of that depth.  (The depth is read when the deferred encoding
+        runs: add frames of one depth between clean() and compute().)"""
         self._global_only("add")
         if in_format != "bgr":
             a, H, W = yuv_frames_args(patch, in_format, size)
+            self._yuv_depth(in_format)
             for f in a:
                 self._chk(self._lib.rrv_add_from_yuv(self._h, f.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], H, W))
             return
@@ -608,23 +657,24 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def _host_frames_yuv_in(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size):
-        """_host_frames for 8-bit YUV 4:2:0 input (the rrv_*_from_yuv entries): one call shape for every output format"""
+        """_host_frames for YUV 4:2:0 input (the rrv_*_from_yuv entries): one call shape for every output format"""
         a, H, W = yuv_frames_args(frames, in_format, size)
         B = a.shape[0]
         Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         if out_format != "bgr":
-            shape = (B, yuv_frame_bytes(Ho, Wo))
+            shape, odt = (B, yuv_frame_bytes(Ho, Wo)), _yuv_np_dtype(out_format)
             if out is None:
-                out = _outputs.empty(shape, np.uint8)
-            elif out.dtype != np.uint8 or out.shape != shape or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous uint8 array of shape %r" % (shape,))
-            desc = _lib.ImageDesc(_lib.DT_U8, _YUV_LAYOUTS[out_format], _lib.SP_PIXEL)
+                out = _outputs.empty(shape, odt)
+            elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous %s array of shape %r" % (odt.name, shape))
+            desc = _lib.ImageDesc(_lib.DT_U8 if odt == np.uint8 else _lib.DT_U16, _YUV_LAYOUTS[out_format], _lib.SP_PIXEL)
         else:
             out, u8 = _output((B, Ho, Wo, 3), dtype, out)
             desc = _lib.ImageDesc(_lib.DT_U8 if u8 else _lib.DT_F32, _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
         head = (self._h, a.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], B, H, W)
         tail = (out.ctypes.data_as(C.c_void_p), desc, _lib.TF_PAD_CROP if pad_crop else 0)
+        self._yuv_depth(in_format, out_format)
         if m is not None:
             self._chk(self._lib.rrv_transfer_mask_from_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, *tail))
         elif style_weights is not None:
@@ -639,7 +689,7 @@ class Stylization():
         weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one);
         out_format "i420" / "nv12": their _yuv forms, uint8 [B][yuv_frame_bytes] whatever `dtype` says"""
         if out_format != "bgr" and out_format not in _YUV_LAYOUTS:
-            raise ValueError("out_format must be 'bgr', 'i420' or 'nv12', got %r" % (out_format,))
+            raise ValueError("out_format must be 'bgr', %s, got %r" % (_YUV_NAMES, out_format))
         if in_format != "bgr":
             return self._host_frames_yuv_in(frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size)
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
@@ -650,12 +700,13 @@ class Stylization():
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         head = (self._h, a.ctypes.data_as(C.c_void_p), B, H, W)
         if out_format != "bgr":
-            shape = (B, yuv_frame_bytes(H, W) if pad_crop else yuv_frame_bytes(H // 8 * 8, W // 8 * 8))
+            shape, odt = (B, yuv_frame_bytes(H, W) if pad_crop else yuv_frame_bytes(H // 8 * 8, W // 8 * 8)), _yuv_np_dtype(out_format)
             if out is None:
-                out = _outputs.empty(shape, np.uint8)
-            elif out.dtype != np.uint8 or out.shape != shape or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous uint8 array of shape %r" % (shape,))
+                out = _outputs.empty(shape, odt)
+            elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous %s array of shape %r" % (odt.name, shape))
             lay, dst = _YUV_LAYOUTS[out_format], out.ctypes.data_as(C.c_void_p)
+            self._yuv_depth(None, out_format)
             if m is not None:
                 self._chk(self._lib.rrv_transfer_mask_batch_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop), lay, dst))
             elif style_weights is not None:
@@ -691,7 +742,12 @@ class Stylization():
         filled; yuv_planes() gives the planes), 1.5 bytes per pixel over PCIe; composes with style_weights / style_masks.
         in_format: "bgr" (default), or "i420" / "nv12" with size=(H, W): `frames` is a uint8 array [B][yuv_frame_bytes(H, W)] of 8-bit
         YUV 4:2:0 frames, read by the first kernel with the matrix of set_yuv_input_matrix (the rrv_*_from_yuv entries): 1.5 bytes
-        per pixel in as well, and no conversion on the host.  A wrong byte count or a missing size raises ValueError."""
+        per pixel in as well, and no conversion on the host.  A wrong byte count or a missing size raises ValueError.
+        10 / 12 / 16 bits: in_format / out_format "i420p10" | "i420p12" | "i420p16" (planar, the code in the low bits: ffmpeg's
+        yuv420p10le, Y4M C420p10) and "p010" | "p012" | "p016" (semi-planar, the code in the high bits: hardware decoders / encoders);
+        the arrays are uint16 [B][yuv_frame_bytes(H, W)] (that many SAMPLES), the name carries the depth (rrv_set_yuv_depth is called
+        here), the matrices are those of set_yuv_matrix / set_yuv_input_matrix(.., bits=) — by default BT.601 limited range at that
+        depth.  Any mix of input and output depth and layout works.  A wrong dtype or shape raises ValueError before any GPU work."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
@@ -737,7 +793,10 @@ class Stylization():
         ([yuv_frame_bytes] unbatched) in the "pixel" space; yuv_planes() gives views of the planes.
         layout "i420" / "nv12" with size=(H, W): x is a uint8 tensor [B, yuv_frame_bytes(H, W)] of 8-bit YUV 4:2:0 frames (a hardware
         decoder's NV12), read with the matrix of set_yuv_input_matrix (the rrv_*_from_yuv_device entries); out_layout then defaults
-        to the same YUV layout, and may be "nchw" / "nhwc"."""
+        to the same YUV layout, and may be "nchw" / "nhwc".
+        layout / out_layout "i420p10" | "i420p12" | "i420p16" | "p010" | "p012" | "p016": 10 / 12 / 16-bit samples as in transfer_batch,
+        in torch.uint16 tensors (this build's torch has the dtype; a torch.int16 tensor holding the same bits, x.view(torch.int16),
+        is taken too, and `out` may be one); a fresh output is torch.uint16."""
         import torch
         yuv_in = layout in _YUV_LAYOUTS
         if yuv_in:
@@ -765,6 +824,7 @@ class Stylization():
         xb = a.x if a.batched else a.x.unsqueeze(0)
         ob = out if a.batched else out.unsqueeze(0)
         flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+        self._yuv_depth(layout, layout if out_layout is None else out_layout)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for b0 in range(0, a.B, TENSOR_BATCH_MAX):
             nb = min(TENSOR_BATCH_MAX, a.B - b0)
@@ -837,31 +897,44 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_PRED, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
-    def set_yuv_matrix(self, standard="bt601", full_range=False):
+    def set_yuv_matrix(self, standard="bt601", full_range=False, bits=8):
         """The conversion matrix of the "i420" / "nv12" outputs (rrv_set_yuv_matrix): a standard ("bt601" | "bt709") and range, or
         twelve finite floats ([3][4]: rows Y, Cb, Cr; columns R, G, B, offset) in place of `standard`; None restores the default,
-        BT.601 limited range.  Read when a call launches; returns the float32 [3][4] matrix now installed."""
+        BT.601 limited range.  Read when a call launches; returns the float32 [3][4] matrix now installed.
+        bits = 10, 12, 16: the matrix of the uint16 outputs instead ("i420p10", "p010", ..: rrv_set_yuv16_matrix, independent of the
+        8-bit one), installed together with that output depth (rrv_set_yuv_depth); None: BT.601 limited range at the depth in force
+        when a call launches."""
+        bits = _yuv_depth(bits)
+        setter = self._lib.rrv_set_yuv_matrix if bits == 8 else self._lib.rrv_set_yuv16_matrix
+        if bits > 8:
+            self._chk(self._lib.rrv_set_yuv_depth(self._h, 0, bits))
         if standard is None:
-            self._chk(self._lib.rrv_set_yuv_matrix(self._h, None))
-            return yuv_matrix("bt601", False)
-        m = yuv_matrix(standard, full_range) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
+            self._chk(setter(self._h, None))
+            return yuv_matrix("bt601", False, bits)
+        m = yuv_matrix(standard, full_range, bits) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
         if m.size != 12:
             raise ValueError("a YUV matrix has 12 coefficients, got %d" % m.size)
-        self._chk(self._lib.rrv_set_yuv_matrix(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(setter(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
         return m.reshape(3, 4).copy()
 
-    def set_yuv_input_matrix(self, standard="bt601", full_range=False):
+    def set_yuv_input_matrix(self, standard="bt601", full_range=False, bits=8):
         """The conversion matrix of the "i420" / "nv12" INPUTS (rrv_set_yuv_input_matrix): a standard ("bt601" | "bt709") and range,
         or twelve finite floats ([3][4]: rows R, G, B; columns Y, Cb, Cr, offset) in place of `standard`; None restores the default,
         BT.601 limited range.  Independent of set_yuv_matrix; read when a call launches its first kernel.  Returns the float32
-        [3][4] matrix now installed."""
+        [3][4] matrix now installed.
+        bits = 10, 12, 16: the matrix of the uint16 inputs instead (rrv_set_yuv16_input_matrix), installed together with that input
+        depth; None: BT.601 limited range at the depth in force when a call launches."""
+        bits = _yuv_depth(bits)
+        setter = self._lib.rrv_set_yuv_input_matrix if bits == 8 else self._lib.rrv_set_yuv16_input_matrix
+        if bits > 8:
+            self._chk(self._lib.rrv_set_yuv_depth(self._h, bits, 0))
         if standard is None:
-            self._chk(self._lib.rrv_set_yuv_input_matrix(self._h, None))
-            return yuv_input_matrix("bt601", False)
-        n = yuv_input_matrix(standard, full_range) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
+            self._chk(setter(self._h, None))
+            return yuv_input_matrix("bt601", False, bits)
+        n = yuv_input_matrix(standard, full_range, bits) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
         if n.size != 12:
             raise ValueError("a YUV matrix has 12 coefficients, got %d" % n.size)
-        self._chk(self._lib.rrv_set_yuv_input_matrix(self._h, n.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(setter(self._h, n.ctypes.data_as(C.POINTER(C.c_float))))
         return n.reshape(3, 4).copy()
 
     def set_host_io(self, mode):

@@ -89,40 +89,60 @@ def resize_bilinear(img, size):
 YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}      # (Kr, Kb); Kg = 1 - Kr - Kb
 
 
-def yuv_matrix(standard="bt601", full_range=False):
-    """rrv_yuv_matrix on the host: float32 [3][4], rows Y, Cb, Cr, columns the coefficients of R, G, B and an offset.  Full range:
+YUV_DEPTHS = (8, 10, 12, 16)
+
+
+def _yuv_depth(bits):
+    if bits not in YUV_DEPTHS:
+        raise ValueError("bits must be 8, 10, 12 or 16, got %r" % (bits,))
+    return int(bits)
+
+
+def yuv_matrix(standard="bt601", full_range=False, bits=8):
+    """rrv_yuv_matrix[_depth] on the host: float32 [3][4], rows Y, Cb, Cr, columns the coefficients of R, G, B and an offset.  Full range:
     Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited range: Y' = 16 + 219/255 Y
-    and the chroma differences times 224/255.  Evaluated in double, each coefficient rounded once to float32."""
+    and the chroma differences times 224/255.  bits = 10, 12, 16: d-bit codes — the limited matrix times 2^(d-8); full range
+    (2^d - 1)/255 in place of 1 and 2^(d-1) in place of 128.  Evaluated in double, each coefficient rounded once to float32."""
+    d = _yuv_depth(bits)
     kr, kb = YUV_STANDARDS[standard]
     k = np.array([kr, 1.0 - kr - kb, kb], np.float64)
-    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    s, top = float(1 << (d - 8)), float((1 << d) - 1)
+    ys, cs = (top / 255.0, top / 255.0) if full_range else (219.0 / 255.0 * s, 224.0 / 255.0 * s)
     m = np.zeros((3, 4), np.float64)
     m[0, :3] = ys * k
     m[1, :3] = cs * (np.array([0.0, 0.0, 1.0]) - k) / (2.0 * (1.0 - kb))
     m[2, :3] = cs * (np.array([1.0, 0.0, 0.0]) - k) / (2.0 * (1.0 - kr))
-    m[:, 3] = (0.0 if full_range else 16.0, 128.0, 128.0)
+    m[:, 3] = (0.0 if full_range else 16.0 * s, 128.0 * s, 128.0 * s)
     return m.astype(np.float32)
 
 
-def yuv_frame_bytes(H, W):
-    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+def yuv_frame_bytes(H, W, bits=8):
+    """bytes of one H x W 4:2:0 frame: H*W + 2*CH*CW samples, one byte each at 8 bits and two above"""
+    return (H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
 
 
-def bgr_to_yuv420(img, m, layout="i420"):
+def bgr_to_yuv420(img, m, layout="i420", bits=8):
     """The GPU's YUV 4:2:0 conversion (include/rerevst_hip.h, the rrv_*_yuv entries) in numpy float32, for frames that come from files:
     img [..][H][W][3] BGR, float32 in 0..255 or uint8; m the twelve matrix floats; returns uint8 [..][yuv_frame_bytes(H, W)] in
     "i420" ([Y][Cb][Cr]) or "nv12" ([Y][CbCr]).  Every product and sum is a float32 operation in the kernel's order, so on the float32
-    output of a transfer entry this gives the bytes of its YUV form."""
+    output of a transfer entry this gives the bytes of its YUV form.  bits = 10, 12, 16 (m a matrix of that depth): uint16 samples
+    [..][H*W + 2*CH*CW], codes clamped to 0..2^bits - 1; "i420" keeps the code in the low bits (RRV_LAY_I420_16, yuv420p10le), "nv12" in
+    the high bits (RRV_LAY_P016, p010le: code << (16 - bits))."""
     if layout not in ("i420", "nv12"):
         raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    d = _yuv_depth(bits)
     f = np.asarray(img).astype(np.float32)
     m = np.asarray(m, np.float32).reshape(3, 4)
     H, W = f.shape[-3:-1]
     lead = f.shape[:-3]
     b, g, r = f[..., 0], f[..., 1], f[..., 2]
-    zero, top, quarter = np.float32(0), np.float32(255), np.float32(0.25)
+    zero, top, quarter = np.float32(0), np.float32((1 << d) - 1), np.float32(0.25)
     comp = [((m[k, 0] * r + m[k, 1] * g) + m[k, 2] * b) + m[k, 3] for k in range(3)]
-    byte = lambda v: np.rint(np.minimum(np.maximum(v, zero), top)).astype(np.uint8)
+    if d == 8:
+        byte = lambda v: np.rint(np.minimum(np.maximum(v, zero), top)).astype(np.uint8)
+    else:
+        shift = np.uint16(16 - d if layout == "nv12" else 0)
+        byte = lambda v: np.left_shift(np.rint(np.minimum(np.maximum(v, zero), top)).astype(np.uint16), shift)
     y0, x0 = np.arange(0, H, 2), np.arange(0, W, 2)
     y1, x1 = np.minimum(y0 + 1, H - 1), np.minimum(x0 + 1, W - 1)          # a row / column past the frame: its nearest one inside
     planes = [byte(comp[0]).reshape(lead + (H * W,))]
@@ -138,32 +158,42 @@ def bgr_to_yuv420(img, m, layout="i420"):
     return np.concatenate(planes, axis=-1)
 
 
-def yuv_input_matrix(standard="bt601", full_range=False):
-    """rrv_yuv_input_matrix on the host, the inverse of yuv_matrix's transform: float32 [3][4], rows R, G, B, columns the coefficients
+def yuv_input_matrix(standard="bt601", full_range=False, bits=8):
+    """rrv_yuv_input_matrix[_depth] on the host, the inverse of yuv_matrix's transform: float32 [3][4], rows R, G, B, columns the coefficients
     of Y, Cb, Cr and an offset.  Limited range: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y, C' = C - 128);
     R = Y' + 2(1-Kr) Cr', B = Y' + 2(1-Kb) Cb', G = Y' - (2 Kb (1-Kb) / Kg) Cb' - (2 Kr (1-Kr) / Kg) Cr', the offsets folded into column 3.
-    Evaluated in double, each coefficient rounded once to float32."""
+    bits = 10, 12, 16 (s = 2^(d-8)): limited range Y' = (Y / s - 16) 255/219, C' = (C / s - 128) 255/224; full range Y' = 255/(2^d - 1) Y,
+    C' = 255/(2^d - 1) (C - 2^(d-1)).  Evaluated in double, each coefficient rounded once to float32."""
+    d = _yuv_depth(bits)
     kr, kb = YUV_STANDARDS[standard]
     kg = 1.0 - kr - kb
-    ys, cs, y0 = (1.0, 1.0, 0.0) if full_range else (255.0 / 219.0, 255.0 / 224.0, 16.0)
+    s, top = float(1 << (d - 8)), float((1 << d) - 1)
+    ys, cs, y0 = (255.0 / top, 255.0 / top, 0.0) if full_range else (255.0 / 219.0 / s, 255.0 / 224.0 / s, 16.0 * s)
+    c0 = 128.0 * s
     cb = (0.0, -(2.0 * kb * (1.0 - kb) / kg), 2.0 * (1.0 - kb))
     cr = (2.0 * (1.0 - kr), -(2.0 * kr * (1.0 - kr) / kg), 0.0)
     n = np.zeros((3, 4), np.float64)
     for k in range(3):
-        n[k] = (ys, cs * cb[k], cs * cr[k], -(ys * y0) - 128.0 * (cs * cb[k]) - 128.0 * (cs * cr[k]))
+        n[k] = (ys, cs * cb[k], cs * cr[k], -(ys * y0) - c0 * (cs * cb[k]) - c0 * (cs * cr[k]))
     return n.astype(np.float32)
 
 
-def yuv420_to_bgr(buf, H, W, n, layout="i420"):
+def yuv420_to_bgr(buf, H, W, n, layout="i420", bits=8):
     """The GPU's YUV 4:2:0 input conversion (include/rerevst_hip.h, the rrv_*_from_yuv entries) in numpy float32: buf uint8
     [..][yuv_frame_bytes(H, W)] in "i420" or "nv12", n the twelve floats of the input matrix; returns float32 [..][H][W][3] BGR, the PIXEL
     frame the first kernel sees.  Pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1); every product and sum is a
-    float32 operation in the kernel's order; the value is clamped to 0..255 and not rounded."""
+    float32 operation in the kernel's order; the value is clamped to 0..255 and not rounded.  bits = 10, 12, 16 (n a matrix of that
+    depth): buf uint16 [..][H*W + 2*CH*CW]; "i420" samples are the codes, "nv12" samples carry the code in the high bits
+    (sample >> (16 - bits), the low bits ignored)."""
     if layout not in ("i420", "nv12"):
         raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    d = _yuv_depth(bits)
     buf = np.asarray(buf)
-    if buf.dtype != np.uint8 or buf.shape[-1] != yuv_frame_bytes(H, W):
-        raise ValueError("a %d x %d %s frame is %d uint8 bytes, got %s %s" % (H, W, layout, yuv_frame_bytes(H, W), buf.dtype, buf.shape))
+    dt = np.uint8 if d == 8 else np.uint16
+    if buf.dtype != dt or buf.shape[-1] != yuv_frame_bytes(H, W):
+        raise ValueError("a %d x %d %s frame at %d bits is %d %s samples, got %s %s" % (H, W, layout, d, yuv_frame_bytes(H, W), np.dtype(dt).name, buf.dtype, buf.shape))
+    if d != 8 and layout == "nv12":
+        buf = np.right_shift(buf, np.uint16(16 - d))
     n = np.asarray(n, np.float32).reshape(3, 4)
     lead = buf.shape[:-1]
     CH, CW = (H + 1) // 2, (W + 1) // 2
