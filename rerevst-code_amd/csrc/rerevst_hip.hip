@@ -155,6 +155,20 @@ struct StyleState {
     float* smean = nullptr;          // [6][32]: mean_{HW} F{1,2}.down_sample(normalised style map) of Filter1..3 (FilterPredictor's style half, constant per style)
 };
 
+// Format of the frames an encoder launch reads: form = IN_* (the conv_first_k instantiation), space = SP_* of a float32 form.  It travels
+// with the request (Xfer::in, the pending sampled frames), never on the handle.
+struct InFmt { int form, space; };
+constexpr InFmt IN_BGR8{IN_U8_HWC, SP_PIXEL};      // uint8 HWC BGR PIXEL: what every entry without a descriptor or an in_layout takes
+inline bool operator!=(InFmt a, InFmt b) { return a.form != b.form || a.space != b.space; }
+
+// The YUV conversion state of one direction (rrv_ctx::yuv_in: rows R, G, B x (Y, Cb, Cr, offset); yuv_out: rows Y, Cb, Cr x (R, G, B, offset)),
+// read when a launch is queued (yuv_launch_params): launches already queued keep what they were queued with.
+struct YuvSide {
+    float m8[12];                         // the 8-bit forms' matrix (rrv_set_yuv_[input_]matrix); BT.601 limited range at rrv_create
+    float m16[12]; bool set16 = false;    // the uint16 forms' own (rrv_set_yuv16_[input_]matrix); not set: BT.601 limited range at the depth in force at launch
+    int bits = 10;                        // code depth of the uint16 forms (rrv_set_yuv_depth)
+};
+
 }  // namespace
 
 // Layers that run F(4x4,3x3) where the launch geometry lets it win (use_f43): bit 0..6 = encoder conv1_2, conv2_1, conv2_2,
@@ -173,7 +187,6 @@ struct rrv_ctx {
     int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots (stream, workspace) pairs
     hipEvent_t slot_ev[RRV_MAX_SLOTS] = {nullptr};   // ordering against the caller's stream (rrv_set_caller_stream)
     hipStream_t caller_stream = nullptr; bool caller_sync = false;
-    int in_form = IN_U8_HWC, in_space = SP_PIXEL;    // the content frames' form (conv_first_k<IN>) while rrv_transfer_image_device runs; uint8 BGR HWC otherwise
     int user_style = -1;                             // style the plain transfer entries use (first computed / last set_state)
     std::string err;
     std::map<std::string, std::vector<float>> hostw;
@@ -226,7 +239,7 @@ struct rrv_ctx {
     // frames handed to rrv_add wait here (uint8, HBM) and are encoded together, 8 per encoder launch, when their
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
-    int pend_form = IN_U8_HWC, pend_space = SP_PIXEL;      // form of the pending frames (rrv_add_image_device keeps a frame as it arrived; conv_first_k<IN> reads it)
+    InFmt pend_in = IN_BGR8;          // format of the pending frames (a frame is kept as it arrived; conv_first_k<IN> reads it)
     // Weights of the blended frame entries (run_xfer, Model::BLEND), per slot 0 / 1: [64][RRV_MAX_STYLES] floats in HBM, which blend_states_dev_k
     // reads, and for host weights a page-locked ring of BLEND_W_RING such blocks: a call fills the next block and copies it on the slot's
     // stream; a block is reused BLEND_W_RING calls later, after its copy's event (long past: no host wait in a running pipeline)
@@ -258,13 +271,7 @@ struct rrv_ctx {
     bool f43_path = false;            // true inside transfer_device only: the preparation pass (prepare_style / add / compute, frame mode) always runs F(2x2,3x3)
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
-    float yuv_in_m[12];               // rrv_set_yuv_input_matrix: rows R, G, B x (Y, Cb, Cr, offset) of the YUV input forms; read at launch (run_encoder), BT.601 limited range at rrv_create
-    // the uint16 YUV forms (RRV_LAY_I420_16 / RRV_LAY_P016): code depths (rrv_set_yuv_depth) and matrices of their own (rrv_set_yuv16_[input_]matrix);
-    // while a matrix is not set, the launch takes BT.601 limited range at the depth then in force
-    int yuv_in_bits = 10, yuv_out_bits = 10;
-    bool yuv16_in_set = false, yuv16_set = false;
-    float yuv16_in_m[12], yuv16_m[12];
-    float yuv_m[12];                  // rrv_set_yuv_matrix: rows Y, Cb, Cr x (R, G, B, offset) of the YUV store form; read at launch (run_last), BT.601 limited range at rrv_create
+    YuvSide yuv_in, yuv_out;          // YUV 4:2:0 input (run_encoder) and output (run_last) conversion
     int host_io = 0;                  // rrv_set_host_io: 0 = staged H2D / D2H copies, 1 = zero copy (kernels read / write page-locked host memory), 2 = input only, 3 = output only
     int n_cus = 256;
     int debug = 0;                    // rrv_set_debug / RRV_DEBUG: 1 = sync + check after every API call, 2 = after every kernel launch
@@ -965,10 +972,23 @@ Plan& pick_plan(rrv_handle h, Plan (&v)[2], int B, int H, int W) {
 // unpadded source frame behind a padded geometry (ReshapeTool on the device): pad on the way in, crop on the way out
 struct PadCrop { int src_H, src_W, top, left; };
 
-// nb: images to encode (plans are grow-only, so a plan may hold room for more)
+// What a launch of a YUV form takes from one direction's state: the twelve coefficients, the shift between a code and a stored sample (P016
+// keeps the code in the high bits) and the largest code.  wide: a uint16 form; msb: P016.
+struct YuvLaunch { float m[12]; int shift; float hi; };
+YuvLaunch yuv_launch_params(const YuvSide& s, bool input, bool wide, bool msb) {
+    YuvLaunch l;
+    const int d = wide ? s.bits : 8;      // (8 bits: shift 0, hi 255 — the 8-bit kernels read neither)
+    if (!wide) memcpy(l.m, s.m8, sizeof l.m);
+    else if (s.set16) memcpy(l.m, s.m16, sizeof l.m);
+    else (void)(input ? rrv_yuv_input_matrix_depth : rrv_yuv_matrix_depth)(RRV_YUV_BT601, 0, d, l.m);
+    l.shift = msb ? 16 - d : 0; l.hi = (float)((1 << d) - 1);
+    return l;
+}
+
+// in: the format of the images at d_img.  nb: images to encode (plans are grow-only, so a plan may hold room for more)
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
 // norm0_bstride != 0: image b's Decoder.norm[0] entry is norm0 + b * norm0_bstride (per-image state sets)
-int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
+int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
                 int norm0_bstride = 0) {
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
@@ -994,16 +1014,15 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, int which, const
         for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, *W_(i), B, lh[i], lw[i], le[i], false, 0, false);
         h->enc_p8_tables = p8;
     }
-    const int inf = h->in_form;      // (the style encoder reads the same forms, in colour: rrv_prepare_style_image_device)
+    const int inf = in.form;         // (the style encoder reads the same forms, in colour: rrv_prepare_style_image_device)
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
-              h->in_space};
+              in.space};
     stamp(h, p8 ? &e.q11 : &e.c11, B);
-    if (in_yuv16(inf)) {
-        if (h->yuv16_in_set) memcpy(fp.yuv_n, h->yuv16_in_m, sizeof fp.yuv_n);
-        else (void)rrv_yuv_input_matrix_depth(RRV_YUV_BT601, 0, h->yuv_in_bits, fp.yuv_n);
-        fp.yuv_shift = inf == IN_YUV_P016 ? 16 - h->yuv_in_bits : 0;
-    } else if (in_yuv(inf)) memcpy(fp.yuv_n, h->yuv_in_m, sizeof fp.yuv_n);
+    if (in_yuv(inf)) {
+        const YuvLaunch y = yuv_launch_params(h->yuv_in, true, in_yuv16(inf), inf == IN_YUV_P016);
+        memcpy(fp.yuv_n, y.m, sizeof fp.yuv_n); fp.yuv_shift = y.shift;
+    }
     static void (*const first_k[IN_FORMS])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>,
                                                       conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>, conv_first_k<IN_YUV_I420_16>, conv_first_k<IN_YUV_P016>};
     RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? 1.5 * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
@@ -1047,14 +1066,16 @@ struct OutFmt { bool u8, chw; int space; int yuv = 0; };
 constexpr bool yuv16_layout(int layout) { return layout == RRV_LAY_I420_16 || layout == RRV_LAY_P016; }
 inline size_t yuv_sample_bytes(OutFmt f) { return yuv16_layout(f.yuv) ? sizeof(uint16_t) : 1; }
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
-constexpr OutFmt out_yuv(int layout) { return OutFmt{true, false, SP_PIXEL, layout}; }
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
+// How one launch sequence reads and writes its frames: both formats and, for the pad geometry, the source window (nullptr: plain frames)
+struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; };
 
 int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
-// One transfer as an entry states it.  The model is named, never inferred from which pointer is set; everything the entries derive
-// from the request (kernel geometry, bytes and elements per frame, the pad and crop window) is computed here and nowhere else.
+// One transfer as an entry states it, both formats included (in, fmt): nothing about a call is kept on the handle, so a format cannot leak
+// into the next call.  The model is named, never inferred from which pointer is set; everything the entries derive from the request
+// (kernel geometry, bytes and elements per frame, the pad and crop window) is computed here and nowhere else.
 //   GLOBAL: Stylization(use_Global=True), one shared state set          FRAME: use_Global=False, statistics per frame
 //   BLEND:  frame b with sum_s wts[b][s] x the state of style s         MASK:  the styles blended per pixel by float32 masks
 enum class Model { GLOBAL, FRAME, BLEND, MASK };
@@ -1070,10 +1091,11 @@ struct Xfer {
     const float* mask = nullptr;    // MASK: [mask_images][ns][H][W], mask_images = B, or 1 = one mask for every frame
     int mask_images = 0;
     bool w_dev = false;             // BLEND: wts is in HBM, written by work the slot's stream is ordered behind
+    InFmt in = IN_BGR8;             // format of the content frames (the descriptor and _from_yuv entries set it)
 
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
-    size_t in_bytes(rrv_handle h) const { return in_frame_bytes(h->in_form, H, W); }                               // per frame, in the scoped input form
+    size_t in_bytes() const { return in_frame_bytes(in.form, H, W); }                                              // per frame, in x.in
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
         return fmt.yuv ? (pad ? yuv_frame_samples(H, W) : yuv_frame_samples(H / 8 * 8, W / 8 * 8)) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
@@ -1251,13 +1273,8 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
     if (fmt.yuv) {
         if (pc && ((pc->top | pc->left) & 1)) return fail(h, RRV_E_ARG, "conv_last: the YUV form needs an even crop origin");
-        if (yuv16_layout(fmt.yuv)) {
-            const int d = h->yuv_out_bits;
-            if (h->yuv16_set) memcpy(lp.yuv_m, h->yuv16_m, sizeof lp.yuv_m);
-            else (void)rrv_yuv_matrix_depth(RRV_YUV_BT601, 0, d, lp.yuv_m);
-            lp.yuv_hi = (float)((1 << d) - 1);
-            lp.yuv_shift = fmt.yuv == RRV_LAY_P016 ? 16 - d : 0;
-        } else memcpy(lp.yuv_m, h->yuv_m, sizeof lp.yuv_m);
+        const YuvLaunch y = yuv_launch_params(h->yuv_out, false, yuv16_layout(fmt.yuv), fmt.yuv == RRV_LAY_P016);
+        memcpy(lp.yuv_m, y.m, sizeof lp.yuv_m); lp.yuv_hi = y.hi; lp.yuv_shift = y.shift;
         lp.yuv_nv12 = fmt.yuv == RRV_LAY_NV12 || fmt.yuv == RRV_LAY_P016;
     }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
@@ -1271,8 +1288,9 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
 // feat != nullptr: skip the encoder and start from a cached raw relu4_1 feature (ring layout, [1,H/8,W/8,512])
 // feats != nullptr (with h->state_images == B): one cached feature per image, each normalised with ITS state set
 // slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
-int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, const float* feat = nullptr,
-                    const PadCrop* pc = nullptr, const float* const* feats = nullptr) {
+int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* feat = nullptr,
+                    const float* const* feats = nullptr) {
+    const PadCrop* const pc = io.pc;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     // Any frame size, as the reference: the three 2x2 max pools floor (H, W) to (H/8, W/8) and the decoder returns
     // 8*(H/8) x 8*(W/8) pixels (test/style_network_global.py:271-281, :111-122) — the stylized frame is [Ho][Wo][3].
@@ -1310,7 +1328,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     } else {
         // per-image state: every frame's relu4_1 is normalised with ITS set's Decoder.norm[0] entry, as the cached-feature branch above does
         if (h->state_images && h->state_images != B) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per frame");
-        RCHK(run_encoder(h, e, d_in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, h->state_images ? (int)RRV_STATE_FLOATS : 0));
+        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, h->state_images ? (int)RRV_STATE_FLOATS : 0));
     }
     const Tens* cur = &e.c41;
     for (int f = 0; f < 3; ++f) {
@@ -1344,7 +1362,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         const bool win = roi && k == 2;
         RCHK(resblock_frame(h, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr));
     }
-    RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, fmt, d.pre, pc, roi ? &wl : nullptr));
+    RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr));
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
@@ -1499,7 +1517,8 @@ int chan_stats1_images(rrv_handle h, const Tens& t, const DecPlan& d, int n) {
 }
 
 // B frames ([B][H][W][3] uint8; with pc: [B][src_H][src_W][3], padded on the way in, cropped on the way out) on `slot`
-int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, OutFmt fmt, const PadCrop* pc) {
+int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io) {
+    const PadCrop* const pc = io.pc;
     if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
     StyleState& S = h->styles[0];
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
@@ -1518,7 +1537,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
         hipLaunchKernelGGL(frame_sets_init_k, dim3((RRV_STATE_FLOATS + 255) / 256, B), dim3(256), 0, h->stream, (const float*)S.blob, st, (int)RRV_STATE_FLOATS,
                            SL.norm[N_DEC1], 512);
     }));
-    RCHK(run_encoder(h, e, d_in, 0, nullptr, pc, B));
+    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     const int hh = c41.H, ww = c41.W;
     // Decoder.norm[0] with each frame's statistics
@@ -1563,7 +1582,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     h->state_images = 0;
     // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
     RCHK(unfused_blocks(h, B, *cur, xs, a, o, st, PS, true, true, [&](const Tens& t, int n, int) { return chan_stats1_images(h, t, d, n); }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, fmt, d.pre, pc));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc));
     // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
     stamp(h, &e.c41, B);
     for (int k = 0; k < 3; ++k)
@@ -1605,8 +1624,9 @@ template <int S> void pyr_launch(const MaskPyrP& p, dim3 grid, hipStream_t s) { 
 
 // B <= MS_GROUP_MAX frames on `slot` (geometry as frame_mode_device); d_mask: [Bm][S][mH][mW] float32 in HBM, Bm = B or 1, at the
 // resolution of the frames as the caller passed them (pc: the unpadded frame)
-int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, const float* d_mask, int S, bool one_mask, void* d_out, OutFmt fmt,
-                     const PadCrop* pc) {
+int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, const float* d_mask, int S, bool one_mask, void* d_out,
+                     const FrameIO& io) {
+    const PadCrop* const pc = io.pc;
     if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "masked transfer: batch must be in 1..16 on slot 0 or 1");
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
     struct Scope { rrv_handle h; ~Scope() { h->stream = h->streams[0]; } } scope{h};
@@ -1634,7 +1654,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
     }
     LevelMask lm[4];
     for (int l = 0; l < 4; ++l) lm[l] = level_mask(d.lm[l], S, one_mask);
-    RCHK(run_encoder(h, e, d_in, 0, nullptr, pc, B));
+    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     Tens fo[3], xs[3], a[3], o[3], dd = d.d, dpart = d.dpart;
     dd.B = dpart.B = B;
@@ -1673,7 +1693,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
                             const int l = t.H == d.lm[0].H ? 0 : t.H == d.lm[1].H ? 1 : 2;
                             return mask_norm(h, t, y, ms, S, n, res, sty, lm[l]);
                         }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, fmt, d.pre, pc));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc));
     stamp(h, &e.c41, B); stamp(h, &d.d, B);
     if (split > 1) stamp(h, &d.dpart, B);
     for (int k = 0; k < 3; ++k)
@@ -1862,8 +1882,8 @@ int rrv_create(int device, rrv_handle* out) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RRV_E_HIP;
     rrv_ctx* h = new rrv_ctx();
     h->dev = device;
-    (void)rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in_m);
-    (void)rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_m);      // what players assume for untagged yuv420p
+    (void)rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in.m8);
+    (void)rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_out.m8);      // what players assume for untagged yuv420p
     bool ok = hipSetDevice(device) == hipSuccess;
     for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipStreamCreateWithFlags(&h->streams[i], hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
@@ -2124,13 +2144,45 @@ int rrv_finalize_weights(rrv_handle h) {
     return RRV_OK;
 }
 
-// The image descriptor of the torch-pipeline entries as conv_first_k's input form and value space; false: not a valid input
-static bool image_in_form(const rrv_image_desc& d, int* form, int* space) {
-    if ((d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32) || (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) ||
-        d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM || (d.dtype == RRV_DT_U8 && d.space != RRV_SP_PIXEL)) return false;
-    *form = (d.dtype == RRV_DT_F32 ? 2 : 0) | (d.layout == RRV_LAY_CHW_RGB ? 1 : 0);
-    *space = d.space;
-    return true;
+// ---- descriptors and layouts -> formats: one parser each way, used by every entry.  A parser says what was wrong; each entry family
+// words its own refusal (the texts are part of what callers see).
+enum class DescErr { OK, UNKNOWN /* a dtype, layout or space that does not exist here */, U8_SPACE /* uint8 outside PIXEL */,
+                     YUV_TYPE /* a YUV layout with another dtype or space than its own */, LAYOUT /* not a YUV 4:2:0 layout */ };
+static bool desc_known(const rrv_image_desc& d, bool yuv) {
+    return (d.dtype == RRV_DT_U8 || d.dtype == RRV_DT_F32 || (d.dtype == RRV_DT_U16 && yuv)) &&
+           (d.layout == RRV_LAY_HWC_BGR || d.layout == RRV_LAY_CHW_RGB || yuv) && d.space >= RRV_SP_PIXEL && d.space <= RRV_SP_NORM;
+}
+// an input descriptor (the torch-pipeline entries, the style image, the sampled frames): conv_first_k's form and value space
+static DescErr parse_in(const rrv_image_desc& d, InFmt* in) {
+    if (!desc_known(d, false)) return DescErr::UNKNOWN;      // (a YUV input goes through the _from_yuv entries)
+    if (d.dtype == RRV_DT_U8 && d.space != RRV_SP_PIXEL) return DescErr::U8_SPACE;
+    *in = InFmt{(d.dtype == RRV_DT_F32 ? IN_F32_HWC : IN_U8_HWC) | (d.layout == RRV_LAY_CHW_RGB ? 1 : 0), d.space};
+    return DescErr::OK;
+}
+// a layout / in_layout of the _yuv / _from_yuv entries: 8-bit YUV 4:2:0 or uint16 samples, integer codes of the PIXEL values (the depth and the
+// matrix are read when the kernel is launched)
+static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12 || yuv16_layout(layout); }
+static DescErr parse_in_yuv(int layout, InFmt* in) {
+    if (!yuv_layout(layout)) return DescErr::LAYOUT;
+    *in = InFmt{layout == RRV_LAY_I420 ? IN_YUV_I420 : layout == RRV_LAY_NV12 ? IN_YUV_NV12 : layout == RRV_LAY_I420_16 ? IN_YUV_I420_16 : IN_YUV_P016, SP_PIXEL};
+    return DescErr::OK;
+}
+static DescErr parse_out_yuv(int layout, OutFmt* out) {
+    if (!yuv_layout(layout)) return DescErr::LAYOUT;
+    *out = OutFmt{true, false, SP_PIXEL, layout};
+    return DescErr::OK;
+}
+// an output descriptor: HWC BGR / CHW RGB, or YUV 4:2:0 as uint8 I420 / NV12 or uint16 RRV_LAY_I420_16 / RRV_LAY_P016 in the PIXEL space
+static DescErr parse_out(const rrv_image_desc& d, OutFmt* out) {
+    const bool is_yuv = parse_out_yuv(d.layout, out) == DescErr::OK;
+    if (!desc_known(d, is_yuv)) return DescErr::UNKNOWN;
+    if (is_yuv && (d.dtype != (yuv16_layout(d.layout) ? RRV_DT_U16 : RRV_DT_U8) || d.space != RRV_SP_PIXEL)) return DescErr::YUV_TYPE;
+    if (d.dtype == RRV_DT_U8 && d.space != RRV_SP_PIXEL) return DescErr::U8_SPACE;
+    if (!is_yuv) *out = OutFmt{d.dtype == RRV_DT_U8, d.layout == RRV_LAY_CHW_RGB, d.space};
+    return DescErr::OK;
+}
+static int refuse_layout(rrv_handle h, const char* what) {      // what: "<entry family>: in_layout" / "<entry family>: layout"
+    return fail(h, RRV_E_ARG, std::string(what) + " must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
 }
 // the handle's stream waits for what `stream` (NULL: the null stream) holds so far
 static int wait_for_stream(rrv_handle h, hipStream_t stream) {
@@ -2138,15 +2190,9 @@ static int wait_for_stream(rrv_handle h, hipStream_t stream) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->slot_ev[0], 0));
     return RRV_OK;
 }
-// conv_first_k reads `form` / `space` while the scope lives (the style image, the sampled frames), uint8 BGR HWC after it
-struct InFormScope {
-    rrv_handle h;
-    InFormScope(rrv_handle h_, int form, int space) : h(h_) { h->in_form = form; h->in_space = space; }
-    ~InFormScope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; }
-};
 
-// device: `style` is in HBM in the given form, complete once `stream` has run what it holds now; else host uint8 BGR HWC
-static int prepare_style(rrv_handle h, const void* style, bool device, int form, int space, hipStream_t stream, int Hs, int Ws, int sid) {
+// device: `style` is in HBM in the format `in`, complete once `stream` has run what it holds now; else host uint8 BGR HWC
+static int prepare_style(rrv_handle h, const void* style, bool device, InFmt in, hipStream_t stream, int Hs, int Ws, int sid) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
@@ -2160,11 +2206,8 @@ static int prepare_style(rrv_handle h, const void* style, bool device, int form,
     }
     RCHK(enc_plan(h, h->enc_style, 1, Hs, Ws));
     EncPlan& e = h->enc_style;
-    {
-        InFormScope in_scope(h, form, space);
-        const int rc = run_encoder(h, e, device ? (const uint8_t*)style : h->d_u8, 1, nullptr, nullptr, 1);
-        if (rc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc; }      // (the caller's image is not read after the call returns)
-    }
+    const int rc_enc = run_encoder(h, e, device ? (const uint8_t*)style : h->d_u8, in, 1, nullptr, nullptr, 1);
+    if (rc_enc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc_enc; }      // (the caller's image is not read after the call returns)
     // cal_mean_std at relu1_1..relu4_1 (style_network_global.py:304-331)
     const Tens* taps[4] = {&e.c11, &e.c21, &e.c31, &e.c41};
     for (int k = 0; k < 4; ++k) RCHK(chan_stats(h, *taps[k], 2, S.blob + SL.sty[k]));
@@ -2197,13 +2240,13 @@ static int prepare_style(rrv_handle h, const void* style, bool device, int form,
 
 int rrv_prepare_style(rrv_handle h, const uint8_t* style, int Hs, int Ws, int sid) {
     if (!h || !style || Hs < 8 || Ws < 8 || sid < 0 || sid >= RRV_MAX_STYLES) return RRV_E_ARG;
-    return prepare_style(h, style, false, IN_U8_HWC, SP_PIXEL, nullptr, Hs, Ws, sid);
+    return prepare_style(h, style, false, IN_BGR8, nullptr, Hs, Ws, sid);
 }
 int rrv_prepare_style_image_device(rrv_handle h, const void* d_style, rrv_image_desc in, int Hs, int Ws, int sid, void* hip_stream) {
     if (!h || !d_style || Hs < 8 || Ws < 8 || sid < 0 || sid >= RRV_MAX_STYLES) return RRV_E_ARG;
-    int form, space;
-    if (!image_in_form(in, &form, &space)) return fail(h, RRV_E_ARG, "prepare_style: unknown dtype, layout or space (uint8 is PIXEL only)");
-    return prepare_style(h, d_style, true, form, space, (hipStream_t)hip_stream, Hs, Ws, sid);
+    InFmt fmt;
+    if (parse_in(in, &fmt) != DescErr::OK) return fail(h, RRV_E_ARG, "prepare_style: unknown dtype, layout or space (uint8 is PIXEL only)");
+    return prepare_style(h, d_style, true, fmt, (hipStream_t)hip_stream, Hs, Ws, sid);
 }
 
 int rrv_clean(rrv_handle h) {
@@ -2225,13 +2268,12 @@ int rrv_clean(rrv_handle h) {
 static int flush_pending(rrv_handle h) {
     if (!h->pend_n) return RRV_OK;
     const int H = h->add_H, W = h->add_W;
-    const size_t fb = in_frame_bytes(h->pend_form, H, W);
+    const size_t fb = in_frame_bytes(h->pend_in.form, H, W);
     const int PB = h->pend_n < 8 ? h->pend_n : 8;        // one plan; the last group may use fewer of its images
     RCHK(enc_plan(h, h->enc_add, PB, H, W));
-    InFormScope in_scope(h, h->pend_form, h->pend_space);      // the pending frames are kept in the form they arrived in
     for (int k0 = 0; k0 < h->pend_n; k0 += PB) {
         const int nb = h->pend_n - k0 < PB ? h->pend_n - k0 : PB;
-        RCHK(run_encoder(h, h->enc_add, h->pend_u8 + (size_t)k0 * fb, 0, nullptr, nullptr, nb));
+        RCHK(run_encoder(h, h->enc_add, h->pend_u8 + (size_t)k0 * fb, h->pend_in, 0, nullptr, nullptr, nb));      // the pending frames are kept in the format they arrived in
         const Tens& f = h->enc_add.c41;
         for (int b = 0; b < nb; ++b) {
             float* keep = nullptr;
@@ -2246,19 +2288,19 @@ static int flush_pending(rrv_handle h) {
     return RRV_OK;
 }
 
-// device: `frame` is in HBM in the given form, complete once `stream` has run what it holds now; else host uint8 BGR HWC
-static int add_frame(rrv_handle h, const void* frame, bool device, int form, int space, hipStream_t stream, int H, int W) {
+// `frame` is in the format `in`.  device: in HBM, complete once `stream` has run what it holds now; else in host memory
+static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hipStream_t stream, int H, int W) {
     RCHK(check_frame(h, H, W, "add"));
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     if ((!h->patches.empty() || h->pend_n) && (H != h->add_H || W != h->add_W))
         return fail(h, RRV_E_ARG, "add: all sampled frames must have the same size");
-    if (h->pend_n && (form != h->pend_form || space != h->pend_space)) {      // one encoder launch reads one form: encode the pending ones first
+    if (h->pend_n && in != h->pend_in) {      // one encoder launch reads one format: encode the pending ones first
         RCHK(sync_all(h));
         RCHK(flush_pending(h));
     }
-    h->pend_form = form; h->pend_space = space;
-    const size_t fb = in_frame_bytes(form, H, W);
+    h->pend_in = in;
+    const size_t fb = in_frame_bytes(in.form, H, W);
     if ((size_t)(h->pend_n + 1) * fb > h->pend_cap) {      // grow (x2) keeping the frames already collected
         const size_t cap = ((size_t)(h->pend_n + 1) * fb) * 2 > 16 * fb ? ((size_t)(h->pend_n + 1) * fb) * 2 : 16 * fb;
         uint8_t* nw = nullptr;
@@ -2281,37 +2323,25 @@ static int add_frame(rrv_handle h, const void* frame, bool device, int form, int
 
 int rrv_add(rrv_handle h, const uint8_t* frame, int H, int W) {
     if (!h || !frame) return RRV_E_ARG;
-    return add_frame(h, frame, false, IN_U8_HWC, SP_PIXEL, nullptr, H, W);
+    return add_frame(h, frame, false, IN_BGR8, nullptr, H, W);
 }
 int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, int H, int W, void* hip_stream) {
     if (!h || !d_frame) return RRV_E_ARG;
-    int form, space;
-    if (!image_in_form(in, &form, &space)) return fail(h, RRV_E_ARG, "add: unknown dtype, layout or space (uint8 is PIXEL only)");
-    return add_frame(h, d_frame, true, form, space, (hipStream_t)hip_stream, H, W);
+    InFmt fmt;
+    if (parse_in(in, &fmt) != DescErr::OK) return fail(h, RRV_E_ARG, "add: unknown dtype, layout or space (uint8 is PIXEL only)");
+    return add_frame(h, d_frame, true, fmt, (hipStream_t)hip_stream, H, W);
 }
 
-// sampled frames as 8-bit YUV 4:2:0 (conv_first_k<IN_YUV_*>); the input matrix is read when the deferred encoding runs
-// (RRV_LAY_I420_16 / RRV_LAY_P016: uint16 samples, the depth and the 16-bit input matrix read then too)
-static bool yuv_in_form(int layout, int* form) {
-    switch (layout) {
-    case RRV_LAY_I420: *form = IN_YUV_I420; return true;
-    case RRV_LAY_NV12: *form = IN_YUV_NV12; return true;
-    case RRV_LAY_I420_16: *form = IN_YUV_I420_16; return true;
-    case RRV_LAY_P016: *form = IN_YUV_P016; return true;
-    }
-    return false;
-}
-int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame, int in_layout, int H, int W) {
+// sampled frames as YUV 4:2:0 (conv_first_k<IN_YUV_*>); the input matrix (the uint16 forms: and the depth) is read when the deferred encoding runs
+static int add_from_yuv(rrv_handle h, const void* frame, bool device, int in_layout, hipStream_t stream, int H, int W) {
     if (!h || !frame) return RRV_E_ARG;
-    int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
-    return add_frame(h, frame, false, form, SP_PIXEL, nullptr, H, W);
+    InFmt in;
+    if (parse_in_yuv(in_layout, &in) != DescErr::OK) return refuse_layout(h, "add_from_yuv: in_layout");
+    return add_frame(h, frame, device, in, stream, H, W);
 }
+int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame, int in_layout, int H, int W) { return add_from_yuv(h, frame, false, in_layout, nullptr, H, W); }
 int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame, int in_layout, int H, int W, void* hip_stream) {
-    if (!h || !d_frame) return RRV_E_ARG;
-    int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "add_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
-    return add_frame(h, d_frame, true, form, SP_PIXEL, (hipStream_t)hip_stream, H, W);
+    return add_from_yuv(h, d_frame, true, in_layout, (hipStream_t)hip_stream, H, W);
 }
 
 int rrv_compute(rrv_handle h) {
@@ -2554,23 +2584,23 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const float* d_w = x.wts;
     if (x.model == Model::BLEND && !x.w_dev) RCHK(stage_blend_weights(h, slot, x.wts, (size_t)x.B * x.ns, &d_w));
     const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
-    const size_t fb = x.in_bytes(h), fo = x.out_bytes();
+    const size_t fb = x.in_bytes(), fo = x.out_bytes();
     const PadCrop crop = x.pad_crop();
-    const PadCrop* const pc = x.pad ? &crop : nullptr;
+    const FrameIO io{x.in, x.fmt, x.pad ? &crop : nullptr};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* const in = (const uint8_t*)d_in + (size_t)b0 * fb;
         void* const out = (char*)d_out + (size_t)b0 * fo;
         switch (x.model) {
         case Model::GLOBAL:
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, x.fmt, nullptr, pc));
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io));
             break;
         case Model::FRAME:
-            RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, x.fmt, pc));
+            RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, io));
             break;
         case Model::MASK:
             RCHK(mask_mode_device(h, slot, in, cnt, KH, KW, x.mask + (x.mask_images == 1 ? 0 : (size_t)b0 * x.mask_floats()), x.ns, x.mask_images == 1, out,
-                                  x.fmt, pc));
+                                  io));
             break;
         case Model::BLEND: {
             SetScope scope{h, -2};
@@ -2584,7 +2614,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             h->active_src = -2;
             for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
             h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, x.fmt, nullptr, pc));
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io));
             h->set_images[slot] = cnt;
             break;
         }
@@ -2647,22 +2677,14 @@ int rrv_transfer_frame_mode_frames_device_u8(rrv_handle h, const void* d_in, int
 // rrv_transfer_image_device: the device entries above with the content frames read as `in` (conv_first_k<IN>) and the
 // stylized frames written as `out` (conv_last_k<U8, CHW, SPACE>); hip_stream orders this call only.  x: the model, B, H, W and what
 // the model blends with; the flags and `out` supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME)
-static bool bad_desc(const rrv_image_desc& d, bool yuv_ok) {
-    return (d.dtype != RRV_DT_U8 && d.dtype != RRV_DT_F32 && !(d.dtype == RRV_DT_U16 && yuv_ok)) ||
-           (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB && !yuv_ok) || d.space < RRV_SP_PIXEL || d.space > RRV_SP_NORM;
+static int refuse_image(rrv_handle h, DescErr e, const char* side) {
+    if (e == DescErr::U8_SPACE) return fail(h, RRV_E_ARG, std::string("transfer_image: a uint8 ") + side + " is in the PIXEL space");
+    if (e == DescErr::YUV_TYPE) return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8, an I420_16 / P016 output uint16, in the PIXEL space");
+    return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
 }
-// a YUV 4:2:0 output descriptor: uint8 I420 / NV12 or uint16 RRV_LAY_I420_16 / RRV_LAY_P016, in the PIXEL space
-static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12 || yuv16_layout(layout); }
-static bool yuv_desc_ok(const rrv_image_desc& d) {
-    return d.dtype == (yuv16_layout(d.layout) ? RRV_DT_U16 : RRV_DT_U8) && d.space == RRV_SP_PIXEL;
-}
-// in_form, in_space: the checked input form (a descriptor's, or IN_YUV_* of the _from_yuv_device entries)
-static int image_run(rrv_handle h, const void* d_in, int in_form, int in_space, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
-    const bool yuv = yuv_layout(out.layout);      // an output layout of the descriptor entries
-    if (bad_desc(out, yuv)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
-    if (yuv && !yuv_desc_ok(out))
-        return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8, an I420_16 / P016 output uint16, in the PIXEL space");
-    if (out.dtype == RRV_DT_U8 && out.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 output is in the PIXEL space");
+// x.in: the parsed input format (a descriptor's, or the in_layout's of the _from_yuv_device entries)
+static int image_run(rrv_handle h, const void* d_in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
+    if (const DescErr e = parse_out(out, &x.fmt); e != DescErr::OK) return refuse_image(h, e, "output");
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
         return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
     if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
@@ -2671,32 +2693,27 @@ static int image_run(rrv_handle h, const void* d_in, int in_form, int in_space, 
         x.model = Model::FRAME;
     }
     x.pad = flags & RRV_TF_PAD_CROP;
-    x.fmt = yuv ? out_yuv(out.layout) : OutFmt{out.dtype == RRV_DT_U8, out.layout == RRV_LAY_CHW_RGB, out.space};
     x.w_dev = flags & RRV_TF_WEIGHTS_DEVICE;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x));
-    struct Scope {
+    struct Scope {      // hip_stream orders this call only
         rrv_handle h; hipStream_t cs; bool sync;
-        ~Scope() { h->in_form = IN_U8_HWC; h->in_space = SP_PIXEL; h->caller_stream = cs; h->caller_sync = sync; }
+        ~Scope() { h->caller_stream = cs; h->caller_sync = sync; }
     } scope{h, h->caller_stream, h->caller_sync};
-    h->in_form = in_form;
-    h->in_space = in_space;
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
     return run_xfer(h, next_slot(h, x), d_in, d_out, x);
 }
-static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
+static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
     if (!h) return RRV_E_ARG;
-    if (bad_desc(in, false)) return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");      // a YUV input goes through the _from_yuv_device entries
-    if (in.dtype == RRV_DT_U8 && in.space != RRV_SP_PIXEL) return fail(h, RRV_E_ARG, "transfer_image: a uint8 input is in the PIXEL space");
-    return image_run(h, d_in, (in.dtype == RRV_DT_F32 ? 2 : 0) | (in.layout == RRV_LAY_CHW_RGB ? 1 : 0), in.space, d_out, out, flags, hip_stream, x);
+    if (const DescErr e = parse_in(in, &x.in); e != DescErr::OK) return refuse_image(h, e, "input");
+    return image_run(h, d_in, d_out, out, flags, hip_stream, x);
 }
-// the same entries reading 8-bit YUV 4:2:0 frames (conv_first_k<IN_YUV_*>): [B][H*W + 2*CH*CW] uint8 in HBM
-static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
+// the same entries reading YUV 4:2:0 frames (conv_first_k<IN_YUV_*>): [B][H*W + 2*CH*CW] uint8 (uint16 for the two 16-bit layouts) in HBM
+static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
     if (!h) return RRV_E_ARG;
-    int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
+    if (parse_in_yuv(in_layout, &x.in) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
-    return image_run(h, d_in, form, SP_PIXEL, d_out, out, flags, hip_stream, x);
+    return image_run(h, d_in, d_out, out, flags, hip_stream, x);
 }
 int rrv_transfer_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W, void* d_out, rrv_image_desc out, int flags,
                                  void* hip_stream) {
@@ -2748,7 +2765,7 @@ static int blend_device(rrv_handle h, const void* d_in, int H, int W, const floa
     RCHK(sync_all(h));
     h->next_slot = 0;
     RCHK(blend_into_current(h, wts, ns));
-    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, d_out, fmt);
+    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, d_out, FrameIO{IN_BGR8, fmt});
 }
 int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
     return blend_device(h, d_in, H, W, wts, ns, d_out, OUT_F32);
@@ -2903,7 +2920,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const int B = x.B;
     const float* const mask = x.mask;
     const int mask_images = x.mask_images;
-    const size_t fb = x.in_bytes(h);                                        // input bytes per frame
+    const size_t fb = x.in_bytes();                                        // input bytes per frame
     const size_t fob = x.out_bytes();                     // output bytes per frame
     char* const outc = (char*)out;
     const int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
@@ -3063,39 +3080,35 @@ int rrv_transfer_frame_mode_frames_u8(rrv_handle h, const uint8_t* frames, int B
 }
 
 // YUV 4:2:0 output of the host entries (conv_last_k's YUV form): frame b at b * (OH*OW + 2*CH*CW) samples of `out`, bytes or (layouts 8 / 9) uint16
+static int yuv_host(rrv_handle h, const uint8_t* frames, int layout, void* out, Xfer x) {
+    if (!h) return RRV_E_ARG;
+    if (parse_out_yuv(layout, &x.fmt) != DescErr::OK) return refuse_layout(h, "transfer_yuv: layout");
+    return host_pipeline(h, frames, out, x);
+}
 int rrv_transfer_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, int flags, int layout, uint8_t* out) {
     if (!h) return RRV_E_ARG;
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_yuv: unknown flags");
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
-    return host_pipeline(h, frames, out, Xfer{flags & RRV_TF_FRAME_MODE ? Model::FRAME : Model::GLOBAL, B, H, W, (flags & RRV_TF_PAD_CROP) != 0, out_yuv(layout)});
+    return yuv_host(h, frames, layout, out, Xfer{flags & RRV_TF_FRAME_MODE ? Model::FRAME : Model::GLOBAL, B, H, W, (flags & RRV_TF_PAD_CROP) != 0});
 }
 int rrv_transfer_blend_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* wts, int ns, int pad_crop, int layout, uint8_t* out) {
-    if (!h) return RRV_E_ARG;
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
-    return host_pipeline(h, frames, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, out_yuv(layout), ns, wts});
+    return yuv_host(h, frames, layout, out, Xfer{Model::BLEND, B, H, W, pad_crop != 0, OUT_F32, ns, wts});
 }
 int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int H, int W, const float* mask, int ns, int mask_images, int pad_crop,
                                 int layout, uint8_t* out) {
-    if (!h) return RRV_E_ARG;
-    if (!yuv_layout(layout)) return fail(h, RRV_E_ARG, "transfer_yuv: layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
-    return host_pipeline(h, frames, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, out_yuv(layout), ns, /* wts */ nullptr, mask, mask_images});
+    return yuv_host(h, frames, layout, out, Xfer{Model::MASK, B, H, W, pad_crop != 0, OUT_F32, ns, /* wts */ nullptr, mask, mask_images});
 }
 
 // 8-bit YUV 4:2:0 input of the host entries (conv_first_k<IN_YUV_*>): frame b at b * (H*W + 2*CH*CW) bytes of `frames`; `out` as float32 or
 // uint8 HWC BGR PIXEL frames or as I420 / NV12.  The staging, the zero-copy path and the copy pool size a frame by Xfer::in_bytes.
 static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, void* out, rrv_image_desc od, int flags, int known_flags, Xfer x) {
     if (!h) return RRV_E_ARG;
-    int form;
-    if (!yuv_in_form(in_layout, &form)) return fail(h, RRV_E_ARG, "transfer_from_yuv: in_layout must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
+    if (parse_in_yuv(in_layout, &x.in) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
     if (flags & ~known_flags) return fail(h, RRV_E_ARG, "transfer_from_yuv: unknown flags");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
-    const bool yuv = yuv_layout(od.layout);
-    if (yuv ? !yuv_desc_ok(od) : ((od.dtype != RRV_DT_U8 && od.dtype != RRV_DT_F32) || od.layout != RRV_LAY_HWC_BGR || od.space != RRV_SP_PIXEL))
+    if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
         return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016");
     if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
     x.pad = (flags & RRV_TF_PAD_CROP) != 0;
-    x.fmt = yuv ? out_yuv(od.layout) : (od.dtype == RRV_DT_U8 ? OUT_U8 : OUT_F32);
-    InFormScope in_scope(h, form, SP_PIXEL);
     return host_pipeline(h, frames, out, x);
 }
 int rrv_transfer_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, void* out, rrv_image_desc od, int flags) {
@@ -3132,15 +3145,6 @@ int rrv_yuv_input_matrix_depth(int standard, int full_range, int bits, float n[1
     return RRV_OK;
 }
 int rrv_yuv_input_matrix(int standard, int full_range, float n[12]) { return rrv_yuv_input_matrix_depth(standard, full_range, 8, n); }
-// handle state, independent of the output matrix, read when conv_first_k is launched
-int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]) {
-    if (!h) return RRV_E_ARG;
-    if (!n) return rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in_m);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(n[i])) return fail(h, RRV_E_ARG, "set_yuv_input_matrix: the twelve coefficients must be finite");
-    memcpy(h->yuv_in_m, n, sizeof h->yuv_in_m);
-    return RRV_OK;
-}
 
 // The conversion matrix of the YUV forms: Y = Kr R + Kg G + Kb B, Cb = 128 + (B - Y) / (2 (1 - Kb)), Cr = 128 + (R - Y) / (2 (1 - Kr)); limited
 // range scales Y by 219/255 (+16) and the chroma differences by 224/255.  Coefficients in double, each rounded once to float32.
@@ -3162,15 +3166,6 @@ int rrv_yuv_matrix_depth(int standard, int full_range, int bits, float m[12]) {
     return RRV_OK;
 }
 int rrv_yuv_matrix(int standard, int full_range, float m[12]) { return rrv_yuv_matrix_depth(standard, full_range, 8, m); }
-// handle state, read when conv_last_k is launched: launches already queued keep the matrix they were queued with
-int rrv_set_yuv_matrix(rrv_handle h, const float m[12]) {
-    if (!h) return RRV_E_ARG;
-    if (!m) return rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_m);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m[i])) return fail(h, RRV_E_ARG, "set_yuv_matrix: the twelve coefficients must be finite");
-    memcpy(h->yuv_m, m, sizeof h->yuv_m);
-    return RRV_OK;
-}
 
 // The uint16 forms' state: the code depth of each side, and matrices independent of the 8-bit ones and of each other.  NULL: BT.601 limited
 // range at the depth in force when a call launches (run_encoder / run_last work it out then).
@@ -3178,25 +3173,27 @@ int rrv_set_yuv_depth(rrv_handle h, int in_bits, int out_bits) {
     if (!h) return RRV_E_ARG;
     auto ok = [](int b) { return b == 0 || b == 10 || b == 12 || b == 16; };
     if (!ok(in_bits) || !ok(out_bits)) return fail(h, RRV_E_ARG, "set_yuv_depth: a depth is 10, 12 or 16 bits (0 leaves it as it is)");
-    if (in_bits) h->yuv_in_bits = in_bits;
-    if (out_bits) h->yuv_out_bits = out_bits;
+    if (in_bits) h->yuv_in.bits = in_bits;
+    if (out_bits) h->yuv_out.bits = out_bits;
     return RRV_OK;
 }
-static int set_yuv16(rrv_handle h, const float* src, float* dst, bool* set, const char* what) {
+// The four matrix setters: the input and the output side are independent of each other, and so are a side's 8-bit and uint16 matrices.
+// NULL puts back BT.601 limited range (the uint16 forms: at the depth in force when a call launches).
+static int set_yuv_matrix(rrv_handle h, bool input, bool wide, const float* src, const char* name) {
     if (!h) return RRV_E_ARG;
-    if (!src) { *set = false; return RRV_OK; }
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(src[i])) return fail(h, RRV_E_ARG, what);
-    memcpy(dst, src, 12 * sizeof(float));
-    *set = true;
+    YuvSide& s = input ? h->yuv_in : h->yuv_out;
+    if (src) {
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(src[i])) return fail(h, RRV_E_ARG, std::string(name) + ": the twelve coefficients must be finite");
+        memcpy(wide ? s.m16 : s.m8, src, sizeof s.m8);
+    } else if (!wide) return (input ? rrv_yuv_input_matrix : rrv_yuv_matrix)(RRV_YUV_BT601, 0, s.m8);
+    if (wide) s.set16 = src != nullptr;
     return RRV_OK;
 }
-int rrv_set_yuv16_matrix(rrv_handle h, const float m[12]) {
-    return h ? set_yuv16(h, m, h->yuv16_m, &h->yuv16_set, "set_yuv16_matrix: the twelve coefficients must be finite") : RRV_E_ARG;
-}
-int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]) {
-    return h ? set_yuv16(h, n, h->yuv16_in_m, &h->yuv16_in_set, "set_yuv16_input_matrix: the twelve coefficients must be finite") : RRV_E_ARG;
-}
+int rrv_set_yuv_matrix(rrv_handle h, const float m[12]) { return set_yuv_matrix(h, false, false, m, "set_yuv_matrix"); }
+int rrv_set_yuv_input_matrix(rrv_handle h, const float n[12]) { return set_yuv_matrix(h, true, false, n, "set_yuv_input_matrix"); }
+int rrv_set_yuv16_matrix(rrv_handle h, const float m[12]) { return set_yuv_matrix(h, false, true, m, "set_yuv16_matrix"); }
+int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]) { return set_yuv_matrix(h, true, true, n, "set_yuv16_input_matrix"); }
 
 // ---- look-ahead form of Stylization.transfer for a one-frame-per-call driver loop (generate_real_video.py:152-171) ----
 // rrv_transfer_async queues H2D copy -> kernels -> D2H copy of ONE frame on the copy / compute streams and returns a
@@ -3252,7 +3249,7 @@ static int transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, void
     RCHK(ensure_active(h));
     HIPCHK(hipMemcpyAsync(st.dev.in, src, fb, hipMemcpyHostToDevice, cs));
     HIPCHK(hipEventRecord(st.in_done, cs));      // the frame has left the caller's buffer (waited for below when the copy reads it directly)
-    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out, fmt);
+    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out, FrameIO{IN_BGR8, fmt});
     // Contract (include/rerevst_hip.h): `frame` may be reused as soon as the call returns.  A pageable frame was copied to
     // staging above; a page-locked one is the DIRECT source of the asynchronous H2D copy, so wait for that copy (queued
     // first on an idle stream: finished long before the launches above were) — also on the error path.
@@ -3309,7 +3306,7 @@ int rrv_generate_content_features(rrv_handle h, const uint8_t* frame, int H, int
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)H * W * 3));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, (size_t)H * W * 3, hipMemcpyHostToDevice, h->stream));
     RCHK(enc_plan(h, h->enc_add, 1, H, W));
-    RCHK(run_encoder(h, h->enc_add, h->d_u8, 0, nullptr, nullptr, 1));
+    RCHK(run_encoder(h, h->enc_add, h->d_u8, IN_BGR8, 0, nullptr, nullptr, 1));
     const Tens& f = h->enc_add.c41;
     RCHK(dalloc(h, &ft.p, feature_floats(H, W), true));
     HIPCHK(hipMemcpyAsync(ft.p, f.p, f.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
@@ -3389,7 +3386,7 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         if (rc != RRV_OK) break;
         e.gen = ++h->launch_gen;
         Tens out41 = one; out41.B = nb; out41.p = arena + (size_t)k * sub * img;
-        rc = run_encoder(h, e, st.dev.in, 0, nullptr, nullptr, nb, &out41);
+        rc = run_encoder(h, e, st.dev.in, IN_BGR8, 0, nullptr, nullptr, nb, &out41);
         if (rc != RRV_OK) break;
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
     }
@@ -3441,7 +3438,7 @@ int rrv_add_patch(rrv_handle h, int feature_id) {
     const float* src = ft.p;
     if (!src) {                  // spilled feature: encode its pixels now
         int rc = enc_plan(h, h->enc_add, 1, ft.H, ft.W);
-        if (rc == RRV_OK) rc = run_encoder(h, h->enc_add, ft.u8, 0, nullptr, nullptr, 1);
+        if (rc == RRV_OK) rc = run_encoder(h, h->enc_add, ft.u8, IN_BGR8, 0, nullptr, nullptr, 1);
         if (rc == RRV_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, RRV_E_HIP, "add_patch: encoder failed");
         if (rc != RRV_OK) { (void)hipFree(keep); return rc; }
         src = h->enc_add.c41.p;
@@ -3462,7 +3459,7 @@ static int transfer_features(rrv_handle h, int feature_id, const float* wts, int
     RCHK(blend_into_current(h, wts, ns));
     const size_t n = (size_t)(ft.H / 8 * 8) * (ft.W / 8 * 8) * 3;
     RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
-    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, fmt, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
+    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, FrameIO{IN_BGR8, fmt}, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
     HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;
@@ -3492,6 +3489,7 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         if (h->features[ids[i]].H != H || h->features[ids[i]].W != W) return fail(h, RRV_E_ARG, "transfer: features of one call must share their size");
     RCHK(claim_staging(h));
     const size_t npx = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3 * out_elem(fmt);      // output bytes per frame
+    const FrameIO io{IN_BGR8, fmt};      // (a spilled feature is re-encoded from its uint8 BGR pixels)
     char* const outc = (char*)out;
     const bool out_pin = is_pinned(out, (size_t)n * npx);
     // Frames per launch sequence (rrv_set_multistyle_group; default: the host entries' ~6.6 Mpixel per launch — 4 at 1152 x 1152,
@@ -3550,14 +3548,14 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         }
         h->active_src = -2;
         if (fp[0] && cnt == 1) {       // one frame per launch: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, fmt, fp[0]));
+            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, io, fp[0]));
         } else if (fp[0]) {
             h->state_images = cnt;
-            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, fmt, nullptr, nullptr, fp);
+            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, io, nullptr, fp);
             h->state_images = 0;
             RCHK(rc);
         } else {
-            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, fmt, nullptr));      // re-encode the pixels
+            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, io));      // re-encode the pixels
         }
         h->set_images[slot] = cnt;
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
@@ -3604,7 +3602,7 @@ static int transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W,
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, nin));
     HIPCHK(hipMemcpyAsync(h->d_u8, frame, nin, hipMemcpyHostToDevice, h->stream));
     RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
-    RCHK(frame_mode_device(h, 0, h->d_u8, 1, H, W, h->d_outf, fmt, nullptr));
+    RCHK(frame_mode_device(h, 0, h->d_u8, 1, H, W, h->d_outf, FrameIO{IN_BGR8, fmt}));
     HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
     HIPCHK(hipStreamSynchronize(h->streams[0]));
     return RRV_OK;

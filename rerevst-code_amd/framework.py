@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .video import YUV_FORMATS, YUV_FORMAT_NAMES, YUV_STANDARDS, _yuv_depth, yuv_frame_bytes  # noqa: F401  (the YUV format table lives there)
 from .weights import weight_table, load_checkpoint
 
 
@@ -91,6 +92,13 @@ class _OutputPool:
         return np.frombuffer(lease, dtype=dt, count=count).reshape(shape)
 
 
+def _u8_frames(frames, what):
+    """equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) as one C-contiguous [B][H][W][3] array"""
+    if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
+        return np.ascontiguousarray(frames)
+    return np.stack([_u8_image(f, what) for f in frames])
+
+
 _outputs = _OutputPool()
 
 _OUT_DTYPES = (np.dtype(np.float32), np.dtype(np.uint8))
@@ -104,10 +112,18 @@ def _out_u8(dtype):
     return dt == np.uint8
 
 
-def _output(shape, dtype, out):
-    """(output array, uint8?) of a host entry.  float32 BGR in 0..255 as the reference returns it, or uint8: the same values
-    rounded half to even on the GPU (== driver.to_uint8 of the float output, bit for bit).  A given `out` selects the format
-    by its own dtype; otherwise `dtype` does and the array comes from the page-locked pool."""
+def _output(shape, dtype, out, out_format="bgr"):
+    """(output array, uint8?) of a host entry; shape: [..][Ho][Wo][3], the stylized frames as BGR.  float32 BGR in 0..255 as the
+    reference returns it, or uint8: the same values rounded half to even on the GPU (== driver.to_uint8 of the float output, bit for
+    bit).  A given `out` selects the format by its own dtype; otherwise `dtype` does and the array comes from the page-locked pool.
+    out_format a YUV 4:2:0 name: [..][yuv_frame_bytes(Ho, Wo)] samples of the format's dtype, whatever `dtype` says."""
+    if out_format != "bgr":
+        shape, odt = tuple(shape[:-3]) + (yuv_frame_bytes(shape[-3], shape[-2]),), YUV_FORMATS[out_format].dtype
+        if out is None:
+            out = _outputs.empty(shape, odt)
+        elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous %s array of shape %r" % (odt.name, shape))
+        return out, odt == np.uint8
     if out is None:
         u8 = _out_u8(dtype)
         return _outputs.empty(shape, np.uint8 if u8 else np.float32), u8
@@ -116,41 +132,15 @@ def _output(shape, dtype, out):
     return out, out.dtype == np.uint8
 
 
-# ===== 8-bit YUV 4:2:0 output (the rrv_*_yuv entries; include/rerevst_hip.h states the arithmetic) =====
-# 10 / 12 / 16-bit forms (RRV_LAY_I420_16 / RRV_LAY_P016): uint16 samples; the format name carries the depth.  "i420pNN": planar, the code in the
-# low bits (ffmpeg yuv420pNNle, Y4M C420pNN); "p0NN": semi-planar, the code in the high bits (ffmpeg p0NNle, hardware decoders / encoders)
-_YUV_LAYOUTS = {"i420": _lib.LAY_I420, "nv12": _lib.LAY_NV12,
-                "i420p10": _lib.LAY_I420_16, "i420p12": _lib.LAY_I420_16, "i420p16": _lib.LAY_I420_16,
-                "p010": _lib.LAY_P016, "p012": _lib.LAY_P016, "p016": _lib.LAY_P016}
-_YUV_BITS = {"i420": 8, "nv12": 8, "i420p10": 10, "i420p12": 12, "i420p16": 16, "p010": 10, "p012": 12, "p016": 16}
-_YUV_NAMES = "'i420', 'nv12', 'i420p10' / 'p12' / 'p16' or 'p010' / 'p012' / 'p016'"
-_YUV_STANDARDS = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709}
-
-
-def _yuv_np_dtype(fmt):
-    return np.dtype(np.uint8 if _YUV_BITS[fmt] == 8 else np.uint16)
-
-
+# ===== YUV 4:2:0 input and output (the rrv_*_yuv / rrv_*_from_yuv entries; include/rerevst_hip.h states the arithmetic) =====
+# The formats by name, their depths and yuv_frame_bytes: video.YUV_FORMATS (imported above).
 def _yuv_torch_dtypes(fmt):
     """torch dtypes of a YUV tensor in format `fmt`, the preferred one first: torch.uint8 at 8 bits; above, torch.uint16 where this
     torch has it, and torch.int16 holding the same bits (x.view(torch.int16))"""
     import torch
-    if _YUV_BITS[fmt] == 8:
+    if YUV_FORMATS[fmt].bits == 8:
         return (torch.uint8,)
     return ((torch.uint16,) if hasattr(torch, "uint16") else ()) + (torch.int16,)
-
-
-def _yuv_depth(bits):
-    if bits not in (8, 10, 12, 16):
-        raise ValueError("bits must be 8, 10, 12 or 16, got %r" % (bits,))
-    return int(bits)
-
-
-def yuv_frame_bytes(H, W, bits=8):
-    """Bytes of one H x W frame in I420 or NV12: H*W luma samples and two chroma planes of ceil(H/2) x ceil(W/2); bits = 10, 12, 16: the
-    same samples in uint16, twice the bytes.  yuv_frame_bytes(H, W) is also the SAMPLE count of a frame at any depth: the last axis of
-    the arrays the YUV formats take and return."""
-    return (int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
 
 
 def yuv_planes(buf, H, W, layout="i420", bits=8):
@@ -159,10 +149,10 @@ def yuv_planes(buf, H, W, layout="i420", bits=8):
     for "nv12" the chroma views are strided (every second byte of the interleaved plane).  bits = 10, 12, 16 (or a layout name that
     carries the depth: "i420p10", "p010", ..): uint16 samples [..][yuv_frame_bytes(H, W)], the same planes; the samples are returned
     as stored ("p010": the code in the high bits)."""
-    if layout not in _YUV_LAYOUTS:
-        raise ValueError("layout must be %s, got %r" % (_YUV_NAMES, layout))
-    bits = _yuv_depth(bits) if _YUV_BITS[layout] == 8 else _YUV_BITS[layout]
-    layout = "i420" if _YUV_LAYOUTS[layout] in (_lib.LAY_I420, _lib.LAY_I420_16) else "nv12"
+    if layout not in YUV_FORMATS:
+        raise ValueError("layout must be %s, got %r" % (YUV_FORMAT_NAMES, layout))
+    fmt = YUV_FORMATS[layout]
+    bits = _yuv_depth(bits) if fmt.bits == 8 else fmt.bits
     if getattr(buf.dtype, "itemsize", None) is not None and buf.dtype.itemsize != (1 if bits == 8 else 2):
         raise ValueError("%d-bit samples are %d bytes each, got %s" % (bits, 1 if bits == 8 else 2, buf.dtype))
     H, W = int(H), int(W)
@@ -171,37 +161,36 @@ def yuv_planes(buf, H, W, layout="i420", bits=8):
         raise ValueError("a %d x %d frame has %d samples, got %d" % (H, W, yuv_frame_bytes(H, W), buf.shape[-1]))
     lead = tuple(buf.shape[:-1])
     y = buf[..., :H * W].reshape(lead + (H, W))
-    if layout == "i420":
+    if fmt.planar:
         return y, buf[..., H * W:H * W + CH * CW].reshape(lead + (CH, CW)), buf[..., H * W + CH * CW:].reshape(lead + (CH, CW))
     c = buf[..., H * W:].reshape(lead + (CH, CW, 2))
     return y, c[..., 0], c[..., 1]
 
 
+def _lib_matrix(entry, standard, full_range, bits):
+    if standard not in YUV_STANDARDS:
+        raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
+    m = np.empty((3, 4), np.float32)
+    if getattr(_lib.load(), entry)(YUV_STANDARDS[standard][0], int(bool(full_range)), _yuv_depth(bits), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("%s refused %r" % (entry, standard))
+    return m
+
+
 def yuv_matrix(standard="bt601", full_range=False, bits=8):
     """rrv_yuv_matrix[_depth]: the float32 [3][4] matrix (rows Y, Cb, Cr; columns R, G, B, offset) of a standard and range, to codes of
     `bits` bits (8, 10, 12, 16); needs no GPU."""
-    if standard not in _YUV_STANDARDS:
-        raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
-    m = np.empty((3, 4), np.float32)
-    if _lib.load().rrv_yuv_matrix_depth(_YUV_STANDARDS[standard], int(bool(full_range)), _yuv_depth(bits), m.ctypes.data_as(C.POINTER(C.c_float))) != 0:
-        raise ValueError("rrv_yuv_matrix_depth refused %r" % (standard,))
-    return m
+    return _lib_matrix("rrv_yuv_matrix_depth", standard, full_range, bits)
 
 
 def yuv_input_matrix(standard="bt601", full_range=False, bits=8):
     """rrv_yuv_input_matrix[_depth]: the float32 [3][4] matrix (rows R, G, B; columns Y, Cb, Cr, offset) that reads YUV codes of `bits`
     bits (8, 10, 12, 16) of a standard and range, the inverse of yuv_matrix's transform; needs no GPU."""
-    if standard not in _YUV_STANDARDS:
-        raise ValueError("standard must be 'bt601' or 'bt709', got %r" % (standard,))
-    n = np.empty((3, 4), np.float32)
-    if _lib.load().rrv_yuv_input_matrix_depth(_YUV_STANDARDS[standard], int(bool(full_range)), _yuv_depth(bits), n.ctypes.data_as(C.POINTER(C.c_float))) != 0:
-        raise ValueError("rrv_yuv_input_matrix_depth refused %r" % (standard,))
-    return n
+    return _lib_matrix("rrv_yuv_input_matrix_depth", standard, full_range, bits)
 
 
 def _yuv_size(in_format, size):
-    if in_format not in _YUV_LAYOUTS:
-        raise ValueError("in_format must be 'bgr', %s, got %r" % (_YUV_NAMES, in_format))
+    if in_format not in YUV_FORMATS:
+        raise ValueError("in_format must be 'bgr', %s, got %r" % (YUV_FORMAT_NAMES, in_format))
     if size is None or len(size) != 2:
         raise ValueError("%r frames need size=(H, W): the buffer does not carry it" % (in_format,))
     H, W = int(size[0]), int(size[1])
@@ -220,7 +209,7 @@ def yuv_frames_args(frames, in_format, size):
     if a.ndim == 1:
         a = a[None]
     fb = yuv_frame_bytes(H, W)
-    dt = _yuv_np_dtype(in_format)
+    dt = YUV_FORMATS[in_format].dtype
     if a.dtype != dt or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != fb:
         raise ValueError("%r frames of %d x %d are %s [B][%d], got %s %s" % (in_format, H, W, dt.name, fb, a.dtype, a.shape))
     return np.ascontiguousarray(a), H, W
@@ -243,8 +232,8 @@ def _on_device(t, what, device):
 
 def _image_desc(dtype, sp, lay, what):
     import torch
-    if lay in _YUV_LAYOUTS and _YUV_BITS[lay] > 8:      # (the caller has checked the dtype against _yuv_torch_dtypes)
-        return _lib.ImageDesc(_lib.DT_U16, _YUV_LAYOUTS[lay], _SPACES[sp])
+    if lay in YUV_FORMATS and YUV_FORMATS[lay].bits > 8:      # (the caller has checked the dtype against _yuv_torch_dtypes)
+        return _lib.ImageDesc(_lib.DT_U16, YUV_FORMATS[lay].layout, _SPACES[sp])
     if dtype == torch.uint8:
         if sp != "pixel":
             raise ValueError("%s: uint8 images are in the 'pixel' space (0..255), not %r" % (what, sp))
@@ -253,16 +242,16 @@ def _image_desc(dtype, sp, lay, what):
         dt = _lib.DT_F32
     else:
         raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
-    return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else _YUV_LAYOUTS[lay], _SPACES[sp])
+    return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else YUV_FORMATS[lay].layout, _SPACES[sp])
 
 
 def _check_out_layout(out_layout, out_space):
     """the output side of both tensor_io_args forms, before the input is looked at: True for an 'i420' / 'nv12' output"""
     if out_space not in _SPACES:
         raise ValueError("out_space must be one of %s, got %r" % (sorted(_SPACES), out_space))
-    yuv = out_layout in _YUV_LAYOUTS         # uint8 [B][yuv_frame_bytes] in the "pixel" space
+    yuv = out_layout in YUV_FORMATS         # uint8 [B][yuv_frame_bytes] in the "pixel" space
     if out_layout not in _LAYOUTS and not yuv:
-        raise ValueError("out_layout must be 'nchw' (RGB), 'nhwc' (BGR), %s, got %r" % (_YUV_NAMES, out_layout))
+        raise ValueError("out_layout must be 'nchw' (RGB), 'nhwc' (BGR), %s, got %r" % (YUV_FORMAT_NAMES, out_layout))
     if yuv and out_space != "pixel":
         raise ValueError("an %r output is in the 'pixel' space, not %r" % (out_layout, out_space))
     return yuv
@@ -271,7 +260,7 @@ def _check_out_layout(out_layout, out_space):
 def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out):
     """(out_desc, out_shape, out_dtype) of B stylized H x W input frames: shared by tensor_io_args and yuv_tensor_io_args"""
     import torch
-    yuv = out_layout in _YUV_LAYOUTS
+    yuv = out_layout in YUV_FORMATS
     Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
     out_shape = (B, yuv_frame_bytes(Ho, Wo)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
     if not batched:
@@ -335,7 +324,7 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
     batched = x.dim() == 2
     B = x.shape[0] if batched else 1
     out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
-    return TensorIO(x=x if x.is_contiguous() else x.contiguous(), in_desc=_YUV_LAYOUTS[layout], out_desc=out_desc, out_shape=out_shape,
+    return TensorIO(x=x if x.is_contiguous() else x.contiguous(), in_desc=YUV_FORMATS[layout].layout, out_desc=out_desc, out_shape=out_shape,
                     out_dtype=out_dtype, B=B, H=H, W=W, batched=batched)
 
 
@@ -418,6 +407,21 @@ def style_mask_args(style_masks, style_weights, B, H, W, style_num, device, use_
     return StyleMasks(host=host, dev=dev, S=S, images=B if len(shp) == 4 else 1)
 
 
+# The C entry of a transfer by (input is YUV, output is YUV) and what blends the styles: 0 nothing (one state; frame mode), 1 per-frame
+# weights, 2 per-pixel masks.  A BGR output takes the entry's _u8 twin for uint8; the plain BGR entry also names the model and geometry.
+_PLAIN, _BLEND, _MASK = 0, 1, 2
+_HOST_ENTRIES = {
+    (False, False): ("rrv_transfer{model}{geometry}", "rrv_transfer_blend_batch", "rrv_transfer_mask_batch"),
+    (False, True): ("rrv_transfer_yuv", "rrv_transfer_blend_batch_yuv", "rrv_transfer_mask_batch_yuv"),
+    (True, False): ("rrv_transfer_from_yuv", "rrv_transfer_blend_from_yuv", "rrv_transfer_mask_from_yuv"),
+}
+_HOST_ENTRIES[True, True] = _HOST_ENTRIES[True, False]      # (the output descriptor of the _from_yuv entries names the format)
+_TENSOR_ENTRIES = {      # by (input is YUV): the output descriptor names every output format
+    False: ("rrv_transfer_image_device", "rrv_transfer_image_blend_device", "rrv_transfer_image_mask_device"),
+    True: ("rrv_transfer_from_yuv_device", "rrv_transfer_blend_from_yuv_device", "rrv_transfer_mask_from_yuv_device"),
+}
+
+
 class Stylization():
     """``Stylization(checkpoint, cuda=True, use_Global=True)`` (test/framework.py:57).
 
@@ -492,8 +496,8 @@ class Stylization():
 
     def _yuv_depth(self, in_format=None, out_format=None):
         """the uint16 formats carry their depth: install it (rrv_set_yuv_depth) before the call that reads or writes them"""
-        bi = _YUV_BITS.get(in_format, 8)
-        bo = _YUV_BITS.get(out_format, 8)
+        bi = YUV_FORMATS[in_format].bits if in_format in YUV_FORMATS else 8
+        bo = YUV_FORMATS[out_format].bits if out_format in YUV_FORMATS else 8
         if bi > 8 or bo > 8:
             self._chk(self._lib.rrv_set_yuv_depth(self._h, bi if bi > 8 else 0, bo if bo > 8 else 0))
 
@@ -507,7 +511,7 @@ class Stylization():
             a, H, W = yuv_frames_args(patch, in_format, size)
             self._yuv_depth(in_format)
             for f in a:
-                self._chk(self._lib.rrv_add_from_yuv(self._h, f.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], H, W))
+                self._chk(self._lib.rrv_add_from_yuv(self._h, f.ctypes.data_as(C.c_void_p), YUV_FORMATS[in_format].layout, H, W))
             return
         a = _u8_image(patch, "patch")
         self._chk(self._lib.rrv_add(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]))
@@ -656,75 +660,41 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _host_frames_yuv_in(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size):
-        """_host_frames for YUV 4:2:0 input (the rrv_*_from_yuv entries): one call shape for every output format"""
-        a, H, W = yuv_frames_args(frames, in_format, size)
-        B = a.shape[0]
-        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        if out_format != "bgr":
-            shape, odt = (B, yuv_frame_bytes(Ho, Wo)), _yuv_np_dtype(out_format)
-            if out is None:
-                out = _outputs.empty(shape, odt)
-            elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous %s array of shape %r" % (odt.name, shape))
-            desc = _lib.ImageDesc(_lib.DT_U8 if odt == np.uint8 else _lib.DT_U16, _YUV_LAYOUTS[out_format], _lib.SP_PIXEL)
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None):
+        """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
+        size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
+        yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
+        if yuv_out and out_format not in YUV_FORMATS:
+            raise ValueError("out_format must be 'bgr', %s, got %r" % (YUV_FORMAT_NAMES, out_format))
+        if yuv_in:
+            a, H, W = yuv_frames_args(frames, in_format, size)
         else:
-            out, u8 = _output((B, Ho, Wo, 3), dtype, out)
-            desc = _lib.ImageDesc(_lib.DT_U8 if u8 else _lib.DT_F32, _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
-        head = (self._h, a.ctypes.data_as(C.c_void_p), _YUV_LAYOUTS[in_format], B, H, W)
-        tail = (out.ctypes.data_as(C.c_void_p), desc, _lib.TF_PAD_CROP if pad_crop else 0)
+            a = _u8_frames(frames, "frame")
+            H, W = a.shape[1:3]
+        B = a.shape[0]
+        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
+        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out, out_format)
         self._yuv_depth(in_format, out_format)
         if m is not None:
-            self._chk(self._lib.rrv_transfer_mask_from_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, *tail))
+            blend, styles = _MASK, (m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images)
         elif style_weights is not None:
             w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
-            self._chk(self._lib.rrv_transfer_blend_from_yuv(*head, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, *tail))
+            blend, styles = _BLEND, (w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S)
         else:
-            self._chk(self._lib.rrv_transfer_from_yuv(*head, tail[0], desc, tail[2] | (0 if self.use_Global else _lib.TF_FRAME_MODE)))
-        return out
-
-    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None):
-        """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames, the checked masks or
-        weights, the output and the entry of the model (rrv_transfer_mask_batch, rrv_transfer_blend_batch, or the plain one);
-        out_format "i420" / "nv12": their _yuv forms, uint8 [B][yuv_frame_bytes] whatever `dtype` says"""
-        if out_format != "bgr" and out_format not in _YUV_LAYOUTS:
-            raise ValueError("out_format must be 'bgr', %s, got %r" % (_YUV_NAMES, out_format))
-        if in_format != "bgr":
-            return self._host_frames_yuv_in(frames, out, dtype, style_weights, style_masks, pad_crop, out_format, in_format, size)
-        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
-            a = np.ascontiguousarray(frames)
-        else:
-            a = np.stack([_u8_image(f, "frame") for f in frames])
-        B, H, W, _ = a.shape
-        m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        head = (self._h, a.ctypes.data_as(C.c_void_p), B, H, W)
-        if out_format != "bgr":
-            shape, odt = (B, yuv_frame_bytes(H, W) if pad_crop else yuv_frame_bytes(H // 8 * 8, W // 8 * 8)), _yuv_np_dtype(out_format)
-            if out is None:
-                out = _outputs.empty(shape, odt)
-            elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous %s array of shape %r" % (odt.name, shape))
-            lay, dst = _YUV_LAYOUTS[out_format], out.ctypes.data_as(C.c_void_p)
-            self._yuv_depth(None, out_format)
-            if m is not None:
-                self._chk(self._lib.rrv_transfer_mask_batch_yuv(*head, m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop), lay, dst))
-            elif style_weights is not None:
-                w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
-                self._chk(self._lib.rrv_transfer_blend_batch_yuv(*head, w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, int(pad_crop), lay, dst))
-            else:
-                flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
-                self._chk(self._lib.rrv_transfer_yuv(*head, flags, lay, dst))
-            return out
-        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out)
-        if m is not None:
-            name, args = "rrv_transfer_mask_batch", (m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images, int(pad_crop))
-        elif style_weights is not None:
-            w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global)
-            name, args = "rrv_transfer_blend_batch", (w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S, int(pad_crop))
-        else:
-            name, args = ("rrv_transfer" if self.use_Global else "rrv_transfer_frame_mode") + ("_frames" if pad_crop else "_batch"), ()
-        self._chk(self._entry(name, u8)(*head, *args, out.ctypes.data_as(C.c_void_p)))
+            blend, styles = _PLAIN, ()
+        name = _HOST_ENTRIES[yuv_in, yuv_out][blend].format(model="" if self.use_Global else "_frame_mode", geometry="_frames" if pad_crop else "_batch")
+        src, dst = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global or blend != _PLAIN else _lib.TF_FRAME_MODE)
+        if yuv_in:        # (h, in, in_layout, B, H, W, [weights, S | masks, S, images,] out, its descriptor, flags)
+            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
+            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+            args = (src, YUV_FORMATS[in_format].layout, B, H, W, *styles, dst, desc, flags)
+        elif yuv_out:     # (h, in, B, H, W, flags | [weights, S | masks, S, images,] pad_crop, layout, out)
+            args = (src, B, H, W, *((flags,) if blend == _PLAIN else styles + (int(pad_crop),)), YUV_FORMATS[out_format].layout, dst)
+        else:             # (h, in, B, H, W, [weights, S, pad_crop | masks, S, images, pad_crop,] out); the _u8 twin by the output's dtype
+            name += "_u8" if u8 else ""
+            args = (src, B, H, W, *(() if blend == _PLAIN else styles + (int(pad_crop),)), dst)
+        self._chk(getattr(self._lib, name)(self._h, *args))
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
@@ -798,7 +768,7 @@ class Stylization():
         in torch.uint16 tensors (this build's torch has the dtype; a torch.int16 tensor holding the same bits, x.view(torch.int16),
         is taken too, and `out` may be one); a fresh output is torch.uint16."""
         import torch
-        yuv_in = layout in _YUV_LAYOUTS
+        yuv_in = layout in YUV_FORMATS
         if yuv_in:
             if space != "pixel":
                 raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
@@ -807,10 +777,7 @@ class Stylization():
         else:
             a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
                                out_layout=out_layout, pad_crop=pad_crop, out=out)
-        mask_fn, blend_fn, plain_fn = ((self._lib.rrv_transfer_mask_from_yuv_device, self._lib.rrv_transfer_blend_from_yuv_device,
-                                        self._lib.rrv_transfer_from_yuv_device) if yuv_in else
-                                       (self._lib.rrv_transfer_image_mask_device, self._lib.rrv_transfer_image_blend_device,
-                                        self._lib.rrv_transfer_image_device))
+        plain_fn, blend_fn, mask_fn = (getattr(self._lib, name) for name in _TENSOR_ENTRIES[yuv_in])
         w = m = None
         if style_masks is not None:
             m = style_mask_args(style_masks, style_weights, a.B, a.H, a.W, self.style_num, self.device, self.use_Global, tensors=True)
@@ -897,6 +864,21 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_PRED, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
+    def _set_matrix(self, set8, set16, matrix_of, input_side, standard, full_range, bits):
+        """set_yuv_matrix / set_yuv_input_matrix: the side's 8-bit or uint16 setter, its depth, and matrix_of(standard, full_range, bits)"""
+        bits = _yuv_depth(bits)
+        setter = set8 if bits == 8 else set16
+        if bits > 8:
+            self._chk(self._lib.rrv_set_yuv_depth(self._h, bits if input_side else 0, 0 if input_side else bits))
+        if standard is None:
+            self._chk(setter(self._h, None))
+            return matrix_of("bt601", False, bits)
+        m = matrix_of(standard, full_range, bits) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
+        if m.size != 12:
+            raise ValueError("a YUV matrix has 12 coefficients, got %d" % m.size)
+        self._chk(setter(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
+        return m.reshape(3, 4).copy()
+
     def set_yuv_matrix(self, standard="bt601", full_range=False, bits=8):
         """The conversion matrix of the "i420" / "nv12" outputs (rrv_set_yuv_matrix): a standard ("bt601" | "bt709") and range, or
         twelve finite floats ([3][4]: rows Y, Cb, Cr; columns R, G, B, offset) in place of `standard`; None restores the default,
@@ -904,18 +886,7 @@ class Stylization():
         bits = 10, 12, 16: the matrix of the uint16 outputs instead ("i420p10", "p010", ..: rrv_set_yuv16_matrix, independent of the
         8-bit one), installed together with that output depth (rrv_set_yuv_depth); None: BT.601 limited range at the depth in force
         when a call launches."""
-        bits = _yuv_depth(bits)
-        setter = self._lib.rrv_set_yuv_matrix if bits == 8 else self._lib.rrv_set_yuv16_matrix
-        if bits > 8:
-            self._chk(self._lib.rrv_set_yuv_depth(self._h, 0, bits))
-        if standard is None:
-            self._chk(setter(self._h, None))
-            return yuv_matrix("bt601", False, bits)
-        m = yuv_matrix(standard, full_range, bits) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
-        if m.size != 12:
-            raise ValueError("a YUV matrix has 12 coefficients, got %d" % m.size)
-        self._chk(setter(self._h, m.ctypes.data_as(C.POINTER(C.c_float))))
-        return m.reshape(3, 4).copy()
+        return self._set_matrix(self._lib.rrv_set_yuv_matrix, self._lib.rrv_set_yuv16_matrix, yuv_matrix, False, standard, full_range, bits)
 
     def set_yuv_input_matrix(self, standard="bt601", full_range=False, bits=8):
         """The conversion matrix of the "i420" / "nv12" INPUTS (rrv_set_yuv_input_matrix): a standard ("bt601" | "bt709") and range,
@@ -924,18 +895,7 @@ class Stylization():
         [3][4] matrix now installed.
         bits = 10, 12, 16: the matrix of the uint16 inputs instead (rrv_set_yuv16_input_matrix), installed together with that input
         depth; None: BT.601 limited range at the depth in force when a call launches."""
-        bits = _yuv_depth(bits)
-        setter = self._lib.rrv_set_yuv_input_matrix if bits == 8 else self._lib.rrv_set_yuv16_input_matrix
-        if bits > 8:
-            self._chk(self._lib.rrv_set_yuv_depth(self._h, bits, 0))
-        if standard is None:
-            self._chk(setter(self._h, None))
-            return yuv_input_matrix("bt601", False, bits)
-        n = yuv_input_matrix(standard, full_range, bits) if isinstance(standard, str) else np.ascontiguousarray(standard, dtype=np.float32).reshape(-1)
-        if n.size != 12:
-            raise ValueError("a YUV matrix has 12 coefficients, got %d" % n.size)
-        self._chk(setter(self._h, n.ctypes.data_as(C.POINTER(C.c_float))))
-        return n.reshape(3, 4).copy()
+        return self._set_matrix(self._lib.rrv_set_yuv_input_matrix, self._lib.rrv_set_yuv16_input_matrix, yuv_input_matrix, True, standard, full_range, bits)
 
     def set_host_io(self, mode):
         """0 (default): staged H2D / D2H copies; 1: zero copy — kernels read / write page-locked host memory directly."""
@@ -1024,10 +984,7 @@ class MultiStyleStylization(Stylization):
         """`generate_content_features` for a run of equally sized frames (a list, or one [B][H][W][3] array) in one call:
         the reference's caching loop ("Multi-style Interpolation/test.py":87-101) pipelined inside the library
         (rrv_generate_content_features_batch).  Returns one ContentFeature per frame."""
-        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.dtype == np.uint8 and frames.shape[3] == 3:
-            a = np.ascontiguousarray(frames)
-        else:
-            a = np.stack([_u8_image(f, "content") for f in frames])
+        a = _u8_frames(frames, "content")
         B, H, W, _ = a.shape
         ids = (C.c_int * B)()
         self._chk(self._lib.rrv_generate_content_features_batch(self._h, a.ctypes.data_as(C.c_void_p), B, H, W, ids))

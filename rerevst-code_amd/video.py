@@ -3,7 +3,11 @@ drop-in: reflect padding / cropping (ReshapeTool, :61-83, :167), the global-feat
 sampling schedule (:129-148) and the frame -> rank sharding used for multi-GPU runs.
 Host-side, negligible cost; numpy only.
 """
+import collections
+
 import numpy as np
+
+from ._lib import LAY_I420, LAY_NV12, LAY_I420_16, LAY_P016, YUV_BT601, YUV_BT709     # constants only: nothing here loads the shared library
 
 
 def padded_size(n):
@@ -86,9 +90,17 @@ def resize_bilinear(img, size):
     return np.clip(np.rint(top * (1 - fy) + bot * fy), 0, 255).astype(np.uint8)
 
 
-YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}      # (Kr, Kb); Kg = 1 - Kr - Kb
-
-
+# ===== the YUV 4:2:0 formats by name: the one table framework.py and the drivers read =====
+# layout: RRV_LAY_* of include/rerevst_hip.h; bits: the code depth; dtype: of a sample (uint16 above 8 bits); planar: [Y][Cb][Cr], else [Y][CbCr].
+# "i420pNN": planar, the code in the low bits (ffmpeg yuv420pNNle, Y4M C420pNN); "p0NN": semi-planar, the code in the high bits (ffmpeg
+# p0NNle, hardware decoders / encoders).
+YuvFormat = collections.namedtuple("YuvFormat", "layout bits dtype planar")
+YUV_FORMATS = {name: YuvFormat(layout, bits, np.dtype(np.uint8 if bits == 8 else np.uint16), planar) for name, layout, bits, planar in (
+    ("i420", LAY_I420, 8, True), ("nv12", LAY_NV12, 8, False),
+    ("i420p10", LAY_I420_16, 10, True), ("i420p12", LAY_I420_16, 12, True), ("i420p16", LAY_I420_16, 16, True),
+    ("p010", LAY_P016, 10, False), ("p012", LAY_P016, 12, False), ("p016", LAY_P016, 16, False))}
+YUV_FORMAT_NAMES = "'i420', 'nv12', 'i420p10' / 'p12' / 'p16' or 'p010' / 'p012' / 'p016'"      # as the refusals list them
+YUV_STANDARDS = {"bt601": (YUV_BT601, 0.299, 0.114), "bt709": (YUV_BT709, 0.2126, 0.0722)}      # (RRV_YUV_*, Kr, Kb); Kg = 1 - Kr - Kb
 YUV_DEPTHS = (8, 10, 12, 16)
 
 
@@ -104,7 +116,7 @@ def yuv_matrix(standard="bt601", full_range=False, bits=8):
     and the chroma differences times 224/255.  bits = 10, 12, 16: d-bit codes — the limited matrix times 2^(d-8); full range
     (2^d - 1)/255 in place of 1 and 2^(d-1) in place of 128.  Evaluated in double, each coefficient rounded once to float32."""
     d = _yuv_depth(bits)
-    kr, kb = YUV_STANDARDS[standard]
+    _, kr, kb = YUV_STANDARDS[standard]
     k = np.array([kr, 1.0 - kr - kb, kb], np.float64)
     s, top = float(1 << (d - 8)), float((1 << d) - 1)
     ys, cs = (top / 255.0, top / 255.0) if full_range else (219.0 / 255.0 * s, 224.0 / 255.0 * s)
@@ -117,8 +129,10 @@ def yuv_matrix(standard="bt601", full_range=False, bits=8):
 
 
 def yuv_frame_bytes(H, W, bits=8):
-    """bytes of one H x W 4:2:0 frame: H*W + 2*CH*CW samples, one byte each at 8 bits and two above"""
-    return (H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
+    """Bytes of one H x W frame in I420 or NV12: H*W luma samples and two chroma planes of ceil(H/2) x ceil(W/2); bits = 10, 12, 16: the
+    same samples in uint16, twice the bytes.  yuv_frame_bytes(H, W) is also the SAMPLE count of a frame at any depth: the last axis of
+    the arrays the YUV formats take and return."""
+    return (int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
 
 
 def bgr_to_yuv420(img, m, layout="i420", bits=8):
@@ -165,7 +179,7 @@ def yuv_input_matrix(standard="bt601", full_range=False, bits=8):
     bits = 10, 12, 16 (s = 2^(d-8)): limited range Y' = (Y / s - 16) 255/219, C' = (C / s - 128) 255/224; full range Y' = 255/(2^d - 1) Y,
     C' = 255/(2^d - 1) (C - 2^(d-1)).  Evaluated in double, each coefficient rounded once to float32."""
     d = _yuv_depth(bits)
-    kr, kb = YUV_STANDARDS[standard]
+    _, kr, kb = YUV_STANDARDS[standard]
     kg = 1.0 - kr - kb
     s, top = float(1 << (d - 8)), float((1 << d) - 1)
     ys, cs, y0 = (255.0 / top, 255.0 / top, 0.0) if full_range else (255.0 / 219.0 / s, 255.0 / 224.0 / s, 16.0 * s)
