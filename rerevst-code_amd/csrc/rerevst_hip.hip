@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <thread>
 #include <stdio.h>
@@ -256,8 +257,23 @@ struct rrv_ctx {
         // rrv_transfer_mask_batch: the sub-batch's style masks, in HBM and (for a pageable caller array) page-locked.  Grow-only and
         // released by rrv_destroy, as the staging buffers above are: rrv_set_debug and the other calls that drop the WORKSPACES keep all of them
         float *mask = nullptr, *mask_pin = nullptr; size_t mask_cap = 0, mask_pin_cap = 0;
+        // the call's last sub-batch leaves in pieces (SeqHook): piece i's conv_last records piece_ev[i], its D2H on copy_out waits for it
+        static constexpr int PIECES_MAX = 16;
+        hipEvent_t piece_ev[PIECES_MAX] = {nullptr};
     } hstage[4];
     hipStream_t copy_in = nullptr, copy_out = nullptr;
+    // How host_pipeline orders its sub-batches (SeqHook; RRV_HOST_PHASE / RRV_HOST_PIECE are A/B knobs, the defaults the measured choice).
+    // host_phase: the tail of sub-batch k+1's launch sequence waits for the last kernel of sub-batch k.  host_piece_px: pixels per piece of
+    // the last sub-batch's conv_last + D2H (0: one launch, one copy; 1 / 2 / 4 frames at 640 x 640 measured alike, 1.03 / 1.07 / 1.12 ms of drain).
+    bool host_phase = true;
+    long host_piece_px = 2L * 640 * 640;
+    // RRV_TIMELINE: the pipelined host entries time each call with events of their own (created by rrv_create, none per call) and print
+    // one line per call to stderr.  Unset: no event exists and no call records one.
+    struct Timeline {
+        static constexpr int N = 64;      // sub-batches per call it can describe (a longer call prints nothing)
+        bool on = false;
+        hipEvent_t entry = nullptr, first = nullptr, k_end[N] = {nullptr}, d_end[N] = {nullptr};
+    } tl;
     // rrv_transfer_async: ticket t lives in staging set t % 4 until rrv_transfer_wait(t) (or a later submission that needs
     // its set) retires it; `out` / `out_bytes` = where a pageable caller buffer still has to be filled from pin_out
     struct Ticket { long id = -1; void* out = nullptr; size_t out_bytes = 0; bool open = false; } tickets[4];
@@ -1231,7 +1247,8 @@ struct BlkDesc { const char* name; int cout, n1, n2, nada, sty; };
 const BlkDesc BLKS[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 128, N_S3N1, N_S3N2, N_DEC3, 1}, {"slice2", 64, N_S2N1, N_S2N2, N_DEC4, 0}};
 
 // block k of the per-frame path, fused across its normalisation layers (saved statistics)
-int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr) {
+// mid_wait: conv2 is launched behind this event (SeqHook::tail_wait)
+int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr, hipEvent_t mid_wait = nullptr) {
     const BlkDesc& b = BLKS[k];
     Tens &xs = d.xs[k], &a = d.a[k], &o = d.o[k], &qa = d.qa[k];
     const float* st = h->cur->active;
@@ -1248,6 +1265,7 @@ int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const
     if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
     if (wa) { c.wy0 = wa->y0; c.wx0 = wa->x0; c.wy1 = wa->y1; c.wx1 = wa->x1; }
     RCHK(conv(h, c));
+    if (mid_wait) HIPCHK(hipStreamWaitEvent(h->stream, mid_wait, 0));
     c = ConvCall{a_in, &o, &h->conv[p + ".conv2"], a.H, a.W}; c.B = B; c.in_p8 = p8;
     if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
     c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[b.n2]; c.res = &xs; c.n2 = st + SL.norm[b.nada]; c.sty = st + SL.sty[b.sty];
@@ -1268,9 +1286,20 @@ LastFn last_kernel(OutFmt f) {
 }
 
 // Decoder.slice1 + transform_back_image (conv_last_k) on a normalised slice2 output
-int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr) {
+// fr: launch frames [fr->first, fr->first + fr->count) of the B only (every tensor and output format is one contiguous block per frame, of
+// fr->out_bytes in d_out); the pre-clamp tap's bookkeeping stays that of the whole batch
+struct FrameRange { int first, count; size_t out_bytes; };
+int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr,
+             const FrameRange* fr = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
+    if (fr) {
+        lp.in += (size_t)fr->first * (size_t)(H + 2) * (size_t)(W + 2) * 64;
+        lp.out_img = (char*)d_out + (size_t)fr->first * fr->out_bytes;
+        if (pre) lp.out_pre = pre + (size_t)fr->first * H * W * 3;
+        lp.B = fr->count;
+    }
+    const int LB = lp.B;
     if (fmt.yuv) {
         if (pc && ((pc->top | pc->left) & 1)) return fail(h, RRV_E_ARG, "conv_last: the YUV form needs an even crop origin");
         const YuvLaunch y = yuv_launch_params(h->yuv_out, false, yuv16_layout(fmt.yuv), fmt.yuv == RRV_LAY_P016);
@@ -1279,17 +1308,31 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
     }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
-    return launch(h, "conv_last", 2.0 * B * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * B * H * W, [&] {
-        const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * B), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
+    return launch(h, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
+        const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * LB), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
         hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
 }
+
+// What host_pipeline asks of one launch sequence beyond its frames.
+//   tail_wait  the sequence's last two launches (slice2.conv2 and conv_last, 1.9 of the 19.7 ms of 16 frames at 640 x 640) are queued behind
+//              this event, the previous sub-batch's last kernel.  The two compute streams still run side by side all the time, but consecutive
+//              sub-batches finish that tail apart instead of together, which is longer than a sub-batch's D2H (1.4 ms): every D2H but the
+//              call's last runs under kernels.  Measured (profiles/r09_call_timeline.txt): a wait further up (in front of the first
+//              filter_down, half a sequence) loses more than the copy it hides, since a stream then runs alone for half a sequence at both
+//              ends of a call, 10.4 ms in place of 9.3; a wait in front of conv_last alone (0.4 ms) hides nothing.
+//   piece      > 0: conv_last runs over ranges of `piece` frames, each followed by its own D2H on `copy` (piece i's ordered by ev[i]) of
+//              frame_bytes per frame from d_out to h_dst: the call's last copy starts behind the first range, not behind the sub-batch
+struct SeqHook {
+    hipEvent_t tail_wait = nullptr;
+    int piece = 0; char* h_dst = nullptr; size_t frame_bytes = 0; hipStream_t copy = nullptr; hipEvent_t* ev = nullptr;
+};
 
 // feat != nullptr: skip the encoder and start from a cached raw relu4_1 feature (ring layout, [1,H/8,W/8,512])
 // feats != nullptr (with h->state_images == B): one cached feature per image, each normalised with ITS state set
 // slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
 int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* feat = nullptr,
-                    const float* const* feats = nullptr) {
+                    const float* const* feats = nullptr, const SeqHook* hk = nullptr) {
     const PadCrop* const pc = io.pc;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     // Any frame size, as the reference: the three 2x2 max pools floor (H, W) to (H/8, W/8) and the decoder returns
@@ -1360,9 +1403,21 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     }
     for (int k = 0; k < 3; ++k) {       // the windows apply to the full-resolution block only
         const bool win = roi && k == 2;
-        RCHK(resblock_frame(h, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr));
+        RCHK(resblock_frame(h, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr, hk && k == 2 ? hk->tail_wait : nullptr));
     }
-    RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr));
+    if (hk && hk->piece > 0 && hk->piece < B) {
+        int i = 0;
+        for (int b0 = 0; b0 < B; b0 += hk->piece, ++i) {
+            const FrameRange fr{b0, B - b0 < hk->piece ? B - b0 : hk->piece, hk->frame_bytes};
+            RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr, &fr));
+            const size_t off = (size_t)b0 * hk->frame_bytes;
+            HIPCHK(hipEventRecord(hk->ev[i], h->stream));
+            HIPCHK(hipStreamWaitEvent(hk->copy, hk->ev[i], 0));
+            HIPCHK(hipMemcpyAsync(hk->h_dst + off, (const char*)d_out + off, (size_t)fr.count * hk->frame_bytes, hipMemcpyDeviceToHost, hk->copy));
+        }
+    } else {
+        RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr));
+    }
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
         HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
@@ -1895,6 +1950,15 @@ int rrv_create(int device, rrv_handle* out) {
     for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipEventCreateWithFlags(&h->slot_ev[i], hipEventDisableTiming) == hipSuccess;
     for (auto& st : h->hstage)
         for (hipEvent_t* e : {&st.in_done, &st.k_done, &st.out_done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (auto& st : h->hstage)
+        for (hipEvent_t& e : st.piece_ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    if (const char* e = getenv("RRV_HOST_PHASE")) h->host_phase = atoi(e) != 0;
+    if (const char* e = getenv("RRV_HOST_PIECE")) { const long n = atol(e); h->host_piece_px = (n < 0 ? 0 : n > 64 ? 64 : n) * 640L * 640L; }      // in 640 x 640 frames
+    if (const char* e = getenv("RRV_TIMELINE")) h->tl.on = atoi(e) != 0;
+    if (h->tl.on) {
+        ok = ok && hipEventCreate(&h->tl.entry) == hipSuccess && hipEventCreate(&h->tl.first) == hipSuccess;
+        for (int i = 0; i < rrv_ctx::Timeline::N; ++i) ok = ok && hipEventCreate(&h->tl.k_end[i]) == hipSuccess && hipEventCreate(&h->tl.d_end[i]) == hipSuccess;
+    }
     // the dynamic-LDS opt-in is a per-device function attribute: set it for THIS device, whatever other handles did
     for (const ConvKey& e : WINO_TABLE)
         if (ok && e.attr) ok = e.attr() == hipSuccess;
@@ -2017,7 +2081,11 @@ int rrv_destroy(rrv_handle h) {
         if (st.mask) (void)hipFree(st.mask);
         if (st.mask_pin) (void)hipHostFree(st.mask_pin);
         for (hipEvent_t e : {st.in_done, st.k_done, st.out_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : st.piece_ev) if (e) (void)hipEventDestroy(e);
     }
+    for (hipEvent_t e : {h->tl.entry, h->tl.first}) if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < rrv_ctx::Timeline::N; ++i)
+        for (hipEvent_t e : {h->tl.k_end[i], h->tl.d_end[i]}) if (e) (void)hipEventDestroy(e);
     if (h->copy_in) (void)hipStreamDestroy(h->copy_in);
     if (h->copy_out) (void)hipStreamDestroy(h->copy_out);
     for (ProfEntry& e : h->prof) { (void)hipEventDestroy(e.e0); (void)hipEventDestroy(e.e1); }
@@ -2565,7 +2633,8 @@ static int stage_blend_weights(rrv_handle h, int slot, const float* wts, size_t 
 //          with per-image state (transfer_device, state_images).  With a fixed kernel mode a frame's arithmetic is that of
 //          rrv_transfer_blend on the frame alone, bit for bit.
 //   MASK   mask_mode_device; it touches no state set
-static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const Xfer& x) {
+// hk (host_pipeline, a request of one launch sequence): handed to transfer_device
+static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const Xfer& x, const SeqHook* hk = nullptr) {
     // What is in flight and reads the state sets this request rewrites drains first: a global entry's work reads state set 0, which
     // slot 0's sets include (frame-mode and blended launches write a slot's sets on that slot's own stream, in order)
     switch (x.model) {
@@ -2593,7 +2662,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
         void* const out = (char*)d_out + (size_t)b0 * fo;
         switch (x.model) {
         case Model::GLOBAL:
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io));
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, nullptr, hk));
             break;
         case Model::FRAME:
             RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, io));
@@ -2614,7 +2683,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             h->active_src = -2;
             for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
             h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io));
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, nullptr, hk));      // (a host sub-batch is one group: the hook's sequence)
             h->set_images[slot] = cnt;
             break;
         }
@@ -2902,6 +2971,32 @@ static bool is_pinned(const void* ptr, size_t bytes) {
     return true;
 }
 static int retire_ticket(rrv_handle h, int set);
+// RRV_TIMELINE: one line per call of a pipelined host entry, every time in ms after the entry event (recorded on an idle stream once the
+// staging is claimed, `setup` ms of host time into the call): the start of the first kernel, the end of each sub-batch's last kernel and
+// of its D2H, and the host's wall time from entry to return.  tools/call_timeline.py reads these lines.
+static int timeline_print(rrv_handle h, const char* who, int frames, int H, int W, int n, double setup_ms, double wall_ms) {
+    auto& tl = h->tl;
+    auto at = [&](hipEvent_t e) { float ms = -1.f; if (hipEventElapsedTime(&ms, tl.entry, e) != hipSuccess) { (void)hipGetLastError(); ms = -1.f; } return ms; };
+    std::string line;
+    char b[96];
+    snprintf(b, sizeof b, "rrv_timeline %s frames=%d size=%dx%d subs=%d", who, frames, H, W, n); line += b;
+    snprintf(b, sizeof b, " setup=%.3f wall=%.3f first_kernel=%.3f k_end=", setup_ms, wall_ms, at(tl.first)); line += b;
+    for (int k = 0; k < n; ++k) { snprintf(b, sizeof b, "%s%.3f", k ? "," : "", at(tl.k_end[k])); line += b; }
+    line += " d2h_end=";
+    for (int k = 0; k < n; ++k) { snprintf(b, sizeof b, "%s%.3f", k ? "," : "", at(tl.d_end[k])); line += b; }
+    fprintf(stderr, "%s\n", line.c_str());
+    return RRV_OK;
+}
+static double host_ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+// frames per piece of a last sub-batch of nb frames of H x W (0: delivered whole): h->host_piece_px pixels, at most PIECES_MAX pieces
+static int tail_piece(rrv_handle h, int nb, int H, int W) {
+    if (h->host_piece_px <= 0) return 0;
+    long p = h->host_piece_px / ((long)H * W);
+    const long least = (nb + rrv_ctx::HostStage::PIECES_MAX - 1) / rrv_ctx::HostStage::PIECES_MAX;
+    if (p < least) p = least;
+    if (p < 1) p = 1;
+    return p < nb ? (int)p : 0;
+}
 // The entries that use all staging sets: open look-ahead tickets own sets, so retire them and wait for everything; the
 // entry then runs its own slots, and the alternating device entries start again at slot 0 after it.
 static int claim_staging(rrv_handle h) {
@@ -2915,6 +3010,7 @@ static int claim_staging(rrv_handle h) {
 // staged mask block.
 static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const Xfer& x) {
     if (!h || !frames || !out) return RRV_E_ARG;
+    const auto t_entry = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x, true));
     const int B = x.B;
@@ -2925,12 +3021,12 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     char* const outc = (char*)out;
     const int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
     const size_t mfl = x.mask_floats();
-    auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out) -> int {      // sub-batch k's kernels
+    auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
         part.B = nb;
         if (x.wts) part.wts = x.wts + (size_t)k * sub * x.ns;
         if (mask) { part.mask = h->hstage[k % HOST_SETS].mask; part.mask_images = mask_images == 1 ? 1 : nb; }
-        return run_xfer(h, slot, d_in, d_out, part);
+        return run_xfer(h, slot, d_in, d_out, part, hk);
     };
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
     // the masks are staged like the frames: a sub-batch's part goes through the set's page-locked block (unless the caller's array is
@@ -2942,6 +3038,14 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const int nchunk = (B + sub - 1) / sub;
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
     const bool zin = h->host_io == 1 || h->host_io == 2, zout = h->host_io == 1 || h->host_io == 3;
+    // The tail wait and the piecewise delivery (SeqHook) order the sub-batches of the models that run transfer_device, on two streams with
+    // staged copies both ways.  Everything else keeps one launch per layer and sub-batch, unordered: one sub-batch or one stream, the
+    // profiled step (slot 0 only), the debug levels, a caller's stream, zero copy.
+    const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !h->caller_sync && h->host_io == 0 &&
+                         (x.model == Model::GLOBAL || x.model == Model::BLEND);
+    const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
+    double tl_setup = 0;
+    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));
@@ -2987,7 +3091,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
             if (mask) HIPCHK(hipMemcpyAsync(st.mask, msrc, mbytes, hipMemcpyHostToDevice, cs));
-            rc = run(slot, k, st.dev.in, nb, st.dev.out);
+            rc = run(slot, k, st.dev.in, nb, st.dev.out, nullptr);
             if (rc != RRV_OK) break;
             HIPCHK(hipMemcpyAsync(out_pin ? out : st.pin.out, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, cs));
             HIPCHK(hipStreamSynchronize(cs));
@@ -3010,14 +3114,27 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
         void* const h_dst = out_pin ? outc + (size_t)k * sub * fob : st.pin.out;
         if (reuse) HIPCHK(hipStreamWaitEvent(cs, st.out_done, 0));             // d_out / pin_out of k-4 has been delivered
         void* const k_out = zout ? h_dst : st.dev.out;
-        rc = run(slot, k, k_in, nb, k_out);
+        SeqHook hk;
+        if (ordered) {
+            if (h->host_phase && k > 0) hk.tail_wait = h->hstage[(k - 1) % HOST_SETS].k_done;      // recorded in this call, behind sub-batch k-1's last kernel
+            if (k == nchunk - 1) {
+                hk.piece = tail_piece(h, nb, x.KH(), x.KW());
+                hk.h_dst = (char*)h_dst; hk.frame_bytes = fob; hk.copy = h->copy_out; hk.ev = st.piece_ev;
+            }
+        }
+        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, cs));
+        rc = run(slot, k, k_in, nb, k_out, ordered ? &hk : nullptr);
         if (rc != RRV_OK) break;
+        if (tl_on) HIPCHK(hipEventRecord(h->tl.k_end[k], cs));
         if (!zin || mask) HIPCHK(hipEventRecord(st.k_done, cs));
         if (zout) { HIPCHK(hipEventRecord(st.out_done, cs)); continue; }
         if (zin && !mask) HIPCHK(hipEventRecord(st.k_done, cs));
-        HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, h->copy_out));
+        if (hk.piece == 0) {      // (in pieces: transfer_device has queued each range's copy behind its conv_last)
+            HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
+            HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)nb * fob, hipMemcpyDeviceToHost, h->copy_out));
+        }
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
+        if (tl_on) HIPCHK(hipEventRecord(h->tl.d_end[k], h->copy_out));
     }
     if (rc != RRV_OK) { (void)sync_all(h); return rc; }
     const int first_open = (host_in || !out_pin) ? (nchunk - HOST_SETS < 0 ? 0 : nchunk - HOST_SETS) : 0;
@@ -3027,6 +3144,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     } else {
         for (int k = first_open; k < nchunk; ++k) RCHK(drain(k));
     }
+    if (tl_on) RCHK(timeline_print(h, "host_pipeline", B, x.KH(), x.KW(), nchunk, tl_setup, host_ms_since(t_entry)));
     return RRV_OK;
 }
 
@@ -3479,6 +3597,7 @@ int rrv_transfer_features_u8(rrv_handle h, int feature_id, const float* wts, int
 // (bit-identical to one frame per call); the default mode chooses the kernels by the group's frames.  Features beyond the cache cap (kept as pixels) run alone through the encoder + decoder entry.
 static int transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, void* out, OutFmt fmt) {
     if (!h || !ids || !wts || !out || n < 1 || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
+    const auto t_entry = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(h->dev));
     for (int i = 0; i < n; ++i)
         if (ids[i] < 0 || ids[i] >= (int)h->features.size() || !(h->features[ids[i]].p || h->features[ids[i]].u8)) return fail(h, RRV_E_ARG, "transfer: unknown feature id");
@@ -3517,6 +3636,9 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         RCHK(stage_reserve(h, i, 0, out_pin ? 0 : (size_t)G * npx, true));
     }
     SetScope scope{h, -2};
+    const bool tl_on = h->tl.on && ngroups > 1 && ngroups <= rrv_ctx::Timeline::N;
+    double tl_setup = 0;
+    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
     auto drain = [&](int k) -> int {
         auto& st = h->hstage[k % nslots];
         HIPCHK(hipEventSynchronize(st.out_done));
@@ -3547,6 +3669,8 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
             for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
         }
         h->active_src = -2;
+        void* const h_dst = out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out;
+        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, h->streams[slot]));
         if (fp[0] && cnt == 1) {       // one frame per launch: its state set is simply the current one (shared-state kernels)
             RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, io, fp[0]));
         } else if (fp[0]) {
@@ -3558,13 +3682,16 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
             RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, io));      // re-encode the pixels
         }
         h->set_images[slot] = cnt;
+        if (tl_on) HIPCHK(hipEventRecord(h->tl.k_end[k], h->streams[slot]));
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
-        HIPCHK(hipMemcpyAsync(out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out, st.dev.out, (size_t)cnt * npx, hipMemcpyDeviceToHost, h->copy_out));
+        HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)cnt * npx, hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
+        if (tl_on) HIPCHK(hipEventRecord(h->tl.d_end[k], h->copy_out));
     }
     if (out_pin) HIPCHK(hipStreamSynchronize(h->copy_out));
     else for (int k = (ngroups - nslots < 0 ? 0 : ngroups - nslots); k < ngroups; ++k) RCHK(drain(k));
+    if (tl_on) RCHK(timeline_print(h, "transfer_features_batch", n, H, W, ngroups, tl_setup, host_ms_since(t_entry)));
     return RRV_OK;
 }
 int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, float* out) {
