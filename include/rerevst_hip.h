@@ -301,9 +301,9 @@ int rrv_transfer_image_device(rrv_handle h, const void* d_in, rrv_image_desc in,
  * flags: RRV_TF_PAD_CROP, RRV_TF_ON_STREAM as above; RRV_TF_FRAME_MODE is RRV_E_ARG (the reference's frame-mode model has no
  * blended state).  RRV_TF_WEIGHTS_DEVICE: style_weight points to device memory, produced on hip_stream (or complete before the
  * call): a blend kernel reads it there, in stream order, and the host never sees the values — weights computed on the GPU need
- * no synchronisation and no copy.  Without it style_weight is host memory, consumed before the call returns (staged through a
- * page-locked ring and copied in stream order: no host synchronisation either); the same float32 values give the same bits
- * either way.  Workspace per slot: 64 x RRV_MAX_STYLES floats in HBM, four times that page-locked. */
+ * no synchronisation and no copy.  Without it style_weight is host memory, read before the call returns (the weights travel in
+ * the blend kernel's argument, a launch sequence's rows at a time: no copy, no host synchronisation and no workspace); the same
+ * float32 values give the same bits either way. */
 #define RRV_TF_WEIGHTS_DEVICE (1 << 3)   /* = 8, next to RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM */
 int rrv_transfer_image_blend_device(rrv_handle h, const void* d_in, rrv_image_desc in, int B, int H, int W,
                                     const float* style_weight, int n_styles,

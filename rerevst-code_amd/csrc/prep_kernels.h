@@ -552,34 +552,19 @@ __global__ void frame_sets_init_k(const float* __restrict__ blob, float* __restr
 
 // blended state for multi-style interpolation: out = sum_s w[s] * state_s
 // ("Multi-style Interpolation/style_network.py":41-45,137-138,354-356)
-// (blend_states_k: blockIdx.y = image of a grouped multi-style launch, its weights w[image][style], its state set out + image * count)
-struct BlendManyP { const float* st[8]; float w[16][8]; int n; float* out; int count; };
-struct BlendP { const float* st[8]; float w[8]; int n; float* out; int count; };
-__global__ void blend_states_k(const BlendManyP p) {
+// blend_sets_k: blockIdx.y = image of a launch sequence, its weights w[image][style], its state set out + image * count.  The weights
+// travel in the kernel argument (w: host weights, up to sixteen images) or are read from device memory (w_dev != nullptr: n floats
+// per image, written by a GPU producer).  One sum in one order, float32: the same weights give the same bits from either source.
+struct BlendSetsP { const float* st[8]; float w[16][8]; const float* w_dev; int n; float* out; int count; };
+__global__ void blend_sets_k(const BlendSetsP p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (i < p.count) {
-        float s = 0.f;
-        for (int k = 0; k < p.n; ++k) s += p.w[b][k] * p.st[k][i];      // the same sum, in the same order, as blend_state_k
-        p.out[(size_t)b * p.count + i] = s;
-    }
-}
-// the same with the weights in device memory (w[image][style], n floats per image): what the blended frame entries run, for
-// weights a GPU producer wrote as for host weights staged there.  Same sum, same order: the same float32 weights give the same bits.
-struct BlendDevP { const float* st[8]; const float* w; int n; float* out; int count; };
-__global__ void blend_states_dev_k(const BlendDevP p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (i < p.count) {
-        const float* __restrict__ w = p.w + (size_t)b * p.n;
-        float s = 0.f;
+    if (i >= p.count) return;
+    float s = 0.f;
+    if (p.w_dev) {      // (uniform)
+        const float* __restrict__ w = p.w_dev + (size_t)b * p.n;
         for (int k = 0; k < p.n; ++k) s += w[k] * p.st[k][i];
-        p.out[(size_t)b * p.count + i] = s;
+    } else {
+        for (int k = 0; k < p.n; ++k) s += p.w[b][k] * p.st[k][i];
     }
-}
-__global__ void blend_state_k(const BlendP p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < p.count) {
-        float s = 0.f;
-        for (int k = 0; k < p.n; ++k) s += p.w[k] * p.st[k][i];
-        p.out[i] = s;
-    }
+    p.out[(size_t)b * p.count + i] = s;
 }

@@ -200,10 +200,11 @@ struct rrv_ctx {
     float* fc_w[6] = {nullptr}; float* fc_b[6] = {nullptr};
     float* zero_bias = nullptr;                // 512 zeros
     // The state the per-frame path reads (blob layout) and the KernelFilter weights folded with its dynamic filters.
-    // Set 0 serves every single-state entry; the batched multi-style entry gives each in-flight frame (slot) its own set,
-    // since every frame there has its own blended state.  `cur` = the set the launch helpers use right now.
-    // The sets live in CONTIGUOUS arrays (set i = base + i * stride): a launch whose images carry their own blended state
-    // (rrv_transfer_features_batch) passes the first set and the strides, the kernels index by image.
+    // Set 0 serves every single-state entry; the grouped models (frame mode, blended frames and cached features: run_xfer) give image g
+    // of a launch sequence on slot 0 / 1 the set MS_GROUP_MAX * slot + g, since every image there has its own state (blend_sets writes
+    // the blended ones).  `cur` = the set the launch helpers use right now.
+    // The sets live in CONTIGUOUS arrays (set i = base + i * stride): a launch whose images carry their own state
+    // passes the first set and the strides, the kernels index by image.
     static constexpr int MS_GROUP_MAX = 16;      // multi-style frames per launch sequence (each with its own blended state set)
     static constexpr int N_SETS = 2 * MS_GROUP_MAX;      // two groups in flight.  9.9 MB per set (state blob + three KernelFilters' folded raw and packed weights), 316 MB of the 288 GB per handle, allocated once by rrv_finalize_weights
     struct StateSet { float* active = nullptr; ConvW fold_down[3], fold_up[3]; } sets[N_SETS];
@@ -228,8 +229,7 @@ struct rrv_ctx {
     size_t feat_cap = (size_t)64 << 30, feat_bytes = 0;
     std::vector<float*> patches;               // relu4_1 features of added frames (ring layout images)
     int patch_h = 0, patch_w = 0, add_H = 0, add_W = 0;
-    uint8_t* d_u8 = nullptr; size_t d_u8_cap = 0;
-    float* d_outf = nullptr; size_t d_outf_cap = 0;
+    uint8_t* d_u8 = nullptr; size_t d_u8_cap = 0;      // a style image / a frame to cache on its way in (prepare_style, rrv_generate_content_features)
     // fixed-size scratch, one allocation made by rrv_finalize_weights: chan_stats partials and means; streaming compute(): second
     // partial buffer, two running accumulators [4][512] doubles; compute(): the predicted content means
     double *stat_part = nullptr, *stat_part2 = nullptr, *stat_acc = nullptr;
@@ -241,11 +241,6 @@ struct rrv_ctx {
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
     InFmt pend_in = IN_BGR8;          // format of the pending frames (a frame is kept as it arrived; conv_first_k<IN> reads it)
-    // Weights of the blended frame entries (run_xfer, Model::BLEND), per slot 0 / 1: [64][RRV_MAX_STYLES] floats in HBM, which blend_states_dev_k
-    // reads, and for host weights a page-locked ring of BLEND_W_RING such blocks: a call fills the next block and copies it on the slot's
-    // stream; a block is reused BLEND_W_RING calls later, after its copy's event (long past: no host wait in a running pipeline)
-    static constexpr int BLEND_W_RING = 4, BLEND_W_FLOATS = 64 * RRV_MAX_STYLES;
-    struct BlendW { float* dev = nullptr; float* pin = nullptr; hipEvent_t ev[BLEND_W_RING] = {nullptr}; bool used[BLEND_W_RING] = {false}; unsigned gen = 0; } blend_w[2];
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -901,6 +896,23 @@ int fold_filters(rrv_handle h, const float* blob, int f /*0..2*/, int nsets = 1)
     return RRV_OK;
 }
 
+// The blend step of every blended entry: state sets h->cur, h->cur + 1, .. of images 0..cnt-1 := sum_s w[image][s] x the computed state of
+// style s (blend_sets_k), their three KernelFilters folded; the sets then hold a blend (active_src -2).  w: [cnt][ns] host weights, read
+// before this returns (they travel in the kernel argument); w_dev: the same array in HBM, read by the kernel on h->stream.
+int blend_sets(rrv_handle h, const float* w, bool w_dev, int ns, int cnt) {
+    static_assert(rrv_ctx::MS_GROUP_MAX <= 16, "BlendSetsP::w holds sixteen images");
+    BlendSetsP bp{};
+    bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
+    for (int s = 0; s < ns; ++s) bp.st[s] = h->styles[s].blob;
+    if (w_dev) bp.w_dev = w;
+    else for (int g = 0; g < cnt; ++g) memcpy(bp.w[g], w + (size_t)g * ns, sizeof(float) * ns);
+    hipLaunchKernelGGL(blend_sets_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
+    HIPCHK(hipGetLastError());
+    h->active_src = -2;
+    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
+    return RRV_OK;
+}
+
 // Conditioning of a style's saved state, read off its six dynamic 32 x 32 filters (FilterPredictor outputs): every state seen
 // so far with seeded or real inputs has filters of Frobenius norm 5.5 .. 5.8 (~ sqrt 32: near-orthogonal), while the weight set
 // built to be ill-conditioned in float32 (every decoder weight x 4; the reference's own float32 run misses its float64 run by
@@ -1083,7 +1095,6 @@ constexpr bool yuv16_layout(int layout) { return layout == RRV_LAY_I420_16 || la
 inline size_t yuv_sample_bytes(OutFmt f) { return yuv16_layout(f.yuv) ? sizeof(uint16_t) : 1; }
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
-inline size_t out_floats(size_t elems, OutFmt f) { return (elems * out_elem(f) + 3) / 4; }     // h->d_outf floats that hold `elems` outputs
 // How one launch sequence reads and writes its frames: both formats and, for the pad geometry, the source window (nullptr: plain frames)
 struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; };
 
@@ -1108,6 +1119,7 @@ struct Xfer {
     int mask_images = 0;
     bool w_dev = false;             // BLEND: wts is in HBM, written by work the slot's stream is ordered behind
     InFmt in = IN_BGR8;             // format of the content frames (the descriptor and _from_yuv entries set it)
+    const float* const* feats = nullptr;      // BLEND: one cached relu4_1 feature per image in place of the frames (d_in may then be null)
 
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
@@ -1128,7 +1140,7 @@ struct SetScope {
     ~SetScope() { h->stream = h->streams[0]; h->cur = &h->sets[0]; h->state_images = 0; h->active_src = src; }
 };
 
-// grow-only device buffer of at least n elements (h->d_u8, h->d_outf); empty after a failed allocation
+// grow-only device buffer of at least n elements (h->d_u8, a staging set's masks); empty after a failed allocation
 template <class T>
 int ensure_dev(rrv_handle h, T*& p, size_t& cap, size_t n) {
     if (cap >= n) return RRV_OK;
@@ -1328,11 +1340,11 @@ struct SeqHook {
     int piece = 0; char* h_dst = nullptr; size_t frame_bytes = 0; hipStream_t copy = nullptr; hipEvent_t* ev = nullptr;
 };
 
-// feat != nullptr: skip the encoder and start from a cached raw relu4_1 feature (ring layout, [1,H/8,W/8,512])
-// feats != nullptr (with h->state_images == B): one cached feature per image, each normalised with ITS state set
+// feats != nullptr: skip the encoder and start from one cached raw relu4_1 feature per image (ring layout, [1,H/8,W/8,512])
+// h->state_images: 0 = every image uses the current state set, B = image b uses set cur + b (frames and cached features alike)
 // slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
-int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* feat = nullptr,
-                    const float* const* feats = nullptr, const SeqHook* hk = nullptr) {
+int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* const* feats = nullptr,
+                    const SeqHook* hk = nullptr) {
     const PadCrop* const pc = io.pc;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     // Any frame size, as the reference: the three 2x2 max pools floor (H, W) to (H/8, W/8) and the decoder returns
@@ -1355,23 +1367,19 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     RCHK(dec_plan(h, d, B, Ho, Wo));
     e.gen = d.gen = ++h->launch_gen;
     const float* st = h->cur->active;
-    if (feats) {  // one cached feature and one state set per image
-        if (h->state_images != B) return fail(h, RRV_E_ARG, "transfer: per-image features need per-image state");
+    // per-image state: every image's relu4_1 is normalised with ITS set's Decoder.norm[0] entry
+    if (h->state_images ? h->state_images != B : (feats && B != 1)) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per image");
+    const long stride = h->state_images ? (long)RRV_STATE_FLOATS : 0;
+    if (feats) {  // cached raw relu4_1 features: Decoder.norm[0] (saved stats + clamp) as a pointwise step per image
         for (int b = 0; b < B; ++b) {
             Tens src; src.p = const_cast<float*>(feats[b]); src.B = 1; src.H = H / 8; src.W = W / 8; src.C = 512;
             Tens dst = e.c41; dst.B = 1; dst.p = e.c41.p + (size_t)b * e.c41.img_floats();
-            const float* n0 = st + (size_t)b * RRV_STATE_FLOATS + SL.norm[N_DEC0];
+            const float* n0 = st + (size_t)b * stride + SL.norm[N_DEC0];
             RCHK(pointwise(h, src, dst, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
         }
-        stamp(h, &e.c41, B);
-    } else if (feat) {   // cached raw relu4_1 feature: Decoder.norm[0] (saved stats + clamp) as a pointwise step
-        Tens src; src.p = const_cast<float*>(feat); src.B = 1; src.H = H / 8; src.W = W / 8; src.C = 512;
-        const float* n0 = st + SL.norm[N_DEC0];
-        RCHK(pointwise(h, src, e.c41, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
+        stamp(h, &e.c41, B);      // (pointwise stamped the one-image views: the debug taps see the tensor as written)
     } else {
-        // per-image state: every frame's relu4_1 is normalised with ITS set's Decoder.norm[0] entry, as the cached-feature branch above does
-        if (h->state_images && h->state_images != B) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per frame");
-        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, h->state_images ? (int)RRV_STATE_FLOATS : 0));
+        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, (int)stride));
     }
     const Tens* cur = &e.c41;
     for (int f = 0; f < 3; ++f) {
@@ -2066,13 +2074,7 @@ int rrv_destroy(rrv_handle h) {
     free_plans(h);
     for (StyleState& s : h->styles) { if (s.blob) (void)hipFree(s.blob); if (s.smean) (void)hipFree(s.smean); tfree(&s.map); }
     if (h->d_u8) (void)hipFree(h->d_u8);
-    if (h->d_outf) (void)hipFree(h->d_outf);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
-    for (auto& bw : h->blend_w) {
-        if (bw.dev) (void)hipFree(bw.dev);
-        if (bw.pin) (void)hipHostFree(bw.pin);
-        for (hipEvent_t e : bw.ev) if (e) (void)hipEventDestroy(e);
-    }
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
     for (auto& st : h->hstage) {
@@ -2575,8 +2577,8 @@ static int next_device_slot(rrv_handle h) {
 }
 
 // Every argument and state check of a transfer, once per API call, before anything is staged or launched.  host: the pipeline cuts
-// sub-batches itself, so any B >= 1 is served; the device and image entries take 1..64 frames.
-static int check_xfer(rrv_handle h, const Xfer& x, bool host = false) {
+// sub-batches itself, so any B >= 1 is served; the device and image entries take 1..64 frames.  state_first: see below.
+static int check_xfer(rrv_handle h, const Xfer& x, bool host = false, bool state_first = false) {
     const bool blend = x.model == Model::BLEND, mask = x.model == Model::MASK;
     if (x.B < 1 || (!host && x.B > 64)) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
     if (x.pad && (x.H < 1 || x.W < 1)) return fail(h, RRV_E_ARG, "transfer: frames must be at least 1 x 1 pixels");
@@ -2585,9 +2587,9 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false) {
     if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
     if (mask && !x.mask) return fail(h, RRV_E_ARG, "transfer: null mask");
     if (mask && x.mask_images != 1 && x.mask_images != x.B) return fail(h, RRV_E_ARG, "transfer: mask_images must be 1 or B");
-    // A handle without weights has no state either.  Every entry reports the weights, except rrv_transfer_mask_batch, which has
-    // always answered RRV_E_STATE: kept as it is.
-    if (!h->finalized && !(mask && host)) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    // A handle without weights has no state either.  Every entry reports the weights, except rrv_transfer_mask_batch and the one-frame
+    // blended entries (rrv_transfer_blend[_device][_u8]: state_first), which have always answered RRV_E_STATE: kept as it is.
+    if (!h->finalized && !(mask && host) && !state_first) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     if (x.model == Model::FRAME && !h->styles[0].prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
     for (int s = 0; s < x.ns; ++s)
         if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "transfer: state not computed for every style");
@@ -2600,38 +2602,13 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false) {
     return RRV_OK;
 }
 
-// n <= BLEND_W_FLOATS host weights -> the slot's device block (allocated on first use), by a copy on the slot's stream from the next block of its page-locked ring
-static int stage_blend_weights(rrv_handle h, int slot, const float* wts, size_t n, const float** d_w) {
-    rrv_ctx::BlendW& bw = h->blend_w[slot];
-    if (!bw.dev) RCHK(dalloc(h, &bw.dev, rrv_ctx::BLEND_W_FLOATS, false));
-    if (!bw.pin) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(float) * rrv_ctx::BLEND_W_RING * rrv_ctx::BLEND_W_FLOATS, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, RRV_E_NOMEM, "blend weights: out of page-locked host memory");
-        }
-        bw.pin = (float*)p;
-    }
-    for (hipEvent_t& e : bw.ev)
-        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const int g = (int)(bw.gen++ % rrv_ctx::BLEND_W_RING);
-    if (bw.used[g]) HIPCHK(hipEventSynchronize(bw.ev[g]));
-    float* const blk = bw.pin + (size_t)g * rrv_ctx::BLEND_W_FLOATS;
-    memcpy(blk, wts, n * sizeof(float));
-    HIPCHK(hipMemcpyAsync(bw.dev, blk, n * sizeof(float), hipMemcpyHostToDevice, h->streams[slot]));
-    HIPCHK(hipEventRecord(bw.ev[g], h->streams[slot]));
-    bw.used[g] = true;
-    *d_w = bw.dev;
-    return RRV_OK;
-}
-
-
 // Runs a checked request from d_in to d_out on `slot` (the grouped models: 0 or 1, the slots that own sixteen state sets each).
 // GLOBAL is one launch sequence for all B frames; the others walk launch sequences of up to MS_GROUP_MAX frames:
 //   FRAME  frame_mode_device: every frame with its own statistics, written to the slot's state sets
-//   BLEND  the group's state sets := sum_s w[b][s] x state_s (blend_states_dev_k), their KernelFilters folded, then encoder AND decoder
-//          with per-image state (transfer_device, state_images).  With a fixed kernel mode a frame's arithmetic is that of
-//          rrv_transfer_blend on the frame alone, bit for bit.
+//   BLEND  the group's state sets := sum_s w[b][s] x state_s with their KernelFilters folded (blend_sets: host weights in the kernel
+//          argument, a group's rows at a time; only w_dev weights are read from HBM), then encoder AND decoder with per-image state
+//          (transfer_device, state_images) -- or, with x.feats, the decoder alone on the group's cached features.  One frame is a group
+//          of one on the shared-state kernels: with a fixed kernel mode a frame's arithmetic does not depend on its group, bit for bit.
 //   MASK   mask_mode_device; it touches no state set
 // hk (host_pipeline, a request of one launch sequence): handed to transfer_device
 static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const Xfer& x, const SeqHook* hk = nullptr) {
@@ -2650,8 +2627,6 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
         HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
     }
-    const float* d_w = x.wts;
-    if (x.model == Model::BLEND && !x.w_dev) RCHK(stage_blend_weights(h, slot, x.wts, (size_t)x.B * x.ns, &d_w));
     const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
     const size_t fb = x.in_bytes(), fo = x.out_bytes();
     const PadCrop crop = x.pad_crop();
@@ -2662,7 +2637,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
         void* const out = (char*)d_out + (size_t)b0 * fo;
         switch (x.model) {
         case Model::GLOBAL:
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, nullptr, hk));
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, hk));
             break;
         case Model::FRAME:
             RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, io));
@@ -2675,15 +2650,9 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             SetScope scope{h, -2};
             h->stream = h->streams[slot];
             h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
-            BlendDevP bp{};
-            bp.n = x.ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS; bp.w = d_w + (size_t)b0 * x.ns;
-            for (int s = 0; s < x.ns; ++s) bp.st[s] = h->styles[s].blob;
-            hipLaunchKernelGGL(blend_states_dev_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
-            HIPCHK(hipGetLastError());
-            h->active_src = -2;
-            for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
+            RCHK(blend_sets(h, x.wts + (size_t)b0 * x.ns, x.w_dev, x.ns, cnt));
             h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, nullptr, hk));      // (a host sub-batch is one group: the hook's sequence)
+            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, x.feats ? x.feats + b0 : nullptr, hk));      // (a host sub-batch is one group: the hook's sequence)
             h->set_images[slot] = cnt;
             break;
         }
@@ -2812,58 +2781,21 @@ int rrv_transfer_image_mask_device(rrv_handle h, const void* d_in, rrv_image_des
     return image_entry(h, d_in, in, d_out, out, flags, hip_stream, Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, n_styles, /* wts */ nullptr, d_mask, mask_images});
 }
 
-// the current state set := sum_s wts[s] x the computed state of style s, with its three KernelFilters folded
-static int blend_into_current(rrv_handle h, const float* wts, int ns) {
-    BlendP bp{};
-    bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
-    for (int s = 0; s < ns; ++s) {
-        if (!h->styles[s].computed) return fail(h, RRV_E_STATE, "blend: state not computed for every style");
-        bp.st[s] = h->styles[s].blob; bp.w[s] = wts[s];
-    }
-    hipLaunchKernelGGL(blend_state_k, dim3((RRV_STATE_FLOATS + 255) / 256), dim3(256), 0, h->stream, bp);
-    HIPCHK(hipGetLastError());
-    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f));
-    h->active_src = -2;
-    return RRV_OK;
-}
-
-// The serialised entries (one shared state set) run on slot 0; the next alternating call starts there.
-static int blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out, OutFmt fmt) {
-    if (!h || !d_in || !d_out || !wts || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
+// The one-frame blended device entries are serialised (one call at a time, on slot 0 and its state set 0); the next alternating
+// call starts there.  A group of one frame of run_xfer.
+static int serial_blend_entry(rrv_handle h, const void* d_in, void* d_out, const Xfer& x) {
+    if (!h || !d_in || !d_out) return RRV_E_ARG;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     h->next_slot = 0;
-    RCHK(blend_into_current(h, wts, ns));
-    return transfer_device(h, 0, (const uint8_t*)d_in, 1, H, W, d_out, FrameIO{IN_BGR8, fmt});
+    RCHK(check_xfer(h, x, false, true));
+    return run_xfer(h, 0, d_in, d_out, x);
 }
 int rrv_transfer_blend_device(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
-    return blend_device(h, d_in, H, W, wts, ns, d_out, OUT_F32);
+    return serial_blend_entry(h, d_in, d_out, Xfer{Model::BLEND, 1, H, W, PLAIN, OUT_F32, ns, wts});
 }
 int rrv_transfer_blend_device_u8(rrv_handle h, const void* d_in, int H, int W, const float* wts, int ns, void* d_out) {
-    return blend_device(h, d_in, H, W, wts, ns, d_out, OUT_U8);
-}
-
-// host-buffer form: H2D, the device entry, D2H
-static int blend_host(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, void* out, OutFmt fmt) {
-    if (!h || !frame || !out || !wts) return RRV_E_ARG;
-    RCHK(check_frame(h, H, W, "transfer"));
-    HIPCHK(hipSetDevice(h->dev));
-    const size_t n = (size_t)H * W * 3;                                  // input bytes
-    const size_t no = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;             // output elements: the stylized frame is 8*(H/8) x 8*(W/8)
-    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, n));
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(no, fmt)));
-    RCHK(sync_all(h));
-    HIPCHK(hipMemcpyAsync(h->d_u8, frame, n, hipMemcpyHostToDevice, h->streams[0]));
-    RCHK(blend_device(h, h->d_u8, H, W, wts, ns, h->d_outf, fmt));
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, no * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
-    HIPCHK(hipStreamSynchronize(h->streams[0]));
-    return RRV_OK;
-}
-int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
-    return blend_host(h, frame, H, W, wts, ns, out, OUT_F32);
-}
-int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, uint8_t* out) {
-    return blend_host(h, frame, H, W, wts, ns, out, OUT_U8);
+    return serial_blend_entry(h, d_in, d_out, Xfer{Model::BLEND, 1, H, W, PLAIN, OUT_U8, ns, wts});
 }
 
 // B frames in sub-batches of up to 8 through four staging sets.  Three engines run concurrently: the H2D copy of
@@ -3007,12 +2939,12 @@ static int claim_staging(rrv_handle h) {
 }
 // The host entries: x.B frames from `frames` to `out` (float32, uint8 or 8-bit YUV 4:2:0 by x.fmt, x.out_bytes() per frame), any B >= 1.  The grouped models run sub-batches of at
 // most MS_GROUP_MAX frames, one launch sequence each; the blended one takes the sub-batch's rows of x.wts, the masked one the set's
-// staged mask block.
-static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const Xfer& x) {
+// staged mask block.  state_first: check_xfer's.
+static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const Xfer& x, bool state_first = false) {
     if (!h || !frames || !out) return RRV_E_ARG;
     const auto t_entry = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(h->dev));
-    RCHK(check_xfer(h, x, true));
+    RCHK(check_xfer(h, x, true, state_first));
     const int B = x.B;
     const float* const mask = x.mask;
     const int mask_images = x.mask_images;
@@ -3153,6 +3085,20 @@ int rrv_transfer(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
 }
 int rrv_transfer_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
     return host_pipeline(h, frame, out, Xfer{Model::GLOBAL, 1, H, W, PLAIN, OUT_U8});
+}
+
+// one frame with one blended state, one frame of the frame mode: a request of one sub-batch (no event, one stream, slot 0 and its state set 0)
+int rrv_transfer_blend(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, float* out) {
+    return host_pipeline(h, frame, out, Xfer{Model::BLEND, 1, H, W, PLAIN, OUT_F32, ns, wts}, true);
+}
+int rrv_transfer_blend_u8(rrv_handle h, const uint8_t* frame, int H, int W, const float* wts, int ns, uint8_t* out) {
+    return host_pipeline(h, frame, out, Xfer{Model::BLEND, 1, H, W, PLAIN, OUT_U8, ns, wts}, true);
+}
+int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
+    return host_pipeline(h, frame, out, Xfer{Model::FRAME, 1, H, W, PLAIN, OUT_F32});
+}
+int rrv_transfer_frame_mode_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
+    return host_pipeline(h, frame, out, Xfer{Model::FRAME, 1, H, W, PLAIN, OUT_U8});
 }
 
 int rrv_transfer_batch(rrv_handle h, const uint8_t* frames, int B, int H, int W, float* out) {
@@ -3567,33 +3513,11 @@ int rrv_add_patch(rrv_handle h, int feature_id) {
     return RRV_OK;
 }
 
-static int transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, void* out, OutFmt fmt) {
-    if (!h || !wts || !out || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
-    if (feature_id < 0 || feature_id >= (int)h->features.size() || !(h->features[feature_id].p || h->features[feature_id].u8)) return RRV_E_ARG;
-    HIPCHK(hipSetDevice(h->dev));
-    RCHK(sync_all(h));
-    h->next_slot = 0;
-    const rrv_ctx::Feature& ft = h->features[feature_id];
-    RCHK(blend_into_current(h, wts, ns));
-    const size_t n = (size_t)(ft.H / 8 * 8) * (ft.W / 8 * 8) * 3;
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
-    RCHK(transfer_device(h, 0, ft.u8, 1, ft.H, ft.W, h->d_outf, FrameIO{IN_BGR8, fmt}, ft.p));      // a spilled feature (p == nullptr) is re-encoded from its pixels
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
-    HIPCHK(hipStreamSynchronize(h->streams[0]));
-    return RRV_OK;
-}
-int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, float* out) {
-    return transfer_features(h, feature_id, wts, ns, out, OUT_F32);
-}
-int rrv_transfer_features_u8(rrv_handle h, int feature_id, const float* wts, int ns, uint8_t* out) {
-    return transfer_features(h, feature_id, wts, ns, out, OUT_U8);
-}
-
 // n cached features, one weight vector each ([n][ns]), in ONE call.  Frames run in GROUPS of up to sixteen per launch
 // sequence — every image of a launch carries its own blended state set (per-image parameters and folded KernelFilter
 // weights, ConvP::par_bstride / w_bstride), so the small relu4_1-level layers see G x the pixel tiles of one frame —
 // and consecutive groups alternate over two (stream, workspace, sixteen state sets): group k+1's blends, folds and
-// decoder overlap group k's D2H copy.  With a fixed kernel mode a frame's arithmetic does not depend on its group
+// decoder overlap group k's D2H copy.  A group is one BLEND request of run_xfer over its cached features; rrv_transfer_features is n = 1.  With a fixed kernel mode a frame's arithmetic does not depend on its group
 // (bit-identical to one frame per call); the default mode chooses the kernels by the group's frames.  Features beyond the cache cap (kept as pixels) run alone through the encoder + decoder entry.
 static int transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, void* out, OutFmt fmt) {
     if (!h || !ids || !wts || !out || n < 1 || ns < 1 || ns > RRV_MAX_STYLES) return RRV_E_ARG;
@@ -3608,7 +3532,6 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         if (h->features[ids[i]].H != H || h->features[ids[i]].W != W) return fail(h, RRV_E_ARG, "transfer: features of one call must share their size");
     RCHK(claim_staging(h));
     const size_t npx = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3 * out_elem(fmt);      // output bytes per frame
-    const FrameIO io{IN_BGR8, fmt};      // (a spilled feature is re-encoded from its uint8 BGR pixels)
     char* const outc = (char*)out;
     const bool out_pin = is_pinned(out, (size_t)n * npx);
     // Frames per launch sequence (rrv_set_multistyle_group; default: the host entries' ~6.6 Mpixel per launch — 4 at 1152 x 1152,
@@ -3635,7 +3558,6 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         RCHK(stage_reserve(h, i, 0, (size_t)G * npx, false));
         RCHK(stage_reserve(h, i, 0, out_pin ? 0 : (size_t)G * npx, true));
     }
-    SetScope scope{h, -2};
     const bool tl_on = h->tl.on && ngroups > 1 && ngroups <= rrv_ctx::Timeline::N;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
@@ -3652,36 +3574,13 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
             if (!out_pin) RCHK(drain(k - nslots));
             HIPCHK(hipStreamWaitEvent(h->streams[slot], st.out_done, 0));      // this slot's device output has left
         }
-        h->stream = h->streams[slot];
         const float* fp[rrv_ctx::MS_GROUP_MAX] = {};
-        h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
-        {   // the group's blends and folds: one launch per step for all its images (same sums as the one-image kernels)
-            static_assert(rrv_ctx::MS_GROUP_MAX <= 16, "BlendManyP::w holds sixteen images");
-            BlendManyP bp{};
-            bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
-            for (int s = 0; s < ns; ++s) bp.st[s] = h->styles[s].blob;
-            for (int g = 0; g < cnt; ++g) {
-                for (int s = 0; s < ns; ++s) bp.w[g][s] = wts[(size_t)(first + g) * ns + s];
-                fp[g] = h->features[ids[first + g]].p;
-            }
-            hipLaunchKernelGGL(blend_states_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
-            HIPCHK(hipGetLastError());
-            for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
-        }
-        h->active_src = -2;
+        for (int g = 0; g < cnt; ++g) fp[g] = h->features[ids[first + g]].p;
         void* const h_dst = out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out;
-        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, h->streams[slot]));
-        if (fp[0] && cnt == 1) {       // one frame per launch: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, nullptr, 1, H, W, st.dev.out, io, fp[0]));
-        } else if (fp[0]) {
-            h->state_images = cnt;
-            const int rc = transfer_device(h, slot, nullptr, cnt, H, W, st.dev.out, io, nullptr, fp);
-            h->state_images = 0;
-            RCHK(rc);
-        } else {
-            RCHK(transfer_device(h, slot, h->features[ids[first]].u8, 1, H, W, st.dev.out, io));      // re-encode the pixels
-        }
-        h->set_images[slot] = cnt;
+        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, h->streams[slot]));      // (a diagnostic: in front of the first group's blend, which is part of its request)
+        Xfer part{Model::BLEND, cnt, H, W, PLAIN, fmt, ns, wts + (size_t)first * ns};
+        if (fp[0]) part.feats = fp;
+        RCHK(run_xfer(h, slot, fp[0] ? nullptr : h->features[ids[first]].u8, st.dev.out, part));      // a spilled feature is re-encoded from its uint8 BGR pixels
         if (tl_on) HIPCHK(hipEventRecord(h->tl.k_end[k], h->streams[slot]));
         HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
@@ -3693,6 +3592,12 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
     else for (int k = (ngroups - nslots < 0 ? 0 : ngroups - nslots); k < ngroups; ++k) RCHK(drain(k));
     if (tl_on) RCHK(timeline_print(h, "transfer_features_batch", n, H, W, ngroups, tl_setup, host_ms_since(t_entry)));
     return RRV_OK;
+}
+int rrv_transfer_features(rrv_handle h, int feature_id, const float* wts, int ns, float* out) {
+    return transfer_features_batch(h, &feature_id, wts, 1, ns, out, OUT_F32);
+}
+int rrv_transfer_features_u8(rrv_handle h, int feature_id, const float* wts, int ns, uint8_t* out) {
+    return transfer_features_batch(h, &feature_id, wts, 1, ns, out, OUT_U8);
 }
 int rrv_transfer_features_batch(rrv_handle h, const int* ids, const float* wts, int n, int ns, float* out) {
     return transfer_features_batch(h, ids, wts, n, ns, out, OUT_F32);
@@ -3711,34 +3616,6 @@ int rrv_release_features(rrv_handle h) {
     h->features.clear();
     h->feat_bytes = 0;
     return RRV_OK;
-}
-
-// Stylization(use_Global=False).transfer (test/framework.py:106-118 with test/style_network_frame.py):
-// per-frame InstanceNorm statistics and per-frame filter prediction.  One frame of frame_mode_device's batch, through
-// blocking pageable copies.
-static int transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, void* out, OutFmt fmt) {
-    if (!h || !frame || !out) return RRV_E_ARG;
-    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
-    RCHK(check_frame(h, H, W, "transfer"));
-    HIPCHK(hipSetDevice(h->dev));
-    StyleState& S = h->styles[0];
-    if (!S.prepared) return fail(h, RRV_E_STATE, "prepare_style has not been called");
-    RCHK(sync_all(h));
-    const size_t nin = (size_t)H * W * 3;
-    const size_t n = (size_t)(H / 8 * 8) * (W / 8 * 8) * 3;       // the stylized frame is 8*(H/8) x 8*(W/8)
-    RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, nin));
-    HIPCHK(hipMemcpyAsync(h->d_u8, frame, nin, hipMemcpyHostToDevice, h->stream));
-    RCHK(ensure_dev(h, h->d_outf, h->d_outf_cap, out_floats(n, fmt)));
-    RCHK(frame_mode_device(h, 0, h->d_u8, 1, H, W, h->d_outf, FrameIO{IN_BGR8, fmt}));
-    HIPCHK(hipMemcpyAsync(out, h->d_outf, n * out_elem(fmt), hipMemcpyDeviceToHost, h->streams[0]));
-    HIPCHK(hipStreamSynchronize(h->streams[0]));
-    return RRV_OK;
-}
-int rrv_transfer_frame_mode(rrv_handle h, const uint8_t* frame, int H, int W, float* out) {
-    return transfer_frame_mode(h, frame, H, W, out, OUT_F32);
-}
-int rrv_transfer_frame_mode_u8(rrv_handle h, const uint8_t* frame, int H, int W, uint8_t* out) {
-    return transfer_frame_mode(h, frame, H, W, out, OUT_U8);
 }
 
 int rrv_get_preclamp_image(rrv_handle h, float* out, int H, int W, int b) {

@@ -31,9 +31,9 @@ The normalised taps are teacher-forced on the GPU's OWN statistics, (v - mean_gp
   |gpu - ref| <= 2^-24 (K_f m_conv + K_point m_point + |ref|)
 with m_conv the convolution's magnitude carried through the later steps' scales only, and m_point the magnitude of every
 pointwise_k pass's own result carried the same way.  The families of the frame-mode path:
-  stat   the statistics kernels' and blend_states_k's own rounding.  Never visible alone at a statistic point (its input is
+  stat   the statistics kernels' and blend_sets_k's own rounding.  Never visible alone at a statistic point (its input is
          overwritten), so there the measured figure is the EXCESS (err - mean(b)) / (2^-24 |mean64|) (resp. the variance
-         form), 0 where the producer's term covers the error; blend_states_k's float32 sum against the float64 sum of the
+         form), 0 where the producer's term covers the error; blend_sets_k's float32 sum against the float64 sum of the
          styles' blobs, relative to the same sum on absolute values, is measured directly.
   point  pointwise_k.  Its input is overwritten in place, so it is never visible alone either: the measured figure is the
          WHOLE error of a normalised tap over 2^-24 m_point (an upper estimate: the convolution's rounding is in it), and the
@@ -60,7 +60,7 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "m
 # and over every case of tests/test_gpu_frame_mode_layers.py (frame mode 1 x 8 x 8 .. 16 x 136 x 200, 2 x 640 x 640, the host
 # entry's second launch sequence, one grouped multi-style launch; the convolutions stayed inside the figures above with their
 # raw epilogues: direct 30.7, f23 3.68, ups 9.02):
-#   stat     2.91 blend_states_k, image 6 of the grouped multi-style launch (a float32 sum of four rounded products: up to 4
+#   stat     2.91 blend_sets_k, image 6 of the grouped multi-style launch (a float32 sum of four rounded products: up to 4
 #                 by construction; image 0: 1.47).  The statistic points' excess over their producer's term was 0 at every
 #                 point of every image (worst: 0.30 of the bound, norm0 at 16 x 8): chan_stat1_k accumulates in float64.
 #   point    3.73 a3 at 640 x 640 (the whole error of the tap over the pointwise result's magnitude; a taps 3.6 .. 3.7, c41
@@ -565,7 +565,7 @@ def frame_checks(get, w, st, smean, fam, k=None, names=None):
 
 
 def blend_ref(blobs, wts):
-    """blend_states_k in float64: sum_s w[s] state_s and the same sum on absolute values (w as the float32 the kernel holds)."""
+    """blend_sets_k in float64: sum_s w[s] state_s and the same sum on absolute values (w as the float32 the kernel holds)."""
     wts = np.asarray(wts, np.float32).astype(np.float64)
     b = np.stack([np.asarray(x, np.float32).astype(np.float64) for x in blobs])
     return wts @ b, np.abs(wts) @ np.abs(b)

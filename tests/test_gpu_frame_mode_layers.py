@@ -161,7 +161,7 @@ def test_second_launch_sequence_of_the_host_entry(pkg, weights):
 
 def test_grouped_multistyle_launch_state_sets_and_layers(pkg, weights, oracle):
     """rrv_transfer_features_batch with per-frame style weights, one group of seven frames: the fused path with one BLENDED state
-    set per image.  Each checked image's set against the float64 sum of the styles' blobs (blend_states_k), and the stages d ..
+    set per image.  Each checked image's set against the float64 sum of the styles' blobs (blend_sets_k), and the stages d ..
     pre against their float64 references on that set."""
     V = importlib.import_module("rerevst-code_amd.video")
     styles = [pkg.synth_style(64, 64, kind="smooth", seed=7 + k) for k in range(4)]
