@@ -218,10 +218,15 @@ __device__ __forceinline__ void f43_out(const f32x2 m0, const f32x2 m1, const f3
 #define P8_COL0 4             /* stored column of pixel x = 0 */
 #endif
 template <int EPI, int LAY = 0>
-__global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
+__global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP) {
     static_assert(!(EPI & E_RES), "same-resolution residuals are not needed by the layers this kernel serves");
     constexpr bool INP8 = (LAY & 1) != 0, OUTP8 = (LAY & 2) != 0;
-    const int WP = p.Wi + 2 + (INP8 ? P8_PAD : 0);      // input pitch in pixels
+    // ConvP is read through conv_args() (conv_mfma.h): each region of the kernel — the prologue, an item's set-up, its epilogue —
+    // loads the fields it uses from kernel-argument memory when it gets there (scalar loads, free beside the vector pipe) instead
+    // of holding ~45 SGPRs of them across the K loop, where they were spilled into vector lanes and reloaded between MFMAs.
+    const ConvPK p0 = conv_args();
+    auto wp_of = [](const ConvPK k) { return k->Wi + 2 + (INP8 ? P8_PAD : 0); };      // input pitch in pixels
+    const int WP = wp_of(p0);
     using G = F43Geo;
     constexpr int ABL = F43_ABL;      // microbenchmark switches; 0 in the library
     constexpr int RAW_BYTES = G::RAW_BYTES, U_BYTES = G::U_BYTES, NT = G::NT, NPOS = G::NPOS;
@@ -230,16 +235,17 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63, t = lane & 15, q = lane >> 4;
     const int tr = t >> 3, tc = t & 7;           // the wave's 16 tiles: 2 rows x 8 columns of 4x4 outputs = 8 x 32 pixels
-    const int nchunks = p.Cin >> 3;              // 8-channel chunks; even and >= 4 (Cin a multiple of 16, >= 32)
-    const int n_ntiles = p.Cout >> 5;
+    const int nchunks = p0->Cin >> 3;              // 8-channel chunks; even and >= 4 (Cin a multiple of 16, >= 32)
 
     // ---- work items (32 x 32 output pixels x 32 couts): the same XCD-aware incremental walk as conv_wino_k
     struct Item { int tx, ty, b, nt; };
     Item cur, nxt, dlt;
     {
+        const ConvPK p = p0;
+        const int n_ntiles = p->Cout >> 5;
         const int GD = gridDim.x, w = blockIdx.x;
         int pix, dpix;
-        if (p.xcd_slabs) {
+        if (p->xcd_slabs) {
             const int PT = (GD >> 3) / n_ntiles;
             pix = (w & 7) * PT + (w >> 3) / n_ntiles; dpix = 8 * PT;
             cur.nt = (w >> 3) % n_ntiles; dlt.nt = 0;
@@ -247,36 +253,39 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
             cur.nt = w % n_ntiles; pix = w / n_ntiles;
             dlt.nt = GD % n_ntiles; dpix = GD / n_ntiles;
         }
-        cur.tx = pix % p.tiles_x; cur.ty = (pix / p.tiles_x) % p.tiles_y; cur.b = pix / (p.tiles_x * p.tiles_y);
-        dlt.tx = dpix % p.tiles_x; dlt.ty = (dpix / p.tiles_x) % p.tiles_y; dlt.b = dpix / (p.tiles_x * p.tiles_y);
+        cur.tx = pix % p->tiles_x; cur.ty = (pix / p->tiles_x) % p->tiles_y; cur.b = pix / (p->tiles_x * p->tiles_y);
+        dlt.tx = dpix % p->tiles_x; dlt.ty = (dpix / p->tiles_x) % p->tiles_y; dlt.b = dpix / (p->tiles_x * p->tiles_y);
     }
-    auto advance = [&](const Item& a) {
+    auto advance = [&](const ConvPK p, const Item& a) {
+        const int n_ntiles = p->Cout >> 5;
         Item r = a;
         r.nt += dlt.nt;
         int carry = 0;
         if (r.nt >= n_ntiles) { r.nt -= n_ntiles; carry = 1; }
         r.tx += dlt.tx + carry;
-        if (r.tx >= p.tiles_x) { r.tx -= p.tiles_x; r.ty += 1; }
+        if (r.tx >= p->tiles_x) { r.tx -= p->tiles_x; r.ty += 1; }
         r.ty += dlt.ty;
-        if (r.ty >= p.tiles_y) { r.ty -= p.tiles_y; r.b += 1; }
+        if (r.ty >= p->tiles_y) { r.ty -= p->tiles_y; r.b += 1; }
         r.b += dlt.b;
         return r;
     };
-    const size_t img_floats = (size_t)(p.Hi + 2) * WP * p.Cin;
-    auto in_of = [&](const Item& a) {      // the tile's halo origin: stored row 32 ty, stored column 32 tx (+ P8_COL0 - 1 in a P8 plane)
-        return p.in + (size_t)a.b * img_floats + (size_t)(((a.ty + p.ty0) * 32) * WP + (a.tx + p.tx0) * 32 + (INP8 ? P8_COL0 - 1 : 0)) * (INP8 ? 8 : p.Cin);
+    auto in_of = [&](const ConvPK p, const Item& a) {      // the tile's halo origin: stored row 32 ty, stored column 32 tx (+ P8_COL0 - 1 in a P8 plane)
+        const int WP = wp_of(p);
+        const size_t img_floats = (size_t)(p->Hi + 2) * WP * p->Cin;
+        return p->in + (size_t)a.b * img_floats + (size_t)(((a.ty + p->ty0) * 32) * WP + (a.tx + p->tx0) * 32 + (INP8 ? P8_COL0 - 1 : 0)) * (INP8 ? 8 : p->Cin);
     };
     // floats from one 8-channel chunk of a pixel to the next: 8 inside an NHWC pixel, one plane in P8 (added to the descriptor's
     // BASE there, so that `lim` below — the bytes to the end of the tile's own plane — bounds every chunk alike)
-    const size_t plane_floats = (size_t)(p.Hi + 2) * WP * 8;
+    const size_t plane_floats = (size_t)(p0->Hi + 2) * WP * 8;
     // bytes from the item's tile origin to the end of ITS image (ring included): LDS-DMA lanes beyond get zeros, so a
     // tile that overruns the image's last rows never sees the next image (a frame's arithmetic is the same in any batch)
-    auto lim_of = [&](const Item& a) {
-        const long rows_left = (long)(p.Hi + 2) - (long)(a.ty + p.ty0) * 32;
-        const long n = (rows_left * WP - (long)(a.tx + p.tx0) * 32 - (INP8 ? P8_COL0 - 1 : 0)) * (INP8 ? 8 : p.Cin) * 4;
+    auto lim_of = [&](const ConvPK p, const Item& a) {
+        const int WP = wp_of(p);
+        const long rows_left = (long)(p->Hi + 2) - (long)(a.ty + p->ty0) * 32;
+        const long n = (rows_left * WP - (long)(a.tx + p->tx0) * 32 - (INP8 ? P8_COL0 - 1 : 0)) * (INP8 ? 8 : p->Cin) * 4;
         return (int)(n > 0x7fffffffL ? 0x7fffffffL : n);
     };
-    auto w_of = [&](const Item& a) { return p.wpk + (size_t)a.nt * nchunks * (U_BYTES / 4); };
+    auto w_of = [&](const ConvPK p, const Item& a) { return p->wpk + (size_t)a.nt * nchunks * (U_BYTES / 4); };
     int asrc[G::RAW_IT];
 #pragma unroll
     for (int it = 0; it < G::RAW_IT; ++it) {
@@ -284,13 +293,13 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
         if (e >= G::RAW_PIECES) e = 0;
         const int half = e & 1, xd = (e >> 1) % 9, ph = ((e >> 1) / 9) & 3, y = (e >> 1) / 36;
         const int x = 4 * xd + ph, par = (y >> 2) & 1;
-        asrc[it] = ((y * WP + x) * (INP8 ? 8 : p.Cin) + 4 * (half ^ par)) * 4;
+        asrc[it] = ((y * WP + x) * (INP8 ? 8 : p0->Cin) + 4 * (half ^ par)) * 4;
         if (ABL & 64) asrc[it] = (it * NT + tid) * 16;      // microbench only (wrong data): the halo requests lane-linear over 40 contiguous KB instead of 32-byte pieces one pixel stride apart
     }
-    bool have = cur.b < p.B, have_nxt = false;
-    const float* in_t = in_of(cur);
-    const float* w_t = w_of(cur);
-    int lim_t = lim_of(cur);
+    bool have = cur.b < p0->B, have_nxt = false;
+    const float* in_t = in_of(p0, cur);
+    const float* w_t = w_of(p0, cur);
+    int lim_t = lim_of(p0, cur);
     const float* in_n = in_t;
     const float* w_n = w_t;
     int lim_n = lim_t;
@@ -310,15 +319,16 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     // saved statistics / style affine at n1 / n2 / sty + b * par_bstride; bias and weights are shared by the layers this kernel serves.
     auto stage_params = [&](int ntile, int img) {
         if (wave < 2) {
+            const ConvPK p = conv_args();
             const int e = tid;
             const int row = e >> 3, col = (e & 7) * 4;
-            const float* src = p.bias;
+            const float* src = p->bias;
             int off = ntile * 32 + col;
-            const int pb = img * p.par_bstride;
-            if (row >= 1 && row <= 4) { src = (EPI & E_NORM1) ? p.n1 : p.bias; off += (EPI & E_NORM1) ? (row - 1) * p.Cout + pb : 0; }
-            if (row >= 5 && row <= 8) { src = (EPI & E_NORM2) ? p.n2 : p.bias; off += (EPI & E_NORM2) ? (row - 5) * p.Cout + pb : 0; }
-            if (row >= 9) { src = (EPI & E_NORM2) ? p.sty : p.bias; off += (EPI & E_NORM2) ? (row - 9) * p.Cout + pb : 0; }
-            if (row > 10) { src = p.bias; off = ntile * 32; }
+            const int pb = img * p->par_bstride;
+            if (row >= 1 && row <= 4) { src = (EPI & E_NORM1) ? p->n1 : p->bias; off += (EPI & E_NORM1) ? (row - 1) * p->Cout + pb : 0; }
+            if (row >= 5 && row <= 8) { src = (EPI & E_NORM2) ? p->n2 : p->bias; off += (EPI & E_NORM2) ? (row - 5) * p->Cout + pb : 0; }
+            if (row >= 9) { src = (EPI & E_NORM2) ? p->sty : p->bias; off += (EPI & E_NORM2) ? (row - 9) * p->Cout + pb : 0; }
+            if (row > 10) { src = p->bias; off = ntile * 32; }
             glds16(src + off, par + wave * 1024);
         }
     };
@@ -331,7 +341,6 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     const unsigned rawB = lds0 + y0 * G::RAW_ROW_BYTES + tc * 32 + ((q ^ (2 * ((tr & 1) ^ 1))) << 3);
     const unsigned offU = lds0 + 2 * RAW_BYTES + t * 64 + ((q ^ ((0 - (t >> 2)) & 3)) << 4);      // cout row t of both blocks, channel pair q: one 16-byte slot
 
-    const unsigned lane_off = (unsigned)(((4 * (q >> 1)) * (p.W + 2) + 16 * (q & 1)) * p.Cout + 2 * t) * 4u;      // epilogue stores, see there
     // Positions whose accumulators live in AGPRs: 28 x 2 blocks x 4 = 224 of the 256; positions 28..35 sit in VGPRs, and the
     // 32 free AGPRs take what the register allocator cannot keep in VGPRs outside the K loops (v_accvgpr moves instead of
     // scratch reloads, whose s_waitcnt vmcnt(0) would serialise the LDS-DMA stream)
@@ -341,7 +350,11 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     constexpr int NAG = F43_NAG;
     f32x4 accA[NAG][2], accV[NPOS - NAG][2];
     int par_ntile = -1, par_img = -1;
-    long long tl[6] = {0, 0, 0, 0, 0, 0}, tl_t = 0;      // ABL & 16 (microbench): cycles per phase, summed over items
+    // ABL & 16 (microbench): cycles per phase, summed over items: 0 set-up, 1 MFMA runs + gaps, 3 barriers, 4 output transform + stores,
+    // 5 input transforms; 6 the item's first chunk pair as a whole, 7 its first steady pair (Cin >= 48); 8 / 9 the kernel's whole run in
+    // shader clocks (s_memtime) and in the constant 100 MHz clock (s_memrealtime): their ratio is the clock the chip held
+    long long tl[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tl_t = 0, pair_t = 0;
+    const long long run_ck = (ABL & 16) ? clock64() : 0, run_rt = (ABL & 16) ? wall_clock64() : 0;
     auto tick = [&](int k) { if (ABL & 16) { const long long n = clock64(); tl[k] += n - tl_t; tl_t = n; } };
     f32x2 v[NPOS];                // transformed patch B^T d B of the chunk in flight: V[r][k] at index k*6 + r (raw piece (dy, dx) at dx*6 + dy)
     f32x4 ur[2][6];               // U fragments of two position batches: [ring slot][r] = {block 0: channels 2q, 2q+1; block 1: the same}
@@ -382,19 +395,30 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     //   tail               : patch column 5; wait; K-loop barrier; request U batch 0 of the next chunk; the whole input
     //                         transform (144 packed ops, three independent lines in lockstep) covers that latency.
     // Every instruction of the loop is a volatile asm: the order written is the order issued.
-    auto chunk_body = [&](int c, auto par_c, auto first_c, bool last) {
+    // TAIL (compile time; the item's last two chunks are peeled out of the K loop): 0 a chunk with two more behind it, 1 the
+    // second-to-last chunk, 2 the last one — no runtime branch or select sits between the MFMAs, the next item's addresses are live in
+    // the peeled pair only, and the compiler sees the registers the last chunk leaves free (it reads no patch and runs no transform).
+    auto chunk_body = [&](int c, auto par_c, auto first_c, auto tail_c) {
         constexpr int PAR = decltype(par_c)::value;
         constexpr bool FIRST = decltype(first_c)::value;
+        constexpr int TAIL = decltype(tail_c)::value;
+        constexpr bool last = TAIL == 2;
         // chunk c requests U(c+1) -> U buffer (c+1)&1 and raw(c+2) -> raw buffer c&1; past the item's end the same
         // slots carry the NEXT item's U(0), raw(0), raw(1) (nchunks is even)
-        const bool own_u = c + 1 < nchunks, own_r = c + 2 < nchunks;
+        constexpr bool own_u = TAIL < 2, own_r = TAIL < 1;
         const rsrc_t rs_u = make_rsrc(own_u ? w_t : w_n);
-        const int rchunk = own_r ? c + 2 : c + 2 - nchunks;
+        const int rchunk = own_r ? c + 2 : TAIL - 1;
         const rsrc_t rs_r = make_rsrc(INP8 ? (own_r ? in_t : in_n) + rchunk * plane_floats : (own_r ? in_t : in_n), own_r ? lim_t : lim_n);
         const int usoff = own_u ? (c + 1) * U_BYTES : 0;
         const int rsoff = INP8 ? 0 : rchunk * 32;
-        char* const udst = smem + 2 * RAW_BYTES + (1 - PAR) * U_BYTES;
-        char* const rdst = smem + PAR * RAW_BYTES;
+        // LDS-DMA destinations = the wave's base + a literal, added where the request is issued (SALU, free beside the vector pipe).  The
+        // base passes through an empty asm once per chunk: as loop invariants the 38 sums of a chunk pair were hoisted out of the item loop
+        // and held in SGPRs across it, which is what pushed the item walk and the descriptors' bases into spill lanes.
+        int wb = wave * 1024;
+        asm volatile("" : "+s"(wb));
+        lds_char* const wdst = (lds_char*)smem + wb;
+        lds_char* const udst = wdst + 2 * RAW_BYTES + (1 - PAR) * U_BYTES;
+        lds_char* const rdst = wdst + PAR * RAW_BYTES;
         const unsigned ub = offU + PAR * U_BYTES;          // U buffer c&1
         const unsigned ubn = offU + (1 - PAR) * U_BYTES;   // U buffer (c+1)&1
         using RBt = std::integral_constant<int, (1 - PAR) * RAW_BYTES>;      // raw buffer (c+1)&1: the next chunk's patch
@@ -413,8 +437,8 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
                 constexpr int step = b * 6 + r;                  // issue order of the 36 position steps of a chunk
                 auto dma_req = [&](auto nc) {                    // request n of the chunk: 0..9 the halo, 10..18 the U block
                     constexpr int n = decltype(nc)::value;
-                    if constexpr (n < G::RAW_IT) bufld16_rs(rs_r, rdst + (n * NT + wave * 64) * 16, asrc[n], rsoff);
-                    else if constexpr (n < G::RAW_IT + G::U_IT) bufld16_rs(rs_u, udst + ((n - G::RAW_IT) * NT + wave * 64) * 16, tid * 16, usoff + (n - G::RAW_IT) * NT * 16);
+                    if constexpr (n < G::RAW_IT) bufld16_rs(rs_r, rdst + n * NT * 16, asrc[n], rsoff);
+                    else if constexpr (n < G::RAW_IT + G::U_IT) bufld16_rs(rs_u, udst + (n - G::RAW_IT) * NT * 16, tid * 16, usoff + (n - G::RAW_IT) * NT * 16);
                 };
                 {      // request n at step n * 28 / 19: the chunk's 19 requests evenly over its first 28 position steps (the CU's L2 -> LDS
                        // path sustains 13-20 B/clock and the kernel needs 76 KB per ~7 000-clock chunk: a request issued into a full
@@ -473,26 +497,44 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
     }
     if (ABL & 16) tl_t = clock64();
     while (have) {
-        const int e_y0 = (cur.ty + p.ty0) * 32, e_x0 = (cur.tx + p.tx0) * 32, e_b = cur.b, e_ntile = cur.nt;
-        nxt = advance(cur);
-        have_nxt = nxt.b < p.B;
-        in_n = have_nxt ? in_of(nxt) : in_t;
-        w_n = have_nxt ? w_of(nxt) : w_t;
-        lim_n = have_nxt ? lim_of(nxt) : lim_t;
-        if (par_ntile != e_ntile || (p.par_bstride != 0 && par_img != e_b)) {
+        if (par_ntile != cur.nt || (conv_args()->par_bstride != 0 && par_img != cur.b)) {
             __syncthreads();
-            stage_params(e_ntile, e_b);
-            par_ntile = e_ntile; par_img = e_b;
+            stage_params(cur.nt, cur.b);
+            par_ntile = cur.nt; par_img = cur.b;
         }
         tick(0);                                  // item setup
-        chunk_body(0, std::integral_constant<int, 0>{}, std::true_type{}, false);
-        chunk_body(1, std::integral_constant<int, 1>{}, std::false_type{}, false);
-        for (int c = 2; c < nchunks; c += 2) {
-            chunk_body(c, std::integral_constant<int, 0>{}, std::false_type{}, false);
-            chunk_body(c + 1, std::integral_constant<int, 1>{}, std::false_type{}, c + 2 == nchunks);
+        if (ABL & 16) pair_t = tl_t;
+        using C0 = std::integral_constant<int, 0>; using C1 = std::integral_constant<int, 1>; using C2 = std::integral_constant<int, 2>;
+        chunk_body(0, C0{}, std::true_type{}, C0{});
+        chunk_body(1, C1{}, std::false_type{}, C0{});
+        if (ABL & 16) { tl[6] += tl_t - pair_t; pair_t = tl_t; }
+        for (int c = 2; c + 2 < nchunks; c += 2) {
+            chunk_body(c, C0{}, std::false_type{}, C0{});
+            chunk_body(c + 1, C1{}, std::false_type{}, C0{});
+            if ((ABL & 16) && c == 2) tl[7] += tl_t - pair_t;
         }
+        // the next item: only the peeled last two chunks (which request its first tiles) and the loop's next turn need it
+        const int e_b = cur.b, e_ntile = cur.nt;
+        int e_y0, e_x0;
+        {
+            const ConvPK pn = conv_args();
+            e_y0 = (cur.ty + pn->ty0) * 32; e_x0 = (cur.tx + pn->tx0) * 32;
+            nxt = advance(pn, cur);
+            have_nxt = nxt.b < pn->B;
+            in_n = have_nxt ? in_of(pn, nxt) : in_t;
+            w_n = have_nxt ? w_of(pn, nxt) : w_t;
+            lim_n = have_nxt ? lim_of(pn, nxt) : lim_t;
+        }
+        chunk_body(nchunks - 2, C0{}, std::false_type{}, C1{});
+        chunk_body(nchunks - 1, C1{}, std::false_type{}, C2{});
         cur = nxt; have = have_nxt; in_t = in_n; w_t = w_n; lim_t = lim_n;
         asm volatile("s_nop 15\n\ts_nop 7");       // the last MFMAs' results before any VALU / v_accvgpr_read touches them
+        const ConvPK p = conv_args();      // the epilogue's fields: loaded here
+        // ... and its lane coordinates derived here, from a lane id the compiler cannot trace to the kernel's start: hoisted out of the
+        // item loop, the epilogue's per-lane offsets and addresses sat in VGPRs across the K loop (parked in the spare AGPRs)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int t = ln & 15, q = ln >> 4;
         auto ACC = [&](int i, int nb) -> f32x4 { return i < NAG ? accA[i][nb] : accV[i - NAG][nb]; };
         if (ABL & 32) {                           // microbench only: no epilogue at all (keeps the accumulators alive)
             f32x4 s = ACC(0, 0);
@@ -500,7 +542,7 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
             for (int i = 0; i < NPOS; ++i)
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) if (i || nb) s += ACC(i, nb);
-            if (s[0] + s[1] + s[2] + s[3] == 123.456f) p.out[tid] = s[0];
+            if (s[0] + s[1] + s[2] + s[3] == 123.456f) p->out[tid] = s[0];
             if (have) next_patch();
             continue;
         }
@@ -517,21 +559,22 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
         // Stores: wave-uniform 64-bit base (SGPRs: image, item origin, the wave's rows, pixel (i, 4e + j)) + ONE
         // loop-invariant 32-bit lane offset (the lane's first tile inside the wave's 8 x 32 pixels and its channel pair): no
         // per-store address arithmetic in vector registers (precomputed addresses would be held across the whole K loop)
+        const unsigned lane_off = (unsigned)(((4 * (q >> 1)) * (p->W + 2) + 16 * (q & 1)) * p->Cout + 2 * t) * 4u;
         constexpr bool POOL = (EPI & E_POOL) != 0;
-        const int Ho = POOL ? (p.H >> 1) : p.H, Wo = POOL ? (p.W >> 1) : p.W;
+        const int Ho = POOL ? (p->H >> 1) : p->H, Wo = POOL ? (p->W >> 1) : p->W;
         constexpr int OP = OUTP8 ? P8_PAD : 0;      // output pitch: Wo + 2 + OP pixels
-        char* const sb = OUTP8 ? (char*)(p.out + (size_t)e_b * (size_t)(Ho + 2) * (Wo + 2 + OP) * p.Cout + (size_t)e_ntile * 4 * (size_t)(Ho + 2) * (Wo + 2 + OP) * 8 +
+        char* const sb = OUTP8 ? (char*)(p->out + (size_t)e_b * (size_t)(Ho + 2) * (Wo + 2 + OP) * p->Cout + (size_t)e_ntile * 4 * (size_t)(Ho + 2) * (Wo + 2 + OP) * 8 +
                                          ((size_t)((POOL ? (e_y0 >> 1) + 4 * wave : e_y0 + 8 * wave) + 1) * (Wo + 2 + OP) + (POOL ? (e_x0 >> 1) : e_x0) + P8_COL0) * 8)
-                               : (char*)(p.out + (size_t)e_b * (size_t)(Ho + 2) * (Wo + 2) * p.Cout +
-                                 ((size_t)((POOL ? (e_y0 >> 1) + 4 * wave : e_y0 + 8 * wave) + 1) * (Wo + 2) + (POOL ? (e_x0 >> 1) : e_x0) + 1) * p.Cout + e_ntile * 32);
-        int rowb = (Wo + 2) * p.Cout * 4, pixb = p.Cout * 4;
-        unsigned st_off = POOL ? (unsigned)(((2 * mr) * (Wo + 2) + 2 * mc0) * p.Cout + 2 * t) * 4u : lane_off;
+                               : (char*)(p->out + (size_t)e_b * (size_t)(Ho + 2) * (Wo + 2) * p->Cout +
+                                 ((size_t)((POOL ? (e_y0 >> 1) + 4 * wave : e_y0 + 8 * wave) + 1) * (Wo + 2) + (POOL ? (e_x0 >> 1) : e_x0) + 1) * p->Cout + e_ntile * 32);
+        int rowb = (Wo + 2) * p->Cout * 4, pixb = p->Cout * 4;
+        unsigned st_off = POOL ? (unsigned)(((2 * mr) * (Wo + 2) + 2 * mc0) * p->Cout + 2 * t) * 4u : lane_off;
         if constexpr (OUTP8) {      // [C/8][Ho+2][Wo+2][8]: a lane's channel pair (2t, 2t+1 of the slab) is 8 bytes of the 32-byte piece of chunk 4 ntile + t/4; pixels 32 bytes apart
             const unsigned plane = (unsigned)(Ho + 2) * (Wo + 2 + OP) * 32u;
             rowb = (Wo + 2 + OP) * 32; pixb = 32;
-            st_off = (POOL ? (unsigned)((2 * mr) * (Wo + 2 + OP) + 2 * mc0) : (unsigned)((4 * (q >> 1)) * (p.W + 2 + OP) + 16 * (q & 1))) * 32u + (unsigned)(t >> 2) * plane + (unsigned)(t & 3) * 8u;
+            st_off = (POOL ? (unsigned)((2 * mr) * (Wo + 2 + OP) + 2 * mc0) : (unsigned)((4 * (q >> 1)) * (p->W + 2 + OP) + 16 * (q & 1))) * 32u + (unsigned)(t >> 2) * plane + (unsigned)(t & 3) * 8u;
         }
-        const bool interior = e_y0 + 32 <= p.H && e_x0 + 32 <= p.W;       // wave-uniform: no per-pixel masks inside the image
+        const bool interior = e_y0 + 32 <= p->H && e_x0 + 32 <= p->W;       // wave-uniform: no per-pixel masks inside the image
         // the per-channel parameters of the lane's two channels: read from LDS once per item
         const char* const pl = par + 8 * t;
         const f32x2 bias = *(const f32x2*)(pl);
@@ -545,7 +588,7 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
         // store (the counter of outstanding vector-memory operations is in order: a load behind a store waits for the store)
         f32x2 rres[4][2][2];
         if constexpr ((EPI & E_RES_UPS) != 0) {
-            const float* const res_b = p.res + (size_t)e_b * (size_t)(p.Hr + 2) * (p.Wr + 2) * p.Cout + e_ntile * 32 + 2 * t;
+            const float* const res_b = p->res + (size_t)e_b * (size_t)(p->Hr + 2) * (p->Wr + 2) * p->Cout + e_ntile * 32 + 2 * t;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -553,9 +596,9 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
 #pragma unroll
                     for (int b2 = 0; b2 < 2; ++b2) {
                         // pixels outside the image read the tensor's first pixel instead (valid memory; their outputs are never stored)
-                        const bool in = (yb + 2 * a < p.H) && (xb0 + 4 * e + 2 * b2 < p.W);
-                        const int pix = in ? (((yb >> 1) + a + 1) * (p.Wr + 2) + ((xb0 + 4 * e) >> 1) + b2 + 1) : 0;
-                        rres[e][a][b2] = *(const f32x2*)(res_b + (size_t)pix * p.Cout);
+                        const bool in = (yb + 2 * a < p->H) && (xb0 + 4 * e + 2 * b2 < p->W);
+                        const int pix = in ? (((yb >> 1) + a + 1) * (p->Wr + 2) + ((xb0 + 4 * e) >> 1) + b2 + 1) : 0;
+                        rres[e][a][b2] = *(const f32x2*)(res_b + (size_t)pix * p->Cout);
                     }
         }
         float lrk = 0.2f;
@@ -628,7 +671,7 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            if (yb + i < p.H && xb0 + 4 * e + j < p.W) *(f32x2*)(dst + i * rowb) = o[i];
+                            if (yb + i < p->H && xb0 + 4 * e + j < p->W) *(f32x2*)(dst + i * rowb) = o[i];
                     }
                 }
             }
@@ -638,8 +681,9 @@ __global__ __launch_bounds__(256, 1) void conv_f43_k(const ConvP p) {
         tick(5);
     }
     if ((ABL & 16) && lane == 0) {
+        tl[8] = clock64() - run_ck; tl[9] = wall_clock64() - run_rt;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) p.dbg[(blockIdx.x * 4 + wave) * 6 + k] = tl[k];
+        for (int k = 0; k < 10; ++k) conv_args()->dbg[(blockIdx.x * 4 + wave) * 10 + k] = tl[k];
     }
 }
 

@@ -74,6 +74,17 @@ struct ConvP {
     int out_p8;        // conv_wino_k (upsample-fused form): `out` is channel-chunk-major [B][Cout/8][H+2][W+2][8] — what conv_f43_k<.., LAY & 1> reads (conv_f43.h)
 };
 
+// The kernel's ConvP in kernel-argument memory (it is the only argument: offset 0).  The pointer comes back through an empty asm,
+// so the loads behind it belong to the place that asked: the compiler cannot merge them with loads at the kernel's start and carry
+// the values in SGPRs from there (a persistent kernel with a long K loop spills them into vector lanes, and on gfx950 every
+// v_readlane / v_writelane takes an issue slot from the MFMAs).  Constant address space: the loads are s_load_dword*.
+typedef const __attribute__((address_space(4))) ConvP* ConvPK;
+__device__ __forceinline__ ConvPK conv_args() {
+    ConvPK k = (ConvPK)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+
 template <int BN>
 struct WaveCfg {
     static constexpr int WAVES_N = (BN >= 64) ? 2 : 1;
@@ -108,6 +119,12 @@ __device__ __forceinline__ rsrc_t make_rsrc(const void* base, int num_records = 
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, num_records, 0x00020000);
 #else
     return rsrc_t{};
+#endif
+}
+typedef __attribute__((address_space(3))) char lds_char;      // LDS pointers are 32 bits: arithmetic on them is one s_add, no flat -> local cast
+__device__ __forceinline__ void bufld16_rs(rsrc_t rs, lds_char* lds_wave_base, int voff, int soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
 #endif
 }
 __device__ __forceinline__ void bufld16_rs(rsrc_t rs, char* lds_wave_base, int voff, int soff) {

@@ -87,7 +87,7 @@ static_assert(Ups5Geo::row_iter(3) < Ups5Geo::NPOS, "next chunk transformed insi
 
 // the shortcut-fused body of conv_wino_k<EPI, 0, 4, 1, 1, PERIMG>
 template <int EPI, int PERIMG>
-__device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
+__device__ __forceinline__ void conv_ups5_body() {
     static_assert(!(EPI & (E_POOL | E_RES | E_RES_UPS | E_NORM2)), "conv1 epilogues only: bias, activation, saved-stat normalise");
     using G = Ups5Geo;
     constexpr int RAW_BYTES = G::RAW_BYTES, U_BYTES = G::U_BYTES, NT = G::NT, NB = G::NB, NPOS = G::NPOS, NUB = G::NUB;
@@ -97,16 +97,19 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
     const int lane = tid & 63, t = lane & 15, q = lane >> 4;
     const int tr = t >> 3, tc = t & 7;
     const int tg = wave;                                // tile rows 2 tg, 2 tg + 1 of the workgroup's 8x8 tiles
-    const int nchunks = p.Cin >> 4;                     // even (Cin >= 64)
-    const int n_ntiles = p.Cout >> 5;
+    // ConvP through conv_args() (conv_mfma.h), region by region as in conv_f43_k: no field is held in SGPRs across the K loop
+    const ConvPK p0 = conv_args();
+    const int nchunks = p0->Cin >> 4;                   // even (Cin >= 64)
 
     // ---- work items: the walk of conv_wino_k
     struct Item { int tx, ty, b, nt; };
     Item cur, nxt, dlt;
     {
+        const ConvPK p = p0;
+        const int n_ntiles = p->Cout >> 5;
         const int GD = gridDim.x, w = blockIdx.x;
         int pix, dpix;
-        if (p.xcd_slabs) {
+        if (p->xcd_slabs) {
             const int PT = (GD >> 3) / n_ntiles;
             pix = (w & 7) * PT + (w >> 3) / n_ntiles; dpix = 8 * PT;
             cur.nt = (w >> 3) % n_ntiles; dlt.nt = 0;
@@ -114,25 +117,26 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
             cur.nt = w % n_ntiles; pix = w / n_ntiles;
             dlt.nt = GD % n_ntiles; dpix = GD / n_ntiles;
         }
-        cur.tx = pix % p.tiles_x; cur.ty = (pix / p.tiles_x) % p.tiles_y; cur.b = pix / (p.tiles_x * p.tiles_y);
-        dlt.tx = dpix % p.tiles_x; dlt.ty = (dpix / p.tiles_x) % p.tiles_y; dlt.b = dpix / (p.tiles_x * p.tiles_y);
+        cur.tx = pix % p->tiles_x; cur.ty = (pix / p->tiles_x) % p->tiles_y; cur.b = pix / (p->tiles_x * p->tiles_y);
+        dlt.tx = dpix % p->tiles_x; dlt.ty = (dpix / p->tiles_x) % p->tiles_y; dlt.b = dpix / (p->tiles_x * p->tiles_y);
     }
-    auto advance = [&](const Item& a) {
+    auto advance = [&](const ConvPK p, const Item& a) {
+        const int n_ntiles = p->Cout >> 5;
         Item r = a;
         r.nt += dlt.nt;
         int carry = 0;
         if (r.nt >= n_ntiles) { r.nt -= n_ntiles; carry = 1; }
         r.tx += dlt.tx + carry;
-        if (r.tx >= p.tiles_x) { r.tx -= p.tiles_x; r.ty += 1; }
+        if (r.tx >= p->tiles_x) { r.tx -= p->tiles_x; r.ty += 1; }
         r.ty += dlt.ty;
-        if (r.ty >= p.tiles_y) { r.ty -= p.tiles_y; r.b += 1; }
+        if (r.ty >= p->tiles_y) { r.ty -= p->tiles_y; r.b += 1; }
         r.b += dlt.b;
         return r;
     };
-    auto in_of = [&](const Item& a) {      // 16x16 low-resolution pixels per item
-        return p.in + (size_t)a.b * (size_t)(p.Hi + 2) * (p.Wi + 2) * p.Cin + (size_t)(((a.ty + p.ty0) * 16) * (p.Wi + 2) + (a.tx + p.tx0) * 16) * p.Cin;
+    auto in_of = [&](const ConvPK p, const Item& a) {      // 16x16 low-resolution pixels per item
+        return p->in + (size_t)a.b * (size_t)(p->Hi + 2) * (p->Wi + 2) * p->Cin + (size_t)(((a.ty + p->ty0) * 16) * (p->Wi + 2) + (a.tx + p->tx0) * 16) * p->Cin;
     };
-    auto w_of = [&](const Item& a) { return p.wpk + (size_t)a.nt * nchunks * (NUB * 32 * 16); };      // weights shared by the images of a launch
+    auto w_of = [&](const ConvPK p, const Item& a) { return p->wpk + (size_t)a.nt * nchunks * (NUB * 32 * 16); };      // weights shared by the images of a launch
     int asrc[G::RAW_IT];
 #pragma unroll
     for (int it = 0; it < G::RAW_IT; ++it) {     // LDS image of the 18x18 halo: even / odd column split (conv_wino_split_k)
@@ -142,12 +146,13 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
         if (P >= G::HALO * G::HALO) P = 0;
         const int hf = P >= G::HALF, rem = P - hf * G::HALF;
         const int hy = rem / 9, hx = 2 * (rem - hy * 9) + hf;
-        asrc[it] = ((hy * (p.Wi + 2) + hx) * p.Cin + 4 * (qq ^ ((hx >> 1) & 3))) * 4;
+        asrc[it] = ((hy * (p0->Wi + 2) + hx) * p0->Cin + 4 * (qq ^ ((hx >> 1) & 3))) * 4;
     }
+    const int tid16 = tid * 16;      // the U requests' lane offset; the epilogue takes its lane id from it
     const int raw_last_num = ((G::RAW_IT - 1) * NT + wave * 64 < G::PIECES) ? 0x7fffffff : 0;
-    bool have = cur.b < p.B, have_nxt = false;
-    const float* in_t = in_of(cur);
-    const float* w_t = w_of(cur);
+    bool have = cur.b < p0->B, have_nxt = false;
+    const float* in_t = in_of(p0, cur);
+    const float* w_t = w_of(p0, cur);
     const float* in_n = in_t;
     const float* w_n = w_t;
     auto stage_u = [&](int chunk) {
@@ -165,13 +170,17 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
     char* const par = smem + 2 * RAW_BYTES + 2 * U_BYTES;
     auto stage_params = [&](int ntile, int img) {
         if (wave < 2) {
+            const ConvPK p = conv_args();
             const int e = tid;
             const int row = e >> 3, col = (e & 7) * 4;
-            const float* src = p.bias;
-            const int pb = PERIMG ? img * p.par_bstride : 0;
+            int rrow = tid16;      // the row again, from a value that is live anyway and through an empty asm: (row - 1) is not precomputed and held in a VGPR across the item loop
+            asm volatile("" : "+v"(rrow));
+            rrow >>= 7;
+            const float* src = p->bias;
+            const int pb = PERIMG ? img * p->par_bstride : 0;
             int off = ntile * 32 + col;
-            if (row >= 1 && row <= 4) { src = (EPI & E_NORM1) ? p.n1 : p.bias; off = (EPI & E_NORM1) ? ntile * 32 + col + pb + (row - 1) * p.Cout : off; }
-            if (row > 4) { src = p.bias; off = ntile * 32; }
+            if (row >= 1 && row <= 4) { src = (EPI & E_NORM1) ? p->n1 : p->bias; off = (EPI & E_NORM1) ? ntile * 32 + col + pb + (rrow - 1) * p->Cout : off; }
+            if (row > 4) { src = p->bias; off = ntile * 32; }
             glds16(src + off, par + wave * 1024);
         }
     };
@@ -186,7 +195,6 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
         offD[dx] = lds0 + P * 64 + ((q ^ ((hx >> 1) & 3)) << 4);
     }
     const unsigned offU = lds0 + 2 * RAW_BYTES + t * 64 + ((q ^ ((0 - (t >> 2)) & 3)) << 4);
-    const unsigned offU1 = offU + U_BYTES;
 
     f32x4 acc[NPOS][NB];
     f32x4 va[16], vb[16];      // V of the current / next chunk: V[ry][kx] in element kx*4 + ry
@@ -198,19 +206,28 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
     auto col_pass = [&](f32x4 (&d)[16], int dx) { pass(d[dx * 4 + 0], d[dx * 4 + 1], d[dx * 4 + 2], d[dx * 4 + 3]); };
     auto row_pass = [&](f32x4 (&d)[16], int r) { pass(d[0 * 4 + r], d[1 * 4 + r], d[2 * 4 + r], d[3 * 4 + r]); };
 
-    auto chunk_body = [&](int c, auto par_c, auto first_c, f32x4 (&vcur)[16], f32x4 (&vnext)[16]) {
+    // TAIL (compile time; an item's last two chunks are peeled out of the K loop): 0 a chunk with two more behind it, 1 the second-to-last,
+    // 2 the last — whose requests carry the next item's first tiles, so the next item's addresses are live in the peeled pair only
+    auto chunk_body = [&](int c, auto par_c, auto first_c, auto tail_c, f32x4 (&vcur)[16], f32x4 (&vnext)[16]) {
         constexpr int PAR = decltype(par_c)::value;
         constexpr bool FIRST = decltype(first_c)::value;
+        constexpr int TAIL = decltype(tail_c)::value;
         // U(c+1) -> U buffer (c+1)&1, raw(c+2) -> raw buffer c&1; past the item's end the next item's U(0), raw(0), raw(1)
-        const bool own_u = c + 1 < nchunks, own_r = c + 2 < nchunks;
+        constexpr bool own_u = TAIL < 2, own_r = TAIL < 1;
         const rsrc_t rs_u = make_rsrc(own_u ? w_t : w_n);
         const rsrc_t rs_r = make_rsrc(own_r ? in_t : in_n);
         const rsrc_t rs_rl = make_rsrc(own_r ? in_t : in_n, raw_last_num);
         const int usoff = own_u ? (c + 1) * U_BYTES : 0;
-        const int rsoff = (own_r ? c + 2 : c + 2 - nchunks) * 64;
-        char* const udst = smem + 2 * RAW_BYTES + (1 - PAR) * U_BYTES;
-        char* const rdst = smem + PAR * RAW_BYTES;
-        const unsigned ub = PAR ? offU1 : offU;
+        const int rsoff = (own_r ? c + 2 : TAIL - 1) * 64;
+        // LDS-DMA destinations = the wave's base + a literal, added where the request is issued; the base passes through an empty asm once
+        // per chunk so that the 38 sums of a chunk pair are not hoisted out of the item loop into SGPRs held across it (conv_f43.h)
+        int wb = wave * 1024;
+        asm volatile("" : "+s"(wb));
+        lds_char* const wdst = (lds_char*)smem + wb;
+        lds_char* const udst = wdst + 2 * RAW_BYTES + (1 - PAR) * U_BYTES;
+        lds_char* const rdst = wdst + PAR * RAW_BYTES;
+        unsigned ub = offU;      // the odd chunks' U buffer: one v_add per chunk instead of a second address held in a VGPR across the item loop
+        if constexpr (PAR != 0) { asm volatile("" : "+v"(ub)); ub += U_BYTES; }
         constexpr int RB = (1 - PAR) * RAW_BYTES;    // raw buffer (c+1)&1
         f32x4 u[4][NB];      // U fragments in flight, slot = position & 3
         f32x4 (&d)[16] = vnext;
@@ -237,8 +254,8 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (i < G::U_IT) bufld16_rs(rs_u, udst + (i * NT + wave * 64) * 16, tid * 16, usoff + i * NT * 16);
-            if constexpr (i < G::RAW_IT) bufld16_rs(i == G::RAW_IT - 1 ? rs_rl : rs_r, rdst + (i * NT + wave * 64) * 16, asrc[i], rsoff);
+            if constexpr (i < G::U_IT) bufld16_rs(rs_u, udst + i * NT * 16, tid16, usoff + i * NT * 16);
+            if constexpr (i < G::RAW_IT) bufld16_rs(i == G::RAW_IT - 1 ? rs_rl : rs_r, rdst + i * NT * 16, asrc[i], rsoff);
             const f32x4 vv = vcur[G::vidx(i)];
 #pragma unroll
             for (int s = 0; s < 4; ++s)
@@ -270,34 +287,55 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
         __syncthreads();      // raw(0) read by every wave before the first chunk requests raw(2) into its buffer
     }
     while (have) {
-        const int e_y0 = (cur.ty + p.ty0) * 32, e_x0 = (cur.tx + p.tx0) * 32, e_b = cur.b, e_ntile = cur.nt;
-        nxt = advance(cur);
-        have_nxt = nxt.b < p.B;
-        in_n = have_nxt ? in_of(nxt) : in_t;
-        w_n = have_nxt ? w_of(nxt) : w_t;
-        if (par_ntile != e_ntile || (PERIMG && par_img != e_b)) {
+        if (par_ntile != cur.nt || (PERIMG && par_img != cur.b)) {
             __syncthreads();
-            stage_params(e_ntile, e_b);
-            par_ntile = e_ntile; par_img = e_b;
+            stage_params(cur.nt, cur.b);
+            par_ntile = cur.nt; par_img = cur.b;
         }
-        chunk_body(0, std::integral_constant<int, 0>{}, std::true_type{}, va, vb);
+        using C0 = std::integral_constant<int, 0>; using C1 = std::integral_constant<int, 1>; using C2 = std::integral_constant<int, 2>;
+        chunk_body(0, C0{}, std::true_type{}, C0{}, va, vb);
         __syncthreads();
-        chunk_body(1, std::integral_constant<int, 1>{}, std::false_type{}, vb, va);
+        chunk_body(1, C1{}, std::false_type{}, C0{}, vb, va);
         __syncthreads();
-        for (int c = 2; c < nchunks; c += 2) {
-            chunk_body(c, std::integral_constant<int, 0>{}, std::false_type{}, va, vb);
+        for (int c = 2; c + 2 < nchunks; c += 2) {
+            chunk_body(c, C0{}, std::false_type{}, C0{}, va, vb);
             __syncthreads();
-            chunk_body(c + 1, std::integral_constant<int, 1>{}, std::false_type{}, vb, va);
+            chunk_body(c + 1, C1{}, std::false_type{}, C0{}, vb, va);
             __syncthreads();
         }
+        // the next item: only the peeled last two chunks (which request its first tiles) and the loop's next turn need it
+        const int e_b = cur.b, e_ntile = cur.nt;
+        int e_y0, e_x0;
+        {
+            const ConvPK pn = conv_args();
+            e_y0 = (cur.ty + pn->ty0) * 32; e_x0 = (cur.tx + pn->tx0) * 32;
+            nxt = advance(pn, cur);
+            have_nxt = nxt.b < pn->B;
+            in_n = have_nxt ? in_of(pn, nxt) : in_t;
+            w_n = have_nxt ? w_of(pn, nxt) : w_t;
+        }
+        chunk_body(nchunks - 2, C0{}, std::false_type{}, C1{}, va, vb);
+        __syncthreads();
+        chunk_body(nchunks - 1, C1{}, std::false_type{}, C2{}, vb, va);
+        __syncthreads();
         cur = nxt; have = have_nxt; in_t = in_n; w_t = w_n;
 
         // ---- output transform + epilogue.  The lane's tile: outputs (yb..yb+3, xb..xb+3), low-resolution pixels (ly0.., lx0..)
-        float* out_b = p.out + (size_t)e_b * (size_t)(p.H + 2) * (p.W + 2 + (p.out_p8 ? 6 : 0)) * p.Cout;
+        const ConvPK p = conv_args();      // the epilogue's fields: loaded here
+        // ... and its lane coordinates derived here, from a lane id the compiler cannot trace to the kernel's start: hoisted out of the
+        // item loop, the epilogue's per-lane offsets and 64-bit addresses sat in VGPRs across the K loop (parked in AGPRs or scratch)
+        int ln = tid16;
+        asm volatile("" : "+v"(ln));
+        ln = (ln >> 4) & 63;
+        const int t = ln & 15, q = ln >> 4, tr = t >> 3, tc = t & 7;
+        float* out_b = p->out + (size_t)e_b * (size_t)(p->H + 2) * (p->W + 2 + (p->out_p8 ? 6 : 0)) * p->Cout;
         const int yb = e_y0 + 8 * tg + 4 * tr, xb = e_x0 + 4 * tc;
+        // the epilogue starts behind the K loop's last MFMA run: scheduled into it, its first reads met the next item's patch (64 VGPRs, live
+        // across the epilogue) at the register limit, and an accumulator quad of the frame-mode instantiation went through scratch
+        __builtin_amdgcn_sched_barrier(0);
         {      // shortcut: sc[a][b] = P_mm + sb P_md + sa P_dm + sa sb P_dd, s0 = -1, s1 = +1 (no bias: conv_shortcut has none)
             const int ly0 = yb >> 1, lx0 = xb >> 1;
-            float* sc_b = p.sc_out + (size_t)e_b * (size_t)(p.Hi + 2) * (p.Wi + 2) * p.Cout;
+            float* sc_b = p->sc_out + (size_t)e_b * (size_t)(p->Hi + 2) * (p->Wi + 2) * p->Cout;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const f32x4 s0 = f4sub(acc[25][nb], acc[27][nb]), s1 = e4add(acc[25][nb], acc[27][nb]);      // a = 0 / 1
@@ -308,8 +346,8 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
                         const int ly = ly0 + a, lx = lx0 + b;
-                        if (ly < p.Hi && lx < p.Wi)
-                            *(f32x4*)(sc_b + ((size_t)(ly + 1) * (p.Wi + 2) + lx + 1) * p.Cout + e_ntile * 32 + nb * 16 + 4 * q) = sc[a][b];
+                        if (ly < p->Hi && lx < p->Wi)
+                            *(f32x4*)(sc_b + ((size_t)(ly + 1) * (p->Wi + 2) + lx + 1) * p->Cout + e_ntile * 32 + nb * 16 + 4 * q) = sc[a][b];
                     }
             }
         }
@@ -345,9 +383,9 @@ __device__ __forceinline__ void conv_ups5_body(const ConvP& p) {
                     if (EPI & E_RELU) o = f4relu(o);
                     if (EPI & E_LRELU) o = f4lrelu(o);
                     if (EPI & E_NORM1) o = f4norm_clamp(o, m1, r1, lo1, hi1);
-                    if (y < p.H && x < p.W) {
-                        if (p.out_p8) *(f32x4*)(out_b + (size_t)(co >> 3) * ((size_t)(p.H + 2) * (p.W + 8) * 8) + ((size_t)(y + 1) * (p.W + 8) + x + 4) * 8 + (co & 7)) = o;
-                        else *(f32x4*)(out_b + ((size_t)(y + 1) * (p.W + 2) + x + 1) * p.Cout + co) = o;
+                    if (y < p->H && x < p->W) {
+                        if (p->out_p8) *(f32x4*)(out_b + (size_t)(co >> 3) * ((size_t)(p->H + 2) * (p->W + 8) * 8) + ((size_t)(y + 1) * (p->W + 8) + x + 4) * 8 + (co & 7)) = o;
+                        else *(f32x4*)(out_b + ((size_t)(y + 1) * (p->W + 2) + x + 1) * p->Cout + co) = o;
                     }
                 }
         }

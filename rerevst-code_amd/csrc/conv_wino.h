@@ -542,7 +542,7 @@ __device__ __forceinline__ void conv_upw_body(const ConvP& p) {
 template <int EPI, int ABL = 0, int NW = 4, int UPS = 1, int SC = 0, int PERIMG = 0>
 __global__ __launch_bounds__(NW * 64, (SC ? Ups5Geo::OCC : WinoGeo<NW, UPS>::OCC)) void conv_wino_k(const ConvP p) {
     static_assert(UPS == 1 && NW == 4, "library kernel: upsample-fused form, 4 waves");
-    if constexpr (SC) conv_ups5_body<EPI, PERIMG>(p);
+    if constexpr (SC) conv_ups5_body<EPI, PERIMG>();      // reads ConvP through conv_args()
     else conv_upw_body<EPI, ABL, NW, UPS, PERIMG>(p);
 }
 

@@ -100,20 +100,23 @@ static void bench(const char* name, int B, int H, int W, int Cin, int Cout) {
     p43.wpk = w43; p23.wpk = w23;
     const double fl = 2.0 * B * H * W * (double)Cin * Cout * 9;      // direct-form FLOPs
     if (F43_ABL & 16) {
-        long long* dbg; CK(hipMalloc(&dbg, (size_t)256 * 4 * 6 * 8));
-        CK(hipMemset(dbg, 0, (size_t)256 * 4 * 6 * 8));
+        constexpr int NTL = 10;      // conv_f43.h: tl[]
+        long long* dbg; CK(hipMalloc(&dbg, (size_t)256 * 4 * NTL * 8));
+        CK(hipMemset(dbg, 0, (size_t)256 * 4 * NTL * 8));
         run43<EPI>(p43, 1, dbg);
         ConvP pg = p43; dim3 gd = grid_for(pg, 32);
         const int items = pg.tiles_x * pg.tiles_y * B * (Cout / 32), g = gd.x;
-        std::vector<long long> h((size_t)g * 4 * 6);
+        std::vector<long long> h((size_t)g * 4 * NTL);
         CK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        double s6[6] = {0};
-        for (size_t i = 0; i < h.size(); ++i) s6[i % 6] += h[i];
+        double s6[NTL] = {0};
+        for (size_t i = 0; i < h.size(); ++i) s6[i % NTL] += h[i];
         const double ipw = (double)items / g;
         const char* nm[6] = {"item setup", "MFMA runs + gaps", "-", "barriers", "output transform + stores", "input transforms (+ next item's patch)"};
         printf("%-22s EPI %2d timeline (clk/item, %d chunks = %d MFMA clk):", name, EPI, Cin / 8, Cin / 8 * 4608);
         for (int k : {0, 1, 3, 5, 4}) printf(" %s %.0f |", nm[k], s6[k] / (g * 4) / ipw);
-        printf(" %.1f items/WG\n", ipw);
+        // the item's first chunk pair against its first steady pair (a spill-free first pair costs what a steady one costs), and the
+        // clock the chip held over the launch: shader clocks per tick of the constant 100 MHz counter
+        printf(" first pair %.0f | steady pair %.0f | %.1f items/WG | %.0f MHz\n", s6[6] / (g * 4) / ipw, s6[7] / (g * 4) / ipw, ipw, s6[9] > 0 ? 100.0 * s6[8] / s6[9] : 0.0);
         CK(hipFree(dbg));
     } else {
         const int it = 10;
