@@ -547,9 +547,35 @@ int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H
  *   what = RRV_DBG_STYLE_PRED: the style half of the filter predictions of prepared style `image` (mean over H x W of
  *     Filter1..3's F1 / F2 down_sample of the normalised style map: [6][32] floats, n == 192); `slot` must be 0.
  *     RRV_E_STATE when that style has not been prepared. */
+/*   what = RRV_DBG_STYLE_BLOB: the state blob of prepared style `image` as it stands, computed or not (after a pass that
+ *     rrv_debug_prep_stop ended early: the entries up to that sync point and the style statistics); `slot` must be 0,
+ *     n == RRV_STATE_FLOATS.  RRV_E_STATE when that style has not been prepared. */
 #define RRV_DBG_STATE_SET 0
 #define RRV_DBG_STYLE_PRED 1
+#define RRV_DBG_STYLE_BLOB 2
 int rrv_debug_copy_state(rrv_handle h, int what, int slot, int image, float* out, int n);
+
+/* Layer-parity stop of the preparation pass.  stage = -1 (default): off.  stage = 0..13, one of the pass's sync points in
+ * order (0 Decoder.norm[0]; 1..3 Filter1..3: both predictions, the fold, frame 0's two folded convolutions and the residual
+ * add; 4 Decoder.norm[1]; 5 + 3k, 6 + 3k, 7 + 3k: norm1, norm2 and the AdaIN norm of residual block k): rrv_compute launches
+ * what it always launches up to and including that sync point's statistic and nothing further, for every prepared style,
+ * resident or streaming.  Below 13 the styles stay "not computed" (the transfer entries refuse them); 13 is a full pass.
+ * Either way the pass's workspace is kept for rrv_debug_copy_prep_tensor until the next rrv_compute, rrv_clean,
+ * rrv_destroy, or this knob being switched off. */
+int rrv_debug_prep_stop(rrv_handle h, int stage);
+
+/* One image of a tensor of the preparation pass, ring layout [H+2][W+2][C], copied to the host after a full
+ * synchronisation; *floats receives its size (nothing is copied when cap is smaller), *H, *W, *C its geometry.
+ *   index 0..19: the workspace kept under rrv_debug_prep_stop, in the order cn nxt t32 d32 u xs4 a4 o4 xs3 a3 o3 xs2 a2 o2
+ *     content grp f0 su1 su2 su3 (d32, u, f0, su*: one image; content: resident passes; grp, f0, su*: streaming passes);
+ *   RRV_DBG_PREP_PATCH: the stored relu4_1 feature of sampled frame `image`;
+ *   RRV_DBG_PREP_STYLE_C11 .. + 3: relu1_1, relu2_1, relu3_1, relu4_1 of the style image the last rrv_prepare_style encoded;
+ *   RRV_DBG_PREP_MAP: the relu4_1 map of prepared style `image`.
+ * RRV_E_STATE for a tensor the last pass did not allocate and for an image beyond the batch. */
+#define RRV_DBG_PREP_PATCH 20
+#define RRV_DBG_PREP_STYLE_C11 21
+#define RRV_DBG_PREP_MAP 25
+int rrv_debug_copy_prep_tensor(rrv_handle h, int index, int image, float* host, size_t cap, size_t* floats, int* H, int* W, int* C);
 
 /* Stream-ordered use of the *_device entries from a caller that produces / consumes the buffers on its own HIP
  * stream (e.g. torch.cuda.current_stream().cuda_stream): see ORDERING above.  enable = 0 switches it off. */

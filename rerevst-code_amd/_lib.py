@@ -29,7 +29,12 @@ LAY_I420_16, LAY_P016 = 8, 9      # 10 / 12 / 16-bit YUV 4:2:0 in uint16 samples
 YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8
-DBG_STATE_SET, DBG_STYLE_PRED = 0, 1
+DBG_STATE_SET, DBG_STYLE_PRED, DBG_STYLE_BLOB = 0, 1, 2
+# rrv_debug_copy_prep_tensor: 0..19 the preparation workspace in this order, then a sampled frame's stored feature, the style
+# encoder's four taps and a style's map
+PREP_TENSORS = ("cn", "nxt", "t32", "d32", "u", "xs4", "a4", "o4", "xs3", "a3", "o3", "xs2", "a2", "o2", "content", "grp", "f0",
+                "su1", "su2", "su3", "patch", "style_c11", "style_c21", "style_c31", "style_c41", "map")
+DBG_PREP_PATCH, DBG_PREP_STYLE_C11, DBG_PREP_MAP = 20, 21, 25
 
 # name -> (restype, argtypes); must list every symbol declared in include/rerevst_hip.h
 SYMBOLS = {
@@ -121,6 +126,9 @@ SYMBOLS = {
     "rrv_debug_copy_tensor_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rrv_debug_copy_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rrv_debug_prep_stop": (C.c_int, [C.c_void_p, C.c_int]),
+    "rrv_debug_copy_prep_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rrv_set_grid_share": (C.c_int, [C.c_void_p, C.c_int]),
     "rrv_set_caller_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rrv_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),

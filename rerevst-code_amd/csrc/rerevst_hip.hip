@@ -237,6 +237,7 @@ struct rrv_ctx {
     size_t ws_cap = (size_t)64 << 30;          // preparation-pass workspace above which compute() streams groups of frames
     int last_groups = 0, last_group_size = 0; size_t last_ws_bytes = 0;
     PrepPlan prep;
+    int prep_stop = -1;               // rrv_debug_prep_stop: rrv_compute ends at this sync point (ST_*) and keeps the plan; -1: off
     // frames handed to rrv_add wait here (uint8, HBM) and are encoded together, 8 per encoder launch, when their
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
@@ -1494,6 +1495,9 @@ size_t prep_bytes(int B, int hh, int ww, bool streaming) {
     return n;
 }
 
+// the 14 sync points of the pass, in order (the streaming pass walks them one by one; rrv_debug_prep_stop ends either pass at one)
+enum { ST_NORM0 = 0, ST_FILTER = 1 /* +f */, ST_NORM1 = 4, ST_BLOCKS = 5 /* +3k: n1, n2, nada */, ST_COUNT = 14 };
+
 // on the plan's content batch (rrv_compute)
 int compute_style(rrv_handle h, int sid) {
     StyleState& S = h->styles[sid];
@@ -1503,10 +1507,13 @@ int compute_style(rrv_handle h, int sid) {
     const int B = content.B, hh = content.H, ww = content.W;
     Tens &cn = P.cn, &nxt = P.nxt, &t32 = P.t32, &d32 = P.d32, &u = P.u;
     float* cmean = h->prep_cmean;
+    const int stop = h->prep_stop;
+    if (stop >= 0) S.computed = false;
     auto body = [&]() -> int {
         // norm[0].compute on the batch (style_network_global.py:396); the style half of the filter predictions
         // (normalized_style :397 through F.down_sample, :161-172) was evaluated once in prepare_style (S.smean)
         RCHK(chan_stats(h, content, 1, st + SL.norm[N_DEC0]));
+        if (stop == ST_NORM0) return WALK_STOP;
         RCHK(apply_norm(h, content, cn, st, N_DEC0));
         Tens* cur = &cn; Tens* other = &nxt;
         for (int f = 0; f < 3; ++f) {
@@ -1526,20 +1533,27 @@ int compute_style(rrv_handle h, int sid) {
             ConvCall c{&cur0, &d32, &h->cur->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, c));
             ConvCall cu{&d32, &u, &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
             RCHK(pointwise(h, *cur, *other, nullptr, nullptr, false, &u, 1, nullptr, nullptr));
+            if (stop == ST_FILTER + f) return WALK_STOP;
             Tens* t = cur; cur = other; other = t;
         }
         h->active_src = -1;   // folded weights now belong to this style's blob; re-activate below
         // AdaIN_compute(1) (style_network_global.py:428)
         RCHK(chan_stats(h, *cur, 1, st + SL.norm[N_DEC1]));
+        if (stop == ST_NORM1) return WALK_STOP;
         RCHK(apply_norm(h, *cur, *cur, st, N_DEC1, nullptr, 3));
         // AdaIN_compute(k + 2) ends block k; nothing reads the last block's normalised output
-        return unfused_blocks(h, B, *cur, P.xs, P.a, P.o, st, 0, false, false, [&](const Tens& t, int n, int) { return chan_stats(h, t, 1, st + SL.norm[n]); });
+        return unfused_blocks(h, B, *cur, P.xs, P.a, P.o, st, 0, false, false, [&](const Tens& t, int n, int point) -> int {
+            RCHK(chan_stats(h, t, 1, st + SL.norm[n]));
+            return stop == ST_BLOCKS + point && stop != ST_COUNT - 1 ? WALK_STOP : RRV_OK;
+        });
     };
     int rc = body();
+    const bool stopped = rc == WALK_STOP;      // rrv_debug_prep_stop: the state is left as far as it got, not computed
+    if (stopped) { rc = RRV_OK; h->active_src = -1; }
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute");
     (void)hipStreamSynchronize(h->stream);
-    if (rc == RRV_OK) S.computed = true;
-    if (rc == RRV_OK) rc = filter_conditioning(h, S);
+    if (rc == RRV_OK && !stopped) S.computed = true;
+    if (rc == RRV_OK && !stopped) rc = filter_conditioning(h, S);
     return rc;
 }
 
@@ -1802,8 +1816,6 @@ int chan_stats_finish(rrv_handle h, int slot, int C, double N, int mode, float* 
     return RRV_OK;
 }
 
-enum { ST_NORM0 = 0, ST_FILTER = 1 /* +f */, ST_NORM1 = 4, ST_BLOCKS = 5 /* +3k: n1, n2, nada */, ST_COUNT = 14 };
-
 // Decoder.compute prefix of one group (`grp`: nb raw relu4_1 features) up to sync point `stage`, whose partial
 // statistics are merged (n_a = elements per channel already merged at that stage's resolution: frames_before * H * W).
 int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int frames_before) {
@@ -1851,6 +1863,8 @@ int compute_style_streaming(rrv_handle h, int sid) {
     PrepPlan& P = h->prep;
     const int B = (int)h->patches.size(), G = P.grp.B, hh = h->patch_h, ww = h->patch_w;
     const size_t img = P.grp.img_floats();
+    const int stop = h->prep_stop;
+    if (stop >= 0) S.computed = false;
     auto body = [&]() -> int {
         for (int stage = 0; stage < ST_COUNT; ++stage) {
             for (int g0 = 0; g0 < B; g0 += G) {
@@ -1887,15 +1901,18 @@ int compute_style_streaming(rrv_handle h, int sid) {
                 const double N = (double)B * (hh << (k + 1)) * (ww << (k + 1));
                 RCHK(chan_stats_finish(h, 0, b.cout, N, 1, st + SL.norm[w == 0 ? b.n1 : (w == 1 ? b.n2 : b.nada)]));
             }
+            if (stage == stop && stop != ST_COUNT - 1) return WALK_STOP;
         }
         return RRV_OK;
     };
     int rc = body();
+    const bool stopped = rc == WALK_STOP;      // rrv_debug_prep_stop
+    if (stopped) rc = RRV_OK;
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute (streaming)");
     (void)hipStreamSynchronize(h->stream);
     h->active_src = -1;
-    if (rc == RRV_OK) S.computed = true;
-    if (rc == RRV_OK) rc = filter_conditioning(h, S);
+    if (rc == RRV_OK && !stopped) S.computed = true;
+    if (rc == RRV_OK && !stopped) rc = filter_conditioning(h, S);
     return rc;
 }
 
@@ -2325,6 +2342,7 @@ int rrv_clean(rrv_handle h) {
     (void)sync_all(h);
     for (float* p : h->patches) (void)hipFree(p);
     h->patches.clear();
+    prep_free(h);      // (a plan kept by rrv_debug_prep_stop)
     h->pend_n = 0;
     h->patch_h = h->patch_w = h->add_H = h->add_W = 0;
     for (StyleState& s : h->styles) s.computed = false;
@@ -2432,6 +2450,7 @@ int rrv_compute(rrv_handle h) {
         while (G < B && prep_bytes(G + 1, hh, ww, true) <= h->ws_cap) ++G;
     }
     h->last_groups = (B + G - 1) / G; h->last_group_size = G; h->last_ws_bytes = prep_bytes(G, hh, ww, streaming);
+    prep_free(h);      // (a plan kept by rrv_debug_prep_stop; empty otherwise)
     RCHK(prep_plan(h, G, hh, ww, streaming));
     int first = -1;
     auto body = [&]() -> int {
@@ -2448,10 +2467,11 @@ int rrv_compute(rrv_handle h) {
     };
     const int rc = body();
     (void)hipStreamSynchronize(h->stream);
-    prep_free(h);      // several GB for a video's sampled frames
+    if (h->prep_stop < 0 || rc != RRV_OK) prep_free(h);      // several GB for a video's sampled frames
     if (rc != RRV_OK) return rc;
     if (h->debug) RCHK(debug_verify(h, "compute"));
     h->active_src = -1;
+    if (!h->styles[first].computed) return RRV_OK;      // rrv_debug_prep_stop ended the pass early: no state to activate
     return activate_state(h, first);
 }
 
@@ -3749,12 +3769,67 @@ int rrv_debug_copy_state(rrv_handle h, int what, int slot, int image, float* out
         HIPCHK(hipMemcpy(out, S.smean, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         return RRV_OK;
     }
+    if (what == RRV_DBG_STYLE_BLOB) {      // as it stands: a pass ended by rrv_debug_prep_stop leaves the later entries unwritten
+        if (slot != 0 || image >= RRV_MAX_STYLES || n != RRV_STATE_FLOATS) return RRV_E_ARG;
+        const StyleState& S = h->styles[image];
+        if (!S.prepared || !S.blob) return fail(h, RRV_E_STATE, "debug_copy_state: prepare_style has not been called for this style");
+        HIPCHK(hipSetDevice(h->dev));
+        RCHK(sync_all(h));
+        HIPCHK(hipMemcpy(out, S.blob, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return RRV_OK;
+    }
     if (what != RRV_DBG_STATE_SET || slot < 0 || slot > 1 || image >= rrv_ctx::MS_GROUP_MAX || n != RRV_STATE_FLOATS) return RRV_E_ARG;
     if (!h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch kept no per-image state");
     if (image >= h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch did not write this image");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
     HIPCHK(hipMemcpy(out, h->sets[rrv_ctx::MS_GROUP_MAX * slot + image].active, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return RRV_OK;
+}
+
+int rrv_debug_prep_stop(rrv_handle h, int stage) {
+    if (!h || stage < -1 || stage >= ST_COUNT) return RRV_E_ARG;
+    if (stage < 0 && h->prep_stop >= 0) {
+        HIPCHK(hipSetDevice(h->dev));
+        RCHK(sync_all(h));
+        prep_free(h);
+    }
+    h->prep_stop = stage;
+    return RRV_OK;
+}
+
+// Layer-parity tap of the preparation pass (tests/test_gpu_prep_layers.py): one image of a tensor the last rrv_compute under
+// rrv_debug_prep_stop kept (index 0..19: the rows of PREP_T), of a sampled frame's stored feature, of the style encoder's plan
+// or of a style's map.  Ring layout.
+int rrv_debug_copy_prep_tensor(rrv_handle h, int index, int image, float* host, size_t cap, size_t* floats, int* H, int* W, int* C) {
+    constexpr int NT = (int)(sizeof(PREP_T) / sizeof(PREP_T[0]));
+    static_assert(NT == RRV_DBG_PREP_PATCH, "rerevst_hip.h numbers the rows of PREP_T");
+    if (!h || index < 0 || index > RRV_DBG_PREP_MAP || image < 0 || !floats) return RRV_E_ARG;
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(sync_all(h));
+    Tens t;
+    int first = 0;      // the image t.p holds (a stored feature and a style's map are allocations of their own)
+    if (index < NT) {
+        t = PREP_T[index].of(h->prep);
+    } else if (index == RRV_DBG_PREP_PATCH) {
+        t.B = (int)h->patches.size(); t.H = h->patch_h; t.W = h->patch_w; t.C = 512;
+        if (image < t.B) { t.p = h->patches[(size_t)image]; first = image; }
+        else if (t.B) t.p = h->patches[0];
+    } else if (index < RRV_DBG_PREP_MAP) {
+        static const size_t enc_row[4] = {0, 2, 4, 8};
+        t = ENC_T[enc_row[index - RRV_DBG_PREP_STYLE_C11]].of(h->enc_style);
+        t.B = 1;
+    } else if (image < RRV_MAX_STYLES && h->styles[image].prepared) {
+        t = h->styles[image].map; t.B = image + 1; first = image;
+    }
+    if (!t.p) return fail(h, RRV_E_STATE, "debug_copy_prep_tensor: the last pass did not allocate this tensor");
+    if (image >= t.B) return fail(h, RRV_E_STATE, "debug_copy_prep_tensor: image beyond the batch");
+    const size_t n = t.img_floats();
+    *floats = n;
+    if (H) *H = t.H;
+    if (W) *W = t.W;
+    if (C) *C = t.C;
+    if (host && cap >= n) HIPCHK(hipMemcpy(host, t.p + (size_t)(image - first) * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return RRV_OK;
 }
 

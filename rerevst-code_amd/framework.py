@@ -864,6 +864,29 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_PRED, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
+    def debug_style_blob(self, style_id=0):
+        """The state blob of a prepared style as it stands, computed or not (rrv_debug_copy_state): after a compute() that
+        debug_prep_stop ended early, the entries up to that sync point and the style statistics."""
+        out = np.empty(_lib.STATE_FLOATS, dtype=np.float32)
+        self._chk(self._lib.rrv_debug_copy_state(self._h, _lib.DBG_STYLE_BLOB, 0, int(style_id), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def debug_prep_stop(self, stage):
+        """compute() ends at sync point `stage` (0..13: Decoder.norm[0], Filter1..3, Decoder.norm[1], then norm1 / norm2 / the AdaIN
+        norm of each residual block) and keeps its workspace for debug_prep_tensor; -1 switches it off (rrv_debug_prep_stop)."""
+        self._chk(self._lib.rrv_debug_prep_stop(self._h, int(stage)))
+
+    def debug_prep_tensor(self, name, image=0):
+        """Image `image` of tensor `name` (_lib.PREP_TENSORS) of the preparation pass (rrv_debug_copy_prep_tensor): float32
+        [H+2][W+2][C] as stored, ring included."""
+        idx = _lib.PREP_TENSORS.index(name)
+        n, H, W, Ch = C.c_size_t(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        tail = (C.byref(n), C.byref(H), C.byref(W), C.byref(Ch))
+        self._chk(self._lib.rrv_debug_copy_prep_tensor(self._h, idx, int(image), None, 0, *tail))
+        out = np.empty(n.value, np.float32)
+        self._chk(self._lib.rrv_debug_copy_prep_tensor(self._h, idx, int(image), out.ctypes.data_as(C.c_void_p), n.value, *tail))
+        return out.reshape(H.value + 2, W.value + 2, Ch.value)
+
     def _set_matrix(self, set8, set16, matrix_of, input_side, standard, full_range, bits):
         """set_yuv_matrix / set_yuv_input_matrix: the side's 8-bit or uint16 setter, its depth, and matrix_of(standard, full_range, bits)"""
         bits = _yuv_depth(bits)

@@ -40,6 +40,8 @@ pointwise_k pass's own result carried the same way.  The families of the frame-m
          bound still carries the convolution's own term with its existing K.
   pred   rect_sums_k + pred_mean_k + fc_filter_k against the reference's form (zero-padded 3 x 3 down_sample convolution,
          mean over H x W, FC with the style half), magnitude: the same arithmetic on absolute values through the FC.
+The preparation pass (tests/prep_ref.py) adds pstat (the two-pass and merged statistics against their own raw tap), gemm
+(conv_mfma_k raw outputs) and ppred (a tap's mean + the FC); their forms are in that module's docstring.
 """
 import numpy as np
 import torch
@@ -47,7 +49,7 @@ import torch.nn.functional as TF
 
 U = 2.0 ** -24
 
-FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "mnorm", "mfilt")
+FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "mnorm", "mfilt", "pstat", "gemm", "ppred")
 
 # max |gpu - ref| / (2^-24 m) per family, over every tap and shape of tests/test_gpu_layers.py on an MI355X (the worst tap):
 #   direct  30.7  c11 (conv_first: the grey fold multiplies 1/std into the weights, so its rounding is relative to the
@@ -74,10 +76,22 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "m
 # measured over the cases 1 x 8 x 8 .. 16 x 136 x 200 (S = 1 .. 8); the split-4, split-1, pad / crop and host-entry cases have
 # NOT yet contributed a figure.  The convolutions stayed inside their figures: direct 28.1, f23 5.24 against its K of 8, ups 10.2
 # against its K of 19.
-MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314}
+# and the three families of the preparation pass (tests/prep_ref.py), over every case of tests/test_gpu_prep_layers.py (resident
+# 1 x 8 x 8 .. 5 x 136 x 200 at all 14 sync points, 1 x 520 x 520 and 4 x 4104 x 8 at the full-resolution ones, three style sizes,
+# two styles, one streamed group at every sync point, five frames in groups of 1, 2 and 3; profiles/prep_layers.txt):
+#   pstat    4.24 norm[2] <- o4 at 1 x 8 x 8 (four pixels; the variance recovered from a float32 rstd carries that rstd's 1.5
+#                 ulp twice; 3.3 .. 4.2 at every size, the merged statistics 3.99, the style statistics 3.82; the means <= 0.5)
+#   gemm     7.95 xs2 at 520 x 520 (conv_mfma_k: one float32 MFMA accumulator per output over all of K, no split; the 1 x 1
+#                 shortcuts 5.9 .. 8.0, the 512 -> 32 predictor convolutions up to 6.0)
+#   ppred    1.91 Filter3.F2 at 5 x 136 x 200 (a 64-term float32 sum in fc_filter_k; 1.0 .. 1.9)
+# The preparation-only instantiations stayed inside the existing figures: f23 2.44 (conv2 raw; the unsplit folded 512 -> 32 and
+# 32 -> 512 convolutions below it), ups 5.2 (the nine-product conv_upw<E_LRELU>), point 2.77.
+MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314,
+            "pstat": 4.24, "gemm": 7.95, "ppred": 1.91}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
 # still rejecting the defects tests/test_layer_ref.py injects (the smallest of them, one weight off by 2^-8, is at 2480)
-K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5, "mnorm": 8.0, "mfilt": 0.7}
+K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5, "mnorm": 8.0, "mfilt": 0.7,
+     "pstat": 9.0, "gemm": 16.0, "ppred": 4.0}
 
 # the tap indices of rrv_debug_copy_tensor_ex
 TAP_NAMES = ["c11", "p1", "c21", "p2", "c31", "c32", "c33", "p3", "c41",
@@ -240,14 +254,20 @@ def _down(f):
     return op
 
 
+def fold_up(f, d, w, st, y0, y1):
+    """up(F2 d) + b: the folded KernelFilter.upsample product alone, (v, m) with the absolute folded product as magnitude."""
+    p = "Decoder.Filter%d.upsample.0." % (f + 1)
+    F2 = st["filt"]["Filter%d.F2" % (f + 1)]
+    d = np.asarray(d, np.float64)
+    v, _ = conv3(d @ F2.T, w[p + "weight"], w[p + "bias"], y0, y1)
+    _, m = conv3(np.abs(d) @ np.abs(F2).T, np.abs(w[p + "weight"]), w[p + "bias"], y0, y1)
+    return v, m
+
+
 def _up(f):
     """f = cur + up(F2 d) (+ Decoder.norm[1] and AdaIN with relu4_1 after Filter3): the folded KernelFilter.upsample."""
     def op(inp, w, st, y0, y1):
-        p = "Decoder.Filter%d.upsample.0." % (f + 1)
-        F2 = st["filt"]["Filter%d.F2" % (f + 1)]
-        d = np.asarray(inp[0], np.float64)
-        v, _ = conv3(d @ F2.T, w[p + "weight"], w[p + "bias"], y0, y1)
-        _, m = conv3(np.abs(d) @ np.abs(F2).T, np.abs(w[p + "weight"]), w[p + "bias"], y0, y1)
+        v, m = fold_up(f, inp[0], w, st, y0, y1)
         r = np.asarray(inp[1][y0:y1], np.float64)
         v, m = v + r, m + np.abs(r)
         if f == 2:

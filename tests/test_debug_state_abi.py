@@ -1,5 +1,6 @@
 """CPU checks of the per-image state read-back (rrv_debug_copy_state): declared in the header, listed in the ctypes table,
-exported by the built library, refuses bad arguments before it touches a device, and has its two framework wrappers."""
+exported by the built library, refuses bad arguments before it touches a device, and has its framework wrappers; the same
+for the preparation pass's stop knob and tensor read-back (rrv_debug_prep_stop, rrv_debug_copy_prep_tensor)."""
 import ctypes as C
 import importlib
 import inspect
@@ -19,9 +20,29 @@ def test_header_table_and_library_carry_the_read_back():
     L = importlib.import_module("rerevst-code_amd._lib")
     assert int(re.search(r"#define RRV_DBG_STATE_SET (\d+)", hdr).group(1)) == L.DBG_STATE_SET == 0
     assert int(re.search(r"#define RRV_DBG_STYLE_PRED (\d+)", hdr).group(1)) == L.DBG_STYLE_PRED == 1
+    assert int(re.search(r"#define RRV_DBG_STYLE_BLOB (\d+)", hdr).group(1)) == L.DBG_STYLE_BLOB == 2
     assert L.SYMBOLS["rrv_debug_copy_state"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int])
+    decl = re.search(r"int\s+rrv_debug_prep_stop\s*\(([^)]*)\)", hdr).group(1)
+    assert [a.strip() for a in decl.split(",")] == ["rrv_handle h", "int stage"]
+    assert L.SYMBOLS["rrv_debug_prep_stop"] == (C.c_int, [C.c_void_p, C.c_int])
+    decl = re.search(r"int\s+rrv_debug_copy_prep_tensor\s*\(([^)]*)\)", hdr).group(1)
+    assert [a.strip() for a in decl.split(",")] == ["rrv_handle h", "int index", "int image", "float* host", "size_t cap", "size_t* floats",
+                                                    "int* H", "int* W", "int* C"]
+    assert L.SYMBOLS["rrv_debug_copy_prep_tensor"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])
+    # the tensor codes: the workspace rows in the order of the library's table, then the three codes the header names
+    assert int(re.search(r"#define RRV_DBG_PREP_PATCH (\d+)", hdr).group(1)) == L.DBG_PREP_PATCH == L.PREP_TENSORS.index("patch") == 20
+    assert int(re.search(r"#define RRV_DBG_PREP_STYLE_C11 (\d+)", hdr).group(1)) == L.DBG_PREP_STYLE_C11 == L.PREP_TENSORS.index("style_c11") == 21
+    assert int(re.search(r"#define RRV_DBG_PREP_MAP (\d+)", hdr).group(1)) == L.DBG_PREP_MAP == L.PREP_TENSORS.index("map") == 25 == len(L.PREP_TENSORS) - 1
+    src = open(os.path.join(ROOT, "rerevst-code_amd", "csrc", "rerevst_hip.hip")).read()
+    table = re.search(r"const TSpec<PrepPlan> PREP_T\[\] = \{(.*?)\n\};", src, re.S).group(1)
+    rows = [m.replace("[", "").replace("]", "") for m in re.findall(r"offsetof\(PrepPlan, ([a-z0-9\[\]]+)\)", table)]
+    alias = {"xs0": "xs4", "a0": "a4", "o0": "o4", "xs1": "xs3", "a1": "a3", "o1": "o3", "xs2": "xs2", "a2": "a2", "o2": "o2", "su0": "su1", "su1": "su2",
+             "su2": "su3"}
+    assert tuple(alias.get(r, r) for r in rows) == L.PREP_TENSORS[:20]
     importlib.import_module("rerevst-code_amd.build").build_lib(verbose=False)
-    assert hasattr(L.load(), "rrv_debug_copy_state")
+    for name in ("rrv_debug_copy_state", "rrv_debug_prep_stop", "rrv_debug_copy_prep_tensor"):
+        assert hasattr(L.load(), name)
 
 
 def test_argument_checks_need_no_device():
@@ -39,10 +60,19 @@ def test_argument_checks_need_no_device():
                                         (L.DBG_STATE_SET, 2, 0, out, buf.size), (L.DBG_STATE_SET, -1, 0, out, buf.size),
                                         (L.DBG_STATE_SET, 0, 16, out, buf.size), (L.DBG_STATE_SET, 0, 0, out, buf.size - 1),
                                         (L.DBG_STYLE_PRED, 1, 0, out, 192), (L.DBG_STYLE_PRED, 0, L.MAX_STYLES, out, 192),
-                                        (L.DBG_STYLE_PRED, 0, 0, out, 191), (2, 0, 0, out, buf.size)):
+                                        (L.DBG_STYLE_PRED, 0, 0, out, 191), (L.DBG_STYLE_BLOB, 1, 0, out, buf.size),
+                                        (L.DBG_STYLE_BLOB, 0, L.MAX_STYLES, out, buf.size), (L.DBG_STYLE_BLOB, 0, 0, out, buf.size - 1),
+                                        (3, 0, 0, out, buf.size)):
             assert fn(h, what, slot, image, o, n) == RRV_E_ARG, (what, slot, image, n)
         assert fn(h, L.DBG_STATE_SET, 0, 0, out, buf.size) == -4                      # RRV_E_STATE: nothing launched yet
         assert fn(h, L.DBG_STYLE_PRED, 0, 0, out, 192) == -4                          # ... and no style prepared
+        assert fn(h, L.DBG_STYLE_BLOB, 0, 0, out, buf.size) == -4
+        stop, tap, n = L.load().rrv_debug_prep_stop, L.load().rrv_debug_copy_prep_tensor, C.c_size_t(0)
+        assert stop(h, -2) == stop(h, 14) == RRV_E_ARG and stop(h, 13) == stop(h, 0) == stop(h, -1) == 0
+        for index, image, fl in ((-1, 0, C.byref(n)), (L.DBG_PREP_MAP + 1, 0, C.byref(n)), (0, -1, C.byref(n)), (0, 0, None)):
+            assert tap(h, index, image, None, 0, fl, None, None, None) == RRV_E_ARG, (index, image)
+        for index in range(len(L.PREP_TENSORS)):
+            assert tap(h, index, 0, None, 0, C.byref(n), None, None, None) == -4, index  # no pass has run, nothing added or prepared
     finally:
         L.load().rrv_destroy(h)
 
@@ -66,4 +96,34 @@ def test_framework_wrappers():
     b = s.debug_style_pred(3)
     assert a.shape == (17536,) and a.dtype == np.float32 and a[0] == 7.0
     assert b.shape == (6, 32) and b.dtype == np.float32 and b[0, 0] == 7.0
-    assert calls == [(0, 1, 5, 17536), (1, 0, 3, 192)]
+    c = s.debug_style_blob(2)
+    assert c.shape == (17536,) and c.dtype == np.float32 and c[0] == 7.0
+    assert calls == [(0, 1, 5, 17536), (1, 0, 3, 192), (2, 0, 2, 17536)]
+
+
+def test_prep_wrappers():
+    F = importlib.import_module("rerevst-code_amd.framework")
+    L = importlib.import_module("rerevst-code_amd._lib")
+    assert list(inspect.signature(F.Stylization.debug_prep_stop).parameters) == ["self", "stage"]
+    assert list(inspect.signature(F.Stylization.debug_prep_tensor).parameters) == ["self", "name", "image"]
+    assert inspect.signature(F.Stylization.debug_prep_tensor).parameters["image"].default == 0
+    calls = []
+
+    class Lib:
+        def rrv_debug_prep_stop(self, h, stage):
+            calls.append(("stop", stage))
+            return 0
+
+        def rrv_debug_copy_prep_tensor(self, h, index, image, host, cap, floats, H, W, Ch):
+            calls.append((index, image, cap))
+            floats._obj.value, H._obj.value, W._obj.value, Ch._obj.value = 4 * 5 * 32, 2, 3, 32
+            if host is not None:
+                C.cast(host, C.POINTER(C.c_float))[639] = 7.0
+            return 0
+
+    s = F.Stylization.__new__(F.Stylization)
+    s._lib, s._h = Lib(), None
+    s.debug_prep_stop(6)
+    t = s.debug_prep_tensor("t32", 1)
+    assert t.shape == (4, 5, 32) and t.dtype == np.float32 and t[3, 4, 31] == 7.0
+    assert calls == [("stop", 6), (L.PREP_TENSORS.index("t32"), 1, 0), (2, 1, 640)]

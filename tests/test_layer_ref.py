@@ -103,7 +103,7 @@ def test_image_given_another_images_state_fails(setup, weights):
 
 
 def test_k_within_four_times_the_measured_maximum():
-    assert set(LR.MEASURED) == set(LR.K) == set(LR.FAMILIES) and {"stat", "point", "pred"} <= set(LR.FAMILIES)
+    assert set(LR.MEASURED) == set(LR.K) == set(LR.FAMILIES) and {"stat", "point", "pred", "pstat", "gemm", "ppred"} <= set(LR.FAMILIES)
     for f in LR.FAMILIES:
         assert 0 < LR.MEASURED[f] <= LR.K[f] <= 4 * LR.MEASURED[f], f
 
@@ -444,3 +444,201 @@ def test_level_mask_decoder(mk):
     off = [a.copy() for a in lv]
     off[2][1, 3, 4] = np.nextafter(off[2][1, 3, 4], np.float32(2))
     assert [ok for _, _, ok, _, _ in MR.check_level_masks({"lm%d" % l: off[l] for l in range(4)}.__getitem__, lv, S)] == [True, True, False, True]
+
+
+# ---- the preparation pass: the references of tests/test_gpu_prep_layers.py ----------------------------------------------------
+
+import prep_ref as PR            # noqa: E402
+
+F32 = np.float32
+
+
+def _lrelu_like(rng, n, C, spread=1.0):
+    """[n, C] float32 shaped like a LeakyReLU output: channel means and scales of their own."""
+    x = rng.standard_normal((n, C)) * rng.uniform(0.2, 3.0, C) * spread + rng.uniform(-1.0, 2.0, C)
+    return np.where(x >= 0, x, 0.2 * x).astype(F32)
+
+
+def _partials32(x, mean=None, keep=None):
+    """chan_stat_k's two passes over the pixels `keep` of x [n, C]: the fp64 sum, or (fp64 sum of fp32 squares about the fp32
+    mean, min, max)."""
+    x = x if keep is None else x[keep]
+    if mean is None:
+        return x.astype(np.float64).sum(axis=0)
+    d = (x - mean).astype(F32)
+    return (d * d).astype(F32).astype(np.float64).sum(axis=0), x.min(axis=0), x.max(axis=0)
+
+
+def _two_pass32(x, mode=1, keep=None, n_for_style=None):
+    """chan_stat_k + chan_final_k (modes 1 and 2) in float32 numpy.  keep: the pixels the passes read (a defect: N stays)."""
+    N = x.shape[0]
+    mean = (_partials32(x, keep=keep) / N).astype(F32)
+    q, mn, mx = _partials32(x, mean, keep)
+    if mode == 2:
+        var = (q / ((N - 1.0) if n_for_style is None else n_for_style)).astype(F32) + F32(1e-5)
+        return mean.astype(np.float64), np.sqrt(var).astype(F32).astype(np.float64)
+    r = (F32(1) / np.sqrt((q / N).astype(F32) + F32(1e-8))).astype(F32)
+    return tuple(a.astype(np.float64) for a in (mean, r, ((mn - mean) * r).astype(F32), ((mx - mean) * r).astype(F32)))
+
+
+def _merged32(groups, frame_px, cross=True, short=False):
+    """chan_stats_group + chan_merge_k + chan_finish_k over groups of pixels [n_b, C] (whole frames of frame_px pixels).
+    cross=False: the merge without d^2 n_a n_b / n; short: n_a one frame short."""
+    acc, n_a = None, 0.0
+    for g in groups:
+        n_b = float(g.shape[0])
+        m32 = (_partials32(g) / n_b).astype(F32)
+        q, mn, mx = _partials32(g, m32)
+        mean_b = _partials32(g) / n_b
+        e = mean_b - m32.astype(np.float64)
+        M2_b = np.maximum(q - n_b * e * e, 0.0)
+        if acc is None:
+            acc = [mean_b, M2_b, mn.astype(np.float64), mx.astype(np.float64)]
+        else:
+            na = n_a - (frame_px if short else 0.0)
+            n, d = na + n_b, mean_b - acc[0]
+            acc[0] = acc[0] + d * (n_b / n)
+            acc[1] = acc[1] + M2_b + (d * d * (na * n_b / n) if cross else 0.0)
+            acc[2], acc[3] = np.minimum(acc[2], mn), np.maximum(acc[3], mx)
+        n_a += n_b
+    m = acc[0].astype(F32)
+    r = (F32(1) / np.sqrt((acc[1] / n_a).astype(F32) + F32(1e-8))).astype(F32)
+    return tuple(a.astype(np.float64) for a in (m, r, ((acc[2].astype(F32) - m) * r).astype(F32), ((acc[3].astype(F32) - m) * r).astype(F32)))
+
+
+def _fc32(w, name, t, smean):
+    """chan_stat_k's mean (mode 0) of t [n, 32] + fc_filter_k in float32."""
+    p = "Decoder.%s.FC." % name
+    vec = np.concatenate([(t.astype(np.float64).sum(axis=0) / t.shape[0]).astype(F32), np.asarray(smean, F32)])
+    return (w[p + "weight"].astype(F32) @ vec + w[p + "bias"].astype(F32)).astype(F32).reshape(32, 32)
+
+
+def test_prep_statistic_stand_ins_pass():
+    rng = np.random.default_rng(5)
+    for n in (1, 6, 254, 19008):
+        x = _lrelu_like(rng, n, 16)
+        ok, worst, ratio = PR.check_pstat(_two_pass32(x), PR.raw_stats(x), LR.K["pstat"])
+        assert ok, "two-pass statistic over %d pixels at %.2f of its bound (ratio %.2f)" % (n, worst, ratio)
+        if n > 1:
+            ok, worst, ratio = PR.check_pstat_style(_two_pass32(x, mode=2), PR.raw_stats(x), LR.K["pstat"])
+            assert ok, "style statistic over %d pixels at %.2f of its bound (ratio %.2f)" % (n, worst, ratio)
+    frames = [_lrelu_like(rng, 35, 16) + F32(0.3 * i) for i in range(5)]      # real mean differences between the groups
+    for sizes in ((1, 1, 1, 1, 1), (2, 2, 1), (3, 2), (5,)):
+        groups, i = [], 0
+        for k in sizes:
+            groups.append(np.concatenate(frames[i:i + k]))
+            i += k
+        ok, worst, ratio = PR.check_pstat(_merged32(groups, 35), PR.raw_stats(np.concatenate(frames)), LR.K["pstat"])
+        assert ok, "merged statistic over groups %s at %.2f of its bound (ratio %.2f)" % (sizes, worst, ratio)
+
+
+def test_prep_mean_and_fc_stand_in_passes_and_a_foreign_style_half_fails(weights):
+    rng = np.random.default_rng(6)
+    t = (rng.standard_normal((425, 32)) * 2.0 + rng.uniform(-1, 1, 32)).astype(F32)
+    smean = rng.standard_normal((6, 32)).astype(F32)
+    t64 = t.astype(np.float64)
+    for i, name in enumerate(LR.FILTER_NAMES):
+        ok, worst, ratio = PR.check_pred(_fc32(weights, name, t, smean[i]), weights, name, t64.mean(axis=0), np.abs(t64).mean(axis=0), smean[i], LR.K["ppred"])
+        assert ok, "%s stand-in at %.2f of its bound (ratio %.2f)" % (name, worst, ratio)
+        ok, worst, _ = PR.check_pred(_fc32(weights, name, t, smean[(i + 2) % 6]), weights, name, t64.mean(axis=0), np.abs(t64).mean(axis=0), smean[i],
+                                     LR.K["ppred"])
+        assert not ok, "%s with another filter's style half passes (worst %.2f)" % (name, worst)
+
+
+def test_prep_statistic_defects_fail():
+    rng = np.random.default_rng(7)
+    K = LR.K["pstat"]
+    x = _lrelu_like(rng, 270400, 4)
+    rs = PR.raw_stats(x)
+    assert PR.check_pstat(_two_pass32(x), rs, K)[0]
+    keep = np.ones(x.shape[0], bool)
+    keep[int(np.argmax(x[:, 0]))] = False
+    assert not PR.check_pstat(_two_pass32(x, keep=keep), rs, K)[0], "the maximum pixel left out passes"
+    # ... and a pixel that holds no extremum: the mean and the variance alone must see it
+    inner = int(np.argsort(x[:, 0])[x.shape[0] // 2])
+    keep = np.ones(x.shape[0], bool)
+    keep[inner] = False
+    assert not PR.check_pstat(_two_pass32(x, keep=keep), rs, K)[0], "one median pixel left out passes"
+    nblk = 1024
+    tail = x.shape[0] - nblk * (x.shape[0] // nblk)
+    assert tail == 64
+    keep = np.ones(x.shape[0], bool)
+    keep[-tail:] = False
+    assert not PR.check_pstat(_two_pass32(x, keep=keep), rs, K)[0], "the last block's tail left out passes"
+    for n in (6, 4096):
+        y = _lrelu_like(rng, n, 16)
+        assert PR.check_pstat_style(_two_pass32(y, mode=2), PR.raw_stats(y), K)[0]
+        assert not PR.check_pstat_style(_two_pass32(y, mode=2, n_for_style=float(n)), PR.raw_stats(y), K)[0], "N instead of N - 1 at N = %d passes" % n
+    frames = [_lrelu_like(rng, 35, 16) + F32(0.3 * i) for i in range(5)]
+    groups = [np.concatenate(frames[0:2]), np.concatenate(frames[2:4]), frames[4]]
+    rs = PR.raw_stats(np.concatenate(frames))
+    assert PR.check_pstat(_merged32(groups, 35), rs, K)[0]
+    assert not PR.check_pstat(_merged32(groups, 35, cross=False), rs, K)[0], "a merge without the cross term passes"
+    assert not PR.check_pstat(_merged32(groups, 35, short=True), rs, K)[0], "n_a one frame short passes"
+
+
+class _FakeRun:
+    def __init__(self, taps, st, B):
+        self.taps, self.st, self.B = taps, st, B
+
+    def get(self, name, b=0):
+        return self.taps[name][b]
+
+
+def _filter_stage32(oracle, w, content, sty, smean, own_residual=False):
+    """Stops 0 and 1 of the resident pass on content [B, h, w, 512] in the oracle's float32 arithmetic, as the kernels run it."""
+    O = oracle
+    B = content.shape[0]
+    st = _empty_state(sty)
+    st["norm"][0] = _two_pass32(content.reshape(-1, 512))
+    mean, rstd = (a.astype(F32) for a in st["norm"][0][:2])
+    cn = ((content - mean) * rstd).astype(F32)
+    t32 = None
+    for g in (1, 2):
+        p = "Decoder.Filter1.F%d." % g
+        t32 = O.conv3x3(cn, w[p + "down_sample.0.weight"], w[p + "down_sample.0.bias"])
+        st["filt"]["Filter1.F%d" % g] = _fc32(w, "Filter1.F%d" % g, t32.reshape(-1, 32), smean[g - 1]).astype(np.float64)
+    F1, F2 = (st["filt"]["Filter1.F%d" % g].astype(F32) for g in (1, 2))
+    p = "Decoder.Filter1."
+    d, u = [], []
+    for b in range(B):
+        d.append(O.lrelu(O.apply_filter(O.conv3x3(cn[b:b + 1], w[p + "down_sample.0.weight"], w[p + "down_sample.0.bias"]), F1)))
+        u.append(O.conv3x3(O.apply_filter(d[b], F2), w[p + "upsample.0.weight"], w[p + "upsample.0.bias"])[0])
+    nxt = np.stack([cn[b] + u[b if own_residual else 0] for b in range(B)]).astype(F32)
+    taps = {"content": content, "cn": cn, "t32": t32, "d32": d[0], "u": u[0][None], "nxt": nxt}
+    return _FakeRun(taps, st, B)
+
+
+def test_prep_filter_stage_stand_in_passes_and_own_residuals_fail(pkg, weights, oracle):
+    """The stage functions themselves on a float32 stand-in of stops 0 and 1 (two images, 4 x 5 features), and quirk Q1: every
+    image given its own residual instead of frame 0's fails on image 1."""
+    prev = oracle.CONV_BACKEND
+    oracle.set_conv_backend("numpy")
+    try:
+        _, sty, smean = _style(oracle, pkg, weights)
+        rng = np.random.default_rng(8)
+        content = np.maximum(rng.standard_normal((2, 4, 5, 512)) + 0.3, 0).astype(F32) * rng.uniform(0.1, 2.0, 512).astype(F32)
+        # (the oracle's float32 numpy convolutions stand in for every kernel family at the direct family's K, as above)
+        k = dict(LR.K, f23=LR.K["direct"], gemm=LR.K["direct"])
+        c = PR.Ctx(weights, smean, (0, 1), k=k)
+        run = _filter_stage32(oracle, weights, content, sty, smean)
+        res = PR.STAGES[0](run, None, c) + PR.STAGES[1](run, None, c)
+        bad = {n: worst for n, _, ok, worst, _ in res if not ok}
+        assert not bad, bad
+        assert {n for n, *_ in res} >= {"norm0", "cn[1]", "t32[1]", "Filter1.F1", "Filter1.F2", "d32", "u", "nxt[0]", "nxt[1]"}
+        run = _filter_stage32(oracle, weights, content, sty, smean, own_residual=True)
+        bad = {n for n, _, ok, _, _ in PR.STAGES[1](run, None, c) if not ok}
+        assert bad == {"nxt[1]"}, bad
+    finally:
+        oracle.set_conv_backend(prev)
+
+
+def test_prep_blob_entries_and_bit_equality():
+    seen = [e for s in range(PR.N_STOPS) for e in PR.stage_entries(s)]
+    assert sorted(seen) == sorted([("norm", i) for i in range(11)] + [("filt", i) for i in range(6)]) and len(PR.STAGES) == 14
+    assert sum(n for _, n in PR.OFFSETS.values()) == 17536
+    a = np.arange(17536, dtype=F32)
+    b = a.copy()
+    o, _ = PR.OFFSETS["norm", 1]          # written at stop 4
+    b[o + 3] = np.nextafter(b[o + 3], F32(0))
+    assert PR.entries_bit_equal(a, b, 4) and not PR.entries_bit_equal(a, b, 5)
