@@ -379,7 +379,7 @@ int rrv_transfer_mask_batch(rrv_handle h, const uint8_t* frames_bgr, int B, int 
  * input forms as before.  rrv_get_preclamp_image works as after the float twin.
  * Not offered: tickets (rrv_transfer_async), the cached-feature entries (rrv_transfer_features[_batch]) and the one-frame
  * rrv_transfer_blend[_device] and rrv_transfer_frame_mode.  The rrv_image_desc entries still refuse RRV_LAY_I420 / RRV_LAY_NV12 as an INPUT
- * layout (RRV_E_ARG): 8-bit YUV frames enter through the rrv_*_from_yuv entries below. */
+ * layout (RRV_E_ARG): 8-bit YUV frames enter through the rrv_*_from_yuv entries below (or through an rrv_image_view, which names any layout). */
 enum {                         /* output-only values of rrv_image_desc.layout (and the in_layout of the _from_yuv entries), after RRV_LAY_HWC_BGR = 0 and RRV_LAY_CHW_RGB = 1 */
     RRV_LAY_I420 = 2,          /* planar Y, Cb, Cr (ffmpeg's yuv420p) */
     RRV_LAY_NV12 = 3           /* planar Y, then interleaved Cb Cr */
@@ -492,6 +492,57 @@ int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]);
  * arrived in; a frame in another form than the pending ones encodes those first. */
 int rrv_prepare_style_image_device(rrv_handle h, const void* d_style, rrv_image_desc in, int Hs, int Ws, int style_id, void* hip_stream);
 int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, int H, int W, void* hip_stream);
+
+/* Strided image views: pitched and windowed device frames, in and out (a hardware decoder's NV12 / P010 surface with a row pitch above the
+ * width, an aligned height and the chroma plane at its own offset; a crop x[:, :, y0:y1, x0:x1] of a torch tensor; a window of a larger canvas
+ * as the output; a grey tensor expanded to three channels; YV12 = I420 with the Cb and Cr offsets swapped).  A view is an image descriptor plus
+ * where the rows of its planes lie.  All strides and offsets are in ELEMENTS of desc.dtype, as torch's are (a float or uint16 row can never be
+ * misaligned); the base pointer is aligned to the element size.  Frame b starts b * frame_stride elements after the base pointer, row r of
+ * plane k plane_offset[k] + r * pitch[k] elements after the frame's start.  Planes per layout (row length in elements x rows), with
+ * CH = (H+1)/2 and CW = (W+1)/2 as everywhere:
+ *   RRV_LAY_HWC_BGR                   one: 3W x H
+ *   RRV_LAY_CHW_RGB                   R, G, B: W x H each
+ *   RRV_LAY_I420, RRV_LAY_I420_16     Y: W x H; Cb, Cr: CW x CH each
+ *   RRV_LAY_NV12, RRV_LAY_P016        Y: W x H; CbCr interleaved: 2 CW x CH
+ * Array entries of planes a layout does not have are ignored.  desc may name every layout on either side: a view entry reads the YUV layouts
+ * as well (the rrv_*_from_yuv_device entries are the view entries on contiguous views).  A view has no semantics of its own: a view call
+ * equals, bit for bit, the contiguous call on the same pixels, in every kernel mode.  Both ends of the hot path address every frame through a
+ * view (conv_first_k / conv_last_k); the contiguous entries build theirs with rrv_image_view_contiguous' formulas.
+ * rrv_image_view_contiguous fills *v with the strides of the contiguous form the other entries take for H x W frames; RRV_E_ARG for a
+ * descriptor no entry knows (or H, W < 1).  rrv_image_view_check says whether B frames of H x W (the frame as passed for an input, the
+ * delivered Ho x Wo frame for an output) can be addressed through *v: RRV_OK or RRV_E_ARG.  Neither needs a handle or a GPU.  The rules:
+ *   1  every stride and offset is >= 0 (and, so that no address arithmetic can wrap, a pitch is at most 2^31 - 1 elements, a plane
+ *      offset and the frame stride at most 2^40);
+ *   2  pitch[k] >= the row length of plane k;
+ *   3  dtype, layout and space are a combination the descriptor entries accept (uint8 and the integer YUV layouts in RRV_SP_PIXEL only;
+ *      RRV_DT_U16 with the two uint16 layouts only);
+ *   4  for an output only: the element extents [plane_offset[k], plane_offset[k] + (rows - 1) * pitch[k] + row length) of the planes of one
+ *      frame are pairwise disjoint, and for B > 1 frame_stride >= the end of the last extent.  Row-interleaved output planes are therefore
+ *      refused.  An input may overlap itself: three equal plane_offsets on RRV_LAY_CHW_RGB read a grey image as R = G = B, frame_stride 0
+ *      reads one frame B times.
+ * The view entries mirror rrv_transfer_image_device, _image_blend_device, _image_mask_device and rrv_add_image_device: the same flags, stream
+ * ordering, slots, limits (1..64 frames) and error codes; masks and weights stay contiguous.  The transfer entries run both checks before any
+ * GPU work; a refusal is RRV_E_ARG, rrv_last_error names the offending field (e.g. "out.pitch[1]") and the handle stays usable.  The ranges
+ * that d_in / in and d_out / out address must not overlap each other: this is NOT checked.  Frames of a batch above the launch group (16 for
+ * the frame-mode, blended and masked models) are found by frame_stride.  rrv_add_view_device compacts the frame into the pending sampled
+ * frames with one 2-D device copy per plane, in the order of hip_stream; everything after that is rrv_add_image_device. */
+typedef struct {
+    rrv_image_desc desc;       /* dtype, layout, space: every layout, the YUV ones included, on either side */
+    int64_t frame_stride;      /* elements of desc.dtype from frame b to frame b + 1 */
+    int64_t plane_offset[3];   /* elements from the frame's start to row 0 of plane k */
+    int64_t pitch[3];          /* elements from one row of plane k to the next */
+} rrv_image_view;
+int rrv_image_view_contiguous(rrv_image_desc d, int H, int W, rrv_image_view* v);
+int rrv_image_view_check(const rrv_image_view* v, int B, int H, int W, int output);
+int rrv_transfer_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W,
+                             void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_view_blend_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W,
+                                   const float* style_weight, int n_styles,
+                                   void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_view_mask_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W,
+                                  const float* d_mask, int n_styles, int mask_images,
+                                  void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_add_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int H, int W, void* hip_stream);
 
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */

@@ -21,10 +21,15 @@ class ImageDesc(C.Structure):
     _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("space", C.c_int)]
 
 
+class ImageView(C.Structure):
+    """rrv_image_view: an image descriptor plus where the rows of its planes lie, in elements of desc.dtype (torch's stride unit)."""
+    _fields_ = [("desc", ImageDesc), ("frame_stride", C.c_int64), ("plane_offset", C.c_int64 * 3), ("pitch", C.c_int64 * 3)]
+
+
 DT_U8, DT_F32 = 0, 1
 DT_U16 = 2                        # uint16 samples: only with LAY_I420_16 / LAY_P016
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
-LAY_I420, LAY_NV12 = 2, 3         # output only: 8-bit YUV 4:2:0, planar / semi-planar
+LAY_I420, LAY_NV12 = 2, 3         # 8-bit YUV 4:2:0, planar / semi-planar (an ImageDesc names them for an output; an ImageView on either side)
 LAY_I420_16, LAY_P016 = 8, 9      # 10 / 12 / 16-bit YUV 4:2:0 in uint16 samples: planar with the code in the low bits / semi-planar with it in the high bits
 YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
@@ -117,6 +122,16 @@ SYMBOLS = {
     "rrv_set_yuv16_input_matrix": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rrv_prepare_style_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_add_image_device": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_image_view_contiguous": (C.c_int, [ImageDesc, C.c_int, C.c_int, C.POINTER(ImageView)]),
+    "rrv_image_view_check": (C.c_int, [C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int]),
+    # strided views: (h, in, ImageView* in, B, H, W, [weights, n_styles | mask, n_styles, mask_images,] out, ImageView* out, flags, hip_stream)
+    "rrv_transfer_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(ImageView),
+                                           C.c_int, C.c_void_p]),
+    "rrv_transfer_view_blend_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),      # style_weight: host or device address
+    "rrv_transfer_view_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),       # d_mask: device address
+    "rrv_add_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

@@ -21,6 +21,9 @@
 //   and shifts it right by FirstP::yuv_shift (0 for the planar form, whose code sits in the low bits; 16 - d for P016, whose code sits in the
 //   high bits); conv_last_k<true, false, SP_PIXEL, true, true> clamps to LastP::yuv_hi = 2^d - 1, shifts the code left by LastP::yuv_shift
 //   and stores a uint16.  3 B/pixel each way.  The 8-bit instantiations are the code they were: the depth is a template argument.
+// Image views (rrv_image_view, the rrv_*_view_device entries): both kernels find a frame's rows through FirstP::v / LastP::v — frame stride, plane
+//   offsets and pitches in elements — so pitched surfaces, crops and canvas windows are read and written in place.  Packed frames are the view
+//   contiguous_view() builds; the values and their order are those of the packed code, only the addresses differ.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,8 +45,25 @@ inline size_t in_frame_bytes(int form, size_t H, size_t W) {                    
     return (in_yuv(form) ? yuv_frame_samples(H, W) : H * W * 3) * in_elem(form);
 }
 
+// Where the rows of a frame's planes lie (include/rerevst_hip.h rrv_image_view), in ELEMENTS of the frame's type: frame b starts fs * b elements
+// after the base pointer, row r of plane k at off[k] + r * pitch[k] from there.  Planes: HWC one (a row is 3 W elements); CHW R, G, B; I420 Y, Cb,
+// Cr; NV12 / P016 Y and the interleaved CbCr rows (2 CW elements).  Both kernels address every frame through one of these, the contiguous
+// frames of the plain entries included (contiguous_view): there is no second addressing path.
+// A pitch is below 2^31 elements (rrv_image_view_check refuses more), so row x pitch is one 32 x 32 -> 64-bit multiply, what row x W was.
+struct ImgView { int64_t fs, off[3]; uint32_t pitch[3]; };
+enum : int { VL_HWC = 0, VL_CHW = 1, VL_I420 = 2, VL_NV12 = 3 };      // plane structure of a layout (the 16-bit YUV layouts share the 8-bit ones')
+inline ImgView contiguous_view(int vl, int64_t H, int64_t W) {
+    const int64_t CH = (H + 1) / 2, CW = (W + 1) / 2;
+    switch (vl) {
+    case VL_HWC:  return ImgView{3 * H * W, {0, 0, 0}, {(uint32_t)(3 * W), 0, 0}};
+    case VL_CHW:  return ImgView{3 * H * W, {0, H * W, 2 * H * W}, {(uint32_t)W, (uint32_t)W, (uint32_t)W}};
+    case VL_I420: return ImgView{H * W + 2 * CH * CW, {0, H * W, H * W + CH * CW}, {(uint32_t)W, (uint32_t)CW, (uint32_t)CW}};
+    default:      return ImgView{H * W + 2 * CH * CW, {0, H * W, 0}, {(uint32_t)W, (uint32_t)(2 * CW), 0}};
+    }
+}
+
 struct FirstP {
-    const void* img;      // [B][H][W][3] BGR (IN_*_HWC) or [B][3][H][W] RGB (IN_*_CHW); uint8 or float32; IN_YUV_*: [B][H*W + 2*CH*CW] uint8 (uint16 for the two 16-bit forms)
+    const void* img;      // frame b's planes through `v`; IN_*_HWC BGR, IN_*_CHW RGB planes, uint8 or float32; IN_YUV_*: Y and chroma planes, uint8 (uint16 for the two 16-bit forms)
     int H, W, B;
     float* out;           // [B,H,W,64] ring layout
     const float* w;       // [27][64]: row (ky*3+kx)*3 + c_rgb
@@ -59,7 +79,9 @@ struct FirstP {
     int space;            // value space of a float32 input (SP_*); a uint8 input is PIXEL
     float yuv_n[12];      // IN_YUV_*: rows R, G, B; columns the coefficients of Y, Cb, Cr and an offset (rrv_set_yuv_input_matrix; the 16-bit forms: rrv_set_yuv16_input_matrix), by value
     int yuv_shift;        // IN_YUV_I420_16: 0; IN_YUV_P016: 16 - d, the code is sample >> yuv_shift (the low bits are ignored)
+    ImgView v;            // where the source frame's rows are, in elements of its type (the SOURCE frame: src_H x src_W in the pad geometry)
 };
+inline int in_view_layout(int form) { return form == IN_YUV_I420 || form == IN_YUV_I420_16 ? VL_I420 : in_yuv(form) ? VL_NV12 : (form & 1) ? VL_CHW : VL_HWC; }
 
 // symmetric (edge-inclusive) reflection of t into [0, n), any distance
 __device__ __forceinline__ int reflect_sym(int t, int n) {
@@ -92,26 +114,28 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
     const int b = bx / p.tiles_y;
     const int y0 = ty * 16, x0 = tx * 16;
     const int SH = p.src_H ? p.src_H : p.H, SW = p.src_H ? p.src_W : p.W;
-    const int CW = (SW + 1) >> 1;                                              // IN_YUV_*: the chroma planes are CH x CW
-    const size_t ysz = (size_t)SH * SW, csz = (size_t)((SH + 1) >> 1) * CW;
-    const T* img = YUV ? (const T*)p.img + (size_t)b * (ysz + 2 * csz) : (const T*)p.img + (size_t)b * SH * SW * 3;
-    struct SrcPx { size_t i; int y, x; };   // index in a plane of the source frame, and its row and column there
+    const T* img = (const T*)p.img + (size_t)b * (size_t)p.v.fs;
+    struct SrcPx { int y, x; };             // row and column of a pixel in the source frame
     auto src_px = [&](int y, int x) {       // padded-frame pixel -> the source pixel it reads
         if (p.src_H) { y = reflect_sym(y - p.pad_top, SH); x = reflect_sym(x - p.pad_left, SW); }
-        return SrcPx{(size_t)y * SW + x, y, x};
+        return SrcPx{y, x};
+    };
+    auto at = [&](int k, int row, int col) -> const T* {      // element `col` of row `row` of plane k
+        return img + ((size_t)p.v.off[k] + (size_t)((uint64_t)(uint32_t)row * p.v.pitch[k]) + (size_t)col);
     };
 
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
     auto norm_of = [&](const SrcPx& s, int c) -> float {      // source pixel -> normalised value of channel c, RGB order (framework.py:27,33-34)
         if constexpr (YUV) {
-            const size_t ci = (size_t)(s.y >> 1) * CW + (s.x >> 1);
+            const T* const pcb = NV12 ? at(1, s.y >> 1, (s.x >> 1) * 2) : at(1, s.y >> 1, s.x >> 1);
+            const T* const pcr = NV12 ? pcb + 1 : at(2, s.y >> 1, s.x >> 1);
             float yy, cb, cr;
             if constexpr (Y16) {
-                yy = (float)(img[s.i] >> p.yuv_shift);
-                cb = (float)(img[NV12 ? ysz + 2 * ci : ysz + ci] >> p.yuv_shift);
-                cr = (float)(img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci] >> p.yuv_shift);
+                yy = (float)(*at(0, s.y, s.x) >> p.yuv_shift);
+                cb = (float)(*pcb >> p.yuv_shift);
+                cr = (float)(*pcr >> p.yuv_shift);
             } else {
-                yy = (float)img[s.i]; cb = (float)img[NV12 ? ysz + 2 * ci : ysz + ci]; cr = (float)img[NV12 ? ysz + 2 * ci + 1 : ysz + csz + ci];
+                yy = (float)*at(0, s.y, s.x); cb = (float)*pcb; cr = (float)*pcr;
             }
             float v;
             {
@@ -122,8 +146,7 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
             }
             return (fminf(fmaxf(v, 0.f), 255.f) / 255.0f - mean[c]) / sd[c];      // as a float32 PIXEL value from here on
         }
-        const size_t i = s.i;
-        const float v = CHW ? (float)img[(size_t)c * SH * SW + i] : (float)img[i * 3 + 2 - c];
+        const float v = CHW ? (float)*at(c, s.y, s.x) : (float)*at(0, s.y, s.x * 3 + 2 - c);
         if constexpr (F32) {
             if (p.space == SP_NORM) return v;
             return ((p.space == SP_UNIT ? v : v / 255.0f) - mean[c]) / sd[c];
@@ -302,6 +325,7 @@ struct LastP {
     // the uint16 instantiation (conv_last_k<true, false, SP_PIXEL, true, true>): samples in place of bytes, yuv_m the 16-bit matrix
     float yuv_hi;         // 2^d - 1, the upper clamp bound of a d-bit code
     int yuv_shift;        // stored sample = code << yuv_shift: 0 planar (code in the low bits), 16 - d for P016 (code in the high bits)
+    ImgView v;            // where out_img's rows are, in elements of its type (the frame as delivered: OH x OW); out_pre stays contiguous
 };
 
 // GEMM first, taps second.  out[y][x][rgb] = sum_tap sum_c w[tap][c][rgb] in[y+ky][x+kx][c] is evaluated as
@@ -341,6 +365,25 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     const float bias[3] = {p.bias[0], p.bias[1], p.bias[2]};
     const int ntiles = p.tiles_x * p.tiles_y * p.B;
     const int OH = p.out_H ? p.out_H : p.H, OW = p.out_H ? p.out_W : p.W;
+    // Store addresses through the view, split as the loads are: a lane's pixel is (lrow, lcol) of EVERY tile, so its offset inside a tile's
+    // rows of each plane is computed once, here; a tile adds its own origin in those planes (tile_org below: uniform, scalar arithmetic).
+    // Planes: HWC one (3 elements per pixel); CHW R, G, B; YUV Y, then Cb | CbCr, then Cr — a chroma sample per 2 x 2 block.
+    const int lrow = 4 * wave + (lane >> 4), lcol = lane & 15;
+    constexpr int NPL = (YUV || CHW) ? 3 : 1;
+    int64_t lane_off[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const bool chroma = YUV && k > 0;
+        const int r = chroma ? lrow >> 1 : lrow, c = chroma ? (lcol >> 1) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? lcol : lcol * 3;
+        lane_off[k] = (int64_t)((uint64_t)(uint32_t)r * p.v.pitch[k]) + c;
+    }
+    // element index in out_img of (lrow, lcol) = (0, 0) of the tile at frame b, delivered-frame pixel (cy0, cx0) (both even; negative left
+    // and above the crop window, where no lane stores)
+    auto tile_org = [&](int k, int b, int cy0, int cx0) -> int64_t {
+        const bool chroma = YUV && k > 0;
+        const int r = chroma ? cy0 >> 1 : cy0, c = chroma ? (cx0 >> 1) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? cx0 : cx0 * 3;
+        return (int64_t)b * p.v.fs + p.v.off[k] + (int64_t)r * (int64_t)p.v.pitch[k] + c;
+    };
     // Tile walk.  Workgroup w runs on XCD w % 8 (observed dispatch order; locality only): each XCD gets ONE contiguous band of
     // the tile list, and the workgroups of an XCD take consecutive tiles of it — horizontally adjacent tiles run on the same
     // XCD at the same time and the rows above / below a round or two apart, so the 18 x 18 halos (1.27x the tensor) are
@@ -468,16 +511,15 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
                     // sample stores: the 16 lanes of a tile row write 16 contiguous Y samples, its 8 even lanes 8 (I420) or 16 (NV12)
                     // chroma samples; rows are OW samples and frames OH*OW + 2*CH*CW, in general not dword aligned
-                    const int CH = (OH + 1) >> 1, CW = (OW + 1) >> 1;
-                    const size_t ysz = (size_t)OH * OW, csz = (size_t)CH * CW;
-                    S* const fr = (S*)p.out_img + (size_t)b * (ysz + 2 * csz);
-                    fr[(size_t)cy * OW + cx] = sample(yuv[0]);
+                    S* const fr = (S*)p.out_img;
+                    const int cy0 = p.out_H ? y0 - p.crop_top : y0, cx0 = p.out_H ? x0 - p.crop_left : x0;      // the tile's origin in the delivered frame
+                    fr[tile_org(0, b, cy0, cx0) + lane_off[0]] = sample(yuv[0]);
                     if (!((row | col) & 1)) {       // the block's top left pixel (cy, cx even: crop and tile origins are even)
                         const S cb = sample(blk[0]);
                         const S cr = sample(blk[1]);
-                        const size_t ci = (size_t)(cy >> 1) * CW + (cx >> 1);
-                        if (p.yuv_nv12) { fr[ysz + 2 * ci] = cb; fr[ysz + 2 * ci + 1] = cr; }
-                        else { fr[ysz + ci] = cb; fr[ysz + csz + ci] = cr; }
+                        const int64_t a1 = tile_org(1, b, cy0, cx0) + lane_off[1];
+                        if (p.yuv_nv12) { fr[a1] = cb; fr[a1 + 1] = cr; }
+                        else { fr[a1] = cb; fr[tile_org(2, b, cy0, cx0) + lane_off[2]] = cr; }
                     }
                 }
             }
@@ -492,6 +534,7 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
                 else im[c] = fminf(fmaxf(o[c] * sd[c] + mean[c], 0.f), 1.f) * 255.f;
             }
             const int cy = p.out_H ? y - p.crop_top : y, cx = p.out_H ? xx - p.crop_left : xx;
+            const int cy0 = p.out_H ? y0 - p.crop_top : y0, cx0 = p.out_H ? x0 - p.crop_left : x0;      // the tile's origin in the delivered frame
             // RGB -> BGR; a lane stores its pixel's 12 bytes, a row of the tile leaves as one 192-byte burst (uint8: 3 bytes as one
             // short + one byte store, a 48-byte row; rows are OW * 3 bytes and in general not dword aligned — measured no slower
             // than the float form, into HBM and into page-locked host memory: profiles/u8_output_rate.json)
@@ -500,21 +543,22 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
             // multiple of 64 — DESIGN §4's misaligned line starts, up to half the write bandwidth of this 12 (3) B/pixel store.
             if constexpr (CHW) {
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
-                    const size_t plane = (size_t)OH * OW, at = (size_t)b * 3 * plane + (size_t)cy * OW + cx;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        if constexpr (U8) ((uint8_t*)p.out_img)[at + c * plane] = (uint8_t)__builtin_rintf(im[c]);
-                        else ((float*)p.out_img)[at + c * plane] = im[c];
+                        const int64_t at = tile_org(c, b, cy0, cx0) + lane_off[c];
+                        if constexpr (U8) ((uint8_t*)p.out_img)[at] = (uint8_t)__builtin_rintf(im[c]);
+                        else ((float*)p.out_img)[at] = im[c];
                     }
                 }
             } else if constexpr (U8) {
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
-                    uint8_t* q = (uint8_t*)p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3;
+                    uint8_t* q = (uint8_t*)p.out_img + (tile_org(0, b, cy0, cx0) + lane_off[0]);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) q[c] = (uint8_t)__builtin_rintf(im[2 - c]);      // im is in [0, 255] and never NaN
                 }
             } else {
-                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) *(f32x3*)((float*)p.out_img + (((size_t)b * OH + cy) * OW + cx) * 3) = f32x3{im[2], im[1], im[0]};
+                if (cy >= 0 && cy < OH && cx >= 0 && cx < OW)
+                    *(f32x3*)((float*)p.out_img + (tile_org(0, b, cy0, cx0) + lane_off[0])) = f32x3{im[2], im[1], im[0]};
             }
         }
     }

@@ -1017,8 +1017,9 @@ YuvLaunch yuv_launch_params(const YuvSide& s, bool input, bool wide, bool msb) {
 // in: the format of the images at d_img.  nb: images to encode (plans are grow-only, so a plan may hold room for more)
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
 // norm0_bstride != 0: image b's Decoder.norm[0] entry is norm0 + b * norm0_bstride (per-image state sets)
+// iv: where the rows of the source frames are (null: contiguous frames, whose view is built here — conv_first_k addresses every frame through one)
 int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
-                int norm0_bstride = 0) {
+                int norm0_bstride = 0, const ImgView* iv = nullptr) {
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
     RCHK(check_image_size(h, H, W, "encoder"));
@@ -1047,6 +1048,7 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
               in.space};
+    fp.v = iv ? *iv : contiguous_view(in_view_layout(inf), pc ? pc->src_H : H, pc ? pc->src_W : W);
     stamp(h, p8 ? &e.q11 : &e.c11, B);
     if (in_yuv(inf)) {
         const YuvLaunch y = yuv_launch_params(h->yuv_in, true, in_yuv16(inf), inf == IN_YUV_P016);
@@ -1097,7 +1099,14 @@ inline size_t yuv_sample_bytes(OutFmt f) { return yuv16_layout(f.yuv) ? sizeof(u
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 // How one launch sequence reads and writes its frames: both formats and, for the pad geometry, the source window (nullptr: plain frames)
-struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; };
+// iv, ov: the views of the frames as passed / as delivered (null: contiguous; run_encoder / run_last build that view)
+struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; const ImgView* iv = nullptr; const ImgView* ov = nullptr; };
+inline int out_view_layout(OutFmt f) { return f.yuv ? (f.yuv == RRV_LAY_I420 || f.yuv == RRV_LAY_I420_16 ? VL_I420 : VL_NV12) : f.chw ? VL_CHW : VL_HWC; }
+inline size_t out_view_elem(OutFmt f) { return f.yuv ? yuv_sample_bytes(f) : out_elem(f); }      // bytes per element of an output view
+inline ImgView img_view(const rrv_image_view& v) {
+    return ImgView{v.frame_stride, {v.plane_offset[0], v.plane_offset[1], v.plane_offset[2]},
+                   {(uint32_t)v.pitch[0], (uint32_t)v.pitch[1], (uint32_t)v.pitch[2]}};      // (a checked view: every pitch is below 2^31)
+}
 
 int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
@@ -1121,7 +1130,15 @@ struct Xfer {
     bool w_dev = false;             // BLEND: wts is in HBM, written by work the slot's stream is ordered behind
     InFmt in = IN_BGR8;             // format of the content frames (the descriptor and _from_yuv entries set it)
     const float* const* feats = nullptr;      // BLEND: one cached relu4_1 feature per image in place of the frames (d_in may then be null)
+    // Where the frames are (the view entries set these after rrv_image_view_check; null: contiguous frames).  run_xfer turns either into
+    // the ImgView both kernels address by, and walks the launch groups by its frame stride.
+    const rrv_image_view* vin = nullptr;
+    const rrv_image_view* vout = nullptr;
 
+    int OH() const { return pad ? H : H / 8 * 8; }            // the frame delivered
+    int OW() const { return pad ? W : W / 8 * 8; }
+    ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), H, W); }
+    ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW()); }
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
     size_t in_bytes() const { return in_frame_bytes(in.form, H, W); }                                              // per frame, in x.in
@@ -1299,16 +1316,18 @@ LastFn last_kernel(OutFmt f) {
 }
 
 // Decoder.slice1 + transform_back_image (conv_last_k) on a normalised slice2 output
-// fr: launch frames [fr->first, fr->first + fr->count) of the B only (every tensor and output format is one contiguous block per frame, of
-// fr->out_bytes in d_out); the pre-clamp tap's bookkeeping stays that of the whole batch
-struct FrameRange { int first, count; size_t out_bytes; };
-int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const Win* wl = nullptr,
+// fr: launch frames [fr->first, fr->first + fr->count) of the B only (every tensor is one contiguous block per frame, the output frames are
+// the view's frame stride apart); the pre-clamp tap's bookkeeping stays that of the whole batch
+// ov: where the rows of the delivered frames are (null: contiguous frames, whose view is built here)
+struct FrameRange { int first, count; };
+int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const ImgView* ov, const Win* wl = nullptr,
              const FrameRange* fr = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
+    lp.v = ov ? *ov : contiguous_view(out_view_layout(fmt), pc ? pc->src_H : H, pc ? pc->src_W : W);
     if (fr) {
         lp.in += (size_t)fr->first * (size_t)(H + 2) * (size_t)(W + 2) * 64;
-        lp.out_img = (char*)d_out + (size_t)fr->first * fr->out_bytes;
+        lp.out_img = (char*)d_out + (size_t)fr->first * (size_t)lp.v.fs * out_view_elem(fmt);
         if (pre) lp.out_pre = pre + (size_t)fr->first * H * W * 3;
         lp.B = fr->count;
     }
@@ -1380,7 +1399,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         }
         stamp(h, &e.c41, B);      // (pointwise stamped the one-image views: the debug taps see the tensor as written)
     } else {
-        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, (int)stride));
+        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, (int)stride, io.iv));
     }
     const Tens* cur = &e.c41;
     for (int f = 0; f < 3; ++f) {
@@ -1417,15 +1436,15 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     if (hk && hk->piece > 0 && hk->piece < B) {
         int i = 0;
         for (int b0 = 0; b0 < B; b0 += hk->piece, ++i) {
-            const FrameRange fr{b0, B - b0 < hk->piece ? B - b0 : hk->piece, hk->frame_bytes};
-            RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr, &fr));
+            const FrameRange fr{b0, B - b0 < hk->piece ? B - b0 : hk->piece};
+            RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr, &fr));
             const size_t off = (size_t)b0 * hk->frame_bytes;
             HIPCHK(hipEventRecord(hk->ev[i], h->stream));
             HIPCHK(hipStreamWaitEvent(hk->copy, hk->ev[i], 0));
             HIPCHK(hipMemcpyAsync(hk->h_dst + off, (const char*)d_out + off, (size_t)fr.count * hk->frame_bytes, hipMemcpyDeviceToHost, hk->copy));
         }
     } else {
-        RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, roi ? &wl : nullptr));
+        RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr));
     }
     if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
@@ -1614,7 +1633,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
         hipLaunchKernelGGL(frame_sets_init_k, dim3((RRV_STATE_FLOATS + 255) / 256, B), dim3(256), 0, h->stream, (const float*)S.blob, st, (int)RRV_STATE_FLOATS,
                            SL.norm[N_DEC1], 512);
     }));
-    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B));
+    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     const int hh = c41.H, ww = c41.W;
     // Decoder.norm[0] with each frame's statistics
@@ -1659,7 +1678,7 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     h->state_images = 0;
     // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
     RCHK(unfused_blocks(h, B, *cur, xs, a, o, st, PS, true, true, [&](const Tens& t, int n, int) { return chan_stats1_images(h, t, d, n); }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
     // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
     stamp(h, &e.c41, B);
     for (int k = 0; k < 3; ++k)
@@ -1731,7 +1750,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
     }
     LevelMask lm[4];
     for (int l = 0; l < 4; ++l) lm[l] = level_mask(d.lm[l], S, one_mask);
-    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B));
+    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     Tens fo[3], xs[3], a[3], o[3], dd = d.d, dpart = d.dpart;
     dd.B = dpart.B = B;
@@ -1770,7 +1789,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
                             const int l = t.H == d.lm[0].H ? 0 : t.H == d.lm[1].H ? 1 : 2;
                             return mask_norm(h, t, y, ms, S, n, res, sty, lm[l]);
                         }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc));
+    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
     stamp(h, &e.c41, B); stamp(h, &d.d, B);
     if (split > 1) stamp(h, &d.dpart, B);
     for (int k = 0; k < 3; ++k)
@@ -2271,6 +2290,74 @@ static DescErr parse_out(const rrv_image_desc& d, OutFmt* out) {
 static int refuse_layout(rrv_handle h, const char* what) {      // what: "<entry family>: in_layout" / "<entry family>: layout"
     return fail(h, RRV_E_ARG, std::string(what) + " must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
 }
+
+// ---- image views (include/rerevst_hip.h rrv_image_view): pure arithmetic, no handle and no GPU
+// rule 3: a dtype / layout / space combination the descriptor entries accept, on either side
+static bool view_desc_ok(const rrv_image_desc& d) {
+    if (d.layout == RRV_LAY_I420 || d.layout == RRV_LAY_NV12) return d.dtype == RRV_DT_U8 && d.space == RRV_SP_PIXEL;
+    if (yuv16_layout(d.layout)) return d.dtype == RRV_DT_U16 && d.space == RRV_SP_PIXEL;
+    if (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) return false;
+    if (d.dtype == RRV_DT_U8) return d.space == RRV_SP_PIXEL;
+    return d.dtype == RRV_DT_F32 && d.space >= RRV_SP_PIXEL && d.space <= RRV_SP_NORM;
+}
+static int view_layout(const rrv_image_desc& d) {
+    return d.layout == RRV_LAY_HWC_BGR ? VL_HWC : d.layout == RRV_LAY_CHW_RGB ? VL_CHW : d.layout == RRV_LAY_I420 || d.layout == RRV_LAY_I420_16 ? VL_I420 : VL_NV12;
+}
+// the planes of an H x W frame: how many, and the row length (elements) and row count of each
+struct Planes { int n; int64_t len[3], rows[3]; };
+static Planes view_planes(int vl, int64_t H, int64_t W) {
+    const int64_t CH = (H + 1) / 2, CW = (W + 1) / 2;
+    switch (vl) {
+    case VL_HWC:  return Planes{1, {3 * W, 0, 0}, {H, 0, 0}};
+    case VL_CHW:  return Planes{3, {W, W, W}, {H, H, H}};
+    case VL_I420: return Planes{3, {W, CW, CW}, {H, CH, CH}};
+    default:      return Planes{2, {W, 2 * CW, 0}, {H, CH, 0}};
+    }
+}
+// the contiguous view of a known descriptor; sizes are not judged here (the entries refuse a frame size in their own words)
+static rrv_image_view contiguous_of(const rrv_image_desc& d, int H, int W) {
+    const ImgView c = contiguous_view(view_layout(d), H > 0 ? H : 0, W > 0 ? W : 0);
+    return rrv_image_view{d, c.fs, {c.off[0], c.off[1], c.off[2]}, {(int64_t)c.pitch[0], (int64_t)c.pitch[1], (int64_t)c.pitch[2]}};
+}
+// the four rules; *why (optional) receives the offending field and what is wrong with it
+static bool view_check(const rrv_image_view& v, int B, int H, int W, bool output, std::string* why) {
+    auto no = [&](const std::string& field, const char* what) { if (why) *why = field + " " + what; return false; };
+    auto idx = [](const char* name, int k) { return std::string(name) + "[" + std::to_string(k) + "]"; };
+    if (!view_desc_ok(v.desc)) return no("desc", "is not a dtype, layout and space combination the descriptor entries accept");
+    if (B < 1 || H < 1 || W < 1) return no("B, H, W", "must be at least 1");
+    const Planes pl = view_planes(view_layout(v.desc), H, W);
+    // upper bounds, so that nothing below (and no address in the kernels) can wrap: a pitch fits 31 bits, an offset or a frame stride 40
+    const int64_t PITCH_MAX = INT32_MAX, SPAN_MAX = (int64_t)1 << 40;
+    if (v.frame_stride < 0) return no("frame_stride", "is negative");
+    if (v.frame_stride > SPAN_MAX) return no("frame_stride", "is above 2^40 elements");
+    for (int k = 0; k < pl.n; ++k) {
+        if (v.plane_offset[k] < 0) return no(idx("plane_offset", k), "is negative");
+        if (v.plane_offset[k] > SPAN_MAX) return no(idx("plane_offset", k), "is above 2^40 elements");
+        if (v.pitch[k] < 0) return no(idx("pitch", k), "is negative");
+        if (v.pitch[k] > PITCH_MAX) return no(idx("pitch", k), "is above 2^31 - 1 elements");
+        if (v.pitch[k] < pl.len[k]) return no(idx("pitch", k), "is shorter than a row of the plane");
+    }
+    if (!output) return true;
+    int64_t end[3], last = 0;
+    for (int k = 0; k < pl.n; ++k) {
+        end[k] = v.plane_offset[k] + (pl.rows[k] - 1) * v.pitch[k] + pl.len[k];
+        last = std::max(last, end[k]);
+    }
+    for (int k = 1; k < pl.n; ++k)
+        for (int j = 0; j < k; ++j)
+            if (v.plane_offset[k] < end[j] && v.plane_offset[j] < end[k]) return no(idx("plane_offset", k), "overlaps another plane of the output frame");
+    if (B > 1 && v.frame_stride < last) return no("frame_stride", "is smaller than the extent of one output frame");
+    return true;
+}
+int rrv_image_view_contiguous(rrv_image_desc d, int H, int W, rrv_image_view* v) {
+    if (!v || !view_desc_ok(d) || H < 1 || W < 1) return RRV_E_ARG;
+    *v = contiguous_of(d, H, W);
+    return RRV_OK;
+}
+int rrv_image_view_check(const rrv_image_view* v, int B, int H, int W, int output) {
+    return v && view_check(*v, B, H, W, output != 0, nullptr) ? RRV_OK : RRV_E_ARG;
+}
+
 // the handle's stream waits for what `stream` (NULL: the null stream) holds so far
 static int wait_for_stream(rrv_handle h, hipStream_t stream) {
     HIPCHK(hipEventRecord(h->slot_ev[0], stream));
@@ -2377,7 +2464,8 @@ static int flush_pending(rrv_handle h) {
 }
 
 // `frame` is in the format `in`.  device: in HBM, complete once `stream` has run what it holds now; else in host memory
-static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hipStream_t stream, int H, int W) {
+// view (device frames only): the frame's rows are where it says; they are compacted into the pending buffer, one 2-D copy per plane
+static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hipStream_t stream, int H, int W, const rrv_image_view* view = nullptr) {
     RCHK(check_frame(h, H, W, "add"));
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
@@ -2399,7 +2487,18 @@ static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hip
     }
     if (device) {      // in the order of the caller's stream, and consumed before the call returns
         RCHK(wait_for_stream(h, stream));
-        HIPCHK(hipMemcpyAsync(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyDeviceToDevice, h->stream));
+        uint8_t* const dst = h->pend_u8 + (size_t)h->pend_n * fb;
+        if (view) {
+            const int vl = in_view_layout(in.form);
+            const size_t el = in_elem(in.form);
+            const ImgView c = contiguous_view(vl, H, W);
+            const Planes pl = view_planes(vl, H, W);
+            for (int k = 0; k < pl.n; ++k)
+                HIPCHK(hipMemcpy2DAsync(dst + (size_t)c.off[k] * el, (size_t)c.pitch[k] * el, (const char*)frame + (size_t)view->plane_offset[k] * el,
+                                        (size_t)view->pitch[k] * el, (size_t)pl.len[k] * el, (size_t)pl.rows[k], hipMemcpyDeviceToDevice, h->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(dst, frame, fb, hipMemcpyDeviceToDevice, h->stream));
+        }
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
         HIPCHK(hipMemcpy(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyHostToDevice));
@@ -2418,6 +2517,21 @@ int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, i
     InFmt fmt;
     if (parse_in(in, &fmt) != DescErr::OK) return fail(h, RRV_E_ARG, "add: unknown dtype, layout or space (uint8 is PIXEL only)");
     return add_frame(h, d_frame, true, fmt, (hipStream_t)hip_stream, H, W);
+}
+
+// a view's descriptor as conv_first_k's form: every layout, the YUV ones included
+static bool parse_in_view(const rrv_image_desc& d, InFmt* in) {
+    if (!view_desc_ok(d)) return false;
+    return (yuv_layout(d.layout) ? parse_in_yuv(d.layout, in) : parse_in(d, in)) == DescErr::OK;
+}
+int rrv_add_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int H, int W, void* hip_stream) {
+    if (!h || !d_frame || !in) return RRV_E_ARG;
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "add_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    RCHK(check_frame(h, H, W, "add"));
+    std::string why;
+    if (!view_check(*in, 1, H, W, false, &why)) return fail(h, RRV_E_ARG, "add_view: in." + why);
+    return add_frame(h, d_frame, true, fmt, (hipStream_t)hip_stream, H, W, in);
 }
 
 // sampled frames as YUV 4:2:0 (conv_first_k<IN_YUV_*>); the input matrix (the uint16 forms: and the depth) is read when the deferred encoding runs
@@ -2648,9 +2762,10 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
         HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
     }
     const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
-    const size_t fb = x.in_bytes(), fo = x.out_bytes();
+    const ImgView vi = x.in_view(), vo = x.out_view();      // the one addressing path: contiguous frames are a view like any other
+    const size_t fb = (size_t)vi.fs * in_elem(x.in.form), fo = (size_t)vo.fs * out_view_elem(x.fmt);      // bytes from a frame to the next
     const PadCrop crop = x.pad_crop();
-    const FrameIO io{x.in, x.fmt, x.pad ? &crop : nullptr};
+    const FrameIO io{x.in, x.fmt, x.pad ? &crop : nullptr, &vi, &vo};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* const in = (const uint8_t*)d_in + (size_t)b0 * fb;
@@ -2740,20 +2855,32 @@ static int refuse_image(rrv_handle h, DescErr e, const char* side) {
     if (e == DescErr::YUV_TYPE) return fail(h, RRV_E_ARG, "transfer_image: an I420 / NV12 output is uint8, an I420_16 / P016 output uint16, in the PIXEL space");
     return fail(h, RRV_E_ARG, "transfer_image: unknown dtype, layout or space");
 }
-// x.in: the parsed input format (a descriptor's, or the in_layout's of the _from_yuv_device entries)
-static int image_run(rrv_handle h, const void* d_in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
-    if (const DescErr e = parse_out(out, &x.fmt); e != DescErr::OK) return refuse_image(h, e, "output");
+// The view entries: frames read through `in` (conv_first_k<IN>, every layout) and written through `out` (conv_last_k's store forms).  x: the model,
+// B, H, W and what the model blends with; the views, the flags and hip_stream supply the rest (RRV_TF_FRAME_MODE turns GLOBAL into FRAME).
+// who: the entry family in the refusal texts.  Everything is checked before any GPU work.
+static int view_run(rrv_handle h, const char* who, const void* d_in, const rrv_image_view* in, void* d_out, const rrv_image_view* out, int flags,
+                    void* hip_stream, Xfer x) {
+    if (!h) return RRV_E_ARG;
+    const std::string w = std::string(who) + ": ";
+    if (!in || !out) return fail(h, RRV_E_ARG, w + "null view");
+    if (!parse_in_view(in->desc, &x.in)) return fail(h, RRV_E_ARG, w + "in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!view_desc_ok(out->desc) || parse_out(out->desc, &x.fmt) != DescErr::OK)      // (a descriptor entry has refused its own in its own words)
+        return fail(h, RRV_E_ARG, w + "out.desc is not a dtype, layout and space combination the descriptor entries accept");
     if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM | (x.model == Model::BLEND ? RRV_TF_WEIGHTS_DEVICE : 0)))
-        return fail(h, RRV_E_ARG, "transfer_image: unknown flags");
-    if (!d_in || !d_out) return fail(h, RRV_E_ARG, "transfer_image: null buffer");
+        return fail(h, RRV_E_ARG, w + "unknown flags");
+    if (!d_in || !d_out) return fail(h, RRV_E_ARG, w + "null buffer");
     if (flags & RRV_TF_FRAME_MODE) {
-        if (x.model != Model::GLOBAL) return fail(h, RRV_E_ARG, "transfer_image: the frame-mode model has no blended state (style weights need the global model)");
+        if (x.model != Model::GLOBAL) return fail(h, RRV_E_ARG, w + "the frame-mode model has no blended state (style weights need the global model)");
         x.model = Model::FRAME;
     }
     x.pad = flags & RRV_TF_PAD_CROP;
     x.w_dev = flags & RRV_TF_WEIGHTS_DEVICE;
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x));
+    std::string why;
+    if (!view_check(*in, x.B, x.H, x.W, false, &why)) return fail(h, RRV_E_ARG, w + "in." + why);
+    if (!view_check(*out, x.B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);
+    x.vin = in; x.vout = out;
     struct Scope {      // hip_stream orders this call only
         rrv_handle h; hipStream_t cs; bool sync;
         ~Scope() { h->caller_stream = cs; h->caller_sync = sync; }
@@ -2761,17 +2888,41 @@ static int image_run(rrv_handle h, const void* d_in, void* d_out, rrv_image_desc
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
     return run_xfer(h, next_slot(h, x), d_in, d_out, x);
 }
-static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
+int rrv_transfer_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W, void* d_out, const rrv_image_view* out,
+                             int flags, void* hip_stream) {
+    return view_run(h, "transfer_view", d_in, in, d_out, out, flags, hip_stream, Xfer{Model::GLOBAL, B, H, W});
+}
+int rrv_transfer_view_blend_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W, const float* style_weight,
+                                   int n_styles, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    return view_run(h, "transfer_view", d_in, in, d_out, out, flags, hip_stream, Xfer{Model::BLEND, B, H, W, PLAIN, OUT_F32, n_styles, style_weight});
+}
+int rrv_transfer_view_mask_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W, const float* d_mask, int n_styles,
+                                  int mask_images, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    return view_run(h, "transfer_view", d_in, in, d_out, out, flags, hip_stream,
+                    Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, n_styles, /* wts */ nullptr, d_mask, mask_images});
+}
+// The descriptor entries are the view entries on contiguous views.  Each family refuses a descriptor or layout in its own words first (the
+// texts are part of what callers see); a frame size is judged by the shared checks, so the views are built for whatever size was passed.
+static int image_run(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
+    OutFmt f;
+    if (const DescErr e = parse_out(out, &f); e != DescErr::OK) return refuse_image(h, e, "output");
+    const bool pad = flags & RRV_TF_PAD_CROP;
+    const rrv_image_view vi = contiguous_of(in, x.H, x.W), vo = contiguous_of(out, pad ? x.H : x.H / 8 * 8, pad ? x.W : x.W / 8 * 8);
+    return view_run(h, "transfer_image", d_in, &vi, d_out, &vo, flags, hip_stream, x);
+}
+static int image_entry(rrv_handle h, const void* d_in, rrv_image_desc in, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
     if (!h) return RRV_E_ARG;
-    if (const DescErr e = parse_in(in, &x.in); e != DescErr::OK) return refuse_image(h, e, "input");
-    return image_run(h, d_in, d_out, out, flags, hip_stream, x);
+    InFmt f;
+    if (const DescErr e = parse_in(in, &f); e != DescErr::OK) return refuse_image(h, e, "input");
+    return image_run(h, d_in, in, d_out, out, flags, hip_stream, x);
 }
 // the same entries reading YUV 4:2:0 frames (conv_first_k<IN_YUV_*>): [B][H*W + 2*CH*CW] uint8 (uint16 for the two 16-bit layouts) in HBM
-static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, Xfer x) {
+static int from_yuv_device(rrv_handle h, const void* d_in, int in_layout, void* d_out, rrv_image_desc out, int flags, void* hip_stream, const Xfer& x) {
     if (!h) return RRV_E_ARG;
-    if (parse_in_yuv(in_layout, &x.in) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
+    InFmt f;
+    if (parse_in_yuv(in_layout, &f) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
-    return image_run(h, d_in, d_out, out, flags, hip_stream, x);
+    return image_run(h, d_in, rrv_image_desc{yuv16_layout(in_layout) ? RRV_DT_U16 : RRV_DT_U8, in_layout, RRV_SP_PIXEL}, d_out, out, flags, hip_stream, x);
 }
 int rrv_transfer_from_yuv_device(rrv_handle h, const void* d_in, int in_layout, int B, int H, int W, void* d_out, rrv_image_desc out, int flags,
                                  void* hip_stream) {

@@ -222,7 +222,8 @@ TENSOR_BATCH_MAX = 64        # images per rrv_transfer_image_device call; transf
 
 
 # what Stylization.transfer_tensor passes to the library, as tensor_io_args() works it out
-TensorIO = collections.namedtuple("TensorIO", "x in_desc out_desc out_shape out_dtype B H W batched")
+# in_view / out_view: the rrv_image_view of a strided x / out that is passed as it is (None: contiguous frames)
+TensorIO = collections.namedtuple("TensorIO", "x in_desc out_desc out_shape out_dtype B H W batched in_view out_view", defaults=(None, None))
 
 
 def _on_device(t, what, device):
@@ -243,6 +244,128 @@ def _image_desc(dtype, sp, lay, what):
     else:
         raise ValueError("%s must be torch.uint8 or torch.float32, got %s" % (what, dtype))
     return _lib.ImageDesc(dt, _LAYOUTS[lay] if lay in _LAYOUTS else YUV_FORMATS[lay].layout, _SPACES[sp])
+
+
+# ===== strided image views (rrv_image_view; include/rerevst_hip.h states the rules) =====
+_ELEM_BYTES = {_lib.DT_U8: 1, _lib.DT_F32: 4, _lib.DT_U16: 2}
+
+
+def _view_planes(layout, H, W):
+    """[(row length in elements, rows)] of the planes of an H x W frame in `layout` ("nhwc", "nchw" or a YUV format name)"""
+    CH, CW = (H + 1) // 2, (W + 1) // 2
+    if layout == "nhwc":
+        return [(3 * W, H)]
+    if layout == "nchw":
+        return [(W, H)] * 3
+    return [(W, H), (CW, CH), (CW, CH)] if YUV_FORMATS[layout].planar else [(W, H), (2 * CW, CH)]
+
+
+def _make_view(desc, frame_stride, plane_offset, pitch):
+    v = _lib.ImageView()
+    v.desc, v.frame_stride = desc, int(frame_stride)
+    for k in range(3):
+        v.plane_offset[k] = int(plane_offset[k]) if k < len(plane_offset) else 0
+        v.pitch[k] = int(pitch[k]) if k < len(pitch) else 0
+    return v
+
+
+def _contiguous_view(desc, H, W):
+    v = _lib.ImageView()
+    if _lib.load().rrv_image_view_contiguous(desc, int(H), int(W), C.byref(v)) != 0:
+        raise ValueError("no entry takes dtype %d, layout %d, space %d" % (desc.dtype, desc.layout, desc.space))
+    return v
+
+
+def image_view_of(t, layout):
+    """The rrv_image_view of a torch tensor [B,3,H,W] / [3,H,W] (layout "nchw") or [B,H,W,3] / [H,W,3] ("nhwc"), or None when its
+    strides do not fit one: pure stride arithmetic, CPU tensors included.  "nchw" fits when stride(-1) == 1, stride(-2) >= W and the
+    channel and batch strides are >= 0 (a channel stride of 0, from expand, reads a grey image as R = G = B); "nhwc" when
+    stride(-1) == 1, stride(-2) == 3 and stride(-3) >= 3 W.  Strides are in elements, as the library's are.  The descriptor carries
+    the layout, the tensor's dtype (uint8 / float32) and the "pixel" space; the caller sets the space."""
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r" % (layout,))
+    if t.dim() not in (3, 4):
+        return None
+    st, shp = tuple(t.stride()), tuple(t.shape)
+    if t.dim() == 3:
+        st, shp = (0,) + st, (1,) + shp
+    names = {"torch.uint8": _lib.DT_U8, "torch.float32": _lib.DT_F32}
+    desc = _lib.ImageDesc(names.get(str(t.dtype), -1), _LAYOUTS[layout], _lib.SP_PIXEL)
+    if layout == "nchw":
+        (_, ch, H, W), (sb, sc, sh, sw) = shp, st
+        if ch != 3 or sw != 1 or sh < W or sc < 0 or sb < 0:
+            return None
+        return _make_view(desc, sb, (0, sc, 2 * sc), (sh, sh, sh))
+    (_, H, W, ch), (sb, sh, sw, sc) = shp, st
+    if ch != 3 or sc != 1 or sw != 3 or sh < 3 * W or sb < 0:
+        return None
+    return _make_view(desc, sb, (0,), (sh,))
+
+
+def _strided_view(t, layout, desc):
+    """image_view_of for a tensor that is not contiguous, with the call's descriptor; None: the tensor is copied / refused as before"""
+    if not hasattr(t, "stride"):
+        return None
+    v = image_view_of(t, layout)
+    if v is not None:
+        v.desc = desc
+    return v
+
+
+class ImageView():
+    """A pitched surface in device memory: frames of `size` = (H, W) in `layout` — a YUV format name ("nv12", "p010", "i420", ..: a
+    hardware decoder's or encoder's surface with a row pitch above the width, an aligned height, the chroma plane at its own offset;
+    YV12 is "i420" with the two chroma offsets swapped) or "nchw" / "nhwc" — inside `storage`, a 1-D tensor of the format's dtype.
+    pitch: elements from one row of a plane to the next, one number per plane or one for all; plane_offset: elements from a frame's
+    start to row 0 of each plane (default: the planes follow each other, each rows x pitch long); frame_stride: elements from frame
+    b to frame b + 1; frames: how many.  All in elements of storage's dtype, as torch strides are.  Raises ValueError when the last
+    addressed element lies beyond storage.numel() or the library's rrv_image_view_check refuses the view (as an input; an output is
+    checked again when it is used as one: its planes must not overlap).  Stylization.transfer_tensor(view, out=view2, ..) and
+    add_tensor(view) take it; nothing is copied."""
+
+    def __init__(self, storage, layout, size, pitch, plane_offset=None, frame_stride=0, frames=1):
+        import torch
+        if layout not in _LAYOUTS and layout not in YUV_FORMATS:
+            raise ValueError("layout must be 'nchw', 'nhwc', %s, got %r" % (YUV_FORMAT_NAMES, layout))
+        H, W = (int(v) for v in size)
+        if H < 1 or W < 1 or int(frames) < 1:
+            raise ValueError("an ImageView holds at least one frame of at least 1 x 1 pixels")
+        if storage.dim() != 1 or not storage.is_contiguous():      # the view is addressed from data_ptr() in unit elements
+            raise ValueError("storage must be a contiguous 1-D tensor, got shape %s, strides %s" % (tuple(storage.shape), tuple(storage.stride())))
+        if layout in YUV_FORMATS:
+            if storage.dtype not in _yuv_torch_dtypes(layout):
+                raise ValueError("an %r surface is %s, got %s" % (layout, " or ".join(str(t) for t in _yuv_torch_dtypes(layout)), storage.dtype))
+            dt = _lib.DT_U8 if YUV_FORMATS[layout].bits == 8 else _lib.DT_U16
+            lay = YUV_FORMATS[layout].layout
+        else:
+            if storage.dtype not in (torch.uint8, torch.float32):
+                raise ValueError("storage must be torch.uint8 or torch.float32, got %s" % (storage.dtype,))
+            dt, lay = (_lib.DT_U8 if storage.dtype == torch.uint8 else _lib.DT_F32), _LAYOUTS[layout]
+        planes = _view_planes(layout, H, W)
+        pitch = [int(pitch)] * len(planes) if np.isscalar(pitch) else [int(v) for v in pitch]
+        if len(pitch) != len(planes):
+            raise ValueError("%r has %d planes, got %d pitches" % (layout, len(planes), len(pitch)))
+        if plane_offset is None:
+            plane_offset = [sum(pitch[j] * planes[j][1] for j in range(k)) for k in range(len(planes))]
+        plane_offset = [int(v) for v in plane_offset]
+        if len(plane_offset) != len(planes):
+            raise ValueError("%r has %d planes, got %d plane offsets" % (layout, len(planes), len(plane_offset)))
+        self.storage, self.layout, self.H, self.W, self.frames = storage, layout, H, W, int(frames)
+        self.view = _make_view(_lib.ImageDesc(dt, lay, _lib.SP_PIXEL), frame_stride, plane_offset, pitch)
+        if _lib.load().rrv_image_view_check(C.byref(self.view), self.frames, H, W, 0) != 0:
+            raise ValueError("the library refuses this view of %d %d x %d %r frames: pitch %r, plane_offset %r, frame_stride %d (every "
+                             "stride is >= 0 and a pitch at least a row long)" % (self.frames, H, W, layout, pitch, plane_offset, int(frame_stride)))
+        end = (self.frames - 1) * int(frame_stride) + max(o + (rows - 1) * p + ln for o, p, (ln, rows) in zip(plane_offset, pitch, planes))
+        if end > storage.numel():
+            raise ValueError("the view addresses %d elements, storage holds %d" % (end, storage.numel()))
+
+    def with_space(self, space, what):
+        """a copy of the library struct with the call's value space ('pixel' for uint8 and the YUV formats)"""
+        v = _lib.ImageView.from_buffer_copy(self.view)
+        if space != "pixel" and v.desc.dtype != _lib.DT_F32:
+            raise ValueError("%s: %s images are in the 'pixel' space (0..255), not %r" % (what, "integer", space))
+        v.desc.space = _SPACES[space]
+        return v
 
 
 def _check_out_layout(out_layout, out_space):
@@ -268,20 +391,45 @@ def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout,
     if out is not None:
         _on_device(out, "out", device)
         out_dtype = out.dtype
-        if tuple(out.shape) != out_shape or not out.is_contiguous():
+        if tuple(out.shape) != out_shape:
             raise ValueError("out must be a contiguous tensor of shape %s, got %s" % (out_shape, tuple(out.shape)))
     out_dtype = (_yuv_torch_dtypes(out_layout)[0] if yuv else torch.float32) if out_dtype is None else out_dtype
     if yuv and out_dtype not in _yuv_torch_dtypes(out_layout):
         raise ValueError("an %r output is %s, got %s" % (out_layout, " or ".join(str(t) for t in _yuv_torch_dtypes(out_layout)), out_dtype))
-    return _image_desc(out_dtype, out_space, out_layout, "out"), out_shape, out_dtype
+    desc = _image_desc(out_dtype, out_space, out_layout, "out")
+    view = None
+    if out is not None and not out.is_contiguous():      # a window of a larger canvas: written in place where its strides fit a view
+        view = None if yuv else _strided_view(out, out_layout, desc)
+        if view is None or _lib.load().rrv_image_view_check(C.byref(view), B, Ho, Wo, 1) != 0:
+            raise ValueError("out must be a contiguous tensor of shape %s, or one whose strides fit an image view (rows of unit "
+                             "element stride, planes and frames that do not overlap), got strides %s" % (out_shape, tuple(out.stride())))
+    return desc, out_shape, out_dtype, view
 
 
 def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
                    pad_crop=False, out=None):
+    """Check the arguments of Stylization.transfer_tensor against a handle on HIP device `device` (an ordinal) without touching the
+    GPU, and work out the call (_tensor_io states the checks).  A non-contiguous `x` is made contiguous: what the entries without a
+    view form (prepare_style_tensor) need.  tensor_view_io_args is the form that keeps a strided `x`."""
+    return _tensor_io(x, device, False, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout, out_layout=out_layout,
+                      pad_crop=pad_crop, out=out)
+
+
+def tensor_view_io_args(x, device, **kw):
+    """tensor_io_args for the callers that pass image views on (transfer_tensor, add_tensor): a non-contiguous `x` whose strides fit a
+    view (image_view_of) is returned as it is, in_view holding its strides; any other is made contiguous."""
+    return _tensor_io(x, device, True, **kw)
+
+
+def _tensor_io(x, device, views, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
+               pad_crop=False, out=None):
     """Check the arguments of Stylization.transfer_tensor against a handle on HIP device `device` (an ordinal) without
     touching the GPU, and work out the call: raises ValueError for a tensor that is not on that device, a channel count
     other than 3, a dtype the space does not allow (uint8 is "pixel" only; otherwise float32), an unknown space or
-    layout, or an `out` of the wrong shape, dtype, device or layout.  A non-contiguous `x` is made contiguous."""
+    layout, or an `out` of the wrong shape, dtype, device or layout.  A non-contiguous `x` is made contiguous — unless `views` is set
+    (the callers that pass views on: transfer_tensor and add_tensor) and its strides fit an image view (image_view_of): it is then
+    returned as it is, in_view holding its strides.  A non-contiguous `out` must fit a view the library accepts as an output
+    (out_view), else ValueError."""
     if space not in _SPACES:
         raise ValueError("space must be one of %s, got %r" % (sorted(_SPACES), space))
     if layout not in _LAYOUTS:
@@ -299,11 +447,14 @@ def tensor_io_args(x, device, *, space="pixel", out_space="pixel", out_dtype=Non
         raise ValueError("x must have 3 channels (%s), got shape %s" % (layout, tuple(x.shape)))
     if B < 1:
         raise ValueError("x holds no image")
-    out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
-    if not x.is_contiguous():
-        x = x.contiguous()
+    out_desc, out_shape, out_dtype, out_view = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
+    in_view = None
+    if not x.is_contiguous():      # a crop, a pitched or an expanded tensor goes by view, with no copy; anything else is copied
+        in_view = _strided_view(x, layout, in_desc) if views else None
+        if in_view is None:
+            x = x.contiguous()
     return TensorIO(x=x, in_desc=in_desc, out_desc=out_desc, out_shape=out_shape, out_dtype=out_dtype, B=B, H=H, W=W,
-                    batched=batched)
+                    batched=batched, in_view=in_view, out_view=out_view)
 
 
 def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=None, out_layout=None, pad_crop=False, out=None):
@@ -323,9 +474,9 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
             layout, H, W, " or ".join(str(t) for t in _yuv_torch_dtypes(layout)), fb, fb, x.dtype, tuple(x.shape)))
     batched = x.dim() == 2
     B = x.shape[0] if batched else 1
-    out_desc, out_shape, out_dtype = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
+    out_desc, out_shape, out_dtype, out_view = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
     return TensorIO(x=x if x.is_contiguous() else x.contiguous(), in_desc=YUV_FORMATS[layout].layout, out_desc=out_desc, out_shape=out_shape,
-                    out_dtype=out_dtype, B=B, H=H, W=W, batched=batched)
+                    out_dtype=out_dtype, B=B, H=H, W=W, batched=batched, out_view=out_view)
 
 
 # the per-frame style weights of a blended call, as style_weight_args() works them out: `host` a C-contiguous float32 [B][S]
@@ -416,6 +567,7 @@ _HOST_ENTRIES = {
     (True, False): ("rrv_transfer_from_yuv", "rrv_transfer_blend_from_yuv", "rrv_transfer_mask_from_yuv"),
 }
 _HOST_ENTRIES[True, True] = _HOST_ENTRIES[True, False]      # (the output descriptor of the _from_yuv entries names the format)
+_VIEW_ENTRIES = ("rrv_transfer_view_device", "rrv_transfer_view_blend_device", "rrv_transfer_view_mask_device")
 _TENSOR_ENTRIES = {      # by (input is YUV): the output descriptor names every output format
     False: ("rrv_transfer_image_device", "rrv_transfer_image_blend_device", "rrv_transfer_image_mask_device"),
     True: ("rrv_transfer_from_yuv_device", "rrv_transfer_blend_from_yuv_device", "rrv_transfer_mask_from_yuv_device"),
@@ -555,10 +707,11 @@ class Stylization():
             a = _u8_image(s, "style")
             self._chk(self._lib.rrv_prepare_style(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], sid))
 
-    def _device_image(self, x, space, layout):
-        """(tensor_io_args' result, current stream) of an input image tensor, by transfer_tensor's rules"""
+    def _device_image(self, x, space, layout, views=False):
+        """(tensor_io_args' result, current stream) of an input image tensor, by transfer_tensor's rules; views: a strided x that fits an
+        image view stays as it is (only for an entry that takes views: the style entries read packed images)"""
         import torch
-        a = tensor_io_args(x, self.device, space=space, layout=layout)
+        a = (tensor_view_io_args if views else tensor_io_args)(x, self.device, space=space, layout=layout)
         return a, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
 
     def prepare_style_tensor(self, style, *, space="pixel", layout="nchw"):
@@ -576,7 +729,22 @@ class Stylization():
         """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch
         [B,3,H,W] / [B,H,W,3] whose images are added in order."""
         self._global_only("add")
-        a, stream = self._device_image(x, space, layout)
+        if isinstance(x, ImageView):      # a surface (any layout, the YUV ones included): each frame is compacted on the GPU
+            import torch
+            _on_device(x.storage, "x.storage", self.device)
+            v = x.with_space(space, "x")
+            self._yuv_depth(x.layout, None)
+            stream = C.c_void_p(torch.cuda.current_stream(x.storage.device).cuda_stream)
+            step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
+            for b in range(x.frames):
+                self._chk(self._lib.rrv_add_view_device(self._h, C.c_void_p(x.storage.data_ptr() + b * step), C.byref(v), x.H, x.W, stream))
+            return
+        a, stream = self._device_image(x, space, layout, views=True)
+        if a.in_view is not None:         # a crop or a pitched tensor: no copy on the torch side
+            step = a.in_view.frame_stride * _ELEM_BYTES[a.in_view.desc.dtype]
+            for b in range(a.B):
+                self._chk(self._lib.rrv_add_view_device(self._h, C.c_void_p(a.x.data_ptr() + b * step), C.byref(a.in_view), a.H, a.W, stream))
+            return
         xb = a.x if a.batched else a.x.unsqueeze(0)
         for b in range(a.B):
             self._chk(self._lib.rrv_add_image_device(self._h, C.c_void_p(xb[b].data_ptr()), a.in_desc, a.H, a.W, stream))
@@ -766,49 +934,95 @@ class Stylization():
         to the same YUV layout, and may be "nchw" / "nhwc".
         layout / out_layout "i420p10" | "i420p12" | "i420p16" | "p010" | "p012" | "p016": 10 / 12 / 16-bit samples as in transfer_batch,
         in torch.uint16 tensors (this build's torch has the dtype; a torch.int16 tensor holding the same bits, x.view(torch.int16),
-        is taken too, and `out` may be one); a fresh output is torch.uint16."""
+        is taken too, and `out` may be one); a fresh output is torch.uint16.
+        Strided tensors: an x that is a crop x[:, :, y0:y1, x0:x1], has pitched rows or is a grey tensor expanded to three channels
+        (image_view_of says which strides fit) is read where it is, with no copy; any other non-contiguous x is copied.  `out` may be
+        a window of a larger canvas: it is written in place and returned (the result is `out`); nothing outside the window is touched.
+        x and / or out may be an ImageView: a pitched surface (a hardware decoder's NV12 / P010, an encoder's input) in a 1-D storage
+        tensor; layout, out_layout and size then come from the view, the result is the `out` view.  A strided call delivers the bits
+        of the contiguous call on the same pixels.  The memory x and out address must not overlap."""
         import torch
+        xv, ov = (t if isinstance(t, ImageView) else None for t in (x, out))
+        if xv is not None:
+            layout, dev_t = xv.layout, xv.storage
         yuv_in = layout in YUV_FORMATS
-        if yuv_in:
-            if space != "pixel":
-                raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
-            a = yuv_tensor_io_args(x, self.device, layout, size, out_space=out_space, out_dtype=out_dtype, out_layout=out_layout,
-                                   pad_crop=pad_crop, out=out)
+        if yuv_in and space != "pixel":
+            raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
+        if xv is not None:      # a surface: its frames are where the view says
+            _on_device(xv.storage, "x.storage", self.device)
+            B, H, W, batched, in_view = xv.frames, xv.H, xv.W, True, xv.with_space(space, "x")
+            in_desc, in_ptr = in_view.desc, xv.storage.data_ptr()
+            out_layout = (ov.layout if ov is not None else layout) if out_layout is None else out_layout
+            _check_out_layout(out_layout, out_space)
+            if ov is None:
+                out_desc, out_shape, out_dtype, out_view = _tensor_out_args(self.device, B, H, W, True, out_space, out_dtype, out_layout, pad_crop, out)
         else:
-            a = tensor_io_args(x, self.device, space=space, out_space=out_space, out_dtype=out_dtype, layout=layout,
-                               out_layout=out_layout, pad_crop=pad_crop, out=out)
-        plain_fn, blend_fn, mask_fn = (getattr(self._lib, name) for name in _TENSOR_ENTRIES[yuv_in])
+            if ov is not None and out_layout is None:
+                out_layout = ov.layout
+            kw = dict(out_space=out_space, out_dtype=ov.storage.dtype if ov is not None else out_dtype, out_layout=out_layout, pad_crop=pad_crop,
+                      out=None if ov is not None else out)
+            a = yuv_tensor_io_args(x, self.device, layout, size, **kw) if yuv_in else tensor_view_io_args(x, self.device, space=space, layout=layout, **kw)
+            B, H, W, batched, in_view, dev_t = a.B, a.H, a.W, a.batched, a.in_view, a.x
+            in_desc, in_ptr = a.in_desc, a.x.data_ptr()
+            out_desc, out_shape, out_dtype, out_view = a.out_desc, a.out_shape, a.out_dtype, a.out_view
+            if yuv_in:
+                out_layout = layout if out_layout is None else out_layout
+        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+        if ov is not None:      # written in place, through the view
+            _on_device(ov.storage, "out.storage", self.device)
+            if out_layout != ov.layout:
+                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
+            if (ov.frames, ov.H, ov.W) != (B, Ho, Wo):
+                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, Ho, Wo, ov.frames, ov.H, ov.W))
+            out_view = ov.with_space(out_space, "out")
+            if self._lib.rrv_image_view_check(C.byref(out_view), B, Ho, Wo, 1) != 0:
+                raise ValueError("out: the planes and frames of an output view must not overlap")
+            out_desc, out_ptr = out_view.desc, ov.storage.data_ptr()
+        else:
+            if out is None:
+                out = torch.empty(out_shape, dtype=out_dtype, device=dev_t.device)
+            out_ptr = out.data_ptr()
+        # The view entries serve a call with a strided side (the other side then goes as its contiguous view), the descriptor entries
+        # every other.  A batch above 64 steps its chunks by the frame stride in bytes: the view's, or a packed frame's.
+        strided = in_view is not None or out_view is not None
+        in_step = out_step = 0
+        if strided:
+            in_desc_s = in_desc if isinstance(in_desc, _lib.ImageDesc) else _lib.ImageDesc(
+                _lib.DT_U8 if YUV_FORMATS[layout].bits == 8 else _lib.DT_U16, in_desc, _lib.SP_PIXEL)
+            vi = in_view if in_view is not None else _contiguous_view(in_desc_s, H, W)
+            vo = out_view if out_view is not None else _contiguous_view(out_desc, Ho, Wo)
+            in_step, out_step = vi.frame_stride * _ELEM_BYTES[vi.desc.dtype], vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
+            in_arg, out_arg = C.byref(vi), C.byref(vo)
+        else:
+            in_arg, out_arg = in_desc, out_desc
+            if B > TENSOR_BATCH_MAX:      # both are contiguous tensors [B, ...]: a frame is a row of the batch
+                xb, ob = a.x if batched else a.x.unsqueeze(0), out if batched else out.unsqueeze(0)
+                in_step, out_step = xb.stride(0) * xb.element_size(), ob.stride(0) * ob.element_size()
+        plain_fn, blend_fn, mask_fn = (getattr(self._lib, name) for name in (_VIEW_ENTRIES if strided else _TENSOR_ENTRIES[yuv_in]))
         w = m = None
         if style_masks is not None:
-            m = style_mask_args(style_masks, style_weights, a.B, a.H, a.W, self.style_num, self.device, self.use_Global, tensors=True)
-            md = m.dev if m.dev is not None else torch.from_numpy(m.host).to(x.device, non_blocking=False)
-            md = md if m.images == 1 else md.reshape(a.B, -1)
+            m = style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global, tensors=True)
+            md = m.dev if m.dev is not None else torch.from_numpy(m.host).to(dev_t.device, non_blocking=False)
+            md = md if m.images == 1 else md.reshape(B, -1)
         if style_weights is not None:
-            w = style_weight_args(style_weights, a.B, self.style_num, self.device, self.use_Global, tensors=True)
-            wd = w.dev.unsqueeze(0).expand(a.B, w.S).contiguous() if w.broadcast else w.dev
-        if out is None:
-            out = torch.empty(a.out_shape, dtype=a.out_dtype, device=x.device)
-        xb = a.x if a.batched else a.x.unsqueeze(0)
-        ob = out if a.batched else out.unsqueeze(0)
+            w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global, tensors=True)
+            wd = w.dev.unsqueeze(0).expand(B, w.S).contiguous() if w.broadcast else w.dev
         flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
         self._yuv_depth(layout, layout if out_layout is None else out_layout)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        for b0 in range(0, a.B, TENSOR_BATCH_MAX):
-            nb = min(TENSOR_BATCH_MAX, a.B - b0)
+        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
+        for b0 in range(0, B, TENSOR_BATCH_MAX):
+            nb = min(TENSOR_BATCH_MAX, B - b0)
+            src, dst = C.c_void_p(in_ptr + b0 * in_step), C.c_void_p(out_ptr + b0 * out_step)
             if m is not None:
                 mp = md.data_ptr() if m.images == 1 else md[b0].data_ptr()
-                self._chk(mask_fn(
-                    self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb,
-                    C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
+                self._chk(mask_fn(self._h, src, in_arg, nb, H, W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb, dst, out_arg, flags, stream))
                 continue
             if w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
                 wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
-                self._chk(blend_fn(
-                    self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W, C.c_void_p(wp), w.S, C.c_void_p(ob[b0].data_ptr()),
-                    a.out_desc, flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
+                self._chk(blend_fn(self._h, src, in_arg, nb, H, W, C.c_void_p(wp), w.S, dst, out_arg,
+                                   flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
                 continue
-            self._chk(plain_fn(self._h, C.c_void_p(xb[b0].data_ptr()), a.in_desc, nb, a.H, a.W,
-                               C.c_void_p(ob[b0].data_ptr()), a.out_desc, flags, stream))
+            self._chk(plain_fn(self._h, src, in_arg, nb, H, W, dst, out_arg, flags, stream))
         return out
 
     def sync(self):
