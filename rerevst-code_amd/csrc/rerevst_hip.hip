@@ -520,7 +520,7 @@ const ConvKey CONV_TABLE[] = {
     CK(128, 1, 0, 0), CK(64, 1, 0, 0),
     // preparation pass: FilterPredictor 512->32 convs (raw outputs)
     CK(32, 9, 0, 0),
-    // direct-form encoder layers (rrv_set_direct_layers / RRV_DIRECT_LAYERS: accuracy where Decoder.norm[0] amplifies the encoder's rounding noise)
+    // direct-form encoder layers (RRV_DIRECT_LAYERS, read by rrv_create: accuracy where Decoder.norm[0] amplifies the encoder's rounding noise)
     CK(64, 9, 0, E_RELU | E_POOL), CK(128, 9, 0, E_RELU), CK(128, 9, 0, E_RELU | E_POOL), CK(128, 9, 0, E_RELU | E_NORM1),
 };
 

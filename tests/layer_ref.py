@@ -86,6 +86,15 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "m
 #   ppred    1.91 Filter3.F2 at 5 x 136 x 200 (a 64-term float32 sum in fc_filter_k; 1.0 .. 1.9)
 # The preparation-only instantiations stayed inside the existing figures: f23 2.44 (conv2 raw; the unsplit folded 512 -> 32 and
 # 32 -> 512 convolutions below it), ups 5.2 (the nine-product conv_upw<E_LRELU>), point 2.77.
+# and over every case of tests/test_gpu_instantiations.py (profiles/instantiations.txt), all inside the figures above, no K touched:
+#   a  blended frames 3 x 72 x 104, per-image conv4_1    f23 2.95 (c41 itself 1.7 .. 2.1), f43 7.13 (mode 2, the P8 chain inside the
+#                                                        grouped launch), ups 5.93, splitk 0.13, direct 28.0, stat 2.0 (blend_sets_k)
+#   b  cached features, per-image pointwise_k            point 1.92 (c41, the whole error over the pass's own magnitude), stat 2.03
+#   c  filter_down with per-image weights, 2 frames      split 4 (64 x 5136): splitk 0.215 frame mode, 0.166 blended; unsplit
+#                                                        (64 x 16400): d 0.48 / 0.57 as f23; c41 2.4 (f23) / 2.6 (point, frame mode)
+#   d  direct-form encoder (conv_mfma_k on 3 x 3 layers) gemm 5.74 (c21, image 4 of 5 x 40 x 56; per tap 3.2 .. 5.7: K = 2304 at most,
+#                                                        against 7.95 at K = 4608 in the preparation pass)
+# Every negative control (an image on its neighbour's state set) landed at 1.1e3 .. 3.9e4 of its bound.
 MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314,
             "pstat": 4.24, "gemm": 7.95, "ppred": 1.91}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
@@ -386,6 +395,8 @@ def family_of(kernel_name, split):
         return "ups"
     if k.startswith("conv_wino"):
         return "splitk" if split else "f23"
+    if k.startswith("conv_mfma<") and k[len("conv_mfma<"):].split(",")[1].strip() == "9":
+        return "gemm"       # the direct-form encoder (RRV_DIRECT_LAYERS): conv_mfma_k on a 3 x 3 layer, one float32 accumulator over 9 Cin
     if k.startswith(("conv_first", "conv_last", "conv_mfma")):
         return "direct"
     raise AssertionError("unknown kernel " + kernel_name)
@@ -582,6 +593,24 @@ def frame_checks(get, w, st, smean, fam, k=None, names=None):
         for y0, y1 in strips(got.shape[0]):
             plain("pre", got[y0:y1], *_last([o2], w, st, y0, y1), fam["pre"])
     return out
+
+
+def cached_c41(p3, w, st):
+    """c41 of a cached relu4_1 feature in a grouped launch (transfer_device with x.feats): conv4_1 + ReLU of the caching call's p3,
+    stored raw, then pointwise_k's Decoder.norm[0] of the image's OWN set, clamp((x - mean) rstd, lo, hi).  Two kernels in one, as
+    COMPOSITE: (v, mc, mp) with mc the convolution's magnitude times rstd and mp the normalisation's own magnitude."""
+    v, m = _enc_stage(19, ())([p3], w, st, 0, p3.shape[0])
+    n0 = st["norm"][0]
+    vn, mp = norm(v, m, n0)
+    return vn, m * n0[1], mp
+
+
+def check2(got, v, mc, mp, kc, kp):
+    """|got - v| <= 2^-24 (kc mc + kp mp + |v|) element-wise: (passes, worst fraction of the bound, worst |got - v| / (2^-24 mp))."""
+    err = np.abs(np.asarray(got, np.float64) - v)
+    bound = U * (kc * mc + kp * mp + np.abs(v))
+    return (bool(np.all(err <= bound)), float((err / np.maximum(bound, 1e-300)).max()),
+            float((err / np.maximum(U * mp, 1e-300)).max()))
 
 
 def blend_ref(blobs, wts):

@@ -113,6 +113,32 @@ class MaskedDecoder:
         return O.conv3x3(h, self._w("slice1.weight"), self._w("slice1.bias"))
 
 
+PATCHES = ((0, 2), (1,), (0, 1), (1, 2))      # the multistyle_s4 setup's frames that style k's state is computed over
+
+
+def distinct_states(s, padded):
+    """Four computed states of the multistyle_s4 setup (its handle `s` with style 0's state computed, closed here, and its padded
+    frames), style k's over the frames PATCHES[k]: style 0's is the setup's own.  Decoder.norm[0] holds statistics of the sampled
+    CONTENT alone, so states computed over one set of frames share it to the bit; a blend of such states holds the same value
+    there under any weights, masks or style order, and a check of c41 could then see no wrong image, mask or style index.  Every
+    pair of these differs there by more than 1e-4 relative (asserted)."""
+    import layer_ref as LR
+    feats = [s.generate_content_features(p) for p in padded]
+    blobs = [s.get_state(0).copy()]
+    for k in range(1, 4):
+        s.clean()
+        for i in PATCHES[k]:
+            s.add_patch(feats[i])
+        s.compute_norm()
+        blobs.append(s.get_state(k).copy())
+    s.close()
+    mean0 = [LR.parse_state(b)["norm"][0][0] for b in blobs]
+    for i in range(4):
+        for j in range(i):
+            assert np.abs(mean0[i] - mean0[j]).max() > 1e-4 * np.abs(mean0[i]).max(), (i, j)
+    return blobs
+
+
 def transfer(net, states, frame_bgr_u8, mask, return_preclamp=False):
     """frame [H][W][3] uint8 BGR (the network's input frame, already padded), mask [S][H][W] float32 -> the stylized frame
     [8*(H/8)][8*(W/8)][3] float32 BGR in 0..255, or the pre-clamp network output [1][..][..][3]"""

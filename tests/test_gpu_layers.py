@@ -127,7 +127,9 @@ def frames_for(pkg, B, H, W, seed=0):
     return np.stack([pkg.synth_frame(seed + i, H, W, kind="smooth") for i in range(B)])
 
 
-SHAPES = [(1, 8, 8), (1, 33, 31), (1, 77, 90), (1, 200, 136), (1, 264, 40), (1, 1032, 8), (5, 40, 56)]
+SHAPES = [(1, 8, 8), (1, 33, 31), (1, 77, 90), (1, 200, 136), (1, 264, 40), (1, 1032, 8), (5, 40, 56),
+          (1, 8, 1032),      # wide and thin: one tile row, 65 tile columns at full resolution
+          (1, 41, 37)]       # a level-0 width = 1 (mod 4): the P8 rows and their 16-byte pieces run along x
 ENC_F43 = ("p1", "c21", "p2", "c31", "c32", "c33", "p3")       # conv1_2 .. conv3_4
 DEC_F43 = ("o4", "o3", "o2")                                   # ResidualBlock.conv2
 

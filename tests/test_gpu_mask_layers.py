@@ -34,30 +34,11 @@ def _report():
     print("[layer ratios at] " + " ".join("%s=%s" % (f, RATIOS[f][1]) for f in LR.FAMILIES))
 
 
-PATCHES = ((0, 2), (1,), (0, 1), (1, 2))      # the setup's frames that style k's state is computed over
-
-
 @pytest.fixture(scope="module")
 def base(pkg, oracle, weights):
-    """Four computed states of the multistyle_s4 setup (its handle, styles and frames), style k's over the frames PATCHES[k]:
-    style 0's is the setup's own.  Decoder.norm[0] holds statistics of the sampled CONTENT alone, so states computed over one
-    set of frames share it to the bit, and with masks that sum to one mask_norm_k at c41 would compute the same value under any
-    mask and any style order: the c41 check could then see no wrong mask index.  Every pair of these differs there."""
-    s, padded = _golden_setup(pkg, oracle, weights, "multistyle_s4")[:2]
-    feats = [s.generate_content_features(p) for p in padded]
-    blobs = [s.get_state(0).copy()]
-    for k in range(1, 4):
-        s.clean()
-        for i in PATCHES[k]:
-            s.add_patch(feats[i])
-        s.compute_norm()
-        blobs.append(s.get_state(k).copy())
-    s.close()
-    mean0 = [LR.parse_state(b)["norm"][0][0] for b in blobs]
-    for i in range(4):
-        for j in range(i):
-            assert np.abs(mean0[i] - mean0[j]).max() > 1e-4 * np.abs(mean0[i]).max(), (i, j)
-    return blobs
+    """Four computed states that differ pairwise in Decoder.norm[0] (mask_ref.distinct_states: with masks that sum to one
+    mask_norm_k at c41 would otherwise compute the same value under any mask and any style order)."""
+    return mask_ref.distinct_states(*_golden_setup(pkg, oracle, weights, "multistyle_s4")[:2])
 
 
 def launch(pkg, weights, base, frames, M, S, pad_crop=False, host=False):

@@ -102,6 +102,80 @@ def test_image_given_another_images_state_fails(setup, weights):
     assert not ok, "image 1 on image 0's state passes the bound (worst %.2f)" % worst
 
 
+# ---- per-image Decoder.norm[0]: the references of tests/test_gpu_instantiations.py, cases a and b ---------------------------------
+
+PI_STATES = ("global_a", "global_b", "global_a_seed1")
+PI_WTS = np.array([[0.6, 0.3, 0.1], [0.1, 0.25, 0.65]], np.float32)      # image 0, image 1: every style active in both
+
+
+def _blend32(blobs, w):
+    """blend_sets_k's stand-in: float32 products summed in style order."""
+    out = np.zeros_like(blobs[0])
+    for s, b in enumerate(blobs):
+        out = (out + w[s] * b).astype(np.float32)
+    return out
+
+
+def _c41_per_image(oracle, weights, p3, st, defect=None):
+    """conv4_1 + ReLU, then Decoder.norm[0] of state st in float32: the fused epilogue (case a) and pointwise_k on a cached feature
+    (case b) are this arithmetic.  defect: 'raw' = the un-normalised feature, 'lo / hi exchanged'."""
+    y = oracle.relu(oracle.conv3x3(p3[None], weights["Encoder.slice.19.weight"], weights["Encoder.slice.19.bias"]))[0]
+    if defect == "raw":
+        return y
+    mean, rstd, lo, hi = (np.asarray(a, np.float32) for a in st["norm"][0])
+    if defect == "lo / hi exchanged":
+        lo, hi = hi, lo
+    return np.minimum(hi, np.maximum(lo, (y - mean) * rstd)).astype(np.float32)
+
+
+def _per_image_verdict(case, got, p3, weights, st):
+    if case == "a":         # the fused epilogue: the c41 stage on the image's blended set
+        return _verdict(got, "c41", [p3], weights, st)[:2]
+    return LR.check2(got, *LR.cached_c41(p3, weights, st), LR.K["direct"], LR.K["point"])[:2]      # (float32 numpy stands in at the direct family's K)
+
+
+@pytest.fixture(scope="module")
+def per_image(setup):
+    blobs = [np.asarray(load_golden(n)["state"], np.float32).reshape(-1) for n in PI_STATES]
+    sets = []
+    for w in PI_WTS:
+        blob = _blend32(blobs, w)
+        ref, mag = LR.blend_ref(blobs, w)
+        assert np.all(np.abs(blob - ref) <= LR.K["stat"] * LR.U * mag)
+        sets.append(LR.parse_state(blob))
+    m0, m1 = sets[0]["norm"][0][0], sets[1]["norm"][0][0]
+    assert np.abs(m0 - m1).max() > 1e-4 * np.abs(m0).max()        # the two images' sets differ where conv4_1 reads them
+    return sets
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_per_image_norm0_stand_in_passes(setup, per_image, weights, case):
+    oracle, acts, _ = setup
+    for b, st in enumerate(per_image):
+        p3 = acts[b][1]
+        ok, worst = _per_image_verdict(case, _c41_per_image(oracle, weights, p3, st), p3, weights, st)
+        assert ok, "case %s image %d: stand-in at %.2f of its bound" % (case, b, worst)
+
+
+@pytest.mark.parametrize("defect", ["neighbour's norm[0]", "lo / hi exchanged", "raw"])
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_per_image_norm0_defect_fails(setup, per_image, weights, case, defect):
+    """Image 1 normalised with image 0's blended entry (a per-image stride of 0), clamped with lo and hi exchanged, or left raw."""
+    oracle, acts, _ = setup
+    p3 = acts[1][1]
+    wrong = _c41_per_image(oracle, weights, p3, per_image[0 if defect.startswith("neighbour") else 1],
+                           defect=None if defect.startswith("neighbour") else defect)
+    ok, worst = _per_image_verdict(case, wrong, p3, weights, per_image[1])
+    assert not ok, "case %s: %s passes the bound (worst %.2f)" % (case, defect, worst)
+
+
+def test_nine_tap_conv_mfma_rows_are_the_gemm_family():
+    assert LR.family_of("conv_mfma<64,9,E_RELU | E_POOL>@64x64@40x56", False) == "gemm"
+    assert LR.family_of("conv_mfma<128,9,E_RELU | E_NORM1>@256x512@5x7", False) == "gemm"
+    assert LR.family_of("conv_mfma<128,1,0>@512x256@5x7", False) == "direct"
+    assert LR.family_of("conv_wino<E_RELU | E_NORM1>@256x512@5x7", False) == "f23"
+
+
 def test_k_within_four_times_the_measured_maximum():
     assert set(LR.MEASURED) == set(LR.K) == set(LR.FAMILIES) and {"stat", "point", "pred", "pstat", "gemm", "ppred"} <= set(LR.FAMILIES)
     for f in LR.FAMILIES:
