@@ -443,7 +443,7 @@ int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames_yuv, int in_l
 int rrv_add_from_yuv(rrv_handle h, const uint8_t* frame_yuv, int in_layout, int H, int W);
 int rrv_add_from_yuv_device(rrv_handle h, const void* d_frame_yuv, int in_layout, int H, int W, void* hip_stream);
 
-/* 10 / 12 / 16-bit YUV 4:2:0, in and out (HEVC Main10, AV1, VP9 profile 2, ProRes: a hardware decoder's P010, ffmpeg's yuv420p10le, a C420p10
+/* 10 / 12 / 16-bit YUV 4:2:0, in and out (HEVC Main10, AV1, VP9 profile 2: a hardware decoder's P010, ffmpeg's yuv420p10le, a C420p10
  * .y4m file): every entry above that takes RRV_LAY_I420 / RRV_LAY_NV12 also takes the two uint16 layouts below; there are no new transfer entries.
  * Frame layout.  Samples are uint16 in host byte order; CH = (H+1)/2, CW = (W+1)/2, frame_samples = H*W + 2*CH*CW; frame b starts at sample
  * b * frame_samples with nothing in between (frame_samples can be odd: a frame is only 2-byte aligned).
@@ -482,6 +482,57 @@ int rrv_yuv_input_matrix_depth(int standard, int full_range, int bits, float n[1
 int rrv_set_yuv16_matrix(rrv_handle h, const float m[12]);
 int rrv_set_yuv16_input_matrix(rrv_handle h, const float n[12]);
 
+/* YUV 4:2:2 and 4:4:4, 8 to 16 bits, in and out (ProRes 422 / 4444 and DNxHR, which are never 4:2:0; broadcast 4:2:2 10-bit contribution
+ * feeds; an SDI capture card's NV16 / P210; 4:4:4 screen content; a C422p10 .y4m file).  The chroma format is a flag OR-ed onto one of the four
+ * YUV layouts above; there are no new entry points, kernels or instantiations: the subsampling is a launch parameter of the YUV kernels.
+ *   RRV_LAY_422 = 0x10   chroma planes of CW = (W+1)/2 columns and CH = H rows: a chroma sample per horizontal pixel pair
+ *   RRV_LAY_444 = 0x20   chroma planes of CW = W columns and CH = H rows: a chroma sample per pixel
+ *   (no flag)            4:2:0 as above: CW = (W+1)/2, CH = (H+1)/2
+ *   layout            value  flag form                 samples  ffmpeg -pix_fmt
+ *   RRV_LAY_I422        18   RRV_LAY_I420    | 0x10    uint8    yuv422p
+ *   RRV_LAY_NV16        19   RRV_LAY_NV12    | 0x10    uint8    nv16
+ *   RRV_LAY_I422_16     24   RRV_LAY_I420_16 | 0x10    uint16   yuv422p10le / 12le / 16le   (Y4M C422p10 / p12 / p16)
+ *   RRV_LAY_P216        25   RRV_LAY_P016    | 0x10    uint16   p210le / p212le / p216le
+ *   RRV_LAY_I444        34   RRV_LAY_I420    | 0x20    uint8    yuv444p
+ *   RRV_LAY_NV24        35   RRV_LAY_NV12    | 0x20    uint8    nv24
+ *   RRV_LAY_I444_16     40   RRV_LAY_I420_16 | 0x20    uint16   yuv444p10le / 12le / 16le   (Y4M C444p10 / p12 / p16)
+ *   RRV_LAY_P416        41   RRV_LAY_P016    | 0x20    uint16   p410le / p412le / p416le
+ * Both flags together, or a flag on a base that is not one of the four YUV layouts (values 16, 17, 32, 33, 48 and above), is RRV_E_ARG, as
+ * 4..7, 10 and -1 stay.
+ * Frame layout: frame_samples = H*W + 2*CH*CW with the CH, CW of the chroma format, the planes in the base layout's order ([Y][Cb][Cr], or
+ * [Y][CbCr interleaved: CH rows of CW pairs]), frame b at sample b * frame_samples, nothing in between.  Views: Y is W x H; a planar Cb or Cr
+ * plane CW x CH; the semi-planar CbCr plane 2 CW x CH (4:4:4: rows of 2W elements).
+ * Where: every place that takes one of the four 4:2:0 layouts takes these eight under the same rules — rrv_transfer_yuv,
+ * rrv_transfer_blend_batch_yuv, rrv_transfer_mask_batch_yuv; the `out` descriptor of the three rrv_transfer_image*_device entries; in_layout
+ * and `out` of the six rrv_*_from_yuv* entries; rrv_add_from_yuv[_device]; either side of the four rrv_*_view_device entries;
+ * rrv_image_view_contiguous and rrv_image_view_check.  The dtype, space, depth (rrv_set_yuv_depth), matrix, flag, sub-batch, host-I/O and
+ * stream rules are those of the base layout, and any mix of chroma format, depth and layout between input and output is allowed (NV12 in ->
+ * P210 out).  As the base layouts, the new ones stay refused as an rrv_image_desc INPUT.  The largest new frame, 4:4:4 in uint16, is 6 bytes
+ * per pixel, half of the float32 BGR frame the staging of the host entries is sized for anyway.
+ * Output arithmetic: c_k, the clamp, rint half to even and the << (16 - d) of the P forms are exactly those of the base layout.
+ *   4:2:2  chroma sample (i, j) = (l + r) * 0.5f of the unrounded, unclamped c_1 (then c_2) of pixels (i, 2j) and (i, 2j+1), evaluated in
+ *          float32 in that order with no contraction; for a last odd column r takes l's value.
+ *   4:4:4  the sample is c_k of its pixel.
+ *   4:2:0  ((tl + tr) + (bl + br)) * 0.25f, unchanged bit for bit.
+ * The pair mean sites chroma at the centre of its pixel pair (4:2:0: of its block), the C420jpeg / MPEG-1 siting the 4:2:0 forms chose; it
+ * is one consistent choice for every subsampled format, not the left-sited chroma of MPEG-2 / H.264 4:2:2.
+ * Input arithmetic: pixel (y, x) takes chroma sample (y >> sy, x >> sx), (sx, sy) = (1, 1) for 4:2:0, (1, 0) for 4:2:2 and (0, 0) for 4:4:4 —
+ * under RRV_TF_PAD_CROP after the reflection — and everything else is as for the base layout.
+ * The bit-identity statements of the 4:2:0 forms hold word for word: a YUV-output call equals this arithmetic applied to its float32 twin's
+ * output for the same frames and frames per call; a YUV-input call equals its float32 PIXEL BGR twin fed with the converted frame; a view call
+ * equals the contiguous call.
+ * Out of scope: packed forms (YUY2, UYVY, v210, Y210), 4:4:4 with alpha, mono, chroma sitings other than the box mean, 4:1:1 and 4:4:0. */
+enum { RRV_LAY_422 = 0x10,      /* on a YUV layout: 4:2:2, CW = (W+1)/2, CH = H */
+       RRV_LAY_444 = 0x20 };    /* on a YUV layout: 4:4:4, CW = W, CH = H */
+enum { RRV_LAY_I422    = RRV_LAY_I420    | RRV_LAY_422,     /* 18 */
+       RRV_LAY_NV16    = RRV_LAY_NV12    | RRV_LAY_422,     /* 19 */
+       RRV_LAY_I422_16 = RRV_LAY_I420_16 | RRV_LAY_422,     /* 24 */
+       RRV_LAY_P216    = RRV_LAY_P016    | RRV_LAY_422,     /* 25 */
+       RRV_LAY_I444    = RRV_LAY_I420    | RRV_LAY_444,     /* 34 */
+       RRV_LAY_NV24    = RRV_LAY_NV12    | RRV_LAY_444,     /* 35 */
+       RRV_LAY_I444_16 = RRV_LAY_I420_16 | RRV_LAY_444,     /* 40 */
+       RRV_LAY_P416    = RRV_LAY_P016    | RRV_LAY_444 };   /* 41 */
+
 /* rrv_prepare_style (test/framework.py:99-104; stylization.py:71-79) and rrv_add (test/framework.py:82-86) for images a torch
  * pipeline already holds in HBM: the rrv_image_desc rules of rrv_transfer_image_device (uint8 only in PIXEL space; any layout;
  * float32 in PIXEL / UNIT / NORM), one image [Hs][Ws] / [H][W] per call.  The style is read in colour, a sampled frame through
@@ -499,11 +550,11 @@ int rrv_add_image_device(rrv_handle h, const void* d_frame, rrv_image_desc in, i
  * where the rows of its planes lie.  All strides and offsets are in ELEMENTS of desc.dtype, as torch's are (a float or uint16 row can never be
  * misaligned); the base pointer is aligned to the element size.  Frame b starts b * frame_stride elements after the base pointer, row r of
  * plane k plane_offset[k] + r * pitch[k] elements after the frame's start.  Planes per layout (row length in elements x rows), with
- * CH = (H+1)/2 and CW = (W+1)/2 as everywhere:
+ * CH = (H+1)/2 and CW = (W+1)/2 as everywhere (with RRV_LAY_422 on the layout CH = H; with RRV_LAY_444 CH = H and CW = W):
  *   RRV_LAY_HWC_BGR                   one: 3W x H
  *   RRV_LAY_CHW_RGB                   R, G, B: W x H each
- *   RRV_LAY_I420, RRV_LAY_I420_16     Y: W x H; Cb, Cr: CW x CH each
- *   RRV_LAY_NV12, RRV_LAY_P016        Y: W x H; CbCr interleaved: 2 CW x CH
+ *   RRV_LAY_I420, RRV_LAY_I420_16     Y: W x H; Cb, Cr: CW x CH each            (and their 4:2:2 / 4:4:4 forms RRV_LAY_I422[_16], RRV_LAY_I444[_16])
+ *   RRV_LAY_NV12, RRV_LAY_P016        Y: W x H; CbCr interleaved: 2 CW x CH     (and RRV_LAY_NV16, RRV_LAY_P216, RRV_LAY_NV24, RRV_LAY_P416)
  * Array entries of planes a layout does not have are ignored.  desc may name every layout on either side: a view entry reads the YUV layouts
  * as well (the rrv_*_from_yuv_device entries are the view entries on contiguous views).  A view has no semantics of its own: a view call
  * equals, bit for bit, the contiguous call on the same pixels, in every kernel mode.  Both ends of the hot path address every frame through a

@@ -31,6 +31,10 @@ DT_U16 = 2                        # uint16 samples: only with LAY_I420_16 / LAY_
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
 LAY_I420, LAY_NV12 = 2, 3         # 8-bit YUV 4:2:0, planar / semi-planar (an ImageDesc names them for an output; an ImageView on either side)
 LAY_I420_16, LAY_P016 = 8, 9      # 10 / 12 / 16-bit YUV 4:2:0 in uint16 samples: planar with the code in the low bits / semi-planar with it in the high bits
+# chroma subsampling flags, OR-ed onto one of the four YUV layouts above: 4:2:2 (CW = (W+1)/2, CH = H) and 4:4:4 (CW = W, CH = H)
+LAY_422, LAY_444 = 0x10, 0x20
+LAY_I422, LAY_NV16, LAY_I422_16, LAY_P216 = LAY_I420 | LAY_422, LAY_NV12 | LAY_422, LAY_I420_16 | LAY_422, LAY_P016 | LAY_422      # 18, 19, 24, 25
+LAY_I444, LAY_NV24, LAY_I444_16, LAY_P416 = LAY_I420 | LAY_444, LAY_NV12 | LAY_444, LAY_I420_16 | LAY_444, LAY_P016 | LAY_444      # 34, 35, 40, 41
 YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8

@@ -21,6 +21,10 @@
 //   and shifts it right by FirstP::yuv_shift (0 for the planar form, whose code sits in the low bits; 16 - d for P016, whose code sits in the
 //   high bits); conv_last_k<true, false, SP_PIXEL, true, true> clamps to LastP::yuv_hi = 2^d - 1, shifts the code left by LastP::yuv_shift
 //   and stores a uint16.  3 B/pixel each way.  The 8-bit instantiations are the code they were: the depth is a template argument.
+// 4:2:2 / 4:4:4 (RRV_LAY_422 / RRV_LAY_444 on a YUV layout): no instantiation of their own — FirstP::csx / csy and LastP::csx / csy are the chroma
+//   shifts of the launch, (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4: a pixel reads chroma sample (y >> csy, x >> csx); the last kernel keeps the lane ^ 1
+//   step of its mean only where csx is set and the lane ^ 16 step only where csy is, and stores a chroma sample per 2^csy x 2^csx block.  2 / 3 samples
+//   per pixel each way.  The shifts are kernel arguments, uniform over the launch.
 // Image views (rrv_image_view, the rrv_*_view_device entries): both kernels find a frame's rows through FirstP::v / LastP::v — frame stride, plane
 //   offsets and pitches in elements — so pitched surfaces, crops and canvas windows are read and written in place.  Packed frames are the view
 //   contiguous_view() builds; the values and their order are those of the packed code, only the addresses differ.
@@ -40,9 +44,17 @@ enum : int { IN_U8_HWC = 0, IN_U8_CHW = 1, IN_F32_HWC = 2, IN_F32_CHW = 3, IN_YU
 inline bool in_yuv(int form) { return form >= IN_YUV_I420; }
 inline bool in_yuv16(int form) { return form >= IN_YUV_I420_16; }
 inline size_t in_elem(int form) { return in_yuv16(form) ? sizeof(uint16_t) : !in_yuv(form) && (form & 2) ? sizeof(float) : 1; }     // bytes per input value
-inline size_t yuv_frame_samples(size_t H, size_t W) { return H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2); }     // Y, Cb, Cr samples of one 4:2:0 frame
-inline size_t in_frame_bytes(int form, size_t H, size_t W) {                                      // bytes of one H x W input frame
-    return (in_yuv(form) ? yuv_frame_samples(H, W) : H * W * 3) * in_elem(form);
+// Chroma format of a YUV frame (include/rerevst_hip.h RRV_LAY_422 / RRV_LAY_444 on a YUV layout): pixel (y, x) belongs to chroma sample
+// (y >> sy, x >> sx), the planes are CH = ceil(H / 2^sy) rows of CW = ceil(W / 2^sx) samples.  The plane ORDER stays the layout's.
+enum : int { CS_420 = 0, CS_422 = 1, CS_444 = 2 };
+inline int chroma_sx(int cs) { return cs == CS_444 ? 0 : 1; }
+inline int chroma_sy(int cs) { return cs == CS_420 ? 1 : 0; }
+inline double yuv_samples_per_pixel(int cs) { return 1.0 + 2.0 / (double)(1 << (chroma_sx(cs) + chroma_sy(cs))); }      // 1.5, 2, 3
+inline size_t yuv_frame_samples(size_t H, size_t W, int cs = CS_420) {     // Y, Cb, Cr samples of one frame
+    return H * W + 2 * ((H + chroma_sy(cs)) >> chroma_sy(cs)) * ((W + chroma_sx(cs)) >> chroma_sx(cs));
+}
+inline size_t in_frame_bytes(int form, size_t H, size_t W, int cs = CS_420) {                     // bytes of one H x W input frame
+    return (in_yuv(form) ? yuv_frame_samples(H, W, cs) : H * W * 3) * in_elem(form);
 }
 
 // Where the rows of a frame's planes lie (include/rerevst_hip.h rrv_image_view), in ELEMENTS of the frame's type: frame b starts fs * b elements
@@ -52,8 +64,8 @@ inline size_t in_frame_bytes(int form, size_t H, size_t W) {                    
 // A pitch is below 2^31 elements (rrv_image_view_check refuses more), so row x pitch is one 32 x 32 -> 64-bit multiply, what row x W was.
 struct ImgView { int64_t fs, off[3]; uint32_t pitch[3]; };
 enum : int { VL_HWC = 0, VL_CHW = 1, VL_I420 = 2, VL_NV12 = 3 };      // plane structure of a layout (the 16-bit YUV layouts share the 8-bit ones')
-inline ImgView contiguous_view(int vl, int64_t H, int64_t W) {
-    const int64_t CH = (H + 1) / 2, CW = (W + 1) / 2;
+inline ImgView contiguous_view(int vl, int64_t H, int64_t W, int cs = CS_420) {
+    const int64_t CH = (H + chroma_sy(cs)) >> chroma_sy(cs), CW = (W + chroma_sx(cs)) >> chroma_sx(cs);
     switch (vl) {
     case VL_HWC:  return ImgView{3 * H * W, {0, 0, 0}, {(uint32_t)(3 * W), 0, 0}};
     case VL_CHW:  return ImgView{3 * H * W, {0, H * W, 2 * H * W}, {(uint32_t)W, (uint32_t)W, (uint32_t)W}};
@@ -79,6 +91,7 @@ struct FirstP {
     int space;            // value space of a float32 input (SP_*); a uint8 input is PIXEL
     float yuv_n[12];      // IN_YUV_*: rows R, G, B; columns the coefficients of Y, Cb, Cr and an offset (rrv_set_yuv_input_matrix; the 16-bit forms: rrv_set_yuv16_input_matrix), by value
     int yuv_shift;        // IN_YUV_I420_16: 0; IN_YUV_P016: 16 - d, the code is sample >> yuv_shift (the low bits are ignored)
+    int csx, csy;         // IN_YUV_*: the chroma shifts, (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4: pixel (y, x) reads chroma sample (y >> csy, x >> csx)
     ImgView v;            // where the source frame's rows are, in elements of its type (the SOURCE frame: src_H x src_W in the pad geometry)
 };
 inline int in_view_layout(int form) { return form == IN_YUV_I420 || form == IN_YUV_I420_16 ? VL_I420 : in_yuv(form) ? VL_NV12 : (form & 1) ? VL_CHW : VL_HWC; }
@@ -95,7 +108,7 @@ __device__ __forceinline__ int reflect_sym(int t, int n) {
 // ((float)px / 255 - mean) / std: a float PIXEL value v as v / 255 (bit-identical for integral v), a UNIT value x in place of
 // px / 255 (the same float where x is the correctly rounded px / 255), a NORM value n as it is.  Everything after that (grey
 // fold, border path, P8 stores, reflect-pad addressing) is shared.
-// IN_YUV_*: source pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1) — after the reflection of the pad geometry, which
+// IN_YUV_*: source pixel (y, x) takes Y[y][x] and the chroma sample (y >> csy, x >> csx) (4:2:0: (y >> 1, x >> 1)) — after the reflection of the pad geometry, which
 // therefore equals reflect-padding the converted frame, also for odd H / W — and v_k = ((n[k][0] Y + n[k][1] Cb) + n[k][2] Cr) + n[k][3],
 // every product and sum rounded to float32 (no contraction), px_k = min(max(v_k, 0), 255), not rounded to an integer: the float PIXEL
 // value.  Frame starts and chroma planes are in general not dword aligned: byte loads (the uint16 forms: 2-byte loads; a frame is an odd
@@ -127,8 +140,9 @@ __global__ __launch_bounds__(256) void conv_first_k(const FirstP p) {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
     auto norm_of = [&](const SrcPx& s, int c) -> float {      // source pixel -> normalised value of channel c, RGB order (framework.py:27,33-34)
         if constexpr (YUV) {
-            const T* const pcb = NV12 ? at(1, s.y >> 1, (s.x >> 1) * 2) : at(1, s.y >> 1, s.x >> 1);
-            const T* const pcr = NV12 ? pcb + 1 : at(2, s.y >> 1, s.x >> 1);
+            const int crow = s.y >> p.csy, ccol = s.x >> p.csx;      // (wave-uniform shifts: the chroma format is a launch parameter)
+            const T* const pcb = at(1, crow, ccol * (NV12 ? 2 : 1));
+            const T* const pcr = NV12 ? pcb + 1 : at(2, crow, ccol);
             float yy, cb, cr;
             if constexpr (Y16) {
                 yy = (float)(*at(0, s.y, s.x) >> p.yuv_shift);
@@ -325,6 +339,7 @@ struct LastP {
     // the uint16 instantiation (conv_last_k<true, false, SP_PIXEL, true, true>): samples in place of bytes, yuv_m the 16-bit matrix
     float yuv_hi;         // 2^d - 1, the upper clamp bound of a d-bit code
     int yuv_shift;        // stored sample = code << yuv_shift: 0 planar (code in the low bits), 16 - d for P016 (code in the high bits)
+    int csx, csy;         // the chroma shifts of the YUV forms: (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4; a chroma sample per 2^csy x 2^csx block
     ImgView v;            // where out_img's rows are, in elements of its type (the frame as delivered: OH x OW); out_pre stays contiguous
 };
 
@@ -348,6 +363,9 @@ struct LastP {
 // of the OUTPUT frame, rint(clamp(((tl + tr) + (bl + br)) * 0.25f, 0, 255)) of the unclamped c_1 / c_2, a pixel of the block outside
 // the frame (odd OH / OW, last row / column) replaced by its nearest one inside.  The crop origin and the tile origins are even, so
 // a block's four pixels are lanes l, l^1, l^16, l^17 of one wave.
+// Chroma format (p.csx, p.csy; wave-uniform): 4:2:2 keeps the lane ^ 1 step only, (l + r) * 0.5f per pixel pair of a row, a last odd column
+// paired with itself; 4:4:4 keeps neither, every pixel stores its own c_1, c_2.  Both shuffles are issued in every format (all 64 lanes
+// active, before the bounds branch); a format only chooses which sums enter the value, so 4:2:0 evaluates the expression above unchanged.
 // Y16 (with YUV): d-bit codes in uint16 samples, 10 / 12 / 16 bits: the clamp's upper bound is p.yuv_hi = 2^d - 1 and the stored sample is
 // code << p.yuv_shift.  The 16 lanes of a tile row write 32 contiguous bytes of Y.  Frames, the chroma planes (OH*OW samples in) and rows are
 // in general only 2-byte aligned, so Cb and Cr leave as two 2-byte stores in both layouts.
@@ -367,21 +385,21 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
     const int OH = p.out_H ? p.out_H : p.H, OW = p.out_H ? p.out_W : p.W;
     // Store addresses through the view, split as the loads are: a lane's pixel is (lrow, lcol) of EVERY tile, so its offset inside a tile's
     // rows of each plane is computed once, here; a tile adds its own origin in those planes (tile_org below: uniform, scalar arithmetic).
-    // Planes: HWC one (3 elements per pixel); CHW R, G, B; YUV Y, then Cb | CbCr, then Cr — a chroma sample per 2 x 2 block.
+    // Planes: HWC one (3 elements per pixel); CHW R, G, B; YUV Y, then Cb | CbCr, then Cr — a chroma sample per 2^csy x 2^csx block.
     const int lrow = 4 * wave + (lane >> 4), lcol = lane & 15;
     constexpr int NPL = (YUV || CHW) ? 3 : 1;
     int64_t lane_off[NPL];
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const bool chroma = YUV && k > 0;
-        const int r = chroma ? lrow >> 1 : lrow, c = chroma ? (lcol >> 1) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? lcol : lcol * 3;
+        const int r = chroma ? lrow >> p.csy : lrow, c = chroma ? (lcol >> p.csx) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? lcol : lcol * 3;
         lane_off[k] = (int64_t)((uint64_t)(uint32_t)r * p.v.pitch[k]) + c;
     }
     // element index in out_img of (lrow, lcol) = (0, 0) of the tile at frame b, delivered-frame pixel (cy0, cx0) (both even; negative left
     // and above the crop window, where no lane stores)
     auto tile_org = [&](int k, int b, int cy0, int cx0) -> int64_t {
         const bool chroma = YUV && k > 0;
-        const int r = chroma ? cy0 >> 1 : cy0, c = chroma ? (cx0 >> 1) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? cx0 : cx0 * 3;
+        const int r = chroma ? cy0 >> p.csy : cy0, c = chroma ? (cx0 >> p.csx) * (k == 1 && p.yuv_nv12 ? 2 : 1) : (YUV || CHW) ? cx0 : cx0 * 3;
         return (int64_t)b * p.v.fs + p.v.off[k] + (int64_t)r * (int64_t)p.v.pitch[k] + c;
     };
     // Tile walk.  Workgroup w runs on XCD w % 8 (observed dispatch order; locality only): each XCD gets ONE contiguous band of
@@ -494,27 +512,31 @@ __global__ __launch_bounds__(256) void conv_last_k(const LastP p) {
             for (int k = 0; k < 2; ++k) {
                 const float c = yuv[k + 1];
                 const float side = __shfl_xor(c, 1);
-                float rs;
-                {
+                float rs = c;
+                if (p.csx) {
 #pragma clang fp contract(off)
                     rs = c + (right_in ? side : c);
                 }
                 const float other = __shfl_xor(rs, 16);
-                {
+                if (p.csy) {             // 4:2:0 (csy implies csx)
 #pragma clang fp contract(off)
                     blk[k] = (rs + (below_in ? other : rs)) * 0.25f;
-                }
+                } else if (p.csx) {      // 4:2:2: the pair mean (l + r) * 0.5f
+#pragma clang fp contract(off)
+                    blk[k] = rs * 0.5f;
+                } else blk[k] = rs;      // 4:4:4: the pixel's own component
             }
             if (y < p.H && xx < p.W) {
                 typedef float f32x3 __attribute__((ext_vector_type(3)));
                 if (p.out_pre) *(f32x3*)(p.out_pre + (((size_t)b * p.H + y) * p.W + xx) * 3) = f32x3{o[0], o[1], o[2]};
                 if (cy >= 0 && cy < OH && cx >= 0 && cx < OW) {
                     // sample stores: the 16 lanes of a tile row write 16 contiguous Y samples, its 8 even lanes 8 (I420) or 16 (NV12)
-                    // chroma samples; rows are OW samples and frames OH*OW + 2*CH*CW, in general not dword aligned
+                    // chroma samples (4:4:4: all 16 lanes, 16 or 32); rows are OW samples and frames OH*OW + 2*CH*CW, in general not dword
+                    // aligned, so a semi-planar Cb, Cr pair leaves as two sample stores in every chroma format
                     S* const fr = (S*)p.out_img;
                     const int cy0 = p.out_H ? y0 - p.crop_top : y0, cx0 = p.out_H ? x0 - p.crop_left : x0;      // the tile's origin in the delivered frame
                     fr[tile_org(0, b, cy0, cx0) + lane_off[0]] = sample(yuv[0]);
-                    if (!((row | col) & 1)) {       // the block's top left pixel (cy, cx even: crop and tile origins are even)
+                    if (!((row & p.csy) | (col & p.csx))) {       // the block's top left pixel (cy, cx even: crop and tile origins are even)
                         const S cb = sample(blk[0]);
                         const S cr = sample(blk[1]);
                         const int64_t a1 = tile_org(1, b, cy0, cx0) + lane_off[1];

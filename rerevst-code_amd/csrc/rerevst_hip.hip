@@ -158,9 +158,9 @@ struct StyleState {
 
 // Format of the frames an encoder launch reads: form = IN_* (the conv_first_k instantiation), space = SP_* of a float32 form.  It travels
 // with the request (Xfer::in, the pending sampled frames), never on the handle.
-struct InFmt { int form, space; };
+struct InFmt { int form, space; int cs = CS_420; };      // cs: chroma format of a YUV form (CS_*), carried next to the layout
 constexpr InFmt IN_BGR8{IN_U8_HWC, SP_PIXEL};      // uint8 HWC BGR PIXEL: what every entry without a descriptor or an in_layout takes
-inline bool operator!=(InFmt a, InFmt b) { return a.form != b.form || a.space != b.space; }
+inline bool operator!=(InFmt a, InFmt b) { return a.form != b.form || a.space != b.space || a.cs != b.cs; }
 
 // The YUV conversion state of one direction (rrv_ctx::yuv_in: rows R, G, B x (Y, Cb, Cr, offset); yuv_out: rows Y, Cb, Cr x (R, G, B, offset)),
 // read when a launch is queued (yuv_launch_params): launches already queued keep what they were queued with.
@@ -1048,15 +1048,16 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
               in.space};
-    fp.v = iv ? *iv : contiguous_view(in_view_layout(inf), pc ? pc->src_H : H, pc ? pc->src_W : W);
+    fp.v = iv ? *iv : contiguous_view(in_view_layout(inf), pc ? pc->src_H : H, pc ? pc->src_W : W, in.cs);
     stamp(h, p8 ? &e.q11 : &e.c11, B);
     if (in_yuv(inf)) {
         const YuvLaunch y = yuv_launch_params(h->yuv_in, true, in_yuv16(inf), inf == IN_YUV_P016);
         memcpy(fp.yuv_n, y.m, sizeof fp.yuv_n); fp.yuv_shift = y.shift;
+        fp.csx = chroma_sx(in.cs); fp.csy = chroma_sy(in.cs);
     }
     static void (*const first_k[IN_FORMS])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>,
                                                       conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>, conv_first_k<IN_YUV_I420_16>, conv_first_k<IN_YUV_P016>};
-    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? 1.5 * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
+    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? yuv_samples_per_pixel(in.cs) * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
         hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
     }));
     ConvCall c;
@@ -1093,8 +1094,17 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
 // yuv = RRV_LAY_I420 / RRV_LAY_NV12 (else 0): 8-bit YUV 4:2:0 of the PIXEL values (conv_last_k's YUV form, the rrv_*_yuv entries); a
 // frame is then Xfer::out_bytes() bytes, not elements x element size.  yuv = RRV_LAY_I420_16 / RRV_LAY_P016: the same in uint16 samples, 10 / 12 /
 // 16-bit codes (conv_last_k's Y16 instantiation), two bytes per sample.
-struct OutFmt { bool u8, chw; int space; int yuv = 0; };
-constexpr bool yuv16_layout(int layout) { return layout == RRV_LAY_I420_16 || layout == RRV_LAY_P016; }
+// A YUV layout value is one of the four base layouts, alone (4:2:0) or with ONE of the chroma flags RRV_LAY_422 / RRV_LAY_444.  OutFmt::yuv holds
+// the BASE layout and OutFmt::cs the chroma format (CS_*); the kernels see the latter only as LastP::csx / csy and through the view.
+struct OutFmt { bool u8, chw; int space; int yuv = 0; int cs = CS_420; };
+constexpr int LAY_CHROMA = RRV_LAY_422 | RRV_LAY_444;
+constexpr int yuv_base(int layout) { return layout & ~LAY_CHROMA; }
+constexpr int yuv_chroma(int layout) { return (layout & RRV_LAY_444) ? CS_444 : (layout & RRV_LAY_422) ? CS_422 : CS_420; }      // of a layout yuv_layout() accepts
+constexpr bool yuv16_layout(int layout) { return yuv_base(layout) == RRV_LAY_I420_16 || yuv_base(layout) == RRV_LAY_P016; }  // of a layout yuv_layout() accepts, or a base
+constexpr bool yuv_layout(int layout) {      // both flags, a flag on a non-YUV base and every value that names nothing: false
+    return (layout & LAY_CHROMA) != LAY_CHROMA &&
+           (yuv_base(layout) == RRV_LAY_I420 || yuv_base(layout) == RRV_LAY_NV12 || yuv_base(layout) == RRV_LAY_I420_16 || yuv_base(layout) == RRV_LAY_P016);
+}
 inline size_t yuv_sample_bytes(OutFmt f) { return yuv16_layout(f.yuv) ? sizeof(uint16_t) : 1; }
 constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
@@ -1137,14 +1147,14 @@ struct Xfer {
 
     int OH() const { return pad ? H : H / 8 * 8; }            // the frame delivered
     int OW() const { return pad ? W : W / 8 * 8; }
-    ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), H, W); }
-    ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW()); }
+    ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), H, W, in.cs); }
+    ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW(), fmt.cs); }
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
-    size_t in_bytes() const { return in_frame_bytes(in.form, H, W); }                                              // per frame, in x.in
+    size_t in_bytes() const { return in_frame_bytes(in.form, H, W, in.cs); }                                              // per frame, in x.in
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
-        return fmt.yuv ? (pad ? yuv_frame_samples(H, W) : yuv_frame_samples(H / 8 * 8, W / 8 * 8)) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
+        return fmt.yuv ? yuv_frame_samples(OH(), OW(), fmt.cs) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
     }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
     PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
@@ -1324,7 +1334,7 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
              const FrameRange* fr = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
-    lp.v = ov ? *ov : contiguous_view(out_view_layout(fmt), pc ? pc->src_H : H, pc ? pc->src_W : W);
+    lp.v = ov ? *ov : contiguous_view(out_view_layout(fmt), pc ? pc->src_H : H, pc ? pc->src_W : W, fmt.cs);
     if (fr) {
         lp.in += (size_t)fr->first * (size_t)(H + 2) * (size_t)(W + 2) * 64;
         lp.out_img = (char*)d_out + (size_t)fr->first * (size_t)lp.v.fs * out_view_elem(fmt);
@@ -1337,10 +1347,11 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
         const YuvLaunch y = yuv_launch_params(h->yuv_out, false, yuv16_layout(fmt.yuv), fmt.yuv == RRV_LAY_P016);
         memcpy(lp.yuv_m, y.m, sizeof lp.yuv_m); lp.yuv_hi = y.hi; lp.yuv_shift = y.shift;
         lp.yuv_nv12 = fmt.yuv == RRV_LAY_NV12 || fmt.yuv == RRV_LAY_P016;
+        lp.csx = chroma_sx(fmt.cs); lp.csy = chroma_sy(fmt.cs);
     }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
-    return launch(h, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? 1.5 * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
+    return launch(h, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
         const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * LB), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
         hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
     });
@@ -2267,18 +2278,20 @@ static DescErr parse_in(const rrv_image_desc& d, InFmt* in) {
 }
 // a layout / in_layout of the _yuv / _from_yuv entries: 8-bit YUV 4:2:0 or uint16 samples, integer codes of the PIXEL values (the depth and the
 // matrix are read when the kernel is launched)
-static bool yuv_layout(int layout) { return layout == RRV_LAY_I420 || layout == RRV_LAY_NV12 || yuv16_layout(layout); }
+// The chroma format (RRV_LAY_422 / RRV_LAY_444 on the layout) travels next to the form / base layout, in InFmt::cs / OutFmt::cs.
 static DescErr parse_in_yuv(int layout, InFmt* in) {
     if (!yuv_layout(layout)) return DescErr::LAYOUT;
-    *in = InFmt{layout == RRV_LAY_I420 ? IN_YUV_I420 : layout == RRV_LAY_NV12 ? IN_YUV_NV12 : layout == RRV_LAY_I420_16 ? IN_YUV_I420_16 : IN_YUV_P016, SP_PIXEL};
+    const int base = yuv_base(layout);
+    *in = InFmt{base == RRV_LAY_I420 ? IN_YUV_I420 : base == RRV_LAY_NV12 ? IN_YUV_NV12 : base == RRV_LAY_I420_16 ? IN_YUV_I420_16 : IN_YUV_P016, SP_PIXEL,
+                yuv_chroma(layout)};
     return DescErr::OK;
 }
 static DescErr parse_out_yuv(int layout, OutFmt* out) {
     if (!yuv_layout(layout)) return DescErr::LAYOUT;
-    *out = OutFmt{true, false, SP_PIXEL, layout};
+    *out = OutFmt{true, false, SP_PIXEL, yuv_base(layout), yuv_chroma(layout)};
     return DescErr::OK;
 }
-// an output descriptor: HWC BGR / CHW RGB, or YUV 4:2:0 as uint8 I420 / NV12 or uint16 RRV_LAY_I420_16 / RRV_LAY_P016 in the PIXEL space
+// an output descriptor: HWC BGR / CHW RGB, or YUV as uint8 I420 / NV12 or uint16 RRV_LAY_I420_16 / RRV_LAY_P016 (each 4:2:0, or 4:2:2 / 4:4:4 by its flag) in the PIXEL space
 static DescErr parse_out(const rrv_image_desc& d, OutFmt* out) {
     const bool is_yuv = parse_out_yuv(d.layout, out) == DescErr::OK;
     if (!desc_known(d, is_yuv)) return DescErr::UNKNOWN;
@@ -2288,25 +2301,26 @@ static DescErr parse_out(const rrv_image_desc& d, OutFmt* out) {
     return DescErr::OK;
 }
 static int refuse_layout(rrv_handle h, const char* what) {      // what: "<entry family>: in_layout" / "<entry family>: layout"
-    return fail(h, RRV_E_ARG, std::string(what) + " must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016");
+    return fail(h, RRV_E_ARG, std::string(what) + " must be RRV_LAY_I420, RRV_LAY_NV12, RRV_LAY_I420_16 or RRV_LAY_P016, alone or with one of RRV_LAY_422 / RRV_LAY_444");
 }
 
 // ---- image views (include/rerevst_hip.h rrv_image_view): pure arithmetic, no handle and no GPU
 // rule 3: a dtype / layout / space combination the descriptor entries accept, on either side
 static bool view_desc_ok(const rrv_image_desc& d) {
-    if (d.layout == RRV_LAY_I420 || d.layout == RRV_LAY_NV12) return d.dtype == RRV_DT_U8 && d.space == RRV_SP_PIXEL;
-    if (yuv16_layout(d.layout)) return d.dtype == RRV_DT_U16 && d.space == RRV_SP_PIXEL;
+    if (yuv_layout(d.layout)) return d.dtype == (yuv16_layout(d.layout) ? RRV_DT_U16 : RRV_DT_U8) && d.space == RRV_SP_PIXEL;
     if (d.layout != RRV_LAY_HWC_BGR && d.layout != RRV_LAY_CHW_RGB) return false;
     if (d.dtype == RRV_DT_U8) return d.space == RRV_SP_PIXEL;
     return d.dtype == RRV_DT_F32 && d.space >= RRV_SP_PIXEL && d.space <= RRV_SP_NORM;
 }
 static int view_layout(const rrv_image_desc& d) {
-    return d.layout == RRV_LAY_HWC_BGR ? VL_HWC : d.layout == RRV_LAY_CHW_RGB ? VL_CHW : d.layout == RRV_LAY_I420 || d.layout == RRV_LAY_I420_16 ? VL_I420 : VL_NV12;
+    return d.layout == RRV_LAY_HWC_BGR ? VL_HWC : d.layout == RRV_LAY_CHW_RGB ? VL_CHW :
+           yuv_base(d.layout) == RRV_LAY_I420 || yuv_base(d.layout) == RRV_LAY_I420_16 ? VL_I420 : VL_NV12;
 }
+static int view_chroma(const rrv_image_desc& d) { return yuv_layout(d.layout) ? yuv_chroma(d.layout) : CS_420; }      // (of a known descriptor)
 // the planes of an H x W frame: how many, and the row length (elements) and row count of each
 struct Planes { int n; int64_t len[3], rows[3]; };
-static Planes view_planes(int vl, int64_t H, int64_t W) {
-    const int64_t CH = (H + 1) / 2, CW = (W + 1) / 2;
+static Planes view_planes(int vl, int64_t H, int64_t W, int cs) {      // cs: the chroma format of the two YUV structures (CS_*)
+    const int64_t CH = (H + chroma_sy(cs)) >> chroma_sy(cs), CW = (W + chroma_sx(cs)) >> chroma_sx(cs);
     switch (vl) {
     case VL_HWC:  return Planes{1, {3 * W, 0, 0}, {H, 0, 0}};
     case VL_CHW:  return Planes{3, {W, W, W}, {H, H, H}};
@@ -2316,7 +2330,7 @@ static Planes view_planes(int vl, int64_t H, int64_t W) {
 }
 // the contiguous view of a known descriptor; sizes are not judged here (the entries refuse a frame size in their own words)
 static rrv_image_view contiguous_of(const rrv_image_desc& d, int H, int W) {
-    const ImgView c = contiguous_view(view_layout(d), H > 0 ? H : 0, W > 0 ? W : 0);
+    const ImgView c = contiguous_view(view_layout(d), H > 0 ? H : 0, W > 0 ? W : 0, view_chroma(d));
     return rrv_image_view{d, c.fs, {c.off[0], c.off[1], c.off[2]}, {(int64_t)c.pitch[0], (int64_t)c.pitch[1], (int64_t)c.pitch[2]}};
 }
 // the four rules; *why (optional) receives the offending field and what is wrong with it
@@ -2325,7 +2339,7 @@ static bool view_check(const rrv_image_view& v, int B, int H, int W, bool output
     auto idx = [](const char* name, int k) { return std::string(name) + "[" + std::to_string(k) + "]"; };
     if (!view_desc_ok(v.desc)) return no("desc", "is not a dtype, layout and space combination the descriptor entries accept");
     if (B < 1 || H < 1 || W < 1) return no("B, H, W", "must be at least 1");
-    const Planes pl = view_planes(view_layout(v.desc), H, W);
+    const Planes pl = view_planes(view_layout(v.desc), H, W, view_chroma(v.desc));
     // upper bounds, so that nothing below (and no address in the kernels) can wrap: a pitch fits 31 bits, an offset or a frame stride 40
     const int64_t PITCH_MAX = INT32_MAX, SPAN_MAX = (int64_t)1 << 40;
     if (v.frame_stride < 0) return no("frame_stride", "is negative");
@@ -2443,7 +2457,7 @@ int rrv_clean(rrv_handle h) {
 static int flush_pending(rrv_handle h) {
     if (!h->pend_n) return RRV_OK;
     const int H = h->add_H, W = h->add_W;
-    const size_t fb = in_frame_bytes(h->pend_in.form, H, W);
+    const size_t fb = in_frame_bytes(h->pend_in.form, H, W, h->pend_in.cs);
     const int PB = h->pend_n < 8 ? h->pend_n : 8;        // one plan; the last group may use fewer of its images
     RCHK(enc_plan(h, h->enc_add, PB, H, W));
     for (int k0 = 0; k0 < h->pend_n; k0 += PB) {
@@ -2476,7 +2490,7 @@ static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hip
         RCHK(flush_pending(h));
     }
     h->pend_in = in;
-    const size_t fb = in_frame_bytes(in.form, H, W);
+    const size_t fb = in_frame_bytes(in.form, H, W, in.cs);
     if ((size_t)(h->pend_n + 1) * fb > h->pend_cap) {      // grow (x2) keeping the frames already collected
         const size_t cap = ((size_t)(h->pend_n + 1) * fb) * 2 > 16 * fb ? ((size_t)(h->pend_n + 1) * fb) * 2 : 16 * fb;
         uint8_t* nw = nullptr;
@@ -2491,8 +2505,8 @@ static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hip
         if (view) {
             const int vl = in_view_layout(in.form);
             const size_t el = in_elem(in.form);
-            const ImgView c = contiguous_view(vl, H, W);
-            const Planes pl = view_planes(vl, H, W);
+            const ImgView c = contiguous_view(vl, H, W, in.cs);
+            const Planes pl = view_planes(vl, H, W, in.cs);
             for (int k = 0; k < pl.n; ++k)
                 HIPCHK(hipMemcpy2DAsync(dst + (size_t)c.off[k] * el, (size_t)c.pitch[k] * el, (const char*)frame + (size_t)view->plane_offset[k] * el,
                                         (size_t)view->pitch[k] * el, (size_t)pl.len[k] * el, (size_t)pl.rows[k], hipMemcpyDeviceToDevice, h->stream));
@@ -3341,7 +3355,7 @@ static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, voi
     if (flags & ~known_flags) return fail(h, RRV_E_ARG, "transfer_from_yuv: unknown flags");
     if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
     if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
-        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016");
+        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
     if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
     x.pad = (flags & RRV_TF_PAD_CROP) != 0;
     return host_pipeline(h, frames, out, x);

@@ -148,24 +148,41 @@ def fps_fraction(fps):
     return f.numerator, f.denominator
 
 
+# chroma format -> (sx, sy): a chroma plane is ceil(height / 2^sy) rows of ceil(width / 2^sx) samples
+CHROMA_PLANES = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+
+
+def y4m_frame_samples(width, height, chroma="420"):
+    """samples of one planar frame: width*height luma and two chroma planes of the chroma format's size"""
+    sx, sy = CHROMA_PLANES[chroma]
+    return width * height + 2 * ((width + sx) >> sx) * ((height + sy) >> sy)
+
+
 class Y4MWriter:
     """Uncompressed YUV4MPEG2 stream, 8-bit 4:2:0 planar (I420) with the chroma sited at the block centres (C420jpeg): one header
     line, then `FRAME\n` and width*height + 2 * ceil(width/2)*ceil(height/2) bytes per frame.  `ffmpeg -i out.y4m` and every
     encoder's command line read it, from a file or a pipe.  full_range tags the header (XCOLORRANGE); the matrix is not part of
     the format (readers assume BT.601 for untagged 4:2:0).  bits = 10, 12, 16: C420p10 / C420p12 / C420p16, the same planes in
     little-endian 16-bit samples with the code in the low bits (what ffmpeg reads and writes for these tags: yuv420p10le ..), twice
-    the bytes per frame."""
+    the bytes per frame.  chroma = "422" / "444": C422 / C444 (above 8 bits C422p10 .. C444p16), planar frames whose chroma planes are
+    height x ceil(width/2) / height x width (ffmpeg yuv422p, yuv444p, yuv422p10le ..); the 4:2:0 tags are the ones above."""
 
-    def __init__(self, path, fps, width, height, full_range=False, bits=8):
+    def __init__(self, path, fps, width, height, full_range=False, bits=8, chroma="420"):
         if bits not in (8, 10, 12, 16):
             raise ValueError("bits must be 8, 10, 12 or 16, got %r" % (bits,))
-        self.path, self.w, self.h, self.bits = path, int(width), int(height), int(bits)
-        self.frame_bytes = (self.w * self.h + 2 * ((self.w + 1) // 2) * ((self.h + 1) // 2)) * (1 if bits == 8 else 2)
+        chroma = str(chroma)
+        if chroma not in CHROMA_PLANES:
+            raise ValueError("chroma must be '420', '422' or '444', got %r" % (chroma,))
+        self.path, self.w, self.h, self.bits, self.chroma = path, int(width), int(height), int(bits), chroma
+        self.frame_bytes = y4m_frame_samples(self.w, self.h, chroma) * (1 if bits == 8 else 2)
         self.frames = 0
         num, den = fps_fraction(fps)
+        if chroma == "420":
+            tag = b"420jpeg" if bits == 8 else b"420p%d" % bits
+        else:
+            tag = chroma.encode() + (b"" if bits == 8 else b"p%d" % bits)
         self.f = open(path, "wb")
-        self.f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s XCOLORRANGE=%s\n" % (self.w, self.h, num, den, b"420jpeg" if bits == 8 else b"420p%d" % bits,
-                                                                                 b"FULL" if full_range else b"LIMITED"))
+        self.f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s XCOLORRANGE=%s\n" % (self.w, self.h, num, den, tag, b"FULL" if full_range else b"LIMITED"))
 
     def append(self, data, shape):
         """One I420 frame (bytes, or a uint8 array; above 8 bits little-endian bytes or a uint16 array of codes) of `shape` =
@@ -176,7 +193,7 @@ class Y4MWriter:
             data = np.ascontiguousarray(data.astype("<u2", copy=False))
         data = memoryview(data).cast("B")
         if data.nbytes != self.frame_bytes:
-            raise ValueError("an I420 frame of %d x %d has %d bytes, got %d" % (self.h, self.w, self.frame_bytes, data.nbytes))
+            raise ValueError("an %s frame of %d x %d has %d bytes, got %d" % ("I" + self.chroma, self.h, self.w, self.frame_bytes, data.nbytes))
         self.f.write(b"FRAME\n")
         self.f.write(data)
         self.frames += 1
@@ -185,9 +202,10 @@ class Y4MWriter:
         self.f.close()
 
 
-def read_y4m(path, high_depth=False):
+def read_y4m(path, high_depth=False, chroma=False):
     """(header fields after the magic as a list of bytes, [frame bytes]) of a YUV4MPEG2 file with 8-bit 4:2:0 frames; high_depth:
-    also C420p10 / C420p12 / C420p16 files, whose frames are twice the bytes (little-endian 16-bit samples)."""
+    also C420p10 / C420p12 / C420p16 files, whose frames are twice the bytes (little-endian 16-bit samples); chroma: also C422 / C444
+    files (with high_depth their pNN forms), whose chroma planes are larger."""
     with open(path, "rb") as f:
         head = f.readline()
         if not head.startswith(b"YUV4MPEG2 ") or not head.endswith(b"\n"):
@@ -195,8 +213,12 @@ def read_y4m(path, high_depth=False):
         fields = head[:-1].split(b" ")[1:]
         dims = {k[:1]: int(k[1:]) for k in fields if k[:1] in (b"W", b"H")}
         w, h = dims[b"W"], dims[b"H"]
-        nbytes = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
-        if high_depth and any(k in Y4MReader.DEEP_COLORSPACES for k in (k[1:] for k in fields if k[:1] == b"C")):
+        tags = [k[1:] for k in fields if k[:1] == b"C"]
+        fmt = "420"
+        if chroma:
+            fmt = next((Y4MReader.CHROMA_COLORSPACES[k][0] for k in tags if k in Y4MReader.CHROMA_COLORSPACES and (high_depth or Y4MReader.CHROMA_COLORSPACES[k][1] == 8)), "420")
+        nbytes = y4m_frame_samples(w, h, fmt)
+        if high_depth and any(k in Y4MReader.DEEP_COLORSPACES or Y4MReader.CHROMA_COLORSPACES.get(k, ("", 8))[1] > 8 for k in tags):
             nbytes *= 2
         frames = []
         while True:
@@ -220,14 +242,20 @@ class Y4MReader:
     indexed once (FRAME lines may carry parameters: frame_params), so frames are read in any order, one or a run at a time, never
     the whole file.  A last frame shorter than frame_bytes is an error.
     high_depth=True also reads C420p10 / C420p12 / C420p16 (ffmpeg -pix_fmt yuv420p10le ..): little-endian 16-bit samples with the code
-    in the low bits, frame_bytes doubled, `bits` = 10 / 12 / 16 (8 otherwise) and read() a uint16 array of frame_bytes / 2 samples."""
+    in the low bits, frame_bytes doubled, `bits` = 10 / 12 / 16 (8 otherwise) and read() a uint16 array of frame_bytes / 2 samples.
+    chroma=True also reads C422 and C444 (ffmpeg -pix_fmt yuv422p / yuv444p) and, together with high_depth=True, C422p10 .. C444p16:
+    planar frames with chroma planes of height x ceil(width/2) / height x width; `chroma` then says "422" / "444" ("420" otherwise).
+    Without the two options those files are refused by name, as C444alpha and Cmono always are."""
 
     COLORSPACES = (b"420jpeg", b"420mpeg2", b"420paldv", b"420")
     DEEP_COLORSPACES = {b"420p10": 10, b"420p12": 12, b"420p16": 16}
+    CHROMA_COLORSPACES = {b"%s%s" % (c, b"p%d" % d if d > 8 else b""): (c.decode(), d) for c in (b"422", b"444") for d in (8, 10, 12, 16)}      # tag -> (chroma, bits)
 
-    def __init__(self, path, high_depth=False):
+    def __init__(self, path, high_depth=False, chroma=False):
         self.path = path
         self.high_depth = bool(high_depth)
+        self.any_chroma = bool(chroma)
+        self.chroma = "420"
         self.bits = 8
         self.f = open(path, "rb")
         try:
@@ -261,6 +289,8 @@ class Y4MReader:
                 self.colorspace = val.decode()
                 if self.high_depth and val in self.DEEP_COLORSPACES:
                     self.bits = self.DEEP_COLORSPACES[val]
+                elif self.any_chroma and val in self.CHROMA_COLORSPACES and (self.high_depth or self.CHROMA_COLORSPACES[val][1] == 8):
+                    self.chroma, self.bits = self.CHROMA_COLORSPACES[val]
                 elif val not in self.COLORSPACES:
                     raise ValueError("%s: colour space C%s is not supported (8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420paldv, C420)"
                                      % (path, val.decode()))
@@ -270,7 +300,7 @@ class Y4MReader:
             raise ValueError("%s: the header names no frame size" % path)
         if self.fps is not None and (self.fps[0] < 1 or self.fps[1] < 1):
             self.fps = None                         # F0:0 = unknown
-        self.frame_samples = self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
+        self.frame_samples = y4m_frame_samples(self.width, self.height, self.chroma)
         self.frame_bytes = self.frame_samples * (1 if self.bits == 8 else 2)
         size = os.fstat(f.fileno()).st_size
         self.offsets, self.frame_params = [], []
@@ -327,15 +357,32 @@ def is_y4m(video_path):
     return video_path is not None and video_path.lower().endswith(".y4m")
 
 
-def video_sink(video_path, fps, yuv=("bt601", False), quality=95, bits=8):
+def check_chroma(chroma, y4m):
+    """the chroma format of a video as "420" / "422" / "444"; ValueError for anything else, and for 4:2:2 / 4:4:4 without a .y4m video
+    to write it into (image files and the Motion-JPEG AVI have no such form)"""
+    chroma = str(chroma)
+    if chroma not in CHROMA_PLANES:
+        raise ValueError("chroma must be '420', '422' or '444', got %r" % (chroma,))
+    if chroma != "420" and not y4m:
+        raise ValueError("chroma %s belongs to a .y4m video: image files and the Motion-JPEG AVI cannot carry it" % chroma)
+    return chroma
+
+
+def y4m_format(chroma, bits):
+    """the planar format name (video.YUV_FORMATS) of a Y4M stream: "i420", "i422p10", "i444p12", .."""
+    return "i" + chroma + ("" if bits == 8 else "p%d" % bits)
+
+
+def video_sink(video_path, fps, yuv=("bt601", False), quality=95, bits=8, chroma="420"):
     """(encode(img) -> (bytes, shape) for the worker threads, open(shape) -> writer with append(bytes, shape) / release()) for a video
-    target: YUV4MPEG2 for *.y4m (video.bgr_to_yuv420 with the matrix of `yuv` = (standard, full_range), at `bits` bits), else Motion-JPEG AVI."""
+    target: YUV4MPEG2 for *.y4m (video.bgr_to_yuv420 with the matrix of `yuv` = (standard, full_range), at `bits` bits, in the chroma
+    format `chroma`), else Motion-JPEG AVI."""
     if is_y4m(video_path):
         import importlib
         video = importlib.import_module("rerevst-code_amd.video")
         m = video.yuv_matrix(*yuv, bits=bits)
-        return (lambda img: (video.bgr_to_yuv420(img, m, "i420", bits=bits).astype("<u2" if bits > 8 else np.uint8, copy=False).tobytes(), img.shape),
-                lambda shape: Y4MWriter(video_path, fps, shape[1], shape[0], full_range=yuv[1], bits=bits))
+        return (lambda img: (video.bgr_to_yuv420(img, m, "i420", bits=bits, chroma=chroma).astype("<u2" if bits > 8 else np.uint8, copy=False).tobytes(), img.shape),
+                lambda shape: Y4MWriter(video_path, fps, shape[1], shape[0], full_range=yuv[1], bits=bits, chroma=chroma))
     return (lambda img: (_encode_jpeg(img, quality), img.shape),
             lambda shape: MJPGWriter(video_path, fps, shape[1], shape[0], quality))
 
@@ -361,11 +408,11 @@ def _encode_jpeg(img, quality):
     return buf.getvalue()
 
 
-def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601", False), bits=8):
+def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601", False), bits=8, chroma="420"):
     """generate_real_video.py:175-186 as written there: re-read the result frames (sorted) and write the MJPG AVI (or the Y4M stream).
     Used when several ranks wrote the frames; decode + encode on the worker threads, the muxer appends in order."""
     writer = None
-    encode, open_writer = video_sink(video_path, fps, yuv, quality, bits=bits)
+    encode, open_writer = video_sink(video_path, fps, yuv, quality, bits=bits, chroma=chroma)
     for data, shape in pool.map(lambda p: encode(read_image_bgr(p)), paths):
         if writer is None:
             writer = open_writer(shape)
@@ -375,7 +422,8 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
-                  io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8):
+                  io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
+                  chroma="420"):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -389,7 +437,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     write_frames=False: no image files, only the video (one rank).  A .y4m target then takes the I420 bytes straight from a model
     that converts on the GPU (Stylization.yuv_output: transfer_frames(out_format="i420")), appended unchanged; in every other case
     the Y4M frames are video.bgr_to_yuv420 of the float frames.  bit_depth 10 / 12 / 16: a C420p10 / p12 / p16 stream
-    (out_format="i420p10" ..: the codes are roundings of the float32 result, not of its 8-bit form)."""
+    (out_format="i420p10" ..: the codes are roundings of the float32 result, not of its 8-bit form).  chroma "422" / "444": a C422 /
+    C444 stream (out_format "i422", "i444p10", ..); it belongs to a .y4m video_path, anything else is a ValueError."""
     import importlib
     import time
     from collections import deque
@@ -405,9 +454,10 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     nthreads = int(io_threads or default_io_threads())
     use_global = getattr(model, "use_Global", True)
     y4m = is_y4m(video_path)
+    chroma = check_chroma(chroma, y4m)
     bit_depth = int(bit_depth) if y4m else 8
-    yuv_fmt, yuv_dtype = ("i420", np.uint8) if bit_depth == 8 else ("i420p%d" % bit_depth, np.uint16)
-    encode, open_writer = video_sink(video_path, fps, yuv, bits=bit_depth) if video_path is not None else (None, None)
+    yuv_fmt, yuv_dtype = y4m_format(chroma, bit_depth), (np.uint8 if bit_depth == 8 else np.uint16)
+    encode, open_writer = video_sink(video_path, fps, yuv, bits=bit_depth, chroma=chroma) if video_path is not None else (None, None)
     t_start = time.perf_counter()
     with ThreadPoolExecutor(nthreads) as pool:
         # ---- once per video (generate_real_video.py:95-146); the sampled frames are decoded in parallel
@@ -481,7 +531,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             biggest = max(h * w for h, w in sizes)
             in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
             if direct:
-                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w) for h, w in sizes),), yuv_dtype) for _ in range(nbuf)]
+                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w, chroma=chroma) for h, w in sizes),), yuv_dtype) for _ in range(nbuf)]
             else:
                 out_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), out_dtype) for _ in range(nbuf)]
 
@@ -489,7 +539,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 (H, W), m = sizes[chunks[k][0] - lo], len(chunks[k])
                 src = in_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
                 if direct:
-                    return src, out_flat[k % nbuf][:m * video.yuv_frame_bytes(H, W)].reshape(m, -1)
+                    return src, out_flat[k % nbuf][:m * video.yuv_frame_bytes(H, W, chroma=chroma)].reshape(m, -1)
                 return src, out_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
 
             def append_chunk(yuv_frames, shape):  # the one video thread: a chunk's I420 frames, unchanged, in order
@@ -577,7 +627,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         if barrier is not None:
             barrier()
         if video_path is not None and world > 1 and rank == 0:
-            mux_video_from_files([os.path.join(out_dir, os.path.basename(p)) for p in sorted(frame_paths)], video_path, fps, pool, yuv=yuv, bits=bit_depth)
+            mux_video_from_files([os.path.join(out_dir, os.path.basename(p)) for p in sorted(frame_paths)], video_path, fps, pool, yuv=yuv, bits=bit_depth, chroma=chroma)
     if stats is not None:
         stats.update(prep_s=t_prep - t_start, frames=hi - lo, frames_s=t_frames - t_prep, gpu_call_s=gpu_s, io_threads=nthreads,
                      frames_per_s=(hi - lo) / max(t_frames - t_prep, 1e-9))
@@ -585,7 +635,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
-                yuv=("bt601", False), io_threads=None, bit_depth=None):
+                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -593,7 +643,10 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     image files the chunk's frames are written as stylize_files writes them, named frame_%06d.png (io_threads encode workers, as in
     stylize_files); any other video_path is the Motion-JPEG AVI.  One rank; returns the paths written.
     A C420p10 / p12 / p16 input (Y4MReader(high_depth=True)) is fed as in_format "i420p10" / "i420p12" / "i420p16", uint16 samples.
-    bit_depth: the depth of a .y4m output, 8 / 10 / 12 / 16; None (default): the input file's depth."""
+    bit_depth: the depth of a .y4m output, 8 / 10 / 12 / 16; None (default): the input file's depth.
+    A C422 / C444 input (and C422p10 ..) is fed as in_format "i422" / "i444p10" / ..: its chroma planes reach the first kernel as they are.
+    chroma: the chroma format of a .y4m output, "420" / "422" / "444"; None (default): the input file's, so a C422p10 file goes to a
+    C422p10 file with no pixel pass on the host."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -605,21 +658,22 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     if write_frames:
         os.makedirs(out_dir, exist_ok=True)
     nthreads = int(io_threads or default_io_threads())
-    with Y4MReader(y4m_path, high_depth=True) as reader, ThreadPoolExecutor(nthreads) as pool, ThreadPoolExecutor(1) as rpool, ThreadPoolExecutor(1) as vpool:
+    with Y4MReader(y4m_path, high_depth=True, chroma=True) as reader, ThreadPoolExecutor(nthreads) as pool, ThreadPoolExecutor(1) as rpool, ThreadPoolExecutor(1) as vpool:
         n, H, W, fb = len(reader), reader.height, reader.width, reader.frame_samples
         in_bits = reader.bits
         out_bits = in_bits if bit_depth is None else int(bit_depth)
-        fmt_of = lambda bits: "i420" if bits == 8 else "i420p%d" % bits
-        in_fmt, out_fmt = fmt_of(in_bits), fmt_of(out_bits)
+        y4m = is_y4m(video_path)
+        out_chroma = check_chroma(chroma, y4m) if chroma is not None else reader.chroma if y4m else "420"
+        in_fmt, out_fmt = y4m_format(reader.chroma, in_bits), y4m_format(out_chroma, out_bits)
+        fob = video.yuv_frame_bytes(H, W, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
         if n < 1:
             raise ValueError("%s holds no frame" % y4m_path)
-        y4m = is_y4m(video_path)
         if fps is None:                          # the file's rate: the exact fraction for a Y4M header, a float for the AVI muxer
             fps = 24 if reader.fps is None else reader.fps if y4m else reader.fps[0] / reader.fps[1]
         size = (H, W)
-        encode, open_writer = video_sink(video_path, fps, yuv, bits=out_bits if y4m else 8) if video_path is not None else (None, None)
+        encode, open_writer = video_sink(video_path, fps, yuv, bits=out_bits if y4m else 8, chroma=out_chroma) if video_path is not None else (None, None)
         t_start = time.perf_counter()
         model.set_yuv_input_matrix(yuv[0], reader.full_range, **deep(in_bits))
         model.prepare_style(read_image_bgr(style_path))
@@ -639,7 +693,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         nbuf = 3
         chunk = max(1, min(int(chunk), n))
         in_buf = [_host_buffer(pkg_empty, (chunk, fb), in_dtype) for _ in range(nbuf)]
-        out_buf = [_host_buffer(pkg_empty, (chunk, fb) if direct else (chunk, H, W, 3), yuv_dtype if direct else out_dtype) for _ in range(nbuf)]
+        out_buf = [_host_buffer(pkg_empty, (chunk, fob) if direct else (chunk, H, W, 3), yuv_dtype if direct else out_dtype) for _ in range(nbuf)]
         starts = list(range(0, n, chunk))
         written, writer, gpu_s = [], None, 0.0
 
@@ -701,7 +755,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
 
 
 def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_path=None, fps=24, chunk=16, style_size=(384, 384), log=print,
-                             io_threads=None, write_frames=True, yuv=("bt601", False), bit_depth=8):
+                             io_threads=None, write_frames=True, yuv=("bt601", False), bit_depth=8, chroma="420"):
     """"Multi-style Interpolation/test.py" on files (VideoStylization :40-111 + the loop :114-131): styles resized to
     384x384, every frame padded and encoded once (features cached by the model), every 16th + the last feature sampled,
     then frame i with the weight ramp; output frames are numbered %d.png as the reference writes them (:131).
@@ -715,7 +769,8 @@ def stylize_files_multistyle(model, style_paths, frame_paths, out_dir, video_pat
     if write_frames:
         os.makedirs(out_dir, exist_ok=True)
     y4m = is_y4m(video_path)
-    encode, open_writer = video_sink(video_path, fps, yuv, bits=int(bit_depth) if y4m else 8) if video_path else (None, None)
+    chroma = check_chroma(chroma, y4m)
+    encode, open_writer = video_sink(video_path, fps, yuv, bits=int(bit_depth) if y4m else 8, chroma=chroma) if video_path else (None, None)
     n, S = len(frame_paths), len(style_paths)
     nthreads = int(io_threads or default_io_threads())
     with ThreadPoolExecutor(nthreads) as pool:
@@ -816,16 +871,18 @@ def main(argv=None, model_factory=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--style", required=True, nargs="+", help="one style image, or several for multi-style interpolation")
-    ap.add_argument("--frames", required=True, help="glob pattern of the content frames, or one .y4m file (4:2:0; 8, 10, 12 or 16 bits), read by the GPU as it is")
+    ap.add_argument("--frames", required=True, help="glob pattern of the content frames, or one .y4m file (4:2:0, 4:2:2 or 4:4:4; 8, 10, 12 or 16 bits), read by the GPU as it is")
     ap.add_argument("--checkpoint", required=True, help="style_net-TIP-final.pth (or 'synthetic' for seeded weights)")
     ap.add_argument("--out", required=True, help="directory for the stylized frames")
-    ap.add_argument("--video", default=None, help="also write a video here: Motion-JPEG for .avi, uncompressed YUV4MPEG2 (4:2:0, see --bit-depth) for .y4m")
+    ap.add_argument("--video", default=None, help="also write a video here: Motion-JPEG for .avi, uncompressed YUV4MPEG2 (see --chroma and --bit-depth) for .y4m")
     ap.add_argument("--no-frames", action="store_true", help="write no image files, only --video (one GPU); a .y4m then takes the I420 bytes "
                     "converted on the GPU")
     ap.add_argument("--yuv", choices=("bt601", "bt709"), default="bt601", help="colour matrix of a .y4m video, written and read")
     ap.add_argument("--full-range", action="store_true", help="full-range (0..255) Y4M instead of limited range (16..235 / 16..240)")
     ap.add_argument("--bit-depth", type=int, choices=(8, 10, 12, 16), default=None, help="sample depth of a .y4m video: C420jpeg for 8, C420p10 / p12 / p16 "
                     "above (default: 8, or the depth of a .y4m input)")
+    ap.add_argument("--chroma", choices=("420", "422", "444"), default=None, help="chroma format of a .y4m video: C420jpeg / C422 / C444 and their pNN forms "
+                    "(default: 420, or the chroma format of a .y4m input)")
     ap.add_argument("--fps", type=float, default=None, help="frame rate of --video (default: 24, or the rate of a .y4m input)")
     ap.add_argument("--no-global", action="store_true", help="per-frame statistics (use_Global=False)")
     ap.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK, else 0)")
@@ -840,6 +897,8 @@ def main(argv=None, model_factory=None):
         ap.error("--no-frames runs on one GPU: the ranks' frames reach the video through their files")
     if args.bit_depth is not None and not is_y4m(args.video):
         ap.error("--bit-depth belongs to --video out.y4m")
+    if args.chroma is not None and not is_y4m(args.video):
+        ap.error("--chroma belongs to --video out.y4m")
     y4m_in = is_y4m(args.frames)
     if y4m_in and args.gpus > 1:
         ap.error("--gpus N with a .y4m input is not supported: a .y4m is stylized on one GPU")
@@ -891,14 +950,14 @@ def main(argv=None, model_factory=None):
     t0 = time.perf_counter()
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
-                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth)
+                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
-                                 write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8)
+                                 write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
     else:
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
-                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8)
+                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

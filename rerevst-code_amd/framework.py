@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .video import YUV_FORMATS, YUV_FORMAT_NAMES, YUV_STANDARDS, _yuv_depth, yuv_frame_bytes  # noqa: F401  (the YUV format table lives there)
+from .video import YUV_FORMATS, YUV_FORMAT_NAMES, YUV_STANDARDS, _yuv_depth, chroma_plane_size, yuv_frame_bytes  # noqa: F401  (the YUV format table lives there)
 from .weights import weight_table, load_checkpoint
 
 
@@ -116,9 +116,9 @@ def _output(shape, dtype, out, out_format="bgr"):
     """(output array, uint8?) of a host entry; shape: [..][Ho][Wo][3], the stylized frames as BGR.  float32 BGR in 0..255 as the
     reference returns it, or uint8: the same values rounded half to even on the GPU (== driver.to_uint8 of the float output, bit for
     bit).  A given `out` selects the format by its own dtype; otherwise `dtype` does and the array comes from the page-locked pool.
-    out_format a YUV 4:2:0 name: [..][yuv_frame_bytes(Ho, Wo)] samples of the format's dtype, whatever `dtype` says."""
+    out_format a YUV format name: [..][yuv_frame_bytes(Ho, Wo, chroma=the format's)] samples of the format's dtype, whatever `dtype` says."""
     if out_format != "bgr":
-        shape, odt = tuple(shape[:-3]) + (yuv_frame_bytes(shape[-3], shape[-2]),), YUV_FORMATS[out_format].dtype
+        shape, odt = tuple(shape[:-3]) + (yuv_frame_bytes(shape[-3], shape[-2], chroma=YUV_FORMATS[out_format].chroma),), YUV_FORMATS[out_format].dtype
         if out is None:
             out = _outputs.empty(shape, odt)
         elif out.dtype != odt or out.shape != shape or not out.flags.c_contiguous:
@@ -148,7 +148,8 @@ def yuv_planes(buf, H, W, layout="i420", bits=8):
     transfer_tensor(out_format / out_layout = "i420" | "nv12") return them (a numpy array or a torch tensor).  Nothing is copied:
     for "nv12" the chroma views are strided (every second byte of the interleaved plane).  bits = 10, 12, 16 (or a layout name that
     carries the depth: "i420p10", "p010", ..): uint16 samples [..][yuv_frame_bytes(H, W)], the same planes; the samples are returned
-    as stored ("p010": the code in the high bits)."""
+    as stored ("p010": the code in the high bits).  A 4:2:2 / 4:4:4 name ("i422", "nv16", "p210", "i444p10", ..) gives chroma planes of
+    chroma_plane_size(H, W, chroma): [..][H][CW] / [..][H][W]."""
     if layout not in YUV_FORMATS:
         raise ValueError("layout must be %s, got %r" % (YUV_FORMAT_NAMES, layout))
     fmt = YUV_FORMATS[layout]
@@ -156,9 +157,9 @@ def yuv_planes(buf, H, W, layout="i420", bits=8):
     if getattr(buf.dtype, "itemsize", None) is not None and buf.dtype.itemsize != (1 if bits == 8 else 2):
         raise ValueError("%d-bit samples are %d bytes each, got %s" % (bits, 1 if bits == 8 else 2, buf.dtype))
     H, W = int(H), int(W)
-    CH, CW = (H + 1) // 2, (W + 1) // 2
-    if buf.shape[-1] != yuv_frame_bytes(H, W):
-        raise ValueError("a %d x %d frame has %d samples, got %d" % (H, W, yuv_frame_bytes(H, W), buf.shape[-1]))
+    CH, CW = chroma_plane_size(H, W, fmt.chroma)
+    if buf.shape[-1] != yuv_frame_bytes(H, W, chroma=fmt.chroma):
+        raise ValueError("a %d x %d %r frame has %d samples, got %d" % (H, W, layout, yuv_frame_bytes(H, W, chroma=fmt.chroma), buf.shape[-1]))
     lead = tuple(buf.shape[:-1])
     y = buf[..., :H * W].reshape(lead + (H, W))
     if fmt.planar:
@@ -208,7 +209,7 @@ def yuv_frames_args(frames, in_format, size):
     a = np.asarray(frames) if isinstance(frames, np.ndarray) else np.stack([np.asarray(f) for f in frames])
     if a.ndim == 1:
         a = a[None]
-    fb = yuv_frame_bytes(H, W)
+    fb = yuv_frame_bytes(H, W, chroma=YUV_FORMATS[in_format].chroma)
     dt = YUV_FORMATS[in_format].dtype
     if a.dtype != dt or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != fb:
         raise ValueError("%r frames of %d x %d are %s [B][%d], got %s %s" % (in_format, H, W, dt.name, fb, a.dtype, a.shape))
@@ -252,11 +253,11 @@ _ELEM_BYTES = {_lib.DT_U8: 1, _lib.DT_F32: 4, _lib.DT_U16: 2}
 
 def _view_planes(layout, H, W):
     """[(row length in elements, rows)] of the planes of an H x W frame in `layout` ("nhwc", "nchw" or a YUV format name)"""
-    CH, CW = (H + 1) // 2, (W + 1) // 2
     if layout == "nhwc":
         return [(3 * W, H)]
     if layout == "nchw":
         return [(W, H)] * 3
+    CH, CW = chroma_plane_size(H, W, YUV_FORMATS[layout].chroma)
     return [(W, H), (CW, CH), (CW, CH)] if YUV_FORMATS[layout].planar else [(W, H), (2 * CW, CH)]
 
 
@@ -276,14 +277,27 @@ def _contiguous_view(desc, H, W):
     return v
 
 
-def image_view_of(t, layout):
+def image_view_of(t, layout, size=None):
     """The rrv_image_view of a torch tensor [B,3,H,W] / [3,H,W] (layout "nchw") or [B,H,W,3] / [H,W,3] ("nhwc"), or None when its
     strides do not fit one: pure stride arithmetic, CPU tensors included.  "nchw" fits when stride(-1) == 1, stride(-2) >= W and the
     channel and batch strides are >= 0 (a channel stride of 0, from expand, reads a grey image as R = G = B); "nhwc" when
     stride(-1) == 1, stride(-2) == 3 and stride(-3) >= 3 W.  Strides are in elements, as the library's are.  The descriptor carries
-    the layout, the tensor's dtype (uint8 / float32) and the "pixel" space; the caller sets the space."""
+    the layout, the tensor's dtype (uint8 / float32) and the "pixel" space; the caller sets the space.
+    A YUV format name ("nv12", "i422", "p210", "i444p10", ..) with size=(H, W): t is [B, frame samples] or [frame samples] of the format's
+    dtype with stride(-1) == 1 and a batch stride >= 0 (every second frame of a buffer, a frame repeated by expand); the planes lie as in
+    the contiguous frame, frames t.stride(0) apart."""
+    if layout in YUV_FORMATS and size is not None:
+        fmt = YUV_FORMATS[layout]
+        H, W = (int(v) for v in size)
+        if t.dim() not in (1, 2) or t.stride(-1) != 1 or t.shape[-1] != yuv_frame_bytes(H, W, chroma=fmt.chroma) or (t.dim() == 2 and t.stride(0) < 0):
+            return None
+        if str(t.dtype) not in (("torch.uint8",) if fmt.bits == 8 else ("torch.uint16", "torch.int16")):
+            return None
+        v = _contiguous_view(_lib.ImageDesc(_lib.DT_U8 if fmt.bits == 8 else _lib.DT_U16, fmt.layout, _lib.SP_PIXEL), H, W)
+        v.frame_stride = int(t.stride(0)) if t.dim() == 2 else 0
+        return v
     if layout not in _LAYOUTS:
-        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r" % (layout,))
+        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), or a YUV format name with size=(H, W), got %r" % (layout,))
     if t.dim() not in (3, 4):
         return None
     st, shp = tuple(t.stride()), tuple(t.shape)
@@ -385,7 +399,7 @@ def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout,
     import torch
     yuv = out_layout in YUV_FORMATS
     Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-    out_shape = (B, yuv_frame_bytes(Ho, Wo)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
+    out_shape = (B, yuv_frame_bytes(Ho, Wo, chroma=YUV_FORMATS[out_layout].chroma)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
     if not batched:
         out_shape = out_shape[1:]
     if out is not None:
@@ -468,7 +482,7 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
     out_layout = layout if out_layout is None else out_layout
     _check_out_layout(out_layout, out_space)
     _on_device(x, "x", device)
-    fb = yuv_frame_bytes(H, W)
+    fb = yuv_frame_bytes(H, W, chroma=YUV_FORMATS[layout].chroma)
     if x.dtype not in _yuv_torch_dtypes(layout) or x.dim() not in (1, 2) or x.shape[-1] != fb or (x.dim() == 2 and x.shape[0] < 1):
         raise ValueError("an %r tensor of %d x %d frames is %s [B, %d] or [%d], got %s %s" % (
             layout, H, W, " or ".join(str(t) for t in _yuv_torch_dtypes(layout)), fb, fb, x.dtype, tuple(x.shape)))
@@ -885,7 +899,11 @@ class Stylization():
         yuv420p10le, Y4M C420p10) and "p010" | "p012" | "p016" (semi-planar, the code in the high bits: hardware decoders / encoders);
         the arrays are uint16 [B][yuv_frame_bytes(H, W)] (that many SAMPLES), the name carries the depth (rrv_set_yuv_depth is called
         here), the matrices are those of set_yuv_matrix / set_yuv_input_matrix(.., bits=) — by default BT.601 limited range at that
-        depth.  Any mix of input and output depth and layout works.  A wrong dtype or shape raises ValueError before any GPU work."""
+        depth.  Any mix of input and output depth and layout works.  A wrong dtype or shape raises ValueError before any GPU work.
+        4:2:2 and 4:4:4: "i422" | "nv16" | "i422p10" / "p12" / "p16" | "p210" / "p212" / "p216" and "i444" | "nv24" | "i444p10" / "p12" /
+        "p16" | "p410" / "p412" / "p416" (ffmpeg yuv422p, nv16, yuv422p10le, p210le, yuv444p, nv24, yuv444p10le, p410le, ..), under the
+        rules of the 4:2:0 name they extend; a frame is yuv_frame_bytes(H, W, chroma="422" | "444") samples, and any mix of chroma format,
+        depth and layout between input and output works ("nv12" in, "p210" out)."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):

@@ -7,7 +7,7 @@ import collections
 
 import numpy as np
 
-from ._lib import LAY_I420, LAY_NV12, LAY_I420_16, LAY_P016, YUV_BT601, YUV_BT709     # constants only: nothing here loads the shared library
+from ._lib import LAY_I420, LAY_NV12, LAY_I420_16, LAY_P016, LAY_422, LAY_444, YUV_BT601, YUV_BT709     # constants only: nothing here loads the shared library
 
 
 def padded_size(n):
@@ -90,16 +90,27 @@ def resize_bilinear(img, size):
     return np.clip(np.rint(top * (1 - fy) + bot * fy), 0, 255).astype(np.uint8)
 
 
-# ===== the YUV 4:2:0 formats by name: the one table framework.py and the drivers read =====
-# layout: RRV_LAY_* of include/rerevst_hip.h; bits: the code depth; dtype: of a sample (uint16 above 8 bits); planar: [Y][Cb][Cr], else [Y][CbCr].
-# "i420pNN": planar, the code in the low bits (ffmpeg yuv420pNNle, Y4M C420pNN); "p0NN": semi-planar, the code in the high bits (ffmpeg
-# p0NNle, hardware decoders / encoders).
-YuvFormat = collections.namedtuple("YuvFormat", "layout bits dtype planar")
-YUV_FORMATS = {name: YuvFormat(layout, bits, np.dtype(np.uint8 if bits == 8 else np.uint16), planar) for name, layout, bits, planar in (
-    ("i420", LAY_I420, 8, True), ("nv12", LAY_NV12, 8, False),
-    ("i420p10", LAY_I420_16, 10, True), ("i420p12", LAY_I420_16, 12, True), ("i420p16", LAY_I420_16, 16, True),
-    ("p010", LAY_P016, 10, False), ("p012", LAY_P016, 12, False), ("p016", LAY_P016, 16, False))}
-YUV_FORMAT_NAMES = "'i420', 'nv12', 'i420p10' / 'p12' / 'p16' or 'p010' / 'p012' / 'p016'"      # as the refusals list them
+# ===== the YUV formats by name: the one table framework.py and the drivers read =====
+# layout: RRV_LAY_* of include/rerevst_hip.h; bits: the code depth; dtype: of a sample (uint16 above 8 bits); planar: [Y][Cb][Cr], else [Y][CbCr];
+# chroma: "420" (a chroma sample per 2 x 2 block), "422" (per horizontal pixel pair) or "444" (per pixel).
+# "i420pNN" / "i422pNN" / "i444pNN": planar, the code in the low bits (ffmpeg yuv420pNNle .., Y4M C420pNN ..); "p0NN" / "p2NN" / "p4NN":
+# semi-planar, the code in the high bits (ffmpeg p0NNle / p2NNle / p4NNle, hardware decoders / encoders and capture cards).
+YuvFormat = collections.namedtuple("YuvFormat", "layout bits dtype planar chroma")
+CHROMA_FLAGS = {"420": 0, "422": LAY_422, "444": LAY_444}
+CHROMA_SHIFTS = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}      # (sx, sy): chroma sample (y >> sy, x >> sx)
+YUV_FORMATS = {name: YuvFormat(layout | CHROMA_FLAGS[chroma], bits, np.dtype(np.uint8 if bits == 8 else np.uint16), planar, chroma)
+               for name, layout, bits, planar, chroma in (
+    ("i420", LAY_I420, 8, True, "420"), ("nv12", LAY_NV12, 8, False, "420"),
+    ("i420p10", LAY_I420_16, 10, True, "420"), ("i420p12", LAY_I420_16, 12, True, "420"), ("i420p16", LAY_I420_16, 16, True, "420"),
+    ("p010", LAY_P016, 10, False, "420"), ("p012", LAY_P016, 12, False, "420"), ("p016", LAY_P016, 16, False, "420"),
+    ("i422", LAY_I420, 8, True, "422"), ("nv16", LAY_NV12, 8, False, "422"),
+    ("i422p10", LAY_I420_16, 10, True, "422"), ("i422p12", LAY_I420_16, 12, True, "422"), ("i422p16", LAY_I420_16, 16, True, "422"),
+    ("p210", LAY_P016, 10, False, "422"), ("p212", LAY_P016, 12, False, "422"), ("p216", LAY_P016, 16, False, "422"),
+    ("i444", LAY_I420, 8, True, "444"), ("nv24", LAY_NV12, 8, False, "444"),
+    ("i444p10", LAY_I420_16, 10, True, "444"), ("i444p12", LAY_I420_16, 12, True, "444"), ("i444p16", LAY_I420_16, 16, True, "444"),
+    ("p410", LAY_P016, 10, False, "444"), ("p412", LAY_P016, 12, False, "444"), ("p416", LAY_P016, 16, False, "444"))}
+YUV_FORMAT_NAMES = ("'i420', 'nv12', 'i420p10' / 'p12' / 'p16' or 'p010' / 'p012' / 'p016' (4:2:2: 'i422', 'nv16', 'i422pNN', 'p210' / 'p212' / 'p216'; "
+                    "4:4:4: 'i444', 'nv24', 'i444pNN', 'p410' / 'p412' / 'p416')")      # as the refusals list them
 YUV_STANDARDS = {"bt601": (YUV_BT601, 0.299, 0.114), "bt709": (YUV_BT709, 0.2126, 0.0722)}      # (RRV_YUV_*, Kr, Kb); Kg = 1 - Kr - Kb
 YUV_DEPTHS = (8, 10, 12, 16)
 
@@ -128,23 +139,41 @@ def yuv_matrix(standard="bt601", full_range=False, bits=8):
     return m.astype(np.float32)
 
 
-def yuv_frame_bytes(H, W, bits=8):
-    """Bytes of one H x W frame in I420 or NV12: H*W luma samples and two chroma planes of ceil(H/2) x ceil(W/2); bits = 10, 12, 16: the
-    same samples in uint16, twice the bytes.  yuv_frame_bytes(H, W) is also the SAMPLE count of a frame at any depth: the last axis of
-    the arrays the YUV formats take and return."""
-    return (int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)) * (1 if _yuv_depth(bits) == 8 else 2)
+def _chroma(chroma):
+    c = str(chroma)
+    if c not in CHROMA_SHIFTS:
+        raise ValueError("chroma must be '420', '422' or '444', got %r" % (chroma,))
+    return c
 
 
-def bgr_to_yuv420(img, m, layout="i420", bits=8):
+def chroma_plane_size(H, W, chroma="420"):
+    """(CH, CW) of an H x W frame's chroma planes: ceil(H/2) x ceil(W/2) for "420", H x ceil(W/2) for "422", H x W for "444"."""
+    sx, sy = CHROMA_SHIFTS[_chroma(chroma)]
+    return (int(H) + sy) >> sy, (int(W) + sx) >> sx
+
+
+def yuv_frame_bytes(H, W, bits=8, chroma="420"):
+    """Bytes of one H x W frame in a planar or semi-planar YUV format: H*W luma samples and two chroma planes of CH x CW samples
+    (chroma_plane_size: ceil(H/2) x ceil(W/2) for 4:2:0, H x ceil(W/2) for 4:2:2, H x W for 4:4:4); bits = 10, 12, 16: the same samples in
+    uint16, twice the bytes.  yuv_frame_bytes(H, W, chroma=..) is also the SAMPLE count of a frame at any depth: the last axis of the
+    arrays the YUV formats take and return."""
+    CH, CW = chroma_plane_size(H, W, chroma)
+    return (int(H) * int(W) + 2 * CH * CW) * (1 if _yuv_depth(bits) == 8 else 2)
+
+
+def bgr_to_yuv420(img, m, layout="i420", bits=8, chroma="420"):
     """The GPU's YUV 4:2:0 conversion (include/rerevst_hip.h, the rrv_*_yuv entries) in numpy float32, for frames that come from files:
     img [..][H][W][3] BGR, float32 in 0..255 or uint8; m the twelve matrix floats; returns uint8 [..][yuv_frame_bytes(H, W)] in
     "i420" ([Y][Cb][Cr]) or "nv12" ([Y][CbCr]).  Every product and sum is a float32 operation in the kernel's order, so on the float32
     output of a transfer entry this gives the bytes of its YUV form.  bits = 10, 12, 16 (m a matrix of that depth): uint16 samples
     [..][H*W + 2*CH*CW], codes clamped to 0..2^bits - 1; "i420" keeps the code in the low bits (RRV_LAY_I420_16, yuv420p10le), "nv12" in
-    the high bits (RRV_LAY_P016, p010le: code << (16 - bits))."""
+    the high bits (RRV_LAY_P016, p010le: code << (16 - bits)).  chroma = "422": a chroma sample per horizontal pixel pair, (l + r) * 0.5f of
+    the unclamped components, a last odd column paired with itself; "444": every pixel's own components ([..][yuv_frame_bytes(H, W,
+    chroma=chroma)] samples); layout still names the plane order ("i420": planar, "nv12": semi-planar)."""
     if layout not in ("i420", "nv12"):
         raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
     d = _yuv_depth(bits)
+    chroma = _chroma(chroma)
     f = np.asarray(img).astype(np.float32)
     m = np.asarray(m, np.float32).reshape(3, 4)
     H, W = f.shape[-3:-1]
@@ -160,15 +189,20 @@ def bgr_to_yuv420(img, m, layout="i420", bits=8):
     y0, x0 = np.arange(0, H, 2), np.arange(0, W, 2)
     y1, x1 = np.minimum(y0 + 1, H - 1), np.minimum(x0 + 1, W - 1)          # a row / column past the frame: its nearest one inside
     planes = [byte(comp[0]).reshape(lead + (H * W,))]
-    chroma = []
+    samples = []
     for c in comp[1:]:
-        rows0, rows1 = c[..., y0, :], c[..., y1, :]
-        mean = ((rows0[..., x0] + rows0[..., x1]) + (rows1[..., x0] + rows1[..., x1])) * quarter
-        chroma.append(byte(mean))
+        if chroma == "444":
+            mean = c
+        elif chroma == "422":
+            mean = (c[..., x0] + c[..., x1]) * np.float32(0.5)
+        else:
+            rows0, rows1 = c[..., y0, :], c[..., y1, :]
+            mean = ((rows0[..., x0] + rows0[..., x1]) + (rows1[..., x0] + rows1[..., x1])) * quarter
+        samples.append(byte(mean))
     if layout == "i420":
-        planes += [c.reshape(lead + (-1,)) for c in chroma]
+        planes += [c.reshape(lead + (-1,)) for c in samples]
     else:
-        planes.append(np.stack(chroma, axis=-1).reshape(lead + (-1,)))
+        planes.append(np.stack(samples, axis=-1).reshape(lead + (-1,)))
     return np.concatenate(planes, axis=-1)
 
 
@@ -192,25 +226,29 @@ def yuv_input_matrix(standard="bt601", full_range=False, bits=8):
     return n.astype(np.float32)
 
 
-def yuv420_to_bgr(buf, H, W, n, layout="i420", bits=8):
+def yuv420_to_bgr(buf, H, W, n, layout="i420", bits=8, chroma="420"):
     """The GPU's YUV 4:2:0 input conversion (include/rerevst_hip.h, the rrv_*_from_yuv entries) in numpy float32: buf uint8
     [..][yuv_frame_bytes(H, W)] in "i420" or "nv12", n the twelve floats of the input matrix; returns float32 [..][H][W][3] BGR, the PIXEL
     frame the first kernel sees.  Pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1); every product and sum is a
     float32 operation in the kernel's order; the value is clamped to 0..255 and not rounded.  bits = 10, 12, 16 (n a matrix of that
     depth): buf uint16 [..][H*W + 2*CH*CW]; "i420" samples are the codes, "nv12" samples carry the code in the high bits
-    (sample >> (16 - bits), the low bits ignored)."""
+    (sample >> (16 - bits), the low bits ignored).  chroma = "422" / "444": the chroma sample is (y, x >> 1) / (y, x), and buf has
+    yuv_frame_bytes(H, W, chroma=chroma) samples."""
     if layout not in ("i420", "nv12"):
         raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
     d = _yuv_depth(bits)
+    chroma = _chroma(chroma)
+    fs = yuv_frame_bytes(H, W, chroma=chroma)
     buf = np.asarray(buf)
     dt = np.uint8 if d == 8 else np.uint16
-    if buf.dtype != dt or buf.shape[-1] != yuv_frame_bytes(H, W):
-        raise ValueError("a %d x %d %s frame at %d bits is %d %s samples, got %s %s" % (H, W, layout, d, yuv_frame_bytes(H, W), np.dtype(dt).name, buf.dtype, buf.shape))
+    if buf.dtype != dt or buf.shape[-1] != fs:
+        raise ValueError("a %d x %d %s frame at %d bits is %d %s samples, got %s %s" % (H, W, layout, d, fs, np.dtype(dt).name, buf.dtype, buf.shape))
     if d != 8 and layout == "nv12":
         buf = np.right_shift(buf, np.uint16(16 - d))
     n = np.asarray(n, np.float32).reshape(3, 4)
     lead = buf.shape[:-1]
-    CH, CW = (H + 1) // 2, (W + 1) // 2
+    CH, CW = chroma_plane_size(H, W, chroma)
+    sx, sy = CHROMA_SHIFTS[chroma]
     y = buf[..., :H * W].reshape(lead + (H, W)).astype(np.float32)
     if layout == "i420":
         cb = buf[..., H * W:H * W + CH * CW].reshape(lead + (CH, CW))
@@ -218,7 +256,7 @@ def yuv420_to_bgr(buf, H, W, n, layout="i420", bits=8):
     else:
         pairs = buf[..., H * W:].reshape(lead + (CH, CW, 2))
         cb, cr = pairs[..., 0], pairs[..., 1]
-    rows, cols = np.arange(H) >> 1, np.arange(W) >> 1
+    rows, cols = np.arange(H) >> sy, np.arange(W) >> sx
     cb = cb[..., rows, :][..., cols].astype(np.float32)
     cr = cr[..., rows, :][..., cols].astype(np.float32)
     zero, top = np.float32(0), np.float32(255)
