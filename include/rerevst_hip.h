@@ -595,6 +595,52 @@ int rrv_transfer_view_mask_device(rrv_handle h, const void* d_in, const rrv_imag
                                   void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
 int rrv_add_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int H, int W, void* hip_stream);
 
+/* Scaling: frames resampled to a working size on the GPU, in front of everything else (the "content size" of style-transfer tools: the working
+ * resolution sets the stroke size of the stylized picture, and the speed).  The source frames are SH x SW in any form the first kernel reads, through
+ * the same views; H x W is the working size, which is also the size of the delivered frame (with RRV_TF_PAD_CROP the resampled H x W frame is what
+ * gets reflect-padded and cropped; without it 8*(H/8) x 8*(W/8) are delivered as always).  Output-side upscaling is the encoder's or the player's.
+ * Arithmetic: one separable filter.  For one axis with S source and D destination samples, s = S / D and support = max(s, 1); output sample i has
+ *   c = s (i + 0.5),  lo = max(int(c - support + 0.5), 0),  n = min(int(c + support + 0.5), S) - lo   (int truncates)
+ *   w_j = tri((lo + j - c + 0.5) / support) / sum_j of the same,  tri(t) = max(0, 1 - |t|),  j = 0 .. n - 1
+ * evaluated and normalised in double, each weight rounded once to float32; the tables are built on the host.  For s > 1 this is the antialiased
+ * triangle filter (PIL's BILINEAR reduce, torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False)); for s <= 1 plain
+ * half-pixel bilinear with edge clamp; for S == D every row is {1, 0} and the resampled value is the source value, bit for bit (the kernel's tables drop a
+ * trailing tap of weight 0 and the sums start from -0, so this holds for -0 and for non-finite float32 inputs too).  Per axis
+ * S / D <= 8 and D / S <= 8 (else RRV_E_ARG), so a row has at most 16 taps.
+ * A source pixel enters as the float32 PIXEL value, BGR, that the first kernel derives from it: uint8 (float)px; float32 PIXEL v; UNIT v * 255.0f;
+ * NORM (v * std + mean) * 255.0f (each operation rounded); every YUV layout, depth and chroma format as documented for rrv_transfer_from_yuv (chroma
+ * sample (y >> csy, x >> csx), the 3 x 4 input matrix with each operation rounded and no contraction, a clamp to 0..255; matrix and depth are read
+ * from the handle when the call launches).  The three channels are filtered in float32, first along rows, then along columns, taps in ascending
+ * order with fused multiply-adds, and are NOT rounded to integers: a 10-bit source keeps its precision.  Frame b's result does not depend on B.
+ * From there on the frames are a float32 HWC BGR PIXEL input: a scaled call equals, bit for bit in a fixed kernel mode, rrv_resample_view_device
+ * followed by the unscaled call on its output.
+ *   rrv_resample_taps                the tables of one axis: first[D], count[D], w[D][cap] (zero beyond count); no handle, no GPU; RRV_E_ARG outside
+ *                                    the ratio limits or when cap is below the largest count
+ *   rrv_resample_view_device         the resampler alone: B (1..64) frames through `in` -> contiguous [B][H][W][3] float32 BGR PIXEL, queued on
+ *                                    hip_stream (NULL: the null stream)
+ *   rrv_transfer_scaled_view_device  rrv_transfer_view_device on the resampled frames: `in` describes SH x SW frames, `out` the delivered ones;
+ *                                    flags RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM; slots, limits and stream ordering as there
+ *   rrv_transfer_scaled              the host twin through the host pipeline: contiguous frames, `in` = {RRV_DT_U8, RRV_LAY_HWC_BGR, RRV_SP_PIXEL}
+ *                                    or any YUV layout with its sample type; `out` what rrv_transfer_from_yuv delivers; flags within
+ *                                    RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE; any B >= 1.  Sub-batches are sized by the working frame as for the unscaled
+ *                                    call and hold at most 4 x its pixel budget of SOURCE pixels (fewer frames per sub-batch above 2 x per axis), so
+ *                                    the staging per set is at most four times the unscaled call's: 16 x 640 x 640 x 4 source pixels
+ *   rrv_add_scaled[_view_device]     rrv_add / rrv_add_view_device for a sampled frame scaled the same way (kept as the float32 working frame)
+ * Checks, all before any GPU work: the view against (SH, SW), the frame rules against (H, W), the ratio limits; RRV_E_ARG names the field and the
+ * handle stays usable.  The resampled frames of a launch group live in a grow-only float32 buffer per workspace slot (12 bytes per working pixel and
+ * frame), reserved with the axis tables before the call's first launch: out of memory is RRV_E_NOMEM and the handle stays usable.
+ * Not offered yet: blended and masked twins, output scaling, a scaled rrv_prepare_style, tickets. */
+int rrv_resample_taps(int S, int D, int* first /*[D]*/, int* count /*[D]*/, float* w /*[D][cap]*/, int cap);
+int rrv_resample_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW,
+                             int H, int W, float* d_out, void* hip_stream);
+int rrv_transfer_scaled_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW,
+                                    int H, int W, void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW,
+                        int H, int W, void* out, rrv_image_desc out_desc, int flags);
+int rrv_add_scaled_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW,
+                               int H, int W, void* hip_stream);
+int rrv_add_scaled(rrv_handle h, const void* frame, rrv_image_desc in, int SH, int SW, int H, int W);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

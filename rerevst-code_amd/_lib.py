@@ -8,7 +8,8 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags)
+# RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
+# reach the main library only).  It finds librerevst_scale.so next to ITSELF (rpath $ORIGIN): a library in another directory needs a copy there.
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -136,6 +137,14 @@ SYMBOLS = {
     "rrv_transfer_view_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                 C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),       # d_mask: device address
     "rrv_add_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_void_p]),
+    # scaling: (h, in, ImageView* in, [B,] SH, SW, H, W, ...): the source frames are SH x SW, H x W is the working size
+    "rrv_resample_taps": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]),
+    "rrv_resample_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_transfer_scaled_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.POINTER(ImageView), C.c_int, C.c_void_p]),
+    "rrv_transfer_scaled": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_add_scaled_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_add_scaled": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

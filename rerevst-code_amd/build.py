@@ -1,4 +1,5 @@
-"""Builds librerevst_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Builds librerevst_scale.so (the resampler's kernels) and librerevst_hip.so (everything else, linked against it) in-tree with hipcc
+for gfx950 (cross-compiles without a GPU).  Two libraries so that each code object holds exactly the kernels its ledger names."""
 import os
 import subprocess
 import sys
@@ -6,27 +7,40 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librerevst_hip.so")
+SCALE_LIB = os.path.join(HERE, "librerevst_scale.so")
 SOURCES = ["rerevst_hip.hip"]
-HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "../../include/rerevst_hip.h"]
+SCALE_SOURCES = ["resample.hip"]
+SCALE_HEADERS = ["resample.h", "conv_thin.h", "conv_mfma.h"]
+HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "resample.h",
+           "../../include/rerevst_hip.h"]
+
+
+def _newer(lib, files):
+    if not os.path.exists(lib):
+        return True
+    t = os.path.getmtime(lib)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in files)
 
 
 def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    return _newer(SCALE_LIB, SCALE_SOURCES + SCALE_HEADERS) or _newer(LIB, SOURCES + HEADERS)
+
+
+def _run(cmd, verbose):
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
 
 
 def build_lib(force=False, verbose=True, extra=()):
     if not force and not _stale():
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
-           "-Wno-unused-result", *extra,
-           *[os.path.join(CSRC, s) for s in SOURCES], "-o", LIB]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-result"]
+    if force or _newer(SCALE_LIB, SCALE_SOURCES + SCALE_HEADERS):
+        _run([*common, *[os.path.join(CSRC, s) for s in SCALE_SOURCES], "-o", SCALE_LIB], verbose)
+    # the main library finds the scale library next to itself, wherever the package lies
+    _run([*common, *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-L" + HERE, "-lrerevst_scale", "-Wl,-rpath,$ORIGIN", "-o", LIB], verbose)
     return LIB
 
 

@@ -26,6 +26,7 @@
 #include "conv_thin.h"
 #include "prep_kernels.h"
 #include "mask_kernels.h"
+#include "resample.h"      // librerevst_scale.so: parameters and the launch entry of the resampler
 
 namespace {
 
@@ -242,6 +243,11 @@ struct rrv_ctx {
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
     InFmt pend_in = IN_BGR8;          // format of the pending frames (a frame is kept as it arrived; conv_first_k<IN> reads it)
+    // The scaled entries (Xfer::SH): a launch group's resampled float32 BGR PIXEL frames, one grow-only buffer per slot, written and read on
+    // the slot's stream; and the tap tables of every (source, destination) axis pair seen so far, in HBM (rs_tables)
+    float* rs_buf[RRV_MAX_SLOTS] = {nullptr}; size_t rs_cap[RRV_MAX_SLOTS] = {0};
+    struct RsTab { void* block = nullptr; RsAxis axis{}; int span = 0; };      // span: source samples the taps of RS_TH consecutive outputs cover, at most
+    std::map<std::pair<int, int>, RsTab> rs_tabs;
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -1144,14 +1150,20 @@ struct Xfer {
     // the ImgView both kernels address by, and walks the launch groups by its frame stride.
     const rrv_image_view* vin = nullptr;
     const rrv_image_view* vout = nullptr;
+    // The scaled entries: the frames as passed are SH x SW and are resampled to the H x W working frame in front of everything else
+    // (run_xfer), so H, W and all that derives from them keep describing the working frame.  0: not scaled, the frames are H x W.
+    int SH = 0, SW = 0;
 
+    bool scaled() const { return SH != 0 || SW != 0; }
+    int IH() const { return scaled() ? SH : H; }              // the frame as passed
+    int IW() const { return scaled() ? SW : W; }
     int OH() const { return pad ? H : H / 8 * 8; }            // the frame delivered
     int OW() const { return pad ? W : W / 8 * 8; }
-    ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), H, W, in.cs); }
+    ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
     ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW(), fmt.cs); }
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
-    size_t in_bytes() const { return in_frame_bytes(in.form, H, W, in.cs); }                                              // per frame, in x.in
+    size_t in_bytes() const { return in_frame_bytes(in.form, IH(), IW(), in.cs); }                                              // per frame, in x.in
     size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
         return fmt.yuv ? yuv_frame_samples(OH(), OW(), fmt.cs) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
@@ -2122,6 +2134,8 @@ int rrv_destroy(rrv_handle h) {
     for (StyleState& s : h->styles) { if (s.blob) (void)hipFree(s.blob); if (s.smean) (void)hipFree(s.smean); tfree(&s.map); }
     if (h->d_u8) (void)hipFree(h->d_u8);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
+    for (float* q : h->rs_buf) if (q) (void)hipFree(q);
+    for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
     for (auto& st : h->hstage) {
@@ -2716,6 +2730,131 @@ int rrv_broadcast_state(rrv_handle h, void* comm, int root, int my_rank, int sid
     return RRV_OK;
 }
 
+// ---- scaling (include/rerevst_hip.h "Scaling"): the axis tables of the resampler, on the host in double, and its launch
+// One axis, S source and D destination samples: s = S / D, support = max(s, 1); output i has its centre at c = s (i + 0.5), first tap
+// lo = max(int(c - support + 0.5), 0), n = min(int(c + support + 0.5), S) - lo taps, weight j = tri((lo + j - c + 0.5) / support) with
+// tri(t) = max(0, 1 - |t|), divided by the row's sum; everything in double, each weight rounded once to float32.  s > 1: the antialiased
+// triangle filter (PIL's, torch's interpolate(mode="bilinear", antialias=True)); s <= 1: half-pixel bilinear with edge clamp; S == D: {1, 0}.
+static bool rs_ratio_ok(int S, int D) { return S >= 1 && D >= 1 && (int64_t)S <= 8 * (int64_t)D && (int64_t)D <= 8 * (int64_t)S; }
+struct RsTaps { std::vector<int> first, count; std::vector<float> w; int taps = 0; };      // w: [D][RS_TAPS], zero beyond count; taps: the largest count
+static RsTaps rs_build(int S, int D) {
+    RsTaps t;
+    t.first.resize(D); t.count.resize(D); t.w.assign((size_t)D * RS_TAPS, 0.f);
+    const double s = (double)S / (double)D, support = s > 1.0 ? s : 1.0;
+    for (int i = 0; i < D; ++i) {
+        const double c = s * (i + 0.5);
+        int lo = (int)(c - support + 0.5);
+        if (lo < 0) lo = 0;
+        int hi = (int)(c + support + 0.5);
+        if (hi > S) hi = S;
+        int n = hi - lo;
+        if (n > RS_TAPS) n = RS_TAPS;      // (cannot happen within the ratio limits: 2 * support + 1 samples at most, 16 at ratio 8)
+        double wt[RS_TAPS], sum = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double u = std::fabs(((double)(lo + j) - c + 0.5) / support);
+            wt[j] = u < 1.0 ? 1.0 - u : 0.0;
+            sum += wt[j];
+        }
+        for (int j = 0; j < n; ++j) t.w[(size_t)i * RS_TAPS + j] = (float)(wt[j] / sum);
+        t.first[i] = lo; t.count[i] = n;
+        t.taps = std::max(t.taps, n);
+    }
+    return t;
+}
+int rrv_resample_taps(int S, int D, int* first, int* count, float* w, int cap) {
+    if (!first || !count || !w || !rs_ratio_ok(S, D)) return RRV_E_ARG;
+    const RsTaps t = rs_build(S, D);
+    if (cap < t.taps) return RRV_E_ARG;
+    for (int i = 0; i < D; ++i) {
+        first[i] = t.first[i]; count[i] = t.count[i];
+        for (int j = 0; j < cap; ++j) w[(size_t)i * cap + j] = j < RS_TAPS ? t.w[(size_t)i * RS_TAPS + j] : 0.f;
+    }
+    return RRV_OK;
+}
+// the tables of an axis pair in HBM: built once per (S, D) and handle, uploaded before the call's first launch (a synchronous copy)
+static int rs_tables(rrv_handle h, int S, int D, const rrv_ctx::RsTab** out) {
+    const auto key = std::make_pair(S, D);
+    auto it = h->rs_tabs.find(key);
+    if (it == h->rs_tabs.end()) {
+        RsTaps t = rs_build(S, D);
+        // The kernel's tables drop a trailing tap of weight 0 (the only place one occurs: |t| = 1 at a row's last tap, e.g. the 0 of an
+        // identity row {1, 0}), so no product 0 x sample enters a sum and the kernel needs no per-tap test.  rrv_resample_taps reports it.
+        for (int i = 0; i < D; ++i)
+            while (t.count[i] > 1 && t.w[(size_t)i * RS_TAPS + t.count[i] - 1] == 0.f) --t.count[i];
+        rrv_ctx::RsTab tab;
+        const size_t ib = (size_t)D * sizeof(int), wb = (size_t)D * RS_TAPS * sizeof(float);
+        RCHK(dmalloc(h, &tab.block, 2 * ib + wb));
+        char* const base = (char*)tab.block;
+        hipError_t e = hipMemcpy(base, t.first.data(), ib, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + ib, t.count.data(), ib, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + 2 * ib, t.w.data(), wb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(tab.block); HIPCHK(e); }
+        tab.axis = RsAxis{(const int*)base, (const int*)(base + ib), (const float*)(base + 2 * ib)};
+        for (int i0 = 0; i0 < D; i0 += RS_TH) {
+            const int i1 = std::min(i0 + RS_TH, D) - 1;
+            tab.span = std::max(tab.span, t.first[i1] + t.count[i1] - t.first[i0]);
+        }
+        it = h->rs_tabs.emplace(key, tab).first;
+    }
+    *out = &it->second;
+    return RRV_OK;
+}
+// both axes' tables of a request.  A caller that keeps changing sizes starts over at 64 tables, once nothing in flight reads the old
+// ones and before either pointer is handed out (a map's entries stay where they are while others are added).
+static int rs_pair(rrv_handle h, int SH, int SW, int H, int W, const rrv_ctx::RsTab** ty, const rrv_ctx::RsTab** tx) {
+    const bool have = h->rs_tabs.count(std::make_pair(SH, H)) && h->rs_tabs.count(std::make_pair(SW, W));
+    if (!have && h->rs_tabs.size() >= 64) {
+        RCHK(sync_all(h));
+        HIPCHK(hipDeviceSynchronize());      // (rrv_resample_view_device queues on the caller's stream)
+        for (auto& kv : h->rs_tabs) (void)hipFree(kv.second.block);
+        h->rs_tabs.clear();
+    }
+    RCHK(rs_tables(h, SH, H, ty));
+    RCHK(rs_tables(h, SW, W, tx));
+    // (cannot happen within the ratio limits; judged here, where every request passes before its first launch)
+    if ((*ty)->span > RS_ROWS_MAX) return fail(h, RRV_E_ARG, "resample: the vertical taps of a tile span more rows than the kernel stages");
+    return RRV_OK;
+}
+// everything a scaled request allocates, before its first launch: both axes' tables and room for `frames` working frames in the slot's buffer
+static int rs_reserve(rrv_handle h, int slot, int frames, int SH, int SW, int H, int W) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
+    return ensure_dev(h, h->rs_buf[slot], h->rs_cap[slot], (size_t)frames * H * W * 3);
+}
+static int check_scale(rrv_handle h, const char* who, int SH, int SW, int H, int W) {
+    if (SH < 1 || SW < 1) return fail(h, RRV_E_ARG, std::string(who) + ": SH, SW must be at least 1");
+    if (H < 1 || W < 1) return fail(h, RRV_E_ARG, std::string(who) + ": H, W must be at least 1");
+    if (!rs_ratio_ok(SH, H)) return fail(h, RRV_E_ARG, std::string(who) + ": SH / H must be within 1/8 .. 8");
+    if (!rs_ratio_ok(SW, W)) return fail(h, RRV_E_ARG, std::string(who) + ": SW / W must be within 1/8 .. 8");
+    return RRV_OK;
+}
+// B frames of SH x SW in the format `in` through `vi` -> contiguous [B][H][W][3] float32 BGR PIXEL at d_out, queued on `stream`.  The tables
+// exist already or are built here (rs_reserve has run for the entries that promise no allocation between launches).
+static int resample_launch(rrv_handle h, hipStream_t stream, const void* d_in, InFmt in, const ImgView& vi, int B, int SH, int SW, int H, int W, float* d_out) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
+    ResampleP p{};
+    p.img = d_in; p.v = vi; p.SH = SH; p.SW = SW; p.H = H; p.W = W; p.B = B; p.out = d_out;
+    p.ay = ty->axis; p.ax = tx->axis;
+    p.tiles_x = (W + RS_TW - 1) / RS_TW; p.tiles_y = (H + RS_TH - 1) / RS_TH; p.rows = ty->span;
+    p.space = in.space;
+    if (in_yuv(in.form)) {
+        const YuvLaunch y = yuv_launch_params(h->yuv_in, true, in_yuv16(in.form), in.form == IN_YUV_P016);
+        memcpy(p.yuv_n, y.m, sizeof p.yuv_n); p.yuv_shift = y.shift;
+        p.csx = chroma_sx(in.cs); p.csy = chroma_sy(in.cs);
+    }
+    struct StreamScope { rrv_handle h; hipStream_t s; ~StreamScope() { h->stream = s; } } scope{h, h->stream};
+    h->stream = stream;
+    int e = 0;
+    // for the profile log: bytes from the shapes; operations two per tap, channel and pass, a row's taps taken as span / RS_TH
+    const double src_bytes = (in_yuv(in.form) ? yuv_samples_per_pixel(in.cs) : 3.0) * in_elem(in.form) * SH * SW;
+    RCHK(launch(h, "resample", 2.0 * B * 3 * ((double)tx->span / RS_TH * SH * W + (double)ty->span / RS_TH * H * W), (src_bytes + 12.0 * H * W) * B, [&] {
+        e = rrv_scale_launch(&p, in.form, stream);
+    }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("resample: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+
 // The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
 // burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
 static int next_device_slot(rrv_handle h) {
@@ -2731,6 +2870,7 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false, bool state
     if (x.B < 1 || (!host && x.B > 64)) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
     if (x.pad && (x.H < 1 || x.W < 1)) return fail(h, RRV_E_ARG, "transfer: frames must be at least 1 x 1 pixels");
     RCHK(check_frame(h, x.KH(), x.KW(), "transfer"));      // the geometry the kernels run, refused before any staging is sized for it
+    if (x.scaled()) RCHK(check_scale(h, "transfer", x.SH, x.SW, x.H, x.W));
     if ((blend || mask) && (x.ns < 1 || x.ns > RRV_MAX_STYLES)) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
     if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
     if (mask && !x.mask) return fail(h, RRV_E_ARG, "transfer: null mask");
@@ -2770,7 +2910,11 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     }
     // Against the caller's stream: what it holds so far (the frames, device-resident weights, the masks) precedes the first launch,
     // and it waits for the last one.  transfer_device brackets its own launches, which is all the global model needs.
-    const bool bracket = h->caller_sync && x.model != Model::GLOBAL;
+    // A scaled request resamples each launch group's frames in front of its model (the resampler reads the caller's frames, so it is
+    // bracketed here for every model); what the request allocates for that exists before the first launch.
+    const bool scaled = x.scaled();
+    if (scaled) RCHK(rs_reserve(h, slot, x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX), x.SH, x.SW, x.H, x.W));
+    const bool bracket = h->caller_sync && (x.model != Model::GLOBAL || scaled);
     if (bracket) {
         HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
         HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
@@ -2779,11 +2923,16 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const ImgView vi = x.in_view(), vo = x.out_view();      // the one addressing path: contiguous frames are a view like any other
     const size_t fb = (size_t)vi.fs * in_elem(x.in.form), fo = (size_t)vo.fs * out_view_elem(x.fmt);      // bytes from a frame to the next
     const PadCrop crop = x.pad_crop();
-    const FrameIO io{x.in, x.fmt, x.pad ? &crop : nullptr, &vi, &vo};
+    const ImgView vw = contiguous_view(VL_HWC, x.H, x.W);      // a scaled request's working frames: float32 HWC BGR PIXEL in the slot's buffer
+    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi, &vo};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
-        const uint8_t* const in = (const uint8_t*)d_in + (size_t)b0 * fb;
+        const uint8_t* in = (const uint8_t*)d_in + (size_t)b0 * fb;
         void* const out = (char*)d_out + (size_t)b0 * fo;
+        if (scaled) {
+            RCHK(resample_launch(h, h->streams[slot], in, x.in, vi, cnt, x.SH, x.SW, x.H, x.W, h->rs_buf[slot]));
+            in = (const uint8_t*)h->rs_buf[slot];
+        }
         switch (x.model) {
         case Model::GLOBAL:
             RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, hk));
@@ -2892,7 +3041,7 @@ static int view_run(rrv_handle h, const char* who, const void* d_in, const rrv_i
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x));
     std::string why;
-    if (!view_check(*in, x.B, x.H, x.W, false, &why)) return fail(h, RRV_E_ARG, w + "in." + why);
+    if (!view_check(*in, x.B, x.IH(), x.IW(), false, &why)) return fail(h, RRV_E_ARG, w + "in." + why);      // (a scaled request: the source frame)
     if (!view_check(*out, x.B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);
     x.vin = in; x.vout = out;
     struct Scope {      // hip_stream orders this call only
@@ -3136,7 +3285,11 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const size_t fb = x.in_bytes();                                        // input bytes per frame
     const size_t fob = x.out_bytes();                     // output bytes per frame
     char* const outc = (char*)out;
-    const int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
+    int sub = x.model == Model::GLOBAL ? host_sub(B, x.KH(), x.KW()) : std::min(host_sub(B, x.KH(), x.KW()), (int)rrv_ctx::MS_GROUP_MAX);
+    // The kernels' work follows the working frame, the staging the SOURCE frame: a scaled request's sub-batch also holds at most four times
+    // HOST_SUB_PIXELS of source pixels (2 x per axis keeps the unscaled call's sub-batches; at 8 x 8 a sub-batch is one or two frames), so
+    // the page-locked and device staging per set stays within four times the unscaled call's.
+    if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
     const size_t mfl = x.mask_floats();
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
@@ -3153,6 +3306,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const bool host_in = !in_pin || (mask && !m_pin);      // a page-locked input block of the set is refilled by the host
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
+    auto slot_of = [&](int k) { return h->profiling ? 0 : (k & 1) % h->n_slots; };      // the compute slot of sub-batch k
     const int nsets = nchunk < HOST_SETS ? nchunk : HOST_SETS;
     const bool zin = h->host_io == 1 || h->host_io == 2, zout = h->host_io == 1 || h->host_io == 3;
     // The tail wait and the piecewise delivery (SeqHook) order the sub-batches of the models that run transfer_device, on two streams with
@@ -3163,6 +3317,8 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
+    if (x.scaled())      // a scaled request: the tables and each compute slot's buffer of working frames, before the first launch
+        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(rs_reserve(h, slot_of(k), sub, x.SH, x.SW, x.H, x.W));      // (slot_of has period 2)
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));
@@ -3203,7 +3359,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
             mbytes = (size_t)(mask_images == 1 ? 1 : nb) * mfl * sizeof(float);
             if (!m_pin) { host_copy(st.mask_pin, msrc, mbytes); msrc = st.mask_pin; }
         }
-        const int slot = h->profiling ? 0 : (k & 1) % h->n_slots;
+        const int slot = slot_of(k);
         hipStream_t cs = h->streams[slot];
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
@@ -3370,6 +3526,87 @@ int rrv_transfer_blend_from_yuv(rrv_handle h, const uint8_t* frames, int in_layo
 int rrv_transfer_mask_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, const float* mask, int ns, int mask_images,
                                void* out, rrv_image_desc od, int flags) {
     return from_yuv_host(h, frames, in_layout, out, od, flags, RRV_TF_PAD_CROP, Xfer{Model::MASK, B, H, W, PLAIN, OUT_F32, ns, /* wts */ nullptr, mask, mask_images});
+}
+
+// ---- the scaled entries: frames of SH x SW resampled to the H x W working frame on the GPU, in front of everything else
+// the resampler alone, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own streams takes part
+int rrv_resample_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, float* d_out, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!in) return fail(h, RRV_E_ARG, "resample_view: null view");
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "resample_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_in || !d_out) return fail(h, RRV_E_ARG, "resample_view: null buffer");
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "resample_view: batch must be in 1..64");
+    RCHK(check_scale(h, "resample_view", SH, SW, H, W));
+    std::string why;
+    if (!view_check(*in, B, SH, SW, false, &why)) return fail(h, RRV_E_ARG, "resample_view: in." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    return resample_launch(h, (hipStream_t)hip_stream, d_in, fmt, img_view(*in), B, SH, SW, H, W, d_out);
+}
+int rrv_transfer_scaled_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, void* d_out,
+                                    const rrv_image_view* out, int flags, void* hip_stream) {
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW;
+    if (h && !x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled_view: SH, SW must be at least 1");
+    return view_run(h, "transfer_scaled_view", d_in, in, d_out, out, flags, hip_stream, x);
+}
+// a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
+static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
+    if (yuv_layout(d.layout)) return parse_in_view(d, in);
+    if (d.dtype != RRV_DT_U8 || d.layout != RRV_LAY_HWC_BGR || d.space != RRV_SP_PIXEL) return false;
+    *in = IN_BGR8;
+    return true;
+}
+int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, void* out, rrv_image_desc od, int flags) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW;
+    if (!parse_in_host(in, &x.in)) return fail(h, RRV_E_ARG, "transfer_scaled: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_scaled: unknown flags");
+    if (!x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled: SH, SW must be at least 1");
+    if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
+        return fail(h, RRV_E_ARG, "transfer_scaled: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
+    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
+    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
+    return host_pipeline(h, (const uint8_t*)frames, out, x);
+}
+// a sampled frame of SH x SW, resampled into slot 0's buffer on the handle's stream and added as the float32 PIXEL frame it then is.
+// device: d_frame is in HBM, complete once `stream` has run what it holds now; else host memory in the contiguous form of `fmt`
+static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, const rrv_image_view* view, hipStream_t stream, int SH, int SW, int H, int W) {
+    RCHK(check_frame(h, H, W, "add"));
+    RCHK(check_scale(h, "add_scaled", SH, SW, H, W));
+    std::string why;
+    if (view && !view_check(*view, 1, SH, SW, false, &why)) return fail(h, RRV_E_ARG, "add_scaled: in." + why);
+    if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
+    if ((!h->patches.empty() || h->pend_n) && (H != h->add_H || W != h->add_W))      // add_frame's rule, judged here before any GPU work
+        return fail(h, RRV_E_ARG, "add: all sampled frames must have the same size");
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(rs_reserve(h, 0, 1, SH, SW, H, W));
+    const void* src = frame;
+    if (device) {
+        RCHK(wait_for_stream(h, stream));
+    } else {
+        const size_t fb = in_frame_bytes(fmt.form, SH, SW, fmt.cs);
+        RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, fb));
+        HIPCHK(hipMemcpyAsync(h->d_u8, frame, fb, hipMemcpyHostToDevice, h->stream));
+        src = h->d_u8;
+    }
+    const ImgView vi = view ? img_view(*view) : contiguous_view(in_view_layout(fmt.form), SH, SW, fmt.cs);
+    const int rc = resample_launch(h, h->stream, src, fmt, vi, 1, SH, SW, H, W, h->rs_buf[0]);
+    if (rc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc; }      // (the caller's frame is not read after the call returns)
+    return add_frame(h, h->rs_buf[0], true, InFmt{IN_F32_HWC, SP_PIXEL}, h->stream, H, W);      // (synchronises: the frame has been read and compacted)
+}
+int rrv_add_scaled_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW, int H, int W, void* hip_stream) {
+    if (!h || !d_frame || !in) return RRV_E_ARG;
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "add_scaled_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    return add_scaled(h, d_frame, true, fmt, in, (hipStream_t)hip_stream, SH, SW, H, W);
+}
+int rrv_add_scaled(rrv_handle h, const void* frame, rrv_image_desc in, int SH, int SW, int H, int W) {
+    if (!h || !frame) return RRV_E_ARG;
+    InFmt fmt;
+    if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, "add_scaled: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    return add_scaled(h, frame, false, fmt, nullptr, nullptr, SH, SW, H, W);
 }
 
 // The matrix of the YUV input forms, the inverse of rrv_yuv_matrix's transform: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y,

@@ -423,7 +423,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420"):
+                  chroma="420", work_size=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -438,7 +438,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     that converts on the GPU (Stylization.yuv_output: transfer_frames(out_format="i420")), appended unchanged; in every other case
     the Y4M frames are video.bgr_to_yuv420 of the float frames.  bit_depth 10 / 12 / 16: a C420p10 / p12 / p16 stream
     (out_format="i420p10" ..: the codes are roundings of the float32 result, not of its 8-bit form).  chroma "422" / "444": a C422 /
-    C444 stream (out_format "i422", "i444p10", ..); it belongs to a .y4m video_path, anything else is a ValueError."""
+    C444 stream (out_format "i422", "i444p10", ..); it belongs to a .y4m video_path, anything else is a ValueError.
+    work_size=(H, W): every frame, the sampled ones included, is resampled to that working size on the GPU (add / transfer_frames with
+    work_size=); the frames and the video written have the working size.  Needs a model with transfer_frames(work_size=)."""
     import importlib
     import time
     from collections import deque
@@ -458,6 +460,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     bit_depth = int(bit_depth) if y4m else 8
     yuv_fmt, yuv_dtype = y4m_format(chroma, bit_depth), (np.uint8 if bit_depth == 8 else np.uint16)
     encode, open_writer = video_sink(video_path, fps, yuv, bits=bit_depth, chroma=chroma) if video_path is not None else (None, None)
+    work = None if work_size is None else (int(work_size[0]), int(work_size[1]))
+    scale_kw = {} if work is None else {"work_size": work}
+    out_size = (lambda hw: hw) if work is None else (lambda hw: work)      # the size of the frame delivered for a source frame of (H, W)
     t_start = time.perf_counter()
     with ThreadPoolExecutor(nthreads) as pool:
         # ---- once per video (generate_real_video.py:95-146); the sampled frames are decoded in parallel
@@ -470,7 +475,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
                 model.clean()
                 for f in pool.map(read_image_bgr, [frame_paths[i] for i in ids]):
-                    model.add(f)
+                    model.add(f, **scale_kw)
                 model.compute()
                 if world > 1:
                     blob = model.get_state()
@@ -529,18 +534,20 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 else:
                     chunks.append([i])
             biggest = max(h * w for h, w in sizes)
+            biggest_out = max(h * w for h, w in map(out_size, sizes))
             in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
             if direct:
-                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w, chroma=chroma) for h, w in sizes),), yuv_dtype) for _ in range(nbuf)]
+                out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w, chroma=chroma) for h, w in map(out_size, sizes)),), yuv_dtype) for _ in range(nbuf)]
             else:
-                out_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), out_dtype) for _ in range(nbuf)]
+                out_flat = [_host_buffer(pkg_empty, (chunk * biggest_out * 3,), out_dtype) for _ in range(nbuf)]
 
             def views(k):                        # chunk k's input / output slots: [frames][H][W][3] views of buffer set k % nbuf ([frames][bytes] of I420)
                 (H, W), m = sizes[chunks[k][0] - lo], len(chunks[k])
                 src = in_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
+                OH, OW = out_size((H, W))
                 if direct:
-                    return src, out_flat[k % nbuf][:m * video.yuv_frame_bytes(H, W, chroma=chroma)].reshape(m, -1)
-                return src, out_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
+                    return src, out_flat[k % nbuf][:m * video.yuv_frame_bytes(OH, OW, chroma=chroma)].reshape(m, -1)
+                return src, out_flat[k % nbuf][:m * OH * OW * 3].reshape(m, OH, OW, 3)
 
             def append_chunk(yuv_frames, shape):  # the one video thread: a chunk's I420 frames, unchanged, in order
                 nonlocal writer
@@ -571,12 +578,12 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     f.result()
                 t0 = time.perf_counter()
                 src, dst = views(k)
-                styled = on_device(src, out=dst, out_format=yuv_fmt) if direct else on_device(src, out=dst)
+                styled = on_device(src, out=dst, out_format=yuv_fmt, **scale_kw) if direct else on_device(src, out=dst, **scale_kw)
                 gpu_s += time.perf_counter() - t0
                 submit_decode(k + 2)             # its input buffer was chunk k-1's: consumed
                 futs = []
                 if direct:
-                    enc[k % nbuf] = [vpool.submit(append_chunk, styled, src.shape[1:3])]
+                    enc[k % nbuf] = [vpool.submit(append_chunk, styled, out_size(src.shape[1:3]))]
                     log("stylized frames %d..%d of %d" % (idx[0], idx[-1], n))
                     continue
                 for j, i in enumerate(idx):
@@ -596,6 +603,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 vpool.shutdown()
         else:
             # frame mode, or a model with only the reference's transfer(): per frame, decode and encode still on the worker threads
+            if work is not None and hi > lo:
+                raise ValueError("work_size needs a model with transfer_frames(work_size=)")
             tool = video.ReshapeTool()
             pending = deque()
             look = deque(pool.submit(read_image_bgr, frame_paths[i]) for i in range(lo, min(hi, lo + 2 * nthreads)))
@@ -635,7 +644,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
-                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None):
+                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -646,7 +655,9 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     bit_depth: the depth of a .y4m output, 8 / 10 / 12 / 16; None (default): the input file's depth.
     A C422 / C444 input (and C422p10 ..) is fed as in_format "i422" / "i444p10" / ..: its chroma planes reach the first kernel as they are.
     chroma: the chroma format of a .y4m output, "420" / "422" / "444"; None (default): the input file's, so a C422p10 file goes to a
-    C422p10 file with no pixel pass on the host."""
+    C422p10 file with no pixel pass on the host.
+    work_size=(H, W): the file's frames are resampled to that working size on the GPU (add / transfer_frames with work_size=, size= stays the
+    file's); the frames written and the .y4m header carry the working size."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -665,7 +676,9 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         y4m = is_y4m(video_path)
         out_chroma = check_chroma(chroma, y4m) if chroma is not None else reader.chroma if y4m else "420"
         in_fmt, out_fmt = y4m_format(reader.chroma, in_bits), y4m_format(out_chroma, out_bits)
-        fob = video.yuv_frame_bytes(H, W, chroma=out_chroma)      # samples of an output frame
+        OH, OW = (H, W) if work_size is None else (int(work_size[0]), int(work_size[1]))      # the frame delivered
+        scale_kw = {} if work_size is None else {"work_size": (OH, OW)}
+        fob = video.yuv_frame_bytes(OH, OW, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
         if n < 1:
@@ -682,7 +695,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
             log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
             model.clean()
             for i in ids:
-                model.add(reader.read(i), in_format=in_fmt, size=size)
+                model.add(reader.read(i), in_format=in_fmt, size=size, **scale_kw)
             model.compute()
         t_prep = time.perf_counter()
         direct = y4m and not write_frames
@@ -693,7 +706,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         nbuf = 3
         chunk = max(1, min(int(chunk), n))
         in_buf = [_host_buffer(pkg_empty, (chunk, fb), in_dtype) for _ in range(nbuf)]
-        out_buf = [_host_buffer(pkg_empty, (chunk, fob) if direct else (chunk, H, W, 3), yuv_dtype if direct else out_dtype) for _ in range(nbuf)]
+        out_buf = [_host_buffer(pkg_empty, (chunk, fob) if direct else (chunk, OH, OW, 3), yuv_dtype if direct else out_dtype) for _ in range(nbuf)]
         starts = list(range(0, n, chunk))
         written, writer, gpu_s = [], None, 0.0
 
@@ -725,12 +738,12 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
             src, dst = in_buf[k % nbuf][:m], out_buf[k % nbuf][:m]
             t0 = time.perf_counter()
             if direct:
-                styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size)
+                styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size, **scale_kw)
             else:
-                styled = model.transfer_frames(src, out=dst, in_format=in_fmt, size=size)
+                styled = model.transfer_frames(src, out=dst, in_format=in_fmt, size=size, **scale_kw)
             gpu_s += time.perf_counter() - t0
             if direct:
-                busy[k % nbuf] = [vpool.submit(append_frames, [(fr, (H, W)) for fr in styled])]
+                busy[k % nbuf] = [vpool.submit(append_frames, [(fr, (OH, OW)) for fr in styled])]
             else:
                 futs = []
                 for j in range(m):
@@ -890,7 +903,20 @@ def main(argv=None, model_factory=None):
                     "70 KB state per style (RCCL), every rank writes its own frames")
     ap.add_argument("--io-threads", type=int, default=0, help="decode / encode worker threads per rank (default: half the host cores, 4..48)")
     ap.add_argument("--chunk", type=int, default=32, help="frames per transfer_frames call")
+    ap.add_argument("--work-size", default=None, metavar="WxH", help="resample every frame to this working size on the GPU (antialiased; at most 8x either "
+                    "way per axis): the frames and the video written have this size.  The working size sets the stroke size of the result, and the speed")
     args = ap.parse_args(argv)
+    work_size = None
+    if args.work_size is not None:
+        try:
+            ww, wh = (int(v) for v in args.work_size.lower().split("x"))
+        except ValueError:
+            ap.error("--work-size is WIDTHxHEIGHT, e.g. 960x540")
+        if ww < 8 or wh < 8:
+            ap.error("--work-size is at least 8x8")
+        if len(args.style) > 1:
+            ap.error("--work-size with multi-style interpolation is not supported: the cached-feature entries take frames at the size they run them")
+        work_size = (wh, ww)
     if args.no_frames and not args.video:
         ap.error("--no-frames needs --video: nothing would be written")
     if args.no_frames and args.gpus > 1:
@@ -950,14 +976,15 @@ def main(argv=None, model_factory=None):
     t0 = time.perf_counter()
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
-                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma)
+                    write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma,
+                    work_size=work_size)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
     else:
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
-                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
+                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

@@ -493,6 +493,42 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
                     out_dtype=out_dtype, B=B, H=H, W=W, batched=batched, out_view=out_view)
 
 
+# ===== scaling (the rrv_*_scaled* entries; include/rerevst_hip.h "Scaling" states the arithmetic) =====
+def _work_size(work_size):
+    """(H, W) of a work_size= keyword: the size the frames are resampled to on the GPU, and the size of the delivered frame"""
+    if work_size is None or len(work_size) != 2:
+        raise ValueError("work_size must be (H, W), got %r" % (work_size,))
+    H, W = int(work_size[0]), int(work_size[1])
+    if H < 1 or W < 1:
+        raise ValueError("work_size must be at least 1 x 1, got %d x %d" % (H, W))
+    return H, W
+
+
+def _no_styles_with_work_size(style_weights, style_masks):
+    if style_weights is not None or style_masks is not None:
+        raise ValueError("work_size does not combine with style_weights / style_masks yet: scale the frames with resample_tensor first")
+
+
+def _host_in_desc(in_format):
+    """rrv_image_desc of host frames as the scaled host entries take them: uint8 BGR HWC, or a YUV format by name"""
+    if in_format == "bgr":
+        return _lib.ImageDesc(_lib.DT_U8, _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+    fmt = YUV_FORMATS[in_format]
+    return _lib.ImageDesc(_lib.DT_U8 if fmt.bits == 8 else _lib.DT_U16, fmt.layout, _lib.SP_PIXEL)
+
+
+def resample_taps(S, D):
+    """rrv_resample_taps: (first [D] int32, count [D] int32, weights [D][16] float32) of one axis of the resampler, S source and D
+    destination samples; needs no GPU.  Raises ValueError outside the ratio limits (S / D and D / S at most 8)."""
+    S, D = int(S), int(D)
+    first, count, w = np.zeros(max(D, 1), np.int32), np.zeros(max(D, 1), np.int32), np.zeros((max(D, 1), 16), np.float32)
+    rc = _lib.load().rrv_resample_taps(S, D, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
+                                       w.ctypes.data_as(C.POINTER(C.c_float)), 16)
+    if rc != 0:
+        raise ValueError("no resampling from %d to %d samples: the ratio is limited to 8 either way" % (S, D))
+    return first, count, w
+
+
 # the per-frame style weights of a blended call, as style_weight_args() works them out: `host` a C-contiguous float32 [B][S]
 # array, or `dev` a float32 torch tensor on the handle's device ([B,S], or [S] with `broadcast` set: one vector for every frame)
 StyleWeights = collections.namedtuple("StyleWeights", "host dev S broadcast")
@@ -667,12 +703,26 @@ class Stylization():
         if bi > 8 or bo > 8:
             self._chk(self._lib.rrv_set_yuv_depth(self._h, bi if bi > 8 else 0, bo if bo > 8 else 0))
 
-    def add(self, patch, in_format="bgr", size=None):
+    def add(self, patch, in_format="bgr", size=None, work_size=None):
         """A sampled frame: uint8 BGR HWC, or with in_format "i420" / "nv12" and size=(H, W) 8-bit YUV 4:2:0 bytes
         [yuv_frame_bytes(H, W)] (or [B][..]: every frame, in order) read by the first kernel (rrv_add_from_yuv); in_format "i420p10" /
         "i420p12" / "i420p16" / "p010" / "p012" / "p016": uint16 samples of that depth.  (The depth is read when the deferred encoding
-        runs: add frames of one depth between clean() and compute().)"""
+        runs: add frames of one depth between clean() and compute().)
+        work_size=(H, W): the frame is resampled to that size on the GPU first, as transfer_frames(work_size=) does (rrv_add_scaled);
+        size= stays the size of the frame as passed."""
         self._global_only("add")
+        if work_size is not None:
+            H, W = _work_size(work_size)
+            if in_format != "bgr":
+                a, SH, SW = yuv_frames_args(patch, in_format, size)
+                self._yuv_depth(in_format)
+            else:
+                a = _u8_image(patch, "patch")
+                SH, SW = a.shape[:2]
+                a = a[None]
+            for f in a:
+                self._chk(self._lib.rrv_add_scaled(self._h, f.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), SH, SW, H, W))
+            return
         if in_format != "bgr":
             a, H, W = yuv_frames_args(patch, in_format, size)
             self._yuv_depth(in_format)
@@ -739,10 +789,57 @@ class Stylization():
                 raise ValueError("a style is one image: [3,H,W] or [H,W,3], got shape %s" % (tuple(s.shape),))
             self._chk(self._lib.rrv_prepare_style_image_device(self._h, C.c_void_p(a.x.data_ptr()), a.in_desc, a.H, a.W, sid, stream))
 
-    def add_tensor(self, x, *, space="pixel", layout="nchw"):
+    def _source_view(self, x, space, layout, size):
+        """The input side of the scaled tensor calls: (rrv_image_view, base address, B, SH, SW, batched, the tensor that names the device,
+        layout name) of x as transfer_tensor reads it: an ImageView, a YUV tensor with size=(SH, SW), or an image tensor (a strided one
+        that fits a view stays where it is)."""
+        if isinstance(x, ImageView):
+            _on_device(x.storage, "x.storage", self.device)
+            return x.with_space(space, "x"), x.storage.data_ptr(), x.frames, x.H, x.W, True, x.storage, x.layout
+        if layout in YUV_FORMATS:
+            if space != "pixel":
+                raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
+            a = yuv_tensor_io_args(x, self.device, layout, size)
+            fmt = YUV_FORMATS[layout]
+            v = _contiguous_view(_lib.ImageDesc(_lib.DT_U8 if fmt.bits == 8 else _lib.DT_U16, fmt.layout, _lib.SP_PIXEL), a.H, a.W)
+        else:
+            a = tensor_view_io_args(x, self.device, space=space, layout=layout)
+            v = a.in_view if a.in_view is not None else _contiguous_view(a.in_desc, a.H, a.W)
+        return v, a.x.data_ptr(), a.B, a.H, a.W, a.batched, a.x, layout
+
+    def resample_tensor(self, x, work_size, *, space="pixel", layout="nchw", size=None):
+        """The resampler alone (rrv_resample_view_device): x as transfer_tensor takes it — an image tensor in `layout` / `space`, a YUV
+        tensor with layout a format name and size=(SH, SW), or an ImageView — resampled to work_size=(H, W) on the GPU, in the order of
+        the current stream.  Returns a float32 tensor [B,H,W,3] ([H,W,3] for an unbatched x): BGR, "pixel" space, not rounded to
+        integers; transfer_tensor(y, layout="nhwc") on it is what transfer_tensor(x, work_size=) computes."""
+        import torch
+        H, W = _work_size(work_size)
+        v, ptr, B, SH, SW, batched, dev_t, lay = self._source_view(x, space, layout, size)
+        self._yuv_depth(lay, None)
+        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev_t.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
+        step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
+        for b0 in range(0, B, TENSOR_BATCH_MAX):
+            nb = min(TENSOR_BATCH_MAX, B - b0)
+            self._chk(self._lib.rrv_resample_view_device(self._h, C.c_void_p(ptr + b0 * step), C.byref(v), nb, SH, SW, H, W,
+                                                         C.c_void_p(out[b0].data_ptr()), stream))
+        return out if batched else out[0]
+
+    def add_tensor(self, x, *, space="pixel", layout="nchw", size=None, work_size=None):
         """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch
-        [B,3,H,W] / [B,H,W,3] whose images are added in order."""
+        [B,3,H,W] / [B,H,W,3] whose images are added in order.  work_size=(H, W): each frame is resampled to that size on the GPU
+        first (rrv_add_scaled_view_device), as transfer_tensor(work_size=) does; x may then also be a YUV tensor with size=(SH, SW)."""
         self._global_only("add")
+        if work_size is not None:
+            import torch
+            H, W = _work_size(work_size)
+            v, ptr, B, SH, SW, _, dev_t, lay = self._source_view(x, space, layout, size)
+            self._yuv_depth(lay, None)
+            stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
+            step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
+            for b in range(B):
+                self._chk(self._lib.rrv_add_scaled_view_device(self._h, C.c_void_p(ptr + b * step), C.byref(v), SH, SW, H, W, stream))
+            return
         if isinstance(x, ImageView):      # a surface (any layout, the YUV ones included): each frame is compacted on the GPU
             import torch
             _on_device(x.storage, "x.storage", self.device)
@@ -842,7 +939,7 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None):
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
         size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
@@ -854,6 +951,17 @@ class Stylization():
             a = _u8_frames(frames, "frame")
             H, W = a.shape[1:3]
         B = a.shape[0]
+        if work_size is not None:      # rrv_transfer_scaled: the frames as passed are SH x SW, everything from here on has the working size
+            _no_styles_with_work_size(style_weights, style_masks)
+            (SH, SW), (H, W) = (H, W), _work_size(work_size)
+            out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out, out_format)
+            self._yuv_depth(in_format, out_format)
+            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
+            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+            flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+            self._chk(self._lib.rrv_transfer_scaled(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, SH, SW, H, W,
+                                                    out.ctypes.data_as(C.c_void_p), desc, flags))
+            return out
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out, out_format)
         self._yuv_depth(in_format, out_format)
@@ -879,7 +987,8 @@ class Stylization():
         self._chk(getattr(self._lib, name)(self._h, *args))
         return out
 
-    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
+    def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
+                       work_size=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -903,10 +1012,14 @@ class Stylization():
         4:2:2 and 4:4:4: "i422" | "nv16" | "i422p10" / "p12" / "p16" | "p210" / "p212" / "p216" and "i444" | "nv24" | "i444p10" / "p12" /
         "p16" | "p410" / "p412" / "p416" (ffmpeg yuv422p, nv16, yuv422p10le, p210le, yuv444p, nv24, yuv444p10le, p410le, ..), under the
         rules of the 4:2:0 name they extend; a frame is yuv_frame_bytes(H, W, chroma="422" | "444") samples, and any mix of chroma format,
-        depth and layout between input and output works ("nv12" in, "p210" out)."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size)
+        depth and layout between input and output works ("nv12" in, "p210" out).
+        work_size=(H, W): the frames are resampled to that working size on the GPU first (rrv_transfer_scaled: an antialiased triangle
+        filter, include/rerevst_hip.h "Scaling") and the result has the working size; size= stays the size of YUV frames as passed.
+        Each axis scales by at most 8 either way.  Not with style_weights / style_masks (ValueError)."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size)
 
-    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None):
+    def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
+                        work_size=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -918,8 +1031,10 @@ class Stylization():
         out_format: "i420" / "nv12" as in transfer_batch: uint8 [B][yuv_frame_bytes(H, W)]; an odd H or W gives a last chroma row
         or column that covers one pixel row / column (replicated, never the padding).
         in_format / size: "i420" / "nv12" input frames [B][yuv_frame_bytes(H, W)], as in transfer_batch; with out_format set too, a
-        decoder's frames go to an encoder with no pixel touched on the host."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size)
+        decoder's frames go to an encoder with no pixel touched on the host.
+        work_size=(H, W): as in transfer_batch; the resampled H x W frame is what gets reflect-padded and cropped, and [B][H][W][3]
+        (or the YUV frames of that size) is what comes back."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -927,7 +1042,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None):
+                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -958,8 +1073,14 @@ class Stylization():
         a window of a larger canvas: it is written in place and returned (the result is `out`); nothing outside the window is touched.
         x and / or out may be an ImageView: a pitched surface (a hardware decoder's NV12 / P010, an encoder's input) in a 1-D storage
         tensor; layout, out_layout and size then come from the view, the result is the `out` view.  A strided call delivers the bits
-        of the contiguous call on the same pixels.  The memory x and out address must not overlap."""
+        of the contiguous call on the same pixels.  The memory x and out address must not overlap.
+        work_size=(H, W): the frames (any of the forms above; size= stays the size of YUV frames as passed) are resampled to that working
+        size on the GPU first (rrv_transfer_scaled_view_device; include/rerevst_hip.h "Scaling"), and the output has the working size:
+        [.., H, W] with pad_crop, else [.., 8*(H//8), 8*(W//8)].  Not with style_weights / style_masks (ValueError)."""
         import torch
+        if work_size is not None:
+            _no_styles_with_work_size(style_weights, style_masks)
+            return self._transfer_tensor_scaled(x, _work_size(work_size), space, out_space, out_dtype, layout, out_layout, pad_crop, out, size)
         xv, ov = (t if isinstance(t, ImageView) else None for t in (x, out))
         if xv is not None:
             layout, dev_t = xv.layout, xv.storage
@@ -1041,6 +1162,43 @@ class Stylization():
                                    flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
                 continue
             self._chk(plain_fn(self._h, src, in_arg, nb, H, W, dst, out_arg, flags, stream))
+        return out
+
+    def _transfer_tensor_scaled(self, x, work, space, out_space, out_dtype, layout, out_layout, pad_crop, out, size):
+        """transfer_tensor(work_size=): the source through its view, the output side worked out for the working size"""
+        import torch
+        H, W = work
+        vi, in_ptr, B, SH, SW, batched, dev_t, layout = self._source_view(x, space, layout, size)
+        ov = out if isinstance(out, ImageView) else None
+        if out_layout is None:
+            out_layout = ov.layout if ov is not None else layout
+        _check_out_layout(out_layout, out_space)
+        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+        if ov is not None:      # written in place, through the view
+            _on_device(ov.storage, "out.storage", self.device)
+            if out_layout != ov.layout:
+                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
+            if (ov.frames, ov.H, ov.W) != (B, Ho, Wo):
+                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, Ho, Wo, ov.frames, ov.H, ov.W))
+            vo = ov.with_space(out_space, "out")
+            if self._lib.rrv_image_view_check(C.byref(vo), B, Ho, Wo, 1) != 0:
+                raise ValueError("out: the planes and frames of an output view must not overlap")
+            out_ptr = ov.storage.data_ptr()
+        else:
+            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
+            if out is None:
+                out = torch.empty(out_shape, dtype=out_dtype, device=dev_t.device)
+            if vo is None:
+                vo = _contiguous_view(out_desc, Ho, Wo)
+            out_ptr = out.data_ptr()
+        in_step, out_step = vi.frame_stride * _ELEM_BYTES[vi.desc.dtype], vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
+        flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+        self._yuv_depth(layout, out_layout)
+        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
+        for b0 in range(0, B, TENSOR_BATCH_MAX):
+            nb = min(TENSOR_BATCH_MAX, B - b0)
+            self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, C.c_void_p(in_ptr + b0 * in_step), C.byref(vi), nb, SH, SW, H, W,
+                                                                C.c_void_p(out_ptr + b0 * out_step), C.byref(vo), flags, stream))
         return out
 
     def sync(self):

@@ -1,0 +1,112 @@
+"""The resampler without a GPU: tests/resample_ref.py against torch's float64 antialiased interpolation, rrv_resample_taps against the
+reference tables, the ratio limits, and the ledger of librerevst_scale.so: every kernel symbol of its gfx950 code object is named here
+and held by one test of tests/test_gpu_resample.py (the rule of tests/kernel_ledger.py; only symbol names are read)."""
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import kernel_ledger as KL
+import resample_ref as R
+
+RRV_OK, RRV_E_ARG = 0, -1
+L = importlib.import_module("rerevst-code_amd._lib")
+assert "rrv_resample_taps" in L.SYMBOLS      # this file is about the resampler the library offers: without its entries nothing here is collected
+
+
+def _lib_taps(S, D, cap=R.TAPS):
+    first, count, w = np.full(max(D, 1), -7, np.int32), np.full(max(D, 1), -7, np.int32), np.full((max(D, 1), cap), np.nan, np.float32)
+    rc = L.load().rrv_resample_taps(S, D, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
+                                    w.ctypes.data_as(C.POINTER(C.c_float)), cap)
+    return rc, first, count, w
+
+
+# (source, destination): non-integer downscale, upscale, about 8x, one axis identity
+TORCH_SHAPES = (((37, 53), (16, 24)), ((33, 47), (72, 96)), ((270, 480), (34, 60)), ((100, 7), (13, 7)))
+
+
+@pytest.mark.parametrize("src,dst", TORCH_SHAPES, ids=["%dx%d_to_%dx%d" % (s + d) for s, d in TORCH_SHAPES])
+def test_reference_agrees_with_torch_float64(src, dst):
+    import torch
+    x = np.random.default_rng(src[0] * 1000 + dst[1]).uniform(0, 255, (2, src[0], src[1], 3))
+    want = torch.nn.functional.interpolate(torch.from_numpy(x).permute(0, 3, 1, 2), size=dst, mode="bilinear", antialias=True, align_corners=False)
+    got = R.resample(x, *dst)
+    err = np.abs(got - want.permute(0, 2, 3, 1).numpy()).max()
+    print("max |reference - torch float64| = %.3g" % err)
+    assert err <= 1e-9
+
+
+AXES = ((53, 24), (37, 16), (47, 96), (33, 72), (480, 60), (270, 34), (100, 13), (7, 7), (192, 24), (128, 16), (300, 200), (50, 40), (72, 72), (8, 64), (1, 8))
+
+
+@pytest.mark.parametrize("S,D", AXES, ids=["%d_to_%d" % a for a in AXES])
+def test_taps_equal_the_reference_tables(S, D):
+    rc, first, count, w = _lib_taps(S, D)
+    assert rc == RRV_OK
+    rf, rn, rw = R.taps(S, D)
+    np.testing.assert_array_equal(first, rf)
+    np.testing.assert_array_equal(count, rn)
+    assert (first >= 0).all() and (count >= 1).all() and (first + count <= S).all()      # what bounds the kernel's reads
+    # each weight within one float32 rounding of the double value; nothing beyond count
+    assert (np.abs(w.astype(np.float64) - rw) <= np.spacing(np.abs(rw).astype(np.float32)).astype(np.float64)).all()
+    for i in range(D):
+        assert not w[i, count[i]:].any()
+    assert (np.abs(w.astype(np.float64).sum(axis=1) - 1.0) <= count * 2.0 ** -24).all()
+
+
+def test_identity_rows_are_one_zero():
+    rc, first, count, w = _lib_taps(72, 72)
+    assert rc == RRV_OK
+    np.testing.assert_array_equal(first, np.arange(72))
+    np.testing.assert_array_equal(count, [2] * 71 + [1])
+    np.testing.assert_array_equal(w[:, 0], np.ones(72, np.float32))
+    assert not w[:, 1:].any()
+
+
+def test_ratio_limits_and_cap():
+    for D in (1, 5, 24):
+        rc, _, count, _ = _lib_taps(8 * D, D)
+        assert rc == RRV_OK and count.max() <= 16
+        assert _lib_taps(8 * D + 1, D)[0] == RRV_E_ARG
+    for S in (1, 5, 24):
+        assert _lib_taps(S, 8 * S)[0] == RRV_OK
+        assert _lib_taps(S, 8 * S + 1)[0] == RRV_E_ARG
+    assert _lib_taps(0, 4)[0] == RRV_E_ARG and _lib_taps(4, 0)[0] == RRV_E_ARG and _lib_taps(-3, 4)[0] == RRV_E_ARG
+    # cap: the largest count of the axis is enough, one less is refused; a wider table is zero beyond count
+    n = int(R.taps(53, 24)[1].max())
+    assert _lib_taps(53, 24, cap=n)[0] == RRV_OK and _lib_taps(53, 24, cap=n - 1)[0] == RRV_E_ARG
+    rc, _, count, w = _lib_taps(53, 24, cap=20)
+    assert rc == RRV_OK and w.shape == (24, 20) and not w[:, n:].any()
+
+
+# ---- the ledger of librerevst_scale.so: kernel symbol -> the test of tests/test_gpu_resample.py that compares THAT instantiation with
+# the float64 reference (resample_k<IN>, IN = conv_first_k's input form; each form is its own compile)
+GPU = "tests/test_gpu_resample.py::"
+SCALE_LEDGER = {
+    "resample_k<0>": GPU + "test_resample_u8_hwc_against_reference",
+    "resample_k<1>": GPU + "test_resample_u8_chw_against_reference",
+    "resample_k<2>": GPU + "test_resample_f32_hwc_against_reference",
+    "resample_k<3>": GPU + "test_resample_f32_chw_against_reference",
+    "resample_k<4>": GPU + "test_resample_i420_against_reference",
+    "resample_k<5>": GPU + "test_resample_nv12_against_reference",
+    "resample_k<6>": GPU + "test_resample_i420_16_against_reference",
+    "resample_k<7>": GPU + "test_resample_p016_against_reference",
+}
+
+
+def test_scale_library_ledger():
+    build = importlib.import_module("rerevst-code_amd.build")
+    build.build_lib(verbose=False)
+    symbols = KL.symbols(build.SCALE_LIB)
+    assert len(symbols) == len(set(symbols))
+    assert set(symbols) == set(SCALE_LEDGER), (sorted(set(symbols) - set(SCALE_LEDGER)), sorted(set(SCALE_LEDGER) - set(symbols)))
+    assert len(set(SCALE_LEDGER.values())) == len(SCALE_LEDGER)      # one test each
+    for key, ref in SCALE_LEDGER.items():
+        path, name = ref.split("::")
+        assert os.path.isfile(os.path.join(KL.ROOT, path)), (key, ref)
+        mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
+        assert callable(getattr(mod, name, None)), (key, ref)
+    # and the main library holds none of them: its own ledger stays what it was
+    assert not [s for s in KL.symbols(build.LIB) if s.startswith("resample")]
