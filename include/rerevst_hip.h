@@ -762,6 +762,11 @@ int rrv_profile_end(rrv_handle h);
 int rrv_profile_count(rrv_handle h);
 int rrv_profile_entry(rrv_handle h, int i, const char** name, float* ms, double* flops, double* bytes,
                       double* flops_executed);
+/* The grid of entry i, for the persistent kernels (the transform-domain convolutions and conv_last walk their work items
+ * with gridDim.x workgroups): *grid = the launch's grid.x, *xcd_slabs = which of the two item walks a transform-domain
+ * launch took (1: the slabs of a pixel tile on one XCD; 0: the plain walk), -1 for a launch that has none (conv_last, the
+ * direct-form convolutions).  Every other launch reports *grid = 0, *xcd_slabs = -1. */
+int rrv_profile_entry_grid(rrv_handle h, int i, unsigned* grid, int* xcd_slabs);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,7 @@ SYMBOLS = {
     "rrv_profile_count": (C.c_int, [C.c_void_p]),
     "rrv_profile_entry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_float),
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rrv_profile_entry_grid": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
 }
 
 # the entries that write a stylized frame; each has a _u8 twin with the same arguments and a uint8 output (its float

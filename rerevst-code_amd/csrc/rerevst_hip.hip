@@ -66,7 +66,8 @@ struct ConvW {           // one convolution's device weights
     int Cout = 0, Cin = 0, taps = 0, BN = 0;
 };
 
-struct ProfEntry { std::string name; hipEvent_t e0, e1; double flops, bytes; float ms; double flops_exec; };
+struct ProfEntry { std::string name; hipEvent_t e0, e1; double flops, bytes; float ms; double flops_exec;
+                   unsigned grid; int xcd_slabs; };      // rrv_profile_entry_grid: what note_grid() said of this launch (0, -1: nothing)
 
 // VGG conv indices and (cin,cout)
 const int VGG_IDX[9] = {0, 2, 5, 7, 10, 12, 14, 16, 19};
@@ -296,6 +297,7 @@ struct rrv_ctx {
     int fail_alloc_in = 0;            // rrv_debug_fail_alloc: the n-th next device allocation reports out-of-memory
     bool profiling = false;
     std::vector<ProfEntry> prof;
+    unsigned note_grid = 0; int note_xcd = -1;      // note_grid(): the next launch()'s grid.x and ConvP::xcd_slabs, for its ProfEntry
 };
 
 namespace {
@@ -474,10 +476,15 @@ int plan_talloc(rrv_handle h, P& p, const TSpec<P> (&spec)[N], int B, int H, int
 
 void stamp(rrv_handle h, const Tens* t, int B) { t->gen = h->launch_gen; t->gen_B = B; }
 
+// The persistent launches (conv(), run_last) say which grid they are about to launch; launch() files it with the entry.
+void note_grid(rrv_handle h, unsigned grid, int xcd_slabs) { h->note_grid = grid; h->note_xcd = xcd_slabs; }
+
 template <typename F>
 int launch(rrv_handle h, const char* name, double flops, double bytes, F&& f, double flops_exec = -1.0) {
+    const unsigned grid = h->note_grid; const int xcd = h->note_xcd;
+    h->note_grid = 0; h->note_xcd = -1;
     if (h->profiling) {
-        ProfEntry e{name, nullptr, nullptr, flops, bytes, 0.f, flops_exec < 0 ? flops : flops_exec};
+        ProfEntry e{name, nullptr, nullptr, flops, bytes, 0.f, flops_exec < 0 ? flops : flops_exec, grid, xcd};
         HIPCHK(hipEventCreate(&e.e0)); HIPCHK(hipEventCreate(&e.e1));
         HIPCHK(hipEventRecord(e.e0, h->stream));
         f();
@@ -743,6 +750,7 @@ int conv(rrv_handle h, const ConvCall& c) {
     }
     stamp(h, c.out, c.B);
     if (fuse_sc) stamp(h, c.sc_out, c.B);
+    note_grid(h, grid.x, wino ? p.xcd_slabs : -1);
     if (h->profiling) {   // "<kernel>@CinxCout@HxW": bench.py groups by the part before '@'
         char nm[160];
         snprintf(nm, sizeof nm, "%s@%dx%d@%dx%d", lay_name ? lay_name : k->name, w.Cin, w.Cout, c.H, c.W);
@@ -1363,9 +1371,11 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
     }
     if (wl) { lp.ty0 = wl->y0 / 16; lp.tx0 = wl->x0 / 16; lp.tiles_y = (wl->y1 - wl->y0) / 16; lp.tiles_x = (wl->x1 - wl->x0) / 16; }
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
+    const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * LB), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
+    const unsigned grid = tiles < resident ? tiles : resident;
+    note_grid(h, grid, -1);
     return launch(h, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
-        const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * LB), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
-        hipLaunchKernelGGL(last_kernel(fmt), dim3(tiles < resident ? tiles : resident), dim3(256), 0, h->stream, lp);
+        hipLaunchKernelGGL(last_kernel(fmt), dim3(grid), dim3(256), 0, h->stream, lp);
     });
 }
 
@@ -4304,6 +4314,13 @@ int rrv_profile_entry(rrv_handle h, int i, const char** name, float* ms, double*
     if (flops) *flops = e.flops;
     if (bytes) *bytes = e.bytes;
     if (flops_executed) *flops_executed = e.flops_exec;
+    return RRV_OK;
+}
+
+int rrv_profile_entry_grid(rrv_handle h, int i, unsigned* grid, int* xcd_slabs) {
+    if (!h || i < 0 || i >= (int)h->prof.size()) return RRV_E_ARG;
+    if (grid) *grid = h->prof[i].grid;
+    if (xcd_slabs) *xcd_slabs = h->prof[i].xcd_slabs;
     return RRV_OK;
 }
 

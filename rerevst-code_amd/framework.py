@@ -1371,6 +1371,17 @@ class Stylization():
             rows.append((name.value.decode(), ms.value, fl.value, by.value, fx.value))
         return rows
 
+    def profile_grids(self):
+        """After profile_end(): one (grid.x, xcd_slabs) per row of its log (rrv_profile_entry_grid).  The persistent kernels
+        report the grid they were launched with; xcd_slabs is 1 / 0 for the two item walks of a transform-domain launch and -1
+        for a launch that has none; every other launch reports (0, -1)."""
+        g, x = C.c_uint(0), C.c_int(0)
+        out = []
+        for i in range(self._lib.rrv_profile_count(self._h)):
+            self._chk(self._lib.rrv_profile_entry_grid(self._h, i, C.byref(g), C.byref(x)))
+            out.append((g.value, x.value))
+        return out
+
 
 class ContentFeature():
     """Handle to an encoder output cached in HBM (what the reference stores as cache/%d.pt)."""
