@@ -67,7 +67,7 @@ struct ConvW {           // one convolution's device weights
 };
 
 struct ProfEntry { std::string name; hipEvent_t e0, e1; double flops, bytes; float ms; double flops_exec;
-                   unsigned grid; int xcd_slabs; };      // rrv_profile_entry_grid: what note_grid() said of this launch (0, -1: nothing)
+                   unsigned grid; int xcd_slabs; };      // rrv_profile_entry_grid: the grid launch() was told of (0, -1: none recorded)
 
 // VGG conv indices and (cin,cout)
 const int VGG_IDX[9] = {0, 2, 5, 7, 10, 12, 14, 16, 19};
@@ -185,11 +185,21 @@ constexpr unsigned F43_DEFAULT_LAYERS = 0x3ff;
 
 struct rrv_ctx {
     int dev = 0;
-    hipStream_t stream = nullptr;              // stream the launch helpers use (= streams[slot in use])
-    hipStream_t streams[RRV_MAX_SLOTS] = {nullptr};
-    int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots (stream, workspace) pairs
-    hipEvent_t slot_ev[RRV_MAX_SLOTS] = {nullptr};   // ordering against the caller's stream (rrv_set_caller_stream)
-    hipStream_t caller_stream = nullptr; bool caller_sync = false;
+    // A slot: a stream, its workspace and what belongs to a launch sequence on it.  How a sequence runs (its stream, state sets, kernel
+    // choice) is never kept here: the entry that starts it says so in a Seq (below) and passes that down.
+    struct Slot {
+        hipStream_t stream = nullptr;
+        hipEvent_t ev = nullptr;                     // ordering against the caller's stream (CallerOrder)
+        // Two workspace geometries per slot: a caller alternating between two frame sizes (e.g. a video and its preview)
+        // keeps both resident instead of re-allocating ~0.76 GB per call; a third size replaces the least recently used.
+        EncPlan enc[2];
+        DecPlan dec[2];
+        // The scaled entries (Xfer::SH): a launch group's resampled float32 BGR PIXEL frames, grow-only, written and read on the slot's stream
+        float* rs_buf = nullptr; size_t rs_cap = 0;
+        int set_images = 0;                          // images whose state sets the slot's last launch wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
+    } slots[RRV_MAX_SLOTS];
+    int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots slots
+    hipStream_t caller_stream = nullptr; bool caller_sync = false;      // rrv_set_caller_stream's setting, written there only (a call with a stream of its own: Xfer::on_stream)
     int user_style = -1;                             // style the plain transfer entries use (first computed / last set_state)
     std::string err;
     std::map<std::string, std::vector<float>> hostw;
@@ -204,22 +214,17 @@ struct rrv_ctx {
     // The state the per-frame path reads (blob layout) and the KernelFilter weights folded with its dynamic filters.
     // Set 0 serves every single-state entry; the grouped models (frame mode, blended frames and cached features: run_xfer) give image g
     // of a launch sequence on slot 0 / 1 the set MS_GROUP_MAX * slot + g, since every image there has its own state (blend_sets writes
-    // the blended ones).  `cur` = the set the launch helpers use right now.
+    // the blended ones).  Which set a launch sequence reads is in its Seq.
     // The sets live in CONTIGUOUS arrays (set i = base + i * stride): a launch whose images carry their own state
     // passes the first set and the strides, the kernels index by image.
     static constexpr int MS_GROUP_MAX = 16;      // multi-style frames per launch sequence (each with its own blended state set)
     static constexpr int N_SETS = 2 * MS_GROUP_MAX;      // two groups in flight.  9.9 MB per set (state blob + three KernelFilters' folded raw and packed weights), 316 MB of the 288 GB per handle, allocated once by rrv_finalize_weights
     struct StateSet { float* active = nullptr; ConvW fold_down[3], fold_up[3]; } sets[N_SETS];
-    StateSet* cur = &sets[0];
-    int state_images = 0;                        // > 0: the launch's images 0..state_images-1 use sets cur, cur+1, .. (per-image state)
-    int set_images[2] = {0, 0};                  // images whose state sets the last launch on slot 0 / 1 wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
+    StateSet* slot_sets(int slot) { return &sets[MS_GROUP_MAX * slot]; }      // the first of the slot's sixteen sets.  Slots 0 and 1 only: the others own none (the grouped models alternate over these two, next_frame_slot)
     float* fold_tmp = nullptr;                 // OIHW scratch for folds (512*32*9 floats)
     StyleState styles[RRV_MAX_STYLES];
-    int active_src = -1;                       // style id whose state is folded (-2: blend)
-    // Two workspace geometries per slot: a caller alternating between two frame sizes (e.g. a video and its preview)
-    // keeps both resident instead of re-allocating ~0.76 GB per call; a third size replaces the least recently used.
-    EncPlan enc_frame[RRV_MAX_SLOTS][2], enc_add, enc_style;
-    DecPlan dec[RRV_MAX_SLOTS][2];
+    int active_src = -1;                       // style id whose state is folded (-1: none, frame mode ran or the state was invalidated; -2: blend).  Written where the sets are written
+    EncPlan enc_add, enc_style;
     unsigned plan_clock = 0;
     unsigned launch_gen = 0;                   // counts the launches of the per-frame chain (Tens::gen)
     // cached raw relu4_1 feature of one (padded) frame, H x W = frame size.  Beyond feat_cap (rrv_set_feature_cache_cap)
@@ -244,9 +249,7 @@ struct rrv_ctx {
     // features are first needed (rrv_compute): the encoder at B = 1 runs at a fraction of its batched rate
     uint8_t* pend_u8 = nullptr; size_t pend_cap = 0; int pend_n = 0;
     InFmt pend_in = IN_BGR8;          // format of the pending frames (a frame is kept as it arrived; conv_first_k<IN> reads it)
-    // The scaled entries (Xfer::SH): a launch group's resampled float32 BGR PIXEL frames, one grow-only buffer per slot, written and read on
-    // the slot's stream; and the tap tables of every (source, destination) axis pair seen so far, in HBM (rs_tables)
-    float* rs_buf[RRV_MAX_SLOTS] = {nullptr}; size_t rs_cap[RRV_MAX_SLOTS] = {0};
+    // The scaled entries (Xfer::SH): the tap tables of every (source, destination) axis pair seen so far, in HBM (rs_tables; Slot::rs_buf holds the frames)
     struct RsTab { void* block = nullptr; RsAxis axis{}; int span = 0; };      // span: source samples the taps of RS_TH consecutive outputs cover, at most
     std::map<std::pair<int, int>, RsTab> rs_tabs;
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
@@ -281,13 +284,11 @@ struct rrv_ctx {
     // its set) retires it; `out` / `out_bytes` = where a pageable caller buffer still has to be filled from pin_out
     struct Ticket { long id = -1; void* out = nullptr; size_t out_bytes = 0; bool open = false; } tickets[4];
     long next_ticket = 0;
-    int grid_share = 1;               // rrv_set_grid_share: persistent grids use 1/grid_share of the CUs
+    int grid_share = 1;               // rrv_set_grid_share: persistent grids use 1/grid_share of the CUs (a Seq starts with it; written by that entry only)
     int f43_mode = 1;                 // rrv_set_f43 / RRV_F43: layers with an F(4x4,3x3) pack run on conv_f43_k — 0 never, 1 where the launch has enough work items for it to win (use_f43), 2 always
     unsigned f43_layers = F43_DEFAULT_LAYERS;   // which of the packed layers may run on conv_f43_k (RRV_F43_LAYERS overrides: experiments / parity attribution)
     bool illcond = false;             // some computed style's state is ill-conditioned (StyleState::illcond)
-    bool enc_p8_tables = false;       // use_f43 prices the encoder layers with conv_f43_k's P8-input ratios (set by run_encoder while it decides / runs a P8 chain)
-    int p8 = 3;                       // channel-chunk-major tensors in front of conv_f43_k launches (conv_f43.h LAY): bit 0 the encoder chain (EncPlan::q11 ..), bit 1 ResidualBlock.conv2's input (DecPlan::qa); RRV_P8=0: NHWC everywhere (A/B, same bits)
-    bool f43_path = false;            // true inside transfer_device only: the preparation pass (prepare_style / add / compute, frame mode) always runs F(2x2,3x3)
+    int p8 = 3;                      // channel-chunk-major tensors in front of conv_f43_k launches (conv_f43.h LAY): bit 0 the encoder chain (EncPlan::q11 ..), bit 1 ResidualBlock.conv2's input (DecPlan::qa); RRV_P8=0: NHWC everywhere (A/B, same bits)
     unsigned direct_layers = 0;       // RRV_DIRECT_LAYERS: encoder convs (bit i = vgg conv i: 1 conv1_2 .. 8 conv4_1) of the per-frame path that run the direct-form kernel
     int ms_group = 0;                 // rrv_set_multistyle_group: frames per launch sequence of rrv_transfer_features_batch (0 = by the frame size)
     YuvSide yuv_in, yuv_out;          // YUV 4:2:0 input (run_encoder) and output (run_last) conversion
@@ -297,10 +298,26 @@ struct rrv_ctx {
     int fail_alloc_in = 0;            // rrv_debug_fail_alloc: the n-th next device allocation reports out-of-memory
     bool profiling = false;
     std::vector<ProfEntry> prof;
-    unsigned note_grid = 0; int note_xcd = -1;      // note_grid(): the next launch()'s grid.x and ConvP::xcd_slabs, for its ProfEntry
 };
 
 namespace {
+
+// How one launch sequence runs.  The entry that knows builds it once (base_seq, slot_seq) and passes it down by reference to everything
+// that launches or chooses a kernel; the request (Xfer) says what the call is, the handle keeps settings and what persists between calls.
+struct Seq {
+    hipStream_t stream;               // every launch of the sequence
+    int slot;                         // the slot whose workspace it uses; -1: none (the preparation pass, weight packing, prepare_style)
+    rrv_ctx::StateSet* set;           // the state set its kernels read ...
+    int state_images;                 // ... or, > 0: image b of 0..state_images-1 reads set + b (per-image state)
+    bool f43;                         // layers with an F(4x4,3x3) pack may run conv_f43_k (use_f43): the per-frame path only, the preparation pass and the unfused walks always run F(2x2,3x3)
+    int share;                        // its persistent grids take 1/share of the CUs (resident_wgs)
+};
+// stream 0, set 0, no F(4x4), the handle's share: everything outside the per-frame path
+Seq base_seq(rrv_handle h) { return Seq{h->slots[0].stream, -1, &h->sets[0], 0, false, h->grid_share}; }
+// a sequence on `slot`: on the shared set 0, or (own_sets, slots 0 and 1) on the slot's own sixteen
+Seq slot_seq(rrv_handle h, int slot, bool own_sets = false) {
+    return Seq{h->slots[slot].stream, slot, own_sets ? h->slot_sets(slot) : &h->sets[0], 0, false, h->grid_share};
+}
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -329,8 +346,8 @@ int check_frame(rrv_handle h, int H, int W, const char* who) {
 }
 
 int sync_all(rrv_handle h) {
-    for (int i = 0; i < RRV_MAX_SLOTS; ++i)
-        if (h->streams[i]) HIPCHK(hipStreamSynchronize(h->streams[i]));
+    for (rrv_ctx::Slot& sl : h->slots)
+        if (sl.stream) HIPCHK(hipStreamSynchronize(sl.stream));
     if (h->copy_in) HIPCHK(hipStreamSynchronize(h->copy_in));
     if (h->copy_out) HIPCHK(hipStreamSynchronize(h->copy_out));
     return RRV_OK;
@@ -357,9 +374,9 @@ int dmalloc(rrv_handle h, void** p, size_t bytes) {
     return RRV_OK;
 }
 
-int dalloc(rrv_handle h, float** p, size_t floats, bool zero = true) {
+int dalloc(rrv_handle h, const Seq& q, float** p, size_t floats, bool zero = true) {
     RCHK(dmalloc(h, (void**)p, floats * sizeof(float)));
-    if (zero) HIPCHK(hipMemsetAsync(*p, 0, floats * sizeof(float), h->stream));
+    if (zero) HIPCHK(hipMemsetAsync(*p, 0, floats * sizeof(float), q.stream));
     return RRV_OK;
 }
 
@@ -406,8 +423,8 @@ int debug_verify(rrv_handle h, const char* where) {
         std::lock_guard<std::mutex> lk(g_dbg_mu);
         for (auto& kv : g_dbg) if (kv.second.h == h) { recs.push_back(kv.second); ptrs.push_back(kv.first); }
     }
-    for (int i = 0; i < RRV_MAX_SLOTS; ++i) if (h->streams[i]) {
-        const hipError_t e = hipStreamSynchronize(h->streams[i]);
+    for (rrv_ctx::Slot& sl : h->slots) if (sl.stream) {
+        const hipError_t e = hipStreamSynchronize(sl.stream);
         if (e != hipSuccess) return fail(h, RRV_E_HIP, std::string("debug: asynchronous fault after ") + where + ": " + hipGetErrorString(e));
     }
     if (recs.empty()) return RRV_OK;
@@ -415,7 +432,7 @@ int debug_verify(rrv_handle h, const char* where) {
     HIPCHK(hipMalloc((void**)&d_cnt, recs.size() * 2 * sizeof(unsigned)));      // the checker's own scratch: not subject to rrv_debug_fail_alloc
     HIPCHK(hipMemset(d_cnt, 0, recs.size() * 2 * sizeof(unsigned)));
     for (size_t i = 0; i < recs.size(); ++i)
-        hipLaunchKernelGGL(dbg_check_k, dim3(64), dim3(256), 0, h->streams[0], (const float*)recs[i].base, (const float*)ptrs[i], recs[i].B, recs[i].H, recs[i].W,
+        hipLaunchKernelGGL(dbg_check_k, dim3(64), dim3(256), 0, h->slots[0].stream, (const float*)recs[i].base, (const float*)ptrs[i], recs[i].B, recs[i].H, recs[i].W,
                            recs[i].C, recs[i].floats, d_cnt + 2 * i);
     std::vector<unsigned> cnt(recs.size() * 2);
     HIPCHK(hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -443,16 +460,16 @@ void tfree(Tens* t) {
 // floats of a ring-layout tensor; slack rows keep tile-overrun halo reads inside the allocation
 size_t tens_floats(int B, int H, int W, int C) { return (size_t)B * (H + 2) * (W + 2) * C + (size_t)20 * (W + 2 + 20) * C; }
 
-int talloc(rrv_handle h, Tens* t, int B, int H, int W, int C) {
+int talloc(rrv_handle h, const Seq& q, Tens* t, int B, int H, int W, int C) {
     tfree(t);
     t->B = B; t->H = H; t->W = W; t->C = C;
     const size_t floats = tens_floats(B, H, W, C);
-    if (!h->debug) return dalloc(h, &t->p, floats, true);
+    if (!h->debug) return dalloc(h, q, &t->p, floats, true);
     RCHK(dmalloc(h, (void**)&t->base, (floats + 2 * DBG_GUARD) * sizeof(float)));
     t->p = t->base + DBG_GUARD;
-    hipLaunchKernelGGL(dbg_fill_k, dim3(16), dim3(256), 0, h->stream, (uint32_t*)t->base, DBG_GUARD, DBG_CANARY);
-    hipLaunchKernelGGL(dbg_fill_k, dim3(16), dim3(256), 0, h->stream, (uint32_t*)(t->p + floats), DBG_GUARD, DBG_CANARY);
-    HIPCHK(hipMemsetAsync(t->p, 0, floats * sizeof(float), h->stream));
+    hipLaunchKernelGGL(dbg_fill_k, dim3(16), dim3(256), 0, q.stream, (uint32_t*)t->base, DBG_GUARD, DBG_CANARY);
+    hipLaunchKernelGGL(dbg_fill_k, dim3(16), dim3(256), 0, q.stream, (uint32_t*)(t->p + floats), DBG_GUARD, DBG_CANARY);
+    HIPCHK(hipMemsetAsync(t->p, 0, floats * sizeof(float), q.stream));
     std::lock_guard<std::mutex> lk(g_dbg_mu);
     g_dbg[t->p] = DbgRec{h, t->base, B, H, W, C, floats};
     return RRV_OK;
@@ -463,12 +480,12 @@ void plan_tfree(P& p, const TSpec<P> (&spec)[N]) { for (const TSpec<P>& s : spec
 // The tensors of a plan's table that `chans` gives a channel count (0: not in this plan), for B images of H x W at level 0.
 // Complete or empty: a failed allocation frees every tensor of the table.
 template <class P, size_t N, class F>
-int plan_talloc(rrv_handle h, P& p, const TSpec<P> (&spec)[N], int B, int H, int W, F&& chans) {
+int plan_talloc(rrv_handle h, const Seq& q, P& p, const TSpec<P> (&spec)[N], int B, int H, int W, F&& chans) {
     for (const TSpec<P>& s : spec) {
         int b = B, hh = H, ww = W, c = chans(s);
         if (!c) continue;
         s.geo(b, hh, ww, c);
-        const int rc = talloc(h, &s.of(p), b, hh, ww, c);
+        const int rc = talloc(h, q, &s.of(p), b, hh, ww, c);
         if (rc != RRV_OK) { plan_tfree(p, spec); return rc; }
     }
     return RRV_OK;
@@ -476,19 +493,15 @@ int plan_talloc(rrv_handle h, P& p, const TSpec<P> (&spec)[N], int B, int H, int
 
 void stamp(rrv_handle h, const Tens* t, int B) { t->gen = h->launch_gen; t->gen_B = B; }
 
-// The persistent launches (conv(), run_last) say which grid they are about to launch; launch() files it with the entry.
-void note_grid(rrv_handle h, unsigned grid, int xcd_slabs) { h->note_grid = grid; h->note_xcd = xcd_slabs; }
-
+// grid, xcd: the persistent launches (conv(), run_last) say which grid.x and ConvP::xcd_slabs they launch, filed with the profile entry
 template <typename F>
-int launch(rrv_handle h, const char* name, double flops, double bytes, F&& f, double flops_exec = -1.0) {
-    const unsigned grid = h->note_grid; const int xcd = h->note_xcd;
-    h->note_grid = 0; h->note_xcd = -1;
+int launch(rrv_handle h, const Seq& q, const char* name, double flops, double bytes, F&& f, double flops_exec = -1.0, unsigned grid = 0, int xcd = -1) {
     if (h->profiling) {
         ProfEntry e{name, nullptr, nullptr, flops, bytes, 0.f, flops_exec < 0 ? flops : flops_exec, grid, xcd};
         HIPCHK(hipEventCreate(&e.e0)); HIPCHK(hipEventCreate(&e.e1));
-        HIPCHK(hipEventRecord(e.e0, h->stream));
+        HIPCHK(hipEventRecord(e.e0, q.stream));
         f();
-        HIPCHK(hipEventRecord(e.e1, h->stream));
+        HIPCHK(hipEventRecord(e.e1, q.stream));
         h->prof.push_back(e);
     } else {
         f();
@@ -496,7 +509,7 @@ int launch(rrv_handle h, const char* name, double flops, double bytes, F&& f, do
     HIPCHK(hipGetLastError());
     if (h->debug >= 2) return debug_verify(h, name);
     if (h->debug == 1) {
-        const hipError_t e = hipStreamSynchronize(h->stream);
+        const hipError_t e = hipStreamSynchronize(q.stream);
         if (e != hipSuccess) return fail(h, RRV_E_HIP, std::string("debug: asynchronous fault in ") + name + ": " + hipGetErrorString(e));
     }
     return RRV_OK;
@@ -517,6 +530,7 @@ struct ConvCall {
     int par_bstride = 0, bias_bstride = 0; long long w_bstride = 0;      // per-image state (ConvP): floats between consecutive images' n1 / n2 / sty, bias, weights
     bool direct = false;           // the direct-form implicit-GEMM kernel (conv_mfma_k: 9 multiplies per output, no transform-domain rounding) instead of a Winograd form
     bool in_p8 = false, out_p8 = false;      // conv_f43_k only: `in` / `out` is the channel-chunk-major twin (a Tens of B * C/8 eight-channel images; conv_f43.h LAY)
+    bool enc_p8 = false;           // an encoder layer of a P8 chain: use_f43 prices it with conv_f43_k's P8-input ratios (run_encoder)
 };
 
 template <int BN, int TAPS, int EPI>
@@ -600,12 +614,12 @@ const F43LayKey F43_LAY_TABLE[] = {
     FKL(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 1),      // ResidualBlock.conv2: P8 in (written by the upsample-fused conv1), NHWC out
 };
 
-// Persistent workgroups of a transform-domain launch: `occ` per CU, on the 1/grid_share of the CUs this launch may use
-// (rrv_set_grid_share, look-ahead tickets: whole XCD rows, never empty).  conv() sizes its grid with it and use_f43 its rounds.
-unsigned resident_wgs(rrv_handle h, int occ) {
+// Persistent workgroups of a transform-domain launch: `occ` per CU, on the 1/share of the CUs this sequence may use
+// (Seq::share: rrv_set_grid_share, look-ahead tickets: whole XCD rows, never empty).  conv() sizes its grid with it and use_f43 its rounds.
+unsigned resident_wgs(rrv_handle h, const Seq& q, int occ) {
     unsigned r = (unsigned)h->n_cus * (unsigned)occ;
-    if (h->grid_share > 1) {
-        r = (r / h->grid_share) & ~7u;      // (a small / partitioned / CU-masked device: n_cus * occ / share < 8)
+    if (q.share > 1) {
+        r = (r / q.share) & ~7u;      // (a small / partitioned / CU-masked device: n_cus * occ / share < 8)
         if (r < 8) r = 8;
     }
     return r;
@@ -620,14 +634,15 @@ unsigned resident_wgs(rrv_handle h, int occ) {
 // every packed layer, from two 1152 x 1152 frames, from one where the items are long (256 channels); never on small
 // frames in small batches.  The rule depends on the layer, the batch and the frame size only (not on what else is in
 // flight): the same call always makes the same choice.
-bool use_f43(rrv_handle h, const ConvW& w, int B, int H, int W, int epi, bool ups, int ksplit, bool per_image) {
-    if (!h->f43_path || !w.pk_f43 || !((h->f43_layers >> w.f43_bit) & 1u) || ups || ksplit > 1 || per_image || h->f43_mode == 0) return false;
+// enc_p8: price an encoder layer with the P8-input ratios (the chain is P8 only as a whole: run_encoder asks so first and falls back to the NHWC ones)
+bool use_f43(rrv_handle h, const Seq& q, const ConvW& w, int B, int H, int W, int epi, bool ups, int ksplit, bool per_image, bool enc_p8 = false) {
+    if (!q.f43 || !w.pk_f43 || !((h->f43_layers >> w.f43_bit) & 1u) || ups || ksplit > 1 || per_image || h->f43_mode == 0) return false;
     if (h->f43_mode == 2) return true;
     // Ill-conditioned state (filter_conditioning): the decoder multiplies whatever error the encoder makes, and F(4x4,3x3) on the
     // seven encoder layers makes 1.4x the error of F(2x2,3x3) (profiles/r05_parity_margin.txt: the x4-decoder weight set goes from
     // 0.73 to 1.42 of the pre-clamp bound with them, stays at 0.73 with the three decoder layers alone): the rule keeps them off.
     if (h->illcond && w.f43_bit < 7) return false;
-    const double R = (double)resident_wgs(h, 1);      // persistent workgroups of this launch: one per CU the handle may use (rrv_create: device CU count under HSA_CU_MASK / RRV_CUS; rrv_set_grid_share / look-ahead tickets: a share of them)
+    const double R = (double)resident_wgs(h, q, 1);      // persistent workgroups of this launch: one per CU the handle may use (rrv_create: device CU count under HSA_CU_MASK / RRV_CUS; rrv_set_grid_share / look-ahead tickets: a share of them)
     auto rounds = [&](double items) { return std::ceil(items / R); };
     const double slabs = w.Cout / 32;
     const double items43 = (double)((H + 31) / 32) * ((W + 31) / 32) * B * slabs, items23 = (double)((H + 15) / 16) * ((W + 15) / 16) * B * slabs;
@@ -636,16 +651,16 @@ bool use_f43(rrv_handle h, const ConvW& w, int B, int H, int W, int epi, bool up
     // round 6: with its input channel-chunk-major conv_f43_k is 12 % faster (run_encoder / resblock_frame feed it that way whenever the
     // consumer runs conv_f43_k; the ReLU layers also WRITE it, 32-byte pieces: profiles/r06_f43_layout.txt, tools/f43_bench.hip -DF43_LAY=1 / 3)
     static const double P8_POOL[3] = {1.47, 1.53, 1.56}, P8_RELU[3] = {1.36, 1.44, 1.52}, P8_RES[3] = {1.41, 1.48, 1.53};
-    const bool p8 = w.f43_bit < 7 ? h->enc_p8_tables : (h->p8 & 2) != 0;      // (the encoder chain is P8 only as a whole: run_encoder asks with the P8 ratios first and falls back to the NHWC ones)
+    const bool p8 = w.f43_bit < 7 ? enc_p8 : (h->p8 & 2) != 0;
     const double base = (epi & E_POOL) ? (p8 ? P8_POOL : BASE_POOL)[ci] : (epi & E_RES_UPS) ? (p8 ? P8_RES : BASE_RES)[ci] : (p8 ? P8_RELU : BASE_RELU)[ci];
     return rounds(items23) >= 1.04 * rounds(items43) * 4.0 / base;
 }
 
-int conv(rrv_handle h, const ConvCall& c) {
+int conv(rrv_handle h, const Seq& q, const ConvCall& c) {
     const ConvW& w = *c.w;
     const ConvKey* k = nullptr;
     bool wino = false;
-    bool f43 = !c.direct && use_f43(h, w, c.B, c.H, c.W, c.epi, c.ups, c.ksplit, c.bias_bstride != 0 || c.w_bstride != 0) &&      // per-image PARAMETERS are conv_f43_k's too (par_bstride); per-image bias / weights (the folded KernelFilter convs) are not
+    bool f43 = !c.direct && use_f43(h, q, w, c.B, c.H, c.W, c.epi, c.ups, c.ksplit, c.bias_bstride != 0 || c.w_bstride != 0, c.enc_p8) &&      // per-image PARAMETERS are conv_f43_k's too (par_bstride); per-image bias / weights (the folded KernelFilter convs) are not
                !((c.wy0 | c.wx0 | c.wy1 | c.wx1) & 31);      // 32 x 32 pixel work items: a window must be aligned to them
     if (f43) {
         f43 = false;
@@ -726,7 +741,7 @@ int conv(rrv_handle h, const ConvCall& c) {
     if (wino) {   // persistent workgroups (one per CU; two for the upsample-fused form), walking tiles_x*tiles_y*B*(Cout/32) work items
         const unsigned slabs = (unsigned)(w.Cout / 32) * ks;
         const unsigned items = (unsigned)(p.tiles_x * p.tiles_y * c.B) * slabs;
-        const unsigned resident = resident_wgs(h, fuse_sc ? Ups5Geo::OCC : c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
+        const unsigned resident = resident_wgs(h, q, fuse_sc ? Ups5Geo::OCC : c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
         grid = dim3(items < resident ? items : resident, 1);
         // slabs of one pixel tile on one XCD (workgroup w runs on XCD w % 8): the raw tile is fetched once per XCD group
         p.xcd_slabs = (grid.x % 8 == 0 && (grid.x / 8) % slabs == 0) ? 1 : 0;
@@ -742,7 +757,7 @@ int conv(rrv_handle h, const ConvCall& c) {
     const double bytes = 4.0 * ((double)c.B * c.in->H * c.in->W * cin + (double)c.B * oh * ow * w.Cout +
                                 (c.res ? (double)c.B * c.res->H * c.res->W * w.Cout : 0.0) + (double)w.Cout * cin * w.taps +
                                 (fuse_sc ? (double)c.B * c.in->H * c.in->W * w.Cout + (double)w.Cout * cin : 0.0));
-    hipStream_t s = h->stream;
+    hipStream_t s = q.stream;
     ConvFn fn = lay_fn ? lay_fn : k->fn;
     if (wino && !f43 && (c.par_bstride | c.bias_bstride || c.w_bstride)) {      // per-image state is a separate instantiation of the F(2x2,3x3) / upsample-fused kernels (conv_f43_k reads par_bstride itself)
         if (!k->fn_img) return fail(h, RRV_E_ARG, "conv: this layer has no per-image-state kernel");
@@ -750,106 +765,106 @@ int conv(rrv_handle h, const ConvCall& c) {
     }
     stamp(h, c.out, c.B);
     if (fuse_sc) stamp(h, c.sc_out, c.B);
-    note_grid(h, grid.x, wino ? p.xcd_slabs : -1);
+    const int xcd = wino ? p.xcd_slabs : -1;
     if (h->profiling) {   // "<kernel>@CinxCout@HxW": bench.py groups by the part before '@'
         char nm[160];
         snprintf(nm, sizeof nm, "%s@%dx%d@%dx%d", lay_name ? lay_name : k->name, w.Cin, w.Cout, c.H, c.W);
-        return launch(h, nm, flops, bytes, [&] { fn(p, grid, s); }, flops_exec);
+        return launch(h, q, nm, flops, bytes, [&] { fn(p, grid, s); }, flops_exec, grid.x, xcd);
     }
-    return launch(h, lay_name ? lay_name : k->name, flops, bytes, [&] { fn(p, grid, s); }, flops_exec);
+    return launch(h, q, lay_name ? lay_name : k->name, flops, bytes, [&] { fn(p, grid, s); }, flops_exec, grid.x, xcd);
 }
 
 // ---- weights ----------------------------------------------------------------------------
-int upload(rrv_handle h, const std::string& key, float** dst, size_t expect) {
+int upload(rrv_handle h, const Seq& q, const std::string& key, float** dst, size_t expect) {
     auto it = h->hostw.find(key);
     if (it == h->hostw.end()) return fail(h, RRV_E_WEIGHTS, "missing weight " + key);
     if (it->second.size() != expect) return fail(h, RRV_E_WEIGHTS, "wrong size for " + key);
-    RCHK(dalloc(h, dst, expect, false));
-    HIPCHK(hipMemcpyAsync(*dst, it->second.data(), expect * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    RCHK(dalloc(h, q, dst, expect, false));
+    HIPCHK(hipMemcpyAsync(*dst, it->second.data(), expect * sizeof(float), hipMemcpyHostToDevice, q.stream));
     return RRV_OK;
 }
 
-int pack(rrv_handle h, ConvW& w) {
-    if (!w.pk) RCHK(dalloc(h, &w.pk, (size_t)w.Cout * w.Cin * w.taps, false));
+int pack(rrv_handle h, const Seq& q, ConvW& w) {
+    if (!w.pk) RCHK(dalloc(h, q, &w.pk, (size_t)w.Cout * w.Cin * w.taps, false));
     const size_t total = (size_t)w.Cout * w.Cin * w.taps;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pack_conv_k, dim3(blocks), dim3(256), 0, h->stream, (const float*)w.raw, w.pk, w.Cout, w.Cin, w.taps, w.BN);
+    hipLaunchKernelGGL(pack_conv_k, dim3(blocks), dim3(256), 0, q.stream, (const float*)w.raw, w.pk, w.Cout, w.Cin, w.taps, w.BN);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
 int bn_for(int cout) { return cout >= 128 ? 128 : (cout >= 64 ? 64 : 32); }
 
-int pack_wino(rrv_handle h, ConvW& w) {
+int pack_wino(rrv_handle h, const Seq& q, ConvW& w) {
     const size_t total = (size_t)w.Cout * w.Cin * 16;
-    if (!w.pk_wino) RCHK(dalloc(h, &w.pk_wino, total, false));
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, w.pk_wino, w.Cout, w.Cin, 0);
+    if (!w.pk_wino) RCHK(dalloc(h, q, &w.pk_wino, total, false));
+    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, q.stream, (const float*)w.raw, w.pk_wino, w.Cout, w.Cin, 0);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
-int pack_f43(rrv_handle h, ConvW& w) {
+int pack_f43(rrv_handle h, const Seq& q, ConvW& w) {
     const size_t total = (size_t)w.Cout * w.Cin * 36;
-    if (!w.pk_f43) RCHK(dalloc(h, &w.pk_f43, total, false));
-    hipLaunchKernelGGL(pack_f43_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, w.pk_f43, w.Cout, w.Cin);
+    if (!w.pk_f43) RCHK(dalloc(h, q, &w.pk_f43, total, false));
+    hipLaunchKernelGGL(pack_f43_k, dim3(4096), dim3(256), 0, q.stream, (const float*)w.raw, w.pk_f43, w.Cout, w.Cin);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
-int pack_ups(rrv_handle h, ConvW& w) {
+int pack_ups(rrv_handle h, const Seq& q, ConvW& w) {
     const size_t total = (size_t)w.Cout * w.Cin * 9;
-    if (!w.pk_ups) RCHK(dalloc(h, &w.pk_ups, total, false));
-    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, w.pk_ups, w.Cout, w.Cin, 1);
+    if (!w.pk_ups) RCHK(dalloc(h, q, &w.pk_ups, total, false));
+    hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, q.stream, (const float*)w.raw, w.pk_ups, w.Cout, w.Cin, 1);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
 // the ResidualBlock's conv1 pack for the five-product form, with the block's 1x1 shortcut (conv_ups5.h)
-int pack_ups_sc(rrv_handle h, ConvW& w, const ConvW& sc) {
+int pack_ups_sc(rrv_handle h, const Seq& q, ConvW& w, const ConvW& sc) {
     if (sc.Cout != w.Cout || sc.Cin != w.Cin || sc.taps != 1) return fail(h, RRV_E_WEIGHTS, "shortcut / conv1 shape mismatch");
     const size_t total = (size_t)w.Cout * w.Cin * Ups5Geo::NUB;
-    if (!w.pk_ups_sc) RCHK(dalloc(h, &w.pk_ups_sc, total, false));
-    hipLaunchKernelGGL(pack_ups5_k, dim3(4096), dim3(256), 0, h->stream, (const float*)w.raw, (const float*)sc.raw, w.pk_ups_sc, w.Cout, w.Cin);
+    if (!w.pk_ups_sc) RCHK(dalloc(h, q, &w.pk_ups_sc, total, false));
+    hipLaunchKernelGGL(pack_ups5_k, dim3(4096), dim3(256), 0, q.stream, (const float*)w.raw, (const float*)sc.raw, w.pk_ups_sc, w.Cout, w.Cin);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
-int make_conv(rrv_handle h, const std::string& prefix, int cout, int cin, int taps, bool has_bias, bool do_pack = true) {
+int make_conv(rrv_handle h, const Seq& q, const std::string& prefix, int cout, int cin, int taps, bool has_bias, bool do_pack = true) {
     ConvW w;
     w.Cout = cout; w.Cin = cin; w.taps = taps; w.BN = bn_for(cout);
-    RCHK(upload(h, prefix + ".weight", &w.raw, (size_t)cout * cin * taps));
-    if (has_bias) RCHK(upload(h, prefix + ".bias", &w.bias, (size_t)cout));
+    RCHK(upload(h, q, prefix + ".weight", &w.raw, (size_t)cout * cin * taps));
+    if (has_bias) RCHK(upload(h, q, prefix + ".bias", &w.bias, (size_t)cout));
     else w.bias = h->zero_bias;
-    if (do_pack) RCHK(pack(h, w));
-    if (do_pack && taps == 9 && cin >= 64 && cout >= 64) RCHK(pack_wino(h, w));
+    if (do_pack) RCHK(pack(h, q, w));
+    if (do_pack && taps == 9 && cin >= 64 && cout >= 64) RCHK(pack_wino(h, q, w));
     h->conv[prefix] = w;
     return RRV_OK;
 }
 
 // ---- statistics helpers -----------------------------------------------------------------
 // mode 0: out[C] = mean;  mode 1: out = norm params [4][C];  mode 2: out = style (mean,std) [2][C]
-int chan_stats(rrv_handle h, const Tens& t, int mode, float* out) {
+int chan_stats(rrv_handle h, const Seq& q, const Tens& t, int mode, float* out) {
     const long npix = (long)t.B * t.H * t.W;
     int nblk = (int)((npix + 255) / 256);        // small tensors (frame mode, B = 1) still get a few dozen workgroups
     if (nblk > 1024) nblk = 1024;
     if (nblk < 1) nblk = 1;
     const int ppb = (int)((npix + nblk - 1) / nblk);
-    // scratch shared by all calls: they are ordered on h->stream (1024 partial blocks x 3 x 512 channels at most)
+    // scratch shared by all calls: they are ordered on q.stream (1024 partial blocks x 3 x 512 channels at most)
     if (t.C > 512) return fail(h, RRV_E_ARG, "chan_stats: more than 512 channels");
     double* part = h->stat_part;
     float* mean = h->stat_mean;
     StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, part, 0, ppb};
     const int fb = (t.C + 15) / 16;
-    RCHK(launch(h, "chan_stat", 0, 0, [&] { hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, h->stream, sp); }));
-    RCHK(launch(h, "chan_final", 0, 0, [&] {
-        hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, h->stream, (const double*)part, nblk, t.C, (double)npix, 0,
+    RCHK(launch(h, q, "chan_stat", 0, 0, [&] { hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, q.stream, sp); }));
+    RCHK(launch(h, q, "chan_final", 0, 0, [&] {
+        hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, q.stream, (const double*)part, nblk, t.C, (double)npix, 0,
                            (const float*)nullptr, mode == 0 ? out : mean);
     }));
     if (mode != 0) {
         sp.pass = 1; sp.mean = mean;
-        RCHK(launch(h, "chan_stat", 0, 0, [&] { hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, h->stream, sp); }));
-        RCHK(launch(h, "chan_final", 0, 0, [&] {
-            hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, h->stream, (const double*)part, nblk, t.C, (double)npix, mode,
+        RCHK(launch(h, q, "chan_stat", 0, 0, [&] { hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, q.stream, sp); }));
+        RCHK(launch(h, q, "chan_final", 0, 0, [&] {
+            hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, q.stream, (const double*)part, nblk, t.C, (double)npix, mode,
                                (const float*)mean, out);
         }));
     }
@@ -857,7 +872,7 @@ int chan_stats(rrv_handle h, const Tens& t, int mode, float* out) {
 }
 
 // par_bstride > 0: image b of x normalises with mean / scale / smean / sstd + b * par_bstride (batched frame mode)
-int pointwise(rrv_handle h, const Tens& x, Tens& y, const float* mean, const float* scale, bool div, const Tens* res,
+int pointwise(rrv_handle h, const Seq& q, const Tens& x, Tens& y, const float* mean, const float* scale, bool div, const Tens* res,
               int res_mode, const float* smean, const float* sstd, const float* lo = nullptr, const float* hi = nullptr, long par_bstride = 0) {
     PointP p{x.p, y.p, x.B, x.H, x.W, x.C, mean, scale, div ? 1 : 0, res ? res->p : nullptr, res_mode,
              res ? res->H : 0, res ? res->W : 0, smean, sstd, lo, hi, 1, par_bstride};
@@ -870,61 +885,61 @@ int pointwise(rrv_handle h, const Tens& x, Tens& y, const float* mean, const flo
     p.segs = segs;
     const int blocks = rows * segs;
     stamp(h, &y, x.B);
-    return launch(h, "pointwise", 0, 0, [&] { hipLaunchKernelGGL(pointwise_k, dim3(blocks), dim3(256), 0, h->stream, p); });
+    return launch(h, q, "pointwise", 0, 0, [&] { hipLaunchKernelGGL(pointwise_k, dim3(blocks), dim3(256), 0, q.stream, p); });
 }
 // y = x normalised with the saved statistics norm[n] of state `st` (no clamp) [+ res, upsampled 2x] [* style std + style mean of entry sty]
-int apply_norm(rrv_handle h, const Tens& x, Tens& y, const float* st, int n, const Tens* res = nullptr, int sty = -1, long par_bstride = 0) {
+int apply_norm(rrv_handle h, const Seq& q, const Tens& x, Tens& y, const float* st, int n, const Tens* res = nullptr, int sty = -1, long par_bstride = 0) {
     const float* m = st + SL.norm[n];
     const float* s = sty < 0 ? nullptr : st + SL.sty[sty];
-    return pointwise(h, x, y, m, m + x.C, false, res, res ? 2 : 0, s, s ? s + x.C : nullptr, nullptr, nullptr, par_bstride);
+    return pointwise(h, q, x, y, m, m + x.C, false, res, res ? 2 : 0, s, s ? s + x.C : nullptr, nullptr, nullptr, par_bstride);
 }
 
 // ---- folded KernelFilter weights for a state blob ------------------------------------------
 // (both folded layers run the row-split transform-domain kernel everywhere — per-frame path and compute()'s frame-0
 // residual alike — so only the Winograd packs are built)
-// nsets > 1: the state sets h->cur, h->cur + 1, .. (blobs RRV_STATE_FLOATS apart, folded weights set-major) in one launch each —
+// nsets > 1: the state sets q.set, q.set + 1, .. (blobs RRV_STATE_FLOATS apart, folded weights set-major) in one launch each —
 // a set's packed 32-cout slabs follow the previous set's, so the pack is the pack of a layer with nsets x the couts.
-int fold_filters(rrv_handle h, const float* blob, int f /*0..2*/, int nsets = 1) {
+int fold_filters(rrv_handle h, const Seq& q, const float* blob, int f /*0..2*/, int nsets = 1) {
     char pre[64];
     snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
     const ConvW& wd = h->conv[std::string(pre) + ".down_sample.0"];
     const ConvW& wu = h->conv[std::string(pre) + ".upsample.0"];
-    ConvW& fd = h->cur->fold_down[f];
-    ConvW& fu = h->cur->fold_up[f];
-    h->set_images[(h->cur - h->sets) / rrv_ctx::MS_GROUP_MAX] = 0;      // the slot's sets are being rewritten; a per-image-state launch counts its images once it is queued
+    ConvW& fd = q.set->fold_down[f];
+    ConvW& fu = q.set->fold_up[f];
+    h->slots[(q.set - h->sets) / rrv_ctx::MS_GROUP_MAX].set_images = 0;      // the slot's sets are being rewritten; a per-image-state launch counts its images once it is queued
     const float* F1 = blob + SL.filt[2 * f];
     const float* F2 = blob + SL.filt[2 * f + 1];
-    hipLaunchKernelGGL(fold_down_k, dim3((32 * 512 * 9 + 255) / 256, nsets), dim3(256), 0, h->stream, F1, (const float*)wd.raw,
+    hipLaunchKernelGGL(fold_down_k, dim3((32 * 512 * 9 + 255) / 256, nsets), dim3(256), 0, q.stream, F1, (const float*)wd.raw,
                        (const float*)wd.bias, fd.raw, fd.bias, 512 * 9, (int)RRV_STATE_FLOATS, 256);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(fold_up_k, dim3((512 * 32 * 9 + 255) / 256, nsets), dim3(256), 0, h->stream, F2, (const float*)wu.raw, fu.raw, 512, (int)RRV_STATE_FLOATS);
+    hipLaunchKernelGGL(fold_up_k, dim3((512 * 32 * 9 + 255) / 256, nsets), dim3(256), 0, q.stream, F2, (const float*)wu.raw, fu.raw, 512, (int)RRV_STATE_FLOATS);
     HIPCHK(hipGetLastError());
     if (nsets == 1) {
-        RCHK(pack_wino(h, fd));          // 512->32 is one Winograd cout slab
-        RCHK(pack_wino(h, fu));          // 32 input channels = two 16-channel chunks per work item
+        RCHK(pack_wino(h, q, fd));          // 512->32 is one Winograd cout slab
+        RCHK(pack_wino(h, q, fu));          // 32 input channels = two 16-channel chunks per work item
     } else {
-        hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, h->stream, (const float*)fd.raw, fd.pk_wino, 32 * nsets, 512, 0);
+        hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, q.stream, (const float*)fd.raw, fd.pk_wino, 32 * nsets, 512, 0);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, h->stream, (const float*)fu.raw, fu.pk_wino, 512 * nsets, 32, 0);
+        hipLaunchKernelGGL(pack_wino_k, dim3(4096), dim3(256), 0, q.stream, (const float*)fu.raw, fu.pk_wino, 512 * nsets, 32, 0);
         HIPCHK(hipGetLastError());
     }
     return RRV_OK;
 }
 
-// The blend step of every blended entry: state sets h->cur, h->cur + 1, .. of images 0..cnt-1 := sum_s w[image][s] x the computed state of
+// The blend step of every blended entry: state sets q.set, q.set + 1, .. of images 0..cnt-1 := sum_s w[image][s] x the computed state of
 // style s (blend_sets_k), their three KernelFilters folded; the sets then hold a blend (active_src -2).  w: [cnt][ns] host weights, read
-// before this returns (they travel in the kernel argument); w_dev: the same array in HBM, read by the kernel on h->stream.
-int blend_sets(rrv_handle h, const float* w, bool w_dev, int ns, int cnt) {
+// before this returns (they travel in the kernel argument); w_dev: the same array in HBM, read by the kernel on q.stream.
+int blend_sets(rrv_handle h, const Seq& q, const float* w, bool w_dev, int ns, int cnt) {
     static_assert(rrv_ctx::MS_GROUP_MAX <= 16, "BlendSetsP::w holds sixteen images");
+    h->active_src = -2;      // from here on, whatever happens: the next global entry re-activates its style
     BlendSetsP bp{};
-    bp.n = ns; bp.out = h->cur->active; bp.count = RRV_STATE_FLOATS;
+    bp.n = ns; bp.out = q.set->active; bp.count = RRV_STATE_FLOATS;
     for (int s = 0; s < ns; ++s) bp.st[s] = h->styles[s].blob;
     if (w_dev) bp.w_dev = w;
     else for (int g = 0; g < cnt; ++g) memcpy(bp.w[g], w + (size_t)g * ns, sizeof(float) * ns);
-    hipLaunchKernelGGL(blend_sets_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, h->stream, bp);
+    hipLaunchKernelGGL(blend_sets_k, dim3((RRV_STATE_FLOATS + 255) / 256, cnt), dim3(256), 0, q.stream, bp);
     HIPCHK(hipGetLastError());
-    h->active_src = -2;
-    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f, cnt));
+    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, q, q.set->active, f, cnt));
     return RRV_OK;
 }
 
@@ -950,10 +965,11 @@ int filter_conditioning(rrv_handle h, StyleState& S) {
 int activate_state(rrv_handle h, int style_id) {
     if (h->active_src == style_id) return RRV_OK;
     RCHK(sync_all(h));
+    const Seq q = base_seq(h);      // the shared set 0
     StyleState& s = h->styles[style_id];
-    HIPCHK(hipMemcpyAsync(h->cur->active, s.blob, RRV_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, h->cur->active, f));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(q.set->active, s.blob, RRV_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
+    for (int f = 0; f < 3; ++f) RCHK(fold_filters(h, q, q.set->active, f));
+    HIPCHK(hipStreamSynchronize(q.stream));
     h->active_src = style_id;
     h->user_style = style_id;
     return RRV_OK;
@@ -987,13 +1003,13 @@ bool p8_fits(int H, int W, int C) { return (double)(H + 2) * (W + 8) * C < 21474
 // A plan is either complete or empty: the geometry is recorded only after every tensor exists; a failed allocation
 // releases what was built so far, and the next call with the same geometry starts over (it must never find a
 // half-built plan that passes the cache test and launch kernels on null tensors).
-// per_frame: a plan of the per-frame path (rrv_ctx::enc_frame), which gets the P8 twins where the chain may run
-int enc_plan(rrv_handle h, EncPlan& e, int B, int H, int W, bool per_frame = false) {      // grow-only in B: a plan made for more images serves fewer
+// per_frame: a plan of the per-frame path (Slot::enc), which gets the P8 twins where the chain may run
+int enc_plan(rrv_handle h, const Seq& q, EncPlan& e, int B, int H, int W, bool per_frame = false) {      // grow-only in B: a plan made for more images serves fewer
     if (e.B >= B && e.H == H && e.W == W && e.c41.p) return RRV_OK;
     RCHK(check_image_size(h, H, W, "encoder"));
     enc_free(e);
     const bool twins = per_frame && (h->p8 & 1) && p8_fits(H, W, 64) && p8_fits(H / 2, W / 2, 128) && p8_fits(H / 4, W / 4, 256);
-    RCHK(plan_talloc(h, e, ENC_T, B, H, W, [&](const TSpec<EncPlan>& s) { return (s.flags & TS_P8) && !twins ? 0 : s.C; }));
+    RCHK(plan_talloc(h, q, e, ENC_T, B, H, W, [&](const TSpec<EncPlan>& s) { return (s.flags & TS_P8) && !twins ? 0 : s.C; }));
     e.B = B; e.H = H; e.W = W;
     return RRV_OK;
 }
@@ -1032,7 +1048,7 @@ YuvLaunch yuv_launch_params(const YuvSide& s, bool input, bool wide, bool msb) {
 // out41 != nullptr: the relu4_1 tensor is written THERE ([nb] ring-layout images, zero ring) instead of the plan's c41 (feature cache)
 // norm0_bstride != 0: image b's Decoder.norm[0] entry is norm0 + b * norm0_bstride (per-image state sets)
 // iv: where the rows of the source frames are (null: contiguous frames, whose view is built here — conv_first_k addresses every frame through one)
-int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
+int run_encoder(rrv_handle h, const Seq& q, EncPlan& e, const uint8_t* d_img, InFmt in, int which, const float* norm0, const PadCrop* pc, int nb, Tens* out41 = nullptr,
                 int norm0_bstride = 0, const ImgView* iv = nullptr) {
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
@@ -1043,20 +1059,18 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
         else snprintf(k, sizeof k, "EncoderStyle.slice%d.%d", STYLE_SLICE[i], VGG_IDX[i]);
         return &h->conv[k];
     };
-    auto D_ = [&](int i) { return which == 0 && h->f43_path && ((h->direct_layers >> i) & 1u) != 0; };
+    auto D_ = [&](int i) { return which == 0 && q.f43 && ((h->direct_layers >> i) & 1u) != 0; };
     // Channel-chunk-major tensors (conv_f43.h LAY) between the seven packed layers when ALL of them run conv_f43_k in this launch (the rule
     // of use_f43 says yes for every launch with enough work items: the batched entries); any other mix keeps NHWC throughout.  Where every
     // level is a multiple of 32 pixels wide the choice changes no bit of the result (conv_f43_k stages the same bytes from either layout);
     // elsewhere the edge tiles see other discarded columns (conv_f43.h P8_PAD): rounding noise, GPU test.  Only a plan with the twins
     // (enc_plan) can run the chain.
-    bool p8 = which == 0 && h->f43_path && e.q11.p != nullptr;
-    struct TablesScope { rrv_handle h; ~TablesScope() { h->enc_p8_tables = false; } } tables_scope{h};
+    bool p8 = which == 0 && q.f43 && e.q11.p != nullptr;
     {
         const int lh[8] = {0, H, H / 2, H / 2, H / 4, H / 4, H / 4, H / 4}, lw[8] = {0, W, W / 2, W / 2, W / 4, W / 4, W / 4, W / 4};
         const int le[8] = {0, E_RELU | E_POOL, E_RELU, E_RELU | E_POOL, E_RELU, E_RELU, E_RELU, E_RELU | E_POOL};
-        h->enc_p8_tables = p8;      // priced as a P8 chain first; if one layer then prefers F(2x2,3x3) the chain is NHWC and every layer is priced again as such (in conv())
-        for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, *W_(i), B, lh[i], lw[i], le[i], false, 0, false);
-        h->enc_p8_tables = p8;
+        // priced as a P8 chain first; if one layer then prefers F(2x2,3x3) the chain is NHWC and every layer is priced again as such (in conv())
+        for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, q, *W_(i), B, lh[i], lw[i], le[i], false, 0, false, true);
     }
     const int inf = in.form;         // (the style encoder reads the same forms, in colour: rrv_prepare_style_image_device)
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
@@ -1071,14 +1085,14 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
     }
     static void (*const first_k[IN_FORMS])(FirstP) = {conv_first_k<IN_U8_HWC>, conv_first_k<IN_U8_CHW>, conv_first_k<IN_F32_HWC>, conv_first_k<IN_F32_CHW>,
                                                       conv_first_k<IN_YUV_I420>, conv_first_k<IN_YUV_NV12>, conv_first_k<IN_YUV_I420_16>, conv_first_k<IN_YUV_P016>};
-    RCHK(launch(h, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? yuv_samples_per_pixel(in.cs) * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
-        hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, h->stream, fp);
+    RCHK(launch(h, q, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? yuv_samples_per_pixel(in.cs) * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
+        hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, q.stream, fp);
     }));
     ConvCall c;
     if (p8) {
         auto L = [&](Tens* in, Tens* out, int i, int hh, int ww, int epi, bool out_p8) {
-            ConvCall k{in, out, W_(i), hh, ww}; k.B = B; k.epi = epi; k.in_p8 = true; k.out_p8 = out_p8;
-            return conv(h, k);
+            ConvCall k{in, out, W_(i), hh, ww}; k.B = B; k.epi = epi; k.in_p8 = k.enc_p8 = true; k.out_p8 = out_p8;
+            return conv(h, q, k);
         };
         RCHK(L(&e.q11, &e.q1, 1, H, W, E_RELU | E_POOL, true));
         RCHK(L(&e.q1, &e.q21, 2, H / 2, W / 2, E_RELU, true));
@@ -1088,17 +1102,17 @@ int run_encoder(rrv_handle h, EncPlan& e, const uint8_t* d_img, InFmt in, int wh
         RCHK(L(&e.q32, &e.q33, 6, e.p2.H, e.p2.W, E_RELU, true));
         RCHK(L(&e.q33, &e.p3, 7, e.p2.H, e.p2.W, E_RELU | E_POOL, false));
     } else {
-    c = ConvCall{&e.c11, &e.p1, W_(1), H, W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(1); RCHK(conv(h, c));
-    c = ConvCall{&e.p1, &e.c21, W_(2), H / 2, W / 2}; c.B = B; c.epi = E_RELU; c.direct = D_(2); RCHK(conv(h, c));
-    c = ConvCall{&e.c21, &e.p2, W_(3), H / 2, W / 2}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(3); RCHK(conv(h, c));
-    c = ConvCall{&e.p2, &e.c31, W_(4), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(4); RCHK(conv(h, c));
-    c = ConvCall{&e.c31, &e.c32, W_(5), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(5); RCHK(conv(h, c));
-    c = ConvCall{&e.c32, &e.c33, W_(6), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(6); RCHK(conv(h, c));
-    c = ConvCall{&e.c33, &e.p3, W_(7), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(7); RCHK(conv(h, c));
+    c = ConvCall{&e.c11, &e.p1, W_(1), H, W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(1); RCHK(conv(h, q, c));
+    c = ConvCall{&e.p1, &e.c21, W_(2), H / 2, W / 2}; c.B = B; c.epi = E_RELU; c.direct = D_(2); RCHK(conv(h, q, c));
+    c = ConvCall{&e.c21, &e.p2, W_(3), H / 2, W / 2}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(3); RCHK(conv(h, q, c));
+    c = ConvCall{&e.p2, &e.c31, W_(4), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(4); RCHK(conv(h, q, c));
+    c = ConvCall{&e.c31, &e.c32, W_(5), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(5); RCHK(conv(h, q, c));
+    c = ConvCall{&e.c32, &e.c33, W_(6), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(6); RCHK(conv(h, q, c));
+    c = ConvCall{&e.c33, &e.p3, W_(7), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(7); RCHK(conv(h, q, c));
     }
     c = ConvCall{&e.p3, out41 ? out41 : &e.c41, W_(8), e.p3.H, e.p3.W}; c.B = B; c.epi = E_RELU | (norm0 ? E_NORM1 : 0); c.n1 = norm0; c.direct = D_(8);
     if (norm0) c.par_bstride = norm0_bstride;
-    RCHK(conv(h, c));
+    RCHK(conv(h, q, c));
     return RRV_OK;
 }
 
@@ -1124,7 +1138,9 @@ constexpr OutFmt OUT_F32{false, false, SP_PIXEL}, OUT_U8{true, false, SP_PIXEL};
 inline size_t out_elem(OutFmt f) { return f.u8 ? 1 : sizeof(float); }
 // How one launch sequence reads and writes its frames: both formats and, for the pad geometry, the source window (nullptr: plain frames)
 // iv, ov: the views of the frames as passed / as delivered (null: contiguous; run_encoder / run_last build that view)
-struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; const ImgView* iv = nullptr; const ImgView* ov = nullptr; };
+// caller: the stream of the caller the sequence is ordered with (its work so far precedes the first launch, it waits for the last), if any
+struct CallerOrder { hipStream_t stream = nullptr; bool sync = false; };
+struct FrameIO { InFmt in; OutFmt out; const PadCrop* pc = nullptr; const ImgView* iv = nullptr; const ImgView* ov = nullptr; CallerOrder caller; };
 inline int out_view_layout(OutFmt f) { return f.yuv ? (f.yuv == RRV_LAY_I420 || f.yuv == RRV_LAY_I420_16 ? VL_I420 : VL_NV12) : f.chw ? VL_CHW : VL_HWC; }
 inline size_t out_view_elem(OutFmt f) { return f.yuv ? yuv_sample_bytes(f) : out_elem(f); }      // bytes per element of an output view
 inline ImgView img_view(const rrv_image_view& v) {
@@ -1134,8 +1150,8 @@ inline ImgView img_view(const rrv_image_view& v) {
 
 int padded_size(int n) { return (n + 128 + 63) / 64 * 64; }      // ReshapeTool.process, generate_real_video.py:66-76
 
-// One transfer as an entry states it, both formats included (in, fmt): nothing about a call is kept on the handle, so a format cannot leak
-// into the next call.  The model is named, never inferred from which pointer is set; everything the entries derive from the request
+// One transfer as an entry states it, both formats and the caller's stream included (in, fmt, with): what the call is lives here, how its launch
+// sequences run in their Seq, and the handle keeps only settings and what persists between calls.  The model is named, never inferred from which pointer is set; everything the entries derive from the request
 // (kernel geometry, bytes and elements per frame, the pad and crop window) is computed here and nowhere else.
 //   GLOBAL: Stylization(use_Global=True), one shared state set          FRAME: use_Global=False, statistics per frame
 //   BLEND:  frame b with sum_s wts[b][s] x the state of style s         MASK:  the styles blended per pixel by float32 masks
@@ -1161,6 +1177,8 @@ struct Xfer {
     // The scaled entries: the frames as passed are SH x SW and are resampled to the H x W working frame in front of everything else
     // (run_xfer), so H, W and all that derives from them keep describing the working frame.  0: not scaled, the frames are H x W.
     int SH = 0, SW = 0;
+    // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
+    bool on_stream = false; hipStream_t with = nullptr;
 
     bool scaled() const { return SH != 0 || SW != 0; }
     int IH() const { return scaled() ? SH : H; }              // the frame as passed
@@ -1178,14 +1196,7 @@ struct Xfer {
     }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
     PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
-};
-
-// What a launch sequence with per-image state sets moves on the handle, put back when it ends: the stream, the current state set and
-// the per-image count.  src: what the sequence leaves in the slot's sets (-1: frame-mode statistics, -2: blends), so that the next
-// global entry re-activates its style.  (transfer_device's own scope puts back the stream only and leaves active_src alone.)
-struct SetScope {
-    rrv_handle h; int src;
-    ~SetScope() { h->stream = h->streams[0]; h->cur = &h->sets[0]; h->state_images = 0; h->active_src = src; }
+    CallerOrder order(rrv_handle h) const { return on_stream ? CallerOrder{with, true} : CallerOrder{h->caller_stream, h->caller_sync}; }
 };
 
 // grow-only device buffer of at least n elements (h->d_u8, a staging set's masks); empty after a failed allocation
@@ -1250,53 +1261,53 @@ int kf_split(int H8, int W8) {
 }
 
 // frame: with the batched frame mode's scratch, mask: with the level masks (a plan built without them is rebuilt, and keeps what it had)
-int dec_plan(rrv_handle h, DecPlan& d, int B, int H, int W, bool frame = false, bool mask = false) {       // complete or empty, as enc_plan
+int dec_plan(rrv_handle h, const Seq& q, DecPlan& d, int B, int H, int W, bool frame = false, bool mask = false) {       // complete or empty, as enc_plan
     if (d.B >= B && d.H == H && d.W == W && d.pre && (!frame || d.spart.p) && (!mask || d.lm[0].p)) return RRV_OK;
     if (d.H == H && d.W == W) { frame = frame || d.spart.p; mask = mask || d.lm[0].p; }
     dec_free(h, d);
     const int split = kf_split(H / 8, W / 8);
-    RCHK(plan_talloc(h, d, DEC_T, B, H, W, [&](const TSpec<DecPlan>& s) {
+    RCHK(plan_talloc(h, q, d, DEC_T, B, H, W, [&](const TSpec<DecPlan>& s) {
         if (s.flags & TS_FRAME) return frame ? s.C : 0;
         if (s.flags & TS_MASK) return mask ? s.C : 0;
         if (s.flags & TS_P8) return (h->p8 & 2) && p8_fits(H >> s.level, W >> s.level, s.C) ? s.C : 0;
         if (s.flags & TS_SPLIT) return split > 1 ? s.C * split : 0;
         return s.C;
     }));
-    const int rc = dalloc(h, &d.pre, (size_t)B * H * W * 3, true);
+    const int rc = dalloc(h, q, &d.pre, (size_t)B * H * W * 3, true);
     if (rc != RRV_OK) { dec_free(h, d); return rc; }
     d.B = B; d.H = H; d.W = W;
     return RRV_OK;
 }
 
 // KernelFilter.down_sample (cur -> d.d), split K by kf_split into the plan's d.dpart
-int filter_down(rrv_handle h, const Tens* cur, DecPlan& d, int f, int B) {
+int filter_down(rrv_handle h, const Seq& q, const Tens* cur, DecPlan& d, int f, int B) {
     const int split = kf_split(cur->H, cur->W);
     if (split == 1) {
-        ConvCall c{cur, &d.d, &h->cur->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = E_LRELU;
-        if (h->state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
-        return conv(h, c);
+        ConvCall c{cur, &d.d, &q.set->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = E_LRELU;
+        if (q.state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
+        return conv(h, q, c);
     }
     Tens& t = d.dpart;
-    ConvCall c{cur, &t, &h->cur->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = 0; c.ksplit = split; c.bias = h->cur->fold_down[f].bias;
-    if (h->state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
-    RCHK(conv(h, c));
+    ConvCall c{cur, &t, &q.set->fold_down[f], cur->H, cur->W}; c.B = B; c.epi = 0; c.ksplit = split; c.bias = q.set->fold_down[f].bias;
+    if (q.state_images) { c.w_bstride = 32 * 512 * 16; c.bias_bstride = 256; }
+    RCHK(conv(h, q, c));
     const long npix = (long)B * (d.d.H + 2) * (d.d.W + 2);
     stamp(h, &d.d, B);
-    return launch(h, "sum_parts", 0, 4.0 * 32 * (split + 1) * npix, [&] {
+    return launch(h, q, "sum_parts", 0, 4.0 * 32 * (split + 1) * npix, [&] {
         const long nb = (npix * 8 + 255) / 256;
-        hipLaunchKernelGGL(sum_parts_lrelu_k, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, h->stream, (const float*)t.p, d.d.p, split, npix);
+        hipLaunchKernelGGL(sum_parts_lrelu_k, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, q.stream, (const float*)t.p, d.d.p, split, npix);
     });
 }
 
 // KernelFilter.upsample (d.d -> out) + the residual `cur`, with the per-image folded weights of a state_images launch.  Filter3's
 // epilogue also applies Decoder.norm[1] and its AdaIN affine (frame mode: an identity entry, then * style_std + style_mean).
-int filter_up(rrv_handle h, const Tens* cur, DecPlan& d, Tens* out, int f, int B) {
-    const float* st = h->cur->active;
-    ConvCall u{&d.d, out, &h->cur->fold_up[f], cur->H, cur->W}; u.B = B;
-    if (h->state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
+int filter_up(rrv_handle h, const Seq& q, const Tens* cur, DecPlan& d, Tens* out, int f, int B) {
+    const float* st = q.set->active;
+    ConvCall u{&d.d, out, &q.set->fold_up[f], cur->H, cur->W}; u.B = B;
+    if (q.state_images) { u.w_bstride = 512 * 32 * 16; u.par_bstride = RRV_STATE_FLOATS; }
     u.epi = E_RES | (f == 2 ? E_NORM2 : 0); u.res = cur;
     if (f == 2) { u.n2 = st + SL.norm[N_DEC1]; u.sty = st + SL.sty[3]; }
-    return conv(h, u);
+    return conv(h, q, u);
 }
 
 struct Win { int y0, x0, y1, x1; };     // output window in pixels, tile aligned; y1 == 0: everything
@@ -1308,29 +1319,29 @@ const BlkDesc BLKS[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 
 
 // block k of the per-frame path, fused across its normalisation layers (saved statistics)
 // mid_wait: conv2 is launched behind this event (SeqHook::tail_wait)
-int resblock_frame(rrv_handle h, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr, hipEvent_t mid_wait = nullptr) {
+int resblock_frame(rrv_handle h, const Seq& q, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr, hipEvent_t mid_wait = nullptr) {
     const BlkDesc& b = BLKS[k];
     Tens &xs = d.xs[k], &a = d.a[k], &o = d.o[k], &qa = d.qa[k];
-    const float* st = h->cur->active;
+    const float* st = q.set->active;
     const std::string p = std::string("Decoder.") + b.name;
     ConvCall c;
     // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin,
     // where the plan has one (dec_plan)
-    const bool p8 = qa.p && use_f43(h, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
+    const bool p8 = qa.p && use_f43(h, q, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
                     !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
     Tens* a_in = p8 ? &qa : &a;
     // conv1 behind the upsample and, in the same kernel, the 1x1 shortcut at the input resolution: up(conv1x1(x)) == conv1x1(up(x))
     c = ConvCall{&in, a_in, &h->conv[p + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1; c.n1 = st + SL.norm[b.n1];
     c.sc_out = &xs; c.out_p8 = p8;
-    if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
+    if (q.state_images) c.par_bstride = RRV_STATE_FLOATS;
     if (wa) { c.wy0 = wa->y0; c.wx0 = wa->x0; c.wy1 = wa->y1; c.wx1 = wa->x1; }
-    RCHK(conv(h, c));
-    if (mid_wait) HIPCHK(hipStreamWaitEvent(h->stream, mid_wait, 0));
+    RCHK(conv(h, q, c));
+    if (mid_wait) HIPCHK(hipStreamWaitEvent(q.stream, mid_wait, 0));
     c = ConvCall{a_in, &o, &h->conv[p + ".conv2"], a.H, a.W}; c.B = B; c.in_p8 = p8;
-    if (h->state_images) c.par_bstride = RRV_STATE_FLOATS;
+    if (q.state_images) c.par_bstride = RRV_STATE_FLOATS;
     c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[b.n2]; c.res = &xs; c.n2 = st + SL.norm[b.nada]; c.sty = st + SL.sty[b.sty];
     if (wo) { c.wy0 = wo->y0; c.wx0 = wo->x0; c.wy1 = wo->y1; c.wx1 = wo->x1; }
-    RCHK(conv(h, c));
+    RCHK(conv(h, q, c));
     return RRV_OK;
 }
 
@@ -1350,7 +1361,7 @@ LastFn last_kernel(OutFmt f) {
 // the view's frame stride apart); the pre-clamp tap's bookkeeping stays that of the whole batch
 // ov: where the rows of the delivered frames are (null: contiguous frames, whose view is built here)
 struct FrameRange { int first, count; };
-int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const ImgView* ov, const Win* wl = nullptr,
+int run_last(rrv_handle h, const Seq& q, const Tens& o2, int B, int H, int W, void* d_out, OutFmt fmt, float* pre, const PadCrop* pc, const ImgView* ov, const Win* wl = nullptr,
              const FrameRange* fr = nullptr) {
     LastP lp{o2.p, H, W, B, h->last_w, h->last_b, d_out, pre, (W + 15) / 16, (H + 15) / 16,
              pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, 0, 0};
@@ -1373,10 +1384,9 @@ int run_last(rrv_handle h, const Tens& o2, int B, int H, int W, void* d_out, Out
     h->last_pre = pre; h->last_pre_H = H; h->last_pre_W = W; h->last_pre_B = B;
     const unsigned tiles = (unsigned)(lp.tiles_x * lp.tiles_y * LB), resident = (unsigned)h->n_cus * 4;     // persistent: 4 workgroups of 35 KB per CU
     const unsigned grid = tiles < resident ? tiles : resident;
-    note_grid(h, grid, -1);
-    return launch(h, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
-        hipLaunchKernelGGL(last_kernel(fmt), dim3(grid), dim3(256), 0, h->stream, lp);
-    });
+    return launch(h, q, "conv_last", 2.0 * LB * H * W * 576 * 3, (256.0 + (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt))) * LB * H * W, [&] {
+        hipLaunchKernelGGL(last_kernel(fmt), dim3(grid), dim3(256), 0, q.stream, lp);
+    }, -1.0, grid, -1);
 }
 
 // What host_pipeline asks of one launch sequence beyond its frames.
@@ -1394,9 +1404,10 @@ struct SeqHook {
 };
 
 // feats != nullptr: skip the encoder and start from one cached raw relu4_1 feature per image (ring layout, [1,H/8,W/8,512])
-// h->state_images: 0 = every image uses the current state set, B = image b uses set cur + b (frames and cached features alike)
-// slot: the (stream, workspace) pair the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
-int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* const* feats = nullptr,
+// q.state_images: 0 = every image uses the state set q.set, B = image b uses q.set + b (frames and cached features alike)
+// q.slot: the slot whose workspace the launches use; the caller chooses it (next_device_slot, sub-batch parity, ticket, group)
+// Writes no state set and leaves active_src alone.
+int transfer_device(rrv_handle h, const Seq& q, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io, const float* const* feats = nullptr,
                     const SeqHook* hk = nullptr) {
     const PadCrop* const pc = io.pc;
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
@@ -1406,38 +1417,36 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     RCHK(check_frame(h, H, W, "transfer"));
     if (h->active_src == -1) return fail(h, RRV_E_STATE, "state not computed: call compute() (or set_state) before transfer()");
     if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer: batch must be in 1..64");
-    struct StreamScope { rrv_handle h; ~StreamScope() { h->stream = h->streams[0]; h->f43_path = false; } } scope{h};
-    h->stream = h->streams[slot];
-    if (slot < 2) h->set_images[slot] = 0;      // (the grouped multi-style entry counts its images after this returns)
-    h->f43_path = true;            // the per-frame path: layers with an F(4x4,3x3) pack may run on conv_f43_k (use_f43)
-    if (h->caller_sync) {    // stream-ordered against the caller: work queued on its stream so far precedes ours
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->slot_ev[slot], 0));
+    rrv_ctx::Slot& sl = h->slots[q.slot];
+    sl.set_images = 0;       // (the grouped multi-style entry counts its images after this returns)
+    if (io.caller.sync) {    // stream-ordered against the caller: work queued on its stream so far precedes ours
+        HIPCHK(hipEventRecord(sl.ev, io.caller.stream));
+        HIPCHK(hipStreamWaitEvent(q.stream, sl.ev, 0));
     }
-    EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
-    DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
-    RCHK(enc_plan(h, e, B, H, W, true));
-    RCHK(dec_plan(h, d, B, Ho, Wo));
+    EncPlan& e = pick_plan(h, sl.enc, B, H, W);
+    DecPlan& d = pick_plan(h, sl.dec, B, Ho, Wo);
+    RCHK(enc_plan(h, q, e, B, H, W, true));
+    RCHK(dec_plan(h, q, d, B, Ho, Wo));
     e.gen = d.gen = ++h->launch_gen;
-    const float* st = h->cur->active;
+    const float* st = q.set->active;
     // per-image state: every image's relu4_1 is normalised with ITS set's Decoder.norm[0] entry
-    if (h->state_images ? h->state_images != B : (feats && B != 1)) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per image");
-    const long stride = h->state_images ? (long)RRV_STATE_FLOATS : 0;
+    if (q.state_images ? q.state_images != B : (feats && B != 1)) return fail(h, RRV_E_ARG, "transfer: per-image state needs one state set per image");
+    const long stride = q.state_images ? (long)RRV_STATE_FLOATS : 0;
     if (feats) {  // cached raw relu4_1 features: Decoder.norm[0] (saved stats + clamp) as a pointwise step per image
         for (int b = 0; b < B; ++b) {
             Tens src; src.p = const_cast<float*>(feats[b]); src.B = 1; src.H = H / 8; src.W = W / 8; src.C = 512;
             Tens dst = e.c41; dst.B = 1; dst.p = e.c41.p + (size_t)b * e.c41.img_floats();
             const float* n0 = st + (size_t)b * stride + SL.norm[N_DEC0];
-            RCHK(pointwise(h, src, dst, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
+            RCHK(pointwise(h, q, src, dst, n0, n0 + 512, false, nullptr, 0, nullptr, nullptr, n0 + 1024, n0 + 1536));
         }
         stamp(h, &e.c41, B);      // (pointwise stamped the one-image views: the debug taps see the tensor as written)
     } else {
-        RCHK(run_encoder(h, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, (int)stride, io.iv));
+        RCHK(run_encoder(h, q, e, d_in, io.in, 0, st + SL.norm[N_DEC0], pc, B, nullptr, (int)stride, io.iv));
     }
     const Tens* cur = &e.c41;
     for (int f = 0; f < 3; ++f) {
-        RCHK(filter_down(h, cur, d, f, B));
-        RCHK(filter_up(h, cur, d, &d.f[f], f, B));
+        RCHK(filter_down(h, q, cur, d, f, B));
+        RCHK(filter_up(h, q, cur, d, &d.f[f], f, B));
         cur = &d.f[f];
     }
     // On-device crop: nothing outside the crop window is delivered, so the full-resolution layers only compute the
@@ -1454,7 +1463,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
         const Win crop{pc->top, pc->left, pc->top + pc->src_H, pc->left + pc->src_W};
         wl = grow(crop, 0);        // conv_last output tiles
         wo = grow(crop, 1);        // slice2.conv2 output feeding them
-        if (use_f43(h, h->conv["Decoder.slice2.conv2"], B, Ho, Wo, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false)) {      // 32 x 32 pixel work items: round the window out to them
+        if (use_f43(h, q, h->conv["Decoder.slice2.conv2"], B, Ho, Wo, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false)) {      // 32 x 32 pixel work items: round the window out to them
             const int lh = (Ho + 31) & ~31, lw = (Wo + 31) & ~31;
             wo = Win{wo.y0 & ~31, wo.x0 & ~31, (wo.y1 + 31) & ~31, (wo.x1 + 31) & ~31};
             if (wo.y1 > lh) wo.y1 = lh;
@@ -1464,24 +1473,24 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
     }
     for (int k = 0; k < 3; ++k) {       // the windows apply to the full-resolution block only
         const bool win = roi && k == 2;
-        RCHK(resblock_frame(h, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr, hk && k == 2 ? hk->tail_wait : nullptr));
+        RCHK(resblock_frame(h, q, B, k, k ? d.o[k - 1] : d.f[2], d, win ? &wa : nullptr, win ? &wo : nullptr, hk && k == 2 ? hk->tail_wait : nullptr));
     }
     if (hk && hk->piece > 0 && hk->piece < B) {
         int i = 0;
         for (int b0 = 0; b0 < B; b0 += hk->piece, ++i) {
             const FrameRange fr{b0, B - b0 < hk->piece ? B - b0 : hk->piece};
-            RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr, &fr));
+            RCHK(run_last(h, q, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr, &fr));
             const size_t off = (size_t)b0 * hk->frame_bytes;
-            HIPCHK(hipEventRecord(hk->ev[i], h->stream));
+            HIPCHK(hipEventRecord(hk->ev[i], q.stream));
             HIPCHK(hipStreamWaitEvent(hk->copy, hk->ev[i], 0));
             HIPCHK(hipMemcpyAsync(hk->h_dst + off, (const char*)d_out + off, (size_t)fr.count * hk->frame_bytes, hipMemcpyDeviceToHost, hk->copy));
         }
     } else {
-        RCHK(run_last(h, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr));
+        RCHK(run_last(h, q, d.o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov, roi ? &wl : nullptr));
     }
-    if (h->caller_sync) {    // ... and whatever the caller queues next sees our output
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->stream));
-        HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
+    if (io.caller.sync) {    // ... and whatever the caller queues next sees our output
+        HIPCHK(hipEventRecord(sl.ev, q.stream));
+        HIPCHK(hipStreamWaitEvent(io.caller.stream, sl.ev, 0));
     }
     if (h->debug) RCHK(debug_verify(h, "transfer"));
     return RRV_OK;
@@ -1498,7 +1507,7 @@ int transfer_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, i
 enum { WALK_STOP = 1 };     // (RRV_E_* are negative)
 // norm(x, y, n, res, sty) is the normalisation step: y = x normalised with entry n [+ res, upsampled 2x] [AdaIN with style entry sty].
 template <class Stat, class Norm>
-int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], bool fused_sc, bool last_adain, Stat&& stat, Norm&& norm) {
+int unfused_blocks(rrv_handle h, const Seq& q, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], bool fused_sc, bool last_adain, Stat&& stat, Norm&& norm) {
     const Tens* in = &x;
     for (int k = 0; k < 3; ++k) {
         const BlkDesc& b = BLKS[k];
@@ -1507,12 +1516,12 @@ int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[
         ConvCall c;
         c = ConvCall{in, &a[k], &h->conv[p + ".conv1"], H2, W2}; c.B = B; c.ups = true; c.epi = E_LRELU;
         if (fused_sc) c.sc_out = &xs[k];
-        RCHK(conv(h, c));
+        RCHK(conv(h, q, c));
         RCHK(stat(a[k], b.n1, 3 * k));
         RCHK(norm(a[k], a[k], b.n1, (const Tens*)nullptr, -1));
-        c = ConvCall{&a[k], &o[k], &h->conv[p + ".conv2"], H2, W2}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, c));
+        c = ConvCall{&a[k], &o[k], &h->conv[p + ".conv2"], H2, W2}; c.B = B; c.epi = E_LRELU; RCHK(conv(h, q, c));
         RCHK(stat(o[k], b.n2, 3 * k + 1));
-        if (!fused_sc) { c = ConvCall{in, &xs[k], &h->conv[p + ".conv_shortcut"], in->H, in->W}; c.B = B; RCHK(conv(h, c)); }
+        if (!fused_sc) { c = ConvCall{in, &xs[k], &h->conv[p + ".conv_shortcut"], in->H, in->W}; c.B = B; RCHK(conv(h, q, c)); }
         RCHK(norm(o[k], o[k], b.n2, (const Tens*)&xs[k], -1));
         RCHK(stat(o[k], b.nada, 3 * k + 2));     // (a fused pointwise + statistics pass measured slower than the two kernels)
         if (k < 2 || last_adain) RCHK(norm(o[k], o[k], b.nada, (const Tens*)nullptr, b.sty));
@@ -1522,18 +1531,18 @@ int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[
 }
 // the walk with the saved statistics of state `st` applied by pointwise_k (apply_norm): the preparation pass and the frame mode
 template <class Stat>
-int unfused_blocks(rrv_handle h, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], const float* st, long par_bstride, bool fused_sc,
+int unfused_blocks(rrv_handle h, const Seq& q, int B, const Tens& x, Tens (&xs)[3], Tens (&a)[3], Tens (&o)[3], const float* st, long par_bstride, bool fused_sc,
                    bool last_adain, Stat&& stat) {
-    return unfused_blocks(h, B, x, xs, a, o, fused_sc, last_adain, stat,
-                          [&](const Tens& t, Tens& y, int n, const Tens* res, int sty) { return apply_norm(h, t, y, st, n, res, sty, par_bstride); });
+    return unfused_blocks(h, q, B, x, xs, a, o, fused_sc, last_adain, stat,
+                          [&](const Tens& t, Tens& y, int n, const Tens* res, int sty) { return apply_norm(h, q, t, y, st, n, res, sty, par_bstride); });
 }
 
 // ---- preparation: Decoder.compute for one style ---------------------------------------------
 void prep_free(rrv_handle h) { plan_tfree(h->prep, PREP_T); }
 int prep_chans(const TSpec<PrepPlan>& s, bool streaming) { return s.flags & (streaming ? TS_RES : TS_STREAM) ? 0 : s.C; }
 // rrv_compute's workspace for B frames (streaming: a group of B) of relu4_1 features hh x ww; complete or empty
-int prep_plan(rrv_handle h, int B, int hh, int ww, bool streaming) {
-    return plan_talloc(h, h->prep, PREP_T, B, hh << 3, ww << 3, [&](const TSpec<PrepPlan>& s) { return prep_chans(s, streaming); });
+int prep_plan(rrv_handle h, const Seq& q, int B, int hh, int ww, bool streaming) {
+    return plan_talloc(h, q, h->prep, PREP_T, B, hh << 3, ww << 3, [&](const TSpec<PrepPlan>& s) { return prep_chans(s, streaming); });
 }
 // what prep_plan allocates
 size_t prep_bytes(int B, int hh, int ww, bool streaming) {
@@ -1551,7 +1560,7 @@ size_t prep_bytes(int B, int hh, int ww, bool streaming) {
 enum { ST_NORM0 = 0, ST_FILTER = 1 /* +f */, ST_NORM1 = 4, ST_BLOCKS = 5 /* +3k: n1, n2, nada */, ST_COUNT = 14 };
 
 // on the plan's content batch (rrv_compute)
-int compute_style(rrv_handle h, int sid) {
+int compute_style(rrv_handle h, const Seq& q, int sid) {
     StyleState& S = h->styles[sid];
     float* st = S.blob;
     PrepPlan& P = h->prep;
@@ -1564,38 +1573,38 @@ int compute_style(rrv_handle h, int sid) {
     auto body = [&]() -> int {
         // norm[0].compute on the batch (style_network_global.py:396); the style half of the filter predictions
         // (normalized_style :397 through F.down_sample, :161-172) was evaluated once in prepare_style (S.smean)
-        RCHK(chan_stats(h, content, 1, st + SL.norm[N_DEC0]));
+        RCHK(chan_stats(h, q, content, 1, st + SL.norm[N_DEC0]));
         if (stop == ST_NORM0) return WALK_STOP;
-        RCHK(apply_norm(h, content, cn, st, N_DEC0));
+        RCHK(apply_norm(h, q, content, cn, st, N_DEC0));
         Tens* cur = &cn; Tens* other = &nxt;
         for (int f = 0; f < 3; ++f) {
             char pre[64];
             snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
             for (int g = 0; g < 2; ++g) {   // FilterPredictor.compute (:161-172) for F1 then F2
                 const ConvW* wp = &h->conv[std::string(pre) + (g ? ".F2" : ".F1") + ".down_sample.0"];
-                ConvCall c{cur, &t32, wp, hh, ww}; c.B = B; RCHK(conv(h, c));
-                RCHK(chan_stats(h, t32, 0, cmean));
-                hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + g],
+                ConvCall c{cur, &t32, wp, hh, ww}; c.B = B; RCHK(conv(h, q, c));
+                RCHK(chan_stats(h, q, t32, 0, cmean));
+                hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, q.stream, (const float*)h->fc_w[2 * f + g],
                                    (const float*)h->fc_b[2 * f + g], (const float*)cmean, (const float*)(S.smean + (2 * f + g) * 32), st + SL.filt[2 * f + g]);
                 HIPCHK(hipGetLastError());
             }
-            RCHK(fold_filters(h, st, f));
+            RCHK(fold_filters(h, q, st, f));
             // KernelFilter.compute (:223-230): only frame 0 passes through apply_filter (Q1)
             Tens cur0 = *cur; cur0.B = 1;
-            ConvCall c{&cur0, &d32, &h->cur->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, c));
-            ConvCall cu{&d32, &u, &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
-            RCHK(pointwise(h, *cur, *other, nullptr, nullptr, false, &u, 1, nullptr, nullptr));
+            ConvCall c{&cur0, &d32, &q.set->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, q, c));
+            ConvCall cu{&d32, &u, &q.set->fold_up[f], hh, ww}; RCHK(conv(h, q, cu));
+            RCHK(pointwise(h, q, *cur, *other, nullptr, nullptr, false, &u, 1, nullptr, nullptr));
             if (stop == ST_FILTER + f) return WALK_STOP;
             Tens* t = cur; cur = other; other = t;
         }
         h->active_src = -1;   // folded weights now belong to this style's blob; re-activate below
         // AdaIN_compute(1) (style_network_global.py:428)
-        RCHK(chan_stats(h, *cur, 1, st + SL.norm[N_DEC1]));
+        RCHK(chan_stats(h, q, *cur, 1, st + SL.norm[N_DEC1]));
         if (stop == ST_NORM1) return WALK_STOP;
-        RCHK(apply_norm(h, *cur, *cur, st, N_DEC1, nullptr, 3));
+        RCHK(apply_norm(h, q, *cur, *cur, st, N_DEC1, nullptr, 3));
         // AdaIN_compute(k + 2) ends block k; nothing reads the last block's normalised output
-        return unfused_blocks(h, B, *cur, P.xs, P.a, P.o, st, 0, false, false, [&](const Tens& t, int n, int point) -> int {
-            RCHK(chan_stats(h, t, 1, st + SL.norm[n]));
+        return unfused_blocks(h, q, B, *cur, P.xs, P.a, P.o, st, 0, false, false, [&](const Tens& t, int n, int point) -> int {
+            RCHK(chan_stats(h, q, t, 1, st + SL.norm[n]));
             return stop == ST_BLOCKS + point && stop != ST_COUNT - 1 ? WALK_STOP : RRV_OK;
         });
     };
@@ -1603,7 +1612,7 @@ int compute_style(rrv_handle h, int sid) {
     const bool stopped = rc == WALK_STOP;      // rrv_debug_prep_stop: the state is left as far as it got, not computed
     if (stopped) { rc = RRV_OK; h->active_src = -1; }
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute");
-    (void)hipStreamSynchronize(h->stream);
+    (void)hipStreamSynchronize(q.stream);
     if (rc == RRV_OK && !stopped) S.computed = true;
     if (rc == RRV_OK && !stopped) rc = filter_conditioning(h, S);
     return rc;
@@ -1621,9 +1630,9 @@ int compute_style(rrv_handle h, int sid) {
 
 // ---- batched frame mode: B <= MS_GROUP_MAX frames per launch sequence ----------------------------------------------------
 // The chain above for B frames at once (the one-frame entry is B = 1).  Every frame's statistics, predicted filters and folded KernelFilter weights go
-// to its own state set (h->cur + b: the sets MS_GROUP_MAX * slot .., initialised from style 0's blob), and every per-frame kernel
+// to its own state set (q.set + b: the sets MS_GROUP_MAX * slot .., initialised from style 0's blob), and every per-frame kernel
 // runs over the B images with image b's result in set b or in row b of the plan's scratch (DecPlan::spart ..).  The statistics
-// kernels partition every image on its own (chan_stats1_images) and the convolutions are F(2x2,3x3) (f43_path stays false), so
+// kernels partition every image on its own (chan_stats1_images) and the convolutions are F(2x2,3x3) (Seq::f43 is false), so
 // an image's bits do not depend on the batch it rides in.  Style 0's blob is only read.
 
 // interior row b of a TS_FRAME scratch tensor (ring layout, B = 1, H = images): contiguous, frame_row_stride floats apart
@@ -1631,47 +1640,45 @@ float* frame_row(const Tens& t) { return t.p + (size_t)(t.W + 3) * t.C; }
 long frame_row_stride(const Tens& t) { return (long)(t.W + 2) * t.C; }
 
 // per-image statistics of the t.B images of t into norm entry `n` of each image's state set: ONE read of the tensor + a merge
-int chan_stats1_images(rrv_handle h, const Tens& t, const DecPlan& d, int n) {
+int chan_stats1_images(rrv_handle h, const Seq& q, const Tens& t, const DecPlan& d, int n) {
     const int nblk = t.H < 512 ? t.H : 512;        // per image min(H, 512) blocks of whole rows (~2 blocks per CU keep the merge short), whatever the batch
     if ((size_t)nblk * 6 * t.C > (size_t)d.spart.W * d.spart.C || t.B > d.spart.H) return fail(h, RRV_E_ARG, "chan_stats1_images: scratch too small");
     double* part = (double*)frame_row(d.spart);
     const long pbs = frame_row_stride(d.spart) / 2;
-    float* out = h->cur->active + SL.norm[n];
+    float* out = q.set->active + SL.norm[n];
     StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, part, 0, 0, 1, pbs};
     stamp(h, &d.spart, t.B);
-    RCHK(launch(h, "chan_stat1", 0, 4.0 * t.B * t.H * t.W * t.C, [&] { hipLaunchKernelGGL(chan_stat1_k, dim3(nblk, t.B), dim3(256), 0, h->stream, sp); }));
-    return launch(h, "chan_stat1_final", 0, 0, [&] {
-        hipLaunchKernelGGL(chan_stat1_final_k, dim3((t.C + 3) / 4, t.B), dim3(256), 0, h->stream, (const double*)part, nblk, t.C, out, pbs, (long)RRV_STATE_FLOATS);
+    RCHK(launch(h, q, "chan_stat1", 0, 4.0 * t.B * t.H * t.W * t.C, [&] { hipLaunchKernelGGL(chan_stat1_k, dim3(nblk, t.B), dim3(256), 0, q.stream, sp); }));
+    return launch(h, q, "chan_stat1_final", 0, 0, [&] {
+        hipLaunchKernelGGL(chan_stat1_final_k, dim3((t.C + 3) / 4, t.B), dim3(256), 0, q.stream, (const double*)part, nblk, t.C, out, pbs, (long)RRV_STATE_FLOATS);
     });
 }
 
-// B frames ([B][H][W][3] uint8; with pc: [B][src_H][src_W][3], padded on the way in, cropped on the way out) on `slot`
-int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io) {
+// B frames ([B][H][W][3] uint8; with pc: [B][src_H][src_W][3], padded on the way in, cropped on the way out) on q.slot, with the slot's own sets (q.set)
+int frame_mode_device(rrv_handle h, const Seq& q, const uint8_t* d_in, int B, int H, int W, void* d_out, const FrameIO& io) {
     const PadCrop* const pc = io.pc;
-    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
+    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || q.slot < 0 || q.slot > 1) return fail(h, RRV_E_ARG, "frame mode: batch must be in 1..16 on slot 0 or 1");
     StyleState& S = h->styles[0];
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
-    SetScope scope{h, -1};
-    h->active_src = -1;                                   // set 0 (slot 0) is overwritten: a later global entry re-activates its state
-    h->stream = h->streams[slot];
-    h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];
-    EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
-    DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
-    RCHK(enc_plan(h, e, B, H, W, true));
-    RCHK(dec_plan(h, d, B, Ho, Wo, true));
+    rrv_ctx::Slot& sl = h->slots[q.slot];
+    h->active_src = -1;                                   // the slot's sets (q.set ..; slot 0: set 0) are overwritten: a later global entry re-activates its state
+    EncPlan& e = pick_plan(h, sl.enc, B, H, W);
+    DecPlan& d = pick_plan(h, sl.dec, B, Ho, Wo);
+    RCHK(enc_plan(h, q, e, B, H, W, true));
+    RCHK(dec_plan(h, q, d, B, Ho, Wo, true));
     e.gen = d.gen = ++h->launch_gen;
-    float* st = h->cur->active;                          // image b: st + b * RRV_STATE_FLOATS
+    float* st = q.set->active;                          // image b: st + b * RRV_STATE_FLOATS
     const long PS = RRV_STATE_FLOATS;
-    RCHK(launch(h, "frame_sets_init", 0, 8.0 * B * RRV_STATE_FLOATS, [&] {
-        hipLaunchKernelGGL(frame_sets_init_k, dim3((RRV_STATE_FLOATS + 255) / 256, B), dim3(256), 0, h->stream, (const float*)S.blob, st, (int)RRV_STATE_FLOATS,
+    RCHK(launch(h, q, "frame_sets_init", 0, 8.0 * B * RRV_STATE_FLOATS, [&] {
+        hipLaunchKernelGGL(frame_sets_init_k, dim3((RRV_STATE_FLOATS + 255) / 256, B), dim3(256), 0, q.stream, (const float*)S.blob, st, (int)RRV_STATE_FLOATS,
                            SL.norm[N_DEC1], 512);
     }));
-    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
+    RCHK(run_encoder(h, q, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     const int hh = c41.H, ww = c41.W;
     // Decoder.norm[0] with each frame's statistics
-    RCHK(chan_stats1_images(h, c41, d, N_DEC0));
-    RCHK(apply_norm(h, c41, c41, st, N_DEC0, nullptr, -1, PS));
+    RCHK(chan_stats1_images(h, q, c41, d, N_DEC0));
+    RCHK(apply_norm(h, q, c41, c41, st, N_DEC0, nullptr, -1, PS));
     Tens fo[3], xs[3], a[3], o[3];
     for (int k = 0; k < 3; ++k) {
         fo[k] = d.f[k]; xs[k] = d.xs[k]; a[k] = d.a[k]; o[k] = d.o[k];
@@ -1683,40 +1690,40 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
     float* const cm = frame_row(d.scm);
     const long Sbs = frame_row_stride(d.srect), cbs = frame_row_stride(d.scm);
     stamp(h, &d.srect, B); stamp(h, &d.scm, B);
-    h->state_images = B > 1 ? B : 0;
+    Seq qf = q;      // the KernelFilter convs alone read per-image state
+    qf.state_images = B > 1 ? B : 0;
     const Tens* cur = &c41;
     for (int f = 0; f < 3; ++f) {
         // (one part: splitting an image's pixels over several blocks per channel quad measured slower, the merge in pred_mean_k costs more)
-        RCHK(launch(h, "rect_sums", 0, 4.0 * B * hh * ww * 512, [&] {
-            hipLaunchKernelGGL(rect_sums_k, dim3(128, 1, B), dim3(256), 0, h->stream, (const float*)cur->p, hh, ww, 512, Sr, Sbs);
+        RCHK(launch(h, q, "rect_sums", 0, 4.0 * B * hh * ww * 512, [&] {
+            hipLaunchKernelGGL(rect_sums_k, dim3(128, 1, B), dim3(256), 0, q.stream, (const float*)cur->p, hh, ww, 512, Sr, Sbs);
         }));
         for (int g = 0; g < 2; ++g) {
             char key[96];
             snprintf(key, sizeof key, "Decoder.Filter%d.F%d.down_sample.0", f + 1, g + 1);
             const ConvW& wp = h->conv[key];
-            RCHK(launch(h, "pred_mean", 2.0 * B * 32 * 4608, 0, [&] {
-                hipLaunchKernelGGL(pred_mean_k, dim3(32, B), dim3(256), 0, h->stream, (const float*)wp.raw, (const float*)wp.bias, (const float*)Sr, 1, 512,
+            RCHK(launch(h, q, "pred_mean", 2.0 * B * 32 * 4608, 0, [&] {
+                hipLaunchKernelGGL(pred_mean_k, dim3(32, B), dim3(256), 0, q.stream, (const float*)wp.raw, (const float*)wp.bias, (const float*)Sr, 1, 512,
                                    1.0 / ((double)hh * ww), cm + 32 * g, Sbs, cbs);
             }));
-            RCHK(launch(h, "fc_filter", 2.0 * B * 1024 * 64, 0, [&] {
-                hipLaunchKernelGGL(fc_filter_k, dim3(4, B), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + g], (const float*)h->fc_b[2 * f + g],
+            RCHK(launch(h, q, "fc_filter", 2.0 * B * 1024 * 64, 0, [&] {
+                hipLaunchKernelGGL(fc_filter_k, dim3(4, B), dim3(256), 0, q.stream, (const float*)h->fc_w[2 * f + g], (const float*)h->fc_b[2 * f + g],
                                    (const float*)(cm + 32 * g), (const float*)(S.smean + (2 * f + g) * 32), st + SL.filt[2 * f + g], (int)cbs, (int)RRV_STATE_FLOATS);
             }));
         }
-        RCHK(fold_filters(h, st, f, B));
-        RCHK(filter_down(h, cur, d, f, B));
-        RCHK(filter_up(h, cur, d, &fo[f], f, B));
+        RCHK(fold_filters(h, q, st, f, B));
+        RCHK(filter_down(h, qf, cur, d, f, B));
+        RCHK(filter_up(h, qf, cur, d, &fo[f], f, B));
         cur = &fo[f];
     }
-    h->state_images = 0;
     // full tensors: each frame's statistics cover its whole (padded) frame, as in the reference
-    RCHK(unfused_blocks(h, B, *cur, xs, a, o, st, PS, true, true, [&](const Tens& t, int n, int) { return chan_stats1_images(h, t, d, n); }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
+    RCHK(unfused_blocks(h, q, B, *cur, xs, a, o, st, PS, true, true, [&](const Tens& t, int n, int) { return chan_stats1_images(h, q, t, d, n); }));
+    RCHK(run_last(h, q, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
     // the launches above wrote views; the debug taps (rrv_debug_copy_tensor_ex) read the plan's own tensors
     stamp(h, &e.c41, B);
     for (int k = 0; k < 3; ++k)
         for (Tens* t : {&d.f[k], &d.xs[k], &d.a[k], &d.o[k]}) stamp(h, t, B);
-    h->set_images[slot] = B;
+    sl.set_images = B;
     if (h->debug) RCHK(debug_verify(h, "transfer (batched frame mode)"));
     return RRV_OK;
 }
@@ -1729,14 +1736,14 @@ int frame_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H,
 // saved statistics of the S styles in place of per-frame ones: encoder (raw relu4_1) -> mask pyramid -> masked norm[0] -> per
 // filter {down_sample raw (split K as filter_down) -> mask_filter_k (F1(p), LeakyReLU, F2(p)) -> upsample + residual} -> masked
 // norm[1] + AdaIN -> per block {conv1 + shortcut -> masked norm1 -> conv2 -> masked norm2 + shortcut -> masked AdaIN} -> slice1.
-// F(2x2,3x3) throughout (f43_path stays false) and a split that follows the frame size: an image's bits do not depend on its batch.
+// F(2x2,3x3) throughout (Seq::f43 is false) and a split that follows the frame size: an image's bits do not depend on its batch.
 // The styles' blobs are only read and no state set is written: the entries around a masked call keep their bits.
 
 LevelMask level_mask(const Tens& t, int S, bool one) {
     return LevelMask{t.p + (size_t)(t.W + 3) * t.C, one ? 0 : (long)t.img_floats(), (t.W + 2) * t.C, S};
 }
 
-int mask_norm(rrv_handle h, const Tens& x, Tens& y, const MaskStates& ms, int S, int n, const Tens* res, int sty, const LevelMask& m) {
+int mask_norm(rrv_handle h, const Seq& q, const Tens& x, Tens& y, const MaskStates& ms, int S, int n, const Tens* res, int sty, const LevelMask& m) {
     if (x.C % 64) return fail(h, RRV_E_ARG, "mask_norm: channels must be a multiple of 64");
     MaskNormP p{x.p, y.p, x.B, x.H, x.W, x.C, ms, S, SL.norm[n], sty < 0 ? -1 : SL.sty[sty], res ? res->p : nullptr, res ? res->H : 0, res ? res->W : 0, m, 1};
     // one block per image row and group of 64 channels; small tensors split their rows so that a few hundred blocks exist
@@ -1745,26 +1752,25 @@ int mask_norm(rrv_handle h, const Tens& x, Tens& y, const MaskStates& ms, int S,
     const int max_segs = (x.W + 15) / 16;
     p.segs = segs > max_segs ? max_segs : segs;
     stamp(h, &y, x.B);
-    return launch(h, "mask_norm", 0, 8.0 * x.B * x.H * x.W * x.C, [&] { hipLaunchKernelGGL(mask_norm_k, dim3((unsigned)(rows * p.segs)), dim3(256), 0, h->stream, p); });
+    return launch(h, q, "mask_norm", 0, 8.0 * x.B * x.H * x.W * x.C, [&] { hipLaunchKernelGGL(mask_norm_k, dim3((unsigned)(rows * p.segs)), dim3(256), 0, q.stream, p); });
 }
 
 typedef void (*PyrFn)(const MaskPyrP&, dim3, hipStream_t);
 template <int S> void pyr_launch(const MaskPyrP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(mask_pyramid_k<S>, grid, dim3(256), 0, s, p); }
 
-// B <= MS_GROUP_MAX frames on `slot` (geometry as frame_mode_device); d_mask: [Bm][S][mH][mW] float32 in HBM, Bm = B or 1, at the
+// B <= MS_GROUP_MAX frames on q.slot (geometry as frame_mode_device); d_mask: [Bm][S][mH][mW] float32 in HBM, Bm = B or 1, at the
 // resolution of the frames as the caller passed them (pc: the unpadded frame)
-int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, int W, const float* d_mask, int S, bool one_mask, void* d_out,
+int mask_mode_device(rrv_handle h, const Seq& q, const uint8_t* d_in, int B, int H, int W, const float* d_mask, int S, bool one_mask, void* d_out,
                      const FrameIO& io) {
     const PadCrop* const pc = io.pc;
-    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || slot < 0 || slot > 1) return fail(h, RRV_E_ARG, "masked transfer: batch must be in 1..16 on slot 0 or 1");
+    if (B < 1 || B > rrv_ctx::MS_GROUP_MAX || q.slot < 0 || q.slot > 1) return fail(h, RRV_E_ARG, "masked transfer: batch must be in 1..16 on slot 0 or 1");
     const int Ho = H / 8 * 8, Wo = W / 8 * 8;
-    struct Scope { rrv_handle h; ~Scope() { h->stream = h->streams[0]; } } scope{h};
-    h->stream = h->streams[slot];
-    h->set_images[slot] = 0;                              // this launch keeps no per-image state set
-    EncPlan& e = pick_plan(h, h->enc_frame[slot], B, H, W);
-    DecPlan& d = pick_plan(h, h->dec[slot], B, Ho, Wo);
-    RCHK(enc_plan(h, e, B, H, W, true));
-    RCHK(dec_plan(h, d, B, Ho, Wo, false, true));
+    rrv_ctx::Slot& sl = h->slots[q.slot];
+    sl.set_images = 0;                                    // this launch keeps no per-image state set
+    EncPlan& e = pick_plan(h, sl.enc, B, H, W);
+    DecPlan& d = pick_plan(h, sl.dec, B, Ho, Wo);
+    RCHK(enc_plan(h, q, e, B, H, W, true));
+    RCHK(dec_plan(h, q, d, B, Ho, Wo, false, true));
     e.gen = d.gen = ++h->launch_gen;
     MaskStates ms{};
     for (int s = 0; s < S; ++s) ms.blob[s] = h->styles[s].blob;
@@ -1777,13 +1783,13 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
         }
         static const PyrFn pyr[8] = {pyr_launch<1>, pyr_launch<2>, pyr_launch<3>, pyr_launch<4>, pyr_launch<5>, pyr_launch<6>, pyr_launch<7>, pyr_launch<8>};
         const int nm = one_mask ? 1 : B;
-        RCHK(launch(h, "mask_pyramid", 0, 8.0 * nm * S * Ho * Wo, [&] {
-            pyr[S - 1](pp, dim3((unsigned)(((Ho / 8) * (Wo / 8) + 255) / 256), (unsigned)nm), h->stream);
+        RCHK(launch(h, q, "mask_pyramid", 0, 8.0 * nm * S * Ho * Wo, [&] {
+            pyr[S - 1](pp, dim3((unsigned)(((Ho / 8) * (Wo / 8) + 255) / 256), (unsigned)nm), q.stream);
         }));
     }
     LevelMask lm[4];
     for (int l = 0; l < 4; ++l) lm[l] = level_mask(d.lm[l], S, one_mask);
-    RCHK(run_encoder(h, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
+    RCHK(run_encoder(h, q, e, d_in, io.in, 0, nullptr, pc, B, nullptr, 0, io.iv));
     Tens c41 = e.c41; c41.B = B;                         // views of B images (plans are grow-only)
     Tens fo[3], xs[3], a[3], o[3], dd = d.d, dpart = d.dpart;
     dd.B = dpart.B = B;
@@ -1792,7 +1798,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
         fo[k].B = xs[k].B = a[k].B = o[k].B = B;
     }
     // Decoder.norm[0], clamped, with the statistics blended at every relu4_1 pixel
-    RCHK(mask_norm(h, c41, c41, ms, S, N_DEC0, nullptr, -1, lm[3]));
+    RCHK(mask_norm(h, q, c41, c41, ms, S, N_DEC0, nullptr, -1, lm[3]));
     const int split = kf_split(c41.H, c41.W);
     const Tens* cur = &c41;
     for (int f = 0; f < 3; ++f) {
@@ -1804,25 +1810,25 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
         Tens& raw = split > 1 ? dpart : dd;
         ConvCall c{cur, &raw, &wd, cur->H, cur->W}; c.B = B; c.epi = 0; c.bias = h->zero_bias;
         if (split > 1) c.ksplit = split;
-        RCHK(conv(h, c));
+        RCHK(conv(h, q, c));
         MaskFilterP fp{raw.p, split, dd.p, wd.bias, ms, S, SL.filt[2 * f], SL.filt[2 * f + 1], lm[3], B, dd.H, dd.W};
         const long npix = (long)B * dd.H * dd.W;
         stamp(h, &dd, B);
-        RCHK(launch(h, "mask_filter", 2.0 * npix * 2048 * (S + 1), 4.0 * npix * 32 * (split + 1), [&] {
-            hipLaunchKernelGGL(mask_filter_k, dim3((unsigned)((npix + 63) / 64)), dim3(256), mask_filter_smem(S), h->stream, fp);
+        RCHK(launch(h, q, "mask_filter", 2.0 * npix * 2048 * (S + 1), 4.0 * npix * 32 * (split + 1), [&] {
+            hipLaunchKernelGGL(mask_filter_k, dim3((unsigned)((npix + 63) / 64)), dim3(256), mask_filter_smem(S), q.stream, fp);
         }));
         ConvCall u{&dd, &fo[f], &wu, cur->H, cur->W}; u.B = B; u.epi = E_RES; u.res = cur;
-        RCHK(conv(h, u));
+        RCHK(conv(h, q, u));
         cur = &fo[f];
     }
     // Decoder.norm[1] + the relu4_1 AdaIN affine
-    RCHK(mask_norm(h, *cur, fo[2], ms, S, N_DEC1, nullptr, 3, lm[3]));
-    RCHK(unfused_blocks(h, B, *cur, xs, a, o, true, true, [](const Tens&, int, int) { return (int)RRV_OK; },
+    RCHK(mask_norm(h, q, *cur, fo[2], ms, S, N_DEC1, nullptr, 3, lm[3]));
+    RCHK(unfused_blocks(h, q, B, *cur, xs, a, o, true, true, [](const Tens&, int, int) { return (int)RRV_OK; },
                         [&](const Tens& t, Tens& y, int n, const Tens* res, int sty) {
                             const int l = t.H == d.lm[0].H ? 0 : t.H == d.lm[1].H ? 1 : 2;
-                            return mask_norm(h, t, y, ms, S, n, res, sty, lm[l]);
+                            return mask_norm(h, q, t, y, ms, S, n, res, sty, lm[l]);
                         }));
-    RCHK(run_last(h, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
+    RCHK(run_last(h, q, o[2], B, Ho, Wo, d_out, io.out, d.pre, pc, io.ov));
     stamp(h, &e.c41, B); stamp(h, &d.d, B);
     if (split > 1) stamp(h, &d.dpart, B);
     for (int k = 0; k < 3; ++k)
@@ -1841,7 +1847,7 @@ int mask_mode_device(rrv_handle h, int slot, const uint8_t* d_in, int B, int H, 
 // statistics already known, contributes its partial (chan_merge_k) and is dropped.  Workspace = one group, whatever B.
 
 // one group's partial statistics of tensor t merged into accumulator `slot` (n_a elements per channel seen before)
-int chan_stats_group(rrv_handle h, const Tens& t, bool want_m2, int slot, double n_a) {
+int chan_stats_group(rrv_handle h, const Seq& q, const Tens& t, bool want_m2, int slot, double n_a) {
     const long npix = (long)t.B * t.H * t.W;
     int nblk = (int)((npix + 255) / 256);
     if (nblk > 1024) nblk = 1024;
@@ -1851,57 +1857,57 @@ int chan_stats_group(rrv_handle h, const Tens& t, bool want_m2, int slot, double
     double* acc = h->stat_acc + (size_t)slot * 4 * 512;
     StatP sp{t.p, t.B, t.H, t.W, t.C, nullptr, h->stat_part, 0, ppb};
     const int fb = (t.C + 15) / 16;
-    hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, h->stream, sp);
+    hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, q.stream, sp);
     if (want_m2) {
-        hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, h->stream, (const double*)h->stat_part, nblk, t.C, (double)npix, 0, (const float*)nullptr, h->stat_mean);
+        hipLaunchKernelGGL(chan_final_k, dim3(fb), dim3(256), 0, q.stream, (const double*)h->stat_part, nblk, t.C, (double)npix, 0, (const float*)nullptr, h->stat_mean);
         sp.pass = 1; sp.mean = h->stat_mean; sp.part = h->stat_part2;
-        hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, h->stream, sp);
+        hipLaunchKernelGGL(chan_stat_k, dim3(nblk), dim3(256), 0, q.stream, sp);
     }
-    hipLaunchKernelGGL(chan_merge_k, dim3(fb), dim3(256), 0, h->stream, (const double*)h->stat_part, want_m2 ? (const double*)h->stat_part2 : (const double*)nullptr,
+    hipLaunchKernelGGL(chan_merge_k, dim3(fb), dim3(256), 0, q.stream, (const double*)h->stat_part, want_m2 ? (const double*)h->stat_part2 : (const double*)nullptr,
                        nblk, t.C, (double)npix, (const float*)h->stat_mean, acc, n_a);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
-int chan_stats_finish(rrv_handle h, int slot, int C, double N, int mode, float* out) {
-    hipLaunchKernelGGL(chan_finish_k, dim3((C + 255) / 256), dim3(256), 0, h->stream, (const double*)(h->stat_acc + (size_t)slot * 4 * 512), C, N, mode, out);
+int chan_stats_finish(rrv_handle h, const Seq& q, int slot, int C, double N, int mode, float* out) {
+    hipLaunchKernelGGL(chan_finish_k, dim3((C + 255) / 256), dim3(256), 0, q.stream, (const double*)(h->stat_acc + (size_t)slot * 4 * 512), C, N, mode, out);
     HIPCHK(hipGetLastError());
     return RRV_OK;
 }
 
 // Decoder.compute prefix of one group (`grp`: nb raw relu4_1 features) up to sync point `stage`, whose partial
 // statistics are merged (n_a = elements per channel already merged at that stage's resolution: frames_before * H * W).
-int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int frames_before) {
+int stream_prefix(rrv_handle h, const Seq& q, int sid, const Tens& grp, int nb, int stage, int frames_before) {
     StyleState& S = h->styles[sid];
     float* st = S.blob;
     PrepPlan& P = h->prep;
     const int hh = grp.H, ww = grp.W;
     auto view = [&](Tens& t) { Tens v = t; v.B = nb; return v; };
     Tens g = grp; g.B = nb;
-    if (stage == ST_NORM0) return chan_stats_group(h, g, true, 0, (double)frames_before * hh * ww);
+    if (stage == ST_NORM0) return chan_stats_group(h, q, g, true, 0, (double)frames_before * hh * ww);
     Tens cn = view(P.cn), nxt = view(P.nxt), t32 = view(P.t32);
-    RCHK(apply_norm(h, g, cn, st, N_DEC0));
+    RCHK(apply_norm(h, q, g, cn, st, N_DEC0));
     Tens* cur = &cn; Tens* other = &nxt;
     for (int f = 0; f < 3; ++f) {
         if (stage == ST_FILTER + f) {
             char pre[64];
             snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
             for (int gi = 0; gi < 2; ++gi) {       // FilterPredictor.compute (:161-172): mean over (B,HW) of down_sample(content)
-                ConvCall c{cur, &t32, &h->conv[std::string(pre) + (gi ? ".F2" : ".F1") + ".down_sample.0"], hh, ww}; c.B = nb; RCHK(conv(h, c));
-                RCHK(chan_stats_group(h, t32, false, gi, (double)frames_before * hh * ww));
+                ConvCall c{cur, &t32, &h->conv[std::string(pre) + (gi ? ".F2" : ".F1") + ".down_sample.0"], hh, ww}; c.B = nb; RCHK(conv(h, q, c));
+                RCHK(chan_stats_group(h, q, t32, false, gi, (double)frames_before * hh * ww));
             }
             return RRV_OK;
         }
-        RCHK(pointwise(h, *cur, *other, nullptr, nullptr, false, &P.su[f], 1, nullptr, nullptr));   // + frame 0's residual (Q1)
+        RCHK(pointwise(h, q, *cur, *other, nullptr, nullptr, false, &P.su[f], 1, nullptr, nullptr));   // + frame 0's residual (Q1)
         Tens* t = cur; cur = other; other = t;
     }
-    if (stage == ST_NORM1) return chan_stats_group(h, *cur, true, 0, (double)frames_before * hh * ww);
-    RCHK(apply_norm(h, *cur, *cur, st, N_DEC1, nullptr, 3));
+    if (stage == ST_NORM1) return chan_stats_group(h, q, *cur, true, 0, (double)frames_before * hh * ww);
+    RCHK(apply_norm(h, q, *cur, *cur, st, N_DEC1, nullptr, 3));
     Tens xs[3], a[3], o[3];
     for (int k = 0; k < 3; ++k) { xs[k] = view(P.xs[k]); a[k] = view(P.a[k]); o[k] = view(P.o[k]); }
     // the statistics before `stage` are known; at `stage` the group's partial is merged and nothing further is launched
-    const int rc = unfused_blocks(h, nb, *cur, xs, a, o, st, 0, false, true, [&](const Tens& t, int, int point) -> int {
+    const int rc = unfused_blocks(h, q, nb, *cur, xs, a, o, st, 0, false, true, [&](const Tens& t, int, int point) -> int {
         if (ST_BLOCKS + point != stage) return RRV_OK;
-        RCHK(chan_stats_group(h, t, true, 0, (double)frames_before * t.H * t.W));
+        RCHK(chan_stats_group(h, q, t, true, 0, (double)frames_before * t.H * t.W));
         return WALK_STOP;
     });
     if (rc != RRV_OK) return rc == WALK_STOP ? RRV_OK : rc;
@@ -1909,7 +1915,7 @@ int stream_prefix(rrv_handle h, int sid, const Tens& grp, int nb, int stage, int
 }
 
 // Decoder.compute for one style over h->patches in groups of the plan's P.grp.B frames (rrv_compute)
-int compute_style_streaming(rrv_handle h, int sid) {
+int compute_style_streaming(rrv_handle h, const Seq& q, int sid) {
     StyleState& S = h->styles[sid];
     float* st = S.blob;
     PrepPlan& P = h->prep;
@@ -1922,36 +1928,36 @@ int compute_style_streaming(rrv_handle h, int sid) {
             for (int g0 = 0; g0 < B; g0 += G) {
                 const int nb = B - g0 < G ? B - g0 : G;
                 for (int b = 0; b < nb; ++b)
-                    HIPCHK(hipMemcpyAsync(P.grp.p + (size_t)b * img, h->patches[g0 + b], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-                RCHK(stream_prefix(h, sid, P.grp, nb, stage, g0));
+                    HIPCHK(hipMemcpyAsync(P.grp.p + (size_t)b * img, h->patches[g0 + b], img * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
+                RCHK(stream_prefix(h, q, sid, P.grp, nb, stage, g0));
             }
             // the sync point: every frame has contributed
             if (stage == ST_NORM0) {
-                RCHK(chan_stats_finish(h, 0, 512, (double)B * hh * ww, 1, st + SL.norm[N_DEC0]));
+                RCHK(chan_stats_finish(h, q, 0, 512, (double)B * hh * ww, 1, st + SL.norm[N_DEC0]));
             } else if (stage >= ST_FILTER && stage < ST_FILTER + 3) {
                 const int f = stage - ST_FILTER;
                 for (int gi = 0; gi < 2; ++gi) {
-                    RCHK(chan_stats_finish(h, gi, 32, (double)B * hh * ww, 0, h->prep_cmean));
-                    hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, h->stream, (const float*)h->fc_w[2 * f + gi], (const float*)h->fc_b[2 * f + gi],
+                    RCHK(chan_stats_finish(h, q, gi, 32, (double)B * hh * ww, 0, h->prep_cmean));
+                    hipLaunchKernelGGL(fc_filter_k, dim3(4), dim3(256), 0, q.stream, (const float*)h->fc_w[2 * f + gi], (const float*)h->fc_b[2 * f + gi],
                                        (const float*)h->prep_cmean, (const float*)(S.smean + (2 * f + gi) * 32), st + SL.filt[2 * f + gi]);
                     HIPCHK(hipGetLastError());
                 }
-                RCHK(fold_filters(h, st, f));
+                RCHK(fold_filters(h, q, st, f));
                 h->active_src = -1;
                 // KernelFilter.compute (:223-230): frame 0 alone passes through apply_filter; its residual u_f is what every frame receives (Q1)
-                HIPCHK(hipMemcpyAsync(P.f0.p, h->patches[0], img * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(P.f0.p, h->patches[0], img * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
                 Tens cn0 = P.cn; cn0.B = 1;
-                RCHK(apply_norm(h, P.f0, cn0, st, N_DEC0));
-                for (int f2 = 0; f2 < f; ++f2) RCHK(pointwise(h, cn0, cn0, nullptr, nullptr, false, &P.su[f2], 1, nullptr, nullptr));
-                ConvCall c{&cn0, &P.d32, &h->cur->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, c));
-                ConvCall cu{&P.d32, &P.su[f], &h->cur->fold_up[f], hh, ww}; RCHK(conv(h, cu));
+                RCHK(apply_norm(h, q, P.f0, cn0, st, N_DEC0));
+                for (int f2 = 0; f2 < f; ++f2) RCHK(pointwise(h, q, cn0, cn0, nullptr, nullptr, false, &P.su[f2], 1, nullptr, nullptr));
+                ConvCall c{&cn0, &P.d32, &q.set->fold_down[f], hh, ww}; c.epi = E_LRELU; RCHK(conv(h, q, c));
+                ConvCall cu{&P.d32, &P.su[f], &q.set->fold_up[f], hh, ww}; RCHK(conv(h, q, cu));
             } else if (stage == ST_NORM1) {
-                RCHK(chan_stats_finish(h, 0, 512, (double)B * hh * ww, 1, st + SL.norm[N_DEC1]));
+                RCHK(chan_stats_finish(h, q, 0, 512, (double)B * hh * ww, 1, st + SL.norm[N_DEC1]));
             } else {
                 const int k = (stage - ST_BLOCKS) / 3, w = (stage - ST_BLOCKS) % 3;
                 const BlkDesc& b = BLKS[k];
                 const double N = (double)B * (hh << (k + 1)) * (ww << (k + 1));
-                RCHK(chan_stats_finish(h, 0, b.cout, N, 1, st + SL.norm[w == 0 ? b.n1 : (w == 1 ? b.n2 : b.nada)]));
+                RCHK(chan_stats_finish(h, q, 0, b.cout, N, 1, st + SL.norm[w == 0 ? b.n1 : (w == 1 ? b.n2 : b.nada)]));
             }
             if (stage == stop && stop != ST_COUNT - 1) return WALK_STOP;
         }
@@ -1961,7 +1967,7 @@ int compute_style_streaming(rrv_handle h, int sid) {
     const bool stopped = rc == WALK_STOP;      // rrv_debug_prep_stop
     if (stopped) rc = RRV_OK;
     if (rc == RRV_OK && h->debug) rc = debug_verify(h, "Decoder.compute (streaming)");
-    (void)hipStreamSynchronize(h->stream);
+    (void)hipStreamSynchronize(q.stream);
     h->active_src = -1;
     if (rc == RRV_OK && !stopped) S.computed = true;
     if (rc == RRV_OK && !stopped) rc = filter_conditioning(h, S);
@@ -2017,14 +2023,13 @@ int rrv_create(int device, rrv_handle* out) {
     (void)rrv_yuv_input_matrix(RRV_YUV_BT601, 0, h->yuv_in.m8);
     (void)rrv_yuv_matrix(RRV_YUV_BT601, 0, h->yuv_out.m8);      // what players assume for untagged yuv420p
     bool ok = hipSetDevice(device) == hipSuccess;
-    for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipStreamCreateWithFlags(&h->streams[i], hipStreamNonBlocking) == hipSuccess;
+    for (rrv_ctx::Slot& sl : h->slots) ok = ok && hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
         delete h;
         return RRV_E_HIP;
     }
-    h->stream = h->streams[0];
     ok = ok && hipStreamCreateWithFlags(&h->copy_in, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&h->copy_out, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < RRV_MAX_SLOTS; ++i) ok = hipEventCreateWithFlags(&h->slot_ev[i], hipEventDisableTiming) == hipSuccess;
+    for (rrv_ctx::Slot& sl : h->slots) ok = ok && hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) == hipSuccess;
     for (auto& st : h->hstage)
         for (hipEvent_t* e : {&st.in_done, &st.k_done, &st.out_done}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     for (auto& st : h->hstage)
@@ -2066,9 +2071,9 @@ int rrv_create(int device, rrv_handle* out) {
 }
 
 static void free_plans(rrv_handle h) {
-    for (auto& pair : h->enc_frame) for (EncPlan& e : pair) enc_free(e);
+    for (rrv_ctx::Slot& sl : h->slots) for (EncPlan& e : sl.enc) enc_free(e);
     enc_free(h->enc_add); enc_free(h->enc_style);
-    for (auto& pair : h->dec) for (DecPlan& d : pair) dec_free(h, d);
+    for (rrv_ctx::Slot& sl : h->slots) for (DecPlan& d : sl.dec) dec_free(h, d);
     prep_free(h);
 }
 
@@ -2095,15 +2100,16 @@ int rrv_debug_selftest(rrv_handle h) {
     RCHK(sync_all(h));
     const int saved = h->debug;
     h->debug = 2;
+    const Seq q = base_seq(h);
     Tens t;
-    int rc = talloc(h, &t, 2, 8, 8, 64);
+    int rc = talloc(h, q, &t, 2, 8, 8, 64);
     if (rc == RRV_OK) rc = debug_verify(h, "selftest (clean)");
     int caught = 0;
     if (rc == RRV_OK) {
-        hipLaunchKernelGGL(dbg_poke_k, dim3(1), dim3(1), 0, h->stream, t.p, (long)t.img_floats() + 5);       // ring pixel (0,0) of image 1
+        hipLaunchKernelGGL(dbg_poke_k, dim3(1), dim3(1), 0, q.stream, t.p, (long)t.img_floats() + 5);       // ring pixel (0,0) of image 1
         if (debug_verify(h, "selftest (ring)") == RRV_E_DEBUG) ++caught;
-        HIPCHK(hipMemsetAsync(t.p + t.img_floats(), 0, 64 * sizeof(float), h->stream));
-        hipLaunchKernelGGL(dbg_poke_k, dim3(1), dim3(1), 0, h->stream, t.p, -3L);                            // guard band in front
+        HIPCHK(hipMemsetAsync(t.p + t.img_floats(), 0, 64 * sizeof(float), q.stream));
+        hipLaunchKernelGGL(dbg_poke_k, dim3(1), dim3(1), 0, q.stream, t.p, -3L);                            // guard band in front
         if (debug_verify(h, "selftest (guard)") == RRV_E_DEBUG) ++caught;
     }
     tfree(&t);
@@ -2144,7 +2150,7 @@ int rrv_destroy(rrv_handle h) {
     for (StyleState& s : h->styles) { if (s.blob) (void)hipFree(s.blob); if (s.smean) (void)hipFree(s.smean); tfree(&s.map); }
     if (h->d_u8) (void)hipFree(h->d_u8);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
-    for (float* q : h->rs_buf) if (q) (void)hipFree(q);
+    for (rrv_ctx::Slot& sl : h->slots) if (sl.rs_buf) (void)hipFree(sl.rs_buf);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
@@ -2162,7 +2168,7 @@ int rrv_destroy(rrv_handle h) {
     if (h->copy_in) (void)hipStreamDestroy(h->copy_in);
     if (h->copy_out) (void)hipStreamDestroy(h->copy_out);
     for (ProfEntry& e : h->prof) { (void)hipEventDestroy(e.e0); (void)hipEventDestroy(e.e1); }
-    for (int i = 0; i < RRV_MAX_SLOTS; ++i) { (void)hipStreamDestroy(h->streams[i]); if (h->slot_ev[i]) (void)hipEventDestroy(h->slot_ev[i]); }
+    for (rrv_ctx::Slot& sl : h->slots) { (void)hipStreamDestroy(sl.stream); if (sl.ev) (void)hipEventDestroy(sl.ev); }
     delete h;
     return RRV_OK;
 }
@@ -2183,11 +2189,12 @@ int rrv_finalize_weights(rrv_handle h) {
     if (!h) return RRV_E_ARG;
     if (h->finalized) return RRV_OK;
     HIPCHK(hipSetDevice(h->dev));
-    RCHK(dalloc(h, &h->zero_bias, 512, true));
+    const Seq q = base_seq(h);
+    RCHK(dalloc(h, q, &h->zero_bias, 512, true));
     {   // the fixed-size scratch (rrv_ctx::stat_part ..): 1024 partial blocks x 3 x 512 channels at most per partial buffer
         constexpr size_t PART = (size_t)1024 * 3 * 512, ACC = (size_t)2 * 4 * 512, FLOATS = 512 + 64;
         float* base;
-        RCHK(dalloc(h, &base, (2 * PART + ACC) * 2 + FLOATS));
+        RCHK(dalloc(h, q, &base, (2 * PART + ACC) * 2 + FLOATS));
         h->stat_part = (double*)base; h->stat_part2 = h->stat_part + PART; h->stat_acc = h->stat_part2 + PART;
         h->stat_mean = (float*)(h->stat_acc + ACC); h->prep_cmean = h->stat_mean + 512;
     }
@@ -2198,23 +2205,23 @@ int rrv_finalize_weights(rrv_handle h) {
             else snprintf(k, sizeof k, "EncoderStyle.slice%d.%d", STYLE_SLICE[i], VGG_IDX[i]);
             if (i == 0) {
                 float* raw = nullptr;
-                RCHK(upload(h, std::string(k) + ".weight", &raw, 64 * 27));
-                RCHK(dalloc(h, &h->first_w[which], 27 * 64, false));
-                hipLaunchKernelGGL(pack_first_k, dim3(7), dim3(256), 0, h->stream, (const float*)raw, h->first_w[which]);
+                RCHK(upload(h, q, std::string(k) + ".weight", &raw, 64 * 27));
+                RCHK(dalloc(h, q, &h->first_w[which], 27 * 64, false));
+                hipLaunchKernelGGL(pack_first_k, dim3(7), dim3(256), 0, q.stream, (const float*)raw, h->first_w[which]);
                 HIPCHK(hipGetLastError());
-                RCHK(upload(h, std::string(k) + ".bias", &h->first_b[which], 64));
+                RCHK(upload(h, q, std::string(k) + ".bias", &h->first_b[which], 64));
                 if (which == 0) {
-                    RCHK(dalloc(h, &h->first_wg, 1216, false));
-                    hipLaunchKernelGGL(pack_first_grey_k, dim3(3), dim3(256), 0, h->stream, (const float*)raw, (const float*)h->first_b[0], h->first_wg);
+                    RCHK(dalloc(h, q, &h->first_wg, 1216, false));
+                    hipLaunchKernelGGL(pack_first_grey_k, dim3(3), dim3(256), 0, q.stream, (const float*)raw, (const float*)h->first_b[0], h->first_wg);
                     HIPCHK(hipGetLastError());
                 }
-                HIPCHK(hipStreamSynchronize(h->stream));
+                HIPCHK(hipStreamSynchronize(q.stream));
                 (void)hipFree(raw);
             } else {
-                RCHK(make_conv(h, k, VGG_COUT[i], VGG_CIN[i], 9, true));
+                RCHK(make_conv(h, q, k, VGG_COUT[i], VGG_CIN[i], 9, true));
                 // per-frame encoder, conv1_2 .. conv3_4 (conv4_1 = 256 -> 512 stays on F(2x2,3x3): alone it costs more of the
                 // parity margin than the other ten layers together, profiles/r03_f43_numerics.txt, for 3.5 % of the frame)
-                if (which == 0 && i < 8) { h->conv[k].f43_bit = i - 1; RCHK(pack_f43(h, h->conv[k])); }
+                if (which == 0 && i < 8) { h->conv[k].f43_bit = i - 1; RCHK(pack_f43(h, q, h->conv[k])); }
             }
         }
     }
@@ -2222,47 +2229,47 @@ int rrv_finalize_weights(rrv_handle h) {
     const char* bn[3] = {"slice4", "slice3", "slice2"};
     for (int b = 0; b < 3; ++b) {
         const std::string p = std::string("Decoder.") + bn[b];
-        RCHK(make_conv(h, p + ".conv1", bc[b][1], bc[b][0], 9, true, false));
-        RCHK(pack_ups(h, h->conv[p + ".conv1"]));
-        RCHK(make_conv(h, p + ".conv2", bc[b][1], bc[b][1], 9, true));
+        RCHK(make_conv(h, q, p + ".conv1", bc[b][1], bc[b][0], 9, true, false));
+        RCHK(pack_ups(h, q, h->conv[p + ".conv1"]));
+        RCHK(make_conv(h, q, p + ".conv2", bc[b][1], bc[b][1], 9, true));
         h->conv[p + ".conv2"].f43_bit = 7 + b;
-        RCHK(pack_f43(h, h->conv[p + ".conv2"]));
-        RCHK(make_conv(h, p + ".conv_shortcut", bc[b][1], bc[b][0], 1, false));
-        RCHK(pack_ups_sc(h, h->conv[p + ".conv1"], h->conv[p + ".conv_shortcut"]));
+        RCHK(pack_f43(h, q, h->conv[p + ".conv2"]));
+        RCHK(make_conv(h, q, p + ".conv_shortcut", bc[b][1], bc[b][0], 1, false));
+        RCHK(pack_ups_sc(h, q, h->conv[p + ".conv1"], h->conv[p + ".conv_shortcut"]));
     }
     {
         float* raw = nullptr;
-        RCHK(upload(h, "Decoder.slice1.weight", &raw, 3 * 64 * 9));
-        RCHK(dalloc(h, &h->last_w, 2 * 4 * 64 * 4, false));
-        hipLaunchKernelGGL(pack_last_k, dim3(8), dim3(256), 0, h->stream, (const float*)raw, h->last_w);
+        RCHK(upload(h, q, "Decoder.slice1.weight", &raw, 3 * 64 * 9));
+        RCHK(dalloc(h, q, &h->last_w, 2 * 4 * 64 * 4, false));
+        hipLaunchKernelGGL(pack_last_k, dim3(8), dim3(256), 0, q.stream, (const float*)raw, h->last_w);
         HIPCHK(hipGetLastError());
-        RCHK(dalloc(h, &h->last_b, 4, true));
+        RCHK(dalloc(h, q, &h->last_b, 4, true));
         auto it = h->hostw.find("Decoder.slice1.bias");
         if (it == h->hostw.end() || it->second.size() != 3) return fail(h, RRV_E_WEIGHTS, "missing weight Decoder.slice1.bias");
-        HIPCHK(hipMemcpyAsync(h->last_b, it->second.data(), 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpyAsync(h->last_b, it->second.data(), 3 * sizeof(float), hipMemcpyHostToDevice, q.stream));
+        HIPCHK(hipStreamSynchronize(q.stream));
         (void)hipFree(raw);
     }
     for (int f = 0; f < 3; ++f) {
         char pre[64];
         snprintf(pre, sizeof pre, "Decoder.Filter%d", f + 1);
-        RCHK(make_conv(h, std::string(pre) + ".down_sample.0", 32, 512, 9, true, false));
-        RCHK(make_conv(h, std::string(pre) + ".upsample.0", 512, 32, 9, true, false));
+        RCHK(make_conv(h, q, std::string(pre) + ".down_sample.0", 32, 512, 9, true, false));
+        RCHK(make_conv(h, q, std::string(pre) + ".upsample.0", 512, 32, 9, true, false));
         // the masked multi-style entries run both layers unfolded, around mask_filter_k, on the row-split transform-domain kernel
-        RCHK(pack_wino(h, h->conv[std::string(pre) + ".down_sample.0"]));
-        RCHK(pack_wino(h, h->conv[std::string(pre) + ".upsample.0"]));
+        RCHK(pack_wino(h, q, h->conv[std::string(pre) + ".down_sample.0"]));
+        RCHK(pack_wino(h, q, h->conv[std::string(pre) + ".upsample.0"]));
         for (int g = 0; g < 2; ++g) {
-            const std::string q = std::string(pre) + (g ? ".F2" : ".F1");
-            RCHK(make_conv(h, q + ".down_sample.0", 32, 512, 9, true));
-            RCHK(upload(h, q + ".FC.weight", &h->fc_w[2 * f + g], 1024 * 64));
-            RCHK(upload(h, q + ".FC.bias", &h->fc_b[2 * f + g], 1024));
+            const std::string fp = std::string(pre) + (g ? ".F2" : ".F1");
+            RCHK(make_conv(h, q, fp + ".down_sample.0", 32, 512, 9, true));
+            RCHK(upload(h, q, fp + ".FC.weight", &h->fc_w[2 * f + g], 1024 * 64));
+            RCHK(upload(h, q, fp + ".FC.bias", &h->fc_b[2 * f + g], 1024));
         }
         {   // folded KernelFilter weights of every state set, set-major inside one allocation per kind
             constexpr int NS = rrv_ctx::N_SETS;
             float *fd_raw, *fd_bias, *fd_pkw, *fu_raw, *fu_pkw;
-            RCHK(dalloc(h, &fd_raw, (size_t)NS * 32 * 512 * 9)); RCHK(dalloc(h, &fd_bias, (size_t)NS * 256));      // bias[32], then zeros: the split-K slabs' bias
-            RCHK(dalloc(h, &fd_pkw, (size_t)NS * 32 * 512 * 16));
-            RCHK(dalloc(h, &fu_raw, (size_t)NS * 512 * 32 * 9)); RCHK(dalloc(h, &fu_pkw, (size_t)NS * 512 * 32 * 16));
+            RCHK(dalloc(h, q, &fd_raw, (size_t)NS * 32 * 512 * 9)); RCHK(dalloc(h, q, &fd_bias, (size_t)NS * 256));      // bias[32], then zeros: the split-K slabs' bias
+            RCHK(dalloc(h, q, &fd_pkw, (size_t)NS * 32 * 512 * 16));
+            RCHK(dalloc(h, q, &fu_raw, (size_t)NS * 512 * 32 * 9)); RCHK(dalloc(h, q, &fu_pkw, (size_t)NS * 512 * 32 * 16));
             for (int i = 0; i < NS; ++i) {
                 ConvW& fd = h->sets[i].fold_down[f];
                 fd.Cout = 32; fd.Cin = 512; fd.taps = 9; fd.BN = 32;
@@ -2276,10 +2283,10 @@ int rrv_finalize_weights(rrv_handle h) {
     }
     {
         float* act;
-        RCHK(dalloc(h, &act, (size_t)rrv_ctx::N_SETS * RRV_STATE_FLOATS));
+        RCHK(dalloc(h, q, &act, (size_t)rrv_ctx::N_SETS * RRV_STATE_FLOATS));
         for (int i = 0; i < rrv_ctx::N_SETS; ++i) h->sets[i].active = act + (size_t)i * RRV_STATE_FLOATS;
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(q.stream));
     h->hostw.clear();
     h->finalized = true;
     return RRV_OK;
@@ -2396,10 +2403,10 @@ int rrv_image_view_check(const rrv_image_view* v, int B, int H, int W, int outpu
     return v && view_check(*v, B, H, W, output != 0, nullptr) ? RRV_OK : RRV_E_ARG;
 }
 
-// the handle's stream waits for what `stream` (NULL: the null stream) holds so far
+// slot 0's stream waits for what `stream` (NULL: the null stream) holds so far
 static int wait_for_stream(rrv_handle h, hipStream_t stream) {
-    HIPCHK(hipEventRecord(h->slot_ev[0], stream));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->slot_ev[0], 0));
+    HIPCHK(hipEventRecord(h->slots[0].ev, stream));
+    HIPCHK(hipStreamWaitEvent(h->slots[0].stream, h->slots[0].ev, 0));
     return RRV_OK;
 }
 
@@ -2408,42 +2415,43 @@ static int prepare_style(rrv_handle h, const void* style, bool device, InFmt in,
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
+    const Seq q = base_seq(h);
     StyleState& S = h->styles[sid];
-    if (!S.blob) RCHK(dalloc(h, &S.blob, RRV_STATE_FLOATS));
+    if (!S.blob) RCHK(dalloc(h, q, &S.blob, RRV_STATE_FLOATS));
     if (device) {
         RCHK(wait_for_stream(h, stream));
     } else {
         RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)Hs * Ws * 3));
-        HIPCHK(hipMemcpyAsync(h->d_u8, style, (size_t)Hs * Ws * 3, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_u8, style, (size_t)Hs * Ws * 3, hipMemcpyHostToDevice, q.stream));
     }
-    RCHK(enc_plan(h, h->enc_style, 1, Hs, Ws));
+    RCHK(enc_plan(h, q, h->enc_style, 1, Hs, Ws));
     EncPlan& e = h->enc_style;
-    const int rc_enc = run_encoder(h, e, device ? (const uint8_t*)style : h->d_u8, in, 1, nullptr, nullptr, 1);
-    if (rc_enc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc_enc; }      // (the caller's image is not read after the call returns)
+    const int rc_enc = run_encoder(h, q, e, device ? (const uint8_t*)style : h->d_u8, in, 1, nullptr, nullptr, 1);
+    if (rc_enc != RRV_OK) { (void)hipStreamSynchronize(q.stream); return rc_enc; }      // (the caller's image is not read after the call returns)
     // cal_mean_std at relu1_1..relu4_1 (style_network_global.py:304-331)
     const Tens* taps[4] = {&e.c11, &e.c21, &e.c31, &e.c41};
-    for (int k = 0; k < 4; ++k) RCHK(chan_stats(h, *taps[k], 2, S.blob + SL.sty[k]));
-    RCHK(talloc(h, &S.map, 1, e.c41.H, e.c41.W, 512));
-    HIPCHK(hipMemcpyAsync(S.map.p, e.c41.p, e.c41.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    for (int k = 0; k < 4; ++k) RCHK(chan_stats(h, q, *taps[k], 2, S.blob + SL.sty[k]));
+    RCHK(talloc(h, q, &S.map, 1, e.c41.H, e.c41.W, 512));
+    HIPCHK(hipMemcpyAsync(S.map.p, e.c41.p, e.c41.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
     {   // FilterPredictor's style half (:161-172 with normalized_style :397): mean_{HW} F.down_sample((map - mean)/std), 6 x 32 values
-        if (!S.smean) RCHK(dalloc(h, &S.smean, 6 * 32));
+        if (!S.smean) RCHK(dalloc(h, q, &S.smean, 6 * 32));
         Tens sn, ts32;
-        int rc = talloc(h, &sn, 1, S.map.H, S.map.W, 512);
-        if (rc == RRV_OK) rc = talloc(h, &ts32, 1, S.map.H, S.map.W, 32);
-        if (rc == RRV_OK) rc = pointwise(h, S.map, sn, S.blob + SL.sty[3], S.blob + SL.sty[3] + 512, true, nullptr, 0, nullptr, nullptr);
+        int rc = talloc(h, q, &sn, 1, S.map.H, S.map.W, 512);
+        if (rc == RRV_OK) rc = talloc(h, q, &ts32, 1, S.map.H, S.map.W, 32);
+        if (rc == RRV_OK) rc = pointwise(h, q, S.map, sn, S.blob + SL.sty[3], S.blob + SL.sty[3] + 512, true, nullptr, 0, nullptr, nullptr);
         for (int f = 0; f < 3 && rc == RRV_OK; ++f)
             for (int g = 0; g < 2 && rc == RRV_OK; ++g) {
                 char key[96];
                 snprintf(key, sizeof key, "Decoder.Filter%d.F%d.down_sample.0", f + 1, g + 1);
                 ConvCall cs{&sn, &ts32, &h->conv[key], sn.H, sn.W};
-                rc = conv(h, cs);
-                if (rc == RRV_OK) rc = chan_stats(h, ts32, 0, S.smean + (2 * f + g) * 32);
+                rc = conv(h, q, cs);
+                if (rc == RRV_OK) rc = chan_stats(h, q, ts32, 0, S.smean + (2 * f + g) * 32);
             }
-        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamSynchronize(q.stream);
         tfree(&sn); tfree(&ts32);
         if (rc != RRV_OK) return rc;
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(q.stream));
     if (h->debug) RCHK(debug_verify(h, "prepare_style"));
     S.prepared = true; S.computed = false;
     if (h->active_src == sid) h->active_src = -1;
@@ -2480,23 +2488,24 @@ int rrv_clean(rrv_handle h) {
 // encode the frames collected by rrv_add (all H x W = add_H x add_W) and append their relu4_1 features to h->patches
 static int flush_pending(rrv_handle h) {
     if (!h->pend_n) return RRV_OK;
+    const Seq q = base_seq(h);
     const int H = h->add_H, W = h->add_W;
     const size_t fb = in_frame_bytes(h->pend_in.form, H, W, h->pend_in.cs);
     const int PB = h->pend_n < 8 ? h->pend_n : 8;        // one plan; the last group may use fewer of its images
-    RCHK(enc_plan(h, h->enc_add, PB, H, W));
+    RCHK(enc_plan(h, q, h->enc_add, PB, H, W));
     for (int k0 = 0; k0 < h->pend_n; k0 += PB) {
         const int nb = h->pend_n - k0 < PB ? h->pend_n - k0 : PB;
-        RCHK(run_encoder(h, h->enc_add, h->pend_u8 + (size_t)k0 * fb, h->pend_in, 0, nullptr, nullptr, nb));      // the pending frames are kept in the format they arrived in
+        RCHK(run_encoder(h, q, h->enc_add, h->pend_u8 + (size_t)k0 * fb, h->pend_in, 0, nullptr, nullptr, nb));      // the pending frames are kept in the format they arrived in
         const Tens& f = h->enc_add.c41;
         for (int b = 0; b < nb; ++b) {
             float* keep = nullptr;
-            RCHK(dalloc(h, &keep, f.img_floats(), false));
-            HIPCHK(hipMemcpyAsync(keep, f.p + (size_t)b * f.img_floats(), f.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+            RCHK(dalloc(h, q, &keep, f.img_floats(), false));
+            HIPCHK(hipMemcpyAsync(keep, f.p + (size_t)b * f.img_floats(), f.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
             h->patches.push_back(keep);
         }
         h->patch_h = f.H; h->patch_w = f.W;
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(q.stream));
     h->pend_n = 0;
     return RRV_OK;
 }
@@ -2526,6 +2535,7 @@ static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hip
     if (device) {      // in the order of the caller's stream, and consumed before the call returns
         RCHK(wait_for_stream(h, stream));
         uint8_t* const dst = h->pend_u8 + (size_t)h->pend_n * fb;
+        const hipStream_t s0 = h->slots[0].stream;
         if (view) {
             const int vl = in_view_layout(in.form);
             const size_t el = in_elem(in.form);
@@ -2533,11 +2543,11 @@ static int add_frame(rrv_handle h, const void* frame, bool device, InFmt in, hip
             const Planes pl = view_planes(vl, H, W, in.cs);
             for (int k = 0; k < pl.n; ++k)
                 HIPCHK(hipMemcpy2DAsync(dst + (size_t)c.off[k] * el, (size_t)c.pitch[k] * el, (const char*)frame + (size_t)view->plane_offset[k] * el,
-                                        (size_t)view->pitch[k] * el, (size_t)pl.len[k] * el, (size_t)pl.rows[k], hipMemcpyDeviceToDevice, h->stream));
+                                        (size_t)view->pitch[k] * el, (size_t)pl.len[k] * el, (size_t)pl.rows[k], hipMemcpyDeviceToDevice, s0));
         } else {
-            HIPCHK(hipMemcpyAsync(dst, frame, fb, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(dst, frame, fb, hipMemcpyDeviceToDevice, s0));
         }
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipStreamSynchronize(s0));
     } else {
         HIPCHK(hipMemcpy(h->pend_u8 + (size_t)h->pend_n * fb, frame, fb, hipMemcpyHostToDevice));
     }
@@ -2603,22 +2613,23 @@ int rrv_compute(rrv_handle h) {
     }
     h->last_groups = (B + G - 1) / G; h->last_group_size = G; h->last_ws_bytes = prep_bytes(G, hh, ww, streaming);
     prep_free(h);      // (a plan kept by rrv_debug_prep_stop; empty otherwise)
-    RCHK(prep_plan(h, G, hh, ww, streaming));
+    const Seq q = base_seq(h);      // the preparation pass: F(2x2,3x3) on set 0, whatever ran before
+    RCHK(prep_plan(h, q, G, hh, ww, streaming));
     int first = -1;
     auto body = [&]() -> int {
         const Tens& content = h->prep.content;
         for (int b = 0; b < B && !streaming; ++b)
             HIPCHK(hipMemcpyAsync(content.p + (size_t)b * content.img_floats(), h->patches[b], content.img_floats() * sizeof(float),
-                                  hipMemcpyDeviceToDevice, h->stream));
+                                  hipMemcpyDeviceToDevice, q.stream));
         for (int s = 0; s < RRV_MAX_STYLES; ++s)
             if (h->styles[s].prepared) {
                 if (first < 0) first = s;
-                RCHK(streaming ? compute_style_streaming(h, s) : compute_style(h, s));
+                RCHK(streaming ? compute_style_streaming(h, q, s) : compute_style(h, q, s));
             }
         return RRV_OK;
     };
     const int rc = body();
-    (void)hipStreamSynchronize(h->stream);
+    (void)hipStreamSynchronize(q.stream);
     if (h->prep_stop < 0 || rc != RRV_OK) prep_free(h);      // several GB for a video's sampled frames
     if (rc != RRV_OK) return rc;
     if (h->debug) RCHK(debug_verify(h, "compute"));
@@ -2642,7 +2653,7 @@ int rrv_set_state(rrv_handle h, const float* in, int n, int sid) {
     if (!h->finalized) return fail(h, RRV_E_WEIGHTS, "weights not finalized");
     HIPCHK(hipSetDevice(h->dev));
     StyleState& S = h->styles[sid];
-    if (!S.blob) RCHK(dalloc(h, &S.blob, RRV_STATE_FLOATS));
+    if (!S.blob) RCHK(dalloc(h, base_seq(h), &S.blob, RRV_STATE_FLOATS));
     RCHK(sync_all(h));
     HIPCHK(hipMemcpy(S.blob, in, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     S.computed = true;
@@ -2728,10 +2739,10 @@ int rrv_broadcast_state(rrv_handle h, void* comm, int root, int my_rank, int sid
     RCHK(sync_all(h));
     StyleState& S = h->styles[sid];
     if (my_rank == root && (!S.blob || !S.computed)) return fail(h, RRV_E_STATE, "broadcast_state: the root has no computed state for this style");
-    if (!S.blob) RCHK(dalloc(h, &S.blob, RRV_STATE_FLOATS));
-    const int rc = g_rccl.Broadcast(S.blob, S.blob, RRV_STATE_FLOATS, /* ncclFloat32 */ 7, root, comm, h->streams[0]);
+    if (!S.blob) RCHK(dalloc(h, base_seq(h), &S.blob, RRV_STATE_FLOATS));
+    const int rc = g_rccl.Broadcast(S.blob, S.blob, RRV_STATE_FLOATS, /* ncclFloat32 */ 7, root, comm, h->slots[0].stream);
     if (rc != 0) return fail(h, RRV_E_COMM, std::string("ncclBroadcast failed: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?"));
-    HIPCHK(hipStreamSynchronize(h->streams[0]));
+    HIPCHK(hipStreamSynchronize(h->slots[0].stream));
     if (my_rank != root) {
         S.computed = true;
         RCHK(filter_conditioning(h, S));
@@ -2829,7 +2840,8 @@ static int rs_pair(rrv_handle h, int SH, int SW, int H, int W, const rrv_ctx::Rs
 static int rs_reserve(rrv_handle h, int slot, int frames, int SH, int SW, int H, int W) {
     const rrv_ctx::RsTab *ty, *tx;
     RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
-    return ensure_dev(h, h->rs_buf[slot], h->rs_cap[slot], (size_t)frames * H * W * 3);
+    rrv_ctx::Slot& sl = h->slots[slot];
+    return ensure_dev(h, sl.rs_buf, sl.rs_cap, (size_t)frames * H * W * 3);
 }
 static int check_scale(rrv_handle h, const char* who, int SH, int SW, int H, int W) {
     if (SH < 1 || SW < 1) return fail(h, RRV_E_ARG, std::string(who) + ": SH, SW must be at least 1");
@@ -2838,9 +2850,9 @@ static int check_scale(rrv_handle h, const char* who, int SH, int SW, int H, int
     if (!rs_ratio_ok(SW, W)) return fail(h, RRV_E_ARG, std::string(who) + ": SW / W must be within 1/8 .. 8");
     return RRV_OK;
 }
-// B frames of SH x SW in the format `in` through `vi` -> contiguous [B][H][W][3] float32 BGR PIXEL at d_out, queued on `stream`.  The tables
+// B frames of SH x SW in the format `in` through `vi` -> contiguous [B][H][W][3] float32 BGR PIXEL at d_out, queued on q.stream.  The tables
 // exist already or are built here (rs_reserve has run for the entries that promise no allocation between launches).
-static int resample_launch(rrv_handle h, hipStream_t stream, const void* d_in, InFmt in, const ImgView& vi, int B, int SH, int SW, int H, int W, float* d_out) {
+static int resample_launch(rrv_handle h, const Seq& q, const void* d_in, InFmt in, const ImgView& vi, int B, int SH, int SW, int H, int W, float* d_out) {
     const rrv_ctx::RsTab *ty, *tx;
     RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
     ResampleP p{};
@@ -2853,13 +2865,11 @@ static int resample_launch(rrv_handle h, hipStream_t stream, const void* d_in, I
         memcpy(p.yuv_n, y.m, sizeof p.yuv_n); p.yuv_shift = y.shift;
         p.csx = chroma_sx(in.cs); p.csy = chroma_sy(in.cs);
     }
-    struct StreamScope { rrv_handle h; hipStream_t s; ~StreamScope() { h->stream = s; } } scope{h, h->stream};
-    h->stream = stream;
     int e = 0;
     // for the profile log: bytes from the shapes; operations two per tap, channel and pass, a row's taps taken as span / RS_TH
     const double src_bytes = (in_yuv(in.form) ? yuv_samples_per_pixel(in.cs) : 3.0) * in_elem(in.form) * SH * SW;
-    RCHK(launch(h, "resample", 2.0 * B * 3 * ((double)tx->span / RS_TH * SH * W + (double)ty->span / RS_TH * H * W), (src_bytes + 12.0 * H * W) * B, [&] {
-        e = rrv_scale_launch(&p, in.form, stream);
+    RCHK(launch(h, q, "resample", 2.0 * B * 3 * ((double)tx->span / RS_TH * SH * W + (double)ty->span / RS_TH * H * W), (src_bytes + 12.0 * H * W) * B, [&] {
+        e = rrv_scale_launch(&p, in.form, q.stream);
     }));
     if (e != 0) return fail(h, RRV_E_HIP, std::string("resample: launch failed: ") + hipGetErrorString((hipError_t)e));
     return RRV_OK;
@@ -2924,51 +2934,53 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     // bracketed here for every model); what the request allocates for that exists before the first launch.
     const bool scaled = x.scaled();
     if (scaled) RCHK(rs_reserve(h, slot, x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX), x.SH, x.SW, x.H, x.W));
-    const bool bracket = h->caller_sync && (x.model != Model::GLOBAL || scaled);
+    rrv_ctx::Slot& sl = h->slots[slot];
+    const CallerOrder caller = x.order(h);
+    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled);
     if (bracket) {
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->caller_stream));
-        HIPCHK(hipStreamWaitEvent(h->streams[slot], h->slot_ev[slot], 0));
+        HIPCHK(hipEventRecord(sl.ev, caller.stream));
+        HIPCHK(hipStreamWaitEvent(sl.stream, sl.ev, 0));
     }
     const int KH = x.KH(), KW = x.KW(), G = x.model == Model::GLOBAL ? x.B : (int)rrv_ctx::MS_GROUP_MAX;
     const ImgView vi = x.in_view(), vo = x.out_view();      // the one addressing path: contiguous frames are a view like any other
     const size_t fb = (size_t)vi.fs * in_elem(x.in.form), fo = (size_t)vo.fs * out_view_elem(x.fmt);      // bytes from a frame to the next
     const PadCrop crop = x.pad_crop();
     const ImgView vw = contiguous_view(VL_HWC, x.H, x.W);      // a scaled request's working frames: float32 HWC BGR PIXEL in the slot's buffer
-    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi, &vo};
+    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi, &vo, caller};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* in = (const uint8_t*)d_in + (size_t)b0 * fb;
         void* const out = (char*)d_out + (size_t)b0 * fo;
+        // the group's sequence: GLOBAL and MASK read no set of the slot's own, FRAME writes and BLEND blends into them (image g: set g of the slot's);
+        // GLOBAL and BLEND are the per-frame path (transfer_device), where F(4x4,3x3) may run
+        Seq q = slot_seq(h, slot, x.model == Model::FRAME || x.model == Model::BLEND);
+        q.f43 = x.model == Model::GLOBAL || x.model == Model::BLEND;
         if (scaled) {
-            RCHK(resample_launch(h, h->streams[slot], in, x.in, vi, cnt, x.SH, x.SW, x.H, x.W, h->rs_buf[slot]));
-            in = (const uint8_t*)h->rs_buf[slot];
+            RCHK(resample_launch(h, q, in, x.in, vi, cnt, x.SH, x.SW, x.H, x.W, sl.rs_buf));
+            in = (const uint8_t*)sl.rs_buf;
         }
         switch (x.model) {
         case Model::GLOBAL:
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, nullptr, hk));
+            RCHK(transfer_device(h, q, in, cnt, KH, KW, out, io, nullptr, hk));
             break;
         case Model::FRAME:
-            RCHK(frame_mode_device(h, slot, in, cnt, KH, KW, out, io));
+            RCHK(frame_mode_device(h, q, in, cnt, KH, KW, out, io));
             break;
         case Model::MASK:
-            RCHK(mask_mode_device(h, slot, in, cnt, KH, KW, x.mask + (x.mask_images == 1 ? 0 : (size_t)b0 * x.mask_floats()), x.ns, x.mask_images == 1, out,
+            RCHK(mask_mode_device(h, q, in, cnt, KH, KW, x.mask + (x.mask_images == 1 ? 0 : (size_t)b0 * x.mask_floats()), x.ns, x.mask_images == 1, out,
                                   io));
             break;
-        case Model::BLEND: {
-            SetScope scope{h, -2};
-            h->stream = h->streams[slot];
-            h->cur = &h->sets[rrv_ctx::MS_GROUP_MAX * slot];       // image g of the group: state set MS_GROUP_MAX * slot + g
-            RCHK(blend_sets(h, x.wts + (size_t)b0 * x.ns, x.w_dev, x.ns, cnt));
-            h->state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the current one (shared-state kernels)
-            RCHK(transfer_device(h, slot, in, cnt, KH, KW, out, io, x.feats ? x.feats + b0 : nullptr, hk));      // (a host sub-batch is one group: the hook's sequence)
-            h->set_images[slot] = cnt;
+        case Model::BLEND:
+            RCHK(blend_sets(h, q, x.wts + (size_t)b0 * x.ns, x.w_dev, x.ns, cnt));      // (the sets count as blends from here on: active_src -2)
+            q.state_images = cnt > 1 ? cnt : 0;      // one frame: its state set is simply the sequence's (shared-state kernels)
+            RCHK(transfer_device(h, q, in, cnt, KH, KW, out, io, x.feats ? x.feats + b0 : nullptr, hk));      // (a host sub-batch is one group: the hook's sequence)
+            sl.set_images = cnt;
             break;
-        }
         }
     }
     if (bracket) {
-        HIPCHK(hipEventRecord(h->slot_ev[slot], h->streams[slot]));
-        HIPCHK(hipStreamWaitEvent(h->caller_stream, h->slot_ev[slot], 0));
+        HIPCHK(hipEventRecord(sl.ev, sl.stream));
+        HIPCHK(hipStreamWaitEvent(caller.stream, sl.ev, 0));
     }
     return RRV_OK;
 }
@@ -3054,11 +3066,7 @@ static int view_run(rrv_handle h, const char* who, const void* d_in, const rrv_i
     if (!view_check(*in, x.B, x.IH(), x.IW(), false, &why)) return fail(h, RRV_E_ARG, w + "in." + why);      // (a scaled request: the source frame)
     if (!view_check(*out, x.B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);
     x.vin = in; x.vout = out;
-    struct Scope {      // hip_stream orders this call only
-        rrv_handle h; hipStream_t cs; bool sync;
-        ~Scope() { h->caller_stream = cs; h->caller_sync = sync; }
-    } scope{h, h->caller_stream, h->caller_sync};
-    if (hip_stream || (flags & RRV_TF_ON_STREAM)) { h->caller_stream = (hipStream_t)hip_stream; h->caller_sync = true; }
+    if (hip_stream || (flags & RRV_TF_ON_STREAM)) { x.on_stream = true; x.with = (hipStream_t)hip_stream; }      // hip_stream orders this call only
     return run_xfer(h, next_slot(h, x), d_in, d_out, x);
 }
 int rrv_transfer_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int H, int W, void* d_out, const rrv_image_view* out,
@@ -3322,11 +3330,11 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // The tail wait and the piecewise delivery (SeqHook) order the sub-batches of the models that run transfer_device, on two streams with
     // staged copies both ways.  Everything else keeps one launch per layer and sub-batch, unordered: one sub-batch or one stream, the
     // profiled step (slot 0 only), the debug levels, a caller's stream, zero copy.
-    const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !h->caller_sync && h->host_io == 0 &&
+    const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !x.order(h).sync && h->host_io == 0 &&
                          (x.model == Model::GLOBAL || x.model == Model::BLEND);
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
-    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
+    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
     if (x.scaled())      // a scaled request: the tables and each compute slot's buffer of working frames, before the first launch
         for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(rs_reserve(h, slot_of(k), sub, x.SH, x.SW, x.H, x.W));      // (slot_of has period 2)
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
@@ -3370,7 +3378,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
             if (!m_pin) { host_copy(st.mask_pin, msrc, mbytes); msrc = st.mask_pin; }
         }
         const int slot = slot_of(k);
-        hipStream_t cs = h->streams[slot];
+        hipStream_t cs = h->slots[slot].stream;
         if (nchunk == 1 && h->host_io == 0) {     // one sub-batch (the reference's one-frame-per-call surface): nothing to overlap, one stream, no events
             HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
             if (mask) HIPCHK(hipMemcpyAsync(st.mask, msrc, mbytes, hipMemcpyHostToDevice, cs));
@@ -3551,7 +3559,9 @@ int rrv_resample_view_device(rrv_handle h, const void* d_in, const rrv_image_vie
     std::string why;
     if (!view_check(*in, B, SH, SW, false, &why)) return fail(h, RRV_E_ARG, "resample_view: in." + why);
     HIPCHK(hipSetDevice(h->dev));
-    return resample_launch(h, (hipStream_t)hip_stream, d_in, fmt, img_view(*in), B, SH, SW, H, W, d_out);
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    return resample_launch(h, q, d_in, fmt, img_view(*in), B, SH, SW, H, W, d_out);
 }
 int rrv_transfer_scaled_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, void* d_out,
                                     const rrv_image_view* out, int flags, void* hip_stream) {
@@ -3592,19 +3602,20 @@ static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, c
         return fail(h, RRV_E_ARG, "add: all sampled frames must have the same size");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(rs_reserve(h, 0, 1, SH, SW, H, W));
+    const Seq q = base_seq(h);
     const void* src = frame;
     if (device) {
         RCHK(wait_for_stream(h, stream));
     } else {
         const size_t fb = in_frame_bytes(fmt.form, SH, SW, fmt.cs);
         RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, fb));
-        HIPCHK(hipMemcpyAsync(h->d_u8, frame, fb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_u8, frame, fb, hipMemcpyHostToDevice, q.stream));
         src = h->d_u8;
     }
     const ImgView vi = view ? img_view(*view) : contiguous_view(in_view_layout(fmt.form), SH, SW, fmt.cs);
-    const int rc = resample_launch(h, h->stream, src, fmt, vi, 1, SH, SW, H, W, h->rs_buf[0]);
-    if (rc != RRV_OK) { (void)hipStreamSynchronize(h->stream); return rc; }      // (the caller's frame is not read after the call returns)
-    return add_frame(h, h->rs_buf[0], true, InFmt{IN_F32_HWC, SP_PIXEL}, h->stream, H, W);      // (synchronises: the frame has been read and compacted)
+    const int rc = resample_launch(h, q, src, fmt, vi, 1, SH, SW, H, W, h->slots[0].rs_buf);
+    if (rc != RRV_OK) { (void)hipStreamSynchronize(q.stream); return rc; }      // (the caller's frame is not read after the call returns)
+    return add_frame(h, h->slots[0].rs_buf, true, InFmt{IN_F32_HWC, SP_PIXEL}, q.stream, H, W);      // (synchronises: the frame has been read and compacted)
 }
 int rrv_add_scaled_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW, int H, int W, void* hip_stream) {
     if (!h || !d_frame || !in) return RRV_E_ARG;
@@ -3728,14 +3739,15 @@ static int transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, void
     // 508 frames/s on one stream, 569 on two, 603 on four with a quarter of the CUs each — profiles/r03_b1_streams.txt)
     const int slot = h->profiling ? 0 : (int)(id % RRV_MAX_SLOTS);      // the ticket's own pair, whatever rrv_set_pipeline says
     h->next_slot = 0;
-    hipStream_t cs = h->streams[slot];
-    struct ShareScope { rrv_handle h; int saved; ~ShareScope() { h->grid_share = saved; } } share_scope{h, h->grid_share};
-    if (!h->profiling && h->grid_share == 1) {       // as many shares as frames in flight once this one is queued (1 .. 4)
+    Seq q = slot_seq(h, slot);
+    q.f43 = true;                                    // the per-frame path
+    hipStream_t cs = q.stream;
+    if (!h->profiling && h->grid_share == 1) {       // this ticket's share: as many shares as frames in flight once it is queued (1 .. 4); else the handle's
         int open = 1;
         for (auto& tk : h->tickets)
             if (tk.open && tk.id != id - HOST_SETS && hipEventQuery(h->hstage[tk.id % HOST_SETS].out_done) == hipErrorNotReady) ++open;
         (void)hipGetLastError();
-        h->grid_share = open > RRV_MAX_SLOTS ? RRV_MAX_SLOTS : open;
+        q.share = open > RRV_MAX_SLOTS ? RRV_MAX_SLOTS : open;
     }
     // No copy streams, whatever rrv_set_host_io says: the frame is copied in on the ticket's OWN stream (1.2 MB; a
     // kernel reading it from host memory byte by byte costs more, bench `zero_copy_input_only`) and the last kernel writes
@@ -3745,7 +3757,7 @@ static int transfer_async(rrv_handle h, const uint8_t* frame, int H, int W, void
     RCHK(ensure_active(h));
     HIPCHK(hipMemcpyAsync(st.dev.in, src, fb, hipMemcpyHostToDevice, cs));
     HIPCHK(hipEventRecord(st.in_done, cs));      // the frame has left the caller's buffer (waited for below when the copy reads it directly)
-    const int rc0 = transfer_device(h, slot, st.dev.in, 1, H, W, out_pin ? out : st.pin.out, FrameIO{IN_BGR8, fmt});
+    const int rc0 = transfer_device(h, q, st.dev.in, 1, H, W, out_pin ? out : st.pin.out, FrameIO{IN_BGR8, fmt, nullptr, nullptr, nullptr, CallerOrder{h->caller_stream, h->caller_sync}});
     // Contract (include/rerevst_hip.h): `frame` may be reused as soon as the call returns.  A pageable frame was copied to
     // staging above; a page-locked one is the DIRECT source of the asynchronous H2D copy, so wait for that copy (queued
     // first on an idle stream: finished long before the launches above were) — also on the error path.
@@ -3800,13 +3812,14 @@ int rrv_generate_content_features(rrv_handle h, const uint8_t* frame, int H, int
         return RRV_OK;
     }
     RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, (size_t)H * W * 3));
-    HIPCHK(hipMemcpyAsync(h->d_u8, frame, (size_t)H * W * 3, hipMemcpyHostToDevice, h->stream));
-    RCHK(enc_plan(h, h->enc_add, 1, H, W));
-    RCHK(run_encoder(h, h->enc_add, h->d_u8, IN_BGR8, 0, nullptr, nullptr, 1));
+    const Seq q = base_seq(h);
+    HIPCHK(hipMemcpyAsync(h->d_u8, frame, (size_t)H * W * 3, hipMemcpyHostToDevice, q.stream));
+    RCHK(enc_plan(h, q, h->enc_add, 1, H, W));
+    RCHK(run_encoder(h, q, h->enc_add, h->d_u8, IN_BGR8, 0, nullptr, nullptr, 1));
     const Tens& f = h->enc_add.c41;
-    RCHK(dalloc(h, &ft.p, feature_floats(H, W), true));
-    HIPCHK(hipMemcpyAsync(ft.p, f.p, f.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    RCHK(dalloc(h, q, &ft.p, feature_floats(H, W), true));
+    HIPCHK(hipMemcpyAsync(ft.p, f.p, f.img_floats() * sizeof(float), hipMemcpyDeviceToDevice, q.stream));
+    HIPCHK(hipStreamSynchronize(q.stream));
     h->feat_bytes += need;
     h->features.push_back(ft);
     *feature_id = (int)h->features.size() - 1;
@@ -3840,8 +3853,8 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
     if (n_res) {
         RCHK(dmalloc(h, (void**)&arena, ((size_t)n_res * img + slack) * sizeof(float)));
         h->feat_blocks.push_back(arena);
-        HIPCHK(hipMemsetAsync(arena, 0, ((size_t)n_res * img + slack) * sizeof(float), h->streams[0]));      // the zero ring of every feature
-        HIPCHK(hipStreamSynchronize(h->streams[0]));
+        HIPCHK(hipMemsetAsync(arena, 0, ((size_t)n_res * img + slack) * sizeof(float), h->slots[0].stream));      // the zero ring of every feature
+        HIPCHK(hipStreamSynchronize(h->slots[0].stream));
         h->feat_bytes += ((size_t)n_res * img + slack) * sizeof(float);
         for (int i = 0; i < n_res; ++i) h->features.push_back(rrv_ctx::Feature{arena + (size_t)i * img, H, W, nullptr, false});
     }
@@ -3862,7 +3875,6 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         RCHK(stage_reserve(h, i, (size_t)sub * fb, 0, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, 0, true));
     }
-    struct Restore { rrv_handle h; ~Restore() { h->stream = h->streams[0]; h->f43_path = false; } } restore{h};
     const int nstreams = (h->profiling || h->n_slots < 2) ? 1 : 2;
     int rc = RRV_OK;
     for (int k = 0; k < nchunk && rc == RRV_OK; ++k) {
@@ -3874,17 +3886,17 @@ int rrv_generate_content_features_batch(rrv_handle h, const uint8_t* frames, int
         const int slot = k % nstreams;
         HIPCHK(hipMemcpyAsync(st.dev.in, src, (size_t)nb * fb, hipMemcpyHostToDevice, h->copy_in));
         HIPCHK(hipEventRecord(st.in_done, h->copy_in));
-        HIPCHK(hipStreamWaitEvent(h->streams[slot], st.in_done, 0));
-        h->stream = h->streams[slot];
-        h->f43_path = true;                  // the same kernel choice as the per-frame path's encoder (rrv_set_f43)
-        EncPlan& e = pick_plan(h, h->enc_frame[slot], nb, H, W);
-        rc = enc_plan(h, e, nb, H, W, true);
+        HIPCHK(hipStreamWaitEvent(h->slots[slot].stream, st.in_done, 0));
+        Seq q = slot_seq(h, slot);
+        q.f43 = true;                        // the same kernel choice as the per-frame path's encoder (rrv_set_f43)
+        EncPlan& e = pick_plan(h, h->slots[slot].enc, nb, H, W);
+        rc = enc_plan(h, q, e, nb, H, W, true);
         if (rc != RRV_OK) break;
         e.gen = ++h->launch_gen;
         Tens out41 = one; out41.B = nb; out41.p = arena + (size_t)k * sub * img;
-        rc = run_encoder(h, e, st.dev.in, IN_BGR8, 0, nullptr, nullptr, nb, &out41);
+        rc = run_encoder(h, q, e, st.dev.in, IN_BGR8, 0, nullptr, nullptr, nb, &out41);
         if (rc != RRV_OK) break;
-        HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
+        HIPCHK(hipEventRecord(st.k_done, h->slots[slot].stream));
     }
     const int rs = sync_all(h);
     if (rc == RRV_OK) rc = rs;
@@ -3929,13 +3941,14 @@ int rrv_add_patch(rrv_handle h, int feature_id) {
     if (!h->patches.empty() && (ft.H != h->add_H || ft.W != h->add_W))
         return fail(h, RRV_E_ARG, "add_patch: all sampled features must have the same size");
     Tens f; f.B = 1; f.H = ft.H / 2 / 2 / 2; f.W = ft.W / 2 / 2 / 2; f.C = 512;
+    const Seq q = base_seq(h);
     float* keep = nullptr;
-    RCHK(dalloc(h, &keep, f.img_floats(), false));
+    RCHK(dalloc(h, q, &keep, f.img_floats(), false));
     const float* src = ft.p;
     if (!src) {                  // spilled feature: encode its pixels now
-        int rc = enc_plan(h, h->enc_add, 1, ft.H, ft.W);
-        if (rc == RRV_OK) rc = run_encoder(h, h->enc_add, ft.u8, IN_BGR8, 0, nullptr, nullptr, 1);
-        if (rc == RRV_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, RRV_E_HIP, "add_patch: encoder failed");
+        int rc = enc_plan(h, q, h->enc_add, 1, ft.H, ft.W);
+        if (rc == RRV_OK) rc = run_encoder(h, q, h->enc_add, ft.u8, IN_BGR8, 0, nullptr, nullptr, 1);
+        if (rc == RRV_OK && hipStreamSynchronize(q.stream) != hipSuccess) rc = fail(h, RRV_E_HIP, "add_patch: encoder failed");
         if (rc != RRV_OK) { (void)hipFree(keep); return rc; }
         src = h->enc_add.c41.p;
     }
@@ -3992,7 +4005,7 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
     }
     const bool tl_on = h->tl.on && ngroups > 1 && ngroups <= rrv_ctx::Timeline::N;
     double tl_setup = 0;
-    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->streams[0])); }
+    if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
     auto drain = [&](int k) -> int {
         auto& st = h->hstage[k % nslots];
         HIPCHK(hipEventSynchronize(st.out_done));
@@ -4004,17 +4017,17 @@ static int transfer_features_batch(rrv_handle h, const int* ids, const float* wt
         auto& st = h->hstage[slot];
         if (k >= nslots) {
             if (!out_pin) RCHK(drain(k - nslots));
-            HIPCHK(hipStreamWaitEvent(h->streams[slot], st.out_done, 0));      // this slot's device output has left
+            HIPCHK(hipStreamWaitEvent(h->slots[slot].stream, st.out_done, 0));      // this slot's device output has left
         }
         const float* fp[rrv_ctx::MS_GROUP_MAX] = {};
         for (int g = 0; g < cnt; ++g) fp[g] = h->features[ids[first + g]].p;
         void* const h_dst = out_pin ? (void*)(outc + (size_t)first * npx) : st.pin.out;
-        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, h->streams[slot]));      // (a diagnostic: in front of the first group's blend, which is part of its request)
+        if (tl_on && k == 0) HIPCHK(hipEventRecord(h->tl.first, h->slots[slot].stream));      // (a diagnostic: in front of the first group's blend, which is part of its request)
         Xfer part{Model::BLEND, cnt, H, W, PLAIN, fmt, ns, wts + (size_t)first * ns};
         if (fp[0]) part.feats = fp;
         RCHK(run_xfer(h, slot, fp[0] ? nullptr : h->features[ids[first]].u8, st.dev.out, part));      // a spilled feature is re-encoded from its uint8 BGR pixels
-        if (tl_on) HIPCHK(hipEventRecord(h->tl.k_end[k], h->streams[slot]));
-        HIPCHK(hipEventRecord(st.k_done, h->streams[slot]));
+        if (tl_on) HIPCHK(hipEventRecord(h->tl.k_end[k], h->slots[slot].stream));
+        HIPCHK(hipEventRecord(st.k_done, h->slots[slot].stream));
         HIPCHK(hipStreamWaitEvent(h->copy_out, st.k_done, 0));
         HIPCHK(hipMemcpyAsync(h_dst, st.dev.out, (size_t)cnt * npx, hipMemcpyDeviceToHost, h->copy_out));
         HIPCHK(hipEventRecord(st.out_done, h->copy_out));
@@ -4123,7 +4136,7 @@ int rrv_debug_copy_tensor(rrv_handle h, int slot, int index, int H, int W, float
     const int row = tap_row(index, enc);
     const Tens* t = nullptr;
     for (int k = 0; k < 2 && !t; ++k) {
-        EncPlan& e = h->enc_frame[slot][k]; DecPlan& d = h->dec[slot][k];
+        EncPlan& e = h->slots[slot].enc[k]; DecPlan& d = h->slots[slot].dec[k];
         if (enc ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0)) t = enc ? &ENC_T[row].of(e) : &DEC_T[row].of(d);
     }
     if (!t || !t->p) return fail(h, RRV_E_STATE, "debug_copy_tensor: no such tensor in this slot");
@@ -4148,7 +4161,7 @@ int rrv_debug_copy_tensor_ex(rrv_handle h, int slot, int index, int image, int H
     const Tens* t = nullptr;
     unsigned pgen = 0;
     for (int k = 0; k < 2; ++k) {
-        EncPlan& e = h->enc_frame[slot][k]; DecPlan& d = h->dec[slot][k];
+        EncPlan& e = h->slots[slot].enc[k]; DecPlan& d = h->slots[slot].dec[k];
         const bool match = enc ? (e.H == H && e.W == W && e.B > 0) : (d.H == H / 8 * 8 && d.W == W / 8 * 8 && d.B > 0);
         const unsigned g = enc ? e.gen : d.gen;
         if (match && (!t || g > pgen)) { t = enc ? &ENC_T[row].of(e) : &DEC_T[row].of(d); pgen = g; }
@@ -4191,11 +4204,11 @@ int rrv_debug_copy_state(rrv_handle h, int what, int slot, int image, float* out
         return RRV_OK;
     }
     if (what != RRV_DBG_STATE_SET || slot < 0 || slot > 1 || image >= rrv_ctx::MS_GROUP_MAX || n != RRV_STATE_FLOATS) return RRV_E_ARG;
-    if (!h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch kept no per-image state");
-    if (image >= h->set_images[slot]) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch did not write this image");
+    if (!h->slots[slot].set_images) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch kept no per-image state");
+    if (image >= h->slots[slot].set_images) return fail(h, RRV_E_STATE, "debug_copy_state: the slot's last launch did not write this image");
     HIPCHK(hipSetDevice(h->dev));
     RCHK(sync_all(h));
-    HIPCHK(hipMemcpy(out, h->sets[rrv_ctx::MS_GROUP_MAX * slot + image].active, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, h->slot_sets(slot)[image].active, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return RRV_OK;
 }
 
