@@ -598,7 +598,7 @@ int rrv_add_view_device(rrv_handle h, const void* d_frame, const rrv_image_view*
 /* Scaling: frames resampled to a working size on the GPU, in front of everything else (the "content size" of style-transfer tools: the working
  * resolution sets the stroke size of the stylized picture, and the speed).  The source frames are SH x SW in any form the first kernel reads, through
  * the same views; H x W is the working size, which is also the size of the delivered frame (with RRV_TF_PAD_CROP the resampled H x W frame is what
- * gets reflect-padded and cropped; without it 8*(H/8) x 8*(W/8) are delivered as always).  Output-side upscaling is the encoder's or the player's.
+ * gets reflect-padded and cropped; without it 8*(H/8) x 8*(W/8) are delivered as always), unless the call names a delivered size ("Output size" below).
  * Arithmetic: one separable filter.  For one axis with S source and D destination samples, s = S / D and support = max(s, 1); output sample i has
  *   c = s (i + 0.5),  lo = max(int(c - support + 0.5), 0),  n = min(int(c + support + 0.5), S) - lo   (int truncates)
  *   w_j = tri((lo + j - c + 0.5) / support) / sum_j of the same,  tri(t) = max(0, 1 - |t|),  j = 0 .. n - 1
@@ -629,7 +629,7 @@ int rrv_add_view_device(rrv_handle h, const void* d_frame, const rrv_image_view*
  * Checks, all before any GPU work: the view against (SH, SW), the frame rules against (H, W), the ratio limits; RRV_E_ARG names the field and the
  * handle stays usable.  The resampled frames of a launch group live in a grow-only float32 buffer per workspace slot (12 bytes per working pixel and
  * frame), reserved with the axis tables before the call's first launch: out of memory is RRV_E_NOMEM and the handle stays usable.
- * Not offered yet: blended and masked twins, output scaling, a scaled rrv_prepare_style, tickets. */
+ * Not offered yet: blended and masked twins, a scaled rrv_prepare_style, tickets. */
 int rrv_resample_taps(int S, int D, int* first /*[D]*/, int* count /*[D]*/, float* w /*[D][cap]*/, int cap);
 int rrv_resample_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW,
                              int H, int W, float* d_out, void* hip_stream);
@@ -640,6 +640,48 @@ int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int
 int rrv_add_scaled_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW,
                                int H, int W, void* hip_stream);
 int rrv_add_scaled(rrv_handle h, const void* frame, rrv_image_desc in, int SH, int SW, int H, int W);
+
+/* Scaling, output size: the stylized working frame resampled to a delivered size DH x DW on the GPU, behind the last kernel, and written in any
+ * output form the last kernel has (float32 / uint8, HWC BGR / planar RGB, the three spaces of the float32 forms, every YUV layout, depth and chroma
+ * format) through the same views.  "Stylize at the working size, deliver at the source's": a 3840 x 2160 NV12 surface in, worked on at 1920 x 1080,
+ * leaves as a 3840 x 2160 NV12 surface, and the host touches no pixel.
+ * The frame that is resampled is the delivered working frame as float32 HWC BGR PIXEL values, what the float32 PIXEL call writes: with
+ * RRV_TF_PAD_CROP the H x W crop window, without it the 8*(H/8) x 8*(W/8) frame.  Call it OH x OW.
+ * Arithmetic.  Resample: exactly the input resampler's, with the rrv_resample_taps tables of (OH -> DH) and (OW -> DW): the three channels in
+ * float32, first along rows, then along columns, taps in ascending order with fused multiply-adds, the sums starting from -0; per axis
+ * OH / DH <= 8 and DH / OH <= 8 (else RRV_E_ARG).  The resampled value v of a pixel and channel is therefore the same bits whatever the output form,
+ * and for DH == OH, DW == OW it is the working frame's value.  From v, with each operation rounded to float32 and none contracted:
+ *   float32 PIXEL   v, not clamped (a bilinear upscale stays within the range of its inputs, 0..255)
+ *   float32 UNIT    v / 255.0f
+ *   float32 NORM    (v / 255.0f - mean_c) / std_c: the normalised form of the DELIVERED pixel, the inverse of what the first kernel does to a
+ *                   uint8 pixel.  It is not the pre-clamp network output the unscaled NORM form delivers: a resampled frame has none.
+ *   uint8           rint(min(max(v, 0), 255)), half to even
+ *   YUV             the last kernel's store, applied to v over the delivered frame: c_k = ((m[k][0] R + m[k][1] G) + m[k][2] B) + m[k][3];
+ *                   Y code = rint(min(max(c_0, 0), 2^d - 1)); a chroma code the same of ((tl + tr) + (bl + br)) * 0.25f (4:2:0), (l + r) * 0.5f
+ *                   (4:2:2) or the pixel's own value (4:4:4) of the unclamped c_1 / c_2, a pixel outside the DH x DW frame (odd last row or
+ *                   column) replaced by its nearest one inside; the code shifted left by 16 - d for the P forms.  Matrix and depth are read
+ *                   from the handle when the call launches.
+ * Frame b's result does not depend on B.  A delivering call equals, bit for bit in a fixed kernel mode, the float32 HWC BGR PIXEL call followed by
+ * rrv_deliver_view_device into the form asked for.  DH x DW equal to OH x OW is the plain call: no kernel is added and every bit is what it was.
+ *   rrv_deliver_view_device           the delivery stage alone: B (1..64) contiguous float32 [H][W][3] BGR PIXEL frames -> DH x DW frames through
+ *                                     `out`, queued on hip_stream (NULL: the null stream); nothing of the handle's own streams takes part
+ *   rrv_transfer_deliver_view_device  rrv_transfer_scaled_view_device with a delivered size: `out` describes DH x DW frames; SH = SW = 0: the frames
+ *                                     are H x W (no input scaling); DH = DW = 0: the working frame is delivered.  Flags RRV_TF_PAD_CROP |
+ *                                     RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM; the caller's stream waits for the delivery, not for the last kernel
+ *   rrv_transfer_deliver              the host twin through the host pipeline, as rrv_transfer_scaled; flags within RRV_TF_PAD_CROP |
+ *                                     RRV_TF_FRAME_MODE.  The output staging per set is sized by the delivered frame, and a sub-batch additionally
+ *                                     holds at most 4 x the pixel budget of DELIVERED pixels (the rule of the source side)
+ * Checks, all before any GPU work: the output view against (DH, DW), the ratio limits between OH x OW and DH x DW, and everything the scaled entries
+ * check; RRV_E_ARG names the field and the handle stays usable.  The working frames of a launch group live in a second grow-only float32 buffer per
+ * workspace slot (12 bytes per working pixel and frame), reserved with the tables before the call's first launch: out of memory is RRV_E_NOMEM and
+ * the handle stays usable.
+ * Not offered yet: blended and masked delivery, tickets and the one-frame entries. */
+int rrv_deliver_view_device(rrv_handle h, const float* d_in, int B, int H, int W, int DH, int DW,
+                            void* d_out, const rrv_image_view* out, void* hip_stream);
+int rrv_transfer_deliver_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W,
+                                     int DH, int DW, void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W,
+                         int DH, int DW, void* out, rrv_image_desc out_desc, int flags);
 
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */

@@ -27,6 +27,7 @@
 #include "prep_kernels.h"
 #include "mask_kernels.h"
 #include "resample.h"      // librerevst_scale.so: parameters and the launch entry of the resampler
+#include "deliver.h"       // librerevst_deliver.so: the same of the output-side resampler
 
 namespace {
 
@@ -196,6 +197,8 @@ struct rrv_ctx {
         DecPlan dec[2];
         // The scaled entries (Xfer::SH): a launch group's resampled float32 BGR PIXEL frames, grow-only, written and read on the slot's stream
         float* rs_buf = nullptr; size_t rs_cap = 0;
+        // A delivered size (Xfer::DH): a launch group's stylized working frames, float32 BGR PIXEL, grow-only, between conv_last_k and deliver_k
+        float* dl_buf = nullptr; size_t dl_cap = 0;
         int set_images = 0;                          // images whose state sets the slot's last launch wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
     } slots[RRV_MAX_SLOTS];
     int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots slots
@@ -1177,20 +1180,26 @@ struct Xfer {
     // The scaled entries: the frames as passed are SH x SW and are resampled to the H x W working frame in front of everything else
     // (run_xfer), so H, W and all that derives from them keep describing the working frame.  0: not scaled, the frames are H x W.
     int SH = 0, SW = 0;
+    // A delivered size: the stylized working frame (WH x WW below) is resampled to DH x DW behind the last kernel (run_xfer), and `fmt`, `vout`
+    // and everything sized by the output describe DH x DW frames.  0, or equal to the working frame: the working frame is delivered.
+    int DH = 0, DW = 0;
     // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
     bool on_stream = false; hipStream_t with = nullptr;
 
     bool scaled() const { return SH != 0 || SW != 0; }
     int IH() const { return scaled() ? SH : H; }              // the frame as passed
     int IW() const { return scaled() ? SW : W; }
-    int OH() const { return pad ? H : H / 8 * 8; }            // the frame delivered
-    int OW() const { return pad ? W : W / 8 * 8; }
+    int WH() const { return pad ? H : H / 8 * 8; }            // the stylized working frame: what the last kernel delivers
+    int WW() const { return pad ? W : W / 8 * 8; }
+    bool delivering() const { return (DH != 0 || DW != 0) && (DH != WH() || DW != WW()); }
+    int OH() const { return delivering() ? DH : WH(); }       // the frame delivered
+    int OW() const { return delivering() ? DW : WW(); }
     ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
     ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW(), fmt.cs); }
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
     size_t in_bytes() const { return in_frame_bytes(in.form, IH(), IW(), in.cs); }                                              // per frame, in x.in
-    size_t out_elems() const { return pad ? (size_t)H * W * 3 : (size_t)(H / 8 * 8) * (W / 8 * 8) * 3; }          // per frame (any input size: 8*(H/8) x 8*(W/8))
+    size_t out_elems() const { return (size_t)OH() * OW() * 3; }                                                   // per frame (any input size: 8*(H/8) x 8*(W/8), or the delivered size)
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
         return fmt.yuv ? yuv_frame_samples(OH(), OW(), fmt.cs) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
     }
@@ -2151,6 +2160,7 @@ int rrv_destroy(rrv_handle h) {
     if (h->d_u8) (void)hipFree(h->d_u8);
     if (h->pend_u8) (void)hipFree(h->pend_u8);
     for (rrv_ctx::Slot& sl : h->slots) if (sl.rs_buf) (void)hipFree(sl.rs_buf);
+    for (rrv_ctx::Slot& sl : h->slots) if (sl.dl_buf) (void)hipFree(sl.dl_buf);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
@@ -2843,6 +2853,13 @@ static int rs_reserve(rrv_handle h, int slot, int frames, int SH, int SW, int H,
     rrv_ctx::Slot& sl = h->slots[slot];
     return ensure_dev(h, sl.rs_buf, sl.rs_cap, (size_t)frames * H * W * 3);
 }
+static int check_deliver(rrv_handle h, const char* who, int H, int W, int DH, int DW) {      // H x W: the stylized working frame
+    if (DH < 1 || DW < 1) return fail(h, RRV_E_ARG, std::string(who) + ": DH, DW must be at least 1");
+    if (H < 1 || W < 1) return fail(h, RRV_E_ARG, std::string(who) + ": the working frame must be at least 1 x 1 pixels");
+    if (!rs_ratio_ok(H, DH)) return fail(h, RRV_E_ARG, std::string(who) + ": DH / the working frame's height must be within 1/8 .. 8");
+    if (!rs_ratio_ok(W, DW)) return fail(h, RRV_E_ARG, std::string(who) + ": DW / the working frame's width must be within 1/8 .. 8");
+    return RRV_OK;
+}
 static int check_scale(rrv_handle h, const char* who, int SH, int SW, int H, int W) {
     if (SH < 1 || SW < 1) return fail(h, RRV_E_ARG, std::string(who) + ": SH, SW must be at least 1");
     if (H < 1 || W < 1) return fail(h, RRV_E_ARG, std::string(who) + ": H, W must be at least 1");
@@ -2875,6 +2892,42 @@ static int resample_launch(rrv_handle h, const Seq& q, const void* d_in, InFmt i
     return RRV_OK;
 }
 
+// ---- output size (include/rerevst_hip.h "Scaling, output size"): the delivery stage behind the last kernel
+// everything a delivering request allocates, before its first launch: both axes' tables and room for `frames` working frames in the slot's buffer
+static int dl_reserve(rrv_handle h, int slot, int frames, int H, int W, int DH, int DW) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    rrv_ctx::Slot& sl = h->slots[slot];
+    return ensure_dev(h, sl.dl_buf, sl.dl_cap, (size_t)frames * H * W * 3);
+}
+// the deliver_k instantiation that writes `f`
+static int deliver_form(OutFmt f) { return f.yuv ? (yuv16_layout(f.yuv) ? DL_YUV16 : DL_YUV8) : f.u8 ? (f.chw ? DL_U8_CHW : DL_U8_HWC) : (f.chw ? DL_F32_CHW : DL_F32_HWC); }
+// B contiguous float32 [H][W][3] BGR PIXEL frames at d_in -> DH x DW frames in the format `fmt` through `vo` at d_out, queued on q.stream.  The
+// tables exist already or are built here (dl_reserve has run for the entries that promise no allocation between launches).
+static int deliver_launch(rrv_handle h, const Seq& q, const float* d_in, int B, int H, int W, int DH, int DW, void* d_out, OutFmt fmt, const ImgView& vo) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    DeliverP p{};
+    p.in = d_in; p.H = H; p.W = W; p.B = B; p.DH = DH; p.DW = DW; p.out = d_out; p.v = vo;
+    p.ay = ty->axis; p.ax = tx->axis;
+    p.tiles_x = (DW + RS_TW - 1) / RS_TW; p.tiles_y = (DH + RS_TH - 1) / RS_TH; p.rows = ty->span;
+    p.space = fmt.space;
+    if (fmt.yuv) {
+        const YuvLaunch y = yuv_launch_params(h->yuv_out, false, yuv16_layout(fmt.yuv), fmt.yuv == RRV_LAY_P016);
+        memcpy(p.yuv_m, y.m, sizeof p.yuv_m); p.yuv_hi = y.hi; p.yuv_shift = y.shift;
+        p.nv12 = fmt.yuv == RRV_LAY_NV12 || fmt.yuv == RRV_LAY_P016;
+        p.csx = chroma_sx(fmt.cs); p.csy = chroma_sy(fmt.cs);
+    }
+    int e = 0;
+    // for the profile log: bytes from the shapes (12 per working pixel read, the delivered frame written); operations as the resampler's
+    const double out_bytes = (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt)) * DH * DW;
+    RCHK(launch(h, q, "deliver", 2.0 * B * 3 * ((double)tx->span / RS_TH * H * DW + (double)ty->span / RS_TH * DH * DW), (12.0 * H * W + out_bytes) * B, [&] {
+        e = rrv_deliver_launch(&p, deliver_form(fmt), q.stream);
+    }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("deliver: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+
 // The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
 // burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
 static int next_device_slot(rrv_handle h) {
@@ -2891,6 +2944,7 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false, bool state
     if (x.pad && (x.H < 1 || x.W < 1)) return fail(h, RRV_E_ARG, "transfer: frames must be at least 1 x 1 pixels");
     RCHK(check_frame(h, x.KH(), x.KW(), "transfer"));      // the geometry the kernels run, refused before any staging is sized for it
     if (x.scaled()) RCHK(check_scale(h, "transfer", x.SH, x.SW, x.H, x.W));
+    if (x.DH != 0 || x.DW != 0) RCHK(check_deliver(h, "transfer", x.WH(), x.WW(), x.DH, x.DW));
     if ((blend || mask) && (x.ns < 1 || x.ns > RRV_MAX_STYLES)) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
     if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
     if (mask && !x.mask) return fail(h, RRV_E_ARG, "transfer: null mask");
@@ -2933,10 +2987,15 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     // A scaled request resamples each launch group's frames in front of its model (the resampler reads the caller's frames, so it is
     // bracketed here for every model); what the request allocates for that exists before the first launch.
     const bool scaled = x.scaled();
-    if (scaled) RCHK(rs_reserve(h, slot, x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX), x.SH, x.SW, x.H, x.W));
+    // A delivering request runs each launch group's model into the slot's buffer of working frames (float32 HWC BGR PIXEL) and the delivery
+    // stage from there to the caller's frames, on the same sequence; the bracket covers it, so the caller's stream waits for deliver_k.
+    const bool delivering = x.delivering();
+    const int group_frames = x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX);
+    if (scaled) RCHK(rs_reserve(h, slot, group_frames, x.SH, x.SW, x.H, x.W));
+    if (delivering) RCHK(dl_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
     rrv_ctx::Slot& sl = h->slots[slot];
     const CallerOrder caller = x.order(h);
-    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled);
+    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || delivering);
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, caller.stream));
         HIPCHK(hipStreamWaitEvent(sl.stream, sl.ev, 0));
@@ -2946,11 +3005,14 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const size_t fb = (size_t)vi.fs * in_elem(x.in.form), fo = (size_t)vo.fs * out_view_elem(x.fmt);      // bytes from a frame to the next
     const PadCrop crop = x.pad_crop();
     const ImgView vw = contiguous_view(VL_HWC, x.H, x.W);      // a scaled request's working frames: float32 HWC BGR PIXEL in the slot's buffer
-    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi, &vo, caller};
+    const ImgView vd = contiguous_view(VL_HWC, x.WH(), x.WW());    // a delivering request's stylized working frames, the same form in the slot's other buffer
+    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, delivering ? OUT_F32 : x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi,
+                     delivering ? &vd : &vo, caller};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* in = (const uint8_t*)d_in + (size_t)b0 * fb;
-        void* const out = (char*)d_out + (size_t)b0 * fo;
+        void* const dst = (char*)d_out + (size_t)b0 * fo;      // the group's frames as the caller gets them
+        void* const out = delivering ? (void*)sl.dl_buf : dst;
         // the group's sequence: GLOBAL and MASK read no set of the slot's own, FRAME writes and BLEND blends into them (image g: set g of the slot's);
         // GLOBAL and BLEND are the per-frame path (transfer_device), where F(4x4,3x3) may run
         Seq q = slot_seq(h, slot, x.model == Model::FRAME || x.model == Model::BLEND);
@@ -2977,6 +3039,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             sl.set_images = cnt;
             break;
         }
+        if (delivering) RCHK(deliver_launch(h, q, sl.dl_buf, cnt, x.WH(), x.WW(), x.DH, x.DW, dst, x.fmt, vo));
     }
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, sl.stream));
@@ -3308,6 +3371,8 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // HOST_SUB_PIXELS of source pixels (2 x per axis keeps the unscaled call's sub-batches; at 8 x 8 a sub-batch is one or two frames), so
     // the page-locked and device staging per set stays within four times the unscaled call's.
     if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
+    // the same rule for the DELIVERED frame, which sizes the output staging
+    if (x.delivering()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.DH * x.DW)));
     const size_t mfl = x.mask_floats();
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
@@ -3330,13 +3395,16 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // The tail wait and the piecewise delivery (SeqHook) order the sub-batches of the models that run transfer_device, on two streams with
     // staged copies both ways.  Everything else keeps one launch per layer and sub-batch, unordered: one sub-batch or one stream, the
     // profiled step (slot 0 only), the debug levels, a caller's stream, zero copy.
+    // A delivering request too: the piecewise drain hooks into transfer_device's last launch, which is then not the request's last kernel.
     const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !x.order(h).sync && h->host_io == 0 &&
-                         (x.model == Model::GLOBAL || x.model == Model::BLEND);
+                         (x.model == Model::GLOBAL || x.model == Model::BLEND) && !x.delivering();
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
     if (x.scaled())      // a scaled request: the tables and each compute slot's buffer of working frames, before the first launch
         for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(rs_reserve(h, slot_of(k), sub, x.SH, x.SW, x.H, x.W));      // (slot_of has period 2)
+    if (x.delivering())      // a delivering request: the same for the stylized working frames
+        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(dl_reserve(h, slot_of(k), sub, x.WH(), x.WW(), x.DH, x.DW));
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));
@@ -3570,6 +3638,30 @@ int rrv_transfer_scaled_view_device(rrv_handle h, const void* d_in, const rrv_im
     if (h && !x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled_view: SH, SW must be at least 1");
     return view_run(h, "transfer_scaled_view", d_in, in, d_out, out, flags, hip_stream, x);
 }
+// ---- the delivering entries: the stylized working frame resampled to DH x DW behind the last kernel (run_xfer)
+// the delivery stage alone, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own streams takes part
+int rrv_deliver_view_device(rrv_handle h, const float* d_in, int B, int H, int W, int DH, int DW, void* d_out, const rrv_image_view* out, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!out) return fail(h, RRV_E_ARG, "deliver_view: null view");
+    OutFmt fmt;
+    if (!view_desc_ok(out->desc) || parse_out(out->desc, &fmt) != DescErr::OK)
+        return fail(h, RRV_E_ARG, "deliver_view: out.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_in || !d_out) return fail(h, RRV_E_ARG, "deliver_view: null buffer");
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "deliver_view: batch must be in 1..64");
+    RCHK(check_deliver(h, "deliver_view", H, W, DH, DW));
+    std::string why;
+    if (!view_check(*out, B, DH, DW, true, &why)) return fail(h, RRV_E_ARG, "deliver_view: out." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    return deliver_launch(h, q, d_in, B, H, W, DH, DW, d_out, fmt, img_view(*out));
+}
+int rrv_transfer_deliver_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, int DH, int DW,
+                                     void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    return view_run(h, "transfer_deliver_view", d_in, in, d_out, out, flags, hip_stream, x);
+}
 // a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
     if (yuv_layout(d.layout)) return parse_in_view(d, in);
@@ -3586,6 +3678,19 @@ int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int
     if (!x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled: SH, SW must be at least 1");
     if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
         return fail(h, RRV_E_ARG, "transfer_scaled: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
+    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
+    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
+    return host_pipeline(h, (const uint8_t*)frames, out, x);
+}
+int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, void* out,
+                         rrv_image_desc od, int flags) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    if (!parse_in_host(in, &x.in)) return fail(h, RRV_E_ARG, "transfer_deliver: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_deliver: unknown flags");
+    if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
+        return fail(h, RRV_E_ARG, "transfer_deliver: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
     if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
     x.pad = (flags & RRV_TF_PAD_CROP) != 0;
     return host_pipeline(h, (const uint8_t*)frames, out, x);

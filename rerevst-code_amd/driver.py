@@ -423,7 +423,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420", work_size=None):
+                  chroma="420", work_size=None, out_size=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -440,7 +440,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     (out_format="i420p10" ..: the codes are roundings of the float32 result, not of its 8-bit form).  chroma "422" / "444": a C422 /
     C444 stream (out_format "i422", "i444p10", ..); it belongs to a .y4m video_path, anything else is a ValueError.
     work_size=(H, W): every frame, the sampled ones included, is resampled to that working size on the GPU (add / transfer_frames with
-    work_size=); the frames and the video written have the working size.  Needs a model with transfer_frames(work_size=)."""
+    work_size=); the frames and the video written have the working size.  Needs a model with transfer_frames(work_size=).
+    out_size=(H, W) or "source": the stylized working frame is resampled to that size on the GPU on its way out (transfer_frames with
+    out_size=; "source": each frame's own size); the frames and the video written have that size."""
     import importlib
     import time
     from collections import deque
@@ -462,7 +464,12 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     encode, open_writer = video_sink(video_path, fps, yuv, bits=bit_depth, chroma=chroma) if video_path is not None else (None, None)
     work = None if work_size is None else (int(work_size[0]), int(work_size[1]))
     scale_kw = {} if work is None else {"work_size": work}
-    out_size = (lambda hw: hw) if work is None else (lambda hw: work)      # the size of the frame delivered for a source frame of (H, W)
+    deliver = None if out_size is None else "source" if isinstance(out_size, str) and out_size == "source" else (int(out_size[0]), int(out_size[1]))
+    if deliver is not None:
+        scale_kw = dict(scale_kw, out_size=deliver)
+    add_kw = {} if work is None else {"work_size": work}                   # (a sampled frame is never delivered)
+    # the size of the frame delivered for a source frame of (H, W)
+    out_size = (lambda hw: hw) if deliver == "source" else (lambda hw: deliver) if deliver is not None else (lambda hw: hw) if work is None else (lambda hw: work)
     t_start = time.perf_counter()
     with ThreadPoolExecutor(nthreads) as pool:
         # ---- once per video (generate_real_video.py:95-146); the sampled frames are decoded in parallel
@@ -475,7 +482,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
                 model.clean()
                 for f in pool.map(read_image_bgr, [frame_paths[i] for i in ids]):
-                    model.add(f, **scale_kw)
+                    model.add(f, **add_kw)
                 model.compute()
                 if world > 1:
                     blob = model.get_state()
@@ -605,6 +612,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             # frame mode, or a model with only the reference's transfer(): per frame, decode and encode still on the worker threads
             if work is not None and hi > lo:
                 raise ValueError("work_size needs a model with transfer_frames(work_size=)")
+            if deliver is not None and hi > lo:
+                raise ValueError("out_size needs a model with transfer_frames(out_size=)")
             tool = video.ReshapeTool()
             pending = deque()
             look = deque(pool.submit(read_image_bgr, frame_paths[i]) for i in range(lo, min(hi, lo + 2 * nthreads)))
@@ -644,7 +653,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
-                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None):
+                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None, out_size=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -657,7 +666,9 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     chroma: the chroma format of a .y4m output, "420" / "422" / "444"; None (default): the input file's, so a C422p10 file goes to a
     C422p10 file with no pixel pass on the host.
     work_size=(H, W): the file's frames are resampled to that working size on the GPU (add / transfer_frames with work_size=, size= stays the
-    file's); the frames written and the .y4m header carry the working size."""
+    file's); the frames written and the .y4m header carry the working size.
+    out_size=(H, W) or "source" (the file's frame size): the stylized working frame is resampled to that size on the GPU on its way out
+    (transfer_frames with out_size=); the frames written, the output staging and the .y4m header carry the delivered size."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -676,8 +687,12 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         y4m = is_y4m(video_path)
         out_chroma = check_chroma(chroma, y4m) if chroma is not None else reader.chroma if y4m else "420"
         in_fmt, out_fmt = y4m_format(reader.chroma, in_bits), y4m_format(out_chroma, out_bits)
-        OH, OW = (H, W) if work_size is None else (int(work_size[0]), int(work_size[1]))      # the frame delivered
-        scale_kw = {} if work_size is None else {"work_size": (OH, OW)}
+        add_kw = {} if work_size is None else {"work_size": (int(work_size[0]), int(work_size[1]))}
+        scale_kw = dict(add_kw)
+        OH, OW = (H, W) if work_size is None else add_kw["work_size"]      # the frame delivered
+        if out_size is not None:
+            OH, OW = (H, W) if isinstance(out_size, str) and out_size == "source" else (int(out_size[0]), int(out_size[1]))
+            scale_kw["out_size"] = (OH, OW)
         fob = video.yuv_frame_bytes(OH, OW, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
@@ -695,7 +710,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
             log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
             model.clean()
             for i in ids:
-                model.add(reader.read(i), in_format=in_fmt, size=size, **scale_kw)
+                model.add(reader.read(i), in_format=in_fmt, size=size, **add_kw)
             model.compute()
         t_prep = time.perf_counter()
         direct = y4m and not write_frames
@@ -878,6 +893,22 @@ def _self_launch(n_ranks, argv):
     return rc
 
 
+def parse_out_size(text):
+    """--out-size: "source", or WIDTHxHEIGHT as (H, W); ValueError for anything else"""
+    if text.lower() == "source":
+        return "source"
+    parts = text.lower().split("x")
+    if len(parts) != 2:
+        raise ValueError("--out-size is WIDTHxHEIGHT, e.g. 3840x2160, or 'source'")
+    try:
+        w, h = int(parts[0]), int(parts[1])
+    except ValueError:
+        raise ValueError("--out-size is WIDTHxHEIGHT, e.g. 3840x2160, or 'source'") from None
+    if w < 1 or h < 1:
+        raise ValueError("--out-size is at least 1x1")
+    return h, w
+
+
 def main(argv=None, model_factory=None):
     """`model_factory(args, device)` builds the model (default: the HIP Stylization / MultiStyleStylization); the CPU tests
     of the multi-rank control flow pass their own."""
@@ -905,7 +936,18 @@ def main(argv=None, model_factory=None):
     ap.add_argument("--chunk", type=int, default=32, help="frames per transfer_frames call")
     ap.add_argument("--work-size", default=None, metavar="WxH", help="resample every frame to this working size on the GPU (antialiased; at most 8x either "
                     "way per axis): the frames and the video written have this size.  The working size sets the stroke size of the result, and the speed")
+    ap.add_argument("--out-size", default=None, metavar="WxH|source", help="resample the stylized frame to this size on the GPU on its way out (at most 8x "
+                    "either way per axis from the working frame); 'source': the size of the frames read.  With --work-size: stylize at the working size, "
+                    "write the source's resolution.  The frames and the video written have this size")
     args = ap.parse_args(argv)
+    out_size = None
+    if args.out_size is not None:
+        try:
+            out_size = parse_out_size(args.out_size)
+        except ValueError as e:
+            ap.error(str(e))
+        if len(args.style) > 1:
+            ap.error("--out-size with multi-style interpolation is not supported: the cached-feature entries deliver the frame they run")
     work_size = None
     if args.work_size is not None:
         try:
@@ -977,14 +1019,15 @@ def main(argv=None, model_factory=None):
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
                     write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma,
-                    work_size=work_size)
+                    work_size=work_size, out_size=out_size)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
     else:
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
-                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size)
+                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
+                      out_size=out_size)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

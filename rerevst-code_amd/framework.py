@@ -509,6 +509,30 @@ def _no_styles_with_work_size(style_weights, style_masks):
         raise ValueError("work_size does not combine with style_weights / style_masks yet: scale the frames with resample_tensor first")
 
 
+def _out_size(out_size, source):
+    """(DH, DW) of an out_size= keyword: the size the stylized working frame is resampled to on the GPU on its way out.  "source": the
+    size of the frames as passed, `source` = (H, W)"""
+    if isinstance(out_size, str):
+        if out_size != "source":
+            raise ValueError("out_size must be (H, W) or 'source', got %r" % (out_size,))
+        return int(source[0]), int(source[1])
+    try:
+        ok = len(out_size) == 2 and all(int(v) == v for v in out_size)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("out_size must be (H, W) or 'source', got %r" % (out_size,))
+    DH, DW = int(out_size[0]), int(out_size[1])
+    if DH < 1 or DW < 1:
+        raise ValueError("out_size must be at least 1 x 1, got %d x %d" % (DH, DW))
+    return DH, DW
+
+
+def _no_styles_with_out_size(style_weights, style_masks):
+    if style_weights is not None or style_masks is not None:
+        raise ValueError("out_size does not combine with style_weights / style_masks yet: deliver the blended frames with deliver_tensor")
+
+
 def _host_in_desc(in_format):
     """rrv_image_desc of host frames as the scaled host entries take them: uint8 BGR HWC, or a YUV format by name"""
     if in_format == "bgr":
@@ -939,7 +963,8 @@ class Stylization():
         name = "rrv_transfer_batch_device" if self.use_Global else "rrv_transfer_frame_mode_batch_device"
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
-    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None):
+    def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None,
+                     out_size=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
         size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
@@ -951,6 +976,20 @@ class Stylization():
             a = _u8_frames(frames, "frame")
             H, W = a.shape[1:3]
         B = a.shape[0]
+        if out_size is not None:       # rrv_transfer_deliver: the stylized working frame leaves as DH x DW frames; SH = SW = 0: no input scaling
+            _no_styles_with_out_size(style_weights, style_masks)
+            DH, DW = _out_size(out_size, (H, W))
+            SH = SW = 0
+            if work_size is not None:
+                (SH, SW), (H, W) = (H, W), _work_size(work_size)
+            out, u8 = _output((B, DH, DW, 3), dtype, out, out_format)
+            self._yuv_depth(in_format, out_format)
+            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
+            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+            flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+            self._chk(self._lib.rrv_transfer_deliver(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, SH, SW, H, W, DH, DW,
+                                                     out.ctypes.data_as(C.c_void_p), desc, flags))
+            return out
         if work_size is not None:      # rrv_transfer_scaled: the frames as passed are SH x SW, everything from here on has the working size
             _no_styles_with_work_size(style_weights, style_masks)
             (SH, SW), (H, W) = (H, W), _work_size(work_size)
@@ -988,7 +1027,7 @@ class Stylization():
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                       work_size=None):
+                       work_size=None, out_size=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -1015,11 +1054,16 @@ class Stylization():
         depth and layout between input and output works ("nv12" in, "p210" out).
         work_size=(H, W): the frames are resampled to that working size on the GPU first (rrv_transfer_scaled: an antialiased triangle
         filter, include/rerevst_hip.h "Scaling") and the result has the working size; size= stays the size of YUV frames as passed.
-        Each axis scales by at most 8 either way.  Not with style_weights / style_masks (ValueError)."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size)
+        Each axis scales by at most 8 either way.  Not with style_weights / style_masks (ValueError).
+        out_size=(DH, DW) or "source": the stylized working frame is resampled to that size on the GPU on its way out (rrv_transfer_deliver;
+        include/rerevst_hip.h "Scaling, output size") and converted to `out` / `dtype` / out_format there: [B][DH][DW][3], or the YUV frames
+        of that size.  "source" is the size of the frames as passed: with work_size, "stylize at the working size, give me back my
+        resolution"; without it, H x W in place of 8*(H//8) x 8*(W//8).  At most 8 either way per axis; not with style_weights /
+        style_masks (ValueError)."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                        work_size=None):
+                        work_size=None, out_size=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -1033,8 +1077,9 @@ class Stylization():
         in_format / size: "i420" / "nv12" input frames [B][yuv_frame_bytes(H, W)], as in transfer_batch; with out_format set too, a
         decoder's frames go to an encoder with no pixel touched on the host.
         work_size=(H, W): as in transfer_batch; the resampled H x W frame is what gets reflect-padded and cropped, and [B][H][W][3]
-        (or the YUV frames of that size) is what comes back."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size)
+        (or the YUV frames of that size) is what comes back.
+        out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -1042,7 +1087,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None):
+                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -1076,8 +1121,16 @@ class Stylization():
         of the contiguous call on the same pixels.  The memory x and out address must not overlap.
         work_size=(H, W): the frames (any of the forms above; size= stays the size of YUV frames as passed) are resampled to that working
         size on the GPU first (rrv_transfer_scaled_view_device; include/rerevst_hip.h "Scaling"), and the output has the working size:
-        [.., H, W] with pad_crop, else [.., 8*(H//8), 8*(W//8)].  Not with style_weights / style_masks (ValueError)."""
+        [.., H, W] with pad_crop, else [.., 8*(H//8), 8*(W//8)].  Not with style_weights / style_masks (ValueError).
+        out_size=(DH, DW) or "source" (the size of the frames as passed): the stylized working frame is resampled to that size on the GPU
+        on its way out (rrv_transfer_deliver_view_device; include/rerevst_hip.h "Scaling, output size"), with or without work_size, into
+        any out_layout / out_space / out_dtype or `out` (a tensor, a window or an ImageView of DH x DW frames): [.., DH, DW].  A "norm"
+        output is then the normalised delivered pixel (a resampled frame has no pre-clamp value).  Not with style_weights / style_masks."""
         import torch
+        if out_size is not None:
+            _no_styles_with_out_size(style_weights, style_masks)
+            return self._transfer_tensor_scaled(x, None if work_size is None else _work_size(work_size), space, out_space, out_dtype, layout, out_layout,
+                                                pad_crop, out, size, out_size)
         if work_size is not None:
             _no_styles_with_work_size(style_weights, style_masks)
             return self._transfer_tensor_scaled(x, _work_size(work_size), space, out_space, out_dtype, layout, out_layout, pad_crop, out, size)
@@ -1164,16 +1217,21 @@ class Stylization():
             self._chk(plain_fn(self._h, src, in_arg, nb, H, W, dst, out_arg, flags, stream))
         return out
 
-    def _transfer_tensor_scaled(self, x, work, space, out_space, out_dtype, layout, out_layout, pad_crop, out, size):
-        """transfer_tensor(work_size=): the source through its view, the output side worked out for the working size"""
+    def _transfer_tensor_scaled(self, x, work, space, out_space, out_dtype, layout, out_layout, pad_crop, out, size, out_size=None):
+        """transfer_tensor(work_size=, out_size=): the source through its view, the output side worked out for the working size, or for the
+        delivered size of out_size (work None: no input scaling)"""
         import torch
-        H, W = work
         vi, in_ptr, B, SH, SW, batched, dev_t, layout = self._source_view(x, space, layout, size)
+        DH, DW = (0, 0) if out_size is None else _out_size(out_size, (SH, SW))
+        if work is None:
+            (H, W), (SH, SW) = (SH, SW), (0, 0)
+        else:
+            H, W = work
         ov = out if isinstance(out, ImageView) else None
         if out_layout is None:
             out_layout = ov.layout if ov is not None else layout
         _check_out_layout(out_layout, out_space)
-        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+        Ho, Wo = (DH, DW) if out_size is not None else (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
         if ov is not None:      # written in place, through the view
             _on_device(ov.storage, "out.storage", self.device)
             if out_layout != ov.layout:
@@ -1185,7 +1243,8 @@ class Stylization():
                 raise ValueError("out: the planes and frames of an output view must not overlap")
             out_ptr = ov.storage.data_ptr()
         else:
-            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
+            oh, ow, whole = (Ho, Wo, True) if out_size is not None else (H, W, pad_crop)      # (a delivered size is the output's size as it is)
+            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, oh, ow, batched, out_space, out_dtype, out_layout, whole, out)
             if out is None:
                 out = torch.empty(out_shape, dtype=out_dtype, device=dev_t.device)
             if vo is None:
@@ -1197,8 +1256,54 @@ class Stylization():
         stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
         for b0 in range(0, B, TENSOR_BATCH_MAX):
             nb = min(TENSOR_BATCH_MAX, B - b0)
-            self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, C.c_void_p(in_ptr + b0 * in_step), C.byref(vi), nb, SH, SW, H, W,
-                                                                C.c_void_p(out_ptr + b0 * out_step), C.byref(vo), flags, stream))
+            src, dst = C.c_void_p(in_ptr + b0 * in_step), C.c_void_p(out_ptr + b0 * out_step)
+            if out_size is not None:
+                self._chk(self._lib.rrv_transfer_deliver_view_device(self._h, src, C.byref(vi), nb, SH, SW, H, W, DH, DW, dst, C.byref(vo), flags, stream))
+            else:
+                self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, src, C.byref(vi), nb, SH, SW, H, W, dst, C.byref(vo), flags, stream))
+        return out
+
+    def deliver_tensor(self, y, out_size, *, out_space="pixel", out_dtype=None, out_layout=None, out=None):
+        """The delivery stage alone (rrv_deliver_view_device): y a float32 tensor [B,H,W,3] ([H,W,3]) on the handle's GPU, BGR, "pixel"
+        space — what transfer_tensor(.., layout="nhwc") and resample_tensor return — resampled to out_size=(DH, DW) on the GPU and written
+        as transfer_tensor(out_size=) writes it: out_layout ("nhwc" by default, "nchw", or a YUV format name), out_space, out_dtype, or
+        `out` (a tensor, a window of a canvas, or an ImageView of DH x DW frames).  Ordered on the current stream, like resample_tensor."""
+        import torch
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() not in (3, 4) or y.shape[-1] != 3:
+            raise ValueError("y must be a float32 tensor [B,H,W,3] or [H,W,3] (BGR, 'pixel' space)")
+        _on_device(y, "y", self.device)
+        batched = y.dim() == 4
+        yb = (y if batched else y.unsqueeze(0)).contiguous()
+        B, H, W = yb.shape[:3]
+        DH, DW = _out_size(out_size, (H, W))
+        ov = out if isinstance(out, ImageView) else None
+        if out_layout is None:
+            out_layout = ov.layout if ov is not None else "nhwc"
+        _check_out_layout(out_layout, out_space)
+        if ov is not None:
+            _on_device(ov.storage, "out.storage", self.device)
+            if out_layout != ov.layout:
+                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
+            if (ov.frames, ov.H, ov.W) != (B, DH, DW):
+                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, DH, DW, ov.frames, ov.H, ov.W))
+            vo = ov.with_space(out_space, "out")
+            if self._lib.rrv_image_view_check(C.byref(vo), B, DH, DW, 1) != 0:
+                raise ValueError("out: the planes and frames of an output view must not overlap")
+            out_ptr = ov.storage.data_ptr()
+        else:
+            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, DH, DW, batched, out_space, out_dtype, out_layout, True, out)
+            if out is None:
+                out = torch.empty(out_shape, dtype=out_dtype, device=y.device)
+            if vo is None:
+                vo = _contiguous_view(out_desc, DH, DW)
+            out_ptr = out.data_ptr()
+        out_step = vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
+        self._yuv_depth(None, out_layout)
+        stream = C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
+        for b0 in range(0, B, TENSOR_BATCH_MAX):
+            nb = min(TENSOR_BATCH_MAX, B - b0)
+            self._chk(self._lib.rrv_deliver_view_device(self._h, C.c_void_p(yb[b0].data_ptr()), nb, H, W, DH, DW, C.c_void_p(out_ptr + b0 * out_step),
+                                                        C.byref(vo), stream))
         return out
 
     def sync(self):
