@@ -3591,16 +3591,23 @@ int rrv_transfer_mask_batch_yuv(rrv_handle h, const uint8_t* frames, int B, int 
 
 // 8-bit YUV 4:2:0 input of the host entries (conv_first_k<IN_YUV_*>): frame b at b * (H*W + 2*CH*CW) bytes of `frames`; `out` as float32 or
 // uint8 HWC BGR PIXEL frames or as I420 / NV12.  The staging, the zero-copy path and the copy pool size a frame by Xfer::in_bytes.
-static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, void* out, rrv_image_desc od, int flags, int known_flags, Xfer x) {
-    if (!h) return RRV_E_ARG;
-    if (parse_in_yuv(in_layout, &x.in) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
-    if (flags & ~known_flags) return fail(h, RRV_E_ARG, "transfer_from_yuv: unknown flags");
-    if (x.H < 8 || x.W < 8) return fail(h, RRV_E_ARG, "transfer_from_yuv: frames must be at least 8 x 8 pixels");
+// The host entries that name their output by descriptor (_from_yuv, _scaled, _deliver) end alike, once each has parsed its input: the flags
+// against those the entry knows, a refusal of the family's own (`refused`: its text, nullptr: none), the output descriptor, flags -> model
+// and pad, the pipeline.  family: the entry family's name, the prefix of every refusal.
+static int desc_host(rrv_handle h, const char* family, const uint8_t* frames, void* out, rrv_image_desc od, int flags, int known_flags, const char* refused, Xfer x) {
+    const std::string who = std::string(family) + ": ";
+    if (flags & ~known_flags) return fail(h, RRV_E_ARG, who + "unknown flags");
+    if (refused) return fail(h, RRV_E_ARG, who + refused);
     if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
-        return fail(h, RRV_E_ARG, "transfer_from_yuv: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
+        return fail(h, RRV_E_ARG, who + "the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
     if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
     x.pad = (flags & RRV_TF_PAD_CROP) != 0;
     return host_pipeline(h, frames, out, x);
+}
+static int from_yuv_host(rrv_handle h, const uint8_t* frames, int in_layout, void* out, rrv_image_desc od, int flags, int known_flags, Xfer x) {
+    if (!h) return RRV_E_ARG;
+    if (parse_in_yuv(in_layout, &x.in) != DescErr::OK) return refuse_layout(h, "transfer_from_yuv: in_layout");
+    return desc_host(h, "transfer_from_yuv", frames, out, od, flags, known_flags, x.H < 8 || x.W < 8 ? "frames must be at least 8 x 8 pixels" : nullptr, x);
 }
 int rrv_transfer_from_yuv(rrv_handle h, const uint8_t* frames, int in_layout, int B, int H, int W, void* out, rrv_image_desc od, int flags) {
     return from_yuv_host(h, frames, in_layout, out, od, flags, RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE, Xfer{Model::GLOBAL, B, H, W});
@@ -3631,12 +3638,17 @@ int rrv_resample_view_device(rrv_handle h, const void* d_in, const rrv_image_vie
     q.stream = (hipStream_t)hip_stream;
     return resample_launch(h, q, d_in, fmt, img_view(*in), B, SH, SW, H, W, d_out);
 }
+// the transfer behind the resampler and / or in front of the delivery stage (DH = DW = 0: none), views on both sides
+static int scaled_view_run(rrv_handle h, const char* who, bool must_scale, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W,
+                           int DH, int DW, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    if (must_scale && h && !x.scaled()) return fail(h, RRV_E_ARG, std::string(who) + ": SH, SW must be at least 1");
+    return view_run(h, who, d_in, in, d_out, out, flags, hip_stream, x);
+}
 int rrv_transfer_scaled_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, void* d_out,
                                     const rrv_image_view* out, int flags, void* hip_stream) {
-    Xfer x{Model::GLOBAL, B, H, W};
-    x.SH = SH; x.SW = SW;
-    if (h && !x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled_view: SH, SW must be at least 1");
-    return view_run(h, "transfer_scaled_view", d_in, in, d_out, out, flags, hip_stream, x);
+    return scaled_view_run(h, "transfer_scaled_view", true, d_in, in, B, SH, SW, H, W, 0, 0, d_out, out, flags, hip_stream);
 }
 // ---- the delivering entries: the stylized working frame resampled to DH x DW behind the last kernel (run_xfer)
 // the delivery stage alone, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own streams takes part
@@ -3658,9 +3670,7 @@ int rrv_deliver_view_device(rrv_handle h, const float* d_in, int B, int H, int W
 }
 int rrv_transfer_deliver_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, int DH, int DW,
                                      void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
-    Xfer x{Model::GLOBAL, B, H, W};
-    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
-    return view_run(h, "transfer_deliver_view", d_in, in, d_out, out, flags, hip_stream, x);
+    return scaled_view_run(h, "transfer_deliver_view", false, d_in, in, B, SH, SW, H, W, DH, DW, d_out, out, flags, hip_stream);
 }
 // a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
@@ -3669,31 +3679,24 @@ static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
     *in = IN_BGR8;
     return true;
 }
-int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, void* out, rrv_image_desc od, int flags) {
+// the scaled host entries: SH x SW frames in the format `in`, through desc_host
+static int scaled_host(rrv_handle h, const char* family, bool must_scale, const void* frames, rrv_image_desc in, void* out, rrv_image_desc od, int flags, Xfer x) {
     if (!h) return RRV_E_ARG;
+    if (!parse_in_host(in, &x.in))
+        return fail(h, RRV_E_ARG, std::string(family) + ": the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    return desc_host(h, family, (const uint8_t*)frames, out, od, flags, RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE,
+                     must_scale && !x.scaled() ? "SH, SW must be at least 1" : nullptr, x);
+}
+int rrv_transfer_scaled(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, void* out, rrv_image_desc od, int flags) {
     Xfer x{Model::GLOBAL, B, H, W};
     x.SH = SH; x.SW = SW;
-    if (!parse_in_host(in, &x.in)) return fail(h, RRV_E_ARG, "transfer_scaled: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
-    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_scaled: unknown flags");
-    if (!x.scaled()) return fail(h, RRV_E_ARG, "transfer_scaled: SH, SW must be at least 1");
-    if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
-        return fail(h, RRV_E_ARG, "transfer_scaled: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
-    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
-    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
-    return host_pipeline(h, (const uint8_t*)frames, out, x);
+    return scaled_host(h, "transfer_scaled", true, frames, in, out, od, flags, x);
 }
 int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, void* out,
                          rrv_image_desc od, int flags) {
-    if (!h) return RRV_E_ARG;
     Xfer x{Model::GLOBAL, B, H, W};
     x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
-    if (!parse_in_host(in, &x.in)) return fail(h, RRV_E_ARG, "transfer_deliver: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
-    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_deliver: unknown flags");
-    if (parse_out(od, &x.fmt) != DescErr::OK || x.fmt.chw || x.fmt.space != SP_PIXEL)
-        return fail(h, RRV_E_ARG, "transfer_deliver: the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
-    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
-    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
-    return host_pipeline(h, (const uint8_t*)frames, out, x);
+    return scaled_host(h, "transfer_deliver", false, frames, in, out, od, flags, x);
 }
 // a sampled frame of SH x SW, resampled into slot 0's buffer on the handle's stream and added as the float32 PIXEL frame it then is.
 // device: d_frame is in HBM, complete once `stream` has run what it holds now; else host memory in the contiguous form of `fmt`

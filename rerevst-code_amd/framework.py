@@ -112,6 +112,12 @@ def _out_u8(dtype):
     return dt == np.uint8
 
 
+def _stylized_size(H, W, pad_crop=False):
+    """(Ho, Wo) of a stylized H x W frame: the frame's own size in the pad / crop geometry (transfer_frames, pad_crop=True); otherwise the
+    max pools floor it to multiples of 8, as in the reference"""
+    return (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+
+
 def _output(shape, dtype, out, out_format="bgr"):
     """(output array, uint8?) of a host entry; shape: [..][Ho][Wo][3], the stylized frames as BGR.  float32 BGR in 0..255 as the
     reference returns it, or uint8: the same values rounded half to even on the GPU (== driver.to_uint8 of the float output, bit for
@@ -394,11 +400,29 @@ def _check_out_layout(out_layout, out_space):
     return yuv
 
 
+def _yuv_in_pixel_space(layout, space):
+    if space != "pixel":
+        raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
+
+
+def _check_in_names(space, layout, size, yuv=True):
+    """the checks of a tensor input that do not look at the tensor: a YUV format name (where the entry reads YUV: `yuv`) with its space and
+    size=(H, W), else the space and layout of an image tensor"""
+    if yuv and layout in YUV_FORMATS:
+        _yuv_in_pixel_space(layout, space)
+        _yuv_size(layout, size)
+        return
+    if space not in _SPACES:
+        raise ValueError("space must be one of %s, got %r" % (sorted(_SPACES), space))
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r" % (layout,))
+
+
 def _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out):
     """(out_desc, out_shape, out_dtype) of B stylized H x W input frames: shared by tensor_io_args and yuv_tensor_io_args"""
     import torch
     yuv = out_layout in YUV_FORMATS
-    Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
+    Ho, Wo = _stylized_size(H, W, pad_crop)
     out_shape = (B, yuv_frame_bytes(Ho, Wo, chroma=YUV_FORMATS[out_layout].chroma)) if yuv else (B, 3, Ho, Wo) if out_layout == "nchw" else (B, Ho, Wo, 3)
     if not batched:
         out_shape = out_shape[1:]
@@ -444,10 +468,7 @@ def _tensor_io(x, device, views, *, space="pixel", out_space="pixel", out_dtype=
     (the callers that pass views on: transfer_tensor and add_tensor) and its strides fit an image view (image_view_of): it is then
     returned as it is, in_view holding its strides.  A non-contiguous `out` must fit a view the library accepts as an output
     (out_view), else ValueError."""
-    if space not in _SPACES:
-        raise ValueError("space must be one of %s, got %r" % (sorted(_SPACES), space))
-    if layout not in _LAYOUTS:
-        raise ValueError("layout must be 'nchw' (RGB) or 'nhwc' (BGR), got %r" % (layout,))
+    _check_in_names(space, layout, None, yuv=False)
     out_layout = layout if out_layout is None else out_layout
     _check_out_layout(out_layout, out_space)
     _on_device(x, "x", device)
@@ -491,6 +512,24 @@ def yuv_tensor_io_args(x, device, layout, size, *, out_space="pixel", out_dtype=
     out_desc, out_shape, out_dtype, out_view = _tensor_out_args(device, B, H, W, batched, out_space, out_dtype, out_layout, pad_crop, out)
     return TensorIO(x=x if x.is_contiguous() else x.contiguous(), in_desc=YUV_FORMATS[layout].layout, out_desc=out_desc, out_shape=out_shape,
                     out_dtype=out_dtype, B=B, H=H, W=W, batched=batched, out_view=out_view)
+
+
+# The two sides of a tensor call as Stylization._source / _target resolve them.  desc: the rrv_image_desc; view: the rrv_image_view of a
+# strided side, None for packed frames; ptr: the address of frame 0; step: bytes from one frame to the next; tensor: the tensor that names
+# the device; layout: the layout name ("nchw", "nhwc" or a YUV format); result: what the call returns (`out` itself, or the fresh tensor).
+_Source = collections.namedtuple("_Source", "desc view ptr B H W batched tensor layout step")
+_Target = collections.namedtuple("_Target", "desc view ptr result layout step")
+
+
+def _whole_view(side, H, W):
+    """the rrv_image_view of a side for the entries that take views: its own, or the contiguous view of packed H x W frames"""
+    return side.view if side.view is not None else _contiguous_view(side.desc, H, W)
+
+
+def _chunks(B, *sides, chunk=TENSOR_BATCH_MAX):
+    """B frames in calls of at most `chunk`: (first frame, frames, the address of the first frame on each side = (base, step in bytes))"""
+    for b0 in range(0, B, chunk):
+        yield (b0, min(chunk, B - b0), *(C.c_void_p(ptr + b0 * step) for ptr, step in sides))
 
 
 # ===== scaling (the rrv_*_scaled* entries; include/rerevst_hip.h "Scaling" states the arithmetic) =====
@@ -735,26 +774,21 @@ class Stylization():
         work_size=(H, W): the frame is resampled to that size on the GPU first, as transfer_frames(work_size=) does (rrv_add_scaled);
         size= stays the size of the frame as passed."""
         self._global_only("add")
-        if work_size is not None:
-            H, W = _work_size(work_size)
-            if in_format != "bgr":
-                a, SH, SW = yuv_frames_args(patch, in_format, size)
-                self._yuv_depth(in_format)
-            else:
-                a = _u8_image(patch, "patch")
-                SH, SW = a.shape[:2]
-                a = a[None]
-            for f in a:
-                self._chk(self._lib.rrv_add_scaled(self._h, f.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), SH, SW, H, W))
-            return
+        work = None if work_size is None else _work_size(work_size)
         if in_format != "bgr":
             a, H, W = yuv_frames_args(patch, in_format, size)
             self._yuv_depth(in_format)
-            for f in a:
-                self._chk(self._lib.rrv_add_from_yuv(self._h, f.ctypes.data_as(C.c_void_p), YUV_FORMATS[in_format].layout, H, W))
-            return
-        a = _u8_image(patch, "patch")
-        self._chk(self._lib.rrv_add(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]))
+        else:
+            a = _u8_image(patch, "patch")[None]
+            H, W = a.shape[1:3]
+        for f in a:
+            src = f.ctypes.data_as(C.c_void_p)
+            if work is not None:
+                self._chk(self._lib.rrv_add_scaled(self._h, src, _host_in_desc(in_format), H, W, *work))
+            elif in_format != "bgr":
+                self._chk(self._lib.rrv_add_from_yuv(self._h, src, YUV_FORMATS[in_format].layout, H, W))
+            else:
+                self._chk(self._lib.rrv_add(self._h, src, H, W))
 
     def compute(self):
         self._global_only("compute")
@@ -795,12 +829,57 @@ class Stylization():
             a = _u8_image(s, "style")
             self._chk(self._lib.rrv_prepare_style(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], sid))
 
-    def _device_image(self, x, space, layout, views=False):
-        """(tensor_io_args' result, current stream) of an input image tensor, by transfer_tensor's rules; views: a strided x that fits an
-        image view stays as it is (only for an entry that takes views: the style entries read packed images)"""
+    def _stream(self, t):
+        """the current stream of t's device, as the entries take it"""
         import torch
-        a = (tensor_view_io_args if views else tensor_io_args)(x, self.device, space=space, layout=layout)
-        return a, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def _flags(self, pad_crop, on_stream=False):
+        """RRV_TF_* of a call: the geometry, the handle's model, and for the tensor entries the caller's stream"""
+        return (_lib.TF_ON_STREAM if on_stream else 0) | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
+
+    def _source(self, x, space, layout, size, views=True, yuv=True):
+        """The input side of a tensor call, resolved once (_Source): x as transfer_tensor reads it — an ImageView, a YUV tensor with `layout` a
+        format name and size=(H, W) (where `yuv` is set: the entries that read YUV frames), or an image tensor in `layout` / `space`.  A strided
+        image tensor that fits a view stays where it is where `views` is set (the entries that take views); any other is copied to a packed one."""
+        if isinstance(x, ImageView):
+            _on_device(x.storage, "x.storage", self.device)
+            v = x.with_space(space, "x")
+            return _Source(v.desc, v, x.storage.data_ptr(), x.frames, x.H, x.W, True, x.storage, x.layout, v.frame_stride * _ELEM_BYTES[v.desc.dtype])
+        if yuv and layout in YUV_FORMATS:
+            _yuv_in_pixel_space(layout, space)
+            a = yuv_tensor_io_args(x, self.device, layout, size)
+            desc, view = _host_in_desc(layout), None
+        else:
+            a = _tensor_io(x, self.device, views, space=space, layout=layout)
+            desc, view = a.in_desc, a.in_view
+        step = view.frame_stride * _ELEM_BYTES[desc.dtype] if view is not None else a.x.stride(0) * a.x.element_size() if a.batched else 0
+        return _Source(desc, view, a.x.data_ptr(), a.B, a.H, a.W, a.batched, a.x, layout, step)
+
+    def _target(self, out, out_layout, out_space, out_dtype, B, Ho, Wo, batched, like, default_layout):
+        """The output side of a tensor call, resolved once (_Target): B frames of Ho x Wo — the size as delivered — into `out` (an ImageView, a
+        tensor or a window of one: written in place) or a fresh tensor on like's device, in out_layout (default: the view's, else
+        default_layout) / out_space / out_dtype."""
+        import torch
+        ov = out if isinstance(out, ImageView) else None
+        if out_layout is None:
+            out_layout = ov.layout if ov is not None else default_layout
+        _check_out_layout(out_layout, out_space)
+        if ov is not None:      # written in place, through the view
+            _on_device(ov.storage, "out.storage", self.device)
+            if out_layout != ov.layout:
+                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
+            if (ov.frames, ov.H, ov.W) != (B, Ho, Wo):
+                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, Ho, Wo, ov.frames, ov.H, ov.W))
+            view = ov.with_space(out_space, "out")
+            if self._lib.rrv_image_view_check(C.byref(view), B, Ho, Wo, 1) != 0:
+                raise ValueError("out: the planes and frames of an output view must not overlap")
+            return _Target(view.desc, view, ov.storage.data_ptr(), out, out_layout, view.frame_stride * _ELEM_BYTES[view.desc.dtype])
+        desc, shape, dtype, view = _tensor_out_args(self.device, B, Ho, Wo, batched, out_space, out_dtype, out_layout, True, out)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=like.device)
+        step = view.frame_stride * _ELEM_BYTES[desc.dtype] if view is not None else out.stride(0) * out.element_size() if batched else 0
+        return _Target(desc, view, out.data_ptr(), out, out_layout, step)
 
     def prepare_style_tensor(self, style, *, space="pixel", layout="nchw"):
         """prepare_style for style images already on the handle's GPU: one torch tensor [3,H,W] RGB (layout="nchw") or
@@ -808,28 +887,10 @@ class Stylization():
         conventions.  Read in the order of torch.cuda.current_stream(); complete when the call returns."""
         styles = style if isinstance(style, (list, tuple)) else [style]
         for sid, s in enumerate(styles):
-            a, stream = self._device_image(s, space, layout)
-            if a.batched:
+            src = self._source(s, space, layout, None, views=False, yuv=False)      # (the style entry reads packed images)
+            if src.batched:
                 raise ValueError("a style is one image: [3,H,W] or [H,W,3], got shape %s" % (tuple(s.shape),))
-            self._chk(self._lib.rrv_prepare_style_image_device(self._h, C.c_void_p(a.x.data_ptr()), a.in_desc, a.H, a.W, sid, stream))
-
-    def _source_view(self, x, space, layout, size):
-        """The input side of the scaled tensor calls: (rrv_image_view, base address, B, SH, SW, batched, the tensor that names the device,
-        layout name) of x as transfer_tensor reads it: an ImageView, a YUV tensor with size=(SH, SW), or an image tensor (a strided one
-        that fits a view stays where it is)."""
-        if isinstance(x, ImageView):
-            _on_device(x.storage, "x.storage", self.device)
-            return x.with_space(space, "x"), x.storage.data_ptr(), x.frames, x.H, x.W, True, x.storage, x.layout
-        if layout in YUV_FORMATS:
-            if space != "pixel":
-                raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
-            a = yuv_tensor_io_args(x, self.device, layout, size)
-            fmt = YUV_FORMATS[layout]
-            v = _contiguous_view(_lib.ImageDesc(_lib.DT_U8 if fmt.bits == 8 else _lib.DT_U16, fmt.layout, _lib.SP_PIXEL), a.H, a.W)
-        else:
-            a = tensor_view_io_args(x, self.device, space=space, layout=layout)
-            v = a.in_view if a.in_view is not None else _contiguous_view(a.in_desc, a.H, a.W)
-        return v, a.x.data_ptr(), a.B, a.H, a.W, a.batched, a.x, layout
+            self._chk(self._lib.rrv_prepare_style_image_device(self._h, C.c_void_p(src.ptr), src.desc, src.H, src.W, sid, self._stream(s)))
 
     def resample_tensor(self, x, work_size, *, space="pixel", layout="nchw", size=None):
         """The resampler alone (rrv_resample_view_device): x as transfer_tensor takes it — an image tensor in `layout` / `space`, a YUV
@@ -838,51 +899,31 @@ class Stylization():
         integers; transfer_tensor(y, layout="nhwc") on it is what transfer_tensor(x, work_size=) computes."""
         import torch
         H, W = _work_size(work_size)
-        v, ptr, B, SH, SW, batched, dev_t, lay = self._source_view(x, space, layout, size)
-        self._yuv_depth(lay, None)
-        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev_t.device)
-        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
-        step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
-        for b0 in range(0, B, TENSOR_BATCH_MAX):
-            nb = min(TENSOR_BATCH_MAX, B - b0)
-            self._chk(self._lib.rrv_resample_view_device(self._h, C.c_void_p(ptr + b0 * step), C.byref(v), nb, SH, SW, H, W,
-                                                         C.c_void_p(out[b0].data_ptr()), stream))
-        return out if batched else out[0]
+        src = self._source(x, space, layout, size)
+        self._yuv_depth(src.layout, None)
+        out = torch.empty((src.B, H, W, 3), dtype=torch.float32, device=src.tensor.device)
+        stream, v = self._stream(src.tensor), _whole_view(src, src.H, src.W)
+        for _, nb, p, q in _chunks(src.B, (src.ptr, src.step), (out.data_ptr(), out.stride(0) * 4)):
+            self._chk(self._lib.rrv_resample_view_device(self._h, p, C.byref(v), nb, src.H, src.W, H, W, q, stream))
+        return out if src.batched else out[0]
 
     def add_tensor(self, x, *, space="pixel", layout="nchw", size=None, work_size=None):
         """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch
         [B,3,H,W] / [B,H,W,3] whose images are added in order.  work_size=(H, W): each frame is resampled to that size on the GPU
         first (rrv_add_scaled_view_device), as transfer_tensor(work_size=) does; x may then also be a YUV tensor with size=(SH, SW)."""
         self._global_only("add")
-        if work_size is not None:
-            import torch
-            H, W = _work_size(work_size)
-            v, ptr, B, SH, SW, _, dev_t, lay = self._source_view(x, space, layout, size)
-            self._yuv_depth(lay, None)
-            stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
-            step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
-            for b in range(B):
-                self._chk(self._lib.rrv_add_scaled_view_device(self._h, C.c_void_p(ptr + b * step), C.byref(v), SH, SW, H, W, stream))
-            return
-        if isinstance(x, ImageView):      # a surface (any layout, the YUV ones included): each frame is compacted on the GPU
-            import torch
-            _on_device(x.storage, "x.storage", self.device)
-            v = x.with_space(space, "x")
-            self._yuv_depth(x.layout, None)
-            stream = C.c_void_p(torch.cuda.current_stream(x.storage.device).cuda_stream)
-            step = v.frame_stride * _ELEM_BYTES[v.desc.dtype]
-            for b in range(x.frames):
-                self._chk(self._lib.rrv_add_view_device(self._h, C.c_void_p(x.storage.data_ptr() + b * step), C.byref(v), x.H, x.W, stream))
-            return
-        a, stream = self._device_image(x, space, layout, views=True)
-        if a.in_view is not None:         # a crop or a pitched tensor: no copy on the torch side
-            step = a.in_view.frame_stride * _ELEM_BYTES[a.in_view.desc.dtype]
-            for b in range(a.B):
-                self._chk(self._lib.rrv_add_view_device(self._h, C.c_void_p(a.x.data_ptr() + b * step), C.byref(a.in_view), a.H, a.W, stream))
-            return
-        xb = a.x if a.batched else a.x.unsqueeze(0)
-        for b in range(a.B):
-            self._chk(self._lib.rrv_add_image_device(self._h, C.c_void_p(xb[b].data_ptr()), a.in_desc, a.H, a.W, stream))
+        work = None if work_size is None else _work_size(work_size)
+        src = self._source(x, space, layout, size, yuv=work is not None)
+        self._yuv_depth(src.layout, None)
+        stream = self._stream(src.tensor)
+        v = _whole_view(src, src.H, src.W) if work is not None else src.view
+        for _, _, p in _chunks(src.B, (src.ptr, src.step), chunk=1):      # a surface, a crop or a pitched tensor: each frame is compacted on the GPU
+            if work is not None:
+                self._chk(self._lib.rrv_add_scaled_view_device(self._h, p, C.byref(v), src.H, src.W, *work, stream))
+            elif v is not None:
+                self._chk(self._lib.rrv_add_view_device(self._h, p, C.byref(v), src.H, src.W, stream))
+            else:
+                self._chk(self._lib.rrv_add_image_device(self._h, p, src.desc, src.H, src.W, stream))
 
     def transfer(self, frame, style_weight=None, dtype=np.float32):
         """uint8 BGR HWC frame -> float32 BGR HWC in 0..255 (test/framework.py:106-118).
@@ -891,7 +932,7 @@ class Stylization():
         output rounded half to even and saturated, on the GPU): a quarter of the bytes."""
         a = _u8_image(frame, "frame")
         H, W = a.shape[:2]
-        out, u8 = _output((H // 8 * 8, W // 8 * 8, 3), dtype, None)     # the max pools floor the size, as in the reference
+        out, u8 = _output((*_stylized_size(H, W), 3), dtype, None)
         if not self.use_Global:
             fn = self._lib.rrv_transfer_frame_mode_u8 if u8 else self._lib.rrv_transfer_frame_mode
             self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p)))
@@ -927,7 +968,7 @@ class Stylization():
             raise RRVError("transfer_async() needs the global-feature-sharing model (use_Global=True)")
         a = _u8_image(frame, "frame")
         H, W = a.shape[:2]
-        out, u8 = _output((H // 8 * 8, W // 8 * 8, 3), dtype, out)
+        out, u8 = _output((*_stylized_size(H, W), 3), dtype, out)
         t = C.c_long(-1)
         fn = self._lib.rrv_transfer_async_u8 if u8 else self._lib.rrv_transfer_async
         self._chk(fn(self._h, a.ctypes.data_as(C.c_void_p), H, W, out.ctypes.data_as(C.c_void_p), C.byref(t)))
@@ -976,34 +1017,21 @@ class Stylization():
             a = _u8_frames(frames, "frame")
             H, W = a.shape[1:3]
         B = a.shape[0]
-        if out_size is not None:       # rrv_transfer_deliver: the stylized working frame leaves as DH x DW frames; SH = SW = 0: no input scaling
+        # Scaling: the frames as passed are SH x SW and H x W becomes the working size (SH = SW = 0: no input scaling); the stylized working
+        # frame leaves at its own size, or resampled to DH x DW.
+        SH = SW = 0
+        if out_size is not None:
             _no_styles_with_out_size(style_weights, style_masks)
             DH, DW = _out_size(out_size, (H, W))
-            SH = SW = 0
-            if work_size is not None:
-                (SH, SW), (H, W) = (H, W), _work_size(work_size)
-            out, u8 = _output((B, DH, DW, 3), dtype, out, out_format)
-            self._yuv_depth(in_format, out_format)
-            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
-            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
-            flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
-            self._chk(self._lib.rrv_transfer_deliver(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, SH, SW, H, W, DH, DW,
-                                                     out.ctypes.data_as(C.c_void_p), desc, flags))
-            return out
-        if work_size is not None:      # rrv_transfer_scaled: the frames as passed are SH x SW, everything from here on has the working size
+        elif work_size is not None:
             _no_styles_with_work_size(style_weights, style_masks)
+        if work_size is not None:
             (SH, SW), (H, W) = (H, W), _work_size(work_size)
-            out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out, out_format)
-            self._yuv_depth(in_format, out_format)
-            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
-            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
-            flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
-            self._chk(self._lib.rrv_transfer_scaled(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, SH, SW, H, W,
-                                                    out.ctypes.data_as(C.c_void_p), desc, flags))
-            return out
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        out, u8 = _output((B, H, W, 3) if pad_crop else (B, H // 8 * 8, W // 8 * 8, 3), dtype, out, out_format)
+        out, u8 = _output((B, *((DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)), 3), dtype, out, out_format)
         self._yuv_depth(in_format, out_format)
+        desc = _lib.ImageDesc(_lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32,
+                              YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
         if m is not None:
             blend, styles = _MASK, (m.host.ctypes.data_as(C.POINTER(C.c_float)), m.S, m.images)
         elif style_weights is not None:
@@ -1011,15 +1039,18 @@ class Stylization():
             blend, styles = _BLEND, (w.host.ctypes.data_as(C.POINTER(C.c_float)), w.S)
         else:
             blend, styles = _PLAIN, ()
+        # The C entry and its arguments: the scaled families take descriptors on both sides; the others go by (input is YUV, output is YUV) and
+        # what blends the styles (_HOST_ENTRIES), and the plain BGR entry also names the model and the geometry.
+        src, dst, flags = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), self._flags(pad_crop)
         name = _HOST_ENTRIES[yuv_in, yuv_out][blend].format(model="" if self.use_Global else "_frame_mode", geometry="_frames" if pad_crop else "_batch")
-        src, dst = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
-        flags = (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global or blend != _PLAIN else _lib.TF_FRAME_MODE)
-        if yuv_in:        # (h, in, in_layout, B, H, W, [weights, S | masks, S, images,] out, its descriptor, flags)
-            dt = _lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32
-            desc = _lib.ImageDesc(dt, YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+        if out_size is not None:
+            name, args = "rrv_transfer_deliver", (src, _host_in_desc(in_format), B, SH, SW, H, W, DH, DW, dst, desc, flags)
+        elif work_size is not None:
+            name, args = "rrv_transfer_scaled", (src, _host_in_desc(in_format), B, SH, SW, H, W, dst, desc, flags)
+        elif yuv_in:      # (h, in, in_layout, B, H, W, [weights, S | masks, S, images,] out, its descriptor, flags)
             args = (src, YUV_FORMATS[in_format].layout, B, H, W, *styles, dst, desc, flags)
         elif yuv_out:     # (h, in, B, H, W, flags | [weights, S | masks, S, images,] pad_crop, layout, out)
-            args = (src, B, H, W, *((flags,) if blend == _PLAIN else styles + (int(pad_crop),)), YUV_FORMATS[out_format].layout, dst)
+            args = (src, B, H, W, *((flags,) if blend == _PLAIN else styles + (int(pad_crop),)), desc.layout, dst)
         else:             # (h, in, B, H, W, [weights, S, pad_crop | masks, S, images, pad_crop,] out); the _u8 twin by the output's dtype
             name += "_u8" if u8 else ""
             args = (src, B, H, W, *(() if blend == _PLAIN else styles + (int(pad_crop),)), dst)
@@ -1129,139 +1160,63 @@ class Stylization():
         import torch
         if out_size is not None:
             _no_styles_with_out_size(style_weights, style_masks)
-            return self._transfer_tensor_scaled(x, None if work_size is None else _work_size(work_size), space, out_space, out_dtype, layout, out_layout,
-                                                pad_crop, out, size, out_size)
-        if work_size is not None:
+        elif work_size is not None:
             _no_styles_with_work_size(style_weights, style_masks)
-            return self._transfer_tensor_scaled(x, _work_size(work_size), space, out_space, out_dtype, layout, out_layout, pad_crop, out, size)
+        work = None if work_size is None else _work_size(work_size)
+        scaled = work is not None or out_size is not None
         xv, ov = (t if isinstance(t, ImageView) else None for t in (x, out))
-        if xv is not None:
-            layout, dev_t = xv.layout, xv.storage
-        yuv_in = layout in YUV_FORMATS
-        if yuv_in and space != "pixel":
-            raise ValueError("an %r input is in the 'pixel' space, not %r" % (layout, space))
-        if xv is not None:      # a surface: its frames are where the view says
-            _on_device(xv.storage, "x.storage", self.device)
-            B, H, W, batched, in_view = xv.frames, xv.H, xv.W, True, xv.with_space(space, "x")
-            in_desc, in_ptr = in_view.desc, xv.storage.data_ptr()
-            out_layout = (ov.layout if ov is not None else layout) if out_layout is None else out_layout
-            _check_out_layout(out_layout, out_space)
-            if ov is None:
-                out_desc, out_shape, out_dtype, out_view = _tensor_out_args(self.device, B, H, W, True, out_space, out_dtype, out_layout, pad_crop, out)
+        # An unscaled call refuses in tensor_io_args' order and words (tests/call_record.json pins which refusal a call meets): the space
+        # of a YUV surface first, and for a tensor x the names of both sides before x is looked at.
+        if not scaled:
+            if xv is not None and xv.layout in YUV_FORMATS:
+                _yuv_in_pixel_space(xv.layout, space)
+            if xv is None:
+                _check_in_names(space, layout, size)
+                _check_out_layout(out_layout if out_layout is not None else ov.layout if ov is not None else layout, out_space)
+        src = self._source(x, space, layout, size)
+        B, H, W, SH, SW = src.B, src.H, src.W, 0, 0
+        if out_size is not None:
+            DH, DW = _out_size(out_size, (H, W))
+        if work is not None:      # the frames as passed are SH x SW; everything from here on has the working size
+            (SH, SW), (H, W) = (H, W), work
+        Ho, Wo = (DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)
+        if not scaled and xv is None and ov is not None:      # (.. and the dtype of an output view for a tensor x, before the view is looked at)
+            _tensor_out_args(self.device, B, Ho, Wo, src.batched, out_space, ov.storage.dtype, ov.layout if out_layout is None else out_layout, True, None)
+        dst = self._target(out, out_layout, out_space, out_dtype, B, Ho, Wo, src.batched, src.tensor, default_layout=src.layout)
+        # The view entries serve a call with a strided side and every scaled call (a packed side then goes as its contiguous view), the
+        # descriptor entries every other: by (input is YUV), the _from_yuv_device entries taking the layout alone.
+        if scaled or src.view is not None or dst.view is not None:
+            vi, vo = _whole_view(src, src.H, src.W), _whole_view(dst, Ho, Wo)
+            in_arg, out_arg, names = C.byref(vi), C.byref(vo), _VIEW_ENTRIES
         else:
-            if ov is not None and out_layout is None:
-                out_layout = ov.layout
-            kw = dict(out_space=out_space, out_dtype=ov.storage.dtype if ov is not None else out_dtype, out_layout=out_layout, pad_crop=pad_crop,
-                      out=None if ov is not None else out)
-            a = yuv_tensor_io_args(x, self.device, layout, size, **kw) if yuv_in else tensor_view_io_args(x, self.device, space=space, layout=layout, **kw)
-            B, H, W, batched, in_view, dev_t = a.B, a.H, a.W, a.batched, a.in_view, a.x
-            in_desc, in_ptr = a.in_desc, a.x.data_ptr()
-            out_desc, out_shape, out_dtype, out_view = a.out_desc, a.out_shape, a.out_dtype, a.out_view
-            if yuv_in:
-                out_layout = layout if out_layout is None else out_layout
-        Ho, Wo = (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-        if ov is not None:      # written in place, through the view
-            _on_device(ov.storage, "out.storage", self.device)
-            if out_layout != ov.layout:
-                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
-            if (ov.frames, ov.H, ov.W) != (B, Ho, Wo):
-                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, Ho, Wo, ov.frames, ov.H, ov.W))
-            out_view = ov.with_space(out_space, "out")
-            if self._lib.rrv_image_view_check(C.byref(out_view), B, Ho, Wo, 1) != 0:
-                raise ValueError("out: the planes and frames of an output view must not overlap")
-            out_desc, out_ptr = out_view.desc, ov.storage.data_ptr()
-        else:
-            if out is None:
-                out = torch.empty(out_shape, dtype=out_dtype, device=dev_t.device)
-            out_ptr = out.data_ptr()
-        # The view entries serve a call with a strided side (the other side then goes as its contiguous view), the descriptor entries
-        # every other.  A batch above 64 steps its chunks by the frame stride in bytes: the view's, or a packed frame's.
-        strided = in_view is not None or out_view is not None
-        in_step = out_step = 0
-        if strided:
-            in_desc_s = in_desc if isinstance(in_desc, _lib.ImageDesc) else _lib.ImageDesc(
-                _lib.DT_U8 if YUV_FORMATS[layout].bits == 8 else _lib.DT_U16, in_desc, _lib.SP_PIXEL)
-            vi = in_view if in_view is not None else _contiguous_view(in_desc_s, H, W)
-            vo = out_view if out_view is not None else _contiguous_view(out_desc, Ho, Wo)
-            in_step, out_step = vi.frame_stride * _ELEM_BYTES[vi.desc.dtype], vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
-            in_arg, out_arg = C.byref(vi), C.byref(vo)
-        else:
-            in_arg, out_arg = in_desc, out_desc
-            if B > TENSOR_BATCH_MAX:      # both are contiguous tensors [B, ...]: a frame is a row of the batch
-                xb, ob = a.x if batched else a.x.unsqueeze(0), out if batched else out.unsqueeze(0)
-                in_step, out_step = xb.stride(0) * xb.element_size(), ob.stride(0) * ob.element_size()
-        plain_fn, blend_fn, mask_fn = (getattr(self._lib, name) for name in (_VIEW_ENTRIES if strided else _TENSOR_ENTRIES[yuv_in]))
+            yuv_in = src.layout in YUV_FORMATS
+            in_arg, out_arg, names = src.desc.layout if yuv_in else src.desc, dst.desc, _TENSOR_ENTRIES[yuv_in]
         w = m = None
         if style_masks is not None:
             m = style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global, tensors=True)
-            md = m.dev if m.dev is not None else torch.from_numpy(m.host).to(dev_t.device, non_blocking=False)
+            md = m.dev if m.dev is not None else torch.from_numpy(m.host).to(src.tensor.device, non_blocking=False)
             md = md if m.images == 1 else md.reshape(B, -1)
         if style_weights is not None:
             w = style_weight_args(style_weights, B, self.style_num, self.device, self.use_Global, tensors=True)
             wd = w.dev.unsqueeze(0).expand(B, w.S).contiguous() if w.broadcast else w.dev
-        flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
-        self._yuv_depth(layout, layout if out_layout is None else out_layout)
-        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
-        for b0 in range(0, B, TENSOR_BATCH_MAX):
-            nb = min(TENSOR_BATCH_MAX, B - b0)
-            src, dst = C.c_void_p(in_ptr + b0 * in_step), C.c_void_p(out_ptr + b0 * out_step)
-            if m is not None:
-                mp = md.data_ptr() if m.images == 1 else md[b0].data_ptr()
-                self._chk(mask_fn(self._h, src, in_arg, nb, H, W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb, dst, out_arg, flags, stream))
-                continue
-            if w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
-                wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
-                self._chk(blend_fn(self._h, src, in_arg, nb, H, W, C.c_void_p(wp), w.S, dst, out_arg,
-                                   flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
-                continue
-            self._chk(plain_fn(self._h, src, in_arg, nb, H, W, dst, out_arg, flags, stream))
-        return out
-
-    def _transfer_tensor_scaled(self, x, work, space, out_space, out_dtype, layout, out_layout, pad_crop, out, size, out_size=None):
-        """transfer_tensor(work_size=, out_size=): the source through its view, the output side worked out for the working size, or for the
-        delivered size of out_size (work None: no input scaling)"""
-        import torch
-        vi, in_ptr, B, SH, SW, batched, dev_t, layout = self._source_view(x, space, layout, size)
-        DH, DW = (0, 0) if out_size is None else _out_size(out_size, (SH, SW))
-        if work is None:
-            (H, W), (SH, SW) = (SH, SW), (0, 0)
-        else:
-            H, W = work
-        ov = out if isinstance(out, ImageView) else None
-        if out_layout is None:
-            out_layout = ov.layout if ov is not None else layout
-        _check_out_layout(out_layout, out_space)
-        Ho, Wo = (DH, DW) if out_size is not None else (H, W) if pad_crop else (H // 8 * 8, W // 8 * 8)
-        if ov is not None:      # written in place, through the view
-            _on_device(ov.storage, "out.storage", self.device)
-            if out_layout != ov.layout:
-                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
-            if (ov.frames, ov.H, ov.W) != (B, Ho, Wo):
-                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, Ho, Wo, ov.frames, ov.H, ov.W))
-            vo = ov.with_space(out_space, "out")
-            if self._lib.rrv_image_view_check(C.byref(vo), B, Ho, Wo, 1) != 0:
-                raise ValueError("out: the planes and frames of an output view must not overlap")
-            out_ptr = ov.storage.data_ptr()
-        else:
-            oh, ow, whole = (Ho, Wo, True) if out_size is not None else (H, W, pad_crop)      # (a delivered size is the output's size as it is)
-            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, oh, ow, batched, out_space, out_dtype, out_layout, whole, out)
-            if out is None:
-                out = torch.empty(out_shape, dtype=out_dtype, device=dev_t.device)
-            if vo is None:
-                vo = _contiguous_view(out_desc, Ho, Wo)
-            out_ptr = out.data_ptr()
-        in_step, out_step = vi.frame_stride * _ELEM_BYTES[vi.desc.dtype], vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
-        flags = _lib.TF_ON_STREAM | (_lib.TF_PAD_CROP if pad_crop else 0) | (0 if self.use_Global else _lib.TF_FRAME_MODE)
-        self._yuv_depth(layout, out_layout)
-        stream = C.c_void_p(torch.cuda.current_stream(dev_t.device).cuda_stream)
-        for b0 in range(0, B, TENSOR_BATCH_MAX):
-            nb = min(TENSOR_BATCH_MAX, B - b0)
-            src, dst = C.c_void_p(in_ptr + b0 * in_step), C.c_void_p(out_ptr + b0 * out_step)
+        flags = self._flags(pad_crop, on_stream=True)
+        self._yuv_depth(src.layout, dst.layout)
+        stream = self._stream(src.tensor)
+        for b0, nb, p, q in _chunks(B, (src.ptr, src.step), (dst.ptr, dst.step)):
             if out_size is not None:
-                self._chk(self._lib.rrv_transfer_deliver_view_device(self._h, src, C.byref(vi), nb, SH, SW, H, W, DH, DW, dst, C.byref(vo), flags, stream))
+                self._chk(self._lib.rrv_transfer_deliver_view_device(self._h, p, in_arg, nb, SH, SW, H, W, DH, DW, q, out_arg, flags, stream))
+            elif work is not None:
+                self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, p, in_arg, nb, SH, SW, H, W, q, out_arg, flags, stream))
+            elif m is not None:
+                mp = md.data_ptr() if m.images == 1 else md[b0].data_ptr()
+                self._chk(getattr(self._lib, names[_MASK])(self._h, p, in_arg, nb, H, W, C.c_void_p(mp), m.S, 1 if m.images == 1 else nb, q, out_arg, flags, stream))
+            elif w is not None:       # the chunk's rows of the weights, by address: host memory, or HBM with TF_WEIGHTS_DEVICE
+                wp = wd[b0].data_ptr() if wd is not None else w.host[b0].ctypes.data
+                self._chk(getattr(self._lib, names[_BLEND])(self._h, p, in_arg, nb, H, W, C.c_void_p(wp), w.S, q, out_arg,
+                                                            flags | (_lib.TF_WEIGHTS_DEVICE if wd is not None else 0), stream))
             else:
-                self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, src, C.byref(vi), nb, SH, SW, H, W, dst, C.byref(vo), flags, stream))
-        return out
+                self._chk(getattr(self._lib, names[_PLAIN])(self._h, p, in_arg, nb, H, W, q, out_arg, flags, stream))
+        return dst.result
 
     def deliver_tensor(self, y, out_size, *, out_space="pixel", out_dtype=None, out_layout=None, out=None):
         """The delivery stage alone (rrv_deliver_view_device): y a float32 tensor [B,H,W,3] ([H,W,3]) on the handle's GPU, BGR, "pixel"
@@ -1276,35 +1231,13 @@ class Stylization():
         yb = (y if batched else y.unsqueeze(0)).contiguous()
         B, H, W = yb.shape[:3]
         DH, DW = _out_size(out_size, (H, W))
-        ov = out if isinstance(out, ImageView) else None
-        if out_layout is None:
-            out_layout = ov.layout if ov is not None else "nhwc"
-        _check_out_layout(out_layout, out_space)
-        if ov is not None:
-            _on_device(ov.storage, "out.storage", self.device)
-            if out_layout != ov.layout:
-                raise ValueError("out is an %r view, out_layout says %r" % (ov.layout, out_layout))
-            if (ov.frames, ov.H, ov.W) != (B, DH, DW):
-                raise ValueError("out must hold %d frames of %d x %d, got %d of %d x %d" % (B, DH, DW, ov.frames, ov.H, ov.W))
-            vo = ov.with_space(out_space, "out")
-            if self._lib.rrv_image_view_check(C.byref(vo), B, DH, DW, 1) != 0:
-                raise ValueError("out: the planes and frames of an output view must not overlap")
-            out_ptr = ov.storage.data_ptr()
-        else:
-            out_desc, out_shape, out_dtype, vo = _tensor_out_args(self.device, B, DH, DW, batched, out_space, out_dtype, out_layout, True, out)
-            if out is None:
-                out = torch.empty(out_shape, dtype=out_dtype, device=y.device)
-            if vo is None:
-                vo = _contiguous_view(out_desc, DH, DW)
-            out_ptr = out.data_ptr()
-        out_step = vo.frame_stride * _ELEM_BYTES[vo.desc.dtype]
-        self._yuv_depth(None, out_layout)
-        stream = C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
-        for b0 in range(0, B, TENSOR_BATCH_MAX):
-            nb = min(TENSOR_BATCH_MAX, B - b0)
-            self._chk(self._lib.rrv_deliver_view_device(self._h, C.c_void_p(yb[b0].data_ptr()), nb, H, W, DH, DW, C.c_void_p(out_ptr + b0 * out_step),
-                                                        C.byref(vo), stream))
-        return out
+        dst = self._target(out, out_layout, out_space, out_dtype, B, DH, DW, batched, y, default_layout="nhwc")
+        vo = _whole_view(dst, DH, DW)
+        self._yuv_depth(None, dst.layout)
+        stream = self._stream(y)
+        for _, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (dst.ptr, dst.step)):
+            self._chk(self._lib.rrv_deliver_view_device(self._h, p, nb, H, W, DH, DW, q, C.byref(vo), stream))
+        return dst.result
 
     def sync(self):
         self._chk(self._lib.rrv_sync(self._h))
@@ -1527,8 +1460,7 @@ class MultiStyleStylization(Stylization):
 
     def transfer(self, cur_feature, style_weight=[1.], out=None, dtype=np.float32):
         """`out` / `dtype`: float32 (default) or uint8 output, as Stylization.transfer_batch."""
-        H, W = cur_feature.shape[0] // 8 * 8, cur_feature.shape[1] // 8 * 8
-        out, u8 = _output((H, W, 3), dtype, out)
+        out, u8 = _output((*_stylized_size(*cur_feature.shape[:2]), 3), dtype, out)
         w = (C.c_float * len(style_weight))(*[float(v) for v in style_weight])
         fn = self._entry("rrv_transfer_features", u8)
         self._chk(fn(self._h, cur_feature.id, w, len(style_weight), out.ctypes.data_as(C.c_void_p)))
@@ -1538,9 +1470,8 @@ class MultiStyleStylization(Stylization):
         """`transfer` for a run of cached features, one weight vector each, pipelined inside the library
         (rrv_transfer_features_batch).  Returns / fills a float32 (or, by `out` / `dtype`, uint8) [n][H][W][3] array."""
         n = len(features)
-        H, W = features[0].shape[0] // 8 * 8, features[0].shape[1] // 8 * 8
         ns = len(style_weights[0])
-        out, u8 = _output((n, H, W, 3), dtype, out)
+        out, u8 = _output((n, *_stylized_size(*features[0].shape[:2]), 3), dtype, out)
         ids = (C.c_int * n)(*[f.id for f in features])
         w = (C.c_float * (n * ns))(*[float(v) for row in style_weights for v in row])
         self._chk(self._entry("rrv_transfer_features_batch", u8)(self._h, ids, w, n, ns, out.ctypes.data_as(C.c_void_p)))

@@ -203,8 +203,8 @@ class _Recorder:
         return entry
 
 
-def test_style_entry_still_gets_packed_images():
-    """prepare_style has no view form: its argument path (tensor_io_args, what _device_image uses unless asked for views) copies a
+def test_style_entry_still_gets_packed_images(monkeypatch):
+    """prepare_style has no view form: its argument path (tensor_io_args, what the input resolver uses unless asked for views) copies a
     crop and an expanded grey image to packed tensors, as it always did, and prepare_style_tensor hands the packed tensor's address and
     the plain descriptor to rrv_prepare_style_image_device."""
     style = torch.arange(3 * 210 * 310, dtype=torch.float32).reshape(3, 210, 310)
@@ -219,11 +219,13 @@ def test_style_entry_still_gets_packed_images():
     s.device, s._lib, s._h = 0, _Recorder(), None
     s._chk = lambda rc: None
     seen = []
-    s._device_image = lambda x, space, layout, views=False: (seen.append(views), ((F.tensor_view_io_args if views else F.tensor_io_args)(_OnGpu(x), 0, space=space, layout=layout), None))[1]
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: type("Stream", (), {"cuda_stream": 0})())
+    s._source = lambda x, space, layout, size, views=True, yuv=True: (seen.append(views), F.Stylization._source(s, _OnGpu(x), space, layout, size, views, yuv))[1]
     s.prepare_style_tensor(crop)
     (name, args), = s._lib.calls
     assert seen == [False] and name == "rrv_prepare_style_image_device"
     assert isinstance(args[2], L.ImageDesc) and (args[3], args[4]) == (190, 295)
+    assert args[1].value not in range(style.data_ptr(), style.data_ptr() + style.numel() * 4)      # the packed copy's address, not the crop's
 
 
 def test_image_view_bounds(pkg, lib):
