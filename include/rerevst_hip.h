@@ -683,6 +683,54 @@ int rrv_transfer_deliver_view_device(rrv_handle h, const void* d_in, const rrv_i
 int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W,
                          int DH, int DW, void* out, rrv_image_desc out_desc, int flags);
 
+/* Guided delivery: the stylized working frame upsampled to the delivered size along the SOURCE's edges, on the GPU, in place of the half-pixel
+ * bilinear resampling of "Output size".  Joint upsampling with the fast guided filter (He & Sun, "Fast Guided Filter", 2015; He, Sun & Tang,
+ * "Guided Image Filtering", 2013): a local linear model stylized = a * luma + b is fitted at the working size, the smooth coefficients are
+ * upsampled instead of the picture, and they are applied to the luma of the full-resolution source.  The network still runs at the working size.
+ * Inputs, per frame, all float32 HWC BGR PIXEL: the stylized working frame P [OH][OW][3] (what the float32 PIXEL call delivers), the source at the
+ * working size X_lo [OH][OW][3] and at the delivered size X_hi [DH][DW][3].
+ * Parameters: the radius r in working pixels, 1..16, and eps > 0 in the units of a 0..1 image; internally e = eps * 65025.
+ * Arithmetic.
+ *   guide         g = (0.114f B + 0.587f G) + 0.299f R of a float32 PIXEL value, each operation rounded to float32: g_lo from X_lo, g_hi from X_hi
+ *   box mean      M_r(f)(y, x): the mean of f over the window [y - r, y + r] x [x - r, x + r] clipped to the frame, divided by the number of
+ *                 pixels actually inside it
+ *   coefficients  per channel c, at the working size:
+ *                   a_c = (M_r(g_lo P_c) - M_r(g_lo) M_r(P_c)) / (M_r(g_lo^2) - M_r(g_lo)^2 + e)
+ *                   b_c = M_r(P_c) - a_c M_r(g_lo)
+ *                   A_c = M_r(a_c), B_c = M_r(b_c)
+ *   upsample      A_c and B_c resampled OH x OW -> DH x DW with the rrv_resample_taps tables of (OH -> DH) and (OW -> DW) in the delivery stage's
+ *                 separable order: along rows first, then along columns, taps ascending
+ *   apply         Q_c = up(A_c) g_hi + up(B_c), not clamped: Q is a float32 HWC BGR PIXEL frame of DH x DW
+ * Q then reaches the output form asked for through the delivery stage at equal size, which is the identity on values ("Output size": for
+ * DH == OH, DW == OW the resampled value is the input's): uint8, planar RGB, the three value spaces and every YUV layout, depth and chroma
+ * format are, word for word, those of "Output size" applied to v = Q.
+ * Per axis DH >= OH and DH / OH <= 8 (else RRV_E_ARG naming the field).  Equal size is allowed: the stage is then an edge-aware smoothing.
+ * This stage is bit-exact to nothing: the moments are float32 sums (of values offset by a per-tile anchor, which leaves covariance and variance
+ * what they are and keeps their cancellation small where the picture is smooth), and the tests hold it to a float64 restatement of the
+ * arithmetic above.  Frame b's result does not depend on B.
+ *   rrv_deliver_guided_view_device   the stage alone: B (1..64) frames d_P, d_guide_lo (both [H][W][3]) and d_guide_hi ([DH][DW][3]), contiguous
+ *                                    float32 BGR PIXEL, -> DH x DW frames through `out`, queued on hip_stream (NULL: the null stream); nothing of
+ *                                    the handle's own streams takes part.  Its coefficient planes and Q live in the handle: calls on different
+ *                                    streams must be ordered by the caller
+ *   rrv_transfer_guided_view_device  rrv_transfer_deliver_view_device with r and eps: the guide is the call's own source frames, X_hi the source
+ *                                    through the input resampler at equal size (the first kernel's float32 PIXEL value of each source pixel, bit
+ *                                    for bit) and X_lo the resampled working input of a scaled call (X_hi itself without input scaling).  Needs
+ *                                    DH x DW == SH x SW, or SH = SW = 0 and DH x DW == H x W; and a delivered working frame of H x W:
+ *                                    RRV_TF_PAD_CROP, or H and W multiples of 8.  Anything else is RRV_E_ARG
+ *   rrv_transfer_guided              the host twin through the host pipeline; sub-batches by the sizing rules of rrv_transfer_deliver
+ * A guided call equals, bit for bit in a fixed kernel mode, the float32 HWC BGR PIXEL call at the working size, the resampler alone for the
+ * two guides, and rrv_deliver_guided_view_device into the form asked for.  r and eps travel with the call, never in the handle.
+ * Checks, all before any GPU work, as "Output size"; RRV_E_ARG names the field and the handle stays usable.  Per workspace slot the stage
+ * keeps three more grow-only float32 buffers (X_hi and Q: 12 bytes per delivered pixel and frame each; the coefficient planes: 24 bytes per
+ * working pixel and frame), reserved with the tables before the call's first launch: out of memory is RRV_E_NOMEM and the handle stays usable.
+ * Not offered: blended and masked guided delivery, tickets and the one-frame entries. */
+int rrv_deliver_guided_view_device(rrv_handle h, const float* d_P, const float* d_guide_lo, const float* d_guide_hi, int B, int H, int W,
+                                   int DH, int DW, int r, float eps, void* d_out, const rrv_image_view* out, void* hip_stream);
+int rrv_transfer_guided_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W,
+                                    int DH, int DW, int r, float eps, void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_guided(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W,
+                        int DH, int DW, int r, float eps, void* out, rrv_image_desc out_desc, int flags);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

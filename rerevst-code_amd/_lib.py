@@ -9,8 +9,8 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
-# reach the main library only).  It finds librerevst_scale.so and librerevst_deliver.so next to ITSELF (rpath $ORIGIN): a library in another
-# directory needs copies of both there.
+# reach the main library only).  It finds librerevst_scale.so, librerevst_deliver.so and librerevst_guided.so next to ITSELF (rpath $ORIGIN): a library
+# in another directory needs copies of the three there.
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -152,6 +152,13 @@ SYMBOLS = {
                                                    C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),
     "rrv_transfer_deliver": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, ImageDesc,
                                        C.c_int]),
+    # guided delivery: (..., H, W, DH, DW, r, eps, out, ...): the working frame reaches DH x DW along the edges of the source's luma
+    "rrv_deliver_guided_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_float, C.c_void_p, C.POINTER(ImageView), C.c_void_p]),
+    "rrv_transfer_guided_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_float, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),
+    "rrv_transfer_guided": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_void_p, ImageDesc, C.c_int]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

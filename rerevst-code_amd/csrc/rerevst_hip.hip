@@ -27,6 +27,7 @@
 #include "prep_kernels.h"
 #include "mask_kernels.h"
 #include "resample.h"      // librerevst_scale.so: parameters and the launch entry of the resampler
+#include "guided.h"        // librerevst_guided.so: the guided delivery stage
 #include "deliver.h"       // librerevst_deliver.so: the same of the output-side resampler
 
 namespace {
@@ -199,6 +200,10 @@ struct rrv_ctx {
         float* rs_buf = nullptr; size_t rs_cap = 0;
         // A delivered size (Xfer::DH): a launch group's stylized working frames, float32 BGR PIXEL, grow-only, between conv_last_k and deliver_k
         float* dl_buf = nullptr; size_t dl_cap = 0;
+        // Guided delivery (Xfer::gr): a launch group's source at the delivered size, coefficient planes and result (X_hi, [6][H][W], Q), grow-only
+        float* gd_xhi = nullptr; size_t gd_xhi_cap = 0;
+        float* gd_ab = nullptr; size_t gd_ab_cap = 0;
+        float* gd_q = nullptr; size_t gd_q_cap = 0;
         int set_images = 0;                          // images whose state sets the slot's last launch wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
     } slots[RRV_MAX_SLOTS];
     int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots slots
@@ -255,6 +260,9 @@ struct rrv_ctx {
     // The scaled entries (Xfer::SH): the tap tables of every (source, destination) axis pair seen so far, in HBM (rs_tables; Slot::rs_buf holds the frames)
     struct RsTab { void* block = nullptr; RsAxis axis{}; int span = 0; };      // span: source samples the taps of RS_TH consecutive outputs cover, at most
     std::map<std::pair<int, int>, RsTab> rs_tabs;
+    // rrv_deliver_guided_view_device's own coefficient planes and result (it runs on the caller's stream, beside whatever the slots hold in flight)
+    float* gd_ab = nullptr; size_t gd_ab_cap = 0;
+    float* gd_q = nullptr; size_t gd_q_cap = 0;
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -1183,6 +1191,9 @@ struct Xfer {
     // A delivered size: the stylized working frame (WH x WW below) is resampled to DH x DW behind the last kernel (run_xfer), and `fmt`, `vout`
     // and everything sized by the output describe DH x DW frames.  0, or equal to the working frame: the working frame is delivered.
     int DH = 0, DW = 0;
+    // Guided delivery (include/rerevst_hip.h "Guided delivery"): radius in working pixels (0: plain delivery) and eps of a 0..1 image.  The stylized
+    // working frame then reaches DH x DW through gf_coeff_k / gf_apply_k with the call's own source frames as the guide, equal sizes included.
+    int gr = 0; float geps = 0.f;
     // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
     bool on_stream = false; hipStream_t with = nullptr;
 
@@ -1192,6 +1203,8 @@ struct Xfer {
     int WH() const { return pad ? H : H / 8 * 8; }            // the stylized working frame: what the last kernel delivers
     int WW() const { return pad ? W : W / 8 * 8; }
     bool delivering() const { return (DH != 0 || DW != 0) && (DH != WH() || DW != WW()); }
+    bool guided() const { return gr != 0; }
+    bool staged() const { return delivering() || guided(); }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
     int OH() const { return delivering() ? DH : WH(); }       // the frame delivered
     int OW() const { return delivering() ? DW : WW(); }
     ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
@@ -2161,6 +2174,9 @@ int rrv_destroy(rrv_handle h) {
     if (h->pend_u8) (void)hipFree(h->pend_u8);
     for (rrv_ctx::Slot& sl : h->slots) if (sl.rs_buf) (void)hipFree(sl.rs_buf);
     for (rrv_ctx::Slot& sl : h->slots) if (sl.dl_buf) (void)hipFree(sl.dl_buf);
+    for (rrv_ctx::Slot& sl : h->slots)
+        for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
+    for (float* q : {h->gd_ab, h->gd_q}) if (q) (void)hipFree(q);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
@@ -2928,6 +2944,52 @@ static int deliver_launch(rrv_handle h, const Seq& q, const float* d_in, int B, 
     return RRV_OK;
 }
 
+// ---- guided delivery (include/rerevst_hip.h "Guided delivery"): the stylized working frame upsampled along the source's edges
+// H x W: the stylized working frame.  Radius, eps and the sizes, judged before any GPU work.
+static int check_guided(rrv_handle h, const char* who, int H, int W, int DH, int DW, int r, float eps) {
+    if (r < 1 || r > GF_R_MAX) return fail(h, RRV_E_ARG, std::string(who) + ": r must be in 1..16");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(h, RRV_E_ARG, std::string(who) + ": eps must be a positive number");
+    if (H < 1 || W < 1) return fail(h, RRV_E_ARG, std::string(who) + ": the working frame must be at least 1 x 1 pixels");
+    if (DH < H || (int64_t)DH > 8 * (int64_t)H) return fail(h, RRV_E_ARG, std::string(who) + ": DH / the working frame's height must be within 1 .. 8");
+    if (DW < W || (int64_t)DW > 8 * (int64_t)W) return fail(h, RRV_E_ARG, std::string(who) + ": DW / the working frame's width must be within 1 .. 8");
+    return RRV_OK;
+}
+// the tables the stage and the equal-size passes around it read: (H, W) -> (DH, DW), and the identity of the delivered size
+static int gd_tables(rrv_handle h, int H, int W, int DH, int DW) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    return rs_pair(h, DH, DW, DH, DW, &ty, &tx);
+}
+// everything a guided request allocates, before its first launch: the tables and room for `frames` frames in the slot's three buffers
+static int gd_reserve(rrv_handle h, int slot, int frames, int H, int W, int DH, int DW) {
+    RCHK(gd_tables(h, H, W, DH, DW));
+    rrv_ctx::Slot& sl = h->slots[slot];
+    RCHK(ensure_dev(h, sl.dl_buf, sl.dl_cap, (size_t)frames * H * W * 3));
+    RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * DH * DW * 3));
+    RCHK(ensure_dev(h, sl.gd_ab, sl.gd_ab_cap, (size_t)frames * H * W * 6));
+    return ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * DH * DW * 3);
+}
+// B frames: P, x_lo [H][W][3] and x_hi [DH][DW][3] -> q [DH][DW][3], all contiguous float32 BGR PIXEL, through the planes `ab` ([B][6][H][W]);
+// queued on q.stream.  The tables exist already or are built here.
+static int guided_launch(rrv_handle h, const Seq& q, const float* P, const float* x_lo, const float* x_hi, int B, int H, int W, int DH, int DW, int r,
+                         float eps, float* ab, float* out) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    GuidedP p{};
+    p.P = P; p.xlo = x_lo; p.xhi = x_hi; p.ab = ab; p.q = out;
+    p.H = H; p.W = W; p.B = B; p.DH = DH; p.DW = DW; p.r = r; p.e = eps * 65025.0f;
+    p.ay = ty->axis; p.ax = tx->axis;
+    if (!guided_tile(&p)) return fail(h, RRV_E_ARG, "guided: no tile of the apply kernel fits the LDS");      // (cannot happen within the radius limit)
+    int e = 0;
+    // for the profile log: bytes from the shapes (P, X_lo read, the planes written and read with their halo counted once, X_hi read, Q written);
+    // operations two per window term, moment and pass, and two per tap and plane
+    const double win = 2.0 * r + 1.0;
+    RCHK(launch(h, q, "guided", (2.0 * 2 * 8 * win * H * W + 2.0 * 2 * 6 * win * H * W + 2.0 * 6 * 4 * DH * DW) * B,
+                ((12.0 + 12.0 + 24.0 + 24.0) * H * W + 24.0 * DH * DW) * B, [&] { e = rrv_guided_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("guided: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+
 // The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
 // burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
 static int next_device_slot(rrv_handle h) {
@@ -2945,6 +3007,12 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false, bool state
     RCHK(check_frame(h, x.KH(), x.KW(), "transfer"));      // the geometry the kernels run, refused before any staging is sized for it
     if (x.scaled()) RCHK(check_scale(h, "transfer", x.SH, x.SW, x.H, x.W));
     if (x.DH != 0 || x.DW != 0) RCHK(check_deliver(h, "transfer", x.WH(), x.WW(), x.DH, x.DW));
+    if (x.guided()) {      // the guide is the call's own source: it has the delivered size, and the frame the model delivers the working size
+        RCHK(check_guided(h, "transfer_guided", x.WH(), x.WW(), x.DH, x.DW, x.gr, x.geps));
+        if (x.model != Model::GLOBAL && x.model != Model::FRAME) return fail(h, RRV_E_ARG, "transfer_guided: blended and masked guided delivery are not offered");
+        if (x.DH != x.IH() || x.DW != x.IW()) return fail(h, RRV_E_ARG, "transfer_guided: DH x DW must be the size of the frames as passed (SH x SW; H x W with SH = SW = 0)");
+        if (x.WH() != x.H || x.WW() != x.W) return fail(h, RRV_E_ARG, "transfer_guided: H and W must be multiples of 8 without RRV_TF_PAD_CROP (the stylized working frame is then H x W)");
+    }
     if ((blend || mask) && (x.ns < 1 || x.ns > RRV_MAX_STYLES)) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
     if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
     if (mask && !x.mask) return fail(h, RRV_E_ARG, "transfer: null mask");
@@ -2989,13 +3057,17 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const bool scaled = x.scaled();
     // A delivering request runs each launch group's model into the slot's buffer of working frames (float32 HWC BGR PIXEL) and the delivery
     // stage from there to the caller's frames, on the same sequence; the bracket covers it, so the caller's stream waits for deliver_k.
-    const bool delivering = x.delivering();
+    // A guided request does the same and then runs the source through the resampler at its own size (X_hi), the guided stage from the
+    // working frames, the working-size source (the scaled request's resampled frames, else X_hi itself) and X_hi to Q, and the delivery
+    // stage at equal size from Q to the caller's frames.
+    const bool delivering = x.delivering(), guided = x.guided(), staged = x.staged();
     const int group_frames = x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX);
     if (scaled) RCHK(rs_reserve(h, slot, group_frames, x.SH, x.SW, x.H, x.W));
-    if (delivering) RCHK(dl_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
+    if (guided) RCHK(gd_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
+    else if (delivering) RCHK(dl_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
     rrv_ctx::Slot& sl = h->slots[slot];
     const CallerOrder caller = x.order(h);
-    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || delivering);
+    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || staged);
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, caller.stream));
         HIPCHK(hipStreamWaitEvent(sl.stream, sl.ev, 0));
@@ -3006,13 +3078,14 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const PadCrop crop = x.pad_crop();
     const ImgView vw = contiguous_view(VL_HWC, x.H, x.W);      // a scaled request's working frames: float32 HWC BGR PIXEL in the slot's buffer
     const ImgView vd = contiguous_view(VL_HWC, x.WH(), x.WW());    // a delivering request's stylized working frames, the same form in the slot's other buffer
-    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, delivering ? OUT_F32 : x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi,
-                     delivering ? &vd : &vo, caller};
+    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, staged ? OUT_F32 : x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi,
+                     staged ? &vd : &vo, caller};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* in = (const uint8_t*)d_in + (size_t)b0 * fb;
         void* const dst = (char*)d_out + (size_t)b0 * fo;      // the group's frames as the caller gets them
-        void* const out = delivering ? (void*)sl.dl_buf : dst;
+        void* const out = staged ? (void*)sl.dl_buf : dst;
+        const uint8_t* const src = in;                         // the group's frames as the caller passed them
         // the group's sequence: GLOBAL and MASK read no set of the slot's own, FRAME writes and BLEND blends into them (image g: set g of the slot's);
         // GLOBAL and BLEND are the per-frame path (transfer_device), where F(4x4,3x3) may run
         Seq q = slot_seq(h, slot, x.model == Model::FRAME || x.model == Model::BLEND);
@@ -3039,7 +3112,13 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             sl.set_images = cnt;
             break;
         }
-        if (delivering) RCHK(deliver_launch(h, q, sl.dl_buf, cnt, x.WH(), x.WW(), x.DH, x.DW, dst, x.fmt, vo));
+        if (guided) {
+            RCHK(resample_launch(h, q, src, x.in, vi, cnt, x.DH, x.DW, x.DH, x.DW, sl.gd_xhi));
+            RCHK(guided_launch(h, q, sl.dl_buf, scaled ? sl.rs_buf : sl.gd_xhi, sl.gd_xhi, cnt, x.WH(), x.WW(), x.DH, x.DW, x.gr, x.geps, sl.gd_ab, sl.gd_q));
+            RCHK(deliver_launch(h, q, sl.gd_q, cnt, x.DH, x.DW, x.DH, x.DW, dst, x.fmt, vo));
+        } else if (delivering) {
+            RCHK(deliver_launch(h, q, sl.dl_buf, cnt, x.WH(), x.WW(), x.DH, x.DW, dst, x.fmt, vo));
+        }
     }
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, sl.stream));
@@ -3372,7 +3451,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // the page-locked and device staging per set stays within four times the unscaled call's.
     if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
     // the same rule for the DELIVERED frame, which sizes the output staging
-    if (x.delivering()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.DH * x.DW)));
+    if (x.staged()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.DH * x.DW)));
     const size_t mfl = x.mask_floats();
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
@@ -3397,13 +3476,15 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // profiled step (slot 0 only), the debug levels, a caller's stream, zero copy.
     // A delivering request too: the piecewise drain hooks into transfer_device's last launch, which is then not the request's last kernel.
     const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !x.order(h).sync && h->host_io == 0 &&
-                         (x.model == Model::GLOBAL || x.model == Model::BLEND) && !x.delivering();
+                         (x.model == Model::GLOBAL || x.model == Model::BLEND) && !x.staged();
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
     if (x.scaled())      // a scaled request: the tables and each compute slot's buffer of working frames, before the first launch
         for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(rs_reserve(h, slot_of(k), sub, x.SH, x.SW, x.H, x.W));      // (slot_of has period 2)
-    if (x.delivering())      // a delivering request: the same for the stylized working frames
+    if (x.guided())          // a guided request: the stylized working frames and the guided stage's three buffers
+        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(gd_reserve(h, slot_of(k), sub, x.WH(), x.WW(), x.DH, x.DW));
+    else if (x.delivering())      // a delivering request: the same for the stylized working frames
         for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(dl_reserve(h, slot_of(k), sub, x.WH(), x.WW(), x.DH, x.DW));
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
@@ -3672,6 +3753,37 @@ int rrv_transfer_deliver_view_device(rrv_handle h, const void* d_in, const rrv_i
                                      void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
     return scaled_view_run(h, "transfer_deliver_view", false, d_in, in, B, SH, SW, H, W, DH, DW, d_out, out, flags, hip_stream);
 }
+// ---- the guided entries (include/rerevst_hip.h "Guided delivery")
+// the stage alone and the equal-size delivery behind it, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own
+// streams takes part.  The coefficient planes and Q live in two buffers of the handle that only this entry uses.
+int rrv_deliver_guided_view_device(rrv_handle h, const float* d_P, const float* d_guide_lo, const float* d_guide_hi, int B, int H, int W, int DH, int DW, int r,
+                                   float eps, void* d_out, const rrv_image_view* out, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!out) return fail(h, RRV_E_ARG, "deliver_guided_view: null view");
+    OutFmt fmt;
+    if (!view_desc_ok(out->desc) || parse_out(out->desc, &fmt) != DescErr::OK)
+        return fail(h, RRV_E_ARG, "deliver_guided_view: out.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_P || !d_guide_lo || !d_guide_hi || !d_out) return fail(h, RRV_E_ARG, "deliver_guided_view: null buffer");
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "deliver_guided_view: batch must be in 1..64");
+    RCHK(check_guided(h, "deliver_guided_view", H, W, DH, DW, r, eps));
+    std::string why;
+    if (!view_check(*out, B, DH, DW, true, &why)) return fail(h, RRV_E_ARG, "deliver_guided_view: out." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(gd_tables(h, H, W, DH, DW));
+    RCHK(ensure_dev(h, h->gd_ab, h->gd_ab_cap, (size_t)B * H * W * 6));
+    RCHK(ensure_dev(h, h->gd_q, h->gd_q_cap, (size_t)B * DH * DW * 3));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    RCHK(guided_launch(h, q, d_P, d_guide_lo, d_guide_hi, B, H, W, DH, DW, r, eps, h->gd_ab, h->gd_q));
+    return deliver_launch(h, q, h->gd_q, B, DH, DW, DH, DW, d_out, fmt, img_view(*out));
+}
+int rrv_transfer_guided_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, int DH, int DW, int r,
+                                    float eps, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    x.gr = r ? r : -1; x.geps = eps;      // (r = 0 is refused as a radius, not taken for a plain delivery)
+    return view_run(h, "transfer_guided_view", d_in, in, d_out, out, flags, hip_stream, x);
+}
 // a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
     if (yuv_layout(d.layout)) return parse_in_view(d, in);
@@ -3697,6 +3809,13 @@ int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, in
     Xfer x{Model::GLOBAL, B, H, W};
     x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
     return scaled_host(h, "transfer_deliver", false, frames, in, out, od, flags, x);
+}
+int rrv_transfer_guided(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, int r, float eps, void* out,
+                        rrv_image_desc od, int flags) {
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    x.gr = r ? r : -1; x.geps = eps;
+    return scaled_host(h, "transfer_guided", false, frames, in, out, od, flags, x);
 }
 // a sampled frame of SH x SW, resampled into slot 0's buffer on the handle's stream and added as the float32 PIXEL frame it then is.
 // device: d_frame is in HBM, complete once `stream` has run what it holds now; else host memory in the contiguous form of `fmt`

@@ -423,7 +423,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420", work_size=None, out_size=None):
+                  chroma="420", work_size=None, out_size=None, guided=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -442,7 +442,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     work_size=(H, W): every frame, the sampled ones included, is resampled to that working size on the GPU (add / transfer_frames with
     work_size=); the frames and the video written have the working size.  Needs a model with transfer_frames(work_size=).
     out_size=(H, W) or "source": the stylized working frame is resampled to that size on the GPU on its way out (transfer_frames with
-    out_size=; "source": each frame's own size); the frames and the video written have that size."""
+    out_size=; "source": each frame's own size); the frames and the video written have that size.
+    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source"), the upscale follows the source's edges."""
     import importlib
     import time
     from collections import deque
@@ -467,6 +468,10 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     deliver = None if out_size is None else "source" if isinstance(out_size, str) and out_size == "source" else (int(out_size[0]), int(out_size[1]))
     if deliver is not None:
         scale_kw = dict(scale_kw, out_size=deliver)
+    if guided is not None:
+        if deliver is None:
+            raise ValueError("guided needs out_size (the size of the frames read)")
+        scale_kw = dict(scale_kw, guide="source", guide_radius=guided[0], guide_eps=guided[1])
     add_kw = {} if work is None else {"work_size": work}                   # (a sampled frame is never delivered)
     # the size of the frame delivered for a source frame of (H, W)
     out_size = (lambda hw: hw) if deliver == "source" else (lambda hw: deliver) if deliver is not None else (lambda hw: hw) if work is None else (lambda hw: work)
@@ -653,7 +658,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
-                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None, out_size=None):
+                yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None, out_size=None,
+                guided=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -668,7 +674,8 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     work_size=(H, W): the file's frames are resampled to that working size on the GPU (add / transfer_frames with work_size=, size= stays the
     file's); the frames written and the .y4m header carry the working size.
     out_size=(H, W) or "source" (the file's frame size): the stylized working frame is resampled to that size on the GPU on its way out
-    (transfer_frames with out_size=); the frames written, the output staging and the .y4m header carry the delivered size."""
+    (transfer_frames with out_size=); the frames written, the output staging and the .y4m header carry the delivered size.
+    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source")."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -693,6 +700,10 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         if out_size is not None:
             OH, OW = (H, W) if isinstance(out_size, str) and out_size == "source" else (int(out_size[0]), int(out_size[1]))
             scale_kw["out_size"] = (OH, OW)
+        if guided is not None:
+            if out_size is None:
+                raise ValueError("guided needs out_size (the size of the frames read)")
+            scale_kw.update(guide="source", guide_radius=guided[0], guide_eps=guided[1])
         fob = video.yuv_frame_bytes(OH, OW, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
@@ -909,6 +920,22 @@ def parse_out_size(text):
     return h, w
 
 
+def parse_guided(text):
+    """--guided: R or R:EPS as (radius, eps), the radius in working pixels 1..16 and eps > 0 in the units of a 0..1 image; ValueError for anything else"""
+    parts = text.split(":")
+    try:
+        if len(parts) not in (1, 2):
+            raise ValueError
+        r, eps = int(parts[0]), float(parts[1]) if len(parts) == 2 else 1e-3
+    except ValueError:
+        raise ValueError("--guided is RADIUS or RADIUS:EPS, e.g. 4:1e-3") from None
+    if not 1 <= r <= 16:
+        raise ValueError("--guided: the radius is 1..16 working pixels")
+    if not eps > 0 or eps == float("inf"):
+        raise ValueError("--guided: eps is a positive number")
+    return r, eps
+
+
 def main(argv=None, model_factory=None):
     """`model_factory(args, device)` builds the model (default: the HIP Stylization / MultiStyleStylization); the CPU tests
     of the multi-rank control flow pass their own."""
@@ -939,6 +966,10 @@ def main(argv=None, model_factory=None):
     ap.add_argument("--out-size", default=None, metavar="WxH|source", help="resample the stylized frame to this size on the GPU on its way out (at most 8x "
                     "either way per axis from the working frame); 'source': the size of the frames read.  With --work-size: stylize at the working size, "
                     "write the source's resolution.  The frames and the video written have this size")
+    ap.add_argument("--guided", nargs="?", const="4:1e-3", default=None, metavar="R[:EPS]", help="with --out-size source: upscale the stylized frame along "
+                    "the edges of the frame read instead of bilinearly (fast guided filter, the source's luma as the guide): box radius R in working pixels "
+                    "(1..16, default 4) and regulariser EPS in the units of a 0..1 image (default 1e-3; smaller keeps more of the source's edges).  "
+                    "video.guided_upsample states the arithmetic in numpy")
     args = ap.parse_args(argv)
     out_size = None
     if args.out_size is not None:
@@ -948,6 +979,14 @@ def main(argv=None, model_factory=None):
             ap.error(str(e))
         if len(args.style) > 1:
             ap.error("--out-size with multi-style interpolation is not supported: the cached-feature entries deliver the frame they run")
+    guided = None
+    if args.guided is not None:
+        try:
+            guided = parse_guided(args.guided)
+        except ValueError as e:
+            ap.error(str(e))
+        if out_size != "source":
+            ap.error("--guided needs --out-size source: the frame read guides the upscale, so the delivered size is its size")
     work_size = None
     if args.work_size is not None:
         try:
@@ -1019,7 +1058,7 @@ def main(argv=None, model_factory=None):
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
                     write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma,
-                    work_size=work_size, out_size=out_size)
+                    work_size=work_size, out_size=out_size, guided=guided)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
@@ -1027,7 +1066,7 @@ def main(argv=None, model_factory=None):
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
                       write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
-                      out_size=out_size)
+                      out_size=out_size, guided=guided)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

@@ -567,6 +567,15 @@ def _out_size(out_size, source):
     return DH, DW
 
 
+def _guide_args(guide, radius, eps, out_size):
+    """(r, eps) of a guided call: guide names the call's own source, and the call names a delivered size"""
+    if guide != "source":
+        raise ValueError("guide must be 'source' (the frames as passed guide the upsampling), got %r" % (guide,))
+    if out_size is None:
+        raise ValueError("guide= needs out_size= (the size of the frames as passed: out_size='source')")
+    return int(radius), float(eps)
+
+
 def _no_styles_with_out_size(style_weights, style_masks):
     if style_weights is not None or style_masks is not None:
         raise ValueError("out_size does not combine with style_weights / style_masks yet: deliver the blended frames with deliver_tensor")
@@ -1005,7 +1014,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None,
-                     out_size=None):
+                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
         size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
@@ -1043,7 +1052,10 @@ class Stylization():
         # what blends the styles (_HOST_ENTRIES), and the plain BGR entry also names the model and the geometry.
         src, dst, flags = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), self._flags(pad_crop)
         name = _HOST_ENTRIES[yuv_in, yuv_out][blend].format(model="" if self.use_Global else "_frame_mode", geometry="_frames" if pad_crop else "_batch")
-        if out_size is not None:
+        if guide is not None:
+            r, eps = _guide_args(guide, guide_radius, guide_eps, out_size)
+            name, args = "rrv_transfer_guided", (src, _host_in_desc(in_format), B, SH, SW, H, W, DH, DW, r, eps, dst, desc, flags)
+        elif out_size is not None:
             name, args = "rrv_transfer_deliver", (src, _host_in_desc(in_format), B, SH, SW, H, W, DH, DW, dst, desc, flags)
         elif work_size is not None:
             name, args = "rrv_transfer_scaled", (src, _host_in_desc(in_format), B, SH, SW, H, W, dst, desc, flags)
@@ -1058,7 +1070,7 @@ class Stylization():
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                       work_size=None, out_size=None):
+                       work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -1090,11 +1102,17 @@ class Stylization():
         include/rerevst_hip.h "Scaling, output size") and converted to `out` / `dtype` / out_format there: [B][DH][DW][3], or the YUV frames
         of that size.  "source" is the size of the frames as passed: with work_size, "stylize at the working size, give me back my
         resolution"; without it, H x W in place of 8*(H//8) x 8*(W//8).  At most 8 either way per axis; not with style_weights /
-        style_masks (ValueError)."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size)
+        style_masks (ValueError).
+        guide="source" with out_size="source" (or that size): guided delivery (rrv_transfer_guided; include/rerevst_hip.h "Guided delivery").
+        The stylized working frame is upsampled along the edges of the source's luma with the fast guided filter instead of bilinearly:
+        guide_radius is the box radius in working pixels (1..16), guide_eps the regulariser in the units of a 0..1 image (smaller keeps
+        more of the source's edges, larger tends to the bilinear picture).  The working size must be delivered whole: H and W of the
+        working frame multiples of 8 (transfer_frames: any).  video.guided_upsample restates the arithmetic in numpy."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size, guide,
+                                 guide_radius, guide_eps)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                        work_size=None, out_size=None):
+                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -1109,8 +1127,10 @@ class Stylization():
         decoder's frames go to an encoder with no pixel touched on the host.
         work_size=(H, W): as in transfer_batch; the resampled H x W frame is what gets reflect-padded and cropped, and [B][H][W][3]
         (or the YUV frames of that size) is what comes back.
-        out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW."""
-        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size)
+        out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW.
+        guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size."""
+        return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size, guide,
+                                 guide_radius, guide_eps)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -1118,7 +1138,8 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
-                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None):
+                        pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None, guide=None,
+                        guide_radius=4, guide_eps=1e-3):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -1156,8 +1177,13 @@ class Stylization():
         out_size=(DH, DW) or "source" (the size of the frames as passed): the stylized working frame is resampled to that size on the GPU
         on its way out (rrv_transfer_deliver_view_device; include/rerevst_hip.h "Scaling, output size"), with or without work_size, into
         any out_layout / out_space / out_dtype or `out` (a tensor, a window or an ImageView of DH x DW frames): [.., DH, DW].  A "norm"
-        output is then the normalised delivered pixel (a resampled frame has no pre-clamp value).  Not with style_weights / style_masks."""
+        output is then the normalised delivered pixel (a resampled frame has no pre-clamp value).  Not with style_weights / style_masks.
+        guide="source" with out_size="source" (or that size): guided delivery (rrv_transfer_guided_view_device; include/rerevst_hip.h "Guided
+        delivery"), guide_radius in working pixels (1..16) and guide_eps in the units of a 0..1 image as in transfer_batch.  The call equals
+        the float32 "nhwc" call at the working size, resample_tensor for the two guides and deliver_tensor(.., guide_lo=, guide_hi=)."""
         import torch
+        if guide is not None:
+            g_r, g_eps = _guide_args(guide, guide_radius, guide_eps, out_size)
         if out_size is not None:
             _no_styles_with_out_size(style_weights, style_masks)
         elif work_size is not None:
@@ -1203,7 +1229,9 @@ class Stylization():
         self._yuv_depth(src.layout, dst.layout)
         stream = self._stream(src.tensor)
         for b0, nb, p, q in _chunks(B, (src.ptr, src.step), (dst.ptr, dst.step)):
-            if out_size is not None:
+            if guide is not None:
+                self._chk(self._lib.rrv_transfer_guided_view_device(self._h, p, in_arg, nb, SH, SW, H, W, DH, DW, g_r, g_eps, q, out_arg, flags, stream))
+            elif out_size is not None:
                 self._chk(self._lib.rrv_transfer_deliver_view_device(self._h, p, in_arg, nb, SH, SW, H, W, DH, DW, q, out_arg, flags, stream))
             elif work is not None:
                 self._chk(self._lib.rrv_transfer_scaled_view_device(self._h, p, in_arg, nb, SH, SW, H, W, q, out_arg, flags, stream))
@@ -1218,11 +1246,15 @@ class Stylization():
                 self._chk(getattr(self._lib, names[_PLAIN])(self._h, p, in_arg, nb, H, W, q, out_arg, flags, stream))
         return dst.result
 
-    def deliver_tensor(self, y, out_size, *, out_space="pixel", out_dtype=None, out_layout=None, out=None):
+    def deliver_tensor(self, y, out_size, *, out_space="pixel", out_dtype=None, out_layout=None, out=None, guide_lo=None, guide_hi=None, guide_radius=4,
+                       guide_eps=1e-3):
         """The delivery stage alone (rrv_deliver_view_device): y a float32 tensor [B,H,W,3] ([H,W,3]) on the handle's GPU, BGR, "pixel"
         space — what transfer_tensor(.., layout="nhwc") and resample_tensor return — resampled to out_size=(DH, DW) on the GPU and written
         as transfer_tensor(out_size=) writes it: out_layout ("nhwc" by default, "nchw", or a YUV format name), out_space, out_dtype, or
-        `out` (a tensor, a window of a canvas, or an ImageView of DH x DW frames).  Ordered on the current stream, like resample_tensor."""
+        `out` (a tensor, a window of a canvas, or an ImageView of DH x DW frames).  Ordered on the current stream, like resample_tensor.
+        guide_lo, guide_hi: the guided stage alone instead (rrv_deliver_guided_view_device; include/rerevst_hip.h "Guided delivery"): float32
+        tensors of y's form, the source at y's size and at out_size (resample_tensor gives both); guide_radius in pixels of y (1..16),
+        guide_eps in the units of a 0..1 image.  out_size is at least y's size and at most 8 times it, per axis."""
         import torch
         if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() not in (3, 4) or y.shape[-1] != 3:
             raise ValueError("y must be a float32 tensor [B,H,W,3] or [H,W,3] (BGR, 'pixel' space)")
@@ -1235,9 +1267,29 @@ class Stylization():
         vo = _whole_view(dst, DH, DW)
         self._yuv_depth(None, dst.layout)
         stream = self._stream(y)
+        if guide_lo is not None or guide_hi is not None:
+            if guide_lo is None or guide_hi is None:
+                raise ValueError("guided delivery needs both guide_lo (the source at y's size) and guide_hi (the source at out_size)")
+            glo, ghi = (self._guide_tensor(g, name, (B, gh, gw, 3), batched) for g, name, gh, gw in ((guide_lo, "guide_lo", H, W), (guide_hi, "guide_hi", DH, DW)))
+            r, eps = _guide_args("source", guide_radius, guide_eps, out_size)
+            for b0, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (dst.ptr, dst.step)):
+                self._chk(self._lib.rrv_deliver_guided_view_device(self._h, p, C.c_void_p(glo[b0].data_ptr()), C.c_void_p(ghi[b0].data_ptr()), nb, H, W, DH, DW,
+                                                                   r, eps, q, C.byref(vo), stream))
+            return dst.result
         for _, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (dst.ptr, dst.step)):
             self._chk(self._lib.rrv_deliver_view_device(self._h, p, nb, H, W, DH, DW, q, C.byref(vo), stream))
         return dst.result
+
+    def _guide_tensor(self, g, name, shape, batched):
+        """a guide of deliver_tensor as a contiguous float32 [B,H,W,3] tensor on the handle's GPU"""
+        import torch
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.dim() != (4 if batched else 3):
+            raise ValueError("%s must be a float32 tensor of y's form (BGR, 'pixel' space)" % name)
+        _on_device(g, name, self.device)
+        gb = (g if batched else g.unsqueeze(0)).contiguous()
+        if tuple(gb.shape) != tuple(shape):
+            raise ValueError("%s has shape %s, expected %s" % (name, tuple(gb.shape), tuple(shape)))
+        return gb
 
     def sync(self):
         self._chk(self._lib.rrv_sync(self._h))

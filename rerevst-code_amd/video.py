@@ -90,6 +90,45 @@ def resize_bilinear(img, size):
     return np.clip(np.rint(top * (1 - fy) + bot * fy), 0, 255).astype(np.uint8)
 
 
+def guided_upsample(stylized, source_lo, source_hi, radius=4, eps=1e-3):
+    """What guided delivery computes (transfer_frames(.., out_size="source", guide="source"); include/rerevst_hip.h "Guided delivery"), in
+    float64 numpy: the stylized working frame [H][W][3] upsampled to the size of source_hi [DH][DW][3] along the edges of the source's
+    luma, source_lo [H][W][3] being the source at the working size.  All BGR in 0..255; radius in working pixels, eps in the units of a
+    0..1 image.  Returns float64 [DH][DW][3], not clamped.  (Fast guided filter, He & Sun 2015: fit stylized = a * luma + b in every
+    window, average and upsample a and b, apply them to the full-resolution luma.)"""
+    P, lo, hi = (np.asarray(v, np.float64) for v in (stylized, source_lo, source_hi))
+    H, W = P.shape[:2]
+    DH, DW = hi.shape[:2]
+    if lo.shape[:2] != (H, W) or DH < H or DW < W or DH > 8 * H or DW > 8 * W or not 1 <= int(radius) <= 16 or not eps > 0:
+        raise ValueError("guided_upsample: source_lo has the stylized frame's size, source_hi 1..8 times it per axis, radius is 1..16, eps > 0")
+    r, e = int(radius), eps * 65025.0
+    k = [float(np.float32(c)) for c in (0.114, 0.587, 0.299)]
+
+    def luma(x):
+        return (k[0] * x[..., 0] + k[1] * x[..., 1]) + k[2] * x[..., 2]
+
+    def box_mean(f):      # the mean over [y - r, y + r] x [x - r, x + r] clipped to the frame
+        c = np.pad(np.cumsum(np.cumsum(f, 0), 1), [(1, 0), (1, 0)] + [(0, 0)] * (f.ndim - 2))
+        y0, y1 = np.maximum(np.arange(H) - r, 0), np.minimum(np.arange(H) + r, H - 1) + 1
+        x0, x1 = np.maximum(np.arange(W) - r, 0), np.minimum(np.arange(W) + r, W - 1) + 1
+        s = c[y1][:, x1] - c[y0][:, x1] - c[y1][:, x0] + c[y0][:, x0]
+        n = ((y1 - y0)[:, None] * (x1 - x0)[None, :]).astype(np.float64)
+        return s / (n[..., None] if f.ndim == 3 else n)
+
+    def up(f):            # half-pixel bilinear with edge clamp, the tables of rrv_resample_taps for an upscale
+        for axis, S, D in ((1, W, DW), (0, H, DH)):
+            c = np.clip((np.arange(D) + 0.5) * (S / D) - 0.5, 0, S - 1)
+            i0 = np.floor(c).astype(np.int64)
+            i1, t = np.minimum(i0 + 1, S - 1), (c - i0).reshape([-1 if a == axis else 1 for a in range(f.ndim)])
+            f = np.take(f, i0, axis) * (1 - t) + np.take(f, i1, axis) * t
+        return f
+    g = luma(lo)
+    mg, mP = box_mean(g), box_mean(P)
+    a = (box_mean(g[..., None] * P) - mg[..., None] * mP) / (box_mean(g * g) - mg * mg + e)[..., None]
+    b = mP - a * mg[..., None]
+    return up(box_mean(a)) * luma(hi)[..., None] + up(box_mean(b))
+
+
 # ===== the YUV formats by name: the one table framework.py and the drivers read =====
 # layout: RRV_LAY_* of include/rerevst_hip.h; bits: the code depth; dtype: of a sample (uint16 above 8 bits); planar: [Y][Cb][Cr], else [Y][CbCr];
 # chroma: "420" (a chroma sample per 2 x 2 block), "422" (per horizontal pixel pair) or "444" (per pixel).
