@@ -718,6 +718,10 @@ int rrv_transfer_deliver(rrv_handle h, const void* frames, rrv_image_desc in, in
  *                                    DH x DW == SH x SW, or SH = SW = 0 and DH x DW == H x W; and a delivered working frame of H x W:
  *                                    RRV_TF_PAD_CROP, or H and W multiples of 8.  Anything else is RRV_E_ARG
  *   rrv_transfer_guided              the host twin through the host pipeline; sub-batches by the sizing rules of rrv_transfer_deliver
+ *   rrv_guided_tile                  the tile the stage launches its second kernel with for a working frame H x W, a delivered frame DH x DW and
+ *                                    radius r: delivered columns per tile (tw; 16 rows), the working rows and columns a tile stages (sy, sx) and
+ *                                    the dynamic LDS of the second and the first kernel in bytes; no handle, no GPU; RRV_E_ARG for a null pointer
+ *                                    and for sizes or a radius the entries above refuse
  * A guided call equals, bit for bit in a fixed kernel mode, the float32 HWC BGR PIXEL call at the working size, the resampler alone for the
  * two guides, and rrv_deliver_guided_view_device into the form asked for.  r and eps travel with the call, never in the handle.
  * Checks, all before any GPU work, as "Output size"; RRV_E_ARG names the field and the handle stays usable.  Per workspace slot the stage
@@ -730,6 +734,7 @@ int rrv_transfer_guided_view_device(rrv_handle h, const void* d_in, const rrv_im
                                     int DH, int DW, int r, float eps, void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
 int rrv_transfer_guided(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W,
                         int DH, int DW, int r, float eps, void* out, rrv_image_desc out_desc, int flags);
+int rrv_guided_tile(int H, int W, int DH, int DW, int r, int* tw, int* sy, int* sx, int* apply_lds_bytes, int* coeff_lds_bytes);
 
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */

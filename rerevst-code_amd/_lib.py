@@ -159,6 +159,7 @@ SYMBOLS = {
                                                   C.c_int, C.c_float, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),
     "rrv_transfer_guided": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_guided_tile": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),      # no handle: (H, W, DH, DW, r, tw, sy, sx, apply LDS, coeff LDS)
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

@@ -9,7 +9,9 @@
 //      that of the arithmetic: in every form consecutive lanes write consecutive elements of a plane row (float: 256 contiguous bytes per
 //      wave and row, uint8: 64), and a chroma sample reads the 1, 2 or 4 pixels of its block out of LDS with no cross-lane traffic.  Frames,
 //      planes and rows of a view are only element aligned, so the integer forms leave as 1- or 2-byte stores.
-// Both passes accumulate in float32 with fmaf from -0, taps in ascending order, as resample_k does; the tables hold no tap of weight 0.
+// Both passes accumulate in float32 with fmaf from -0, taps in ascending order, as resample_k does.  The tables rs_build makes do hold taps of weight
+// exactly 0, always a row's last (the 0 of an identity row {1, 0}; the third tap of some upscaled samples, e.g. 7 -> 55, sample 27: {4.4e-16, 1, 0}),
+// and rrv_resample_taps reports them; the host drops them from the copy it uploads, so the tables the kernels read hold none.
 // Reads are bounded by the tap tables (first + count <= S on both axes, built by the host).  Tile origins are even (16 x 64), so a chroma
 // block never straddles tiles; a block's pixel outside the frame (odd last row or column) is replaced by its nearest one inside, which
 // lies in the same tile.  Every address is computed in 64 bits from the view, as conv_last_k does.

@@ -43,6 +43,8 @@ inline size_t guided_apply_lds_bytes(int r, int sy, int sx) {      // staged a, 
     return ((size_t)6 * (sy + 2 * r) * (sx + 2 * r) + (size_t)6 * (sy + 2 * r) * sx) * sizeof(float);
 }
 // Fills tw, sy, sx of `p` from its sizes and radius: the widest tile whose LDS fits.  False: none does (cannot happen for r <= GF_R_MAX).
+// Within r <= GF_R_MAX only 64 and 32 are ever chosen (sy <= 18 and sx <= 34 at tw = 32: 120,000 bytes at r = 16); the 16 and 8 of the loop
+// are never reached and stay as the margin of a larger radius (tests/test_guided_host.py sweeps the rule through rrv_guided_tile).
 inline bool guided_tile(GuidedP* p) {
     p->sy = guided_span(p->H, p->DH, GF_AT_H);
     for (int tw = 64; tw >= 8; tw >>= 1) {

@@ -2954,6 +2954,19 @@ static int check_guided(rrv_handle h, const char* who, int H, int W, int DH, int
     if (DW < W || (int64_t)DW > 8 * (int64_t)W) return fail(h, RRV_E_ARG, std::string(who) + ": DW / the working frame's width must be within 1 .. 8");
     return RRV_OK;
 }
+// the tile guided_launch gives gf_apply_k for these sizes and the dynamic LDS of both kernels; the sizes and the radius are check_guided's
+int rrv_guided_tile(int H, int W, int DH, int DW, int r, int* tw, int* sy, int* sx, int* apply_lds_bytes, int* coeff_lds_bytes) {
+    if (!tw || !sy || !sx || !apply_lds_bytes || !coeff_lds_bytes) return RRV_E_ARG;
+    if (r < 1 || r > GF_R_MAX || H < 1 || W < 1) return RRV_E_ARG;
+    if (DH < H || (int64_t)DH > 8 * (int64_t)H || DW < W || (int64_t)DW > 8 * (int64_t)W) return RRV_E_ARG;
+    GuidedP p{};
+    p.H = H; p.W = W; p.DH = DH; p.DW = DW; p.r = r;
+    if (!guided_tile(&p)) return RRV_E_ARG;      // (cannot happen within the radius limit)
+    *tw = p.tw; *sy = p.sy; *sx = p.sx;
+    *apply_lds_bytes = (int)guided_apply_lds_bytes(r, p.sy, p.sx);
+    *coeff_lds_bytes = (int)guided_coeff_lds_bytes(r);
+    return RRV_OK;
+}
 // the tables the stage and the equal-size passes around it read: (H, W) -> (DH, DW), and the identity of the delivered size
 static int gd_tables(rrv_handle h, int H, int W, int DH, int DW) {
     const rrv_ctx::RsTab *ty, *tx;

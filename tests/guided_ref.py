@@ -32,7 +32,45 @@ CASES = {
     "b": ((40, 72), (97, 131), 5),
     "c": ((24, 24), (24, 24), 4),
     "d": ((8, 16), (64, 128), 16),
+    # the tiles of gf_apply_k (tile() below; tests/test_gpu_guided.py asserts them through rrv_guided_tile)
+    "e": ((24, 80), (24, 80), 16),          # tw = 32 at 120,000 B of LDS, equal size
+    "f": ((24, 80), (24, 80), 11),          # tw = 64 at 147,840 B, the largest request that fits
+    "g": ((24, 80), (30, 90), 16),          # tw = 32 with two-tap rows and columns, seams at 32 and 64, a last tile of 26 columns
+    "h_row": ((1, 40), (8, 75), 3),         # a one-pixel axis: the window is the frame on that axis, the anchor clamps
+    "h_col": ((40, 1), (75, 8), 3),
+    "j": ((17, 33), (33, 65), 2),           # last tiles of one row and one column in both kernels
+    "k": ((9, 10), (72, 80), 1),            # 8 x on both axes with the smallest radius
 }
+
+# The tile of gf_apply_k, restated from csrc/guided.h: 16 delivered rows by tw columns, tw the widest of 64, 32, 16, 8 whose dynamic LDS fits.
+R_MAX = 16
+AT_H, CT_H, CT_W = 16, 16, 32
+LDS_MAX = 152 * 1024
+
+
+def span(S, D, T):
+    """working samples that T consecutive delivered samples' taps span at most, S -> D with D >= S"""
+    return min((T - 1) * S // D + 3, S)
+
+
+def apply_lds_bytes(r, sy, sx):
+    """staged planes [6][sy + 2r][sx + 2r] and their row sums [6][sy + 2r][sx], float32"""
+    return (6 * (sy + 2 * r) * (sx + 2 * r) + 6 * (sy + 2 * r) * sx) * 4
+
+
+def coeff_lds_bytes(r):
+    """staged g, P_c [4][16 + 2r][32 + 2r] and the row sums of the eight moments [8][16 + 2r][32], float32"""
+    return (4 * (CT_H + 2 * r) * (CT_W + 2 * r) + 8 * (CT_H + 2 * r) * CT_W) * 4
+
+
+def tile(H, W, DH, DW, r):
+    """(tw, sy, sx, apply LDS bytes) of working H x W, delivered DH x DW and radius r; None where no tile fits"""
+    sy = span(H, DH, AT_H)
+    for tw in (64, 32, 16, 8):
+        sx = span(W, DW, tw)
+        if apply_lds_bytes(r, sy, sx) <= LDS_MAX:
+            return tw, sy, sx, apply_lds_bytes(r, sy, sx)
+    return None
 
 
 def luma(x, dtype=np.float64):
@@ -177,4 +215,46 @@ NAIVE_ERR = {
     ("d", "noise", 0.01): 6.367e-04,
     ("d", "step", 0.0001): 2.827e-04,
     ("d", "step", 0.01): 2.228e-04,
+    ("e", "ramp", 0.0001): 3.031e-04,
+    ("e", "ramp", 0.01): 7.100e-05,
+    ("e", "noise", 0.0001): 5.777e-05,
+    ("e", "noise", 0.01): 5.980e-05,
+    ("e", "step", 0.0001): 3.315e-03,
+    ("e", "step", 0.01): 2.528e-04,
+    ("f", "ramp", 0.0001): 4.807e-04,
+    ("f", "ramp", 0.01): 4.614e-05,
+    ("f", "noise", 0.0001): 4.834e-05,
+    ("f", "noise", 0.01): 4.832e-05,
+    ("f", "step", 0.0001): 4.057e-02,
+    ("f", "step", 0.01): 3.618e-04,
+    ("g", "ramp", 0.0001): 2.625e-04,
+    ("g", "ramp", 0.01): 6.631e-05,
+    ("g", "noise", 0.0001): 1.449e-04,
+    ("g", "noise", 0.01): 1.017e-04,
+    ("g", "step", 0.0001): 2.848e-03,
+    ("g", "step", 0.01): 2.225e-04,
+    ("h_row", "ramp", 0.0001): 4.632e-03,
+    ("h_row", "ramp", 0.01): 6.659e-05,
+    ("h_row", "noise", 0.0001): 3.785e-02,
+    ("h_row", "noise", 0.01): 2.531e-04,
+    ("h_row", "step", 0.0001): 1.178e-02,
+    ("h_row", "step", 0.01): 2.229e-04,
+    ("h_col", "ramp", 0.0001): 4.316e-03,
+    ("h_col", "ramp", 0.01): 7.589e-05,
+    ("h_col", "noise", 0.0001): 6.067e-03,
+    ("h_col", "noise", 0.01): 1.721e-04,
+    ("h_col", "step", 0.0001): 2.978e-02,
+    ("h_col", "step", 0.01): 3.725e-04,
+    ("j", "ramp", 0.0001): 8.207e-04,
+    ("j", "ramp", 0.01): 3.933e-05,
+    ("j", "noise", 0.0001): 1.953e-03,
+    ("j", "noise", 0.01): 1.878e-04,
+    ("j", "step", 0.0001): 5.297e-03,
+    ("j", "step", 0.01): 9.243e-05,
+    ("k", "ramp", 0.0001): 1.583e-03,
+    ("k", "ramp", 0.01): 3.933e-05,
+    ("k", "noise", 0.0001): 8.571e-02,
+    ("k", "noise", 0.01): 2.518e-04,
+    ("k", "step", 0.0001): 1.127e-02,
+    ("k", "step", 0.01): 7.753e-05,
 }

@@ -100,6 +100,50 @@ def test_stage_against_float64(hip, case, kind, eps):
     assert err <= bound
 
 
+def _tile(case):
+    work, dst, r = G.CASES[case]
+    out = [C.c_int(-1) for _ in range(5)]
+    assert L.load().rrv_guided_tile(*work, *dst, r, *[C.byref(v) for v in out]) == RRV_OK
+    return tuple(v.value for v in out)      # tw, sy, sx, gf_apply_k's LDS bytes, gf_coeff_k's
+
+
+def test_the_new_cases_run_the_tiles_they_are_for():
+    """What the library launches for cases e, f and g of test_stage_against_float64, from the library itself: gf_apply_k with 32 columns per
+    tile (e, g), and with 64 at the largest LDS request that fits, far above the 64 KB a launch gets without the attribute (f)"""
+    assert _tile("e")[:4] == (32, 18, 34, 120000)
+    assert _tile("f")[:4] == (64, 18, 66, 147840) and 65536 < 147840 <= 152 * 1024
+    assert _tile("g")[:4] == (32, 15, 30, 103776)
+    assert all(_tile(c)[0] == 64 and _tile(c)[3] <= 65536 for c in G.CASES if c not in ("e", "f", "g"))
+    assert _tile("d")[4] == _tile("e")[4] == 98304      # gf_coeff_k at r = 16: above 64 KB as well
+
+
+def test_one_working_pixel_is_delivered_bit_for_bit(hip):
+    """(1, 1) -> (8, 8): every window is the one pixel, so covariance and variance are exactly 0, a = 0, b = P, and Q[y][x][c] = P[0][0][c] bit for
+    bit, whatever the guide, the radius and eps"""
+    rng = np.random.default_rng(17)
+    P = rng.uniform(1.0, 255.0, (3, 1, 1, 3)).astype(np.float32)
+    lo = rng.uniform(0.0, 255.0, (3, 1, 1, 3)).astype(np.float32)
+    hi = rng.uniform(0.0, 255.0, (3, 8, 8, 3)).astype(np.float32)
+    want = np.broadcast_to(P, (3, 8, 8, 3))
+    for r in (1, 5, 16):
+        for eps in (1e-6,) + G.EPS:
+            assert np.array_equal(G.stage(P, lo, hi, r, eps, np.float32), want) and np.array_equal(G.stage(P, lo, hi, r, eps), want)
+            got = _host(hip, hip.deliver_tensor(_dev(P), (8, 8), guide_lo=_dev(lo), guide_hi=_dev(hi), guide_radius=r, guide_eps=eps))
+            np.testing.assert_array_equal(got, want)
+
+
+def test_the_batch_limit_equals_one_call_per_frame(hip):
+    """B = 64, the entry's limit: frame b's bits are those of the call on frame b alone"""
+    work, dst, r = (8, 8), (16, 24), 4
+    P, lo, hi = (_dev(a) for a in G.inputs("noise", 64, work, dst, seed=4))
+    kw = dict(guide_radius=r, guide_eps=1e-3)
+    whole = _host(hip, hip.deliver_tensor(P, dst, guide_lo=lo, guide_hi=hi, **kw))
+    ones = [hip.deliver_tensor(P[b], dst, guide_lo=lo[b], guide_hi=hi[b], **kw) for b in range(64)]
+    ones = _host(hip, _torch().stack(ones))
+    assert whole.shape == (64, *dst, 3) and not np.array_equal(whole[0], whole[63])
+    np.testing.assert_array_equal(whole, ones)
+
+
 def test_each_frame_equals_its_own_call(hip):
     """B = 3 distinct frames: frame b's bits are those of the call on frame b alone"""
     work, dst, r = (40, 72), (97, 131), 4

@@ -1,7 +1,10 @@
 """Guided delivery without a GPU: tests/guided_ref.py against what the arithmetic must do on inputs with a known answer, its committed
 yardstick against what the float32 restatement gives, the ledger of librerevst_guided.so (every kernel symbol of its gfx950 code object
 is named here and held by one test of tests/test_gpu_guided.py; the rule of tests/kernel_ledger.py, only symbol names are read), and the
-guide= / --guided argument handling and video.guided_upsample."""
+guide= / --guided argument handling and video.guided_upsample.  Then what gf_apply_k's correctness rests on and no GPU is needed for: the
+tile rule (rrv_guided_tile against guided_ref.tile), the span bound on every table the library builds, and five deliberate flaws that the
+GPU test's bounds must reject."""
+import ctypes as C
 import importlib
 import os
 
@@ -18,10 +21,13 @@ FW = importlib.import_module("rerevst-code_amd.framework")
 D = importlib.import_module("rerevst-code_amd.driver")
 V = importlib.import_module("rerevst-code_amd.video")
 
+RRV_OK, RRV_E_ARG = 0, -1
 GPU = "tests/test_gpu_guided.py::"
 GUIDED_LEDGER = {
     "gf_coeff_k": GPU + "test_stage_against_float64",
-    "gf_apply_k": GPU + "test_each_frame_equals_its_own_call",      # (and test_stage_against_float64: both kernels run in every case)
+    # (and test_stage_against_float64: both kernels run in every case.  gf_apply_k at tw = 32 runs in its cases e and g, at the largest LDS request
+    # in case f; test_the_new_cases_run_the_tiles_they_are_for holds them to that through rrv_guided_tile)
+    "gf_apply_k": GPU + "test_each_frame_equals_its_own_call",
 }
 
 
@@ -90,6 +96,216 @@ def test_the_yardstick_is_what_the_restatement_gives():
         text = f.read()
     for (case, kind, eps), err in G.NAIVE_ERR.items():
         assert "%-5s %-6s %-7g %.3e" % (case, kind, eps, err) in text, (case, kind, eps)
+
+
+def test_new_yardsticks_are_above_one_ulp_at_255():
+    """a bound of a few float32 ulps of a grey level would decide the test by rounding alone"""
+    assert min(G.NAIVE_ERR.values()) >= 2.0 ** -16
+
+
+# ---- the tile of gf_apply_k: rrv_guided_tile against the restatement of csrc/guided.h in guided_ref
+def _lib_tile(H, W, DH, DW, r):
+    out = [C.c_int(-7) for _ in range(5)]
+    rc = L.load().rrv_guided_tile(H, W, DH, DW, r, *[C.byref(v) for v in out])
+    return rc, tuple(v.value for v in out)
+
+
+def test_tile_query_refuses_what_the_entries_refuse():
+    lib = L.load()
+    assert _lib_tile(24, 80, 24, 80, 16)[0] == RRV_OK
+    for bad in ((24, 80, 24, 80, 0), (24, 80, 24, 80, 17), (24, 80, 24, 80, -1), (0, 80, 24, 80, 4), (24, 0, 24, 80, 4), (24, 80, 23, 80, 4),
+                (24, 80, 24, 79, 4), (24, 80, 193, 80, 4), (24, 80, 24, 641, 4), (-1, -1, -1, -1, 4)):
+        rc, out = _lib_tile(*bad)
+        assert rc == RRV_E_ARG and out == (-7,) * 5, bad      # and nothing is written
+    assert _lib_tile(24, 80, 192, 640, 4)[0] == RRV_OK
+    ok = [C.c_int(-7) for _ in range(5)]
+    for k in range(5):      # each null pointer
+        args = [C.byref(v) for v in ok]
+        args[k] = None
+        assert lib.rrv_guided_tile(24, 80, 24, 80, 4, *args) == RRV_E_ARG
+    assert [v.value for v in ok] == [-7] * 5
+
+
+def test_tile_rule_pinned_facts():
+    assert G.span(80, 80, 64) == 66 and G.span(80, 80, 32) == 34 and G.span(24, 24, 16) == 18 and G.span(1, 8, 16) == 1 and G.span(8, 64, 16) == 4
+    for (work, dst, r), want in ((((24, 80), (24, 80), 16), (32, 18, 34, 120000)), (((24, 80), (24, 80), 11), (64, 18, 66, 147840)),
+                                 (((24, 80), (30, 90), 16), (32, 15, 30, 103776))):
+        assert G.tile(*work, *dst, r) == want
+        rc, out = _lib_tile(*work, *dst, r)
+        assert rc == RRV_OK and out == want + (G.coeff_lds_bytes(r),)
+    # what makes case f the limit: at tw = 64 the radius above it no longer fits, and the rejected tw = 64 tile of case e is as the header's formula says
+    assert G.apply_lds_bytes(16, 18, 66) == 196800 > G.LDS_MAX >= 147840 and G.tile(24, 80, 24, 80, 12)[0] == 32
+    assert G.coeff_lds_bytes(16) == (4 * 48 * 64 + 8 * 48 * 32) * 4
+    for case, (work, dst, r) in G.CASES.items():      # every case the GPU test runs
+        rc, out = _lib_tile(*work, *dst, r)
+        assert rc == RRV_OK and out == G.tile(*work, *dst, r) + (G.coeff_lds_bytes(r),), case
+    assert {c: G.tile(*w, *d, r)[0] for c, (w, d, r) in G.CASES.items() if G.tile(*w, *d, r)[0] != 64} == {"e": 32, "g": 32}
+    assert max(G.tile(*G.CASES[c][0], *G.CASES[c][1], G.CASES[c][2])[3] for c in ("a_r1", "a_r4", "a_r9", "b", "c", "d")) == 44928      # without e, f, g: under 64 KB
+
+
+def test_tile_rule_sweep():
+    """r in 1..16, working sizes 1..96 per axis, ratios 1, 1.25, 2, 3.7 and 8 (the same on both axes, and every pair of them on a coarser grid of
+    sizes): the library's tile is the restatement's, a tile always exists, and only tw = 64 and 32 are ever chosen"""
+    ratios = (1.0, 1.25, 2.0, 3.7, 8.0)
+    chosen, n = set(), 0
+    coarse = (1, 2, 7, 16, 17, 31, 33, 64, 80, 96)
+
+    def one(H, W, DH, DW, r):
+        want = G.tile(H, W, DH, DW, r)
+        rc, out = _lib_tile(H, W, DH, DW, r)
+        assert want is not None and rc == RRV_OK and out == want + (G.coeff_lds_bytes(r),), (H, W, DH, DW, r, out, want)
+        assert want[3] <= G.LDS_MAX and want[1] == G.span(H, DH, 16) and want[2] == G.span(W, DW, want[0])
+        chosen.add(want[0])
+    for r in range(1, G.R_MAX + 1):
+        for q in ratios:
+            for H in range(1, 97):
+                for W in range(1, 97):
+                    one(H, W, max(H, int(H * q)), max(W, int(W * q)), r)
+                    n += 1
+        for qy in ratios:
+            for qx in ratios:
+                if qx != qy:
+                    for H in coarse:
+                        for W in coarse:
+                            one(H, W, max(H, int(H * qy)), max(W, int(W * qx)), r)
+    assert n == 16 * 5 * 96 * 96 and chosen == {64, 32}
+
+
+# ---- the span bound on the library's own tables: gf_apply_k leaves out every tap beyond the sy x sx working samples its LDS holds
+_TAP_CAP = 4
+_TAP_BUF = (np.zeros(8 * 1080, np.int32), np.zeros(8 * 1080, np.int32), np.zeros(8 * 1080 * _TAP_CAP, np.float32))
+
+
+def _tables(S, D):
+    first, count, w = _TAP_BUF
+    rc = L.load().rrv_resample_taps(S, D, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
+                                    w.ctypes.data_as(C.POINTER(C.c_float)), _TAP_CAP)
+    assert rc == RRV_OK, (S, D)      # (a row of more than _TAP_CAP taps is refused: an upscale has three at the most)
+    return first[:D], count[:D], w[:D * _TAP_CAP].reshape(D, _TAP_CAP)
+
+
+def _check_axis(S, D):
+    """-> (tiles checked, tiles whose span equals the bound, samples with a third tap)"""
+    first, count, w = _tables(S, D)
+    assert (np.diff(first) >= 0).all() and count.min() >= 1 and count.max() <= 3 and (first + count <= S).all(), (S, D)
+    assert not w[:, 2:].any(), (S, D)      # a third tap weighs exactly 0.0f: the kernel's two taps are all of the sum
+    end = first + count
+    tiles = tight = 0
+    for T in (16, 64, 32):      # GF_AT_H rows; the two widths guided_tile() ever chooses
+        i0 = np.arange(0, D, T)
+        i1 = np.minimum(i0 + T, D) - 1
+        used = end[i1] - first[i0]
+        bound = G.span(S, D, T)
+        assert (used <= bound).all(), (S, D, T, int(i0[np.argmax(used)]), int(used.max()), bound)
+        tiles += len(i0)
+        tight += int((used == bound).sum())
+    return tiles, tight, int((count == 3).sum())
+
+
+def test_span_bound_holds_on_every_table():
+    """every S in 1..128 and D in S..8S, every tile origin i0 = k T: first[i1] + count[i1] - first[i0] <= span(S, D, T) for the tile's last sample
+    i1; first is non-decreasing, no sample has more than three taps and the third weighs nothing.  Then the sizes of real video."""
+    tiles = tight = third = 0
+    for S in range(1, 129):
+        for D in range(S, 8 * S + 1):
+            a, b, c = _check_axis(S, D)
+            tiles, tight, third = tiles + a, tight + b, third + c
+    for S in (360, 540, 720, 1080):
+        for D in (1080, 2160):
+            if S <= D <= 8 * S:
+                a, b, c = _check_axis(S, D)
+                tiles, tight, third = tiles + a, tight + b, third + c
+    print("span bound: %d tiles, %d with no slack, %d samples with a third tap" % (tiles, tight, third))
+    assert tight > 0 and third > 0      # the bound is met with equality somewhere, and three-tap samples exist: neither assertion above is vacuous
+    first, count, w = _tables(7, 55)      # the example of csrc/deliver.hip
+    assert count[27] == 3 and w[27, 1] == 1.0 and w[27, 2] == 0.0 and 0.0 < w[27, 0] < 1e-15
+
+
+# ---- the bounds reject wrong arithmetic: five flawed float32 restatements against the float64 reference
+def _flawed_upsample(drop_col=False, early_row=False):
+    """guided_ref.upsample with the second tap of every 32nd delivered column (31, 63, ..: a 32-column tile's last) dropped, or the last delivered
+    row's taps starting one working row early"""
+    def up(f, DH, DW):
+        dt = f.dtype.type
+        for axis, D in ((2, DW), (1, DH)):
+            first, count, w = R.taps(f.shape[axis], D)
+            w = w.astype(np.float32).astype(f.dtype)
+            if drop_col and axis == 2:
+                w[31::32, 1] = 0
+            if early_row and axis == 1:
+                first = first.copy()
+                first[-1] = max(first[-1] - 1, 0)
+            shape = [1] * f.ndim
+            shape[axis] = D
+            out = np.zeros(f.shape[:axis] + (D,) + f.shape[axis + 1:], f.dtype)
+            for j in range(int(count.max())):
+                idx = np.minimum(first + j, f.shape[axis] - 1)
+                out = out + np.where(j < count, w[:, j], dt(0)).reshape(shape) * np.take(f, idx, axis=axis)
+            f = out
+        return f
+    return up
+
+
+def _border_box_mean(f, r):
+    """guided_ref.box_mean with the corner window divided by one pixel too many"""
+    H, W = f.shape[1:3]
+    cnt = (G.window_count(H, r)[:, None] * G.window_count(W, r)[None, :]).astype(f.dtype)
+    cnt[0, 0] += 1
+    s = G._axis_sum(G._axis_sum(f, r, 2), r, 1)
+    return s / (cnt[..., None] if f.ndim == 4 else cnt)
+
+
+def _wrong_e(orig):
+    return lambda P, x_lo, r, eps, dtype=np.float64: orig(P, x_lo, r, eps * 65536.0 / 65025.0, dtype)
+
+
+FLAWS = {
+    "border_window_one_pixel_more": lambda: ("box_mean", _border_box_mean),
+    "luma_b_and_r_swapped": lambda: ("LUMA", (G.LUMA[2], G.LUMA[1], G.LUMA[0])),
+    "e_is_eps_65536": lambda: ("coefficients", _wrong_e(G.coefficients)),
+    "second_tap_of_every_32nd_column_dropped": lambda: ("upsample", _flawed_upsample(drop_col=True)),
+    "last_row_one_working_row_early": lambda: ("upsample", _flawed_upsample(early_row=True)),
+}
+
+
+def _can_show(flaw, case):
+    (H, W), (DH, DW), r = G.CASES[case]
+    if flaw == "second_tap_of_every_32nd_column_dropped":      # needs a column 31 with two taps: an upscale along the row and DW >= 32
+        return DW > W and DW >= 32
+    if flaw == "last_row_one_working_row_early":                # needs two working rows whose means differ: with r >= H - 1 every window holds every
+        return r < H - 1                                        # row, A and B are the same in all of them, and which row a tap reads changes nothing
+    return True
+
+
+@pytest.mark.parametrize("flaw", sorted(FLAWS))
+def test_the_bounds_reject_a_flawed_restatement(flaw, monkeypatch):
+    """Each flaw, in the float32 restatement only (the float64 reference is computed first, from the clean module): in every case that can show
+    it the error exceeds TOL_FACTOR x NAIVE_ERR for at least one (kind, eps); in a case that cannot, the flawed restatement's error is the
+    clean one's, which is what "cannot" means.  A GPU kernel with the same flaw would fail test_stage_against_float64 in the same cases."""
+    shows = {c for c in G.CASES if _can_show(flaw, c)}
+    if flaw == "second_tap_of_every_32nd_column_dropped":
+        assert shows == {"b", "d", "g", "h_row", "j", "k"}      # (h_col delivers 8 columns; case k, DW = 80, does show it)
+    elif flaw == "last_row_one_working_row_early":
+        assert shows == set(G.CASES) - {"a_r9", "d", "h_row"}   # (8 rows under r = 9 and r = 16, and the one-row frame)
+    else:
+        assert shows == set(G.CASES)
+    clean = {}
+    for case, (work, dst, r) in G.CASES.items():
+        for kind in G.KINDS:
+            P, lo, hi = G.inputs(kind, 1, work, dst)
+            for eps in G.EPS:
+                clean[case, kind, eps] = (P, lo, hi, G.stage(P, lo, hi, r, eps))
+    name, value = FLAWS[flaw]()
+    monkeypatch.setattr(G, name, value)
+    worst = {}
+    for (case, kind, eps), (P, lo, hi, ref) in clean.items():
+        err = float(np.abs(G.stage(P, lo, hi, G.CASES[case][2], eps, np.float32).astype(np.float64) - ref).max())
+        if case in shows:
+            worst[case] = max(worst.get(case, 0.0), err / (G.TOL_FACTOR * G.NAIVE_ERR[case, kind, eps]))
+        else:
+            assert float("%.3e" % err) == G.NAIVE_ERR[case, kind, eps], (flaw, case, kind, eps)
+    print(flaw, {c: "%.3g" % v for c, v in sorted(worst.items())})
+    assert set(worst) == shows and all(v > 1.0 for v in worst.values()), (flaw, worst)
 
 
 def test_guide_arguments():
