@@ -76,6 +76,12 @@ const int VGG_IDX[9] = {0, 2, 5, 7, 10, 12, 14, 16, 19};
 const int VGG_CIN[9] = {3, 64, 64, 128, 128, 256, 256, 256, 256};
 const int VGG_COUT[9] = {64, 64, 128, 128, 256, 256, 256, 256, 512};
 const int STYLE_SLICE[9] = {1, 2, 2, 3, 3, 4, 4, 4, 4};
+std::string enc_key(int which, int i) {      // the checkpoint's name of VGG conv i (0..8) of the content (which = 0) / style (1) encoder
+    char k[64];
+    if (which == 0) snprintf(k, sizeof k, "Encoder.slice.%d", VGG_IDX[i]);
+    else snprintf(k, sizeof k, "EncoderStyle.slice%d.%d", STYLE_SLICE[i], VGG_IDX[i]);
+    return k;
+}
 
 struct EncPlan {   // encoder activations for one (B, H, W)
     int B = 0, H = 0, W = 0;
@@ -133,6 +139,16 @@ const TSpec<EncPlan> ENC_T[] = {
     {offsetof(EncPlan, c32), 2, 256}, {offsetof(EncPlan, c33), 2, 256}, {offsetof(EncPlan, p3), 3, 256}, {offsetof(EncPlan, c41), 3, 512},
     {offsetof(EncPlan, q11), 0, 64, TS_P8}, {offsetof(EncPlan, q1), 1, 64, TS_P8}, {offsetof(EncPlan, q21), 1, 128, TS_P8}, {offsetof(EncPlan, q2), 2, 128, TS_P8},
     {offsetof(EncPlan, q31), 2, 256, TS_P8}, {offsetof(EncPlan, q32), 2, 256, TS_P8}, {offsetof(EncPlan, q33), 2, 256, TS_P8},
+};
+// The encoder's 3x3 layers conv1_2 .. conv4_1 (VGG conv 1..8): level (H, W >> level), epilogue, and what the layer reads and writes in the
+// NHWC chain and in the channel-chunk-major one — a P8 twin where the two differ: conv3_4 writes, and conv4_1 reads, the NHWC p3 in either.
+typedef Tens EncPlan::*EncT;
+struct EncLayer { int level, epi; EncT in, out, qin, qout; };
+const EncLayer ENC_LAYERS[8] = {
+    {0, E_RELU | E_POOL, &EncPlan::c11, &EncPlan::p1, &EncPlan::q11, &EncPlan::q1},   {1, E_RELU, &EncPlan::p1, &EncPlan::c21, &EncPlan::q1, &EncPlan::q21},
+    {1, E_RELU | E_POOL, &EncPlan::c21, &EncPlan::p2, &EncPlan::q21, &EncPlan::q2},   {2, E_RELU, &EncPlan::p2, &EncPlan::c31, &EncPlan::q2, &EncPlan::q31},
+    {2, E_RELU, &EncPlan::c31, &EncPlan::c32, &EncPlan::q31, &EncPlan::q32},          {2, E_RELU, &EncPlan::c32, &EncPlan::c33, &EncPlan::q32, &EncPlan::q33},
+    {2, E_RELU | E_POOL, &EncPlan::c33, &EncPlan::p3, &EncPlan::q33, &EncPlan::p3},   {3, E_RELU, &EncPlan::p3, &EncPlan::c41, &EncPlan::p3, &EncPlan::c41},
 };
 const TSpec<DecPlan> DEC_T[] = {
     {offsetof(DecPlan, d), 3, 32}, {offsetof(DecPlan, f[0]), 3, 512}, {offsetof(DecPlan, f[1]), 3, 512}, {offsetof(DecPlan, f[2]), 3, 512}, {offsetof(DecPlan, xs[0]), 3, 256},
@@ -544,85 +560,66 @@ struct ConvCall {
     bool enc_p8 = false;           // an encoder layer of a P8 chain: use_f43 prices it with conv_f43_k's P8-input ratios (run_encoder)
 };
 
-template <int BN, int TAPS, int EPI>
-void conv_launch(const ConvP& p, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((conv_mfma_k<BN, TAPS, EPI>), grid, dim3(256), 0, s, p);
-}
-
 typedef void (*ConvFn)(const ConvP&, dim3, hipStream_t);
 typedef hipError_t (*AttrFn)();       // per-DEVICE opt-in for > 64 KB of dynamic LDS (run by rrv_create after hipSetDevice)
-struct ConvKey { int BN, TAPS, UPS, EPI; ConvFn fn; const char* name; AttrFn attr; ConvFn fn_img = nullptr; };   // fn_img: the per-image-state instantiation, where one exists
-#define CK(BN, TAPS, UPS, EPI) {BN, TAPS, UPS, EPI, &conv_launch<BN, TAPS, EPI>, "conv_mfma<" #BN "," #TAPS "," #EPI ">", nullptr}
-const ConvKey CONV_TABLE[] = {
-    // 1x1 shortcuts of the residual blocks (evaluated before the upsample)
-    CK(128, 1, 0, 0), CK(64, 1, 0, 0),
-    // preparation pass: FilterPredictor 512->32 convs (raw outputs)
-    CK(32, 9, 0, 0),
-    // direct-form encoder layers (RRV_DIRECT_LAYERS, read by rrv_create: accuracy where Decoder.norm[0] amplifies the encoder's rounding noise)
-    CK(64, 9, 0, E_RELU | E_POOL), CK(128, 9, 0, E_RELU), CK(128, 9, 0, E_RELU | E_POOL), CK(128, 9, 0, E_RELU | E_NORM1),
-};
-
-constexpr int WINO_NW = 8;     // waves per Winograd workgroup (conv_wino.h: 8 = two waves per SIMD, one 16-cout block each)
 constexpr int UPW_NW = 4;      // upsample-fused form: 4 waves, 54 KB of LDS, two workgroups per CU (with the shortcut: 154 KB, one, conv_ups5.h)
-template <int NW, int UPS, int SC>
-constexpr int wino_smem() { return SC ? Ups5Geo::SMEM : WinoGeo<NW, UPS>::SMEM; }
-template <int EPI, int NW, int UPS, int SC, int PERIMG = 0>
-void wino_launch(const ConvP& p, dim3 grid, hipStream_t s) {
-    constexpr int smem = wino_smem<NW, UPS, SC>();
-    hipLaunchKernelGGL((conv_wino_k<EPI, 0, NW, UPS, SC, PERIMG>), grid, dim3(NW * 64), smem, s, p);
-}
-template <int EPI, int NW, int UPS, int SC, int PERIMG = 0>
-hipError_t wino_attr() {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_smem<NW, UPS, SC>());
-    if (e == hipSuccess && PERIMG) e = hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, NW, UPS, SC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_smem<NW, UPS, SC>());
-    return e;
-}
-template <int EPI, int PERIMG>
-void wsplit_launch(const ConvP& p, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((conv_wino_split_k<EPI, PERIMG>), grid, dim3(512), WSPLIT_SMEM_BYTES, s, p);
-}
-template <int EPI, int PERIMG>
-hipError_t wsplit_attr() {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_split_k<EPI, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, WSPLIT_SMEM_BYTES);
-    if (e == hipSuccess && PERIMG) e = hipFuncSetAttribute((const void*)conv_wino_split_k<EPI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WSPLIT_SMEM_BYTES);
-    return e;
-}
-template <int EPI, int LAY = 0>
-void f43_launch(const ConvP& p, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((conv_f43_k<EPI, LAY>), grid, dim3(F43Geo::NT), F43Geo::SMEM, s, p);
-}
-template <int EPI, int LAY = 0>
-hipError_t f43_attr() { return hipFuncSetAttribute((const void*)conv_f43_k<EPI, LAY>, hipFuncAttributeMaxDynamicSharedMemorySize, F43Geo::SMEM); }
-#define FK(EPI) {32, 9, 0, EPI, &f43_launch<EPI>, "conv_f43<" #EPI ">", &f43_attr<EPI>, nullptr}
-// the same kernels on channel-chunk-major tensors (conv_f43.h LAY: bit 0 input, bit 1 output): the instantiations the per-frame path uses
-struct F43LayKey { int EPI, LAY; ConvFn fn; const char* name; AttrFn attr; };
-#define FKL(EPI, LAY) {EPI, LAY, &f43_launch<EPI, LAY>, "conv_f43<" #EPI ", " #LAY ">", &f43_attr<EPI, LAY>}
-// F(4x4,3x3): the same-resolution 3x3 layers of the per-frame path with Cin, Cout >= 64, when the launch carries enough
-// frames (conv()).  3-6x the rounding error of F(2x2,3x3) and 1.13-1.22x its rate at 8 frames per launch.
-#define WK(EPI) {32, 9, 0, EPI, &wsplit_launch<EPI, 0>, "conv_wino<" #EPI ">", &wsplit_attr<EPI, 0>, nullptr}
-// decoder layers: also instantiated with per-image state (grouped multi-style launches)
-#define WKI(EPI) {32, 9, 0, EPI, &wsplit_launch<EPI, 0>, "conv_wino<" #EPI ">", &wsplit_attr<EPI, 1>, &wsplit_launch<EPI, 1>}
-#define UW(EPI) {32, 9, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 0>, "conv_upw<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 0>}
-#define UWS(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1>}
-#define UWSI(EPI) {32, 29, 1, EPI, &wino_launch<EPI, UPW_NW, 1, 1>, "conv_upw_sc<" #EPI ">", &wino_attr<EPI, UPW_NW, 1, 1, 1>, &wino_launch<EPI, UPW_NW, 1, 1, 1>}
-const ConvKey WINO_TABLE[] = {
-    WK(E_RELU), WK(E_RELU | E_POOL), WKI(E_RELU | E_NORM1) /* conv4_1 + Decoder.norm[0]; per image: blended frames */, WKI(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2), WKI(E_LRELU),      // (E_LRELU per image: filter_down of a batched frame-mode launch without split K)
-    WKI(0),     // raw partial sums of a split-K launch
-    // KernelFilter 32->512 convs with the folded dynamic filter (+ residual, + AdaIN after Filter3)
-    WKI(E_RES), WKI(E_RES | E_NORM2),
-    // ResidualBlock.conv1 behind the nearest-x2 upsample (forward pass / preparation pass)
-    UW(E_LRELU | E_NORM1), UW(E_LRELU),
-    // the same with the block's 1x1 shortcut fused in: five-product form, 25 + 4 positions per 2x2 input pixels (per-frame path)
-    UWSI(E_LRELU | E_NORM1),
-    // frame mode: raw conv1 output (its statistics are per frame) + fused shortcut
-    UWS(E_LRELU),
-};
 
-const ConvKey F43_TABLE[] = { FK(E_RELU), FK(E_RELU | E_POOL), FK(E_RELU | E_NORM1), FK(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2) };
-const F43LayKey F43_LAY_TABLE[] = {
-    FKL(E_RELU | E_POOL, 3), FKL(E_RELU, 3),      // conv1_2, conv2_2 / conv2_1, conv3_1 .. conv3_3: P8 in, P8 out
-    FKL(E_RELU | E_POOL, 1),                      // conv3_4: P8 in, NHWC out (conv4_1 runs the row-split kernel)
-    FKL(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 1),      // ResidualBlock.conv2: P8 in (written by the upsample-fused conv1), NHWC out
+// The four kernel families, each with its launch and (where it needs > 64 KB of LDS) its attribute function — of ONE instantiation each
+template <int BN, int TAPS, int EPI>
+void mfma_launch(const ConvP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv_mfma_k<BN, TAPS, EPI>), grid, dim3(256), 0, s, p); }
+template <int EPI, int IMG>
+void wsplit_launch(const ConvP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv_wino_split_k<EPI, IMG>), grid, dim3(512), WSPLIT_SMEM_BYTES, s, p); }
+template <int EPI, int IMG>
+hipError_t wsplit_attr() { return hipFuncSetAttribute((const void*)conv_wino_split_k<EPI, IMG>, hipFuncAttributeMaxDynamicSharedMemorySize, WSPLIT_SMEM_BYTES); }
+template <int SC>
+constexpr int upw_smem() { return SC ? Ups5Geo::SMEM : WinoGeo<UPW_NW, 1>::SMEM; }
+template <int EPI, int SC, int IMG>
+void upw_launch(const ConvP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv_wino_k<EPI, 0, UPW_NW, 1, SC, IMG>), grid, dim3(UPW_NW * 64), upw_smem<SC>(), s, p); }
+template <int EPI, int SC, int IMG>
+hipError_t upw_attr() { return hipFuncSetAttribute((const void*)conv_wino_k<EPI, 0, UPW_NW, 1, SC, IMG>, hipFuncAttributeMaxDynamicSharedMemorySize, upw_smem<SC>()); }
+template <int EPI, int LAY>
+void f43_launch(const ConvP& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv_f43_k<EPI, LAY>), grid, dim3(F43Geo::NT), F43Geo::SMEM, s, p); }
+template <int EPI, int LAY>
+hipError_t f43_attr() { return hipFuncSetAttribute((const void*)conv_f43_k<EPI, LAY>, hipFuncAttributeMaxDynamicSharedMemorySize, F43Geo::SMEM); }
+
+// One row per launchable instantiation: what selects it (choose_conv), then what launches it.  A row exists only for a kernel
+// some caller reaches, so the library holds no other (tests/kernel_ledger.py).
+//   MFMA  conv_mfma_k        direct-form implicit GEMM, keyed by the layer's BN / TAPS as well
+//   WINO  conv_wino_split_k  F(2x2,3x3), row-split: every 3x3 layer with a transform-domain pack
+//   UPW   conv_wino_k        the upsample-fused form; SC: with the block's 1x1 shortcut fused in (five-product form, 25 + 4 positions per 2x2 input pixels)
+//   F43   conv_f43_k         F(4x4,3x3) where use_f43 says so; LAY: channel-chunk-major tensors (conv_f43.h: bit 0 input, bit 1 output)
+// IMG: the instantiation that reads per-image state (grouped multi-style launches, blended frames); conv_f43_k reads par_bstride itself.
+enum ConvFam { MFMA, WINO, UPW, F43 };
+struct ConvRow { ConvFam fam; int BN, TAPS, EPI, SC, LAY, IMG; ConvFn fn; AttrFn attr; const char* name; };
+#define MF(BN, TAPS, EPI) {MFMA, BN, TAPS, EPI, 0, 0, 0, &mfma_launch<BN, TAPS, EPI>, nullptr, "conv_mfma<" #BN "," #TAPS "," #EPI ">"}
+#define WS(EPI, IMG) {WINO, 32, 9, EPI, 0, 0, IMG, &wsplit_launch<EPI, IMG>, &wsplit_attr<EPI, IMG>, "conv_wino<" #EPI ">"}
+#define UP(EPI, SC, IMG) {UPW, 32, SC ? 29 : 9, EPI, SC, 0, IMG, &upw_launch<EPI, SC, IMG>, &upw_attr<EPI, SC, IMG>, SC ? "conv_upw_sc<" #EPI ">" : "conv_upw<" #EPI ">"}
+#define F4(EPI, LAY) {F43, 32, 9, EPI, 0, LAY, 0, &f43_launch<EPI, LAY>, &f43_attr<EPI, LAY>, LAY ? "conv_f43<" #EPI ", " #LAY ">" : "conv_f43<" #EPI ">"}
+const ConvRow CONV_ROWS[] = {
+    // 1x1 shortcuts of the residual blocks (evaluated before the upsample)
+    MF(128, 1, 0), MF(64, 1, 0),
+    // preparation pass: FilterPredictor 512->32 convs (raw outputs)
+    MF(32, 9, 0),
+    // direct-form encoder layers (RRV_DIRECT_LAYERS, read by rrv_create: accuracy where Decoder.norm[0] amplifies the encoder's rounding noise)
+    MF(64, 9, E_RELU | E_POOL), MF(128, 9, E_RELU), MF(128, 9, E_RELU | E_POOL), MF(128, 9, E_RELU | E_NORM1),
+    // encoder layers
+    WS(E_RELU, 0), WS(E_RELU | E_POOL, 0),
+    // decoder layers, also with per-image state: conv4_1 + Decoder.norm[0] (per image: blended frames), ResidualBlock.conv2,
+    // filter_down (per image: a batched frame-mode launch without split K), the raw partial sums of a split-K launch
+    WS(E_RELU | E_NORM1, 0), WS(E_RELU | E_NORM1, 1), WS(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 0), WS(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 1),
+    WS(E_LRELU, 0), WS(E_LRELU, 1), WS(0, 0), WS(0, 1),
+    // KernelFilter 32->512 convs with the folded dynamic filter (+ residual, + AdaIN after Filter3)
+    WS(E_RES, 0), WS(E_RES, 1), WS(E_RES | E_NORM2, 0), WS(E_RES | E_NORM2, 1),
+    // ResidualBlock.conv1 behind the nearest-x2 upsample (forward pass / preparation pass)
+    UP(E_LRELU, 0, 0),
+    // the same with the block's shortcut fused in (per-frame path); frame mode: raw conv1 output (its statistics are per frame)
+    UP(E_LRELU | E_NORM1, 1, 0), UP(E_LRELU | E_NORM1, 1, 1), UP(E_LRELU, 1, 0),
+    // F(4x4,3x3): the same-resolution 3x3 layers of the per-frame path with Cin, Cout >= 64, when the launch carries enough
+    // frames (use_f43).  3-6x the rounding error of F(2x2,3x3) and 1.13-1.22x its rate at 8 frames per launch.
+    F4(E_RELU, 0), F4(E_RELU | E_POOL, 0), F4(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 0),
+    F4(E_RELU | E_POOL, 3), F4(E_RELU, 3),      // conv1_2, conv2_2 / conv2_1, conv3_1 .. conv3_3: P8 in, P8 out
+    F4(E_RELU | E_POOL, 1),                     // conv3_4: P8 in, NHWC out (conv4_1 runs the row-split kernel)
+    F4(E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, 1),      // ResidualBlock.conv2: P8 in (written by the upsample-fused conv1), NHWC out
 };
 
 // Persistent workgroups of a transform-domain launch: `occ` per CU, on the 1/share of the CUs this sequence may use
@@ -646,8 +643,12 @@ unsigned resident_wgs(rrv_handle h, const Seq& q, int occ) {
 // frames in small batches.  The rule depends on the layer, the batch and the frame size only (not on what else is in
 // flight): the same call always makes the same choice.
 // enc_p8: price an encoder layer with the P8-input ratios (the chain is P8 only as a whole: run_encoder asks so first and falls back to the NHWC ones)
-bool use_f43(rrv_handle h, const Seq& q, const ConvW& w, int B, int H, int W, int epi, bool ups, int ksplit, bool per_image, bool enc_p8 = false) {
-    if (!q.f43 || !w.pk_f43 || !((h->f43_layers >> w.f43_bit) & 1u) || ups || ksplit > 1 || per_image || h->f43_mode == 0) return false;
+// Everything comes from the call that will be launched, and no tensor is read: a caller may ask before `in` / `out` are bound.
+bool use_f43(rrv_handle h, const Seq& q, const ConvCall& c) {
+    const ConvW& w = *c.w;
+    const bool per_image = c.bias_bstride != 0 || c.w_bstride != 0;      // per-image PARAMETERS are conv_f43_k's too (par_bstride); per-image bias / weights (the folded KernelFilter convs) are not
+    if (c.direct || ((c.wy0 | c.wx0 | c.wy1 | c.wx1) & 31)) return false;      // 32 x 32 pixel work items: a window must be aligned to them
+    if (!q.f43 || !w.pk_f43 || !((h->f43_layers >> w.f43_bit) & 1u) || c.ups || c.ksplit > 1 || per_image || h->f43_mode == 0) return false;
     if (h->f43_mode == 2) return true;
     // Ill-conditioned state (filter_conditioning): the decoder multiplies whatever error the encoder makes, and F(4x4,3x3) on the
     // seven encoder layers makes 1.4x the error of F(2x2,3x3) (profiles/r05_parity_margin.txt: the x4-decoder weight set goes from
@@ -656,89 +657,98 @@ bool use_f43(rrv_handle h, const Seq& q, const ConvW& w, int B, int H, int W, in
     const double R = (double)resident_wgs(h, q, 1);      // persistent workgroups of this launch: one per CU the handle may use (rrv_create: device CU count under HSA_CU_MASK / RRV_CUS; rrv_set_grid_share / look-ahead tickets: a share of them)
     auto rounds = [&](double items) { return std::ceil(items / R); };
     const double slabs = w.Cout / 32;
-    const double items43 = (double)((H + 31) / 32) * ((W + 31) / 32) * B * slabs, items23 = (double)((H + 15) / 16) * ((W + 15) / 16) * B * slabs;
+    const double items43 = (double)((c.H + 31) / 32) * ((c.W + 31) / 32) * c.B * slabs, items23 = (double)((c.H + 15) / 16) * ((c.W + 15) / 16) * c.B * slabs;
     const int ci = w.Cin >= 256 ? 2 : (w.Cin >= 128 ? 1 : 0);
     static const double BASE_POOL[3] = {1.33, 1.38, 1.41}, BASE_RELU[3] = {1.29, 1.35, 1.39}, BASE_RES[3] = {1.26, 1.33, 1.38};      // round 5 (profiles/r05_f43_timeline.txt, F43_DMA=6)
     // round 6: with its input channel-chunk-major conv_f43_k is 12 % faster (run_encoder / resblock_frame feed it that way whenever the
     // consumer runs conv_f43_k; the ReLU layers also WRITE it, 32-byte pieces: profiles/r06_f43_layout.txt, tools/f43_bench.hip -DF43_LAY=1 / 3)
     static const double P8_POOL[3] = {1.47, 1.53, 1.56}, P8_RELU[3] = {1.36, 1.44, 1.52}, P8_RES[3] = {1.41, 1.48, 1.53};
-    const bool p8 = w.f43_bit < 7 ? enc_p8 : (h->p8 & 2) != 0;
-    const double base = (epi & E_POOL) ? (p8 ? P8_POOL : BASE_POOL)[ci] : (epi & E_RES_UPS) ? (p8 ? P8_RES : BASE_RES)[ci] : (p8 ? P8_RELU : BASE_RELU)[ci];
+    const bool p8 = w.f43_bit < 7 ? c.enc_p8 : (h->p8 & 2) != 0;
+    const double base = (c.epi & E_POOL) ? (p8 ? P8_POOL : BASE_POOL)[ci] : (c.epi & E_RES_UPS) ? (p8 ? P8_RES : BASE_RES)[ci] : (p8 ? P8_RELU : BASE_RELU)[ci];
     return rounds(items23) >= 1.04 * rounds(items43) * 4.0 / base;
 }
 
-int conv(rrv_handle h, const Seq& q, const ConvCall& c) {
+inline bool per_image_state(const ConvCall& c) { return (c.par_bstride | c.bias_bstride) != 0 || c.w_bstride != 0; }
+inline int conv_ksplit(const ConvCall& c) { return c.ksplit > 1 ? c.ksplit : 1; }
+
+const ConvRow* conv_row(ConvFam fam, const ConvCall& c, bool sc, int lay, bool img) {
+    for (const ConvRow& e : CONV_ROWS)
+        if (e.fam == fam && e.EPI == c.epi && e.SC == (int)sc && e.LAY == lay && e.IMG == (int)img && (fam != MFMA || (e.BN == c.w->BN && e.TAPS == c.w->taps))) return &e;
+    return nullptr;
+}
+
+// The kernel that runs this call: its row of CONV_ROWS, or null with the refusal in `why`.  Like use_f43 it reads the call and the
+// layer's packs, never a tensor.  F(4x4,3x3) where use_f43 says so, else the layer's transform-domain form where it has the pack,
+// else the direct form.
+const ConvRow* choose_conv(rrv_handle h, const Seq& q, const ConvCall& c, std::string& why) {
     const ConvW& w = *c.w;
-    const ConvKey* k = nullptr;
-    bool wino = false;
-    bool f43 = !c.direct && use_f43(h, q, w, c.B, c.H, c.W, c.epi, c.ups, c.ksplit, c.bias_bstride != 0 || c.w_bstride != 0, c.enc_p8) &&      // per-image PARAMETERS are conv_f43_k's too (par_bstride); per-image bias / weights (the folded KernelFilter convs) are not
-               !((c.wy0 | c.wx0 | c.wy1 | c.wx1) & 31);      // 32 x 32 pixel work items: a window must be aligned to them
-    if (f43) {
-        f43 = false;
-        for (const ConvKey& e : F43_TABLE)
-            if (e.EPI == c.epi) { k = &e; f43 = true; wino = true; break; }
+    const bool fuse_sc = c.ups && c.sc_out != nullptr, img = per_image_state(c);
+    const int lay = (c.in_p8 ? 1 : 0) | (c.out_p8 ? 2 : 0);
+    const bool ups_p8 = lay == 2 && c.ups;      // the upsample-fused kernel writes a P8 tensor through ConvP::out_p8 (no separate instantiation)
+    auto refuse = [&](const char* text) { why = text; return nullptr; };
+    if (fuse_sc && !w.pk_ups_sc) return refuse("conv: no shortcut-fused pack for this layer");
+    const ConvRow* k = nullptr;
+    bool no_img = false;
+    if (use_f43(h, q, c)) {      // (an epilogue conv_f43_k does not have in any layout: the F(2x2,3x3) form)
+        k = conv_row(F43, c, false, lay, false);
+        if (!k && lay && conv_row(F43, c, false, 0, false)) return refuse("conv: no conv_f43_k instantiation for this layout");
     }
-    const bool fuse_sc = c.ups && c.sc_out != nullptr;
-    if (fuse_sc && !w.pk_ups_sc) return fail(h, RRV_E_ARG, "conv: no shortcut-fused pack for this layer");
-    if (!f43 && !c.direct && (c.ups ? w.pk_ups != nullptr : w.pk_wino != nullptr)) {      // every 3x3 layer with a transform-domain pack runs conv_wino_k
-        for (const ConvKey& e : WINO_TABLE)
-            if (e.EPI == c.epi && e.UPS == (int)c.ups && (e.TAPS == 29) == fuse_sc) { k = &e; wino = true; break; }
+    if (!k && !c.direct && (c.ups ? w.pk_ups != nullptr : w.pk_wino != nullptr)) {      // every 3x3 layer with a transform-domain pack runs its Winograd form
+        const ConvFam fam = c.ups ? UPW : WINO;
+        k = conv_row(fam, c, fuse_sc, 0, img);
+        if (!k && img) { k = conv_row(fam, c, fuse_sc, 0, false); no_img = k != nullptr; }      // (refused below, behind the refusals that came first)
     }
-    const int ks = c.ksplit > 1 ? c.ksplit : 1;
-    if (ks > 1 && !(wino && !c.ups && w.Cout == 32 && (w.Cin % (32 * ks)) == 0 && c.bias))
-        return fail(h, RRV_E_ARG, "conv: split K needs the row-split kernel, a 32-cout layer, an even number of 16-channel chunks per slice and a split bias");
-    if (!k && !c.ups) {
-        for (const ConvKey& e : CONV_TABLE)
-            if (e.BN == w.BN && e.TAPS == w.taps && e.EPI == c.epi) { k = &e; break; }
-    }
+    const bool wino = k != nullptr;
+    if (c.ksplit > 1 && !(wino && !c.ups && w.Cout == 32 && (w.Cin % (32 * c.ksplit)) == 0 && c.bias))
+        return refuse("conv: split K needs the row-split kernel, a 32-cout layer, an even number of 16-channel chunks per slice and a split bias");
+    if (!k && !c.ups) k = conv_row(MFMA, c, false, 0, false);
     if (!k) {
         char b[128];
         snprintf(b, sizeof b, "no conv kernel for BN=%d taps=%d ups=%d epi=%d", w.BN, w.taps, (int)c.ups, c.epi);
-        return fail(h, RRV_E_ARG, b);
+        return refuse(b);
     }
-    const int lay = (c.in_p8 ? 1 : 0) | (c.out_p8 ? 2 : 0);
-    ConvFn lay_fn = nullptr;
-    const char* lay_name = nullptr;
-    const bool ups_p8 = lay == 2 && c.ups;      // the upsample-fused kernel writes a P8 tensor through ConvP::out_p8 (no separate instantiation)
-    if (lay && !ups_p8) {
-        if (!f43) return fail(h, RRV_E_ARG, "conv: channel-chunk-major tensors are conv_f43_k's");
-        for (const F43LayKey& e : F43_LAY_TABLE)
-            if (e.EPI == c.epi && e.LAY == lay) { lay_fn = e.fn; lay_name = e.name; }
-        if (!lay_fn) return fail(h, RRV_E_ARG, "conv: no conv_f43_k instantiation for this layout");
-    }
-    ConvP p{};
+    if (lay && !ups_p8 && k->fam != F43) return refuse("conv: channel-chunk-major tensors are conv_f43_k's");
+    if (ups_p8 && !wino) return refuse("conv: no upsample-fused kernel for this layer");
+    if (img && !wino) return refuse("conv: per-image state needs a transform-domain kernel");
+    if (c.ups && (c.bias_bstride || c.w_bstride)) return refuse("conv: the upsample-fused kernel shares weights and bias over the images of a launch");
+    if (no_img) return refuse("conv: this layer has no per-image-state kernel");
+    return k;
+}
+
+// The launch parameters of call `c` on row `k`, the geometry of its tensors checked.  win_frac: the part of the (tile-rounded) frame the window computes
+int conv_params(rrv_handle h, const ConvCall& c, const ConvRow& k, ConvP& p, double& win_frac) {
+    const ConvW& w = *c.w;
+    const bool wino = k.fam != MFMA, f43 = k.fam == F43, fuse_sc = k.SC != 0;
+    const int ks = conv_ksplit(c);
     p.in = c.in->p; p.Hi = c.in->H; p.Wi = c.in->W - (c.in_p8 ? 6 : 0); p.Cin = w.Cin;
     p.out = c.out->p; p.H = c.H; p.W = c.W; p.Cout = w.Cout; p.B = c.B;
     p.in_bstride0 = 1;
-    p.wpk = f43 ? w.pk_f43 : wino ? (c.ups ? (fuse_sc ? w.pk_ups_sc : w.pk_ups) : w.pk_wino) : w.pk; p.bias = w.bias;
+    p.wpk = f43 ? w.pk_f43 : k.fam == UPW ? (fuse_sc ? w.pk_ups_sc : w.pk_ups) : wino ? w.pk_wino : w.pk; p.bias = w.bias;
     if (fuse_sc) {
         if (c.sc_out->H != c.in->H || c.sc_out->W != c.in->W || c.sc_out->C != w.Cout) return fail(h, RRV_E_ARG, "conv: shortcut output geometry mismatch");
         p.sc_out = c.sc_out->p;
     }
-    if (!p.wpk) return fail(h, RRV_E_ARG, "conv: weights not packed for this kernel"); p.n1 = c.n1; p.n2 = c.n2; p.sty = c.sty;
+    if (!p.wpk) return fail(h, RRV_E_ARG, "conv: weights not packed for this kernel");
+    p.n1 = c.n1; p.n2 = c.n2; p.sty = c.sty;
     if (c.bias) p.bias = c.bias;
     p.par_bstride = c.par_bstride; p.bias_bstride = c.bias_bstride; p.w_bstride = c.w_bstride;
-    if (ups_p8) { if (!wino) return fail(h, RRV_E_ARG, "conv: no upsample-fused kernel for this layer"); p.out_p8 = 1; }
-    if ((c.par_bstride | c.bias_bstride || c.w_bstride) && !wino) return fail(h, RRV_E_ARG, "conv: per-image state needs a transform-domain kernel");
-    if (c.ups && (c.bias_bstride || c.w_bstride)) return fail(h, RRV_E_ARG, "conv: the upsample-fused kernel shares weights and bias over the images of a launch");
+    if (c.out_p8 && c.ups) p.out_p8 = 1;
     if (ks > 1) {       // the [1 slab][Cin/16 chunks] weight pack read as [ks slabs][Cin/16/ks chunks]: slab s = input channel slice s
         p.Cin = w.Cin / ks; p.cstride = w.Cin; p.cin_slab_step = w.Cin / ks; p.Cout = 32 * ks;
     }
     if (c.res) { p.res = c.res->p; p.Hr = c.res->H; p.Wr = c.res->W; }
-    p.tiles_x = (c.W + 15) / 16; p.tiles_y = (c.H + 7) / 8;
     if ((c.in_p8 ? c.in->C != 8 || c.in->B < c.B * (w.Cin / 8) : c.in->C != w.Cin) ||
         (c.out_p8 ? c.out->C != 8 || c.out->B < c.B * (w.Cout / 8) : c.out->C != w.Cout * ks)) return fail(h, RRV_E_ARG, "conv: channel mismatch");
     const int eh = c.ups ? c.H / 2 : c.H, ew = c.ups ? c.W / 2 : c.W;
     if (c.in->H != eh || c.in->W != ew + (c.in_p8 ? 6 : 0)) return fail(h, RRV_E_ARG, "conv: input geometry mismatch");      // (a P8 twin is 6 pixels wider: conv_f43.h P8_PAD)
     const int oh = (c.epi & E_POOL) ? c.H / 2 : c.H, ow = (c.epi & E_POOL) ? c.W / 2 : c.W;
     if (c.out->H != oh || c.out->W != ow + (c.out_p8 ? 6 : 0)) return fail(h, RRV_E_ARG, "conv: output geometry mismatch");
-    const int TS = f43 || fuse_sc ? 32 : 16;             // pixel tile edge of a work item
-    if (wino) { p.tiles_x = (c.W + TS - 1) / TS; p.tiles_y = (c.H + TS - 1) / TS; }
-    double win_frac = 1.0;
+    const int TS = f43 || fuse_sc ? 32 : 16, TY = wino ? TS : 8;             // pixel tile edge of a work item (the direct form: 16 x 8)
+    p.tiles_x = (c.W + TS - 1) / TS; p.tiles_y = (c.H + TY - 1) / TY;
     if (wino && c.wy1 > c.wy0 && c.wx1 > c.wx0) {      // output window (on-device crop: nothing outside it is ever read)
         if ((c.wy0 | c.wx0 | c.wy1 | c.wx1) & 15) return fail(h, RRV_E_ARG, "conv: window must be tile aligned");
         int wy0 = c.wy0, wx0 = c.wx0, wy1 = c.wy1, wx1 = c.wx1;
-        if (TS == 32 && !f43) {      // shortcut-fused conv1: round the window out to its 32 x 32 items (the extra outputs are exact)
+        if (fuse_sc) {      // shortcut-fused conv1: round the window out to its 32 x 32 items (the extra outputs are exact)
             wy0 &= ~31; wx0 &= ~31; wy1 = (wy1 + 31) & ~31; wx1 = (wx1 + 31) & ~31;
             if (wy1 > ((c.H + 31) & ~31)) wy1 = (c.H + 31) & ~31;
             if (wx1 > ((c.W + 31) & ~31)) wx1 = (c.W + 31) & ~31;
@@ -748,41 +758,54 @@ int conv(rrv_handle h, const Seq& q, const ConvCall& c) {
         const int TD = fuse_sc ? 32 : 16;          // the shortcut-fused form computes the rounded window's tiles
         win_frac = ((double)(wy1 - wy0) * (wx1 - wx0)) / ((double)((c.H + TD - 1) / TD * TD) * ((c.W + TD - 1) / TD * TD));
     }
-    dim3 grid((unsigned)(p.tiles_x * p.tiles_y * c.B), (unsigned)(w.Cout / w.BN));
-    if (wino) {   // persistent workgroups (one per CU; two for the upsample-fused form), walking tiles_x*tiles_y*B*(Cout/32) work items
-        const unsigned slabs = (unsigned)(w.Cout / 32) * ks;
-        const unsigned items = (unsigned)(p.tiles_x * p.tiles_y * c.B) * slabs;
-        const unsigned resident = resident_wgs(h, q, fuse_sc ? Ups5Geo::OCC : c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
-        grid = dim3(items < resident ? items : resident, 1);
-        // slabs of one pixel tile on one XCD (workgroup w runs on XCD w % 8): the raw tile is fetched once per XCD group
-        p.xcd_slabs = (grid.x % 8 == 0 && (grid.x / 8) % slabs == 0) ? 1 : 0;
-    }
-    const double px = (double)c.B * c.H * c.W * win_frac;
-    // algorithmic FLOPs = the reference's direct convolution (taps multiply-adds per output);
-    // executed: Winograd F(2x2,3x3) needs 16 multiplies per 2x2 outputs (4 per pixel), F(4x4,3x3) 36 per 4x4 (2.25 per pixel), the upsample-fused form 9 (2.25 per pixel)
-    // (with the fused shortcut the five-product form: 25 + 4 positions per 4x4 outputs, 29/16 per output pixel)
-    const double cin = w.Cin;
+    return RRV_OK;
+}
+
+// The grid of the launch; a transform-domain launch also learns here whether the slabs of one pixel tile share an XCD (ConvP::xcd_slabs)
+dim3 conv_grid(rrv_handle h, const Seq& q, const ConvCall& c, const ConvRow& k, ConvP& p) {
+    const ConvW& w = *c.w;
+    if (k.fam == MFMA) return dim3((unsigned)(p.tiles_x * p.tiles_y * c.B), (unsigned)(w.Cout / w.BN));
+    // persistent workgroups (one per CU; two for the upsample-fused form), walking tiles_x*tiles_y*B*(Cout/32) work items
+    const unsigned slabs = (unsigned)(w.Cout / 32) * conv_ksplit(c);
+    const unsigned items = (unsigned)(p.tiles_x * p.tiles_y * c.B) * slabs;
+    const unsigned resident = resident_wgs(h, q, k.SC ? Ups5Geo::OCC : c.ups ? WinoGeo<UPW_NW, 1>::OCC : 1);      // rrv_set_grid_share leaves CUs to the launches of the other stream(s)
+    const unsigned gx = items < resident ? items : resident;
+    // slabs of one pixel tile on one XCD (workgroup w runs on XCD w % 8): the raw tile is fetched once per XCD group
+    p.xcd_slabs = (gx % 8 == 0 && (gx / 8) % slabs == 0) ? 1 : 0;
+    return dim3(gx, 1);
+}
+
+// What the profile files with the launch.  flops: algorithmic = the reference's direct convolution (taps multiply-adds per output).
+// flops_exec: Winograd F(2x2,3x3) needs 16 multiplies per 2x2 outputs (4 per pixel), F(4x4,3x3) 36 per 4x4 (2.25 per pixel), the upsample-fused
+// form 9 (2.25 per pixel) (with the fused shortcut the five-product form: 25 + 4 positions per 4x4 outputs, 29/16 per output pixel)
+struct ConvCost { double flops, flops_exec, bytes; };
+ConvCost conv_cost(const ConvCall& c, const ConvRow& k, double win_frac) {
+    const ConvW& w = *c.w;
+    const bool fuse_sc = k.SC != 0;
+    const double px = (double)c.B * c.H * c.W * win_frac, cin = w.Cin, in_px = (double)c.B * c.in->H * c.in->W;
+    const int oh = (c.epi & E_POOL) ? c.H / 2 : c.H, ow = (c.epi & E_POOL) ? c.W / 2 : c.W;
     const double flops_sc = fuse_sc ? 2.0 * c.B * c.in->H * c.in->W * (double)w.Cout * cin : 0.0;
-    const double flops = 2.0 * px * w.Cout * cin * w.taps + flops_sc;
-    const double flops_exec = 2.0 * px * w.Cout * cin * (f43 ? 2.25 : wino ? (c.ups ? (fuse_sc ? 29.0 / 16.0 : 2.25) : 4.0) : (double)w.taps);
-    const double bytes = 4.0 * ((double)c.B * c.in->H * c.in->W * cin + (double)c.B * oh * ow * w.Cout +
-                                (c.res ? (double)c.B * c.res->H * c.res->W * w.Cout : 0.0) + (double)w.Cout * cin * w.taps +
-                                (fuse_sc ? (double)c.B * c.in->H * c.in->W * w.Cout + (double)w.Cout * cin : 0.0));
-    hipStream_t s = q.stream;
-    ConvFn fn = lay_fn ? lay_fn : k->fn;
-    if (wino && !f43 && (c.par_bstride | c.bias_bstride || c.w_bstride)) {      // per-image state is a separate instantiation of the F(2x2,3x3) / upsample-fused kernels (conv_f43_k reads par_bstride itself)
-        if (!k->fn_img) return fail(h, RRV_E_ARG, "conv: this layer has no per-image-state kernel");
-        fn = k->fn_img;
-    }
+    const double per_px = k.fam == F43 ? 2.25 : k.fam == UPW ? (fuse_sc ? 29.0 / 16.0 : 2.25) : k.fam == WINO ? 4.0 : (double)w.taps;
+    return {2.0 * px * w.Cout * cin * w.taps + flops_sc, 2.0 * px * w.Cout * cin * per_px,
+            4.0 * (in_px * cin + (double)c.B * oh * ow * w.Cout + (c.res ? (double)c.B * c.res->H * c.res->W * w.Cout : 0.0) + (double)w.Cout * cin * w.taps +
+                   (fuse_sc ? in_px * w.Cout + (double)w.Cout * cin : 0.0))};
+}
+
+int conv(rrv_handle h, const Seq& q, const ConvCall& c) {
+    std::string why;
+    const ConvRow* k = choose_conv(h, q, c, why);
+    if (!k) return fail(h, RRV_E_ARG, why);
+    ConvP p{};
+    double win_frac = 1.0;
+    RCHK(conv_params(h, c, *k, p, win_frac));
+    const dim3 grid = conv_grid(h, q, c, *k, p);
+    const ConvCost cost = conv_cost(c, *k, win_frac);
     stamp(h, c.out, c.B);
-    if (fuse_sc) stamp(h, c.sc_out, c.B);
-    const int xcd = wino ? p.xcd_slabs : -1;
-    if (h->profiling) {   // "<kernel>@CinxCout@HxW": bench.py groups by the part before '@'
-        char nm[160];
-        snprintf(nm, sizeof nm, "%s@%dx%d@%dx%d", lay_name ? lay_name : k->name, w.Cin, w.Cout, c.H, c.W);
-        return launch(h, q, nm, flops, bytes, [&] { fn(p, grid, s); }, flops_exec, grid.x, xcd);
-    }
-    return launch(h, q, lay_name ? lay_name : k->name, flops, bytes, [&] { fn(p, grid, s); }, flops_exec, grid.x, xcd);
+    if (k->SC) stamp(h, c.sc_out, c.B);
+    char nm[160];
+    if (h->profiling) snprintf(nm, sizeof nm, "%s@%dx%d@%dx%d", k->name, c.w->Cin, c.w->Cout, c.H, c.W);      // "<kernel>@CinxCout@HxW": bench.py groups by the part before '@'
+    const hipStream_t s = q.stream;
+    return launch(h, q, h->profiling ? nm : k->name, cost.flops, cost.bytes, [&] { k->fn(p, grid, s); }, cost.flops_exec, grid.x, k->fam != MFMA ? p.xcd_slabs : -1);
 }
 
 // ---- weights ----------------------------------------------------------------------------
@@ -1064,25 +1087,22 @@ int run_encoder(rrv_handle h, const Seq& q, EncPlan& e, const uint8_t* d_img, In
     const int H = e.H, W = e.W, B = nb;
     if (nb < 1 || nb > e.B) return fail(h, RRV_E_ARG, "run_encoder: batch does not fit the plan");
     RCHK(check_image_size(h, H, W, "encoder"));
-    auto W_ = [&](int i) -> const ConvW* {
-        char k[64];
-        if (which == 0) snprintf(k, sizeof k, "Encoder.slice.%d", VGG_IDX[i]);
-        else snprintf(k, sizeof k, "EncoderStyle.slice%d.%d", STYLE_SLICE[i], VGG_IDX[i]);
-        return &h->conv[k];
-    };
     auto D_ = [&](int i) { return which == 0 && q.f43 && ((h->direct_layers >> i) & 1u) != 0; };
+    auto call = [&](int i, bool p8) {      // the call of VGG conv i (1..8) in the NHWC or the P8 chain
+        const EncLayer& l = ENC_LAYERS[i - 1];
+        ConvCall k{&(e.*(p8 ? l.qin : l.in)), &(e.*(p8 ? l.qout : l.out)), &h->conv[enc_key(which, i)], H >> l.level, W >> l.level};
+        k.B = B; k.epi = l.epi; k.direct = D_(i);
+        if (p8) { k.in_p8 = k.enc_p8 = l.qin != l.in; k.out_p8 = l.qout != l.out; }
+        return k;
+    };
     // Channel-chunk-major tensors (conv_f43.h LAY) between the seven packed layers when ALL of them run conv_f43_k in this launch (the rule
     // of use_f43 says yes for every launch with enough work items: the batched entries); any other mix keeps NHWC throughout.  Where every
     // level is a multiple of 32 pixels wide the choice changes no bit of the result (conv_f43_k stages the same bytes from either layout);
     // elsewhere the edge tiles see other discarded columns (conv_f43.h P8_PAD): rounding noise, GPU test.  Only a plan with the twins
     // (enc_plan) can run the chain.
+    // priced as a P8 chain first; if one layer then prefers F(2x2,3x3) the chain is NHWC and every layer is priced again as such (in conv())
     bool p8 = which == 0 && q.f43 && e.q11.p != nullptr;
-    {
-        const int lh[8] = {0, H, H / 2, H / 2, H / 4, H / 4, H / 4, H / 4}, lw[8] = {0, W, W / 2, W / 2, W / 4, W / 4, W / 4, W / 4};
-        const int le[8] = {0, E_RELU | E_POOL, E_RELU, E_RELU | E_POOL, E_RELU, E_RELU, E_RELU, E_RELU | E_POOL};
-        // priced as a P8 chain first; if one layer then prefers F(2x2,3x3) the chain is NHWC and every layer is priced again as such (in conv())
-        for (int i = 1; i <= 7 && p8; ++i) p8 = !D_(i) && use_f43(h, q, *W_(i), B, lh[i], lw[i], le[i], false, 0, false, true);
-    }
+    for (int i = 1; i <= 7 && p8; ++i) p8 = use_f43(h, q, call(i, true));
     const int inf = in.form;         // (the style encoder reads the same forms, in colour: rrv_prepare_style_image_device)
     FirstP fp{d_img, H, W, B, p8 ? e.q11.p : e.c11.p, h->first_w[which], h->first_b[which], which == 0 ? 1 : 0, (W + 15) / 16, (H + 15) / 16,
               which == 0 ? h->first_wg : nullptr, pc ? pc->src_H : 0, pc ? pc->src_W : 0, pc ? pc->top : 0, pc ? pc->left : 0, p8 ? 1 : 0,
@@ -1099,31 +1119,14 @@ int run_encoder(rrv_handle h, const Seq& q, EncPlan& e, const uint8_t* d_img, In
     RCHK(launch(h, q, "conv_first", 2.0 * B * H * W * 27 * 64, ((in_yuv(inf) ? yuv_samples_per_pixel(in.cs) * in_elem(inf) : 3.0 * in_elem(inf)) + 256.0) * B * H * W, [&] {
         hipLaunchKernelGGL(first_k[inf], dim3(fp.tiles_x * fp.tiles_y * B), dim3(256), 0, q.stream, fp);
     }));
-    ConvCall c;
-    if (p8) {
-        auto L = [&](Tens* in, Tens* out, int i, int hh, int ww, int epi, bool out_p8) {
-            ConvCall k{in, out, W_(i), hh, ww}; k.B = B; k.epi = epi; k.in_p8 = k.enc_p8 = true; k.out_p8 = out_p8;
-            return conv(h, q, k);
-        };
-        RCHK(L(&e.q11, &e.q1, 1, H, W, E_RELU | E_POOL, true));
-        RCHK(L(&e.q1, &e.q21, 2, H / 2, W / 2, E_RELU, true));
-        RCHK(L(&e.q21, &e.q2, 3, H / 2, W / 2, E_RELU | E_POOL, true));
-        RCHK(L(&e.q2, &e.q31, 4, e.p2.H, e.p2.W, E_RELU, true));
-        RCHK(L(&e.q31, &e.q32, 5, e.p2.H, e.p2.W, E_RELU, true));
-        RCHK(L(&e.q32, &e.q33, 6, e.p2.H, e.p2.W, E_RELU, true));
-        RCHK(L(&e.q33, &e.p3, 7, e.p2.H, e.p2.W, E_RELU | E_POOL, false));
-    } else {
-    c = ConvCall{&e.c11, &e.p1, W_(1), H, W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(1); RCHK(conv(h, q, c));
-    c = ConvCall{&e.p1, &e.c21, W_(2), H / 2, W / 2}; c.B = B; c.epi = E_RELU; c.direct = D_(2); RCHK(conv(h, q, c));
-    c = ConvCall{&e.c21, &e.p2, W_(3), H / 2, W / 2}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(3); RCHK(conv(h, q, c));
-    c = ConvCall{&e.p2, &e.c31, W_(4), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(4); RCHK(conv(h, q, c));
-    c = ConvCall{&e.c31, &e.c32, W_(5), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(5); RCHK(conv(h, q, c));
-    c = ConvCall{&e.c32, &e.c33, W_(6), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU; c.direct = D_(6); RCHK(conv(h, q, c));
-    c = ConvCall{&e.c33, &e.p3, W_(7), e.p2.H, e.p2.W}; c.B = B; c.epi = E_RELU | E_POOL; c.direct = D_(7); RCHK(conv(h, q, c));
+    for (int i = 1; i <= 8; ++i) {
+        ConvCall c = call(i, p8);
+        if (i == 8) {      // conv4_1: the caller's output, Decoder.norm[0] fused in
+            if (out41) c.out = out41;
+            if (norm0) { c.epi |= E_NORM1; c.n1 = norm0; c.par_bstride = norm0_bstride; }
+        }
+        RCHK(conv(h, q, c));
     }
-    c = ConvCall{&e.p3, out41 ? out41 : &e.c41, W_(8), e.p3.H, e.p3.W}; c.B = B; c.epi = E_RELU | (norm0 ? E_NORM1 : 0); c.n1 = norm0; c.direct = D_(8);
-    if (norm0) c.par_bstride = norm0_bstride;
-    RCHK(conv(h, q, c));
     return RRV_OK;
 }
 
@@ -1339,32 +1342,35 @@ struct Win { int y0, x0, y1, x1; };     // output window in pixels, tile aligned
 struct BlkDesc { const char* name; int cout, n1, n2, nada, sty; };
 const BlkDesc BLKS[3] = {{"slice4", 256, N_S4N1, N_S4N2, N_DEC2, 2}, {"slice3", 128, N_S3N1, N_S3N2, N_DEC3, 1}, {"slice2", 64, N_S2N1, N_S2N2, N_DEC4, 0}};
 
+// conv2 of block k of the per-frame path, on the NHWC a[k] (resblock_frame rebinds it to the P8 twin); wo: its output window, if any
+ConvCall block_conv2(rrv_handle h, const Seq& q, int B, int k, DecPlan& d, const Win* wo) {
+    const BlkDesc& b = BLKS[k];
+    const float* st = q.set->active;
+    ConvCall c{&d.a[k], &d.o[k], &h->conv[std::string("Decoder.") + b.name + ".conv2"], d.a[k].H, d.a[k].W}; c.B = B;
+    if (q.state_images) c.par_bstride = RRV_STATE_FLOATS;
+    c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[b.n2]; c.res = &d.xs[k]; c.n2 = st + SL.norm[b.nada]; c.sty = st + SL.sty[b.sty];
+    if (wo) { c.wy0 = wo->y0; c.wx0 = wo->x0; c.wy1 = wo->y1; c.wx1 = wo->x1; }
+    return c;
+}
+
 // block k of the per-frame path, fused across its normalisation layers (saved statistics)
 // mid_wait: conv2 is launched behind this event (SeqHook::tail_wait)
 int resblock_frame(rrv_handle h, const Seq& q, int B, int k, const Tens& in, DecPlan& d, const Win* wa = nullptr, const Win* wo = nullptr, hipEvent_t mid_wait = nullptr) {
     const BlkDesc& b = BLKS[k];
-    Tens &xs = d.xs[k], &a = d.a[k], &o = d.o[k], &qa = d.qa[k];
-    const float* st = q.set->active;
-    const std::string p = std::string("Decoder.") + b.name;
-    ConvCall c;
+    Tens &xs = d.xs[k], &a = d.a[k], &qa = d.qa[k];
+    ConvCall c2 = block_conv2(h, q, B, k, d, wo);
     // conv2 on conv_f43_k reads its input channel-chunk-major (conv_f43.h LAY; same bits, 12 % faster): conv1 then writes the twin,
     // where the plan has one (dec_plan)
-    const bool p8 = qa.p && use_f43(h, q, h->conv[p + ".conv2"], B, a.H, a.W, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false) &&
-                    !(wo && ((wo->y0 | wo->x0 | wo->y1 | wo->x1) & 31));
-    Tens* a_in = p8 ? &qa : &a;
+    const bool p8 = qa.p && use_f43(h, q, c2);
+    if (p8) { c2.in = &qa; c2.in_p8 = true; }
     // conv1 behind the upsample and, in the same kernel, the 1x1 shortcut at the input resolution: up(conv1x1(x)) == conv1x1(up(x))
-    c = ConvCall{&in, a_in, &h->conv[p + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1; c.n1 = st + SL.norm[b.n1];
-    c.sc_out = &xs; c.out_p8 = p8;
+    ConvCall c{&in, p8 ? &qa : &a, &h->conv[std::string("Decoder.") + b.name + ".conv1"], a.H, a.W}; c.B = B; c.ups = true; c.epi = E_LRELU | E_NORM1;
+    c.n1 = q.set->active + SL.norm[b.n1]; c.sc_out = &xs; c.out_p8 = p8;
     if (q.state_images) c.par_bstride = RRV_STATE_FLOATS;
     if (wa) { c.wy0 = wa->y0; c.wx0 = wa->x0; c.wy1 = wa->y1; c.wx1 = wa->x1; }
     RCHK(conv(h, q, c));
     if (mid_wait) HIPCHK(hipStreamWaitEvent(q.stream, mid_wait, 0));
-    c = ConvCall{a_in, &o, &h->conv[p + ".conv2"], a.H, a.W}; c.B = B; c.in_p8 = p8;
-    if (q.state_images) c.par_bstride = RRV_STATE_FLOATS;
-    c.epi = E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2; c.n1 = st + SL.norm[b.n2]; c.res = &xs; c.n2 = st + SL.norm[b.nada]; c.sty = st + SL.sty[b.sty];
-    if (wo) { c.wy0 = wo->y0; c.wx0 = wo->x0; c.wy1 = wo->y1; c.wx1 = wo->x1; }
-    RCHK(conv(h, q, c));
-    return RRV_OK;
+    return conv(h, q, c2);
 }
 
 // the conv_last_k instantiation that writes `f`
@@ -1485,7 +1491,7 @@ int transfer_device(rrv_handle h, const Seq& q, const uint8_t* d_in, int B, int 
         const Win crop{pc->top, pc->left, pc->top + pc->src_H, pc->left + pc->src_W};
         wl = grow(crop, 0);        // conv_last output tiles
         wo = grow(crop, 1);        // slice2.conv2 output feeding them
-        if (use_f43(h, q, h->conv["Decoder.slice2.conv2"], B, Ho, Wo, E_LRELU | E_NORM1 | E_RES_UPS | E_NORM2, false, 0, false)) {      // 32 x 32 pixel work items: round the window out to them
+        if (use_f43(h, q, block_conv2(h, q, B, 2, d, nullptr))) {      // 32 x 32 pixel work items: round the window out to them (asked before the window exists: the call carries none)
             const int lh = (Ho + 31) & ~31, lw = (Wo + 31) & ~31;
             wo = Win{wo.y0 & ~31, wo.x0 & ~31, (wo.y1 + 31) & ~31, (wo.x1 + 31) & ~31};
             if (wo.y1 > lh) wo.y1 = lh;
@@ -2064,11 +2070,7 @@ int rrv_create(int device, rrv_handle* out) {
         for (int i = 0; i < rrv_ctx::Timeline::N; ++i) ok = ok && hipEventCreate(&h->tl.k_end[i]) == hipSuccess && hipEventCreate(&h->tl.d_end[i]) == hipSuccess;
     }
     // the dynamic-LDS opt-in is a per-device function attribute: set it for THIS device, whatever other handles did
-    for (const ConvKey& e : WINO_TABLE)
-        if (ok && e.attr) ok = e.attr() == hipSuccess;
-    for (const ConvKey& e : F43_TABLE)
-        if (ok && e.attr) ok = e.attr() == hipSuccess;
-    for (const F43LayKey& e : F43_LAY_TABLE)
+    for (const ConvRow& e : CONV_ROWS)
         if (ok && e.attr) ok = e.attr() == hipSuccess;
     if (!ok) {
         delete h;
@@ -2226,16 +2228,14 @@ int rrv_finalize_weights(rrv_handle h) {
     }
     for (int which = 0; which < 2; ++which) {
         for (int i = 0; i < 9; ++i) {
-            char k[64];
-            if (which == 0) snprintf(k, sizeof k, "Encoder.slice.%d", VGG_IDX[i]);
-            else snprintf(k, sizeof k, "EncoderStyle.slice%d.%d", STYLE_SLICE[i], VGG_IDX[i]);
+            const std::string k = enc_key(which, i);
             if (i == 0) {
                 float* raw = nullptr;
-                RCHK(upload(h, q, std::string(k) + ".weight", &raw, 64 * 27));
+                RCHK(upload(h, q, k + ".weight", &raw, 64 * 27));
                 RCHK(dalloc(h, q, &h->first_w[which], 27 * 64, false));
                 hipLaunchKernelGGL(pack_first_k, dim3(7), dim3(256), 0, q.stream, (const float*)raw, h->first_w[which]);
                 HIPCHK(hipGetLastError());
-                RCHK(upload(h, q, std::string(k) + ".bias", &h->first_b[which], 64));
+                RCHK(upload(h, q, k + ".bias", &h->first_b[which], 64));
                 if (which == 0) {
                     RCHK(dalloc(h, q, &h->first_wg, 1216, false));
                     hipLaunchKernelGGL(pack_first_grey_k, dim3(3), dim3(256), 0, q.stream, (const float*)raw, (const float*)h->first_b[0], h->first_wg);
@@ -2251,16 +2251,15 @@ int rrv_finalize_weights(rrv_handle h) {
             }
         }
     }
-    const int bc[3][2] = {{512, 256}, {256, 128}, {128, 64}};
-    const char* bn[3] = {"slice4", "slice3", "slice2"};
     for (int b = 0; b < 3; ++b) {
-        const std::string p = std::string("Decoder.") + bn[b];
-        RCHK(make_conv(h, q, p + ".conv1", bc[b][1], bc[b][0], 9, true, false));
+        const std::string p = std::string("Decoder.") + BLKS[b].name;
+        const int cout = BLKS[b].cout, cin = 2 * cout;      // (each block halves the channels)
+        RCHK(make_conv(h, q, p + ".conv1", cout, cin, 9, true, false));
         RCHK(pack_ups(h, q, h->conv[p + ".conv1"]));
-        RCHK(make_conv(h, q, p + ".conv2", bc[b][1], bc[b][1], 9, true));
+        RCHK(make_conv(h, q, p + ".conv2", cout, cout, 9, true));
         h->conv[p + ".conv2"].f43_bit = 7 + b;
         RCHK(pack_f43(h, q, h->conv[p + ".conv2"]));
-        RCHK(make_conv(h, q, p + ".conv_shortcut", bc[b][1], bc[b][0], 1, false));
+        RCHK(make_conv(h, q, p + ".conv_shortcut", cout, cin, 1, false));
         RCHK(pack_ups_sc(h, q, h->conv[p + ".conv1"], h->conv[p + ".conv_shortcut"]));
     }
     {

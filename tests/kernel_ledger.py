@@ -60,7 +60,7 @@ def _add(kind, keys, ref, what):
 
 
 # ---- the convolutions ---------------------------------------------------------------------------------------------------------------------
-# conv_wino_split_k<EPI, PERIMG> (WINO_TABLE: WK = shared state only, WKI = fn_img too).  EPI: 1 ReLU, 65 + pool, 5 + Decoder.norm[0],
+# conv_wino_split_k<EPI, IMG> (CONV_ROWS: WS(EPI, 0) = shared state, WS(EPI, 1) = the per-image row, where a caller reaches one).  EPI: 1 ReLU, 65 + pool, 5 + Decoder.norm[0],
 # 54 ResidualBlock.conv2, 2 LeakyReLU, 0 raw split-K slices, 8 + residual, 40 + residual + AdaIN
 EVERY = GL + "test_every_layer_against_its_own_input"
 _add("layer", "conv_wino_split_k<1, 0>", EVERY, "kind f23: the rows of c21 / c31 / c32 / c33 are conv_wino<E_RELU> (family_of), NHWC taps")
@@ -72,7 +72,7 @@ _add("layer", "conv_wino_split_k<0, 0>", GL + "test_split_k_kernel_filter", "640
 _add("layer", "conv_wino_split_k<8, 0>", EVERY, "f1 / f2 (two kernels in one, LR.COMPOSITE): the up rows are conv_wino<E_RES>")
 _add("layer", "conv_wino_split_k<40, 0>", EVERY, "f3's row is conv_wino, family f23")
 _add("layer", "conv_wino_split_k<5, 1>", IN + "test_blended_frames_per_image_conv4_1",
-     "c41's row is conv_wino<..> at 256 x 512 and debug_state_set(0, 1) succeeds: conv() took fn_img; image 2 on set 0 fails")
+     "c41's row is conv_wino<..> at 256 x 512 and debug_state_set(0, 1) succeeds: conv() took the IMG row; image 2 on set 0 fails")
 _add("layer", "conv_wino_split_k<54, 1>", IN + "test_blended_frames_per_image_conv4_1",
      "kind default: o4 / o3 / o2 asserted f23 in a launch with per-image state (the grouped test of the frame-mode suite too)")
 _add("layer", "conv_wino_split_k<2, 1>", IN + "test_filter_down_per_image_weights_frame_mode",
@@ -81,27 +81,20 @@ _add("layer", "conv_wino_split_k<0, 1>", FM + "test_every_frame_mode_stage",
      "B > 1: dpart has 256 channels (split 8) under per-image folded weights; split 4: test_gpu_instantiations, 64 x 5136")
 _add("layer", "conv_wino_split_k<8, 1>", FM + "test_every_frame_mode_stage", "B > 1: f1 / f2 on each image's own folded weights; image 7 on set 8 fails f1")
 _add("layer", "conv_wino_split_k<40, 1>", FM + "test_every_frame_mode_stage", "B > 1: f3 on each image's own set; image 7 on set 8 fails f3")
-_add("unreachable", ["conv_wino_split_k<1, 1>", "conv_wino_split_k<65, 1>"], None,
-     "WINO_TABLE: WK(E_RELU) and WK(E_RELU | E_POOL) have no fn_img, and conv() fails a per-image call on such a row")
 
-# conv_wino_k<EPI, 0, 4, UPS=1, SC, PERIMG>: the upsample-fused ResidualBlock.conv1 (EPI 6: LeakyReLU + norm1; 2: raw LeakyReLU)
+# conv_wino_k<EPI, 0, 4, UPS=1, SC, IMG> (CONV_ROWS: UP(EPI, SC, IMG)): the upsample-fused ResidualBlock.conv1 (EPI 6: LeakyReLU + norm1; 2: raw LeakyReLU)
 _add("layer", "conv_wino_k<6, 0, 4, 1, 1, 0>", EVERY, "every kind: a4 / a3 / a2 and xs4 / xs3 / xs2 asserted family ups (conv_upw_sc rows)")
 _add("layer", "conv_wino_k<6, 0, 4, 1, 1, 1>", IN + "test_blended_frames_per_image_conv4_1",
      "a4 / a3 / a2 of images 0 and 2 on their own sets in a launch with per-image state (resblock_frame sets par_bstride)")
 _add("layer", "conv_wino_k<2, 0, 4, 1, 1, 0>", FM + "test_every_frame_mode_stage", "frame_families: the conv1 rows are conv_upw_sc, family ups, raw output + statistics")
 _add("layer", "conv_wino_k<2, 0, 4, 1, 0, 0>", PL + "test_every_stop_of_the_resident_pass", "the nine-product conv_upw<E_LRELU> of the preparation pass (unfused shortcut)")
-_add("unreachable", ["conv_wino_k<6, 0, 4, 1, 0, 0>", "conv_wino_k<6, 0, 4, 1, 0, 1>"], None,
-     "UW(E_LRELU | E_NORM1): only resblock_frame asks for this epilogue behind the upsample, and it always passes sc_out (TAPS 29)")
-_add("unreachable", ["conv_wino_k<2, 0, 4, 1, 0, 1>", "conv_wino_k<2, 0, 4, 1, 1, 1>"], None,
-     "UW(E_LRELU) and UWS(E_LRELU) have no fn_img: the frame-mode and preparation walks normalise with pointwise_k, not in conv1")
 
-# conv_f43_k<EPI, LAY> (F43_TABLE, F43_LAY_TABLE; per-image parameters are read by the same instantiation)
+# conv_f43_k<EPI, LAY> (CONV_ROWS: F4(EPI, LAY); per-image parameters are read by the same instantiation)
 _add("layer", ["conv_f43_k<1, 0>", "conv_f43_k<65, 0>", "conv_f43_k<54, 0>"], EVERY, "kind f43_nhwc: ENC_F43 + DEC_F43 asserted f43, every layout 0")
 _add("layer", ["conv_f43_k<65, 3>", "conv_f43_k<1, 3>", "conv_f43_k<65, 1>", "conv_f43_k<54, 1>"], EVERY,
      "kind f43_p8: ENC_F43 + DEC_F43 asserted f43, c11 .. c33 and a4 / a3 / a2 layout 1, p3 layout 0")
-_add("unreachable", "conv_f43_k<5, 0>", None, "FK(E_RELU | E_NORM1): conv4_1 gets no F(4x4) pack (rrv_finalize_weights packs i < 8 only), so use_f43 is false for it")
 
-# conv_mfma_k<BN, TAPS, EPI, ..> (CONV_TABLE)
+# conv_mfma_k<BN, TAPS, EPI, ..> (CONV_ROWS: MF(BN, TAPS, EPI))
 _add("layer", ["conv_mfma_k<128, 1, 0, 0, 0, 1>", "conv_mfma_k<64, 1, 0, 0, 0, 1>"], PL + "test_every_stop_of_the_resident_pass",
      "the unfused 1 x 1 shortcuts of the preparation pass, family gemm")
 _add("layer", "conv_mfma_k<32, 9, 0, 0, 0, 1>", PL + "test_every_stop_of_the_resident_pass", "the FilterPredictor 512 -> 32 convolutions, family gemm")

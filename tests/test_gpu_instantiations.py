@@ -156,7 +156,7 @@ def test_blended_frames_per_image_conv4_1(pkg, weights, states, kind):
     s, seq = blend_launch(pkg, weights, states, frames, WTS, mode=None if kind == "default" else 2)
     try:
         assert seq[8][0].startswith("conv_wino<") and "@256x512@" in seq[8][0], seq[8]       # conv4_1: the row-split kernel
-        s.debug_state_set(0, 1)                                 # the launch had per-image state: conv() took fn_img
+        s.debug_state_set(0, 1)                                 # the launch had per-image state: conv() took the per-image row
         with pytest.raises(pkg.RRVError, match="did not write this image"):
             s.debug_state_set(0, B)
         sets = {}
