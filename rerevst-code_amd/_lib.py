@@ -9,8 +9,8 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
-# reach the main library only).  It finds librerevst_scale.so, librerevst_deliver.so and librerevst_guided.so next to ITSELF (rpath $ORIGIN): a library
-# in another directory needs copies of the three there.
+# reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
+# needs a copy of it there.
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8

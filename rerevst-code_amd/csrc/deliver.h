@@ -1,9 +1,8 @@
-// deliver.h — parameters and the launch entry of librerevst_deliver.so, the output-side resampler behind the last kernel.
+// deliver.h — parameters and the launch entry of the output-side resampler behind the last kernel (librerevst_stages.so).
 //
-// deliver_k<OUT> (deliver.hip) reads B contiguous float32 [H][W][3] BGR PIXEL frames (what conv_last_k<false> stores, crop applied),
+// deliver_k<OUT> (deliver_k.h) reads B contiguous float32 [H][W][3] BGR PIXEL frames (what conv_last_k<false> stores, crop applied),
 // resamples them to DH x DW with the input resampler's arithmetic and tap tables (rrv_resample_taps, (H -> DH) and (W -> DW)), and
-// writes the result through an ImgView in one of conv_last_k's output forms.  The kernels live in a library of their own so that the
-// kernel sets of librerevst_hip.so and librerevst_scale.so stay what their ledgers name; this header is all the main library sees of them.
+// writes the result through an ImgView in one of conv_last_k's output forms.  This header is all the main library sees of the kernels.
 #pragma once
 #include "resample.h"   // RS_* tile and tap constants, RsAxis; conv_thin.h: SP_* spaces, ImgView
 

@@ -1,11 +1,10 @@
-// guided.h — parameters and the launch entry of librerevst_guided.so, the guided delivery stage (include/rerevst_hip.h "Guided delivery").
+// guided.h — parameters and the launch entry of the guided delivery stage (include/rerevst_hip.h "Guided delivery"; librerevst_stages.so).
 //
-// Two kernels (guided.hip) turn B stylized working frames P [H][W][3] and the source at both sizes, X_lo [H][W][3] and X_hi [DH][DW][3] (all
+// Two kernels (guided_k.h) turn B stylized working frames P [H][W][3] and the source at both sizes, X_lo [H][W][3] and X_hi [DH][DW][3] (all
 // contiguous float32 BGR PIXEL), into the frames Q [DH][DW][3] of the same form:
 //   gf_coeff_k   the local linear model stylized = a * luma + b of every working pixel: ab [B][6][H][W], planes a_B a_G a_R b_B b_G b_R
 //   gf_apply_k   box mean of the six planes, resampled H x W -> DH x DW with the delivery stage's tap tables, applied to the luma of X_hi
-// The kernels live in a library of their own so that the kernel sets of the other three stay what their ledgers name; this header is all
-// the main library sees of them.
+// This header is all the main library sees of them.
 #pragma once
 #include "resample.h"   // RsAxis, RS_TAPS
 

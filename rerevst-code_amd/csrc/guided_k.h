@@ -1,4 +1,4 @@
-// guided.hip — librerevst_guided.so: the guided delivery stage (include/rerevst_hip.h "Guided delivery"), gfx950.
+// guided_k.h — the guided delivery stage (include/rerevst_hip.h "Guided delivery"), gfx950; part of stages.hip (librerevst_stages.so).
 //
 // Joint upsampling with the fast guided filter (He & Sun 2015): the source's luma g guides the stylized working frame P to the delivered size.
 // Both kernels are bound by HBM traffic; all their scratch is dynamic LDS in planar form ([plane][row][column], 4-byte accesses at stride one:
@@ -201,25 +201,4 @@ __global__ __launch_bounds__(256) void gf_apply_k(const GuidedP p) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) p.q[at + k] = fmaf(up[k], g, up[3 + k]);
     }
-}
-
-extern "C" int rrv_guided_launch(const GuidedP* p, void* stream) {
-    if (!p || !p->P || !p->xlo || !p->xhi || !p->ab || !p->q) return (int)hipErrorInvalidValue;
-    if (p->B < 1 || p->H < 1 || p->W < 1 || p->DH < p->H || p->DW < p->W || p->r < 1 || p->r > GF_R_MAX) return (int)hipErrorInvalidValue;
-    if (p->tw != 64 && p->tw != 32 && p->tw != 16 && p->tw != 8) return (int)hipErrorInvalidValue;
-    // the kernel stages what p.sy x p.sx holds and no more; smaller than a tile's span would drop taps, so the sizes are the bound's or refused
-    if (p->sy != guided_span(p->H, p->DH, GF_AT_H) || p->sx != guided_span(p->W, p->DW, p->tw)) return (int)hipErrorInvalidValue;
-    const size_t lds_c = guided_coeff_lds_bytes(p->r), lds_a = guided_apply_lds_bytes(p->r, p->sy, p->sx);
-    if (lds_a > GF_LDS_MAX) return (int)hipErrorInvalidValue;
-    // dynamic LDS above 64 KB needs the attribute on the current device; set at every launch (cheap), so no state is shared between devices or threads
-    hipError_t e = hipFuncSetAttribute((const void*)gf_coeff_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)guided_coeff_lds_bytes(GF_R_MAX));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gf_apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS_MAX);
-    if (e != hipSuccess) return (int)e;
-    const unsigned ct = (unsigned)((p->W + GF_CT_W - 1) / GF_CT_W) * (unsigned)((p->H + GF_CT_H - 1) / GF_CT_H) * (unsigned)p->B;
-    hipLaunchKernelGGL(gf_coeff_k, dim3(ct), dim3(256), lds_c, (hipStream_t)stream, *p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const unsigned at = (unsigned)((p->DW + p->tw - 1) / p->tw) * (unsigned)((p->DH + GF_AT_H - 1) / GF_AT_H) * (unsigned)p->B;
-    hipLaunchKernelGGL(gf_apply_k, dim3(at), dim3(256), lds_a, (hipStream_t)stream, *p);
-    return (int)hipGetLastError();
 }

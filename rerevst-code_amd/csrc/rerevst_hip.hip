@@ -26,9 +26,9 @@
 #include "conv_thin.h"
 #include "prep_kernels.h"
 #include "mask_kernels.h"
-#include "resample.h"      // librerevst_scale.so: parameters and the launch entry of the resampler
-#include "guided.h"        // librerevst_guided.so: the guided delivery stage
-#include "deliver.h"       // librerevst_deliver.so: the same of the output-side resampler
+#include "resample.h"      // librerevst_stages.so: parameters and the launch entry of the resampler
+#include "guided.h"        //                       of the guided delivery stage
+#include "deliver.h"       //                       of the output-side resampler
 
 namespace {
 
@@ -2861,6 +2861,15 @@ static int rs_pair(rrv_handle h, int SH, int SW, int H, int W, const rrv_ctx::Rs
     if ((*ty)->span > RS_ROWS_MAX) return fail(h, RRV_E_ARG, "resample: the vertical taps of a tile span more rows than the kernel stages");
     return RRV_OK;
 }
+// What a stage's launch over tiles of RS_TH x RS_TW pixels of an H x W destination starts from: both axes' tables (they exist already or
+// are built here), the tiles per frame, and the largest span of a tile's taps on either axis (rows: what a tile stages in LDS).
+struct RsGrid { RsAxis ay, ax; int tiles_x, tiles_y, rows, cols; };
+static int rs_grid(rrv_handle h, int SH, int SW, int H, int W, RsGrid* g) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
+    *g = RsGrid{ty->axis, tx->axis, (W + RS_TW - 1) / RS_TW, (H + RS_TH - 1) / RS_TH, ty->span, tx->span};
+    return RRV_OK;
+}
 // everything a scaled request allocates, before its first launch: both axes' tables and room for `frames` working frames in the slot's buffer
 static int rs_reserve(rrv_handle h, int slot, int frames, int SH, int SW, int H, int W) {
     const rrv_ctx::RsTab *ty, *tx;
@@ -2883,14 +2892,13 @@ static int check_scale(rrv_handle h, const char* who, int SH, int SW, int H, int
     return RRV_OK;
 }
 // B frames of SH x SW in the format `in` through `vi` -> contiguous [B][H][W][3] float32 BGR PIXEL at d_out, queued on q.stream.  The tables
-// exist already or are built here (rs_reserve has run for the entries that promise no allocation between launches).
+// exist already or are built here (reserve_stages has run for the entries that promise no allocation between launches).
 static int resample_launch(rrv_handle h, const Seq& q, const void* d_in, InFmt in, const ImgView& vi, int B, int SH, int SW, int H, int W, float* d_out) {
-    const rrv_ctx::RsTab *ty, *tx;
-    RCHK(rs_pair(h, SH, SW, H, W, &ty, &tx));
+    RsGrid g;
+    RCHK(rs_grid(h, SH, SW, H, W, &g));
     ResampleP p{};
     p.img = d_in; p.v = vi; p.SH = SH; p.SW = SW; p.H = H; p.W = W; p.B = B; p.out = d_out;
-    p.ay = ty->axis; p.ax = tx->axis;
-    p.tiles_x = (W + RS_TW - 1) / RS_TW; p.tiles_y = (H + RS_TH - 1) / RS_TH; p.rows = ty->span;
+    p.ay = g.ay; p.ax = g.ax; p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.rows = g.rows;
     p.space = in.space;
     if (in_yuv(in.form)) {
         const YuvLaunch y = yuv_launch_params(h->yuv_in, true, in_yuv16(in.form), in.form == IN_YUV_P016);
@@ -2900,7 +2908,7 @@ static int resample_launch(rrv_handle h, const Seq& q, const void* d_in, InFmt i
     int e = 0;
     // for the profile log: bytes from the shapes; operations two per tap, channel and pass, a row's taps taken as span / RS_TH
     const double src_bytes = (in_yuv(in.form) ? yuv_samples_per_pixel(in.cs) : 3.0) * in_elem(in.form) * SH * SW;
-    RCHK(launch(h, q, "resample", 2.0 * B * 3 * ((double)tx->span / RS_TH * SH * W + (double)ty->span / RS_TH * H * W), (src_bytes + 12.0 * H * W) * B, [&] {
+    RCHK(launch(h, q, "resample", 2.0 * B * 3 * ((double)g.cols / RS_TH * SH * W + (double)g.rows / RS_TH * H * W), (src_bytes + 12.0 * H * W) * B, [&] {
         e = rrv_scale_launch(&p, in.form, q.stream);
     }));
     if (e != 0) return fail(h, RRV_E_HIP, std::string("resample: launch failed: ") + hipGetErrorString((hipError_t)e));
@@ -2908,24 +2916,16 @@ static int resample_launch(rrv_handle h, const Seq& q, const void* d_in, InFmt i
 }
 
 // ---- output size (include/rerevst_hip.h "Scaling, output size"): the delivery stage behind the last kernel
-// everything a delivering request allocates, before its first launch: both axes' tables and room for `frames` working frames in the slot's buffer
-static int dl_reserve(rrv_handle h, int slot, int frames, int H, int W, int DH, int DW) {
-    const rrv_ctx::RsTab *ty, *tx;
-    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
-    rrv_ctx::Slot& sl = h->slots[slot];
-    return ensure_dev(h, sl.dl_buf, sl.dl_cap, (size_t)frames * H * W * 3);
-}
 // the deliver_k instantiation that writes `f`
 static int deliver_form(OutFmt f) { return f.yuv ? (yuv16_layout(f.yuv) ? DL_YUV16 : DL_YUV8) : f.u8 ? (f.chw ? DL_U8_CHW : DL_U8_HWC) : (f.chw ? DL_F32_CHW : DL_F32_HWC); }
 // B contiguous float32 [H][W][3] BGR PIXEL frames at d_in -> DH x DW frames in the format `fmt` through `vo` at d_out, queued on q.stream.  The
-// tables exist already or are built here (dl_reserve has run for the entries that promise no allocation between launches).
+// tables exist already or are built here (reserve_stages has run for the entries that promise no allocation between launches).
 static int deliver_launch(rrv_handle h, const Seq& q, const float* d_in, int B, int H, int W, int DH, int DW, void* d_out, OutFmt fmt, const ImgView& vo) {
-    const rrv_ctx::RsTab *ty, *tx;
-    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    RsGrid g;
+    RCHK(rs_grid(h, H, W, DH, DW, &g));
     DeliverP p{};
     p.in = d_in; p.H = H; p.W = W; p.B = B; p.DH = DH; p.DW = DW; p.out = d_out; p.v = vo;
-    p.ay = ty->axis; p.ax = tx->axis;
-    p.tiles_x = (DW + RS_TW - 1) / RS_TW; p.tiles_y = (DH + RS_TH - 1) / RS_TH; p.rows = ty->span;
+    p.ay = g.ay; p.ax = g.ax; p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.rows = g.rows;
     p.space = fmt.space;
     if (fmt.yuv) {
         const YuvLaunch y = yuv_launch_params(h->yuv_out, false, yuv16_layout(fmt.yuv), fmt.yuv == RRV_LAY_P016);
@@ -2936,7 +2936,7 @@ static int deliver_launch(rrv_handle h, const Seq& q, const float* d_in, int B, 
     int e = 0;
     // for the profile log: bytes from the shapes (12 per working pixel read, the delivered frame written); operations as the resampler's
     const double out_bytes = (fmt.yuv ? yuv_samples_per_pixel(fmt.cs) * yuv_sample_bytes(fmt) : 3.0 * out_elem(fmt)) * DH * DW;
-    RCHK(launch(h, q, "deliver", 2.0 * B * 3 * ((double)tx->span / RS_TH * H * DW + (double)ty->span / RS_TH * DH * DW), (12.0 * H * W + out_bytes) * B, [&] {
+    RCHK(launch(h, q, "deliver", 2.0 * B * 3 * ((double)g.cols / RS_TH * H * DW + (double)g.rows / RS_TH * DH * DW), (12.0 * H * W + out_bytes) * B, [&] {
         e = rrv_deliver_launch(&p, deliver_form(fmt), q.stream);
     }));
     if (e != 0) return fail(h, RRV_E_HIP, std::string("deliver: launch failed: ") + hipGetErrorString((hipError_t)e));
@@ -2972,25 +2972,32 @@ static int gd_tables(rrv_handle h, int H, int W, int DH, int DW) {
     RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
     return rs_pair(h, DH, DW, DH, DW, &ty, &tx);
 }
-// everything a guided request allocates, before its first launch: the tables and room for `frames` frames in the slot's three buffers
-static int gd_reserve(rrv_handle h, int slot, int frames, int H, int W, int DH, int DW) {
-    RCHK(gd_tables(h, H, W, DH, DW));
+// Everything the stages of request `x` allocate on `slot` for `frames` frames at a time, before the request's first launch.  Scaled: both
+// axes' tables and the slot's buffer of working frames.  Then guided: its tables, the stylized working frames and the stage's three buffers;
+// or delivering: the tables and the stylized working frames.
+static int reserve_stages(rrv_handle h, int slot, int frames, const Xfer& x) {
+    if (x.scaled()) RCHK(rs_reserve(h, slot, frames, x.SH, x.SW, x.H, x.W));
+    if (!x.staged()) return RRV_OK;
+    const int H = x.WH(), W = x.WW();
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(x.guided() ? gd_tables(h, H, W, x.DH, x.DW) : rs_pair(h, H, W, x.DH, x.DW, &ty, &tx));
     rrv_ctx::Slot& sl = h->slots[slot];
     RCHK(ensure_dev(h, sl.dl_buf, sl.dl_cap, (size_t)frames * H * W * 3));
-    RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * DH * DW * 3));
+    if (!x.guided()) return RRV_OK;
+    RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * x.DH * x.DW * 3));
     RCHK(ensure_dev(h, sl.gd_ab, sl.gd_ab_cap, (size_t)frames * H * W * 6));
-    return ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * DH * DW * 3);
+    return ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * x.DH * x.DW * 3);
 }
 // B frames: P, x_lo [H][W][3] and x_hi [DH][DW][3] -> q [DH][DW][3], all contiguous float32 BGR PIXEL, through the planes `ab` ([B][6][H][W]);
 // queued on q.stream.  The tables exist already or are built here.
 static int guided_launch(rrv_handle h, const Seq& q, const float* P, const float* x_lo, const float* x_hi, int B, int H, int W, int DH, int DW, int r,
                          float eps, float* ab, float* out) {
-    const rrv_ctx::RsTab *ty, *tx;
-    RCHK(rs_pair(h, H, W, DH, DW, &ty, &tx));
+    RsGrid g;      // (its tiles are guided_tile's: only the axes are taken)
+    RCHK(rs_grid(h, H, W, DH, DW, &g));
     GuidedP p{};
     p.P = P; p.xlo = x_lo; p.xhi = x_hi; p.ab = ab; p.q = out;
     p.H = H; p.W = W; p.B = B; p.DH = DH; p.DW = DW; p.r = r; p.e = eps * 65025.0f;
-    p.ay = ty->axis; p.ax = tx->axis;
+    p.ay = g.ay; p.ax = g.ax;
     if (!guided_tile(&p)) return fail(h, RRV_E_ARG, "guided: no tile of the apply kernel fits the LDS");      // (cannot happen within the radius limit)
     int e = 0;
     // for the profile log: bytes from the shapes (P, X_lo read, the planes written and read with their halo counted once, X_hi read, Q written);
@@ -3074,9 +3081,7 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     // stage at equal size from Q to the caller's frames.
     const bool delivering = x.delivering(), guided = x.guided(), staged = x.staged();
     const int group_frames = x.model == Model::GLOBAL ? x.B : std::min(x.B, (int)rrv_ctx::MS_GROUP_MAX);
-    if (scaled) RCHK(rs_reserve(h, slot, group_frames, x.SH, x.SW, x.H, x.W));
-    if (guided) RCHK(gd_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
-    else if (delivering) RCHK(dl_reserve(h, slot, group_frames, x.WH(), x.WW(), x.DH, x.DW));
+    RCHK(reserve_stages(h, slot, group_frames, x));
     rrv_ctx::Slot& sl = h->slots[slot];
     const CallerOrder caller = x.order(h);
     const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || staged);
@@ -3492,12 +3497,8 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
-    if (x.scaled())      // a scaled request: the tables and each compute slot's buffer of working frames, before the first launch
-        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(rs_reserve(h, slot_of(k), sub, x.SH, x.SW, x.H, x.W));      // (slot_of has period 2)
-    if (x.guided())          // a guided request: the stylized working frames and the guided stage's three buffers
-        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(gd_reserve(h, slot_of(k), sub, x.WH(), x.WW(), x.DH, x.DW));
-    else if (x.delivering())      // a delivering request: the same for the stylized working frames
-        for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(dl_reserve(h, slot_of(k), sub, x.WH(), x.WW(), x.DH, x.DW));
+    // a scaled, delivering or guided request: the tables and each compute slot's buffers, before the first launch
+    for (int k = 0; k < std::min(nchunk, 2); ++k) RCHK(reserve_stages(h, slot_of(k), sub, x));      // (slot_of has period 2)
     for (int i = 0; i < nsets; ++i) {      // device staging for the copied directions, pinned staging for pageable caller arrays
         RCHK(stage_reserve(h, i, zin ? 0 : (size_t)sub * fb, zout ? 0 : (size_t)sub * fob, false));
         RCHK(stage_reserve(h, i, in_pin ? 0 : (size_t)sub * fb, out_pin ? 0 : (size_t)sub * fob, true));

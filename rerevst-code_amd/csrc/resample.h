@@ -1,10 +1,9 @@
-// resample.h — parameters and the launch entry of librerevst_scale.so, the antialiased resampler in front of the first kernel.
+// resample.h — parameters and the launch entry of the antialiased resampler in front of the first kernel (librerevst_stages.so).
 //
-// resample_k<IN> (resample.hip) reads B source frames of SH x SW pixels in any of conv_first_k's eight input forms, through the same ImgView,
+// resample_k<IN> (resample_k.h) reads B source frames of SH x SW pixels in any of conv_first_k's eight input forms, through the same ImgView,
 // and writes contiguous [B][H][W][3] float32 BGR PIXEL frames: a separable triangle filter whose per-axis tap tables the host builds
 // (rrv_resample_taps: first source sample, tap count and normalised float32 weights per output sample, at most RS_TAPS taps).
-// The kernels live in a library of their own so that librerevst_hip.so's kernel set stays what its ledger names; this header is all the
-// main library sees of them.
+// This header is all the main library sees of the kernels.
 #pragma once
 #include "conv_thin.h"   // IN_* forms, SP_* spaces, ImgView
 

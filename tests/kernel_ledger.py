@@ -44,6 +44,24 @@ def symbols(lib):
     return [short(d) for d in out]
 
 
+def check_stage_ledger(ledger, family, one_test_each):
+    """A stage's ledger (kernel symbol -> "file::test", the test that holds THAT kernel to its reference) against librerevst_stages.so:
+    the kernels of the library whose name contains `family` are exactly the ledger's keys, and every test it names exists."""
+    build = importlib.import_module("rerevst-code_amd.build")
+    build.build_lib(verbose=False)
+    stages = symbols(build.STAGES_LIB)
+    assert len(stages) == len(set(stages))
+    mine = {s for s in stages if family in s}
+    assert mine == set(ledger), (sorted(mine - set(ledger)), sorted(set(ledger) - mine))
+    if one_test_each:
+        assert len(set(ledger.values())) == len(ledger)
+    for key, ref in ledger.items():
+        path, name = ref.split("::")
+        assert os.path.isfile(os.path.join(ROOT, path)), (key, ref)
+        mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
+        assert callable(getattr(mod, name, None)), (key, ref)
+
+
 GL = "tests/test_gpu_layers.py::"
 FM = "tests/test_gpu_frame_mode_layers.py::"
 MK = "tests/test_gpu_mask_layers.py::"

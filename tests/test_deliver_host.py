@@ -1,9 +1,8 @@
-"""The delivery stage without a GPU: the ledger of librerevst_deliver.so (every kernel symbol of its gfx950 code object is named here
+"""The delivery stage without a GPU: its ledger (every deliver_k symbol of librerevst_stages.so's gfx950 code object is named here
 and held by one test of tests/test_gpu_deliver.py; the rule of tests/kernel_ledger.py, only symbol names are read), the out_size= and
 --out-size argument handling, and tests/deliver_ref.py: its tolerances against the header's operation count and its float64 values
 against torch's bilinear interpolation on an upscale."""
 import importlib
-import os
 
 import numpy as np
 import pytest
@@ -17,7 +16,7 @@ assert "rrv_deliver_view_device" in L.SYMBOLS      # this file is about the deli
 FW = importlib.import_module("rerevst-code_amd.framework")
 D = importlib.import_module("rerevst-code_amd.driver")
 
-# ---- the ledger of librerevst_deliver.so: kernel symbol -> the test of tests/test_gpu_deliver.py that holds THAT instantiation to the
+# ---- the delivery stage's ledger: kernel symbol -> the test of tests/test_gpu_deliver.py that holds THAT instantiation to the
 # reference (deliver_k<OUT>, OUT the output form: float32 HWC / CHW, uint8 HWC / CHW, 8-bit YUV, uint16 YUV; each its own compile)
 GPU = "tests/test_gpu_deliver.py::"
 DELIVER_LEDGER = {
@@ -31,20 +30,7 @@ DELIVER_LEDGER = {
 
 
 def test_deliver_library_ledger():
-    build = importlib.import_module("rerevst-code_amd.build")
-    build.build_lib(verbose=False)
-    symbols = KL.symbols(build.DELIVER_LIB)
-    assert len(symbols) == len(set(symbols))
-    assert set(symbols) == set(DELIVER_LEDGER), (sorted(set(symbols) - set(DELIVER_LEDGER)), sorted(set(DELIVER_LEDGER) - set(symbols)))
-    assert len(set(DELIVER_LEDGER.values())) == len(DELIVER_LEDGER)      # one test each
-    for key, ref in DELIVER_LEDGER.items():
-        path, name = ref.split("::")
-        assert os.path.isfile(os.path.join(KL.ROOT, path)), (key, ref)
-        mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
-        assert callable(getattr(mod, name, None)), (key, ref)
-    # and the other two libraries hold none of them: their own ledgers stay what they were
-    assert not [s for s in KL.symbols(build.LIB) if "deliver" in s]
-    assert not [s for s in KL.symbols(build.SCALE_LIB) if "deliver" in s]
+    KL.check_stage_ledger(DELIVER_LEDGER, "deliver", one_test_each=True)
 
 
 def test_out_size_argument():

@@ -1,6 +1,6 @@
 """Guided delivery without a GPU: tests/guided_ref.py against what the arithmetic must do on inputs with a known answer, its committed
-yardstick against what the float32 restatement gives, the ledger of librerevst_guided.so (every kernel symbol of its gfx950 code object
-is named here and held by one test of tests/test_gpu_guided.py; the rule of tests/kernel_ledger.py, only symbol names are read), and the
+yardstick against what the float32 restatement gives, the stage's ledger (every gf_ kernel symbol of librerevst_stages.so's gfx950 code
+object is named here and held by one test of tests/test_gpu_guided.py; the rule of tests/kernel_ledger.py, only symbol names are read), and the
 guide= / --guided argument handling and video.guided_upsample.  Then what gf_apply_k's correctness rests on and no GPU is needed for: the
 tile rule (rrv_guided_tile against guided_ref.tile), the span bound on every table the library builds, and five deliberate flaws that the
 GPU test's bounds must reject."""
@@ -32,19 +32,7 @@ GUIDED_LEDGER = {
 
 
 def test_guided_library_ledger():
-    build = importlib.import_module("rerevst-code_amd.build")
-    build.build_lib(verbose=False)
-    symbols = KL.symbols(build.GUIDED_LIB)
-    assert len(symbols) == len(set(symbols))
-    assert set(symbols) == set(GUIDED_LEDGER), (sorted(set(symbols) - set(GUIDED_LEDGER)), sorted(set(GUIDED_LEDGER) - set(symbols)))
-    for key, ref in GUIDED_LEDGER.items():
-        path, name = ref.split("::")
-        assert os.path.isfile(os.path.join(KL.ROOT, path)), (key, ref)
-        mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
-        assert callable(getattr(mod, name, None)), (key, ref)
-    # and the other three libraries hold none of them: their own ledgers stay what they were
-    for lib in (build.LIB, build.SCALE_LIB, build.DELIVER_LIB):
-        assert not [s for s in KL.symbols(lib) if s.startswith("gf_")]
+    KL.check_stage_ledger(GUIDED_LEDGER, "gf_", one_test_each=False)
 
 
 def test_a_linear_model_is_recovered():
@@ -217,7 +205,7 @@ def test_span_bound_holds_on_every_table():
                 tiles, tight, third = tiles + a, tight + b, third + c
     print("span bound: %d tiles, %d with no slack, %d samples with a third tap" % (tiles, tight, third))
     assert tight > 0 and third > 0      # the bound is met with equality somewhere, and three-tap samples exist: neither assertion above is vacuous
-    first, count, w = _tables(7, 55)      # the example of csrc/deliver.hip
+    first, count, w = _tables(7, 55)      # the example of csrc/deliver_k.h
     assert count[27] == 3 and w[27, 1] == 1.0 and w[27, 2] == 0.0 and 0.0 < w[27, 0] < 1e-15
 
 

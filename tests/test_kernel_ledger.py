@@ -37,6 +37,16 @@ def test_every_kernel_has_one_entry_and_no_entry_is_stale(symbols):
     assert not stale, "ledger entries for kernels the library does not have: %s" % sorted(stale)
 
 
+def test_the_stages_library_is_the_three_stage_ledgers_and_the_main_library_holds_none_of_them(symbols):
+    from test_deliver_host import DELIVER_LEDGER
+    from test_guided_host import GUIDED_LEDGER
+    from test_resample_host import SCALE_LEDGER
+    assert len(SCALE_LEDGER) + len(DELIVER_LEDGER) + len(GUIDED_LEDGER) == len({**SCALE_LEDGER, **DELIVER_LEDGER, **GUIDED_LEDGER}) == 16
+    stages = KL.symbols(importlib.import_module("rerevst-code_amd.build").STAGES_LIB)
+    assert sorted(stages) == sorted([*SCALE_LEDGER, *DELIVER_LEDGER, *GUIDED_LEDGER]), stages
+    assert not [s for s in symbols if "resample" in s or "deliver" in s or "gf_" in s]
+
+
 def test_entries_are_well_formed_and_cited_tests_exist():
     for key, (kind, ref, what) in KL.LEDGER.items():
         assert kind in KINDS and what, key

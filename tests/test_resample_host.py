@@ -1,9 +1,8 @@
 """The resampler without a GPU: tests/resample_ref.py against torch's float64 antialiased interpolation, rrv_resample_taps against the
-reference tables, the ratio limits, and the ledger of librerevst_scale.so: every kernel symbol of its gfx950 code object is named here
+reference tables, the ratio limits, and the resampler's ledger: every resample_k symbol of librerevst_stages.so's gfx950 code object is named here
 and held by one test of tests/test_gpu_resample.py (the rule of tests/kernel_ledger.py; only symbol names are read)."""
 import ctypes as C
 import importlib
-import os
 
 import numpy as np
 import pytest
@@ -81,7 +80,7 @@ def test_ratio_limits_and_cap():
     assert rc == RRV_OK and w.shape == (24, 20) and not w[:, n:].any()
 
 
-# ---- the ledger of librerevst_scale.so: kernel symbol -> the test of tests/test_gpu_resample.py that compares THAT instantiation with
+# ---- the resampler's ledger: kernel symbol -> the test of tests/test_gpu_resample.py that compares THAT instantiation with
 # the float64 reference (resample_k<IN>, IN = conv_first_k's input form; each form is its own compile)
 GPU = "tests/test_gpu_resample.py::"
 SCALE_LEDGER = {
@@ -97,16 +96,4 @@ SCALE_LEDGER = {
 
 
 def test_scale_library_ledger():
-    build = importlib.import_module("rerevst-code_amd.build")
-    build.build_lib(verbose=False)
-    symbols = KL.symbols(build.SCALE_LIB)
-    assert len(symbols) == len(set(symbols))
-    assert set(symbols) == set(SCALE_LEDGER), (sorted(set(symbols) - set(SCALE_LEDGER)), sorted(set(SCALE_LEDGER) - set(symbols)))
-    assert len(set(SCALE_LEDGER.values())) == len(SCALE_LEDGER)      # one test each
-    for key, ref in SCALE_LEDGER.items():
-        path, name = ref.split("::")
-        assert os.path.isfile(os.path.join(KL.ROOT, path)), (key, ref)
-        mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
-        assert callable(getattr(mod, name, None)), (key, ref)
-    # and the main library holds none of them: its own ledger stays what it was
-    assert not [s for s in KL.symbols(build.LIB) if s.startswith("resample")]
+    KL.check_stage_ledger(SCALE_LEDGER, "resample", one_test_each=True)

@@ -20,7 +20,9 @@ run is recorded as "not measured", never estimated.
 Every leg is a process in a session of its own.  The first leg that exits non-zero or runs past --leg-timeout ends the measurement: its
 whole process group is killed, nothing more is started on the GPU, what was measured so far is written with "not measured" for the rest,
 and the tool exits non-zero.
-`--leg NAME` runs one leg (what the child processes do; RRV_LIB_PATH names the library)."""
+`--leg NAME` runs one leg (what the child processes do; RRV_LIB_PATH names the library).  FORM_CASES adds a 960 x 540 -> 1920 x 1080
+`trace:` leg for each output form (uint8 and float32, HWC and planar, P010): not part of the JSON, they let a comparison of two builds
+time every deliver_k<OUT> at one size (profiles/stages.txt)."""
 import argparse
 import csv
 import glob
@@ -41,6 +43,10 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # case: (working frame, delivered frame, output format, bytes per delivered pixel)
 KERNEL_CASES = {"1080_to_2160_nv12": ((1080, 1920), (2160, 3840), "nv12", 1.5), "1080_to_2160_u8": ((1080, 1920), (2160, 3840), "bgr", 3.0),
                 "1080_to_2160_p010": ((1080, 1920), (2160, 3840), "p010", 3.0), "540_to_1080_nv12": ((540, 960), (1080, 1920), "nv12", 1.5)}
+# one leg for each output form at 540 -> 1080 (every deliver_k<OUT> then has one at that size); main() measures the four above, `--leg trace:<case>` any
+FORM_CASES = {"540_to_1080_" + f: ((540, 960), (1080, 1920), f, b) for f, b in (("bgr", 3.0), ("u8_chw", 3.0), ("f32", 12.0), ("f32_chw", 12.0), ("p010", 3.0))}
+MEASURED = list(KERNEL_CASES)
+KERNEL_CASES.update(FORM_CASES)
 # host leg: (source frame, work_size or None, out_size or None, out_format)
 HOST_CASES = {"4k_u8_deliver": ((2160, 3840), (1080, 1920), "source", "bgr"), "4k_u8_work": ((2160, 3840), (1080, 1920), None, "bgr"),
               "4k_nv12_deliver": ((2160, 3840), (1080, 1920), "source", "nv12"), "4k_nv12_work": ((2160, 3840), (1080, 1920), None, "nv12"),
@@ -89,7 +95,10 @@ def leg_trace(pkg, case, repeats):
     (H, W), (DH, DW), fmt, _ = KERNEL_CASES[case]
     m = _model(pkg, H, W)
     x = torch.from_numpy(_source(FRAMES_PER_CALL, H, W)).cuda()
-    kw = dict(out_layout="nhwc", out_dtype=torch.uint8) if fmt == "bgr" else dict(out_layout=fmt)
+    if fmt in ("bgr", "u8_chw", "f32", "f32_chw"):
+        kw = dict(out_layout="nchw" if fmt.endswith("_chw") else "nhwc", out_dtype=torch.float32 if fmt.startswith("f32") else torch.uint8)
+    else:
+        kw = dict(out_layout=fmt)
     torch.cuda.synchronize()
     for _ in range(repeats + 1):
         m.transfer_tensor(x, layout="nhwc", pad_crop=True, out_size=(DH, DW), **kw)
@@ -205,10 +214,10 @@ def measure(a, res):
     """Every leg in order, each in a process of its own; the first one that fails ends the measurement (the exception leaves here)."""
     if not a.skip_kernel_legs:
         if shutil.which("rocprofv3") is None:
-            for case in KERNEL_CASES:
+            for case in MEASURED:
                 res["kernel_" + case] = "not measured (rocprofv3 not found)"
         else:
-            for case in KERNEL_CASES:
+            for case in MEASURED:
                 res["kernel_" + case] = kernel_leg(case, a)
     if a.skip_host_legs:
         return
@@ -256,7 +265,7 @@ def main():
                           "leg; ms per call, medians over %d calls after a warm-up call" % a.kernel_repeats,
            "host_legs": "uint8 BGR frames, %d per call at 512 x 512 and %d at 3840 x 2160, page-locked buffers, staged copies, profiler off, %d repeats"
                         % (a.frames, a.frames_4k, a.repeats)}
-    keys = ["kernel_" + c for c in KERNEL_CASES] + ["host_plain_512", "host_plain_512_parent"] + ["host_" + c for c in HOST_CASES if c != "plain"]
+    keys = ["kernel_" + c for c in MEASURED] + ["host_plain_512", "host_plain_512_parent"] + ["host_" + c for c in HOST_CASES if c != "plain"]
     failed = None
     try:
         measure(a, res)

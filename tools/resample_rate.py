@@ -18,7 +18,9 @@ recorded as "not measured", never estimated.
 Every leg is a process in a session of its own.  The first leg that exits non-zero or runs past --leg-timeout ends the measurement: its
 whole process group is killed, nothing more is started on the GPU, what was measured so far is written with "not measured" for the rest,
 and the tool exits non-zero.
-`--leg NAME` runs one leg (what the child processes do; RRV_LIB_PATH names the library)."""
+`--leg NAME` runs one leg (what the child processes do; RRV_LIB_PATH names the library).  FORM_CASES adds a 1920 x 1080 -> 960 x 540
+`trace:` leg for each input form the measured cases do not read (uint8 planar, float32 HWC and planar, I420, ten-bit planar and P010):
+not part of the JSON, they let a comparison of two builds time every resample_k<IN> (profiles/stages.txt)."""
 import argparse
 import csv
 import glob
@@ -38,6 +40,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_CASES = {"2160_nv12": ((2160, 3840), (1080, 1920), "nv12"), "2160_bgr": ((2160, 3840), (1080, 1920), "bgr"),
                 "1080_nv12": ((1080, 1920), (540, 960), "nv12"), "1080_bgr": ((1080, 1920), (540, 960), "bgr")}
+# one leg for each input form the four above do not read (every resample_k<IN> then has one); main() measures the four, `--leg trace:<case>` any
+FORM_CASES = {"1080_" + f: ((1080, 1920), (540, 960), f) for f in ("u8_chw", "f32", "f32_chw", "i420", "i420p10", "p010")}
+KERNEL_CASES.update(FORM_CASES)
+MEASURED = [c for c in KERNEL_CASES if c not in FORM_CASES]
+SOURCE_BYTES = {"bgr": 3.0, "u8_chw": 3.0, "f32": 12.0, "f32_chw": 12.0, "nv12": 1.5, "i420": 1.5, "i420p10": 3.0, "p010": 3.0}      # per source pixel
 FRAMES_PER_CALL = 16
 PEAK_BYTES_S, PEAK_FP32_S = 8.0e12, 157.3e12
 
@@ -71,9 +78,15 @@ def _model(pkg, H, W):
 
 
 def _source(fmt, n, H, W, seed=3):
-    """n random source frames: uint8 BGR [n][H][W][3], or NV12 bytes [n][H*W*3/2] (even H, W)"""
+    """n random source frames: uint8 BGR [n][H][W][3] ("f32": float32; "_chw": planar [n][3][H][W]), or 4:2:0 samples [n][H*W*3/2] (even
+    H, W): bytes, or ten-bit codes as int16 (the bits of uint16; "p010" keeps them in the high bits)"""
     rng = np.random.default_rng(seed)
-    base = rng.integers(0, 256, (4, H, W, 3) if fmt == "bgr" else (4, H * W * 3 // 2), dtype=np.uint8)
+    if fmt in ("i420p10", "p010"):
+        base = (rng.integers(0, 1024, (4, H * W * 3 // 2), dtype=np.uint16) << (6 if fmt == "p010" else 0)).view(np.int16)
+    elif fmt in ("nv12", "i420"):
+        base = rng.integers(0, 256, (4, H * W * 3 // 2), dtype=np.uint8)
+    else:
+        base = rng.integers(0, 256, (4, 3, H, W) if fmt.endswith("_chw") else (4, H, W, 3), dtype=np.uint8).astype(np.float32 if fmt.startswith("f32") else np.uint8)
     return base[np.arange(n) % 4]
 
 
@@ -83,7 +96,7 @@ def leg_trace(pkg, case, repeats):
     (SH, SW), (H, W), fmt = KERNEL_CASES[case]
     m = _model(pkg, H, W)
     x = torch.from_numpy(_source(fmt, FRAMES_PER_CALL, SH, SW)).cuda()
-    kw = dict(layout="nhwc") if fmt == "bgr" else dict(layout="nv12", size=(SH, SW))
+    kw = dict(layout="nchw" if fmt.endswith("_chw") else "nhwc") if fmt in ("bgr", "u8_chw", "f32", "f32_chw") else dict(layout=fmt, size=(SH, SW))
     torch.cuda.synchronize()
     for _ in range(repeats + 1):
         m.transfer_tensor(x, pad_crop=True, out_layout="nhwc", work_size=(H, W), **kw)
@@ -99,7 +112,7 @@ def algorithmic(case):
     sys.path.insert(0, HERE)
     taps = importlib.import_module("rerevst-code_amd.framework").resample_taps
     ny, nx = taps(SH, H)[1].astype(np.int64), taps(SW, W)[1].astype(np.int64)
-    bytes_ = ((1.5 if fmt == "nv12" else 3.0) * SH * SW + 12.0 * H * W) * FRAMES_PER_CALL
+    bytes_ = (SOURCE_BYTES[fmt] * SH * SW + 12.0 * H * W) * FRAMES_PER_CALL
     ops = 2.0 * 3 * (float(nx.sum()) * SH + float(ny.sum()) * W) * FRAMES_PER_CALL      # horizontal pass over the source rows, vertical over the columns
     return bytes_, ops
 
@@ -197,10 +210,10 @@ def measure(a, res):
     """Every leg in order, each in a process of its own; the first one that fails ends the measurement (the exception leaves here)."""
     if not a.skip_kernel_legs:
         if shutil.which("rocprofv3") is None:
-            for case in KERNEL_CASES:
+            for case in MEASURED:
                 res["kernel_" + case] = "not measured (rocprofv3 not found)"
         else:
-            for case in KERNEL_CASES:
+            for case in MEASURED:
                 res["kernel_" + case] = kernel_leg(case, a)
     if a.skip_host_legs:
         return
@@ -241,7 +254,7 @@ def main():
     res = {"kernel_legs": "16 frames per call, pad / crop, float32 BGR out; rocprofv3 --kernel-trace --stats, one run per leg; ms per call, medians over "
                           "%d calls after a warm-up call" % a.kernel_repeats,
            "host_legs": "%d uint8 BGR frames per call, page-locked buffers, staged copies, profiler off, %d repeats" % (a.frames, a.repeats)}
-    keys = ["kernel_" + c for c in KERNEL_CASES] + ["host_plain_540", "host_plain_540_parent", "host_scaled_1080_to_540"]
+    keys = ["kernel_" + c for c in MEASURED] + ["host_plain_540", "host_plain_540_parent", "host_scaled_1080_to_540"]
     failed = None
     try:
         measure(a, res)
