@@ -820,6 +820,41 @@ int rrv_debug_prep_stop(rrv_handle h, int stage);
 #define RRV_DBG_PREP_MAP 25
 int rrv_debug_copy_prep_tensor(rrv_handle h, int index, int image, float* host, size_t cap, size_t* floats, int* H, int* W, int* C);
 
+/* Weight read-back (tests/test_gpu_packs.py): every weight buffer the handle holds in HBM after rrv_finalize_weights, as the
+ * kernels read it.  rrv_debug_weight_count returns how many there are (>= 0), RRV_E_ARG for a null handle, RRV_E_STATE before
+ * rrv_finalize_weights.  Buffer `index` (0 .. count - 1, in a fixed order: the convolutions by checkpoint key, conv1_1, Decoder.slice1,
+ * the folded KernelFilters) is described by rrv_debug_weight_info: *key (at most keycap bytes with the terminator; RRV_E_ARG when it
+ * does not fit) is the checkpoint prefix of the convolution ("Decoder.Filter<f>.fold_down" / ".fold_up" for a folded KernelFilter),
+ * *form one of
+ *   RRV_DBG_W_RAW         OIHW as in the checkpoint (a fold: the folded product), Cout * Cin * taps floats
+ *   RRV_DBG_W_PK          the direct-form pack [Cout/BN][Cin/16][taps][BN][16], *BN its tile
+ *   RRV_DBG_W_PK_WINO     the F(2x2,3x3) pack [Cout/32][Cin/16][16][32][16]
+ *   RRV_DBG_W_PK_UPS      the nine-product upsample pack [Cout/32][Cin/16][9][32][16]
+ *   RRV_DBG_W_PK_UPS_SC   the five-product upsample pack with the 1 x 1 shortcut [Cout/32][Cin/16][26][32][16]
+ *   RRV_DBG_W_PK_F43      the F(4x4,3x3) pack [Cout/32][Cin/8][36][16][4][2][2]
+ *   RRV_DBG_W_BIAS        [Cout] (zeros for a bias-free convolution; a folded down_sample: 256 floats, 32 biases and zeros)
+ *   RRV_DBG_W_FIRST       conv1_1 as [27][64];  RRV_DBG_W_FIRST_GREY its grey fold, 1216 floats
+ *   RRV_DBG_W_LAST        Decoder.slice1 as conv_last_k's MFMA operands [2][4][64][4];  its RRV_DBG_W_BIAS has 4 floats
+ * *Cout, *Cin, *taps the convolution's shape, *sets the number of state sets that have a buffer of their own (1: a checkpoint weight;
+ * the folded KernelFilters: the handle's state sets), *floats the size of one.  Any out pointer may be null.
+ * rrv_debug_copy_weights copies buffer `index` of state set `set` (0 unless *sets > 1) to the host after a full synchronisation;
+ * *floats receives its size, nothing is copied when cap is smaller.  RRV_E_ARG for a bad index or set, RRV_E_STATE for the folded
+ * weights of a set no launch or state change has folded yet; rrv_last_error says which. */
+#define RRV_DBG_W_RAW 0
+#define RRV_DBG_W_PK 1
+#define RRV_DBG_W_PK_WINO 2
+#define RRV_DBG_W_PK_UPS 3
+#define RRV_DBG_W_PK_UPS_SC 4
+#define RRV_DBG_W_PK_F43 5
+#define RRV_DBG_W_BIAS 6
+#define RRV_DBG_W_FIRST 7
+#define RRV_DBG_W_FIRST_GREY 8
+#define RRV_DBG_W_LAST 9
+int rrv_debug_weight_count(rrv_handle h);
+int rrv_debug_weight_info(rrv_handle h, int index, char* key, size_t keycap, int* form, int* Cout, int* Cin, int* taps, int* BN, int* sets,
+                          size_t* floats);
+int rrv_debug_copy_weights(rrv_handle h, int index, int set, float* host, size_t cap, size_t* floats);
+
 /* Stream-ordered use of the *_device entries from a caller that produces / consumes the buffers on its own HIP
  * stream (e.g. torch.cuda.current_stream().cuda_stream): see ORDERING above.  enable = 0 switches it off. */
 int rrv_set_caller_stream(rrv_handle h, void* hip_stream, int enable);

@@ -46,6 +46,8 @@ DBG_STATE_SET, DBG_STYLE_PRED, DBG_STYLE_BLOB = 0, 1, 2
 PREP_TENSORS = ("cn", "nxt", "t32", "d32", "u", "xs4", "a4", "o4", "xs3", "a3", "o3", "xs2", "a2", "o2", "content", "grp", "f0",
                 "su1", "su2", "su3", "patch", "style_c11", "style_c21", "style_c31", "style_c41", "map")
 DBG_PREP_PATCH, DBG_PREP_STYLE_C11, DBG_PREP_MAP = 20, 21, 25
+# rrv_debug_weight_info: the forms of a weight buffer (RRV_DBG_W_*), by value
+WEIGHT_FORMS = ("raw", "pk", "pk_wino", "pk_ups", "pk_ups_sc", "pk_f43", "bias", "first", "first_grey", "last")
 
 # name -> (restype, argtypes); must list every symbol declared in include/rerevst_hip.h
 SYMBOLS = {
@@ -172,6 +174,10 @@ SYMBOLS = {
     "rrv_debug_prep_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "rrv_debug_copy_prep_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rrv_debug_weight_count": (C.c_int, [C.c_void_p]),
+    "rrv_debug_weight_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "rrv_debug_copy_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrv_set_grid_share": (C.c_int, [C.c_void_p, C.c_int]),
     "rrv_set_caller_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rrv_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -394,7 +394,7 @@ __device__ __forceinline__ void conv_ups5_body() {
 }
 
 // U = G g G^T of the upsample-fused form above, in double and rounded once, packed as [Cout/32][Cin/16][26 blocks][32 couts]
-// [16 floats] with the pieces XOR-swizzled by (cout>>2)&3 (pack_wino_k's image); block 25 = the 1x1 shortcut / 4.
+// [16 floats] with the pieces XOR-swizzled by -(cout>>2)&3 (pack_wino_k's image); block 25 = the 1x1 shortcut / 4.
 __global__ void pack_ups5_k(const float* __restrict__ w, const float* __restrict__ wsc, float* __restrict__ dst, int Cout, int Cin) {
     constexpr int CH = 16, NUB = Ups5Geo::NUB;
     const size_t total = (size_t)Cout * Cin * NUB;

@@ -547,7 +547,8 @@ __global__ __launch_bounds__(NW * 64, (SC ? Ups5Geo::OCC : WinoGeo<NW, UPS>::OCC
 }
 
 // Weight transform U = G g G^T, packed as [Cout/32][Cin/16][pos][32 couts][16 floats]; the 16-byte pieces are
-// XOR-swizzled by (cout>>2)&3.  ups = 0: G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (16 positions);
+// XOR-swizzled by -(cout>>2)&3 (piece q of cout j is stored at q ^ (0,3,2,1)[(j>>2)&3]; offU of the LDS readers undoes it).
+// ups = 0: G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (16 positions);
 // ups = 1: G = [[1,1,1],[1,0,0],[0,0,1]] (9 positions, the upsample-fused form above).
 __global__ void pack_wino_k(const float* __restrict__ w, float* __restrict__ dst, int Cout, int Cin, int ups) {
     constexpr int CH = 16;

@@ -243,7 +243,7 @@ struct rrv_ctx {
     // passes the first set and the strides, the kernels index by image.
     static constexpr int MS_GROUP_MAX = 16;      // multi-style frames per launch sequence (each with its own blended state set)
     static constexpr int N_SETS = 2 * MS_GROUP_MAX;      // two groups in flight.  9.9 MB per set (state blob + three KernelFilters' folded raw and packed weights), 316 MB of the 288 GB per handle, allocated once by rrv_finalize_weights
-    struct StateSet { float* active = nullptr; ConvW fold_down[3], fold_up[3]; } sets[N_SETS];
+    struct StateSet { float* active = nullptr; ConvW fold_down[3], fold_up[3]; unsigned folded = 0; } sets[N_SETS];      // folded: bit f = fold_filters has written KernelFilter f's weights (rrv_debug_copy_weights)
     StateSet* slot_sets(int slot) { return &sets[MS_GROUP_MAX * slot]; }      // the first of the slot's sixteen sets.  Slots 0 and 1 only: the others own none (the grouped models alternate over these two, next_frame_slot)
     float* fold_tmp = nullptr;                 // OIHW scratch for folds (512*32*9 floats)
     StyleState styles[RRV_MAX_STYLES];
@@ -941,6 +941,7 @@ int fold_filters(rrv_handle h, const Seq& q, const float* blob, int f /*0..2*/, 
     ConvW& fd = q.set->fold_down[f];
     ConvW& fu = q.set->fold_up[f];
     h->slots[(q.set - h->sets) / rrv_ctx::MS_GROUP_MAX].set_images = 0;      // the slot's sets are being rewritten; a per-image-state launch counts its images once it is queued
+    for (int i = 0; i < nsets; ++i) q.set[i].folded |= 1u << f;
     const float* F1 = blob + SL.filt[2 * f];
     const float* F2 = blob + SL.filt[2 * f + 1];
     hipLaunchKernelGGL(fold_down_k, dim3((32 * 512 * 9 + 255) / 256, nsets), dim3(256), 0, q.stream, F1, (const float*)wd.raw,
@@ -4495,6 +4496,99 @@ int rrv_debug_copy_prep_tensor(rrv_handle h, int index, int image, float* host, 
     if (W) *W = t.W;
     if (C) *C = t.C;
     if (host && cap >= n) HIPCHK(hipMemcpy(host, t.p + (size_t)(image - first) * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RRV_OK;
+}
+
+// ---- weight read-back (tests/test_gpu_packs.py) ----------------------------------------------------------------------------------------
+// One row per buffer, in the order the header promises.  p: the buffer (a folded KernelFilter's: state set 0's); fold: 0 a checkpoint
+// weight, 1 + f / 4 + f the folded down / up weights of KernelFilter f (one buffer per state set).
+namespace {
+struct WRef { std::string key; int form; const float* p; size_t floats; int Cout, Cin, taps, BN, fold; };
+std::vector<WRef> weight_list(rrv_handle h) {
+    std::vector<WRef> v;
+    auto add = [&](const std::string& key, int form, const float* p, size_t floats, const ConvW& w, int fold = 0) {
+        if (p) v.push_back({key, form, p, floats, w.Cout, w.Cin, w.taps, form == RRV_DBG_W_PK ? w.BN : 0, fold});
+    };
+    for (const auto& kv : h->conv) {
+        const ConvW& w = kv.second;
+        const size_t n = (size_t)w.Cout * w.Cin;
+        add(kv.first, RRV_DBG_W_RAW, w.raw, n * w.taps, w);
+        add(kv.first, RRV_DBG_W_PK, w.pk, n * w.taps, w);
+        add(kv.first, RRV_DBG_W_PK_WINO, w.pk_wino, n * 16, w);
+        add(kv.first, RRV_DBG_W_PK_UPS, w.pk_ups, n * 9, w);
+        add(kv.first, RRV_DBG_W_PK_UPS_SC, w.pk_ups_sc, n * Ups5Geo::NUB, w);
+        add(kv.first, RRV_DBG_W_PK_F43, w.pk_f43, n * 36, w);
+        add(kv.first, RRV_DBG_W_BIAS, w.bias, (size_t)w.Cout, w);
+    }
+    ConvW first; first.Cout = 64; first.Cin = 3; first.taps = 9;
+    for (int which = 0; which < 2; ++which) {
+        add(enc_key(which, 0), RRV_DBG_W_FIRST, h->first_w[which], 27 * 64, first);
+        if (which == 0) add(enc_key(0, 0), RRV_DBG_W_FIRST_GREY, h->first_wg, 1216, first);
+        add(enc_key(which, 0), RRV_DBG_W_BIAS, h->first_b[which], 64, first);
+    }
+    ConvW last; last.Cout = 3; last.Cin = 64; last.taps = 9;
+    add("Decoder.slice1", RRV_DBG_W_LAST, h->last_w, 2 * 4 * 64 * 4, last);
+    add("Decoder.slice1", RRV_DBG_W_BIAS, h->last_b, 4, last);
+    for (int f = 0; f < 3; ++f) {
+        char pre[64];
+        snprintf(pre, sizeof pre, "Decoder.Filter%d.fold_", f + 1);
+        const ConvW &fd = h->sets[0].fold_down[f], &fu = h->sets[0].fold_up[f];
+        add(std::string(pre) + "down", RRV_DBG_W_RAW, fd.raw, (size_t)32 * 512 * 9, fd, 1 + f);
+        add(std::string(pre) + "down", RRV_DBG_W_BIAS, fd.bias, 256, fd, 1 + f);
+        add(std::string(pre) + "down", RRV_DBG_W_PK_WINO, fd.pk_wino, (size_t)32 * 512 * 16, fd, 1 + f);
+        add(std::string(pre) + "up", RRV_DBG_W_RAW, fu.raw, (size_t)512 * 32 * 9, fu, 4 + f);
+        add(std::string(pre) + "up", RRV_DBG_W_PK_WINO, fu.pk_wino, (size_t)512 * 32 * 16, fu, 4 + f);
+    }
+    return v;
+}
+}  // namespace
+
+int rrv_debug_weight_count(rrv_handle h) {
+    if (!h) return RRV_E_ARG;
+    if (!h->finalized) return fail(h, RRV_E_STATE, "debug_weight_count: the weights are not finalized");
+    return (int)weight_list(h).size();
+}
+
+int rrv_debug_weight_info(rrv_handle h, int index, char* key, size_t keycap, int* form, int* Cout, int* Cin, int* taps, int* BN, int* sets,
+                          size_t* floats) {
+    if (!h) return RRV_E_ARG;
+    if (!h->finalized) return fail(h, RRV_E_STATE, "debug_weight_info: the weights are not finalized");
+    const std::vector<WRef> v = weight_list(h);
+    if (index < 0 || index >= (int)v.size()) return fail(h, RRV_E_ARG, "debug_weight_info: no weight buffer " + std::to_string(index));
+    const WRef& r = v[(size_t)index];
+    if (key) {
+        if (r.key.size() + 1 > keycap) return fail(h, RRV_E_ARG, "debug_weight_info: the key needs " + std::to_string(r.key.size() + 1) + " bytes");
+        memcpy(key, r.key.c_str(), r.key.size() + 1);
+    }
+    if (form) *form = r.form;
+    if (Cout) *Cout = r.Cout;
+    if (Cin) *Cin = r.Cin;
+    if (taps) *taps = r.taps;
+    if (BN) *BN = r.BN;
+    if (sets) *sets = r.fold ? rrv_ctx::N_SETS : 1;
+    if (floats) *floats = r.floats;
+    return RRV_OK;
+}
+
+int rrv_debug_copy_weights(rrv_handle h, int index, int set, float* host, size_t cap, size_t* floats) {
+    if (!h || !floats) return RRV_E_ARG;
+    if (!h->finalized) return fail(h, RRV_E_STATE, "debug_copy_weights: the weights are not finalized");
+    const std::vector<WRef> v = weight_list(h);
+    if (index < 0 || index >= (int)v.size()) return fail(h, RRV_E_ARG, "debug_copy_weights: no weight buffer " + std::to_string(index));
+    const WRef& r = v[(size_t)index];
+    if (set < 0 || set >= (r.fold ? rrv_ctx::N_SETS : 1)) return fail(h, RRV_E_ARG, "debug_copy_weights: " + r.key + " has no state set " + std::to_string(set));
+    const float* p = r.p;
+    if (r.fold) {
+        const int f = (r.fold - 1) % 3;
+        if (!(h->sets[set].folded >> f & 1u))
+            return fail(h, RRV_E_STATE, "debug_copy_weights: nothing has folded " + r.key + " of state set " + std::to_string(set));
+        const ConvW& w = r.fold <= 3 ? h->sets[set].fold_down[f] : h->sets[set].fold_up[f];
+        p = r.form == RRV_DBG_W_RAW ? w.raw : r.form == RRV_DBG_W_BIAS ? w.bias : w.pk_wino;
+    }
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(sync_all(h));
+    *floats = r.floats;
+    if (host && cap >= r.floats) HIPCHK(hipMemcpy(host, p, r.floats * sizeof(float), hipMemcpyDeviceToHost));
     return RRV_OK;
 }
 

@@ -1367,6 +1367,29 @@ class Stylization():
         self._chk(self._lib.rrv_debug_copy_prep_tensor(self._h, idx, int(image), out.ctypes.data_as(C.c_void_p), n.value, *tail))
         return out.reshape(H.value + 2, W.value + 2, Ch.value)
 
+    def debug_weights(self):
+        """Every weight buffer the handle holds in HBM, in the library's order (rrv_debug_weight_count / _info): yields
+        (info, read) with info = {"key", "form" (_lib.WEIGHT_FORMS), "Cout", "Cin", "taps", "BN", "sets", "floats"} and read(set=0)
+        the buffer of that state set as flat float32 (rrv_debug_copy_weights; `sets` > 1: the folded KernelFilter weights, refused
+        for a set nothing has folded)."""
+        count = self._lib.rrv_debug_weight_count(self._h)
+        if count < 0:
+            self._chk(count)
+        for i in range(count):
+            key = C.create_string_buffer(128)
+            form, cout, cin, taps, bn, sets, n = [C.c_int(0) for _ in range(6)] + [C.c_size_t(0)]
+            self._chk(self._lib.rrv_debug_weight_info(self._h, i, key, len(key), C.byref(form), C.byref(cout), C.byref(cin), C.byref(taps), C.byref(bn),
+                                                      C.byref(sets), C.byref(n)))
+            info = {"key": key.value.decode(), "form": _lib.WEIGHT_FORMS[form.value], "Cout": cout.value, "Cin": cin.value, "taps": taps.value,
+                    "BN": bn.value, "sets": sets.value, "floats": n.value}
+
+            def read(set=0, i=i, floats=n.value):
+                out, got = np.empty(floats, np.float32), C.c_size_t(0)
+                self._chk(self._lib.rrv_debug_copy_weights(self._h, i, int(set), out.ctypes.data_as(C.c_void_p), out.size, C.byref(got)))
+                assert got.value == floats
+                return out
+            yield info, read
+
     def _set_matrix(self, set8, set16, matrix_of, input_side, standard, full_range, bits):
         """set_yuv_matrix / set_yuv_input_matrix: the side's 8-bit or uint16 setter, its depth, and matrix_of(standard, full_range, bits)"""
         bits = _yuv_depth(bits)

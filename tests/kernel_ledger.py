@@ -3,7 +3,6 @@ code object (symbols() below: tools/isa_diff.py kernels() on the built library, 
 to one entry (kind, what):
   layer        a float64 layer reference of the kernel's own GPU input: ("file::test", how the test proves that THIS kernel ran)
   entry        an entry-level reference, or bit-identity to a `layer`-checked instantiation: ("file::test", what it compares)
-  indirect     a pack / fold kernel whose only consumers are `layer`-checked convolutions: (the consumer's key, what it produces)
   debug        dbg_*: (None, what it is for)
   unreachable  compiled, but no lookup can select it: (None, the lookup that never does)
 Every instantiation is its own compile here (inline-asm MFMAs, pinned AGPRs, 150 KB of LDS), and one instantiation alone has been
@@ -67,6 +66,7 @@ FM = "tests/test_gpu_frame_mode_layers.py::"
 MK = "tests/test_gpu_mask_layers.py::"
 PL = "tests/test_gpu_prep_layers.py::"
 IN = "tests/test_gpu_instantiations.py::"
+PK = "tests/test_gpu_packs.py::"
 
 LEDGER = {}
 
@@ -145,15 +145,19 @@ _add("layer", "blend_sets_k", FM + "test_grouped_multistyle_launch_state_sets_an
 _add("layer", ["mask_norm_k", "mask_filter_k"] + ["mask_pyramid_k<%d>" % s for s in range(1, 9)], MK + "test_every_masked_stage",
      "mask_families asserts the 37-launch sequence; S = 1 .. 8 each have a case; level masks bit for bit, families mnorm / mfilt")
 
-# ---- packs and folds: correct exactly when their consumer is ---------------------------------------------------------------------------------
-_add("indirect", "pack_wino_k", "conv_wino_split_k<1, 0>", "the F(2x2,3x3) and the nine-product upsample packs")
-_add("indirect", "pack_f43_k", "conv_f43_k<1, 0>", "the F(4x4,3x3) pack")
-_add("indirect", "pack_ups5_k", "conv_wino_k<6, 0, 4, 1, 1, 0>", "the five-product pack with the 1 x 1 shortcut")
-_add("indirect", "pack_conv_k", "conv_mfma_k<128, 1, 0, 0, 0, 1>", "the direct-form pack")
-_add("indirect", ["pack_first_k", "pack_first_grey_k"], "conv_first_k<0>", "conv1_1's weights (colour for the style encoder, the grey fold for the content encoder)")
-_add("indirect", "pack_last_k", "conv_last_k<false, false, 0, false, false>", "Decoder.slice1's weights")
-_add("indirect", "fold_down_k", "conv_wino_split_k<0, 0>", "F1 folded into KernelFilter.down_sample, per state set")
-_add("indirect", "fold_up_k", "conv_wino_split_k<8, 0>", "F2 folded into KernelFilter.upsample, per state set")
+# ---- packs and folds: each buffer a handle holds, read back (rrv_debug_copy_weights) and held to a reference of its own ------------------------
+# The read-back walks the handle's own ConvW / first_w / last_w / state-set pointers, the ones every launch passes to its kernel, and
+# test_the_enumeration_is_the_cases pins the walk to the cases: the buffer a case reads is the buffer that kernel wrote.
+BUF = PK + "test_buffer_against_its_reference"
+_add("layer", "pack_wino_k", BUF, "every pk_wino (16 positions; the folded KernelFilters' at 32 and at 32 x nsets couts) and pk_ups (9 positions) buffer: float32, n = 4")
+_add("layer", "pack_f43_k", BUF, "every pk_f43 buffer: each element the one rounding of the extended-precision U")
+_add("layer", "pack_ups5_k", BUF, "every pk_ups_sc buffer: the 25 positions rounded once, the shortcut block w / 4 exactly")
+_add("layer", "pack_conv_k", BUF, "every pk buffer at BN 32, 64 and 128, 1 and 9 taps: bit for bit")
+_add("layer", "pack_first_k", BUF, "the `first` buffers of both encoders: bit for bit")
+_add("layer", "pack_first_grey_k", BUF, "Encoder.slice.0's first_grey buffer: W1, W0 and the folded bias, float32 with n = 3 / 4 / 29")
+_add("layer", "pack_last_k", BUF, "Decoder.slice1's `last` buffer with its zero rows 27..31: bit for bit")
+_add("layer", "fold_down_k", BUF, "Decoder.Filter<f>.fold_down raw and bias: set 0 under two states in turn, sets 0..2 of a grouped launch each on its own F1; image 1 on set 0's fails")
+_add("layer", "fold_up_k", BUF, "Decoder.Filter<f>.fold_up raw: the same sets on their own F2; image 1 on set 0's fails")
 
 # ---- debug -------------------------------------------------------------------------------------------------------------------------------
 _add("debug", ["dbg_poke_k", "(anonymous namespace)::dbg_check_k", "(anonymous namespace)::dbg_fill_k"], None, "rrv_set_debug's canaries and self-test")

@@ -49,7 +49,8 @@ import torch.nn.functional as TF
 
 U = 2.0 ** -24
 
-FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "mnorm", "mfilt", "pstat", "gemm", "ppred")
+FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "mnorm", "mfilt", "pstat", "gemm", "ppred",
+            "once", "pack32", "grey", "fold")      # the last four: the weight packs and folds (tests/pack_ref.py)
 
 # max |gpu - ref| / (2^-24 m) per family, over every tap and shape of tests/test_gpu_layers.py on an MI355X (the worst tap):
 #   direct  30.7  c11 (conv_first: the grey fold multiplies 1/std into the weights, so its rounding is relative to the
@@ -95,12 +96,23 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "m
 #   d  direct-form encoder (conv_mfma_k on 3 x 3 layers) gemm 5.74 (c21, image 4 of 5 x 40 x 56; per tap 3.2 .. 5.7: K = 2304 at most,
 #                                                        against 7.95 at K = 4608 in the preparation pass)
 # Every negative control (an image on its neighbour's state set) landed at 1.1e3 .. 3.9e4 of its bound.
+# and the four families of the weight packs and folds (tests/pack_ref.py), over every buffer of tests/test_gpu_packs.py on
+# synthetic_weights(0) (profiles/packs.txt).  Each has a derived cap n, the float32 roundings on an element's path (the docstring of
+# tests/test_gpu_packs.py); K is that cap where the measured maximum reaches a quarter of it, else 2 x the measured maximum, rounded up:
+#   once     0.5  pack_f43_k and pack_ups5_k, in ulp32 of the extended-precision value: every element is the one rounding of it
+#                 (cap 1/2 + 2^-20 for the order of the kernel's float64 evaluation; 0.5 measured on every buffer)
+#   pack32   2.60 pack_wino_k, pk_wino of Encoder.slice.10 (cap n = 4, so K = 4; the nine-product form 2.21, the folded
+#                 KernelFilters' packs 2.02 .. 2.48, at one set and set-major alike)
+#   grey     1.83 pack_first_grey_k (caps 3 / 4 / 29 for W1 / W0 / the folded bias; K = 4 applies under each part's own cap)
+#   fold     5.44 fold_up_k, image 1 of the grouped launch (cap n = 32, so K = 11; fold_down_k 4.92, its bias 3.01: a 32-term
+#                 float32 sum against sum |F||W|)
+# Image 1's folded weights on image 0's filter (the control): ratios 3.0e6 .. 8.4e6, its pack on image 0's folded weights 7e10 and more.
 MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314,
-            "pstat": 4.24, "gemm": 7.95, "ppred": 1.91}
+            "pstat": 4.24, "gemm": 7.95, "ppred": 1.91, "once": 0.5, "pack32": 2.60, "grey": 1.83, "fold": 5.44}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
 # still rejecting the defects tests/test_layer_ref.py injects (the smallest of them, one weight off by 2^-8, is at 2480)
 K = {"direct": 62.0, "f23": 8.0, "ups": 19.0, "f43": 25.0, "splitk": 0.5, "stat": 6.0, "point": 8.0, "pred": 2.5, "mnorm": 8.0, "mfilt": 0.7,
-     "pstat": 9.0, "gemm": 16.0, "ppred": 4.0}
+     "pstat": 9.0, "gemm": 16.0, "ppred": 4.0, "once": 0.5 + 2.0 ** -20, "pack32": 4.0, "grey": 4.0, "fold": 11.0}
 
 # the tap indices of rrv_debug_copy_tensor_ex
 TAP_NAMES = ["c11", "p1", "c21", "p2", "c31", "c32", "c33", "p3", "c41",
@@ -618,3 +630,126 @@ def blend_ref(blobs, wts):
     wts = np.asarray(wts, np.float32).astype(np.float64)
     b = np.stack([np.asarray(x, np.float32).astype(np.float64) for x in blobs])
     return wts @ b, np.abs(wts) @ np.abs(b)
+
+
+# ---- clamp ends on every channel ----------------------------------------------------------------------------------------------------------
+# With the golden states the clamps of norm() touch 2e-4 .. 2e-3 of the values, so a kernel that stages lo / hi of the wrong channel for
+# some lanes, or swaps the ends, is seen only where the few clamping channels happen to lie.  clamp_state() builds a state whose ends cut
+# into every channel at every norm point; clamp_conditions() says whether they do.
+CLAMP_Q = (30.0, 70.0)      # the percentiles of a channel's pre-clamp value that become lo and hi
+NORM_OFF = [4 * sum(NORM_CH[:n]) for n in range(len(NORM_CH))]
+# norm point -> (the taps its kernel reads, the tap it writes, the style entry of the AdaIN behind it or None)
+NORM_POINTS = {0: (("p3",), "c41", None), 1: (("d", "f2"), "f3", 3)}
+for _blk, _xin, _xs, _a, _o in FRAME_BLOCKS:
+    NORM_POINTS[RES[_blk][0]] = ((_xin,), _a, None)
+    NORM_POINTS[RES[_blk][1]] = ((_a,), None, None)           # norm2: its clamped value lives only inside conv2's epilogue
+    NORM_POINTS[RES[_blk][2]] = ((_a, _xs), _o, RES[_blk][3])
+ATOM = 0.5      # a channel with more than this share of its pre-clamp values on ONE value cannot have 0.2 at lo, at hi and inside
+
+
+def norm_pre(n, get, w, st):
+    """The pre-clamp value (v - mean) rstd at norm point n of one image in float64, [H][W][C], from the taps get(name) its kernel reads
+    (NORM_POINTS) and, for the AdaIN norm of a residual block, norm2's ends in st."""
+    mean, rstd = st["norm"][n][:2]
+    if n == 0:
+        p3 = get("p3")
+        v = _enc_stage(19, ())([p3], w, st, 0, p3.shape[0])[0]
+    elif n == 1:
+        d = get("d")
+        v = fold_up(2, d, w, st, 0, d.shape[0])[0] + np.asarray(get("f2"), np.float64)
+    else:
+        blk, xin, xs, a, _ = next(b for b in FRAME_BLOCKS if n in RES[b[0]][:3])
+        pre = "Decoder.%s." % blk
+        if n == RES[blk][0]:
+            x = get(xin)
+            v = lrelu(*conv3(x, w[pre + "conv1.weight"], w[pre + "conv1.bias"], 0, 2 * x.shape[0], ups=True))[0]
+        else:
+            t = get(a)
+            v = lrelu(*conv3(t, w[pre + "conv2.weight"], w[pre + "conv2.bias"], 0, t.shape[0]))[0]
+            if n == RES[blk][2]:
+                v = norm(v, v, st["norm"][RES[blk][1]])[0] + _up2(get(xs), t.shape[0], t.shape[1])
+    return (v - mean) * rstd
+
+
+def clamp_shares(pre, lo, hi):
+    """Per channel, over every pixel of every image in pre (a list of [H][W][C]), as float32 compares them: the share of pre-clamp values
+    at or below lo, at or above hi, and strictly inside; which channels are not constant; the share of a channel's commonest value
+    (ReLU's zeros at Decoder.norm[0]): (at_lo, at_hi, inside, live, atom)."""
+    flat = np.concatenate([np.asarray(p).reshape(-1, p.shape[-1]) for p in pre]).astype(np.float32)
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    at_lo, at_hi = (flat <= lo).mean(axis=0), (flat >= hi).mean(axis=0)
+    inside = ((flat > lo) & (flat < hi)).mean(axis=0)
+    srt = np.sort(flat, axis=0)
+    run = np.ones(flat.shape[1], np.int64)
+    best = run.copy()
+    for r in range(1, srt.shape[0]):
+        run = np.where(srt[r] == srt[r - 1], run + 1, 1)
+        best = np.maximum(best, run)
+    return at_lo, at_hi, inside, flat.max(axis=0) > flat.min(axis=0), best / flat.shape[0]
+
+
+def clamp_conditions(shares, floor, masks=None):
+    """The norm points and channels that miss the conditions: on every channel that is not constant the share at lo and the share at hi
+    are at least `floor`, and so is the share strictly inside unless more than ATOM of the channel sits on one value (then lo and hi
+    fall on that value whatever the percentiles).  masks: {norm point: (live, atom)} to use instead of the shares' own (the
+    construction's, for shares taken from another forward of the same frames).  Returns [(norm point, channel, shares)]."""
+    bad = []
+    for n, (at_lo, at_hi, inside, live, atom) in sorted(shares.items()):
+        if masks is not None:
+            live, atom = masks[n]
+        miss = live & ((at_lo < floor) | (at_hi < floor) | ((inside < floor) & (atom <= ATOM)))
+        bad.extend((n, int(c), (float(at_lo[c]), float(at_hi[c]), float(inside[c]))) for c in np.nonzero(miss)[0])
+    return bad
+
+
+def clamp_state(weights, blob, frames):
+    """The float64 stages free-running over `frames` (uint8 [H][W][3] each) with blob's means, rstds, filters and style statistics; at each
+    of the 11 norm points lo[c], hi[c] become the 30th and 70th percentile of channel c's pre-clamp value over all frames, rounded to
+    float32, and the forward goes on with the values clamped so.  A channel whose pre-clamp value is constant keeps the blob's ends.
+    Returns (the new blob, {norm point: clamp_shares of the construction})."""
+    w = weights
+    new = np.array(blob, np.float32, copy=True).reshape(-1)
+    st = parse_state(new)
+    shares = {}
+    taps = []
+    for f in frames:
+        x = grey_input(f)
+        for name in FRAME_ENC:
+            x = STAGES[name][2]([x], w, st, 0, STAGES[name][3](*f.shape[:2])[0])[0]
+        taps.append({"p3": x})
+
+    def point(n):
+        mean, rstd, lo0, hi0 = st["norm"][n]
+        pre = [norm_pre(n, t.__getitem__, w, st) for t in taps]
+        flat = np.concatenate([p.reshape(-1, p.shape[-1]) for p in pre])
+        live = flat.max(axis=0) > flat.min(axis=0)
+        lo = np.where(live, np.percentile(flat, CLAMP_Q[0], axis=0).astype(np.float32).astype(np.float64), lo0)
+        hi = np.where(live, np.percentile(flat, CLAMP_Q[1], axis=0).astype(np.float32).astype(np.float64), hi0)
+        C = NORM_CH[n]
+        new[NORM_OFF[n] + 2 * C:NORM_OFF[n] + 3 * C], new[NORM_OFF[n] + 3 * C:NORM_OFF[n] + 4 * C] = lo, hi
+        st["norm"][n] = (mean, rstd, lo, hi)
+        shares[n] = clamp_shares(pre, lo, hi)
+        out, sty = NORM_POINTS[n][1:]
+        for t, p in zip(taps, pre):
+            v = np.minimum(hi, np.maximum(lo, p))
+            if out is not None:
+                t[out] = v if sty is None else v * st["sty"][sty][1] + st["sty"][sty][0]
+
+    point(0)
+    for t in taps:
+        t["f1"] = _composite(0)([t["c41"]], w, st, 0, t["c41"].shape[0])[0]
+        t["f2"] = _composite(1)([t["f1"]], w, st, 0, t["f1"].shape[0])[0]
+        t["d"] = _down(2)([t["f2"]], w, st, 0, t["f2"].shape[0])[0]
+    point(1)
+    for blk, xin, xs, _, _ in FRAME_BLOCKS:
+        for t in taps:
+            t[xs] = conv1(t[xin], w["Decoder.%s.conv_shortcut.weight" % blk], 0, t[xin].shape[0])[0]
+        for n in RES[blk][:3]:
+            point(n)
+    assert sorted(shares) == list(range(len(NORM_CH)))
+    assert np.array_equal(np.delete(new, _ends()), np.delete(np.asarray(blob, np.float32).reshape(-1), _ends()))      # only lo and hi moved
+    return new, shares
+
+
+def _ends():
+    return np.concatenate([np.arange(NORM_OFF[n] + 2 * C, NORM_OFF[n] + 4 * C) for n, C in enumerate(NORM_CH)])

@@ -1,6 +1,7 @@
 """CPU checks of the per-image state read-back (rrv_debug_copy_state): declared in the header, listed in the ctypes table,
 exported by the built library, refuses bad arguments before it touches a device, and has its framework wrappers; the same
-for the preparation pass's stop knob and tensor read-back (rrv_debug_prep_stop, rrv_debug_copy_prep_tensor)."""
+for the preparation pass's stop knob and tensor read-back (rrv_debug_prep_stop, rrv_debug_copy_prep_tensor) and for the weight read-back
+(rrv_debug_weight_count, rrv_debug_weight_info, rrv_debug_copy_weights)."""
 import ctypes as C
 import importlib
 import inspect
@@ -127,3 +128,78 @@ def test_prep_wrappers():
     t = s.debug_prep_tensor("t32", 1)
     assert t.shape == (4, 5, 32) and t.dtype == np.float32 and t[3, 4, 31] == 7.0
     assert calls == [("stop", 6), (L.PREP_TENSORS.index("t32"), 1, 0), (2, 1, 640)]
+
+
+def test_weight_read_back_is_declared_listed_and_exported():
+    hdr = open(os.path.join(ROOT, "include", "rerevst_hip.h")).read()
+    L = importlib.import_module("rerevst-code_amd._lib")
+    decl = re.search(r"int\s+rrv_debug_weight_count\s*\(([^)]*)\)", hdr).group(1)
+    assert [a.strip() for a in decl.split(",")] == ["rrv_handle h"]
+    assert L.SYMBOLS["rrv_debug_weight_count"] == (C.c_int, [C.c_void_p])
+    decl = re.search(r"int\s+rrv_debug_weight_info\s*\(([^)]*)\)", hdr).group(1)
+    assert [a.strip() for a in decl.split(",")] == ["rrv_handle h", "int index", "char* key", "size_t keycap", "int* form", "int* Cout", "int* Cin",
+                                                    "int* taps", "int* BN", "int* sets", "size_t* floats"]
+    assert L.SYMBOLS["rrv_debug_weight_info"] == (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(C.c_size_t)])
+    decl = re.search(r"int\s+rrv_debug_copy_weights\s*\(([^)]*)\)", hdr).group(1)
+    assert [a.strip() for a in decl.split(",")] == ["rrv_handle h", "int index", "int set", "float* host", "size_t cap", "size_t* floats"]
+    assert L.SYMBOLS["rrv_debug_copy_weights"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)])
+    forms = dict(re.findall(r"#define RRV_DBG_W_([A-Z0-9_]+) (\d+)", hdr))
+    assert [k.lower() for k, v in sorted(forms.items(), key=lambda kv: int(kv[1]))] == list(L.WEIGHT_FORMS)
+    assert sorted(int(v) for v in forms.values()) == list(range(len(L.WEIGHT_FORMS)))
+    importlib.import_module("rerevst-code_amd.build").build_lib(verbose=False)
+    lib = L.load()
+    n = C.c_size_t(0)
+    assert lib.rrv_debug_weight_count(None) == RRV_E_ARG                                   # no handle: refused before any device is touched
+    assert lib.rrv_debug_weight_info(None, 0, None, 0, None, None, None, None, None, None, C.byref(n)) == RRV_E_ARG
+    assert lib.rrv_debug_copy_weights(None, 0, 0, None, 0, C.byref(n)) == RRV_E_ARG
+    h = C.c_void_p()
+    if lib.rrv_create(0, C.byref(h)) != 0:
+        return                                                                             # no GPU here: a handle cannot exist
+    try:
+        assert lib.rrv_debug_weight_count(h) == -4                                         # RRV_E_STATE: no weights finalized
+        assert lib.rrv_debug_copy_weights(h, 0, 0, None, 0, None) == RRV_E_ARG
+        assert lib.rrv_debug_copy_weights(h, 0, 0, None, 0, C.byref(n)) == -4
+    finally:
+        lib.rrv_destroy(h)
+
+
+def test_weight_wrapper():
+    F = importlib.import_module("rerevst-code_amd.framework")
+    L = importlib.import_module("rerevst-code_amd._lib")
+    assert list(inspect.signature(F.Stylization.debug_weights).parameters) == ["self"]
+    rows = [(b"Encoder.slice.2", L.WEIGHT_FORMS.index("pk"), 64, 64, 9, 64, 1, 36864), (b"Decoder.Filter1.fold_up", L.WEIGHT_FORMS.index("raw"), 512, 32, 9, 0, 32, 6)]
+    calls = []
+
+    class Lib:
+        def rrv_debug_weight_count(self, h):
+            return len(rows)
+
+        def rrv_debug_weight_info(self, h, i, key, keycap, form, cout, cin, taps, bn, sets, floats):
+            assert keycap == len(key) >= len(rows[i][0]) + 1
+            key.value = rows[i][0]
+            for ref, v in zip((form, cout, cin, taps, bn, sets, floats), rows[i][1:]):
+                ref._obj.value = v
+            return 0
+
+        def rrv_debug_copy_weights(self, h, i, set_, host, cap, floats):
+            calls.append((i, set_, cap))
+            floats._obj.value = rows[i][7]
+            C.cast(host, C.POINTER(C.c_float))[cap - 1] = 7.0 + set_
+            return 0
+
+        def rrv_last_error(self, h):
+            return b"refused"
+
+    s = F.Stylization.__new__(F.Stylization)
+    s._lib, s._h = Lib(), None
+    got = list(s.debug_weights())
+    assert [g[0] for g in got] == [
+        {"key": "Encoder.slice.2", "form": "pk", "Cout": 64, "Cin": 64, "taps": 9, "BN": 64, "sets": 1, "floats": 36864},
+        {"key": "Decoder.Filter1.fold_up", "form": "raw", "Cout": 512, "Cin": 32, "taps": 9, "BN": 0, "sets": 32, "floats": 6}]
+    a, b = got[0][1](), got[1][1](5)
+    assert a.shape == (36864,) and a.dtype == np.float32 and a[-1] == 7.0 and b.shape == (6,) and b[-1] == 12.0
+    assert calls == [(0, 0, 36864), (1, 5, 6)]
+    Lib.rrv_debug_weight_count = lambda self, h: -4
+    import pytest
+    with pytest.raises(F.RRVError, match="refused"):
+        list(s.debug_weights())

@@ -94,9 +94,9 @@ class Taps:
         return v
 
 
-def check_image(s, weights, st, seq, H, W, b, frame, names=None):
-    """Every stage (or `names`) of image b: returns {stage: family}; asserts each bound."""
-    t = Taps(s, H, W, b, frame)
+def check_image(s, weights, st, seq, H, W, b, frame, names=None, taps=None):
+    """Every stage (or `names`) of image b: returns {stage: family}; asserts each bound.  taps: the image's Taps, to share what is read."""
+    t = Taps(s, H, W, b, frame) if taps is None else taps
     fam = {}
     for name, (li, inputs, op, geo) in LR.STAGES.items():
         if names and name not in names:
@@ -134,6 +134,24 @@ ENC_F43 = ("p1", "c21", "p2", "c31", "c32", "c33", "p3")       # conv1_2 .. conv
 DEC_F43 = ("o4", "o3", "o2")                                   # ResidualBlock.conv2
 
 
+def assert_kind(kind, fam, lay):
+    """The kernel families and layouts a case of `kind` claims to cover ran."""
+    assert fam["c11"] == fam["pre"] == "direct"
+    assert fam["xs4"] == fam["a4"] == fam["a3"] == fam["a2"] == "ups"
+    assert fam["d"] in ("splitk", "f23") and fam["f3"] == fam["c41"] == "f23"
+    if kind == "f23":
+        assert all(fam[n] == "f23" for n in ENC_F43 + DEC_F43)
+        assert not any(lay.values()), lay
+    else:
+        assert all(fam[n] == "f43" for n in ENC_F43 + DEC_F43), fam
+        p8_names = ("c11",) + ENC_F43[:-1] + ("a4", "a3", "a2")
+        assert all(lay[n] == (1 if kind == "f43_p8" else 0) for n in p8_names), lay
+        assert lay["p3"] == 0
+
+
+KINDS = {"f23": (0, 3), "f43_p8": (2, 3), "f43_nhwc": (2, 0)}      # kind -> (rrv_set_f43 mode, RRV_P8)
+
+
 @pytest.mark.parametrize("kind", ["f23", "f43_p8", "f43_nhwc"])
 @pytest.mark.parametrize("shape", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
 def test_every_layer_against_its_own_input(pkg, weights, kind, shape):
@@ -141,22 +159,59 @@ def test_every_layer_against_its_own_input(pkg, weights, kind, shape):
     blob = load_golden("global_a")["state"]
     st = LR.parse_state(blob)
     frames = frames_for(pkg, B, H, W)
-    mode, p8 = {"f23": (0, 3), "f43_p8": (2, 3), "f43_nhwc": (2, 0)}[kind]
+    mode, p8 = KINDS[kind]
     s, seq, _ = launch(pkg, weights, frames, blob, mode, p8=p8)
     try:
         for b in sorted({0, B - 1}):
             fam, lay = check_image(s, weights, st, seq, H, W, b, frames[b])
-            assert fam["c11"] == fam["pre"] == "direct"
-            assert fam["xs4"] == fam["a4"] == fam["a3"] == fam["a2"] == "ups"
-            assert fam["d"] in ("splitk", "f23") and fam["f3"] == fam["c41"] == "f23"
-            if kind == "f23":
-                assert all(fam[n] == "f23" for n in ENC_F43 + DEC_F43)
-                assert not any(lay.values()), lay
-            else:
-                assert all(fam[n] == "f43" for n in ENC_F43 + DEC_F43), fam
-                p8_names = ("c11",) + ENC_F43[:-1] + ("a4", "a3", "a2")
-                assert all(lay[n] == (1 if kind == "f43_p8" else 0) for n in p8_names), lay
-                assert lay["p3"] == 0
+            assert_kind(kind, fam, lay)
+    finally:
+        s.close()
+
+
+CLAMP_SHAPE = (5, 40, 56)
+_CLAMP = {}
+
+
+def clamp_setup(pkg, weights):
+    """(frames, blob, construction shares) of the clamp-end state for CLAMP_SHAPE, built once for the module."""
+    if not _CLAMP:
+        frames = frames_for(pkg, *CLAMP_SHAPE)
+        blob, shares = LR.clamp_state(weights, load_golden("global_a")["state"], list(frames))
+        _CLAMP["v"] = (frames, blob, shares)
+    return _CLAMP["v"]
+
+
+@pytest.mark.parametrize("kind", ["f23", "f43_p8", "f43_nhwc"])
+def test_clamp_ends_on_every_channel(pkg, weights, kind):
+    """global_a with lo / hi of every channel at every norm point moved to the 30th / 70th percentile of its pre-clamp value over the five
+    frames (LR.clamp_state; means, rstds, filters and style statistics untouched, so the kernel choice is what it was): every stage of all
+    five images within its bound.  Conditions, not measurements: on the float64 forward the state was built from, every channel that is
+    not constant has at least 0.2 of its values at lo, 0.2 at hi and 0.2 strictly inside; on the teacher-forced reference of the GPU's own
+    taps (they differ from that forward by rounding only) at least 0.1 each.  The share inside is not asked of a channel with more than
+    half of its values on one value: 237 of Decoder.norm[0]'s 498 live channels, where conv4_1's ReLU leaves 50 .. 99 % zeros at these
+    frames and both percentiles fall on the zero (their shares at lo and at hi are still asked; no channel of the other ten norm points)."""
+    B, H, W = CLAMP_SHAPE
+    frames, blob, built = clamp_setup(pkg, weights)
+    assert LR.clamp_conditions(built, 0.2) == []
+    st = LR.parse_state(blob)
+    mode, p8 = KINDS[kind]
+    s, seq, _ = launch(pkg, weights, frames, blob, mode, p8=p8)
+    try:
+        pre = {n: [] for n in built}
+        for b in range(B):
+            t = Taps(s, H, W, b, frames[b])
+            fam, lay = check_image(s, weights, st, seq, H, W, b, frames[b], taps=t)
+            assert_kind(kind, fam, lay)
+            for n in built:
+                pre[n].append(LR.norm_pre(n, t.get, weights, st))
+        forced = {n: LR.clamp_shares(pre[n], st["norm"][n][2], st["norm"][n][3]) for n in built}
+        for n, (at_lo, at_hi, inside, live, atom) in sorted(forced.items()):
+            live = built[n][3]
+            print("[clamp shares] %s norm %d: at lo >= %.3f, at hi >= %.3f, inside >= %.3f (channels asked: %d, %d of them not for the inside)"
+                  % (kind, n, at_lo[live].min(), at_hi[live].min(), inside[live & (built[n][4] <= LR.ATOM)].min(), live.sum(),
+                     (live & (built[n][4] > LR.ATOM)).sum()))
+        assert LR.clamp_conditions(forced, 0.1, masks={n: (built[n][3], built[n][4]) for n in built}) == []
     finally:
         s.close()
 

@@ -9,7 +9,7 @@ import pytest
 
 import kernel_ledger as KL
 
-KINDS = ("layer", "entry", "indirect", "debug", "unreachable")
+KINDS = ("layer", "entry", "debug", "unreachable")
 
 # Compiled, never launched: a kernel that joins or leaves this list did so on purpose (and then has, or loses, its layer test).
 UNREACHABLE = set()
@@ -55,12 +55,16 @@ def test_entries_are_well_formed_and_cited_tests_exist():
             assert os.path.isfile(os.path.join(KL.ROOT, path)), (key, ref)
             mod = importlib.import_module(os.path.splitext(os.path.basename(path))[0])
             assert callable(getattr(mod, name, None)), (key, ref)
-        elif kind == "indirect":
-            assert KL.LEDGER[ref][0] == "layer", (key, ref)
-            assert key.startswith(("pack_", "fold_")), key
         else:
             assert ref is None, key
             assert (kind == "debug") == ("dbg_" in key), key
+
+
+def test_packs_and_folds_have_a_reference_of_their_own():
+    """No kernel is vouched for by its consumer any more: the kind `indirect` is gone, and every pack / fold kernel cites tests/test_gpu_packs.py."""
+    assert not [k for k, e in KL.LEDGER.items() if e[0] == "indirect"]
+    packs = {k: e for k, e in KL.LEDGER.items() if k.startswith(("pack_", "fold_"))}
+    assert len(packs) == 9 and all(e[0] == "layer" and e[1].startswith("tests/test_gpu_packs.py::") for e in packs.values()), packs
 
 
 def test_the_unreachable_kernels_are_the_listed_ones():

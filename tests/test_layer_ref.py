@@ -169,6 +169,72 @@ def test_per_image_norm0_defect_fails(setup, per_image, weights, case, defect):
     assert not ok, "case %s: %s passes the bound (worst %.2f)" % (case, defect, worst)
 
 
+# ---- clamp ends on every channel: the state of tests/test_gpu_layers.py::test_clamp_ends_on_every_channel ------------------------------------------
+
+CLAMP_SHAPE = (5, 40, 56)
+
+
+@pytest.fixture(scope="module")
+def clamp(pkg, weights):
+    frames = [pkg.synth_frame(i, *CLAMP_SHAPE[1:], kind="smooth") for i in range(CLAMP_SHAPE[0])]
+    blob0 = np.asarray(load_golden("global_a")["state"], np.float32).reshape(-1)
+    blob, shares = LR.clamp_state(weights, blob0, frames)
+    return blob0, blob, shares
+
+
+def test_clamp_state_cuts_into_every_channel(clamp):
+    """The construction-time conditions: at every norm point every channel that is not constant has 0.2 of its values at lo, 0.2 at hi and
+    0.2 strictly inside (the inside share is not asked where more than half of a channel sits on one value: ReLU's zeros at
+    Decoder.norm[0], and nowhere else); nothing but lo and hi differs from the blob it was built from."""
+    blob0, blob, shares = clamp
+    assert LR.clamp_conditions(shares, 0.2) == []
+    st0, st = LR.parse_state(blob0), LR.parse_state(blob)
+    for n, (at_lo, at_hi, inside, live, atom) in shares.items():
+        assert live.sum() >= 0.95 * live.size, (n, int(live.sum()))
+        assert not np.any(live & (atom > LR.ATOM)) or n == 0, n
+        assert np.all(inside[live & (atom <= LR.ATOM)] >= 0.2) and np.all(at_lo[live] >= 0.2) and np.all(at_hi[live] >= 0.2), n
+        for k in (0, 1):
+            assert np.array_equal(st["norm"][n][k], st0["norm"][n][k])
+        for k in (2, 3):      # a constant channel keeps the blob's ends
+            assert np.array_equal(st["norm"][n][k][~live], st0["norm"][n][k][~live])
+        assert np.all(st["norm"][n][2] <= st["norm"][n][3])
+    assert all(np.array_equal(st["filt"][k], st0["filt"][k]) for k in st["filt"])
+    assert all(np.array_equal(a, b) for x, y in zip(st["sty"], st0["sty"]) for a, b in zip(x, y))
+    # the check itself can fail: with the golden state's own ends almost nothing clamps
+    assert LR.clamp_conditions({0: LR.clamp_shares([np.zeros((2, 2, 4)), np.ones((2, 2, 4))], np.full(4, -9.0), np.full(4, 9.0))}, 0.2)
+
+
+def _c41_clamp(oracle, weights, p3, st, defect=None):
+    """conv4_1 + ReLU + Decoder.norm[0] in float32 on state st; defect: the ends of channel c + 4, the ends exchanged, no clamp."""
+    y = oracle.relu(oracle.conv3x3(p3[None], weights["Encoder.slice.19.weight"], weights["Encoder.slice.19.bias"]))[0]
+    mean, rstd, lo, hi = (np.asarray(a, np.float32) for a in st["norm"][0])
+    v = ((y - mean) * rstd).astype(np.float32)
+    if defect == "clamp omitted":
+        return v
+    if defect == "lo / hi of channel c + 4":
+        lo, hi = np.roll(lo, -4), np.roll(hi, -4)
+    if defect == "lo and hi exchanged":
+        lo, hi = hi, lo
+    return np.minimum(hi, np.maximum(lo, v)).astype(np.float32)
+
+
+def test_clamp_state_stand_in_passes(setup, clamp, weights):
+    oracle, acts, _ = setup
+    st = LR.parse_state(clamp[1])
+    for _, p3 in acts:
+        ok, worst, ratio = _verdict(_c41_clamp(oracle, weights, p3, st), "c41", [p3], weights, st)
+        assert ok, "conv4_1 + clamped norm0 stand-in at %.2f of its bound (ratio %.2f)" % (worst, ratio)
+
+
+@pytest.mark.parametrize("defect", ["lo / hi of channel c + 4", "lo and hi exchanged", "clamp omitted"])
+def test_clamp_defect_fails(setup, clamp, weights, defect):
+    oracle, acts, _ = setup
+    st = LR.parse_state(clamp[1])
+    p3 = acts[0][1]
+    ok, worst, _ = _verdict(_c41_clamp(oracle, weights, p3, st, defect), "c41", [p3], weights, st)
+    assert not ok, "%s passes the bound (worst %.2f)" % (defect, worst)
+
+
 def test_nine_tap_conv_mfma_rows_are_the_gemm_family():
     assert LR.family_of("conv_mfma<64,9,E_RELU | E_POOL>@64x64@40x56", False) == "gemm"
     assert LR.family_of("conv_mfma<128,9,E_RELU | E_NORM1>@256x512@5x7", False) == "gemm"
