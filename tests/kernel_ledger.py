@@ -67,6 +67,7 @@ MK = "tests/test_gpu_mask_layers.py::"
 PL = "tests/test_gpu_prep_layers.py::"
 IN = "tests/test_gpu_instantiations.py::"
 PK = "tests/test_gpu_packs.py::"
+WIN = "; windowed launch (pad / crop): tests/test_gpu_window_layers.py::"
 
 LEDGER = {}
 
@@ -84,7 +85,7 @@ EVERY = GL + "test_every_layer_against_its_own_input"
 _add("layer", "conv_wino_split_k<1, 0>", EVERY, "kind f23: the rows of c21 / c31 / c32 / c33 are conv_wino<E_RELU> (family_of), NHWC taps")
 _add("layer", "conv_wino_split_k<65, 0>", EVERY, "kind f23: the rows of p1 / p2 / p3 are conv_wino<E_RELU | E_POOL>")
 _add("layer", "conv_wino_split_k<5, 0>", EVERY, "every kind: c41's row is conv_wino<E_RELU | E_NORM1>, one shared state set")
-_add("layer", "conv_wino_split_k<54, 0>", EVERY, "kind f23: the rows of o4 / o3 / o2 are conv_wino, asserted f23")
+_add("layer", "conv_wino_split_k<54, 0>", EVERY, "kind f23: the rows of o4 / o3 / o2 are conv_wino, asserted f23" + WIN + "test_windowed_launch_on_a_stale_workspace, kind f23")
 _add("layer", "conv_wino_split_k<2, 0>", GL + "test_split_k_kernel_filter", "1536 x 2048: no sum_parts row follows, dpart is refused: the unsplit LeakyReLU kernel")
 _add("layer", "conv_wino_split_k<0, 0>", GL + "test_split_k_kernel_filter", "640 and 1152: sum_parts follows each down row, dpart has 32 x split channels")
 _add("layer", "conv_wino_split_k<8, 0>", EVERY, "f1 / f2 (two kernels in one, LR.COMPOSITE): the up rows are conv_wino<E_RES>")
@@ -92,7 +93,7 @@ _add("layer", "conv_wino_split_k<40, 0>", EVERY, "f3's row is conv_wino, family 
 _add("layer", "conv_wino_split_k<5, 1>", IN + "test_blended_frames_per_image_conv4_1",
      "c41's row is conv_wino<..> at 256 x 512 and debug_state_set(0, 1) succeeds: conv() took the IMG row; image 2 on set 0 fails")
 _add("layer", "conv_wino_split_k<54, 1>", IN + "test_blended_frames_per_image_conv4_1",
-     "kind default: o4 / o3 / o2 asserted f23 in a launch with per-image state (the grouped test of the frame-mode suite too)")
+     "kind default: o4 / o3 / o2 asserted f23 in a launch with per-image state (the grouped test of the frame-mode suite too)" + WIN + "test_windowed_launch_with_per_image_state")
 _add("layer", "conv_wino_split_k<2, 1>", IN + "test_filter_down_per_image_weights_frame_mode",
      "64 x 16400: the down rows are conv_wino<E_LRELU> without sum_parts, dpart refused, two images; image 1's d on set 0 fails")
 _add("layer", "conv_wino_split_k<0, 1>", FM + "test_every_frame_mode_stage",
@@ -101,16 +102,16 @@ _add("layer", "conv_wino_split_k<8, 1>", FM + "test_every_frame_mode_stage", "B 
 _add("layer", "conv_wino_split_k<40, 1>", FM + "test_every_frame_mode_stage", "B > 1: f3 on each image's own set; image 7 on set 8 fails f3")
 
 # conv_wino_k<EPI, 0, 4, UPS=1, SC, IMG> (CONV_ROWS: UP(EPI, SC, IMG)): the upsample-fused ResidualBlock.conv1 (EPI 6: LeakyReLU + norm1; 2: raw LeakyReLU)
-_add("layer", "conv_wino_k<6, 0, 4, 1, 1, 0>", EVERY, "every kind: a4 / a3 / a2 and xs4 / xs3 / xs2 asserted family ups (conv_upw_sc rows)")
+_add("layer", "conv_wino_k<6, 0, 4, 1, 1, 0>", EVERY, "every kind: a4 / a3 / a2 and xs4 / xs3 / xs2 asserted family ups (conv_upw_sc rows)" + WIN + "test_windowed_launch_on_a_stale_workspace, every kind")
 _add("layer", "conv_wino_k<6, 0, 4, 1, 1, 1>", IN + "test_blended_frames_per_image_conv4_1",
-     "a4 / a3 / a2 of images 0 and 2 on their own sets in a launch with per-image state (resblock_frame sets par_bstride)")
+     "a4 / a3 / a2 of images 0 and 2 on their own sets in a launch with per-image state (resblock_frame sets par_bstride)" + WIN + "test_windowed_launch_with_per_image_state")
 _add("layer", "conv_wino_k<2, 0, 4, 1, 1, 0>", FM + "test_every_frame_mode_stage", "frame_families: the conv1 rows are conv_upw_sc, family ups, raw output + statistics")
 _add("layer", "conv_wino_k<2, 0, 4, 1, 0, 0>", PL + "test_every_stop_of_the_resident_pass", "the nine-product conv_upw<E_LRELU> of the preparation pass (unfused shortcut)")
 
 # conv_f43_k<EPI, LAY> (CONV_ROWS: F4(EPI, LAY); per-image parameters are read by the same instantiation)
-_add("layer", ["conv_f43_k<1, 0>", "conv_f43_k<65, 0>", "conv_f43_k<54, 0>"], EVERY, "kind f43_nhwc: ENC_F43 + DEC_F43 asserted f43, every layout 0")
+_add("layer", ["conv_f43_k<1, 0>", "conv_f43_k<65, 0>", "conv_f43_k<54, 0>"], EVERY, "kind f43_nhwc: ENC_F43 + DEC_F43 asserted f43, every layout 0" + WIN + "test_windowed_launch_on_a_stale_workspace, kind f43_nhwc (<54, 0>)")
 _add("layer", ["conv_f43_k<65, 3>", "conv_f43_k<1, 3>", "conv_f43_k<65, 1>", "conv_f43_k<54, 1>"], EVERY,
-     "kind f43_p8: ENC_F43 + DEC_F43 asserted f43, c11 .. c33 and a4 / a3 / a2 layout 1, p3 layout 0")
+     "kind f43_p8: ENC_F43 + DEC_F43 asserted f43, c11 .. c33 and a4 / a3 / a2 layout 1, p3 layout 0" + WIN + "test_windowed_launch_on_a_stale_workspace, kind f43_p8 (<54, 1>)")
 
 # conv_mfma_k<BN, TAPS, EPI, ..> (CONV_ROWS: MF(BN, TAPS, EPI))
 _add("layer", ["conv_mfma_k<128, 1, 0, 0, 0, 1>", "conv_mfma_k<64, 1, 0, 0, 0, 1>"], PL + "test_every_stop_of_the_resident_pass",
@@ -125,7 +126,7 @@ _add("entry", ["conv_first_k<1>", "conv_first_k<2>", "conv_first_k<3>"], "tests/
      "planar / float32 input gives the bits of the uint8 HWC path (conv_first_k<0>)")
 _add("entry", ["conv_first_k<4>", "conv_first_k<5>"], "tests/test_gpu_yuv_input.py::test_device_entries", "8-bit I420 / NV12 input against the converted frame's path")
 _add("entry", ["conv_first_k<6>", "conv_first_k<7>"], "tests/test_gpu_yuv16.py::test_input_device_entries", "10 / 12 / 16-bit planar and P01x input")
-_add("layer", "conv_last_k<false, false, 0, false, false>", EVERY, "pre (the pre-clamp output) from o2, family direct")
+_add("layer", "conv_last_k<false, false, 0, false, false>", EVERY, "pre (the pre-clamp output) from o2, family direct" + WIN + "test_windowed_launch_on_a_stale_workspace; the uint8 and NV12 forms: test_windowed_launch_in_the_quantising_output_forms")
 _add("entry", ["conv_last_k<false, false, 1, false, false>", "conv_last_k<false, false, 2, false, false>", "conv_last_k<false, true, 0, false, false>",
                "conv_last_k<false, true, 1, false, false>", "conv_last_k<false, true, 2, false, false>", "conv_last_k<true, true, 0, false, false>"],
      "tests/test_gpu_tensor_io.py::test_output_forms", "every output form against the float32 BGR frame of conv_last_k<false, false, 0, false, false>")

@@ -1,5 +1,6 @@
 """Per-layer float64 references for the activation taps (rrv_debug_copy_tensor_ex) and the error model that bounds
-each kernel's own rounding.  Plain module (no pytest): imported by tests/test_gpu_layers.py and tests/test_layer_ref.py.
+each kernel's own rounding.  Plain module (no pytest): imported by tests/test_gpu_layers.py and tests/test_layer_ref.py (and the
+other layer suites; the windows of the pad / crop entries, crop_windows, are tests/test_gpu_window_layers.py's).
 
 Teacher forcing: every stage is evaluated in float64 from the GPU's OWN input tap(s), the unfolded checkpoint weights and
 the saved state, so a check sees one kernel's error and nothing upstream (Decoder.norm[0]'s amplification of encoder
@@ -107,6 +108,14 @@ FAMILIES = ("direct", "f23", "ups", "f43", "splitk", "stat", "point", "pred", "m
 #   fold     5.44 fold_up_k, image 1 of the grouped launch (cap n = 32, so K = 11; fold_down_k 4.92, its bias 3.01: a 32-term
 #                 float32 sum against sum |F||W|)
 # Image 1's folded weights on image 0's filter (the control): ratios 3.0e6 .. 8.4e6, its pack on image 0's folded weights 7e10 and more.
+# and over every case of tests/test_gpu_window_layers.py (the windowed launches of the pad / crop entries at 192 x 192, each stage on its
+# window alone; profiles/windows.txt), all inside the figures above, no K touched:
+#   ups      8.36 xs2 (the fused shortcut, kinds f43_p8 / f43_nhwc at 47 x 49; f23 7.67, blended 6.68); a2 2.7 (f23), 4.42 (both f43 kinds;
+#                 the P8 twin written through a window holds the NHWC launch's bits), 2.4 blended with per-image state
+#   f23      1.82 o2 (conv_wino_split_k<54,0> windowed; <54,1> with per-image state 1.64)
+#   f43      2.74 o2 (conv_f43_k<54,0> and <54,1> windowed: the same figure in both layouts)
+#   direct   1.28 pre (conv_last_k on wl, evaluated where its taps stay inside wo)
+# The control (image 1 of the blended call on image 0's set): a2 at 1.96e5, o2 at 4.9e5 in ratio.
 MEASURED = {"direct": 30.7, "f23": 3.7, "ups": 9.2, "f43": 12.5, "splitk": 0.24, "stat": 2.91, "point": 3.73, "pred": 1.21, "mnorm": 3.64, "mfilt": 0.314,
             "pstat": 4.24, "gemm": 7.95, "ppred": 1.91, "once": 0.5, "pack32": 2.60, "grey": 1.83, "fold": 5.44}
 # K = 2 x the measured maximum, rounded up (at most 4x it): margin for shapes and images outside the measured set while
@@ -422,6 +431,138 @@ def check(got, v, m, k):
     ratio = err / np.maximum(U * m, 1e-300)
     worst = float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
     return bool(np.all(err <= bound)), worst, float(ratio.max()) if err.size else 0.0
+
+
+# ---- the windows of the pad / crop entries (rrv_transfer_frames*, RRV_TF_PAD_CROP) ------------------------------------------------------
+# Restated from the comments of transfer_device and conv_params, nothing imported from the library.  A source frame of H x W is reflect-
+# padded to padded_size(H) x padded_size(W) on its way into conv_first_k and the crop that starts at (CROP0, CROP0) is delivered, so the
+# full-resolution block computes windows only.  A window is (y0, x0, y1, x1) in pixels of its own tensor, y1 / x1 exclusive:
+#   wl   what conv_last_k computes: the crop rounded out to its 16 x 16 tiles
+#   wo   what slice2.conv2 writes in o2: the crop + one halo pixel, rounded out to 16 (to the 32 x 32 items of conv_f43_k where conv2 runs on it)
+#   wa   what the shortcut-fused conv1 really writes in a2 (or its P8 twin): wo + one halo pixel rounded out to 16 is what transfer_device
+#        asks for, conv_params rounds that out to the kernel's 32 x 32 items, clipped to the frame rounded up to 32
+#   xs   wa halved: what the same launch writes in xs2, at half the resolution
+# Every round-out stops at the frame rounded up to the tile; an element of a window beyond the frame itself is never stored.
+CROP0 = 64
+
+
+def padded_size(n):
+    """ReshapeTool.process: n + 2 x 64 rounded up to a multiple of 64."""
+    return (n + 128 + 63) // 64 * 64
+
+
+def _grow(lo, hi, halo, lim):
+    """[lo, hi) + halo pixels each side, rounded out to 16, inside [0, lim rounded up to 16)."""
+    return max(lo - halo, 0) & ~15, min((hi + halo + 15) & ~15, (lim + 15) & ~15)
+
+
+def _out32(lo, hi, lim):
+    return lo & ~31, min((hi + 31) & ~31, (lim + 31) & ~31)
+
+
+def _axis_windows(n, conv2_f43):
+    P = padded_size(n)
+    crop = (CROP0, CROP0 + n)
+    wl = _grow(*crop, 0, P)
+    wo = _grow(*crop, 1, P)
+    if conv2_f43:
+        wo = _out32(*wo, P)
+    wa = _out32(*_grow(*wo, 1, P), P)
+    return {"P": P, "crop": crop, "wl": wl, "wo": wo, "wa": wa, "xs": (wa[0] // 2, wa[1] // 2)}
+
+
+WINDOW_NAMES = ("crop", "wl", "wo", "wa", "xs")
+
+
+def crop_windows(H, W, conv2_f43):
+    """The windows of a pad / crop call on H x W source frames: {"PH", "PW": the padded geometry; "crop", "wl", "wo", "wa", "xs": (y0, x0, y1, x1)}."""
+    y, x = _axis_windows(H, conv2_f43), _axis_windows(W, conv2_f43)
+    out = {"PH": y["P"], "PW": x["P"]}
+    for n in WINDOW_NAMES:
+        out[n] = (y[n][0], x[n][0], y[n][1], x[n][1])
+    return out
+
+
+def clip(win, H, W):
+    """The part of a window inside an H x W tensor."""
+    return max(win[0], 0), max(win[1], 0), min(win[2], H), min(win[3], W)
+
+
+def inside(a, b):
+    """Window a lies in window b (an empty a lies in everything)."""
+    return a[2] <= a[0] or a[3] <= a[1] or (b[0] <= a[0] and b[1] <= a[1] and a[2] <= b[2] and a[3] <= b[3])
+
+
+def reads3(win, H, W):
+    """The elements of an H x W input that a 3 x 3 convolution (pad 1) reads for the outputs in `win`; what falls outside the frame is the zero ring."""
+    return clip((win[0] - 1, win[1] - 1, win[2] + 1, win[3] + 1), H, W)
+
+
+def reads_half(win, H, W):
+    """The elements of the half-resolution residual that the outputs in `win` of an H x W tensor read: (y // 2, x // 2)."""
+    y0, x0, y1, x1 = clip(win, H, W)
+    return (y0 // 2, x0 // 2, (y1 + 1) // 2, (x1 + 1) // 2) if y1 > y0 and x1 > x0 else (0, 0, 0, 0)
+
+
+def pre_checkable(w):
+    """The part of wl whose 3 x 3 reads of o2 lie in wo or outside the frame: where the pre-clamp tap of a windowed launch has a reference.  It holds
+    the crop (window_faults), not always all of wl: with (CROP0 + n) = 15 (mod 16) wl and wo both end one pixel behind the crop."""
+    PH, PW = w["PH"], w["PW"]
+    wo, wl = w["wo"], w["wl"]
+    lo = lambda v: v if v == 0 else v + 1
+    hi = lambda v, lim: v if v >= lim else v - 1
+    ok = (lo(wo[0]), lo(wo[1]), hi(wo[2], PH), hi(wo[3], PW))
+    return max(wl[0], ok[0]), max(wl[1], ok[1]), min(wl[2], ok[2]), min(wl[3], ok[3])
+
+
+def window_faults(w):
+    """The window rule as conditions on index arithmetic; returns the ones `w` (crop_windows' form) breaks, [] when every consumer reads what
+    its producer wrote:
+      last   conv_last_k computes every crop pixel, and every o2 element its 3 x 3 taps read for a crop pixel lies in wo or outside the frame
+      conv2  every a2 element slice2.conv2 reads for a pixel of wo lies in wa or outside the frame
+      res    every xs2 element conv2's upsampled residual reads for a pixel of wo lies in xs"""
+    PH, PW = w["PH"], w["PW"]
+    bad = []
+    if not inside(w["crop"], clip(w["wl"], PH, PW)):
+        bad.append("last: a crop pixel outside wl")
+    if not inside(reads3(w["crop"], PH, PW), w["wo"]):
+        bad.append("last: reads o2 outside wo")
+    if not inside(reads3(clip(w["wo"], PH, PW), PH, PW), w["wa"]):
+        bad.append("conv2: reads a2 outside wa")
+    if not inside(reads_half(w["wo"], PH, PW), w["xs"]):
+        bad.append("res: reads xs2 outside its window")
+    return bad
+
+
+def shrink(win, side, tile):
+    """`win` with one tile taken off side 0..3 (y0, x0, y1, x1): the negative controls of the window tests."""
+    v = list(win)
+    v[side] += tile if side < 2 else -tile
+    return tuple(v)
+
+
+def window_mask(win, H, W, layout=0, C=None):
+    """Boolean mask of a tap AS STORED that is True on the window's pixels: the ring layout [H+2][W+2][C] keeps pixel (y, x) at (y + 1, x + 1),
+    the P8 layout [C/8][H+2][W+8][8] at row y + 1 and column x + 4; layout None: the pre-clamp tap, [H][W][C] with nothing around it."""
+    y0, x0, y1, x1 = clip(win, H, W)
+    if layout is None:
+        m = np.zeros((H, W, C), bool)
+        m[y0:y1, x0:x1] = True
+    elif layout == 1:
+        m = np.zeros((C // 8, H + 2, W + 8, 8), bool)
+        m[:, y0 + 1:y1 + 1, x0 + 4:x1 + 4] = True
+    else:
+        m = np.zeros((H + 2, W + 2, C), bool)
+        m[y0 + 1:y1 + 1, x0 + 1:x1 + 1] = True
+    return m.reshape(-1)
+
+
+def window_stage(name, inp, w, st, win):
+    """Stage `name` of STAGES on the window `win` of its output alone: (v, m) as [y1-y0][x1-x0][C].  The rows are evaluated at the full width
+    of the inputs, so what a column outside the window holds never enters a value inside it beyond the stage's own reads."""
+    y0, x0, y1, x1 = win
+    v, m = STAGES[name][2](inp, w, st, y0, y1)
+    return v[:, x0:x1], m[:, x0:x1]
 
 
 # ---- frame mode (Stylization(use_Global=False): frame_mode_device) ---------------------------------------------------------

@@ -782,3 +782,162 @@ def test_prep_blob_entries_and_bit_equality():
     o, _ = PR.OFFSETS["norm", 1]          # written at stop 4
     b[o + 3] = np.nextafter(b[o + 3], F32(0))
     assert PR.entries_bit_equal(a, b, 4) and not PR.entries_bit_equal(a, b, 5)
+
+
+# ---- the windows of the pad / crop entries: LR.crop_windows against the window rule, and the rule's negative controls -----------------
+
+def test_padded_size_is_the_oracles(oracle):
+    assert [LR.padded_size(n) for n in range(1, 700)] == [oracle.padded_size(n) for n in range(1, 700)]
+
+
+@pytest.mark.parametrize("conv2_f43", [False, True], ids=["f23", "f43"])
+def test_crop_windows_suffice_for_every_source_size(conv2_f43):
+    """H, W in 1..256: every o2 element conv_last reads for a crop pixel lies in wo or outside the frame, every a2 element conv2 reads for
+    a wo pixel in the written a2 window or outside the frame, every xs2 element of the upsampled residual in the halved window
+    (LR.window_faults: conditions on index arithmetic, no exception), and the windows have the alignment their kernels' items need."""
+    for H in range(1, 257):
+        for W in range(1, 257):
+            w = LR.crop_windows(H, W, conv2_f43)
+            assert LR.window_faults(w) == [], (H, W, w)
+            assert not any(v & 15 for v in w["wl"] + w["wo"]) and not any(v & 31 for v in w["wa"]) and not any(v & 15 for v in w["xs"]), (H, W, w)
+            assert not conv2_f43 or not any(v & 31 for v in w["wo"]), (H, W, w)
+            for n in ("wl", "wo", "wa"):
+                assert LR.inside(w[n], (0, 0, w["PH"], w["PW"])), (H, W, n, w)      # (a padded size is a multiple of 64: no round-out leaves it)
+            assert LR.inside(w["crop"], LR.pre_checkable(w)), (H, W, w)
+
+
+def test_tightest_window_is_one_row_behind_the_crop():
+    """(64 + H) = 15 (mod 16): the crop's last row reads o2 row 64 + H, and wo (the 16-aligned form) ends exactly there, one row behind the
+    crop, with wl; one row less and conv_last would read a stale row."""
+    tight = [H for H in range(1, 257) if (LR.CROP0 + H) % 16 == 15]
+    assert tight[:3] == [15, 31, 47] and len(tight) == 16
+    for H in tight:
+        w = LR.crop_windows(H, H, False)
+        assert w["wo"][2] == w["wo"][3] == LR.CROP0 + H + 1 == w["wl"][2]
+        assert LR.window_faults(w) == []
+        for side in (2, 3):
+            v = list(w["wo"])
+            v[side] -= 1
+            assert LR.window_faults(dict(w, wo=tuple(v))) == ["last: reads o2 outside wo"]
+        # the rows of wl behind the crop have no reference: their taps reach past wo
+        assert LR.pre_checkable(w)[2:] == (LR.CROP0 + H, LR.CROP0 + H)
+    for H in range(1, 257):         # nowhere else is wo that tight on the far side
+        if H not in tight:
+            assert LR.crop_windows(H, H, False)["wo"][2] > LR.CROP0 + H + 1
+
+
+# One source size per window form, both padded to 192 x 192.  16-aligned wo: crop ends 79 = 15 (mod 16) on both axes, the tight end, where wo ends
+# at 80 = 16 (mod 32) and every strip of all three windows is read.  32-aligned wo: 79 on y and 127 = 31 (mod 32) on x, the one residue at which
+# the far wa strip reaches the crop.
+WIN_SRC = {False: (15, 15), True: (15, 63)}
+SHRINKS = [(n, side) for n in ("wo", "wa", "xs") for side in range(4)]
+
+
+def _cone(w):
+    """What a crop pixel depends on, by index arithmetic: the o2, a2 and xs2 elements inside the frame."""
+    PH, PW = w["PH"], w["PW"]
+    o2 = LR.reads3(w["crop"], PH, PW)
+    return {"wo": o2, "wa": LR.reads3(o2, PH, PW), "xs": LR.reads_half(o2, PH, PW)}
+
+
+def _meet(a, b):
+    return max(a[0], b[0]) < min(a[2], b[2]) and max(a[1], b[1]) < min(a[3], b[3])
+
+
+def _strip(win, side, tile):
+    """What shrink(win, side, tile) takes off."""
+    v = list(win)
+    if side < 2:
+        v[side + 2] = win[side] + tile
+    else:
+        v[side - 2] = win[side] - tile
+    return tuple(v)
+
+
+@pytest.fixture(scope="module")
+def window_decode(weights):
+    """The float64 decoder stages behind o3 at 192 x 192 (slice2.conv1 + shortcut, slice2.conv2, conv_last) for the source sizes of WIN_SRC: frame A
+    is what the call stylizes, every tensor holds frame B's values (an unrelated o3 through the same stages; noise on the rows no window
+    reaches) wherever the windowed evaluation does not write.  Every evaluation runs the stage on the same rows at the full width and then
+    keeps the window, so two evaluations whose inputs agree on what a value reads give that value bit for bit."""
+    st = LR.parse_state(load_golden("global_a")["state"])
+    rng = np.random.default_rng(77)
+    P = 192
+    assert {LR.padded_size(n) for hw in WIN_SRC.values() for n in hw} == {P}
+    ROWS = 128          # a2 rows evaluated: no window of either form goes further down (asserted below)
+    full, stale = {}, {}
+    for who, seed in ((full, 1), (stale, 2)):
+        o3 = np.random.default_rng(seed).standard_normal((P // 2, P // 2, 128))
+        a2 = rng.standard_normal((P, P, 64))
+        a2[:ROWS] = LR.STAGES["a2"][2]([o3], weights, st, 0, ROWS)[0]
+        who["a2"], who["xs2"] = a2, LR.STAGES["xs2"][2]([o3], weights, st, 0, P // 2)[0]
+    stale["o2"] = rng.standard_normal((P, P, 64))
+
+    def paste(dst, src, win):
+        y0, x0, y1, x1 = LR.clip(win, *dst.shape[:2])
+        out = dst.copy()
+        out[y0:y1, x0:x1] = src[y0:y1, x0:x1]
+        return out
+
+    def run(w, base):
+        """(crop, o2 on the unshrunk wo) of frame A evaluated through the windows w; base: the unshrunk windows (they fix the rows evaluated)."""
+        assert base["wa"][2] <= ROWS
+        y0, _, y1, _ = base["wo"]
+        a2 = paste(stale["a2"], full["a2"], w["wa"])
+        xs = paste(stale["xs2"], full["xs2"], w["xs"])
+        v = np.zeros((P, P, 64))
+        v[y0:y1] = LR.STAGES["o2"][2]([a2, xs], weights, st, y0, y1)[0]
+        o2 = paste(stale["o2"], v, w["wo"])
+        cy0, cx0, cy1, cx1 = base["crop"]
+        pre = LR.STAGES["pre"][2]([o2], weights, st, cy0, cy1)[0][:, cx0:cx1]
+        by0, bx0, by1, bx1 = base["wo"]
+        return pre, o2[by0:by1, bx0:bx1]
+
+    return run
+
+
+@pytest.mark.parametrize("conv2_f43", [False, True], ids=["f23", "f43"])
+def test_windows_are_necessary_on_the_float64_decoder(window_decode, conv2_f43):
+    """The crop evaluated through the windows of LR.crop_windows from tensors that hold another frame's values everywhere else equals the
+    evaluation through windows that cover everything, exactly.  Then each of wo, wa and the shortcut window one tile short on one side (16;
+    32 for the fused conv1's items and for wo where conv2 runs on conv_f43_k; 16 half-resolution pixels for xs2):
+      - window_faults names the broken condition and o2 inside wo changes, exactly where index arithmetic says a wo pixel (for wo: a crop
+        pixel) reads the strip taken off;
+      - the CROP changes exactly where index arithmetic says a crop pixel depends on that strip (_cone).
+    16-aligned wo, 15 x 15: all twelve strips break a condition and all twelve change the crop.
+    32-aligned wo, 15 x 63: the wo and wa strips break their conditions, the xs2 strips do not, at this or ANY size.  wo starts at 32, so wa
+    starts at 0 and xs2 at 0, and the near xs2 strip 0..15 ends where wo's first row reads (32 // 2); wo ends on a multiple of 32, so wa ends
+    32 further, xs2 16 further, and the far xs2 strip starts at wo's end halved, one row behind the last one read.  The fused kernel writes
+    its shortcut for whole 32 x 32 items, a tile more than conv2 reads on each side: larger than needed, not smaller, which is the side the
+    GPU suite pins by comparing what was written.  Of the strips that break a condition, the crop sees both wo strips per axis and the far wa
+    strip on x: the near wa strip 0..31 ends 30 rows before a2 row 62 = 64 - 2, the first a crop pixel depends on, at every size, and the far
+    one starts at wo's end, which the crop's last a2 row 64 + n + 1 reaches only for 64 + n = 31 (mod 32), as on x here."""
+    base = LR.crop_windows(*WIN_SRC[conv2_f43], conv2_f43)
+    PH, PW = base["PH"], base["PW"]
+    everything = dict(base, wo=(0, 0, PH, PW), wa=(0, 0, PH, PW), xs=(0, 0, PH // 2, PW // 2))
+    ref_crop, ref_o2 = window_decode(everything, base)
+    crop, o2 = window_decode(base, base)
+    assert np.array_equal(crop, ref_crop) and np.array_equal(o2, ref_o2)
+    assert LR.window_faults(base) == []
+    cone = _cone(base)
+    wo_in = LR.clip(base["wo"], PH, PW)
+    needed = {"wo": cone["wo"], "wa": LR.reads3(wo_in, PH, PW), "xs": LR.reads_half(wo_in, PH, PW)}
+    tiles = {"wo": 32 if conv2_f43 else 16, "wa": 32, "xs": 16}
+    want = {"wo": "last: reads o2 outside wo", "wa": "conv2: reads a2 outside wa", "xs": "res: reads xs2 outside its window"}
+    broke, seen = set(), set()
+    for name, side in SHRINKS:
+        w = dict(base)
+        w[name] = LR.shrink(base[name], side, tiles[name])
+        strip = _strip(base[name], side, tiles[name])
+        breaks, visible = _meet(strip, needed[name]), _meet(strip, cone[name])
+        assert (want[name] in LR.window_faults(w)) == breaks, (name, side, LR.window_faults(w))
+        crop, o2 = window_decode(w, base)
+        assert np.array_equal(o2, ref_o2) != breaks, (name, side, breaks)
+        assert np.array_equal(crop, ref_crop) != visible, (name, side, visible)
+        broke |= {(name, side)} if breaks else set()
+        seen |= {(name, side)} if visible else set()
+    if conv2_f43:
+        assert broke == {s for s in SHRINKS if s[0] != "xs"}, broke
+        assert seen == {("wo", 0), ("wo", 1), ("wo", 2), ("wo", 3), ("wa", 3)}, seen
+    else:
+        assert broke == seen == set(SHRINKS), (broke, seen)
