@@ -736,6 +736,73 @@ int rrv_transfer_guided(rrv_handle h, const void* frames, rrv_image_desc in, int
                         int DH, int DW, int r, float eps, void* out, rrv_image_desc out_desc, int flags);
 int rrv_guided_tile(int H, int W, int DH, int DW, int r, int* tw, int* sy, int* sx, int* apply_lds_bytes, int* coeff_lds_bytes);
 
+/* Compositing: the stylized frame mixed with its own source on the GPU, behind the delivery or guided stage and in front of the output form:
+ * how strongly the style applies (strength, per frame), where (a matte, per pixel) and whether the source keeps its colours or its luminance.
+ * Inputs, per frame, float32 HWC BGR PIXEL of the delivered size DH x DW: P, the stylized frame at the delivered size (the working frame itself,
+ * the delivery stage's bilinear result, or the guided stage's Q), and S, the source at the delivered size.
+ * Arithmetic, each operation rounded to float32 and none contracted:
+ *   g(v)   = (0.114f v_B + 0.587f v_G) + 0.299f v_R                the guided stage's luma
+ *   keep RRV_KEEP_NONE:    C_c = P_c
+ *   keep RRV_KEEP_COLOUR:  d = g(P) - g(S);  C_c = S_c + d         source colours, stylized luminance (the luminance-only transfer of Gatys et
+ *                                                                  al., "Preserving Color in Neural Artistic Style Transfer", 2016)
+ *   keep RRV_KEEP_LUMA:    d = g(S) - g(P);  C_c = P_c + d         stylized colours, source luminance
+ *   alpha  = strength_b                                            without a matte
+ *          = strength_b * m(y, x)                                  float32 matte
+ *          = strength_b * ((float)u(y, x) / 255.0f)                uint8 matte
+ *   out_c  = (1.0f - alpha) * S_c + alpha * C_c                    two products and one sum; not clamped
+ * For finite inputs alpha == 0 returns S_c numerically equal and alpha == 1 returns C_c bit for bit: inside a hard matte the result is the
+ * stylized frame's bits, outside it the source's.  strength_b must lie in [0, 1]; anything else, NaN included, is RRV_E_ARG.  Matte values are
+ * device data and are not checked: values outside 0..1 extrapolate.  The result then reaches the output form asked for through the delivery
+ * stage at equal size (the identity on values, as Q does in "Guided delivery"), so every output form, YUV layout, bit depth and pitched view
+ * is, word for word, that of "Output size" applied to v = out.  Frame b's result does not depend on B.
+ *   rrv_composite              the request: per-frame strengths in HOST memory (NULL: 1 for every frame), the matte ([matte_frames][DH][DW]
+ *                              contiguous, RRV_DT_F32 or RRV_DT_U8, matte_frames 1 = one matte for every frame, or B; device memory for the
+ *                              device entries, host memory for the host twin; NULL: none) and keep
+ *   rrv_composite_view_device  the stage alone: B (1..64) contiguous frames d_P and d_src -> DH x DW frames through `out`, queued on hip_stream
+ *                              (NULL: the null stream); nothing of the handle's own streams takes part.  The mixed frame lives in a buffer of the
+ *                              handle: calls on different streams must be ordered by the caller.  The buffers need only be element aligned
+ *   rrv_transfer_composite_view_device
+ *                              rrv_transfer_deliver_view_device (r = 0) or rrv_transfer_guided_view_device (r, eps) with a request: S is the
+ *                              call's own source frames through the input resampler to the delivered size -- at equal size the first kernel's
+ *                              float32 PIXEL value of each source pixel, bit for bit, whatever the input form; the resampled working input of a
+ *                              scaled call when the working frame is the one delivered; the guided stage's X_hi.  The source need not have the
+ *                              delivered size: any ratio the resampler accepts (<= 8 per axis).  Needs a delivered working frame of H x W
+ *                              (RRV_TF_PAD_CROP, or H and W multiples of 8) and the GLOBAL or FRAME model.  c == NULL, or no matte with every
+ *                              strength 1 and keep RRV_KEEP_NONE, is exactly the call without a request: no kernel is added, every bit is what
+ *                              it was
+ *   rrv_transfer_composite     the host twin through the host pipeline, any B; sub-batches by the sizing rules of rrv_transfer_deliver; the matte
+ *                              rides each sub-batch's staging with its frames; strengths and a per-frame matte are indexed by the frame's
+ *                              position in the whole call
+ *   rrv_composite_grid         the launch rule of the stage for B frames of DH x DW: a thread takes 4 consecutive pixels of the flat run of
+ *                              B * DH * DW per step, 256 threads per workgroup, grid = min(ceil(B DH DW / 1024), 2048) workgroups and
+ *                              pixels_per_pass = grid * 1024; larger runs are grid-strided.  No handle, no GPU; RRV_E_ARG for a null pointer or
+ *                              sizes below 1
+ * A compositing call equals, bit for bit in a fixed kernel mode, the float32 HWC BGR PIXEL call with the same sizes and guide, the resampler
+ * alone for the source at the delivered size, and rrv_composite_view_device into the form asked for.
+ * Checks, all before any GPU work: those of the entry without a request, then the request (strength, keep, matte_dtype, matte_frames); RRV_E_ARG
+ * names the field and the handle stays usable.  Per workspace slot the stage shares the guided stage's X_hi and Q buffers (12 bytes per
+ * delivered pixel and frame each), reserved with the tables before the call's first launch: out of memory is RRV_E_NOMEM and the handle stays
+ * usable.
+ * Not offered: blended and masked compositing, tickets and the one-frame entries, a matte at any size but the delivered one. */
+#define RRV_KEEP_NONE 0
+#define RRV_KEEP_COLOUR 1
+#define RRV_KEEP_LUMA 2
+typedef struct rrv_composite {
+    const float* strength;   /* host memory, one per frame of the call; NULL: 1 for every frame */
+    const void* matte;       /* NULL: none.  [matte_frames][DH][DW] contiguous; device memory for the device entries, host for the host twin */
+    int matte_dtype;         /* RRV_DT_F32 or RRV_DT_U8 */
+    int matte_frames;        /* 1 (one matte for every frame) or B */
+    int keep;                /* RRV_KEEP_* */
+} rrv_composite;
+int rrv_composite_view_device(rrv_handle h, const float* d_P, const float* d_src, int B, int DH, int DW, const rrv_composite* c,
+                              void* d_out, const rrv_image_view* out, void* hip_stream);
+int rrv_transfer_composite_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W,
+                                       int DH, int DW, int r, float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out,
+                                       int flags, void* hip_stream);
+int rrv_transfer_composite(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W,
+                           int DH, int DW, int r, float eps, const rrv_composite* c, void* out, rrv_image_desc out_desc, int flags);
+int rrv_composite_grid(int B, int DH, int DW, unsigned* grid, int* pixels_per_pass);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
 # reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
-# needs a copy of it there.
+# needs a copy of it there (and of librerevst_compose.so).
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -28,6 +28,11 @@ class ImageView(C.Structure):
     _fields_ = [("desc", ImageDesc), ("frame_stride", C.c_int64), ("plane_offset", C.c_int64 * 3), ("pitch", C.c_int64 * 3)]
 
 
+class Composite(C.Structure):
+    """rrv_composite: a compositing request (per-frame strengths in host memory, the matte, what the source keeps)."""
+    _fields_ = [("strength", C.POINTER(C.c_float)), ("matte", C.c_void_p), ("matte_dtype", C.c_int), ("matte_frames", C.c_int), ("keep", C.c_int)]
+
+
 DT_U8, DT_F32 = 0, 1
 DT_U16 = 2                        # uint16 samples: only with LAY_I420_16 / LAY_P016
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
@@ -39,6 +44,7 @@ LAY_I422, LAY_NV16, LAY_I422_16, LAY_P216 = LAY_I420 | LAY_422, LAY_NV12 | LAY_4
 LAY_I444, LAY_NV24, LAY_I444_16, LAY_P416 = LAY_I420 | LAY_444, LAY_NV12 | LAY_444, LAY_I420_16 | LAY_444, LAY_P016 | LAY_444      # 34, 35, 40, 41
 YUV_BT601, YUV_BT709 = 0, 1
 SP_PIXEL, SP_UNIT, SP_NORM = 0, 1, 2
+KEEP_NONE, KEEP_COLOUR, KEEP_LUMA = 0, 1, 2
 TF_PAD_CROP, TF_FRAME_MODE, TF_ON_STREAM, TF_WEIGHTS_DEVICE = 1, 2, 4, 8
 DBG_STATE_SET, DBG_STYLE_PRED, DBG_STYLE_BLOB = 0, 1, 2
 # rrv_debug_copy_prep_tensor: 0..19 the preparation workspace in this order, then a sampled frame's stored feature, the style
@@ -162,6 +168,14 @@ SYMBOLS = {
     "rrv_transfer_guided": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, ImageDesc, C.c_int]),
     "rrv_guided_tile": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),      # no handle: (H, W, DH, DW, r, tw, sy, sx, apply LDS, coeff LDS)
+    # compositing: (..., DH, DW[, r, eps], Composite* c, out, ...): the delivered frame mixed with its source by strength, matte and keep (r = 0: bilinear delivery)
+    "rrv_composite_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Composite), C.c_void_p, C.POINTER(ImageView),
+                                            C.c_void_p]),
+    "rrv_transfer_composite_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_float, C.POINTER(Composite), C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),
+    "rrv_transfer_composite": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.POINTER(Composite), C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_composite_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_int)]),      # no handle: (B, DH, DW, grid, pixels per pass)
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

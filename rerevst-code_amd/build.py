@@ -1,7 +1,8 @@
 """Builds librerevst_stages.so (the kernels of the frame stages around the network: input resampler, delivery, guided delivery; one
-translation unit, csrc/stages.hip) and librerevst_hip.so (everything else, linked against it) in-tree with hipcc for gfx950
-(cross-compiles without a GPU).  Two libraries so that the main unit's kernel set and compile time stay what they are and the stages
-rebuild in seconds."""
+translation unit, csrc/stages.hip), librerevst_compose.so (the compositing stage behind them; one translation unit, csrc/compose.hip) and
+librerevst_hip.so (everything else, linked against both) in-tree with hipcc for gfx950 (cross-compiles without a GPU).  Three libraries so
+that the main unit's kernel set and compile time stay what they are, the stages rebuild in seconds, and the stages' kernel set stays the
+sixteen its ledgers pin until the compositing kernels move in with them."""
 import os
 import subprocess
 import sys
@@ -11,9 +12,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librerevst_hip.so")
 STAGES_LIB = os.path.join(HERE, "librerevst_stages.so")
 SOURCES = ["rerevst_hip.hip"]
+COMPOSE_LIB = os.path.join(HERE, "librerevst_compose.so")
 STAGES_SOURCES = ["stages.hip"]
+COMPOSE_SOURCES = ["compose.hip"]
+COMPOSE_HEADERS = ["compose.h", "compose_k.h"]
 STAGES_HEADERS = ["resample_k.h", "deliver_k.h", "guided_k.h", "rs_tile.h", "resample.h", "deliver.h", "guided.h", "conv_thin.h", "conv_mfma.h"]
-HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "resample.h", "deliver.h", "guided.h",
+HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "resample.h", "deliver.h", "guided.h", "compose.h",
            "../../include/rerevst_hip.h"]
 
 
@@ -32,14 +36,18 @@ def _run(cmd, verbose):
 
 def build_lib(force=False, verbose=True, extra=()):
     stages = force or _newer(STAGES_LIB, STAGES_SOURCES + STAGES_HEADERS)
-    if not stages and not _newer(LIB, SOURCES + HEADERS):
+    compose = force or _newer(COMPOSE_LIB, COMPOSE_SOURCES + COMPOSE_HEADERS)
+    if not stages and not compose and not _newer(LIB, SOURCES + HEADERS):
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-result"]
     if stages:
         _run([*common, *[os.path.join(CSRC, s) for s in STAGES_SOURCES], "-o", STAGES_LIB], verbose)
-    # the main library finds its companion next to itself, wherever the package lies
-    _run([*common, *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-L" + HERE, "-lrerevst_stages", "-Wl,-rpath,$ORIGIN", "-o", LIB], verbose)
+    if compose:
+        _run([*common, *[os.path.join(CSRC, s) for s in COMPOSE_SOURCES], "-o", COMPOSE_LIB], verbose)
+    # the main library finds its companions next to itself, wherever the package lies
+    _run([*common, *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-L" + HERE, "-lrerevst_stages", "-lrerevst_compose", "-Wl,-rpath,$ORIGIN", "-o", LIB],
+         verbose)
     return LIB
 
 

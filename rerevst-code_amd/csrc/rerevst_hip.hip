@@ -28,6 +28,7 @@
 #include "mask_kernels.h"
 #include "resample.h"      // librerevst_stages.so: parameters and the launch entry of the resampler
 #include "guided.h"        //                       of the guided delivery stage
+#include "compose.h"       //                       of the compositing stage (librerevst_compose.so)
 #include "deliver.h"       //                       of the output-side resampler
 
 namespace {
@@ -279,6 +280,8 @@ struct rrv_ctx {
     // rrv_deliver_guided_view_device's own coefficient planes and result (it runs on the caller's stream, beside whatever the slots hold in flight)
     float* gd_ab = nullptr; size_t gd_ab_cap = 0;
     float* gd_q = nullptr; size_t gd_q_cap = 0;
+    // rrv_composite_view_device's own mixed frame (it runs on the caller's stream too)
+    float* cm_buf = nullptr; size_t cm_cap = 0;
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -1198,6 +1201,12 @@ struct Xfer {
     // Guided delivery (include/rerevst_hip.h "Guided delivery"): radius in working pixels (0: plain delivery) and eps of a 0..1 image.  The stylized
     // working frame then reaches DH x DW through gf_coeff_k / gf_apply_k with the call's own source frames as the guide, equal sizes included.
     int gr = 0; float geps = 0.f;
+    // Compositing (include/rerevst_hip.h "Compositing"; set_composite): the delivered float32 frame is mixed with the call's own source at the
+    // delivered size before it reaches the output form.  cstr: one strength per frame of THIS request in host memory (null: 1); cmatte:
+    // [cm_frames][OH][OW] in HBM (null: none), cm_frames 1 or B.  comp unset: nothing is composited and nothing of this is read.
+    bool comp = false;
+    const float* cstr = nullptr; const void* cmatte = nullptr;
+    int cm_dt = RRV_DT_F32, cm_frames = 0, ckeep = RRV_KEEP_NONE;
     // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
     bool on_stream = false; hipStream_t with = nullptr;
 
@@ -1208,7 +1217,7 @@ struct Xfer {
     int WW() const { return pad ? W : W / 8 * 8; }
     bool delivering() const { return (DH != 0 || DW != 0) && (DH != WH() || DW != WW()); }
     bool guided() const { return gr != 0; }
-    bool staged() const { return delivering() || guided(); }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
+    bool staged() const { return delivering() || guided() || comp; }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
     int OH() const { return delivering() ? DH : WH(); }       // the frame delivered
     int OW() const { return delivering() ? DW : WW(); }
     ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
@@ -1221,6 +1230,8 @@ struct Xfer {
         return fmt.yuv ? yuv_frame_samples(OH(), OW(), fmt.cs) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
     }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
+    size_t matte_bytes() const { return (size_t)OH() * OW() * (cm_dt == RRV_DT_U8 ? 1 : 4); }                      // of one frame's matte
+    bool src_is_rs() const { return scaled() && !delivering(); }      // comp: S is the resampled working input (the delivered frame is the working frame)
     PadCrop pad_crop() const { return PadCrop{H, W, 64, 64}; }
     CallerOrder order(rrv_handle h) const { return on_stream ? CallerOrder{with, true} : CallerOrder{h->caller_stream, h->caller_sync}; }
 };
@@ -2179,7 +2190,7 @@ int rrv_destroy(rrv_handle h) {
     for (rrv_ctx::Slot& sl : h->slots) if (sl.dl_buf) (void)hipFree(sl.dl_buf);
     for (rrv_ctx::Slot& sl : h->slots)
         for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
-    for (float* q : {h->gd_ab, h->gd_q}) if (q) (void)hipFree(q);
+    for (float* q : {h->gd_ab, h->gd_q, h->cm_buf}) if (q) (void)hipFree(q);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
@@ -2981,9 +2992,19 @@ static int reserve_stages(rrv_handle h, int slot, int frames, const Xfer& x) {
     if (!x.staged()) return RRV_OK;
     const int H = x.WH(), W = x.WW();
     const rrv_ctx::RsTab *ty, *tx;
-    RCHK(x.guided() ? gd_tables(h, H, W, x.DH, x.DW) : rs_pair(h, H, W, x.DH, x.DW, &ty, &tx));
+    if (x.guided()) RCHK(gd_tables(h, H, W, x.DH, x.DW));
+    else if (x.delivering()) RCHK(rs_pair(h, H, W, x.DH, x.DW, &ty, &tx));
     rrv_ctx::Slot& sl = h->slots[slot];
     RCHK(ensure_dev(h, sl.dl_buf, sl.dl_cap, (size_t)frames * H * W * 3));
+    if (x.comp) {      // the equal-size tables of the delivered frame, S where the source is resampled for it, P where the working frame is not it
+        const int OH = x.OH(), OW = x.OW();
+        RCHK(rs_pair(h, OH, OW, OH, OW, &ty, &tx));
+        if (!x.guided() && !x.src_is_rs()) {
+            RCHK(rs_pair(h, x.IH(), x.IW(), OH, OW, &ty, &tx));
+            RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * OH * OW * 3));
+        }
+        if (!x.guided() && x.delivering()) RCHK(ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * OH * OW * 3));
+    }
     if (!x.guided()) return RRV_OK;
     RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * x.DH * x.DW * 3));
     RCHK(ensure_dev(h, sl.gd_ab, sl.gd_ab_cap, (size_t)frames * H * W * 6));
@@ -3010,6 +3031,54 @@ static int guided_launch(rrv_handle h, const Seq& q, const float* P, const float
     return RRV_OK;
 }
 
+// ---- compositing (include/rerevst_hip.h "Compositing"): the delivered float32 frame mixed with the source at the delivered size
+int rrv_composite_grid(int B, int DH, int DW, unsigned* grid, int* pixels_per_pass) {
+    if (!grid || !pixels_per_pass || B < 1 || DH < 1 || DW < 1) return RRV_E_ARG;
+    *grid = compose_grid((size_t)B * (size_t)DH * (size_t)DW);
+    *pixels_per_pass = (int)(*grid * 1024u);
+    return RRV_OK;
+}
+// A request as an entry got it -> the fields of `x`, judged before any GPU work; B: the frames `c->strength` holds.  A request that composites
+// nothing (null; no matte, every strength 1, keep none) leaves x as it is: the call is then the one without a request.
+static int set_composite(rrv_handle h, const char* who, const rrv_composite* c, int B, Xfer* x) {
+    if (!c) return RRV_OK;
+    const std::string w = std::string(who) + ": ";
+    if (c->keep != RRV_KEEP_NONE && c->keep != RRV_KEEP_COLOUR && c->keep != RRV_KEEP_LUMA) return fail(h, RRV_E_ARG, w + "keep must be one of RRV_KEEP_NONE, RRV_KEEP_COLOUR, RRV_KEEP_LUMA");
+    if (B < 1) return fail(h, RRV_E_ARG, w + "batch must be at least 1");
+    bool ones = true;
+    if (c->strength)
+        for (int b = 0; b < B; ++b) {
+            const float v = c->strength[b];
+            if (!(v >= 0.f && v <= 1.f)) return fail(h, RRV_E_ARG, w + "strength must lie in 0..1 for every frame");      // (NaN fails both comparisons)
+            ones = ones && v == 1.f;
+        }
+    if (c->matte) {
+        if (c->matte_dtype != RRV_DT_F32 && c->matte_dtype != RRV_DT_U8) return fail(h, RRV_E_ARG, w + "matte_dtype must be RRV_DT_F32 or RRV_DT_U8");
+        if (c->matte_frames != 1 && c->matte_frames != B) return fail(h, RRV_E_ARG, w + "matte_frames must be 1 or B");
+    }
+    if (!c->matte && ones && c->keep == RRV_KEEP_NONE) return RRV_OK;
+    x->comp = true;
+    x->cstr = c->strength; x->cmatte = c->matte; x->cm_dt = c->matte_dtype; x->cm_frames = c->matte ? c->matte_frames : 0; x->ckeep = c->keep;
+    return RRV_OK;
+}
+// B frames P and S -> out (may be P), all contiguous [OH][OW][3] float32 BGR PIXEL; str: B strengths in host memory (null: 1); queued on q.stream
+static int composite_launch(rrv_handle h, const Seq& q, const float* P, const float* S, int B, int OH, int OW, const float* str, const void* matte, int matte_dt,
+                            int matte_frames, int keep, float* out) {
+    ComposeP p{};
+    p.P = P; p.S = S; p.matte = matte; p.out = out;
+    p.frame_px = (size_t)OH * (size_t)OW; p.B = B; p.matte_frames = matte_frames; p.keep = keep;
+    for (int b = 0; b < B; ++b) p.strength[b] = str ? str[b] : 1.0f;
+    const int form = !matte ? CM_NONE : matte_dt == RRV_DT_U8 ? CM_U8 : CM_F32;
+    int e = 0;
+    // for the profile log: bytes from the shapes (P and S read, the result written, the matte read once per frame); two products and a sum per value, the lumas
+    const double px = (double)B * OH * OW;
+    RCHK(launch(h, q, "composite", (9.0 + (keep ? 14.0 : 0.0) + (matte ? 2.0 : 1.0)) * px, (36.0 + (form == CM_F32 ? 4.0 : form == CM_U8 ? 1.0 : 0.0)) * px, [&] {
+        e = rrv_compose_launch(&p, form, q.stream);
+    }, -1.0, compose_grid((size_t)B * p.frame_px)));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("composite: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+
 // The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
 // burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
 static int next_device_slot(rrv_handle h) {
@@ -3032,6 +3101,11 @@ static int check_xfer(rrv_handle h, const Xfer& x, bool host = false, bool state
         if (x.model != Model::GLOBAL && x.model != Model::FRAME) return fail(h, RRV_E_ARG, "transfer_guided: blended and masked guided delivery are not offered");
         if (x.DH != x.IH() || x.DW != x.IW()) return fail(h, RRV_E_ARG, "transfer_guided: DH x DW must be the size of the frames as passed (SH x SW; H x W with SH = SW = 0)");
         if (x.WH() != x.H || x.WW() != x.W) return fail(h, RRV_E_ARG, "transfer_guided: H and W must be multiples of 8 without RRV_TF_PAD_CROP (the stylized working frame is then H x W)");
+    }
+    if (x.comp) {      // (the request itself: set_composite)
+        if (x.model != Model::GLOBAL && x.model != Model::FRAME) return fail(h, RRV_E_ARG, "transfer_composite: blended and masked compositing are not offered");
+        if (x.WH() != x.H || x.WW() != x.W) return fail(h, RRV_E_ARG, "transfer_composite: H and W must be multiples of 8 without RRV_TF_PAD_CROP (the stylized working frame is then H x W)");
+        if (!x.guided() && !x.src_is_rs()) RCHK(check_scale(h, "transfer_composite: the source against the delivered frame", x.IH(), x.IW(), x.OH(), x.OW()));
     }
     if ((blend || mask) && (x.ns < 1 || x.ns > RRV_MAX_STYLES)) return fail(h, RRV_E_ARG, "transfer: n_styles must be in 1..RRV_MAX_STYLES");
     if (blend && !x.wts) return fail(h, RRV_E_ARG, "transfer: null style weights");
@@ -3130,13 +3204,31 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             sl.set_images = cnt;
             break;
         }
+        // What leaves through the delivery stage: the staged working frames (PH x PW = the working size), or the guided stage's Q at the
+        // delivered size.  A compositing request brings P to the delivered size first -- Q, or the delivery stage's float32 PIXEL result in
+        // Q's buffer, or the working frame itself -- and mixes it in place with S: the guided stage's X_hi, the scaled request's working
+        // input when that frame is the one delivered, else the source through the resampler into X_hi's buffer.
+        if (!staged) continue;
+        const int OH = x.OH(), OW = x.OW();
+        float* P = sl.dl_buf;
+        int PH = x.WH(), PW = x.WW();
         if (guided) {
             RCHK(resample_launch(h, q, src, x.in, vi, cnt, x.DH, x.DW, x.DH, x.DW, sl.gd_xhi));
             RCHK(guided_launch(h, q, sl.dl_buf, scaled ? sl.rs_buf : sl.gd_xhi, sl.gd_xhi, cnt, x.WH(), x.WW(), x.DH, x.DW, x.gr, x.geps, sl.gd_ab, sl.gd_q));
-            RCHK(deliver_launch(h, q, sl.gd_q, cnt, x.DH, x.DW, x.DH, x.DW, dst, x.fmt, vo));
-        } else if (delivering) {
-            RCHK(deliver_launch(h, q, sl.dl_buf, cnt, x.WH(), x.WW(), x.DH, x.DW, dst, x.fmt, vo));
+            P = sl.gd_q; PH = OH; PW = OW;
         }
+        if (x.comp) {
+            const float* S = sl.gd_xhi;
+            if (!guided && delivering) {
+                RCHK(deliver_launch(h, q, sl.dl_buf, cnt, PH, PW, OH, OW, sl.gd_q, OUT_F32, contiguous_view(VL_HWC, OH, OW)));
+                P = sl.gd_q; PH = OH; PW = OW;
+            }
+            if (!guided && x.src_is_rs()) S = sl.rs_buf;
+            else if (!guided) RCHK(resample_launch(h, q, src, x.in, vi, cnt, x.IH(), x.IW(), OH, OW, sl.gd_xhi));
+            const void* const matte = x.cmatte && x.cm_frames != 1 ? (const char*)x.cmatte + (size_t)b0 * x.matte_bytes() : x.cmatte;
+            RCHK(composite_launch(h, q, P, S, cnt, OH, OW, x.cstr ? x.cstr + b0 : nullptr, matte, x.cm_dt, x.cm_frames == 1 ? 1 : cnt, x.ckeep, P));
+        }
+        RCHK(deliver_launch(h, q, P, cnt, PH, PW, OH, OW, dst, x.fmt, vo));
     }
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, sl.stream));
@@ -3458,8 +3550,9 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     HIPCHK(hipSetDevice(h->dev));
     RCHK(check_xfer(h, x, true, state_first));
     const int B = x.B;
-    const float* const mask = x.mask;
-    const int mask_images = x.mask_images;
+    // what rides the staging beside the frames: the MASK model's style masks, or a compositing request's matte (host memory here); in bytes
+    const char* const mask = x.comp ? (const char*)x.cmatte : (const char*)x.mask;
+    const int mask_images = x.comp ? x.cm_frames : x.mask_images;
     const size_t fb = x.in_bytes();                                        // input bytes per frame
     const size_t fob = x.out_bytes();                     // output bytes per frame
     char* const outc = (char*)out;
@@ -3469,20 +3562,24 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // the page-locked and device staging per set stays within four times the unscaled call's.
     if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
     // the same rule for the DELIVERED frame, which sizes the output staging
-    if (x.staged()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.DH * x.DW)));
-    const size_t mfl = x.mask_floats();
+    if (x.staged()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.OH() * x.OW())));
+    const size_t mfb = x.comp ? x.matte_bytes() : x.mask_floats() * sizeof(float);      // of one image's masks / one frame's matte
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
         part.B = nb;
         if (x.wts) part.wts = x.wts + (size_t)k * sub * x.ns;
-        if (mask) { part.mask = h->hstage[k % HOST_SETS].mask; part.mask_images = mask_images == 1 ? 1 : nb; }
+        if (mask && !x.comp) { part.mask = h->hstage[k % HOST_SETS].mask; part.mask_images = mask_images == 1 ? 1 : nb; }
+        if (x.comp) {      // strengths and a per-frame matte by the frame's position in the whole call
+            if (x.cstr) part.cstr = x.cstr + (size_t)k * sub;
+            if (mask) { part.cmatte = h->hstage[k % HOST_SETS].mask; part.cm_frames = mask_images == 1 ? 1 : nb; }
+        }
         return run_xfer(h, slot, d_in, d_out, part, hk);
     };
     const bool in_pin = is_pinned(frames, (size_t)B * fb), out_pin = is_pinned(out, (size_t)B * fob);
     // the masks are staged like the frames: a sub-batch's part goes through the set's page-locked block (unless the caller's array is
     // page-locked) to its HBM block by a copy on copy_in, in front of the in_done event its kernels wait for; k_done frees both again
-    const size_t msub = (size_t)(mask_images == 1 ? 1 : sub) * mfl;
-    const bool m_pin = mask && is_pinned(mask, (size_t)mask_images * mfl * sizeof(float));
+    const size_t msub = ((size_t)(mask_images == 1 ? 1 : sub) * mfb + sizeof(float) - 1) / sizeof(float);      // floats of a set's block
+    const bool m_pin = mask && is_pinned(mask, (size_t)mask_images * mfb);
     const bool host_in = !in_pin || (mask && !m_pin);      // a page-locked input block of the set is refilled by the host
     RCHK(claim_staging(h));
     const int nchunk = (B + sub - 1) / sub;
@@ -3533,12 +3630,12 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
         const int nb = count(k);
         const uint8_t* src = frames + (size_t)k * sub * fb;
         if (!in_pin) { host_copy(st.pin.in, src, (size_t)nb * fb); src = st.pin.in; }
-        const float* msrc = nullptr;
+        const char* msrc = nullptr;
         size_t mbytes = 0;
         if (mask) {
-            msrc = mask + (mask_images == 1 ? 0 : (size_t)k * sub * mfl);
-            mbytes = (size_t)(mask_images == 1 ? 1 : nb) * mfl * sizeof(float);
-            if (!m_pin) { host_copy(st.mask_pin, msrc, mbytes); msrc = st.mask_pin; }
+            msrc = mask + (mask_images == 1 ? 0 : (size_t)k * sub * mfb);
+            mbytes = (size_t)(mask_images == 1 ? 1 : nb) * mfb;
+            if (!m_pin) { host_copy(st.mask_pin, msrc, mbytes); msrc = (const char*)st.mask_pin; }
         }
         const int slot = slot_of(k);
         hipStream_t cs = h->slots[slot].stream;
@@ -3798,6 +3895,44 @@ int rrv_transfer_guided_view_device(rrv_handle h, const void* d_in, const rrv_im
     x.gr = r ? r : -1; x.geps = eps;      // (r = 0 is refused as a radius, not taken for a plain delivery)
     return view_run(h, "transfer_guided_view", d_in, in, d_out, out, flags, hip_stream, x);
 }
+// ---- the compositing entries (include/rerevst_hip.h "Compositing")
+// the stage alone and the equal-size delivery behind it, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own
+// streams takes part.  The mixed frame lives in a buffer of the handle that only this entry uses.
+int rrv_composite_view_device(rrv_handle h, const float* d_P, const float* d_src, int B, int DH, int DW, const rrv_composite* c, void* d_out,
+                              const rrv_image_view* out, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!out) return fail(h, RRV_E_ARG, "composite_view: null view");
+    OutFmt fmt;
+    if (!view_desc_ok(out->desc) || parse_out(out->desc, &fmt) != DescErr::OK)
+        return fail(h, RRV_E_ARG, "composite_view: out.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_P || !d_src || !d_out) return fail(h, RRV_E_ARG, "composite_view: null buffer");
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "composite_view: batch must be in 1..64");
+    RCHK(check_deliver(h, "composite_view", DH, DW, DH, DW));
+    Xfer x{Model::GLOBAL, B, DH, DW};
+    static const rrv_composite plain{nullptr, nullptr, RRV_DT_F32, 0, RRV_KEEP_NONE};
+    RCHK(set_composite(h, "composite_view", c ? c : &plain, B, &x));      // (the stage alone runs a request that composites nothing too: out = P)
+    std::string why;
+    if (!view_check(*out, B, DH, DW, true, &why)) return fail(h, RRV_E_ARG, "composite_view: out." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, DH, DW, DH, DW, &ty, &tx));
+    RCHK(ensure_dev(h, h->cm_buf, h->cm_cap, (size_t)B * DH * DW * 3));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    const rrv_composite& r = c ? *c : plain;
+    RCHK(composite_launch(h, q, d_P, d_src, B, DH, DW, r.strength, r.matte, r.matte_dtype, r.matte ? r.matte_frames : 0, r.keep, h->cm_buf));
+    return deliver_launch(h, q, h->cm_buf, B, DH, DW, DH, DW, d_out, fmt, img_view(*out));
+}
+int rrv_transfer_composite_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, int DH, int DW, int r,
+                                       float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    if (r) { x.gr = r; x.geps = eps; }
+    if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer_composite_view: batch must be in 1..64");      // (c->strength holds B values: judged before they are read)
+    RCHK(set_composite(h, "transfer_composite_view", c, B, &x));
+    return view_run(h, "transfer_composite_view", d_in, in, d_out, out, flags, hip_stream, x);
+}
 // a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {
     if (yuv_layout(d.layout)) return parse_in_view(d, in);
@@ -3830,6 +3965,16 @@ int rrv_transfer_guided(rrv_handle h, const void* frames, rrv_image_desc in, int
     x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
     x.gr = r ? r : -1; x.geps = eps;
     return scaled_host(h, "transfer_guided", false, frames, in, out, od, flags, x);
+}
+int rrv_transfer_composite(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, int r, float eps,
+                           const rrv_composite* c, void* out, rrv_image_desc od, int flags) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    x.SH = SH; x.SW = SW; x.DH = DH; x.DW = DW;
+    if (r) { x.gr = r; x.geps = eps; }
+    if (B < 1) return fail(h, RRV_E_ARG, "transfer_composite: batch must be at least 1");
+    RCHK(set_composite(h, "transfer_composite", c, B, &x));
+    return scaled_host(h, "transfer_composite", false, frames, in, out, od, flags, x);
 }
 // a sampled frame of SH x SW, resampled into slot 0's buffer on the handle's stream and added as the float32 PIXEL frame it then is.
 // device: d_frame is in HBM, complete once `stream` has run what it holds now; else host memory in the contiguous form of `fmt`

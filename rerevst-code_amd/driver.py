@@ -423,7 +423,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420", work_size=None, out_size=None, guided=None):
+                  chroma="420", work_size=None, out_size=None, guided=None, composite=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -443,7 +443,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     work_size=); the frames and the video written have the working size.  Needs a model with transfer_frames(work_size=).
     out_size=(H, W) or "source": the stylized working frame is resampled to that size on the GPU on its way out (transfer_frames with
     out_size=; "source": each frame's own size); the frames and the video written have that size.
-    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source"), the upscale follows the source's edges."""
+    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source"), the upscale follows the source's edges.
+    composite=dict(strength=, fade=, matte=, keep=): the stylized frame is mixed with the frame read on the GPU (Compositing; transfer_frames with
+    strength= / matte= / keep=); strengths and mattes go by the absolute frame number.  Needs a model with transfer_frames(strength=)."""
     import importlib
     import time
     from collections import deque
@@ -473,6 +475,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             raise ValueError("guided needs out_size (the size of the frames read)")
         scale_kw = dict(scale_kw, guide="source", guide_radius=guided[0], guide_eps=guided[1])
     add_kw = {} if work is None else {"work_size": work}                   # (a sampled frame is never delivered)
+    comp = Compositing(n, **composite) if composite else None
     # the size of the frame delivered for a source frame of (H, W)
     out_size = (lambda hw: hw) if deliver == "source" else (lambda hw: deliver) if deliver is not None else (lambda hw: hw) if work is None else (lambda hw: work)
     t_start = time.perf_counter()
@@ -590,7 +593,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     f.result()
                 t0 = time.perf_counter()
                 src, dst = views(k)
-                styled = on_device(src, out=dst, out_format=yuv_fmt, **scale_kw) if direct else on_device(src, out=dst, **scale_kw)
+                call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, out_size(src.shape[1:3])))
+                styled = on_device(src, out=dst, out_format=yuv_fmt, **call_kw) if direct else on_device(src, out=dst, **call_kw)
                 gpu_s += time.perf_counter() - t0
                 submit_decode(k + 2)             # its input buffer was chunk k-1's: consumed
                 futs = []
@@ -619,6 +623,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 raise ValueError("work_size needs a model with transfer_frames(work_size=)")
             if deliver is not None and hi > lo:
                 raise ValueError("out_size needs a model with transfer_frames(out_size=)")
+            if comp is not None and hi > lo:
+                raise ValueError("strength / fade / matte / keep need a model with transfer_frames(strength=)")
             tool = video.ReshapeTool()
             pending = deque()
             look = deque(pool.submit(read_image_bgr, frame_paths[i]) for i in range(lo, min(hi, lo + 2 * nthreads)))
@@ -659,7 +665,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
                 yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None, out_size=None,
-                guided=None):
+                guided=None, composite=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -675,7 +681,8 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     file's); the frames written and the .y4m header carry the working size.
     out_size=(H, W) or "source" (the file's frame size): the stylized working frame is resampled to that size on the GPU on its way out
     (transfer_frames with out_size=); the frames written, the output staging and the .y4m header carry the delivered size.
-    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source")."""
+    guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source").
+    composite=dict(strength=, fade=, matte=, keep=): as in stylize_files; the source mixed in is the file's frame as the GPU reads it."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -704,6 +711,7 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
             if out_size is None:
                 raise ValueError("guided needs out_size (the size of the frames read)")
             scale_kw.update(guide="source", guide_radius=guided[0], guide_eps=guided[1])
+        comp = Compositing(n, **composite) if composite else None
         fob = video.yuv_frame_bytes(OH, OW, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
@@ -763,10 +771,11 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
                 f.result()
             src, dst = in_buf[k % nbuf][:m], out_buf[k % nbuf][:m]
             t0 = time.perf_counter()
+            call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(range(c0, c0 + m), (OH, OW)))
             if direct:
-                styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size, **scale_kw)
+                styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size, **call_kw)
             else:
-                styled = model.transfer_frames(src, out=dst, in_format=in_fmt, size=size, **scale_kw)
+                styled = model.transfer_frames(src, out=dst, in_format=in_fmt, size=size, **call_kw)
             gpu_s += time.perf_counter() - t0
             if direct:
                 busy[k % nbuf] = [vpool.submit(append_frames, [(fr, (OH, OW)) for fr in styled])]
@@ -904,6 +913,69 @@ def _self_launch(n_ranks, argv):
     return rc
 
 
+def fade_strengths(n, strength=1.0, fade=0):
+    """--strength S --fade N for a video of n frames: frame i gets S * min(1, i / N, (n - 1 - i) / N), a linear ramp from 0 at the first frame
+    to S at frame N and back to 0 at the last one (N = 0: S for every frame).  Indexed by the absolute frame number, so the shards of a
+    --gpus run agree.  A list of n floats."""
+    s, fade = float(strength), int(fade)
+    if not 0.0 <= s <= 1.0:
+        raise ValueError("--strength lies in 0..1")
+    if fade < 0:
+        raise ValueError("--fade is a number of frames, 0 or more")
+    return [s * min(1.0, i / fade, (n - 1 - i) / fade) if fade else s for i in range(n)]
+
+
+def list_mattes(path, n):
+    """--matte PATH for n frames: one grey image for every frame (a file), or a directory with one image per frame, taken in sorted order.
+    Returns the n paths; ValueError when the directory does not hold exactly n files."""
+    if os.path.isdir(path):
+        files = sorted(os.path.join(path, f) for f in os.listdir(path) if os.path.isfile(os.path.join(path, f)))
+        if len(files) != n:
+            raise ValueError("--matte %s holds %d images for %d frames: one per frame" % (path, len(files), n))
+        return files
+    if not os.path.isfile(path):
+        raise ValueError("--matte %s does not exist" % path)
+    return [path] * n
+
+
+def read_matte(path, size):
+    """a matte image as uint8 [H][W] grey (any mode, through Pillow); ValueError unless it has the delivered size (H, W)"""
+    with _pil().open(path) as im:
+        m = np.asarray(im.convert("L"), np.uint8)
+    if m.shape != tuple(size):
+        raise ValueError("matte %s is %dx%d, the delivered frame %dx%d" % (path, m.shape[1], m.shape[0], size[1], size[0]))
+    return m
+
+
+class Compositing():
+    """--strength / --fade / --matte / --keep of a run over n frames: kw(idx, size) gives the strength=, matte=, keep= keywords of
+    transfer_frames for the frames with the absolute numbers idx, delivered at size (H, W).  One matte file is read once and shared."""
+
+    def __init__(self, n, strength=None, fade=0, matte=None, keep=None):
+        if keep not in (None, "colour", "color", "luma"):
+            raise ValueError("--keep is colour or luma")
+        self.keep = keep
+        self.strengths = None if strength is None and not fade else fade_strengths(n, 1.0 if strength is None else strength, fade)
+        self.mattes = None if matte is None else list_mattes(matte, n)
+        self.shared = matte is not None and not os.path.isdir(matte)
+        self._one = None
+
+    def kw(self, idx, size):
+        kw = {}
+        if self.strengths is not None:
+            kw["strength"] = [self.strengths[i] for i in idx]
+        if self.mattes is not None:
+            if self.shared:
+                if self._one is None or self._one.shape[1:] != tuple(size):
+                    self._one = read_matte(self.mattes[0], size)[None]
+                kw["matte"] = self._one
+            else:
+                kw["matte"] = np.stack([read_matte(self.mattes[i], size) for i in idx])
+        if self.keep is not None:
+            kw["keep"] = self.keep
+        return kw
+
+
 def parse_out_size(text):
     """--out-size: "source", or WIDTHxHEIGHT as (H, W); ValueError for anything else"""
     if text.lower() == "source":
@@ -970,7 +1042,26 @@ def main(argv=None, model_factory=None):
                     "the edges of the frame read instead of bilinearly (fast guided filter, the source's luma as the guide): box radius R in working pixels "
                     "(1..16, default 4) and regulariser EPS in the units of a 0..1 image (default 1e-3; smaller keeps more of the source's edges).  "
                     "video.guided_upsample states the arithmetic in numpy")
+    ap.add_argument("--strength", type=float, default=None, metavar="S", help="how much of the stylized frame shows, 0..1: the result is mixed with the frame "
+                    "read on the GPU, (1 - S) source + S stylized (video.composite states the arithmetic in numpy)")
+    ap.add_argument("--fade", type=int, default=0, metavar="N", help="ramp the strength linearly from 0 to S over the first N frames and back over the last N "
+                    "(S: --strength, default 1)")
+    ap.add_argument("--matte", default=None, metavar="PATH", help="where the style applies: a grey image of the delivered size for every frame (white: stylized, "
+                    "black: the frame read), or a directory with one such image per frame, in sorted order")
+    ap.add_argument("--keep", choices=("colour", "color", "luma"), default=None, help="colour: the frame read keeps its colours and takes the stylized "
+                    "luminance; luma: it keeps its luminance and takes the stylized colours")
     args = ap.parse_args(argv)
+    composite = None
+    if args.strength is not None or args.fade or args.matte is not None or args.keep is not None:
+        if len(args.style) > 1:
+            ap.error("--strength / --fade / --matte / --keep with multi-style interpolation are not supported: blended compositing is not offered")
+        if args.strength is not None and not 0.0 <= args.strength <= 1.0:      # (NaN fails both comparisons)
+            ap.error("--strength lies in 0..1")
+        if args.fade < 0:
+            ap.error("--fade is a number of frames, 0 or more")
+        if args.matte is not None and not os.path.exists(args.matte):
+            ap.error("--matte %s does not exist" % args.matte)
+        composite = dict(strength=args.strength, fade=args.fade, matte=args.matte, keep=args.keep)
     out_size = None
     if args.out_size is not None:
         try:
@@ -1058,7 +1149,7 @@ def main(argv=None, model_factory=None):
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
                     write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma,
-                    work_size=work_size, out_size=out_size, guided=guided)
+                    work_size=work_size, out_size=out_size, guided=guided, composite=composite)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
@@ -1066,7 +1157,7 @@ def main(argv=None, model_factory=None):
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
                       write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
-                      out_size=out_size, guided=guided)
+                      out_size=out_size, guided=guided, composite=composite)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

@@ -581,6 +581,73 @@ def _no_styles_with_out_size(style_weights, style_masks):
         raise ValueError("out_size does not combine with style_weights / style_masks yet: deliver the blended frames with deliver_tensor")
 
 
+# ===== compositing (the rrv_*composite* entries; include/rerevst_hip.h "Compositing" states the arithmetic) =====
+KEEP_NAMES = {None: _lib.KEEP_NONE, "colour": _lib.KEEP_COLOUR, "color": _lib.KEEP_COLOUR, "luma": _lib.KEEP_LUMA}
+
+
+class CompositeArgs():
+    """strength= / matte= / keep= of a call of B frames delivered at H x W, checked: `strength` a float32 [B] array, `matte` None, a
+    C-contiguous ndarray or (tensors) a contiguous torch tensor on the device, [frames][H][W] float32 or uint8 with frames 1 or B, `keep`
+    an RRV_KEEP_* value.  request(b0, nb) is the rrv_composite of frames b0 .. b0 + nb - 1."""
+
+    def __init__(self, strength, matte, keep, B, H, W, tensors=False, device=None):
+        if keep not in KEEP_NAMES:
+            raise ValueError("keep must be None, 'colour' ('color') or 'luma', got %r" % (keep,))
+        self.keep = KEEP_NAMES[keep]
+        try:
+            st = np.ones(B, np.float32) if strength is None else np.ascontiguousarray(np.broadcast_to(np.asarray(strength, np.float32).reshape(-1), (B,)))
+        except ValueError:
+            raise ValueError("strength must be one number or a sequence of %d, one per frame" % B) from None
+        if not bool(np.all((st >= 0) & (st <= 1))):
+            raise ValueError("strength must lie in 0..1 for every frame, got %r" % (strength,))
+        self.strength, self.matte, self.frames, self.dtype, self.step = st, None, 0, _lib.DT_F32, 0
+        if matte is None:
+            return
+        is_tensor = tensors and not isinstance(matte, np.ndarray)
+        if is_tensor:
+            import torch
+            if not isinstance(matte, torch.Tensor):
+                raise ValueError("matte must be a torch tensor on the handle's device or an ndarray, float32 or uint8")
+            _on_device(matte, "matte", device)
+            kinds = {torch.float32: _lib.DT_F32, torch.uint8: _lib.DT_U8}
+        else:
+            matte = np.asarray(matte)
+            kinds = {np.dtype(np.float32): _lib.DT_F32, np.dtype(np.uint8): _lib.DT_U8}
+        if matte.dtype not in kinds:
+            raise ValueError("matte must be float32 or uint8, got %s" % (matte.dtype,))
+        shape = tuple(matte.shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[0] not in (1, B) or shape[1:] != (H, W):
+            raise ValueError("matte has shape %s, expected [%d or 1][%d][%d]: the delivered size" % (tuple(matte.shape), B, H, W))
+        self.dtype, self.frames = kinds[matte.dtype], shape[0]
+        self.matte = matte.reshape(shape).contiguous() if is_tensor else np.ascontiguousarray(matte.reshape(shape))
+        self.step = H * W * (1 if self.dtype == _lib.DT_U8 else 4)
+
+    def on_device(self, like):
+        """the matte in HBM for the device entries: a host array is copied there on the current stream"""
+        if self.matte is not None and isinstance(self.matte, np.ndarray):
+            import torch
+            self.matte = torch.from_numpy(self.matte).to(like.device, non_blocking=False)
+        return self
+
+    def request(self, b0, nb):
+        ptr = None
+        if self.matte is not None:
+            base = self.matte.ctypes.data if isinstance(self.matte, np.ndarray) else self.matte.data_ptr()
+            ptr = base + (0 if self.frames == 1 else b0 * self.step)
+        return _lib.Composite(self.strength[b0:].ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(ptr), self.dtype, 1 if self.frames == 1 else nb, self.keep)
+
+
+def _composite_args(strength, matte, keep, style_weights, style_masks, B, H, W, tensors=False, device=None):
+    """None when no compositing keyword is given (the call is then what it was), else the checked CompositeArgs"""
+    if strength is None and matte is None and keep is None:
+        return None
+    if style_weights is not None or style_masks is not None:
+        raise ValueError("strength / matte / keep do not combine with style_weights / style_masks: blended and masked compositing are not offered")
+    return CompositeArgs(strength, matte, keep, B, H, W, tensors, device)
+
+
 def _host_in_desc(in_format):
     """rrv_image_desc of host frames as the scaled host entries take them: uint8 BGR HWC, or a YUV format by name"""
     if in_format == "bgr":
@@ -1014,7 +1081,7 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None,
-                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
+                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
         size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
@@ -1037,7 +1104,9 @@ class Stylization():
         if work_size is not None:
             (SH, SW), (H, W) = (H, W), _work_size(work_size)
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
-        out, u8 = _output((B, *((DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)), 3), dtype, out, out_format)
+        Ho, Wo = (DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)
+        comp = _composite_args(strength, matte, keep, style_weights, style_masks, B, Ho, Wo)
+        out, u8 = _output((B, Ho, Wo, 3), dtype, out, out_format)
         self._yuv_depth(in_format, out_format)
         desc = _lib.ImageDesc(_lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32,
                               YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
@@ -1052,7 +1121,12 @@ class Stylization():
         # what blends the styles (_HOST_ENTRIES), and the plain BGR entry also names the model and the geometry.
         src, dst, flags = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), self._flags(pad_crop)
         name = _HOST_ENTRIES[yuv_in, yuv_out][blend].format(model="" if self.use_Global else "_frame_mode", geometry="_frames" if pad_crop else "_batch")
-        if guide is not None:
+        if comp is not None:      # (r = 0: bilinear delivery; DH = DW = 0: the working frame is delivered)
+            r, eps = _guide_args(guide, guide_radius, guide_eps, out_size) if guide is not None else (0, 0.0)
+            req = comp.request(0, B)
+            name, args = "rrv_transfer_composite", (src, _host_in_desc(in_format), B, SH, SW, H, W, *((DH, DW) if out_size is not None else (0, 0)), r, eps,
+                                                    C.byref(req), dst, desc, flags)
+        elif guide is not None:
             r, eps = _guide_args(guide, guide_radius, guide_eps, out_size)
             name, args = "rrv_transfer_guided", (src, _host_in_desc(in_format), B, SH, SW, H, W, DH, DW, r, eps, dst, desc, flags)
         elif out_size is not None:
@@ -1070,7 +1144,7 @@ class Stylization():
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                       work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
+                       work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -1107,12 +1181,18 @@ class Stylization():
         The stylized working frame is upsampled along the edges of the source's luma with the fast guided filter instead of bilinearly:
         guide_radius is the box radius in working pixels (1..16), guide_eps the regulariser in the units of a 0..1 image (smaller keeps
         more of the source's edges, larger tends to the bilinear picture).  The working size must be delivered whole: H and W of the
-        working frame multiples of 8 (transfer_frames: any).  video.guided_upsample restates the arithmetic in numpy."""
+        working frame multiples of 8 (transfer_frames: any).  video.guided_upsample restates the arithmetic in numpy.
+        strength / matte / keep: compositing with the frames as passed (rrv_transfer_composite; include/rerevst_hip.h "Compositing"), on
+        the GPU, behind the delivery or guided stage and in front of out_format / dtype.  strength: one number in 0..1 or one per frame, how
+        much of the stylized frame shows; matte: a float32 (0..1) or uint8 (0..255) array [B or 1][Ho][Wo] at the delivered size, where it
+        shows; keep: "colour" ("color") keeps the source's colours and takes the stylized luminance, "luma" the reverse.  They combine with
+        work_size, out_size, guide, in_format, out_format and dtype; the working size must be delivered whole as for guide=.  Not with
+        style_weights / style_masks (ValueError).  video.composite restates the arithmetic in numpy."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps)
+                                 guide_radius, guide_eps, strength, matte, keep)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3):
+                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -1128,9 +1208,10 @@ class Stylization():
         work_size=(H, W): as in transfer_batch; the resampled H x W frame is what gets reflect-padded and cropped, and [B][H][W][3]
         (or the YUV frames of that size) is what comes back.
         out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW.
-        guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size."""
+        guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size.
+        strength / matte / keep: compositing with the frames as passed, as in transfer_batch; any working size."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps)
+                                 guide_radius, guide_eps, strength, matte, keep)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -1139,7 +1220,7 @@ class Stylization():
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
                         pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None, guide=None,
-                        guide_radius=4, guide_eps=1e-3):
+                        guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -1180,8 +1261,13 @@ class Stylization():
         output is then the normalised delivered pixel (a resampled frame has no pre-clamp value).  Not with style_weights / style_masks.
         guide="source" with out_size="source" (or that size): guided delivery (rrv_transfer_guided_view_device; include/rerevst_hip.h "Guided
         delivery"), guide_radius in working pixels (1..16) and guide_eps in the units of a 0..1 image as in transfer_batch.  The call equals
-        the float32 "nhwc" call at the working size, resample_tensor for the two guides and deliver_tensor(.., guide_lo=, guide_hi=)."""
+        the float32 "nhwc" call at the working size, resample_tensor for the two guides and deliver_tensor(.., guide_lo=, guide_hi=).
+        strength / matte / keep: compositing with x itself (rrv_transfer_composite_view_device; include/rerevst_hip.h "Compositing"), as in
+        transfer_batch; matte a float32 or uint8 tensor [B or 1, Ho, Wo] on the handle's device, read in the order of the current stream
+        like style_masks (an ndarray is copied there).  The call equals the float32 "nhwc" call with the same work_size / out_size / guide,
+        resample_tensor for the source at the delivered size and composite_tensor."""
         import torch
+        composite = strength is not None or matte is not None or keep is not None
         if guide is not None:
             g_r, g_eps = _guide_args(guide, guide_radius, guide_eps, out_size)
         if out_size is not None:
@@ -1189,7 +1275,7 @@ class Stylization():
         elif work_size is not None:
             _no_styles_with_work_size(style_weights, style_masks)
         work = None if work_size is None else _work_size(work_size)
-        scaled = work is not None or out_size is not None
+        scaled = work is not None or out_size is not None or composite      # (the view entries serve every compositing call)
         xv, ov = (t if isinstance(t, ImageView) else None for t in (x, out))
         # An unscaled call refuses in tensor_io_args' order and words (tests/call_record.json pins which refusal a call meets): the space
         # of a YUV surface first, and for a tensor x the names of both sides before x is looked at.
@@ -1208,7 +1294,10 @@ class Stylization():
         Ho, Wo = (DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)
         if not scaled and xv is None and ov is not None:      # (.. and the dtype of an output view for a tensor x, before the view is looked at)
             _tensor_out_args(self.device, B, Ho, Wo, src.batched, out_space, ov.storage.dtype, ov.layout if out_layout is None else out_layout, True, None)
+        comp = _composite_args(strength, matte, keep, style_weights, style_masks, B, Ho, Wo, tensors=True, device=self.device)
         dst = self._target(out, out_layout, out_space, out_dtype, B, Ho, Wo, src.batched, src.tensor, default_layout=src.layout)
+        if comp is not None:
+            comp.on_device(src.tensor)
         # The view entries serve a call with a strided side and every scaled call (a packed side then goes as its contiguous view), the
         # descriptor entries every other: by (input is YUV), the _from_yuv_device entries taking the layout alone.
         if scaled or src.view is not None or dst.view is not None:
@@ -1229,7 +1318,12 @@ class Stylization():
         self._yuv_depth(src.layout, dst.layout)
         stream = self._stream(src.tensor)
         for b0, nb, p, q in _chunks(B, (src.ptr, src.step), (dst.ptr, dst.step)):
-            if guide is not None:
+            if comp is not None:
+                req = comp.request(b0, nb)
+                self._chk(self._lib.rrv_transfer_composite_view_device(self._h, p, in_arg, nb, SH, SW, H, W, *((DH, DW) if out_size is not None else (0, 0)),
+                                                                       g_r if guide is not None else 0, g_eps if guide is not None else 0.0, C.byref(req),
+                                                                       q, out_arg, flags, stream))
+            elif guide is not None:
                 self._chk(self._lib.rrv_transfer_guided_view_device(self._h, p, in_arg, nb, SH, SW, H, W, DH, DW, g_r, g_eps, q, out_arg, flags, stream))
             elif out_size is not None:
                 self._chk(self._lib.rrv_transfer_deliver_view_device(self._h, p, in_arg, nb, SH, SW, H, W, DH, DW, q, out_arg, flags, stream))
@@ -1278,6 +1372,31 @@ class Stylization():
             return dst.result
         for _, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (dst.ptr, dst.step)):
             self._chk(self._lib.rrv_deliver_view_device(self._h, p, nb, H, W, DH, DW, q, C.byref(vo), stream))
+        return dst.result
+
+    def composite_tensor(self, stylized, source, *, strength=None, matte=None, keep=None, out_space="pixel", out_dtype=None, out_layout=None, out=None):
+        """The compositing stage alone (rrv_composite_view_device; include/rerevst_hip.h "Compositing"): stylized and source float32 tensors
+        [B,H,W,3] ([H,W,3]) on the handle's GPU, BGR, "pixel" space, of one size -- what transfer_tensor(.., layout="nhwc") and
+        resample_tensor return -- mixed by strength (a number or one per frame, 0..1), matte (float32 or uint8 [B or 1, H, W], a tensor on
+        the device or an ndarray) and keep (None, "colour" / "color", "luma") and written as deliver_tensor writes a frame of that size:
+        out_layout ("nhwc" by default, "nchw", or a YUV format name), out_space, out_dtype, or `out`.  Ordered on the current stream.  The
+        tensors need no alignment beyond their elements'.  video.composite restates the arithmetic in numpy."""
+        import torch
+        if not isinstance(stylized, torch.Tensor) or stylized.dtype != torch.float32 or stylized.dim() not in (3, 4) or stylized.shape[-1] != 3:
+            raise ValueError("stylized must be a float32 tensor [B,H,W,3] or [H,W,3] (BGR, 'pixel' space)")
+        _on_device(stylized, "stylized", self.device)
+        batched = stylized.dim() == 4
+        yb = (stylized if batched else stylized.unsqueeze(0)).contiguous()
+        B, H, W = yb.shape[:3]
+        sb = self._guide_tensor(source, "source", (B, H, W, 3), batched)
+        comp = CompositeArgs(strength, matte, keep, B, H, W, tensors=True, device=self.device).on_device(yb)
+        dst = self._target(out, out_layout, out_space, out_dtype, B, H, W, batched, stylized, default_layout="nhwc")
+        vo = _whole_view(dst, H, W)
+        self._yuv_depth(None, dst.layout)
+        stream = self._stream(stylized)
+        for b0, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (dst.ptr, dst.step)):
+            req = comp.request(b0, nb)
+            self._chk(self._lib.rrv_composite_view_device(self._h, p, C.c_void_p(sb[b0].data_ptr()), nb, H, W, C.byref(req), q, C.byref(vo), stream))
         return dst.result
 
     def _guide_tensor(self, g, name, shape, batched):

@@ -129,6 +129,47 @@ def guided_upsample(stylized, source_lo, source_hi, radius=4, eps=1e-3):
     return up(box_mean(a)) * luma(hi)[..., None] + up(box_mean(b))
 
 
+def composite(stylized, source, strength=None, matte=None, keep=None):
+    """What compositing computes (transfer_frames(.., strength=, matte=, keep=); include/rerevst_hip.h "Compositing"), restated in numpy
+    with every operation on float32 arrays, so the GPU result equals it bit for bit.  stylized and source: [B][H][W][3] or [H][W][3], BGR
+    in 0..255, of one size.  strength: None (1), a number or one per frame, in 0..1.  matte: None, or [B or 1][H][W] ([H][W]) float32 in
+    0..1 or uint8 in 0..255.  keep: None, "colour" / "color" (the source's colours, the stylized luminance) or "luma" (the reverse).
+    Returns float32 of the inputs' shape, not clamped."""
+    P, S = np.asarray(stylized, np.float32), np.asarray(source, np.float32)
+    if P.shape != S.shape or P.ndim not in (3, 4) or P.shape[-1] != 3:
+        raise ValueError("composite: stylized and source are [B][H][W][3] or [H][W][3] arrays of one shape")
+    if keep not in (None, "colour", "color", "luma"):
+        raise ValueError("composite: keep must be None, 'colour' ('color') or 'luma', got %r" % (keep,))
+    batched = P.ndim == 4
+    if not batched:
+        P, S = P[None], S[None]
+    B, H, W = P.shape[:3]
+    f = np.float32
+    alpha = np.broadcast_to(np.asarray(1.0 if strength is None else strength, f).reshape(-1), (B,)).reshape(B, 1, 1)
+    if not np.all((alpha >= 0) & (alpha <= 1)):
+        raise ValueError("composite: strength must lie in 0..1")
+    if matte is not None:
+        m = np.asarray(matte)
+        m = m[None] if m.ndim == 2 else m
+        if m.dtype not in (np.float32, np.uint8) or m.ndim != 3 or m.shape[0] not in (1, B) or m.shape[1:] != (H, W):
+            raise ValueError("composite: matte is float32 or uint8 [B or 1][H][W] at the frames' size")
+        alpha = alpha * (m if m.dtype == np.float32 else m.astype(f) / f(255.0))
+
+    def luma(v):
+        return (f(0.114) * v[..., 0] + f(0.587) * v[..., 1]) + f(0.299) * v[..., 2]
+
+    if keep is None:
+        C = P
+    elif keep == "luma":
+        C = P + (luma(S) - luma(P))[..., None]
+    else:
+        C = S + (luma(P) - luma(S))[..., None]
+    alpha = np.broadcast_to(alpha, (B, H, W))[..., None].astype(f)
+    out = (f(1.0) - alpha) * S + alpha * C
+    assert out.dtype == np.float32
+    return out if batched else out[0]
+
+
 # ===== the YUV formats by name: the one table framework.py and the drivers read =====
 # layout: RRV_LAY_* of include/rerevst_hip.h; bits: the code depth; dtype: of a sample (uint16 above 8 bits); planar: [Y][Cb][Cr], else [Y][CbCr];
 # chroma: "420" (a chroma sample per 2 x 2 block), "422" (per horizontal pixel pair) or "444" (per pixel).
