@@ -803,6 +803,77 @@ int rrv_transfer_composite(rrv_handle h, const void* frames, rrv_image_desc in, 
                            int DH, int DW, int r, float eps, const rrv_composite* c, void* out, rrv_image_desc out_desc, int flags);
 int rrv_composite_grid(int B, int DH, int DW, unsigned* grid, int* pixels_per_pass);
 
+/* JPEG output: float32 frames encoded as baseline JPEG on the GPU, one stream per frame, so that a compressed frame is what leaves HBM.
+ * Input, per frame, float32 HWC BGR PIXEL values v of H x W, contiguous: what the float32 forms of the other stages deliver.
+ * Parameters travel with the call in an rrv_jpeg, never in the handle: quality 1..100; chroma 420, 422 or 444; restart, the MCUs per restart
+ * interval, 1..65535, or 0 for the library's choice, one MCU row per interval (rrv_jpeg_plan reports the interval actually used).
+ * Samples.  Per component the 8-bit code the YUV output forms define, with the BT.601 full-range matrix (rrv_yuv_matrix's values for
+ * RRV_YUV_BT601, full_range = 1) whatever matrix the handle holds: c_k, the chroma box mean of the unrounded c_1 / c_2, the clamp and rint half
+ * to even of "Output size".  The planes coded are therefore, bit for bit, the I420 / I422 / I444 frame the delivery stage writes for the same
+ * frames with that matrix set.  Rows and columns beyond a plane, up to the next whole MCU (16 x 16, 16 x 8 or 8 x 8 pixels), repeat the
+ * plane's last sample.
+ * Transform and quantisation.  Sample - 128; the 8 x 8 DCT-II with JPEG's normalisation, F(u,v) = C(u) C(v) / 4 sum_xy f(x,y) cos((2x+1) u pi/16)
+ * cos((2y+1) v pi/16), C(0) = 1/sqrt 2, in float32; the Annex K tables scaled the IJG way (s = 5000 / quality below 50, else 200 - 2 quality;
+ * (base s + 50) / 100 in integers, clamped to 1..255); coefficient = rint(F / Q).  The contract is the rounding of the exact quotient: a value
+ * within float32 error of a rounding boundary may go either way.
+ * Coefficient blocks: int16 [B][blocks][64], a block's 64 values in zigzag order, the blocks of a frame in scan order: MCUs row by row, in an
+ * MCU Y's blocks row by row, then Cb, then Cr.
+ * Stream.  One baseline sequential frame: SOI, APP0 (JFIF 1.01, no density), two DQT (luma 0, chroma 1), SOF0 (8 bits, three components, Y
+ * sampled 2x2 / 2x1 / 1x1, chroma 1x1), four DHT with the Annex K tables (DC 0, AC 0, DC 1, AC 1), DRI, one interleaved SOS, the
+ * entropy-coded intervals, EOI.  An interval is padded with 1-bits to a byte and followed by RST0..7 in rotation, except the last; DC prediction
+ * restarts at every interval; every 0xFF data byte is followed by 0x00.  The bytes are a function of the coefficient blocks and the three
+ * parameters only.  A DC coefficient outside -1024..1023 or an AC one outside -1023..1023 (the first half produces none) is coded as the
+ * nearest end of its range.
+ * Where it is written.  Frame b goes to d_out + b * cap and its byte count to d_sizes[b].  Nothing is ever written at or beyond cap bytes of a
+ * slot.  A frame that does not fit gets d_sizes[b] = -(the bytes it needs), its slot's content is unspecified, the other frames are unaffected
+ * and the call still returns RRV_OK: the sizes are device results.
+ *   rrv_jpeg_tables          the two quantisation tables of a quality, natural order; no handle, no GPU
+ *   rrv_jpeg_bound           a capacity no frame of H x W can exceed: every block at its longest code with every byte stuffed; no handle, no GPU
+ *   rrv_jpeg_plan            MCU columns and rows, the interval used, blocks per frame and header bytes; no handle, no GPU
+ *   rrv_jpeg_blocks_device   the first half alone: B (1..64) contiguous frames d_in -> d_coef (16-byte aligned), queued on hip_stream (NULL: the
+ *                            null stream); nothing of the handle's own streams takes part
+ *   rrv_jpeg_entropy_device  the second half alone: coefficient blocks -> streams and sizes, queued the same way.  Interval lengths and offsets
+ *                            live in a buffer of the handle (8 bytes per interval and frame, grow-only): calls on different streams must be
+ *                            ordered by the caller
+ *   rrv_jpeg_encode_device   both halves, the blocks in a buffer of the handle (128 bytes per block, grow-only); equals the two calls above bit
+ *                            for bit
+ *   rrv_transfer_jpeg_view_device
+ *                            rrv_transfer_composite_view_device with JPEG as the output form: its arguments up to the request c (NULL: none), then
+ *                            the rrv_jpeg, the slots d_out, cap and d_sizes in place of the output buffer and view.  Every combination of SH x SW,
+ *                            DH x DW, guide (r, eps) and compositing that entry accepts; the frame encoded is the float32 HWC BGR PIXEL frame it
+ *                            would deliver, which stays in the workspace slot.  GLOBAL or (RRV_TF_FRAME_MODE) FRAME model
+ *   rrv_transfer_jpeg        the host twin, any B: host frames (uint8 HWC BGR or a YUV layout, as rrv_transfer_composite takes them), host `out`
+ *                            and host `sizes`, a host matte.  Sub-batches alternate over two compute slots and two staging sets: a
+ *                            sub-batch's sizes are read back, then sizes[b] bytes of every frame that fitted are copied, so only those bytes
+ *                            cross PCIe, while the GPU runs the next sub-batch
+ * A transfer with JPEG output equals, bit for bit in a fixed kernel mode, the float32 HWC BGR PIXEL call with the same sizes, guide and request
+ * followed by rrv_jpeg_encode_device; a frame's bytes do not depend on B or on its position in the call.
+ * Checks, all before any GPU work: the batch, the sizes (1..65535, and rrv_jpeg_bound below 2^31), quality, chroma, restart, cap (at least the
+ * header and EOI), null or misaligned buffers, and for the transfer entries those of the entry without JPEG; RRV_E_ARG names the field and the
+ * handle stays usable.  Scratch (128 bytes per block for the coefficients, 8 per interval) is grow-only, per workspace slot for the transfer
+ * entries and in the handle for the stage alone, and reserved with the other stage buffers before the call's first launch: out of memory is
+ * RRV_E_NOMEM and the handle stays usable.  Results do not depend on what the scratch held before.  These buffers are plain allocations: the
+ * guard bands of rrv_set_debug do not cover them.
+ * Not offered: blended and masked models, tickets and the one-frame entries. */
+typedef struct rrv_jpeg {
+    int quality;             /* 1..100 */
+    int chroma;              /* 420, 422 or 444 */
+    int restart;             /* MCUs per restart interval, 1..65535; 0: one MCU row */
+} rrv_jpeg;
+int rrv_jpeg_tables(int quality, uint16_t luma[64], uint16_t chroma[64]);
+int rrv_jpeg_bound(int H, int W, int chroma, int restart, size_t* bytes);
+int rrv_jpeg_plan(int H, int W, int chroma, int restart, int* mcu_cols, int* mcu_rows, int* interval, int* blocks, int* header_bytes);
+int rrv_jpeg_blocks_device(rrv_handle h, const float* d_in, int B, int H, int W, const rrv_jpeg* p, int16_t* d_coef, void* hip_stream);
+int rrv_jpeg_entropy_device(rrv_handle h, const int16_t* d_coef, int B, int H, int W, const rrv_jpeg* p, uint8_t* d_out, size_t cap,
+                            int* d_sizes, void* hip_stream);
+int rrv_jpeg_encode_device(rrv_handle h, const float* d_in, int B, int H, int W, const rrv_jpeg* p, uint8_t* d_out, size_t cap,
+                           int* d_sizes, void* hip_stream);
+int rrv_transfer_jpeg_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W,
+                                  int DH, int DW, int r, float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* d_out, size_t cap,
+                                  int* d_sizes, int flags, void* hip_stream);
+int rrv_transfer_jpeg(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, int r,
+                      float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* out, size_t cap, int* sizes, int flags);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
 # reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
-# needs a copy of it there (and of librerevst_compose.so).
+# needs a copy of it there (and of librerevst_compose.so and librerevst_jpeg.so).
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -31,6 +31,11 @@ class ImageView(C.Structure):
 class Composite(C.Structure):
     """rrv_composite: a compositing request (per-frame strengths in host memory, the matte, what the source keeps)."""
     _fields_ = [("strength", C.POINTER(C.c_float)), ("matte", C.c_void_p), ("matte_dtype", C.c_int), ("matte_frames", C.c_int), ("keep", C.c_int)]
+
+
+class Jpeg(C.Structure):
+    """rrv_jpeg: the parameters of a JPEG encode (quality 1..100; chroma 420, 422 or 444; MCUs per restart interval, 0 = one MCU row)."""
+    _fields_ = [("quality", C.c_int), ("chroma", C.c_int), ("restart", C.c_int)]
 
 
 DT_U8, DT_F32 = 0, 1
@@ -176,6 +181,18 @@ SYMBOLS = {
     "rrv_transfer_composite": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                          C.POINTER(Composite), C.c_void_p, ImageDesc, C.c_int]),
     "rrv_composite_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_int)]),      # no handle: (B, DH, DW, grid, pixels per pass)
+    # JPEG output: tables, bound and plan need no handle; (h, in, B, H, W, Jpeg* p, out[, cap, sizes], hip_stream)
+    "rrv_jpeg_tables": (C.c_int, [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
+    "rrv_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rrv_jpeg_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),      # (H, W, chroma, restart, MCU columns, MCU rows, interval, blocks, header bytes)
+    "rrv_jpeg_blocks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Jpeg), C.c_void_p, C.c_void_p]),
+    "rrv_jpeg_entropy_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rrv_jpeg_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    # (h, in, ImageView* / ImageDesc in, B, SH, SW, H, W, DH, DW, r, eps, Composite* c, Jpeg* p, out, cap, sizes, flags[, hip_stream])
+    "rrv_transfer_jpeg_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_float, C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "rrv_transfer_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                    C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

@@ -30,6 +30,7 @@
 #include "guided.h"        //                       of the guided delivery stage
 #include "compose.h"       //                       of the compositing stage (librerevst_compose.so)
 #include "deliver.h"       //                       of the output-side resampler
+#include "jpeg.h"          // librerevst_jpeg.so: plan, tables, header and the launch entries of the JPEG output stage
 
 namespace {
 
@@ -221,6 +222,9 @@ struct rrv_ctx {
         float* gd_xhi = nullptr; size_t gd_xhi_cap = 0;
         float* gd_ab = nullptr; size_t gd_ab_cap = 0;
         float* gd_q = nullptr; size_t gd_q_cap = 0;
+        // JPEG output (Xfer::jp): a launch group's coefficient blocks and its interval lengths and offsets ([2][frames][intervals]), grow-only
+        int16_t* jp_coef = nullptr; size_t jp_coef_cap = 0;
+        uint32_t* jp_idx = nullptr; size_t jp_idx_cap = 0;
         int set_images = 0;                          // images whose state sets the slot's last launch wrote (frame mode, grouped multi-style); 0: it kept no per-image state (rrv_debug_copy_state)
     } slots[RRV_MAX_SLOTS];
     int n_slots = 2, next_slot = 0;                  // the alternating device entries cycle over n_slots slots
@@ -282,6 +286,10 @@ struct rrv_ctx {
     float* gd_q = nullptr; size_t gd_q_cap = 0;
     // rrv_composite_view_device's own mixed frame (it runs on the caller's stream too)
     float* cm_buf = nullptr; size_t cm_cap = 0;
+    // the JPEG entries' own scratch (they run on the caller's stream too): rrv_jpeg_encode_device's coefficient blocks, and the interval
+    // lengths and offsets of the entropy half ([2][B][intervals]).  Grow-only; every word read was written by the same call
+    int16_t* jp_coef = nullptr; size_t jp_coef_cap = 0;
+    uint32_t* jp_idx = nullptr; size_t jp_idx_cap = 0;
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -1207,6 +1215,9 @@ struct Xfer {
     bool comp = false;
     const float* cstr = nullptr; const void* cmatte = nullptr;
     int cm_dt = RRV_DT_F32, cm_frames = 0, ckeep = RRV_KEEP_NONE;
+    // JPEG output (include/rerevst_hip.h "JPEG output"; set_jpeg): the delivered float32 frame is encoded where the delivery stage would
+    // write the output form.  d_out is then the slots (frame b at b * jp->cap bytes) and jp_sizes the B sizes, both in HBM.
+    const JpegP* jp = nullptr; int* jp_sizes = nullptr;
     // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
     bool on_stream = false; hipStream_t with = nullptr;
 
@@ -1217,7 +1228,7 @@ struct Xfer {
     int WW() const { return pad ? W : W / 8 * 8; }
     bool delivering() const { return (DH != 0 || DW != 0) && (DH != WH() || DW != WW()); }
     bool guided() const { return gr != 0; }
-    bool staged() const { return delivering() || guided() || comp; }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
+    bool staged() const { return delivering() || guided() || comp || jp; }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
     int OH() const { return delivering() ? DH : WH(); }       // the frame delivered
     int OW() const { return delivering() ? DW : WW(); }
     ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
@@ -2191,6 +2202,9 @@ int rrv_destroy(rrv_handle h) {
     for (rrv_ctx::Slot& sl : h->slots)
         for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
     for (float* q : {h->gd_ab, h->gd_q, h->cm_buf}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)h->jp_coef, (void*)h->jp_idx}) if (q) (void)hipFree(q);
+    for (rrv_ctx::Slot& sl : h->slots)
+        for (void* q : {(void*)sl.jp_coef, (void*)sl.jp_idx}) if (q) (void)hipFree(q);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
     if (h->stat_part) (void)hipFree(h->stat_part);
     for (float* q : {h->first_w[0], h->first_w[1], h->first_b[0], h->first_b[1], h->first_wg}) if (q) (void)hipFree(q);
@@ -3005,6 +3019,11 @@ static int reserve_stages(rrv_handle h, int slot, int frames, const Xfer& x) {
         }
         if (!x.guided() && x.delivering()) RCHK(ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * OH * OW * 3));
     }
+    if (x.jp) {      // the blocks and the interval index; the float32 frame at the delivered size where nothing else has made one
+        RCHK(ensure_dev(h, sl.jp_coef, sl.jp_coef_cap, (size_t)frames * x.jp->blocks * 64));
+        RCHK(ensure_dev(h, sl.jp_idx, sl.jp_idx_cap, 2 * (size_t)frames * x.jp->n_int));
+        if (!x.guided() && !x.comp && x.delivering()) RCHK(ensure_dev(h, sl.gd_q, sl.gd_q_cap, (size_t)frames * x.OH() * x.OW() * 3));
+    }
     if (!x.guided()) return RRV_OK;
     RCHK(ensure_dev(h, sl.gd_xhi, sl.gd_xhi_cap, (size_t)frames * x.DH * x.DW * 3));
     RCHK(ensure_dev(h, sl.gd_ab, sl.gd_ab_cap, (size_t)frames * H * W * 6));
@@ -3079,6 +3098,38 @@ static int composite_launch(rrv_handle h, const Seq& q, const float* P, const fl
     return RRV_OK;
 }
 
+// ---- JPEG output (include/rerevst_hip.h "JPEG output"): the delivered float32 frame encoded in place of the output form
+// The request and the sizes of a JPEG entry -> the kernels' parameters, judged before any GPU work.  entropy: the call writes streams (cap counts).
+static int set_jpeg(rrv_handle h, const char* who, const rrv_jpeg* j, int B, int H, int W, bool entropy, size_t cap, JpegP* p) {
+    const std::string w = std::string(who) + ": ";
+    if (!j) return fail(h, RRV_E_ARG, w + "null rrv_jpeg");
+    if (B < 1 || B > JP_B_MAX) return fail(h, RRV_E_ARG, w + "batch must be in 1..64");
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(h, RRV_E_ARG, w + "H, W must be in 1..65535");
+    if (j->quality < 1 || j->quality > 100) return fail(h, RRV_E_ARG, w + "quality must be in 1..100");
+    if (!jpeg_chroma_ok(j->chroma)) return fail(h, RRV_E_ARG, w + "chroma must be 420, 422 or 444");
+    if (j->restart < 0 || j->restart > 65535) return fail(h, RRV_E_ARG, w + "restart must be in 0..65535 (0: one MCU row per interval)");
+    if (!jpeg_fill(p, H, W, j->chroma, j->quality, j->restart)) return fail(h, RRV_E_ARG, w + "quality, chroma or restart out of range");
+    p->B = B; p->cap = cap;
+    if (entropy) {
+        if (jpeg_bound(*p) > (size_t)0x7fffffff) return fail(h, RRV_E_ARG, w + "the frame is too large: rrv_jpeg_bound must stay below 2^31 bytes");
+        if (cap < (size_t)p->header_len + 2) return fail(h, RRV_E_ARG, w + "cap must hold at least the header and EOI (rrv_jpeg_plan's header bytes + 2)");
+    }
+    return RRV_OK;
+}
+static int jpeg_blocks_launch(rrv_handle h, const Seq& q, const JpegP& p) {
+    int e = 0;
+    // for the profile log: 12 bytes per pixel read, the blocks written; the two 8-point passes at 29 operations each per 8 samples
+    RCHK(launch(h, q, "jpeg_blocks", 2.0 * 29.0 / 8.0 * 64.0 * p.blocks * p.B, (12.0 * p.H * p.W + 128.0 * p.blocks) * p.B, [&] { e = rrv_jpeg_blocks_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("jpeg_blocks: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+static int jpeg_entropy_launch(rrv_handle h, const Seq& q, const JpegP& p) {
+    int e = 0;
+    // for the profile log: the blocks read twice by each of the two passes; the bytes written are device results and not counted
+    RCHK(launch(h, q, "jpeg_entropy", 0.0, 4.0 * 128.0 * p.blocks * p.B, [&] { e = rrv_jpeg_entropy_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("jpeg_entropy: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
 // The alternating device entries: consecutive calls cycle over n_slots (stream, workspace) pairs so that the tail / store
 // burst of one batch's kernels overlaps the next batch's kernels (frames are independent).  Profiled launches stay on slot 0.
 static int next_device_slot(rrv_handle h) {
@@ -3228,6 +3279,19 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             const void* const matte = x.cmatte && x.cm_frames != 1 ? (const char*)x.cmatte + (size_t)b0 * x.matte_bytes() : x.cmatte;
             RCHK(composite_launch(h, q, P, S, cnt, OH, OW, x.cstr ? x.cstr + b0 : nullptr, matte, x.cm_dt, x.cm_frames == 1 ? 1 : cnt, x.ckeep, P));
         }
+        if (x.jp) {      // the encoder takes the place of the delivery into the output form; it reads the float32 frame at the delivered size
+            if (!guided && !x.comp && delivering) {
+                RCHK(deliver_launch(h, q, sl.dl_buf, cnt, PH, PW, OH, OW, sl.gd_q, OUT_F32, contiguous_view(VL_HWC, OH, OW)));
+                P = sl.gd_q;
+            }
+            JpegP p = *x.jp;
+            p.B = cnt; p.in = P; p.coef = sl.jp_coef;
+            p.out = (uint8_t*)d_out + (size_t)b0 * p.cap; p.sizes = x.jp_sizes + b0;
+            p.lens = sl.jp_idx; p.offs = sl.jp_idx + (size_t)cnt * p.n_int;
+            RCHK(jpeg_blocks_launch(h, q, p));
+            RCHK(jpeg_entropy_launch(h, q, p));
+            continue;
+        }
         RCHK(deliver_launch(h, q, P, cnt, PH, PW, OH, OW, dst, x.fmt, vo));
     }
     if (bracket) {
@@ -3316,7 +3380,7 @@ static int view_run(rrv_handle h, const char* who, const void* d_in, const rrv_i
     RCHK(check_xfer(h, x));
     std::string why;
     if (!view_check(*in, x.B, x.IH(), x.IW(), false, &why)) return fail(h, RRV_E_ARG, w + "in." + why);      // (a scaled request: the source frame)
-    if (!view_check(*out, x.B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);
+    if (!view_check(*out, x.B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);      // (the view's geometry alone: with x.jp, d_out holds byte slots, not this view's frames)
     x.vin = in; x.vout = out;
     if (hip_stream || (flags & RRV_TF_ON_STREAM)) { x.on_stream = true; x.with = (hipStream_t)hip_stream; }      // hip_stream orders this call only
     return run_xfer(h, next_slot(h, x), d_in, d_out, x);
@@ -3932,6 +3996,163 @@ int rrv_transfer_composite_view_device(rrv_handle h, const void* d_in, const rrv
     if (B < 1 || B > 64) return fail(h, RRV_E_ARG, "transfer_composite_view: batch must be in 1..64");      // (c->strength holds B values: judged before they are read)
     RCHK(set_composite(h, "transfer_composite_view", c, B, &x));
     return view_run(h, "transfer_composite_view", d_in, in, d_out, out, flags, hip_stream, x);
+}
+// ---- JPEG output (include/rerevst_hip.h "JPEG output")
+int rrv_jpeg_tables(int quality, uint16_t luma[64], uint16_t chroma[64]) {
+    if (!luma || !chroma || quality < 1 || quality > 100) return RRV_E_ARG;
+    jpeg_tables(quality, luma, chroma);
+    return RRV_OK;
+}
+int rrv_jpeg_bound(int H, int W, int chroma, int restart, size_t* bytes) {
+    JpegP p{};
+    if (!bytes || !jpeg_plan(H, W, chroma, restart, &p)) return RRV_E_ARG;
+    *bytes = jpeg_bound(p);
+    return RRV_OK;
+}
+int rrv_jpeg_plan(int H, int W, int chroma, int restart, int* mcu_cols, int* mcu_rows, int* interval, int* blocks, int* header_bytes) {
+    JpegP p{};
+    if (!mcu_cols || !mcu_rows || !interval || !blocks || !header_bytes || !jpeg_plan(H, W, chroma, restart, &p)) return RRV_E_ARG;
+    *mcu_cols = p.mcu_cols; *mcu_rows = p.mcu_rows; *interval = p.interval; *blocks = p.blocks; *header_bytes = p.header_len;
+    return RRV_OK;
+}
+// the halves alone and together, queued on hip_stream itself (NULL: the null stream): nothing of the handle's own streams takes part
+int rrv_jpeg_blocks_device(rrv_handle h, const float* d_in, int B, int H, int W, const rrv_jpeg* j, int16_t* d_coef, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegP p{};
+    RCHK(set_jpeg(h, "jpeg_blocks", j, B, H, W, false, 0, &p));
+    if (!d_in || !d_coef) return fail(h, RRV_E_ARG, "jpeg_blocks: null buffer");
+    if ((uintptr_t)d_coef & 15) return fail(h, RRV_E_ARG, "jpeg_blocks: d_coef must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->dev));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    p.in = d_in; p.coef = d_coef;
+    return jpeg_blocks_launch(h, q, p);
+}
+int rrv_jpeg_entropy_device(rrv_handle h, const int16_t* d_coef, int B, int H, int W, const rrv_jpeg* j, uint8_t* d_out, size_t cap, int* d_sizes, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegP p{};
+    RCHK(set_jpeg(h, "jpeg_entropy", j, B, H, W, true, cap, &p));
+    if (!d_coef || !d_out || !d_sizes) return fail(h, RRV_E_ARG, "jpeg_entropy: null buffer");
+    if ((uintptr_t)d_coef & 15) return fail(h, RRV_E_ARG, "jpeg_entropy: d_coef must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->dev));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    RCHK(ensure_dev(h, h->jp_idx, h->jp_idx_cap, 2 * (size_t)B * p.n_int));
+    p.coef = const_cast<int16_t*>(d_coef); p.out = d_out; p.sizes = d_sizes;
+    p.lens = h->jp_idx; p.offs = h->jp_idx + (size_t)B * p.n_int;
+    return jpeg_entropy_launch(h, q, p);
+}
+int rrv_jpeg_encode_device(rrv_handle h, const float* d_in, int B, int H, int W, const rrv_jpeg* j, uint8_t* d_out, size_t cap, int* d_sizes, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegP p{};
+    RCHK(set_jpeg(h, "jpeg_encode", j, B, H, W, true, cap, &p));
+    if (!d_in || !d_out || !d_sizes) return fail(h, RRV_E_ARG, "jpeg_encode: null buffer");
+    HIPCHK(hipSetDevice(h->dev));
+    // both scratch buffers before the first launch: out of memory leaves nothing queued
+    RCHK(ensure_dev(h, h->jp_coef, h->jp_coef_cap, (size_t)B * p.blocks * 64));
+    RCHK(ensure_dev(h, h->jp_idx, h->jp_idx_cap, 2 * (size_t)B * p.n_int));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    p.in = d_in; p.coef = h->jp_coef; p.out = d_out; p.sizes = d_sizes;
+    p.lens = h->jp_idx; p.offs = h->jp_idx + (size_t)B * p.n_int;
+    RCHK(jpeg_blocks_launch(h, q, p));
+    return jpeg_entropy_launch(h, q, p);
+}
+static bool parse_in_host(const rrv_image_desc& d, InFmt* in);
+// a transfer whose output form is JPEG: the request of rrv_transfer_composite_view_device with the encoder behind it
+static int jpeg_xfer(rrv_handle h, const char* who, int B, int SH, int SW, int H, int W, int DH, int DW, int r, float eps, const rrv_composite* c, int flags,
+                     const rrv_jpeg* j, size_t cap, int max_B, Xfer* x, JpegP* p) {
+    *x = Xfer{Model::GLOBAL, B, H, W};
+    x->SH = SH; x->SW = SW; x->DH = DH; x->DW = DW;
+    if (r) { x->gr = r; x->geps = eps; }
+    if (B < 1 || (max_B && B > max_B)) return fail(h, RRV_E_ARG, std::string(who) + (max_B ? ": batch must be in 1..64" : ": batch must be at least 1"));
+    RCHK(set_composite(h, who, c, B, x));
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM)) return fail(h, RRV_E_ARG, std::string(who) + ": unknown flags");
+    x->pad = (flags & RRV_TF_PAD_CROP) != 0;
+    RCHK(set_jpeg(h, who, j, 1, x->OH(), x->OW(), true, cap, p));      // (the delivered frame; the batch is judged above, and per launch group later)
+    x->jp = p;
+    return RRV_OK;
+}
+int rrv_transfer_jpeg_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int H, int W, int DH, int DW, int r,
+                                  float eps, const rrv_composite* c, const rrv_jpeg* j, uint8_t* d_out, size_t cap, int* d_sizes, int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    JpegP p{};
+    RCHK(jpeg_xfer(h, "transfer_jpeg_view", B, SH, SW, H, W, DH, DW, r, eps, c, flags, j, cap, 64, &x, &p));
+    if (!d_sizes) return fail(h, RRV_E_ARG, "transfer_jpeg_view: null buffer");
+    x.jp_sizes = d_sizes;
+    // The checks of the view entries run on a stand-in for the output view: the float32 frame the encoder reads, which lives in the slot.
+    // d_out is NOT a buffer of that view: it holds B slots of cap bytes, and run_xfer never addresses it through the view (Xfer::jp).  view_run
+    // judges an output view by its own geometry only; a check that relates d_out to the view has to skip a request with x.jp set.
+    const rrv_image_view vo = contiguous_of(rrv_image_desc{RRV_DT_F32, RRV_LAY_HWC_BGR, RRV_SP_PIXEL}, x.OH(), x.OW());
+    return view_run(h, "transfer_jpeg_view", d_in, in, d_out, &vo, flags, hip_stream, x);
+}
+// The host twin.  Sub-batch k runs on compute slot k & 1 with staging set k & 1: frames up, the request, the sizes to the host.  Once sub-batch
+// k + 1 is queued the host waits for k, reads its sizes and copies sizes[b] bytes of every frame that fitted, while the GPU runs k + 1.
+int rrv_transfer_jpeg(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, int r, float eps,
+                      const rrv_composite* c, const rrv_jpeg* j, uint8_t* out, size_t cap, int* sizes, int flags) {
+    if (!h) return RRV_E_ARG;
+    Xfer x{Model::GLOBAL, B, H, W};
+    JpegP p{};
+    RCHK(jpeg_xfer(h, "transfer_jpeg", B, SH, SW, H, W, DH, DW, r, eps, c, flags & ~RRV_TF_ON_STREAM, j, cap, 0, &x, &p));
+    if (flags & RRV_TF_ON_STREAM) return fail(h, RRV_E_ARG, "transfer_jpeg: unknown flags");
+    if (!frames || !out || !sizes) return fail(h, RRV_E_ARG, "transfer_jpeg: null buffer");
+    if (!parse_in_host(in, &x.in)) return fail(h, RRV_E_ARG, "transfer_jpeg: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(check_xfer(h, x, true));
+    int sub = std::min(host_sub(B, x.KH(), x.KW()), 64);
+    if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
+    sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.OH() * x.OW())));
+    RCHK(claim_staging(h));
+    const size_t fb = x.in_bytes(), sizes_at = ((size_t)sub * cap + 15) & ~(size_t)15, mfb = x.matte_bytes();
+    const int nchunk = (B + sub - 1) / sub;
+    auto slot_of = [&](int k) { return h->profiling ? 0 : (k & 1) % h->n_slots; };
+    // everything either slot and either staging set allocates, before the first launch
+    for (int k = 0; k < std::min(nchunk, 2); ++k) {
+        RCHK(reserve_stages(h, slot_of(k), x.model == Model::GLOBAL ? sub : std::min(sub, (int)rrv_ctx::MS_GROUP_MAX), x));
+        RCHK(stage_reserve(h, k, (size_t)sub * fb, sizes_at + (size_t)sub * sizeof(int), false));
+        RCHK(stage_reserve(h, k, 0, (size_t)sub * sizeof(int), true));      // the sizes land page-locked: their copy must not hold the host
+        if (x.cmatte) RCHK(ensure_dev(h, h->hstage[k].mask, h->hstage[k].mask_cap, ((size_t)(x.cm_frames == 1 ? 1 : sub) * mfb + 3) / 4));
+    }
+    auto count = [&](int k) { return std::min(sub, B - k * sub); };
+    auto finish = [&](int k) -> int {      // sub-batch k's sizes, then its bytes
+        rrv_ctx::HostStage& st = h->hstage[k & 1];
+        const hipStream_t cs = h->slots[slot_of(k)].stream;
+        const int b0 = k * sub, nb = count(k);
+        HIPCHK(hipStreamSynchronize(cs));      // (the sizes have arrived with it)
+        memcpy(sizes + b0, st.pin.out, (size_t)nb * sizeof(int));
+        for (int b = 0; b < nb; ++b)
+            if (sizes[b0 + b] > 0)
+                HIPCHK(hipMemcpyAsync(out + (size_t)(b0 + b) * cap, (const uint8_t*)st.dev.out + (size_t)b * cap, (size_t)sizes[b0 + b], hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        return RRV_OK;
+    };
+    auto pipeline = [&]() -> int {      // (a lambda so that every way out, the HIP checks' included, passes the one exit below)
+    for (int k = 0; k < nchunk; ++k) {
+        rrv_ctx::HostStage& st = h->hstage[k & 1];      // (free again: finish(k - 2) has run)
+        const int slot = slot_of(k), b0 = k * sub, nb = count(k);
+        const hipStream_t cs = h->slots[slot].stream;
+        HIPCHK(hipMemcpyAsync(st.dev.in, (const uint8_t*)frames + (size_t)b0 * fb, (size_t)nb * fb, hipMemcpyHostToDevice, cs));
+        Xfer part = x;
+        part.B = nb;
+        if (x.cstr) part.cstr = x.cstr + b0;
+        if (x.cmatte) {
+            const char* const m = (const char*)x.cmatte + (x.cm_frames == 1 ? 0 : (size_t)b0 * mfb);
+            HIPCHK(hipMemcpyAsync(st.mask, m, (size_t)(x.cm_frames == 1 ? 1 : nb) * mfb, hipMemcpyHostToDevice, cs));
+            part.cmatte = st.mask; part.cm_frames = x.cm_frames == 1 ? 1 : nb;
+        }
+        int* const d_sizes = (int*)((char*)st.dev.out + sizes_at);
+        part.jp_sizes = d_sizes;
+        RCHK(run_xfer(h, slot, st.dev.in, st.dev.out, part));
+        HIPCHK(hipMemcpyAsync(st.pin.out, d_sizes, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, cs));
+        if (k > 0) RCHK(finish(k - 1));
+    }
+    return finish(nchunk - 1);
+    };
+    const int rc = pipeline();
+    if (rc != RRV_OK) (void)sync_all(h);      // nothing of a failed call is left in flight on the staging sets
+    return rc;
 }
 // a host frame format of the scaled host entries: uint8 HWC BGR, or any YUV layout with its own dtype
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in) {

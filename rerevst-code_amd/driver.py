@@ -423,7 +423,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420", work_size=None, out_size=None, guided=None, composite=None):
+                  chroma="420", work_size=None, out_size=None, guided=None, composite=None, gpu_jpeg=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -445,7 +445,10 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     out_size=; "source": each frame's own size); the frames and the video written have that size.
     guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source"), the upscale follows the source's edges.
     composite=dict(strength=, fade=, matte=, keep=): the stylized frame is mixed with the frame read on the GPU (Compositing; transfer_frames with
-    strength= / matte= / keep=); strengths and mattes go by the absolute frame number.  Needs a model with transfer_frames(strength=)."""
+    strength= / matte= / keep=); strengths and mattes go by the absolute frame number.  Needs a model with transfer_frames(strength=).
+    gpu_jpeg=dict(quality=, chroma=): the frames are encoded as baseline JPEG on the GPU (transfer_frames with out_format="jpeg"; one rank).  The
+    chunks of an .avi video_path and the frame files, written as <name>.jpg, are those bytes, unchanged: with write_frames=False no pixel reaches
+    the host.  Needs a model with jpeg_output (Stylization); not with a .y4m video_path."""
     import importlib
     import time
     from collections import deque
@@ -461,6 +464,13 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     nthreads = int(io_threads or default_io_threads())
     use_global = getattr(model, "use_Global", True)
     y4m = is_y4m(video_path)
+    if gpu_jpeg is not None:
+        if y4m:
+            raise ValueError("gpu_jpeg writes JPEG data: a .y4m video takes YUV frames")
+        if world > 1:
+            raise ValueError("gpu_jpeg runs on one rank")
+        if getattr(model, "jpeg_output", False) is not True or getattr(model, "transfer_frames", None) is None:
+            raise ValueError("gpu_jpeg needs a model with transfer_frames(out_format=\"jpeg\")")
     chroma = check_chroma(chroma, y4m)
     bit_depth = int(bit_depth) if y4m else 8
     yuv_fmt, yuv_dtype = y4m_format(chroma, bit_depth), (np.uint8 if bit_depth == 8 else np.uint16)
@@ -531,6 +541,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         out_dtype = np.uint8 if uint8_output(model) and not y4m else np.float32
         # only a .y4m to write and a model that converts on the GPU: the chunk's I420 bytes go from its output buffer to the file
         direct = fast and y4m and not write_frames and getattr(model, "yuv_output", False) is True
+        jpeg_direct = fast and gpu_jpeg is not None      # the GPU's JPEG bytes go to the AVI and / or the .jpg files unchanged
         if direct:
             model.set_yuv_matrix(*yuv, **({"bits": bit_depth} if bit_depth > 8 else {}))
         gpu_s = 0.0
@@ -551,7 +562,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             biggest = max(h * w for h, w in sizes)
             biggest_out = max(h * w for h, w in map(out_size, sizes))
             in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
-            if direct:
+            if jpeg_direct:
+                out_flat = None
+            elif direct:
                 out_flat = [_host_buffer(pkg_empty, (chunk * max(video.yuv_frame_bytes(h, w, chroma=chroma) for h, w in map(out_size, sizes)),), yuv_dtype) for _ in range(nbuf)]
             else:
                 out_flat = [_host_buffer(pkg_empty, (chunk * biggest_out * 3,), out_dtype) for _ in range(nbuf)]
@@ -560,6 +573,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 (H, W), m = sizes[chunks[k][0] - lo], len(chunks[k])
                 src = in_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
                 OH, OW = out_size((H, W))
+                if jpeg_direct:
+                    return src, None
                 if direct:
                     return src, out_flat[k % nbuf][:m * video.yuv_frame_bytes(OH, OW, chroma=chroma)].reshape(m, -1)
                 return src, out_flat[k % nbuf][:m * OH * OW * 3].reshape(m, OH, OW, 3)
@@ -570,7 +585,18 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     writer = open_writer(shape)
                 for fr in yuv_frames:
                     writer.append(fr, shape)
-            vpool = ThreadPoolExecutor(1) if direct else None
+
+            def append_jpegs(streams, shape, paths):  # the one video thread: a chunk's JPEG frames, unchanged, in order
+                nonlocal writer
+                for j, data in enumerate(streams):
+                    if video_path is not None:
+                        if writer is None:
+                            writer = open_writer(shape)
+                        writer.write_jpeg(data, shape)
+                    if paths:
+                        with open(paths[j], "wb") as f:
+                            f.write(data)
+            vpool = ThreadPoolExecutor(1) if direct or jpeg_direct else None
 
             def load(path, dst):                 # worker: decode straight into the page-locked input slot
                 img = read_image_bgr(path)
@@ -594,10 +620,26 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 t0 = time.perf_counter()
                 src, dst = views(k)
                 call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, out_size(src.shape[1:3])))
-                styled = on_device(src, out=dst, out_format=yuv_fmt, **call_kw) if direct else on_device(src, out=dst, **call_kw)
+                if jpeg_direct:
+                    jkw = dict(call_kw, out_format="jpeg", jpeg_quality=gpu_jpeg.get("quality", 95), jpeg_chroma=gpu_jpeg.get("chroma", "420"))
+                    try:
+                        styled = on_device(src, **jkw)
+                    except ValueError as e:      # a frame beyond the default two bytes per pixel: once more with room for any frame
+                        if "jpeg_cap" not in str(e):
+                            raise
+                        plan = importlib.import_module("rerevst-code_amd.framework").jpeg_plan(*out_size(src.shape[1:3]), jkw["jpeg_chroma"])
+                        styled = on_device(src, jpeg_cap=plan["bound"], **jkw)
+                else:
+                    styled = on_device(src, out=dst, out_format=yuv_fmt, **call_kw) if direct else on_device(src, out=dst, **call_kw)
                 gpu_s += time.perf_counter() - t0
                 submit_decode(k + 2)             # its input buffer was chunk k-1's: consumed
                 futs = []
+                if jpeg_direct:
+                    paths = [os.path.join(out_dir, os.path.splitext(os.path.basename(frame_paths[i]))[0] + ".jpg") for i in idx] if write_frames else []
+                    written.extend(paths)
+                    enc[k % nbuf] = [vpool.submit(append_jpegs, styled, out_size(src.shape[1:3]) + (3,), paths)]
+                    log("stylized frames %d..%d of %d" % (idx[0], idx[-1], n))
+                    continue
                 if direct:
                     enc[k % nbuf] = [vpool.submit(append_chunk, styled, out_size(src.shape[1:3]))]
                     log("stylized frames %d..%d of %d" % (idx[0], idx[-1], n))
@@ -625,6 +667,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 raise ValueError("out_size needs a model with transfer_frames(out_size=)")
             if comp is not None and hi > lo:
                 raise ValueError("strength / fade / matte / keep need a model with transfer_frames(strength=)")
+            if gpu_jpeg is not None and hi > lo:
+                raise ValueError("gpu_jpeg needs a model with transfer_frames(out_format=\"jpeg\")")
             tool = video.ReshapeTool()
             pending = deque()
             look = deque(pool.submit(read_image_bgr, frame_paths[i]) for i in range(lo, min(hi, lo + 2 * nthreads)))
@@ -1050,7 +1094,20 @@ def main(argv=None, model_factory=None):
                     "black: the frame read), or a directory with one such image per frame, in sorted order")
     ap.add_argument("--keep", choices=("colour", "color", "luma"), default=None, help="colour: the frame read keeps its colours and takes the stylized "
                     "luminance; luma: it keeps its luminance and takes the stylized colours")
+    ap.add_argument("--gpu-jpeg", action="store_true", help="encode the frames as baseline JPEG on the GPU (one GPU, one style, image-file input): the chunks of "
+                    "--video x.avi and the frame files, written as <name>.jpg, are the GPU's bytes; with --no-frames no pixel reaches the host")
+    ap.add_argument("--jpeg-quality", type=int, default=95, metavar="Q", help="quality of --gpu-jpeg, 1..100 (default 95, what the .avi path uses)")
+    ap.add_argument("--jpeg-chroma", choices=("420", "422", "444"), default="420", help="chroma subsampling of --gpu-jpeg (default 420)")
     args = ap.parse_args(argv)
+    gpu_jpeg = None
+    if args.gpu_jpeg:
+        if is_y4m(args.video):
+            ap.error("--gpu-jpeg writes JPEG data: --video takes an .avi with it")
+        if is_y4m(args.frames) or len(args.style) > 1 or args.gpus > 1:
+            ap.error("--gpu-jpeg runs the single-style flow over image files on one GPU")
+        if not 1 <= args.jpeg_quality <= 100:
+            ap.error("--jpeg-quality lies in 1..100")
+        gpu_jpeg = dict(quality=args.jpeg_quality, chroma=args.jpeg_chroma)
     composite = None
     if args.strength is not None or args.fade or args.matte is not None or args.keep is not None:
         if len(args.style) > 1:
@@ -1157,7 +1214,7 @@ def main(argv=None, model_factory=None):
         stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
                       io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
                       write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
-                      out_size=out_size, guided=guided, composite=composite)
+                      out_size=out_size, guided=guided, composite=composite, **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}))
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

@@ -532,6 +532,78 @@ def _chunks(B, *sides, chunk=TENSOR_BATCH_MAX):
         yield (b0, min(chunk, B - b0), *(C.c_void_p(ptr + b0 * step) for ptr, step in sides))
 
 
+# ===== JPEG output (the rrv_jpeg_* entries; include/rerevst_hip.h "JPEG output" states the format) =====
+def jpeg_args(quality=90, chroma="420", restart=None):
+    """The rrv_jpeg of the jpeg_* keywords: quality 1..100, chroma "420" / "422" / "444" (or the number), restart the MCUs per restart
+    interval (1..65535; None: the library's choice, one MCU row)"""
+    try:
+        q = int(quality)
+        ok = q == quality and not isinstance(quality, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not 1 <= q <= 100:
+        raise ValueError("jpeg_quality must be an integer in 1..100, got %r" % (quality,))
+    if str(chroma) not in ("420", "422", "444") or isinstance(chroma, bool):
+        raise ValueError("jpeg_chroma must be '420', '422' or '444', got %r" % (chroma,))
+    if restart is None:
+        r = 0
+    else:
+        try:
+            r = int(restart)
+            ok = r == restart and not isinstance(restart, bool)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or not 1 <= r <= 65535:
+            raise ValueError("jpeg_restart must be None or an integer in 1..65535 (MCUs per restart interval), got %r" % (restart,))
+    return _lib.Jpeg(q, int(str(chroma)), r)
+
+
+def _jpeg_alone(style_weights, style_masks, what):
+    if style_weights is not None or style_masks is not None:
+        raise ValueError("%s does not combine with style_weights / style_masks: JPEG output is for the global and the frame model" % what)
+
+
+def jpeg_tables(quality):
+    """(luma, chroma): the two uint16 [64] quantisation tables of a quality, natural order (rrv_jpeg_tables; no GPU)"""
+    j = jpeg_args(quality)
+    lu, ch = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    u16 = C.POINTER(C.c_uint16)
+    if _lib.load().rrv_jpeg_tables(j.quality, lu.ctypes.data_as(u16), ch.ctypes.data_as(u16)) != 0:
+        raise ValueError("rrv_jpeg_tables refused quality %r" % (quality,))
+    return lu, ch
+
+
+def jpeg_plan(H, W, chroma="420", restart=None):
+    """dict(mcu_cols, mcu_rows, interval, blocks, header_bytes, bound) of an H x W frame (rrv_jpeg_plan, rrv_jpeg_bound; no GPU)"""
+    j = jpeg_args(90, chroma, restart)
+    v = [C.c_int(0) for _ in range(5)]
+    n = C.c_size_t(0)
+    lib = _lib.load()
+    if lib.rrv_jpeg_plan(int(H), int(W), j.chroma, j.restart, *(C.byref(x) for x in v)) != 0 or lib.rrv_jpeg_bound(int(H), int(W), j.chroma, j.restart, C.byref(n)) != 0:
+        raise ValueError("JPEG frames are 1..65535 pixels per side, got %r x %r" % (H, W))
+    return dict(zip(("mcu_cols", "mcu_rows", "interval", "blocks", "header_bytes"), (x.value for x in v)), bound=n.value)
+
+
+def jpeg_slot_bytes(H, W, chroma="420", restart=None, cap=None):
+    """the slot size of a jpeg_cap= keyword: None is two bytes per pixel plus the header (never more than the bound); a number must hold the header"""
+    plan = jpeg_plan(H, W, chroma, restart)
+    if cap is None:
+        return min(2 * int(H) * int(W) + plan["header_bytes"] + 2, plan["bound"])
+    if isinstance(cap, bool) or int(cap) != cap or int(cap) < plan["header_bytes"] + 2:
+        raise ValueError("jpeg_cap must be an integer of at least the header and EOI (%d bytes), got %r" % (plan["header_bytes"] + 2, cap))
+    return int(cap)
+
+
+def jpeg_frames(data, sizes):
+    """the frames of an encode as a list of bytes: data uint8 [B][cap], sizes int32 [B] (tensors or arrays).  A frame that did not fit raises."""
+    data, sizes = (np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in (data, sizes))
+    short = [(b, -int(n)) for b, n in enumerate(sizes) if n < 0]
+    if short:
+        raise ValueError("jpeg_cap = %d bytes is too small: frame %d needs %d (frames that did not fit: %s)"
+                         % (data.shape[1], short[0][0], short[0][1], [b for b, _ in short]))
+    return [data[b, :int(n)].tobytes() for b, n in enumerate(sizes)]
+
+
 # ===== scaling (the rrv_*_scaled* entries; include/rerevst_hip.h "Scaling" states the arithmetic) =====
 def _work_size(work_size):
     """(H, W) of a work_size= keyword: the size the frames are resampled to on the GPU, and the size of the delivered frame"""
@@ -778,6 +850,8 @@ class Stylization():
     # transfer_batch / transfer_frames take out_format="i420" | "nv12" (the rrv_*_yuv entries): driver.stylize_files asks for it when
     # it writes only a .y4m video
     yuv_output = True
+    # transfer_batch / transfer_frames take out_format="jpeg" (rrv_transfer_jpeg): driver.stylize_files asks for it with gpu_jpeg=
+    jpeg_output = True
     # transfer_batch / transfer_frames / add take in_format="i420" | "nv12" with size=(H, W) (the rrv_*_from_yuv entries): driver.stylize_y4m
     # feeds a .y4m input that way
     yuv_input = True
@@ -1081,9 +1155,16 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None,
-                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
+                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None, jpeg=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
-        size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES)"""
+        size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES).
+        jpeg: (quality, chroma, restart, cap) of out_format="jpeg" (rrv_transfer_jpeg): a list of bytes comes back"""
+        is_jpeg = out_format == "jpeg"
+        if is_jpeg:
+            _jpeg_alone(style_weights, style_masks, 'out_format="jpeg"')
+            if out is not None or np.dtype(dtype) != np.float32:
+                raise ValueError('out_format="jpeg" returns a list of bytes: out= and dtype= do not apply')
+            j, out_format = jpeg_args(*jpeg[:3]), "bgr"
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
         if yuv_out and out_format not in YUV_FORMATS:
             raise ValueError("out_format must be 'bgr', %s, got %r" % (YUV_FORMAT_NAMES, out_format))
@@ -1106,6 +1187,16 @@ class Stylization():
         m = None if style_masks is None else style_mask_args(style_masks, style_weights, B, H, W, self.style_num, self.device, self.use_Global)
         Ho, Wo = (DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)
         comp = _composite_args(strength, matte, keep, style_weights, style_masks, B, Ho, Wo)
+        if is_jpeg:      # (r = 0: bilinear delivery; DH = DW = 0: the working frame is delivered; a null request: nothing is composited)
+            cap = jpeg_slot_bytes(Ho, Wo, jpeg[1], jpeg[2], jpeg[3])
+            r, eps = _guide_args(guide, guide_radius, guide_eps, out_size) if guide is not None else (0, 0.0)
+            req = comp.request(0, B) if comp is not None else None
+            data, sizes = np.empty((B, cap), np.uint8), np.zeros(B, np.int32)
+            self._yuv_depth(in_format, None)
+            self._chk(self._lib.rrv_transfer_jpeg(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, SH, SW, H, W,
+                                                  *((DH, DW) if out_size is not None else (0, 0)), r, eps, C.byref(req) if req is not None else None, C.byref(j),
+                                                  data.ctypes.data_as(C.c_void_p), cap, sizes.ctypes.data_as(C.c_void_p), self._flags(pad_crop)))
+            return jpeg_frames(data, sizes)
         out, u8 = _output((B, Ho, Wo, 3), dtype, out, out_format)
         self._yuv_depth(in_format, out_format)
         desc = _lib.ImageDesc(_lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32,
@@ -1144,7 +1235,8 @@ class Stylization():
         return out
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                       work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
+                       work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None,
+                       jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -1187,12 +1279,18 @@ class Stylization():
         much of the stylized frame shows; matte: a float32 (0..1) or uint8 (0..255) array [B or 1][Ho][Wo] at the delivered size, where it
         shows; keep: "colour" ("color") keeps the source's colours and takes the stylized luminance, "luma" the reverse.  They combine with
         work_size, out_size, guide, in_format, out_format and dtype; the working size must be delivered whole as for guide=.  Not with
-        style_weights / style_masks (ValueError).  video.composite restates the arithmetic in numpy."""
+        style_weights / style_masks (ValueError).  video.composite restates the arithmetic in numpy.
+        out_format="jpeg": the delivered frame is encoded as baseline JPEG on the GPU (rrv_transfer_jpeg; include/rerevst_hip.h "JPEG
+        output") and a list of B `bytes` comes back, each a complete .jpg file: jpeg_quality 1..100, jpeg_chroma "420" | "422" | "444",
+        jpeg_restart the MCUs per restart interval (None: one MCU row), jpeg_cap the bytes reserved per frame (None: two per delivered pixel
+        plus the header; a frame that does not fit raises a ValueError that names jpeg_cap).  It combines with work_size, out_size, guide,
+        strength / matte / keep and in_format; not with style_weights / style_masks, out= or dtype=."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps, strength, matte, keep)
+                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
-                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
+                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None,
+                        jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -1209,9 +1307,10 @@ class Stylization():
         (or the YUV frames of that size) is what comes back.
         out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW.
         guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size.
-        strength / matte / keep: compositing with the frames as passed, as in transfer_batch; any working size."""
+        strength / matte / keep: compositing with the frames as passed, as in transfer_batch; any working size.
+        out_format="jpeg" with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap: a list of `bytes`, as in transfer_batch."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps, strength, matte, keep)
+                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -1220,7 +1319,8 @@ class Stylization():
 
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
                         pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None, guide=None,
-                        guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None):
+                        guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None, jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None,
+                        jpeg_cap=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -1265,9 +1365,19 @@ class Stylization():
         strength / matte / keep: compositing with x itself (rrv_transfer_composite_view_device; include/rerevst_hip.h "Compositing"), as in
         transfer_batch; matte a float32 or uint8 tensor [B or 1, Ho, Wo] on the handle's device, read in the order of the current stream
         like style_masks (an ndarray is copied there).  The call equals the float32 "nhwc" call with the same work_size / out_size / guide,
-        resample_tensor for the source at the delivered size and composite_tensor."""
+        resample_tensor for the source at the delivered size and composite_tensor.
+        out_layout="jpeg": the delivered frame is encoded as baseline JPEG on the GPU (rrv_transfer_jpeg_view_device; include/rerevst_hip.h
+        "JPEG output") with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap as in transfer_batch.  Returns (uint8 [B][cap] tensor, int32
+        [B] sizes tensor) in stream order, as encode_jpeg_tensor does (framework.jpeg_frames reads them on the host); the call equals the
+        float32 "nhwc" call followed by encode_jpeg_tensor.  Not with style_weights / style_masks, out=, out_dtype= or another out_space."""
         import torch
         composite = strength is not None or matte is not None or keep is not None
+        is_jpeg = isinstance(out_layout, str) and out_layout == "jpeg"
+        if is_jpeg:
+            _jpeg_alone(style_weights, style_masks, 'out_layout="jpeg"')
+            if out is not None or out_dtype is not None or out_space != "pixel":
+                raise ValueError('out_layout="jpeg" returns (bytes tensor, sizes tensor): out=, out_dtype= and out_space= do not apply')
+            j = jpeg_args(jpeg_quality, jpeg_chroma, jpeg_restart)
         if guide is not None:
             g_r, g_eps = _guide_args(guide, guide_radius, guide_eps, out_size)
         if out_size is not None:
@@ -1275,7 +1385,7 @@ class Stylization():
         elif work_size is not None:
             _no_styles_with_work_size(style_weights, style_masks)
         work = None if work_size is None else _work_size(work_size)
-        scaled = work is not None or out_size is not None or composite      # (the view entries serve every compositing call)
+        scaled = work is not None or out_size is not None or composite or is_jpeg      # (the view entries serve every compositing and JPEG call)
         xv, ov = (t if isinstance(t, ImageView) else None for t in (x, out))
         # An unscaled call refuses in tensor_io_args' order and words (tests/call_record.json pins which refusal a call meets): the space
         # of a YUV surface first, and for a tensor x the names of both sides before x is looked at.
@@ -1295,6 +1405,21 @@ class Stylization():
         if not scaled and xv is None and ov is not None:      # (.. and the dtype of an output view for a tensor x, before the view is looked at)
             _tensor_out_args(self.device, B, Ho, Wo, src.batched, out_space, ov.storage.dtype, ov.layout if out_layout is None else out_layout, True, None)
         comp = _composite_args(strength, matte, keep, style_weights, style_masks, B, Ho, Wo, tensors=True, device=self.device)
+        if is_jpeg:
+            cap = jpeg_slot_bytes(Ho, Wo, jpeg_chroma, jpeg_restart, jpeg_cap)
+            data = torch.empty((B, cap), dtype=torch.uint8, device=src.tensor.device)
+            sizes = torch.empty((B,), dtype=torch.int32, device=src.tensor.device)
+            if comp is not None:
+                comp.on_device(src.tensor)
+            vi = _whole_view(src, src.H, src.W)
+            self._yuv_depth(src.layout, None)
+            for b0, nb, p, q, sz in _chunks(B, (src.ptr, src.step), (data.data_ptr(), cap), (sizes.data_ptr(), 4)):
+                req = comp.request(b0, nb) if comp is not None else None
+                self._chk(self._lib.rrv_transfer_jpeg_view_device(self._h, p, C.byref(vi), nb, SH, SW, H, W, *((DH, DW) if out_size is not None else (0, 0)),
+                                                                  g_r if guide is not None else 0, g_eps if guide is not None else 0.0,
+                                                                  C.byref(req) if req is not None else None, C.byref(j), q, cap, sz,
+                                                                  self._flags(pad_crop, on_stream=True), self._stream(src.tensor)))
+            return data, sizes
         dst = self._target(out, out_layout, out_space, out_dtype, B, Ho, Wo, src.batched, src.tensor, default_layout=src.layout)
         if comp is not None:
             comp.on_device(src.tensor)
@@ -1398,6 +1523,62 @@ class Stylization():
             req = comp.request(b0, nb)
             self._chk(self._lib.rrv_composite_view_device(self._h, p, C.c_void_p(sb[b0].data_ptr()), nb, H, W, C.byref(req), q, C.byref(vo), stream))
         return dst.result
+
+    def _jpeg_frames(self, y, what):
+        import torch
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() not in (3, 4) or y.shape[-1] != 3:
+            raise ValueError("%s must be a float32 tensor [B,H,W,3] or [H,W,3] (BGR, 'pixel' space)" % what)
+        _on_device(y, what, self.device)
+        return (y if y.dim() == 4 else y.unsqueeze(0)).contiguous()
+
+    def jpeg_blocks_tensor(self, y, *, jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None):
+        """The first half of the JPEG stage alone (rrv_jpeg_blocks_device): the quantised coefficient blocks of y, an int16 tensor
+        [B][blocks][64] in zigzag order, the blocks in scan order.  Ordered on the current stream."""
+        import torch
+        yb = self._jpeg_frames(y, "y")
+        B, H, W = yb.shape[:3]
+        j = jpeg_args(jpeg_quality, jpeg_chroma, jpeg_restart)
+        blocks = jpeg_plan(H, W, jpeg_chroma, jpeg_restart)["blocks"]
+        coef = torch.empty((B, blocks, 64), dtype=torch.int16, device=yb.device)
+        for _, nb, p, q in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (coef.data_ptr(), blocks * 128)):
+            self._chk(self._lib.rrv_jpeg_blocks_device(self._h, p, nb, H, W, C.byref(j), q, self._stream(yb)))
+        return coef
+
+    def jpeg_entropy_tensor(self, coef, size, *, jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
+        """The second half alone (rrv_jpeg_entropy_device): coef an int16 tensor [B][blocks][64] as jpeg_blocks_tensor returns it, of frames of
+        size=(H, W) -> (uint8 [B][cap] tensor, int32 [B] sizes tensor).  Ordered on the current stream."""
+        import torch
+        H, W = int(size[0]), int(size[1])
+        j = jpeg_args(jpeg_quality, jpeg_chroma, jpeg_restart)
+        cap = jpeg_slot_bytes(H, W, jpeg_chroma, jpeg_restart, jpeg_cap)
+        blocks = jpeg_plan(H, W, jpeg_chroma, jpeg_restart)["blocks"]
+        if not isinstance(coef, torch.Tensor) or coef.dtype != torch.int16 or coef.dim() != 3 or tuple(coef.shape[1:]) != (blocks, 64):
+            raise ValueError("coef must be an int16 tensor [B][%d][64] for %d x %d frames" % (blocks, H, W))
+        _on_device(coef, "coef", self.device)
+        cb = coef.contiguous()
+        B = cb.shape[0]
+        data = torch.empty((B, cap), dtype=torch.uint8, device=cb.device)
+        sizes = torch.empty((B,), dtype=torch.int32, device=cb.device)
+        for _, nb, p, q, sz in _chunks(B, (cb.data_ptr(), blocks * 128), (data.data_ptr(), cap), (sizes.data_ptr(), 4)):
+            self._chk(self._lib.rrv_jpeg_entropy_device(self._h, p, nb, H, W, C.byref(j), q, cap, sz, self._stream(cb)))
+        return data, sizes
+
+    def encode_jpeg_tensor(self, y, *, jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
+        """The JPEG stage alone (rrv_jpeg_encode_device; include/rerevst_hip.h "JPEG output"): y a float32 tensor [B,H,W,3] ([H,W,3]) on the
+        handle's GPU, BGR, "pixel" space -- what transfer_tensor(.., layout="nhwc"), deliver_tensor and composite_tensor return -- encoded as
+        baseline JPEG on the GPU.  Returns (uint8 [B][cap] tensor, int32 [B] sizes tensor) in stream order: frame b is data[b, :sizes[b]]; a
+        frame that did not fit has sizes[b] = -(the bytes it needs).  jpeg_cap: bytes per slot (None: two per pixel plus the header).
+        framework.jpeg_frames turns the pair into a list of bytes on the host."""
+        import torch
+        yb = self._jpeg_frames(y, "y")
+        B, H, W = yb.shape[:3]
+        j = jpeg_args(jpeg_quality, jpeg_chroma, jpeg_restart)
+        cap = jpeg_slot_bytes(H, W, jpeg_chroma, jpeg_restart, jpeg_cap)
+        data = torch.empty((B, cap), dtype=torch.uint8, device=yb.device)
+        sizes = torch.empty((B,), dtype=torch.int32, device=yb.device)
+        for _, nb, p, q, sz in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (data.data_ptr(), cap), (sizes.data_ptr(), 4)):
+            self._chk(self._lib.rrv_jpeg_encode_device(self._h, p, nb, H, W, C.byref(j), q, cap, sz, self._stream(yb)))
+        return data, sizes
 
     def _guide_tensor(self, g, name, shape, batched):
         """a guide of deliver_tensor as a contiguous float32 [B,H,W,3] tensor on the handle's GPU"""
