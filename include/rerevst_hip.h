@@ -31,7 +31,8 @@ enum {
     RRV_E_STATE = -4,      /* transfer before compute()/set_state, compute with no frames, ... */
     RRV_E_NOMEM = -5,      /* out of device (or page-locked host) memory */
     RRV_E_DEBUG = -6,      /* bounds-checked debug mode found a store outside a tensor's valid region */
-    RRV_E_COMM = -7        /* RCCL: library not found, or a communicator / collective call failed */
+    RRV_E_COMM = -7,       /* RCCL: library not found, or a communicator / collective call failed */
+    RRV_E_DATA = -8        /* JPEG input: a stream the parser refuses, or a frame whose entropy-coded data is corrupt */
 };
 
 /* Floats in the per-style shared-state blob: 11 norm layers x {mean,rstd,lo,hi}[C]
@@ -873,6 +874,114 @@ int rrv_transfer_jpeg_view_device(rrv_handle h, const void* d_in, const rrv_imag
                                   int* d_sizes, int flags, void* hip_stream);
 int rrv_transfer_jpeg(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int H, int W, int DH, int DW, int r,
                       float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* out, size_t cap, int* sizes, int flags);
+
+/* JPEG input: one baseline JPEG stream per frame decoded on the GPU into the 8-bit planar frame the YUV-input forms read ("8-bit YUV 4:2:0
+ * INPUT", "Chroma formats"), so that a compressed frame is what enters HBM.
+ * Streams taken.  Baseline sequential (SOF0), 8 bits; three components (any ids) that are YCbCr, Y sampled 1x1, 2x1 or 2x2 and both chroma
+ * components 1x1 (chroma 444, 422, 420), or one component (grey, chroma 400); one scan, interleaved for three components, Ss = 0, Se = 63,
+ * Ah = Al = 0; any number of DQT / DHT segments with 8-bit quantisers and table ids 0..1, the last definition before SOS holding; no DHT at all
+ * means the Annex K tables (MJPG in AVI); DRI present or not; APPn / COM segments and fill bytes; a missing EOI, or bytes behind it.
+ * rrv_jpeg_parse refuses everything else in words (why): progressive, extended, lossless and arithmetic frames, 12-bit samples, 16-bit
+ * quantisers, other sampling factors, two or four components, an APP14 Adobe segment whose transform is not YCbCr, a scan that does not code
+ * all components (several scans), a table a scan names and nobody defined, code lengths that over-subscribe the code space, H or W of 0, a
+ * header that ends early.  It reads SOI .. SOS only, on any byte string, and needs no handle and no GPU: RRV_OK, RRV_E_DATA with the reason, or
+ * RRV_E_ARG for a null pointer.  All frames of one call share H, W and chroma; tables and restart intervals may differ frame by frame.
+ * Entropy half.  The scan's bytes become coefficient blocks in the layout of "JPEG output": int16 [B][blocks][64], a block's values in zigzag
+ * order, the blocks in scan order (grey: one block per MCU).  It is a function of the stream alone, so for this library's own streams it is
+ * the inverse of rrv_jpeg_entropy_device bit for bit.  A marker is FF followed by a byte that is neither 00 nor FF.  With DRI the scan has
+ * `intervals` intervals: marker k < intervals - 1 must be RST(k mod 8) and ends interval k; the next marker (EOI as a rule; it must not be a
+ * restart marker) or the stream's end ends the last; nothing behind it is read.  Without DRI the one interval ends at the first marker or the
+ * stream's end.  DC prediction starts from 0 in every interval; FF 00 is the data byte FF.
+ * Pixel half.  Per block: coefficient x the component's quantiser; the 8 x 8 inverse DCT with JPEG's normalisation, f(x,y) = 1/4 sum_uv C(u)
+ * C(v) F(u,v) cos((2x+1) u pi/16) cos((2y+1) v pi/16), C(0) = 1/sqrt 2, in float32; + 128, clamped to 0..255, rint half to even.  The contract
+ * is the rounding of the exact value: a value within float32 error of a half-integer may go either way.
+ * Planes.  Y is H x W, Cb and Cr CH x CW with CH = ceil(H / vs), CW = ceil(W / hs); the MCU padding is dropped.  A frame is [Y][Cb][Cr],
+ * frame_bytes = H W + 2 CH CW, frame b at b * frame_bytes: RRV_LAY_I420 / _I422 / _I444 of "YUV input".  Grey is an I444 frame whose chroma
+ * planes hold 128.  The stage upsamples no chroma: a decoded frame enters the network through the YUV-input arithmetic (which replicates
+ * chroma, and says why nothing better would show), with rrv_yuv_input_matrix(RRV_YUV_BT601, full_range = 1), JFIF's colour space.
+ * Status.  d_status[b] is 0 for a decoded frame, else one of RRV_JPEG_ST_* (rrv_jpeg_status_words gives the words).  A failed frame leaves
+ * unspecified content in its own blocks and planes only; the other frames of the call are unaffected and the call still returns RRV_OK: the
+ * statuses are device results, as the encoder's sizes are.  Corrupt bytes cannot make a kernel loop or store outside the frame's own blocks:
+ * every loop runs over block and coefficient counts, never over the data.
+ *   rrv_jpeg_parse           stream -> rrv_jpeg_info
+ *   rrv_jpeg_scan_device     the entropy half alone: B (1..64) streams, frame b at d_streams + b * cap, with their parsed infos (host) -> d_coef
+ *                            (16-byte aligned) and d_status, queued on hip_stream (NULL: the null stream); nothing of the handle's own streams
+ *                            takes part.  The frame descriptors (about 4 KB per frame) and the interval starts live in buffers of the handle
+ *                            (grow-only): calls on different streams must be ordered by the caller
+ *   rrv_jpeg_planes_device   the pixel half alone: coefficient blocks -> planes, queued the same way (the infos give the size and quantisers)
+ *   rrv_jpeg_decode_device   both halves, the blocks in a buffer of the handle (128 bytes per block, grow-only); equals the two calls above bit
+ *                            for bit
+ * Checks, all before any GPU work: the batch, the infos (one size and chroma format; fields that hold together, as rrv_jpeg_parse fills them),
+ * cap against every frame's scan, null or misaligned buffers; RRV_E_ARG names the field and the handle stays usable.  Scratch is reserved
+ * before the call's first launch: out of memory is RRV_E_NOMEM and the handle stays usable.  Results do not depend on what the scratch held
+ * before.  These buffers are plain allocations: the guard bands of rrv_set_debug do not cover them.
+ * As an input form.  rrv_transfer_from_jpeg_view_device is rrv_transfer_composite_view_device with JPEG streams in place of the input buffer and
+ * view: d_streams, cap and the parsed infos (B 1..64), then the working size (0, 0: the streams' own size; else the decoded frames are resampled
+ * to it, "Scaling"), then that entry's DH, DW, r, eps, request c (NULL: none), output buffer and view, then d_status, the flags and the stream.
+ * The decode is queued on hip_stream (NULL: the null stream) into a buffer of the handle and the transfer is ordered behind it on that stream
+ * (RRV_TF_ON_STREAM is implied); GLOBAL or (RRV_TF_FRAME_MODE) FRAME model; every output form.  rrv_transfer_jpeg_from_jpeg_view_device is its twin
+ * with JPEG as the output form too (the arguments of rrv_transfer_jpeg_view_device behind the request).  A transfer from JPEG equals, bit for bit
+ * in a fixed kernel mode, rrv_jpeg_decode_device followed by the same entry reading those planes (RRV_LAY_I420 / _I422 / _I444) with
+ * rrv_yuv_input_matrix(RRV_YUV_BT601, 1) installed -- whatever matrix the handle holds, which is put aside while the call queues its launches
+ * and is unchanged afterwards.  All checks, the decode's and those of the transfer behind
+ * it (sizes, guide, request, output view or rrv_jpeg and cap, flags, the model's state), run before anything is queued or copied; the host
+ * twins make them on their first sub-batch's request once every stream is parsed.  (rrv_add_from_jpeg judges the stream first and the frame
+ * rules of rrv_add after the decode has run into the handle's scratch.)
+ * Host twins, any B: rrv_transfer_from_jpeg and rrv_transfer_jpeg_from_jpeg take B host pointers and sizes, parse every stream first (a stream
+ * the parser refuses: RRV_E_DATA, the message names the frame and the reason, nothing has run), copy each frame's own bytes, run sub-batches of
+ * sixteen one after the other on the handle's first stream and read the statuses back per sub-batch: a corrupt frame is RRV_E_DATA naming its
+ * index (frames of earlier sub-batches have been written), and the handle stays usable.  `out`: a contiguous output of descriptor `od`
+ * (rrv_transfer_from_jpeg), or slots of out_cap bytes and host sizes (rrv_transfer_jpeg_from_jpeg, which takes strengths and keep but no matte).
+ * A host matte of rrv_transfer_from_jpeg is uploaded per sub-batch.  rrv_add_from_jpeg: rrv_add for a sampled frame that is a host JPEG stream
+ * (working size 0, 0: its own): decoded on the GPU and added as the float32 PIXEL frame "Scaling" makes of the planes with the same matrix (at
+ * the stream's own size every tap weight is 1), not deferred; RRV_E_DATA for a refused or corrupt stream.  Not offered: blended and masked
+ * models, tickets, the one-frame entries.
+ * A stream without restart intervals is decoded by one lane per frame: correct, and slow (DESIGN.md says how slow); the frames of a call still
+ * run side by side. */
+#define RRV_JPEG_ST_DATA 1               /* the entropy-coded data ran out */
+#define RRV_JPEG_ST_CODE 2               /* invalid Huffman code */
+#define RRV_JPEG_ST_RUN 3                /* a run past coefficient 63 */
+#define RRV_JPEG_ST_CATEGORY 4           /* magnitude category out of range (DC above 11, AC above 10) */
+#define RRV_JPEG_ST_MARKER_MISSING 5     /* fewer restart markers than the plan has intervals */
+#define RRV_JPEG_ST_MARKER_WRONG 6       /* a marker that is not the restart marker expected in rotation */
+#define RRV_JPEG_ST_MARKER_SURPLUS 7     /* a restart marker behind the last interval */
+typedef struct rrv_jpeg_info {
+    int H, W;
+    int chroma;                  /* 400, 420, 422 or 444 */
+    int components;              /* 1 or 3 */
+    int interval;                /* MCUs per restart interval; 0: none */
+    int mcu_cols, mcu_rows;
+    int blocks;                  /* per frame */
+    int intervals;               /* per frame; 1 without DRI */
+    int reserved;
+    size_t scan_offset;          /* of the scan's bytes in the stream ... */
+    size_t scan_bytes;           /* ... and from there to the stream's end */
+    uint8_t q[3][64];            /* the quantisers per component, natural order */
+    uint8_t huff_dc[3];          /* per component: which DC specification (0 / 1) ... */
+    uint8_t huff_ac[3];          /* ... and which AC one */
+    uint8_t huff_given;          /* 0: no DHT in the stream, the specifications are Annex K's */
+    uint8_t pad;
+    uint8_t huff_bits[4][16];    /* the four Huffman specifications, DC 0, DC 1, AC 0, AC 1: codes per length 1..16 ... */
+    uint8_t huff_vals[4][256];   /* ... and the symbols in code order */
+} rrv_jpeg_info;
+int rrv_jpeg_parse(const uint8_t* stream, size_t size, rrv_jpeg_info* info, char* why, size_t why_len);
+const char* rrv_jpeg_status_words(int status);
+int rrv_jpeg_scan_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int16_t* d_coef, int* d_status,
+                         void* hip_stream);
+int rrv_jpeg_planes_device(rrv_handle h, const int16_t* d_coef, const rrv_jpeg_info* infos, int B, uint8_t* d_planes, void* hip_stream);
+int rrv_jpeg_decode_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, uint8_t* d_planes, int* d_status,
+                           void* hip_stream);
+int rrv_transfer_from_jpeg_view_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int work_H, int work_W, int DH,
+                                       int DW, int r, float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out, int* d_status, int flags,
+                                       void* hip_stream);
+int rrv_transfer_jpeg_from_jpeg_view_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int work_H, int work_W,
+                                            int DH, int DW, int r, float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* d_out, size_t out_cap,
+                                            int* d_sizes, int* d_status, int flags, void* hip_stream);
+int rrv_transfer_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, int work_H, int work_W, int DH, int DW, int r, float eps,
+                           const rrv_composite* c, void* out, rrv_image_desc od, int flags);
+int rrv_add_from_jpeg(rrv_handle h, const uint8_t* stream, size_t size, int work_H, int work_W);
+int rrv_transfer_jpeg_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, int work_H, int work_W, int DH, int DW, int r,
+                                float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* out, size_t out_cap, int* out_sizes, int flags);
 
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */

@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
 # reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
-# needs a copy of it there (and of librerevst_compose.so and librerevst_jpeg.so).
+# needs a copy of it there (and of librerevst_compose.so, librerevst_jpeg.so and librerevst_jpeg_in.so).
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -38,6 +38,15 @@ class Jpeg(C.Structure):
     _fields_ = [("quality", C.c_int), ("chroma", C.c_int), ("restart", C.c_int)]
 
 
+class JpegInfo(C.Structure):
+    """rrv_jpeg_info: what rrv_jpeg_parse reads from a baseline JPEG stream's header (include/rerevst_hip.h "JPEG input")."""
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("chroma", C.c_int), ("components", C.c_int), ("interval", C.c_int), ("mcu_cols", C.c_int),
+                ("mcu_rows", C.c_int), ("blocks", C.c_int), ("intervals", C.c_int), ("reserved", C.c_int), ("scan_offset", C.c_size_t),
+                ("scan_bytes", C.c_size_t), ("q", C.c_uint8 * 64 * 3), ("huff_dc", C.c_uint8 * 3), ("huff_ac", C.c_uint8 * 3), ("huff_given", C.c_uint8),
+                ("pad", C.c_uint8), ("huff_bits", C.c_uint8 * 16 * 4), ("huff_vals", C.c_uint8 * 256 * 4)]
+
+
+E_DATA = -8                       # RRV_E_DATA: a JPEG stream the parser refuses, or a frame whose entropy-coded data is corrupt
 DT_U8, DT_F32 = 0, 1
 DT_U16 = 2                        # uint16 samples: only with LAY_I420_16 / LAY_P016
 LAY_HWC_BGR, LAY_CHW_RGB = 0, 1
@@ -193,6 +202,24 @@ SYMBOLS = {
                                                 C.c_int, C.c_float, C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "rrv_transfer_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                     C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    # JPEG input: the parser needs no handle; (h, streams, cap, JpegInfo* infos, B, coef / planes, status, hip_stream)
+    "rrv_jpeg_parse": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.c_char_p, C.c_size_t]),
+    "rrv_jpeg_status_words": (C.c_char_p, [C.c_int]),
+    "rrv_jpeg_scan_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rrv_jpeg_planes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(JpegInfo), C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_jpeg_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # JPEG as the input form: (h, streams, cap, infos, B, work H, W, DH, DW, r, eps, Composite* c, [Jpeg* p,] out, view | cap, sizes, status, flags, hip_stream)
+    "rrv_transfer_from_jpeg_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_float, C.POINTER(Composite), C.c_void_p, C.POINTER(ImageView), C.c_void_p, C.c_int, C.c_void_p]),
+    "rrv_transfer_jpeg_from_jpeg_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          C.c_float, C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
+                                                          C.c_void_p]),
+    # the host twins: (h, char** streams, size_t* sizes, B, work H, W, DH, DW, r, eps, Composite* c, [Jpeg* p,] out, desc | cap, sizes, flags)
+    "rrv_transfer_from_jpeg": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.POINTER(Composite), C.c_void_p, ImageDesc, C.c_int]),
+    "rrv_add_from_jpeg": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
+    "rrv_transfer_jpeg_from_jpeg": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                              C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

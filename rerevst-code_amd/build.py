@@ -1,7 +1,8 @@
 """Builds librerevst_stages.so (the kernels of the frame stages around the network: input resampler, delivery, guided delivery; one
 translation unit, csrc/stages.hip), librerevst_compose.so (the compositing stage behind them; one translation unit, csrc/compose.hip),
-librerevst_jpeg.so (the JPEG output stage; one translation unit, csrc/jpeg.hip) and librerevst_hip.so (everything else, linked against the
-three) in-tree with hipcc for gfx950 (cross-compiles without a GPU).  Four libraries so that the main unit's kernel set and compile time stay
+librerevst_jpeg.so (the JPEG output stage; one translation unit, csrc/jpeg.hip), librerevst_jpeg_in.so (the JPEG input stage; one translation
+unit, csrc/jpeg_in.hip) and librerevst_hip.so (everything else, linked against the four) in-tree with hipcc for gfx950 (cross-compiles without
+a GPU).  Five libraries so that the main unit's kernel set and compile time stay
 what they are, the stages rebuild in seconds, and the kernel sets of the stages and the compositing library stay what their ledgers pin."""
 import os
 import subprocess
@@ -19,8 +20,11 @@ COMPOSE_HEADERS = ["compose.h", "compose_k.h"]
 JPEG_LIB = os.path.join(HERE, "librerevst_jpeg.so")
 JPEG_SOURCES = ["jpeg.hip"]
 JPEG_HEADERS = ["jpeg.h", "jpeg_k.h"]
+JPEG_IN_LIB = os.path.join(HERE, "librerevst_jpeg_in.so")
+JPEG_IN_SOURCES = ["jpeg_in.hip"]
+JPEG_IN_HEADERS = ["jpeg_dec.h", "jpeg_dec_k.h", "jpeg.h"]
 STAGES_HEADERS = ["resample_k.h", "deliver_k.h", "guided_k.h", "rs_tile.h", "resample.h", "deliver.h", "guided.h", "conv_thin.h", "conv_mfma.h"]
-HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "resample.h", "deliver.h", "guided.h", "compose.h", "jpeg.h",
+HEADERS = ["conv_mfma.h", "conv_wino.h", "conv_ups5.h", "conv_wino_split.h", "conv_f43.h", "conv_thin.h", "prep_kernels.h", "mask_kernels.h", "resample.h", "deliver.h", "guided.h", "compose.h", "jpeg.h", "jpeg_dec.h",
            "../../include/rerevst_hip.h"]
 
 
@@ -41,7 +45,8 @@ def build_lib(force=False, verbose=True, extra=()):
     stages = force or _newer(STAGES_LIB, STAGES_SOURCES + STAGES_HEADERS)
     compose = force or _newer(COMPOSE_LIB, COMPOSE_SOURCES + COMPOSE_HEADERS)
     jpeg = force or _newer(JPEG_LIB, JPEG_SOURCES + JPEG_HEADERS)
-    if not stages and not compose and not jpeg and not _newer(LIB, SOURCES + HEADERS):
+    jpeg_in = force or _newer(JPEG_IN_LIB, JPEG_IN_SOURCES + JPEG_IN_HEADERS)
+    if not stages and not compose and not jpeg and not jpeg_in and not _newer(LIB, SOURCES + HEADERS):
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-result"]
@@ -51,8 +56,10 @@ def build_lib(force=False, verbose=True, extra=()):
         _run([*common, *[os.path.join(CSRC, s) for s in COMPOSE_SOURCES], "-o", COMPOSE_LIB], verbose)
     if jpeg:
         _run([*common, *[os.path.join(CSRC, s) for s in JPEG_SOURCES], "-o", JPEG_LIB], verbose)
+    if jpeg_in:
+        _run([*common, *[os.path.join(CSRC, s) for s in JPEG_IN_SOURCES], "-o", JPEG_IN_LIB], verbose)
     # the main library finds its companions next to itself, wherever the package lies
-    _run([*common, *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-L" + HERE, "-lrerevst_stages", "-lrerevst_compose", "-lrerevst_jpeg", "-Wl,-rpath,$ORIGIN", "-o", LIB],
+    _run([*common, *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-L" + HERE, "-lrerevst_stages", "-lrerevst_compose", "-lrerevst_jpeg", "-lrerevst_jpeg_in", "-Wl,-rpath,$ORIGIN", "-o", LIB],
          verbose)
     return LIB
 

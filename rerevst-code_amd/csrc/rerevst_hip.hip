@@ -30,7 +30,9 @@
 #include "guided.h"        //                       of the guided delivery stage
 #include "compose.h"       //                       of the compositing stage (librerevst_compose.so)
 #include "deliver.h"       //                       of the output-side resampler
+#include <functional>
 #include "jpeg.h"          // librerevst_jpeg.so: plan, tables, header and the launch entries of the JPEG output stage
+#include "jpeg_dec.h"      // ... and of the JPEG input stage: parser, plan, decode tables and launch entries
 
 namespace {
 
@@ -290,6 +292,18 @@ struct rrv_ctx {
     // lengths and offsets of the entropy half ([2][B][intervals]).  Grow-only; every word read was written by the same call
     int16_t* jp_coef = nullptr; size_t jp_coef_cap = 0;
     uint32_t* jp_idx = nullptr; size_t jp_idx_cap = 0;
+    // the JPEG input entries' scratch (caller's stream too): the frame descriptors and decode tables of a call, the interval starts
+    // ([B][intervals + 1]) and rrv_jpeg_decode_device's coefficient blocks.  Grow-only; every word read was written by the same call
+    JpegDecFrame* jd_frames = nullptr; size_t jd_frames_cap = 0;
+    uint32_t* jd_ivl = nullptr; size_t jd_ivl_cap = 0;
+    int16_t* jd_coef = nullptr; size_t jd_coef_cap = 0;
+    // the from-JPEG transfer entries: the decoded planes the network reads; the host twins' stream slots, statuses, output and matte of a sub-batch
+    uint8_t* jd_planes = nullptr; size_t jd_planes_cap = 0;
+    uint8_t* jd_streams = nullptr; size_t jd_streams_cap = 0;
+    int* jd_status = nullptr; size_t jd_status_cap = 0;
+    uint8_t* jd_out = nullptr; size_t jd_out_cap = 0;
+    uint8_t* jd_matte = nullptr; size_t jd_matte_cap = 0;
+    void* jd_pin = nullptr; size_t jd_pin_cap = 0; hipEvent_t jd_ev = nullptr;      // the descriptors' page-locked staging and the event behind its last copy
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
     // the copies from and to the caller's pageable arrays of consecutive sub-batches overlap
@@ -2202,7 +2216,10 @@ int rrv_destroy(rrv_handle h) {
     for (rrv_ctx::Slot& sl : h->slots)
         for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
     for (float* q : {h->gd_ab, h->gd_q, h->cm_buf}) if (q) (void)hipFree(q);
-    for (void* q : {(void*)h->jp_coef, (void*)h->jp_idx}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)h->jp_coef, (void*)h->jp_idx, (void*)h->jd_frames, (void*)h->jd_ivl, (void*)h->jd_coef, (void*)h->jd_planes, (void*)h->jd_streams,
+                    (void*)h->jd_status, (void*)h->jd_out, (void*)h->jd_matte}) if (q) (void)hipFree(q);
+    if (h->jd_pin) (void)hipHostFree(h->jd_pin);
+    if (h->jd_ev) (void)hipEventDestroy(h->jd_ev);
     for (rrv_ctx::Slot& sl : h->slots)
         for (void* q : {(void*)sl.jp_coef, (void*)sl.jp_idx}) if (q) (void)hipFree(q);
     for (auto& kv : h->rs_tabs) if (kv.second.block) (void)hipFree(kv.second.block);
@@ -4058,6 +4075,356 @@ int rrv_jpeg_encode_device(rrv_handle h, const float* d_in, int B, int H, int W,
     RCHK(jpeg_blocks_launch(h, q, p));
     return jpeg_entropy_launch(h, q, p);
 }
+// ---- JPEG input (include/rerevst_hip.h "JPEG input")
+static_assert(sizeof(rrv_jpeg_info) == sizeof(JpegInfo) && offsetof(rrv_jpeg_info, scan_offset) == offsetof(JpegInfo, scan_offset) &&
+              offsetof(rrv_jpeg_info, q) == offsetof(JpegInfo, q) && offsetof(rrv_jpeg_info, huff_bits) == offsetof(JpegInfo, huff_bits) &&
+              offsetof(rrv_jpeg_info, huff_vals) == offsetof(JpegInfo, huff_vals), "rrv_jpeg_info is jpeg_dec.h's JpegInfo");
+static_assert(RRV_JPEG_ST_DATA == JD_DATA && RRV_JPEG_ST_CODE == JD_CODE && RRV_JPEG_ST_RUN == JD_RUN && RRV_JPEG_ST_CATEGORY == JD_CATEGORY &&
+              RRV_JPEG_ST_MARKER_MISSING == JD_MARKER_MISSING && RRV_JPEG_ST_MARKER_WRONG == JD_MARKER_WRONG && RRV_JPEG_ST_MARKER_SURPLUS == JD_MARKER_SURPLUS,
+              "the status codes of the header are the kernels'");
+int rrv_jpeg_parse(const uint8_t* stream, size_t size, rrv_jpeg_info* info, char* why, size_t why_len) {
+    if (why && why_len) why[0] = 0;
+    if (!info) { jpeg_refuse(why, why_len, "null rrv_jpeg_info"); return RRV_E_ARG; }
+    if (!stream) { jpeg_refuse(why, why_len, "null stream"); return RRV_E_ARG; }
+    return jpeg_parse(stream, size, reinterpret_cast<JpegInfo*>(info), why, why_len) ? RRV_OK : RRV_E_DATA;
+}
+const char* rrv_jpeg_status_words(int status) { return jpeg_status_words(status); }
+// The infos of a call -> the kernels' parameters and the frame descriptors (host), judged before any GPU work.  scan: the call reads streams.
+static int set_jpeg_in(rrv_handle h, const char* who, const rrv_jpeg_info* infos, int B, bool scan, size_t cap, JpegDecP* p, std::vector<JpegDecFrame>* frames) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 1 || B > JP_B_MAX) return fail(h, RRV_E_ARG, w + "batch must be in 1..64");
+    if (!infos) return fail(h, RRV_E_ARG, w + "null rrv_jpeg_info array");
+    const JpegInfo* const f = reinterpret_cast<const JpegInfo*>(infos);
+    if (!jpeg_dec_fill(f[0], p)) return fail(h, RRV_E_ARG, w + "info 0: H, W must be in 1..65535, chroma 400, 420, 422 or 444, interval 0..65535");
+    p->B = B; p->cap = cap; p->n_int_max = 1;
+    frames->resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const std::string wb = w + "info " + std::to_string(b) + ": ";
+        if (f[b].H != f[0].H || f[b].W != f[0].W || f[b].chroma != f[0].chroma)
+            return fail(h, RRV_E_ARG, wb + "a " + std::to_string(f[b].H) + " x " + std::to_string(f[b].W) + " frame, chroma " + std::to_string(f[b].chroma) + ", in a call of " +
+                                          std::to_string(f[0].H) + " x " + std::to_string(f[0].W) + ", chroma " + std::to_string(f[0].chroma) +
+                                          ": the frames of one call share H, W and the chroma format");
+        if (!jpeg_dec_frame(f[b], &(*frames)[(size_t)b]))
+            return fail(h, RRV_E_ARG, wb + "its fields do not hold together (interval, MCU counts, blocks, intervals, scan bytes below 2^32, Huffman specifications): pass what rrv_jpeg_parse filled");
+        if (scan && (f[b].scan_offset > cap || f[b].scan_bytes > cap - f[b].scan_offset))
+            return fail(h, RRV_E_ARG, wb + "cap = " + std::to_string(cap) + " bytes is below the frame's size, " + std::to_string(f[b].scan_offset + f[b].scan_bytes));
+        p->n_int_max = std::max(p->n_int_max, f[b].intervals);
+    }
+    return RRV_OK;
+}
+// the descriptors into the handle's buffer, ordered on the call's stream.  They go through a page-locked buffer of the handle, so the copy is a
+// true asynchronous one whatever the runtime does with pageable memory; an event says when the previous call's copy has left that buffer.
+static int jpeg_in_upload(rrv_handle h, const Seq& q, const std::vector<JpegDecFrame>& frames, JpegDecP* p) {
+    const size_t bytes = frames.size() * sizeof(JpegDecFrame);
+    if (h->jd_ev) HIPCHK(hipEventSynchronize(h->jd_ev));
+    else HIPCHK(hipEventCreateWithFlags(&h->jd_ev, hipEventDisableTiming));
+    if (h->jd_pin_cap < bytes) {
+        if (h->jd_pin) (void)hipHostFree(h->jd_pin);
+        h->jd_pin = nullptr; h->jd_pin_cap = 0;
+        if (hipHostMalloc(&h->jd_pin, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->jd_pin = nullptr; return fail(h, RRV_E_NOMEM, "jpeg input: out of page-locked host memory for the frame descriptors"); }
+        h->jd_pin_cap = bytes;
+    }
+    memcpy(h->jd_pin, frames.data(), bytes);
+    HIPCHK(hipMemcpyAsync(h->jd_frames, h->jd_pin, bytes, hipMemcpyHostToDevice, q.stream));
+    HIPCHK(hipEventRecord(h->jd_ev, q.stream));
+    p->frames = h->jd_frames;
+    p->ivl = h->jd_ivl;
+    return RRV_OK;
+}
+static int jpeg_scan_launch(rrv_handle h, const Seq& q, const JpegDecP& p) {
+    int e = 0;
+    // for the profile log: the slots read once by each of the two kernels at most, the blocks cleared and written
+    RCHK(launch(h, q, "jpeg_scan", 0.0, (2.0 * p.cap + 2.0 * 128.0 * p.blocks) * p.B, [&] { e = rrv_jpeg_scan_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("jpeg_scan: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+static int jpeg_planes_launch(rrv_handle h, const Seq& q, const JpegDecP& p) {
+    int e = 0;
+    // for the profile log: the blocks read, the planes written; one multiply per coefficient and the two 8-point passes at 29 operations each per 8 samples
+    RCHK(launch(h, q, "jpeg_planes", (1.0 + 2.0 * 29.0 / 8.0) * 64.0 * p.blocks * p.B, (128.0 * p.blocks + (double)p.frame_bytes) * p.B, [&] { e = rrv_jpeg_planes_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("jpeg_planes: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+int rrv_jpeg_scan_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int16_t* d_coef, int* d_status, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegDecP p{};
+    std::vector<JpegDecFrame> frames;
+    RCHK(set_jpeg_in(h, "jpeg_scan", infos, B, true, cap, &p, &frames));
+    if (!d_streams || !d_coef) return fail(h, RRV_E_ARG, "jpeg_scan: null buffer");
+    if (!d_status) return fail(h, RRV_E_ARG, "jpeg_scan: null d_status");
+    if ((uintptr_t)d_coef & 15) return fail(h, RRV_E_ARG, "jpeg_scan: d_coef must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(ensure_dev(h, h->jd_frames, h->jd_frames_cap, (size_t)B));
+    RCHK(ensure_dev(h, h->jd_ivl, h->jd_ivl_cap, (size_t)B * (p.n_int_max + 1)));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    p.streams = d_streams; p.coef = d_coef; p.status = d_status;
+    RCHK(jpeg_in_upload(h, q, frames, &p));
+    return jpeg_scan_launch(h, q, p);
+}
+int rrv_jpeg_planes_device(rrv_handle h, const int16_t* d_coef, const rrv_jpeg_info* infos, int B, uint8_t* d_planes, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegDecP p{};
+    std::vector<JpegDecFrame> frames;
+    RCHK(set_jpeg_in(h, "jpeg_planes", infos, B, false, 0, &p, &frames));
+    if (!d_coef || !d_planes) return fail(h, RRV_E_ARG, "jpeg_planes: null buffer");
+    if ((uintptr_t)d_coef & 15) return fail(h, RRV_E_ARG, "jpeg_planes: d_coef must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(ensure_dev(h, h->jd_frames, h->jd_frames_cap, (size_t)B));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    p.coef = const_cast<int16_t*>(d_coef); p.planes = d_planes;
+    RCHK(jpeg_in_upload(h, q, frames, &p));
+    return jpeg_planes_launch(h, q, p);
+}
+int rrv_jpeg_decode_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, uint8_t* d_planes, int* d_status, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    JpegDecP p{};
+    std::vector<JpegDecFrame> frames;
+    RCHK(set_jpeg_in(h, "jpeg_decode", infos, B, true, cap, &p, &frames));
+    if (!d_streams || !d_planes) return fail(h, RRV_E_ARG, "jpeg_decode: null buffer");
+    if (!d_status) return fail(h, RRV_E_ARG, "jpeg_decode: null d_status");
+    HIPCHK(hipSetDevice(h->dev));
+    // every scratch buffer before the first launch: out of memory leaves nothing queued
+    RCHK(ensure_dev(h, h->jd_frames, h->jd_frames_cap, (size_t)B));
+    RCHK(ensure_dev(h, h->jd_ivl, h->jd_ivl_cap, (size_t)B * (p.n_int_max + 1)));
+    RCHK(ensure_dev(h, h->jd_coef, h->jd_coef_cap, (size_t)B * p.blocks * 64));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    p.streams = d_streams; p.coef = h->jd_coef; p.planes = d_planes; p.status = d_status;
+    RCHK(jpeg_in_upload(h, q, frames, &p));
+    RCHK(jpeg_scan_launch(h, q, p));
+    return jpeg_planes_launch(h, q, p);
+}
+// ---- transfers whose INPUT form is JPEG: the decode stage in front of the compositing view entry (or its JPEG-out twin), which reads the planes
+// as the 8-bit I420 / I422 / I444 frames they are.  JFIF's colour space is BT.601 full range whatever matrix the handle holds: the handle's
+// matrix is put aside while the entry queues its launches (a launch keeps the matrix it was queued with) and put back on every way out.
+struct JfifMatrix {
+    rrv_handle h; float keep[12];
+    explicit JfifMatrix(rrv_handle h_) : h(h_) { memcpy(keep, h->yuv_in.m8, sizeof keep); (void)rrv_yuv_input_matrix(RRV_YUV_BT601, 1, h->yuv_in.m8); }
+    ~JfifMatrix() { memcpy(h->yuv_in.m8, keep, sizeof keep); }
+};
+// A from-JPEG call in two steps, so that every check of the decode AND of the transfer behind it runs before anything is queued:
+// jpeg_in_check judges the decode's arguments and builds the frame descriptors on the host, jpeg_in_queue reserves the scratch and queues the
+// decode of the B streams into the handle's planes buffer on `stream`.
+struct JpegInCall { JpegDecP p{}; std::vector<JpegDecFrame> frames; rrv_image_view vin{}; };
+static int jpeg_in_check(rrv_handle h, const char* who, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, const int* d_status, JpegInCall* k) {
+    RCHK(set_jpeg_in(h, who, infos, B, true, cap, &k->p, &k->frames));
+    if (!d_streams) return fail(h, RRV_E_ARG, std::string(who) + ": null buffer");
+    if (!d_status) return fail(h, RRV_E_ARG, std::string(who) + ": null d_status");
+    if (k->p.H < 8 || k->p.W < 8) return fail(h, RRV_E_ARG, std::string(who) + ": frames must be at least 8 x 8 pixels");
+    const int lay = k->p.ncomp == 1 || (k->p.hs == 1 && k->p.vs == 1) ? RRV_LAY_I444 : k->p.vs == 2 ? RRV_LAY_I420 : RRV_LAY_I422;
+    k->vin = contiguous_of(rrv_image_desc{RRV_DT_U8, lay, RRV_SP_PIXEL}, k->p.H, k->p.W);
+    return RRV_OK;
+}
+static int jpeg_in_queue(rrv_handle h, JpegInCall& k, const uint8_t* d_streams, int* d_status, hipStream_t stream) {
+    JpegDecP& p = k.p;
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(ensure_dev(h, h->jd_frames, h->jd_frames_cap, (size_t)p.B));
+    RCHK(ensure_dev(h, h->jd_ivl, h->jd_ivl_cap, (size_t)p.B * (p.n_int_max + 1)));
+    RCHK(ensure_dev(h, h->jd_coef, h->jd_coef_cap, (size_t)p.B * p.blocks * 64));
+    RCHK(ensure_dev(h, h->jd_planes, h->jd_planes_cap, (size_t)p.B * p.frame_bytes));
+    Seq q = base_seq(h);
+    q.stream = stream;
+    p.streams = d_streams; p.coef = h->jd_coef; p.planes = h->jd_planes; p.status = d_status;
+    RCHK(jpeg_in_upload(h, q, k.frames, &p));
+    RCHK(jpeg_scan_launch(h, q, p));
+    return jpeg_planes_launch(h, q, p);
+}
+// the sizes of a from-JPEG request: a working size of 0 x 0 is the source's
+static void jpeg_in_sizes(const rrv_jpeg_info* infos, int work_H, int work_W, int* SH, int* SW, int* H, int* W) {
+    const bool scaled = work_H != 0 || work_W != 0;
+    *SH = scaled ? infos[0].H : 0; *SW = scaled ? infos[0].W : 0;
+    *H = scaled ? work_H : infos[0].H; *W = scaled ? work_W : infos[0].W;
+}
+// The checks the transfer behind the decode will make (those of rrv_transfer_composite_view_device / rrv_transfer_jpeg_view_device through view_run),
+// made here on the same request before the decode is queued: nothing has run when one of them refuses.  out: the output view, or null with j
+// (JPEG out).  *ox receives the request (its OH(), OW(), out_bytes()).
+static int jpeg_in_precheck(rrv_handle h, const char* who, const JpegInCall& k, const rrv_jpeg_info* infos, int B, int work_H, int work_W, int DH, int DW, int r,
+                            float eps, const rrv_composite* c, const rrv_image_view* out, const rrv_jpeg* j, size_t out_cap, int flags, bool host, Xfer* ox) {
+    const std::string w = std::string(who) + ": ";
+    Xfer x{Model::GLOBAL, B, 0, 0};
+    jpeg_in_sizes(infos, work_H, work_W, &x.SH, &x.SW, &x.H, &x.W);
+    x.DH = DH; x.DW = DW;
+    if (r) { x.gr = r; x.geps = eps; }
+    RCHK(set_composite(h, who, c, B, &x));
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | (host ? 0 : RRV_TF_ON_STREAM))) return fail(h, RRV_E_ARG, w + "unknown flags");
+    x.pad = (flags & RRV_TF_PAD_CROP) != 0;
+    if (flags & RRV_TF_FRAME_MODE) x.model = Model::FRAME;
+    if (!parse_in_view(k.vin.desc, &x.in)) return fail(h, RRV_E_ARG, w + "the decoded layout is not an input form");
+    if (out && (!view_desc_ok(out->desc) || parse_out(out->desc, &x.fmt) != DescErr::OK))
+        return fail(h, RRV_E_ARG, w + "out.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (j) {
+        JpegP jp{};
+        RCHK(set_jpeg(h, who, j, 1, x.OH(), x.OW(), true, out_cap, &jp));
+    }
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(check_xfer(h, x));
+    std::string why;
+    if (out && !view_check(*out, B, x.OH(), x.OW(), true, &why)) return fail(h, RRV_E_ARG, w + "out." + why);
+    *ox = x;
+    return RRV_OK;
+}
+int rrv_transfer_from_jpeg_view_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int work_H, int work_W, int DH,
+                                       int DW, int r, float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out, int* d_status, int flags,
+                                       void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!d_out || !out) return fail(h, RRV_E_ARG, "transfer_from_jpeg_view: null output buffer or view");
+    JpegInCall k;
+    Xfer x{Model::GLOBAL, B, 0, 0};
+    RCHK(jpeg_in_check(h, "transfer_from_jpeg_view", d_streams, cap, infos, B, d_status, &k));
+    RCHK(jpeg_in_precheck(h, "transfer_from_jpeg_view", k, infos, B, work_H, work_W, DH, DW, r, eps, c, out, nullptr, 0, flags, false, &x));
+    RCHK(jpeg_in_queue(h, k, d_streams, d_status, (hipStream_t)hip_stream));
+    const JfifMatrix jfif(h);
+    return rrv_transfer_composite_view_device(h, h->jd_planes, &k.vin, B, x.SH, x.SW, x.H, x.W, DH, DW, r, eps, c, d_out, out, flags | RRV_TF_ON_STREAM, hip_stream);
+}
+int rrv_transfer_jpeg_from_jpeg_view_device(rrv_handle h, const uint8_t* d_streams, size_t cap, const rrv_jpeg_info* infos, int B, int work_H, int work_W,
+                                            int DH, int DW, int r, float eps, const rrv_composite* c, const rrv_jpeg* j, uint8_t* d_out, size_t out_cap,
+                                            int* d_sizes, int* d_status, int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!d_out || !d_sizes || !j) return fail(h, RRV_E_ARG, "transfer_jpeg_from_jpeg_view: null output buffer, sizes or rrv_jpeg");
+    JpegInCall k;
+    Xfer x{Model::GLOBAL, B, 0, 0};
+    RCHK(jpeg_in_check(h, "transfer_jpeg_from_jpeg_view", d_streams, cap, infos, B, d_status, &k));
+    RCHK(jpeg_in_precheck(h, "transfer_jpeg_from_jpeg_view", k, infos, B, work_H, work_W, DH, DW, r, eps, c, nullptr, j, out_cap, flags, false, &x));
+    RCHK(jpeg_in_queue(h, k, d_streams, d_status, (hipStream_t)hip_stream));
+    const JfifMatrix jfif(h);
+    return rrv_transfer_jpeg_view_device(h, h->jd_planes, &k.vin, B, x.SH, x.SW, x.H, x.W, DH, DW, r, eps, c, j, d_out, out_cap, d_sizes, flags | RRV_TF_ON_STREAM,
+                                         hip_stream);
+}
+// The host twins: every stream parsed on the host first (a refusal is RRV_E_DATA naming the frame), then sub-batches of up to sixteen frames on
+// the handle's first stream: each frame's own bytes up, the device entry, the statuses and the output back.  One sub-batch at a time: simple, and
+// not the pipeline of the other host entries.  A corrupt frame is RRV_E_DATA naming it; the frames before its sub-batch have been written.
+constexpr int JPEG_IN_SUB = 16;
+// `before` makes the transfer's own checks on the first sub-batch's request once the streams are parsed: nothing has been copied or queued then.
+static int jpeg_in_host(rrv_handle h, const char* who, const uint8_t* const* streams, const size_t* sizes, int B, std::vector<JpegInfo>* infos, size_t* cap,
+                        const std::function<int(int)>& before, const std::function<int(int, int, hipStream_t)>& run) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 1) return fail(h, RRV_E_ARG, w + "batch must be at least 1");
+    if (!streams || !sizes) return fail(h, RRV_E_ARG, w + "null streams or sizes");
+    infos->resize((size_t)B);
+    size_t most = 0;
+    for (int b = 0; b < B; ++b) {
+        char why[200];
+        if (!streams[b]) return fail(h, RRV_E_ARG, w + "stream " + std::to_string(b) + " is null");
+        if (!jpeg_parse(streams[b], sizes[b], &(*infos)[(size_t)b], why, sizeof why)) return fail(h, RRV_E_DATA, w + "frame " + std::to_string(b) + ": " + why);
+        const JpegInfo &f = (*infos)[(size_t)b], &f0 = (*infos)[0];
+        if (f.H != f0.H || f.W != f0.W || f.chroma != f0.chroma)
+            return fail(h, RRV_E_ARG, w + "frame " + std::to_string(b) + " is " + std::to_string(f.H) + " x " + std::to_string(f.W) + ", chroma " + std::to_string(f.chroma) +
+                                          "; frame 0 is " + std::to_string(f0.H) + " x " + std::to_string(f0.W) + ", chroma " + std::to_string(f0.chroma) +
+                                          ": the frames of one call share H, W and the chroma format");
+        most = std::max(most, sizes[b]);
+    }
+    *cap = (most + 15) & ~(size_t)15;
+    const int sub = std::min(B, JPEG_IN_SUB);
+    RCHK(before(sub));
+    HIPCHK(hipSetDevice(h->dev));
+    const hipStream_t s = h->slots[0].stream;
+    RCHK(ensure_dev(h, h->jd_streams, h->jd_streams_cap, (size_t)sub * *cap));
+    RCHK(ensure_dev(h, h->jd_status, h->jd_status_cap, (size_t)sub));
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        for (int b = 0; b < nb; ++b) HIPCHK(hipMemcpyAsync(h->jd_streams + (size_t)b * *cap, streams[b0 + b], sizes[b0 + b], hipMemcpyHostToDevice, s));
+        int rc = run(b0, nb, s);
+        int st[JPEG_IN_SUB] = {0};
+        if (rc == RRV_OK) {
+            HIPCHK(hipMemcpyAsync(st, h->jd_status, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (int b = 0; b < nb; ++b)
+                if (st[b] != JD_OK) return fail(h, RRV_E_DATA, w + "frame " + std::to_string(b0 + b) + " is corrupt: " + jpeg_status_words(st[b]));
+        } else {
+            (void)hipStreamSynchronize(s);      // (the caller's streams are not read after the call returns)
+            return rc;
+        }
+    }
+    return RRV_OK;
+}
+// the checks of a host twin's first sub-batch (jpeg_in_check, jpeg_in_precheck) on host pointers that are only tested for null
+static int jpeg_in_host_precheck(rrv_handle h, const char* who, const uint8_t* const* streams, size_t cap, const std::vector<JpegInfo>& infos, int nb, int work_H,
+                                 int work_W, int DH, int DW, int r, float eps, const rrv_composite* c, const rrv_image_desc* od, const rrv_jpeg* j, size_t out_cap,
+                                 int flags, Xfer* x) {
+    const rrv_jpeg_info* const in = reinterpret_cast<const rrv_jpeg_info*>(infos.data());
+    JpegInCall k;
+    int dummy = 0;
+    RCHK(jpeg_in_check(h, who, streams[0], cap, in, nb, &dummy, &k));
+    rrv_composite part{};
+    if (c) { part = *c; if (c->matte && c->matte_frames != 1) part.matte_frames = nb; }
+    rrv_image_view vo{};
+    if (od) {      // (the view's geometry follows from the request; only the descriptor can be wrong)
+        vo.desc = *od;
+        OutFmt f;
+        if (!view_desc_ok(*od) || parse_out(*od, &f) != DescErr::OK)
+            return fail(h, RRV_E_ARG, std::string(who) + ": out is not a dtype, layout and space combination the descriptor entries accept");
+    }
+    RCHK(jpeg_in_precheck(h, who, k, in, nb, work_H, work_W, DH, DW, r, eps, c ? &part : nullptr, nullptr, j, out_cap, flags, true, x));
+    if (od && parse_out(*od, &x->fmt) != DescErr::OK) return fail(h, RRV_E_ARG, std::string(who) + ": out descriptor");
+    return RRV_OK;
+}
+// a host matte of sub-batch [b0, b0 + nb) in HBM, and the request that names it
+static int jpeg_in_request(rrv_handle h, const rrv_composite* c, int b0, int nb, size_t frame_px, hipStream_t s, rrv_composite* part) {
+    if (!c) return RRV_OK;
+    *part = *c;
+    if (c->strength) part->strength = c->strength + b0;
+    if (c->matte) {
+        const size_t mfb = frame_px * (c->matte_dtype == RRV_DT_U8 ? 1 : 4);
+        const int frames = c->matte_frames == 1 ? 1 : nb;
+        RCHK(ensure_dev(h, h->jd_matte, h->jd_matte_cap, (size_t)frames * mfb));
+        HIPCHK(hipMemcpyAsync(h->jd_matte, (const uint8_t*)c->matte + (c->matte_frames == 1 ? 0 : (size_t)b0 * mfb), (size_t)frames * mfb, hipMemcpyHostToDevice, s));
+        part->matte = h->jd_matte; part->matte_frames = frames;
+    }
+    return RRV_OK;
+}
+int rrv_transfer_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, int work_H, int work_W, int DH, int DW, int r, float eps,
+                           const rrv_composite* c, void* out, rrv_image_desc od, int flags) {
+    if (!h) return RRV_E_ARG;
+    if (!out) return fail(h, RRV_E_ARG, "transfer_from_jpeg: null buffer");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_from_jpeg: unknown flags");
+    std::vector<JpegInfo> infos;
+    size_t cap = 0, ob = 0, opx = 0;
+    rrv_image_view vo{};
+    return jpeg_in_host(h, "transfer_from_jpeg", streams, sizes, B, &infos, &cap, [&](int sub) -> int {
+        Xfer x{Model::GLOBAL, sub, 0, 0};
+        RCHK(jpeg_in_host_precheck(h, "transfer_from_jpeg", streams, cap, infos, sub, work_H, work_W, DH, DW, r, eps, c, &od, nullptr, 0, flags, &x));
+        vo = contiguous_of(od, x.OH(), x.OW());      // the delivered frame, from the first stream's size
+        ob = x.out_bytes(); opx = (size_t)x.OH() * x.OW();
+        return ensure_dev(h, h->jd_out, h->jd_out_cap, (size_t)sub * ob);
+    }, [&](int b0, int nb, hipStream_t s) -> int {
+        const rrv_jpeg_info* const in = reinterpret_cast<const rrv_jpeg_info*>(infos.data()) + b0;
+        rrv_composite part{};
+        RCHK(jpeg_in_request(h, c, b0, nb, opx, s, &part));
+        RCHK(rrv_transfer_from_jpeg_view_device(h, h->jd_streams, cap, in, nb, work_H, work_W, DH, DW, r, eps, c ? &part : nullptr, h->jd_out, &vo, h->jd_status, flags, s));
+        HIPCHK(hipMemcpyAsync((uint8_t*)out + (size_t)b0 * ob, h->jd_out, (size_t)nb * ob, hipMemcpyDeviceToHost, s));
+        return RRV_OK;
+    });
+}
+int rrv_transfer_jpeg_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, int work_H, int work_W, int DH, int DW, int r, float eps,
+                                const rrv_composite* c, const rrv_jpeg* j, uint8_t* out, size_t out_cap, int* out_sizes, int flags) {
+    if (!h) return RRV_E_ARG;
+    if (!out || !out_sizes || !j) return fail(h, RRV_E_ARG, "transfer_jpeg_from_jpeg: null buffer, sizes or rrv_jpeg");
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE)) return fail(h, RRV_E_ARG, "transfer_jpeg_from_jpeg: unknown flags");
+    if (c && c->matte) return fail(h, RRV_E_ARG, "transfer_jpeg_from_jpeg: a matte is not taken by this host entry (the device entry takes one)");
+    std::vector<JpegInfo> infos;
+    size_t cap = 0;
+    const size_t sizes_at = ((size_t)JPEG_IN_SUB * out_cap + 15) & ~(size_t)15;
+    return jpeg_in_host(h, "transfer_jpeg_from_jpeg", streams, sizes, B, &infos, &cap, [&](int sub) -> int {
+        Xfer x{Model::GLOBAL, sub, 0, 0};
+        RCHK(jpeg_in_host_precheck(h, "transfer_jpeg_from_jpeg", streams, cap, infos, sub, work_H, work_W, DH, DW, r, eps, c, nullptr, j, out_cap, flags, &x));
+        return ensure_dev(h, h->jd_out, h->jd_out_cap, sizes_at + JPEG_IN_SUB * sizeof(int));
+    }, [&](int b0, int nb, hipStream_t s) -> int {
+        const rrv_jpeg_info* const in = reinterpret_cast<const rrv_jpeg_info*>(infos.data()) + b0;
+        rrv_composite part{};
+        RCHK(jpeg_in_request(h, c, b0, nb, 0, s, &part));
+        int* const d_sizes = reinterpret_cast<int*>(h->jd_out + sizes_at);
+        RCHK(rrv_transfer_jpeg_from_jpeg_view_device(h, h->jd_streams, cap, in, nb, work_H, work_W, DH, DW, r, eps, c ? &part : nullptr, j, h->jd_out, out_cap, d_sizes,
+                                                     h->jd_status, flags, s));
+        HIPCHK(hipMemcpyAsync(out_sizes + b0, d_sizes, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int b = 0; b < nb; ++b)
+            if (out_sizes[b0 + b] > 0)
+                HIPCHK(hipMemcpyAsync(out + (size_t)(b0 + b) * out_cap, h->jd_out + (size_t)b * out_cap, (size_t)out_sizes[b0 + b], hipMemcpyDeviceToHost, s));
+        return RRV_OK;
+    });
+}
 static bool parse_in_host(const rrv_image_desc& d, InFmt* in);
 // a transfer whose output form is JPEG: the request of rrv_transfer_composite_view_device with the encoder behind it
 static int jpeg_xfer(rrv_handle h, const char* who, int B, int SH, int SW, int H, int W, int DH, int DW, int r, float eps, const rrv_composite* c, int flags,
@@ -4223,6 +4590,39 @@ static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, c
     const int rc = resample_launch(h, q, src, fmt, vi, 1, SH, SW, H, W, h->slots[0].rs_buf);
     if (rc != RRV_OK) { (void)hipStreamSynchronize(q.stream); return rc; }      // (the caller's frame is not read after the call returns)
     return add_frame(h, h->slots[0].rs_buf, true, InFmt{IN_F32_HWC, SP_PIXEL}, q.stream, H, W);      // (synchronises: the frame has been read and compacted)
+}
+// a sampled frame that is a JPEG stream: parsed here, decoded on the handle's stream into the planes buffer and added as the float32 PIXEL frame
+// the resampler makes of the planes with JFIF's matrix (at the stream's own size when work_H = work_W = 0: every tap weight is then 1)
+int rrv_add_from_jpeg(rrv_handle h, const uint8_t* stream, size_t size, int work_H, int work_W) {
+    if (!h) return RRV_E_ARG;
+    if (!stream) return fail(h, RRV_E_ARG, "add_from_jpeg: null stream");
+    JpegInfo info;
+    char why[200];
+    if (!jpeg_parse(stream, size, &info, why, sizeof why)) return fail(h, RRV_E_DATA, std::string("add_from_jpeg: ") + why);
+    HIPCHK(hipSetDevice(h->dev));
+    const size_t cap = (size + 15) & ~(size_t)15;
+    RCHK(ensure_dev(h, h->jd_streams, h->jd_streams_cap, cap));
+    RCHK(ensure_dev(h, h->jd_status, h->jd_status_cap, 1));
+    const hipStream_t s = h->slots[0].stream;
+    HIPCHK(hipMemcpyAsync(h->jd_streams, stream, size, hipMemcpyHostToDevice, s));
+    JpegInCall k;
+    int rc = jpeg_in_check(h, "add_from_jpeg", h->jd_streams, cap, reinterpret_cast<const rrv_jpeg_info*>(&info), 1, h->jd_status, &k);
+    if (rc == RRV_OK) rc = jpeg_in_queue(h, k, h->jd_streams, h->jd_status, s);
+    const rrv_image_view& vin = k.vin;
+    int st = 0;
+    if (rc == RRV_OK) {
+        HIPCHK(hipMemcpyAsync(&st, h->jd_status, sizeof st, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (st != JD_OK) return fail(h, RRV_E_DATA, std::string("add_from_jpeg: the frame is corrupt: ") + jpeg_status_words(st));
+    } else {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    InFmt fmt;
+    if (!parse_in_view(vin.desc, &fmt)) return fail(h, RRV_E_ARG, "add_from_jpeg: the decoded layout is not an input form");
+    const bool scaled = work_H != 0 || work_W != 0;
+    const JfifMatrix jfif(h);
+    return add_scaled(h, h->jd_planes, true, fmt, &vin, s, info.H, info.W, scaled ? work_H : info.H, scaled ? work_W : info.W);
 }
 int rrv_add_scaled_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW, int H, int W, void* hip_stream) {
     if (!h || !d_frame || !in) return RRV_E_ARG;

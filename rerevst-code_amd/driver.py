@@ -132,6 +132,56 @@ class MJPGWriter:
         self.f.close()
 
 
+class MJPGReader:
+    """The JPEG frames of a Motion-JPEG AVI, as bytes: what MJPGWriter writes and what `ffmpeg -c:v mjpeg` writes (whose frames carry no
+    DHT segment: the Annex K tables are implied, and the JPEG input stage takes them so).  Walks the '00dc' chunks of the 'movi' list in file
+    order -- no index is needed or read -- through 'rec ' lists, past JUNK, audio and index chunks and the pad byte behind an odd length.
+    fps comes from the video stream's header (rate / scale), else from the main header's microseconds per frame."""
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, "rb") as f:
+            data = f.read()
+        if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+            raise ValueError("%s is not an AVI file (no RIFF 'AVI ' header)" % path)
+        self.fps, self.width, self.height, self.fourcc = None, None, None, None
+        self.frames = []
+        usec = [0]
+
+        def walk(pos, end, inside):
+            while pos + 8 <= end:
+                cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+                body = pos + 8
+                stop = min(body + size, end)      # (a file cut short: what is there is read)
+                if cid == b"LIST" and size >= 4:
+                    walk(body + 4, stop, data[body:body + 4])
+                elif inside == b"hdrl" and cid == b"avih" and size >= 40:
+                    usec[0], self.width, self.height = struct.unpack("<I", data[body:body + 4])[0], *struct.unpack("<II", data[body + 32:body + 40])
+                elif inside == b"strl" and cid == b"strh" and size >= 28 and data[body:body + 4] == b"vids" and self.fourcc is None:
+                    self.fourcc = data[body + 4:body + 8]
+                    scale, rate = struct.unpack("<II", data[body + 20:body + 28])
+                    if scale and rate:
+                        self.fps = rate / scale
+                elif inside in (b"movi", b"rec ") and cid[2:4] == b"dc" and cid[:2].isdigit():
+                    if stop > body:      # (an empty chunk is a dropped frame: nothing to decode)
+                        self.frames.append(data[body:stop])
+                pos = body + size + (size & 1)
+
+        walk(12, len(data), b"AVI ")
+        if self.fps is None and usec[0]:
+            self.fps = 1e6 / usec[0]
+        if self.fourcc is not None and self.fourcc.upper() not in (b"MJPG", b"JPEG", b"\0\0\0\0"):
+            raise ValueError("%s holds %r video, not Motion-JPEG" % (path, self.fourcc.decode("latin-1")))
+        if not self.frames:
+            raise ValueError("%s holds no video frames ('00dc' chunks in a 'movi' list)" % path)
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __iter__(self):
+        return iter(self.frames)
+
+
 def fps_fraction(fps):
     """A frame rate as the fraction a Y4M header wants: 24 -> (24, 1), 23.976 -> (24000, 1001) (the NTSC rates), else the nearest
     fraction with a denominator up to 1000."""
@@ -423,7 +473,7 @@ def mux_video_from_files(paths, video_path, fps, pool, quality=95, yuv=("bt601",
 
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
-                  chroma="420", work_size=None, out_size=None, guided=None, composite=None, gpu_jpeg=None):
+                  chroma="420", work_size=None, out_size=None, guided=None, composite=None, gpu_jpeg=None, gpu_decode=False, frame_data=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -448,7 +498,11 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     strength= / matte= / keep=); strengths and mattes go by the absolute frame number.  Needs a model with transfer_frames(strength=).
     gpu_jpeg=dict(quality=, chroma=): the frames are encoded as baseline JPEG on the GPU (transfer_frames with out_format="jpeg"; one rank).  The
     chunks of an .avi video_path and the frame files, written as <name>.jpg, are those bytes, unchanged: with write_frames=False no pixel reaches
-    the host.  Needs a model with jpeg_output (Stylization); not with a .y4m video_path."""
+    the host.  Needs a model with jpeg_output (Stylization); not with a .y4m video_path.
+    gpu_decode: the frames are baseline JPEG streams -- .jpg / .jpeg files read as bytes on the worker threads, or frame_data, a list of bytes that
+    stands for the files (the chunks of an MJPG AVI; frame_paths then only name the outputs) -- decoded on the GPU (transfer_frames / add with
+    in_format="jpeg"; one rank), the sampled frames of the preparation pass included.  Every header is parsed before anything is written: a
+    stream the parser refuses is a ValueError that names the file and the reason.  With gpu_jpeg and write_frames=False no pixel is on the host."""
     import importlib
     import time
     from collections import deque
@@ -471,6 +525,30 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             raise ValueError("gpu_jpeg runs on one rank")
         if getattr(model, "jpeg_output", False) is not True or getattr(model, "transfer_frames", None) is None:
             raise ValueError("gpu_jpeg needs a model with transfer_frames(out_format=\"jpeg\")")
+    jpeg_sizes = None
+    if gpu_decode or frame_data is not None:
+        if world > 1:
+            raise ValueError("gpu_decode runs on one rank")
+        if getattr(model, "jpeg_input", False) is not True or getattr(model, "transfer_frames", None) is None:
+            raise ValueError("gpu_decode needs a model with transfer_frames(in_format=\"jpeg\")")
+        if frame_data is not None and len(frame_data) != n:
+            raise ValueError("frame_data holds %d streams for %d frame names" % (len(frame_data), n))
+        jpeg_info = importlib.import_module("rerevst-code_amd.framework").jpeg_info
+
+        def stream_of(i):                      # the bytes of frame i
+            if frame_data is not None:
+                return frame_data[i]
+            with open(frame_paths[i], "rb") as f:
+                return f.read()
+        jpeg_sizes = []
+        for i, p in enumerate(frame_paths):
+            if frame_data is None and not p.lower().endswith((".jpg", ".jpeg")):
+                raise ValueError("gpu_decode reads .jpg / .jpeg frame files: %s is not one" % p)
+            try:
+                info = jpeg_info(stream_of(i))      # (the whole file: EXIF thumbnails and ICC profiles can put SOS far in; the workers read it again)
+            except ValueError as e:
+                raise ValueError("%s: %s" % (p, e)) from None
+            jpeg_sizes.append((info["H"], info["W"]))
     chroma = check_chroma(chroma, y4m)
     bit_depth = int(bit_depth) if y4m else 8
     yuv_fmt, yuv_dtype = y4m_format(chroma, bit_depth), (np.uint8 if bit_depth == 8 else np.uint16)
@@ -499,8 +577,12 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 ids = video.sample_indices(n)
                 log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
                 model.clean()
-                for f in pool.map(read_image_bgr, [frame_paths[i] for i in ids]):
-                    model.add(f, **add_kw)
+                if jpeg_sizes is not None:
+                    for data in pool.map(stream_of, ids):
+                        model.add(data, in_format="jpeg", **add_kw)
+                else:
+                    for f in pool.map(read_image_bgr, [frame_paths[i] for i in ids]):
+                        model.add(f, **add_kw)
                 model.compute()
                 if world > 1:
                     blob = model.get_state()
@@ -549,7 +631,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             # The reference reshapes every frame on its own (generate_real_video.py:152-171) and so accepts a list of mixed
             # sizes; the batched entry needs equal sizes per call.  The headers are read up front (no decode) and the chunks
             # are cut from RUNS of equally sized frames: a uniform video is one run, a mixed list degrades to shorter chunks.
-            sizes = list(pool.map(image_size, frame_paths[lo:hi]))          # (H, W) per frame of this shard
+            sizes = jpeg_sizes[lo:hi] if jpeg_sizes is not None else list(pool.map(image_size, frame_paths[lo:hi]))          # (H, W) per frame of this shard
             pkg_empty = getattr(importlib.import_module("rerevst-code_amd"), "pinned_empty", None)
             nbuf = 3
             chunk = max(1, min(int(chunk), hi - lo))
@@ -561,7 +643,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     chunks.append([i])
             biggest = max(h * w for h, w in sizes)
             biggest_out = max(h * w for h, w in map(out_size, sizes))
-            in_flat = [_host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
+            in_flat = [[None] * chunk if jpeg_sizes is not None else _host_buffer(pkg_empty, (chunk * biggest * 3,), np.uint8) for _ in range(nbuf)]
             if jpeg_direct:
                 out_flat = None
             elif direct:
@@ -571,7 +653,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
 
             def views(k):                        # chunk k's input / output slots: [frames][H][W][3] views of buffer set k % nbuf ([frames][bytes] of I420)
                 (H, W), m = sizes[chunks[k][0] - lo], len(chunks[k])
-                src = in_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)
+                src = in_flat[k % nbuf] if jpeg_sizes is not None else in_flat[k % nbuf][:m * H * W * 3].reshape(m, H, W, 3)      # (JPEG streams: a list of bytes)
                 OH, OW = out_size((H, W))
                 if jpeg_direct:
                     return src, None
@@ -598,6 +680,9 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                             f.write(data)
             vpool = ThreadPoolExecutor(1) if direct or jpeg_direct else None
 
+            def load_stream(i, dst, j):          # worker: the file's bytes; the GPU decodes them
+                dst[j] = stream_of(i)
+
             def load(path, dst):                 # worker: decode straight into the page-locked input slot
                 img = read_image_bgr(path)
                 if img.shape != dst.shape:
@@ -610,7 +695,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
             def submit_decode(k):
                 if k < len(chunks) and k not in dec:
                     dst = views(k)[0]
-                    dec[k] = [pool.submit(load, frame_paths[i], dst[j]) for j, i in enumerate(chunks[k])]
+                    dec[k] = [pool.submit(load_stream, i, dst, j) if jpeg_sizes is not None else pool.submit(load, frame_paths[i], dst[j]) for j, i in enumerate(chunks[k])]
             submit_decode(0); submit_decode(1)
             for k, idx in enumerate(chunks):
                 for f in dec.pop(k):
@@ -619,7 +704,12 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     f.result()
                 t0 = time.perf_counter()
                 src, dst = views(k)
-                call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, out_size(src.shape[1:3])))
+                src_hw = sizes[idx[0] - lo]
+                if jpeg_sizes is not None:
+                    src = list(src[:len(idx)])
+                call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, out_size(src_hw)))
+                if jpeg_sizes is not None:
+                    call_kw = dict(call_kw, in_format="jpeg")
                 if jpeg_direct:
                     jkw = dict(call_kw, out_format="jpeg", jpeg_quality=gpu_jpeg.get("quality", 95), jpeg_chroma=gpu_jpeg.get("chroma", "420"))
                     try:
@@ -627,7 +717,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     except ValueError as e:      # a frame beyond the default two bytes per pixel: once more with room for any frame
                         if "jpeg_cap" not in str(e):
                             raise
-                        plan = importlib.import_module("rerevst-code_amd.framework").jpeg_plan(*out_size(src.shape[1:3]), jkw["jpeg_chroma"])
+                        plan = importlib.import_module("rerevst-code_amd.framework").jpeg_plan(*out_size(src_hw), jkw["jpeg_chroma"])
                         styled = on_device(src, jpeg_cap=plan["bound"], **jkw)
                 else:
                     styled = on_device(src, out=dst, out_format=yuv_fmt, **call_kw) if direct else on_device(src, out=dst, **call_kw)
@@ -637,11 +727,11 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 if jpeg_direct:
                     paths = [os.path.join(out_dir, os.path.splitext(os.path.basename(frame_paths[i]))[0] + ".jpg") for i in idx] if write_frames else []
                     written.extend(paths)
-                    enc[k % nbuf] = [vpool.submit(append_jpegs, styled, out_size(src.shape[1:3]) + (3,), paths)]
+                    enc[k % nbuf] = [vpool.submit(append_jpegs, styled, out_size(src_hw) + (3,), paths)]
                     log("stylized frames %d..%d of %d" % (idx[0], idx[-1], n))
                     continue
                 if direct:
-                    enc[k % nbuf] = [vpool.submit(append_chunk, styled, out_size(src.shape[1:3]))]
+                    enc[k % nbuf] = [vpool.submit(append_chunk, styled, out_size(src_hw))]
                     log("stylized frames %d..%d of %d" % (idx[0], idx[-1], n))
                     continue
                 for j, i in enumerate(idx):
@@ -669,6 +759,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 raise ValueError("strength / fade / matte / keep need a model with transfer_frames(strength=)")
             if gpu_jpeg is not None and hi > lo:
                 raise ValueError("gpu_jpeg needs a model with transfer_frames(out_format=\"jpeg\")")
+            if jpeg_sizes is not None and hi > lo:
+                raise ValueError("gpu_decode needs a model with transfer_frames(in_format=\"jpeg\")")
             tool = video.ReshapeTool()
             pending = deque()
             look = deque(pool.submit(read_image_bgr, frame_paths[i]) for i in range(lo, min(hi, lo + 2 * nthreads)))
@@ -1098,7 +1190,20 @@ def main(argv=None, model_factory=None):
                     "--video x.avi and the frame files, written as <name>.jpg, are the GPU's bytes; with --no-frames no pixel reaches the host")
     ap.add_argument("--jpeg-quality", type=int, default=95, metavar="Q", help="quality of --gpu-jpeg, 1..100 (default 95, what the .avi path uses)")
     ap.add_argument("--jpeg-chroma", choices=("420", "422", "444"), default="420", help="chroma subsampling of --gpu-jpeg (default 420)")
+    ap.add_argument("--gpu-decode", action="store_true", help="the content frames are .jpg / .jpeg files: read them as bytes and decode them on the GPU (one GPU, "
+                    "one style; baseline JPEG, refused in words otherwise).  --frames in.avi (Motion-JPEG) implies it")
     args = ap.parse_args(argv)
+    avi_in = args.frames.lower().endswith(".avi")
+    if avi_in or args.gpu_decode:
+        what = "--frames in.avi" if avi_in else "--gpu-decode"
+        if len(args.style) > 1 or args.gpus > 1:
+            ap.error("%s runs the single-style flow on one GPU (--gpus %d, %d styles)" % (what, args.gpus, len(args.style)))
+        if not avi_in:
+            if is_y4m(args.frames):
+                ap.error("--gpu-decode reads .jpg / .jpeg frame files: a .y4m input needs no codec")
+            other = [p for p in sorted(glob.glob(args.frames)) if not p.lower().endswith((".jpg", ".jpeg"))]
+            if other:
+                ap.error("--gpu-decode reads .jpg / .jpeg frame files: %s is not one (%d of the files --frames matches are not)" % (other[0], len(other)))
     gpu_jpeg = None
     if args.gpu_jpeg:
         if is_y4m(args.video):
@@ -1159,6 +1264,14 @@ def main(argv=None, model_factory=None):
         ap.error("--gpus N with a .y4m input is not supported: a .y4m is stylized on one GPU")
     if y4m_in and len(args.style) > 1:
         ap.error("multi-style interpolation with a .y4m input is not supported: the cached-feature entries read image files")
+    avi_frames = None
+    if avi_in:
+        try:
+            avi_frames = MJPGReader(args.frames)
+        except (OSError, ValueError) as e:
+            ap.error(str(e))
+        if args.fps is None and avi_frames.fps:
+            args.fps = avi_frames.fps
     if not y4m_in and args.fps is None:
         args.fps = 24
     for sp in args.style:
@@ -1211,10 +1324,26 @@ def main(argv=None, model_factory=None):
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
     else:
-        stylize_files(model, args.style[0], list_frames(args.frames), args.out, args.video, args.fps, chunk=args.chunk, log=log,
-                      io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
-                      write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
-                      out_size=out_size, guided=guided, composite=composite, **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}))
+        decode_kw = {}
+        if avi_frames is not None:      # the AVI's chunks stand for the frame files; the names are those of the outputs
+            stem = os.path.splitext(os.path.basename(args.frames))[0]
+            frame_list = ["%s_%06d.jpg" % (stem, i) for i in range(len(avi_frames))]
+            decode_kw = dict(gpu_decode=True, frame_data=list(avi_frames))
+        else:
+            frame_list = list_frames(args.frames)
+            if args.gpu_decode:
+                decode_kw = dict(gpu_decode=True)
+        try:
+            stylize_files(model, args.style[0], frame_list, args.out, args.video, args.fps, chunk=args.chunk, log=log,
+                          io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
+                          write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
+                          out_size=out_size, guided=guided, composite=composite, **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}), **decode_kw)
+        except ValueError as e:
+            if not decode_kw:
+                raise
+            if hasattr(model, "close"):
+                model.close()
+            sys.exit("error: %s" % e)      # (a stream the parser refuses: the file and the reason, before any frame is written)
     if stats:
         print("[rank %d] %d frames in %.2f s = %.1f frames/s file -> file (%d I/O threads; GPU calls %.2f s; preparation %.2f s)"
               % (rank, stats["frames"], stats["frames_s"], stats["frames_per_s"], stats["io_threads"], stats["gpu_call_s"], stats["prep_s"]), flush=True)

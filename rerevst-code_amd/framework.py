@@ -604,6 +604,70 @@ def jpeg_frames(data, sizes):
     return [data[b, :int(n)].tobytes() for b, n in enumerate(sizes)]
 
 
+# ===== JPEG input (rrv_jpeg_parse and the decode entries; include/rerevst_hip.h "JPEG input" states the streams taken and the arithmetic) =====
+JPEG_IN_LAYOUTS = {400: "i444", 420: "i420", 422: "i422", 444: "i444"}      # the YUV layout a decoded frame has (grey: chroma planes of 128)
+
+
+def _jpeg_parse(data, what="data"):
+    """the rrv_jpeg_info of one stream; a stream the parser refuses raises ValueError with the library's words"""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError("%s must be bytes (one baseline JPEG stream), got %s" % (what, type(data).__name__))
+    data = bytes(data)
+    info, why = _lib.JpegInfo(), C.create_string_buffer(256)
+    rc = _lib.load().rrv_jpeg_parse(C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(info), why, len(why))
+    if rc != 0:
+        raise ValueError("%s is not a JPEG stream this stage takes: %s" % (what, why.value.decode() or "rrv_jpeg_parse failed with %d" % rc))
+    return info
+
+
+def jpeg_info(data):
+    """What rrv_jpeg_parse reads from the header of one baseline JPEG stream (no GPU): dict(H, W, chroma 400 / 420 / 422 / 444, components,
+    interval (0: none), mcu_cols, mcu_rows, blocks, intervals, scan_offset, scan_bytes, q: uint8 [components][64] natural order, huff_dc,
+    huff_ac: the specification each component uses, huff_given: the stream has DHT segments, huff: {"dc0", "dc1", "ac0", "ac1": (bits, vals)}).
+    A stream the stage does not take raises ValueError with the reason."""
+    f = _jpeg_parse(data)
+    nc = f.components
+    d = {k: int(getattr(f, k)) for k in ("H", "W", "chroma", "components", "interval", "mcu_cols", "mcu_rows", "blocks", "intervals", "scan_offset", "scan_bytes")}
+    d["q"] = np.array([list(f.q[c]) for c in range(nc)], np.uint8)
+    d["huff_dc"], d["huff_ac"] = [int(f.huff_dc[c]) for c in range(nc)], [int(f.huff_ac[c]) for c in range(nc)]
+    d["huff_given"] = bool(f.huff_given)
+    d["huff"] = {}
+    for k, name in enumerate(("dc0", "dc1", "ac0", "ac1")):
+        bits = [int(v) for v in f.huff_bits[k]]
+        d["huff"][name] = (bits, [int(v) for v in f.huff_vals[k][:sum(bits)]])
+    return d
+
+
+def jpeg_status_words(status):
+    """the words of a d_status value of the decode entries (rrv_jpeg_status_words)"""
+    return _lib.load().rrv_jpeg_status_words(int(status)).decode()
+
+
+def _jpeg_streams(streams):
+    """a list of bytes -> (JpegInfo array, uint8 ndarray [B][cap] with frame b's bytes at the start of row b, cap)"""
+    if isinstance(streams, (bytes, bytearray, memoryview)) or len(streams) < 1:
+        raise ValueError("expected a non-empty list of bytes, one baseline JPEG stream per frame")
+    infos = (_lib.JpegInfo * len(streams))()
+    for b, s in enumerate(streams):
+        infos[b] = _jpeg_parse(s, "stream %d" % b)
+        if (infos[b].H, infos[b].W, infos[b].chroma) != (infos[0].H, infos[0].W, infos[0].chroma):
+            raise ValueError("stream %d is %d x %d, chroma %d; stream 0 is %d x %d, chroma %d: the frames of one call share H, W and the chroma format"
+                             % (b, infos[b].H, infos[b].W, infos[b].chroma, infos[0].H, infos[0].W, infos[0].chroma))
+    cap = (max(len(s) for s in streams) + 15) & ~15
+    host = np.zeros((len(streams), cap), np.uint8)
+    for b, s in enumerate(streams):
+        host[b, :len(s)] = np.frombuffer(bytes(s), np.uint8)
+    return infos, host, cap
+
+
+def _jpeg_statuses(status):
+    """a decode call's statuses, read on the host: a corrupt frame raises ValueError naming its index and the reason"""
+    st = status.cpu().numpy()
+    bad = [(b, int(v)) for b, v in enumerate(st) if v != 0]
+    if bad:
+        raise ValueError("JPEG frame %d is corrupt: %s (frames that failed: %s)" % (bad[0][0], jpeg_status_words(bad[0][1]), [b for b, _ in bad]))
+
+
 # ===== scaling (the rrv_*_scaled* entries; include/rerevst_hip.h "Scaling" states the arithmetic) =====
 def _work_size(work_size):
     """(H, W) of a work_size= keyword: the size the frames are resampled to on the GPU, and the size of the delivered frame"""
@@ -852,6 +916,8 @@ class Stylization():
     yuv_output = True
     # transfer_batch / transfer_frames take out_format="jpeg" (rrv_transfer_jpeg): driver.stylize_files asks for it with gpu_jpeg=
     jpeg_output = True
+    # transfer_batch / transfer_frames / add take in_format="jpeg" (rrv_transfer_from_jpeg, rrv_add_from_jpeg): driver.stylize_files asks for it with gpu_decode=
+    jpeg_input = True
     # transfer_batch / transfer_frames / add take in_format="i420" | "nv12" with size=(H, W) (the rrv_*_from_yuv entries): driver.stylize_y4m
     # feeds a .y4m input that way
     yuv_input = True
@@ -925,6 +991,19 @@ class Stylization():
         size= stays the size of the frame as passed."""
         self._global_only("add")
         work = None if work_size is None else _work_size(work_size)
+        if in_format == "jpeg":      # (rrv_add_from_jpeg: one stream, or a list of them; the size comes from the stream)
+            if size is not None:
+                raise ValueError('in_format="jpeg": the size comes from the streams, size= does not apply')
+            work = _work_size(work_size) if work_size is not None else (0, 0)
+            for data in ([patch] if isinstance(patch, (bytes, bytearray, memoryview)) else patch):
+                data = bytes(data)
+                try:
+                    self._chk(self._lib.rrv_add_from_jpeg(self._h, data, len(data), *work))
+                except RRVError as e:
+                    if getattr(e, "code", 0) == _lib.E_DATA:
+                        raise ValueError(str(e)) from None
+                    raise
+            return
         if in_format != "bgr":
             a, H, W = yuv_frames_args(patch, in_format, size)
             self._yuv_depth(in_format)
@@ -1168,6 +1247,9 @@ class Stylization():
         yuv_in, yuv_out = in_format != "bgr", out_format != "bgr"
         if yuv_out and out_format not in YUV_FORMATS:
             raise ValueError("out_format must be 'bgr', %s, got %r" % (YUV_FORMAT_NAMES, out_format))
+        if in_format == "jpeg":
+            return self._host_from_jpeg(frames, out, dtype, style_weights, style_masks, pad_crop, out_format, j if is_jpeg else None, jpeg, size, work_size,
+                                        out_size, guide, guide_radius, guide_eps, strength, matte, keep)
         if yuv_in:
             a, H, W = yuv_frames_args(frames, in_format, size)
         else:
@@ -1234,6 +1316,52 @@ class Stylization():
         self._chk(getattr(self._lib, name)(self._h, *args))
         return out
 
+    def _host_from_jpeg(self, streams, out, dtype, style_weights, style_masks, pad_crop, out_format, j, jpeg, size, work_size, out_size, guide, guide_radius,
+                        guide_eps, strength, matte, keep):
+        """in_format="jpeg" of transfer_batch / transfer_frames (rrv_transfer_from_jpeg, rrv_transfer_jpeg_from_jpeg): `streams` a list of bytes,
+        one baseline JPEG stream per frame; the size comes from the streams.  j: the rrv_jpeg of out_format="jpeg", else None."""
+        _jpeg_alone(style_weights, style_masks, 'in_format="jpeg"')
+        if size is not None:
+            raise ValueError('in_format="jpeg": the size comes from the streams, size= does not apply')
+        if isinstance(streams, (bytes, bytearray, memoryview)) or len(streams) < 1 or not all(isinstance(s, (bytes, bytearray, memoryview)) for s in streams):
+            raise ValueError('in_format="jpeg": frames must be a non-empty list of bytes, one baseline JPEG stream per frame')
+        streams = [bytes(s) for s in streams]
+        f = _jpeg_parse(streams[0], "frame 0")
+        B, H, W = len(streams), f.H, f.W
+        for b in range(1, B):      # (the library parses them again; a stream it would refuse, or another size, is a ValueError here, before any GPU work)
+            g = _jpeg_parse(streams[b], "frame %d" % b)
+            if (g.H, g.W, g.chroma) != (f.H, f.W, f.chroma):
+                raise ValueError("frame %d is %d x %d, chroma %d; frame 0 is %d x %d, chroma %d: the frames of one call share H, W and the chroma format"
+                                 % (b, g.H, g.W, g.chroma, f.H, f.W, f.chroma))
+        WH = WW = 0
+        if out_size is not None:
+            DH, DW = _out_size(out_size, (H, W))
+        if work_size is not None:
+            H, W = WH, WW = _work_size(work_size)
+        Ho, Wo = (DH, DW) if out_size is not None else _stylized_size(H, W, pad_crop)
+        comp = _composite_args(strength, matte, keep, None, None, B, Ho, Wo)
+        r, eps = _guide_args(guide, guide_radius, guide_eps, out_size) if guide is not None else (0, 0.0)
+        req = comp.request(0, B) if comp is not None else None
+        ptrs, sizes = (C.c_char_p * B)(*streams), (C.c_size_t * B)(*[len(s) for s in streams])
+        head = (self._h, ptrs, sizes, B, WH, WW, *((DH, DW) if out_size is not None else (0, 0)), r, eps, C.byref(req) if req is not None else None)
+        try:
+            if j is not None:
+                cap = jpeg_slot_bytes(Ho, Wo, jpeg[1], jpeg[2], jpeg[3])
+                data, osz = np.empty((B, cap), np.uint8), np.zeros(B, np.int32)
+                self._chk(self._lib.rrv_transfer_jpeg_from_jpeg(*head, C.byref(j), data.ctypes.data_as(C.c_void_p), cap, osz.ctypes.data_as(C.c_void_p), self._flags(pad_crop)))
+                return jpeg_frames(data, osz)
+            yuv_out = out_format != "bgr"
+            out, u8 = _output((B, Ho, Wo, 3), dtype, out, out_format)
+            self._yuv_depth(None, out_format)
+            desc = _lib.ImageDesc(_lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32,
+                                  YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+            self._chk(self._lib.rrv_transfer_from_jpeg(*head, out.ctypes.data_as(C.c_void_p), desc, self._flags(pad_crop)))
+            return out
+        except RRVError as e:
+            if getattr(e, "code", 0) == _lib.E_DATA:      # a refused or corrupt stream: the library's words
+                raise ValueError(str(e)) from None
+            raise
+
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None,
                        jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
@@ -1284,7 +1412,12 @@ class Stylization():
         output") and a list of B `bytes` comes back, each a complete .jpg file: jpeg_quality 1..100, jpeg_chroma "420" | "422" | "444",
         jpeg_restart the MCUs per restart interval (None: one MCU row), jpeg_cap the bytes reserved per frame (None: two per delivered pixel
         plus the header; a frame that does not fit raises a ValueError that names jpeg_cap).  It combines with work_size, out_size, guide,
-        strength / matte / keep and in_format; not with style_weights / style_masks, out= or dtype=."""
+        strength / matte / keep and in_format; not with style_weights / style_masks, out= or dtype=.
+        in_format="jpeg": `frames` is a list of `bytes`, one baseline JPEG stream per frame, all of one size and chroma format, decoded on the
+        GPU (rrv_transfer_from_jpeg / rrv_transfer_jpeg_from_jpeg; include/rerevst_hip.h "JPEG input"); the size comes from the streams
+        (size= is refused), the colour space is JFIF's whatever set_yuv_input_matrix holds, and it combines with work_size, out_size, guide,
+        strength / matte / keep, every out_format (no matte with out_format="jpeg") and dtype; not with style_weights / style_masks.  A
+        stream the parser refuses or a corrupt frame raises ValueError with the frame's index and the library's words."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size, guide,
                                  guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
 
@@ -1308,7 +1441,8 @@ class Stylization():
         out_size=(DH, DW) or "source": as in transfer_batch; the cropped H x W frame is what gets resampled to DH x DW.
         guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size.
         strength / matte / keep: compositing with the frames as passed, as in transfer_batch; any working size.
-        out_format="jpeg" with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap: a list of `bytes`, as in transfer_batch."""
+        out_format="jpeg" with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap: a list of `bytes`, as in transfer_batch.
+        in_format="jpeg": a list of `bytes` in, as in transfer_batch."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size, guide,
                                  guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
 
@@ -1579,6 +1713,62 @@ class Stylization():
         for _, nb, p, q, sz in _chunks(B, (yb.data_ptr(), yb.stride(0) * 4), (data.data_ptr(), cap), (sizes.data_ptr(), 4)):
             self._chk(self._lib.rrv_jpeg_encode_device(self._h, p, nb, H, W, C.byref(j), q, cap, sz, self._stream(yb)))
         return data, sizes
+
+    def jpeg_coefficients_tensor(self, streams, *, check=True, return_status=False):
+        """The entropy half of the JPEG input stage alone (rrv_jpeg_scan_device; include/rerevst_hip.h "JPEG input"): a list of bytes, one
+        baseline JPEG stream per frame, all of one size and chroma format -> the int16 tensor [B][blocks][64] of their coefficient blocks
+        (zigzag order, scan order) on the handle's GPU, in stream order.  check: read the statuses back and raise ValueError for a corrupt
+        frame; return_status: (coef, int32 [B] status tensor) instead, nothing read back."""
+        return self._jpeg_in(streams, False, check, return_status)
+
+    def decode_jpeg_tensor(self, streams, *, check=True, return_status=False):
+        """The JPEG input stage alone (rrv_jpeg_decode_device): a list of bytes, one baseline JPEG stream per frame, all of one size and chroma
+        format -> (uint8 tensor [B][frame_bytes] of planar frames on the handle's GPU, layout name "i420" | "i422" | "i444") in stream order:
+        what transfer_tensor(.., layout=name, size=(H, W)) reads, with rrv_yuv_input_matrix(BT.601, full range) as JFIF's colour space.  A
+        grey stream gives an "i444" frame whose chroma planes hold 128.  check / return_status as in jpeg_coefficients_tensor."""
+        return self._jpeg_in(streams, True, check, return_status)
+
+    def _jpeg_in(self, streams, planes, check, return_status):
+        import torch
+        infos, host, cap = _jpeg_streams(streams)
+        B, f = len(streams), infos[0]
+        dev = torch.device("cuda", self.device)
+        d = torch.from_numpy(host).to(dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        if planes:
+            hs, vs = (2 if f.chroma in (420, 422) else 1), (2 if f.chroma == 420 else 1)
+            step = f.H * f.W + 2 * (-(-f.H // vs)) * (-(-f.W // hs))
+            out = torch.empty((B, step), dtype=torch.uint8, device=dev)
+        else:
+            step = f.blocks * 128
+            out = torch.empty((B, f.blocks, 64), dtype=torch.int16, device=dev)
+        fn = self._lib.rrv_jpeg_decode_device if planes else self._lib.rrv_jpeg_scan_device
+        for b0, nb, p, q, st in _chunks(B, (d.data_ptr(), cap), (out.data_ptr(), step), (status.data_ptr(), 4)):
+            sub = (_lib.JpegInfo * nb)(*infos[b0:b0 + nb])
+            self._chk(fn(self._h, p, cap, sub, nb, q, st, self._stream(d)))
+        if return_status:
+            return (out, JPEG_IN_LAYOUTS[f.chroma], status) if planes else (out, status)
+        if check:
+            _jpeg_statuses(status)
+        return (out, JPEG_IN_LAYOUTS[f.chroma]) if planes else out
+
+    def jpeg_planes_tensor(self, coef, streams):
+        """The pixel half alone (rrv_jpeg_planes_device): coef an int16 tensor [B][blocks][64] as jpeg_coefficients_tensor returns it for
+        `streams` (which give the size and the quantisers) -> (uint8 planes tensor, layout name) as decode_jpeg_tensor returns them."""
+        import torch
+        infos, _, _ = _jpeg_streams(streams)
+        B, f = len(streams), infos[0]
+        if not isinstance(coef, torch.Tensor) or coef.dtype != torch.int16 or tuple(coef.shape) != (B, f.blocks, 64):
+            raise ValueError("coef must be an int16 tensor [%d][%d][64] for these streams" % (B, f.blocks))
+        _on_device(coef, "coef", self.device)
+        cb = coef.contiguous()
+        hs, vs = (2 if f.chroma in (420, 422) else 1), (2 if f.chroma == 420 else 1)
+        step = f.H * f.W + 2 * (-(-f.H // vs)) * (-(-f.W // hs))
+        out = torch.empty((B, step), dtype=torch.uint8, device=cb.device)
+        for b0, nb, p, q in _chunks(B, (cb.data_ptr(), f.blocks * 128), (out.data_ptr(), step)):
+            sub = (_lib.JpegInfo * nb)(*infos[b0:b0 + nb])
+            self._chk(self._lib.rrv_jpeg_planes_device(self._h, p, sub, nb, q, self._stream(cb)))
+        return out, JPEG_IN_LAYOUTS[f.chroma]
 
     def _guide_tensor(self, g, name, shape, batched):
         """a guide of deliver_tensor as a contiguous float32 [B,H,W,3] tensor on the handle's GPU"""
