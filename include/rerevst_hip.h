@@ -983,6 +983,48 @@ int rrv_add_from_jpeg(rrv_handle h, const uint8_t* stream, size_t size, int work
 int rrv_transfer_jpeg_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, int work_H, int work_W, int DH, int DW, int r,
                                 float eps, const rrv_composite* c, const rrv_jpeg* p, uint8_t* out, size_t out_cap, int* out_sizes, int flags);
 
+/* ---- Shots: the signature a cut detector compares, computed on the GPU for every frame of a video.
+ * The saved state (statistics, clamp range, predicted filters) belongs to one sequence.  A file with cuts is several: the driver detects the
+ * cuts, then runs clean / add / compute once per shot (INTEGRATION.md "Shots").  The library supplies what has to see every frame: the
+ * signature.  The rule that turns signatures into cuts is host arithmetic (video.shot_distances, video.detect_cuts).
+ * Signature.  uint32 sig[16][32] per frame = RRV_SHOT_SIG_WORDS words: a 32-bin luma histogram for each cell of a 4 x 4 grid over a float32
+ * [H][W][3] BGR PIXEL frame, H, W >= 4 (smaller: RRV_E_ARG), cell cy * 4 + cx.  Integer arithmetic from the first step on, so it is exact
+ * (video.shot_signature restates it in numpy and the GPU equals it word for word):
+ *   per channel  c8 = clamp(rint(v), 0, 255), rint half to even; written so that !(v > 0) gives 0: NaN and -inf give 0, +inf gives 255;
+ *   luma         Y = (29 B8 + 150 G8 + 77 R8 + 128) >> 8, 0..255;   bin = Y >> 3;
+ *   cell         pixel (y, x) lies in cell ((4 y) / H, (4 x) / W), integer division: cell row cy holds the rows ceil(cy H / 4) ..
+ *                ceil((cy + 1) H / 4) - 1, the columns alike.
+ * Every cell's counts sum to its pixel count.  The kernel uses no global atomics and zeroes nothing: every output word is written exactly once
+ * by one thread, so the result is deterministic and depends neither on B nor on what d_sig held before.
+ * Thumbnail.  The signature is taken from a thumbnail, so that its cost does not grow with the frame and film grain does not reach it.
+ * rrv_shot_plan (no handle, no GPU): f = the smallest integer in 1..8 with ceil(max(SH, SW) / f) <= 512, or 8 if there is none; th =
+ * ceil(SH / f), tw = ceil(SW / f).  512 x 512 stays, 1080 x 1920 and 2160 x 3840 become 270 x 480, 4320 x 7680 becomes 540 x 960.  The ratio
+ * of either axis is at most 8, the resampler's limit ("Scaling"); a frame whose thumbnail falls below 4 x 4 is RRV_E_ARG.
+ *   rrv_shot_signature_device          the kernel alone: B (1..64) contiguous frames at d_frames -> d_sig [B][16][32], queued on hip_stream
+ *                                      (NULL: the null stream); nothing of the handle's own streams takes part
+ *   rrv_shot_signature_view_device     B (1..64) frames of SH x SW in any input form, view or surface the resampler reads, resampled to the
+ *                                      plan's thumbnail, then the kernel; by definition rrv_resample_view_device to (th, tw) followed by
+ *                                      rrv_shot_signature_device, bit for bit.  The thumbnails live in a buffer of the handle (float32,
+ *                                      grow-only), reserved with the tap tables before anything is queued: out of memory is RRV_E_NOMEM and
+ *                                      the handle stays usable.  Calls on different streams must be ordered by the caller
+ *   rrv_shot_signature                 the host twin, any B >= 1: uint8 HWC BGR frames or any YUV layout with its sample type, as
+ *                                      rrv_transfer_scaled takes them, contiguous; sub-batches of sixteen through a staging buffer, one after
+ *                                      the other on the handle's first stream; synchronous (sig is written when it returns)
+ *   rrv_shot_signature_from_jpeg       the host twin for baseline JPEG streams ("JPEG input"): every stream parsed first (a stream the parser
+ *                                      refuses: RRV_E_DATA naming the frame, nothing has run), decoded by the JPEG input stage, the signature
+ *                                      taken from the planes with rrv_yuv_input_matrix(RRV_YUV_BT601, 1) installed for the call (the handle's
+ *                                      matrix is put aside and unchanged afterwards).  One size and chroma format per call (RRV_E_ARG naming
+ *                                      the frame); a corrupt frame is RRV_E_DATA naming its index, and the handle stays usable
+ * All checks run before any GPU work.  What is reserved before anything is queued is the thumbnail buffer, the tap tables and the host twins'
+ * staging; the JPEG twin's decode scratch is reserved per sub-batch behind the upload of its streams, as in the other from-JPEG host twins
+ * (out of memory there is RRV_E_NOMEM too, and the handle stays usable).  Not offered: tickets, pipelined host twins. */
+#define RRV_SHOT_SIG_WORDS 512
+int rrv_shot_plan(int SH, int SW, int* th, int* tw);
+int rrv_shot_signature_device(rrv_handle h, const float* d_frames, int B, int H, int W, uint32_t* d_sig, void* hip_stream);
+int rrv_shot_signature_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, uint32_t* d_sig, void* hip_stream);
+int rrv_shot_signature(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, uint32_t* sig);
+int rrv_shot_signature_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, uint32_t* sig);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

@@ -10,7 +10,7 @@ from .synth import synth_frame, synth_style  # noqa: F401
 
 
 def __getattr__(name):
-    if name in ("Stylization", "RRVError", "MultiStyleStylization", "ContentFeature", "pinned_empty", "yuv_frame_bytes", "yuv_planes", "yuv_matrix", "yuv_input_matrix", "ImageView", "image_view_of", "resample_taps"):
+    if name in ("Stylization", "RRVError", "MultiStyleStylization", "ContentFeature", "pinned_empty", "yuv_frame_bytes", "yuv_planes", "yuv_matrix", "yuv_input_matrix", "ImageView", "image_view_of", "resample_taps", "shot_plan"):
         from . import framework
         return getattr(framework, name)
     raise AttributeError(name)

@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
 # reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
-# needs a copy of it there (and of librerevst_compose.so, librerevst_jpeg.so and librerevst_jpeg_in.so).
+# needs a copy of it there (and of librerevst_compose.so, librerevst_jpeg.so, librerevst_jpeg_in.so and librerevst_shots.so).
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -220,6 +220,12 @@ SYMBOLS = {
     "rrv_add_from_jpeg": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
     "rrv_transfer_jpeg_from_jpeg": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.POINTER(Composite), C.POINTER(Jpeg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    # shots: the plan needs no handle; (h, frames, [view | desc,] B, [SH, SW | H, W,] sig[, hip_stream]); sig: uint32 [B][16][32]
+    "rrv_shot_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rrv_shot_signature_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_shot_signature_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_shot_signature": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rrv_shot_signature_from_jpeg": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

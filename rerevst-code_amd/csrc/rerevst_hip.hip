@@ -33,6 +33,7 @@
 #include <functional>
 #include "jpeg.h"          // librerevst_jpeg.so: plan, tables, header and the launch entries of the JPEG output stage
 #include "jpeg_dec.h"      // ... and of the JPEG input stage: parser, plan, decode tables and launch entries
+#include "shots.h"         // librerevst_shots.so: parameters and the launch entry of the shot signature
 
 namespace {
 
@@ -303,6 +304,11 @@ struct rrv_ctx {
     int* jd_status = nullptr; size_t jd_status_cap = 0;
     uint8_t* jd_out = nullptr; size_t jd_out_cap = 0;
     uint8_t* jd_matte = nullptr; size_t jd_matte_cap = 0;
+    // the shot signature entries (include/rerevst_hip.h "Shots"): the thumbnails of a call (caller's stream too), and the host twins' frames and
+    // signatures of a sub-batch.  Grow-only; every word read was written by the same call
+    float* sg_thumb = nullptr; size_t sg_thumb_cap = 0;
+    uint8_t* sg_in = nullptr; size_t sg_in_cap = 0;
+    uint32_t* sg_sig = nullptr; size_t sg_sig_cap = 0;
     void* jd_pin = nullptr; size_t jd_pin_cap = 0; hipEvent_t jd_ev = nullptr;      // the descriptors' page-locked staging and the event behind its last copy
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
@@ -2217,7 +2223,7 @@ int rrv_destroy(rrv_handle h) {
         for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
     for (float* q : {h->gd_ab, h->gd_q, h->cm_buf}) if (q) (void)hipFree(q);
     for (void* q : {(void*)h->jp_coef, (void*)h->jp_idx, (void*)h->jd_frames, (void*)h->jd_ivl, (void*)h->jd_coef, (void*)h->jd_planes, (void*)h->jd_streams,
-                    (void*)h->jd_status, (void*)h->jd_out, (void*)h->jd_matte}) if (q) (void)hipFree(q);
+                    (void*)h->jd_status, (void*)h->jd_out, (void*)h->jd_matte, (void*)h->sg_thumb, (void*)h->sg_in, (void*)h->sg_sig}) if (q) (void)hipFree(q);
     if (h->jd_pin) (void)hipHostFree(h->jd_pin);
     if (h->jd_ev) (void)hipEventDestroy(h->jd_ev);
     for (rrv_ctx::Slot& sl : h->slots)
@@ -4635,6 +4641,128 @@ int rrv_add_scaled(rrv_handle h, const void* frame, rrv_image_desc in, int SH, i
     InFmt fmt;
     if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, "add_scaled: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
     return add_scaled(h, frame, false, fmt, nullptr, nullptr, SH, SW, H, W);
+}
+
+// ---- shots (include/rerevst_hip.h "Shots"): the signature of a frame's thumbnail, what a cut detector compares
+static_assert(SG_WORDS == RRV_SHOT_SIG_WORDS, "the header's signature size is the kernel's");
+int rrv_shot_plan(int SH, int SW, int* th, int* tw) {
+    if (!th || !tw || SH < 1 || SW < 1) return RRV_E_ARG;
+    const int64_t m = std::max(SH, SW);
+    int f = 8;
+    for (int k = 1; k <= 8; ++k)
+        if ((m + k - 1) / k <= 512) { f = k; break; }
+    *th = (SH + f - 1) / f; *tw = (SW + f - 1) / f;
+    return RRV_OK;
+}
+// B contiguous float32 [H][W][3] BGR PIXEL frames at d_frames -> d_sig [B][16][32], queued on q.stream
+static int shot_sig_launch(rrv_handle h, const Seq& q, const float* d_frames, int B, int H, int W, uint32_t* d_sig) {
+    ShotsP p{d_frames, d_sig, B, H, W};
+    int e = 0;
+    // for the profile log: bytes from the shapes; eleven integer operations per pixel
+    RCHK(launch(h, q, "shot_sig", 11.0 * B * H * W, (12.0 * H * W + 4.0 * SG_WORDS) * B, [&] { e = rrv_shots_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("shot_sig: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+int rrv_shot_signature_device(rrv_handle h, const float* d_frames, int B, int H, int W, uint32_t* d_sig, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!d_frames || !d_sig) return fail(h, RRV_E_ARG, "shot_signature: null buffer");
+    if (B < 1 || B > SG_B_MAX) return fail(h, RRV_E_ARG, "shot_signature: batch must be in 1..64");
+    if (H < SG_MIN || W < SG_MIN) return fail(h, RRV_E_ARG, "shot_signature: frames must be at least 4 x 4 pixels");
+    HIPCHK(hipSetDevice(h->dev));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    return shot_sig_launch(h, q, d_frames, B, H, W, d_sig);
+}
+// The checks of a signature request on SH x SW frames and its thumbnail size.  (SH, SW >= 1 and th, tw >= 4 put SH / th and SW / tw within
+// 1 .. 8, the resampler's limits.)
+static int shot_check(rrv_handle h, const char* who, int SH, int SW, int* th, int* tw) {
+    if (rrv_shot_plan(SH, SW, th, tw) != RRV_OK) return fail(h, RRV_E_ARG, std::string(who) + ": SH, SW must be at least 1");
+    if (*th < SG_MIN || *tw < SG_MIN)
+        return fail(h, RRV_E_ARG, std::string(who) + ": the thumbnail of a " + std::to_string(SH) + " x " + std::to_string(SW) + " frame is " + std::to_string(*th) + " x " +
+                                      std::to_string(*tw) + ", below 4 x 4 (rrv_shot_plan)");
+    return check_scale(h, who, SH, SW, *th, *tw);
+}
+// everything a signature request of `frames` frames allocates, before its first launch: both axes' tables and the thumbnails
+static int shot_reserve(rrv_handle h, int frames, int SH, int SW, int th, int tw) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, SH, SW, th, tw, &ty, &tx));
+    return ensure_dev(h, h->sg_thumb, h->sg_thumb_cap, (size_t)frames * th * tw * 3);
+}
+// B (1..64) frames of SH x SW in the format `fmt` through `v` -> their thumbnails -> d_sig, queued on `stream`; shot_reserve has run
+static int shot_queue(rrv_handle h, const void* d_in, InFmt fmt, const rrv_image_view& v, int B, int SH, int SW, int th, int tw, uint32_t* d_sig, hipStream_t stream) {
+    Seq q = base_seq(h);
+    q.stream = stream;
+    RCHK(resample_launch(h, q, d_in, fmt, img_view(v), B, SH, SW, th, tw, h->sg_thumb));
+    return shot_sig_launch(h, q, h->sg_thumb, B, th, tw, d_sig);
+}
+int rrv_shot_signature_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, uint32_t* d_sig, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!in) return fail(h, RRV_E_ARG, "shot_signature_view: null view");
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "shot_signature_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_in || !d_sig) return fail(h, RRV_E_ARG, "shot_signature_view: null buffer");
+    if (B < 1 || B > SG_B_MAX) return fail(h, RRV_E_ARG, "shot_signature_view: batch must be in 1..64");
+    int th = 0, tw = 0;
+    RCHK(shot_check(h, "shot_signature_view", SH, SW, &th, &tw));
+    std::string why;
+    if (!view_check(*in, B, SH, SW, false, &why)) return fail(h, RRV_E_ARG, "shot_signature_view: in." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(shot_reserve(h, B, SH, SW, th, tw));
+    return shot_queue(h, d_in, fmt, *in, B, SH, SW, th, tw, d_sig, (hipStream_t)hip_stream);
+}
+// The host twins: sub-batches of up to sixteen frames on the handle's first stream, one after the other: frames up, the request, signatures back.
+constexpr int SHOT_SUB = 16;
+int rrv_shot_signature(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, uint32_t* sig) {
+    if (!h) return RRV_E_ARG;
+    if (!frames || !sig) return fail(h, RRV_E_ARG, "shot_signature: null buffer");
+    if (B < 1) return fail(h, RRV_E_ARG, "shot_signature: batch must be at least 1");
+    InFmt fmt;
+    if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, "shot_signature: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    int th = 0, tw = 0;
+    RCHK(shot_check(h, "shot_signature", SH, SW, &th, &tw));
+    HIPCHK(hipSetDevice(h->dev));
+    const int sub = std::min(B, SHOT_SUB);
+    const size_t fb = in_frame_bytes(fmt.form, SH, SW, fmt.cs);
+    const rrv_image_view v = contiguous_of(in, SH, SW);
+    RCHK(shot_reserve(h, sub, SH, SW, th, tw));
+    RCHK(ensure_dev(h, h->sg_in, h->sg_in_cap, (size_t)sub * fb));
+    RCHK(ensure_dev(h, h->sg_sig, h->sg_sig_cap, (size_t)sub * SG_WORDS));
+    const hipStream_t s = h->slots[0].stream;
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        HIPCHK(hipMemcpyAsync(h->sg_in, (const uint8_t*)frames + (size_t)b0 * fb, (size_t)nb * fb, hipMemcpyHostToDevice, s));
+        const int rc = shot_queue(h, h->sg_in, fmt, v, nb, SH, SW, th, tw, h->sg_sig, s);
+        if (rc != RRV_OK) { (void)hipStreamSynchronize(s); return rc; }      // (the caller's frames are not read after the call returns)
+        HIPCHK(hipMemcpyAsync(sig + (size_t)b0 * SG_WORDS, h->sg_sig, (size_t)nb * SG_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RRV_OK;
+}
+int rrv_shot_signature_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, uint32_t* sig) {
+    if (!h) return RRV_E_ARG;
+    if (!sig) return fail(h, RRV_E_ARG, "shot_signature_from_jpeg: null buffer");
+    std::vector<JpegInfo> infos;
+    size_t cap = 0;
+    int th = 0, tw = 0;
+    return jpeg_in_host(h, "shot_signature_from_jpeg", streams, sizes, B, &infos, &cap, [&](int sub) -> int {
+        JpegInCall k;
+        int dummy = 0;
+        RCHK(jpeg_in_check(h, "shot_signature_from_jpeg", streams[0], cap, reinterpret_cast<const rrv_jpeg_info*>(infos.data()), sub, &dummy, &k));
+        RCHK(shot_check(h, "shot_signature_from_jpeg", k.p.H, k.p.W, &th, &tw));
+        HIPCHK(hipSetDevice(h->dev));
+        RCHK(shot_reserve(h, sub, k.p.H, k.p.W, th, tw));
+        return ensure_dev(h, h->sg_sig, h->sg_sig_cap, (size_t)sub * SG_WORDS);
+    }, [&](int b0, int nb, hipStream_t s) -> int {
+        JpegInCall k;
+        RCHK(jpeg_in_check(h, "shot_signature_from_jpeg", h->jd_streams, cap, reinterpret_cast<const rrv_jpeg_info*>(infos.data()) + b0, nb, h->jd_status, &k));
+        RCHK(jpeg_in_queue(h, k, h->jd_streams, h->jd_status, s));
+        InFmt fmt;
+        if (!parse_in_view(k.vin.desc, &fmt)) return fail(h, RRV_E_ARG, "shot_signature_from_jpeg: the decoded layout is not an input form");
+        const JfifMatrix jfif(h);      // JFIF's colour space whatever matrix the handle holds: put aside here, back on every way out
+        RCHK(shot_queue(h, h->jd_planes, fmt, k.vin, nb, k.p.H, k.p.W, th, tw, h->sg_sig, s));
+        HIPCHK(hipMemcpyAsync(sig + (size_t)b0 * SG_WORDS, h->sg_sig, (size_t)nb * SG_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        return RRV_OK;
+    });
 }
 
 // The matrix of the YUV input forms, the inverse of rrv_yuv_matrix's transform: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y,

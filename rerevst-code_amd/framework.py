@@ -5,6 +5,7 @@ librerevst_hip.so on one MI355X; this class only marshals numpy buffers through 
 """
 import collections
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -792,6 +793,27 @@ def _host_in_desc(in_format):
     return _lib.ImageDesc(_lib.DT_U8 if fmt.bits == 8 else _lib.DT_U16, fmt.layout, _lib.SP_PIXEL)
 
 
+def shot_plan(H, W):
+    """rrv_shot_plan in Python (include/rerevst_hip.h "Shots"): the thumbnail size (th, tw) the shot signature of an H x W frame is taken
+    from: f = the smallest integer in 1..8 with ceil(max(H, W) / f) <= 512, or 8 if there is none; th = ceil(H / f), tw = ceil(W / f)."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("shot_plan: H, W must be at least 1, got %d x %d" % (H, W))
+    f = next((k for k in range(1, 9) if -(-max(H, W) // k) <= 512), 8)
+    return -(-H // f), -(-W // f)
+
+
+def _runs(keys):
+    """[(first, count)] of the runs of equal consecutive keys"""
+    runs = []
+    for i, k in enumerate(keys):
+        if runs and keys[runs[-1][0]] == k:
+            runs[-1][1] += 1
+        else:
+            runs.append([i, 1])
+    return [(a, b) for a, b in runs]
+
+
 def resample_taps(S, D):
     """rrv_resample_taps: (first [D] int32, count [D] int32, weights [D][16] float32) of one axis of the resampler, S source and D
     destination samples; needs no GPU.  Raises ValueError outside the ratio limits (S / D and D / S at most 8)."""
@@ -921,6 +943,9 @@ class Stylization():
     # transfer_batch / transfer_frames / add take in_format="i420" | "nv12" with size=(H, W) (the rrv_*_from_yuv entries): driver.stylize_y4m
     # feeds a .y4m input that way
     yuv_input = True
+    # shot_signatures(frames, in_format=, size=) computes the signatures a cut detector compares (the rrv_shot_signature entries):
+    # driver.stylize_files / stylize_y4m ask for it with shots="auto"
+    shot_detection = True
 
     def __init__(self, checkpoint, cuda=True, use_Global=True, device=None, style_num=1):
         if not cuda:
@@ -1135,6 +1160,63 @@ class Stylization():
         for _, nb, p, q in _chunks(src.B, (src.ptr, src.step), (out.data_ptr(), out.stride(0) * 4)):
             self._chk(self._lib.rrv_resample_view_device(self._h, p, C.byref(v), nb, src.H, src.W, H, W, q, stream))
         return out if src.batched else out[0]
+
+    def shot_signatures(self, frames, in_format="bgr", size=None):
+        """The shot signatures of host frames (include/rerevst_hip.h "Shots"): np.uint32 [B][16][32], a 32-bin luma histogram for each cell
+        of a 4 x 4 grid over each frame's thumbnail (shot_plan), computed on the GPU; video.shot_distances and video.detect_cuts turn them
+        into cuts.  Needs no torch and no prepared style.  in_format: every host form of transfer_frames — "bgr" (uint8 HWC frames: one
+        [B][H][W][3] array or a list, whose sizes may differ: runs of equal size go to the GPU together), a YUV format name with
+        size=(H, W), or "jpeg" (a list of bytes, grouped into runs of one size and chroma format; JFIF's colour space).  A stream the parser
+        refuses or a corrupt frame raises ValueError with the frame's index in `frames` and the library's words."""
+        if in_format == "jpeg":
+            if size is not None:
+                raise ValueError('in_format="jpeg": the size comes from the streams, size= does not apply')
+            if isinstance(frames, (bytes, bytearray, memoryview)) or len(frames) < 1 or not all(isinstance(s, (bytes, bytearray, memoryview)) for s in frames):
+                raise ValueError('in_format="jpeg": frames must be a non-empty list of bytes, one baseline JPEG stream per frame')
+            streams = [bytes(s) for s in frames]
+            infos = [_jpeg_parse(s, "frame %d" % b) for b, s in enumerate(streams)]
+            out = np.empty((len(streams), 16, 32), np.uint32)
+            for b0, nb in _runs([(f.H, f.W, f.chroma) for f in infos]):
+                ptrs, sizes = (C.c_char_p * nb)(*streams[b0:b0 + nb]), (C.c_size_t * nb)(*[len(s) for s in streams[b0:b0 + nb]])
+                try:
+                    self._chk(self._lib.rrv_shot_signature_from_jpeg(self._h, ptrs, sizes, nb, out[b0:].ctypes.data_as(C.c_void_p)))
+                except RRVError as e:
+                    if getattr(e, "code", 0) == _lib.E_DATA:      # a refused or corrupt stream: the library's words, its index in the run made the caller's
+                        raise ValueError(re.sub(r"\bframe (\d+)", lambda m: "frame %d" % (b0 + int(m.group(1))), str(e), count=1)) from None
+                    raise
+            return out
+        if in_format != "bgr":
+            a, H, W = yuv_frames_args(frames, in_format, size)
+            self._yuv_depth(in_format)
+            groups = [(a, H, W)]
+        elif isinstance(frames, np.ndarray) and frames.ndim == 4:
+            a = _u8_frames(frames, "frame")
+            groups = [(a, a.shape[1], a.shape[2])]
+        else:
+            imgs = [_u8_image(f, "frame") for f in frames]
+            if not imgs:
+                raise ValueError("shot_signatures: no frames")
+            groups = [(np.stack(imgs[b0:b0 + nb]), *imgs[b0].shape[:2]) for b0, nb in _runs([f.shape for f in imgs])]
+        out = np.empty((sum(len(a) for a, _, _ in groups), 16, 32), np.uint32)
+        b0 = 0
+        for a, H, W in groups:
+            self._chk(self._lib.rrv_shot_signature(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), len(a), H, W, out[b0:].ctypes.data_as(C.c_void_p)))
+            b0 += len(a)
+        return out
+
+    def shot_signatures_tensor(self, x, *, space="pixel", layout="nchw", size=None):
+        """shot_signatures for frames already on the handle's GPU (rrv_shot_signature_view_device), with resample_tensor's input
+        conventions: an image tensor in `layout` / `space`, a YUV tensor with layout a format name and size=(H, W), or an ImageView.  Runs in
+        the order of the current stream and returns an int32 tensor [B,16,32] (B = 1 for an unbatched x) on x's device: the uint32 words of
+        the signature, whose counts never reach 2^31.  Equals resample_tensor(x, shot_plan(H, W)) followed by the kernel, bit for bit."""
+        import torch
+        src = self._source(x, space, layout, size)
+        self._yuv_depth(src.layout, None)
+        out = torch.empty((src.B, 16, 32), dtype=torch.int32, device=src.tensor.device)
+        stream, v = self._stream(src.tensor), _whole_view(src, src.H, src.W)
+        for _, nb, p, q in _chunks(src.B, (src.ptr, src.step), (out.data_ptr(), 2048)):
+            self._chk(self._lib.rrv_shot_signature_view_device(self._h, p, C.byref(v), nb, src.H, src.W, q, stream))
+        return out
 
     def add_tensor(self, x, *, space="pixel", layout="nchw", size=None, work_size=None):
         """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch

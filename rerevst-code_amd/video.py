@@ -344,6 +344,126 @@ def yuv420_to_bgr(buf, H, W, n, layout="i420", bits=8, chroma="420"):
     return np.stack(rgb[::-1], axis=-1)
 
 
+# ===== shots: the signature, the distance between frames, the rule that finds the cuts, the shots file (INTEGRATION.md "Shots") =====
+def shot_signature(frame):
+    """The shot signature of one frame (include/rerevst_hip.h "Shots"; Stylization.shot_signatures computes it on the GPU for the frame's
+    thumbnail), restated in numpy: frame [H][W][3] BGR in the PIXEL space, any real dtype, H, W >= 4 -> uint32 [16][32], a 32-bin luma
+    histogram for each cell of a 4 x 4 grid.  Integers from the first step on, so the GPU equals it word for word:
+    c8 = clamp(rint(v), 0, 255) per channel (half to even; NaN and everything not above 0 give 0, +inf gives 255),
+    Y = (29 B8 + 150 G8 + 77 R8 + 128) >> 8, bin = Y >> 3, and pixel (y, x) lies in cell ((4 y) // H, (4 x) // W)."""
+    v = np.asarray(frame, np.float32)
+    if v.ndim != 3 or v.shape[2] != 3 or v.shape[0] < 4 or v.shape[1] < 4:
+        raise ValueError("shot_signature: frame is [H][W][3] with H, W >= 4, got %s" % (v.shape,))
+    H, W = v.shape[:2]
+    with np.errstate(invalid="ignore"):
+        c8 = np.where(v > 0, np.minimum(np.rint(v), np.float32(255)), np.float32(0)).astype(np.int64)
+    Y = (29 * c8[..., 0] + 150 * c8[..., 1] + 77 * c8[..., 2] + 128) >> 8
+    cell = ((4 * np.arange(H)) // H)[:, None] * 4 + ((4 * np.arange(W)) // W)[None, :]
+    return np.bincount((cell * 32 + (Y >> 3)).ravel(), minlength=512).reshape(16, 32).astype(np.uint32)
+
+
+def shot_distances(sigs, sizes=None):
+    """sigs [N][16][32] (shot_signature / Stylization.shot_signatures) -> float64 D[N], D[0] = 0: D[f] is the mean over the 16 cells of
+    sum_k |sig[f][c][k] - sig[f-1][c][k]| / (2 n_c), n_c the cell's pixel count (its counts' sum): 0 for equal histograms, 1 when no cell's
+    histograms overlap.  sizes: optional, one (H, W) per frame; a change of frame size gives D[f] = 1 (as do signatures whose cells hold
+    different pixel counts: they come from thumbnails of different sizes)."""
+    s = np.asarray(sigs).astype(np.int64)
+    if s.ndim != 3 or s.shape[1:] != (16, 32):
+        raise ValueError("shot_distances: sigs is [N][16][32], got %s" % (s.shape,))
+    N = s.shape[0]
+    if sizes is not None and len(sizes) != N:
+        raise ValueError("shot_distances: %d sizes for %d signatures" % (len(sizes), N))
+    D = np.zeros(N, np.float64)
+    if N < 2:
+        return D
+    n = s.sum(axis=2)                                                     # [N][16]
+    if (n < 1).any():
+        raise ValueError("shot_distances: a cell without pixels: not a signature")
+    D[1:] = (np.abs(s[1:] - s[:-1]).sum(axis=2) / (2.0 * n[1:])).mean(axis=1)
+    changed = (n[1:] != n[:-1]).any(axis=1)
+    if sizes is not None:
+        changed |= np.array([tuple(sizes[f]) != tuple(sizes[f - 1]) for f in range(1, N)])
+    D[1:][changed] = 1.0
+    return D
+
+
+def size_changes(sizes):
+    """the frames f >= 1 whose size differs from frame f - 1's: the cuts no rule may drop (a shot's sampled frames share one size)"""
+    return [f for f in range(1, len(sizes)) if tuple(sizes[f]) != tuple(sizes[f - 1])]
+
+
+def detect_cuts(D, threshold=0.35, ratio=3.0, window=8, min_len=8, forced=()):
+    """The first frame of every shot, starting with 0, from the distances of shot_distances.  Scanning upwards, frame f >= 1 starts a shot when
+    D[f] >= threshold, and D[f] >= ratio * median(D[g] for g in [max(1, f - window), min(N - 1, f + window)], g != f) (no such g: this
+    condition holds), and f - previous_cut >= min_len.  forced: frames that start a shot whatever the rule says (size_changes: the driver
+    passes them, so a size change is always a cut).
+    The four defaults are design parameters that nobody has tuned on real footage: a hard cut between shots of different brightness or
+    layout clears them by a wide margin, dissolves, fades and flash frames are outside what the rule sees."""
+    D = np.asarray(D, np.float64)
+    N = len(D)
+    forced = set(int(f) for f in forced)
+    cuts = [0]
+    for f in range(1, N):
+        if f in forced:
+            cuts.append(f)
+            continue
+        if D[f] < threshold or f - cuts[-1] < min_len:
+            continue
+        near = [D[g] for g in range(max(1, f - window), min(N - 1, f + window) + 1) if g != f]
+        if not near or D[f] >= ratio * float(np.median(near)):
+            cuts.append(f)
+    return cuts
+
+
+def shots_from_cuts(cuts, n):
+    """[(lo, hi)] of the shots of an n-frame video whose first frames are `cuts` (sorted, starting with 0): shot k is the frames lo .. hi - 1"""
+    cuts = [int(c) for c in cuts]
+    return [(c, cuts[k + 1] if k + 1 < len(cuts) else int(n)) for k, c in enumerate(cuts)]
+
+
+def check_shots(shots, n):
+    """a list of (lo, hi) pairs as [(int, int)]; ValueError unless they tile 0 .. n - 1 in order, none empty"""
+    out = [(int(lo), int(hi)) for lo, hi in shots]
+    if not out or out[0][0] != 0 or out[-1][1] != n or any(lo >= hi for lo, hi in out) or any(out[k][1] != out[k + 1][0] for k in range(len(out) - 1)):
+        raise ValueError("shots must tile the frames 0..%d in order, each (lo, hi) with lo < hi, got %r" % (n - 1, out))
+    return out
+
+
+def write_shots(path, cuts):
+    """The shots file: text, one first-frame index per line, `#` comments."""
+    with open(path, "w") as f:
+        f.write("# first frame of every shot, one per line\n")
+        for c in cuts:
+            f.write("%d\n" % int(c))
+
+
+def read_shots(path, n):
+    """The first-frame indices of a shots file for an n-frame video (write_shots; text, one index per line, `#` starts a comment, blank
+    lines are skipped).  ValueError, in words, for a line that is no integer and for a list that is unsorted, repeated, out of range or
+    missing 0."""
+    cuts = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            text = line.split("#", 1)[0].strip()
+            if not text:
+                continue
+            try:
+                cuts.append(int(text))
+            except ValueError:
+                raise ValueError("%s, line %d: %r is not a frame index" % (path, no, text)) from None
+    for a, b in zip(cuts, cuts[1:]):
+        if b == a:
+            raise ValueError("%s: frame %d is listed twice" % (path, a))
+        if b < a:
+            raise ValueError("%s: the list is not sorted (%d follows %d)" % (path, b, a))
+    for c in cuts:
+        if not 0 <= c < n:
+            raise ValueError("%s: frame %d is out of range, the video has %d frames" % (path, c, n))
+    if not cuts or cuts[0] != 0:
+        raise ValueError("%s: the first shot starts at frame 0, which the list is missing" % path)
+    return cuts
+
+
 def shard_range(frame_num, rank, world):
     """Contiguous block of frames owned by `rank`."""
     lo = frame_num * rank // world
