@@ -1025,6 +1025,74 @@ int rrv_shot_signature_view_device(rrv_handle h, const void* d_in, const rrv_ima
 int rrv_shot_signature(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, uint32_t* sig);
 int rrv_shot_signature_from_jpeg(rrv_handle h, const uint8_t* const* streams, const size_t* sizes, int B, uint32_t* sig);
 
+/* ---- Picture area: the active picture of letterboxed and pillarboxed frames, found on the GPU and stylized as a window of the frame.
+ * A 2.39:1 film in a 16:9 container is a quarter black.  Stylized whole, the bars enter the saved state's statistics, come out as texture,
+ * bend the stroke pattern at their edge, take a quarter of every kernel's time, and subtitles inside them are painted over.  A matte fixes
+ * only what is shown.  The library supplies what has to see every frame (the line profile), the window as part of a call, and the
+ * entries that stylize inside it; the rule that turns profiles into a window is host arithmetic (video.detect_picture).
+ * Line profile.  uint32 prof[H + W] per frame: row_cnt[H], the number of lit pixels of every row, then col_cnt[W], of every column, of a
+ * float32 [H][W][3] BGR PIXEL frame, H, W >= 8 (smaller: RRV_E_ARG).  Integer arithmetic from the rounding on, with the shot signature's luma,
+ * so it is exact (video.picture_profile restates it in numpy and the GPU equals it word for word):
+ *   per channel  c8 = clamp(rint(v), 0, 255), rint half to even; written so that !(v > 0) gives 0: NaN and -inf give 0, +inf gives 255;
+ *   luma         Y = (29 B8 + 150 G8 + 77 R8 + 128) >> 8, 0..255;   a pixel is lit iff Y > threshold, threshold in 0..254 (else RRV_E_ARG).
+ * Per frame sum(row_cnt) == sum(col_cnt).  RRV_PICTURE_THRESHOLD = 10 is ffmpeg cropdetect's default of 24 on limited-range codes, moved to
+ * the full-range values the first kernel produces; like the rule's defaults it has not been tuned on real footage.  The kernels use no global
+ * atomics and zero nothing: every output word is written exactly once by one thread, so the result is deterministic and depends neither on
+ * B nor on what d_prof held before.
+ * Window.  rrv_picture {y0, x0, h, w}: rows y0 .. y0 + h - 1 and columns x0 .. x0 + w - 1 of an SH x SW frame.  One rule for every layout,
+ * so that a chroma sample never straddles the edge (rrv_picture_check; no handle, no GPU; RRV_OK or RRV_E_ARG, and the entries below name
+ * the field in rrv_last_error): y0, x0 even and >= 0; h, w >= 8; y0 + h <= SH, x0 + w <= SW; h even unless y0 + h == SH; w even unless
+ * x0 + w == SW.
+ * rrv_picture_view (no handle, no GPU) turns the view of the whole frames into the view of the window: plane offsets move by y0 rows and x0
+ * samples (three elements per pixel for RRV_LAY_HWC_BGR), for chroma planes by the layout's subsampling (y0 >> csy rows, x0 >> csx samples,
+ * times two for interleaved CbCr); pitches and the frame stride stay.  The result with the frame size h x w is an ordinary view: "a view
+ * has no semantics of its own".  RRV_E_ARG for a null pointer, an unknown descriptor or a refused window.
+ *   rrv_picture_profile_device         the kernels alone: B (1..64) contiguous frames at d_frames -> d_prof [B][H + W], queued on hip_stream
+ *                                      (NULL: the null stream); the column scratch lives in a grow-only buffer of the handle
+ *   rrv_picture_profile_view_device    B (1..64) frames of SH x SW in any input form, view or surface the resampler reads; by definition
+ *                                      rrv_resample_view_device to (SH, SW), the equal-size identity, followed by rrv_picture_profile_device,
+ *                                      bit for bit.  The float frames and the scratch live in grow-only buffers of the handle, reserved with
+ *                                      the tap tables before anything is queued: out of memory is RRV_E_NOMEM and the handle stays usable.
+ *                                      Calls on different streams must be ordered by the caller
+ *   rrv_scan_frames                    the host twin of the whole detection pass, any B >= 1: host frames as rrv_shot_signature takes them;
+ *                                      every sub-batch (at most sixteen frames and 16 x 640 x 640 x 4 source pixels, the scaled host twins'
+ *                                      budget) is uploaded once, one after the other on the handle's first stream.  sig (NULL: none) is, word
+ *                                      for word, what rrv_shot_signature returns for the same frames, [B][512]; prof (NULL: none) what the
+ *                                      view entry returns, [B][SH + SW].  Both NULL is RRV_E_ARG.  Synchronous
+ * Add.  rrv_add_picture_view_device / rrv_add_picture are by definition rrv_add_scaled_view_device with the window's view, SH := p->h,
+ * SW := p->w, bit for bit in the saved state; H, W is the working size, 0, 0 the window's own.  (The host twin uploads the whole frame.)
+ * Transfer.  The delivered frame has the source's size SH x SW.  By definition, bit for bit in a fixed kernel mode:
+ *   1  canvas = the resampler alone on the whole source at equal size: the float32 HWC BGR PIXEL value the first kernel derives from each
+ *      source pixel, whatever the input form;
+ *   2  canvas[:, y0:y0+h, x0:x0+w] = the float32 HWC BGR PIXEL result of rrv_transfer_composite_view_device on the window's view with
+ *      SH := h, SW := w, the working size H x W (0, 0: the window's), DH := h, DW := w, and the call's r, eps (the guide is the window of the
+ *      source), c (a matte has the window's size [.][h][w]) and flags;
+ *   3  the output = canvas through the delivery stage at equal size into `out`: every output form, YUV layout, depth, chroma format and
+ *      pitched view is word for word that of "Output size".
+ * So outside the window a uint8 BGR output of a uint8 BGR source is the source's bytes.  RRV_TF_PAD_CROP is forced; the other flags taken
+ * are RRV_TF_FRAME_MODE and RRV_TF_ON_STREAM (models: the global and the frame-mode one).  A window equal to the whole frame is exactly
+ * the composite entry without a window: no kernel is added and every bit is what it was.  The request is placed by the delivery stage
+ * writing a float32 view with the canvas's pitch (or by the last kernel itself where nothing is staged), so no kernel of the other six
+ * libraries changes.  The canvas lives in a grow-only buffer per workspace slot (12 bytes per source pixel and frame of a launch group).
+ * rrv_transfer_picture is the host twin through the host pipeline like rrv_transfer_composite, any B >= 1; its sub-batches follow the whole
+ * frame's pixel count.  All checks run before any GPU work, the buffers are reserved before the first launch, RRV_E_NOMEM leaves the handle
+ * usable.  Not offered: JPEG input and output forms with a window, blended and masked models, tickets and the one-frame entries. */
+#define RRV_PICTURE_THRESHOLD 10
+typedef struct rrv_picture { int y0, x0, h, w; } rrv_picture;     /* window of an SH x SW frame, in pixels */
+int rrv_picture_check(int SH, int SW, const rrv_picture* p);
+int rrv_picture_view(const rrv_image_view* full, int SH, int SW, const rrv_picture* p, rrv_image_view* win);
+int rrv_picture_profile_device(rrv_handle h, const float* d_frames, int B, int H, int W, int threshold, uint32_t* d_prof, void* hip_stream);
+int rrv_picture_profile_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int threshold, uint32_t* d_prof,
+                                    void* hip_stream);
+int rrv_scan_frames(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int threshold, uint32_t* sig, uint32_t* prof);
+int rrv_add_picture_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW, const rrv_picture* p, int H, int W,
+                                void* hip_stream);
+int rrv_add_picture(rrv_handle h, const void* frame, rrv_image_desc in, int SH, int SW, const rrv_picture* p, int H, int W);
+int rrv_transfer_picture_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, const rrv_picture* p, int H, int W,
+                                     int r, float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out, int flags, void* hip_stream);
+int rrv_transfer_picture(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, const rrv_picture* p, int H, int W,
+                         int r, float eps, const rrv_composite* c, void* out, rrv_image_desc out_desc, int flags);
+
 /* Debug/parity taps: pre-clamp network output (normalised RGB, NHWC [H][W][3]) of the last
  * transfer, copied to host. */
 int rrv_get_preclamp(rrv_handle h, float* out, int H, int W);

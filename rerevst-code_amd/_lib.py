@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RRV_LIB_PATH: another build of the same library (A/B runs of kernel variants: `python -m rerevst-code_amd.build` with extra -D flags, which
 # reach the main library only).  It finds its companion librerevst_stages.so next to ITSELF (rpath $ORIGIN): a library in another directory
-# needs a copy of it there (and of librerevst_compose.so, librerevst_jpeg.so, librerevst_jpeg_in.so and librerevst_shots.so).
+# needs a copy of it there (and of librerevst_compose.so, librerevst_jpeg.so, librerevst_jpeg_in.so, librerevst_shots.so and librerevst_picture.so).
 LIB_PATH = os.environ.get("RRV_LIB_PATH") or os.path.join(HERE, "librerevst_hip.so")
 STATE_FLOATS = 17536
 MAX_STYLES = 8
@@ -31,6 +31,11 @@ class ImageView(C.Structure):
 class Composite(C.Structure):
     """rrv_composite: a compositing request (per-frame strengths in host memory, the matte, what the source keeps)."""
     _fields_ = [("strength", C.POINTER(C.c_float)), ("matte", C.c_void_p), ("matte_dtype", C.c_int), ("matte_frames", C.c_int), ("keep", C.c_int)]
+
+
+class Picture(C.Structure):
+    """rrv_picture: the window (y0, x0, h, w) of a frame, in pixels (include/rerevst_hip.h "Picture area")."""
+    _fields_ = [("y0", C.c_int), ("x0", C.c_int), ("h", C.c_int), ("w", C.c_int)]
 
 
 class Jpeg(C.Structure):
@@ -226,6 +231,18 @@ SYMBOLS = {
     "rrv_shot_signature_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rrv_shot_signature": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rrv_shot_signature_from_jpeg": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
+    # picture area: the check and the view need no handle; (h, frames, [view | desc,] B, SH, SW, threshold, prof[, hip_stream]); prof: uint32 [B][SH + SW]
+    "rrv_picture_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(Picture)]),
+    "rrv_picture_view": (C.c_int, [C.POINTER(ImageView), C.c_int, C.c_int, C.POINTER(Picture), C.POINTER(ImageView)]),
+    "rrv_picture_profile_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_picture_profile_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_scan_frames": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rrv_add_picture_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.POINTER(Picture), C.c_int, C.c_int, C.c_void_p]),
+    "rrv_add_picture": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.POINTER(Picture), C.c_int, C.c_int]),
+    "rrv_transfer_picture_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_int, C.c_int, C.POINTER(Picture), C.c_int, C.c_int,
+                                                   C.c_int, C.c_float, C.POINTER(Composite), C.c_void_p, C.POINTER(ImageView), C.c_int, C.c_void_p]),
+    "rrv_transfer_picture": (C.c_int, [C.c_void_p, C.c_void_p, ImageDesc, C.c_int, C.c_int, C.c_int, C.POINTER(Picture), C.c_int, C.c_int, C.c_int, C.c_float,
+                                       C.POINTER(Composite), C.c_void_p, ImageDesc, C.c_int]),
     "rrv_get_preclamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rrv_get_preclamp_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rrv_sync": (C.c_int, [C.c_void_p]),

@@ -34,6 +34,7 @@
 #include "jpeg.h"          // librerevst_jpeg.so: plan, tables, header and the launch entries of the JPEG output stage
 #include "jpeg_dec.h"      // ... and of the JPEG input stage: parser, plan, decode tables and launch entries
 #include "shots.h"         // librerevst_shots.so: parameters and the launch entry of the shot signature
+#include "picture.h"       // librerevst_picture.so: parameters and the launch entry of the line profile
 
 namespace {
 
@@ -223,6 +224,7 @@ struct rrv_ctx {
         float* dl_buf = nullptr; size_t dl_cap = 0;
         // Guided delivery (Xfer::gr): a launch group's source at the delivered size, coefficient planes and result (X_hi, [6][H][W], Q), grow-only
         float* gd_xhi = nullptr; size_t gd_xhi_cap = 0;
+        float* pc_canvas = nullptr; size_t pc_canvas_cap = 0;      // a picture request's canvas: the group's whole source frames, float32 HWC BGR PIXEL
         float* gd_ab = nullptr; size_t gd_ab_cap = 0;
         float* gd_q = nullptr; size_t gd_q_cap = 0;
         // JPEG output (Xfer::jp): a launch group's coefficient blocks and its interval lengths and offsets ([2][frames][intervals]), grow-only
@@ -309,6 +311,12 @@ struct rrv_ctx {
     float* sg_thumb = nullptr; size_t sg_thumb_cap = 0;
     uint8_t* sg_in = nullptr; size_t sg_in_cap = 0;
     uint32_t* sg_sig = nullptr; size_t sg_sig_cap = 0;
+    // the picture-area entries (include/rerevst_hip.h "Picture area"): the float frames and the column scratch of a profile call (caller's stream
+    // too), and rrv_scan_frames' frames and results of a sub-batch.  Grow-only; every word read was written by the same call
+    float* pc_frames = nullptr; size_t pc_frames_cap = 0;
+    uint32_t* pc_part = nullptr; size_t pc_part_cap = 0;
+    uint8_t* pc_in = nullptr; size_t pc_in_cap = 0;
+    uint32_t* pc_prof = nullptr; size_t pc_prof_cap = 0;
     void* jd_pin = nullptr; size_t jd_pin_cap = 0; hipEvent_t jd_ev = nullptr;      // the descriptors' page-locked staging and the event behind its last copy
     const float* last_pre = nullptr; int last_pre_H = 0, last_pre_W = 0, last_pre_B = 0;   // where rrv_get_preclamp finds the last tap
     // host-buffer entry: two staging sets (pinned host + device, input and output) so that H2D / kernels / D2H /
@@ -1240,6 +1248,13 @@ struct Xfer {
     const JpegP* jp = nullptr; int* jp_sizes = nullptr;
     // Order this call with the stream `with` (view_run's hip_stream / RRV_TF_ON_STREAM); unset: rrv_set_caller_stream's setting (order())
     bool on_stream = false; hipStream_t with = nullptr;
+    // The picture area (include/rerevst_hip.h "Picture area"; the rrv_transfer_picture entries set it once, run_xfer reads it): the frames as
+    // passed and as delivered are FH x FW, and everything above describes the WINDOW (py0, px0, SH x SW) of them as a compositing request
+    // with DH x DW = SH x SW: vin is the window's view.  vfull / vout are the views of the whole frames, in and out.  run_xfer fills a
+    // float32 canvas from the whole source, lets the request write the window of it, and delivers the canvas at equal size.
+    bool pic = false;
+    int py0 = 0, px0 = 0, FH = 0, FW = 0;
+    const rrv_image_view* vfull = nullptr;
 
     bool scaled() const { return SH != 0 || SW != 0; }
     int IH() const { return scaled() ? SH : H; }              // the frame as passed
@@ -1249,15 +1264,17 @@ struct Xfer {
     bool delivering() const { return (DH != 0 || DW != 0) && (DH != WH() || DW != WW()); }
     bool guided() const { return gr != 0; }
     bool staged() const { return delivering() || guided() || comp || jp; }  // the last kernel writes the slot's buffer of working frames, not the caller's frames
+    bool indirect() const { return staged() || pic; }                        // the caller's frames are written by a stage behind the model, not by its last kernel
     int OH() const { return delivering() ? DH : WH(); }       // the frame delivered
     int OW() const { return delivering() ? DW : WW(); }
     ImgView in_view() const { return vin ? img_view(*vin) : contiguous_view(in_view_layout(in.form), IH(), IW(), in.cs); }
     ImgView out_view() const { return vout ? img_view(*vout) : contiguous_view(out_view_layout(fmt), OH(), OW(), fmt.cs); }
     int KH() const { return pad ? padded_size(H) : H; }      // the geometry the kernels run
     int KW() const { return pad ? padded_size(W) : W; }
-    size_t in_bytes() const { return in_frame_bytes(in.form, IH(), IW(), in.cs); }                                              // per frame, in x.in
+    size_t in_bytes() const { return pic ? in_frame_bytes(in.form, FH, FW, in.cs) : in_frame_bytes(in.form, IH(), IW(), in.cs); }                                              // per frame, in x.in
     size_t out_elems() const { return (size_t)OH() * OW() * 3; }                                                   // per frame (any input size: 8*(H/8) x 8*(W/8), or the delivered size)
     size_t out_bytes() const {                                                                                      // per frame, in x.fmt
+        if (pic) return fmt.yuv ? yuv_frame_samples(FH, FW, fmt.cs) * yuv_sample_bytes(fmt) : (size_t)FH * FW * 3 * out_elem(fmt);      // the whole frame is delivered
         return fmt.yuv ? yuv_frame_samples(OH(), OW(), fmt.cs) * yuv_sample_bytes(fmt) : out_elems() * out_elem(fmt);
     }
     size_t mask_floats() const { return (size_t)ns * H * W; }                                                      // of one image's masks
@@ -2220,10 +2237,11 @@ int rrv_destroy(rrv_handle h) {
     for (rrv_ctx::Slot& sl : h->slots) if (sl.rs_buf) (void)hipFree(sl.rs_buf);
     for (rrv_ctx::Slot& sl : h->slots) if (sl.dl_buf) (void)hipFree(sl.dl_buf);
     for (rrv_ctx::Slot& sl : h->slots)
-        for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q}) if (q) (void)hipFree(q);
+        for (float* q : {sl.gd_xhi, sl.gd_ab, sl.gd_q, sl.pc_canvas}) if (q) (void)hipFree(q);
     for (float* q : {h->gd_ab, h->gd_q, h->cm_buf}) if (q) (void)hipFree(q);
     for (void* q : {(void*)h->jp_coef, (void*)h->jp_idx, (void*)h->jd_frames, (void*)h->jd_ivl, (void*)h->jd_coef, (void*)h->jd_planes, (void*)h->jd_streams,
-                    (void*)h->jd_status, (void*)h->jd_out, (void*)h->jd_matte, (void*)h->sg_thumb, (void*)h->sg_in, (void*)h->sg_sig}) if (q) (void)hipFree(q);
+                    (void*)h->jd_status, (void*)h->jd_out, (void*)h->jd_matte, (void*)h->sg_thumb, (void*)h->sg_in, (void*)h->sg_sig,
+                    (void*)h->pc_frames, (void*)h->pc_part, (void*)h->pc_in, (void*)h->pc_prof}) if (q) (void)hipFree(q);
     if (h->jd_pin) (void)hipHostFree(h->jd_pin);
     if (h->jd_ev) (void)hipEventDestroy(h->jd_ev);
     for (rrv_ctx::Slot& sl : h->slots)
@@ -3026,6 +3044,11 @@ static int gd_tables(rrv_handle h, int H, int W, int DH, int DW) {
 // or delivering: the tables and the stylized working frames.
 static int reserve_stages(rrv_handle h, int slot, int frames, const Xfer& x) {
     if (x.scaled()) RCHK(rs_reserve(h, slot, frames, x.SH, x.SW, x.H, x.W));
+    if (x.pic) {      // the equal-size tables of the whole frame (the resampler in, the delivery stage out) and the canvas
+        const rrv_ctx::RsTab *fy, *fx;
+        RCHK(rs_pair(h, x.FH, x.FW, x.FH, x.FW, &fy, &fx));
+        RCHK(ensure_dev(h, h->slots[slot].pc_canvas, h->slots[slot].pc_canvas_cap, (size_t)frames * x.FH * x.FW * 3));
+    }
     if (!x.staged()) return RRV_OK;
     const int H = x.WH(), W = x.WW();
     const rrv_ctx::RsTab *ty, *tx;
@@ -3233,7 +3256,8 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     RCHK(reserve_stages(h, slot, group_frames, x));
     rrv_ctx::Slot& sl = h->slots[slot];
     const CallerOrder caller = x.order(h);
-    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || staged);
+    const bool pic = x.pic;
+    const bool bracket = caller.sync && (x.model != Model::GLOBAL || scaled || staged || pic);
     if (bracket) {
         HIPCHK(hipEventRecord(sl.ev, caller.stream));
         HIPCHK(hipStreamWaitEvent(sl.stream, sl.ev, 0));
@@ -3244,18 +3268,24 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
     const PadCrop crop = x.pad_crop();
     const ImgView vw = contiguous_view(VL_HWC, x.H, x.W);      // a scaled request's working frames: float32 HWC BGR PIXEL in the slot's buffer
     const ImgView vd = contiguous_view(VL_HWC, x.WH(), x.WW());    // a delivering request's stylized working frames, the same form in the slot's other buffer
-    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, staged ? OUT_F32 : x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi,
-                     staged ? &vd : &vo, caller};
+    // a picture request: the whole source frames, the canvas of a group, and the window of the canvas as an output view with the canvas's pitch
+    const ImgView vf = pic ? img_view(*x.vfull) : vi;
+    const ImgView vc = contiguous_view(VL_HWC, x.FH, x.FW);
+    const ImgView vcw{vc.fs, {((int64_t)x.py0 * x.FW + x.px0) * 3, 0, 0}, {vc.pitch[0], 0, 0}};
+    const FrameIO io{scaled ? InFmt{IN_F32_HWC, SP_PIXEL} : x.in, staged || pic ? OUT_F32 : x.fmt, x.pad ? &crop : nullptr, scaled ? &vw : &vi,
+                     staged ? &vd : pic ? &vcw : &vo, caller};
     for (int b0 = 0; b0 < x.B; b0 += G) {
         const int cnt = x.B - b0 < G ? x.B - b0 : G;
         const uint8_t* in = (const uint8_t*)d_in + (size_t)b0 * fb;
         void* const dst = (char*)d_out + (size_t)b0 * fo;      // the group's frames as the caller gets them
-        void* const out = staged ? (void*)sl.dl_buf : dst;
+        void* const out = staged ? (void*)sl.dl_buf : pic ? (void*)sl.pc_canvas : dst;
         const uint8_t* const src = in;                         // the group's frames as the caller passed them
         // the group's sequence: GLOBAL and MASK read no set of the slot's own, FRAME writes and BLEND blends into them (image g: set g of the slot's);
         // GLOBAL and BLEND are the per-frame path (transfer_device), where F(4x4,3x3) may run
         Seq q = slot_seq(h, slot, x.model == Model::FRAME || x.model == Model::BLEND);
         q.f43 = x.model == Model::GLOBAL || x.model == Model::BLEND;
+        // a picture request: the canvas first, every source pixel as the first kernel's float32 value; the window of it is overwritten below
+        if (pic) RCHK(resample_launch(h, q, src, x.in, vf, cnt, x.FH, x.FW, x.FH, x.FW, sl.pc_canvas));
         if (scaled) {
             RCHK(resample_launch(h, q, in, x.in, vi, cnt, x.SH, x.SW, x.H, x.W, sl.rs_buf));
             in = (const uint8_t*)sl.rs_buf;
@@ -3282,7 +3312,11 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
         // delivered size.  A compositing request brings P to the delivered size first -- Q, or the delivery stage's float32 PIXEL result in
         // Q's buffer, or the working frame itself -- and mixes it in place with S: the guided stage's X_hi, the scaled request's working
         // input when that frame is the one delivered, else the source through the resampler into X_hi's buffer.
-        if (!staged) continue;
+        if (!staged && !pic) continue;
+        if (!staged) {      // the last kernel has written the window of the canvas
+            RCHK(deliver_launch(h, q, sl.pc_canvas, cnt, x.FH, x.FW, x.FH, x.FW, dst, x.fmt, vo));
+            continue;
+        }
         const int OH = x.OH(), OW = x.OW();
         float* P = sl.dl_buf;
         int PH = x.WH(), PW = x.WW();
@@ -3313,6 +3347,11 @@ static int run_xfer(rrv_handle h, int slot, const void* d_in, void* d_out, const
             p.lens = sl.jp_idx; p.offs = sl.jp_idx + (size_t)cnt * p.n_int;
             RCHK(jpeg_blocks_launch(h, q, p));
             RCHK(jpeg_entropy_launch(h, q, p));
+            continue;
+        }
+        if (pic) {      // the request's float32 frame into the window of the canvas, the canvas at equal size into the output form
+            RCHK(deliver_launch(h, q, P, cnt, PH, PW, OH, OW, sl.pc_canvas, OUT_F32, vcw));
+            RCHK(deliver_launch(h, q, sl.pc_canvas, cnt, x.FH, x.FW, x.FH, x.FW, dst, x.fmt, vo));
             continue;
         }
         RCHK(deliver_launch(h, q, P, cnt, PH, PW, OH, OW, dst, x.fmt, vo));
@@ -3650,6 +3689,8 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     if (x.scaled()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.SH * x.SW)));
     // the same rule for the DELIVERED frame, which sizes the output staging
     if (x.staged()) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.OH() * x.OW())));
+    // a picture request stages and delivers the WHOLE frame
+    if (x.pic) sub = (int)std::max(1L, std::min((long)sub, 4 * HOST_SUB_PIXELS / ((long)x.FH * x.FW)));
     const size_t mfb = x.comp ? x.matte_bytes() : x.mask_floats() * sizeof(float);      // of one image's masks / one frame's matte
     auto run = [&](int slot, int k, const void* d_in, int nb, void* d_out, const SeqHook* hk) -> int {      // sub-batch k's kernels
         Xfer part = x;
@@ -3678,7 +3719,7 @@ static int host_pipeline(rrv_handle h, const uint8_t* frames, void* out, const X
     // profiled step (slot 0 only), the debug levels, a caller's stream, zero copy.
     // A delivering request too: the piecewise drain hooks into transfer_device's last launch, which is then not the request's last kernel.
     const bool ordered = nchunk > 1 && h->n_slots > 1 && !h->profiling && !h->debug && !x.order(h).sync && h->host_io == 0 &&
-                         (x.model == Model::GLOBAL || x.model == Model::BLEND) && !x.staged();
+                         (x.model == Model::GLOBAL || x.model == Model::BLEND) && !x.indirect();
     const bool tl_on = h->tl.on && nchunk > 1 && nchunk <= rrv_ctx::Timeline::N && h->host_io == 0;
     double tl_setup = 0;
     if (tl_on) { tl_setup = host_ms_since(t_entry); HIPCHK(hipEventRecord(h->tl.entry, h->slots[0].stream)); }
@@ -4572,7 +4613,9 @@ int rrv_transfer_composite(rrv_handle h, const void* frames, rrv_image_desc in, 
 }
 // a sampled frame of SH x SW, resampled into slot 0's buffer on the handle's stream and added as the float32 PIXEL frame it then is.
 // device: d_frame is in HBM, complete once `stream` has run what it holds now; else host memory in the contiguous form of `fmt`
-static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, const rrv_image_view* view, hipStream_t stream, int SH, int SW, int H, int W) {
+// host_bytes: what a host frame uploads when `view` is a window of a larger frame (0: the contiguous SH x SW frame)
+static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, const rrv_image_view* view, hipStream_t stream, int SH, int SW, int H, int W,
+                      size_t host_bytes = 0) {
     RCHK(check_frame(h, H, W, "add"));
     RCHK(check_scale(h, "add_scaled", SH, SW, H, W));
     std::string why;
@@ -4587,7 +4630,7 @@ static int add_scaled(rrv_handle h, const void* frame, bool device, InFmt fmt, c
     if (device) {
         RCHK(wait_for_stream(h, stream));
     } else {
-        const size_t fb = in_frame_bytes(fmt.form, SH, SW, fmt.cs);
+        const size_t fb = host_bytes ? host_bytes : in_frame_bytes(fmt.form, SH, SW, fmt.cs);
         RCHK(ensure_dev(h, h->d_u8, h->d_u8_cap, fb));
         HIPCHK(hipMemcpyAsync(h->d_u8, frame, fb, hipMemcpyHostToDevice, q.stream));
         src = h->d_u8;
@@ -4763,6 +4806,219 @@ int rrv_shot_signature_from_jpeg(rrv_handle h, const uint8_t* const* streams, co
         HIPCHK(hipMemcpyAsync(sig + (size_t)b0 * SG_WORDS, h->sg_sig, (size_t)nb * SG_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         return RRV_OK;
     });
+}
+
+// ---- picture area (include/rerevst_hip.h "Picture area"): the line profile a bar detector reads, and the window of a frame as part of a call
+static_assert(RRV_PICTURE_THRESHOLD >= 0 && RRV_PICTURE_THRESHOLD <= PC_T_MAX, "the header's default threshold is one the kernel takes");
+// the window rules; nullptr: a window of an SH x SW frame, else the offending field and what is wrong with it
+static const char* picture_why(int SH, int SW, const rrv_picture* p) {
+    if (!p) return "picture is null";
+    if (SH < 1 || SW < 1) return "SH, SW must be at least 1";
+    if (p->y0 < 0 || (p->y0 & 1)) return "picture.y0 must be even and at least 0";
+    if (p->x0 < 0 || (p->x0 & 1)) return "picture.x0 must be even and at least 0";
+    if (p->h < 8) return "picture.h must be at least 8";
+    if (p->w < 8) return "picture.w must be at least 8";
+    if ((int64_t)p->y0 + p->h > SH) return "picture.h reaches below the frame (y0 + h > SH)";
+    if ((int64_t)p->x0 + p->w > SW) return "picture.w reaches beyond the frame (x0 + w > SW)";
+    if ((p->h & 1) && p->y0 + p->h != SH) return "picture.h must be even unless the window reaches the frame's bottom edge";
+    if ((p->w & 1) && p->x0 + p->w != SW) return "picture.w must be even unless the window reaches the frame's right edge";
+    return nullptr;
+}
+int rrv_picture_check(int SH, int SW, const rrv_picture* p) { return picture_why(SH, SW, p) ? RRV_E_ARG : RRV_OK; }
+static bool picture_whole(int SH, int SW, const rrv_picture& p) { return p.y0 == 0 && p.x0 == 0 && p.h == SH && p.w == SW; }
+// the view of the window of a frame addressed through `full` (a known descriptor, a checked window): offsets move, pitches and the frame stride stay
+static rrv_image_view window_of(const rrv_image_view& full, const rrv_picture& p) {
+    rrv_image_view w = full;
+    const int64_t y0 = p.y0, x0 = p.x0;
+    const int cs = view_chroma(full.desc), cy = (int)(y0 >> chroma_sy(cs)), cx = (int)(x0 >> chroma_sx(cs));
+    switch (view_layout(full.desc)) {
+    case VL_HWC: w.plane_offset[0] += y0 * full.pitch[0] + 3 * x0; break;
+    case VL_CHW: for (int k = 0; k < 3; ++k) w.plane_offset[k] += y0 * full.pitch[k] + x0; break;
+    case VL_I420:
+        w.plane_offset[0] += y0 * full.pitch[0] + x0;
+        for (int k = 1; k < 3; ++k) w.plane_offset[k] += (int64_t)cy * full.pitch[k] + cx;
+        break;
+    default:
+        w.plane_offset[0] += y0 * full.pitch[0] + x0;
+        w.plane_offset[1] += (int64_t)cy * full.pitch[1] + 2 * (int64_t)cx;
+        break;
+    }
+    return w;
+}
+int rrv_picture_view(const rrv_image_view* full, int SH, int SW, const rrv_picture* p, rrv_image_view* win) {
+    if (!full || !win || !view_desc_ok(full->desc) || picture_why(SH, SW, p)) return RRV_E_ARG;
+    *win = window_of(*full, *p);
+    return RRV_OK;
+}
+// B contiguous float32 [H][W][3] BGR PIXEL frames at d_frames -> d_prof [B][H + W] through the scratch `part`, queued on q.stream
+static int picture_launch(rrv_handle h, const Seq& q, const float* d_frames, int B, int H, int W, int threshold, uint32_t* part, uint32_t* d_prof) {
+    PictureP p{d_frames, d_prof, part, B, H, W, threshold};
+    int e = 0;
+    // for the profile log: bytes from the shapes (the frames read, the scratch written and read, the profile written); fourteen integer operations per pixel
+    RCHK(launch(h, q, "picture_profile", 14.0 * B * H * W, (12.0 * H * W + 8.0 * pc_strips(H) * W + 4.0 * (H + W)) * B, [&] { e = rrv_picture_launch(&p, q.stream); }));
+    if (e != 0) return fail(h, RRV_E_HIP, std::string("picture_profile: launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RRV_OK;
+}
+static int picture_profile_check(rrv_handle h, const char* who, int B, int H, int W, int threshold) {
+    if (B < 1 || B > PC_B_MAX) return fail(h, RRV_E_ARG, std::string(who) + ": batch must be in 1..64");
+    if (H < PC_MIN || W < PC_MIN) return fail(h, RRV_E_ARG, std::string(who) + ": frames must be at least 8 x 8 pixels");
+    if (threshold < 0 || threshold > PC_T_MAX) return fail(h, RRV_E_ARG, std::string(who) + ": threshold must be in 0..254");
+    return RRV_OK;
+}
+int rrv_picture_profile_device(rrv_handle h, const float* d_frames, int B, int H, int W, int threshold, uint32_t* d_prof, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!d_frames || !d_prof) return fail(h, RRV_E_ARG, "picture_profile: null buffer");
+    RCHK(picture_profile_check(h, "picture_profile", B, H, W, threshold));
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(ensure_dev(h, h->pc_part, h->pc_part_cap, pc_part_words(B, H, W)));
+    Seq q = base_seq(h);
+    q.stream = (hipStream_t)hip_stream;
+    return picture_launch(h, q, d_frames, B, H, W, threshold, h->pc_part, d_prof);
+}
+// everything a profile request of `frames` frames of SH x SW allocates, before its first launch: the equal-size tables, the float frames, the scratch
+static int picture_reserve(rrv_handle h, int frames, int SH, int SW) {
+    const rrv_ctx::RsTab *ty, *tx;
+    RCHK(rs_pair(h, SH, SW, SH, SW, &ty, &tx));
+    RCHK(ensure_dev(h, h->pc_frames, h->pc_frames_cap, (size_t)frames * SH * SW * 3));
+    return ensure_dev(h, h->pc_part, h->pc_part_cap, pc_part_words(frames, SH, SW));
+}
+// B (1..64) frames of SH x SW in the format `fmt` through `v` -> their float32 frames -> d_prof, queued on `stream`; picture_reserve has run
+static int picture_queue(rrv_handle h, const void* d_in, InFmt fmt, const rrv_image_view& v, int B, int SH, int SW, int threshold, uint32_t* d_prof, hipStream_t stream) {
+    Seq q = base_seq(h);
+    q.stream = stream;
+    RCHK(resample_launch(h, q, d_in, fmt, img_view(v), B, SH, SW, SH, SW, h->pc_frames));
+    return picture_launch(h, q, h->pc_frames, B, SH, SW, threshold, h->pc_part, d_prof);
+}
+int rrv_picture_profile_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, int threshold, uint32_t* d_prof, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    if (!in) return fail(h, RRV_E_ARG, "picture_profile_view: null view");
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "picture_profile_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (!d_in || !d_prof) return fail(h, RRV_E_ARG, "picture_profile_view: null buffer");
+    RCHK(picture_profile_check(h, "picture_profile_view", B, SH, SW, threshold));
+    std::string why;
+    if (!view_check(*in, B, SH, SW, false, &why)) return fail(h, RRV_E_ARG, "picture_profile_view: in." + why);
+    HIPCHK(hipSetDevice(h->dev));
+    RCHK(picture_reserve(h, B, SH, SW));
+    return picture_queue(h, d_in, fmt, *in, B, SH, SW, threshold, d_prof, (hipStream_t)hip_stream);
+}
+// The host twin of the whole detection pass: every sub-batch is uploaded once and gives its signatures and / or its profiles, one after the
+// other on the handle's first stream.  A sub-batch holds at most sixteen frames and at most 4 x HOST_SUB_PIXELS source pixels (the scaled
+// host twins' budget), so that the float frames of a 4K sub-batch stay what a scaled call stages.
+int rrv_scan_frames(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, int threshold, uint32_t* sig, uint32_t* prof) {
+    if (!h) return RRV_E_ARG;
+    if (!frames) return fail(h, RRV_E_ARG, "scan_frames: null buffer");
+    if (!sig && !prof) return fail(h, RRV_E_ARG, "scan_frames: sig and prof are both null: nothing to compute");
+    if (B < 1) return fail(h, RRV_E_ARG, "scan_frames: batch must be at least 1");
+    InFmt fmt;
+    if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, "scan_frames: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    if (SH < 1 || SW < 1) return fail(h, RRV_E_ARG, "scan_frames: SH, SW must be at least 1");
+    int th = 0, tw = 0;
+    if (sig) RCHK(shot_check(h, "scan_frames", SH, SW, &th, &tw));
+    if (prof) RCHK(picture_profile_check(h, "scan_frames", 1, SH, SW, threshold));
+    HIPCHK(hipSetDevice(h->dev));
+    const int sub = (int)std::max(1L, std::min((long)std::min(B, SHOT_SUB), 4 * HOST_SUB_PIXELS / ((long)SH * SW)));
+    const size_t fb = in_frame_bytes(fmt.form, SH, SW, fmt.cs), pw = (size_t)SH + SW;
+    const rrv_image_view v = contiguous_of(in, SH, SW);
+    if (sig) {
+        RCHK(shot_reserve(h, sub, SH, SW, th, tw));
+        RCHK(ensure_dev(h, h->sg_sig, h->sg_sig_cap, (size_t)sub * SG_WORDS));
+    }
+    if (prof) {
+        RCHK(picture_reserve(h, sub, SH, SW));
+        RCHK(ensure_dev(h, h->pc_prof, h->pc_prof_cap, (size_t)sub * pw));
+    }
+    RCHK(ensure_dev(h, h->pc_in, h->pc_in_cap, (size_t)sub * fb));
+    const hipStream_t s = h->slots[0].stream;
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        HIPCHK(hipMemcpyAsync(h->pc_in, (const uint8_t*)frames + (size_t)b0 * fb, (size_t)nb * fb, hipMemcpyHostToDevice, s));
+        int rc = RRV_OK;
+        if (sig) rc = shot_queue(h, h->pc_in, fmt, v, nb, SH, SW, th, tw, h->sg_sig, s);
+        if (rc == RRV_OK && prof) rc = picture_queue(h, h->pc_in, fmt, v, nb, SH, SW, threshold, h->pc_prof, s);
+        if (rc != RRV_OK) { (void)hipStreamSynchronize(s); return rc; }      // (the caller's frames are not read after the call returns)
+        if (sig) HIPCHK(hipMemcpyAsync(sig + (size_t)b0 * SG_WORDS, h->sg_sig, (size_t)nb * SG_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (prof) HIPCHK(hipMemcpyAsync(prof + (size_t)b0 * pw, h->pc_prof, (size_t)nb * pw * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RRV_OK;
+}
+// The add entries: rrv_add_scaled_view_device on the window's view, SH := p->h, SW := p->w; H = W = 0: the window's own size
+int rrv_add_picture_view_device(rrv_handle h, const void* d_frame, const rrv_image_view* in, int SH, int SW, const rrv_picture* p, int H, int W, void* hip_stream) {
+    if (!h || !d_frame || !in) return RRV_E_ARG;
+    InFmt fmt;
+    if (!parse_in_view(in->desc, &fmt)) return fail(h, RRV_E_ARG, "add_picture_view: in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    if (const char* why = picture_why(SH, SW, p)) return fail(h, RRV_E_ARG, std::string("add_picture_view: ") + why);
+    std::string vwhy;
+    if (!view_check(*in, 1, SH, SW, false, &vwhy)) return fail(h, RRV_E_ARG, "add_picture_view: in." + vwhy);
+    const rrv_image_view win = window_of(*in, *p);
+    return add_scaled(h, d_frame, true, fmt, &win, (hipStream_t)hip_stream, p->h, p->w, H || W ? H : p->h, H || W ? W : p->w);
+}
+int rrv_add_picture(rrv_handle h, const void* frame, rrv_image_desc in, int SH, int SW, const rrv_picture* p, int H, int W) {
+    if (!h || !frame) return RRV_E_ARG;
+    InFmt fmt;
+    if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, "add_picture: the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    if (const char* why = picture_why(SH, SW, p)) return fail(h, RRV_E_ARG, std::string("add_picture: ") + why);
+    const rrv_image_view win = window_of(contiguous_of(in, SH, SW), *p);
+    return add_scaled(h, frame, false, fmt, &win, nullptr, p->h, p->w, H || W ? H : p->h, H || W ? W : p->w, in_frame_bytes(fmt.form, SH, SW, fmt.cs));
+}
+// The transfer entries: the request on the window as a compositing request (SH := h, SW := w, the working size, DH := h, DW := w) with
+// Xfer::pic set; run_xfer places its float32 result in the canvas of the whole source and delivers that.  `x` arrives with B and the window
+// fields unset; who: the entry's name in the refusals.  Returns 1 where the window is the whole frame (the caller runs the composite entry).
+static int set_picture(rrv_handle h, const char* who, int B, int SH, int SW, const rrv_picture* p, int H, int W, int r, float eps, const rrv_composite* c, int flags,
+                       bool host, Xfer* x) {
+    const std::string w = std::string(who) + ": ";
+    if (const char* why = picture_why(SH, SW, p)) return fail(h, RRV_E_ARG, w + why);
+    if (flags & ~(RRV_TF_PAD_CROP | RRV_TF_FRAME_MODE | RRV_TF_ON_STREAM)) return fail(h, RRV_E_ARG, w + "the flags are RRV_TF_FRAME_MODE and RRV_TF_ON_STREAM (RRV_TF_PAD_CROP is forced); blended and masked models are not offered with a window");
+    if (B < 1 || (!host && B > 64)) return fail(h, RRV_E_ARG, w + (host ? "batch must be at least 1" : "batch must be in 1..64"));
+    if ((H != 0 || W != 0) && (H < 1 || W < 1)) return fail(h, RRV_E_ARG, w + "H, W must be at least 1, or both 0 for the window's own size");
+    const bool work = (H != 0 || W != 0) && (H != p->h || W != p->w);      // a working size of its own: the window is resampled to it
+    *x = Xfer{Model::GLOBAL, B, work ? H : p->h, work ? W : p->w};
+    if (work) { x->SH = p->h; x->SW = p->w; }
+    x->DH = p->h; x->DW = p->w;
+    if (r) { x->gr = r; x->geps = eps; }
+    RCHK(set_composite(h, who, c, B, x));
+    if (picture_whole(SH, SW, *p)) return 1;
+    x->pic = true; x->py0 = p->y0; x->px0 = p->x0; x->FH = SH; x->FW = SW;
+    return RRV_OK;
+}
+int rrv_transfer_picture_view_device(rrv_handle h, const void* d_in, const rrv_image_view* in, int B, int SH, int SW, const rrv_picture* p, int H, int W, int r,
+                                     float eps, const rrv_composite* c, void* d_out, const rrv_image_view* out, int flags, void* hip_stream) {
+    if (!h) return RRV_E_ARG;
+    const char* const who = "transfer_picture_view";
+    if (!in || !out) return fail(h, RRV_E_ARG, std::string(who) + ": null view");
+    Xfer x{Model::GLOBAL, B, H, W};
+    const int rc = set_picture(h, who, B, SH, SW, p, H, W, r, eps, c, flags, false, &x);
+    if (rc < 0) return rc;
+    flags |= RRV_TF_PAD_CROP;
+    if (rc == 1) return view_run(h, who, d_in, in, d_out, out, flags, hip_stream, x);      // the whole frame: the composite entry, no kernel added
+    if (!view_desc_ok(in->desc)) return fail(h, RRV_E_ARG, std::string(who) + ": in.desc is not a dtype, layout and space combination the descriptor entries accept");
+    std::string why;
+    if (!view_check(*in, B, SH, SW, false, &why)) return fail(h, RRV_E_ARG, std::string(who) + ": in." + why);
+    if (view_desc_ok(out->desc) && !view_check(*out, B, SH, SW, true, &why)) return fail(h, RRV_E_ARG, std::string(who) + ": out." + why);      // (an unknown out.desc: view_run's words)
+    const rrv_image_view win = window_of(*in, *p);
+    x.vfull = in;
+    return view_run(h, who, d_in, &win, d_out, out, flags, hip_stream, x);
+}
+int rrv_transfer_picture(rrv_handle h, const void* frames, rrv_image_desc in, int B, int SH, int SW, const rrv_picture* p, int H, int W, int r, float eps,
+                         const rrv_composite* c, void* out, rrv_image_desc od, int flags) {
+    if (!h) return RRV_E_ARG;
+    const char* const who = "transfer_picture";
+    Xfer x{Model::GLOBAL, B, H, W};
+    if (flags & RRV_TF_ON_STREAM) return fail(h, RRV_E_ARG, std::string(who) + ": unknown flags");
+    const int rc = set_picture(h, who, B, SH, SW, p, H, W, r, eps, c, flags, true, &x);
+    if (rc < 0) return rc;
+    flags |= RRV_TF_PAD_CROP;
+    if (rc == 1) return scaled_host(h, who, false, frames, in, out, od, flags, x);
+    InFmt fmt;
+    if (!parse_in_host(in, &fmt)) return fail(h, RRV_E_ARG, std::string(who) + ": the input is uint8 HWC BGR or a YUV layout with its own sample type, in the PIXEL space");
+    OutFmt ofmt;
+    if (parse_out(od, &ofmt) != DescErr::OK || ofmt.chw || ofmt.space != SP_PIXEL)
+        return fail(h, RRV_E_ARG, std::string(who) + ": the output is float32 or uint8 HWC BGR in the PIXEL space, uint8 I420 / NV12, or uint16 I420_16 / P016 (4:2:0, or with RRV_LAY_422 / RRV_LAY_444)");
+    // the views of the whole contiguous frames on both sides and of the window; they live until the pipeline has returned (it is synchronous)
+    const rrv_image_view full = contiguous_of(in, SH, SW), win = window_of(full, *p), vout = contiguous_of(od, SH, SW);
+    x.vfull = &full; x.vin = &win; x.vout = &vout;
+    return scaled_host(h, who, false, frames, in, out, od, flags, x);
 }
 
 // The matrix of the YUV input forms, the inverse of rrv_yuv_matrix's transform: Y' = (Y - 16) 255/219, C' = (C - 128) 255/224 (full range: Y' = Y,

@@ -531,10 +531,82 @@ def shot_runs(shots, lo, hi):
     return [k for k, (a, b) in enumerate(shots) for _ in range(max(a, lo), min(b, hi))]
 
 
+def resolve_picture(picture, model, world=1, gpu_jpeg=False, jpeg_in=False, deliver=None):
+    """The picture= keyword of stylize_files / stylize_y4m: None (off), "auto" (stays: the detection pass follows), "WxH+X+Y" or
+    (y0, x0, h, w) -> None, "auto" or the window as a tuple.  ValueError, in words, for what is not offered with a window: several ranks,
+    the JPEG forms on the GPU, a delivered size other than the source's."""
+    import importlib
+    video = importlib.import_module("rerevst-code_amd.video")
+    if picture is None:
+        return None
+    if world > 1:
+        raise ValueError("picture runs on one rank: a window per shot on several ranks is not offered")
+    if gpu_jpeg or jpeg_in:
+        raise ValueError("picture does not combine with gpu_jpeg / gpu_decode (or an .avi input): the JPEG input and output forms are not offered with a window")
+    if getattr(model, "picture_detection", False) is not True or getattr(model, "transfer_frames", None) is None:
+        raise ValueError("picture needs a model with transfer_frames(picture=) and scan_frames (Stylization.picture_detection)")
+    if deliver is not None and deliver != "source":
+        raise ValueError("picture: the frames written keep the source's size (out_size is implied to be 'source'), got out_size=%r" % (deliver,))
+    if isinstance(picture, str):
+        return "auto" if picture == "auto" else video.parse_picture(picture)
+    if len(picture) != 4:
+        raise ValueError("picture is 'auto', 'WxH+X+Y' or (y0, x0, h, w), got %r" % (picture,))
+    return tuple(int(v) for v in picture)
+
+
+def _size_runs(sizes, i0, i1):
+    """[(first, last)] of the runs of equally sized frames within i0 .. i1 - 1"""
+    runs = []
+    for i in range(i0, i1):
+        if runs and tuple(sizes[runs[-1][0]]) == tuple(sizes[i]):
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return [(a, b) for a, b in runs]
+
+
+def detect_pass(model, n, fetch, sizes, chunk=32, log=print, shots=None, shot_params=None, picture_params=None, **scan_kw):
+    """The detection pass of picture="auto", with shots="auto" one pass for both results: every frame through model.scan_frames in chunks
+    (each frame is decoded and uploaded once), then the cuts as detect_shots finds them and one window per shot (without shots: one for the
+    file) from that shot's profiles by video.detect_picture.  shots: "auto", the given list or None; picture_params: threshold= of the
+    profile and the rule's line= / vote= / dark= / gap= / min_bar= / min_keep=.  Returns (shots, windows): windows[k] belongs to
+    (shots or [(0, n)])[k].  Logs both."""
+    import importlib
+    video = importlib.import_module("rerevst-code_amd.video")
+    rule = dict(picture_params or {})
+    threshold = int(rule.pop("threshold", 10))
+    auto = isinstance(shots, str) and shots == "auto"
+    chunk = max(1, int(chunk))
+    starts = list(range(0, n, chunk))
+    sigs, profs, ahead = [], [], fetch(0, min(n, chunk))
+    for k in range(len(starts)):
+        frames = ahead.result()
+        if k + 1 < len(starts):
+            ahead = fetch(starts[k + 1], min(n, starts[k + 1] + chunk))
+        for a, b in _size_runs(sizes, starts[k], starts[k] + len(frames)):      # (a call takes frames of one size)
+            sig, prof = model.scan_frames(frames[a - starts[k]:b - starts[k]], threshold=threshold, signatures=auto, profiles=True, **scan_kw)
+            profs += list(prof)
+            if auto:
+                sigs.append(sig)
+    if auto:
+        D = video.shot_distances(np.concatenate(sigs), sizes)
+        cuts = video.detect_cuts(D, forced=video.size_changes(sizes), **(shot_params or {}))
+        shots = video.shots_from_cuts(cuts, n)
+        log("Shots: %d in %d frames, starting at %s" % (len(shots), n, ", ".join(str(c) for c in cuts)))
+    windows = []
+    for a, b in shots or [(0, n)]:
+        if len(set(tuple(sz) for sz in sizes[a:b])) != 1:
+            raise ValueError("picture: the frames %d..%d have several sizes; one window covers frames of one size (shots=\"auto\" cuts at every size change)" % (a, b - 1))
+        H, W = sizes[a]
+        windows.append(video.detect_picture(np.stack(profs[a:b]), H, W, **rule))
+        log("Picture area of frames %d..%d (%d x %d): %s" % (a, b - 1, W, H, video.format_picture(windows[-1])))
+    return shots, windows
+
+
 def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=24, chunk=32, log=print,
                   io_threads=None, rank=0, world=1, broadcast=None, barrier=None, stats=None, write_frames=True, yuv=("bt601", False), bit_depth=8,
                   chroma="420", work_size=None, out_size=None, guided=None, composite=None, gpu_jpeg=None, gpu_decode=False, frame_data=None,
-                  shots=None, write_shots=None, shot_params=None):
+                  shots=None, write_shots=None, shot_params=None, picture=None, picture_params=None):
     """The reference script's main flow for one style and one frame list; returns the frame paths THIS rank wrote.
 
     Throughput form: the three stages of the reference's loop — cv2.imread, framework.transfer,
@@ -570,7 +642,15 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
     straddles a shot boundary, and every other option works unchanged (compositing still goes by the absolute frame number).  "auto" runs a
     detection pass first (detect_shots: every frame through model.shot_signatures, image files decoded on the worker threads -- so each is
     decoded twice; a shots file avoids that -- JPEG streams passed as bytes; shot_params: the rule's threshold= / min_len=).  One rank, the
-    global model.  write_shots: a path that receives the shots' first frames (video.write_shots), whatever gave them."""
+    global model.  write_shots: a path that receives the shots' first frames (video.write_shots), whatever gave them.
+    picture: None (default: every flow makes the calls it always made), "auto", "WxH+X+Y" or (y0, x0, h, w): the active picture area inside
+    letterbox / pillarbox bars (INTEGRATION.md "Picture area").  Only that window is sampled (add(picture=)) and stylized
+    (transfer_frames(picture=)); the frames and videos written keep the source's size, and outside the window they are the source, so
+    subtitles and logos inside a bar pass through.  "auto" runs a detection pass first (detect_pass: model.scan_frames; with
+    shots="auto" it is ONE pass for both results) and finds one window per shot from that shot's frames (without shots: one for the list,
+    whose frames then share one size); picture_params: threshold= of the line profile and video.detect_picture's line= / vote= / dark= /
+    gap= / min_bar= / min_keep= (none of them tuned on real footage).  A matte of composite= covers the window.  One rank; not with
+    gpu_jpeg, gpu_decode / frame_data or an out_size other than "source".  stats["pictures"] lists the windows as WxH+X+Y."""
     import importlib
     import time
     from collections import deque
@@ -633,11 +713,25 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         scale_kw = dict(scale_kw, guide="source", guide_radius=guided[0], guide_eps=guided[1])
     add_kw = {} if work is None else {"work_size": work}                   # (a sampled frame is never delivered)
     comp = Compositing(n, **composite) if composite else None
+    picture = resolve_picture(picture, model, world, gpu_jpeg is not None, jpeg_sizes is not None, deliver)
+    windows = None            # with picture: one window per entry of (shots or [(0, n)])
     # the size of the frame delivered for a source frame of (H, W)
-    out_size = (lambda hw: hw) if deliver == "source" else (lambda hw: deliver) if deliver is not None else (lambda hw: hw) if work is None else (lambda hw: work)
+    out_size = (lambda hw: hw) if deliver == "source" or picture is not None else (lambda hw: deliver) if deliver is not None else (lambda hw: hw) if work is None else (lambda hw: work)
     t_start = time.perf_counter()
     shot_s = 0.0              # preparation passes that ran between chunks (shots)
     with ThreadPoolExecutor(nthreads) as pool:
+        if picture is not None:
+            all_sizes = list(pool.map(image_size, frame_paths))
+            if picture == "auto":
+                shots, windows = detect_pass(model, n, lambda i0, i1: _Gathered(pool.submit(read_image_bgr, p) for p in frame_paths[i0:i1]), all_sizes, chunk,
+                                             log, shots, shot_params, picture_params)
+            else:
+                if shots == "auto":
+                    shots = detect_shots(model, n, lambda i0, i1: _Gathered(pool.submit(read_image_bgr, p) for p in frame_paths[i0:i1]), all_sizes, chunk, log,
+                                         shot_params)
+                windows = [video.check_picture(picture, *all_sizes[a]) for a, _ in shots or [(0, n)]]
+                if len(set(all_sizes)) != 1:
+                    raise ValueError("picture: one window covers frames of one size, the list holds %d sizes" % len(set(all_sizes)))
         if shots == "auto":
             if jpeg_sizes is not None:
                 shots = detect_shots(model, n, lambda i0, i1: _Gathered(pool.submit(stream_of, i) for i in range(i0, i1)), jpeg_sizes, chunk, log,
@@ -648,6 +742,11 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
         if write_shots is not None and shots is not None:
             video.write_shots(write_shots, [a for a, _ in shots])
 
+        def window_of(i):                       # the window of frame i's shot, as the picture= keyword of add / transfer_frames ({}: no picture)
+            if windows is None:
+                return {}
+            return {"picture": next(w for w, (a, b) in zip(windows, shots or [(0, n)]) if a <= i < b)}
+
         def prepare(first, last):               # clean / add / compute over the frames first .. last - 1, as a video of their own
             ids = [first + i for i in video.sample_indices(last - first)]
             log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
@@ -657,7 +756,7 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                     model.add(data, in_format="jpeg", **add_kw)
             else:
                 for f in pool.map(read_image_bgr, [frame_paths[i] for i in ids]):
-                    model.add(f, **add_kw)
+                    model.add(f, **add_kw, **window_of(first))
             model.compute()
 
         def prepare_shot(i):                    # frame i is about to be stylized: its shot's state, if it is a shot's first frame
@@ -800,7 +899,10 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 src_hw = sizes[idx[0] - lo]
                 if jpeg_sizes is not None:
                     src = list(src[:len(idx)])
-                call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, out_size(src_hw)))
+                pic_kw = window_of(idx[0])
+                call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(idx, pic_kw["picture"][2:] if pic_kw else out_size(src_hw)))
+                if pic_kw:
+                    call_kw = dict(call_kw, **pic_kw)
                 if jpeg_sizes is not None:
                     call_kw = dict(call_kw, in_format="jpeg")
                 if jpeg_direct:
@@ -852,6 +954,8 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                 raise ValueError("strength / fade / matte / keep need a model with transfer_frames(strength=)")
             if gpu_jpeg is not None and hi > lo:
                 raise ValueError("gpu_jpeg needs a model with transfer_frames(out_format=\"jpeg\")")
+            if picture is not None and hi > lo:
+                raise ValueError("picture needs a model with transfer_frames(picture=)")
             if jpeg_sizes is not None and hi > lo:
                 raise ValueError("gpu_decode needs a model with transfer_frames(in_format=\"jpeg\")")
             tool = video.ReshapeTool()
@@ -892,12 +996,14 @@ def stylize_files(model, style_path, frame_paths, out_dir, video_path=None, fps=
                      frames_per_s=(hi - lo) / max(t_frames - t_prep - shot_s, 1e-9))
         if shots is not None:
             stats.update(shots=len(shots))
+        if windows is not None:
+            stats.update(pictures=[video.format_picture(w) for w in windows])
     return written
 
 
 def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None, chunk=32, log=print, stats=None, write_frames=True,
                 yuv=("bt601", False), io_threads=None, bit_depth=None, chroma=None, work_size=None, out_size=None,
-                guided=None, composite=None, shots=None, write_shots=None, shot_params=None):
+                guided=None, composite=None, shots=None, write_shots=None, shot_params=None, picture=None, picture_params=None):
     """stylize_files for a .y4m INPUT (Y4MReader): the frames stay 8-bit YUV 4:2:0 from the file to the GPU (add / transfer_frames with
     in_format="i420": the first kernel reads Y, Cb, Cr) — no image codec and no colour conversion on the host.  The input matrix is
     `yuv`'s standard with the range the file's XCOLORRANGE names; fps defaults to the file's rate.  video_path *.y4m with
@@ -916,7 +1022,9 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
     guided=(radius, eps) with out_size: guided delivery (transfer_frames with guide="source").
     composite=dict(strength=, fade=, matte=, keep=): as in stylize_files; the source mixed in is the file's frame as the GPU reads it.
     shots / write_shots / shot_params: as in stylize_files; the detection pass of "auto" reads the file's frames on the reader thread and
-    passes them to model.shot_signatures as they are (in_format, size), and the chunks start over at every shot."""
+    passes them to model.shot_signatures as they are (in_format, size), and the chunks start over at every shot.
+    picture / picture_params: as in stylize_files; the detection pass of "auto" passes the file's frames to model.scan_frames as they are,
+    and the frames written keep the file's size whatever work_size says."""
     import importlib
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -946,6 +1054,10 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
                 raise ValueError("guided needs out_size (the size of the frames read)")
             scale_kw.update(guide="source", guide_radius=guided[0], guide_eps=guided[1])
         comp = Compositing(n, **composite) if composite else None
+        picture = resolve_picture(picture, model, deliver=None if out_size is None or (OH, OW) == (H, W) else (OH, OW))
+        windows = None            # with picture: one window per entry of (shots or [(0, n)])
+        if picture is not None:
+            OH, OW = H, W
         fob = video.yuv_frame_bytes(OH, OW, chroma=out_chroma)      # samples of an output frame
         in_dtype, yuv_dtype = (np.uint8 if in_bits == 8 else np.uint16), (np.uint8 if out_bits == 8 else np.uint16)
         deep = lambda bits: {"bits": bits} if bits > 8 else {}
@@ -958,22 +1070,35 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
         encode, open_writer = video_sink(video_path, fps, yuv, bits=out_bits if y4m else 8, chroma=out_chroma) if video_path is not None else (None, None)
         t_start = time.perf_counter()
         model.set_yuv_input_matrix(yuv[0], reader.full_range, **deep(in_bits))
+
+        def read_frames(i0, i1):                 # the one reader thread: a chunk of the file's frames, as they are
+            buf = np.empty((i1 - i0, fb), np.uint8 if in_bits == 8 else np.uint16)
+            reader.read_run(i0, buf)
+            return buf
+        if picture == "auto":
+            shots, windows = detect_pass(model, n, lambda i0, i1: rpool.submit(read_frames, i0, i1), [size] * n, chunk, log, shots, shot_params, picture_params,
+                                         in_format=in_fmt, size=size)
+        elif picture is not None:
+            windows = [video.check_picture(picture, H, W)] * len(shots if isinstance(shots, list) else [0])
         if shots == "auto":
-            def read_frames(i0, i1):             # the one reader thread: a chunk of the file's frames, as they are
-                buf = np.empty((i1 - i0, fb), np.uint8 if in_bits == 8 else np.uint16)
-                reader.read_run(i0, buf)
-                return buf
             shots = detect_shots(model, n, lambda i0, i1: rpool.submit(read_frames, i0, i1), [size] * n, chunk, log, shot_params, in_format=in_fmt, size=size)
         if write_shots is not None and shots is not None:
             video.write_shots(write_shots, [a for a, _ in shots])
         model.prepare_style(read_image_bgr(style_path))
+        if windows is not None and len(windows) != len(shots or [0]):      # (a given window and shots="auto": one window, every shot)
+            windows = windows[:1] * len(shots or [0])
+
+        def window_of(i):                        # the window of frame i's shot, as the picture= keyword of add / transfer_frames ({}: no picture)
+            if windows is None:
+                return {}
+            return {"picture": next(w for w, (a, b) in zip(windows, shots or [(0, n)]) if a <= i < b)}
 
         def prepare(first, last):                # clean / add / compute over the frames first .. last - 1, as a video of their own
             ids = [first + i for i in video.sample_indices(last - first)]
             log("Preparations for Sequence-Level Global Feature Sharing (%d sampled frames)" % len(ids))
             model.clean()
             for i in ids:
-                model.add(reader.read(i), in_format=in_fmt, size=size, **add_kw)
+                model.add(reader.read(i), in_format=in_fmt, size=size, **add_kw, **window_of(first))
             model.compute()
         if getattr(model, "use_Global", True) and shots is None:
             prepare(0, n)
@@ -1027,7 +1152,10 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
                 prepare(c0, shot_first[c0])
                 shot_s += time.perf_counter() - t0
             t0 = time.perf_counter()
-            call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(range(c0, c0 + m), (OH, OW)))
+            pic_kw = window_of(c0)
+            call_kw = scale_kw if comp is None else dict(scale_kw, **comp.kw(range(c0, c0 + m), pic_kw["picture"][2:] if pic_kw else (OH, OW)))
+            if pic_kw:
+                call_kw = dict(call_kw, **pic_kw)
             if direct:
                 styled = model.transfer_frames(src, out=dst, out_format=out_fmt, in_format=in_fmt, size=size, **call_kw)
             else:
@@ -1057,6 +1185,8 @@ def stylize_y4m(model, style_path, y4m_path, out_dir, video_path=None, fps=None,
                      frames_per_s=n / max(t_frames - t_prep - shot_s, 1e-9))
         if shots is not None:
             stats.update(shots=len(shots))
+        if windows is not None:
+            stats.update(pictures=[video.format_picture(w) for w in windows])
     return written
 
 
@@ -1321,7 +1451,33 @@ def main(argv=None, model_factory=None):
     ap.add_argument("--shot-threshold", type=float, default=None, metavar="T", help="--shots auto: the smallest signature distance that can be a cut, 0..1 "
                     "(default 0.35; video.detect_cuts: an untuned design parameter)")
     ap.add_argument("--shot-min-len", type=int, default=None, metavar="N", help="--shots auto: the shortest shot, in frames (default 8; untuned likewise)")
+    ap.add_argument("--picture", default=None, metavar="auto|WxH+X+Y", help="stylize only the active picture area inside letterbox / pillarbox bars and pass the "
+                    "rest of the frame through from the source (one GPU, one style; not with --gpu-jpeg, --gpu-decode or an .avi input): 'auto' finds the "
+                    "bars on the GPU in a pass over every frame first (with --shots auto one pass for both, and one window per shot), WxH+X+Y names the window")
+    ap.add_argument("--picture-threshold", type=int, default=None, metavar="T", help="--picture auto: a pixel is lit when its luma is above T, 0..254 (default 10: "
+                    "ffmpeg cropdetect's 24 on limited-range codes moved to full range; an untuned design parameter)")
+    ap.add_argument("--picture-min-bar", type=int, default=None, metavar="N", help="--picture auto: a bar thinner than N lines is dropped (default 4; untuned likewise)")
     args = ap.parse_args(argv)
+    picture_kw = {}
+    if args.picture != "auto" and (args.picture_threshold is not None or args.picture_min_bar is not None):
+        ap.error("--picture-threshold and --picture-min-bar belong to --picture auto: nothing else detects bars")
+    if args.picture is not None:
+        if args.gpus > 1:
+            ap.error("--picture runs on one GPU (--gpus %d): a window per shot on several ranks is not offered" % args.gpus)
+        if len(args.style) > 1:
+            ap.error("--picture runs the single-style flow (%d styles): blended models are not offered with a window" % len(args.style))
+        if args.gpu_jpeg or args.gpu_decode or args.frames.lower().endswith(".avi"):
+            ap.error("--picture does not combine with --gpu-jpeg, --gpu-decode or an .avi input: the JPEG forms are not offered with a window")
+        if args.picture_threshold is not None and not 0 <= args.picture_threshold <= 254:
+            ap.error("--picture-threshold is a luma value, 0..254")
+        if args.picture_min_bar is not None and args.picture_min_bar < 0:
+            ap.error("--picture-min-bar is a number of lines, 0 or more")
+        if args.picture != "auto":
+            try:
+                __import__("importlib").import_module("rerevst-code_amd.video").parse_picture(args.picture)
+            except ValueError as e:
+                ap.error("--picture: %s" % e)
+        picture_kw = dict(picture=args.picture, picture_params={k: v for k, v in (("threshold", args.picture_threshold), ("min_bar", args.picture_min_bar)) if v is not None})
     shot_kw = {}
     if args.shots != "auto" and (args.shot_threshold is not None or args.shot_min_len is not None):
         ap.error("--shot-threshold and --shot-min-len belong to --shots auto: nothing else detects cuts")
@@ -1470,7 +1626,7 @@ def main(argv=None, model_factory=None):
     if y4m_in:
         stylize_y4m(model, args.style[0], args.frames, args.out, args.video, args.fps, chunk=args.chunk, log=log, stats=stats,
                     write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), io_threads=args.io_threads or None, bit_depth=args.bit_depth, chroma=args.chroma,
-                    work_size=work_size, out_size=out_size, guided=guided, composite=composite, **shot_kw)
+                    work_size=work_size, out_size=out_size, guided=guided, composite=composite, **shot_kw, **picture_kw)
     elif len(args.style) > 1:
         stylize_files_multistyle(model, args.style, list_frames(args.frames), args.out, args.video, args.fps, io_threads=args.io_threads or None, log=log,
                                  write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420")
@@ -1488,7 +1644,7 @@ def main(argv=None, model_factory=None):
             stylize_files(model, args.style[0], frame_list, args.out, args.video, args.fps, chunk=args.chunk, log=log,
                           io_threads=args.io_threads or None, rank=rank, world=world, broadcast=broadcast, barrier=barrier, stats=stats,
                           write_frames=not args.no_frames, yuv=(args.yuv, args.full_range), bit_depth=args.bit_depth or 8, chroma=args.chroma or "420", work_size=work_size,
-                          out_size=out_size, guided=guided, composite=composite, **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}), **decode_kw, **shot_kw)
+                          out_size=out_size, guided=guided, composite=composite, **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}), **decode_kw, **shot_kw, **picture_kw)
         except ValueError as e:
             if not decode_kw:
                 raise

@@ -10,7 +10,7 @@ import re
 import numpy as np
 
 from . import _lib
-from .video import YUV_FORMATS, YUV_FORMAT_NAMES, YUV_STANDARDS, _yuv_depth, chroma_plane_size, yuv_frame_bytes  # noqa: F401  (the YUV format table lives there)
+from .video import YUV_FORMATS, YUV_FORMAT_NAMES, YUV_STANDARDS, _yuv_depth, check_picture, chroma_plane_size, yuv_frame_bytes  # noqa: F401  (the YUV format table lives there)
 from .weights import weight_table, load_checkpoint
 
 
@@ -379,6 +379,18 @@ class ImageView():
         end = (self.frames - 1) * int(frame_stride) + max(o + (rows - 1) * p + ln for o, p, (ln, rows) in zip(plane_offset, pitch, planes))
         if end > storage.numel():
             raise ValueError("the view addresses %d elements, storage holds %d" % (end, storage.numel()))
+
+    def window(self, y0, x0, h, w):
+        """The view of the window (y0, x0, h, w) of every frame (rrv_picture_view; include/rerevst_hip.h "Picture area"): an ImageView of
+        h x w frames in the same storage, plane offsets moved, pitches and the frame stride kept.  The window follows video.check_picture's
+        rule (even origin, at least 8 x 8, even sizes unless it reaches the frame's edge), so that no chroma sample straddles its edge."""
+        y0, x0, h, w = check_picture((y0, x0, h, w), self.H, self.W)
+        win = _lib.ImageView()
+        if _lib.load().rrv_picture_view(C.byref(self.view), self.H, self.W, C.byref(_lib.Picture(y0, x0, h, w)), C.byref(win)) != 0:
+            raise ValueError("the library refuses the window (%d, %d, %d, %d) of %d x %d frames" % (y0, x0, h, w, self.H, self.W))
+        o = object.__new__(ImageView)
+        o.storage, o.layout, o.H, o.W, o.frames, o.view = self.storage, self.layout, h, w, self.frames, win
+        return o
 
     def with_space(self, space, what):
         """a copy of the library struct with the call's value space ('pixel' for uint8 and the YUV formats)"""
@@ -785,6 +797,18 @@ def _composite_args(strength, matte, keep, style_weights, style_masks, B, H, W, 
     return CompositeArgs(strength, matte, keep, B, H, W, tensors, device)
 
 
+def _picture_args(picture, H, W, out_size, style_weights, style_masks, jpeg):
+    """The checked rrv_picture of a picture= keyword on H x W frames, and what does not combine with it: the delivered frame has the
+    source's size, so out_size is implied to be "source"; the blended and masked models and the JPEG forms are not offered with a window"""
+    if style_weights is not None or style_masks is not None:
+        raise ValueError("picture= does not combine with style_weights / style_masks: blended and masked models are not offered with a window")
+    if jpeg:
+        raise ValueError('picture= does not combine with the "jpeg" input and output forms: decode or encode with the JPEG entries around the call')
+    if out_size is not None and _out_size(out_size, (H, W)) != (H, W):
+        raise ValueError("picture=: the delivered frame has the source's size (out_size is implied to be 'source'), got out_size=%r" % (out_size,))
+    return _lib.Picture(*check_picture(picture, H, W))
+
+
 def _host_in_desc(in_format):
     """rrv_image_desc of host frames as the scaled host entries take them: uint8 BGR HWC, or a YUV format by name"""
     if in_format == "bgr":
@@ -946,6 +970,10 @@ class Stylization():
     # shot_signatures(frames, in_format=, size=) computes the signatures a cut detector compares (the rrv_shot_signature entries):
     # driver.stylize_files / stylize_y4m ask for it with shots="auto"
     shot_detection = True
+    # picture_profiles / scan_frames compute the line profiles video.detect_picture reads, and picture=(y0, x0, h, w) on add, add_tensor,
+    # transfer_batch, transfer_frames and transfer_tensor stylizes inside that window of the frame (the rrv_*picture* entries):
+    # driver.stylize_files / stylize_y4m ask for both with picture="auto"
+    picture_detection = True
 
     def __init__(self, checkpoint, cuda=True, use_Global=True, device=None, style_num=1):
         if not cuda:
@@ -1007,15 +1035,19 @@ class Stylization():
         if bi > 8 or bo > 8:
             self._chk(self._lib.rrv_set_yuv_depth(self._h, bi if bi > 8 else 0, bo if bo > 8 else 0))
 
-    def add(self, patch, in_format="bgr", size=None, work_size=None):
+    def add(self, patch, in_format="bgr", size=None, work_size=None, picture=None):
         """A sampled frame: uint8 BGR HWC, or with in_format "i420" / "nv12" and size=(H, W) 8-bit YUV 4:2:0 bytes
         [yuv_frame_bytes(H, W)] (or [B][..]: every frame, in order) read by the first kernel (rrv_add_from_yuv); in_format "i420p10" /
         "i420p12" / "i420p16" / "p010" / "p012" / "p016": uint16 samples of that depth.  (The depth is read when the deferred encoding
         runs: add frames of one depth between clean() and compute().)
         work_size=(H, W): the frame is resampled to that size on the GPU first, as transfer_frames(work_size=) does (rrv_add_scaled);
-        size= stays the size of the frame as passed."""
+        size= stays the size of the frame as passed.
+        picture=(y0, x0, h, w): only that window of the frame is added (rrv_add_picture; include/rerevst_hip.h "Picture area"): the saved
+        state equals, byte for byte, that of adding the cropped frame; with work_size the window is resampled to it.  Not with "jpeg"."""
         self._global_only("add")
         work = None if work_size is None else _work_size(work_size)
+        if picture is not None and in_format == "jpeg":
+            _picture_args(picture, 8, 8, None, None, None, True)
         if in_format == "jpeg":      # (rrv_add_from_jpeg: one stream, or a list of them; the size comes from the stream)
             if size is not None:
                 raise ValueError('in_format="jpeg": the size comes from the streams, size= does not apply')
@@ -1035,9 +1067,12 @@ class Stylization():
         else:
             a = _u8_image(patch, "patch")[None]
             H, W = a.shape[1:3]
+        pic = None if picture is None else _picture_args(picture, H, W, None, None, None, False)
         for f in a:
             src = f.ctypes.data_as(C.c_void_p)
-            if work is not None:
+            if pic is not None:
+                self._chk(self._lib.rrv_add_picture(self._h, src, _host_in_desc(in_format), H, W, C.byref(pic), *(work if work is not None else (0, 0))))
+            elif work is not None:
                 self._chk(self._lib.rrv_add_scaled(self._h, src, _host_in_desc(in_format), H, W, *work))
             elif in_format != "bgr":
                 self._chk(self._lib.rrv_add_from_yuv(self._h, src, YUV_FORMATS[in_format].layout, H, W))
@@ -1218,18 +1253,67 @@ class Stylization():
             self._chk(self._lib.rrv_shot_signature_view_device(self._h, p, C.byref(v), nb, src.H, src.W, q, stream))
         return out
 
-    def add_tensor(self, x, *, space="pixel", layout="nchw", size=None, work_size=None):
+    def scan_frames(self, frames, in_format="bgr", size=None, threshold=10, signatures=True, profiles=True):
+        """The whole detection pass over host frames in one upload (rrv_scan_frames; include/rerevst_hip.h "Picture area"): returns
+        (signatures, profiles), np.uint32 [B][16][32] as shot_signatures gives them, word for word, and np.uint32 [B][H + W] as
+        picture_profiles does; the one not asked for is None (asking for neither is a ValueError).  frames: one [B][H][W][3] uint8 BGR
+        array or a list of equally sized frames, or with in_format a YUV format name and size=(H, W) the samples [B][..].  threshold: the
+        profile's, 0..254 (10: ffmpeg cropdetect's 24 on limited-range codes moved to full range; not tuned on real footage)."""
+        if not signatures and not profiles:
+            raise ValueError("scan_frames: neither signatures nor profiles asked for")
+        if in_format == "jpeg":
+            raise ValueError('scan_frames: in_format="jpeg" is not offered (shot_signatures takes JPEG streams)')
+        if in_format != "bgr":
+            a, H, W = yuv_frames_args(frames, in_format, size)
+            self._yuv_depth(in_format)
+        else:
+            a = _u8_frames(frames, "frame")
+            H, W = a.shape[1:3]
+        B = len(a)
+        sig = np.empty((B, 16, 32), np.uint32) if signatures else None
+        prof = np.empty((B, H + W), np.uint32) if profiles else None
+        self._chk(self._lib.rrv_scan_frames(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, H, W, int(threshold),
+                                            sig.ctypes.data_as(C.c_void_p) if signatures else None, prof.ctypes.data_as(C.c_void_p) if profiles else None))
+        return sig, prof
+
+    def picture_profiles(self, frames, in_format="bgr", size=None, threshold=10):
+        """The line profiles of host frames (include/rerevst_hip.h "Picture area"): np.uint32 [B][H + W], per frame the lit pixels of every
+        row, then of every column (video.picture_profile restates it), computed on the GPU; video.detect_picture turns them into the
+        active picture area.  scan_frames with the profiles alone."""
+        return self.scan_frames(frames, in_format=in_format, size=size, threshold=threshold, signatures=False, profiles=True)[1]
+
+    def picture_profiles_tensor(self, x, *, space="pixel", layout="nchw", size=None, threshold=10):
+        """picture_profiles for frames already on the handle's GPU (rrv_picture_profile_view_device), with resample_tensor's input
+        conventions.  Runs in the order of the current stream and returns an int32 tensor [B, H + W] (B = 1 for an unbatched x) on x's
+        device: the uint32 words of the profile, whose counts never reach 2^31.  Equals resample_tensor(x, (H, W)) followed by the
+        kernels, bit for bit."""
+        import torch
+        src = self._source(x, space, layout, size)
+        self._yuv_depth(src.layout, None)
+        n = src.H + src.W
+        out = torch.empty((src.B, n), dtype=torch.int32, device=src.tensor.device)
+        stream, v = self._stream(src.tensor), _whole_view(src, src.H, src.W)
+        for _, nb, p, q in _chunks(src.B, (src.ptr, src.step), (out.data_ptr(), 4 * n)):
+            self._chk(self._lib.rrv_picture_profile_view_device(self._h, p, C.byref(v), nb, src.H, src.W, int(threshold), q, stream))
+        return out
+
+    def add_tensor(self, x, *, space="pixel", layout="nchw", size=None, work_size=None, picture=None):
         """add for sampled frames already on the handle's GPU (transfer_tensor's input conventions): one image, or a batch
         [B,3,H,W] / [B,H,W,3] whose images are added in order.  work_size=(H, W): each frame is resampled to that size on the GPU
-        first (rrv_add_scaled_view_device), as transfer_tensor(work_size=) does; x may then also be a YUV tensor with size=(SH, SW)."""
+        first (rrv_add_scaled_view_device), as transfer_tensor(work_size=) does; x may then also be a YUV tensor with size=(SH, SW).
+        picture=(y0, x0, h, w): only that window of each frame is added (rrv_add_picture_view_device), as add(picture=) does; x may then
+        also be a YUV tensor with size=(SH, SW)."""
         self._global_only("add")
         work = None if work_size is None else _work_size(work_size)
-        src = self._source(x, space, layout, size, yuv=work is not None)
+        src = self._source(x, space, layout, size, yuv=work is not None or picture is not None)
+        pic = None if picture is None else _picture_args(picture, src.H, src.W, None, None, None, False)
         self._yuv_depth(src.layout, None)
         stream = self._stream(src.tensor)
-        v = _whole_view(src, src.H, src.W) if work is not None else src.view
+        v = _whole_view(src, src.H, src.W) if work is not None or pic is not None else src.view
         for _, _, p in _chunks(src.B, (src.ptr, src.step), chunk=1):      # a surface, a crop or a pitched tensor: each frame is compacted on the GPU
-            if work is not None:
+            if pic is not None:
+                self._chk(self._lib.rrv_add_picture_view_device(self._h, p, C.byref(v), src.H, src.W, C.byref(pic), *(work if work is not None else (0, 0)), stream))
+            elif work is not None:
                 self._chk(self._lib.rrv_add_scaled_view_device(self._h, p, C.byref(v), src.H, src.W, *work, stream))
             elif v is not None:
                 self._chk(self._lib.rrv_add_view_device(self._h, p, C.byref(v), src.H, src.W, stream))
@@ -1316,11 +1400,14 @@ class Stylization():
         self._chk(self._entry(name, _out_u8(dtype))(self._h, C.c_void_p(d_in_ptr), B, H, W, C.c_void_p(d_out_ptr)))
 
     def _host_frames(self, frames, out, dtype, style_weights, style_masks, pad_crop, out_format="bgr", in_format="bgr", size=None, work_size=None,
-                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None, jpeg=None):
+                     out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None, jpeg=None, picture=None):
         """transfer_batch (pad_crop False) / transfer_frames (True): the host array of the frames (uint8 BGR, or YUV 4:2:0 samples for
         size=(H, W)), the checked masks or weights, the output in out_format, and the C entry of that combination (_HOST_ENTRIES).
         jpeg: (quality, chroma, restart, cap) of out_format="jpeg" (rrv_transfer_jpeg): a list of bytes comes back"""
         is_jpeg = out_format == "jpeg"
+        if picture is not None:
+            return self._host_picture(frames, out, dtype, style_weights, style_masks, out_format, in_format, size, work_size, out_size, guide, guide_radius,
+                                      guide_eps, strength, matte, keep, picture)
         if is_jpeg:
             _jpeg_alone(style_weights, style_masks, 'out_format="jpeg"')
             if out is not None or np.dtype(dtype) != np.float32:
@@ -1398,6 +1485,33 @@ class Stylization():
         self._chk(getattr(self._lib, name)(self._h, *args))
         return out
 
+    def _host_picture(self, frames, out, dtype, style_weights, style_masks, out_format, in_format, size, work_size, out_size, guide, guide_radius, guide_eps,
+                      strength, matte, keep, picture):
+        """picture= of transfer_batch / transfer_frames (rrv_transfer_picture): the window is stylized, the frame comes back at its own size"""
+        if in_format == "jpeg" or out_format == "jpeg":
+            _picture_args(picture, 8, 8, None, None, None, True)
+        yuv_out = out_format != "bgr"
+        if yuv_out and out_format not in YUV_FORMATS:
+            raise ValueError("out_format must be 'bgr', %s, got %r" % (YUV_FORMAT_NAMES, out_format))
+        if in_format != "bgr":
+            a, H, W = yuv_frames_args(frames, in_format, size)
+        else:
+            a = _u8_frames(frames, "frame")
+            H, W = a.shape[1:3]
+        B = a.shape[0]
+        pic = _picture_args(picture, H, W, out_size, style_weights, style_masks, False)
+        work = (0, 0) if work_size is None else _work_size(work_size)
+        r, eps = _guide_args(guide, guide_radius, guide_eps, "source") if guide is not None else (0, 0.0)
+        comp = _composite_args(strength, matte, keep, None, None, B, pic.h, pic.w)
+        req = comp.request(0, B) if comp is not None else None
+        out, u8 = _output((B, H, W, 3), dtype, out, out_format)
+        self._yuv_depth(in_format, out_format)
+        desc = _lib.ImageDesc(_lib.DT_U16 if out.dtype == np.uint16 else _lib.DT_U8 if u8 else _lib.DT_F32,
+                              YUV_FORMATS[out_format].layout if yuv_out else _lib.LAY_HWC_BGR, _lib.SP_PIXEL)
+        self._chk(self._lib.rrv_transfer_picture(self._h, a.ctypes.data_as(C.c_void_p), _host_in_desc(in_format), B, H, W, C.byref(pic), *work, r, eps,
+                                                 C.byref(req) if req is not None else None, out.ctypes.data_as(C.c_void_p), desc, self._flags(True)))
+        return out
+
     def _host_from_jpeg(self, streams, out, dtype, style_weights, style_masks, pad_crop, out_format, j, jpeg, size, work_size, out_size, guide, guide_radius,
                         guide_eps, strength, matte, keep):
         """in_format="jpeg" of transfer_batch / transfer_frames (rrv_transfer_from_jpeg, rrv_transfer_jpeg_from_jpeg): `streams` a list of bytes,
@@ -1446,7 +1560,7 @@ class Stylization():
 
     def transfer_batch(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
                        work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None,
-                       jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
+                       jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None, picture=None):
         """Stylize equally sized uint8 BGR frames (a list, or one [B][H][W][3] array) in one call; sub-batches are
         pipelined inside the library (copy in / kernels / copy out).  `out`: optional float32 or uint8 [B][H][W][3] array
         to fill instead of allocating a fresh one (its dtype selects the output format; else `dtype` does).
@@ -1499,13 +1613,19 @@ class Stylization():
         GPU (rrv_transfer_from_jpeg / rrv_transfer_jpeg_from_jpeg; include/rerevst_hip.h "JPEG input"); the size comes from the streams
         (size= is refused), the colour space is JFIF's whatever set_yuv_input_matrix holds, and it combines with work_size, out_size, guide,
         strength / matte / keep, every out_format (no matte with out_format="jpeg") and dtype; not with style_weights / style_masks.  A
-        stream the parser refuses or a corrupt frame raises ValueError with the frame's index and the library's words."""
+        stream the parser refuses or a corrupt frame raises ValueError with the frame's index and the library's words.
+        picture=(y0, x0, h, w): the active picture area (rrv_transfer_picture; include/rerevst_hip.h "Picture area").  Only that window of
+        the frames is stylized, with transfer_frames' geometry whichever of the two is called (reflect padding inside the window, so no bar
+        bends the strokes), and the frames come back at their own size: outside the window every pixel is the source's, passed through the
+        input and output conversions (uint8 BGR in and out: the source's bytes).  out_size is implied to be "source" (another size is a
+        ValueError).  It combines with work_size (the window is resampled to it), guide, strength / matte / keep (a matte has the window's
+        size [B or 1][h][w]), in_format, out_format and dtype; not with style_weights / style_masks or the "jpeg" forms (ValueError)."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, False, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
+                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap), picture)
 
     def transfer_frames(self, frames, out=None, dtype=np.float32, style_weights=None, style_masks=None, out_format="bgr", in_format="bgr", size=None,
                         work_size=None, out_size=None, guide=None, guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None,
-                        jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None):
+                        jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None, jpeg_cap=None, picture=None):
         """UNPADDED uint8 BGR frames (a list, or one [B][H][W][3] array) -> [B][H][W][3] float32 stylized frames.
         The reference driver's ReshapeTool.process + crop (test/generate_real_video.py:61-83, :167) run on the
         device, without the padded copies on the host or over PCIe: the same picture as pad -> transfer -> crop (bit-identical
@@ -1524,9 +1644,10 @@ class Stylization():
         guide / guide_radius / guide_eps: guided delivery, as in transfer_batch; any working size.
         strength / matte / keep: compositing with the frames as passed, as in transfer_batch; any working size.
         out_format="jpeg" with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap: a list of `bytes`, as in transfer_batch.
-        in_format="jpeg": a list of `bytes` in, as in transfer_batch."""
+        in_format="jpeg": a list of `bytes` in, as in transfer_batch.
+        picture=(y0, x0, h, w): the active picture area, as in transfer_batch."""
         return self._host_frames(frames, out, dtype, style_weights, style_masks, True, out_format, in_format, size, work_size, out_size, guide,
-                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap))
+                                 guide_radius, guide_eps, strength, matte, keep, (jpeg_quality, jpeg_chroma, jpeg_restart, jpeg_cap), picture)
 
     def transfer_frames_device(self, d_in_ptr, B, H, W, d_out_ptr, dtype=np.float32):
         """Same on HBM buffers ([B][H][W][3] uint8 -> [B][H][W][3] float32 or uint8), asynchronous on the library stream."""
@@ -1536,7 +1657,7 @@ class Stylization():
     def transfer_tensor(self, x, *, space="pixel", out_space="pixel", out_dtype=None, layout="nchw", out_layout=None,
                         pad_crop=False, out=None, style_weights=None, style_masks=None, size=None, work_size=None, out_size=None, guide=None,
                         guide_radius=4, guide_eps=1e-3, strength=None, matte=None, keep=None, jpeg_quality=90, jpeg_chroma="420", jpeg_restart=None,
-                        jpeg_cap=None):
+                        jpeg_cap=None, picture=None):
         """Stylize torch tensors already on the handle's GPU, ordered on torch.cuda.current_stream(x.device) (no host sync).
 
         x: [B,3,H,W] RGB (layout="nchw", torch's convention) or [B,H,W,3] BGR ("nhwc", cv2's); unbatched [3,H,W] / [H,W,3]
@@ -1585,10 +1706,32 @@ class Stylization():
         out_layout="jpeg": the delivered frame is encoded as baseline JPEG on the GPU (rrv_transfer_jpeg_view_device; include/rerevst_hip.h
         "JPEG output") with jpeg_quality / jpeg_chroma / jpeg_restart / jpeg_cap as in transfer_batch.  Returns (uint8 [B][cap] tensor, int32
         [B] sizes tensor) in stream order, as encode_jpeg_tensor does (framework.jpeg_frames reads them on the host); the call equals the
-        float32 "nhwc" call followed by encode_jpeg_tensor.  Not with style_weights / style_masks, out=, out_dtype= or another out_space."""
+        float32 "nhwc" call followed by encode_jpeg_tensor.  Not with style_weights / style_masks, out=, out_dtype= or another out_space.
+        picture=(y0, x0, h, w): the active picture area (rrv_transfer_picture_view_device; include/rerevst_hip.h "Picture area"), as in
+        transfer_batch: pad_crop is forced, the output has the source's size (out_size is implied to be "source") in any out_layout /
+        out_space / out_dtype or `out`, and a matte has the window's size.  The call equals resample_tensor(x, (H, W)) as the canvas, the
+        float32 "nhwc" pad_crop call on the window (ImageView.window or the crop) with the same work_size / guide / strength / matte / keep and
+        out_size="source" written into the canvas's window, and deliver_tensor(canvas, (H, W), ..), bit for bit in a fixed kernel mode."""
         import torch
         composite = strength is not None or matte is not None or keep is not None
         is_jpeg = isinstance(out_layout, str) and out_layout == "jpeg"
+        if picture is not None:
+            src = self._source(x, space, layout, size)
+            pic = _picture_args(picture, src.H, src.W, out_size, style_weights, style_masks, is_jpeg)
+            work = (0, 0) if work_size is None else _work_size(work_size)
+            g_r, g_eps = _guide_args(guide, guide_radius, guide_eps, "source") if guide is not None else (0, 0.0)
+            comp = _composite_args(strength, matte, keep, None, None, src.B, pic.h, pic.w, tensors=True, device=self.device)
+            dst = self._target(out, out_layout, out_space, out_dtype, src.B, src.H, src.W, src.batched, src.tensor, default_layout=src.layout)
+            if comp is not None:
+                comp.on_device(src.tensor)
+            vi, vo = _whole_view(src, src.H, src.W), _whole_view(dst, src.H, src.W)
+            self._yuv_depth(src.layout, dst.layout)
+            flags, stream = self._flags(True, on_stream=True), self._stream(src.tensor)
+            for b0, nb, p, q in _chunks(src.B, (src.ptr, src.step), (dst.ptr, dst.step)):
+                req = comp.request(b0, nb) if comp is not None else None
+                self._chk(self._lib.rrv_transfer_picture_view_device(self._h, p, C.byref(vi), nb, src.H, src.W, C.byref(pic), *work, g_r, g_eps,
+                                                                     C.byref(req) if req is not None else None, q, C.byref(vo), flags, stream))
+            return dst.result
         if is_jpeg:
             _jpeg_alone(style_weights, style_masks, 'out_layout="jpeg"')
             if out is not None or out_dtype is not None or out_space != "pixel":

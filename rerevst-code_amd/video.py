@@ -464,6 +464,136 @@ def read_shots(path, n):
     return cuts
 
 
+# ===== picture area: the line profile, the rule that finds the bars, the window as text (INTEGRATION.md "Picture area") =====
+def picture_profile(frame, threshold=10):
+    """The line profile of one frame (include/rerevst_hip.h "Picture area"; Stylization.picture_profiles computes it on the GPU), restated in
+    numpy: frame [H][W][3] BGR in the PIXEL space, any real dtype, H, W >= 8 -> uint32 [H + W]: row_cnt[H], the lit pixels of every row,
+    then col_cnt[W], of every column.  Integers from the rounding on, so the GPU equals it word for word: c8 = clamp(rint(v), 0, 255) per
+    channel (half to even; NaN and everything not above 0 give 0, +inf gives 255), Y = (29 B8 + 150 G8 + 77 R8 + 128) >> 8, and a pixel is
+    lit iff Y > threshold (0..254).  The default of 10 is ffmpeg cropdetect's default of 24 on limited-range codes, moved to the full-range
+    values the first kernel produces; nobody has tuned it on real footage."""
+    v = np.asarray(frame, np.float32)
+    if v.ndim != 3 or v.shape[2] != 3 or v.shape[0] < 8 or v.shape[1] < 8:
+        raise ValueError("picture_profile: frame is [H][W][3] with H, W >= 8, got %s" % (v.shape,))
+    threshold = int(threshold)
+    if not 0 <= threshold <= 254:
+        raise ValueError("picture_profile: threshold must be in 0..254, got %d" % threshold)
+    with np.errstate(invalid="ignore"):
+        c8 = np.where(v > 0, np.minimum(np.rint(v), np.float32(255)), np.float32(0)).astype(np.int64)
+    lit = ((29 * c8[..., 0] + 150 * c8[..., 1] + 77 * c8[..., 2] + 128) >> 8) > threshold
+    return np.concatenate([lit.sum(axis=1), lit.sum(axis=0)]).astype(np.uint32)
+
+
+def _centre_run(picture, gap):
+    """[lo, hi) of the run of picture lines around the centre line n // 2, grown outwards past gaps of fewer than `gap` lines; None if the
+    centre line is not picture"""
+    n = len(picture)
+    c = n // 2
+    if not picture[c]:
+        return None
+    lo = hi = c
+    miss = 0
+    for i in range(c - 1, -1, -1):
+        if picture[i]:
+            lo, miss = i, 0
+        else:
+            miss += 1
+            if miss >= gap:
+                break
+    miss = 0
+    for i in range(c + 1, n):
+        if picture[i]:
+            hi, miss = i, 0
+        else:
+            miss += 1
+            if miss >= gap:
+                break
+    return lo, hi + 1
+
+
+def detect_picture(profs, H, W, line=0.02, vote=0.1, dark=0.05, gap=4, min_bar=4, min_keep=0.5):
+    """The active picture area (y0, x0, h, w) of H x W frames from their line profiles profs [N][H + W] (picture_profile /
+    Stylization.picture_profiles / scan_frames): the window inside letterbox and pillarbox bars, or the whole frame (0, 0, H, W).
+      1  A frame votes iff sum(row_cnt) >= dark * H * W: dark frames and fades say nothing about bars.  No voters: the whole frame.
+      2  Row y is picture iff row_cnt[y] > line * W in at least max(1, ceil(vote * voters)) voting frames; column x likewise with line * H.
+      3  Per axis the run of picture lines that contains the centre line n // 2 (not picture: the whole frame), grown outwards in each
+         direction past gaps of fewer than `gap` non-picture lines and stopped at the first gap of `gap` lines: subtitles and logos inside
+         a bar are separated from the picture by dark lines, stay in the bar and are passed through from the source.
+      4  A bar thinner than min_bar lines is dropped: that side goes to the frame's edge.
+      5  The low edge is rounded up to even, the high edge down to even unless it is the frame's edge (the window rule of the entries).
+      6  A window that keeps less than min_keep of either axis (or fewer than 8 lines, the entries' minimum) gives the whole frame.
+    The six defaults and the profile's threshold of 10 are design parameters that nobody has tuned on real footage; 10 is ffmpeg
+    cropdetect's default of 24 on limited-range codes, moved to the full-range values the first kernel produces."""
+    H, W = int(H), int(W)
+    p = np.asarray(profs)
+    if p.ndim == 1:
+        p = p[None]
+    if p.ndim != 2 or p.shape[1] != H + W:
+        raise ValueError("detect_picture: profs is [N][H + W] = [N][%d], got %s" % (H + W, p.shape,))
+    whole = (0, 0, H, W)
+    p = p.astype(np.int64)
+    rows, cols = p[:, :H], p[:, H:]
+    voting = rows.sum(axis=1) >= dark * H * W
+    voters = int(voting.sum())
+    if voters == 0:
+        return whole
+    need = max(1, int(np.ceil(vote * voters)))
+    window = []
+    for cnt, n, across in ((rows[voting], H, W), (cols[voting], W, H)):
+        run = _centre_run((cnt > line * across).sum(axis=0) >= need, int(gap))
+        if run is None:
+            return whole
+        lo, hi = run
+        if lo < min_bar:
+            lo = 0
+        if n - hi < min_bar:
+            hi = n
+        lo += lo & 1
+        if hi != n:
+            hi -= hi & 1
+        if hi - lo < min_keep * n or hi - lo < 8:
+            return whole
+        window.append((lo, hi - lo))
+    (y0, h), (x0, w) = window
+    return (y0, x0, h, w)
+
+
+def check_picture(picture, H, W):
+    """(y0, x0, h, w) as ints; ValueError naming the field unless it is a window of an H x W frame by the rule of rrv_picture_check: y0, x0
+    even and >= 0; h, w >= 8; y0 + h <= H, x0 + w <= W; h even unless y0 + h == H; w even unless x0 + w == W"""
+    try:
+        y0, x0, h, w = (int(v) for v in picture)
+    except (TypeError, ValueError):
+        raise ValueError("picture is (y0, x0, h, w), got %r" % (picture,)) from None
+    for name, o, n, full in (("y0", y0, h, H), ("x0", x0, w, W)):
+        size = "h" if name == "y0" else "w"
+        if o < 0 or o & 1:
+            raise ValueError("picture: %s must be even and at least 0, got %d" % (name, o))
+        if n < 8:
+            raise ValueError("picture: %s must be at least 8, got %d" % (size, n))
+        if o + n > full:
+            raise ValueError("picture: %s reaches beyond the frame (%s + %s = %d > %d)" % (size, name, size, o + n, full))
+        if n & 1 and o + n != full:
+            raise ValueError("picture: %s must be even unless the window reaches the frame's edge, got %d" % (size, n))
+    return y0, x0, h, w
+
+
+def format_picture(picture):
+    """(y0, x0, h, w) -> "WxH+X+Y", the geometry text of ffmpeg's crop filter and of --picture"""
+    y0, x0, h, w = (int(v) for v in picture)
+    return "%dx%d+%d+%d" % (w, h, x0, y0)
+
+
+def parse_picture(text):
+    """"WxH+X+Y" -> (y0, x0, h, w); ValueError in words for anything else (the window rule is check_picture's, against a frame size)"""
+    import re
+    m = re.fullmatch(r"\s*(\d+)x(\d+)\+(\d+)\+(\d+)\s*", str(text))
+    if not m:
+        raise ValueError("picture: %r is not WxH+X+Y (for instance 1920x804+0+138)" % (text,))
+    w, h, x0, y0 = (int(g) for g in m.groups())
+    return y0, x0, h, w
+
+
 def shard_range(frame_num, rank, world):
     """Contiguous block of frames owned by `rank`."""
     lo = frame_num * rank // world
